@@ -8,6 +8,12 @@ Contract (driver):  python bench.py --gpus N --steps K --warmup W
   A "step" = one full training step (msteps=32 unrolled solver+CNN forward, loss, reverse sweep, gradient
   all-reduce, TF-Adam) on a synthetic batch of 6 simulations per GPU (BASELINE.json configs[2]);
   value = sim-steps/s of the whole job = N*B*msteps*K / time.
+  A plain run sets up, warms up, times the K steps and prints the headline line (metric, value, unit,
+  ms_per_step, dtype, ...).  --full adds everything else the line used to carry: per-step distribution and
+  clock, device-state probes, per-kernel rooflines, the strict-fp32 / bf16x6 / recipe / roll-out / Burgers /
+  karman-3d legs, the data-parallel bookkeeping and the CPU baseline.
+  --dump-outputs DIR writes what the last timed step computed (loss, per-step losses, final state,
+  gradient, updated weights) as DIR/<name>.npy; the inputs are seeded, so two builds can be compared.
 """
 import argparse
 import json
@@ -44,10 +50,10 @@ def parse():
                         "within ~10 steps: see workload_deviations in the JSON line)")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--no-extras", action="store_true", help="skip the strict-fp32 leg, the 64x32 recipe, the roll-out and the full-chip solver launch")
-    p.add_argument("--all-legs", action="store_true", help="N > 1: rank 0 also runs the single-GPU side legs (strict fp32, bf16x6, recipe, roll-out, karman-3d) "
+    p.add_argument("--all-legs", action="store_true", help="N > 1 with --full: rank 0 also runs the single-GPU side legs (strict fp32, bf16x6, recipe, roll-out, karman-3d) "
                    "while the other ranks wait; by default an N > 1 run spends its lease on the data-parallel measurement only")
     p.add_argument("--no-graph", action="store_true", help="launch the ~1000 kernels of a step eagerly instead of replaying the hipGraph")
-    p.add_argument("--k3d-dp", action="store_true", help="N > 1: also time the karman-3d SOL-16 step data parallel (one simulation per rank, BASELINE "
+    p.add_argument("--k3d-dp", action="store_true", help="N > 1 with --full: also time the karman-3d SOL-16 step data parallel (one simulation per rank, BASELINE "
                                                          "configs[4]); off by default: a second collective path must not be able to hang the contract line")
     p.add_argument("--precision", default="split", choices=["split", "bf16x6", "fp32"], help="conv arithmetic of the timed steps")
     p.add_argument("--cpu-msteps", type=int, default=2, help="msteps of the bounded CPU-baseline sample")
@@ -59,7 +65,15 @@ def parse():
     p.add_argument("--comm", default="torch", choices=["torch", "lib"],
                    help="N > 1: the gradient all-reduce through torch.distributed.all_reduce (RCCL via PyTorch) or through the library's own "
                         "RCCL communicator (sol_allreduce_grads, csrc/comm.hip; needs one device per rank)")
-    return p.parse_args()
+    p.add_argument("--full", action="store_true",
+                   help="also run every measurement beyond the headline (side legs, probes, rooflines, CPU baseline); the --no-* options "
+                        "above trim a --full run")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the outputs of the last timed step (loss, loss_steps, final state, gradient, weights) as DIR/<name>.npy")
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be >= 1")
+    return args
 
 
 def self_launch(args):
@@ -72,6 +86,28 @@ def self_launch(args):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus),
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
     raise SystemExit(subprocess.call(cmd, env=env))
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(wl, loss, path):
+    """The arrays a caller of the timed step receives after its last call: the loss, the per-step losses, the final state
+    (density, vy, vx), the gradient and the weights Adam left.  float32.  Beyond DUMP_LIMIT_BYTES in all, every array is
+    replaced by a fixed sample of its flattened elements (sorted indices drawn by numpy's default_rng(0))."""
+    import numpy as np
+    tr = wl.trainer
+    d, vy, vx = tr.final
+    outs = {"loss": np.array(loss, dtype=np.float32), "loss_steps": tr.loss_steps, "final_density": d, "final_vy": vy, "final_vx": vx,
+            "grads": tr.grads, "params": wl.net.params}
+    outs = {k: (v if isinstance(v, np.ndarray) else v.detach().float().cpu().numpy()) for k, v in outs.items()}
+    total = sum(v.nbytes for v in outs.values())
+    os.makedirs(path, exist_ok=True)
+    for name, a in outs.items():
+        if total > DUMP_LIMIT_BYTES and a.size > 1:
+            k = max(1, a.size * DUMP_LIMIT_BYTES // total)
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, k, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def cpu_baseline(args, Y, X, B):
@@ -646,9 +682,13 @@ def main():
 
     for _ in range(max(0, args.prewarm)):
         wl.step(args.lr)
-    state_before = device_state(sol_amd, dev) if (rank == 0 and not args.no_device_state) else None
-    sec, loss, trace, per_step_ms = timed_steps(wl, args.lr, args.steps, args.warmup, barrier, per_step=True)
-    state_after = device_state(sol_amd, dev) if (rank == 0 and not args.no_device_state) else None
+    probe = rank == 0 and args.full and not args.no_device_state
+    state_before = device_state(sol_amd, dev) if probe else None
+    sec, loss, trace, *per_step_ms = timed_steps(wl, args.lr, args.steps, args.warmup, barrier, per_step=args.full)
+    per_step_ms = per_step_ms[0] if per_step_ms else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(wl, loss, args.dump_outputs)
+    state_after = device_state(sol_amd, dev) if probe else None
     tsec = torch.tensor([sec], dtype=torch.float64, device=dev)
     rank_ms = [sec / args.steps * 1e3]
     if world > 1:
@@ -672,7 +712,7 @@ def main():
 
     # ---- multi-GPU bookkeeping: all-reduce cost and replica consistency -------------------------
     dp = None
-    if world > 1:
+    if world > 1 and args.full:
         ev = lambda: torch.cuda.Event(enable_timing=True)
         a, b = ev(), ev()
         g = tr._flat.clone()                  # what a training step exchanges: [gradient | loss], ONE collective
@@ -706,10 +746,20 @@ def main():
                 print("bench.py: WARNING the replicas' weights diverged", file=sys.stderr, flush=True)
 
     k3d_dp = None
-    if args.k3d_dp and world > 1:
+    if args.k3d_dp and world > 1 and args.full:
         k3d_dp = karman3d_dp_leg(sol_amd, dev, world, barrier)
     out = None
     if rank == 0:
+        out = {"metric": "sim-steps/s, SOL-32 training (karman-2d 128x64, fwd+bwd+Adam)",
+               "value": value, "unit": "sim-steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+               "ms_per_step": ms_per_step, "valid": bool(valid), "rank_skew": rank_skew, "pre_warmup_steps": max(0, args.prewarm),
+               "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+               "dtype": {"split": "f32 (fp16x3 split MFMA in 32-ch convs)", "bf16x6": "f32 (bf16x6 split MFMA in 32-ch convs)", "fp32": "f32"}[args.precision],
+               "data": "synthetic",
+               "config": {"workload": "karman-2d %dx%d SOL-%d, batch %d Re values per GPU (BASELINE configs[2])" % (Y, X, ms, B),
+                          "global_batch": world * B, "msteps": ms, "parallelism": "dp%d" % world, "lr": args.lr},
+               "loss": loss, "loss_warmup": trace}
+    if rank == 0 and args.full:
         N = Y * X
         Nf = (Y + 1) * X + Y * (X + 1)
         ev = lambda: torch.cuda.Event(enable_timing=True)
@@ -788,10 +838,7 @@ def main():
         bname, bst = pick("k_karman_bwd_bww", "k_karman_bwd")
         kern_tab = {k: {"calls": v["calls"], "avg_us": round(v["avg_us"], 2), "share": round(v["total_us"] / tot_prof, 4)}
                     for k, v in sorted(prof.items(), key=lambda kv: -kv[1]["total_us"])}
-        out = {
-            "metric": "sim-steps/s, SOL-32 training (karman-2d 128x64, fwd+bwd+Adam)",
-            "value": value, "unit": "sim-steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": ms_per_step,
+        out.update({
             # the distribution of the K timed steps (HIP events around every step, no synchronisation added) and the clock the box held
             "ms_per_step_median": _quantile(per_step_ms, 0.5), "ms_per_step_p10": _quantile(per_step_ms, 0.1), "ms_per_step_p90": _quantile(per_step_ms, 0.9),
             # the two reference-width companions of the headline arithmetic FIRST (filled in below): the same step with true 24-bit operand
@@ -805,14 +852,10 @@ def main():
             # SOL-32), the no-grad roll-out at B = 1 and at the bench batch, one karman-3d SOL-16 step
             "recipe_64x32_b3_ms_per_step": None, "rollout_b1_us_per_step": None, "rollout_b6_us_per_step": None, "karman3d_sol16_ms_per_step": None,
             "burgers_non_ms_per_step": None, "burgers_sol04_ms_per_step": None,
-            "valid": bool(valid), "rank_skew": rank_skew, "pre_warmup_steps": max(0, args.prewarm),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "scaling_status": ("this line is the N = %d point of a weak-scaling series (6 simulations per GPU); the driver computes the curve from its own "
                                "N = 1, 2, 4, 8 runs.  No N > 1 run on separate GPUs had executed when this file was committed (no multi-GPU node in "
                                "rounds 1-6): the 1 -> 8 curve is UNMEASURED, nothing is extrapolated here; tools/scale.sh runs the four points + the "
                                "DESIGN.md section 6 checklist on a node that has them" % world),
-            "dtype": {"split": "f32 (fp16x3 split MFMA in 32-ch convs)", "bf16x6": "f32 (bf16x6 split MFMA in 32-ch convs)", "fp32": "f32"}[args.precision],
-            "data": "synthetic",
             "dtype_note": "fp32 tensors and fp32 accumulation everywhere; with precision=split the 32-channel convolutions evaluate each fp32 "
                           "product as three exact fp16 MFMA products of power-of-two scaled 22-bit operand splits (single convolution: error vs float64 <= the "
                           "fp32-MFMA kernel's, tests/test_gpu_parity.py::test_split_conv_relative_l2_not_worse_than_fp32_mfma); strict_fp32 = same step on "
@@ -821,8 +864,6 @@ def main():
                           "the network), not the arithmetic: test_sol32_split_trainer_equals_strict_fp32_on_weights_representable_in_two_fp16_planes"
                           % precision_note(),
             "precision_at_c3": load_precision(),
-            "config": {"workload": "karman-2d %dx%d SOL-%d, batch %d Re values per GPU (BASELINE configs[2])" % (Y, X, ms, B),
-                       "global_batch": world * B, "msteps": ms, "parallelism": "dp%d" % world, "lr": args.lr},
             "workload_deviations_from_survey_8d": [
                 "ground truth = plain solver roll-out of the start state perturbed by 0.05 x seeded noise (seed 4321+rank), not independent "
                 "seed-4321 noise frames: unreachable random targets make Adam blow the 32-step unroll up",
@@ -833,7 +874,6 @@ def main():
                 "value / ms_per_step = wall clock over the K timed steps / K (barrier + synchronize on both sides); the median and the p10 / p90 of "
                 "per-step HIP events are printed beside it (ms_per_step_median, step_time_distribution_ms)",
             ],
-            "loss": loss, "loss_warmup": trace,
             "step_time_distribution_ms": step_distribution(per_step_ms),
             # the shader clock the device HELD during the timed steps (s_memtime / s_memrealtime stamps in front of every step): boxes of this pool
             # run the same build at 11.8 .. 12.8 ms per step with identical idle / probe clocks; this is the number that moves with them
@@ -857,7 +897,7 @@ def main():
                                      "conv_fp32_equiv_TFLOPs_of_step": 3.0 * 520000.0 * N * B * ms / (ms_per_step * 1e-3) / 1e12},
             "data_parallel": dp,
             "cpu_affinity": {k: v for k, v in (sol_amd.dist.AFFINITY or {}).items() if k != "inherited"} or None,
-        }
+        })
         if out["roofline"] is roof_conv and roof_solver:     # the north star's second roofline, inside the object the driver's `parsed` keeps
             out["roofline"]["solver_step"] = {"kernel": sname, "bound": "hbm", "frac": roof_solver["frac"], "achieved_GBps": roof_solver["achieved"],
                                               "launch_us": roof_solver["launch_us"], "share_of_step_kernel_time": roof_solver["share_of_step_kernel_time"],
@@ -973,6 +1013,7 @@ def main():
             out["cpu_baseline"] = cpu_baseline(args, Y, X, B)
         else:
             out["cpu_baseline"] = None
+    if rank == 0:
         print(json.dumps(out), flush=True)
     if world > 1:
         torch.distributed.barrier()

@@ -281,3 +281,29 @@ def test_dcopy_validates_its_operands_before_touching_the_library():
         _lib.dcopy_(torch.zeros(6), torch.zeros(5))      # sizes
     with pytest.raises(_lib.SolError):
         _lib.dcopy_(torch.zeros(4, dtype=torch.float64), torch.zeros(4, dtype=torch.float64))
+
+
+def test_bench_dump_outputs_writes_the_last_steps_arrays_within_the_size_cap(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: one float32 .npy per output of the timed step; above the cap, the same seeded sample every run."""
+    import types
+    import bench
+    g = torch.Generator().manual_seed(0)
+    r = lambda *s: torch.rand(*s, generator=g, dtype=torch.float32)
+    B, Y, X, ms, n = 2, 16, 8, 3, 500
+    tr = types.SimpleNamespace(final=[r(B, Y, X), r(B, Y + 1, X), r(B, Y, X + 1)], loss_steps=r(ms), grads=r(n))
+    wl = types.SimpleNamespace(trainer=tr, net=types.SimpleNamespace(params=r(n).requires_grad_(True)))
+    bench.dump_outputs(wl, 1.25, str(tmp_path / "full"))
+    want = {"loss": torch.tensor(1.25, dtype=torch.float32), "loss_steps": tr.loss_steps, "final_density": tr.final[0], "final_vy": tr.final[1],
+            "final_vx": tr.final[2], "grads": tr.grads, "params": wl.net.params.detach()}
+    assert sorted(p.name for p in (tmp_path / "full").iterdir()) == sorted(k + ".npy" for k in want)
+    for k, v in want.items():
+        a = np.load(tmp_path / "full" / (k + ".npy"))
+        assert a.dtype == np.float32 and np.array_equal(a, v.numpy())
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 2000)
+    for run in ("a", "b"):
+        bench.dump_outputs(wl, 1.25, str(tmp_path / run))
+    total = sum(p.stat().st_size - 128 for p in (tmp_path / "a").iterdir())          # minus the .npy header
+    assert total <= 2000
+    for k, v in want.items():
+        a, b = np.load(tmp_path / "a" / (k + ".npy")), np.load(tmp_path / "b" / (k + ".npy"))
+        assert a.dtype == np.float32 and np.array_equal(a, b) and np.isin(a, v.numpy().reshape(-1)).all()

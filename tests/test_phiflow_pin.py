@@ -182,7 +182,7 @@ def test_train_comparator_on_the_committed_oracle_fixture():
     assert "default" in ok and "Q5 grad_pad=dirichlet0" not in ok and "Q2+Q5" not in ok, report(res)
 
 
-def test_generator_script_fails_clearly_without_the_reference_stack_and_finds_the_reference_definitions():
+def test_generator_script_fails_clearly_without_the_reference_stack_and_finds_the_reference_definitions(tmp_path):
     script = os.path.join(GOLDEN, "make_phiflow_fixtures.py")
     try:
         import phi  # noqa: F401
@@ -192,21 +192,31 @@ def test_generator_script_fails_clearly_without_the_reference_stack_and_finds_th
     if not have_phi:
         r = subprocess.run([sys.executable, script], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
         assert r.returncode != 0 and "phiflow==1.5.1" in r.stdout and "tensorflow 1.15" in r.stdout
-    ref = "/root/reference"
-    if not os.path.exists(os.path.join(ref, "karman-2d", "karman_train.py")):
-        pytest.skip("reference checkout absent (GPU box): the definition lookup is checked in the build container")
     sys.path.insert(0, GOLDEN)
     import make_phiflow_fixtures as mk
-    # the named definitions exist in the reference and are plain def / class statements the extractor can lift; executing them needs
-    # phi, so here only the lookup is exercised (with stand-ins for the base classes)
+    # the extractor lifts the named top-level def / class statements out of a script laid out like the reference's (other statements,
+    # nested definitions, decorated classes on phi base classes) and refuses a missing name; executing the real definitions needs phi,
+    # so the scripts here are stand-ins written by this test, and the namespace holds stand-ins for the base classes
     class _Base:                                            # noqa: E306
         def __init__(self, *a, **k):
             pass
     ns = {"IncompressibleFlow": _Base, "Gravity": lambda: None, "Burgers": _Base, "BurgersVelocity": _Base, "DomainState": type("D", (), {"domain": None}),
           "struct": type("S", (), {"definition": staticmethod(lambda: (lambda c: c)), "variable": staticmethod(lambda **k: (lambda f: f))})}
-    mk.reference_defs(os.path.join(ref, "karman-2d", "karman_train.py"), ["to_feature", "to_staggered", "model_mars_moon", "KarmanFlow"], ns)
-    mk.reference_defs(os.path.join(ref, "burgers", "burgers_train.py"), ["BurgersVelocitySMAC", "BurgersTest"], ns)
+    karman = tmp_path / "karman_train.py"
+    karman.write_text("import sys\nRES = 32\n\n\ndef to_feature(v, re):\n    def inner():\n        return 0\n    return v\n\n\n"
+                      "def to_staggered(t, box):\n    return t\n\n\ndef model_mars_moon(shape):\n    return shape\n\n\n"
+                      "class KarmanFlow(IncompressibleFlow):\n    def __init__(self):\n        IncompressibleFlow.__init__(self)\n        self.g = Gravity()\n\n\n"
+                      "if __name__ == '__main__':\n    sys.exit(1)\n")
+    burgers = tmp_path / "burgers_train.py"
+    burgers.write_text("@struct.definition()\nclass BurgersVelocitySMAC(BurgersVelocity):\n    @struct.variable(default=0)\n    def velocity(self, v):\n"
+                       "        return v\n\n\nclass BurgersTest(Burgers):\n    pass\n\n\nraise SystemExit('top-level code must not run')\n")
+    mk.reference_defs(str(karman), ["to_feature", "to_staggered", "model_mars_moon", "KarmanFlow"], ns)
+    mk.reference_defs(str(burgers), ["BurgersVelocitySMAC", "BurgersTest"], ns)
     assert all(k in ns for k in ("KarmanFlow", "to_feature", "to_staggered", "model_mars_moon", "BurgersTest", "BurgersVelocitySMAC"))
+    assert "inner" not in ns and "RES" not in ns and issubclass(ns["KarmanFlow"], _Base) and issubclass(ns["BurgersVelocitySMAC"], _Base)
+    assert ns["to_staggered"](5, None) == 5
+    with pytest.raises(SystemExit, match="does not define"):
+        mk.reference_defs(str(karman), ["KarmanFlow", "inner"], ns)
     assert mk.velocity_bc(64, 32, 1).sum() == 190 and mk.velocity_bc(128, 64, 1).sum() == 382         # the BC-cell counts of the known-answer tests
 
 

@@ -10,15 +10,15 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$R/gpurun_out/r6prof
 rm -rf "$OUT"; mkdir -p "$OUT"
 cd /tmp; export TMPDIR=/tmp
-ARGS="--steps 20 --warmup 5"
-[ "${1:-}" = "--2d-only" ] && ARGS="--steps 10 --warmup 3 --no-cpu-baseline"
+ARGS="--full --steps 20 --warmup 5"
+[ "${1:-}" = "--2d-only" ] && ARGS="--full --steps 10 --warmup 3 --no-cpu-baseline"
 if [ "${1:-}" = "--pmc-only" ]; then      # the counter passes of the 2-D step alone (after a source change: the traffic file is tied to the build)
   for C in FETCH_SIZE WRITE_SIZE; do
-    rocprofv3 --pmc $C --output-format csv -d $OUT/pmc_$C -o pmc -- python $R/bench.py --steps 3 --warmup 1 --prewarm 0 --no-extras --no-cpu-baseline --no-device-state > /dev/null 2>>$OUT/rocprof.err
+    rocprofv3 --pmc $C --output-format csv -d $OUT/pmc_$C -o pmc -- python $R/bench.py --full --steps 3 --warmup 1 --prewarm 0 --no-extras --no-cpu-baseline --no-device-state > /dev/null 2>>$OUT/rocprof.err
     python $R/tools/pmc_summary.py $OUT/pmc_$C "" --json $OUT/r06_pmc_traffic.json > $OUT/pmc_$C.txt
   done
   rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES SQ_WAVE_CYCLES SQ_WAIT_INST_LDS SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_INSTS_VALU_MFMA_MOPS_F16 \
-    --output-format csv -d $OUT/pmc_sq -o pmc -- python $R/bench.py --steps 3 --warmup 1 --prewarm 0 --no-extras --no-cpu-baseline --no-device-state > /dev/null 2>>$OUT/rocprof.err
+    --output-format csv -d $OUT/pmc_sq -o pmc -- python $R/bench.py --full --steps 3 --warmup 1 --prewarm 0 --no-extras --no-cpu-baseline --no-device-state > /dev/null 2>>$OUT/rocprof.err
   python $R/tools/pmc_summary.py $OUT/pmc_sq "k_" > $OUT/pmc_sq.txt
   rm -rf $OUT/pmc_FETCH_SIZE $OUT/pmc_WRITE_SIZE $OUT/pmc_sq; ls -la $OUT; exit 0
 fi
@@ -27,11 +27,11 @@ rocprofv3 --kernel-trace --stats -d $OUT/trace -o trace -- python $R/bench.py $A
 DB=$(find $OUT/trace -name "*.db" | head -1)
 if [ -n "$DB" ]; then python $R/tools/rocpd_stats.py "$DB" > $OUT/kernel_stats.txt; else ls -R $OUT/trace > $OUT/kernel_stats.txt; fi
 for C in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --pmc $C --output-format csv -d $OUT/pmc_$C -o pmc -- python $R/bench.py --steps 3 --warmup 1 --prewarm 0 --no-extras --no-cpu-baseline --no-device-state > /dev/null 2>>$OUT/rocprof.err
+  rocprofv3 --pmc $C --output-format csv -d $OUT/pmc_$C -o pmc -- python $R/bench.py --full --steps 3 --warmup 1 --prewarm 0 --no-extras --no-cpu-baseline --no-device-state > /dev/null 2>>$OUT/rocprof.err
   python $R/tools/pmc_summary.py $OUT/pmc_$C "" --json $OUT/r06_pmc_traffic.json > $OUT/pmc_$C.txt
 done
 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES SQ_WAVE_CYCLES SQ_WAIT_INST_LDS SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_INSTS_VALU_MFMA_MOPS_F16 \
-  --output-format csv -d $OUT/pmc_sq -o pmc -- python $R/bench.py --steps 3 --warmup 1 --prewarm 0 --no-extras --no-cpu-baseline --no-device-state > /dev/null 2>>$OUT/rocprof.err
+  --output-format csv -d $OUT/pmc_sq -o pmc -- python $R/bench.py --full --steps 3 --warmup 1 --prewarm 0 --no-extras --no-cpu-baseline --no-device-state > /dev/null 2>>$OUT/rocprof.err
 python $R/tools/pmc_summary.py $OUT/pmc_sq "k_" > $OUT/pmc_sq.txt
 if [ "${1:-}" = "--2d-only" ]; then rm -rf $OUT/trace $OUT/pmc_FETCH_SIZE $OUT/pmc_WRITE_SIZE $OUT/pmc_sq; ls -la $OUT; exit 0; fi     # (the karman-3d passes take ten minutes of box time)
 # karman-3d: kernel trace + HBM counters of the forward roll-out and one training step

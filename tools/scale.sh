@@ -1,26 +1,28 @@
 #!/bin/bash
 # The 1 -> 8 GPU weak-scaling series of BASELINE.json's metric (karman-2d 128x64 SOL-32, 6 simulations per GPU) on ONE node, plus the
 # readiness checklist of DESIGN.md section 6.  Needs a node with 8 MI355X; nothing here has run on such a node (rounds 1-6 had none).
-#   tools/scale.sh [steps] [warmup]          -> gpurun_out/scale_N{1,2,4,8}.json + a table on stdout
+#   tools/scale.sh [steps] [warmup]          -> $SCALE_OUT/scale_N{1,2,4,8}.json (default scale_out/) + a table on stdout
 #   tools/scale.sh --dry-run                 -> the same launcher, parser and table on ONE GPU: N = 1 and N = 2 (two ranks time-sharing the
 #                                               device over gloo -- bench.py falls back to gloo only when there are more ranks than devices and
 #                                               REFUSES any non-nccl backend otherwise), 3 steps each.  Says nothing about xGMI; it exists so
 #                                               that the first real run on an 8-GPU lease does not fail on a typo.
-# Each point is the driver's own command (python -m torch.distributed.run ... bench.py --gpus N); N > 1 runs skip the single-GPU side legs.
+# Each point is the driver's own command (python -m torch.distributed.run ... bench.py --gpus N); N > 1 runs add --full for the
+# data-parallel bookkeeping the table reads and skip the single-GPU side legs.
 set -u
 cd "$(dirname "$0")/.."
 export HSA_ENABLE_IPC_MODE_LEGACY=0
 NS="1 2 4 8"
 if [ "${1:-}" = "--dry-run" ]; then NS="1 2"; shift; set -- 3 1; export SOL_SCALE_DRY=1; fi
 STEPS=${1:-20}; WARM=${2:-5}
-mkdir -p gpurun_out
+export SCALE_OUT=${SCALE_OUT:-scale_out}
+mkdir -p "$SCALE_OUT"
 for N in $NS; do
   PORT=$((29500 + N))
   if [ "$N" = 1 ]; then
-    python bench.py --gpus 1 --steps "$STEPS" --warmup "$WARM" --no-extras --no-cpu-baseline > gpurun_out/scale_N1.json 2> gpurun_out/scale_N1.err
+    python bench.py --gpus 1 --steps "$STEPS" --warmup "$WARM" --no-extras --no-cpu-baseline > "$SCALE_OUT/scale_N1.json" 2> "$SCALE_OUT/scale_N1.err"
   else
     python -m torch.distributed.run --nnodes=1 --nproc-per-node "$N" --master-addr 127.0.0.1 --master-port "$PORT" \
-      bench.py --gpus "$N" --steps "$STEPS" --warmup "$WARM" --no-cpu-baseline > "gpurun_out/scale_N$N.json" 2> "gpurun_out/scale_N$N.err"
+      bench.py --gpus "$N" --steps "$STEPS" --warmup "$WARM" --full --no-cpu-baseline > "$SCALE_OUT/scale_N$N.json" 2> "$SCALE_OUT/scale_N$N.err"
   fi
   echo "N=$N rc=$?" >&2
 done
@@ -30,7 +32,7 @@ rows = []
 import os
 for n in ((1, 2) if os.environ.get("SOL_SCALE_DRY") else (1, 2, 4, 8)):
     try:
-        rows.append(json.loads(open("gpurun_out/scale_N%d.json" % n).read().strip().splitlines()[-1]))
+        rows.append(json.loads(open(os.path.join(os.environ["SCALE_OUT"], "scale_N%d.json" % n)).read().strip().splitlines()[-1]))
     except Exception as e:      # noqa: BLE001
         print("N=%d: no line (%s)" % (n, e))
 if rows:
