@@ -428,6 +428,12 @@ typedef struct sol_karman3d_cfg {
     const float* direct;    /* DEVICE blob of the direct pressure solver for the scene's `active` mask
                                (three sine-transform matrices, 1/eigenvalues, capacitance matrix of the
                                obstacle cells; layout: precond3d.direct_solver_blob3d).  Required.       */
+    /* pressure solver (all zero = the direct solve; appended in ABI 216) */
+    int32_t pressure_solver;   /* 0: direct (capacitance blob), 1: preconditioned CG (blob with nS = 0)  */
+    int32_t cg_max_iter;       /* CG: launch budget in iterations (>= 1); the launch sequence is fixed    */
+    float cg_rtol, cg_atol;    /* CG: a simulation stops when |r|_2 <= max(cg_rtol |b|_2, cg_atol)        */
+    int32_t* cg_info;          /* CG: DEVICE [B][2] or NULL: iterations used, converged (0/1), written by
+                                  every solve (the adjoint's solve overwrites the forward's)              */
 } sol_karman3d_cfg;
 int32_t sol_abi_size_karman3d(void);      /* sizeof(sol_karman3d_cfg) of the library (checked by the ctypes mirror) */
 
@@ -448,7 +454,8 @@ int sol_karman3d_step_fwd(const sol_karman3d_cfg* cfg, void* stream,
                           void* workspace, size_t workspace_bytes);
 /* Adjoint of the step w.r.t. its input velocity (the density is a passive tracer: buoyancy_factor = 0, karman_train.py:363).
  * saved_v*: the post-diffusion + BC velocity the forward call stored (saved_vy/vx/vz, all three or NULL there).  The
- * pressure adjoint is a second direct solve with the same symmetric matrix (PhiFlow's custom gradient of the CG solve).
+ * pressure adjoint is a second solve with the same symmetric matrix and the same solver as the forward step (PhiFlow's
+ * custom gradient of the CG solve).
  * The advection adjoint scatters in 64-bit fixed point (integer global atomics, power-of-two scale from max|gradient|):
  * the result is reproducible BIT FOR BIT from run to run.
  * workspace: sol_karman3d_step_bwd_workspace_bytes(cfg) bytes, 16-byte aligned. */
@@ -459,6 +466,10 @@ int sol_karman3d_step_bwd(const sol_karman3d_cfg* cfg, void* stream,
                           const float* g_vy_out, const float* g_vx_out, const float* g_vz_out,
                           float* g_vy_in, float* g_vx_in, float* g_vz_in,
                           const int32_t* direct_header_host, void* workspace, size_t workspace_bytes);
+/* The step's pressure solve alone: M p = rhs with M = -A for the scene's `active` mask (the solver cfg->pressure_solver selects;
+ * the CG solve reports to cfg->cg_info).  rhs, p [B,Y,X,Z] (rhs is read only); workspace: sol_karman3d_step_workspace_bytes(cfg). */
+int sol_karman3d_pressure_solve(const sol_karman3d_cfg* cfg, void* stream, const float* active, const float* rhs, float* p,
+                                const int32_t* direct_header_host, void* workspace, size_t workspace_bytes);
 /* velocity += s_c * out[..., c] for the three components (to_staggered + add, karman_train.py:88-90, 424-426):
  * out [B,Y,X,Z,cout], cout >= 3; the last face of each component's own axis receives no correction. */
 int sol_karman3d_correct(void* stream, const float* out, int32_t cout, float s0, float s1, float s2,

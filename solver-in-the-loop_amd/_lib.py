@@ -40,7 +40,10 @@ class Karman3DCfg(C.Structure):
     _fields_ = [("B", C.c_int32), ("Y", C.c_int32), ("X", C.c_int32), ("Z", C.c_int32),
                 ("dx", C.c_float), ("dt", C.c_float), ("res", C.c_float),
                 ("grad_pad", C.c_int32), ("inflow_before", C.c_int32),
-                ("direct_n", C.c_int32), ("direct", C.c_void_p)]
+                ("direct_n", C.c_int32), ("direct", C.c_void_p),
+                # appended in ABI 216 (all zero = the direct solve): pressure solver, CG budget / tolerances, DEVICE [B][2] report or NULL
+                ("pressure_solver", C.c_int32), ("cg_max_iter", C.c_int32), ("cg_rtol", C.c_float), ("cg_atol", C.c_float),
+                ("cg_info", C.c_void_p)]
 
 
 class TrainCfg(C.Structure):
@@ -107,6 +110,7 @@ _SIGS = {
     "sol_karman3d_step_fwd": (C.c_int, [C.POINTER(Karman3DCfg), _P] + [_P] * 9 + [C.c_int64] + [_P] * 8 + [C.POINTER(C.c_float), _P, _P, C.c_size_t]),
     "sol_karman3d_step_bwd_workspace_bytes": (C.c_size_t, [C.POINTER(Karman3DCfg)]),
     "sol_karman3d_step_bwd": (C.c_int, [C.POINTER(Karman3DCfg), _P] + [_P] * 6 + [C.c_int64] + [_P] * 6 + [_P, _P, C.c_size_t]),
+    "sol_karman3d_pressure_solve": (C.c_int, [C.POINTER(Karman3DCfg), _P, _P, _P, _P, _P, _P, C.c_size_t]),
     "sol_karman3d_correct": (C.c_int, [_P, _P, C.c_int32] + [C.c_float] * 3 + [_P] * 3 + [C.c_int32] * 4),
     "sol_karman3d_correct_bwd": (C.c_int, [_P] * 7 + [C.c_float] * 3 + [_P] + [C.c_int32] * 4),
     "sol_karman3d_feature_bwd": (C.c_int, [_P, _P] + [C.c_float] * 3 + [_P] * 3 + [C.c_int32] * 4),
@@ -143,7 +147,7 @@ def lib_path():
     return _build.LIB
 
 
-ABI_VERSION = 215     # sol_version() of the library these bindings were written against
+ABI_VERSION = 216     # sol_version() of the library these bindings were written against
 
 # Debugging overrides: environment variable -> (option, value).  Read ONCE here, in Python, when the library is loaded;
 # the library itself never reads the environment (options are set through sol_set_option, include/sol_hip.h).

@@ -36,6 +36,14 @@ int sol_bww_batched_reduce(void* stream, const float* partial, float* dw_hwio, f
 int sol_gemm_f32(hipStream_t s, int batch, const float* A, int lda, long sA, const float* Bm, int ldb, long sB, float* C, int ldc, long sC,
                  int M, int N, int K, int accumulate);
 
+// karman-3d pressure solvers (karman3d.hip / karman3d_pcg.hip): dst = G src with G = the empty-box solve on the blob of cfg->direct
+// (*res = t1 or t2, whichever holds dst; skip = per-simulation done words [B] or NULL); the preconditioned CG solve M x = b (b is
+// overwritten with the residual; *x_out = the solution; active = the [Y,X,Z] mask) in the workspace of k3_pcg_workspace_bytes
+int k3_apply_G(hipStream_t s, const sol_karman3d_cfg* c, const float* src, float* t1, float* t2, float** res_out, const int* skip);
+size_t k3_pcg_workspace_bytes(const sol_karman3d_cfg* c);
+int k3_pcg_check(const sol_karman3d_cfg* c, const int32_t* hdr);
+int k3_pcg_solve(hipStream_t s, const sol_karman3d_cfg* c, const float* active, float* b, float* t1, float* t2, void* ws, float** x_out);
+
 // forward / backward-data convolution arguments (conv5x5.hip, conv5x5_sb.hip)
 struct ConvArgs {
     const float *x, *wp, *bias, *res, *act;

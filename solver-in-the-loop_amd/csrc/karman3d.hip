@@ -357,8 +357,18 @@ __global__ void __launch_bounds__(256) k3_project(K3Args a) {
     }
 }
 
+// skip / nskip: the preconditioned CG solve (karman3d_pcg.hip) hands in its per-simulation done words -- a transform launched after
+// every simulation has converged returns at once (the launch sequence is fixed so that it captures); the direct solve passes NULL
+__device__ __forceinline__ bool k3_all_done(const int* skip, int nskip) {
+    if (!skip) return false;
+    for (int q = 0; q < nskip; ++q)
+        if (!skip[q]) return false;
+    return true;
+}
+
 // T[e] *= il[e]  (1 / eigenvalue of the empty-box Laplacian, natural [m][c][e] order)
-__global__ void __launch_bounds__(256) k3_scale(float* __restrict__ T, const float* __restrict__ il, int N) {
+__global__ void __launch_bounds__(256) k3_scale(float* __restrict__ T, const float* __restrict__ il, int N, const int* __restrict__ skip, int nskip) {
+    if (k3_all_done(skip, nskip)) return;
     const int b = blockIdx.y;
     for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < N; e += gridDim.x * blockDim.x) T[(size_t)b * N + e] *= il[e];
 }
@@ -405,7 +415,8 @@ __global__ void __launch_bounds__(256) k3_cap_apply(const float* __restrict__ pa
 // of a plane cost ONE read and ONE write of the plane instead of two each).  Q symmetric, so the same kernel serves the
 // forward and the inverse direction.
 __global__ void __launch_bounds__(256) k3_tzx(const float* __restrict__ in, float* __restrict__ out, const float* __restrict__ Qx,
-                                               const float* __restrict__ Qz, int X, int Z) {
+                                               const float* __restrict__ Qz, int X, int Z, const int* __restrict__ skip, int nskip) {
+    if (k3_all_done(skip, nskip)) return;
     __shared__ float A[64][65], Q[64][65];
     const size_t plane = (size_t)blockIdx.x * X * Z;
     const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
@@ -448,7 +459,8 @@ __global__ void __launch_bounds__(256) k3_tzx(const float* __restrict__ in, floa
 // k3_ty: one workgroup = a slab of 32 columns (flattened (x, z) index) x all Y rows of one simulation:
 // out = Qy diag(il) Qy f  -- forward transform along y, division by the eigenvalues, inverse transform, one read / write.
 __global__ void __launch_bounds__(256) k3_ty(const float* __restrict__ in, float* __restrict__ out, const float* __restrict__ Qy,
-                                              const float* __restrict__ il, int Y, int XZ) {
+                                              const float* __restrict__ il, int Y, int XZ, const int* __restrict__ skip, int nskip) {
+    if (k3_all_done(skip, nskip)) return;
     extern __shared__ __align__(16) float lty[];          // Qy [Y][Y+4] + F [Y][36]
     const int QS = Y + 4;
     float* Q = lty;
@@ -508,7 +520,8 @@ typedef float f32x16_t __attribute__((ext_vector_type(16)));
 // one workgroup = a slab of 32 columns x all Y rows: out = Qy diag(il) Qy f (Y % 32 == 0, Y <= 128; wave w owns row tile w)
 template <int YK>                              // YK = Y / 2 K steps (64 at Y = 128)
 __global__ void __launch_bounds__(256) k3_ty_mfma(const float* __restrict__ in, float* __restrict__ out, const float* __restrict__ Qy,
-                                                   const float* __restrict__ il, int XZ) {
+                                                   const float* __restrict__ il, int XZ, const int* __restrict__ skip, int nskip) {
+    if (k3_all_done(skip, nskip)) return;
     constexpr int Y = 2 * YK;
     __shared__ __align__(16) float Fm[Y * 32], Tm[Y * 32];
     const int b = blockIdx.y, c0 = blockIdx.x * 32;
@@ -551,7 +564,8 @@ __global__ void __launch_bounds__(256) k3_ty_mfma(const float* __restrict__ in, 
 // one workgroup = one (x, z) plane: out = Qx (F Qz)  (X, Z in {32, 64}); wave = (row tile, column tile)
 template <int XK, int ZK>                      // K steps of the two products: X / 2, Z / 2
 __global__ void __launch_bounds__(256) k3_tzx_mfma(const float* __restrict__ in, float* __restrict__ out, const float* __restrict__ Qx,
-                                                    const float* __restrict__ Qz) {
+                                                    const float* __restrict__ Qz, const int* __restrict__ skip, int nskip) {
+    if (k3_all_done(skip, nskip)) return;
     constexpr int X = 2 * XK, Z = 2 * ZK, SA = 66, SB = 96;      // A-type / B-type LDS strides (words)
     __shared__ __align__(16) float Fa[X * SA], Tb[X * SB];
     const size_t plane = (size_t)blockIdx.x * X * Z;
@@ -653,27 +667,28 @@ __global__ void __launch_bounds__(256) k3_fill(float* __restrict__ y, const floa
 
 int grid_for(size_t n) { const size_t g = (n + 255) / 256; return (int)(g < 1 ? 1 : (g > 65535 ? 65535 : g)); }
 
-// ---- direct pressure solve: M x = R (M = -A), in place helpers shared by the forward step and its adjoint.  R is modified
-// (the capacitance correction is subtracted from it); *res = the buffer (T1 or T2) that holds x.
-int pressure_solve3d(hipStream_t s, const sol_karman3d_cfg* c, const int32_t* hdr, float* R, float* T1, float* T2, float** res_out) {
+}  // namespace
+
+// ---- the empty-box solve G = M_r^-1 (three sine transforms each way + the 1/eigenvalue scaling) on the blob's matrices: the direct
+// solve applies it twice around the capacitance correction, the preconditioned CG solve (karman3d_pcg.hip) once per iteration.
+// dst = G src (src preserved); *res_out = the buffer (t1 or t2) that holds dst.  skip: per-simulation done words [B] or NULL.
+int k3_apply_G(hipStream_t s, const sol_karman3d_cfg* c, const float* src, float* t1, float* t2, float** res_out, const int* skip) {
     const int B = c->B, Y = c->Y, X = c->X, Z = c->Z, N = Y * X * Z;
-    const int nS = hdr[4], SP = hdr[5];
     const float* Qy = c->direct + FD3_HEADER;
     const float* Qx = Qy + (size_t)Y * Y;
     const float* Qz = Qx + (size_t)X * X;
     const float* il = Qz + (size_t)Z * Z;
-    const float* KpT = il + (size_t)N;
-    const int* sidx = reinterpret_cast<const int*>(KpT + (size_t)SP * SP);
     // One sine transform of the whole batch along each axis = one batched GEMM:
     //   z: [(b,j,i)] x Z times Qz;   x: per (b, j): Qx times [X x Z];   y: per b: Qy times [Y x (X Z)]
+    // (the GEMMs do not read `skip`: a converged CG solve on a grid without the LDS-resident transforms still pays them)
     auto tz = [&](const float* in, float* out) { return sol_gemm_f32(s, 1, in, Z, 0, Qz, Z, 0, out, Z, 0, B * Y * X, Z, Z, 0); };
     auto tx = [&](const float* in, float* out) { return sol_gemm_f32(s, B * Y, Qx, X, 0, in, Z, (long)X * Z, out, Z, (long)X * Z, X, Z, X, 0); };
     auto ty = [&](const float* in, float* out) { return sol_gemm_f32(s, B, Qy, Y, 0, in, X * Z, (long)N, out, X * Z, (long)N, Y, X * Z, Y, 0); };
-    auto G = [&](float* src, float* t1, float* t2) -> int {     // t2 = G src  (src is preserved)
+    auto G = [&](const float* src, float* t1, float* t2) -> int {     // t2 = G src  (src is preserved)
         if (int e = tz(src, t1)) return e;
         if (int e = tx(t1, t2)) return e;
         if (int e = ty(t2, t1)) return e;
-        SOL_LAUNCH(k3_scale, dim3(grid_for(N), B), dim3(256), 0, s, t1, il, N);
+        SOL_LAUNCH(k3_scale, dim3(grid_for(N), B), dim3(256), 0, s, t1, il, N, skip, B);
         if (int e = ty(t1, t2)) return e;
         if (int e = tx(t2, t1)) return e;
         return tz(t1, t2);
@@ -684,39 +699,52 @@ int pressure_solve3d(hipStream_t s, const sol_karman3d_cfg* c, const int32_t* hd
     const size_t ty_lds = ((size_t)Y * (Y + 4) + (size_t)Y * 36) * sizeof(float);
     // the matrix-core kernels are instantiated for the shapes that occur: Y in {128, 64, 32}, X, Z in {64, 32}
     const bool mfma_tf = sol_opt().k3d_mfma_tf && fused_tf && (X == 64 || X == 32) && (Z == 64 || Z == 32) && (Y == 128 || Y == 64 || Y == 32);
-    auto Gf = [&](float* src, float* t1, float* t2) -> int {
+    auto Gf = [&](const float* src, float* t1, float* t2) -> int {
         static std::atomic<unsigned long long> optin{0};
         if (int e = sol_lds_optin(optin, {SOL_K(k3_ty)}, "k3_ty")) return e;
         if (mfma_tf) {
             auto tzx = [&](const float* in, float* out) {
-                if (X == 64 && Z == 64) SOL_LAUNCH((k3_tzx_mfma<32, 32>), dim3(B * Y), dim3(256), 0, s, in, out, Qx, Qz);
-                else if (X == 64) SOL_LAUNCH((k3_tzx_mfma<32, 16>), dim3(B * Y), dim3(256), 0, s, in, out, Qx, Qz);
-                else if (Z == 64) SOL_LAUNCH((k3_tzx_mfma<16, 32>), dim3(B * Y), dim3(256), 0, s, in, out, Qx, Qz);
-                else SOL_LAUNCH((k3_tzx_mfma<16, 16>), dim3(B * Y), dim3(256), 0, s, in, out, Qx, Qz);
+                if (X == 64 && Z == 64) SOL_LAUNCH((k3_tzx_mfma<32, 32>), dim3(B * Y), dim3(256), 0, s, in, out, Qx, Qz, skip, B);
+                else if (X == 64) SOL_LAUNCH((k3_tzx_mfma<32, 16>), dim3(B * Y), dim3(256), 0, s, in, out, Qx, Qz, skip, B);
+                else if (Z == 64) SOL_LAUNCH((k3_tzx_mfma<16, 32>), dim3(B * Y), dim3(256), 0, s, in, out, Qx, Qz, skip, B);
+                else SOL_LAUNCH((k3_tzx_mfma<16, 16>), dim3(B * Y), dim3(256), 0, s, in, out, Qx, Qz, skip, B);
             };
             tzx(src, t1);
-            if (Y == 128) SOL_LAUNCH(k3_ty_mfma<64>, dim3(X * Z / 32, B), dim3(256), 0, s, (const float*)t1, t2, Qy, il, X * Z);
-            else if (Y == 64) SOL_LAUNCH(k3_ty_mfma<32>, dim3(X * Z / 32, B), dim3(256), 0, s, (const float*)t1, t2, Qy, il, X * Z);
-            else SOL_LAUNCH(k3_ty_mfma<16>, dim3(X * Z / 32, B), dim3(256), 0, s, (const float*)t1, t2, Qy, il, X * Z);
+            if (Y == 128) SOL_LAUNCH(k3_ty_mfma<64>, dim3(X * Z / 32, B), dim3(256), 0, s, (const float*)t1, t2, Qy, il, X * Z, skip, B);
+            else if (Y == 64) SOL_LAUNCH(k3_ty_mfma<32>, dim3(X * Z / 32, B), dim3(256), 0, s, (const float*)t1, t2, Qy, il, X * Z, skip, B);
+            else SOL_LAUNCH(k3_ty_mfma<16>, dim3(X * Z / 32, B), dim3(256), 0, s, (const float*)t1, t2, Qy, il, X * Z, skip, B);
             tzx(t2, t1);
         } else {
-            SOL_LAUNCH(k3_tzx, dim3(B * Y), dim3(256), 0, s, src, t1, Qx, Qz, X, Z);
-            SOL_LAUNCH(k3_ty, dim3(X * Z / 32, B), dim3(256), ty_lds, s, t1, t2, Qy, il, Y, X * Z);
-            SOL_LAUNCH(k3_tzx, dim3(B * Y), dim3(256), 0, s, t2, t1, Qx, Qz, X, Z);
+            SOL_LAUNCH(k3_tzx, dim3(B * Y), dim3(256), 0, s, src, t1, Qx, Qz, X, Z, skip, B);
+            SOL_LAUNCH(k3_ty, dim3(X * Z / 32, B), dim3(256), ty_lds, s, t1, t2, Qy, il, Y, X * Z, skip, B);
+            SOL_LAUNCH(k3_tzx, dim3(B * Y), dim3(256), 0, s, t2, t1, Qx, Qz, X, Z, skip, B);
         }
         SOL_LAUNCH_CHECK();
         return SOL_OK;
     };
     // result in `res`: T2 for the GEMM path, T1 for the fused path
-    float* res = fused_tf ? T1 : T2;
+    *res_out = fused_tf ? t1 : t2;
+    return fused_tf ? Gf(src, t1, t2) : G(src, t1, t2);
+}
+
+namespace {
+
+// ---- direct pressure solve: M x = R (M = -A), in place helpers shared by the forward step and its adjoint.  R is modified
+// (the capacitance correction is subtracted from it); *res = the buffer (T1 or T2) that holds x.
+int pressure_solve3d(hipStream_t s, const sol_karman3d_cfg* c, const int32_t* hdr, float* R, float* T1, float* T2, float** res_out) {
+    const int B = c->B, Y = c->Y, X = c->X, Z = c->Z, N = Y * X * Z;
+    const int nS = hdr[4], SP = hdr[5];
+    const float* KpT = c->direct + FD3_HEADER + (size_t)Y * Y + (size_t)X * X + (size_t)Z * Z + (size_t)N;
+    const int* sidx = reinterpret_cast<const int*>(KpT + (size_t)SP * SP);
+    float* res = nullptr;
+    if (int e = k3_apply_G(s, c, R, T1, T2, &res, nullptr)) return e;
     *res_out = res;
-    if (int e = fused_tf ? Gf(R, T1, T2) : G(R, T1, T2)) return e;
     if (nS > 0) {
         SOL_REQUIRE(SP / CAPQ <= 1024 && SP % 64 == 0, "direct-solver blob: SP = %d does not fit the capacitance kernel", SP);
-        float* cpart = fused_tf ? T2 : T1;          // scratch: the buffer G does not return its result in (B * CAPQ * SP <= B * N floats)
+        float* cpart = res == T1 ? T2 : T1;         // scratch: the buffer G does not return its result in (B * CAPQ * SP <= B * N floats)
         SOL_LAUNCH(k3_capacitance, dim3(SP / 32, CAPQ, B), dim3(256), 0, s, res, KpT, sidx, cpart, SP, N);
         SOL_LAUNCH(k3_cap_apply, dim3((SP + 255) / 256, B), dim3(256), 0, s, cpart, sidx, R, SP, N);
-        if (int e = fused_tf ? Gf(R, T1, T2) : G(R, T1, T2)) return e;
+        if (int e = k3_apply_G(s, c, R, T1, T2, &res, nullptr)) return e;
     }
     SOL_LAUNCH_CHECK();
     return SOL_OK;
@@ -733,7 +761,14 @@ int check_blob3d(const sol_karman3d_cfg* c, const int32_t* hdr) {
     SOL_REQUIRE(nS >= 0 && SP >= nS && SP % 64 == 0 && SP <= 8192 && (size_t)8 * SP <= N, "direct-solver blob header is inconsistent (nS %d, SP %d)", nS, SP);
     const size_t want = (size_t)FD3_HEADER + (size_t)Y * Y + (size_t)X * X + (size_t)Z * Z + N + (size_t)SP * SP + SP;
     SOL_REQUIRE((size_t)c->direct_n == want, "direct-solver blob has %d words, expected %zu", c->direct_n, want);
-    return SOL_OK;
+    return k3_pcg_check(c, hdr);
+}
+
+// the pressure solve the cfg selects: M x = R (R is overwritten); *res = the buffer that holds x
+int pressure_solve_any3d(hipStream_t s, const sol_karman3d_cfg* c, const int32_t* hdr, const float* active, float* R, float* T1, float* T2,
+                         void* pcg_ws, float** res) {
+    if (c->pressure_solver == 1) return k3_pcg_solve(s, c, active, R, T1, T2, pcg_ws, res);
+    return pressure_solve3d(s, c, hdr, R, T1, T2, res);
 }
 
 // ========================================================================================================================
@@ -1091,9 +1126,9 @@ extern "C" int32_t sol_abi_size_karman3d(void) { return (int32_t)sizeof(sol_karm
 extern "C" size_t sol_karman3d_step_workspace_bytes(const sol_karman3d_cfg* c) {
     if (!c) return 0;
     const size_t B = c->B, Y = c->Y, X = c->X, Z = c->Z;
-    // three diffused components + rhs + two transform buffers
+    // three diffused components + rhs + two transform buffers (+ the CG solve's vectors and slabs)
     const size_t floats = B * ((Y + 1) * X * Z + Y * (X + 1) * Z + Y * X * (Z + 1) + 3 * Y * X * Z) + 256;
-    return floats * sizeof(float);
+    return floats * sizeof(float) + k3_pcg_workspace_bytes(c);
 }
 
 extern "C" int sol_karman3d_step_fwd(const sol_karman3d_cfg* c, void* stream,
@@ -1124,6 +1159,7 @@ extern "C" int sol_karman3d_step_fwd(const sol_karman3d_cfg* c, void* stream,
     float* R = w; w += (size_t)B * N;
     float* T1 = w; w += (size_t)B * N;
     float* T2 = w; w += (size_t)B * N;
+    void* pcg_ws = w + 256;
     if (saved_vy) { svy = saved_vy; svx = saved_vx; svz = saved_vz; }     // training: the post-diffusion velocity is the only state the adjoint needs
 
     K3Args a{};
@@ -1148,7 +1184,7 @@ extern "C" int sol_karman3d_step_fwd(const sol_karman3d_cfg* c, void* stream,
     SOL_LAUNCH_CHECK();
 
     float* res = nullptr;
-    if (int e = pressure_solve3d(s, c, direct_header_host, R, T1, T2, &res)) return e;
+    if (int e = pressure_solve_any3d(s, c, direct_header_host, active, R, T1, T2, pcg_ws, &res)) return e;
     a.p = res;
     SOL_LAUNCH(k3_project, dim3(grid_for(faces), B), dim3(256), 0, s, a);
     SOL_LAUNCH_CHECK();
@@ -1160,7 +1196,7 @@ extern "C" size_t sol_karman3d_step_bwd_workspace_bytes(const sol_karman3d_cfg* 
     const size_t B = c->B, Y = c->Y, X = c->X, Z = c->Z;
     // g_a (fp32) and g_c (int64 fixed point), three components each + rhs + two transform buffers + the absmax slots
     const size_t floats = B * (3 * ((Y + 1) * X * Z + Y * (X + 1) * Z + Y * X * (Z + 1)) + 3 * Y * X * Z + K3B_SLOTS) + 256;
-    return floats * sizeof(float);
+    return floats * sizeof(float) + k3_pcg_workspace_bytes(c);
 }
 
 extern "C" int sol_karman3d_step_bwd(const sol_karman3d_cfg* c, void* stream,
@@ -1193,11 +1229,12 @@ extern "C" int sol_karman3d_step_bwd(const sol_karman3d_cfg* c, void* stream,
     float* R = w; w += (size_t)B * N;
     float* T1 = w; w += (size_t)B * N;
     float* T2 = w; w += (size_t)B * N;
+    void* pcg_ws = w + 256;
     a.rhs = R; a.giy = g_vy_in; a.gix = g_vx_in; a.giz = g_vz_in;
     SOL_LAUNCH(k3b_rhs, dim3(grid_for(N), B), dim3(256), 0, s, a);
     SOL_LAUNCH_CHECK();
     float* res = nullptr;
-    if (int e = pressure_solve3d(s, c, direct_header_host, R, T1, T2, &res)) return e;
+    if (int e = pressure_solve_any3d(s, c, direct_header_host, active, R, T1, T2, pcg_ws, &res)) return e;
     a.gdiv = res;
     {   // wave per column, a few columns per wave: 1 024 workgroups at most publish into the 64 absmax slots
         const size_t cols = (size_t)(Y + 1) * X + (size_t)Y * (X + 1) + (size_t)Y * X;
@@ -1212,6 +1249,28 @@ extern "C" int sol_karman3d_step_bwd(const sol_karman3d_cfg* c, void* stream,
     } else
     SOL_LAUNCH(k3b_advect_adj, dim3(grid_for((size_t)((Y + 1) * X + Y * (X + 1) + Y * X) * 64), B), dim3(256), 0, s, a);
     SOL_LAUNCH(k3b_diffuse_adj, dim3(grid_for(faces), B), dim3(256), 0, s, a);
+    SOL_LAUNCH_CHECK();
+    return SOL_OK;
+}
+
+extern "C" int sol_karman3d_pressure_solve(const sol_karman3d_cfg* c, void* stream, const float* active, const float* rhs, float* p,
+                                           const int32_t* direct_header_host, void* workspace, size_t workspace_bytes) {
+    SOL_REQUIRE(c != nullptr, "cfg is NULL");
+    SOL_REQUIRE(c->B >= 1 && c->Y >= 8 && c->X >= 8 && c->Z >= 8 && c->B <= 65535, "sol_karman3d_pressure_solve: B >= 1, Y, X, Z >= 8");
+    SOL_REQUIRE(active && rhs && p && workspace, "sol_karman3d_pressure_solve: NULL pointer argument");
+    if (int e = check_blob3d(c, direct_header_host)) return e;
+    SOL_REQUIRE(workspace_bytes >= sol_karman3d_step_workspace_bytes(c), "workspace too small");
+    const int B = c->B;
+    const size_t N = (size_t)c->Y * c->X * c->Z, faces = (size_t)(c->Y + 1) * c->X * c->Z + (size_t)c->Y * (c->X + 1) * c->Z + (size_t)c->Y * c->X * (c->Z + 1);
+    hipStream_t s = (hipStream_t)stream;
+    float* w = static_cast<float*>(workspace) + B * faces;          // the step's layout: R, T1, T2 after the three components
+    float* R = w; w += B * N;
+    float* T1 = w; w += B * N;
+    float* T2 = w; w += B * N;
+    SOL_LAUNCH(k3_fill, dim3(grid_for(B * N)), dim3(256), 0, s, R, rhs, B * N);
+    float* res = nullptr;
+    if (int e = pressure_solve_any3d(s, c, direct_header_host, active, R, T1, T2, w + 256, &res)) return e;
+    SOL_LAUNCH(k3_fill, dim3(grid_for(B * N)), dim3(256), 0, s, p, (const float*)res, B * N);
     SOL_LAUNCH_CHECK();
     return SOL_OK;
 }

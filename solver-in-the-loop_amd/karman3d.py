@@ -54,14 +54,34 @@ def velocity_bc_masks3d(Y, X, Z):
     return vn, np.copy(vn)
 
 
-class Scene3D:
-    """Device-resident constants of a karman-3d scene: masks + the direct pressure-solver blob (precond3d)."""
+PRESSURE_SOLVERS3D = ("auto", "direct", "cg")
+CG_MAX_ITER3D = 120             # launch budget of the CG solve: 28-87 iterations measured at rtol 1e-6
 
-    def __init__(self, Y, X, Z, length=100.0, device="cuda", velBCy=None, velBCyMask=None):
+
+class Scene3D:
+    """Device-resident constants of a karman-3d scene: masks + the pressure-solver blob (precond3d).
+
+    active [Y,X,Z] (1 = fluid, 0 = solid; default: scene_arrays3d's sphere) and inflow [Y,X,Z] (default: its inflow box).
+    pressure_solver: "direct" = the capacitance-corrected direct solve (ValueError where precond3d.direct_solver_blob3d refuses
+    the mask), "cg" = the preconditioned CG solve (any mask; the blob without capacitance part), "auto" = direct where the blob
+    builds, else CG.  The choice is `self.pressure_solver` ("direct" or "cg")."""
+
+    def __init__(self, Y, X, Z, length=100.0, device="cuda", velBCy=None, velBCyMask=None, active=None, inflow=None, pressure_solver="auto"):
         from .precond3d import direct_solver_blob3d
+        if pressure_solver not in PRESSURE_SOLVERS3D:
+            raise ValueError("pressure_solver must be one of %s, got %r" % (PRESSURE_SOLVERS3D, pressure_solver))
         self.Y, self.X, self.Z = Y, X, Z
         self.dx = length / X
-        active, inflow = scene_arrays3d(Y, X, Z, length)
+        if active is None or inflow is None:
+            act0, inf0 = scene_arrays3d(Y, X, Z, length)
+            active = act0 if active is None else active
+            inflow = inf0 if inflow is None else inflow
+        active = np.asarray(active, dtype=np.float64)
+        inflow = np.asarray(inflow, dtype=np.float64)
+        if active.shape != (Y, X, Z) or inflow.shape != (Y, X, Z):
+            raise ValueError("active / inflow must be [Y,X,Z] = %s, got %s / %s" % ((Y, X, Z), active.shape, inflow.shape))
+        if not np.all((active == 0.0) | (active == 1.0)):
+            raise ValueError("active must hold 0 (solid) and 1 (fluid) only")
         bcv, bcm = velocity_bc_masks3d(Y, X, Z)
         if velBCy is not None:
             bcv, bcm = np.asarray(velBCy, dtype=np.float64), np.asarray(velBCyMask, dtype=np.float64)
@@ -74,27 +94,47 @@ class Scene3D:
         self.inflow = _lib.f32(inflow, device)
         self.velBCy = _lib.f32(bcv, device)
         self.velBCyMask = _lib.f32(bcm, device)
-        blob = direct_solver_blob3d(active)
-        if blob is None:
+        blob = direct_solver_blob3d(active) if pressure_solver != "cg" else None
+        if blob is None and pressure_solver == "direct":
             raise ValueError("the direct pressure solver does not support this scene (%dx%dx%d)" % (Y, X, Z))
+        self.pressure_solver = "direct" if blob is not None else "cg"
+        if blob is None:
+            blob = direct_solver_blob3d(np.ones_like(active))        # the CG preconditioner: the empty-box solve (nS = 0)
         self.direct = torch.from_numpy(blob).to(device)
         self.direct_header = np.ascontiguousarray(blob[:16].view(np.int32))
 
 
 class Karman3DFlow:
-    """`simulator.step(...)` of the 3-D scene: one sol_karman3d_step_fwd."""
+    """`simulator.step(...)` of the 3-D scene: one sol_karman3d_step_fwd.
 
-    def __init__(self, scene, batch_size, dt=1.0, res=None, grad_pad="replicate", inflow_order="after"):
+    cg_rtol / cg_atol / cg_max_iter: the CG solve of a scene with pressure_solver == "cg" (names and tolerances of the 2-D
+    KarmanFlow; cg_max_iter is the fixed launch budget).  After a forward step on such a scene `solve_info` holds "iterations"
+    and "converged" (device int32 [B]); the adjoint adds "iterations_bwd" and "converged_bwd".  The direct solve reports nothing."""
+
+    def __init__(self, scene, batch_size, dt=1.0, res=None, grad_pad="replicate", inflow_order="after",
+                 cg_rtol=1e-6, cg_atol=1e-9, cg_max_iter=CG_MAX_ITER3D):
         _lib.require_gpu()
         self.lib = _lib.load()
         self.scene, self.B = scene, batch_size
         s = scene
+        self.cg = s.pressure_solver == "cg"
         self.cfg = Karman3DCfg(batch_size, s.Y, s.X, s.Z, float(s.dx), float(dt), float(s.X if res is None else res),
                                {"replicate": 0, "dirichlet0": 1}[grad_pad], {"after": 0, "before": 1}[inflow_order],
-                               s.direct.numel(), s.direct.data_ptr())
+                               s.direct.numel(), s.direct.data_ptr(),
+                               1 if self.cg else 0, int(cg_max_iter), float(cg_rtol), float(cg_atol), None)
         nbytes = max(self.lib.sol_karman3d_step_workspace_bytes(C.byref(self.cfg)), self.lib.sol_karman3d_step_bwd_workspace_bytes(C.byref(self.cfg)))
         self.workspace = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=s.active.device)
         self.workspace_bytes = nbytes
+        self.solve_info = {}
+
+    def _cg_info(self):
+        """a fresh device report [B][2] for the next call (a captured graph keeps its own), or None for the direct solve"""
+        if not self.cg:
+            self.cfg.cg_info = None
+            return None
+        info = torch.empty(self.B, 2, dtype=torch.int32, device=self.scene.active.device)      # (every solve writes it)
+        self.cfg.cg_info = info.data_ptr()
+        return info
 
     def _fwd(self, d, vy, vx, vz, re, saved=None, feat_out=None, feat_scale=None):
         s, B = self.scene, self.B
@@ -107,21 +147,41 @@ class Karman3DFlow:
             assert feat_out.shape == (B, Y, X, Z, 4) and feat_out.is_contiguous()
             fs = (C.c_float * 4)(*[float(v) for v in feat_scale])
         sv = saved if saved is not None else (None, None, None)
+        info = self._cg_info()
         check(self.lib.sol_karman3d_step_fwd(C.byref(self.cfg), stream(), ptr(d), ptr(vy), ptr(vx), ptr(vz), ptr(re),
                                              ptr(s.active), ptr(s.inflow), ptr(s.velBCy), ptr(s.velBCyMask), s.bc_stride,
                                              ptr(out[0]), ptr(out[1]), ptr(out[2]), ptr(out[3]), ptr(sv[0]), ptr(sv[1]), ptr(sv[2]),
                                              ptr(feat_out), fs,
                                              s.direct_header.ctypes.data_as(C.c_void_p), ptr(self.workspace), self.workspace_bytes))
+        if info is not None:
+            self.solve_info = {"iterations": info[:, 0], "converged": info[:, 1]}
         return tuple(out)
 
     def _bwd(self, saved, re, gvy, gvx, gvz):
         s = self.scene
         gi = [torch.empty_like(t) for t in saved]
+        info = self._cg_info()
         check(self.lib.sol_karman3d_step_bwd(C.byref(self.cfg), stream(), ptr(saved[0]), ptr(saved[1]), ptr(saved[2]), ptr(re),
                                              ptr(s.active), ptr(s.velBCyMask), s.bc_stride, ptr(gvy), ptr(gvx), ptr(gvz),
                                              ptr(gi[0]), ptr(gi[1]), ptr(gi[2]),
                                              s.direct_header.ctypes.data_as(C.c_void_p), ptr(self.workspace), self.workspace_bytes))
+        if info is not None:
+            self.solve_info = dict(self.solve_info, iterations_bwd=info[:, 0], converged_bwd=info[:, 1])
         return gi
+
+    def pressure_solve(self, rhs):
+        """The step's pressure solve alone (sol_karman3d_pressure_solve): p with M p = rhs, M = -A for the scene's mask; rhs [B,Y,X,Z].
+        No gradient.  A CG scene reports to solve_info["iterations"] / ["converged"]."""
+        s = self.scene
+        rhs = _lib.f32(rhs)
+        assert rhs.shape == (self.B, s.Y, s.X, s.Z)
+        p = torch.empty_like(rhs)
+        info = self._cg_info()
+        check(self.lib.sol_karman3d_pressure_solve(C.byref(self.cfg), stream(), ptr(s.active), ptr(rhs), ptr(p),
+                                                   s.direct_header.ctypes.data_as(C.c_void_p), ptr(self.workspace), self.workspace_bytes))
+        if info is not None:
+            self.solve_info = {"iterations": info[:, 0], "converged": info[:, 1]}
+        return p
 
     def step(self, d, vy, vx, vz, re, feat_out=None, feat_scale=None):
         """(d, vy, vx, vz) -> new tensors after one solver step.  Differentiable with respect to the velocity (the density is

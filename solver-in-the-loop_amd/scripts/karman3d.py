@@ -40,13 +40,17 @@ def main(argv=None):
     p.add_argument("--train-steps", default=4, type=int, help="training steps of the demo")
     p.add_argument("--lr", default=1e-5, type=float)
     p.add_argument("--seed", default=0, type=int)
+    p.add_argument("--obstacle-mask", default=None, help="[Y,X,Z] .npy mask of the scene (1 = fluid, 0 = solid) instead of the sphere")
+    p.add_argument("--pressure-solver", default="auto", choices=k3.PRESSURE_SOLVERS3D,
+                   help="direct (capacitance blob), cg (preconditioned CG, any mask) or auto (direct where it builds)")
     params = vars(p.parse_args(argv))
     select_gpu(params["gpu"])
     log = logger()
     res = params["res"]
     Y, X, Z = 2 * res, res, res
     dev = "cuda"
-    sc = k3.Scene3D(Y, X, Z, length=float(params["len"]), device=dev)
+    active = np.load(params["obstacle_mask"]) if params["obstacle_mask"] else None
+    sc = k3.Scene3D(Y, X, Z, length=float(params["len"]), device=dev, active=active, pressure_solver=params["pressure_solver"])
     sim = k3.Karman3DFlow(sc, 1)
     f = lambda a: torch.as_tensor(a, dtype=torch.float32, device=dev).contiguous()
     # karman.py:106-110 in 3-D: uniform flow along y + a sideways poke behind the obstacle
@@ -63,6 +67,7 @@ def main(argv=None):
         with open(path + "/params.pickle", "wb") as fh:
             pickle.dump(params, fh)
     log.info(params)
+    log.info("pressure solver: %s" % sc.pressure_solver)
     net = ro = None
     if params["model"]:
         blob = torch.load(params["model"], map_location="cpu")
