@@ -149,6 +149,30 @@ int sol_karman_step_fwd_large(const sol_karman_cfg* cfg, void* stream,
                               float* feat_out, const float* feat_scale,
                               const int32_t* direct_header_host,
                               void* workspace, size_t workspace_bytes);
+/* The same step with a preconditioned CG pressure solve, for ANY obstacle mask (scenes whose direct blob is refused: perturbed cells
+ * beyond one 64 x 64 window, an ill-conditioned capacitance system).  Arguments as sol_karman_step_fwd_large, except: cfg.direct is
+ * not read; `box_blob` = DEVICE blob of the empty-box solve (precond.box_solver_blob(Y, X): header with nS = 0, Qy, Qx, 1/lam), the
+ * preconditioner; `box_header_host` = HOST copy of its first 16 words; `cg_info` = DEVICE int32 [2][B] written by the call: row 0 the
+ * iterations used, row 1 converged (0/1) -- a simulation that does not converge within cfg.cg_max_iter is reported there, its pressure
+ * is the last iterate.  A simulation stops when |r|_2 <= max(cfg.cg_rtol |b|_2, cfg.cg_atol) (cg_max_iter >= 1, tolerances >= 0, not
+ * both zero); the dot products are fixed-order fp64 sums, so results are bit-reproducible.  Under stream capture the call issues
+ * the full cg_max_iter budget and never synchronises; an eager call reads one 4-byte device word back every 16 iterations and stops
+ * issuing iterations once every simulation has converged.  `workspace`: DEVICE scratch of
+ * sol_karman_step_large_cg_workspace_bytes(cfg) bytes. */
+size_t sol_karman_step_large_cg_workspace_bytes(const sol_karman_cfg* cfg);
+int sol_karman_step_fwd_large_cg(const sol_karman_cfg* cfg, void* stream,
+                                 const float* d_in, const float* vy_in, const float* vx_in,
+                                 const float* re, const float* active, const float* inflow,
+                                 const float* velBCy, const float* velBCyMask, int64_t bc_batch_stride,
+                                 float* d_out, float* vy_out, float* vx_out,
+                                 float* feat_out, const float* feat_scale,
+                                 const float* box_blob, const int32_t* box_header_host, int32_t* cg_info,
+                                 void* workspace, size_t workspace_bytes);
+/* The CG step's pressure solve alone: M p = rhs with M = -A for the scene's `active` mask [Y,X] (precond.scene_matrix); rhs, p
+ * [B,Y,X] (rhs is read only); other arguments as sol_karman_step_fwd_large_cg. */
+int sol_karman_pressure_solve_large(const sol_karman_cfg* cfg, void* stream, const float* active, const float* rhs, float* p,
+                                    const float* box_blob, const int32_t* box_header_host, int32_t* cg_info,
+                                    void* workspace, size_t workspace_bytes);
 
 /* active  [Y,X]  1 - obstacle mask (cell centres inside Obstacle geometries -> 0)
  * inflow  [Y,X]  inflow rate mask (Inflow(box[5:10,25:75]) -> 1 inside)

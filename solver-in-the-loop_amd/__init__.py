@@ -9,7 +9,7 @@ from ._lib import SolError, load, declared_symbols, lib_path  # noqa: F401
 from .fluid import (box, Box, Sphere, Inflow, Obstacle, Gravity, Domain, OPEN, PERIODIC,  # noqa: F401
                     CenteredGrid, StaggeredGrid, Fluid, BurgersVelocitySMAC, unstack_staggered_tensor)
 from . import ops, dist  # noqa: F401
-from .karman import KarmanFlow, to_feature, to_staggered, lr_schedule, velocity_bc_masks  # noqa: F401
+from .karman import KarmanFlow, to_feature, to_staggered, lr_schedule, velocity_bc_masks, parse_obstacles  # noqa: F401
 from .model import model_mars_moon, model_mercury, MarsMoon, Mercury, ConvNet  # noqa: F401
 from .trainer import SolTrainer, SolRollout, GraphTrainer, make_trainer  # noqa: F401
 from . import synthetic, scene, burgers  # noqa: F401

@@ -175,10 +175,12 @@ struct GArgs {
     int M, N, K, lda, ldb, ldc, lds;
     long sA, sB, sC;
     int accumulate;
+    const int* skip;        // per-simulation done words [batch] (the CG solve's preconditioner) or NULL
 };
 __global__ void __launch_bounds__(256) k_l_gemm(GArgs g) {
     __shared__ float As[16][65], Bs[16][65];
     const int b = blockIdx.z, m0 = blockIdx.y * 64, n0 = blockIdx.x * 64;
+    if (g.skip && g.skip[b]) return;
     const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
     const float* A = g.A + (size_t)b * g.sA;
     const float* Bm = g.Bm + (size_t)b * g.sB;
@@ -221,8 +223,10 @@ __global__ void __launch_bounds__(256) k_l_gemm(GArgs g) {
 }
 
 // T[m][c] = (add ? T[m][c] + add[m][c] * il : T[m][c] * il) with il = ilT[c][m] (1 / eigenvalue, stored transposed in the blob)
-__global__ void k_l_scale(float* __restrict__ T, const float* __restrict__ add, const float* __restrict__ ilT, int Y, int X) {
+__global__ void k_l_scale(float* __restrict__ T, const float* __restrict__ add, const float* __restrict__ ilT, int Y, int X,
+                          const int* __restrict__ skip) {
     const int b = blockIdx.y;
+    if (skip && skip[b]) return;
     for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < Y * X; e += gridDim.x * blockDim.x) {
         const int m = e / X, c = e - m * X;
         const float il = ilT[(size_t)c * Y + m];
@@ -253,11 +257,22 @@ __global__ void k_l_capacitance(const float* __restrict__ x0w, const float* __re
 struct Header { int Y, X, wy0, wx0, nS, SP, win; };
 
 int gemm(hipStream_t s, int batch, const float* A, int lda, long sA, const float* Bm, int ldb, long sB, float* C, int ldc, long sC,
-         int M, int N, int K, int accumulate) {
-    GArgs g{A, Bm, nullptr, C, M, N, K, lda, ldb, ldc, 0, sA, sB, sC, accumulate};
+         int M, int N, int K, int accumulate, const int* skip = nullptr) {
+    GArgs g{A, Bm, nullptr, C, M, N, K, lda, ldb, ldc, 0, sA, sB, sC, accumulate, skip};
     SOL_LAUNCH(k_l_gemm, dim3((N + 63) / 64, (M + 63) / 64, batch), dim3(256), 0, s, g);
     SOL_LAUNCH_CHECK();
     return SOL_OK;
+}
+
+LArgs large_args(const sol_karman_cfg* c, const SolLargeStep& io, float* svy, float* svx, float* rhs, const float* p) {
+    LArgs a{};
+    a.B = c->B; a.Y = c->Y; a.X = c->X; a.dtdx = c->dt / c->dx; a.dt = c->dt; a.adt = c->dt * c->res * c->res;
+    a.grad_pad = c->grad_pad; a.inflow_before = c->inflow_before;
+    a.d_in = io.d_in; a.vy_in = io.vy_in; a.vx_in = io.vx_in; a.re = io.re; a.active = io.active; a.inflow = io.inflow;
+    a.bcv = io.velBCy; a.bcm = io.velBCyMask; a.bc_stride = io.bc_stride;
+    a.d_out = io.d_out; a.vy_out = io.vy_out; a.vx_out = io.vx_out; a.svy = svy; a.svx = svx; a.rhs = rhs; a.feat = io.feat_out; a.p = p;
+    if (io.feat_scale) { a.fs0 = io.feat_scale[0]; a.fs1 = io.feat_scale[1]; a.fs2 = io.feat_scale[2]; }
+    return a;
 }
 
 }  // namespace
@@ -266,6 +281,50 @@ int gemm(hipStream_t s, int batch, const float* A, int lda, long sA, const float
 int sol_gemm_f32(hipStream_t s, int batch, const float* A, int lda, long sA, const float* Bm, int ldb, long sB, float* C, int ldc, long sC,
                  int M, int N, int K, int accumulate) {
     return gemm(s, batch, A, lda, sA, Bm, ldb, sB, C, ldc, sC, M, N, K, accumulate);
+}
+
+// ---- the stencil phases around the pressure solve (shared with karman_large_pcg.hip) ----
+int sol_large_front(const sol_karman_cfg* c, hipStream_t s, const SolLargeStep& io, float* svy, float* svx, float* rhs) {
+    const LArgs a = large_args(c, io, svy, svx, rhs, nullptr);
+    const int B = c->B, N = c->Y * c->X, faces = (c->Y + 1) * c->X + c->Y * (c->X + 1);
+    SOL_LAUNCH(k_l_diffuse, dim3((faces + 255) / 256, B), dim3(256), 0, s, a);
+    SOL_LAUNCH(k_l_advect, dim3((faces + N + 255) / 256, B), dim3(256), 0, s, a);
+    SOL_LAUNCH(k_l_div, dim3((N + 255) / 256, B), dim3(256), 0, s, a);
+    SOL_LAUNCH_CHECK();
+    return SOL_OK;
+}
+
+int sol_large_project(const sol_karman_cfg* c, hipStream_t s, const SolLargeStep& io, const float* p) {
+    const LArgs a = large_args(c, io, nullptr, nullptr, nullptr, p);
+    const int faces = (c->Y + 1) * c->X + c->Y * (c->X + 1);
+    SOL_LAUNCH(k_l_project, dim3((faces + 255) / 256, c->B), dim3(256), 0, s, a);
+    SOL_LAUNCH_CHECK();
+    return SOL_OK;
+}
+
+// ---- the empty-box solve G = M_r^-1 (sine-transform diagonalisation of the rectangle), in two halves: the direct solve adds its
+// capacitance correction to the spectral coefficients T2 in between, the CG solve applies both halves back to back.  All matrices
+// row-major [Y][X] per simulation; Qy, Qx symmetric.  blob: the sections after the header (Qy, Qx, 1/lam transposed)
+int sol_large_box_forward(hipStream_t s, int B, int Y, int X, const float* blob, const float* src, float* T1, float* T2, const int* skip) {
+    const float* Qy = blob + FDL_HEADER;
+    const float* Qx = Qy + (size_t)Y * Y;
+    const float* ilT = Qx + (size_t)X * X;             // [X][Y]
+    const long sN = (long)Y * X;
+    // T1 = Qy src ;  T2 = (T1 Qx) / lam
+    if (int e = gemm(s, B, Qy, Y, 0, src, X, sN, T1, X, sN, Y, X, Y, 0, skip)) return e;
+    if (int e = gemm(s, B, T1, X, sN, Qx, X, 0, T2, X, sN, Y, X, X, 0, skip)) return e;
+    SOL_LAUNCH(k_l_scale, dim3((Y * X + 255) / 256, B), dim3(256), 0, s, T2, (const float*)nullptr, ilT, Y, X, skip);
+    SOL_LAUNCH_CHECK();
+    return SOL_OK;
+}
+
+int sol_large_box_back(hipStream_t s, int B, int Y, int X, const float* blob, const float* T2, float* T1, float* dst, const int* skip) {
+    const float* Qy = blob + FDL_HEADER;
+    const float* Qx = Qy + (size_t)Y * Y;
+    const long sN = (long)Y * X;
+    // dst = Qy (T2 Qx)
+    if (int e = gemm(s, B, T2, X, sN, Qx, X, 0, T1, X, sN, Y, X, X, 0, skip)) return e;
+    return gemm(s, B, Qy, Y, 0, T1, X, sN, dst, X, sN, Y, X, Y, 0, skip);
 }
 
 extern "C" size_t sol_karman_step_large_workspace_bytes(const sol_karman_cfg* c) {
@@ -320,25 +379,12 @@ extern "C" int sol_karman_step_fwd_large(const sol_karman_cfg* c, void* stream,
     float* X0 = w; w += (size_t)B * 64 * 64;           // [win][win]
     float* W2 = w; w += (size_t)B * 64 * 64;
 
-    LArgs a{};
-    a.B = B; a.Y = Y; a.X = X; a.dtdx = c->dt / c->dx; a.dt = c->dt; a.adt = c->dt * c->res * c->res;
-    a.grad_pad = c->grad_pad; a.inflow_before = c->inflow_before;
-    a.d_in = d_in; a.vy_in = vy_in; a.vx_in = vx_in; a.re = re; a.active = active; a.inflow = inflow;
-    a.bcv = velBCy; a.bcm = velBCyMask; a.bc_stride = bc_batch_stride;
-    a.d_out = d_out; a.vy_out = vy_out; a.vx_out = vx_out; a.svy = svy; a.svx = svx; a.rhs = T0; a.feat = feat_out; a.p = T0;
-    if (feat_scale) { a.fs0 = feat_scale[0]; a.fs1 = feat_scale[1]; a.fs2 = feat_scale[2]; }
-    const int faces = (Y + 1) * X + Y * (X + 1);
-    SOL_LAUNCH(k_l_diffuse, dim3((faces + 255) / 256, B), dim3(256), 0, s, a);
-    SOL_LAUNCH(k_l_advect, dim3((faces + N + 255) / 256, B), dim3(256), 0, s, a);
-    SOL_LAUNCH(k_l_div, dim3((N + 255) / 256, B), dim3(256), 0, s, a);
-    SOL_LAUNCH_CHECK();
+    const SolLargeStep io{d_in, vy_in, vx_in, re, active, inflow, velBCy, velBCyMask, bc_batch_stride, d_out, vy_out, vx_out, feat_out, feat_scale};
+    if (int e = sol_large_front(c, s, io, svy, svx, T0)) return e;
 
-    // ---- direct pressure solve.  All matrices row-major [Y][X] per simulation; Qy, Qx symmetric.
+    // ---- direct pressure solve: the empty-box solve of the rhs with the capacitance correction on its spectral coefficients
     const long sN = N, sU = (long)Y * 64, sW = 64 * 64;
-    // T1 = Qy rhs ;  T2 = (T1 Qx) / lam
-    if (int e = gemm(s, B, Qy, Y, 0, T0, X, sN, T1, X, sN, Y, X, Y, 0)) return e;
-    if (int e = gemm(s, B, T1, X, sN, Qx, X, 0, T2, X, sN, Y, X, X, 0)) return e;
-    SOL_LAUNCH(k_l_scale, dim3((N + 255) / 256, B), dim3(256), 0, s, T2, (const float*)nullptr, ilT, Y, X);
+    if (int e = sol_large_box_forward(s, B, Y, X, c->direct, T0, T1, T2, nullptr)) return e;
     // window values of G b: U = T2 Qx[:, win] ; X0 = Qy[win, :] U
     if (int e = gemm(s, B, T2, X, sN, QxW, win, 0, U, win, sU, Y, win, X, 0)) return e;
     if (int e = gemm(s, B, Qy + (size_t)h.wy0 * Y, Y, 0, U, win, sU, X0, win, sW, win, win, Y, 0)) return e;
@@ -348,11 +394,8 @@ extern "C" int sol_karman_step_fwd_large(const sol_karman_cfg* c, void* stream,
     // spectral coefficients of the correction: V = Qy[:, win] W2 ; T2 += ((V Qx[win, :])) / lam
     if (int e = gemm(s, B, Qy + h.wy0, Y, 0, W2, win, sW, V, win, sU, Y, win, win, 0)) return e;
     if (int e = gemm(s, B, V, win, sU, Qx + (size_t)h.wx0 * X, X, 0, T1, X, sN, Y, X, win, 0)) return e;
-    SOL_LAUNCH(k_l_scale, dim3((N + 255) / 256, B), dim3(256), 0, s, T2, (const float*)T1, ilT, Y, X);
+    SOL_LAUNCH(k_l_scale, dim3((N + 255) / 256, B), dim3(256), 0, s, T2, (const float*)T1, ilT, Y, X, (const int*)nullptr);
     // p = Qy (T2 Qx)
-    if (int e = gemm(s, B, T2, X, sN, Qx, X, 0, T1, X, sN, Y, X, X, 0)) return e;
-    if (int e = gemm(s, B, Qy, Y, 0, T1, X, sN, T0, X, sN, Y, X, Y, 0)) return e;
-    SOL_LAUNCH(k_l_project, dim3((faces + 255) / 256, B), dim3(256), 0, s, a);
-    SOL_LAUNCH_CHECK();
-    return SOL_OK;
+    if (int e = sol_large_box_back(s, B, Y, X, c->direct, T2, T1, T0, nullptr)) return e;
+    return sol_large_project(c, s, io, T0);
 }

@@ -23,11 +23,96 @@ def velocity_bc_masks(Y, X, batch_size=None):
     return vn, np.copy(vn)
 
 
+DEFAULT_OBSTACLES = ("sphere:50,50,10",)       # KarmanFlow's Obstacle(Sphere([50, 50], 10)), karman_train.py:169
+
+
+def _num(v):
+    return "%g" % v
+
+
+def parse_obstacles(spec):
+    """Obstacles of a scene from their text form (the scripts' --obstacle): one spec string or a list of them, each
+    `sphere:CY,CX,R` (centre and radius) or `box:Y0:Y1,X0:X1` (inclusive bounds), in domain coordinates (the domain is
+    box[0:2*len, 0:len], y first); `none` (alone) = no obstacle.  Returns a list of Obstacle(Sphere | Box)."""
+    specs = [spec] if isinstance(spec, str) else list(spec)
+    if any(str(s).strip().lower() == "none" for s in specs):
+        if len(specs) != 1:
+            raise ValueError("obstacle spec 'none' cannot be combined with other obstacles (got %r)" % (specs,))
+        return []
+    out = []
+    for s in specs:
+        kind, _, args = str(s).strip().partition(":")
+        kind = kind.lower()
+        try:
+            if kind == "sphere":
+                vals = [float(v) for v in args.split(",")]
+                if len(vals) != 3 or vals[2] <= 0:
+                    raise ValueError
+                out.append(Obstacle(Sphere(vals[:2], vals[2])))
+            elif kind == "box":
+                rng = [[float(v) for v in part.split(":")] for part in args.split(",")]
+                if len(rng) != 2 or any(len(r) != 2 or r[1] < r[0] for r in rng):
+                    raise ValueError
+                out.append(Obstacle(Box([rng[0][0], rng[1][0]], [rng[0][1], rng[1][1]])))
+            else:
+                raise ValueError
+        except ValueError:
+            raise ValueError("bad obstacle spec %r: expected 'sphere:CY,CX,R' (R > 0), 'box:Y0:Y1,X0:X1' (Y0 <= Y1, X0 <= X1) "
+                             "or 'none'" % (s,)) from None
+    return out
+
+
+def obstacle_spec(obstacles):
+    """Inverse of parse_obstacles: the canonical spec strings of a list of Obstacle(Sphere | Box)."""
+    out = []
+    for ob in obstacles:
+        g = ob.geometry if isinstance(ob, Obstacle) else ob
+        if isinstance(g, Sphere):
+            out.append("sphere:%s,%s,%s" % (_num(g.center[0]), _num(g.center[1]), _num(g.radius)))
+        elif isinstance(g, Box):
+            out.append("box:%s:%s,%s:%s" % (_num(g.lower[0]), _num(g.upper[0]), _num(g.lower[1]), _num(g.upper[1])))
+        else:
+            raise TypeError("obstacle geometry must be Sphere or Box, got %r" % (g,))
+    return out
+
+
+def scene_record(obstacles=None, active=None):
+    """Picklable description of a scene (what the scripts store in params.pickle / dataStats.pickle): {"obstacles": canonical spec
+    strings or None, "active": [Y, X] float32 mask or None}.  Neither given: the default sphere."""
+    if obstacles is not None and active is not None:
+        raise ValueError("give obstacles or an active mask, not both")
+    if active is not None:
+        return {"obstacles": None, "active": np.ascontiguousarray(np.asarray(active, dtype=np.float32))}
+    if obstacles is None:
+        return {"obstacles": list(DEFAULT_OBSTACLES), "active": None}
+    obs = parse_obstacles(obstacles) if isinstance(obstacles, str) or (obstacles and isinstance(obstacles[0], str)) else obstacles
+    return {"obstacles": obstacle_spec(obs), "active": None}
+
+
+def scenes_equal(a, b):
+    if (a["active"] is None) != (b["active"] is None):
+        return False
+    if a["active"] is not None:
+        return a["active"].shape == b["active"].shape and bool(np.array_equal(a["active"], b["active"]))
+    return list(a["obstacles"]) == list(b["obstacles"])
+
+
+def describe_scene(rec):
+    if rec["active"] is not None:
+        return "mask %dx%d (%d obstacle cells)" % (rec["active"].shape + (int((rec["active"] == 0).sum()),))
+    return ", ".join(rec["obstacles"]) or "none"
+
+
 class KarmanFlow:
-    """KarmanFlow(IncompressibleFlow), karman_train.py:166-185."""
+    """KarmanFlow(IncompressibleFlow), karman_train.py:166-185.
+
+    obstacles: list of Obstacle(Sphere | Box) in domain coordinates (the PhiFlow-2 spelling, karman-2d-phi2/karman_train.py:162),
+    resolution independent; [] = no obstacle.  active: a [Y, X] mask (1 = fluid) for exactly one grid.  Neither: the reference's
+    Obstacle(Sphere([50, 50], 10))."""
 
     def __init__(self, pressure_solver=None, make_input_divfree=False, make_output_divfree=True,
-                 cg_rtol=1e-6, cg_atol=1e-9, cg_max_iter=2000, grad_pad="replicate", inflow_order="after"):
+                 cg_rtol=1e-6, cg_atol=1e-9, cg_max_iter=2000, grad_pad="replicate", inflow_order="after",
+                 obstacles=None, active=None):
         # the reference's plug point: None = this build's default ("auto": the direct solver where the grid and the
         # scene allow it, else the two-level preconditioned CG), or one of "direct" / "cg"
         if pressure_solver not in (None, "auto", "direct", "cg"):
@@ -37,16 +122,51 @@ class KarmanFlow:
         if make_input_divfree or not make_output_divfree:
             raise NotImplementedError("only (make_input_divfree=False, make_output_divfree=True) is on the reference path")
         self.infl = Inflow(box[5:10, 25:75])
-        self.obst = Obstacle(Sphere([50, 50], 10))
+        if obstacles is not None and active is not None:
+            raise ValueError("KarmanFlow: give obstacles or an active mask, not both")
+        self.active = None
+        if active is not None:
+            if isinstance(active, torch.Tensor):
+                active = active.detach().cpu().numpy()
+            self.active = (np.asarray(active, dtype=np.float64) != 0).astype(np.float64)
+            if self.active.ndim != 2:
+                raise ValueError("KarmanFlow: active must be a [Y, X] mask, got shape %s" % (self.active.shape,))
+            self.obstacles, self.obst = None, None
+        elif obstacles is not None:
+            self.obstacles = [ob if isinstance(ob, Obstacle) else Obstacle(ob) for ob in obstacles]
+            for ob in self.obstacles:
+                if not isinstance(ob.geometry, (Sphere, Box)):
+                    raise TypeError("KarmanFlow: obstacle geometries must be Sphere or Box, got %r" % (ob.geometry,))
+            self.obst = None
+        else:
+            self.obst = Obstacle(Sphere([50, 50], 10))
+            self.obstacles = [self.obst]
         self._solver = dict(cg_rtol=cg_rtol, cg_atol=cg_atol, cg_max_iter=cg_max_iter,
                             grad_pad=grad_pad, inflow_order=inflow_order)
         self._cache = {}
         self.solve_info = {}
 
+    def scene(self):
+        """scene_record of this flow's obstacles / mask."""
+        if self.active is not None:
+            return scene_record(active=self.active)
+        return {"obstacles": obstacle_spec(self.obstacles), "active": None}
+
     # -- constant masks of the scene for a given domain ----------------------------------
     def scene_arrays(self, domain):
         yc, xc = domain.cell_centers()
-        active = 1.0 - self.obst.geometry.value_at(yc, xc)
+        if self.active is not None:
+            if tuple(self.active.shape) != tuple(domain.resolution):
+                raise ValueError("KarmanFlow: the active mask is %dx%d, the domain is %dx%d (a mask describes exactly one grid; "
+                                 "use obstacles=[...] for a resolution-independent scene)" % (self.active.shape + tuple(domain.resolution)))
+            active = self.active.copy()
+        elif self.obst is not None:
+            active = 1.0 - self.obst.geometry.value_at(yc, xc)
+        else:
+            solid = np.zeros(yc.shape)
+            for ob in self.obstacles:
+                solid = np.maximum(solid, ob.geometry.value_at(yc, xc))
+            active = 1.0 - solid
         inflow = self.infl.geometry.value_at(yc, xc) * self.infl.rate
         return active, inflow
 
@@ -94,16 +214,16 @@ class KarmanFlow:
         vy = smoke.velocity.data[0].data.reshape(B, Y + 1, X)
         vx = smoke.velocity.data[1].data.reshape(B, Y, X + 1)
         info = {}
+        self.pressure_solver_used = masks.pressure_solver        # "direct" or "cg" (SceneMasks' choice for this grid and scene)
         if masks.large:
-            # beyond the one-workgroup kernels (data generation at 256 x 128, karman.py:98-159): forward-only path
-            if masks.direct is None:
-                raise ValueError("grids larger than 128x64 need the direct pressure solver (scene not supported / pressure_solver='cg')")
+            # beyond the one-workgroup kernels (data generation at 256 x 128, karman.py:98-159): forward-only path, direct solve
+            # where the scene's blob builds, else the preconditioned CG (solve_info: iterations / converged per simulation)
             if torch.is_grad_enabled() and (vy.requires_grad or vx.requires_grad):
                 raise NotImplementedError("the large-grid solver step (%dx%d) is forward only" % (Y, X))
-            if getattr(self, "_large_ws", None) is None or self._large_ws[0] != (B, Y, X, str(dev)):
-                n = ops._lib.load().sol_karman_step_large_workspace_bytes(ops.C.byref(cfg))
+            n = ops.large_workspace_bytes(cfg, masks)
+            if getattr(self, "_large_ws", None) is None or self._large_ws[0] != (B, Y, X, str(dev)) or self._large_ws[1].numel() * 4 < n:
                 self._large_ws = ((B, Y, X, str(dev)), torch.empty((n + 3) // 4, dtype=torch.float32, device=dev))
-            d2, vy2, vx2 = ops.karman_step_large(d, vy, vx, re_t, cfg, masks, self._large_ws[1])
+            d2, vy2, vx2 = ops.karman_step_large(d, vy, vx, re_t, cfg, masks, self._large_ws[1], info)
         else:
             d2, vy2, vx2 = ops.karman_step(d, vy, vx, re_t, cfg, masks, info)
         self.solve_info = info

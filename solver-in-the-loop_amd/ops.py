@@ -69,25 +69,74 @@ class SceneMasks:
                 self.direct_header = np.ascontiguousarray(blob[:16].view(np.int32))      # host copy: sizes the large-grid launches
         if want == "direct" and self.direct is None:
             raise ValueError("the direct pressure solver does not support this scene (%dx%d)" % (Y, X))
+        # large grids without a direct blob ("cg", or a scene the blob refuses): the preconditioned CG solve of the large-grid step
+        # (sol_karman_step_fwd_large_cg) with the empty-box solve as its preconditioner
+        self.box = None
+        self.box_header = None
+        if self.large and self.direct is None:
+            from .precond import box_solver_blob
+            blob = box_solver_blob(Y, X)
+            self.box = torch.from_numpy(blob).to(device)
+            self.box_header = np.ascontiguousarray(blob[:16].view(np.int32))
+        self.pressure_solver = "direct" if self.direct is not None else "cg"
 
 
-def karman_step_large(d, vy, vx, re, cfg, masks, workspace=None):
+def large_workspace_bytes(cfg, masks):
+    """Device scratch of the large-grid step for the scene's solver (direct or CG)."""
+    lib = _lib.load()
+    if masks.direct is None:
+        return lib.sol_karman_step_large_cg_workspace_bytes(C.byref(cfg))
+    return lib.sol_karman_step_large_workspace_bytes(C.byref(cfg))
+
+
+def karman_step_large(d, vy, vx, re, cfg, masks, workspace=None, info=None):
     """Forward-only step for grids beyond the one-workgroup kernels (data generation at 256 x 128,
-    /root/reference/karman-2d/karman.py:98-159): sol_karman_step_fwd_large.  Returns (d, vy, vx) after the step."""
+    /root/reference/karman-2d/karman.py:98-159): sol_karman_step_fwd_large (direct solve) or sol_karman_step_fwd_large_cg (CG solve,
+    masks.pressure_solver == "cg").  Returns (d, vy, vx) after the step; with the CG solve, `info` (a dict) receives "iterations" and
+    "converged", device int32 [B] each."""
     _lib.require_gpu()
     lib = _lib.load()
     d, vy, vx, re = (_lib.f32(t) for t in (d, vy, vx, re))
     B, Y, X = cfg.B, cfg.Y, cfg.X
     assert vy.shape == (B, Y + 1, X) and vx.shape == (B, Y, X + 1) and d.shape == (B, Y, X) and re.shape == (B,)
-    nbytes = lib.sol_karman_step_large_workspace_bytes(C.byref(cfg))
+    nbytes = large_workspace_bytes(cfg, masks)
     if workspace is None or workspace.numel() * 4 < nbytes:
         workspace = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=vy.device)
     d_out, vy_out, vx_out = torch.empty_like(d), torch.empty_like(vy), torch.empty_like(vx)
-    check(lib.sol_karman_step_fwd_large(C.byref(cfg), stream(), ptr(d), ptr(vy), ptr(vx), ptr(re),
-                                        ptr(masks.active), ptr(masks.inflow), ptr(masks.velBCy), ptr(masks.velBCyMask),
-                                        masks.bc_stride, ptr(d_out), ptr(vy_out), ptr(vx_out), None, None,
-                                        masks.direct_header.ctypes.data_as(C.c_void_p), ptr(workspace), workspace.numel() * 4))
+    head = (C.byref(cfg), stream(), ptr(d), ptr(vy), ptr(vx), ptr(re), ptr(masks.active), ptr(masks.inflow), ptr(masks.velBCy),
+            ptr(masks.velBCyMask), masks.bc_stride, ptr(d_out), ptr(vy_out), ptr(vx_out), None, None)
+    if masks.direct is not None:
+        check(lib.sol_karman_step_fwd_large(*head, masks.direct_header.ctypes.data_as(C.c_void_p), ptr(workspace), workspace.numel() * 4))
+    else:
+        cg_info = torch.empty(2, B, dtype=torch.int32, device=vy.device)
+        check(lib.sol_karman_step_fwd_large_cg(*head, ptr(masks.box), masks.box_header.ctypes.data_as(C.c_void_p), ptr(cg_info),
+                                               ptr(workspace), workspace.numel() * 4))
+        if info is not None:
+            info["iterations"], info["converged"] = cg_info[0], cg_info[1]
     return d_out, vy_out, vx_out
+
+
+def pressure_solve_large(rhs, cfg, masks, workspace=None, info=None):
+    """The large-grid CG step's pressure solve alone (sol_karman_pressure_solve_large): p [B,Y,X] with M p = rhs, M = -A of the
+    scene's mask (precond.scene_matrix).  `info` receives "iterations" / "converged" (device int32 [B])."""
+    _lib.require_gpu()
+    lib = _lib.load()
+    if masks.box is None:
+        raise ValueError("pressure_solve_large needs a scene prepared for the large-grid CG solve (SceneMasks.pressure_solver == 'cg')")
+    rhs = _lib.f32(rhs)
+    B, Y, X = cfg.B, cfg.Y, cfg.X
+    assert rhs.shape == (B, Y, X)
+    nbytes = lib.sol_karman_step_large_cg_workspace_bytes(C.byref(cfg))
+    if workspace is None or workspace.numel() * 4 < nbytes:
+        workspace = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=rhs.device)
+    p = torch.empty_like(rhs)
+    cg_info = torch.empty(2, B, dtype=torch.int32, device=rhs.device)
+    check(lib.sol_karman_pressure_solve_large(C.byref(cfg), stream(), ptr(masks.active), ptr(rhs), ptr(p), ptr(masks.box),
+                                              masks.box_header.ctypes.data_as(C.c_void_p), ptr(cg_info), ptr(workspace),
+                                              workspace.numel() * 4))
+    if info is not None:
+        info["iterations"], info["converged"] = cg_info[0], cg_info[1]
+    return p
 
 
 def _scale3(vals):

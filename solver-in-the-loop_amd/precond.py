@@ -149,6 +149,62 @@ def direct_solver_blob(active, max_window=FD_WIN):
     return np.concatenate(parts)
 
 
+def box_solver_blob(Y, X):
+    """float32 blob of the empty-box solve G = M_r^-1 alone: the direct_solver_blob layout with nS = SP = 0 (no capacitance part, no
+    window: win = 0), i.e. header[16] = {magic, Y, X, 0, 0, 0, 0, 0, ...}; Qy[Y*Y]; Qx[X*X]; invlamT[X*Y].  The preconditioner of
+    the large-grid CG solve (sol_karman_step_fwd_large_cg), which takes any obstacle."""
+    Qy, Qx = dst_matrix(Y), dst_matrix(X)
+    lam = (2 - 2 * np.cos(np.pi * np.arange(1, Y + 1) / (Y + 1)))[:, None] + (2 - 2 * np.cos(np.pi * np.arange(1, X + 1) / (X + 1)))[None, :]
+    header = np.zeros(FD_HEADER, dtype=np.int32)
+    header[:3] = [FD_MAGIC, Y, X]
+    return np.concatenate([header.view(np.float32), Qy.astype(np.float32).ravel(), Qx.astype(np.float32).ravel(),
+                           (1.0 / lam).T.astype(np.float32).ravel()])
+
+
+def box_solve_reference(blob, b):
+    """float64 numpy restatement of G b on a box_solver_blob (b [Y, X])."""
+    hdr = blob[:FD_HEADER].view(np.int32)
+    assert hdr[0] == FD_MAGIC and hdr[5] == 0
+    Y, X = int(hdr[1]), int(hdr[2])
+    o = FD_HEADER
+    Qy = blob[o:o + Y * Y].astype(np.float64).reshape(Y, Y); o += Y * Y
+    Qx = blob[o:o + X * X].astype(np.float64).reshape(X, X); o += X * X
+    il = blob[o:o + X * Y].astype(np.float64).reshape(X, Y).T
+    return Qy @ (((Qy @ b) @ Qx) * il) @ Qx
+
+
+def pcg_reference(active, blob, b, rtol=1e-6, atol=1e-9, max_iter=2000):
+    """float64 numpy restatement of the large-grid CG solve (csrc/karman_large_pcg.hip) of M x = b, M = scene_matrix(active), with
+    the empty-box preconditioner of `blob`; returns (x, iterations, converged)."""
+    act = (np.asarray(active, dtype=np.float64) != 0).astype(np.float64)
+    Y, X = act.shape
+    acc = np.pad(act, 1, mode="edge")
+    diag = np.maximum(acc[0:Y, 1:X + 1] + acc[2:Y + 2, 1:X + 1] + acc[1:Y + 1, 0:X] + acc[1:Y + 1, 2:X + 2], 1.0)
+
+    def apply_M(p):
+        pa = np.pad(p * act, 1)
+        return diag * p - act * (pa[2:, 1:-1] + pa[:-2, 1:-1] + pa[1:-1, 2:] + pa[1:-1, :-2])
+
+    b = np.asarray(b, dtype=np.float64)
+    x, r = np.zeros_like(b), b.copy()
+    bb = float((b * b).sum())
+    stop = max(rtol * rtol * bb, atol * atol)
+    if float((r * r).sum()) <= stop:
+        return x, 0, True
+    z = box_solve_reference(blob, r)
+    p, rz = z, float((r * z).sum())
+    for k in range(1, max_iter + 1):
+        q = apply_M(p)
+        al = rz / float((p * q).sum())
+        x, r = x + al * p, r - al * q
+        if float((r * r).sum()) <= stop:
+            return x, k, True
+        z = box_solve_reference(blob, r)
+        rz_new = float((r * z).sum())
+        p, rz = z + (rz_new / rz) * p, rz_new
+    return x, max_iter, False
+
+
 def direct_solve_reference(blob, b):
     """float64 numpy restatement of the device algorithm on the blob (used by the CPU tests)."""
     hdr = blob[:FD_HEADER].view(np.int32)

@@ -18,6 +18,40 @@ def logger(path=None):
     return log
 
 
+def add_scene_args(p):
+    """--obstacle / --obstacle-mask / --pressure-solver of the 2-D scripts (defaults: the reference's sphere, automatic solver)."""
+    p.add_argument("--obstacle", action="append", default=None, metavar="SPEC",
+                   help="obstacle in domain coordinates, repeatable: sphere:CY,CX,R | box:Y0:Y1,X0:X1 | none (default: sphere:50,50,10)")
+    p.add_argument("--obstacle-mask", default=None, metavar="FILE.npy", help="[Y, X] fluid mask (1 = fluid) for exactly this grid")
+    p.add_argument("--pressure-solver", default="auto", choices=("auto", "direct", "cg"), help="pressure solve of the solver step")
+
+
+def scene_from_args(params):
+    """scene_record of the scene flags, or None when neither flag is given."""
+    import numpy as np
+    from sol_amd import karman
+    if params["obstacle"] is not None and params["obstacle_mask"] is not None:
+        raise SystemExit("give --obstacle or --obstacle-mask, not both")
+    if params["obstacle_mask"] is not None:
+        return karman.scene_record(active=np.load(params["obstacle_mask"]))
+    if params["obstacle"] is not None:
+        try:
+            return karman.scene_record(obstacles=karman.parse_obstacles(params["obstacle"]))
+        except ValueError as e:
+            raise SystemExit(str(e))
+    return None
+
+
+def flow_kwargs(rec):
+    """KarmanFlow / GraphTrainer keywords of a scene_record (None: the default scene)."""
+    from sol_amd import karman
+    if rec is None:
+        return {}
+    if rec["active"] is not None:
+        return {"active": rec["active"]}
+    return {"obstacles": karman.parse_obstacles(rec["obstacles"]) if rec["obstacles"] else []}
+
+
 def select_gpu(gpu):
     """`--gpu` of the reference scripts sets CUDA_VISIBLE_DEVICES (karman_train.py:49).  Same here (HIP honours
     HIP_VISIBLE_DEVICES / CUDA_VISIBLE_DEVICES) when the process is not a rank of a launcher, which owns the device choice,

@@ -2,14 +2,15 @@
 """karman-2d data generation -- same flags as /root/reference/karman-2d/karman.py:33-47, the loop of
 :138-159 on the fused HIP solver step (one kernel launch per frame, state stays on the GPU).
 -r <= 64 runs the fused one-workgroup-per-simulation kernel; larger grids (the reference's 256x128 `-r 128`
-reference solutions, Makefile:19-28) run the forward-only multi-launch path with the direct pressure solver."""
+reference solutions, Makefile:19-28) run the forward-only multi-launch path: the direct pressure solver where the scene's blob builds,
+else the preconditioned CG.  --obstacle / --obstacle-mask choose the scene (recorded in params.pickle as "scene")."""
 import argparse
 import pickle
 
 import numpy as np
 import torch
 
-from _common import logger, select_gpu
+from _common import add_scene_args, flow_kwargs, logger, scene_from_args, select_gpu
 import sol_amd
 from sol_amd import ops, scene
 
@@ -29,13 +30,16 @@ def main(argv=None):
     p.add_argument("-d", "--scale", default=4, type=int, help="down-sampling scale of hires")
     p.add_argument("-l", "--len", default=100, type=int, help="length of the reference axis")
     p.add_argument("--seed", default=0, type=int, help="seed for random number generator")
+    add_scene_args(p)
     params = vars(p.parse_args(argv))
     select_gpu(params["gpu"])
     log = logger()
     res = params["res"]
     Y, X = 2 * res, res
     dom = sol_amd.Domain([Y, X], box=sol_amd.box[0:params["len"] * 2, 0:params["len"]])
-    sim = sol_amd.KarmanFlow()
+    rec = scene_from_args(params)
+    sim = sol_amd.KarmanFlow(pressure_solver=params["pressure_solver"], **flow_kwargs(rec))
+    params["scene"] = sim.scene()
     d0 = scene.downsample(scene.read_zipped_array(params["initdH"]), params["scale"]) if params["initdH"] else np.zeros((1, Y, X, 1))
     if params["initvH"]:
         vn = scene.downsample_staggered(scene.read_zipped_array(params["initvH"]), params["scale"])
@@ -51,7 +55,8 @@ def main(argv=None):
         logger(path + "/run.log")
         with open(path + "/params.pickle", "wb") as f:
             pickle.dump(params, f)
-    log.info(params)
+    log.info({k: v for k, v in params.items() if k != "scene"})
+    log.info("scene: %s" % sol_amd.karman.describe_scene(params["scene"]))
 
     def write(state, i):
         scene.scene_write(path, [state.density.data.cpu().numpy(), state.velocity.staggered_tensor().cpu().numpy()], ["dens", "velo"], i)
@@ -61,8 +66,15 @@ def main(argv=None):
     with torch.no_grad():
         for i in range(1, params["simsteps"]):
             st = sim.step(st, re=[params["re"]], res=res, velBCy=velBCy, velBCyMask=velBCyMask)
+            if i == 1:
+                log.info("pressure solver: %s" % sim.pressure_solver_used)
+            info = sim.solve_info
+            if "converged" in info and not bool(info["converged"].all()):
+                raise RuntimeError("step {}: the CG pressure solve did not converge within {} iterations (iterations {}); "
+                                   "the scene may be unsolvable (an enclosed fluid region?)".format(
+                                       i, sim._solver["cg_max_iter"], info["iterations"].tolist()))
             if i % 100 == 0:
-                log.info("Step {:06d}".format(i))
+                log.info("Step {:06d}".format(i) + (", CG iterations {}".format(info["iterations"].tolist()) if "converged" in info else ""))
             if params["skipsteps"] < i and path:
                 write(st, i)
     return path

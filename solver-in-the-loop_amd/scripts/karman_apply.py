@@ -8,7 +8,7 @@ import pickle
 import numpy as np
 import torch
 
-from _common import logger, select_gpu
+from _common import add_scene_args, flow_kwargs, logger, scene_from_args, select_gpu
 import sol_amd
 from sol_amd import ops, scene
 
@@ -26,6 +26,7 @@ def main(argv=None):
     p.add_argument("-o", "--output", default="/tmp/phiflow/run", help="path to an output directory")
     p.add_argument("--stats", default="/tmp/phiflow/data/dataStats.pickle", help="path to datastats")
     p.add_argument("--model", default="/tmp/phiflow/tf/model.pt", help="path to a trained model")
+    add_scene_args(p)
     params = vars(p.parse_args(argv))
     select_gpu(params["gpu"])
     log = logger()
@@ -46,13 +47,22 @@ def main(argv=None):
         pickle.dump(params, f)
     with open(params["stats"], "rb") as f:
         data_stats = pickle.load(f)
-    log.info(data_stats)
+    log.info({k: v for k, v in data_stats.items() if k != "scene"})
     model = sol_amd.ConvNet.load(params["model"])
     model.summary(print_fn=log.info)
-    sim = sol_amd.KarmanFlow()
+    # the scene: the one the model was trained on (dataStats "scene"), else the flags, else the reference's sphere
+    rec = data_stats.get("scene")
+    flags = scene_from_args(params)
+    if rec is not None and flags is not None and not sol_amd.karman.scenes_equal(rec, flags):
+        log.info("--obstacle / --obstacle-mask ignored: the model was trained on the scene of %s" % params["stats"])
+    rec = rec if rec is not None else flags
+    sim = sol_amd.KarmanFlow(**flow_kwargs(rec))
+    log.info("scene: %s" % sol_amd.karman.describe_scene(sim.scene()))
     active, inflow = sim.scene_arrays(dom)
     velBCy, velBCyMask = sol_amd.velocity_bc_masks(Y, X)
-    masks = ops.SceneMasks(active, inflow, velBCy.reshape(Y + 1, X), velBCyMask.reshape(Y + 1, X))
+    masks = ops.SceneMasks(active, inflow, velBCy.reshape(Y + 1, X), velBCyMask.reshape(Y + 1, X),
+                           pressure_solver=params["pressure_solver"])
+    log.info("pressure solver: %s" % masks.pressure_solver)
     ro = sol_amd.SolRollout(model, masks, 1, Y, X, dom.dx[1], data_stats["std"][1], data_stats["ext.std"][0])
     f = lambda a: torch.as_tensor(np.ascontiguousarray(a), dtype=torch.float32, device="cuda").contiguous()
     vy0, vx0 = scene.split_staggered(np.asarray(vn, dtype=np.float32))

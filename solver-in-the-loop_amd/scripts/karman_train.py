@@ -17,7 +17,7 @@ import time
 import numpy as np
 import torch
 
-from _common import logger, select_gpu
+from _common import add_scene_args, flow_kwargs, logger, scene_from_args, select_gpu
 import sol_amd
 from sol_amd import ops, scene
 
@@ -49,6 +49,7 @@ def main(argv=None):
     p.add_argument("--tf", default="/tmp/phiflow/tf", help="path to an output dir (model, logs, etc.)")
     p.add_argument("--host-feed", action="store_true", help="assemble every batch on the host and copy it (the reference's feed_dict path) "
                                                             "instead of gathering from the device-resident set")
+    add_scene_args(p)
     params = vars(p.parse_args(argv))
     select_gpu(params["gpu"])
     rank, world, local = sol_amd.dist.init_from_env()
@@ -70,6 +71,22 @@ def main(argv=None):
                                 skip_preprocessing=params["skip_ds"], scale=params["scale"])
     if params["only_ds"]:
         return None
+    # the scene: recorded by karman.py in every simulation's params.pickle (sets without the record: the default sphere); they
+    # must agree, and an explicit --obstacle / --obstacle-mask must agree with them
+    rec_set = None
+    for s in dataset.dataSims:
+        with open(s + "/params.pickle", "rb") as f:
+            r = pickle.load(f).get("scene") or sol_amd.karman.scene_record()
+        if rec_set is not None and not sol_amd.karman.scenes_equal(r, rec_set):
+            raise SystemExit("the simulations of the training set disagree on the scene: %s has %s, others %s"
+                             % (s, sol_amd.karman.describe_scene(r), sol_amd.karman.describe_scene(rec_set)))
+        rec_set = r
+    rec = scene_from_args(params)
+    if rec is not None and rec_set is not None and not sol_amd.karman.scenes_equal(rec, rec_set):
+        raise SystemExit("--obstacle / --obstacle-mask (%s) contradict the scene of the training set (%s)"
+                         % (sol_amd.karman.describe_scene(rec), sol_amd.karman.describe_scene(rec_set)))
+    rec = rec if rec is not None else rec_set
+    log.info("scene: %s" % sol_amd.karman.describe_scene(rec))
     if params["pretf"]:
         # karman_train.py:351-355: the supervised model's own input / output normalisation travels in stats.pickle next to it
         with open(os.path.dirname(params["pretf"]) + "/stats.pickle", "rb") as f:
@@ -87,10 +104,12 @@ def main(argv=None):
     dev = torch.device("cuda", local % torch.cuda.device_count())
     torch.cuda.set_device(dev)
     dom = sol_amd.Domain([Y, X], box=sol_amd.box[0:params["len"] * 2, 0:params["len"]])
-    simulator_lo = sol_amd.KarmanFlow()
+    simulator_lo = sol_amd.KarmanFlow(**flow_kwargs(rec))
     active, inflow = simulator_lo.scene_arrays(dom)
     velBCy, velBCyMask = sol_amd.velocity_bc_masks(Y, X)
-    masks = ops.SceneMasks(active, inflow, velBCy.reshape(Y + 1, X), velBCyMask.reshape(Y + 1, X), dev)
+    masks = ops.SceneMasks(active, inflow, velBCy.reshape(Y + 1, X), velBCyMask.reshape(Y + 1, X), dev,
+                           pressure_solver=params["pressure_solver"])
+    log.info("pressure solver: %s" % masks.pressure_solver)
     # eval('model_'+params['model']) (karman_train.py:394): mars_moon runs the C++ schedule (SolTrainer), mercury the
     # autograd composition of the same ops captured into a hipGraph (GraphTrainer)
     assert params["model"] in sol_amd.model.MODELS, "unknown model %r (have: %s)" % (params["model"], ", ".join(sol_amd.model.MODELS))
@@ -103,6 +122,7 @@ def main(argv=None):
         log.info("load an initial model (warm start): {}".format(params["inittf"]))
         model.set_weights(sol_amd.ConvNet.load(params["inittf"], device="cpu").get_weights())
     os.makedirs(params["tf"], exist_ok=True)
+    dataset.dataStats.setdefault("scene", rec)
     if params["resume"] < 1:
         if rank == 0:
             with open(params["tf"] + "/dataStats.pickle", "wb") as f:
@@ -114,7 +134,8 @@ def main(argv=None):
     trainer = sol_amd.make_trainer(model, masks, Bl, Y, X, ms, dom.dx[1], std_v, dataset.dataStats["ext.std"][0],
                                  clip_grad=params["clip_grad"],
                                  in_std_v=dataset.dataStats["in.std"][1] if "in.std" in dataset.dataStats else None,
-                                 out_std_v=dataset.dataStats["out.std"] if "out.std" in dataset.dataStats else None)
+                                 out_std_v=dataset.dataStats["out.std"] if "out.std" in dataset.dataStats else None,
+                                 pressure_solver=params["pressure_solver"], **flow_kwargs(rec))
     # persistent device buffers: the captured hipGraph keeps their addresses, new data is copied in
     f32 = lambda shape: torch.empty(shape, dtype=torch.float32, device=dev)
     d0, vy0, vx0, re = f32((Bl, Y, X)), f32((Bl, Y + 1, X)), f32((Bl, Y, X + 1)), f32((Bl,))

@@ -253,11 +253,12 @@ class GraphTrainer:
     def __init__(self, net, B, Y, X, msteps, std_v, std_re, res=None, clip_grad=False, beta1=0.9, beta2=0.999, eps=1e-8,
                  group=None, use_graph=True, comm=None, in_std_v=None, out_std_v=None, pressure_solver=None,
                  dx=None, dt=1.0, masks=None, cg_rtol=1e-6, cg_atol=1e-9, cg_max_iter=2000, grad_pad="replicate",
-                 inflow_order="after", conv_precision="split", schedule="manual"):
+                 inflow_order="after", conv_precision="split", schedule="manual", obstacles=None, active=None):
         """dx: cell size (default 100 / X, the reference's `--len 100`); the domain is box[0:Y*dx, 0:X*dx] as the scripts
-        build it (karman_train.py:363: box[0:len*2, 0:len]).  masks: optional SceneMasks of the caller -- its boundary
-        arrays are used; its scene must be the one KarmanFlow derives from the domain (checked).  The solver options are
-        those of SolTrainer and are forwarded to KarmanFlow.  schedule: "manual" | "autograd" (see the class docstring)."""
+        build it (karman_train.py:363: box[0:len*2, 0:len]).  obstacles / active: the scene of KarmanFlow (default: the reference's
+        sphere).  masks: optional SceneMasks of the caller -- its boundary arrays are used; its scene must be the one KarmanFlow
+        derives from the domain and the obstacles (checked).  The solver options are those of SolTrainer and are forwarded to
+        KarmanFlow.  schedule: "manual" | "autograd" (see the class docstring)."""
         if schedule not in ("manual", "autograd"):
             raise ValueError("schedule must be 'manual' or 'autograd'")
         self.schedule = schedule
@@ -272,15 +273,15 @@ class GraphTrainer:
         self.dt = float(dt)
         self.dom = fluid.Domain([Y, X], box=fluid.box[0:Y * dx, 0:X * dx])
         self.sim = karman.KarmanFlow(pressure_solver=pressure_solver, cg_rtol=cg_rtol, cg_atol=cg_atol, cg_max_iter=cg_max_iter,
-                                     grad_pad=grad_pad, inflow_order=inflow_order)
+                                     grad_pad=grad_pad, inflow_order=inflow_order, obstacles=obstacles, active=active)
         self.res = X if res is None else res
         if masks is not None:
             import numpy as np
             active, inflow = self.sim.scene_arrays(self.dom)
             if not (np.array_equal(masks.active.reshape(Y, X).cpu().numpy(), active.astype(np.float32)) and
                     np.array_equal(masks.inflow.reshape(Y, X).cpu().numpy(), inflow.astype(np.float32))):
-                raise ValueError("GraphTrainer composes KarmanFlow.step, whose scene (inflow box, sphere) follows from the domain; "
-                                 "the given masks describe a different scene")
+                raise ValueError("GraphTrainer composes KarmanFlow.step, whose scene (inflow box, obstacles) follows from the domain "
+                                 "and the obstacles / active arguments; the given masks describe a different scene")
             self.bcv = masks.velBCy.reshape(-1, Y + 1, X, 1).cpu().numpy()
             self.bcm = masks.velBCyMask.reshape(-1, Y + 1, X, 1).cpu().numpy()
         else:
@@ -428,5 +429,9 @@ class GraphTrainer:
 def make_trainer(net, masks, B, Y, X, msteps, dx, std_v, std_re, **kw):
     """SolTrainer (the C++ schedule: model_mars_moon) or GraphTrainer (autograd composition in a hipGraph: everything else)."""
     if net.name == "mars_moon":
+        # the C++ schedule takes its scene and its pressure solver from `masks` alone (obstacles / active / pressure_solver
+        # describe them for GraphTrainer's KarmanFlow)
+        for k in ("obstacles", "active", "pressure_solver"):
+            kw.pop(k, None)
         return SolTrainer(net, masks, B, Y, X, msteps, dx, std_v, std_re, **kw)
     return GraphTrainer(net, B, Y, X, msteps, std_v, std_re, dx=dx, masks=masks, **kw)     # unknown keywords raise TypeError
