@@ -35,7 +35,7 @@ int sol_bww_batched_reduce(void* stream, const float* partial, float* dw_hwio, f
 // C[b] (M x N) = (accumulate ? C[b] : 0) + A[b] (M x K) * B[b] (K x N), row major, fp32, batch strides may be 0 (karman_large.hip)
 int sol_gemm_f32(hipStream_t s, int batch, const float* A, int lda, long sA, const float* Bm, int ldb, long sB, float* C, int ldc, long sC,
                  int M, int N, int K, int accumulate);
-// karman-2d large-grid step (karman_large.hip), shared by its direct and its CG pressure solve (karman_large_pcg.hip): the step's
+// karman-2d large-grid step (karman_large.hip), shared by its direct and its CG pressure solve (pcg.hip): the step's
 // arguments; diffuse / advect / rhs = -div (front) and v -= mask grad p (+ features) around the solve; the empty-box solve G = M_r^-1
 // of the blob's sine transforms in two halves, T2 = ((Qy src) Qx) / lam and dst = Qy (T2 Qx) (skip = per-simulation done words or NULL:
 // every launch of a finished simulation returns at once)
@@ -50,7 +50,7 @@ int sol_large_project(const sol_karman_cfg* c, hipStream_t s, const SolLargeStep
 int sol_large_box_forward(hipStream_t s, int B, int Y, int X, const float* blob, const float* src, float* T1, float* T2, const int* skip);
 int sol_large_box_back(hipStream_t s, int B, int Y, int X, const float* blob, const float* T2, float* T1, float* dst, const int* skip);
 
-// karman-3d pressure solvers (karman3d.hip / karman3d_pcg.hip): dst = G src with G = the empty-box solve on the blob of cfg->direct
+// karman-3d pressure solvers (karman3d.hip / pcg.hip): dst = G src with G = the empty-box solve on the blob of cfg->direct
 // (*res = t1 or t2, whichever holds dst; skip = per-simulation done words [B] or NULL); the preconditioned CG solve M x = b (b is
 // overwritten with the residual; *x_out = the solution; active = the [Y,X,Z] mask) in the workspace of k3_pcg_workspace_bytes
 int k3_apply_G(hipStream_t s, const sol_karman3d_cfg* c, const float* src, float* t1, float* t2, float** res_out, const int* skip);

@@ -357,7 +357,7 @@ __global__ void __launch_bounds__(256) k3_project(K3Args a) {
     }
 }
 
-// skip / nskip: the preconditioned CG solve (karman3d_pcg.hip) hands in its per-simulation done words -- a transform launched after
+// skip / nskip: the preconditioned CG solve (pcg.hip) hands in its per-simulation done words -- a transform launched after
 // every simulation has converged returns at once (the launch sequence is fixed so that it captures); the direct solve passes NULL
 __device__ __forceinline__ bool k3_all_done(const int* skip, int nskip) {
     if (!skip) return false;
@@ -670,7 +670,7 @@ int grid_for(size_t n) { const size_t g = (n + 255) / 256; return (int)(g < 1 ? 
 }  // namespace
 
 // ---- the empty-box solve G = M_r^-1 (three sine transforms each way + the 1/eigenvalue scaling) on the blob's matrices: the direct
-// solve applies it twice around the capacitance correction, the preconditioned CG solve (karman3d_pcg.hip) once per iteration.
+// solve applies it twice around the capacitance correction, the preconditioned CG solve (pcg.hip) once per iteration.
 // dst = G src (src preserved); *res_out = the buffer (t1 or t2) that holds dst.  skip: per-simulation done words [B] or NULL.
 int k3_apply_G(hipStream_t s, const sol_karman3d_cfg* c, const float* src, float* t1, float* t2, float** res_out, const int* skip) {
     const int B = c->B, Y = c->Y, X = c->X, Z = c->Z, N = Y * X * Z;

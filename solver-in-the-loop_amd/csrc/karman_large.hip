@@ -283,7 +283,7 @@ int sol_gemm_f32(hipStream_t s, int batch, const float* A, int lda, long sA, con
     return gemm(s, batch, A, lda, sA, Bm, ldb, sB, C, ldc, sC, M, N, K, accumulate);
 }
 
-// ---- the stencil phases around the pressure solve (shared with karman_large_pcg.hip) ----
+// ---- the stencil phases around the pressure solve (shared with pcg.hip) ----
 int sol_large_front(const sol_karman_cfg* c, hipStream_t s, const SolLargeStep& io, float* svy, float* svx, float* rhs) {
     const LArgs a = large_args(c, io, svy, svx, rhs, nullptr);
     const int B = c->B, N = c->Y * c->X, faces = (c->Y + 1) * c->X + c->Y * (c->X + 1);

@@ -1,0 +1,407 @@
+// Preconditioned conjugate-gradient pressure solve for any obstacle mask: one engine, two users -- karman-3d (cfg.pressure_solver = 1,
+// DESIGN 4.8) and the karman-2d large grids.
+//
+// The system is the one the direct solves (karman3d.hip, karman_large.hip) invert: M p = b with M = -A, PhiFlow's pressure matrix --
+// diagonal = max(number of accessible neighbours, 1) with edge padding (a neighbour outside the box counts as the cell itself, p = 0
+// there), -active_c active_n between neighbours, obstacle rows decoupled (precond.scene_matrix, precond3d._accessible_diag).  CG on M
+// preconditioned with the empty-box solve G = M_r^-1 (the sine transforms of a blob with nS = 0: k3_apply_G in 3-D,
+// sol_large_box_forward / _back in 2-D), i.e. oracle/sol_oracle3d.solve_pcg / precond.pcg_reference in fp32 with fp64 dot products.
+//
+// Launch structure (pcg_run):
+//   pcg_init                      x = 0, r = b (in place), per-workgroup partials of |b|^2, done = 0, ndone = 0
+//   G, pcg_dot                    z = G r, convergence test, partials of <r, z>
+//   cg_max_iter x [ pcg_stencil   p = z + beta p (into the other p buffer), q = M p, partials of <p, q>
+//                   pcg_update    alpha = <r, z> / <p, q>, x += alpha p, r -= alpha q, partials of |r|^2
+//                   G, pcg_dot ]  (the last iteration: pcg_dot as the convergence test only)
+// Only pcg_stencil depends on the dimension: its Grid type decomposes the cell index and visits the neighbours in a fixed order
+// (2-D j-, j+, i-, i+; 3-D j-, j+, i-, i+, k-, k+), which fixes the fp32 sums.  Every dot product is a slab of per-workgroup fp64
+// partials [B][nwg <= 512] that the NEXT kernel sums in a fixed order in every one of its workgroups (no float atomics: the solve is
+// bit-reproducible).  pcg_dot stops a simulation when the recursively updated |r|_2 <= max(cg_rtol |b|_2, cg_atol): it sets the
+// simulation's done word and counts it in ndone, after which its x, r and p are frozen and every per-simulation kernel returns at once
+// (so do the transforms of G that read the done words).  The iterations used and the converged flag go to cg_info at
+// info[b * info_stride] and info[b * info_stride + info_conv]: [B][2] in 3-D, [2][B] in 2-D.
+//
+// The launch sequence is fixed and never synchronises with the host under capture (hipStreamIsCapturing): a trainer or roll-out graph
+// captures the full cg_max_iter budget.  The ONE synchronising case: with poll_every > 0 (the 2-D user: 16), an EAGER call reads ndone
+// back to the host every poll_every iterations and stops issuing iterations once all B simulations are done -- data generation runs
+// thousands of eager steps with the PhiFlow budget of 2000.  The results do not depend on where it stops: a finished simulation's state
+// is frozen either way.  The 3-D user passes 0 and always issues the full budget.
+#include "common.hpp"
+
+namespace {
+
+constexpr int PCG_T = 256;          // threads per workgroup
+constexpr int PCG_MAXWG = 512;      // workgroups per simulation (= partials per slab row)
+constexpr int FDL_MAGIC = 0x46443032;
+
+int pcg_nwg(size_t N) { const size_t g = (N + PCG_T - 1) / PCG_T; return (int)(g < (size_t)PCG_MAXWG ? g : (size_t)PCG_MAXWG); }
+
+struct PcgArgs {
+    int B, N, nwg;
+    int info_stride, info_conv;     // cg_info layout (see above)
+    float rtol, atol;
+    const float* active;
+    float *x, *r, *q, *p[2];
+    double *bb, *rr, *pq, *rz[2];   // slabs [B][nwg]
+    int* done;                      // [B]
+    int* ndone;                     // [1]: simulations finished so far
+    int* info;
+};
+
+// cell(c): the index decomposition, taken before the cell's loads (that order keeps the loads' latency behind the integer
+// divisions); neighbours: the visit in the fixed order
+struct Grid2 {
+    int Y, X;
+    struct Cell { int j, i; };
+    __device__ __forceinline__ Cell cell(int c) const { const int j = c / X; return {j, c - j * X}; }
+    template <class F> __device__ __forceinline__ void neighbours(Cell p, int c, F&& nb) const {
+        nb(p.j > 0, c - X); nb(p.j + 1 < Y, c + X);
+        nb(p.i > 0, c - 1); nb(p.i + 1 < X, c + 1);
+    }
+};
+
+struct Grid3 {
+    int Y, X, Z;
+    struct Cell { int j, i, k; };
+    __device__ __forceinline__ Cell cell(int c) const { const int k = c % Z, i = (c / Z) % X, j = c / (X * Z); return {j, i, k}; }
+    template <class F> __device__ __forceinline__ void neighbours(Cell p, int c, F&& nb) const {
+        const int XZ = X * Z;
+        nb(p.j > 0, c - XZ); nb(p.j + 1 < Y, c + XZ);
+        nb(p.i > 0, c - Z);  nb(p.i + 1 < X, c + Z);
+        nb(p.k > 0, c - 1);  nb(p.k + 1 < Z, c + 1);
+    }
+};
+
+// sum of v over the workgroup, the same fixed order every run; the result is valid in every thread
+__device__ double pcg_block_sum(double v) {
+    __shared__ double red[PCG_T / 64];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    __syncthreads();                                // (a previous call's readers are done with red)
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double t = 0.0;
+#pragma unroll
+    for (int w = 0; w < PCG_T / 64; ++w) t += red[w];
+    return t;
+}
+
+__device__ double pcg_slab_sum(const double* row, int n) {
+    double v = 0.0;
+    for (int k = threadIdx.x; k < n; k += PCG_T) v += row[k];
+    return pcg_block_sum(v);
+}
+
+__device__ __forceinline__ void pcg_publish(double* slab, int nwg, double part) {
+    const double t = pcg_block_sum(part);
+    if (threadIdx.x == 0) slab[(size_t)blockIdx.y * nwg + blockIdx.x] = t;
+}
+
+__global__ void __launch_bounds__(PCG_T) pcg_init(PcgArgs a) {
+    const int b = blockIdx.y;
+    const size_t o = (size_t)b * a.N;
+    double acc = 0.0;
+    for (int c = blockIdx.x * PCG_T + threadIdx.x; c < a.N; c += a.nwg * PCG_T) {
+        const float v = a.r[o + c];
+        a.x[o + c] = 0.f;
+        acc += (double)v * v;
+    }
+    const double t = pcg_block_sum(acc);
+    if (threadIdx.x == 0) {
+        a.bb[(size_t)b * a.nwg + blockIdx.x] = t;
+        a.rr[(size_t)b * a.nwg + blockIdx.x] = t;
+        if (blockIdx.x == 0) a.done[b] = 0;
+        if (blockIdx.x == 0 && b == 0) *a.ndone = 0;
+    }
+}
+
+// p_new = z + beta p_old (beta = rz_cur / rz_prev; first: p_new = z), q = M p_new, partials of <p_new, q>
+template <class Grid>
+__global__ void __launch_bounds__(PCG_T) pcg_stencil(PcgArgs a, Grid g, const float* __restrict__ z, const float* __restrict__ pold,
+                                                      float* __restrict__ pnew, const double* __restrict__ rzc,
+                                                      const double* __restrict__ rzp, int first) {
+    const int b = blockIdx.y;
+    if (a.done[b]) return;
+    float beta = 0.f;
+    if (!first) {
+        const double cur = pcg_slab_sum(rzc + (size_t)b * a.nwg, a.nwg), prev = pcg_slab_sum(rzp + (size_t)b * a.nwg, a.nwg);
+        beta = (float)(cur / fmax(prev, 1e-300));
+    }
+    const size_t o = (size_t)b * a.N;
+    const float* zb = z + o;
+    const float* pb = pold + o;
+    auto pn = [&](int e) { return first ? zb[e] : fmaf(beta, pb[e], zb[e]); };
+    auto act = [&](int e) { return a.active[e] != 0.f ? 1.f : 0.f; };
+    double acc = 0.0;
+    for (int c = blockIdx.x * PCG_T + threadIdx.x; c < a.N; c += a.nwg * PCG_T) {
+        const typename Grid::Cell at = g.cell(c);
+        const float ac = act(c), pc = pn(c);
+        float n = 0.f, s = 0.f;
+        g.neighbours(at, c, [&](bool inside, int e) {
+            if (inside) { const float an = act(e); n += an; s += an * pn(e); }
+            else n += ac;                           // outside the box: accessible iff the cell is (edge padding), p = 0 there
+        });
+        const float qv = fmaxf(n, 1.f) * pc - ac * s;
+        pnew[o + c] = pc;
+        a.q[o + c] = qv;
+        acc += (double)pc * qv;
+    }
+    pcg_publish(a.pq, a.nwg, acc);
+}
+
+// alpha = <r, z> / <p, q>;  x += alpha p;  r -= alpha q;  partials of |r|^2
+__global__ void __launch_bounds__(PCG_T) pcg_update(PcgArgs a, const float* __restrict__ p, const double* __restrict__ rzc) {
+    const int b = blockIdx.y;
+    if (a.done[b]) return;
+    const double rz = pcg_slab_sum(rzc + (size_t)b * a.nwg, a.nwg), pq = pcg_slab_sum(a.pq + (size_t)b * a.nwg, a.nwg);
+    const float al = (float)(rz / fmax(pq, 1e-300));
+    const size_t o = (size_t)b * a.N;
+    double acc = 0.0;
+    for (int c = blockIdx.x * PCG_T + threadIdx.x; c < a.N; c += a.nwg * PCG_T) {
+        a.x[o + c] = fmaf(al, p[o + c], a.x[o + c]);
+        const float r = fmaf(-al, a.q[o + c], a.r[o + c]);
+        a.r[o + c] = r;
+        acc += (double)r * r;
+    }
+    pcg_publish(a.rr, a.nwg, acc);
+}
+
+// convergence test after `iter` updates (every workgroup of the simulation takes the same decision from the same slabs; the
+// first one records it and counts the simulation as finished), then the partials of <r, z> unless the simulation stopped or this
+// is the last iteration (z == NULL)
+__global__ void __launch_bounds__(PCG_T) pcg_dot(PcgArgs a, const float* __restrict__ z, double* __restrict__ rz, int iter) {
+    const int b = blockIdx.y;
+    if (a.done[b]) return;
+    const double bb = pcg_slab_sum(a.bb + (size_t)b * a.nwg, a.nwg), rr = pcg_slab_sum(a.rr + (size_t)b * a.nwg, a.nwg);
+    const double rt = (double)a.rtol, at = (double)a.atol;
+    const bool conv = rr <= fmax(rt * rt * bb, at * at);
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        a.info[b * a.info_stride] = iter;
+        a.info[b * a.info_stride + a.info_conv] = conv ? 1 : 0;
+        if (conv) { a.done[b] = 1; atomicAdd(a.ndone, 1); }
+    }
+    if (conv || !z) return;
+    const size_t o = (size_t)b * a.N;
+    double acc = 0.0;
+    for (int c = blockIdx.x * PCG_T + threadIdx.x; c < a.N; c += a.nwg * PCG_T) acc += (double)a.r[o + c] * z[o + c];
+    pcg_publish(rz, a.nwg, acc);
+}
+
+// bump allocator over a caller's workspace (ws == NULL: sizes only); every buffer starts on 256 bytes
+struct Carve {
+    char* w;
+    size_t off = 0;
+    explicit Carve(void* ws) : w(ws ? reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(ws) + 255) / 256 * 256) : nullptr) {}
+    template <class T> T* take(size_t n) { T* p = w ? reinterpret_cast<T*>(w + off) : nullptr; off += (n * sizeof(T) + 255) / 256 * 256; return p; }
+    size_t bytes() const { return off + 256; }     // + the alignment of the caller's pointer
+};
+
+// the CG buffers: slabs, done words, x, the two p buffers, q (the caller sets r, active, info and the tolerances)
+PcgArgs pcg_carve(Carve& w, size_t B, size_t N) {
+    PcgArgs a{};
+    a.B = (int)B; a.N = (int)N; a.nwg = pcg_nwg(N);
+    a.bb = w.take<double>(B * a.nwg);
+    a.rr = w.take<double>(B * a.nwg);
+    a.pq = w.take<double>(B * a.nwg);
+    a.rz[0] = w.take<double>(B * a.nwg);
+    a.rz[1] = w.take<double>(B * a.nwg);
+    a.done = w.take<int>(B);
+    a.ndone = w.take<int>(1);
+    a.x = w.take<float>(B * N);
+    a.p[0] = w.take<float>(B * N);
+    a.p[1] = w.take<float>(B * N);
+    a.q = w.take<float>(B * N);
+    return a;
+}
+
+// M x = b by PCG (b = a.r is overwritten with the residual, x = a.x); apply_G(&z) applies G to a.r and points z at the result
+template <class Grid, class ApplyG>
+int pcg_run(hipStream_t s, const PcgArgs& a, Grid g, int K, int poll_every, ApplyG&& apply_G) {
+    bool poll = false;
+    if (poll_every > 0) {
+        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+        SOL_HIP_CHECK(hipStreamIsCapturing(s, &cap));
+        poll = cap == hipStreamCaptureStatusNone;
+    }
+    const dim3 grid(a.nwg, a.B), blk(PCG_T);
+    float* z = nullptr;
+    SOL_LAUNCH(pcg_init, grid, blk, 0, s, a);
+    if (int e = apply_G(&z)) return e;
+    SOL_LAUNCH(pcg_dot, grid, blk, 0, s, a, (const float*)z, a.rz[0], 0);
+    for (int k = 1; k <= K; ++k) {
+        SOL_LAUNCH(pcg_stencil<Grid>, grid, blk, 0, s, a, g, (const float*)z, (const float*)a.p[(k - 1) & 1], a.p[k & 1],
+                   (const double*)a.rz[(k - 1) & 1], (const double*)a.rz[k & 1], k == 1 ? 1 : 0);
+        SOL_LAUNCH(pcg_update, grid, blk, 0, s, a, (const float*)a.p[k & 1], (const double*)a.rz[(k - 1) & 1]);
+        if (k < K) {
+            if (int e = apply_G(&z)) return e;
+            SOL_LAUNCH(pcg_dot, grid, blk, 0, s, a, (const float*)z, a.rz[k & 1], k);
+        } else {
+            SOL_LAUNCH(pcg_dot, grid, blk, 0, s, a, (const float*)nullptr, (double*)nullptr, k);
+        }
+        if (poll && k < K && k % poll_every == 0) {
+            SOL_LAUNCH_CHECK();
+            int finished = 0;
+            SOL_HIP_CHECK(hipMemcpyAsync(&finished, a.ndone, sizeof(int), hipMemcpyDeviceToHost, s));
+            SOL_HIP_CHECK(hipStreamSynchronize(s));
+            if (finished >= a.B) break;
+        }
+    }
+    SOL_LAUNCH_CHECK();
+    return SOL_OK;
+}
+
+// ---- karman-3d: the CG buffers, then the cg_info fallback [B][2] (cfg.cg_info NULL) ----
+PcgArgs k3_layout(const sol_karman3d_cfg* c, void* ws, size_t* bytes = nullptr) {
+    Carve w(ws);
+    PcgArgs a = pcg_carve(w, c->B, (size_t)c->Y * c->X * c->Z);
+    int* info = w.take<int>(2 * (size_t)c->B);
+    a.info = c->cg_info ? c->cg_info : info;
+    a.info_stride = 2; a.info_conv = 1;
+    a.rtol = c->cg_rtol; a.atol = c->cg_atol;
+    if (bytes) *bytes = w.bytes();
+    return a;
+}
+
+// ---- karman-2d large grids: the step's buffers (sv_y, sv_x, rhs / residual, two transform buffers), the CG buffers, then z ----
+struct Large {
+    float *svy, *svx, *T1, *T2, *z;
+    PcgArgs a;
+    size_t bytes;
+};
+
+Large large_layout(const sol_karman_cfg* c, void* ws) {
+    const size_t B = c->B, Y = c->Y, X = c->X, N = Y * X;
+    Carve w(ws);
+    Large l{};
+    l.svy = w.take<float>(B * (Y + 1) * X);
+    l.svx = w.take<float>(B * Y * (X + 1));
+    float* R = w.take<float>(B * N);
+    l.T1 = w.take<float>(B * N);
+    l.T2 = w.take<float>(B * N);
+    l.a = pcg_carve(w, B, N);
+    l.z = w.take<float>(B * N);
+    l.a.r = R;
+    l.a.info_stride = 1; l.a.info_conv = c->B;
+    l.a.rtol = c->cg_rtol; l.a.atol = c->cg_atol;
+    l.bytes = w.bytes();
+    return l;
+}
+
+// checks shared by the two entry points (before any launch)
+int large_check(const sol_karman_cfg* c, const char* who, const float* box_blob, const int32_t* hdr, const int32_t* cg_info,
+                const void* workspace, size_t workspace_bytes) {
+    SOL_REQUIRE(c != nullptr, "cfg is NULL");
+    SOL_REQUIRE(c->B >= 1 && c->B <= 65535 && c->Y >= 16 && c->X >= 16, "%s: B in [1, 65535], Y, X >= 16 (got %d, %d, %d)", who, c->B, c->Y, c->X);
+    SOL_REQUIRE((size_t)c->Y * c->X < ((size_t)1 << 30), "%s: grid too large", who);
+    SOL_REQUIRE(box_blob && hdr && cg_info && workspace, "%s: NULL pointer argument (box blob, its host header, cg_info and workspace are required)", who);
+    SOL_REQUIRE(c->cg_max_iter >= 1, "%s: cfg.cg_max_iter must be >= 1, got %d", who, c->cg_max_iter);
+    SOL_REQUIRE(c->cg_rtol >= 0.f && c->cg_rtol < INFINITY && c->cg_atol >= 0.f && c->cg_atol < INFINITY,
+                "%s: cfg.cg_rtol and cfg.cg_atol must be >= 0 and finite, got %g, %g", who, (double)c->cg_rtol, (double)c->cg_atol);
+    SOL_REQUIRE(c->cg_rtol > 0.f || c->cg_atol > 0.f, "%s: cfg.cg_rtol and cfg.cg_atol are both zero (the solve could never stop)", who);
+    SOL_REQUIRE(hdr[0] == FDL_MAGIC, "%s: box_header_host must be the first 16 words of the blob (host copy)", who);
+    SOL_REQUIRE(hdr[1] == c->Y && hdr[2] == c->X, "%s: the box blob is for a %dx%d grid, cfg is %dx%d", who, hdr[1], hdr[2], c->Y, c->X);
+    SOL_REQUIRE(hdr[5] == 0 && hdr[6] == 0, "%s: the CG solve needs the empty-box blob (nS = 0: precond.box_solver_blob), this one has nS = %d",
+                who, hdr[5]);
+    SOL_REQUIRE(workspace_bytes >= large_layout(c, nullptr).bytes, "%s: workspace too small (%zu < %zu bytes)", who, workspace_bytes,
+                large_layout(c, nullptr).bytes);
+    return SOL_OK;
+}
+
+// M x = b by PCG; b (= l.a.r) is overwritten with the residual
+int large_solve(hipStream_t s, const sol_karman_cfg* c, const float* blob, const float* active, const Large& l, int32_t* info) {
+    const int B = c->B, Y = c->Y, X = c->X;
+    PcgArgs a = l.a;
+    a.active = active;
+    a.info = info;
+    auto apply_G = [&](float** z) -> int {
+        *z = l.z;
+        if (int e = sol_large_box_forward(s, B, Y, X, blob, a.r, l.T1, l.T2, a.done)) return e;
+        return sol_large_box_back(s, B, Y, X, blob, l.T2, l.T1, l.z, a.done);
+    };
+    return pcg_run(s, a, Grid2{Y, X}, c->cg_max_iter, 16, apply_G);
+}
+
+__global__ void __launch_bounds__(PCG_T) large_copy(float* __restrict__ dst, const float* __restrict__ src, size_t n) {
+    for (size_t e = (size_t)blockIdx.x * PCG_T + threadIdx.x; e < n; e += (size_t)gridDim.x * PCG_T) dst[e] = src[e];
+}
+
+}  // namespace
+
+size_t k3_pcg_workspace_bytes(const sol_karman3d_cfg* c) {
+    size_t bytes = 0;
+    if (c && c->pressure_solver == 1) k3_layout(c, nullptr, &bytes);
+    return bytes;
+}
+
+// the solver fields of the cfg against the blob header (shared by the forward and the adjoint entry points)
+int k3_pcg_check(const sol_karman3d_cfg* c, const int32_t* hdr) {
+    SOL_REQUIRE(c->pressure_solver == 0 || c->pressure_solver == 1, "cfg.pressure_solver must be 0 (direct) or 1 (preconditioned CG), got %d", c->pressure_solver);
+    if (c->pressure_solver == 0) return SOL_OK;       // the direct solve takes any valid blob (nS = 0: the empty box)
+    SOL_REQUIRE(hdr[4] == 0, "the preconditioned CG solve (pressure_solver = 1) needs the blob without capacitance part (nS = 0: "
+                "precond3d.direct_solver_blob3d(np.ones_like(active))), this one has nS = %d", hdr[4]);
+    SOL_REQUIRE(c->cg_max_iter >= 1, "cfg.cg_max_iter must be >= 1 for the CG solve, got %d", c->cg_max_iter);
+    SOL_REQUIRE(c->cg_rtol > 0.f && c->cg_rtol < INFINITY, "cfg.cg_rtol must be > 0 (and finite), got %g", (double)c->cg_rtol);
+    SOL_REQUIRE(c->cg_atol >= 0.f && c->cg_atol < INFINITY, "cfg.cg_atol must be >= 0 (and finite), got %g", (double)c->cg_atol);
+    return SOL_OK;
+}
+
+int k3_pcg_solve(hipStream_t s, const sol_karman3d_cfg* c, const float* active, float* b, float* t1, float* t2, void* ws, float** x_out) {
+    PcgArgs a = k3_layout(c, ws);
+    a.active = active;
+    a.r = b;
+    auto apply_G = [&](float** z) { return k3_apply_G(s, c, b, t1, t2, z, a.done); };
+    if (int e = pcg_run(s, a, Grid3{c->Y, c->X, c->Z}, c->cg_max_iter, 0, apply_G)) return e;
+    *x_out = a.x;
+    return SOL_OK;
+}
+
+extern "C" size_t sol_karman_step_large_cg_workspace_bytes(const sol_karman_cfg* c) {
+    if (!c || c->B < 1 || c->Y < 1 || c->X < 1) return 0;
+    return large_layout(c, nullptr).bytes;
+}
+
+extern "C" int sol_karman_step_fwd_large_cg(const sol_karman_cfg* c, void* stream,
+                                            const float* d_in, const float* vy_in, const float* vx_in,
+                                            const float* re, const float* active, const float* inflow,
+                                            const float* velBCy, const float* velBCyMask, int64_t bc_batch_stride,
+                                            float* d_out, float* vy_out, float* vx_out,
+                                            float* feat_out, const float* feat_scale,
+                                            const float* box_blob, const int32_t* box_header_host, int32_t* cg_info,
+                                            void* workspace, size_t workspace_bytes) {
+    const char* who = "sol_karman_step_fwd_large_cg";
+    if (int e = large_check(c, who, box_blob, box_header_host, cg_info, workspace, workspace_bytes)) return e;
+    SOL_REQUIRE(vy_in && vx_in && re && active && velBCy && velBCyMask && vy_out && vx_out, "%s: NULL pointer argument", who);
+    SOL_REQUIRE((d_in && inflow) || !d_out, "%s: density output requested without d_in / inflow", who);
+    SOL_REQUIRE(!feat_out || feat_scale, "%s: feat_out requires feat_scale", who);
+    SOL_REQUIRE(vy_in != vy_out && vx_in != vx_out && (d_in != d_out || !d_out), "%s: outputs must not alias the inputs", who);
+    const void* outs[] = {d_out, vy_out, vx_out, feat_out, cg_info};
+    const void* ins[] = {d_in, vy_in, vx_in, re, active, inflow, velBCy, velBCyMask, box_blob};
+    for (const void* o : outs)
+        for (const void* i : ins) SOL_REQUIRE(!o || o != i, "%s: outputs must not alias the inputs", who);
+    hipStream_t s = (hipStream_t)stream;
+    const Large l = large_layout(c, workspace);
+    const SolLargeStep io{d_in, vy_in, vx_in, re, active, inflow, velBCy, velBCyMask, bc_batch_stride, d_out, vy_out, vx_out, feat_out, feat_scale};
+    if (int e = sol_large_front(c, s, io, l.svy, l.svx, l.a.r)) return e;
+    if (int e = large_solve(s, c, box_blob, active, l, cg_info)) return e;
+    return sol_large_project(c, s, io, l.a.x);
+}
+
+extern "C" int sol_karman_pressure_solve_large(const sol_karman_cfg* c, void* stream, const float* active, const float* rhs, float* p,
+                                               const float* box_blob, const int32_t* box_header_host, int32_t* cg_info,
+                                               void* workspace, size_t workspace_bytes) {
+    const char* who = "sol_karman_pressure_solve_large";
+    if (int e = large_check(c, who, box_blob, box_header_host, cg_info, workspace, workspace_bytes)) return e;
+    SOL_REQUIRE(active && rhs && p, "%s: NULL pointer argument", who);
+    SOL_REQUIRE(p != rhs && p != active && p != box_blob && (const void*)cg_info != rhs && (const void*)cg_info != active,
+                "%s: outputs must not alias the inputs", who);
+    hipStream_t s = (hipStream_t)stream;
+    const Large l = large_layout(c, workspace);
+    const size_t n = (size_t)c->B * c->Y * c->X;
+    const size_t nb = (n + PCG_T - 1) / PCG_T;
+    const unsigned g = (unsigned)(nb < 4096 ? nb : 4096);
+    SOL_LAUNCH(large_copy, dim3(g), dim3(PCG_T), 0, s, l.a.r, rhs, n);
+    if (int e = large_solve(s, c, box_blob, active, l, cg_info)) return e;
+    SOL_LAUNCH(large_copy, dim3(g), dim3(PCG_T), 0, s, p, (const float*)l.a.x, n);
+    SOL_LAUNCH_CHECK();
+    return SOL_OK;
+}

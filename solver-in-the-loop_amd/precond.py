@@ -174,7 +174,7 @@ def box_solve_reference(blob, b):
 
 
 def pcg_reference(active, blob, b, rtol=1e-6, atol=1e-9, max_iter=2000):
-    """float64 numpy restatement of the large-grid CG solve (csrc/karman_large_pcg.hip) of M x = b, M = scene_matrix(active), with
+    """float64 numpy restatement of the large-grid CG solve (csrc/pcg.hip) of M x = b, M = scene_matrix(active), with
     the empty-box preconditioner of `blob`; returns (x, iterations, converged)."""
     act = (np.asarray(active, dtype=np.float64) != 0).astype(np.float64)
     Y, X = act.shape

@@ -1,6 +1,6 @@
-"""karman-2d custom obstacles on the GPU (pytest -m gpu): the large-grid CG step (sol_karman_step_fwd_large_cg) and its solve alone
-against the float64 oracle with the scene's geometry, the default scene's direct path unchanged, reproducibility (eager and
-captured), training / roll-out on a CG scene at 128 x 64, and the three scripts end to end with --obstacle.
+"""karman-2d custom obstacles on the GPU (pytest -m gpu): the large-grid CG step (sol_karman_step_fwd_large_cg, csrc/pcg.hip) and
+its solve alone against the float64 oracle with the scene's geometry, the default scene's direct path unchanged, reproducibility
+(eager and captured), training / roll-out on a CG scene at 128 x 64, and the three scripts end to end with --obstacle.
 Tolerances: fields 1e-5 relative L2, gradients 1e-4 (the suite's)."""
 import glob
 import importlib.util

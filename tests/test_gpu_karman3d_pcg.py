@@ -1,4 +1,4 @@
-"""GPU tests of the karman-3d preconditioned CG pressure solve (pytest -m gpu): csrc/karman3d_pcg.hip through the C ABI and
+"""GPU tests of the karman-3d preconditioned CG pressure solve (pytest -m gpu): csrc/pcg.hip through the C ABI and
 Scene3D(active=..., pressure_solver=...) against oracle/sol_oracle3d.py (float64: sparse LU on small grids, its own PCG
 beyond) on the oracle's obstacles, against the direct solve where that builds, and held to properties where the oracle cannot
 afford the size.  Tolerances as in test_gpu_karman3d.py: fields 1e-5, gradients 1e-4 relative L2."""

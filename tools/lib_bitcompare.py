@@ -1,6 +1,7 @@
 #!/usr/bin/env python
-"""Does a library variant (tools/ab_lib.py --build NAME ...) compute the SAME BITS as the product library?  One C3 training step (loss,
-gradient, final state) and one small karman-3d training step per library in fresh processes (SOL_HIP_LIB), SHA-1 of every result.
+"""Does a library variant (tools/ab_lib.py --build NAME ...) compute the SAME BITS as the product library?  Two karman-2d training steps
+(loss, gradient, final state) and the CG pressure solves (the 2-D large step eager and replayed, its solve alone, the 3-D step and its
+adjoint: fields and cg_info) per library in fresh processes (SOL_HIP_LIB), SHA-1 of every result, one verdict per leg.
     python tools/lib_bitcompare.py NAME [NAME2 ...]        (on the GPU box)"""
 import hashlib
 import json
@@ -25,6 +26,47 @@ if "--child" in sys.argv:
         g = tr.grads
         g = torch.cat([t.flatten() for t in g]) if isinstance(g, (list, tuple)) else g
         out["%dx%dx%d_ms%d" % (B, Y, X, ms)] = {"loss": float(loss).hex(), "grad": sha(g), "final": [sha(t) for t in tr.final]}
+    # the CG pressure solves (csrc/pcg.hip): the 2-D large step on two cylinders eager and replayed from a graph, its solve alone,
+    # and the 3-D cylinder forward + adjoint step
+    sys.path.insert(0, os.path.join(ROOT, "oracle"))
+    import sol_oracle3d as o3
+    from sol_amd import fluid, karman, karman3d, ops
+    B, Y, X = 2, 256, 128
+    dom = fluid.Domain([Y, X], box=fluid.box[0:200, 0:100])
+    active, inflow = karman.KarmanFlow(obstacles=karman.parse_obstacles(["sphere:50,50,10", "sphere:120,50,10"])).scene_arrays(dom)
+    bc = karman.velocity_bc_masks(Y, X)[0].reshape(Y + 1, X)
+    mk = ops.SceneMasks(active, inflow, bc, bc, dev, pressure_solver="cg")
+    cfg = ops.karman_cfg(B, Y, X, dom.dx[1], masks=mk, cg_max_iter=600)
+    gen = torch.Generator().manual_seed(1)
+    d0, vy0, vx0 = (t.to(dev) for t in (torch.rand(B, Y, X, generator=gen), 1.0 + 0.1 * torch.randn(B, Y + 1, X, generator=gen),
+                                        0.1 * torch.randn(B, Y, X + 1, generator=gen)))
+    re = torch.full((B,), 1.6e5, device=dev)
+    ws = torch.empty((ops.large_workspace_bytes(cfg, mk) + 3) // 4, dtype=torch.float32, device=dev)
+    cg = lambda outs, info: [sha(t) for t in outs] + [info["iterations"].tolist(), info["converged"].tolist()]
+    with torch.no_grad():
+        d, vy, vx = ops.karman_step_large(d0, vy0, vx0, re, cfg, mk, ws)         # spun up: divergence free, in the scene
+        info = {}
+        out["cg2d_step_eager"] = cg(ops.karman_step_large(d, vy, vx, re, cfg, mk, ws, info), info)
+        s, gr, info = torch.cuda.Stream(), torch.cuda.CUDAGraph(), {}
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s), torch.cuda.graph(gr, stream=s):
+            outs = ops.karman_step_large(d, vy, vx, re, cfg, mk, ws, info)
+        torch.cuda.current_stream().wait_stream(s)
+        gr.replay()
+        torch.cuda.synchronize()
+        out["cg2d_step_replayed"] = cg(outs, info)
+        info = {}
+        rhs = -((vy0[:, 1:] - vy0[:, :-1]) + (vx0[:, :, 1:] - vx0[:, :, :-1]))   # -div of the unprojected field
+        out["cg2d_solve"] = cg([ops.pressure_solve_large(rhs, cfg, mk, info=info)], info)
+    B, Y, X, Z = 2, 32, 16, 16
+    g3 = o3.geometry(Y, X, Z, obstacle="cylinder")
+    sim = karman3d.Karman3DFlow(karman3d.Scene3D(Y, X, Z, device=dev, active=g3.active, inflow=g3.inflow, pressure_solver="cg"), B)
+    d, v = o3.synthetic_state(B, Y, X, Z, 41)
+    v = [t.float().to(dev).requires_grad_(True) for t in v]
+    outs = sim.step(d.float().to(dev), *v, torch.tensor(o3.RE_TRAIN[:B], dtype=torch.float32, device=dev))
+    sum((t * (k + 1.0)).sum() for k, t in enumerate(outs[1:])).backward()
+    out["cg3d_fwd_adjoint"] = [sha(t) for t in list(outs) + [t.grad for t in v]] + \
+        [sim.solve_info[k].tolist() for k in ("iterations", "converged", "iterations_bwd", "converged_bwd")]
     print(json.dumps(out))
     sys.exit(0)
 names = ["product"] + [a for a in sys.argv[1:] if not a.startswith("--")]
@@ -41,4 +83,5 @@ for n in names:
         raise
     print(n, json.dumps(res[n]), flush=True)
 for n in names[1:]:
-    print("%-10s %s" % (n, "BIT-IDENTICAL to product" if res[n] == res["product"] else "DIFFERS from product"))
+    for leg in res["product"]:
+        print("%-10s %-20s %s" % (n, leg, "BIT-IDENTICAL to product" if res[n].get(leg) == res["product"][leg] else "DIFFERS from product"))
