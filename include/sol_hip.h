@@ -76,6 +76,8 @@ int sol_abi_sizes(int32_t* karman_cfg, int32_t* burgers_cfg, int32_t* train_cfg)
  *                       of the batch x height stack per twelve-wave workgroup; 0: one row per 256-thread workgroup.  Same results bit for bit
  *   k3d_adj_tile (1)    karman-3d: the advection adjoint's fixed-point scatter goes through an int64 LDS window per workgroup (4 x 4 columns + halo 2),
  *                       flushed with one global atomic per non-zero cell; 0: every contribution is a global atomic.  Same results bit for bit
+ *   k2d_adj_tile (1)    karman-2d large grids: the advection adjoint's fixed-point scatter goes through an int64 LDS window per workgroup (16 x 16 cells
+ *                       + halo 4), flushed with one global atomic per non-zero cell; 0: every contribution is a global atomic.  Same results bit for bit
  *   k3d_conv_persist (0) karman-3d: 1 = the one-launch Conv3D kernel as 256 workgroups of consecutive eight-row tiles (the next tile's rows and weight
  *                       sets requested during the last tap rows of the tile) when the tile count is a multiple of 256; same results bit for bit,
  *                       measured slower (register spills), kept as a tested experiment
@@ -136,8 +138,8 @@ int sol_karman_direct_supported(int32_t Y, int32_t X);
 /* Forward step for grids beyond the one-workgroup kernels (the reference generates its data at 256 x 128:
  * karman-2d/karman.py:98-159, Makefile:19-28 `-r 128`).  Same arithmetic and argument meaning as sol_karman_step_fwd,
  * decomposed into chip-wide launches on global memory; the pressure system is solved DIRECTLY, so cfg.direct (blob
- * with a 16/32/64 window, precond.direct_solver_blob(active, max_window=64)) is required.  Forward only: no saved
- * state, no adjoint.  Outputs must not alias inputs.  `direct_header_host`: HOST copy of the first 16 words of the blob
+ * with a 16/32/64 window, precond.direct_solver_blob(active, max_window=64)) is required.  This form keeps no state
+ * (the differentiable pair is sol_karman_step_fwd_large_saved / sol_karman_step_bwd_large below).  Outputs must not alias inputs.  `direct_header_host`: HOST copy of the first 16 words of the blob
  * (grid, window origin/size, number of perturbed cells: they size the launches).  `workspace`: DEVICE scratch of
  * sol_karman_step_large_workspace_bytes(cfg) bytes. */
 size_t sol_karman_step_large_workspace_bytes(const sol_karman_cfg* cfg);
@@ -173,6 +175,37 @@ int sol_karman_step_fwd_large_cg(const sol_karman_cfg* cfg, void* stream,
 int sol_karman_pressure_solve_large(const sol_karman_cfg* cfg, void* stream, const float* active, const float* rhs, float* p,
                                     const float* box_blob, const int32_t* box_header_host, int32_t* cg_info,
                                     void* workspace, size_t workspace_bytes);
+
+/* Adjoint of the large-grid step with respect to its input velocity, for both solvers (csrc/karman_large_bwd.hip).  The solver is
+ * chosen by the cfg: cfg.direct set = the direct solve (direct_header_host required; box_blob / box_header_host / cg_info are not read
+ * and may be NULL), cfg.direct NULL = the preconditioned CG (box_blob, box_header_host, cg_info [2][B] required as for
+ * sol_karman_step_fwd_large_cg; direct_header_host is not read).
+ *   sol_karman_step_fwd_large_saved: the forward step (same launches and results as sol_karman_step_fwd_large / _large_cg without
+ *     features) that also hands out the post-diffusion velocity saved_vy [B,Y+1,X] / saved_vx [B,Y,X+1], the only state the adjoint
+ *     needs.  `workspace`: the forward workspace of the solver (sol_karman_step_large_workspace_bytes / _large_cg_workspace_bytes).
+ *   sol_karman_step_bwd_large: g_vy_in / g_vx_in = (d step / d v_in)^T (g_vy_out, g_vx_out); the density carries no gradient.  Stages:
+ *     rhs of the adjoint projection, the forward step's pressure solve (same symmetric matrix), g_a, the advection adjoint as a scatter
+ *     in 64-bit fixed point (order independent: results are bit-reproducible; LDS window per 16 x 16 tile, option k2d_adj_tile), the
+ *     diffusion adjoint.  A non-finite output gradient makes that simulation's input gradient NaN.  With the CG solve, cg_info reports
+ *     the adjoint solve's iterations / converged; under stream capture the call issues the full cfg.cg_max_iter budget and never
+ *     synchronises, an eager call stops issuing iterations (checked every 16) once every simulation has converged.
+ *     `workspace`: DEVICE scratch of sol_karman_step_bwd_large_workspace_bytes(cfg) bytes (covers either solver as the cfg selects it). */
+size_t sol_karman_step_bwd_large_workspace_bytes(const sol_karman_cfg* cfg);
+int sol_karman_step_fwd_large_saved(const sol_karman_cfg* cfg, void* stream,
+                                    const float* d_in, const float* vy_in, const float* vx_in,
+                                    const float* re, const float* active, const float* inflow,
+                                    const float* velBCy, const float* velBCyMask, int64_t bc_batch_stride,
+                                    float* d_out, float* vy_out, float* vx_out, float* saved_vy, float* saved_vx,
+                                    const int32_t* direct_header_host,
+                                    const float* box_blob, const int32_t* box_header_host, int32_t* cg_info,
+                                    void* workspace, size_t workspace_bytes);
+int sol_karman_step_bwd_large(const sol_karman_cfg* cfg, void* stream,
+                              const float* saved_vy, const float* saved_vx, const float* re, const float* active,
+                              const float* velBCyMask, int64_t bc_batch_stride,
+                              const float* g_vy_out, const float* g_vx_out, float* g_vy_in, float* g_vx_in,
+                              const int32_t* direct_header_host,
+                              const float* box_blob, const int32_t* box_header_host, int32_t* cg_info,
+                              void* workspace, size_t workspace_bytes);
 
 /* active  [Y,X]  1 - obstacle mask (cell centres inside Obstacle geometries -> 0)
  * inflow  [Y,X]  inflow rate mask (Inflow(box[5:10,25:75]) -> 1 inside)

@@ -49,6 +49,20 @@ int sol_large_front(const sol_karman_cfg* c, hipStream_t s, const SolLargeStep& 
 int sol_large_project(const sol_karman_cfg* c, hipStream_t s, const SolLargeStep& io, const float* p);
 int sol_large_box_forward(hipStream_t s, int B, int Y, int X, const float* blob, const float* src, float* T1, float* T2, const int* skip);
 int sol_large_box_back(hipStream_t s, int B, int Y, int X, const float* blob, const float* T2, float* T1, float* dst, const int* skip);
+// the step's pressure solve M x = b for either solver (pcg.hip; shared by the forward entry points and the adjoint, karman_large_bwd.hip):
+// direct = the capacitance solve on cfg.direct (hdr: host copy of its header, sol_large_direct_check), else the preconditioned CG with the
+// empty-box solve of box_blob, reporting to cg_info [2][B] (sol_large_cg_check).  ws: sol_large_solver_bytes(c, direct) bytes; the caller
+// writes b to sol_large_solver_rhs(c, direct, ws) (overwritten); *x = the buffer inside ws that holds the solution.
+size_t sol_large_direct_floats(const sol_karman_cfg* c);
+int sol_large_direct_check(const sol_karman_cfg* c, const char* who, const int32_t* hdr);
+int sol_large_direct_solve(hipStream_t s, const sol_karman_cfg* c, const int32_t* hdr, float* base);
+int sol_large_cg_check(const sol_karman_cfg* c, const char* who, const float* box_blob, const int32_t* hdr, const int32_t* cg_info, const void* workspace);
+size_t sol_large_solver_bytes(const sol_karman_cfg* c, bool direct);
+float* sol_large_solver_rhs(const sol_karman_cfg* c, bool direct, void* ws);
+int pressure_solve_any2d(hipStream_t s, const sol_karman_cfg* c, bool direct, const int32_t* hdr, const float* box_blob, const float* active,
+                         int32_t* cg_info, void* ws, float** x);
+int sol_large_step(const sol_karman_cfg* c, hipStream_t s, const SolLargeStep& io, float* svy, float* svx, bool direct, const int32_t* hdr,
+                   const float* box_blob, int32_t* cg_info, void* solver_ws);
 
 // karman-3d pressure solvers (karman3d.hip / pcg.hip): dst = G src with G = the empty-box solve on the blob of cfg->direct
 // (*res = t1 or t2, whichever holds dst; skip = per-simulation done words [B] or NULL); the preconditioned CG solve M x = b (b is
@@ -251,6 +265,8 @@ struct SolOptions {
                           //    five rounds of 32-row workgroups (k_conv5x5_bww_sb_jobs); 0: five launches
     int fwd_bands;        // 1 (default): the 128 x 64 forward solver step of the training / roll-out path as FOUR workgroups per simulation (k_karman_fwd_bands:
                           //    stencil phases on row bands with recomputed halos, the direct solve on band 0's CU, two hand-offs through global memory); 0: one workgroup
+    int k2d_adj_tile;     // 1 (default): the large-grid karman-2d advection adjoint scatters into an int64 LDS window per workgroup tile (k_lb_advect_adj_tile);
+                          //    0: global atomics only (k_lb_advect_adj).  Same results bit for bit
     int k3d_tile;         // 1: karman-3d advection from LDS tiles holding the full z column + halo; 0 (default, measured faster at B <= 2): wave-per-column gathers from global memory
 };
 SolOptions& sol_opt();

@@ -11,7 +11,8 @@
 //                 the capacitance correction of the obstacle (precond.direct_solver_blob, window 16/32/64): eight small
 //                 fp32 GEMMs (k_l_gemm) + gather / K' / scatter kernels
 //   k_l_project   v -= mask * grad p  (+ fused to_feature)
-// Forward only (no saved state, no adjoint): this path generates reference data, it is not trained through.
+// The adjoint of this path lives in karman_large_bwd.hip; it reads the post-diffusion velocity (sv_y, sv_x) that
+// sol_karman_step_fwd_large_saved hands out and runs the same pressure solve (pressure_solve_any2d, pcg.hip).
 #include "common.hpp"
 
 namespace {
@@ -327,11 +328,64 @@ int sol_large_box_back(hipStream_t s, int B, int Y, int X, const float* blob, co
     return gemm(s, B, Qy, Y, 0, T1, X, sN, dst, X, sN, Y, X, Y, 0, skip);
 }
 
+// ---- the direct pressure solve on its own buffers (shared by the forward step and the adjoint, karman_large_bwd.hip) ----
+// layout from `base`: T0 (rhs in, pressure out), T1, T2 (spectral coefficients), window scratch (u, t2w: Y*64 each; x0w, W2: 64*64 each)
+size_t sol_large_direct_floats(const sol_karman_cfg* c) {
+    const size_t B = c->B, Y = c->Y, X = c->X;
+    return B * (3 * Y * X + 2 * Y * 64 + 2 * 64 * 64);
+}
+
+int sol_large_direct_check(const sol_karman_cfg* c, const char* who, const int32_t* hdr) {
+    SOL_REQUIRE(c->direct && c->direct_n > 0, "%s needs the direct-solver blob (cfg.direct)", who);
+    SOL_REQUIRE(hdr && hdr[0] == 0x46443032, "%s: direct_header_host must be the first 16 words of the blob (host copy)", who);
+    const Header h{hdr[1], hdr[2], hdr[3], hdr[4], hdr[5], hdr[6], hdr[7]};
+    SOL_REQUIRE(h.SP >= h.nS && h.SP <= 4096 && h.wy0 >= 0 && h.wx0 >= 0 && h.wy0 + h.win <= c->Y && h.wx0 + h.win <= c->X,
+                "direct-solver blob header is inconsistent");
+    SOL_REQUIRE(h.Y == c->Y && h.X == c->X, "direct-solver blob is for a %dx%d grid, cfg is %dx%d", h.Y, h.X, c->Y, c->X);
+    SOL_REQUIRE(h.win == 16 || h.win == 32 || h.win == 64, "direct-solver blob: unsupported window %d", h.win);
+    return SOL_OK;
+}
+
+// M p = T0 by the empty-box solve of the rhs with the capacitance correction on its spectral coefficients; p overwrites T0 (= base)
+int sol_large_direct_solve(hipStream_t s, const sol_karman_cfg* c, const int32_t* hdr, float* base) {
+    const Header h{hdr[1], hdr[2], hdr[3], hdr[4], hdr[5], hdr[6], hdr[7]};
+    const int B = c->B, Y = c->Y, X = c->X, N = Y * X, win = h.win, SP = h.SP;
+    // blob sections
+    const float* Qy = c->direct + FDL_HEADER;
+    const float* Qx = Qy + (size_t)Y * Y;
+    const float* ilT = Qx + (size_t)X * X;             // [X][Y]
+    const float* KpT = ilT + (size_t)X * Y;
+    const int* sidx = reinterpret_cast<const int*>(KpT + (size_t)SP * SP);
+    const float* QxW = reinterpret_cast<const float*>(sidx + SP);     // [X][win]
+    float* w = base;
+    float* T0 = w; w += (size_t)B * N;                 // rhs / T3 / pressure
+    float* T1 = w; w += (size_t)B * N;
+    float* T2 = w; w += (size_t)B * N;                 // spectral coefficients, stored TRANSPOSED [X][Y] (matches ilT)
+    float* U = w; w += (size_t)B * Y * 64;             // [Y][win]
+    float* V = w; w += (size_t)B * Y * 64;
+    float* X0 = w; w += (size_t)B * 64 * 64;           // [win][win]
+    float* W2 = w; w += (size_t)B * 64 * 64;
+    const long sN = N, sU = (long)Y * 64, sW = 64 * 64;
+    if (int e = sol_large_box_forward(s, B, Y, X, c->direct, T0, T1, T2, nullptr)) return e;
+    // window values of G b: U = T2 Qx[:, win] ; X0 = Qy[win, :] U
+    if (int e = gemm(s, B, T2, X, sN, QxW, win, 0, U, win, sU, Y, win, X, 0)) return e;
+    if (int e = gemm(s, B, Qy + (size_t)h.wy0 * Y, Y, 0, U, win, sU, X0, win, sW, win, win, Y, 0)) return e;
+    // W2 = -scatter(K' gather(X0))
+    SOL_LAUNCH(k_l_capacitance, dim3(B), dim3(256), SP * sizeof(float), s, X0, KpT, sidx, W2, SP, win);
+    SOL_LAUNCH_CHECK();
+    // spectral coefficients of the correction: V = Qy[:, win] W2 ; T2 += ((V Qx[win, :])) / lam
+    if (int e = gemm(s, B, Qy + h.wy0, Y, 0, W2, win, sW, V, win, sU, Y, win, win, 0)) return e;
+    if (int e = gemm(s, B, V, win, sU, Qx + (size_t)h.wx0 * X, X, 0, T1, X, sN, Y, X, win, 0)) return e;
+    SOL_LAUNCH(k_l_scale, dim3((N + 255) / 256, B), dim3(256), 0, s, T2, (const float*)T1, ilT, Y, X, (const int*)nullptr);
+    // p = Qy (T2 Qx)
+    return sol_large_box_back(s, B, Y, X, c->direct, T2, T1, T0, nullptr);
+}
+
 extern "C" size_t sol_karman_step_large_workspace_bytes(const sol_karman_cfg* c) {
     if (!c) return 0;
     const size_t B = c->B, Y = c->Y, X = c->X;
-    // sv_y, sv_x, three N-sized buffers (rhs / transforms), window scratch (u, t2w: Y*64 each; x0w, W2: 64*64 each)
-    const size_t floats = B * ((Y + 1) * X + Y * (X + 1) + 3 * Y * X + 2 * Y * 64 + 2 * 64 * 64) + 256;
+    // sv_y, sv_x, then the direct solve's buffers
+    const size_t floats = B * ((Y + 1) * X + Y * (X + 1)) + sol_large_direct_floats(c) + 256;
     return floats * sizeof(float);
 }
 
@@ -351,51 +405,12 @@ extern "C" int sol_karman_step_fwd_large(const sol_karman_cfg* c, void* stream,
     SOL_REQUIRE(c->direct && c->direct_n > 0, "sol_karman_step_fwd_large needs the direct-solver blob (cfg.direct)");
     SOL_REQUIRE(workspace_bytes >= sol_karman_step_large_workspace_bytes(c), "workspace too small");
     SOL_REQUIRE(vy_in != vy_out && vx_in != vx_out && d_in != d_out, "sol_karman_step_fwd_large: outputs must not alias the inputs");
-    SOL_REQUIRE(direct_header_host && direct_header_host[0] == 0x46443032, "sol_karman_step_fwd_large: direct_header_host must be the first 16 words of the blob (host copy)");
-    const Header h{direct_header_host[1], direct_header_host[2], direct_header_host[3], direct_header_host[4],
-                   direct_header_host[5], direct_header_host[6], direct_header_host[7]};
-    SOL_REQUIRE(h.SP >= h.nS && h.SP <= 4096 && h.wy0 >= 0 && h.wx0 >= 0 && h.wy0 + h.win <= c->Y && h.wx0 + h.win <= c->X,
-                "direct-solver blob header is inconsistent");
-    SOL_REQUIRE(h.Y == c->Y && h.X == c->X, "direct-solver blob is for a %dx%d grid, cfg is %dx%d", h.Y, h.X, c->Y, c->X);
-    SOL_REQUIRE(h.win == 16 || h.win == 32 || h.win == 64, "direct-solver blob: unsupported window %d", h.win);
-    const int B = c->B, Y = c->Y, X = c->X, N = Y * X, win = h.win, SP = h.SP;
-    hipStream_t s = (hipStream_t)stream;
-    // blob sections
-    const float* Qy = c->direct + FDL_HEADER;
-    const float* Qx = Qy + (size_t)Y * Y;
-    const float* ilT = Qx + (size_t)X * X;             // [X][Y]
-    const float* KpT = ilT + (size_t)X * Y;
-    const int* sidx = reinterpret_cast<const int*>(KpT + (size_t)SP * SP);
-    const float* QxW = reinterpret_cast<const float*>(sidx + SP);     // [X][win]
-    // workspace carve
+    if (int e = sol_large_direct_check(c, "sol_karman_step_fwd_large", direct_header_host)) return e;
+    const size_t B = c->B, Y = c->Y, X = c->X;
+    // workspace carve: sv_y, sv_x, the solver's buffers
     float* w = static_cast<float*>(workspace);
-    float* svy = w; w += (size_t)B * (Y + 1) * X;
-    float* svx = w; w += (size_t)B * Y * (X + 1);
-    float* T0 = w; w += (size_t)B * N;                 // rhs / T3 / pressure
-    float* T1 = w; w += (size_t)B * N;
-    float* T2 = w; w += (size_t)B * N;                 // spectral coefficients, stored TRANSPOSED [X][Y] (matches ilT)
-    float* U = w; w += (size_t)B * Y * 64;             // [Y][win]
-    float* V = w; w += (size_t)B * Y * 64;
-    float* X0 = w; w += (size_t)B * 64 * 64;           // [win][win]
-    float* W2 = w; w += (size_t)B * 64 * 64;
-
+    float* svy = w; w += B * (Y + 1) * X;
+    float* svx = w; w += B * Y * (X + 1);
     const SolLargeStep io{d_in, vy_in, vx_in, re, active, inflow, velBCy, velBCyMask, bc_batch_stride, d_out, vy_out, vx_out, feat_out, feat_scale};
-    if (int e = sol_large_front(c, s, io, svy, svx, T0)) return e;
-
-    // ---- direct pressure solve: the empty-box solve of the rhs with the capacitance correction on its spectral coefficients
-    const long sN = N, sU = (long)Y * 64, sW = 64 * 64;
-    if (int e = sol_large_box_forward(s, B, Y, X, c->direct, T0, T1, T2, nullptr)) return e;
-    // window values of G b: U = T2 Qx[:, win] ; X0 = Qy[win, :] U
-    if (int e = gemm(s, B, T2, X, sN, QxW, win, 0, U, win, sU, Y, win, X, 0)) return e;
-    if (int e = gemm(s, B, Qy + (size_t)h.wy0 * Y, Y, 0, U, win, sU, X0, win, sW, win, win, Y, 0)) return e;
-    // W2 = -scatter(K' gather(X0))
-    SOL_LAUNCH(k_l_capacitance, dim3(B), dim3(256), SP * sizeof(float), s, X0, KpT, sidx, W2, SP, win);
-    SOL_LAUNCH_CHECK();
-    // spectral coefficients of the correction: V = Qy[:, win] W2 ; T2 += ((V Qx[win, :])) / lam
-    if (int e = gemm(s, B, Qy + h.wy0, Y, 0, W2, win, sW, V, win, sU, Y, win, win, 0)) return e;
-    if (int e = gemm(s, B, V, win, sU, Qx + (size_t)h.wx0 * X, X, 0, T1, X, sN, Y, X, win, 0)) return e;
-    SOL_LAUNCH(k_l_scale, dim3((N + 255) / 256, B), dim3(256), 0, s, T2, (const float*)T1, ilT, Y, X, (const int*)nullptr);
-    // p = Qy (T2 Qx)
-    if (int e = sol_large_box_back(s, B, Y, X, c->direct, T2, T1, T0, nullptr)) return e;
-    return sol_large_project(c, s, io, T0);
+    return sol_large_step(c, (hipStream_t)stream, io, svy, svx, true, direct_header_host, nullptr, nullptr, w);
 }

@@ -1,0 +1,408 @@
+// Adjoint of the large-grid karman-2d step (karman_large.hip) with respect to its input velocity, for both pressure solvers.
+// The density is a passive tracer: no adjoint, as on the one-workgroup path.  The chain is the 2-D projection of the 3-D adjoint
+// (karman3d.hip, "Adjoint of the 3-D step"); stages in reverse order of the forward step:
+//   k_lb_rhs          q = G^T (mask . g_out)                  adjoint of  out = v~ - mask . G p.  Boundary faces: with replicate padding
+//                                                              their pressure gradient is zero (they do not depend on p), with dirichlet0
+//                                                              it is +-p of the adjacent cell.  Side job: clears the scatter accumulators
+//                                                              and the absmax slots.
+//   pressure          g_div = M^-1 q                           the forward step's solve with the same symmetric matrix
+//                                                              (pressure_solve_any2d: direct launches or PCG)
+//   k_lb_ga           g_a = mask . (g_out + D^T g_div)         adjoint of rhs = -div and of the hard-BC face masks; publishes max|g_a|
+//   k_lb_advect_adj*  scatter of g_a through the bilinear gathers of the semi-Lagrangian step, for the field term AND the back-trace
+//                     (velocity) term, into g_c: int64 FIXED POINT (scale = a power of two with max|g_a| * scale in [2^37, 2^38)), so the
+//                     accumulation is order independent and the adjoint reproducible bit for bit.  Range, stated: a finite contribution
+//                     beyond 2^25 max|g_a| saturates in __float2ll_rn -- the back-trace term is g_a times a DIFFERENCE of the saved field
+//                     times dt/dx, so that takes |dv| dt/dx > 3e7, a simulation that has long blown up; a non-finite g_a makes the whole
+//                     simulation's input gradient NaN (k_lb_ga publishes a NaN maximum, lb_scale).  Resolution: 2^-37 max|g_a| per
+//                     contribution.  The default form accumulates in an int64 LDS window per 16 x 16-cell tile (halo 4 faces; targets
+//                     beyond the window go to global memory) and flushes one vector atomic per non-zero window cell.
+//   k_lb_diffuse_adj  g_in = (I + alpha L^T)(g_c . (1 - bcm)) for v_y, (I + alpha L^T) g_c for v_x: gather form of the transposed
+//                     replicate-padded Laplacian; converts the fixed-point g_c back to fp32 as it reads it
+#include "common.hpp"
+
+namespace {
+
+constexpr int LB_SLOTS = 64;            // absmax slots per simulation (one per lane of the reading wave)
+constexpr int LB_FIXBITS = 37;          // max|g_a| * 2^shift lies in [2^37, 2^38)
+constexpr int LB_T = 16, LB_H = 4, LB_W = LB_T + 2 * LB_H + 1;      // tile of 16 x 16 cells; window of 25 x 25 faces per component
+
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+__device__ __forceinline__ float acc_at(const float* act, int Y, int X, int j, int i) {   // 'boundary' extrapolation of the active mask
+    return act[clampi(j, 0, Y - 1) * X + clampi(i, 0, X - 1)] != 0.f ? 1.f : 0.f;
+}
+// hard-BC face masks of the forward step (karman_large.hip)
+__device__ __forceinline__ float mask_y(const float* act, int Y, int X, int j, int i) { return acc_at(act, Y, X, j - 1, i) * acc_at(act, Y, X, j, i); }
+__device__ __forceinline__ float mask_x(const float* act, int Y, int X, int j, int i) { return acc_at(act, Y, X, j, i - 1) * acc_at(act, Y, X, j, i); }
+
+struct LBArgs {
+    int B, Y, X;
+    float dtdx, adt;
+    int grad_pad;
+    const float *re, *active, *bcm;
+    long bc_stride;
+    const float *svy, *svx;             // saved post-diffusion velocity
+    const float *goy, *gox;             // gradient w.r.t. the step's output velocity
+    float *gay, *gax;                   // g_a
+    long long *gcy, *gcx;               // g_c: int64 fixed-point accumulators [B][faces] (cleared by k_lb_rhs)
+    unsigned* gmax;                     // [B][LB_SLOTS] bits of max|g_a| per simulation (cleared by k_lb_rhs, published by k_lb_ga)
+    float *giy, *gix;                   // result: gradient w.r.t. the step's input velocity
+    float* rhs;
+    const float* gdiv;
+};
+
+// power-of-two fixed-point scale of simulation b's scatter and its inverse, from the published max|g_a| (wave-uniform result)
+__device__ __forceinline__ void lb_scale(const unsigned* gmax_b, float& qs, float& qi) {
+    const unsigned m = amax_wave_max(gmax_b[threadIdx.x & (LB_SLOTS - 1)]);
+    if (m >= 0x7f800000u) {                   // k_lb_ga met an inf / nan gradient in this simulation: nothing is scattered (qs = 0) and the
+        qs = 0.f;                             // conversion back (value * qi) makes EVERY input gradient of the simulation NaN
+        qi = __uint_as_float(0x7fc00000u);
+        return;
+    }
+    int e = (int)(m >> 23) - 127;
+    e = m == 0u ? 0 : min(max(e, -80), 120);
+    qs = __uint_as_float((unsigned)(LB_FIXBITS - e + 127) << 23);
+    qi = __uint_as_float((unsigned)(e - LB_FIXBITS + 127) << 23);
+}
+
+__global__ void __launch_bounds__(256) k_lb_rhs(LBArgs a) {
+    const int Y = a.Y, X = a.X, XP = X + 1, N = Y * X, nVy = (Y + 1) * X, nVx = Y * XP;
+    const int b = blockIdx.y;
+    const float* gy = a.goy + (size_t)b * nVy;
+    const float* gx = a.gox + (size_t)b * nVx;
+    const bool keep = a.grad_pad == 1;           // dirichlet0: the boundary faces' gradient depends on p; replicate: it is zero
+    for (int c = blockIdx.x * blockDim.x + threadIdx.x; c < N; c += gridDim.x * blockDim.x) {
+        const int j = c / X, i = c - j * X;
+        auto wy = [&](int jj) { return (keep || (jj != 0 && jj != Y)) ? mask_y(a.active, Y, X, jj, i) * gy[jj * X + i] : 0.f; };
+        auto wx = [&](int ii) { return (keep || (ii != 0 && ii != X)) ? mask_x(a.active, Y, X, j, ii) * gx[j * XP + ii] : 0.f; };
+        a.rhs[(size_t)b * N + c] = (wy(j) - wy(j + 1)) + (wx(i) - wx(i + 1));
+    }
+    // side job: clear slice b of the fixed-point accumulators (y and x components are contiguous: [B][nVy] then [B][nVx]) and the absmax slots
+    const size_t faces = (size_t)nVy + nVx;
+    long long* zc = a.gcy + (size_t)b * faces;
+    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < faces; e += (size_t)gridDim.x * blockDim.x) zc[e] = 0ll;
+    if (blockIdx.x == 0 && threadIdx.x < LB_SLOTS) a.gmax[b * LB_SLOTS + threadIdx.x] = 0u;
+}
+
+__global__ void __launch_bounds__(256) k_lb_ga(LBArgs a) {
+    const int Y = a.Y, X = a.X, XP = X + 1, N = Y * X, nVy = (Y + 1) * X, nVx = Y * XP;
+    const int b = blockIdx.y;
+    const float* P = a.gdiv + (size_t)b * N;
+    auto cell = [&](int j, int i) { return ((unsigned)j < (unsigned)Y && (unsigned)i < (unsigned)X) ? P[j * X + i] : 0.f; };
+    float vmax = 0.f;
+    bool bad = false;
+    for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < nVy + nVx; k += gridDim.x * blockDim.x) {
+        float v;
+        if (k < nVy) {
+            const int j = k / X, i = k - j * X;
+            v = mask_y(a.active, Y, X, j, i) * (a.goy[(size_t)b * nVy + k] + cell(j - 1, i) - cell(j, i));
+            a.gay[(size_t)b * nVy + k] = v;
+        } else {
+            const int q = k - nVy, j = q / XP, i = q - j * XP;
+            v = mask_x(a.active, Y, X, j, i) * (a.gox[(size_t)b * nVx + q] + cell(j, i - 1) - cell(j, i));
+            a.gax[(size_t)b * nVx + q] = v;
+        }
+        vmax = fmaxf(vmax, fabsf(v));
+        bad |= !(fabsf(v) <= 3.402823466e38f);      // inf or nan (fmaxf drops a NaN)
+    }
+    // max|g_a| of this simulation -> the scale of the fixed-point scatter (at most one atomic per workgroup).  A non-finite g_a publishes
+    // the bits of a NaN -- the largest value the integer maximum can see -- and lb_scale turns that into "scatter nothing, convert back
+    // to NaN".  The maximum is order independent; a workgroup that cannot raise its slot publishes nothing.
+    __shared__ unsigned red[4];
+    const unsigned wmax = amax_wave_max(bad ? 0x7fc00000u : __float_as_uint(vmax));
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = wmax;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const unsigned mb = max(max(red[0], red[1]), max(red[2], red[3]));
+        unsigned* slot = &a.gmax[b * LB_SLOTS + (blockIdx.x & (LB_SLOTS - 1))];
+        if (mb > __atomic_load_n(slot, __ATOMIC_RELAXED)) atomicMax(slot, mb);
+    }
+}
+
+// Where a contribution goes.  GAdd: straight into the int64 accumulators in global memory.  TAdd: into the workgroup's int64 LDS window
+// when the target face lies inside it, else into global memory -- integer adds commute, so both give the same bits.  Each contribution
+// is rounded to the fixed-point grid on its own, then added as an integer.
+struct GAdd {
+    long long *gy, *gx;
+    float qs;
+    int X;
+    __device__ __forceinline__ void operator()(int comp, int jj, int ii, float v) const {
+        long long* p = comp == 0 ? gy + jj * X + ii : gx + jj * (X + 1) + ii;
+        ::atomicAdd(reinterpret_cast<unsigned long long*>(p), (unsigned long long)__float2ll_rn(v * qs));
+    }
+};
+struct TAdd {
+    GAdd g;
+    unsigned long long* L;         // [2][LB_W][LB_W]
+    int jw0, iw0;
+    __device__ __forceinline__ void operator()(int comp, int jj, int ii, float v) const {
+        const int lj = jj - jw0, li = ii - iw0;
+        if ((unsigned)lj < (unsigned)LB_W && (unsigned)li < (unsigned)LB_W)
+            ::atomicAdd(&L[(comp * LB_W + lj) * LB_W + li], (unsigned long long)__float2ll_rn(v * g.qs));
+        else g(comp, jj, ii, v);
+    }
+};
+
+// adjoint of one advected face value of component C (0: v_y [Y+1][X], 1: v_x [Y][X+1]) at (j, i): gs = g_a there.  The departure point
+// is recomputed from the saved field with the forward step's expressions (k_l_advect, bil_clamp), operation for operation, so floorf and
+// the clamps decide as they did.  No fused multiply-adds: the two scatter kernels are held to the same bits by the test suite.
+template <int C, class Add>
+__device__ __forceinline__ void lb_advect_adj_point(const LBArgs& a, const float* sy, const float* sx, const Add& add, int j, int i, float gs) {
+#pragma clang fp contract(off)
+    const int Y = a.Y, X = a.X, XP = X + 1;
+    float uy, ux;
+    int ja = 0, jb = 0, ia = 0, ib = 0;
+    if (C == 0) {
+        ja = max(j - 1, 0); jb = min(j, Y - 1);
+        uy = sy[j * X + i];
+        ux = 0.25f * (sx[ja * XP + i] + sx[ja * XP + i + 1] + sx[jb * XP + i] + sx[jb * XP + i + 1]);
+    } else {
+        ia = max(i - 1, 0); ib = min(i, X - 1);
+        ux = sx[j * XP + i];
+        uy = 0.25f * (sy[j * X + ia] + sy[j * X + ib] + sy[(j + 1) * X + ia] + sy[(j + 1) * X + ib]);
+    }
+    const int H = Y + (C == 0), W = X + (C == 1);
+    const float* f = C == 0 ? sy : sx;
+    const float oy = -uy * a.dtdx, ox = -ux * a.dtdx;
+    const float fy = floorf(oy), fx = floorf(ox);
+    const float wy = oy - fy, wx = ox - fx;
+    const int jf = j + (int)fy, iF = i + (int)fx;
+    const int j0 = clampi(jf, 0, H - 1), j1 = clampi(jf + 1, 0, H - 1);
+    const int i0 = clampi(iF, 0, W - 1), i1 = clampi(iF + 1, 0, W - 1);
+    float dy = 0.f, dx = 0.f;                    // d(sample) / d(offset) along each axis
+#pragma unroll
+    for (int cj = 0; cj < 2; ++cj)
+#pragma unroll
+        for (int ci = 0; ci < 2; ++ci) {
+            const int jj = cj ? j1 : j0, ii = ci ? i1 : i0;
+            const float by = cj ? wy : 1.f - wy, bx = ci ? wx : 1.f - wx;
+            const float v = f[jj * W + ii];
+            add(C, jj, ii, by * bx * gs);                   // field term
+            dy += (cj ? 1.f : -1.f) * bx * v;
+            dx += by * (ci ? 1.f : -1.f) * v;
+        }
+    // back-trace term: offset = -dtdx * u(x0), onto the velocity samples that formed u
+    const float guy = -a.dtdx * gs * dy, gux = -a.dtdx * gs * dx;
+    if (C == 0) {
+        add(0, j, i, guy);
+        const float qx = 0.25f * gux;
+        add(1, ja, i, qx); add(1, ja, i + 1, qx); add(1, jb, i, qx); add(1, jb, i + 1, qx);
+    } else {
+        add(1, j, i, gux);
+        const float qy = 0.25f * guy;
+        add(0, j, ia, qy); add(0, j, ib, qy); add(0, j + 1, ia, qy); add(0, j + 1, ib, qy);
+    }
+}
+
+// every contribution a global int64 atomic (option k2d_adj_tile = 0; the reference form of the tile kernel)
+__global__ void __launch_bounds__(256) k_lb_advect_adj(LBArgs a) {
+    const int Y = a.Y, X = a.X, XP = X + 1, nVy = (Y + 1) * X, nVx = Y * XP;
+    const int b = blockIdx.y;
+    const float* sy = a.svy + (size_t)b * nVy;
+    const float* sx = a.svx + (size_t)b * nVx;
+    float qs, qi;
+    lb_scale(a.gmax + b * LB_SLOTS, qs, qi);
+    const GAdd add{a.gcy + (size_t)b * nVy, a.gcx + (size_t)b * nVx, qs, X};
+    for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < nVy + nVx; k += gridDim.x * blockDim.x) {
+        if (k < nVy) {
+            const float g = a.gay[(size_t)b * nVy + k];
+            if (g != 0.f) lb_advect_adj_point<0>(a, sy, sx, add, k / X, k % X, g);
+        } else {
+            const int q = k - nVy;
+            const float g = a.gax[(size_t)b * nVx + q];
+            if (g != 0.f) lb_advect_adj_point<1>(a, sy, sx, add, q / XP, q % XP, g);
+        }
+    }
+}
+
+// The same scatter with an LDS window per workgroup: a workgroup owns the faces of 16 x 16 cells (the last tile row also face row Y, the
+// last tile column face column X) and accumulates into a 25 x 25 int64 window per component (10 KB); the nine contributions of a face --
+// four corners of its bilinear gather, five back-trace terms -- land within |u| dt/dx + 1 faces of it.  Targets beyond the halo of 4 go
+// to global memory directly, so any CFL number is handled.  Integer adds commute: the result equals k_lb_advect_adj's bit for bit.
+__global__ void __launch_bounds__(256) k_lb_advect_adj_tile(LBArgs a, int nti) {
+    __shared__ unsigned long long win[2 * LB_W * LB_W];
+    const int Y = a.Y, X = a.X, XP = X + 1, nVy = (Y + 1) * X, nVx = Y * XP;
+    const int b = blockIdx.y;
+    const int tj = (int)blockIdx.x / nti, ti = (int)blockIdx.x % nti, j0 = tj * LB_T, i0 = ti * LB_T;
+    const float* sy = a.svy + (size_t)b * nVy;
+    const float* sx = a.svx + (size_t)b * nVx;
+    float qs, qi;
+    lb_scale(a.gmax + b * LB_SLOTS, qs, qi);
+    const GAdd gadd{a.gcy + (size_t)b * nVy, a.gcx + (size_t)b * nVx, qs, X};
+    const TAdd add{gadd, win, j0 - LB_H, i0 - LB_H};
+    for (int e = threadIdx.x; e < 2 * LB_W * LB_W; e += 256) win[e] = 0ull;
+    __syncthreads();
+    const int j1 = min(j0 + LB_T, Y), i1 = min(i0 + LB_T, X);
+    const int j1y = j0 + LB_T >= Y ? Y + 1 : j1, i1x = i0 + LB_T >= X ? X + 1 : i1;
+    const int nI = i1 - i0, wX = i1x - i0, nY = (j1y - j0) * nI, nX = (j1 - j0) * wX;
+    for (int t = threadIdx.x; t < nY + nX; t += 256) {
+        if (t < nY) {
+            const int j = j0 + t / nI, i = i0 + t % nI;
+            const float g = a.gay[(size_t)b * nVy + j * X + i];
+            if (g != 0.f) lb_advect_adj_point<0>(a, sy, sx, add, j, i, g);
+        } else {
+            const int q = t - nY, j = j0 + q / wX, i = i0 + q % wX;
+            const float g = a.gax[(size_t)b * nVx + j * XP + i];
+            if (g != 0.f) lb_advect_adj_point<1>(a, sy, sx, add, j, i, g);
+        }
+    }
+    __syncthreads();
+    for (int e = threadIdx.x; e < 2 * LB_W * LB_W; e += 256) {
+        const unsigned long long v = win[e];
+        if (v == 0ull) continue;                                   // (window cells outside the arrays never receive a contribution)
+        const int li = e % LB_W, lj = (e / LB_W) % LB_W, comp = e / (LB_W * LB_W);
+        const int jj = j0 - LB_H + lj, ii = i0 - LB_H + li;
+        long long* p = comp == 0 ? gadd.gy + jj * X + ii : gadd.gx + jj * XP + ii;
+        ::atomicAdd(reinterpret_cast<unsigned long long*>(p), v);
+    }
+}
+
+// alpha (L^T g) at (j, i) of a component array [n0][n1]: the transposed replicate-padded 5-point Laplacian in gather form -- a neighbour
+// q - delta inside the array contributes g there, a direction that leaves the array contributes g[q] itself
+__device__ __forceinline__ float lapT5(const long long* g, float qi, float sc_here, const float* scm, int n0, int n1, int j, int i) {
+    const int c = j * n1 + i;
+    auto at = [&](int q) { const float v = __ll2float_rn(g[q]) * qi; return scm ? v * (1.f - scm[q]) : v; };
+    const float v = __ll2float_rn(g[c]) * qi * sc_here;
+    float acc = -4.f * v;
+    acc += j + 1 < n0 ? at(c + n1) : v;
+    acc += j > 0 ? at(c - n1) : v;
+    acc += i + 1 < n1 ? at(c + 1) : v;
+    acc += i > 0 ? at(c - 1) : v;
+    return acc;
+}
+
+__global__ void __launch_bounds__(256) k_lb_diffuse_adj(LBArgs a) {
+    const int Y = a.Y, X = a.X, XP = X + 1, nVy = (Y + 1) * X, nVx = Y * XP;
+    const int b = blockIdx.y;
+    const float alpha = a.adt / a.re[b];
+    float qs, qi;
+    lb_scale(a.gmax + b * LB_SLOTS, qs, qi);
+    for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < nVy + nVx; e += gridDim.x * blockDim.x) {
+        if (e < nVy) {
+            const int j = e / X, i = e - j * X;
+            const long long* g = a.gcy + (size_t)b * nVy;
+            const float* m = a.bcm + (size_t)b * a.bc_stride;          // g' = g . (1 - bcm): the BC blend's adjoint
+            const float sc = 1.f - m[e];
+            a.giy[(size_t)b * nVy + e] = __ll2float_rn(g[e]) * qi * sc + alpha * lapT5(g, qi, sc, m, Y + 1, X, j, i);
+        } else {
+            const int q = e - nVy, j = q / XP, i = q - j * XP;
+            const long long* g = a.gcx + (size_t)b * nVx;
+            a.gix[(size_t)b * nVx + q] = __ll2float_rn(g[q]) * qi + alpha * lapT5(g, qi, 1.f, nullptr, Y, XP, j, i);
+        }
+    }
+}
+
+// the adjoint's own buffers in front of the solver's part: g_c (int64), g_a (fp32), the absmax slots; 256-byte granules
+struct BwdLayout {
+    long long* gc;
+    float* ga;
+    unsigned* gmax;
+    void* solver;
+    size_t bytes;
+};
+BwdLayout bwd_layout(const sol_karman_cfg* c, bool direct, void* ws) {
+    const size_t B = c->B, Y = c->Y, X = c->X, faces = (Y + 1) * X + Y * (X + 1);
+    char* w = ws ? reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(ws) + 255) / 256 * 256) : nullptr;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { char* p = w ? w + off : nullptr; off += align_up(bytes, 256); return p; };
+    BwdLayout l{};
+    l.gc = reinterpret_cast<long long*>(take(B * faces * sizeof(long long)));
+    l.ga = reinterpret_cast<float*>(take(B * faces * sizeof(float)));
+    l.gmax = reinterpret_cast<unsigned*>(take(B * LB_SLOTS * sizeof(unsigned)));
+    l.solver = take(sol_large_solver_bytes(c, direct));
+    l.bytes = off + 256;                       // + the alignment of the caller's pointer
+    return l;
+}
+
+int common_check(const sol_karman_cfg* c, const char* who) {
+    SOL_REQUIRE(c != nullptr, "%s: cfg is NULL", who);
+    SOL_REQUIRE(c->B >= 1 && c->B <= 65535 && c->Y >= 16 && c->X >= 16, "%s: B in [1, 65535], Y, X >= 16 (got %d, %d, %d)", who, c->B, c->Y, c->X);
+    SOL_REQUIRE((size_t)c->Y * c->X < ((size_t)1 << 28), "%s: grid too large for 32-bit face indices", who);
+    return SOL_OK;
+}
+
+}  // namespace
+
+extern "C" size_t sol_karman_step_bwd_large_workspace_bytes(const sol_karman_cfg* c) {
+    if (!c || c->B < 1 || c->Y < 1 || c->X < 1) return 0;
+    return bwd_layout(c, c->direct != nullptr, nullptr).bytes;
+}
+
+extern "C" int sol_karman_step_fwd_large_saved(const sol_karman_cfg* c, void* stream,
+                                               const float* d_in, const float* vy_in, const float* vx_in,
+                                               const float* re, const float* active, const float* inflow,
+                                               const float* velBCy, const float* velBCyMask, int64_t bc_batch_stride,
+                                               float* d_out, float* vy_out, float* vx_out, float* saved_vy, float* saved_vx,
+                                               const int32_t* direct_header_host,
+                                               const float* box_blob, const int32_t* box_header_host, int32_t* cg_info,
+                                               void* workspace, size_t workspace_bytes) {
+    const char* who = "sol_karman_step_fwd_large_saved";
+    if (int e = common_check(c, who)) return e;
+    const bool direct = c->direct != nullptr;
+    SOL_REQUIRE(vy_in && vx_in && re && active && velBCy && velBCyMask && vy_out && vx_out && saved_vy && saved_vx && workspace,
+                "%s: NULL pointer argument", who);
+    SOL_REQUIRE((d_in && inflow) || !d_out, "%s: density output requested without d_in / inflow", who);
+    if (direct) { if (int e = sol_large_direct_check(c, who, direct_header_host)) return e; }
+    else if (int e = sol_large_cg_check(c, who, box_blob, box_header_host, cg_info, workspace)) return e;
+    const size_t need = sol_large_solver_bytes(c, direct) + 256;
+    SOL_REQUIRE(workspace_bytes >= need, "%s: workspace too small (%zu < %zu bytes)", who, workspace_bytes, need);
+    const void* outs[] = {d_out, vy_out, vx_out, saved_vy, saved_vx, cg_info};
+    const void* ins[] = {d_in, vy_in, vx_in, re, active, inflow, velBCy, velBCyMask, box_blob};
+    for (const void* o : outs)
+        for (const void* i : ins) SOL_REQUIRE(!o || o != i, "%s: outputs must not alias the inputs", who);
+    SOL_REQUIRE(saved_vy != vy_out && saved_vx != vx_out && saved_vy != saved_vx, "%s: saved_vy / saved_vx must be buffers of their own", who);
+    void* solver = reinterpret_cast<void*>((reinterpret_cast<uintptr_t>(workspace) + 255) / 256 * 256);
+    const SolLargeStep io{d_in, vy_in, vx_in, re, active, inflow, velBCy, velBCyMask, bc_batch_stride, d_out, vy_out, vx_out, nullptr, nullptr};
+    return sol_large_step(c, (hipStream_t)stream, io, saved_vy, saved_vx, direct, direct_header_host, box_blob, cg_info, solver);
+}
+
+extern "C" int sol_karman_step_bwd_large(const sol_karman_cfg* c, void* stream,
+                                         const float* saved_vy, const float* saved_vx, const float* re, const float* active,
+                                         const float* velBCyMask, int64_t bc_batch_stride,
+                                         const float* g_vy_out, const float* g_vx_out, float* g_vy_in, float* g_vx_in,
+                                         const int32_t* direct_header_host,
+                                         const float* box_blob, const int32_t* box_header_host, int32_t* cg_info,
+                                         void* workspace, size_t workspace_bytes) {
+    const char* who = "sol_karman_step_bwd_large";
+    if (int e = common_check(c, who)) return e;
+    const bool direct = c->direct != nullptr;
+    SOL_REQUIRE(saved_vy && saved_vx && re && active && velBCyMask && g_vy_out && g_vx_out && g_vy_in && g_vx_in && workspace,
+                "%s: NULL pointer argument", who);
+    if (direct) { if (int e = sol_large_direct_check(c, who, direct_header_host)) return e; }
+    else if (int e = sol_large_cg_check(c, who, box_blob, box_header_host, cg_info, workspace)) return e;
+    const size_t need = bwd_layout(c, direct, nullptr).bytes;
+    SOL_REQUIRE(workspace_bytes >= need, "%s: workspace too small (%zu < %zu bytes)", who, workspace_bytes, need);
+    const void* outs[] = {g_vy_in, g_vx_in, cg_info};
+    const void* ins[] = {saved_vy, saved_vx, re, active, velBCyMask, g_vy_out, g_vx_out, box_blob};
+    for (const void* o : outs)
+        for (const void* i : ins) SOL_REQUIRE(!o || o != i, "%s: outputs must not alias the inputs", who);
+    SOL_REQUIRE(g_vy_in != g_vx_in, "%s: g_vy_in and g_vx_in must be buffers of their own", who);
+    const int B = c->B, Y = c->Y, X = c->X, N = Y * X;
+    const size_t nVy = (size_t)(Y + 1) * X, nVx = (size_t)Y * (X + 1), faces = nVy + nVx;
+    hipStream_t s = (hipStream_t)stream;
+    const BwdLayout l = bwd_layout(c, direct, workspace);
+    LBArgs a{};
+    a.B = B; a.Y = Y; a.X = X; a.dtdx = c->dt / c->dx; a.adt = c->dt * c->res * c->res; a.grad_pad = c->grad_pad;
+    a.re = re; a.active = active; a.bcm = velBCyMask; a.bc_stride = bc_batch_stride;
+    a.svy = saved_vy; a.svx = saved_vx; a.goy = g_vy_out; a.gox = g_vx_out;
+    a.gcy = l.gc; a.gcx = l.gc + B * nVy;
+    a.gay = l.ga; a.gax = l.ga + B * nVy;
+    a.gmax = l.gmax;
+    a.giy = g_vy_in; a.gix = g_vx_in;
+    a.rhs = sol_large_solver_rhs(c, direct, l.solver);
+    const unsigned gN = (unsigned)((N + 255) / 256), gF = (unsigned)((faces + 255) / 256);
+    SOL_LAUNCH(k_lb_rhs, dim3(gN, B), dim3(256), 0, s, a);
+    SOL_LAUNCH_CHECK();
+    float* q = nullptr;
+    if (int e = pressure_solve_any2d(s, c, direct, direct_header_host, box_blob, active, cg_info, l.solver, &q)) return e;
+    a.gdiv = q;
+    SOL_LAUNCH(k_lb_ga, dim3(gF, B), dim3(256), 0, s, a);
+    if (sol_opt().k2d_adj_tile) {
+        const int ntj = (Y + LB_T - 1) / LB_T, nti = (X + LB_T - 1) / LB_T;
+        SOL_LAUNCH(k_lb_advect_adj_tile, dim3(ntj * nti, B), dim3(256), 0, s, a, nti);
+    } else {
+        SOL_LAUNCH(k_lb_advect_adj, dim3(gF, B), dim3(256), 0, s, a);
+    }
+    SOL_LAUNCH(k_lb_diffuse_adj, dim3(gF, B), dim3(256), 0, s, a);
+    SOL_LAUNCH_CHECK();
+    return SOL_OK;
+}

@@ -269,12 +269,16 @@ struct Large {
     size_t bytes;
 };
 
-Large large_layout(const sol_karman_cfg* c, void* ws) {
+// with_sv = false: the solver's part alone (the adjoint's workspace, and pressure_solve_any2d on the address of the forward layout's
+// rhs buffer: every buffer starts on 256 bytes, so both carves of one workspace name the same addresses)
+Large large_layout(const sol_karman_cfg* c, void* ws, bool with_sv = true) {
     const size_t B = c->B, Y = c->Y, X = c->X, N = Y * X;
     Carve w(ws);
     Large l{};
-    l.svy = w.take<float>(B * (Y + 1) * X);
-    l.svx = w.take<float>(B * Y * (X + 1));
+    if (with_sv) {
+        l.svy = w.take<float>(B * (Y + 1) * X);
+        l.svx = w.take<float>(B * Y * (X + 1));
+    }
     float* R = w.take<float>(B * N);
     l.T1 = w.take<float>(B * N);
     l.T2 = w.take<float>(B * N);
@@ -287,9 +291,11 @@ Large large_layout(const sol_karman_cfg* c, void* ws) {
     return l;
 }
 
-// checks shared by the two entry points (before any launch)
-int large_check(const sol_karman_cfg* c, const char* who, const float* box_blob, const int32_t* hdr, const int32_t* cg_info,
-                const void* workspace, size_t workspace_bytes) {
+}  // namespace
+
+// checks of the CG solve's arguments (before any launch), shared with the adjoint (karman_large_bwd.hip)
+int sol_large_cg_check(const sol_karman_cfg* c, const char* who, const float* box_blob, const int32_t* hdr, const int32_t* cg_info,
+                       const void* workspace) {
     SOL_REQUIRE(c != nullptr, "cfg is NULL");
     SOL_REQUIRE(c->B >= 1 && c->B <= 65535 && c->Y >= 16 && c->X >= 16, "%s: B in [1, 65535], Y, X >= 16 (got %d, %d, %d)", who, c->B, c->Y, c->X);
     SOL_REQUIRE((size_t)c->Y * c->X < ((size_t)1 << 30), "%s: grid too large", who);
@@ -302,6 +308,15 @@ int large_check(const sol_karman_cfg* c, const char* who, const float* box_blob,
     SOL_REQUIRE(hdr[1] == c->Y && hdr[2] == c->X, "%s: the box blob is for a %dx%d grid, cfg is %dx%d", who, hdr[1], hdr[2], c->Y, c->X);
     SOL_REQUIRE(hdr[5] == 0 && hdr[6] == 0, "%s: the CG solve needs the empty-box blob (nS = 0: precond.box_solver_blob), this one has nS = %d",
                 who, hdr[5]);
+    return SOL_OK;
+}
+
+namespace {
+
+// checks shared by the two entry points (before any launch)
+int large_check(const sol_karman_cfg* c, const char* who, const float* box_blob, const int32_t* hdr, const int32_t* cg_info,
+                const void* workspace, size_t workspace_bytes) {
+    if (int e = sol_large_cg_check(c, who, box_blob, hdr, cg_info, workspace)) return e;
     SOL_REQUIRE(workspace_bytes >= large_layout(c, nullptr).bytes, "%s: workspace too small (%zu < %zu bytes)", who, workspace_bytes,
                 large_layout(c, nullptr).bytes);
     return SOL_OK;
@@ -326,6 +341,37 @@ __global__ void __launch_bounds__(PCG_T) large_copy(float* __restrict__ dst, con
 }
 
 }  // namespace
+
+// ---- karman-2d large grids: the pressure solve the caller selects, M x = b, on a solver workspace of sol_large_solver_bytes ----
+// direct: the capacitance solve on cfg.direct (hdr = its host header); else PCG with the empty-box solve of box_blob as preconditioner,
+// reporting to cg_info [2][B].  The caller writes b into sol_large_solver_rhs(...) (overwritten); *x = the buffer that holds the solution.
+size_t sol_large_solver_bytes(const sol_karman_cfg* c, bool direct) {
+    return direct ? sol_large_direct_floats(c) * sizeof(float) + 256 : large_layout(c, nullptr, false).bytes;
+}
+
+float* sol_large_solver_rhs(const sol_karman_cfg* c, bool direct, void* ws) {
+    return direct ? static_cast<float*>(ws) : large_layout(c, ws, false).a.r;
+}
+
+int pressure_solve_any2d(hipStream_t s, const sol_karman_cfg* c, bool direct, const int32_t* hdr, const float* box_blob, const float* active,
+                         int32_t* cg_info, void* ws, float** x) {
+    if (direct) {
+        *x = static_cast<float*>(ws);
+        return sol_large_direct_solve(s, c, hdr, *x);
+    }
+    const Large l = large_layout(c, ws, false);
+    *x = l.a.x;
+    return large_solve(s, c, box_blob, active, l, cg_info);
+}
+
+// diffuse / advect / rhs, the solve, the projection: the whole forward step (sv_y, sv_x: where the post-diffusion velocity goes)
+int sol_large_step(const sol_karman_cfg* c, hipStream_t s, const SolLargeStep& io, float* svy, float* svx, bool direct, const int32_t* hdr,
+                   const float* box_blob, int32_t* cg_info, void* solver_ws) {
+    if (int e = sol_large_front(c, s, io, svy, svx, sol_large_solver_rhs(c, direct, solver_ws))) return e;
+    float* p = nullptr;
+    if (int e = pressure_solve_any2d(s, c, direct, hdr, box_blob, io.active, cg_info, solver_ws, &p)) return e;
+    return sol_large_project(c, s, io, p);
+}
 
 size_t k3_pcg_workspace_bytes(const sol_karman3d_cfg* c) {
     size_t bytes = 0;
@@ -381,9 +427,7 @@ extern "C" int sol_karman_step_fwd_large_cg(const sol_karman_cfg* c, void* strea
     hipStream_t s = (hipStream_t)stream;
     const Large l = large_layout(c, workspace);
     const SolLargeStep io{d_in, vy_in, vx_in, re, active, inflow, velBCy, velBCyMask, bc_batch_stride, d_out, vy_out, vx_out, feat_out, feat_scale};
-    if (int e = sol_large_front(c, s, io, l.svy, l.svx, l.a.r)) return e;
-    if (int e = large_solve(s, c, box_blob, active, l, cg_info)) return e;
-    return sol_large_project(c, s, io, l.a.x);
+    return sol_large_step(c, s, io, l.svy, l.svx, false, nullptr, box_blob, cg_info, l.a.r);
 }
 
 extern "C" int sol_karman_pressure_solve_large(const sol_karman_cfg* c, void* stream, const float* active, const float* rhs, float* p,

@@ -216,10 +216,9 @@ class KarmanFlow:
         info = {}
         self.pressure_solver_used = masks.pressure_solver        # "direct" or "cg" (SceneMasks' choice for this grid and scene)
         if masks.large:
-            # beyond the one-workgroup kernels (data generation at 256 x 128, karman.py:98-159): forward-only path, direct solve
-            # where the scene's blob builds, else the preconditioned CG (solve_info: iterations / converged per simulation)
-            if torch.is_grad_enabled() and (vy.requires_grad or vx.requires_grad):
-                raise NotImplementedError("the large-grid solver step (%dx%d) is forward only" % (Y, X))
+            # beyond the one-workgroup kernels (data generation at 256 x 128, karman.py:98-159): the multi-launch path, direct solve
+            # where the scene's blob builds, else the preconditioned CG (solve_info: iterations / converged per simulation, and
+            # iterations_bwd / converged_bwd after backward()); differentiable like the small path (ops.KarmanStepLargeFn)
             n = ops.large_workspace_bytes(cfg, masks)
             if getattr(self, "_large_ws", None) is None or self._large_ws[0] != (B, Y, X, str(dev)) or self._large_ws[1].numel() * 4 < n:
                 self._large_ws = ((B, Y, X, str(dev)), torch.empty((n + 3) // 4, dtype=torch.float32, device=dev))

@@ -60,7 +60,7 @@ class SceneMasks:
         want = os.environ.get("SOL_PRESSURE_SOLVER", pressure_solver)
         if want not in ("auto", "direct", "cg"):
             raise ValueError("pressure_solver must be 'auto', 'direct' or 'cg' (got %r)" % (want,))
-        self.large = Y * X > 8192 or X > 64          # beyond the one-workgroup kernels: forward-only multi-launch path
+        self.large = Y * X > 8192 or X > 64          # beyond the one-workgroup kernels: the multi-launch path (karman_step_large)
         if want != "cg" and (self.large or _lib.load().sol_karman_direct_supported(Y, X)):
             from .precond import direct_solver_blob
             blob = direct_solver_blob(self.active.reshape(Y, X).cpu().numpy(), max_window=64 if self.large else 16)
@@ -89,16 +89,79 @@ def large_workspace_bytes(cfg, masks):
     return lib.sol_karman_step_large_workspace_bytes(C.byref(cfg))
 
 
+def _hdr(a):
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+class KarmanStepLargeFn(torch.autograd.Function):
+    """The large-grid step with its hand-written adjoint (sol_karman_step_fwd_large_saved / sol_karman_step_bwd_large), for the scene's
+    solver (direct or CG).  Differentiable with respect to the velocity; the density is a passive tracer."""
+
+    @staticmethod
+    def forward(ctx, d, vy, vx, re, cfg, masks, workspace, info):
+        lib = _lib.load()
+        B = cfg.B
+        d, vy, vx = d.contiguous(), vy.contiguous(), vx.contiguous()
+        nbytes = large_workspace_bytes(cfg, masks)
+        if workspace is None or workspace.numel() * 4 < nbytes:
+            workspace = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=vy.device)
+        d_out, vy_out, vx_out = torch.empty_like(d), torch.empty_like(vy), torch.empty_like(vx)
+        svy, svx = torch.empty_like(vy), torch.empty_like(vx)
+        cg = masks.direct is None
+        cg_info = torch.empty(2, B, dtype=torch.int32, device=vy.device) if cg else None
+        check(lib.sol_karman_step_fwd_large_saved(
+            C.byref(cfg), stream(), ptr(d), ptr(vy), ptr(vx), ptr(re), ptr(masks.active), ptr(masks.inflow), ptr(masks.velBCy),
+            ptr(masks.velBCyMask), masks.bc_stride, ptr(d_out), ptr(vy_out), ptr(vx_out), ptr(svy), ptr(svx),
+            _hdr(masks.direct_header), ptr(masks.box), _hdr(masks.box_header), ptr(cg_info), ptr(workspace), workspace.numel() * 4))
+        if cg and info is not None:
+            info["iterations"], info["converged"] = cg_info[0], cg_info[1]
+        ctx.save_for_backward(svy, svx, re)
+        ctx.cfg, ctx.masks, ctx.info = cfg, masks, info
+        ctx.mark_non_differentiable(d_out)
+        return d_out, vy_out, vx_out
+
+    @staticmethod
+    def backward(ctx, _gd, gvy, gvx):
+        svy, svx, re = ctx.saved_tensors
+        gvy = torch.zeros_like(svy) if gvy is None else gvy.contiguous()
+        gvx = torch.zeros_like(svx) if gvx is None else gvx.contiguous()
+        oy, ox = karman_step_large_bwd(svy, svx, re, gvy, gvx, ctx.cfg, ctx.masks, info=ctx.info)
+        return None, oy, ox, None, None, None, None, None
+
+
+def karman_step_large_bwd(svy, svx, re, gvy, gvx, cfg, masks, workspace=None, info=None):
+    """Adjoint of the large-grid step (sol_karman_step_bwd_large): (g_vy_in, g_vx_in) from the saved post-diffusion velocity and the
+    gradient with respect to the step's output velocity.  With the CG solve, `info` receives "iterations_bwd" / "converged_bwd"."""
+    lib = _lib.load()
+    nbytes = lib.sol_karman_step_bwd_large_workspace_bytes(C.byref(cfg))
+    if workspace is None or workspace.numel() * 4 < nbytes:
+        workspace = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=svy.device)
+    oy, ox = torch.empty_like(svy), torch.empty_like(svx)
+    cg = masks.direct is None
+    cg_info = torch.empty(2, cfg.B, dtype=torch.int32, device=svy.device) if cg else None
+    check(lib.sol_karman_step_bwd_large(
+        C.byref(cfg), stream(), ptr(svy), ptr(svx), ptr(re), ptr(masks.active), ptr(masks.velBCyMask), masks.bc_stride,
+        ptr(gvy), ptr(gvx), ptr(oy), ptr(ox), _hdr(masks.direct_header), ptr(masks.box), _hdr(masks.box_header), ptr(cg_info),
+        ptr(workspace), workspace.numel() * 4))
+    if cg and info is not None:
+        info["iterations_bwd"], info["converged_bwd"] = cg_info[0], cg_info[1]
+    return oy, ox
+
+
 def karman_step_large(d, vy, vx, re, cfg, masks, workspace=None, info=None):
-    """Forward-only step for grids beyond the one-workgroup kernels (data generation at 256 x 128,
+    """The step for grids beyond the one-workgroup kernels (data generation at 256 x 128,
     /root/reference/karman-2d/karman.py:98-159): sol_karman_step_fwd_large (direct solve) or sol_karman_step_fwd_large_cg (CG solve,
     masks.pressure_solver == "cg").  Returns (d, vy, vx) after the step; with the CG solve, `info` (a dict) receives "iterations" and
-    "converged", device int32 [B] each."""
+    "converged", device int32 [B] each.  When grad is enabled and vy or vx requires a gradient the call goes through KarmanStepLargeFn
+    (same forward launches, plus the saved post-diffusion velocity) and `info` also receives "iterations_bwd" / "converged_bwd" after
+    backward(); otherwise nothing is kept."""
     _lib.require_gpu()
     lib = _lib.load()
     d, vy, vx, re = (_lib.f32(t) for t in (d, vy, vx, re))
     B, Y, X = cfg.B, cfg.Y, cfg.X
     assert vy.shape == (B, Y + 1, X) and vx.shape == (B, Y, X + 1) and d.shape == (B, Y, X) and re.shape == (B,)
+    if torch.is_grad_enabled() and (vy.requires_grad or vx.requires_grad):
+        return KarmanStepLargeFn.apply(d, vy, vx, re, cfg, masks, workspace, info)
     nbytes = large_workspace_bytes(cfg, masks)
     if workspace is None or workspace.numel() * 4 < nbytes:
         workspace = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=vy.device)

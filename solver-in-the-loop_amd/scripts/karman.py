@@ -2,7 +2,7 @@
 """karman-2d data generation -- same flags as /root/reference/karman-2d/karman.py:33-47, the loop of
 :138-159 on the fused HIP solver step (one kernel launch per frame, state stays on the GPU).
 -r <= 64 runs the fused one-workgroup-per-simulation kernel; larger grids (the reference's 256x128 `-r 128`
-reference solutions, Makefile:19-28) run the forward-only multi-launch path: the direct pressure solver where the scene's blob builds,
+reference solutions, Makefile:19-28) run the multi-launch path (nothing is kept for a backward pass here): the direct pressure solver where the scene's blob builds,
 else the preconditioned CG.  --obstacle / --obstacle-mask choose the scene (recorded in params.pickle as "scene")."""
 import argparse
 import pickle

@@ -39,6 +39,15 @@ def _karman_fwd_saved(d, vy, vx, re, scene):
     d, vy, vx, re = (_lib.f32(t) for t in (d, vy, vx, re))
     d_out, vy_out, vx_out = torch.empty_like(d), torch.empty_like(vy), torch.empty_like(vx)
     svy, svx = torch.empty_like(vy), torch.empty_like(vx)
+    if masks.large:         # beyond the one-workgroup kernels: the multi-launch step of the scene's solver (direct or CG)
+        nbytes = ops.large_workspace_bytes(cfg, masks)
+        ws = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=vy.device)
+        cg_info = torch.empty(2, cfg.B, dtype=torch.int32, device=vy.device) if masks.direct is None else None
+        check(lib.sol_karman_step_fwd_large_saved(
+            C.byref(cfg), stream(), ptr(d), ptr(vy), ptr(vx), ptr(re), ptr(masks.active), ptr(masks.inflow), ptr(masks.velBCy),
+            ptr(masks.velBCyMask), masks.bc_stride, ptr(d_out), ptr(vy_out), ptr(vx_out), ptr(svy), ptr(svx),
+            ops._hdr(masks.direct_header), ptr(masks.box), ops._hdr(masks.box_header), ptr(cg_info), ptr(ws), ws.numel() * 4))
+        return d_out, vy_out, vx_out, svy, svx
     check(lib.sol_karman_step_fwd(C.byref(cfg), stream(), ptr(d), ptr(vy), ptr(vx), ptr(re), ptr(masks.active), ptr(masks.inflow),
                                   ptr(masks.velBCy), ptr(masks.velBCyMask), masks.bc_stride, ptr(d_out), ptr(vy_out), ptr(vx_out),
                                   ptr(svy), ptr(svx), None, None, None))
@@ -49,6 +58,8 @@ def _karman_bwd(svy, svx, re, gvy, gvx, scene):
     cfg, masks = _SCENES[scene]
     lib = _lib.load()
     gvy, gvx = gvy.contiguous(), gvx.contiguous()
+    if masks.large:
+        return ops.karman_step_large_bwd(svy.contiguous(), svx.contiguous(), _lib.f32(re), gvy, gvx, cfg, masks)
     oy, ox = torch.empty_like(svy), torch.empty_like(svx)
     check(lib.sol_karman_step_bwd(C.byref(cfg), stream(), ptr(svy), ptr(svx), ptr(re), ptr(masks.active), ptr(masks.velBCyMask),
                                   masks.bc_stride, ptr(gvy), ptr(gvx), None, None, ptr(oy), ptr(ox), None))
@@ -56,6 +67,10 @@ def _karman_bwd(svy, svx, re, gvy, gvx, scene):
 
 
 def _karman_step(d, vy, vx, re, scene):
+    cfg, masks = _SCENES[scene]
+    if masks.large:         # no gradient wanted: the plain forward entry points, nothing saved
+        with torch.no_grad():
+            return ops.karman_step_large(d, vy, vx, re, cfg, masks)
     return _karman_fwd_saved(d, vy, vx, re, scene)[:3]
 
 

@@ -55,6 +55,16 @@ class _conv_precision_scope:
         return False
 
 
+def _refuse_large_grid(who, Y, X):
+    """The trainers stop at the one-workgroup solver grids: the solver step itself is differentiable beyond them (ops.KarmanStepLargeFn),
+    but the 5x5 weight gradient is built for image rows of W <= 64 pixels (sol_conv5x5_bwd_weight, csrc/conv5x5.hip).  Refused here, at
+    construction, instead of in the middle of the first reverse sweep."""
+    if Y * X > 8192 or X > 64:
+        raise ValueError("%s: a %dx%d domain is beyond the trainers -- the 5x5 weight gradient (sol_conv5x5_bwd_weight) is built for "
+                         "W <= 64 and the fused solver adjoint for at most 8192 cells; differentiate single large-grid steps with "
+                         "KarmanFlow.step / ops.karman_step_large" % (who, Y, X))
+
+
 class SolTrainer:
     def __init__(self, net, masks, B, Y, X, msteps, dx, std_v, std_re, dt=1.0, res=None,
                  clip_grad=False, beta1=0.9, beta2=0.999, eps=1e-8, group=None, use_graph=True,
@@ -66,6 +76,7 @@ class SolTrainer:
         it for the duration of the call (and restores the previous value), so trainers of different precision can alternate in
         one process.  None keeps whatever the option table holds
         (e.g. a SOL_CONV_NO_SB / SOL_CONV_NO_FP16 debugging override applied when the library was loaded)."""
+        _refuse_large_grid("SolTrainer", Y, X)
         _lib.require_gpu()
         self.lib = _lib.load()
         self.conv_precision = _conv_precision_code(conv_precision)
@@ -263,6 +274,7 @@ class GraphTrainer:
             raise ValueError("schedule must be 'manual' or 'autograd'")
         self.schedule = schedule
         self._sched = None
+        _refuse_large_grid("GraphTrainer", Y, X)
         from . import fluid, karman
         _lib.require_gpu()
         self.lib = _lib.load()
