@@ -514,4 +514,8 @@ __device__ __forceinline__ void amax_publish_last(float v, unsigned* slots, unsi
     }
 }
 
+
+// index clamp of the large-grid 2-D and the 3-D sources (karman_step.hip keeps an identical one of its own in its anonymous namespace)
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }

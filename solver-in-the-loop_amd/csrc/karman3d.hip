@@ -21,7 +21,7 @@
 //   k3_project      v -= mask * grad p, fused to_feature (4 channels: three components + Re)
 // The adjoint of the step (sol_karman3d_step_bwd: k3b_* kernels, second half of this file) reverses these stages; its
 // advection scatter runs in 64-bit fixed point and is bit-reproducible.
-#include "common.hpp"
+#include "fixed_scatter.hpp"
 
 namespace {
 
@@ -38,8 +38,6 @@ struct K3Args {
     const float* p;
     float fs0, fs1, fs2, fs3;
 };
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // 7-point replicate-padded Laplacian of one component array [n0][n1][n2] at (j, i, k)
 __device__ __forceinline__ float lap7(const float* f, int n0, int n1, int n2, int j, int i, int k) {
@@ -778,13 +776,9 @@ int pressure_solve_any3d(hipStream_t s, const sol_karman3d_cfg* c, const int32_t
 //   k3b_gva        g_a = mask . (g_out + D^T g_div)          (adjoint of the divergence and of the hard-BC face masks)
 //   k3b_advect_adj scatter of g_a through the trilinear gathers of the semi-Lagrangian step, for the field term AND the
 //                  back-trace (velocity) term, into g_c.  The scatter runs in 64-bit FIXED POINT (global_atomic_add_x2 on
-//                  int64 accumulators, scale = a power of two with max|g_a| * scale in [2^37, 2^38): integer addition is
-//                  order independent, so the adjoint is reproducible BIT FOR BIT (run twice, compare) --
-//                  the scheme of the 2-D kernels (int32 into LDS) with the headroom global memory affords:
-//                  2^25 single-contribution range above max|g_a|, resolution 2^-37 max|g_a|.  Bounds, stated: a FINITE contribution
-//                  beyond 2^25 max|g_a| saturates in __float2ll_rn (the back-trace term is g_a times a velocity DIFFERENCE of the
-//                  saved field times dt/dx: it would take |dv| dt/dx > 3e7, i.e. a simulation that has already blown up); a
-//                  NON-FINITE g_a poisons the whole simulation's input gradient (k3b_gva publishes a NaN maximum, k3b_scale).
+//                  int64 accumulators): integer addition is order independent, so the adjoint is reproducible BIT FOR BIT
+//                  (run twice, compare).  fixed_scatter.hpp states the scheme, its range, its resolution
+//                  and what a non-finite g_a does.
 //   k3b_diffuse_adj g_in = (I + alpha L^T)(g_c . (1 - bcm))  (gather form of the transposed replicate-padded Laplacian; converts
 //                  the fixed-point g_c back to fp32 as it reads it)
 // ========================================================================================================================
@@ -798,27 +792,11 @@ struct K3BArgs {
     const float *goy, *gox, *goz;           // gradient w.r.t. the step's output velocity
     float *gay, *gax, *gaz;                 // g_a
     long long *gcy, *gcx, *gcz;             // g_c: int64 fixed-point accumulators (zeroed by k3b_rhs before the scatter)
-    unsigned* gmax;                         // [B][K3B_SLOTS] bits of max|g_a| per simulation (zeroed by k3b_rhs, published by k3b_gva)
+    unsigned* gmax;                         // [B][FX_SLOTS] bits of max|g_a| per simulation (zeroed by k3b_rhs, published by k3b_gva)
     float *giy, *gix, *giz;                 // result: gradient w.r.t. the step's input velocity
     float* rhs;
     const float* gdiv;
 };
-
-constexpr int K3B_SLOTS = 64;            // absmax slots per simulation (one per lane of the reading wave; same-address atomics serialise in the L2)
-constexpr int K3B_FIXBITS = 37;           // max|g_a| * 2^shift lies in [2^37, 2^38)
-// power-of-two fixed-point scale of simulation b's scatter and its inverse, from the published max|g_a| (wave-uniform result)
-__device__ __forceinline__ void k3b_scale(const unsigned* gmax_b, float& qs, float& qi) {
-    const unsigned m = amax_wave_max(gmax_b[threadIdx.x & (K3B_SLOTS - 1)]);
-    if (m >= 0x7f800000u) {                   // k3b_gva met an inf / nan gradient in this simulation: nothing is scattered (qs = 0) and the
-        qs = 0.f;                             // conversion back (k3b_diffuse_adj: value * qi) makes EVERY input gradient of the simulation NaN --
-        qi = __uint_as_float(0x7fc00000u);    // as the fp32 atomics this scheme replaced did, instead of laundering it into finite numbers
-        return;
-    }
-    int e = (int)(m >> 23) - 127;
-    e = m == 0u ? 0 : min(max(e, -80), 120);
-    qs = __uint_as_float((unsigned)(K3B_FIXBITS - e + 127) << 23);
-    qi = __uint_as_float((unsigned)(e - K3B_FIXBITS + 127) << 23);
-}
 
 template <int AX>
 __device__ __forceinline__ bool boundary_face(int Y, int X, int Z, int j, int i, int k) {
@@ -843,7 +821,7 @@ __global__ void __launch_bounds__(256) k3b_rhs(K3BArgs a) {
     const size_t faces = (size_t)(Y + 1) * X * Z + (size_t)Y * (X + 1) * Z + (size_t)Y * X * (Z + 1);
     uint4* zc = reinterpret_cast<uint4*>(a.gcy) + (size_t)b * (faces / 2);     // faces is even for the grids check_blob3d admits (asserted by the host)
     for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < faces / 2; e += (size_t)gridDim.x * blockDim.x) zc[e] = make_uint4(0u, 0u, 0u, 0u);
-    if (blockIdx.x == 0 && threadIdx.x < K3B_SLOTS) a.gmax[b * K3B_SLOTS + threadIdx.x] = 0u;
+    if (blockIdx.x == 0 && threadIdx.x < FX_SLOTS) a.gmax[b * FX_SLOTS + threadIdx.x] = 0u;
 }
 
 __global__ void __launch_bounds__(256) k3b_gva(K3BArgs a) {
@@ -884,36 +862,19 @@ __global__ void __launch_bounds__(256) k3b_gva(K3BArgs a) {
             }
         }
     }
-    // max|g_a| of this simulation -> the scale of the fixed-point scatter (one atomic per workgroup).  A non-finite g_a publishes
-    // the bits of a NaN -- the largest value the integer maximum can see -- and k3b_scale turns that into "scatter nothing, convert
-    // back to NaN": the simulation's input gradient is NaN, not a finite number made of saturated integer conversions.
-    __shared__ unsigned red[16];
-    const unsigned wmax = amax_wave_max(bad ? 0x7fc00000u : __float_as_uint(vmax));
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = wmax;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned mb = 0u;
-        for (int w = 0; w < (int)(blockDim.x >> 6); ++w) mb = max(mb, red[w]);
-        // (thousands of workgroups share the 64 slots of a simulation and same-address atomics serialise in the L2, ~0.3 us apiece:
-        //  33 us for this kernel.  A workgroup whose maximum does not exceed what the slot already holds has nothing to publish;
-        //  the maximum is order independent, so the filter changes nothing but the number of atomics.)
-        unsigned* slot = &a.gmax[b * K3B_SLOTS + (blockIdx.x & (K3B_SLOTS - 1))];
-        if (mb > __atomic_load_n(slot, __ATOMIC_RELAXED)) atomicMax(slot, mb);
-    }
+    fx_publish_max(a.gmax + b * FX_SLOTS, vmax, bad);      // max|g_a| of this simulation -> the scale of the fixed-point scatter
 }
 
-// adjoint of one advected face value of component C at (j, i, k): gs = g_a there
-// Where a contribution goes.  GAdd: straight into the int64 accumulators in global memory.  TAdd (k3b_advect_adj_tile): into the workgroup's int64
-// LDS window when the target face lies inside it, else into global memory -- integer adds commute, so both give the same bits.
-// Order-independent accumulation: round to the fixed-point grid FIRST (each contribution on its own), then integer add.
+// Where a contribution goes (fx_add).  GAdd: straight into the int64 accumulators in global memory.  TAdd (k3b_advect_adj_tile): into the
+// workgroup's int64 LDS window when the target face lies inside it, else into global memory.
 struct GAdd {
     long long *gy, *gx, *gz;
     float qs;
     int X, Z;
-    __device__ __forceinline__ void operator()(int comp, int jj, int ii, int kk, float v) const {
-        long long* p = comp == 0 ? gy + ((size_t)jj * X + ii) * Z + kk : (comp == 1 ? gx + ((size_t)jj * (X + 1) + ii) * Z + kk : gz + ((size_t)jj * X + ii) * (Z + 1) + kk);
-        ::atomicAdd(reinterpret_cast<unsigned long long*>(p), (unsigned long long)__float2ll_rn(v * qs));
+    __device__ __forceinline__ long long* at(int comp, int jj, int ii, int kk) const {
+        return comp == 0 ? gy + ((size_t)jj * X + ii) * Z + kk : (comp == 1 ? gx + ((size_t)jj * (X + 1) + ii) * Z + kk : gz + ((size_t)jj * X + ii) * (Z + 1) + kk);
     }
+    __device__ __forceinline__ void operator()(int comp, int jj, int ii, int kk, float v) const { fx_add(at(comp, jj, ii, kk), v, qs); }
 };
 constexpr int K3B_TJ = 4, K3B_TH = 2, K3B_TW = K3B_TJ + 2 * K3B_TH;      // tile of 4 x 4 columns, window of 8 x 8 columns (halo 2: CFL < 2)
 struct TAdd {
@@ -922,12 +883,12 @@ struct TAdd {
     int jw0, iw0, ZP;
     __device__ __forceinline__ void operator()(int comp, int jj, int ii, int kk, float v) const {
         const int lj = jj - jw0, li = ii - iw0;
-        if ((unsigned)lj < (unsigned)K3B_TW && (unsigned)li < (unsigned)K3B_TW)
-            ::atomicAdd(&L[((comp * K3B_TW + lj) * K3B_TW + li) * ZP + kk], (unsigned long long)__float2ll_rn(v * g.qs));
+        if ((unsigned)lj < (unsigned)K3B_TW && (unsigned)li < (unsigned)K3B_TW) fx_add(&L[((comp * K3B_TW + lj) * K3B_TW + li) * ZP + kk], v, g.qs);
         else g(comp, jj, ii, kk, v);
     }
 };
 
+// adjoint of one advected face value of component C at (j, i, k): gs = g_a there
 template <int C, class Add>
 __device__ __forceinline__ void advect_adj_point(const K3BArgs& a, const GR& r, const Add& add, int j, int i, int k, float gs) {
     // no fused multiply-adds here: which products the compiler contracts depends on the kernel this is inlined into, and the two scatter
@@ -1007,7 +968,7 @@ __global__ void __launch_bounds__(256) k3b_advect_adj(K3BArgs a) {
     long long* gx = a.gcx + (size_t)b * nVx;
     long long* gz = a.gcz + (size_t)b * nVz;
     float qs, qi;
-    k3b_scale(a.gmax + b * K3B_SLOTS, qs, qi);
+    fx_scale(a.gmax + b * FX_SLOTS, qs, qi);
     const GAdd add{gy, gx, gz, qs, X, Z};
     const int cY = (Y + 1) * X, cX = Y * (X + 1), cC = Y * X;
     const int lane = threadIdx.x & 63;
@@ -1042,11 +1003,11 @@ __global__ void __launch_bounds__(256) k3b_advect_adj_tile(K3BArgs a, int nti) {
     GR r;
     r.sy = a.svy + (size_t)b * nVy; r.sx = a.svx + (size_t)b * nVx; r.sz = a.svz + (size_t)b * nVz; r.Y = Y; r.X = X; r.Z = Z;
     float qs, qi;
-    k3b_scale(a.gmax + b * K3B_SLOTS, qs, qi);
+    fx_scale(a.gmax + b * FX_SLOTS, qs, qi);
     const GAdd gadd{a.gcy + (size_t)b * nVy, a.gcx + (size_t)b * nVx, a.gcz + (size_t)b * nVz, qs, X, Z};
     const TAdd add{gadd, smem_adj, j0 - K3B_TH, i0 - K3B_TH, ZP};
     const int ncell = 3 * K3B_TW * K3B_TW * ZP;
-    for (int e = threadIdx.x; e < ncell; e += 256) smem_adj[e] = 0ull;
+    fx_window_clear(smem_adj, ncell, 256);
     __syncthreads();
     // column tasks: y faces j0 .. j1y-1 (the last tile row also owns face row Y), x faces i0 .. i1x-1 (the last tile column: face column X), cells
     const int j1 = min(j0 + K3B_TJ, Y), i1 = min(i0 + K3B_TJ, X);
@@ -1066,31 +1027,10 @@ __global__ void __launch_bounds__(256) k3b_advect_adj_tile(K3BArgs a, int nti) {
         }
     }
     __syncthreads();
-    for (int e = threadIdx.x; e < ncell; e += 256) {
-        const unsigned long long v = smem_adj[e];
-        if (v == 0ull) continue;                                   // (cells outside the arrays never receive a contribution)
+    fx_window_flush(smem_adj, ncell, 256, [&](int e) {
         const int kk = e % ZP, li = (e / ZP) % K3B_TW, lj = (e / (ZP * K3B_TW)) % K3B_TW, comp = e / (ZP * K3B_TW * K3B_TW);
-        const int jj = j0 - K3B_TH + lj, ii = i0 - K3B_TH + li;
-        long long* p = comp == 0 ? gadd.gy + ((size_t)jj * X + ii) * Z + kk : (comp == 1 ? gadd.gx + ((size_t)jj * (X + 1) + ii) * Z + kk : gadd.gz + ((size_t)jj * X + ii) * (Z + 1) + kk);
-        ::atomicAdd(reinterpret_cast<unsigned long long*>(p), v);
-    }
-}
-
-// (I + alpha L^T) g at (j, i, k) of a component array [n0][n1][n2]: the transposed replicate-padded 7-point Laplacian in gather
-// form -- a neighbour q - delta inside the array contributes g there, a direction that leaves the array contributes g[q] itself
-__device__ __forceinline__ float lapT7(const long long* g, float qi, float sc_here, const float* scm, int n0, int n1, int n2, int j, int i, int k) {
-    const size_t s0 = (size_t)n1 * n2, s1 = n2;
-    const size_t c = (size_t)j * s0 + (size_t)i * s1 + k;
-    auto at = [&](size_t q) { const float v = __ll2float_rn(g[q]) * qi; return scm ? v * (1.f - scm[q]) : v; };
-    const float v = __ll2float_rn(g[c]) * qi * sc_here;
-    float acc = -6.f * v;
-    acc += j + 1 < n0 ? at(c + s0) : v;
-    acc += j > 0 ? at(c - s0) : v;
-    acc += i + 1 < n1 ? at(c + s1) : v;
-    acc += i > 0 ? at(c - s1) : v;
-    acc += k + 1 < n2 ? at(c + 1) : v;
-    acc += k > 0 ? at(c - 1) : v;
-    return acc;
+        return gadd.at(comp, j0 - K3B_TH + lj, i0 - K3B_TH + li, kk);
+    });
 }
 
 __global__ void __launch_bounds__(256) k3b_diffuse_adj(K3BArgs a) {
@@ -1099,22 +1039,24 @@ __global__ void __launch_bounds__(256) k3b_diffuse_adj(K3BArgs a) {
     const int b = blockIdx.y;
     const float alpha = a.adt / a.re[b];
     float qs, qi;
-    k3b_scale(a.gmax + b * K3B_SLOTS, qs, qi);
+    fx_scale(a.gmax + b * FX_SLOTS, qs, qi);
+    // g' + alpha L^T g' as ONE rounding of the centre product plus the rounded alpha * (L^T g'): the fused multiply-add is spelled out,
+    // because which of the two products the compiler fuses depends on what else uses the centre value, and the bits move with it
     for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < nVy + nVx + nVz; e += gridDim.x * blockDim.x) {
         if (e < nVy) {
             const int k = e % Z, i = (e / Z) % X, j = e / (Z * X);
             const long long* g = a.gcy + (size_t)b * nVy;
             const float* m = a.bcm + (size_t)b * a.bc_stride;          // g' = g . (1 - bcm): the BC blend's adjoint
             const float sc = 1.f - m[e];
-            a.giy[(size_t)b * nVy + e] = __ll2float_rn(g[e]) * qi * sc + alpha * lapT7(g, qi, sc, m, Y + 1, X, Z, j, i, k);
+            a.giy[(size_t)b * nVy + e] = __fmaf_rn(fx_get(g, e, qi), sc, alpha * lapT<3>(g, qi, sc, m, e, {j, i, k}, {Y + 1, X, Z}));
         } else if (e < nVy + nVx) {
             const int q = e - nVy, k = q % Z, i = (q / Z) % (X + 1), j = q / (Z * (X + 1));
             const long long* g = a.gcx + (size_t)b * nVx;
-            a.gix[(size_t)b * nVx + q] = __ll2float_rn(g[q]) * qi + alpha * lapT7(g, qi, 1.f, nullptr, Y, X + 1, Z, j, i, k);
+            a.gix[(size_t)b * nVx + q] = fx_get_fma(g, q, qi, alpha * lapT<3>(g, qi, 1.f, nullptr, q, {j, i, k}, {Y, X + 1, Z}));
         } else {
             const int q = e - nVy - nVx, k = q % (Z + 1), i = (q / (Z + 1)) % X, j = q / ((Z + 1) * X);
             const long long* g = a.gcz + (size_t)b * nVz;
-            a.giz[(size_t)b * nVz + q] = __ll2float_rn(g[q]) * qi + alpha * lapT7(g, qi, 1.f, nullptr, Y, X, Z + 1, j, i, k);
+            a.giz[(size_t)b * nVz + q] = fx_get_fma(g, q, qi, alpha * lapT<3>(g, qi, 1.f, nullptr, q, {j, i, k}, {Y, X, Z + 1}));
         }
     }
 }
@@ -1195,7 +1137,7 @@ extern "C" size_t sol_karman3d_step_bwd_workspace_bytes(const sol_karman3d_cfg* 
     if (!c) return 0;
     const size_t B = c->B, Y = c->Y, X = c->X, Z = c->Z;
     // g_a (fp32) and g_c (int64 fixed point), three components each + rhs + two transform buffers + the absmax slots
-    const size_t floats = B * (3 * ((Y + 1) * X * Z + Y * (X + 1) * Z + Y * X * (Z + 1)) + 3 * Y * X * Z + K3B_SLOTS) + 256;
+    const size_t floats = B * (3 * ((Y + 1) * X * Z + Y * (X + 1) * Z + Y * X * (Z + 1)) + 3 * Y * X * Z + FX_SLOTS) + 256;
     return floats * sizeof(float) + k3_pcg_workspace_bytes(c);
 }
 
@@ -1225,7 +1167,7 @@ extern "C" int sol_karman3d_step_bwd(const sol_karman3d_cfg* c, void* stream,
     long long* gc = reinterpret_cast<long long*>(w); w += 2 * B * faces;
     a.gcy = gc; a.gcx = gc + B * nVy; a.gcz = a.gcx + B * nVx;
     a.gay = w; w += B * nVy; a.gax = w; w += B * nVx; a.gaz = w; w += B * nVz;
-    a.gmax = reinterpret_cast<unsigned*>(w); w += (size_t)B * K3B_SLOTS;
+    a.gmax = reinterpret_cast<unsigned*>(w); w += (size_t)B * FX_SLOTS;
     float* R = w; w += (size_t)B * N;
     float* T1 = w; w += (size_t)B * N;
     float* T2 = w; w += (size_t)B * N;

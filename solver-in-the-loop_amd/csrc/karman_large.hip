@@ -13,23 +13,11 @@
 //   k_l_project   v -= mask * grad p  (+ fused to_feature)
 // The adjoint of this path lives in karman_large_bwd.hip; it reads the post-diffusion velocity (sv_y, sv_x) that
 // sol_karman_step_fwd_large_saved hands out and runs the same pressure solve (pressure_solve_any2d, pcg.hip).
-#include "common.hpp"
+#include "large2d.hpp"
 
 namespace {
 
 constexpr int FDL_HEADER = 16;
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-__device__ __forceinline__ float acc_at(const float* act, int Y, int X, int j, int i) {   // 'boundary' extrapolation of the active mask
-    return act[clampi(j, 0, Y - 1) * X + clampi(i, 0, X - 1)] != 0.f ? 1.f : 0.f;
-}
-// hard-BC face masks: a face is open iff both cells it separates are accessible (outside the OPEN domain counts as accessible)
-__device__ __forceinline__ float mask_y(const float* act, int Y, int X, int j, int i) {   // face between rows j-1 and j
-    return acc_at(act, Y, X, j - 1, i) * acc_at(act, Y, X, j, i);
-}
-__device__ __forceinline__ float mask_x(const float* act, int Y, int X, int j, int i) {   // face between columns i-1 and i
-    return acc_at(act, Y, X, j, i - 1) * acc_at(act, Y, X, j, i);
-}
 
 struct LArgs {
     int B, Y, X;

@@ -9,30 +9,18 @@
 //                                                              (pressure_solve_any2d: direct launches or PCG)
 //   k_lb_ga           g_a = mask . (g_out + D^T g_div)         adjoint of rhs = -div and of the hard-BC face masks; publishes max|g_a|
 //   k_lb_advect_adj*  scatter of g_a through the bilinear gathers of the semi-Lagrangian step, for the field term AND the back-trace
-//                     (velocity) term, into g_c: int64 FIXED POINT (scale = a power of two with max|g_a| * scale in [2^37, 2^38)), so the
-//                     accumulation is order independent and the adjoint reproducible bit for bit.  Range, stated: a finite contribution
-//                     beyond 2^25 max|g_a| saturates in __float2ll_rn -- the back-trace term is g_a times a DIFFERENCE of the saved field
-//                     times dt/dx, so that takes |dv| dt/dx > 3e7, a simulation that has long blown up; a non-finite g_a makes the whole
-//                     simulation's input gradient NaN (k_lb_ga publishes a NaN maximum, lb_scale).  Resolution: 2^-37 max|g_a| per
-//                     contribution.  The default form accumulates in an int64 LDS window per 16 x 16-cell tile (halo 4 faces; targets
-//                     beyond the window go to global memory) and flushes one vector atomic per non-zero window cell.
+//                     (velocity) term, into g_c: int64 fixed point, order independent, so the adjoint is reproducible bit for bit
+//                     (fixed_scatter.hpp states the scheme, its range, its resolution and what a non-finite g_a does).  The default
+//                     form accumulates in an int64 LDS window per 16 x 16-cell tile (halo 4 faces; targets beyond the window go to
+//                     global memory) and flushes one vector atomic per non-zero window cell.
 //   k_lb_diffuse_adj  g_in = (I + alpha L^T)(g_c . (1 - bcm)) for v_y, (I + alpha L^T) g_c for v_x: gather form of the transposed
 //                     replicate-padded Laplacian; converts the fixed-point g_c back to fp32 as it reads it
-#include "common.hpp"
+#include "fixed_scatter.hpp"
+#include "large2d.hpp"
 
 namespace {
 
-constexpr int LB_SLOTS = 64;            // absmax slots per simulation (one per lane of the reading wave)
-constexpr int LB_FIXBITS = 37;          // max|g_a| * 2^shift lies in [2^37, 2^38)
 constexpr int LB_T = 16, LB_H = 4, LB_W = LB_T + 2 * LB_H + 1;      // tile of 16 x 16 cells; window of 25 x 25 faces per component
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-__device__ __forceinline__ float acc_at(const float* act, int Y, int X, int j, int i) {   // 'boundary' extrapolation of the active mask
-    return act[clampi(j, 0, Y - 1) * X + clampi(i, 0, X - 1)] != 0.f ? 1.f : 0.f;
-}
-// hard-BC face masks of the forward step (karman_large.hip)
-__device__ __forceinline__ float mask_y(const float* act, int Y, int X, int j, int i) { return acc_at(act, Y, X, j - 1, i) * acc_at(act, Y, X, j, i); }
-__device__ __forceinline__ float mask_x(const float* act, int Y, int X, int j, int i) { return acc_at(act, Y, X, j, i - 1) * acc_at(act, Y, X, j, i); }
 
 struct LBArgs {
     int B, Y, X;
@@ -44,25 +32,11 @@ struct LBArgs {
     const float *goy, *gox;             // gradient w.r.t. the step's output velocity
     float *gay, *gax;                   // g_a
     long long *gcy, *gcx;               // g_c: int64 fixed-point accumulators [B][faces] (cleared by k_lb_rhs)
-    unsigned* gmax;                     // [B][LB_SLOTS] bits of max|g_a| per simulation (cleared by k_lb_rhs, published by k_lb_ga)
+    unsigned* gmax;                     // [B][FX_SLOTS] bits of max|g_a| per simulation (cleared by k_lb_rhs, published by k_lb_ga)
     float *giy, *gix;                   // result: gradient w.r.t. the step's input velocity
     float* rhs;
     const float* gdiv;
 };
-
-// power-of-two fixed-point scale of simulation b's scatter and its inverse, from the published max|g_a| (wave-uniform result)
-__device__ __forceinline__ void lb_scale(const unsigned* gmax_b, float& qs, float& qi) {
-    const unsigned m = amax_wave_max(gmax_b[threadIdx.x & (LB_SLOTS - 1)]);
-    if (m >= 0x7f800000u) {                   // k_lb_ga met an inf / nan gradient in this simulation: nothing is scattered (qs = 0) and the
-        qs = 0.f;                             // conversion back (value * qi) makes EVERY input gradient of the simulation NaN
-        qi = __uint_as_float(0x7fc00000u);
-        return;
-    }
-    int e = (int)(m >> 23) - 127;
-    e = m == 0u ? 0 : min(max(e, -80), 120);
-    qs = __uint_as_float((unsigned)(LB_FIXBITS - e + 127) << 23);
-    qi = __uint_as_float((unsigned)(e - LB_FIXBITS + 127) << 23);
-}
 
 __global__ void __launch_bounds__(256) k_lb_rhs(LBArgs a) {
     const int Y = a.Y, X = a.X, XP = X + 1, N = Y * X, nVy = (Y + 1) * X, nVx = Y * XP;
@@ -80,7 +54,7 @@ __global__ void __launch_bounds__(256) k_lb_rhs(LBArgs a) {
     const size_t faces = (size_t)nVy + nVx;
     long long* zc = a.gcy + (size_t)b * faces;
     for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < faces; e += (size_t)gridDim.x * blockDim.x) zc[e] = 0ll;
-    if (blockIdx.x == 0 && threadIdx.x < LB_SLOTS) a.gmax[b * LB_SLOTS + threadIdx.x] = 0u;
+    if (blockIdx.x == 0 && threadIdx.x < FX_SLOTS) a.gmax[b * FX_SLOTS + threadIdx.x] = 0u;
 }
 
 __global__ void __launch_bounds__(256) k_lb_ga(LBArgs a) {
@@ -104,31 +78,17 @@ __global__ void __launch_bounds__(256) k_lb_ga(LBArgs a) {
         vmax = fmaxf(vmax, fabsf(v));
         bad |= !(fabsf(v) <= 3.402823466e38f);      // inf or nan (fmaxf drops a NaN)
     }
-    // max|g_a| of this simulation -> the scale of the fixed-point scatter (at most one atomic per workgroup).  A non-finite g_a publishes
-    // the bits of a NaN -- the largest value the integer maximum can see -- and lb_scale turns that into "scatter nothing, convert back
-    // to NaN".  The maximum is order independent; a workgroup that cannot raise its slot publishes nothing.
-    __shared__ unsigned red[4];
-    const unsigned wmax = amax_wave_max(bad ? 0x7fc00000u : __float_as_uint(vmax));
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = wmax;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const unsigned mb = max(max(red[0], red[1]), max(red[2], red[3]));
-        unsigned* slot = &a.gmax[b * LB_SLOTS + (blockIdx.x & (LB_SLOTS - 1))];
-        if (mb > __atomic_load_n(slot, __ATOMIC_RELAXED)) atomicMax(slot, mb);
-    }
+    fx_publish_max(a.gmax + b * FX_SLOTS, vmax, bad);      // max|g_a| of this simulation -> the scale of the fixed-point scatter
 }
 
-// Where a contribution goes.  GAdd: straight into the int64 accumulators in global memory.  TAdd: into the workgroup's int64 LDS window
-// when the target face lies inside it, else into global memory -- integer adds commute, so both give the same bits.  Each contribution
-// is rounded to the fixed-point grid on its own, then added as an integer.
+// Where a contribution goes (fx_add).  GAdd: straight into the int64 accumulators in global memory.  TAdd: into the workgroup's int64 LDS
+// window when the target face lies inside it, else into global memory.
 struct GAdd {
     long long *gy, *gx;
     float qs;
     int X;
-    __device__ __forceinline__ void operator()(int comp, int jj, int ii, float v) const {
-        long long* p = comp == 0 ? gy + jj * X + ii : gx + jj * (X + 1) + ii;
-        ::atomicAdd(reinterpret_cast<unsigned long long*>(p), (unsigned long long)__float2ll_rn(v * qs));
-    }
+    __device__ __forceinline__ long long* at(int comp, int jj, int ii) const { return comp == 0 ? gy + jj * X + ii : gx + jj * (X + 1) + ii; }
+    __device__ __forceinline__ void operator()(int comp, int jj, int ii, float v) const { fx_add(at(comp, jj, ii), v, qs); }
 };
 struct TAdd {
     GAdd g;
@@ -136,8 +96,7 @@ struct TAdd {
     int jw0, iw0;
     __device__ __forceinline__ void operator()(int comp, int jj, int ii, float v) const {
         const int lj = jj - jw0, li = ii - iw0;
-        if ((unsigned)lj < (unsigned)LB_W && (unsigned)li < (unsigned)LB_W)
-            ::atomicAdd(&L[(comp * LB_W + lj) * LB_W + li], (unsigned long long)__float2ll_rn(v * g.qs));
+        if ((unsigned)lj < (unsigned)LB_W && (unsigned)li < (unsigned)LB_W) fx_add(&L[(comp * LB_W + lj) * LB_W + li], v, g.qs);
         else g(comp, jj, ii, v);
     }
 };
@@ -200,7 +159,7 @@ __global__ void __launch_bounds__(256) k_lb_advect_adj(LBArgs a) {
     const float* sy = a.svy + (size_t)b * nVy;
     const float* sx = a.svx + (size_t)b * nVx;
     float qs, qi;
-    lb_scale(a.gmax + b * LB_SLOTS, qs, qi);
+    fx_scale(a.gmax + b * FX_SLOTS, qs, qi);
     const GAdd add{a.gcy + (size_t)b * nVy, a.gcx + (size_t)b * nVx, qs, X};
     for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < nVy + nVx; k += gridDim.x * blockDim.x) {
         if (k < nVy) {
@@ -226,10 +185,10 @@ __global__ void __launch_bounds__(256) k_lb_advect_adj_tile(LBArgs a, int nti) {
     const float* sy = a.svy + (size_t)b * nVy;
     const float* sx = a.svx + (size_t)b * nVx;
     float qs, qi;
-    lb_scale(a.gmax + b * LB_SLOTS, qs, qi);
+    fx_scale(a.gmax + b * FX_SLOTS, qs, qi);
     const GAdd gadd{a.gcy + (size_t)b * nVy, a.gcx + (size_t)b * nVx, qs, X};
     const TAdd add{gadd, win, j0 - LB_H, i0 - LB_H};
-    for (int e = threadIdx.x; e < 2 * LB_W * LB_W; e += 256) win[e] = 0ull;
+    fx_window_clear(win, 2 * LB_W * LB_W, 256);
     __syncthreads();
     const int j1 = min(j0 + LB_T, Y), i1 = min(i0 + LB_T, X);
     const int j1y = j0 + LB_T >= Y ? Y + 1 : j1, i1x = i0 + LB_T >= X ? X + 1 : i1;
@@ -246,28 +205,10 @@ __global__ void __launch_bounds__(256) k_lb_advect_adj_tile(LBArgs a, int nti) {
         }
     }
     __syncthreads();
-    for (int e = threadIdx.x; e < 2 * LB_W * LB_W; e += 256) {
-        const unsigned long long v = win[e];
-        if (v == 0ull) continue;                                   // (window cells outside the arrays never receive a contribution)
+    fx_window_flush(win, 2 * LB_W * LB_W, 256, [&](int e) {
         const int li = e % LB_W, lj = (e / LB_W) % LB_W, comp = e / (LB_W * LB_W);
-        const int jj = j0 - LB_H + lj, ii = i0 - LB_H + li;
-        long long* p = comp == 0 ? gadd.gy + jj * X + ii : gadd.gx + jj * XP + ii;
-        ::atomicAdd(reinterpret_cast<unsigned long long*>(p), v);
-    }
-}
-
-// alpha (L^T g) at (j, i) of a component array [n0][n1]: the transposed replicate-padded 5-point Laplacian in gather form -- a neighbour
-// q - delta inside the array contributes g there, a direction that leaves the array contributes g[q] itself
-__device__ __forceinline__ float lapT5(const long long* g, float qi, float sc_here, const float* scm, int n0, int n1, int j, int i) {
-    const int c = j * n1 + i;
-    auto at = [&](int q) { const float v = __ll2float_rn(g[q]) * qi; return scm ? v * (1.f - scm[q]) : v; };
-    const float v = __ll2float_rn(g[c]) * qi * sc_here;
-    float acc = -4.f * v;
-    acc += j + 1 < n0 ? at(c + n1) : v;
-    acc += j > 0 ? at(c - n1) : v;
-    acc += i + 1 < n1 ? at(c + 1) : v;
-    acc += i > 0 ? at(c - 1) : v;
-    return acc;
+        return gadd.at(comp, j0 - LB_H + lj, i0 - LB_H + li);
+    });
 }
 
 __global__ void __launch_bounds__(256) k_lb_diffuse_adj(LBArgs a) {
@@ -275,18 +216,20 @@ __global__ void __launch_bounds__(256) k_lb_diffuse_adj(LBArgs a) {
     const int b = blockIdx.y;
     const float alpha = a.adt / a.re[b];
     float qs, qi;
-    lb_scale(a.gmax + b * LB_SLOTS, qs, qi);
+    fx_scale(a.gmax + b * FX_SLOTS, qs, qi);
+    // g' + alpha L^T g' with the rounded g' as the addend of ONE fused multiply-add, spelled out: left to the compiler, which product is
+    // fused depends on the surrounding code, and the bits move with it
     for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < nVy + nVx; e += gridDim.x * blockDim.x) {
         if (e < nVy) {
             const int j = e / X, i = e - j * X;
             const long long* g = a.gcy + (size_t)b * nVy;
             const float* m = a.bcm + (size_t)b * a.bc_stride;          // g' = g . (1 - bcm): the BC blend's adjoint
             const float sc = 1.f - m[e];
-            a.giy[(size_t)b * nVy + e] = __ll2float_rn(g[e]) * qi * sc + alpha * lapT5(g, qi, sc, m, Y + 1, X, j, i);
+            a.giy[(size_t)b * nVy + e] = __fmaf_rn(alpha, lapT<2>(g, qi, sc, m, e, {j, i}, {Y + 1, X}), fx_get(g, e, qi) * sc);
         } else {
             const int q = e - nVy, j = q / XP, i = q - j * XP;
             const long long* g = a.gcx + (size_t)b * nVx;
-            a.gix[(size_t)b * nVx + q] = __ll2float_rn(g[q]) * qi + alpha * lapT5(g, qi, 1.f, nullptr, Y, XP, j, i);
+            a.gix[(size_t)b * nVx + q] = __fmaf_rn(alpha, lapT<2>(g, qi, 1.f, nullptr, q, {j, i}, {Y, XP}), fx_get(g, q, qi));
         }
     }
 }
@@ -307,7 +250,7 @@ BwdLayout bwd_layout(const sol_karman_cfg* c, bool direct, void* ws) {
     BwdLayout l{};
     l.gc = reinterpret_cast<long long*>(take(B * faces * sizeof(long long)));
     l.ga = reinterpret_cast<float*>(take(B * faces * sizeof(float)));
-    l.gmax = reinterpret_cast<unsigned*>(take(B * LB_SLOTS * sizeof(unsigned)));
+    l.gmax = reinterpret_cast<unsigned*>(take(B * FX_SLOTS * sizeof(unsigned)));
     l.solver = take(sol_large_solver_bytes(c, direct));
     l.bytes = off + 256;                       // + the alignment of the caller's pointer
     return l;

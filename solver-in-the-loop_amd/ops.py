@@ -93,6 +93,31 @@ def _hdr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def _workspace(nbytes, workspace, device):
+    """`workspace` when it holds nbytes, else a fresh buffer that does"""
+    if workspace is None or workspace.numel() * 4 < nbytes:
+        workspace = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=device)
+    return workspace
+
+
+def _cg_info(masks, B, device):
+    """[2][B] int32 that the large-grid CG solve reports to; None for a scene with the direct solver"""
+    return torch.empty(2, B, dtype=torch.int32, device=device) if masks.direct is None else None
+
+
+def _publish_cg(info, cg_info, suffix=""):
+    if info is not None and cg_info is not None:
+        info["iterations" + suffix], info["converged" + suffix] = cg_info[0], cg_info[1]
+
+
+def _large_fwd(d, vy, vx, re, cfg, masks):
+    """Outputs of the large-grid forward step and the fourteen arguments its three entry points begin with"""
+    outs = torch.empty_like(d), torch.empty_like(vy), torch.empty_like(vx)
+    head = (C.byref(cfg), stream(), ptr(d), ptr(vy), ptr(vx), ptr(re), ptr(masks.active), ptr(masks.inflow), ptr(masks.velBCy),
+            ptr(masks.velBCyMask), masks.bc_stride, *(ptr(t) for t in outs))
+    return outs, head
+
+
 class KarmanStepLargeFn(torch.autograd.Function):
     """The large-grid step with its hand-written adjoint (sol_karman_step_fwd_large_saved / sol_karman_step_bwd_large), for the scene's
     solver (direct or CG).  Differentiable with respect to the velocity; the density is a passive tracer."""
@@ -100,25 +125,18 @@ class KarmanStepLargeFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, d, vy, vx, re, cfg, masks, workspace, info):
         lib = _lib.load()
-        B = cfg.B
         d, vy, vx = d.contiguous(), vy.contiguous(), vx.contiguous()
-        nbytes = large_workspace_bytes(cfg, masks)
-        if workspace is None or workspace.numel() * 4 < nbytes:
-            workspace = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=vy.device)
-        d_out, vy_out, vx_out = torch.empty_like(d), torch.empty_like(vy), torch.empty_like(vx)
+        workspace = _workspace(large_workspace_bytes(cfg, masks), workspace, vy.device)
+        outs, head = _large_fwd(d, vy, vx, re, cfg, masks)
         svy, svx = torch.empty_like(vy), torch.empty_like(vx)
-        cg = masks.direct is None
-        cg_info = torch.empty(2, B, dtype=torch.int32, device=vy.device) if cg else None
-        check(lib.sol_karman_step_fwd_large_saved(
-            C.byref(cfg), stream(), ptr(d), ptr(vy), ptr(vx), ptr(re), ptr(masks.active), ptr(masks.inflow), ptr(masks.velBCy),
-            ptr(masks.velBCyMask), masks.bc_stride, ptr(d_out), ptr(vy_out), ptr(vx_out), ptr(svy), ptr(svx),
-            _hdr(masks.direct_header), ptr(masks.box), _hdr(masks.box_header), ptr(cg_info), ptr(workspace), workspace.numel() * 4))
-        if cg and info is not None:
-            info["iterations"], info["converged"] = cg_info[0], cg_info[1]
+        cg_info = _cg_info(masks, cfg.B, vy.device)
+        check(lib.sol_karman_step_fwd_large_saved(*head, ptr(svy), ptr(svx), _hdr(masks.direct_header), ptr(masks.box),
+                                                  _hdr(masks.box_header), ptr(cg_info), ptr(workspace), workspace.numel() * 4))
+        _publish_cg(info, cg_info)
         ctx.save_for_backward(svy, svx, re)
         ctx.cfg, ctx.masks, ctx.info = cfg, masks, info
-        ctx.mark_non_differentiable(d_out)
-        return d_out, vy_out, vx_out
+        ctx.mark_non_differentiable(outs[0])
+        return outs
 
     @staticmethod
     def backward(ctx, _gd, gvy, gvx):
@@ -133,18 +151,14 @@ def karman_step_large_bwd(svy, svx, re, gvy, gvx, cfg, masks, workspace=None, in
     """Adjoint of the large-grid step (sol_karman_step_bwd_large): (g_vy_in, g_vx_in) from the saved post-diffusion velocity and the
     gradient with respect to the step's output velocity.  With the CG solve, `info` receives "iterations_bwd" / "converged_bwd"."""
     lib = _lib.load()
-    nbytes = lib.sol_karman_step_bwd_large_workspace_bytes(C.byref(cfg))
-    if workspace is None or workspace.numel() * 4 < nbytes:
-        workspace = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=svy.device)
+    workspace = _workspace(lib.sol_karman_step_bwd_large_workspace_bytes(C.byref(cfg)), workspace, svy.device)
     oy, ox = torch.empty_like(svy), torch.empty_like(svx)
-    cg = masks.direct is None
-    cg_info = torch.empty(2, cfg.B, dtype=torch.int32, device=svy.device) if cg else None
+    cg_info = _cg_info(masks, cfg.B, svy.device)
     check(lib.sol_karman_step_bwd_large(
         C.byref(cfg), stream(), ptr(svy), ptr(svx), ptr(re), ptr(masks.active), ptr(masks.velBCyMask), masks.bc_stride,
         ptr(gvy), ptr(gvx), ptr(oy), ptr(ox), _hdr(masks.direct_header), ptr(masks.box), _hdr(masks.box_header), ptr(cg_info),
         ptr(workspace), workspace.numel() * 4))
-    if cg and info is not None:
-        info["iterations_bwd"], info["converged_bwd"] = cg_info[0], cg_info[1]
+    _publish_cg(info, cg_info, "_bwd")
     return oy, ox
 
 
@@ -162,21 +176,16 @@ def karman_step_large(d, vy, vx, re, cfg, masks, workspace=None, info=None):
     assert vy.shape == (B, Y + 1, X) and vx.shape == (B, Y, X + 1) and d.shape == (B, Y, X) and re.shape == (B,)
     if torch.is_grad_enabled() and (vy.requires_grad or vx.requires_grad):
         return KarmanStepLargeFn.apply(d, vy, vx, re, cfg, masks, workspace, info)
-    nbytes = large_workspace_bytes(cfg, masks)
-    if workspace is None or workspace.numel() * 4 < nbytes:
-        workspace = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=vy.device)
-    d_out, vy_out, vx_out = torch.empty_like(d), torch.empty_like(vy), torch.empty_like(vx)
-    head = (C.byref(cfg), stream(), ptr(d), ptr(vy), ptr(vx), ptr(re), ptr(masks.active), ptr(masks.inflow), ptr(masks.velBCy),
-            ptr(masks.velBCyMask), masks.bc_stride, ptr(d_out), ptr(vy_out), ptr(vx_out), None, None)
-    if masks.direct is not None:
-        check(lib.sol_karman_step_fwd_large(*head, masks.direct_header.ctypes.data_as(C.c_void_p), ptr(workspace), workspace.numel() * 4))
+    workspace = _workspace(large_workspace_bytes(cfg, masks), workspace, vy.device)
+    outs, head = _large_fwd(d, vy, vx, re, cfg, masks)
+    cg_info = _cg_info(masks, B, vy.device)
+    if cg_info is None:
+        check(lib.sol_karman_step_fwd_large(*head, None, None, _hdr(masks.direct_header), ptr(workspace), workspace.numel() * 4))
     else:
-        cg_info = torch.empty(2, B, dtype=torch.int32, device=vy.device)
-        check(lib.sol_karman_step_fwd_large_cg(*head, ptr(masks.box), masks.box_header.ctypes.data_as(C.c_void_p), ptr(cg_info),
+        check(lib.sol_karman_step_fwd_large_cg(*head, None, None, ptr(masks.box), _hdr(masks.box_header), ptr(cg_info),
                                                ptr(workspace), workspace.numel() * 4))
-        if info is not None:
-            info["iterations"], info["converged"] = cg_info[0], cg_info[1]
-    return d_out, vy_out, vx_out
+    _publish_cg(info, cg_info)
+    return outs
 
 
 def pressure_solve_large(rhs, cfg, masks, workspace=None, info=None):
@@ -189,16 +198,13 @@ def pressure_solve_large(rhs, cfg, masks, workspace=None, info=None):
     rhs = _lib.f32(rhs)
     B, Y, X = cfg.B, cfg.Y, cfg.X
     assert rhs.shape == (B, Y, X)
-    nbytes = lib.sol_karman_step_large_cg_workspace_bytes(C.byref(cfg))
-    if workspace is None or workspace.numel() * 4 < nbytes:
-        workspace = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=rhs.device)
+    workspace = _workspace(lib.sol_karman_step_large_cg_workspace_bytes(C.byref(cfg)), workspace, rhs.device)
     p = torch.empty_like(rhs)
-    cg_info = torch.empty(2, B, dtype=torch.int32, device=rhs.device)
+    cg_info = _cg_info(masks, B, rhs.device)
     check(lib.sol_karman_pressure_solve_large(C.byref(cfg), stream(), ptr(masks.active), ptr(rhs), ptr(p), ptr(masks.box),
                                               masks.box_header.ctypes.data_as(C.c_void_p), ptr(cg_info), ptr(workspace),
                                               workspace.numel() * 4))
-    if info is not None:
-        info["iterations"], info["converged"] = cg_info[0], cg_info[1]
+    _publish_cg(info, cg_info)
     return p
 
 
@@ -414,9 +420,7 @@ def burgers_step_large(vy, vx, fy, fx, cfg, circ, workspace=None):
     vy, vx = _lib.f32(vy), _lib.f32(vx)
     fy = None if fy is None else _lib.f32(fy)
     fx = None if fx is None else _lib.f32(fx)
-    nbytes = lib.sol_burgers_step_large_workspace_bytes(C.byref(cfg))
-    if workspace is None or workspace.numel() * 4 < nbytes:
-        workspace = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=vy.device)
+    workspace = _workspace(lib.sol_burgers_step_large_workspace_bytes(C.byref(cfg)), workspace, vy.device)
     oy, ox = torch.empty_like(vy), torch.empty_like(vx)
     check(lib.sol_burgers_step_fwd_large(C.byref(cfg), stream(), ptr(vy), ptr(vx), ptr(fy), ptr(fx),
                                          ptr(circ[0]), ptr(circ[1]), ptr(circ[2]), ptr(circ[3]), ptr(oy), ptr(ox),

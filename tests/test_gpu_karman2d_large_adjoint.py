@@ -10,64 +10,25 @@ untrimmed metric keeps a 5x margin on the default sphere and the plate (state se
 of the squared error sits in 20 entries.  There the TRIMMED metric is asserted: each gradient component may leave out at most 0.1 %
 of its entries (those with the largest absolute deviation); one boundary row (128 faces per simulation) or column (256) is already
 more than that hides."""
+import os
+import sys
+
 import numpy as np
 import pytest
 import torch
 
 import sol_amd
 import sol_oracle as o
-from sol_amd import _lib, fluid, karman, ops, precond
+from sol_amd import _lib, fluid, karman, ops
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from large2d_scenes import CG_RTOL, DEV, PLATE, TOL_FIELD, TOL_GRAD, TWO, active_of, f32, geometry, masks, rel, state
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-TOL_FIELD = 1e-5
-TOL_GRAD = 1e-4
-CG_RTOL = 1e-7
 TRIM = 1e-3                                          # a cap, not a tuning knob (module docstring)
-TWO = ["sphere:50,50,10", "sphere:120,50,10"]       # two cylinders in tandem
-PLATE = ["box:70:73,20:80"]                          # a plate across the channel
 Y, X = 256, 128
 
 
-# ---- helpers copied from tests/test_gpu_karman2d_obstacles.py ------------------------------------------------------------------
-def rel(a, b):
-    a = torch.as_tensor(np.asarray(a.detach().cpu() if isinstance(a, torch.Tensor) else a), dtype=torch.float64)
-    b = torch.as_tensor(np.asarray(b.detach().cpu() if isinstance(b, torch.Tensor) else b), dtype=torch.float64)
-    return float((a - b).norm() / (b.norm() + 1e-300))
-
-
-def f32(t):
-    return torch.as_tensor(np.asarray(t), dtype=torch.float32).to(DEV).contiguous()
-
-
-def active_of(specs, Y, X):
-    dom = fluid.Domain([Y, X], box=fluid.box[0:200, 0:100])
-    return karman.KarmanFlow(obstacles=karman.parse_obstacles(specs)).scene_arrays(dom)[0]
-
-
-def geometry(Y, X, active):
-    """The oracle's KarmanGeometry (a fresh instance, never the cached one) with the masks of a custom obstacle."""
-    g = o.KarmanGeometry(Y, X)
-    g.active = np.asarray(active, dtype=np.float64)
-    g.obstacle = 1.0 - g.active
-    acc = np.pad(g.active, 1, mode="edge")
-    g.my = np.minimum(acc[0:Y + 1, 1:X + 1], acc[1:Y + 2, 1:X + 1])
-    g.mx = np.minimum(acc[1:Y + 1, 0:X + 1], acc[1:Y + 1, 1:X + 2])
-    g.diag = np.minimum(-(acc[0:Y, 1:X + 1] + acc[2:Y + 2, 1:X + 1] + acc[1:Y + 1, 0:X] + acc[1:Y + 1, 2:X + 2]), -1.0)
-    return g
-
-
-def state(B, Y, X, seed, g=None):
-    """seeded smooth noise; with a geometry: spun up by one float64 oracle step in that scene, rounded to fp32 values"""
-    d, vy, vx = o.synthetic_state(B, Y, X, seed, project_it=False)
-    re = torch.tensor([o.RE_TRAIN[i % 6] for i in range(B)], dtype=torch.float64)
-    if g is not None:
-        with torch.no_grad():
-            d, vy, vx = (t.float().double() for t in o.karman_step(d, vy, vx, re, g))
-    return d, vy, vx, re
-
-
-# ---- this file's own helpers --------------------------------------------------------------------------------------------------------
 def trimmed_rel(a, b, frac=TRIM):
     """relative L2 of a against b after leaving out the floor(frac * n) entries with the largest |a - b| (the norm of b is taken over
     the entries kept) -> (value, entries left out, largest deviation left out)"""
@@ -85,10 +46,6 @@ def trimmed_rel(a, b, frac=TRIM):
 def scene_of(specs):
     """(oracle geometry, specs) of the default sphere (None) or a list of obstacle specs"""
     return o.KarmanGeometry(Y, X) if specs is None else geometry(Y, X, active_of(specs, Y, X))
-
-
-def masks(g, solver="auto"):
-    return ops.SceneMasks(g.active, g.inflow, g.bc_mask, g.bc_mask, DEV, pressure_solver=solver)
 
 
 def cotangent(B):

@@ -1,7 +1,9 @@
 #!/usr/bin/env python
 """Does a library variant (tools/ab_lib.py --build NAME ...) compute the SAME BITS as the product library?  Two karman-2d training steps
-(loss, gradient, final state) and the CG pressure solves (the 2-D large step eager and replayed, its solve alone, the 3-D step and its
-adjoint: fields and cg_info) per library in fresh processes (SOL_HIP_LIB), SHA-1 of every result, one verdict per leg.
+(loss, gradient, final state), the CG pressure solves (the 2-D large step eager and replayed, its solve alone, the 3-D step and its
+adjoint: fields and cg_info) and the adjoints' fixed-point scatter with the LDS window and with global atomics only (the 2-D large-grid
+adjoint, direct on the default sphere and CG on two cylinders, B = 2; the 3-D direct-solve adjoint at 128 x 64 x 64, B = 1) per library
+in fresh processes (SOL_HIP_LIB), SHA-1 of every result, one verdict per leg.
     python tools/lib_bitcompare.py NAME [NAME2 ...]        (on the GPU box)"""
 import hashlib
 import json
@@ -67,6 +69,54 @@ if "--child" in sys.argv:
     sum((t * (k + 1.0)).sum() for k, t in enumerate(outs[1:])).backward()
     out["cg3d_fwd_adjoint"] = [sha(t) for t in list(outs) + [t.grad for t in v]] + \
         [sim.solve_info[k].tolist() for k in ("iterations", "converged", "iterations_bwd", "converged_bwd")]
+    # the fixed-point scatter of the adjoints (csrc/fixed_scatter.hpp), both forms of each: input gradients (and iterations_bwd with CG)
+    from sol_amd import _lib
+
+    def tiled(option, fn):
+        res = []
+        for tile in (1, 0):
+            _lib.set_option(option, tile)
+            try:
+                res.append(fn())
+            finally:
+                _lib.set_option(option, 1)
+        return res
+
+    def adjoint2d(specs):
+        B, Y, X = 2, 256, 128
+        dom = fluid.Domain([Y, X], box=fluid.box[0:200, 0:100])
+        active, inflow = karman.KarmanFlow(obstacles=None if specs is None else karman.parse_obstacles(specs)).scene_arrays(dom)
+        bc = karman.velocity_bc_masks(Y, X)[0].reshape(Y + 1, X)
+        mk = ops.SceneMasks(active, inflow, bc, bc, dev)
+        cfg = ops.karman_cfg(B, Y, X, dom.dx[1], masks=mk, cg_max_iter=600)
+        with torch.no_grad():
+            st = ops.karman_step_large(d0, vy0, vx0, re, cfg, mk)               # spun up in this scene
+        gen = torch.Generator().manual_seed(3)
+        w = [torch.randn(t.shape, generator=gen).to(dev) for t in st[1:]]
+
+        def run():
+            v, info = [t.clone().requires_grad_(True) for t in st[1:]], {}
+            outs = ops.karman_step_large(st[0], v[0], v[1], re, cfg, mk, info=info)
+            g = torch.autograd.grad(outs[1:], v, w)
+            return [mk.pressure_solver] + [sha(t) for t in g] + ([info["iterations_bwd"].tolist()] if "iterations_bwd" in info else [])
+        return tiled("k2d_adj_tile", run)
+    out["adj2d_sphere_direct"] = adjoint2d(None)
+    out["adj2d_two_cylinders_cg"] = adjoint2d(["sphere:50,50,10", "sphere:120,50,10"])
+
+    B, Y, X, Z = 1, 128, 64, 64
+    sim = karman3d.Karman3DFlow(karman3d.Scene3D(Y, X, Z, device=dev, pressure_solver="direct"), B)
+    d, v3 = o3.synthetic_state(B, Y, X, Z, 41)
+    re3 = torch.tensor(o3.RE_TRAIN[:B], dtype=torch.float32, device=dev)
+    with torch.no_grad():
+        st3 = sim.step(d.float().to(dev), *(t.float().to(dev) for t in v3), re3)
+    gen = torch.Generator().manual_seed(3)
+    w3 = [torch.randn(t.shape, generator=gen).to(dev) for t in st3[1:]]
+
+    def run3d():
+        v = [t.clone().requires_grad_(True) for t in st3[1:]]
+        outs = sim.step(st3[0], *v, re3)
+        return [sha(t) for t in torch.autograd.grad(outs[1:], v, w3)]
+    out["adj3d_direct_128x64x64"] = tiled("k3d_adj_tile", run3d)
     print(json.dumps(out))
     sys.exit(0)
 names = ["product"] + [a for a in sys.argv[1:] if not a.startswith("--")]
