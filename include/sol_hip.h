@@ -326,7 +326,9 @@ int sol_conv5x5_scaled(void* stream, const float* x, const float* packed, const 
 /* dW[5,5,cin,cout] += sum_px x[px+tap] * dz[px];  db[cout] += sum_px dz[px].
  * `partial` is a caller workspace of sol_conv5x5_bwd_weight_ws_floats() floats that the
  * caller zeroes once and may reuse to ACCUMULATE over many calls (the unrolled steps share
- * the weights); sol_conv5x5_bwd_weight_reduce() folds it into dw/db.                     */
+ * the weights); sol_conv5x5_bwd_weight_reduce() folds it into dw/db.
+ * W: 4 <= W <= 64 with W % 4 == 0, or a multiple of 64 (W / 64 column tiles per row block, each
+ * with its own slice of `partial`: the workspace grows by that factor).                    */
 size_t sol_conv5x5_bwd_weight_ws_floats(int32_t B, int32_t H, int32_t W, int32_t cin, int32_t cout);
 int sol_conv5x5_bwd_weight(void* stream, const float* x, const float* dz, float* partial,
                            int32_t B, int32_t H, int32_t W, int32_t cin, int32_t cout);

@@ -737,8 +737,12 @@ __global__ void __launch_bounds__(256) k_conv5x5_bww(BwArgs a) {
     extern __shared__ __align__(16) float smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int g = lane >> 4, li = lane & 15;
-    const int H = a.H, W = a.W;
+    // image rows wider than 64 pixels (a.W % 64 == 0): W is the 64-pixel column tile of this workgroup, blk = (row block, tile); the
+    // halo pixels of the staged x row come from the neighbouring tiles.  a.W <= 64: one tile, the whole row.
+    const int H = a.H, WI = a.W, W = WI > 64 ? 64 : WI;
+    const int tiles = WI / W;
     const int dy = blockIdx.x % 5, blk = blockIdx.x / 5;
+    const int rblk = blk / tiles, x0 = (blk - rblk * tiles) * W;
     const int bufsz = (W + 4) * CPX + W * CPZ;    // floats per stage: x row then dz row
     const int ta = wave / NTC, tc = wave % NTC;
     const bool active_wave = wave < NTA * NTC;
@@ -749,7 +753,7 @@ __global__ void __launch_bounds__(256) k_conv5x5_bww(BwArgs a) {
     float bsum = 0.f;
 
     const int R = a.nseg * a.B * H, RPS = a.B * H;
-    const int gr_end = min((blk + 1) * a.rb, R);
+    const int gr_end = min((rblk + 1) * a.rb, R);
     // rows this workgroup visits: dy == 2 always (bias needs every dz row), else only valid taps
     auto row_valid = [&](int gr) { const int y = gr % H, yy = y + dy - 2; return yy >= 0 && yy < H; };
     auto next_row = [&](int gr) { while (gr < gr_end && !(dy == 2 || row_valid(gr))) ++gr; return gr; };
@@ -760,23 +764,23 @@ __global__ void __launch_bounds__(256) k_conv5x5_bww(BwArgs a) {
         const int seg = gr / RPS, grs = gr - seg * RPS;
         const int b = grs / H, y = grs - b * H, yy = y + dy - 2;
         const bool valid = yy >= 0 && yy < H;
-        const float4* gx = reinterpret_cast<const float4*>(a.x + (size_t)seg * a.x_seg) + (size_t)(b * H + (valid ? yy : 0)) * W * XF4;
+        const float4* gx = reinterpret_cast<const float4*>(a.x + (size_t)seg * a.x_seg) + (size_t)(b * H + (valid ? yy : 0)) * WI * XF4;
 #pragma unroll
         for (int n = 0; n < NXR; ++n) {
             const int e = tid + n * 256;
-            const int px = e / XF4, c4 = e - px * XF4, xx = px - 2;
+            const int px = e / XF4, c4 = e - px * XF4, xx = x0 + px - 2;
             xr[n] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (valid && px < W + 4 && xx >= 0 && xx < W) xr[n] = gx[xx * XF4 + c4];
+            if (valid && px < W + 4 && xx >= 0 && xx < WI) xr[n] = gx[xx * XF4 + c4];
         }
         if constexpr (COUT > 4) {
-            const float4* gz = reinterpret_cast<const float4*>(a.dz + (size_t)seg * a.dz_seg) + (size_t)(b * H + y) * W * (COUT / 4);
+            const float4* gz = reinterpret_cast<const float4*>(a.dz + (size_t)seg * a.dz_seg) + ((size_t)(b * H + y) * WI + x0) * (COUT / 4);
 #pragma unroll
             for (int n = 0; n < NZR; ++n) {
                 const int e = tid + n * 256;
                 zr[n] = e < W * (COUT / 4) ? gz[e] : make_float4(0.f, 0.f, 0.f, 0.f);
             }
         } else {
-            const float2* gz = reinterpret_cast<const float2*>(a.dz + (size_t)seg * a.dz_seg) + (size_t)(b * H + y) * W;
+            const float2* gz = reinterpret_cast<const float2*>(a.dz + (size_t)seg * a.dz_seg) + (size_t)(b * H + y) * WI + x0;
             const float2 v = tid < W ? gz[tid] : make_float2(0.f, 0.f);
             zr[0] = make_float4(v.x, v.y, 0.f, 0.f);
         }
@@ -802,7 +806,7 @@ __global__ void __launch_bounds__(256) k_conv5x5_bww(BwArgs a) {
         }
     };
 
-    int gr = next_row(blk * a.rb);
+    int gr = next_row(rblk * a.rb);
     int cur = 0;
     if (gr < gr_end) {
         load_row(gr);
@@ -979,7 +983,9 @@ __global__ void __launch_bounds__(256) k_conv5x5_bww32(BwArgs a) {
 // MODE 1 (ONE 16-column tile, 10 / 16 used instead of 10 / 32): half the matrix-pipe cycles per pixel for the same products
 // (the kernels are bound by the fp32 matrix pipe: 40 x 64 clocks per row and wave before, 40 x 32 / 50 x 32 now).  MT = 2 (four
 // real input channels: 20 folded entries, two 16-row tiles) costs what the 32 x 32 form did.
-template <int MODE, int MT>
+// WIDE (a.W = 64 * tiles): blk = (row block, column tile); the tile's dz pixels are its own 64, the halo pixels of its x rows come
+// from the neighbouring tiles (zero at the image border).
+template <int MODE, int MT, bool WIDE = false>
 __global__ void __launch_bounds__(256) k_conv5x5_bww_thin(BwArgs a) {
     constexpr int W = 64;
     constexpr int XC = MODE == 0 ? 4 : 32, ZC = MODE == 0 ? 32 : 2;            // channels per pixel of x / dz
@@ -997,6 +1003,8 @@ __global__ void __launch_bounds__(256) k_conv5x5_bww_thin(BwArgs a) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int n16 = lane & 15, kq = lane >> 4;
     const int H = a.H, blk = blockIdx.x;
+    const int WI = WIDE ? a.W : W, tiles = WIDE ? a.W / W : 1;
+    const int rblk = WIDE ? blk / tiles : blk, x0 = WIDE ? (blk - rblk * tiles) * W : 0;
     bt_f4 acc[5][NTM][NTN];
 #pragma unroll
     for (int d = 0; d < 5; ++d)
@@ -1006,23 +1014,23 @@ __global__ void __launch_bounds__(256) k_conv5x5_bww_thin(BwArgs a) {
             for (int tn = 0; tn < NTN; ++tn) acc[d][tm][tn] = (bt_f4){0.f, 0.f, 0.f, 0.f};
     float bsum[2] = {0.f, 0.f};
     const int R = a.nseg * a.B * H, RPS = a.B * H;
-    const int gr_end = min((blk + 1) * a.rb, R);
+    const int gr_end = min((rblk + 1) * a.rb, R);
     float4 xr[NXR], zr[NZR];
     // iteration row gr: MODE 0 = dz (output) row, needs x rows y+dy-2; MODE 1 = x (input) row, needs dz rows y+2-dy
     auto load_row = [&](int gr) {
         const int seg = gr / RPS, grs = gr - seg * RPS;
         const int b = grs / H, y = grs - b * H;
-        const float* xb = a.x + (size_t)seg * a.x_seg + (size_t)b * H * W * XC;
-        const float* zb = a.dz + (size_t)seg * a.dz_seg + (size_t)b * H * W * ZC;
+        const float* xb = a.x + (size_t)seg * a.x_seg + (size_t)b * H * WI * XC;
+        const float* zb = a.dz + (size_t)seg * a.dz_seg + ((size_t)b * H * WI + x0) * ZC;
 #pragma unroll
         for (int n = 0; n < NXR; ++n) {
             const int e = tid + n * 256;              // float4 index inside the x stage
             xr[n] = make_float4(0.f, 0.f, 0.f, 0.f);
             if (e < XF4) {
                 const int row = e / (XSZ / 4), f = e - row * (XSZ / 4);
-                const int px = f / (XC / 4), c4 = f - px * (XC / 4), xx = px - 2;
+                const int px = f / (XC / 4), c4 = f - px * (XC / 4), xx = x0 + px - 2;
                 const int yy = MODE == 0 ? y + row - 2 : y;
-                if (yy >= 0 && yy < H && xx >= 0 && xx < W) xr[n] = reinterpret_cast<const float4*>(xb + ((size_t)yy * W + xx) * XC)[c4];
+                if (yy >= 0 && yy < H && xx >= 0 && xx < WI) xr[n] = reinterpret_cast<const float4*>(xb + ((size_t)yy * WI + xx) * XC)[c4];
             }
         }
 #pragma unroll
@@ -1031,11 +1039,11 @@ __global__ void __launch_bounds__(256) k_conv5x5_bww_thin(BwArgs a) {
             zr[n] = make_float4(0.f, 0.f, 0.f, 0.f);
             if (e < ZF4) {
                 if (MODE == 0) {                      // one dz row, no halo: pixels 0..63 at stage pixels 0..63
-                    if (e < W * ZC / 4) zr[n] = reinterpret_cast<const float4*>(zb + (size_t)y * W * ZC)[e];
+                    if (e < W * ZC / 4) zr[n] = reinterpret_cast<const float4*>(zb + (size_t)y * WI * ZC)[e];
                 } else {                              // five dz rows y+2-dy, each [72 px][2] with pixel p at stage pixel p+4
                     const int row = e / (ZSZ / 4), f = e - row * (ZSZ / 4);      // f: float4 = 2 pixels
                     const int yy = y + 2 - row, p = 2 * f - 4;
-                    if (yy >= 0 && yy < H && p >= 0 && p < W) zr[n] = reinterpret_cast<const float4*>(zb + ((size_t)yy * W + p) * ZC)[0];
+                    if (yy >= 0 && yy < H && p >= 0 && p < W) zr[n] = reinterpret_cast<const float4*>(zb + ((size_t)yy * WI + p) * ZC)[0];
                 }
             }
         }
@@ -1046,7 +1054,7 @@ __global__ void __launch_bounds__(256) k_conv5x5_bww_thin(BwArgs a) {
 #pragma unroll
         for (int n = 0; n < NZR; ++n) { const int e = tid + n * 256; if (e < ZF4) reinterpret_cast<float4*>(buf + XROWS * XSZ)[e] = zr[n]; }
     };
-    int gr = blk * a.rb, cur = 0;
+    int gr = rblk * a.rb, cur = 0;
     if (gr < gr_end) { load_row(gr); store_row(smem); }
     __syncthreads();
     for (; gr < gr_end; ++gr) {
@@ -1393,8 +1401,12 @@ extern "C" int sol_conv5x5_scaled(void* stream, const float* x, const float* pac
     return conv_impl(stream, x, packed, bias, residual, act_ref, y, B, H, W, cin, cout, epilogue, slope, x_absmax, y_absmax);
 }
 
-static int bww_dims(int rows, int rb, int cin, int cout, int* nblk, int* IP, int* OP) {
-    *nblk = (rows + rb - 1) / rb;
+// column tiles of an image row for the weight gradient: one up to 64 pixels, W / 64 beyond
+static int bww_tiles(int W) { return W > 64 ? W / 64 : 1; }
+
+// nblk: slices of the partial buffer = row blocks x column tiles
+static int bww_dims(int rows, int rb, int cin, int cout, int* nblk, int* IP, int* OP, int tiles = 1) {
+    *nblk = (rows + rb - 1) / rb * tiles;
     *IP = cin <= 4 ? 16 : 32;
     *OP = cout <= 16 ? 16 : 32;
     return 0;
@@ -1408,9 +1420,9 @@ static int pick_rb(int rows, int cin = 32, int cout = 32) {
     return RB;
 }
 
-extern "C" size_t sol_conv5x5_bwd_weight_ws_floats(int32_t B, int32_t H, int32_t /*W*/, int32_t cin, int32_t cout) {
+extern "C" size_t sol_conv5x5_bwd_weight_ws_floats(int32_t B, int32_t H, int32_t W, int32_t cin, int32_t cout) {
     int nblk, IP, OP;
-    bww_dims(B * H, RB, cin, cout, &nblk, &IP, &OP);
+    bww_dims(B * H, RB, cin, cout, &nblk, &IP, &OP, bww_tiles(W));
     return (size_t)nblk * (25 * IP * OP + OP);
 }
 
@@ -1427,7 +1439,10 @@ static int bww_launch(void* stream, const float* x, const float* dz, float* part
                       int rb, int overwrite, int B, int H, int W, int cin, int cout, int nblk_layout = 0,
                       const unsigned* xmax = nullptr, const unsigned* zmax = nullptr, long xmax_seg = 0, long zmax_seg = 0, int cin_real = 0) {
     SOL_REQUIRE(x && dz && partial, "sol_conv5x5_bwd_weight: NULL pointer");
-    SOL_REQUIRE(B >= 1 && H >= 1 && W >= 4 && W % 4 == 0 && W <= 64, "sol_conv5x5_bwd_weight: need 4 <= W <= 64, W %% 4 == 0 (got %d)", W);
+    SOL_REQUIRE(B >= 1 && H >= 1 && W >= 4 && W % 4 == 0, "sol_conv5x5_bwd_weight: need W >= 4, W %% 4 == 0 (got %d)", W);
+    SOL_REQUIRE(W <= 64 || W % 64 == 0, "sol_conv5x5_bwd_weight: rows wider than 64 pixels must be a multiple of 64 pixels wide (got W = %d)", W);
+    SOL_REQUIRE(W <= 64 || (nblk_layout == 0 && nseg == 1), "sol_conv5x5_bwd_weight: the batched forms take W <= 64 (got %d)", W);
+    const int tiles = bww_tiles(W), Wt = W > 64 ? 64 : W;
     SOL_REQUIRE((cin == 4 || cin == 32) && (cout == 2 || cout == 32),
                 "sol_conv5x5_bwd_weight: supported (cin,cout) are {4,32}x{2,32} (got %d,%d)", cin, cout);
     BwArgs a{};
@@ -1435,13 +1450,26 @@ static int bww_launch(void* stream, const float* x, const float* dz, float* part
     a.nseg = nseg; a.rb = rb; a.x_seg = x_seg; a.dz_seg = dz_seg; a.overwrite = overwrite;
     a.xmax = xmax; a.zmax = zmax; a.xmax_seg = xmax_seg; a.zmax_seg = zmax_seg; a.cin_real = cin_real;
     int IP, OP;
-    bww_dims(nseg * B * H, rb, cin, cout, &a.nblk, &IP, &OP);
+    bww_dims(nseg * B * H, rb, cin, cout, &a.nblk, &IP, &OP, tiles);
     const int nblk_run = a.nblk;                    // workgroups needed for this launch's rows
     if (nblk_layout > 0) a.nblk = nblk_layout;      // partial buffer laid out for a (larger) reference launch
     const int CPX = cin == 4 ? 4 : 48, CPZ = cout <= 4 ? 4 : 48;
-    const size_t lds = 2 * ((size_t)(W + 4) * CPX + (size_t)W * CPZ) * sizeof(float);   // double buffered rows
+    const size_t lds = 2 * ((size_t)(Wt + 4) * CPX + (size_t)Wt * CPZ) * sizeof(float);   // double buffered rows (of one column tile)
     const int grid = nblk_run * 5;
     hipStream_t s = (hipStream_t)stream;
+    if (W > 64 && ((cin == 4 && cout == 32) || (cin == 32 && cout == 2)) && sol_opt().conv_thin) {
+        // the same kernels per 64-pixel column tile (grid = row blocks x tiles)
+        if (cin == 4) {
+            const size_t l0 = 2 * (size_t)(5 * 68 * 4 + 68 * 32) * sizeof(float);
+            if (a.cin_real >= 1 && a.cin_real <= 3) SOL_LAUNCH((k_conv5x5_bww_thin<0, 1, true>), dim3(nblk_run), dim3(256), l0, s, a);
+            else SOL_LAUNCH((k_conv5x5_bww_thin<0, 2, true>), dim3(nblk_run), dim3(256), l0, s, a);
+        } else {
+            const size_t l1 = 2 * (size_t)(68 * 32 + 5 * 72 * 2) * sizeof(float);
+            SOL_LAUNCH((k_conv5x5_bww_thin<1, 2, true>), dim3(nblk_run), dim3(256), l1, s, a);
+        }
+        SOL_LAUNCH_CHECK();
+        return SOL_OK;
+    }
     if (W == 64 && ((cin == 4 && cout == 32) || (cin == 32 && cout == 2)) && sol_opt().conv_thin) {
         // all five tap rows in one workgroup: grid = nblk; LDS = 2 stages (>= the 16 KB fold buffer)
         if (cin == 4) {
@@ -1456,7 +1484,7 @@ static int bww_launch(void* stream, const float* x, const float* dz, float* part
         SOL_LAUNCH_CHECK();
         return SOL_OK;
     }
-    if (cin == 32 && cout == 32 && W == 64 && sol_opt().conv_precision != 2) return sol_bww_sb_launch(s, a, nblk_run);
+    if (cin == 32 && cout == 32 && W % 64 == 0 && sol_opt().conv_precision != 2) return sol_bww_sb_launch(s, a, nblk_run);   // (W > 64: its wide kernel)
     if (cin == 32 && cout == 32 && W == 64 && sol_opt().conv_bww32) {
         const size_t lds3 = 2 * ((size_t)(64 + 4) * 32 + 64 * 32) * sizeof(float);
         SOL_LAUNCH(k_conv5x5_bww32, dim3(grid), dim3(256), lds3, s, a);
@@ -1510,11 +1538,11 @@ int sol_bww_batched_jobs(void* stream, int n, const float* const* x, const float
     return sol_bww_sb_jobs_launch((hipStream_t)stream, p);
 }
 
-static int bww_reduce(void* stream, const float* partial, float* dw_hwio, float* db, int rows, int rb, int cin, int cout, int accumulate, int tt = 0) {
+static int bww_reduce(void* stream, const float* partial, float* dw_hwio, float* db, int rows, int rb, int cin, int cout, int accumulate, int tt = 0, int tiles = 1) {
     SOL_REQUIRE(partial && dw_hwio && db, "sol_conv5x5_bwd_weight_reduce: NULL pointer");
     SOL_REQUIRE(cin >= 1 && cin <= 32 && cout >= 1 && cout <= 32, "sol_conv5x5_bwd_weight_reduce: channels out of range");
     int nblk, IP, OP;
-    bww_dims(rows, rb, cin <= 4 ? 4 : 32, cout, &nblk, &IP, &OP);
+    bww_dims(rows, rb, cin <= 4 ? 4 : 32, cout, &nblk, &IP, &OP, tiles);
     const int total = 25 * cin * cout + cout;
     float* pm = const_cast<float*>(partial);       // the caller's workspace: chunk sums are folded in place
     const int chunk = 16, ny = (nblk + chunk - 1) / chunk;
@@ -1531,9 +1559,10 @@ static int bww_reduce(void* stream, const float* partial, float* dw_hwio, float*
 }
 
 extern "C" int sol_conv5x5_bwd_weight_reduce(void* stream, const float* partial, float* dw_hwio, float* db,
-                                             int32_t B, int32_t H, int32_t /*W*/, int32_t cin, int32_t cout,
+                                             int32_t B, int32_t H, int32_t W, int32_t cin, int32_t cout,
                                              int32_t accumulate) {
-    return bww_reduce(stream, partial, dw_hwio, db, B * H, RB, cin, cout, accumulate);
+    SOL_REQUIRE(W <= 64 || W % 64 == 0, "sol_conv5x5_bwd_weight_reduce: rows wider than 64 pixels must be a multiple of 64 pixels wide (got W = %d)", W);
+    return bww_reduce(stream, partial, dw_hwio, db, B * H, RB, cin, cout, accumulate, 0, bww_tiles(W));
 }
 
 // ---- per-step jobs for the fused solver-adjoint + weight-gradient launch (32 -> 32 layers, W == 64) ----------------
@@ -1555,7 +1584,7 @@ int sol_bww_step_job(BwArgs* out, const float* x, const float* dz, float* partia
 
 // n <= 12 layers at once: rows[i] / rb[i] as in bww_reduce (rb <= 0: pick_rb), same summation order as the per-layer launches
 int sol_bww_reduce_layers(void* stream, int n, float* const* partial, float* const* dw_hwio, float* const* db, const int* rows, const int* rb,
-                          const int* cin, const int* cout, int accumulate, int taps_transposed) {
+                          const int* cin, const int* cout, int accumulate, int taps_transposed, int tiles) {
     SOL_REQUIRE(n >= 1 && n <= 12, "sol_bww_reduce_layers: 1 <= n <= 12");
     ReduceJobs J{};
     int max_total = 0, max_ny = 1;
@@ -1563,7 +1592,7 @@ int sol_bww_reduce_layers(void* stream, int n, float* const* partial, float* con
         SOL_REQUIRE(partial[i] && dw_hwio[i] && db[i] && cin[i] >= 1 && cin[i] <= 32 && cout[i] >= 1 && cout[i] <= 32, "sol_bww_reduce_layers: bad layer %d", i);
         ReduceJob& r = J.j[i];
         const int rbi = rb[i] > 0 ? rb[i] : pick_rb(rows[i], cin[i] <= 4 ? 4 : 32, cout[i]);
-        bww_dims(rows[i], rbi, cin[i] <= 4 ? 4 : 32, cout[i], &r.nblk, &r.IP, &r.OP);
+        bww_dims(rows[i], rbi, cin[i] <= 4 ? 4 : 32, cout[i], &r.nblk, &r.IP, &r.OP, tiles);
         r.partial = partial[i]; r.dw = dw_hwio[i]; r.db = db[i]; r.cin = cin[i]; r.cout = cout[i];
         r.ny = (r.nblk + 15) / 16; r.accumulate = accumulate; r.tt = taps_transposed;
         max_total = max_total > 25 * cin[i] * cout[i] + cout[i] ? max_total : 25 * cin[i] * cout[i] + cout[i];
@@ -1582,11 +1611,12 @@ int sol_bww_reduce_layers(void* stream, int n, float* const* partial, float* con
 // the reduction of sol_conv5x5_bwd_weight's partial sums for n <= 12 layers of one image size in two launches (same summation order as n calls
 // of sol_conv5x5_bwd_weight_reduce); dw_hwio[k] / db[k] may point straight into a flat gradient buffer
 extern "C" int sol_conv5x5_bwd_weight_reduce_jobs(void* stream, int32_t n, float* const* partial, float* const* dw_hwio, float* const* db,
-                                                  int32_t B, int32_t H, int32_t /*W*/, const int32_t* cin, const int32_t* cout, int32_t accumulate) {
+                                                  int32_t B, int32_t H, int32_t W, const int32_t* cin, const int32_t* cout, int32_t accumulate) {
     SOL_REQUIRE(n >= 1 && n <= 12 && partial && dw_hwio && db && cin && cout && B >= 1 && H >= 1, "sol_conv5x5_bwd_weight_reduce_jobs: 1 <= n <= 12 layers, no NULL array");
+    SOL_REQUIRE(W <= 64 || W % 64 == 0, "sol_conv5x5_bwd_weight_reduce_jobs: rows wider than 64 pixels must be a multiple of 64 pixels wide (got W = %d)", W);
     int rows[12], rb[12], ci[12], co[12];
     for (int k = 0; k < n; ++k) { rows[k] = B * H; rb[k] = RB; ci[k] = cin[k]; co[k] = cout[k]; }
-    return sol_bww_reduce_layers(stream, n, partial, dw_hwio, db, rows, rb, ci, co, accumulate, 0);
+    return sol_bww_reduce_layers(stream, n, partial, dw_hwio, db, rows, rb, ci, co, accumulate, 0, bww_tiles(W));
 }
 
 int sol_bww_step_reduce(void* stream, const float* partial, float* dw_hwio, float* db, int B, int H, int rb, int cin, int cout, int accumulate) {

@@ -494,6 +494,13 @@ __global__ void __launch_bounds__(512) k_conv5x5_bww_sb(BwArgs a) {
     extern __shared__ __align__(16) unsigned char smem_sb[];
     bww_sb_body<KIND>(a, blockIdx.x, smem_sb);
 }
+// image rows of a.W = 64 * tiles pixels: workgroup = (row block, column tile), the x halo comes from the neighbouring tiles
+// (bww_sb_body<KIND, true>).  A kernel of its own: the W == 64 kernels above keep their code.
+template <int KIND>
+__global__ void __launch_bounds__(512) k_conv5x5_bww_sb_wide(BwArgs a) {
+    extern __shared__ __align__(16) unsigned char smem_sb[];
+    bww_sb_body<KIND, true>(a, blockIdx.x, smem_sb);
+}
 // n <= 5 weight-gradient jobs in ONE launch (karman-3d: the five depth slices of a Conv3D layer, which were five launches of one round of
 // workgroups each -- every one with its own dispatch gap, cold start and tail): workgroup u runs block u % wg_per of job u / wg_per
 template <int KIND>
@@ -574,7 +581,7 @@ constexpr size_t sb_lds(int OP) { return (size_t)4 * 3 * 68 * 64 + 2 * (size_t)5
 int init_sb_kernels() {
     // static LDS (the conv kernels' epilogue-prefetch regions) counts against the same 160 KB
     static std::atomic<unsigned long long> optin{0};
-    return sol_lds_optin(optin, {SOL_K(k_conv5x5_bww_sb<0>), SOL_K(k_conv5x5_bww_sb<2>), SOL_K(k_conv5x5_bww_sb_jobs<0>), SOL_K(k_conv5x5_bww_sb_jobs<2>), SOL_K(k_conv5x5_sb<1, 0>), SOL_K(k_conv5x5_sb<2, 0>),
+    return sol_lds_optin(optin, {SOL_K(k_conv5x5_bww_sb<0>), SOL_K(k_conv5x5_bww_sb<2>), SOL_K(k_conv5x5_bww_sb_jobs<0>), SOL_K(k_conv5x5_bww_sb_jobs<2>), SOL_K(k_conv5x5_bww_sb_wide<0>), SOL_K(k_conv5x5_sb<1, 0>), SOL_K(k_conv5x5_sb<2, 0>),
                                  SOL_K(k_conv5x5_sb<1, 1>), SOL_K(k_conv5x5_sb<2, 1>), SOL_K(k_conv5x5_sb<1, 2>), SOL_K(k_conv5x5_sb<2, 2>)},
                          "split conv kernels", true);
 }
@@ -647,6 +654,14 @@ int sol_conv_sb_launch(hipStream_t s, const ConvArgs& a, int NT, int ntiles) {
 
 int sol_bww_sb_launch(hipStream_t s, const BwArgs& a, int nblk_run) {
     if (int e = init_sb_kernels()) return e;
+    if (a.W > 64) {
+        // wide rows (sol_conv5x5_bwd_weight, which passes no absmax slots): the bf16 six-product body per 64-pixel column tile;
+        // nblk_run counts (row block, tile) pairs
+        SOL_REQUIRE(a.W % 64 == 0, "sol_bww_sb_launch: W > 64 must be a multiple of 64 (got %d)", a.W);
+        SOL_LAUNCH(k_conv5x5_bww_sb_wide<0>, dim3(nblk_run), dim3(512), BW_LDS, s, a);
+        SOL_LAUNCH_CHECK();
+        return SOL_OK;
+    }
     const bool use_sh = sol_opt().conv_precision == 0;
     // fp16 three-product kernel: absmax of both operands known and no workgroup straddles two segments
     if (use_sh && a.xmax && a.zmax && (a.B * a.H) % a.rb == 0) SOL_LAUNCH(k_conv5x5_bww_sb<2>, dim3(nblk_run), dim3(512), BW_LDS, s, a);

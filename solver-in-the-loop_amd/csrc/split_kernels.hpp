@@ -123,9 +123,22 @@ constexpr int BW_LDS = 2 * 3 * BW_XPL + 6 * 3 * BW_ZPL;   // 122,880 B (three pl
 
 // KIND 0: bf16 planes x3, six products;  KIND 2: fp16 planes x2 scaled per segment by the absmax of x / dz, three products
 // (the host guarantees that a workgroup's rows lie in ONE segment)
-template <int KIND>
+//
+// WIDE (a.W a multiple of 64 beyond 64): the image is a.W / 64 column tiles and the W == 64 algorithm runs per tile.  Block blk is
+// (row block blk / tiles, tile blk % tiles) and keeps its own slice of `partial`, so the reduce kernels sum row blocks and tiles in
+// one fixed order.  A tile's dz row is its own 64 pixels (every dz pixel has one owner: the bias gradient counts it once); its x row
+// is 68 pixels: halo positions 0, 1 / 66, 67 hold the last / first two pixels of the neighbouring tile where there is one (32 items
+// of 1 px x 4 ch, moved by lanes 0..31 of wave 0, written as the 2-byte halves of the planes' pixel pairs) and stay zero at the image
+// border.  Every thread issues the halo request (lanes without a halo item ask for the first pixel of their own row and drop it):
+// the request stream, and with it every vmcnt wait, is the same in all waves.  The halo item of x row r is requested one row BEFORE
+// the row item of x row r + 1 and staged together with the row item of x row r, i.e. right behind the requests the row items' waits
+// retire anyway: the three rows of look-ahead of the row items are untouched, at the price of two rotating float4.  Register budget
+// and the forms that spilled: DESIGN.md 4.5-4.7.
+template <int KIND, bool WIDE = false>
 __device__ __forceinline__ void bww_sb_body(const BwArgs& a, const int blk, unsigned char* smem_sb) {
     constexpr int W = 64;
+    const int tiles = WIDE ? a.W / W : 1, WI = WIDE ? a.W : W;          // column tiles, image width
+    const int rblk = WIDE ? blk / tiles : blk, tile = WIDE ? blk - rblk * tiles : 0;
     constexpr int NPL = KIND == 2 ? 2 : 3;
     constexpr int BW_XST = NPL * BW_XPL, BW_ZST = NPL * BW_ZPL;
     unsigned char* const XS = smem_sb;
@@ -137,7 +150,7 @@ __device__ __forceinline__ void bww_sb_body(const BwArgs& a, const int blk, unsi
     const int mt = wave & 1, nt = (wave >> 1) & 1, kb = wave >> 2;
     const int H = a.H;
     const int R = a.nseg * a.B * H, RPS = a.B * H;
-    const int r0 = blk * a.rb, r1 = min(r0 + a.rb, R);
+    const int r0 = rblk * a.rb, r1 = min(r0 + a.rb, R);
 
     // Staging roles: waves 0..3 move the x row, waves 4..7 the dz row.  One item = 2 pixels x 4 channels (two float4 requests);
     // both roles have exactly 256 items per row: x items are the image pixel pairs (2i, 2i+1) -> halo positions (2i+2, 2i+3);
@@ -148,6 +161,10 @@ __device__ __forceinline__ void bww_sb_body(const BwArgs& a, const int blk, unsi
 #endif
     const int it = tid & 255;
     const int pxg = it >> 3, c4 = it & 7;          // 2-pixel group, channel quad
+    // WIDE: halo item of this thread, hp = 0..3: image pixels x0-2, x0-1, x0+64, x0+65 -> halo positions 0, 1, 66, 67
+    const int hp = (lane >> 3) & 3, hside = hp >> 1;
+    const bool hitem = WIDE && wave == 0 && lane < 32 && (hside ? tile + 1 < tiles : tile > 0);
+    const int hoff = hitem ? ((hside ? W : -2) + (hp & 1)) * 8 + c4 : c4;      // float4 offset from the tile's first pixel of the row
     float bs[4] = {0.f, 0.f, 0.f, 0.f};
     float sx = 1.f, sz = 1.f, out_scale = 1.f;
     if constexpr (KIND == 2) {
@@ -165,13 +182,24 @@ __device__ __forceinline__ void bww_sb_body(const BwArgs& a, const int blk, unsi
     unsigned long long role_base = (unsigned long long)(xrole ? a.x : a.dz);
     long role_seg = xrole ? a.x_seg : a.dz_seg;
     asm volatile("" : "+s"(role_base), "+s"(role_seg));
+    auto row_ptr = [&](int gr) __attribute__((always_inline)) {
+        typedef const f32x4 __attribute__((address_space(1)))* gf4p;
+        const int rr = gr >= 0 && gr < R ? gr : r0, seg = rr / RPS, grs = rr - seg * RPS;
+        return (gf4p)(role_base + ((unsigned long long)seg * role_seg + (unsigned long long)grs * WI * 32 + (unsigned long long)tile * (W * 32)) * sizeof(float));
+    };
+    // WIDE: the halo item of x row gx_row (dz role: a dropped request of the same shape)
+    auto request_halo = [&](int gx_row, float4& h) __attribute__((always_inline)) {
+        if constexpr (WIDE) {
+            if (BWW_DBG & 8) { h = make_float4(1e-3f, 2e-3f, -1e-3f, 5e-4f); return; }
+            const f32x4 e = row_ptr(xrole ? gx_row : r0)[hoff];
+            h = make_float4(e[0], e[1], e[2], e[3]);
+        }
+    };
     auto request = [&](int gx_row, int gz_row, float4& v0, float4& v1) __attribute__((always_inline)) {
         const int gr = xrole ? gx_row : gz_row;
         // (global address space spelled out: a pointer made from the opaque integer is generic, and flat loads also count in
         // lgkmcnt -- the LDS-only barriers below would wait for them)
-        typedef const f32x4 __attribute__((address_space(1)))* gf4p;
-        const int rr = gr >= 0 && gr < R ? gr : r0, seg = rr / RPS, grs = rr - seg * RPS;
-        gf4p rp = (gf4p)(role_base + ((unsigned long long)seg * role_seg + (unsigned long long)grs * W * 32) * sizeof(float));
+        const auto rp = row_ptr(gr);
         if (BWW_DBG & 8) { v0 = v1 = make_float4(1e-3f, 2e-3f, -1e-3f, 5e-4f); return; }
         const f32x4 q0 = rp[(2 * pxg) * 8 + c4], q1 = rp[(2 * pxg + 1) * 8 + c4];
         v0 = make_float4(q0[0], q0[1], q0[2], q0[3]);
@@ -194,9 +222,34 @@ __device__ __forceinline__ void bww_sb_body(const BwArgs& a, const int blk, unsi
         }
     };
     // write the item as x row gx_row / dz row gz_row (callers pass rows that are in range for the thread's role)
-    auto stage = [&](int gx_row, int gz_row, const float4& v0, const float4& v1) __attribute__((always_inline)) {
-        if (xrole) store_item(v0, v1, pxg + 1, XS + (gx_row & 1) * BW_XST, BW_XPL, 256, true);
-        else {
+    // WIDE: one halo pixel x 4 channels -> the 2-byte half hpos & 1 of pixel pair hpos >> 1, every plane
+    auto store_halo = [&](const float4& h, unsigned char* base) __attribute__((always_inline)) {
+        const float e[4] = {h.x, h.y, h.z, h.w};
+        // (the lane index made opaque: the four swizzled addresses are recomputed here once per row instead of living in registers
+        //  across the MFMA block)
+        int ln = lane;
+        asm volatile("" : "+v"(ln));
+        const int hq = (ln >> 3) & 3, hps = (hq >> 1) ? 66 + (hq & 1) : (hq & 1), pg = hps >> 1;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const int ch = 4 * (ln & 7) + c;
+            unsigned p[3];
+            if constexpr (KIND == 2) split2u(e[c], 0.f, sx, p[0], p[1]);
+            else split3(e[c], 0.f, p[0], p[1], p[2]);
+            unsigned char* q = base + ch * 256 + ((((pg >> 2) ^ bw_swx(ch)) << 4) | ((pg & 3) << 2)) + 2 * (hps & 1);
+#pragma unroll
+            for (int pl = 0; pl < NPL; ++pl) *reinterpret_cast<unsigned short*>(q + pl * BW_XPL) = (unsigned short)p[pl];
+        }
+    };
+    auto stage = [&](int gx_row, int gz_row, const float4& v0, const float4& v1, const float4& h) __attribute__((always_inline)) {
+        if (xrole) {
+            store_item(v0, v1, pxg + 1, XS + (gx_row & 1) * BW_XST, BW_XPL, 256, true);
+            if constexpr (WIDE) {
+                if (wave == 0) {
+                    if (hitem) store_halo(h, XS + (gx_row & 1) * BW_XST);
+                }
+            }
+        } else {
             store_item(v0, v1, pxg, ZS + ((gz_row + 6) % 6) * BW_ZST, BW_ZPL, 128, false);
             if (gz_row >= r0 && gz_row < r1) {   // bias gradient: every owned dz row is staged exactly once
                 bs[0] += v0.x + v1.x;
@@ -217,9 +270,13 @@ __device__ __forceinline__ void bww_sb_body(const BwArgs& a, const int blk, unsi
     constexpr int XD = PIPE ? 2 : 1, ZD = PIPE ? 4 : 3;          // row gr stages x row gr + XD and dz row gr + ZD
     float4 sA0, sA1, sB0, sB1, sC0, sC1;
     sA0 = sA1 = sB0 = sB1 = sC0 = sC1 = make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 hP, hQ;                                               // WIDE: the halo items of x rows gr + XD (staged in row gr) and gr + XD + 1
+    hP = hQ = make_float4(0.f, 0.f, 0.f, 0.f);
     {
         constexpr int NZ0 = ZD + 2;                              // dz rows staged here: r0-2 .. r0+ZD-1
-        float4 pv[NZ0][2];
+        float4 pv[NZ0][2], ph[XD];
+#pragma unroll
+        for (int k = 0; k < XD; ++k) request_halo(r0 + k < r1 ? r0 + k : r0, ph[k]);
         if (xrole) {
 #pragma unroll
             for (int k = 0; k < XD; ++k) request(r0 + k < r1 ? r0 + k : r0, 0, pv[k][0], pv[k][1]);
@@ -228,22 +285,25 @@ __device__ __forceinline__ void bww_sb_body(const BwArgs& a, const int blk, unsi
             for (int k = 0; k < NZ0; ++k) request(0, r0 - 2 + k, pv[k][0], pv[k][1]);
         }
         request(r0 + XD < r1 ? r0 + XD : r0, r0 + ZD, sB0, sB1);
+        request_halo(r0 + XD < r1 ? r0 + XD : r0, hQ);
         request(r0 + XD + 1 < r1 ? r0 + XD + 1 : r0, r0 + ZD + 1, sC0, sC1);
         __builtin_amdgcn_sched_barrier(0);
         if (xrole) {
 #pragma unroll
             for (int k = 0; k < XD; ++k)
-                if (r0 + k < r1) stage(r0 + k, 0, pv[k][0], pv[k][1]);
+                if (r0 + k < r1) stage(r0 + k, 0, pv[k][0], pv[k][1], ph[k]);
             // the zero halo positions (0, 1) and (66, 67) of both stages, all planes: 2 x NPL x 32 channels x 2 pieces
+            // (WIDE: only the sides at the image border -- the others belong to the halo items)
             for (int e = tid; e < 2 * NPL * 32 * 2; e += 256) {
                 const int side = e & 1, ch = (e >> 1) & 31, pl = (e >> 6) % NPL, st = e / (64 * NPL);
                 const int pg = side ? 33 : 0;
+                if (WIDE && (side ? tile + 1 < tiles : tile > 0)) continue;
                 *reinterpret_cast<unsigned*>(XS + st * BW_XST + pl * BW_XPL + ch * 256 + ((((pg >> 2) ^ bw_swx(ch)) << 4) | ((pg & 3) << 2))) = 0u;
             }
         } else {
 #pragma unroll
             for (int k = 0; k < NZ0; ++k)
-                if (z_in_range(r0 - 2 + k)) stage(0, r0 - 2 + k, pv[k][0], pv[k][1]);
+                if (z_in_range(r0 - 2 + k)) stage(0, r0 - 2 + k, pv[k][0], pv[k][1], hP);
         }
     }
 #define BW_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")   /* LDS only: requests stay in flight */
@@ -286,13 +346,15 @@ __device__ __forceinline__ void bww_sb_body(const BwArgs& a, const int blk, unsi
 
     // one image row: request the items of x row gr+XD+2 / dz row gr+ZD+2 into (i0, i1), run the 25 taps of row gr, write the items
     // held in (o0, o1) -- x row gr+XD / dz row gr+ZD, requested two iterations ago -- to LDS
-    auto do_row = [&](const int gr, float4& i0, float4& i1, const float4& o0, const float4& o1) __attribute__((always_inline)) {
+    // (WIDE: the halo item of x row gr+XD+1 is requested into hi in front of them, the one of x row gr+XD, held in ho, is written)
+    auto do_row = [&](const int gr, float4& i0, float4& i1, const float4& o0, const float4& o1, float4& hi, const float4& ho) __attribute__((always_inline)) {
         const int y = gr % H;
         BWW_STAMP(gr, 0);
 #ifdef BWW_PROF
         { const unsigned t_ = (unsigned)__builtin_amdgcn_s_memrealtime(); if (lane == 0 && gr - r0 < 40) bww_st[(gr - r0) * 8 + 6] = t_; }      // 100 MHz: the clock the CU holds
 #endif
         const bool req_late = PIPE && BWW_REQ_LATE && !xrole;            // (wave uniform)
+        request_halo(gr + XD + 1 < r1 ? gr + XD + 1 : r0, hi);
         if (!req_late) request(gr + XD + 2 < r1 ? gr + XD + 2 : r0, gr + ZD + 2, i0, i1);
         __builtin_amdgcn_sched_barrier(0);
         // Phase shift between the two waves of a SIMD (waves w and w + 4): the dz role stages its row at the HEAD of the iteration, the x role
@@ -300,15 +362,15 @@ __device__ __forceinline__ void bww_sb_body(const BwArgs& a, const int blk, unsi
         // idle) and both multiplying at the same time.  Legal: the slot written (dz row gr+ZD) is read by nobody during this iteration.
         // Same-box A/B, three alternations (tools/ab_lib.py): 0 (both late) 11.554, 1 (dz early) 11.430, 2 (x early) 11.612, 3 (both early) 11.521 ms per step.
         if (BWW_PHASE_SHIFT == 1 && !xrole) {
-            if (!(BWW_DBG & 2) && z_in_range(gr + ZD)) stage(gr + XD, gr + ZD, o0, o1);
+            if (!(BWW_DBG & 2) && z_in_range(gr + ZD)) stage(gr + XD, gr + ZD, o0, o1, ho);
             __builtin_amdgcn_sched_barrier(0);
         }
         if (BWW_PHASE_SHIFT == 2 && xrole) {            // (variant: the x role stages early, the dz role late)
-            if (!(BWW_DBG & 2) && gr + XD < r1) stage(gr + XD, gr + ZD, o0, o1);
+            if (!(BWW_DBG & 2) && gr + XD < r1) stage(gr + XD, gr + ZD, o0, o1, ho);
             __builtin_amdgcn_sched_barrier(0);
         }
         if (BWW_PHASE_SHIFT == 3) {                     // (variant: both roles stage early)
-            if (!(BWW_DBG & 2) && (xrole ? gr + XD < r1 : z_in_range(gr + ZD))) stage(gr + XD, gr + ZD, o0, o1);
+            if (!(BWW_DBG & 2) && (xrole ? gr + XD < r1 : z_in_range(gr + ZD))) stage(gr + XD, gr + ZD, o0, o1, ho);
             __builtin_amdgcn_sched_barrier(0);
         }
         if (req_late) {
@@ -404,7 +466,7 @@ __device__ __forceinline__ void bww_sb_body(const BwArgs& a, const int blk, unsi
         __builtin_amdgcn_sched_barrier(0);
         BWW_STAMP(gr, 3);                               // last MFMA issued
         __builtin_amdgcn_sched_barrier(0);
-        if (!(BWW_DBG & 2) && (xrole ? ((BWW_PHASE_SHIFT & 2) == 0 && gr + XD < r1) : ((BWW_PHASE_SHIFT & 1) == 0 && z_in_range(gr + ZD)))) stage(gr + XD, gr + ZD, o0, o1);
+        if (!(BWW_DBG & 2) && (xrole ? ((BWW_PHASE_SHIFT & 2) == 0 && gr + XD < r1) : ((BWW_PHASE_SHIFT & 1) == 0 && z_in_range(gr + ZD)))) stage(gr + XD, gr + ZD, o0, o1, ho);
         if constexpr (PIPE) {
             // operands of row gr + 1: x row gr + 1 and dz row gr + 3 were staged during row gr - 1 (visible since its barrier); the slots written
             // during THIS row (x row gr + 2, dz row gr + 4) are other slots.  The x role waits for the barrier here anyway; for the dz role the
@@ -423,17 +485,17 @@ __device__ __forceinline__ void bww_sb_body(const BwArgs& a, const int blk, unsi
     for (int gr = r0; gr < r1; gr += 6) {
         // (early exits, not `if (gr + k < r1) do_row(...)`: behind a conditional row every register-resident dz fragment would be a
         // phi of its shifted and unshifted place -- 32 copies and their temporaries per row, 227 spilled registers)
-        do_row(gr, sA0, sA1, sB0, sB1);
+        do_row(gr, sA0, sA1, sB0, sB1, hP, hQ);
         if (gr + 1 >= r1) break;
-        do_row(gr + 1, sB0, sB1, sC0, sC1);
+        do_row(gr + 1, sB0, sB1, sC0, sC1, hQ, hP);
         if (gr + 2 >= r1) break;
-        do_row(gr + 2, sC0, sC1, sA0, sA1);
+        do_row(gr + 2, sC0, sC1, sA0, sA1, hP, hQ);
         if (gr + 3 >= r1) break;
-        do_row(gr + 3, sA0, sA1, sB0, sB1);
+        do_row(gr + 3, sA0, sA1, sB0, sB1, hQ, hP);
         if (gr + 4 >= r1) break;
-        do_row(gr + 4, sB0, sB1, sC0, sC1);
+        do_row(gr + 4, sB0, sB1, sC0, sC1, hP, hQ);
         if (gr + 5 >= r1) break;
-        do_row(gr + 5, sC0, sC1, sA0, sA1);
+        do_row(gr + 5, sC0, sC1, sA0, sA1, hQ, hP);
     }
 #ifdef BWW_PROF
     if (g_bww_prof)

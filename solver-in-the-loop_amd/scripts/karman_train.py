@@ -111,7 +111,8 @@ def main(argv=None):
                            pressure_solver=params["pressure_solver"])
     log.info("pressure solver: %s" % masks.pressure_solver)
     # eval('model_'+params['model']) (karman_train.py:394): mars_moon runs the C++ schedule (SolTrainer), mercury the
-    # autograd composition of the same ops captured into a hipGraph (GraphTrainer)
+    # hand-written schedule captured into a hipGraph (GraphTrainer); a domain beyond the one-workgroup grids (-s 1 on a -r 128 set):
+    # LargeGridTrainer, either model
     assert params["model"] in sol_amd.model.MODELS, "unknown model %r (have: %s)" % (params["model"], ", ".join(sol_amd.model.MODELS))
     model = sol_amd.model.MODELS[params["model"]](3, 2, seed, dev)
     model.summary(print_fn=log.info)

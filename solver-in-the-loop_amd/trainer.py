@@ -56,12 +56,13 @@ class _conv_precision_scope:
 
 
 def _refuse_large_grid(who, Y, X):
-    """The trainers stop at the one-workgroup solver grids: the solver step itself is differentiable beyond them (ops.KarmanStepLargeFn),
-    but the 5x5 weight gradient is built for image rows of W <= 64 pixels (sol_conv5x5_bwd_weight, csrc/conv5x5.hip).  Refused here, at
-    construction, instead of in the middle of the first reverse sweep."""
+    """SolTrainer and GraphTrainer stop at the one-workgroup solver grids: their solver launches (sol_karman_step_fwd / _bwd, the fused
+    adjoint) are built for at most 8192 cells and rows of W <= 64 cells.  Beyond them LargeGridTrainer runs the same schedule over the
+    large-grid solver pair.  Refused here, at construction, instead of in the middle of the first reverse sweep."""
     if Y * X > 8192 or X > 64:
         raise ValueError("%s: a %dx%d domain is beyond the trainers -- the 5x5 weight gradient (sol_conv5x5_bwd_weight) is built for "
-                         "W <= 64 and the fused solver adjoint for at most 8192 cells; differentiate single large-grid steps with "
+                         "W <= 64 in the schedules of this class and the fused solver adjoint for at most 8192 cells; train on such a "
+                         "domain with LargeGridTrainer (X a multiple of 64), differentiate single large-grid steps with "
                          "KarmanFlow.step / ops.karman_step_large" % (who, Y, X))
 
 
@@ -274,7 +275,7 @@ class GraphTrainer:
             raise ValueError("schedule must be 'manual' or 'autograd'")
         self.schedule = schedule
         self._sched = None
-        _refuse_large_grid("GraphTrainer", Y, X)
+        self._check_grid(Y, X)
         from . import fluid, karman
         _lib.require_gpu()
         self.lib = _lib.load()
@@ -322,6 +323,10 @@ class GraphTrainer:
         self.use_graph, self._graph = use_graph, None
         self._want_final, self._eager = False, False
         self._dp = DPStep(self._fwd_bwd_flat, self._apply_flat, group=group, comm=comm, flat=self._flat)
+
+    @staticmethod
+    def _check_grid(Y, X):
+        _refuse_large_grid("GraphTrainer", Y, X)
 
     def _unrolled(self):
         if self.schedule == "manual":
@@ -438,8 +443,123 @@ class GraphTrainer:
     train_step = SolTrainer.train_step
 
 
+class LargeGridTrainer(GraphTrainer):
+    """GraphTrainer's call surface (constructor keywords, fwd_bwd / train_step / apply_gradients, `grads`, `loss_steps`, `final`, data
+    parallel through DPStep, use_graph) for domains BEYOND the one-workgroup solver grids: more than 8192 cells or rows wider than 64
+    cells, X a multiple of 64 (the reference's 256 x 128 data-generation grid).  The hand-written schedule of
+    GraphTrainer._unrolled_schedule over the large-grid solver pair: per unrolled step sol_karman_step_fwd_large_saved (direct or CG
+    pressure solve, as SceneMasks decides for the scene and `pressure_solver`) -> scaled features -> NetSchedule2D.forward ->
+    correction -> ops.l2_loss_fwd_bwd; in reverse NetSchedule2D.backward (weight gradients of W = 64 * tiles rows: the wide form of
+    sol_conv5x5_bwd_weight) -> feature gradient / in_std added to the cotangent on the faces to_feature reads ->
+    sol_karman_step_bwd_large.  Networks: mars_moon and mercury.
+
+    use_graph=True captures the step once (kernel nodes only, sol_graph_check).  With a CG scene the iteration count of a solve is not
+    known at capture time: a captured step issues the launches of the WHOLE `cg_max_iter` budget per solve (converged iterations fall
+    through), so choose cg_max_iter close to what the scene needs -- or run such scenes with use_graph=False, which stops at
+    convergence and is fully supported.  After a step `solve_info` holds "iterations" / "converged" [msteps, B] and "iterations_bwd" /
+    "converged_bwd" [msteps - 1, B] (the first unrolled step's input receives no gradient: its solver adjoint is not run) for CG scenes."""
+
+    def __init__(self, net, B, Y, X, msteps, std_v, std_re, **kw):
+        if kw.get("schedule", "manual") != "manual":
+            raise ValueError("LargeGridTrainer runs the hand-written schedule only (schedule='manual')")
+        super().__init__(net, B, Y, X, msteps, std_v, std_re, **kw)
+        self.solve_info = {}
+
+    @staticmethod
+    def _check_grid(Y, X):
+        if Y * X <= 8192 and X <= 64:
+            raise ValueError("LargeGridTrainer: a %dx%d domain is served by the one-workgroup trainers -- use SolTrainer (mars_moon) or "
+                             "GraphTrainer (make_trainer picks)" % (Y, X))
+        if X % 64 != 0:
+            raise ValueError("LargeGridTrainer: the convolutions of a large domain take rows of X %% 64 == 0 cells (got %dx%d)" % (Y, X))
+
+    def _unrolled_schedule(self):
+        from .schedule2d import NetSchedule2D
+        d, vy, vx, re, gt_vy, gt_vx = self._in
+        B, Y, X, ms = self.B, self.Y, self.X, self.msteps
+        dev = self.device
+        lib = self.lib
+        if self._sched is None:
+            self._sched = NetSchedule2D(self.net, B, Y, X)
+            self._mk = mk = self.sim._masks(self.dom, self.bcv, self.bcm, dev)
+            self._kcfg = cfg = ops.karman_cfg(B, Y, X, self.dom.dx[1], dt=self.dt, res=self.res, masks=mk, **self.sim._solver)
+            self._fs = [1.0 / float(v) for v in self._scale_in_host]
+            ws = lambda n: torch.empty((int(n) + 3) // 4, dtype=torch.float32, device=dev)
+            self._ws_fwd = ws(ops.large_workspace_bytes(cfg, mk))
+            self._ws_bwd = ws(lib.sol_karman_step_bwd_large_workspace_bytes(C.byref(cfg)))
+            self._zplane = torch.zeros(B, Y, X, dtype=torch.float32, device=dev)      # the fourth (padding) input channel
+            self.pressure_solver_used = mk.pressure_solver
+        sch, mk, cfg, fs = self._sched, self._mk, self._kcfg, self._fs
+        so, sl = self._scale_out_host, self._std_loss_host
+        hdr, bhdr = ops._hdr(mk.direct_header), ops._hdr(mk.box_header)
+        sch.begin_step()
+        re_plane = (re * fs[2]).reshape(B, 1, 1).expand(B, Y, X)
+        keep, losses, it_f, it_b = [], [], [], []
+        for i in range(ms):
+            (d2, vy2, vx2), head = ops._large_fwd(d, vy, vx, re, cfg, mk)
+            svy, svx = torch.empty_like(vy), torch.empty_like(vx)
+            cg = ops._cg_info(mk, B, dev)
+            check(lib.sol_karman_step_fwd_large_saved(*head, ptr(svy), ptr(svx), hdr, ptr(mk.box), bhdr, ptr(cg), ptr(self._ws_fwd),
+                                                      self._ws_fwd.numel() * 4))
+            it_f.append(cg)
+            # to_feature / in_std (karman_train.py:77-86, 413-416), padded to the four channels the first layer's kernels read
+            feat = torch.stack([vy2[:, :Y] * fs[0], vx2[:, :, :X] * fs[1], re_plane, self._zplane], dim=-1)
+            out, state = sch.forward(feat)
+            vy2[:, :Y].add_(out[..., 0], alpha=so[0])             # to_staggered + add: the last row / column gets no correction
+            vx2[:, :, :X].add_(out[..., 1], alpha=so[1])
+            li, gi = ops.l2_loss_fwd_bwd((vy2, vx2), (gt_vy[i], gt_vx[i]), sl, gscale=1.0 / ms)
+            losses.append(li.reshape(()))
+            keep.append((svy, svx, state, gi))
+            d, vy, vx = d2, vy2, vx2
+        gin = None
+        for i in range(ms - 1, -1, -1):
+            svy, svx, state, G = keep[i]
+            if gin is not None:
+                G[0].add_(gin[0])
+                G[1].add_(gin[1])
+            dO = torch.stack([G[0][:, :Y] * so[0], G[1][:, :, :X] * so[1]], dim=-1)
+            dfeat = sch.backward(state, dO)
+            keep[i] = None
+            if i == 0:
+                break                                             # nothing differentiates the start state
+            G[0][:, :Y].add_(dfeat[..., 0], alpha=fs[0])
+            G[1][:, :, :X].add_(dfeat[..., 1], alpha=fs[1])
+            oy, ox = torch.empty_like(svy), torch.empty_like(svx)
+            cg = ops._cg_info(mk, B, dev)
+            check(lib.sol_karman_step_bwd_large(C.byref(cfg), stream(), ptr(svy), ptr(svx), ptr(re), ptr(mk.active), ptr(mk.velBCyMask),
+                                                mk.bc_stride, ptr(G[0]), ptr(G[1]), ptr(oy), ptr(ox), hdr, ptr(mk.box), bhdr, ptr(cg),
+                                                ptr(self._ws_bwd), self._ws_bwd.numel() * 4))
+            it_b.append(cg)
+            gin = (oy, ox)
+        losses = _lib.stack0(losses)
+        _lib.dcopy_(self.loss_steps, losses)
+        _lib.dcopy_(self.grads, sch.end_step())
+        for dst, src in zip(self._fin, (d, vy, vx)):
+            _lib.dcopy_(dst, src)
+        if it_f[0] is not None:
+            self._cg_steps = (it_f, it_b[::-1])
+
+    def _fwd_bwd(self, *a, **kw):
+        loss = super()._fwd_bwd(*a, **kw)
+        cgs = getattr(self, "_cg_steps", None)
+        if cgs is not None:                         # (the [2, B] buffers of a captured step are the graph's own: refilled by every replay)
+            f, b = cgs
+            self.solve_info = {"iterations": torch.stack([t[0] for t in f]), "converged": torch.stack([t[1] for t in f])}
+            if b:
+                self.solve_info["iterations_bwd"] = torch.stack([t[0] for t in b])
+                self.solve_info["converged_bwd"] = torch.stack([t[1] for t in b])
+        return loss
+
+
+def _beyond_one_workgroup(Y, X):
+    return Y * X > 8192 or X > 64
+
+
 def make_trainer(net, masks, B, Y, X, msteps, dx, std_v, std_re, **kw):
-    """SolTrainer (the C++ schedule: model_mars_moon) or GraphTrainer (autograd composition in a hipGraph: everything else)."""
+    """SolTrainer (the C++ schedule: model_mars_moon), GraphTrainer (every other network) or, for a domain beyond the one-workgroup
+    solver grids, LargeGridTrainer (either network)."""
+    if _beyond_one_workgroup(Y, X):
+        return LargeGridTrainer(net, B, Y, X, msteps, std_v, std_re, dx=dx, masks=masks, **kw)
     if net.name == "mars_moon":
         # the C++ schedule takes its scene and its pressure solver from `masks` alone (obstacles / active / pressure_solver
         # describe them for GraphTrainer's KarmanFlow)
