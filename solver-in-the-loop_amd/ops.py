@@ -35,6 +35,12 @@ def karman_cfg(B, Y, X, dx, dt=1.0, res=None, cg_rtol=1e-6, cg_atol=1e-9, cg_max
     return cfg
 
 
+def beyond_one_workgroup(Y, X):
+    """True for a grid the one-workgroup solver kernels (sol_karman_step_fwd / _bwd, the fused adjoint) do not take: more than 8192 cells
+    or rows wider than 64 cells.  Such a grid runs the multi-launch path (karman_step_large, trainer.LargeGridTrainer)."""
+    return Y * X > 8192 or X > 64
+
+
 class SceneMasks:
     """Device-resident constant masks of a scene: active (1 - obstacle), inflow rate, velBCy,
     velBCyMask (reference: KarmanFlow.__init__ karman_train.py:166-171 and :366-373)."""
@@ -48,9 +54,10 @@ class SceneMasks:
         n = (Y + 1) * X
         assert self.velBCy.numel() % n == 0 and self.velBCy.numel() == self.velBCyMask.numel()
         self.bc_stride = 0 if self.velBCy.numel() == n else n
+        self.large = beyond_one_workgroup(Y, X)      # the multi-launch path (karman_step_large)
         # two-level CG preconditioner (host-prepared dense coarse inverse), when the grid allows it
         self.coarse_inv = None
-        if precondition and not os.environ.get("SOL_NO_PRECOND") and Y * X <= 8192 and _lib.load().sol_karman_precond_supported(Y, X):
+        if precondition and not os.environ.get("SOL_NO_PRECOND") and not self.large and _lib.load().sol_karman_precond_supported(Y, X):
             from .precond import coarse_inverse
             self.coarse_inv = _lib.f32(coarse_inverse(self.active.reshape(Y, X).cpu().numpy()), device)
         # direct pressure solver (fast diagonalisation + capacitance correction) where it is built and the
@@ -60,7 +67,6 @@ class SceneMasks:
         want = os.environ.get("SOL_PRESSURE_SOLVER", pressure_solver)
         if want not in ("auto", "direct", "cg"):
             raise ValueError("pressure_solver must be 'auto', 'direct' or 'cg' (got %r)" % (want,))
-        self.large = Y * X > 8192 or X > 64          # beyond the one-workgroup kernels: the multi-launch path (karman_step_large)
         if want != "cg" and (self.large or _lib.load().sol_karman_direct_supported(Y, X)):
             from .precond import direct_solver_blob
             blob = direct_solver_blob(self.active.reshape(Y, X).cpu().numpy(), max_window=64 if self.large else 16)
@@ -124,15 +130,7 @@ class KarmanStepLargeFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, d, vy, vx, re, cfg, masks, workspace, info):
-        lib = _lib.load()
-        d, vy, vx = d.contiguous(), vy.contiguous(), vx.contiguous()
-        workspace = _workspace(large_workspace_bytes(cfg, masks), workspace, vy.device)
-        outs, head = _large_fwd(d, vy, vx, re, cfg, masks)
-        svy, svx = torch.empty_like(vy), torch.empty_like(vx)
-        cg_info = _cg_info(masks, cfg.B, vy.device)
-        check(lib.sol_karman_step_fwd_large_saved(*head, ptr(svy), ptr(svx), _hdr(masks.direct_header), ptr(masks.box),
-                                                  _hdr(masks.box_header), ptr(cg_info), ptr(workspace), workspace.numel() * 4))
-        _publish_cg(info, cg_info)
+        outs, svy, svx = karman_step_large_saved(d, vy, vx, re, cfg, masks, workspace, info)
         ctx.save_for_backward(svy, svx, re)
         ctx.cfg, ctx.masks, ctx.info = cfg, masks, info
         ctx.mark_non_differentiable(outs[0])
@@ -145,6 +143,21 @@ class KarmanStepLargeFn(torch.autograd.Function):
         gvx = torch.zeros_like(svx) if gvx is None else gvx.contiguous()
         oy, ox = karman_step_large_bwd(svy, svx, re, gvy, gvx, ctx.cfg, ctx.masks, info=ctx.info)
         return None, oy, ox, None, None, None, None, None
+
+
+def karman_step_large_saved(d, vy, vx, re, cfg, masks, workspace=None, info=None):
+    """The differentiable form of the large-grid step without autograd (sol_karman_step_fwd_large_saved): ((d, vy, vx) after the step,
+    saved vy, saved vx) -- the post-diffusion velocity karman_step_large_bwd takes.  `info` as in karman_step_large."""
+    lib = _lib.load()
+    d, vy, vx = d.contiguous(), vy.contiguous(), vx.contiguous()
+    workspace = _workspace(large_workspace_bytes(cfg, masks), workspace, vy.device)
+    outs, head = _large_fwd(d, vy, vx, re, cfg, masks)
+    svy, svx = torch.empty_like(vy), torch.empty_like(vx)
+    cg_info = _cg_info(masks, cfg.B, vy.device)
+    check(lib.sol_karman_step_fwd_large_saved(*head, ptr(svy), ptr(svx), _hdr(masks.direct_header), ptr(masks.box),
+                                              _hdr(masks.box_header), ptr(cg_info), ptr(workspace), workspace.numel() * 4))
+    _publish_cg(info, cg_info)
+    return outs, svy, svx
 
 
 def karman_step_large_bwd(svy, svx, re, gvy, gvx, cfg, masks, workspace=None, info=None):

@@ -56,17 +56,76 @@ class _conv_precision_scope:
 
 
 def _refuse_large_grid(who, Y, X):
-    """SolTrainer and GraphTrainer stop at the one-workgroup solver grids: their solver launches (sol_karman_step_fwd / _bwd, the fused
-    adjoint) are built for at most 8192 cells and rows of W <= 64 cells.  Beyond them LargeGridTrainer runs the same schedule over the
+    """SolTrainer and GraphTrainer stop at the one-workgroup solver grids (ops.beyond_one_workgroup): their solver launches
+    (sol_karman_step_fwd / _bwd, the fused adjoint) are built for those.  Beyond them LargeGridTrainer runs the same schedule over the
     large-grid solver pair.  Refused here, at construction, instead of in the middle of the first reverse sweep."""
-    if Y * X > 8192 or X > 64:
+    if ops.beyond_one_workgroup(Y, X):
         raise ValueError("%s: a %dx%d domain is beyond the trainers -- the 5x5 weight gradient (sol_conv5x5_bwd_weight) is built for "
                          "W <= 64 in the schedules of this class and the fused solver adjoint for at most 8192 cells; train on such a "
                          "domain with LargeGridTrainer (X a multiple of 64), differentiate single large-grid steps with "
                          "KarmanFlow.step / ops.karman_step_large" % (who, Y, X))
 
 
-class SolTrainer:
+def _train_cfg(kc, msteps, net, std_v, std_re, in_std_v, out_std_v):
+    """TrainCfg with its normalisation fields.  --pretf (karman_train.py:351-355,416-421): separate input / output normalisation of a
+    pre-trained supervised model; 0.0 pairs stand for "as std_v"."""
+    i0, i1 = (float(in_std_v[0]), float(in_std_v[1])) if in_std_v is not None else (0.0, 0.0)
+    o0, o1 = (float(out_std_v[0]), float(out_std_v[1])) if out_std_v is not None else (0.0, 0.0)
+    return TrainCfg(kc, msteps, float(std_v[0]), float(std_v[1]), float(std_re), float(net.slope), i0, i1, o0, o1)
+
+
+class _AdamDP:
+    """The optimiser / data-parallel surface of the 2-D trainers: the flat gradient with its loss slot, TF-Adam state, the per-step
+    losses and the DPStep that composes fwd_bwd (the subclass's) with ONE all-reduce and apply_gradients.  A constructor calls
+    _init_adam where it allocated these buffers before, then allocates its own outputs, then calls _init_dp."""
+
+    def _init_adam(self, net, msteps, clip_grad, beta1, beta2, eps):
+        dev = net.params.device
+        n = net.n_params
+        # gradient + one slot for the loss: the data-parallel exchange is ONE all-reduce of this buffer (dist.DPStep)
+        self._flat = torch.zeros(n + 1, dtype=torch.float32, device=dev)
+        self.grads = self._flat[:n]
+        self.m = torch.zeros(n, dtype=torch.float32, device=dev)
+        self.v = torch.zeros(n, dtype=torch.float32, device=dev)
+        self.loss_steps = torch.zeros(msteps, dtype=torch.float32, device=dev)
+        self.t = 0
+        self.clip_norm = 1e-3 if clip_grad else 0.0      # karman_train.py:453
+        self.beta1, self.beta2, self.eps = beta1, beta2, eps
+        self._offsets = (C.c_int64 * len(net.offsets))(*[int(o) for o in net.offsets])
+        self.final = None
+        self._want_final, self._eager = False, False
+
+    def _init_dp(self, group, comm):
+        self.scratch = torch.zeros(64, dtype=torch.float32, device=self._flat.device)
+        self._dp = DPStep(self._fwd_bwd_flat, self._apply_flat, group=group, comm=comm, flat=self._flat)
+
+    def apply_gradients(self, lr):
+        """tf.compat.v1.train.AdamOptimizer(lr) update (+ optional per-tensor clip_by_norm)."""
+        self.t += 1
+        n = self.net.n_params
+        check(self.lib.sol_adam_tf_step(stream(), ptr(self.net.params.detach()), ptr(self.grads), ptr(self.m), ptr(self.v),
+                                        n, self.t, float(lr), self.beta1, self.beta2, self.eps, float(self.clip_norm),
+                                        self._offsets, len(self.net.shapes), ptr(self.scratch)))
+
+    # ---- data-parallel composition --------------------------------------------------------
+    def _fwd_bwd_flat(self, *batch):
+        loss = self.fwd_bwd(*batch, want_final=self._want_final, eager=self._eager)
+        return loss, self.grads
+
+    def _apply_flat(self, grads, lr):
+        assert grads is self.grads
+        self.apply_gradients(lr)
+
+    def train_step(self, d0, vy0, vx0, re, gt_vy, gt_vx, lr, want_final=False, eager=False):
+        """One training step on this rank's shard; returns the GLOBAL loss tensor.  want_final=True also produces
+        the state after the last unrolled step in self.final = [density, vy, vx] (this is what makes the engine
+        advect the passive density at all: like the TF graph of the reference, nothing that no output needs is run)."""
+        self._want_final = want_final
+        self._eager = eager
+        return self._dp(d0, vy0, vx0, re, gt_vy, gt_vx, lr=lr)
+
+
+class SolTrainer(_AdamDP):
     def __init__(self, net, masks, B, Y, X, msteps, dx, std_v, std_re, dt=1.0, res=None,
                  clip_grad=False, beta1=0.9, beta2=0.999, eps=1e-8, group=None, use_graph=True,
                  cg_rtol=1e-6, cg_atol=1e-9, cg_max_iter=2000, grad_pad="replicate", inflow_order="after",
@@ -86,38 +145,21 @@ class SolTrainer:
         self.B, self.Y, self.X, self.msteps = B, Y, X, msteps
         kc = ops.karman_cfg(B, Y, X, dx, dt=dt, res=res, cg_rtol=cg_rtol, cg_atol=cg_atol,
                             cg_max_iter=cg_max_iter, grad_pad=grad_pad, inflow_order=inflow_order, masks=masks)
-        # --pretf (karman_train.py:351-355,416-421): separate input / output normalisation of a pre-trained supervised model
-        i0, i1 = (float(in_std_v[0]), float(in_std_v[1])) if in_std_v is not None else (0.0, 0.0)
-        o0, o1 = (float(out_std_v[0]), float(out_std_v[1])) if out_std_v is not None else (0.0, 0.0)
-        self.cfg = TrainCfg(kc, msteps, float(std_v[0]), float(std_v[1]), float(std_re), float(net.slope), i0, i1, o0, o1)
+        self.cfg = _train_cfg(kc, msteps, net, std_v, std_re, in_std_v, out_std_v)
         dev = net.params.device
         self.device = dev
         nbytes = self.lib.sol_train_workspace_bytes(C.byref(self.cfg))
         self.workspace = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=dev)
         self.workspace_bytes = nbytes
-        n = net.n_params
-        # gradient + one slot for the loss: the data-parallel exchange is ONE all-reduce of this buffer (dist.DPStep)
-        self._flat = torch.zeros(n + 1, dtype=torch.float32, device=dev)
-        self.grads = self._flat[:n]
-        self.m = torch.zeros(n, dtype=torch.float32, device=dev)
-        self.v = torch.zeros(n, dtype=torch.float32, device=dev)
-        self.loss_steps = torch.zeros(msteps, dtype=torch.float32, device=dev)
+        self._init_adam(net, msteps, clip_grad, beta1, beta2, eps)
         self.iters_fwd = torch.zeros(msteps * B, dtype=torch.int32, device=dev)
         self.iters_bwd = torch.zeros(msteps * B, dtype=torch.int32, device=dev)
-        self.scratch = torch.zeros(64, dtype=torch.float32, device=dev)
-        self.t = 0
-        self.clip_norm = 1e-3 if clip_grad else 0.0      # karman_train.py:453
-        self.beta1, self.beta2, self.eps = beta1, beta2, eps
-        self._offsets = (C.c_int64 * len(net.offsets))(*[int(o) for o in net.offsets])
-        self.final = None
         self.use_graph = use_graph
         self._graphs = {}           # want_final -> (key, handle): replayable hipGraphs of the whole fwd+bwd
         self._captures = 0          # re-captures caused by MOVED input buffers so far
         self._stage = None          # internal input buffers, used once the caller's buffers turn out not to be persistent
         self._fin = None
-        self._want_final = False
-        self._eager = False
-        self._dp = DPStep(self._fwd_bwd_flat, self._apply_flat, group=group, comm=comm, flat=self._flat)
+        self._init_dp(group, comm)
 
     def __del__(self):
         try:
@@ -183,31 +225,6 @@ class SolTrainer:
         self.final = fin if want_final else None
         return self.loss_steps.sum() / ms
 
-    def apply_gradients(self, lr):
-        """tf.compat.v1.train.AdamOptimizer(lr) update (+ optional per-tensor clip_by_norm)."""
-        self.t += 1
-        n = self.net.n_params
-        check(self.lib.sol_adam_tf_step(stream(), ptr(self.net.params.detach()), ptr(self.grads), ptr(self.m), ptr(self.v),
-                                        n, self.t, float(lr), self.beta1, self.beta2, self.eps, float(self.clip_norm),
-                                        self._offsets, len(self.net.shapes), ptr(self.scratch)))
-
-    # ---- data-parallel composition --------------------------------------------------------
-    def _fwd_bwd_flat(self, *batch):
-        loss = self.fwd_bwd(*batch, want_final=self._want_final, eager=self._eager)
-        return loss, self.grads
-
-    def _apply_flat(self, grads, lr):
-        assert grads is self.grads
-        self.apply_gradients(lr)
-
-    def train_step(self, d0, vy0, vx0, re, gt_vy, gt_vx, lr, want_final=False, eager=False):
-        """One training step on this rank's shard; returns the GLOBAL loss tensor.  want_final=True also produces
-        the state after the last unrolled step in self.final = [density, vy, vx] (this is what makes the engine
-        advect the passive density at all: like the TF graph of the reference, nothing that no output needs is run)."""
-        self._want_final = want_final
-        self._eager = eager
-        return self._dp(d0, vy0, vx0, re, gt_vy, gt_vx, lr=lr)
-
     # ---- algorithmic traffic of the solver part (SURVEY.md section 8d) ---------------------
     def solver_algorithmic_bytes(self):
         """4*(10*Nf + 9*N + 11*N*k) per forward sample-step and 4*(2*(10*Nf+9*N) + 11*N*k_bwd)
@@ -233,9 +250,7 @@ class SolRollout:
         self.conv_precision = _conv_precision_code(conv_precision)
         self.net, self.masks, self.B = net, masks, B
         kc = ops.karman_cfg(B, Y, X, dx, dt=dt, res=res, masks=masks, **solver)
-        i0, i1 = (float(in_std_v[0]), float(in_std_v[1])) if in_std_v is not None else (0.0, 0.0)
-        o0, o1 = (float(out_std_v[0]), float(out_std_v[1])) if out_std_v is not None else (0.0, 0.0)
-        self.cfg = TrainCfg(kc, 1, float(std_v[0]), float(std_v[1]), float(std_re), float(net.slope), i0, i1, o0, o1)
+        self.cfg = _train_cfg(kc, 1, net, std_v, std_re, in_std_v, out_std_v)
         nbytes = self.lib.sol_rollout_workspace_bytes(C.byref(self.cfg))
         self.workspace = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=net.params.device)
         self.workspace_bytes = nbytes
@@ -251,7 +266,7 @@ class SolRollout:
         return iters.reshape(nsteps, self.B)
 
 
-class GraphTrainer:
+class GraphTrainer(_AdamDP):
     """The SolTrainer call surface for networks the C++ trainer has no fused schedule for (`model_mercury`,
     karman_train.py:92-99 / `eval('model_'+...)` at :394).  The unrolled step of karman_train.py:397-457 runs as a HAND-WRITTEN
     schedule over the C ABI (`schedule="manual"`, default since round 6: _unrolled_schedule -- forward unroll keeping what the
@@ -260,7 +275,8 @@ class GraphTrainer:
     (`schedule="autograd"`, rounds 2-5); either way captured once into a hipGraph over static buffers: a step copies the batch in
     and replays.  Same outputs as SolTrainer: the loss, `grads` (flat, Keras get_weights() order), `loss_steps`, `final` =
     [density, vy, vx] after the last step; TF-Adam with optional per-tensor clip; data parallel through the same DPStep (one SUM
-    all-reduce of `grads`)."""
+    all-reduce of `grads`): the _AdamDP surface both classes derive from.  _unrolled_schedule is the only copy of the 2-D unrolled
+    step; what depends on the solver sits in _schedule_setup / _solver_fwd / _solver_bwd, which LargeGridTrainer overrides."""
 
     def __init__(self, net, B, Y, X, msteps, std_v, std_re, res=None, clip_grad=False, beta1=0.9, beta2=0.999, eps=1e-8,
                  group=None, use_graph=True, comm=None, in_std_v=None, out_std_v=None, pressure_solver=None,
@@ -275,6 +291,7 @@ class GraphTrainer:
             raise ValueError("schedule must be 'manual' or 'autograd'")
         self.schedule = schedule
         self._sched = None
+        self._cg_fwd, self._cg_bwd = [], []       # what the solver launches of a step report (LargeGridTrainer, CG scenes)
         self._check_grid(Y, X)
         from . import fluid, karman
         _lib.require_gpu()
@@ -299,30 +316,18 @@ class GraphTrainer:
             self.bcm = masks.velBCyMask.reshape(-1, Y + 1, X, 1).cpu().numpy()
         else:
             self.bcv, self.bcm = karman.velocity_bc_masks(Y, X, batch_size=B)
-        t = lambda v: torch.tensor([float(a) for a in v], dtype=torch.float32, device=dev)
-        self.scale_loss = t(std_v)
-        self._std_loss_host = (float(std_v[0]), float(std_v[1]))
-        self.scale_in = t(list(in_std_v if in_std_v is not None else std_v) + [std_re])
-        self.scale_out = t(out_std_v if out_std_v is not None else std_v)
         # (host copies: a .tolist() of a device tensor is a synchronising copy -- illegal inside a capture)
+        self._std_loss_host = (float(std_v[0]), float(std_v[1]))
         self._scale_in_host = tuple(float(a) for a in (list(in_std_v if in_std_v is not None else std_v) + [std_re]))
         self._scale_out_host = tuple(float(a) for a in (out_std_v if out_std_v is not None else std_v))
+        t = lambda v: torch.tensor(v, dtype=torch.float32, device=dev)
+        self.scale_loss, self.scale_in, self.scale_out = t(self._std_loss_host), t(self._scale_in_host), t(self._scale_out_host)
         f32 = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)
         self._in = [f32(B, Y, X), f32(B, Y + 1, X), f32(B, Y, X + 1), f32(B), f32(msteps, B, Y + 1, X), f32(msteps, B, Y, X + 1)]
-        n = net.n_params
-        self._flat = f32(n + 1)                   # gradient + loss slot: one all-reduce per step (dist.DPStep)
-        self.grads, self.m, self.v = self._flat[:n], f32(n), f32(n)
-        self.loss_steps = f32(msteps)
+        self._init_adam(net, msteps, clip_grad, beta1, beta2, eps)
         self._fin = [f32(B, Y, X), f32(B, Y + 1, X), f32(B, Y, X + 1)]
-        self.final = None
-        self.scratch = f32(64)
-        self.t = 0
-        self.clip_norm = 1e-3 if clip_grad else 0.0
-        self.beta1, self.beta2, self.eps = beta1, beta2, eps
-        self._offsets = (C.c_int64 * len(net.offsets))(*[int(o) for o in net.offsets])
         self.use_graph, self._graph = use_graph, None
-        self._want_final, self._eager = False, False
-        self._dp = DPStep(self._fwd_bwd_flat, self._apply_flat, group=group, comm=comm, flat=self._flat)
+        self._init_dp(group, comm)
 
     @staticmethod
     def _check_grid(Y, X):
@@ -336,31 +341,24 @@ class GraphTrainer:
 
     def _unrolled_schedule(self):
         """karman_train.py:397-457 differentiated by hand (the 2-D counterpart of karman3d.Karman3DTrainer._unrolled_schedule; train.hip does
-        the same in C++ for model_mars_moon).  Forward, per unrolled step i: sol_karman_step_fwd (saves the post-diffusion velocity, writes
-        the SCALED features itself) -> the network's forward launches (schedule2d.NetSchedule2D) -> velocity += out_std * to_staggered(out)
-        -> loss_i and d loss_i / d v_i in one pass (sol_l2_loss_fwd_bwd, gradient pre-scaled by 1 / msteps).  Reverse, i = n-1 .. 0:
-        G = d loss_i / d v_i + (adjoint of step i+1 w.r.t. its input) -> d out = out_std * G at the corrected faces -> the network's reverse
-        sweep (weight gradients accumulated over the steps in the layers' partial buffers) -> sol_karman_step_bwd, which adds the feature
-        gradient / in_std itself (dfeat).  One reduce per layer at the end."""
-        from .schedule2d import NetSchedule2D
+        the same in C++ for model_mars_moon).  The ONE copy of the 2-D unrolled step: LargeGridTrainer runs it too and overrides only
+        _schedule_setup / _solver_fwd / _solver_bwd.  Forward, per unrolled step i: the solver step (saves the post-diffusion velocity,
+        hands back the SCALED features) -> the network's forward launches (schedule2d.NetSchedule2D) -> velocity += out_std *
+        to_staggered(out) -> loss_i and d loss_i / d v_i in one pass (sol_l2_loss_fwd_bwd, gradient pre-scaled by 1 / msteps).  Reverse,
+        i = n-1 .. 0: G = d loss_i / d v_i + (adjoint of step i+1 w.r.t. its input) -> d out = out_std * G at the corrected faces -> the
+        network's reverse sweep (weight gradients accumulated over the steps in the layers' partial buffers) -> the solver adjoint, which
+        also takes in the feature gradient / in_std.  One reduce per layer at the end."""
         d, vy, vx, re, gt_vy, gt_vx = self._in
-        B, Y, X, ms = self.B, self.Y, self.X, self.msteps
-        dev = self.device
+        Y, X, ms = self.Y, self.X, self.msteps
         if self._sched is None:
-            self._sched = NetSchedule2D(self.net, B, Y, X)
-            self._mk = self.sim._masks(self.dom, self.bcv, self.bcm, dev)
-            self._kcfg = ops.karman_cfg(B, Y, X, self.dom.dx[1], dt=self.dt, res=self.res, masks=self._mk, **self.sim._solver)
-            self._fs = [1.0 / float(v) for v in self._scale_in_host]
-        sch, mk, cfg, lib = self._sched, self._mk, self._kcfg, self.lib
-        fs3 = (C.c_float * 3)(*self._fs)
+            self._schedule_setup()
+        sch = self._sched
         so, sl = self._scale_out_host, self._std_loss_host
+        self._cg_fwd, self._cg_bwd = [], []
         sch.begin_step()
         keep, losses = [], []
         for i in range(ms):
-            d2, vy2, vx2, svy, svx = torch.empty_like(d), torch.empty_like(vy), torch.empty_like(vx), torch.empty_like(vy), torch.empty_like(vx)
-            feat = torch.empty(B, Y, X, 4, dtype=torch.float32, device=dev)
-            check(lib.sol_karman_step_fwd(C.byref(cfg), stream(), ptr(d), ptr(vy), ptr(vx), ptr(re), ptr(mk.active), ptr(mk.inflow), ptr(mk.velBCy),
-                                          ptr(mk.velBCyMask), mk.bc_stride, ptr(d2), ptr(vy2), ptr(vx2), ptr(svy), ptr(svx), ptr(feat), fs3, None))
+            d2, vy2, vx2, svy, svx, feat = self._solver_fwd(d, vy, vx, re)
             out, state = sch.forward(feat)
             vy2[:, :Y].add_(out[..., 0], alpha=so[0])             # to_staggered + add (karman_train.py:88-90, 424-426): the last row / column gets no correction
             vx2[:, :, :X].add_(out[..., 1], alpha=so[1])
@@ -375,17 +373,49 @@ class GraphTrainer:
                 G[0].add_(gin[0])
                 G[1].add_(gin[1])
             dO = torch.stack([G[0][:, :Y] * so[0], G[1][:, :, :X] * so[1]], dim=-1)
-            dfeat = sch.backward(state, dO)[..., :2].contiguous()
-            oy, ox = torch.empty_like(svy), torch.empty_like(svx)
-            check(lib.sol_karman_step_bwd(C.byref(cfg), stream(), ptr(svy), ptr(svx), ptr(re), ptr(mk.active), ptr(mk.velBCyMask), mk.bc_stride,
-                                          ptr(G[0]), ptr(G[1]), ptr(dfeat), fs3, ptr(oy), ptr(ox), None))
-            gin = (oy, ox)
+            dfeat = sch.backward(state, dO)
             keep[i] = None
+            # nothing differentiates the start state: at i == 0 the result of the small-grid solver adjoint is UNREAD (the launch is kept
+            # as it always ran; LargeGridTrainer never issued it)
+            if i > 0 or self._adjoint_of_first_step:
+                gin = self._solver_bwd(svy, svx, re, G, dfeat)
         losses = _lib.stack0(losses)
         _lib.dcopy_(self.loss_steps, losses)
         _lib.dcopy_(self.grads, sch.end_step())
         for dst, src in zip(self._fin, (d, vy, vx)):
             _lib.dcopy_(dst, src)
+
+    _adjoint_of_first_step = True
+
+    def _schedule_setup(self):
+        """Once, on the first run of the schedule: the network's launches, the scene's device masks, the solver configuration"""
+        from .schedule2d import NetSchedule2D
+        B, Y, X = self.B, self.Y, self.X
+        self._sched = NetSchedule2D(self.net, B, Y, X)
+        self._mk = self.sim._masks(self.dom, self.bcv, self.bcm, self.device)
+        self._kcfg = ops.karman_cfg(B, Y, X, self.dom.dx[1], dt=self.dt, res=self.res, masks=self._mk, **self.sim._solver)
+        self._fs = [1.0 / float(v) for v in self._scale_in_host]
+        self._fs3 = (C.c_float * 3)(*self._fs)
+
+    def _solver_fwd(self, d, vy, vx, re):
+        """One solver step -> (d2, vy2, vx2, saved vy, saved vx, features / in_std [B,Y,X,4]): sol_karman_step_fwd writes the features itself"""
+        mk = self._mk
+        d2, vy2, vx2, svy, svx = torch.empty_like(d), torch.empty_like(vy), torch.empty_like(vx), torch.empty_like(vy), torch.empty_like(vx)
+        feat = torch.empty(self.B, self.Y, self.X, 4, dtype=torch.float32, device=self.device)
+        check(self.lib.sol_karman_step_fwd(C.byref(self._kcfg), stream(), ptr(d), ptr(vy), ptr(vx), ptr(re), ptr(mk.active), ptr(mk.inflow),
+                                           ptr(mk.velBCy), ptr(mk.velBCyMask), mk.bc_stride, ptr(d2), ptr(vy2), ptr(vx2), ptr(svy), ptr(svx),
+                                           ptr(feat), self._fs3, None))
+        return d2, vy2, vx2, svy, svx, feat
+
+    def _solver_bwd(self, svy, svx, re, G, dfeat):
+        """Adjoint of one solver step: cotangent G of its output velocity, dfeat of its features -> cotangent of its input velocity.
+        sol_karman_step_bwd adds dfeat / in_std itself."""
+        mk = self._mk
+        dfeat = dfeat[..., :2].contiguous()
+        oy, ox = torch.empty_like(svy), torch.empty_like(svx)
+        check(self.lib.sol_karman_step_bwd(C.byref(self._kcfg), stream(), ptr(svy), ptr(svx), ptr(re), ptr(mk.active), ptr(mk.velBCyMask),
+                                           mk.bc_stride, ptr(G[0]), ptr(G[1]), ptr(dfeat), self._fs3, ptr(oy), ptr(ox), None))
+        return oy, ox
 
     def _unrolled_autograd(self):
         from . import fluid, karman
@@ -437,21 +467,16 @@ class GraphTrainer:
         self.final = self._fin if want_final else None
         return self.loss_steps.sum() / self.msteps
 
-    apply_gradients = SolTrainer.apply_gradients
-    _fwd_bwd_flat = SolTrainer._fwd_bwd_flat
-    _apply_flat = SolTrainer._apply_flat
-    train_step = SolTrainer.train_step
-
 
 class LargeGridTrainer(GraphTrainer):
     """GraphTrainer's call surface (constructor keywords, fwd_bwd / train_step / apply_gradients, `grads`, `loss_steps`, `final`, data
-    parallel through DPStep, use_graph) for domains BEYOND the one-workgroup solver grids: more than 8192 cells or rows wider than 64
-    cells, X a multiple of 64 (the reference's 256 x 128 data-generation grid).  The hand-written schedule of
-    GraphTrainer._unrolled_schedule over the large-grid solver pair: per unrolled step sol_karman_step_fwd_large_saved (direct or CG
-    pressure solve, as SceneMasks decides for the scene and `pressure_solver`) -> scaled features -> NetSchedule2D.forward ->
-    correction -> ops.l2_loss_fwd_bwd; in reverse NetSchedule2D.backward (weight gradients of W = 64 * tiles rows: the wide form of
-    sol_conv5x5_bwd_weight) -> feature gradient / in_std added to the cotangent on the faces to_feature reads ->
-    sol_karman_step_bwd_large.  Networks: mars_moon and mercury.
+    parallel through DPStep, use_graph) for domains BEYOND the one-workgroup solver grids (ops.beyond_one_workgroup), X a multiple of
+    64 (the reference's 256 x 128 data-generation grid).  The schedule IS GraphTrainer._unrolled_schedule (forward
+    unroll, correction, ops.l2_loss_fwd_bwd, reverse sweep with NetSchedule2D.backward -- weight gradients of W = 64 * tiles rows: the
+    wide form of sol_conv5x5_bwd_weight --, epilogue); this class only supplies the large-grid solver pair: _solver_fwd =
+    ops.karman_step_large_saved (direct or CG pressure solve, as SceneMasks decides for the scene and `pressure_solver`) + the scaled
+    features assembled in torch, _solver_bwd = feature gradient / in_std added to the cotangent on the faces to_feature reads +
+    ops.karman_step_large_bwd, _schedule_setup = their workspaces.  Networks: mars_moon and mercury.
 
     use_graph=True captures the step once (kernel nodes only, sol_graph_check).  With a CG scene the iteration count of a solve is not
     known at capture time: a captured step issues the launches of the WHOLE `cg_max_iter` budget per solve (converged iterations fall
@@ -467,98 +492,56 @@ class LargeGridTrainer(GraphTrainer):
 
     @staticmethod
     def _check_grid(Y, X):
-        if Y * X <= 8192 and X <= 64:
+        if not ops.beyond_one_workgroup(Y, X):
             raise ValueError("LargeGridTrainer: a %dx%d domain is served by the one-workgroup trainers -- use SolTrainer (mars_moon) or "
                              "GraphTrainer (make_trainer picks)" % (Y, X))
         if X % 64 != 0:
             raise ValueError("LargeGridTrainer: the convolutions of a large domain take rows of X %% 64 == 0 cells (got %dx%d)" % (Y, X))
 
-    def _unrolled_schedule(self):
-        from .schedule2d import NetSchedule2D
-        d, vy, vx, re, gt_vy, gt_vx = self._in
-        B, Y, X, ms = self.B, self.Y, self.X, self.msteps
-        dev = self.device
-        lib = self.lib
-        if self._sched is None:
-            self._sched = NetSchedule2D(self.net, B, Y, X)
-            self._mk = mk = self.sim._masks(self.dom, self.bcv, self.bcm, dev)
-            self._kcfg = cfg = ops.karman_cfg(B, Y, X, self.dom.dx[1], dt=self.dt, res=self.res, masks=mk, **self.sim._solver)
-            self._fs = [1.0 / float(v) for v in self._scale_in_host]
-            ws = lambda n: torch.empty((int(n) + 3) // 4, dtype=torch.float32, device=dev)
-            self._ws_fwd = ws(ops.large_workspace_bytes(cfg, mk))
-            self._ws_bwd = ws(lib.sol_karman_step_bwd_large_workspace_bytes(C.byref(cfg)))
-            self._zplane = torch.zeros(B, Y, X, dtype=torch.float32, device=dev)      # the fourth (padding) input channel
-            self.pressure_solver_used = mk.pressure_solver
-        sch, mk, cfg, fs = self._sched, self._mk, self._kcfg, self._fs
-        so, sl = self._scale_out_host, self._std_loss_host
-        hdr, bhdr = ops._hdr(mk.direct_header), ops._hdr(mk.box_header)
-        sch.begin_step()
-        re_plane = (re * fs[2]).reshape(B, 1, 1).expand(B, Y, X)
-        keep, losses, it_f, it_b = [], [], [], []
-        for i in range(ms):
-            (d2, vy2, vx2), head = ops._large_fwd(d, vy, vx, re, cfg, mk)
-            svy, svx = torch.empty_like(vy), torch.empty_like(vx)
-            cg = ops._cg_info(mk, B, dev)
-            check(lib.sol_karman_step_fwd_large_saved(*head, ptr(svy), ptr(svx), hdr, ptr(mk.box), bhdr, ptr(cg), ptr(self._ws_fwd),
-                                                      self._ws_fwd.numel() * 4))
-            it_f.append(cg)
-            # to_feature / in_std (karman_train.py:77-86, 413-416), padded to the four channels the first layer's kernels read
-            feat = torch.stack([vy2[:, :Y] * fs[0], vx2[:, :, :X] * fs[1], re_plane, self._zplane], dim=-1)
-            out, state = sch.forward(feat)
-            vy2[:, :Y].add_(out[..., 0], alpha=so[0])             # to_staggered + add: the last row / column gets no correction
-            vx2[:, :, :X].add_(out[..., 1], alpha=so[1])
-            li, gi = ops.l2_loss_fwd_bwd((vy2, vx2), (gt_vy[i], gt_vx[i]), sl, gscale=1.0 / ms)
-            losses.append(li.reshape(()))
-            keep.append((svy, svx, state, gi))
-            d, vy, vx = d2, vy2, vx2
-        gin = None
-        for i in range(ms - 1, -1, -1):
-            svy, svx, state, G = keep[i]
-            if gin is not None:
-                G[0].add_(gin[0])
-                G[1].add_(gin[1])
-            dO = torch.stack([G[0][:, :Y] * so[0], G[1][:, :, :X] * so[1]], dim=-1)
-            dfeat = sch.backward(state, dO)
-            keep[i] = None
-            if i == 0:
-                break                                             # nothing differentiates the start state
-            G[0][:, :Y].add_(dfeat[..., 0], alpha=fs[0])
-            G[1][:, :, :X].add_(dfeat[..., 1], alpha=fs[1])
-            oy, ox = torch.empty_like(svy), torch.empty_like(svx)
-            cg = ops._cg_info(mk, B, dev)
-            check(lib.sol_karman_step_bwd_large(C.byref(cfg), stream(), ptr(svy), ptr(svx), ptr(re), ptr(mk.active), ptr(mk.velBCyMask),
-                                                mk.bc_stride, ptr(G[0]), ptr(G[1]), ptr(oy), ptr(ox), hdr, ptr(mk.box), bhdr, ptr(cg),
-                                                ptr(self._ws_bwd), self._ws_bwd.numel() * 4))
-            it_b.append(cg)
-            gin = (oy, ox)
-        losses = _lib.stack0(losses)
-        _lib.dcopy_(self.loss_steps, losses)
-        _lib.dcopy_(self.grads, sch.end_step())
-        for dst, src in zip(self._fin, (d, vy, vx)):
-            _lib.dcopy_(dst, src)
-        if it_f[0] is not None:
-            self._cg_steps = (it_f, it_b[::-1])
+    _adjoint_of_first_step = False
+
+    def _schedule_setup(self):
+        super()._schedule_setup()
+        cfg, mk, dev = self._kcfg, self._mk, self.device
+        ws = lambda n: torch.empty((int(n) + 3) // 4, dtype=torch.float32, device=dev)
+        self._ws_fwd = ws(ops.large_workspace_bytes(cfg, mk))
+        self._ws_bwd = ws(self.lib.sol_karman_step_bwd_large_workspace_bytes(C.byref(cfg)))
+        self._zplane = torch.zeros(self.B, self.Y, self.X, dtype=torch.float32, device=dev)      # the fourth (padding) input channel
+        self.pressure_solver_used = mk.pressure_solver
+
+    def _solver_fwd(self, d, vy, vx, re):
+        B, Y, X, fs = self.B, self.Y, self.X, self._fs
+        if not self._cg_fwd:                                  # first unrolled step of this run: one Reynolds-number plane serves them all
+            self._re_plane = (re * fs[2]).reshape(B, 1, 1).expand(B, Y, X)
+        info = {}
+        (d2, vy2, vx2), svy, svx = ops.karman_step_large_saved(d, vy, vx, re, self._kcfg, self._mk, self._ws_fwd, info)
+        self._cg_fwd.append(info)
+        # to_feature / in_std (karman_train.py:77-86, 413-416), padded to the four channels the first layer's kernels read
+        feat = torch.stack([vy2[:, :Y] * fs[0], vx2[:, :, :X] * fs[1], self._re_plane, self._zplane], dim=-1)
+        return d2, vy2, vx2, svy, svx, feat
+
+    def _solver_bwd(self, svy, svx, re, G, dfeat):
+        Y, X, fs = self.Y, self.X, self._fs
+        G[0][:, :Y].add_(dfeat[..., 0], alpha=fs[0])          # feature gradient / in_std on the faces to_feature reads
+        G[1][:, :, :X].add_(dfeat[..., 1], alpha=fs[1])
+        info = {}
+        self._cg_bwd.append(info)
+        return ops.karman_step_large_bwd(svy, svx, re, G[0], G[1], self._kcfg, self._mk, workspace=self._ws_bwd, info=info)
 
     def _fwd_bwd(self, *a, **kw):
         loss = super()._fwd_bwd(*a, **kw)
-        cgs = getattr(self, "_cg_steps", None)
-        if cgs is not None:                         # (the [2, B] buffers of a captured step are the graph's own: refilled by every replay)
-            f, b = cgs
-            self.solve_info = {"iterations": torch.stack([t[0] for t in f]), "converged": torch.stack([t[1] for t in f])}
+        if self.pressure_solver_used == "cg":       # (the [2, B] buffers of a captured step are the graph's own: refilled by every replay)
+            f, b = self._cg_fwd, self._cg_bwd[::-1]
+            self.solve_info = {k: torch.stack([t[k] for t in f]) for k in ("iterations", "converged")}
             if b:
-                self.solve_info["iterations_bwd"] = torch.stack([t[0] for t in b])
-                self.solve_info["converged_bwd"] = torch.stack([t[1] for t in b])
+                self.solve_info.update({k: torch.stack([t[k] for t in b]) for k in ("iterations_bwd", "converged_bwd")})
         return loss
-
-
-def _beyond_one_workgroup(Y, X):
-    return Y * X > 8192 or X > 64
 
 
 def make_trainer(net, masks, B, Y, X, msteps, dx, std_v, std_re, **kw):
     """SolTrainer (the C++ schedule: model_mars_moon), GraphTrainer (every other network) or, for a domain beyond the one-workgroup
     solver grids, LargeGridTrainer (either network)."""
-    if _beyond_one_workgroup(Y, X):
+    if ops.beyond_one_workgroup(Y, X):
         return LargeGridTrainer(net, B, Y, X, msteps, std_v, std_re, dx=dx, masks=masks, **kw)
     if net.name == "mars_moon":
         # the C++ schedule takes its scene and its pressure solver from `masks` alone (obstacles / active / pressure_solver
