@@ -170,6 +170,27 @@ int sol_karman_step_fwd_large_cg(const sol_karman_cfg* cfg, void* stream,
                                  float* feat_out, const float* feat_scale,
                                  const float* box_blob, const int32_t* box_header_host, int32_t* cg_info,
                                  void* workspace, size_t workspace_bytes);
+/* sol_karman_step_fwd_large_cg with a WARM-STARTED solve: `p_inout` [B,Y,X] DEVICE is read as the initial guess x0 and overwritten with
+ * the step's pressure -- a roll-out hands the same buffer to consecutive steps (same matrix, a right-hand side that has barely moved).
+ * The solve starts from x = x0, r = b - M x0 and runs as the cold one: same test |r|_2 <= max(cfg.cg_rtol |b|_2, cfg.cg_atol) against
+ * |b| (a guess that already meets it reports 0 iterations, converged), same fixed-order fp64 sums, bit-reproducible; an all-zero guess
+ * gives the cold call's bits.  A simulation whose guess holds a NaN or an Inf starts from x0 = 0.  Same workspace as the cold call
+ * (sol_karman_step_large_cg_workspace_bytes); p_inout must not lie inside it. */
+int sol_karman_step_fwd_large_cg_warm(const sol_karman_cfg* cfg, void* stream,
+                                      const float* d_in, const float* vy_in, const float* vx_in,
+                                      const float* re, const float* active, const float* inflow,
+                                      const float* velBCy, const float* velBCyMask, int64_t bc_batch_stride,
+                                      float* d_out, float* vy_out, float* vx_out,
+                                      float* feat_out, const float* feat_scale,
+                                      const float* box_blob, const int32_t* box_header_host, int32_t* cg_info,
+                                      float* p_inout, void* workspace, size_t workspace_bytes);
+/* The corrector's output applied to a staggered velocity (to_staggered + add, karman_train.py:88-90, 424-426), one launch for both
+ * components, any Y, X >= 1:  vy[b,j,i] += s0 * out[b,j,i,0] (j < Y),  vx[b,j,i] += s1 * out[b,j,i,1] (i < X), each fl(v + fl(s * o));
+ * the last row of vy [B,Y+1,X] and the last column of vx [B,Y,X+1] are not touched.  out [B,Y,X,2] (8-byte aligned).  cor_y [B,Y+1,X] /
+ * cor_x [B,Y,X+1] (both NULL, or both given): receive the applied correction, zero on that row and column (the corTf frame of
+ * karman_apply.py:138-158). */
+int sol_karman_correct(void* stream, const float* out, float* vy, float* vx, float* cor_y, float* cor_x,
+                       int32_t B, int32_t Y, int32_t X, float s0, float s1);
 /* The CG step's pressure solve alone: M p = rhs with M = -A for the scene's `active` mask [Y,X] (precond.scene_matrix); rhs, p
  * [B,Y,X] (rhs is read only); other arguments as sol_karman_step_fwd_large_cg. */
 int sol_karman_pressure_solve_large(const sol_karman_cfg* cfg, void* stream, const float* active, const float* rhs, float* p,

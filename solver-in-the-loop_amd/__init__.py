@@ -11,7 +11,8 @@ from .fluid import (box, Box, Sphere, Inflow, Obstacle, Gravity, Domain, OPEN, P
 from . import ops, dist  # noqa: F401
 from .karman import KarmanFlow, to_feature, to_staggered, lr_schedule, velocity_bc_masks, parse_obstacles  # noqa: F401
 from .model import model_mars_moon, model_mercury, MarsMoon, Mercury, ConvNet  # noqa: F401
-from .trainer import SolTrainer, SolRollout, GraphTrainer, LargeGridTrainer, make_trainer  # noqa: F401
+from .trainer import (SolTrainer, SolRollout, GraphTrainer, LargeGridTrainer, LargeGridRollout, make_trainer,  # noqa: F401
+                      make_rollout)
 from . import synthetic, scene, burgers  # noqa: F401
 from .burgers import BurgersTest, BurgersTrainer, BurgersRollout, TFAdam  # noqa: F401
 from . import karman3d, precond3d  # noqa: F401

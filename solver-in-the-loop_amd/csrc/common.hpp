@@ -52,7 +52,8 @@ int sol_large_box_back(hipStream_t s, int B, int Y, int X, const float* blob, co
 // the step's pressure solve M x = b for either solver (pcg.hip; shared by the forward entry points and the adjoint, karman_large_bwd.hip):
 // direct = the capacitance solve on cfg.direct (hdr: host copy of its header, sol_large_direct_check), else the preconditioned CG with the
 // empty-box solve of box_blob, reporting to cg_info [2][B] (sol_large_cg_check).  ws: sol_large_solver_bytes(c, direct) bytes; the caller
-// writes b to sol_large_solver_rhs(c, direct, ws) (overwritten); *x = the buffer inside ws that holds the solution.
+// writes b to sol_large_solver_rhs(c, direct, ws) (overwritten); *x = the buffer inside ws that holds the solution.  x0 (CG only): NULL, or
+// the initial guess [B][Y][X] of a warm-started solve (a simulation whose guess is not finite starts from zero).
 size_t sol_large_direct_floats(const sol_karman_cfg* c);
 int sol_large_direct_check(const sol_karman_cfg* c, const char* who, const int32_t* hdr);
 int sol_large_direct_solve(hipStream_t s, const sol_karman_cfg* c, const int32_t* hdr, float* base);
@@ -60,9 +61,9 @@ int sol_large_cg_check(const sol_karman_cfg* c, const char* who, const float* bo
 size_t sol_large_solver_bytes(const sol_karman_cfg* c, bool direct);
 float* sol_large_solver_rhs(const sol_karman_cfg* c, bool direct, void* ws);
 int pressure_solve_any2d(hipStream_t s, const sol_karman_cfg* c, bool direct, const int32_t* hdr, const float* box_blob, const float* active,
-                         int32_t* cg_info, void* ws, float** x);
+                         int32_t* cg_info, void* ws, float** x, const float* x0 = nullptr);
 int sol_large_step(const sol_karman_cfg* c, hipStream_t s, const SolLargeStep& io, float* svy, float* svx, bool direct, const int32_t* hdr,
-                   const float* box_blob, int32_t* cg_info, void* solver_ws);
+                   const float* box_blob, int32_t* cg_info, void* solver_ws, const float* x0 = nullptr);
 
 // karman-3d pressure solvers (karman3d.hip / pcg.hip): dst = G src with G = the empty-box solve on the blob of cfg->direct
 // (*res = t1 or t2, whichever holds dst; skip = per-simulation done words [B] or NULL); the preconditioned CG solve M x = b (b is

@@ -11,6 +11,8 @@
 //                 the capacitance correction of the obstacle (precond.direct_solver_blob, window 16/32/64): eight small
 //                 fp32 GEMMs (k_l_gemm) + gather / K' / scatter kernels
 //   k_l_project   v -= mask * grad p  (+ fused to_feature)
+// and, for a roll-out with the trained corrector (trainer.LargeGridRollout), the correction launch after the network:
+//   k_l_correct   v_y, v_x += out_std * to_staggered(network output)  (+ the applied correction as a field of its own)
 // The adjoint of this path lives in karman_large_bwd.hip; it reads the post-diffusion velocity (sv_y, sv_x) that
 // sol_karman_step_fwd_large_saved hands out and runs the same pressure solve (pressure_solve_any2d, pcg.hip).
 #include "large2d.hpp"
@@ -151,6 +153,35 @@ __global__ void k_l_project(LArgs a) {
                 float* f = a.feat + ((size_t)b * N + j * X + i) * 4;
                 f[1] = v * a.fs1; f[2] = a.re[b] * a.fs2; f[3] = 0.f;
             }
+        }
+    }
+}
+
+// velocity += s * to_staggered(out) (karman_train.py:88-90, 424-426), both components in one launch: a thread takes one pixel, reads its
+// two channels as one 8-byte load and adds them to the pixel's low y face and low x face -- consecutive lanes store consecutive
+// addresses in both components; the high row of v_y and the high column of v_x have no pixel and stay as they are.  cor_y / cor_x
+// (both or neither): the applied correction [B,Y+1,X] / [B,Y,X+1], zero on that row and column.  The result is fl(v + fl(s * o)).
+__global__ void __launch_bounds__(256) k_l_correct(const float2* __restrict__ out, float* __restrict__ vy, float* __restrict__ vx,
+                                                   float* __restrict__ cor_y, float* __restrict__ cor_x, size_t n, int Y, int X, float s0, float s1) {
+    const size_t N = (size_t)Y * X;
+    for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (size_t)gridDim.x * 256) {
+        const float2 o = out[e];
+        const size_t b = e / N;
+        const int c = (int)(e - b * N), j = c / X, i = c - j * X;
+        const size_t ky = b * (N + X) + c, kx = b * (N + Y) + (size_t)j * (X + 1) + i;
+        float cy, cx, ny, nx;
+        {
+#pragma clang fp contract(off)
+            cy = s0 * o.x; cx = s1 * o.y;
+            ny = vy[ky] + cy; nx = vx[kx] + cx;
+        }
+        vy[ky] = ny;
+        vx[kx] = nx;
+        if (cor_y) {
+            cor_y[ky] = cy;
+            cor_x[kx] = cx;
+            if (j == Y - 1) cor_y[ky + X] = 0.f;
+            if (i == X - 1) cor_x[kx + 1] = 0.f;
         }
     }
 }
@@ -401,4 +432,16 @@ extern "C" int sol_karman_step_fwd_large(const sol_karman_cfg* c, void* stream,
     float* svx = w; w += B * Y * (X + 1);
     const SolLargeStep io{d_in, vy_in, vx_in, re, active, inflow, velBCy, velBCyMask, bc_batch_stride, d_out, vy_out, vx_out, feat_out, feat_scale};
     return sol_large_step(c, (hipStream_t)stream, io, svy, svx, true, direct_header_host, nullptr, nullptr, w);
+}
+
+extern "C" int sol_karman_correct(void* stream, const float* out, float* vy, float* vx, float* cor_y, float* cor_x,
+                                  int32_t B, int32_t Y, int32_t X, float s0, float s1) {
+    SOL_REQUIRE(out && vy && vx, "sol_karman_correct: NULL pointer argument");
+    SOL_REQUIRE((cor_y != nullptr) == (cor_x != nullptr), "sol_karman_correct: cor_y and cor_x go together (both or neither NULL)");
+    SOL_REQUIRE(B >= 1 && Y >= 1 && X >= 1, "sol_karman_correct: B, Y, X >= 1 (got %d, %d, %d)", B, Y, X);
+    const size_t n = (size_t)B * Y * X, nb = (n + 255) / 256;
+    SOL_LAUNCH(k_l_correct, dim3((unsigned)(nb < 4096 ? nb : 4096)), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const float2*>(out), vy, vx,
+               cor_y, cor_x, n, Y, X, s0, s1);
+    SOL_LAUNCH_CHECK();
+    return SOL_OK;
 }

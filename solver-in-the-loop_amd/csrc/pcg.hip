@@ -9,6 +9,9 @@
 //
 // Launch structure (pcg_run):
 //   pcg_init                      x = 0, r = b (in place), per-workgroup partials of |b|^2, done = 0, ndone = 0
+//     (with an initial guess x0:  pcg_guess_scan, pcg_init_warm -- x = x0, r = b - M x0, partials of |b|^2 and |r|^2; a simulation
+//      whose guess holds a NaN or an Inf starts from x = 0 instead.  The test below stays against |b|: a guess that already meets it
+//      reports 0 iterations)
 //   G, pcg_dot                    z = G r, convergence test, partials of <r, z>
 //   cg_max_iter x [ pcg_stencil   p = z + beta p (into the other p buffer), q = M p, partials of <p, q>
 //                   pcg_update    alpha = <r, z> / <p, q>, x += alpha p, r -= alpha q, partials of |r|^2
@@ -115,6 +118,56 @@ __global__ void __launch_bounds__(PCG_T) pcg_init(PcgArgs a) {
     }
 }
 
+// ---- warm start: the caller's guess x0 [B][N] ----
+// per-workgroup counts of the non-finite values of x0 into the <p, q> slab (free until the first pcg_stencil): pcg_init_warm sums a
+// simulation's row and drops a guess that holds a NaN or an Inf
+__global__ void __launch_bounds__(PCG_T) pcg_guess_scan(PcgArgs a, const float* __restrict__ x0) {
+    const size_t o = (size_t)blockIdx.y * a.N;
+    double bad = 0.0;
+    for (int c = blockIdx.x * PCG_T + threadIdx.x; c < a.N; c += a.nwg * PCG_T) bad += fabsf(x0[o + c]) < INFINITY ? 0.0 : 1.0;
+    pcg_publish(a.pq, a.nwg, bad);
+}
+
+// x = x0, r = b - M x0 with (M x)_c = fma(max(n, 1), x_c, -(active_c s)), n and s summed over the neighbours in pcg_stencil's order (the
+// masks are 0 / 1, so the products inside s are exact); a simulation with a non-finite guess gets pcg_init's x = 0, r = b, and an
+// all-zero guess gives the same bits.  Partials of |b|^2 and |r|^2, done = 0, ndone = 0
+template <class Grid>
+__global__ void __launch_bounds__(PCG_T) pcg_init_warm(PcgArgs a, Grid g, const float* __restrict__ x0) {
+    const int b = blockIdx.y;
+    const size_t o = (size_t)b * a.N;
+    const bool use = pcg_slab_sum(a.pq + (size_t)b * a.nwg, a.nwg) == 0.0;
+    const float* xb = x0 + o;
+    double accb = 0.0, accr = 0.0;
+    for (int c = blockIdx.x * PCG_T + threadIdx.x; c < a.N; c += a.nwg * PCG_T) {
+        const float v = a.r[o + c];
+        float pc = 0.f, r = v;
+        if (use) {
+            const typename Grid::Cell at = g.cell(c);
+            const float ac = a.active[c] != 0.f ? 1.f : 0.f;
+            pc = xb[c];
+            float n = 0.f, s = 0.f;
+            g.neighbours(at, c, [&](bool inside, int e) {
+                float an = ac, pv = 0.f;            // outside the box: accessible iff the cell is, p = 0 there (as pcg_stencil)
+                if (inside) { an = a.active[e] != 0.f ? 1.f : 0.f; pv = an * xb[e]; }
+                n += an; s += pv;
+            });
+            const float qv = fmaf(fmaxf(n, 1.f), pc, -(ac * s));
+            r = v - qv;
+        }
+        a.x[o + c] = pc;
+        a.r[o + c] = r;
+        accb += (double)v * v;
+        accr += (double)r * r;
+    }
+    const double tb = pcg_block_sum(accb), tr = pcg_block_sum(accr);
+    if (threadIdx.x == 0) {
+        a.bb[(size_t)b * a.nwg + blockIdx.x] = tb;
+        a.rr[(size_t)b * a.nwg + blockIdx.x] = tr;
+        if (blockIdx.x == 0) a.done[b] = 0;
+        if (blockIdx.x == 0 && b == 0) *a.ndone = 0;
+    }
+}
+
 // p_new = z + beta p_old (beta = rz_cur / rz_prev; first: p_new = z), q = M p_new, partials of <p_new, q>
 template <class Grid>
 __global__ void __launch_bounds__(PCG_T) pcg_stencil(PcgArgs a, Grid g, const float* __restrict__ z, const float* __restrict__ pold,
@@ -214,9 +267,10 @@ PcgArgs pcg_carve(Carve& w, size_t B, size_t N) {
     return a;
 }
 
-// M x = b by PCG (b = a.r is overwritten with the residual, x = a.x); apply_G(&z) applies G to a.r and points z at the result
+// M x = b by PCG (b = a.r is overwritten with the residual, x = a.x); apply_G(&z) applies G to a.r and points z at the result.
+// x0: NULL (start from x = 0), or the initial guess [B][N] (read by the first two launches only; not a.x)
 template <class Grid, class ApplyG>
-int pcg_run(hipStream_t s, const PcgArgs& a, Grid g, int K, int poll_every, ApplyG&& apply_G) {
+int pcg_run(hipStream_t s, const PcgArgs& a, Grid g, int K, int poll_every, ApplyG&& apply_G, const float* x0 = nullptr) {
     bool poll = false;
     if (poll_every > 0) {
         hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
@@ -225,7 +279,12 @@ int pcg_run(hipStream_t s, const PcgArgs& a, Grid g, int K, int poll_every, Appl
     }
     const dim3 grid(a.nwg, a.B), blk(PCG_T);
     float* z = nullptr;
-    SOL_LAUNCH(pcg_init, grid, blk, 0, s, a);
+    if (x0) {
+        SOL_LAUNCH(pcg_guess_scan, grid, blk, 0, s, a, x0);
+        SOL_LAUNCH(pcg_init_warm<Grid>, grid, blk, 0, s, a, g, x0);
+    } else {
+        SOL_LAUNCH(pcg_init, grid, blk, 0, s, a);
+    }
     if (int e = apply_G(&z)) return e;
     SOL_LAUNCH(pcg_dot, grid, blk, 0, s, a, (const float*)z, a.rz[0], 0);
     for (int k = 1; k <= K; ++k) {
@@ -323,7 +382,8 @@ int large_check(const sol_karman_cfg* c, const char* who, const float* box_blob,
 }
 
 // M x = b by PCG; b (= l.a.r) is overwritten with the residual
-int large_solve(hipStream_t s, const sol_karman_cfg* c, const float* blob, const float* active, const Large& l, int32_t* info) {
+int large_solve(hipStream_t s, const sol_karman_cfg* c, const float* blob, const float* active, const Large& l, int32_t* info,
+                const float* x0 = nullptr) {
     const int B = c->B, Y = c->Y, X = c->X;
     PcgArgs a = l.a;
     a.active = active;
@@ -333,7 +393,7 @@ int large_solve(hipStream_t s, const sol_karman_cfg* c, const float* blob, const
         if (int e = sol_large_box_forward(s, B, Y, X, blob, a.r, l.T1, l.T2, a.done)) return e;
         return sol_large_box_back(s, B, Y, X, blob, l.T2, l.T1, l.z, a.done);
     };
-    return pcg_run(s, a, Grid2{Y, X}, c->cg_max_iter, 16, apply_G);
+    return pcg_run(s, a, Grid2{Y, X}, c->cg_max_iter, 16, apply_G, x0);
 }
 
 __global__ void __launch_bounds__(PCG_T) large_copy(float* __restrict__ dst, const float* __restrict__ src, size_t n) {
@@ -354,22 +414,22 @@ float* sol_large_solver_rhs(const sol_karman_cfg* c, bool direct, void* ws) {
 }
 
 int pressure_solve_any2d(hipStream_t s, const sol_karman_cfg* c, bool direct, const int32_t* hdr, const float* box_blob, const float* active,
-                         int32_t* cg_info, void* ws, float** x) {
+                         int32_t* cg_info, void* ws, float** x, const float* x0) {
     if (direct) {
         *x = static_cast<float*>(ws);
         return sol_large_direct_solve(s, c, hdr, *x);
     }
     const Large l = large_layout(c, ws, false);
     *x = l.a.x;
-    return large_solve(s, c, box_blob, active, l, cg_info);
+    return large_solve(s, c, box_blob, active, l, cg_info, x0);
 }
 
 // diffuse / advect / rhs, the solve, the projection: the whole forward step (sv_y, sv_x: where the post-diffusion velocity goes)
 int sol_large_step(const sol_karman_cfg* c, hipStream_t s, const SolLargeStep& io, float* svy, float* svx, bool direct, const int32_t* hdr,
-                   const float* box_blob, int32_t* cg_info, void* solver_ws) {
+                   const float* box_blob, int32_t* cg_info, void* solver_ws, const float* x0) {
     if (int e = sol_large_front(c, s, io, svy, svx, sol_large_solver_rhs(c, direct, solver_ws))) return e;
     float* p = nullptr;
-    if (int e = pressure_solve_any2d(s, c, direct, hdr, box_blob, io.active, cg_info, solver_ws, &p)) return e;
+    if (int e = pressure_solve_any2d(s, c, direct, hdr, box_blob, io.active, cg_info, solver_ws, &p, x0)) return e;
     return sol_large_project(c, s, io, p);
 }
 
@@ -406,6 +466,34 @@ extern "C" size_t sol_karman_step_large_cg_workspace_bytes(const sol_karman_cfg*
     return large_layout(c, nullptr).bytes;
 }
 
+namespace {
+
+// sol_karman_step_fwd_large_cg and its warm-started form (p_inout: NULL, or the guess in / the step's pressure out)
+int large_cg_step(const char* who, const sol_karman_cfg* c, void* stream, const SolLargeStep& io, const float* box_blob,
+                  const int32_t* box_header_host, int32_t* cg_info, float* p_inout, void* workspace, size_t workspace_bytes) {
+    if (int e = large_check(c, who, box_blob, box_header_host, cg_info, workspace, workspace_bytes)) return e;
+    SOL_REQUIRE(io.vy_in && io.vx_in && io.re && io.active && io.velBCy && io.velBCyMask && io.vy_out && io.vx_out, "%s: NULL pointer argument", who);
+    SOL_REQUIRE((io.d_in && io.inflow) || !io.d_out, "%s: density output requested without d_in / inflow", who);
+    SOL_REQUIRE(!io.feat_out || io.feat_scale, "%s: feat_out requires feat_scale", who);
+    SOL_REQUIRE(io.vy_in != io.vy_out && io.vx_in != io.vx_out && (io.d_in != io.d_out || !io.d_out), "%s: outputs must not alias the inputs", who);
+    const void* outs[] = {io.d_out, io.vy_out, io.vx_out, io.feat_out, cg_info, p_inout};
+    const void* ins[] = {io.d_in, io.vy_in, io.vx_in, io.re, io.active, io.inflow, io.velBCy, io.velBCyMask, box_blob};
+    for (const void* o : outs)
+        for (const void* i : ins) SOL_REQUIRE(!o || o != i, "%s: outputs must not alias the inputs", who);
+    hipStream_t s = (hipStream_t)stream;
+    const Large l = large_layout(c, workspace);
+    if (int e = sol_large_step(c, s, io, l.svy, l.svx, false, nullptr, box_blob, cg_info, l.a.r, p_inout)) return e;
+    if (p_inout) {
+        const size_t n = (size_t)c->B * c->Y * c->X;
+        const size_t nb = (n + PCG_T - 1) / PCG_T;
+        SOL_LAUNCH(large_copy, dim3((unsigned)(nb < 4096 ? nb : 4096)), dim3(PCG_T), 0, s, p_inout, (const float*)l.a.x, n);
+        SOL_LAUNCH_CHECK();
+    }
+    return SOL_OK;
+}
+
+}  // namespace
+
 extern "C" int sol_karman_step_fwd_large_cg(const sol_karman_cfg* c, void* stream,
                                             const float* d_in, const float* vy_in, const float* vx_in,
                                             const float* re, const float* active, const float* inflow,
@@ -414,20 +502,22 @@ extern "C" int sol_karman_step_fwd_large_cg(const sol_karman_cfg* c, void* strea
                                             float* feat_out, const float* feat_scale,
                                             const float* box_blob, const int32_t* box_header_host, int32_t* cg_info,
                                             void* workspace, size_t workspace_bytes) {
-    const char* who = "sol_karman_step_fwd_large_cg";
-    if (int e = large_check(c, who, box_blob, box_header_host, cg_info, workspace, workspace_bytes)) return e;
-    SOL_REQUIRE(vy_in && vx_in && re && active && velBCy && velBCyMask && vy_out && vx_out, "%s: NULL pointer argument", who);
-    SOL_REQUIRE((d_in && inflow) || !d_out, "%s: density output requested without d_in / inflow", who);
-    SOL_REQUIRE(!feat_out || feat_scale, "%s: feat_out requires feat_scale", who);
-    SOL_REQUIRE(vy_in != vy_out && vx_in != vx_out && (d_in != d_out || !d_out), "%s: outputs must not alias the inputs", who);
-    const void* outs[] = {d_out, vy_out, vx_out, feat_out, cg_info};
-    const void* ins[] = {d_in, vy_in, vx_in, re, active, inflow, velBCy, velBCyMask, box_blob};
-    for (const void* o : outs)
-        for (const void* i : ins) SOL_REQUIRE(!o || o != i, "%s: outputs must not alias the inputs", who);
-    hipStream_t s = (hipStream_t)stream;
-    const Large l = large_layout(c, workspace);
     const SolLargeStep io{d_in, vy_in, vx_in, re, active, inflow, velBCy, velBCyMask, bc_batch_stride, d_out, vy_out, vx_out, feat_out, feat_scale};
-    return sol_large_step(c, s, io, l.svy, l.svx, false, nullptr, box_blob, cg_info, l.a.r);
+    return large_cg_step("sol_karman_step_fwd_large_cg", c, stream, io, box_blob, box_header_host, cg_info, nullptr, workspace, workspace_bytes);
+}
+
+extern "C" int sol_karman_step_fwd_large_cg_warm(const sol_karman_cfg* c, void* stream,
+                                                 const float* d_in, const float* vy_in, const float* vx_in,
+                                                 const float* re, const float* active, const float* inflow,
+                                                 const float* velBCy, const float* velBCyMask, int64_t bc_batch_stride,
+                                                 float* d_out, float* vy_out, float* vx_out,
+                                                 float* feat_out, const float* feat_scale,
+                                                 const float* box_blob, const int32_t* box_header_host, int32_t* cg_info,
+                                                 float* p_inout, void* workspace, size_t workspace_bytes) {
+    const char* who = "sol_karman_step_fwd_large_cg_warm";
+    SOL_REQUIRE(p_inout != nullptr, "%s: NULL pointer argument (p_inout: the initial guess in, the step's pressure out)", who);
+    const SolLargeStep io{d_in, vy_in, vx_in, re, active, inflow, velBCy, velBCyMask, bc_batch_stride, d_out, vy_out, vx_out, feat_out, feat_scale};
+    return large_cg_step(who, c, stream, io, box_blob, box_header_host, cg_info, p_inout, workspace, workspace_bytes);
 }
 
 extern "C" int sol_karman_pressure_solve_large(const sol_karman_cfg* c, void* stream, const float* active, const float* rhs, float* p,

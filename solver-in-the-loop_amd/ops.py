@@ -116,9 +116,10 @@ def _publish_cg(info, cg_info, suffix=""):
         info["iterations" + suffix], info["converged" + suffix] = cg_info[0], cg_info[1]
 
 
-def _large_fwd(d, vy, vx, re, cfg, masks):
-    """Outputs of the large-grid forward step and the fourteen arguments its three entry points begin with"""
-    outs = torch.empty_like(d), torch.empty_like(vy), torch.empty_like(vx)
+def _large_fwd(d, vy, vx, re, cfg, masks, outs=None):
+    """Outputs of the large-grid forward step (fresh unless given) and the fourteen arguments its entry points begin with"""
+    if outs is None:
+        outs = torch.empty_like(d), torch.empty_like(vy), torch.empty_like(vx)
     head = (C.byref(cfg), stream(), ptr(d), ptr(vy), ptr(vx), ptr(re), ptr(masks.active), ptr(masks.inflow), ptr(masks.velBCy),
             ptr(masks.velBCyMask), masks.bc_stride, *(ptr(t) for t in outs))
     return outs, head
@@ -175,30 +176,69 @@ def karman_step_large_bwd(svy, svx, re, gvy, gvx, cfg, masks, workspace=None, in
     return oy, ox
 
 
-def karman_step_large(d, vy, vx, re, cfg, masks, workspace=None, info=None):
+def karman_step_large(d, vy, vx, re, cfg, masks, workspace=None, info=None, feat=None, feat_scale=None, p_guess=None, out=None):
     """The step for grids beyond the one-workgroup kernels (data generation at 256 x 128,
     /root/reference/karman-2d/karman.py:98-159): sol_karman_step_fwd_large (direct solve) or sol_karman_step_fwd_large_cg (CG solve,
     masks.pressure_solver == "cg").  Returns (d, vy, vx) after the step; with the CG solve, `info` (a dict) receives "iterations" and
     "converged", device int32 [B] each.  When grad is enabled and vy or vx requires a gradient the call goes through KarmanStepLargeFn
     (same forward launches, plus the saved post-diffusion velocity) and `info` also receives "iterations_bwd" / "converged_bwd" after
-    backward(); otherwise nothing is kept."""
+    backward(); otherwise nothing is kept.
+    No-grad extras (a roll-out, trainer.LargeGridRollout): `feat` [B,Y,X,4] receives the network's input, to_feature of the new velocity
+    times `feat_scale` (three factors, 1 / std; channel 3 is zero); `p_guess` [B,Y,X] warm-starts the CG solve
+    (sol_karman_step_fwd_large_cg_warm: read as the initial guess, overwritten with the step's pressure) and is an error on a scene with
+    the direct solver; `out` = (d, vy, vx) buffers to write instead of fresh tensors (they must not be the inputs)."""
+    if p_guess is not None and masks.direct is not None:
+        raise ValueError("karman_step_large: p_guess warm-starts the CG pressure solve; this scene runs the direct solver (no iteration to start)")
     _lib.require_gpu()
     lib = _lib.load()
     d, vy, vx, re = (_lib.f32(t) for t in (d, vy, vx, re))
     B, Y, X = cfg.B, cfg.Y, cfg.X
     assert vy.shape == (B, Y + 1, X) and vx.shape == (B, Y, X + 1) and d.shape == (B, Y, X) and re.shape == (B,)
+    extras = feat is not None or p_guess is not None or out is not None
     if torch.is_grad_enabled() and (vy.requires_grad or vx.requires_grad):
+        if extras:
+            raise ValueError("karman_step_large: feat / p_guess / out belong to the no-grad step (the differentiable step keeps its own state)")
         return KarmanStepLargeFn.apply(d, vy, vx, re, cfg, masks, workspace, info)
+    if (feat is None) != (feat_scale is None):
+        raise ValueError("karman_step_large: feat and feat_scale go together")
+    if feat is not None and (feat.shape != (B, Y, X, 4) or feat.device != vy.device):
+        raise ValueError("karman_step_large: feat must be [B,Y,X,4] = %s on %s (got %s on %s)" % ((B, Y, X, 4), vy.device, tuple(feat.shape), feat.device))
+    if p_guess is not None and (p_guess.shape != (B, Y, X) or p_guess.device != vy.device):
+        raise ValueError("karman_step_large: p_guess must be [B,Y,X] = %s on %s (got %s on %s)" % ((B, Y, X), vy.device, tuple(p_guess.shape), p_guess.device))
     workspace = _workspace(large_workspace_bytes(cfg, masks), workspace, vy.device)
-    outs, head = _large_fwd(d, vy, vx, re, cfg, masks)
+    if out is None:
+        outs, head = _large_fwd(d, vy, vx, re, cfg, masks)
+    else:
+        outs = tuple(out)
+        if [tuple(t.shape) for t in outs] != [tuple(t.shape) for t in (d, vy, vx)]:
+            raise ValueError("karman_step_large: out must be (d, vy, vx) buffers of the inputs' shapes")
+        head = _large_fwd(d, vy, vx, re, cfg, masks, outs)[1]
+    fs = None if feat_scale is None else (feat_scale if isinstance(feat_scale, C.Array) else _scale3(feat_scale))
     cg_info = _cg_info(masks, B, vy.device)
     if cg_info is None:
-        check(lib.sol_karman_step_fwd_large(*head, None, None, _hdr(masks.direct_header), ptr(workspace), workspace.numel() * 4))
-    else:
-        check(lib.sol_karman_step_fwd_large_cg(*head, None, None, ptr(masks.box), _hdr(masks.box_header), ptr(cg_info),
+        check(lib.sol_karman_step_fwd_large(*head, ptr(feat), fs, _hdr(masks.direct_header), ptr(workspace), workspace.numel() * 4))
+    elif p_guess is None:
+        check(lib.sol_karman_step_fwd_large_cg(*head, ptr(feat), fs, ptr(masks.box), _hdr(masks.box_header), ptr(cg_info),
                                                ptr(workspace), workspace.numel() * 4))
+    else:
+        check(lib.sol_karman_step_fwd_large_cg_warm(*head, ptr(feat), fs, ptr(masks.box), _hdr(masks.box_header), ptr(cg_info),
+                                                    ptr(p_guess), ptr(workspace), workspace.numel() * 4))
     _publish_cg(info, cg_info)
     return outs
+
+
+def karman_correct(out, vy, vx, s, cor=None):
+    """velocity += s * to_staggered(out) in place, one launch (sol_karman_correct; karman_train.py:88-90, 424-426): out [B,Y,X,2] the
+    network's output, vy [B,Y+1,X] / vx [B,Y,X+1] whose last row / column get no correction, s = (s0, s1) the output scale per
+    component.  cor = (cor_y, cor_x) of the velocity's shapes receive the applied correction (zero on that row / column)."""
+    _lib.require_gpu()
+    B, Y, X = vx.shape[0], vx.shape[1], vy.shape[2]
+    if out.shape != (B, Y, X, 2) or vy.shape != (B, Y + 1, X) or vx.shape != (B, Y, X + 1):
+        raise ValueError("karman_correct: out %s, vy %s, vx %s are not [B,Y,X,2], [B,Y+1,X], [B,Y,X+1]" % (tuple(out.shape), tuple(vy.shape), tuple(vx.shape)))
+    cy, cx = (None, None) if cor is None else cor
+    if cor is not None and (cy.shape != vy.shape or cx.shape != vx.shape):
+        raise ValueError("karman_correct: cor must be (cor_y, cor_x) of the velocity's shapes")
+    check(_lib.load().sol_karman_correct(stream(), ptr(out), ptr(vy), ptr(vx), ptr(cy), ptr(cx), B, Y, X, float(s[0]), float(s[1])))
 
 
 def pressure_solve_large(rhs, cfg, masks, workspace=None, info=None):

@@ -38,13 +38,16 @@ def _int_array(vals):
 
 
 class NetSchedule2D:
-    def __init__(self, net, B, H, W):
+    def __init__(self, net, B, H, W, train=True):
+        """train=False (a roll-out: forward only): no weight-gradient partial buffers, no backward-data packs, and the absmax slots of the
+        forward are persistent buffers cleared by one library launch per call (no torch fill between the launches)."""
         if net.name not in ("mars_moon", "mercury"):
             raise _lib.SolError("NetSchedule2D: no hand-written schedule for network %r" % net.name)
         _lib.require_gpu()
         self.lib = lib = _lib.load()
         self.net, self.B, self.H, self.W = net, int(B), int(H), int(W)
         self.scaled = self.W % 64 == 0               # 64-pixel rows: the split-precision kernels + absmax hand-over
+        self.train = bool(train)
         if net.cin > 4:
             raise _lib.SolError("NetSchedule2D: at most 4 input channels (got %d)" % net.cin)
         if net.cout != 2:
@@ -58,10 +61,10 @@ class NetSchedule2D:
         for cin, cout in dims:
             u = _Unit()
             u.cin, u.cout, u.cin_k = cin, cout, (4 if cin <= 4 else 32)
-            u.ws = int(lib.sol_conv5x5_bwd_weight_ws_floats(self.B, self.H, self.W, u.cin_k, cout))
+            u.ws = int(lib.sol_conv5x5_bwd_weight_ws_floats(self.B, self.H, self.W, u.cin_k, cout)) if self.train else 0
             total += (u.ws + 3) // 4 * 4
             u.pf = f(lib.sol_conv5x5_packed_floats(cin, cout, ops.CONV_FWD))
-            u.pb = f(lib.sol_conv5x5_packed_floats(cout, cin, ops.CONV_BWD_DATA))
+            u.pb = f(lib.sol_conv5x5_packed_floats(cout, cin, ops.CONV_BWD_DATA)) if self.train else None
             self.units.append(u)
         self._partials = f(total)
         off = 0
@@ -86,6 +89,11 @@ class NetSchedule2D:
                 u.src, u.w, u.b = src, torch.empty(src.shape, dtype=torch.float32, device=dev), b
                 u.dw, u.db = torch.empty(src.shape, dtype=torch.float32, device=dev), f(u.cout)
         n = len(self.units)
+        if not self.train:
+            self._fwd_slots = torch.zeros(11 if mm else 3, ops.AMAX_SLOTS, dtype=torch.int32, device=dev) if self.scaled else None
+            self._pack_args = (n, _ptr_array([u.w for u in self.units]), _int_array([u.cin for u in self.units]), _int_array([u.cout for u in self.units]),
+                               _int_array([ops.CONV_FWD] * n), _ptr_array([u.pf for u in self.units]))
+            return
         self._pack_args = (2 * n, _ptr_array([u.w for u in self.units] * 2), _int_array([u.cin for u in self.units] + [u.cout for u in self.units]),
                            _int_array([u.cout for u in self.units] + [u.cin for u in self.units]), _int_array([ops.CONV_FWD] * n + [ops.CONV_BWD_DATA] * n),
                            _ptr_array([u.pf for u in self.units] + [u.pb for u in self.units]))
@@ -100,7 +108,8 @@ class NetSchedule2D:
             if u.src is not None:
                 u.w.copy_(u.src)                      # (strided halves of a mercury kernel: an elementwise copy kernel)
         check(self.lib.sol_conv5x5_pack_jobs(stream(), *self._pack_args))
-        check(self.lib.sol_copy_words(stream(), ptr(self._partials), None, self._partials.numel()))
+        if self.train:
+            check(self.lib.sol_copy_words(stream(), ptr(self._partials), None, self._partials.numel()))
 
     # ---- launches -----------------------------------------------------------------------------------------------------------
     def _conv(self, x, packed, bias, residual, act_ref, cout, epi, xmax, ymax):
@@ -120,6 +129,9 @@ class NetSchedule2D:
         check(self.lib.sol_conv5x5_bwd_weight(stream(), ptr(xk), ptr(dz), ptr(u.part), self.B, self.H, self.W, u.cin_k, u.cout))
 
     def _slots(self, n, dev):
+        if not self.train and self.scaled:          # forward only: the persistent slots, cleared by a library launch
+            check(self.lib.sol_copy_words(stream(), ptr(self._fwd_slots), None, self._fwd_slots.numel()))
+            return self._fwd_slots
         return torch.zeros(n, ops.AMAX_SLOTS, dtype=torch.int32, device=dev) if self.scaled else [None] * n
 
     # ---- forward ------------------------------------------------------------------------------------------------------------
@@ -149,6 +161,8 @@ class NetSchedule2D:
     def backward(self, state, g_out):
         """d loss / d x [B,H,W,cin] for the output gradient g_out [B,H,W,cout]; the weight gradients of this call are added to the layers'
         partial buffers (end_step reduces them)."""
+        if not self.train:
+            raise _lib.SolError("NetSchedule2D(train=False) runs the forward pass only")
         xk, am, acts = state
         U, D, N = self.units, ops.EPI_DLRELU, ops.EPI_NONE
         g = _lib.f32(g_out).contiguous()
@@ -182,6 +196,8 @@ class NetSchedule2D:
     def end_step(self):
         """reduce every layer's partial sums (sol_conv5x5_bwd_weight_reduce_jobs: two launches for all layers); returns the flat gradient in
         Keras get_weights() order (self.flat: model_mars_moon's layers reduce straight into it)"""
+        if not self.train:
+            raise _lib.SolError("NetSchedule2D(train=False) runs the forward pass only")
         check(self.lib.sol_conv5x5_bwd_weight_reduce_jobs(stream(), *self._reduce_args))
         if self.net.name == "mercury":
             # kernel 2 is [5,5,32,64] = the two output halves side by side, kernel 4 is [5,5,64,2] = the two input halves stacked;

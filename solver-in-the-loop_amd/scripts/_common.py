@@ -18,12 +18,16 @@ def logger(path=None):
     return log
 
 
-def add_scene_args(p):
-    """--obstacle / --obstacle-mask / --pressure-solver of the 2-D scripts (defaults: the reference's sphere, automatic solver)."""
+def add_scene_args(p, warm_start=False):
+    """--obstacle / --obstacle-mask / --pressure-solver of the 2-D scripts (defaults: the reference's sphere, automatic solver);
+    warm_start: also --cg-warm-start (the roll-out script, which performs consecutive solves of one scene)."""
     p.add_argument("--obstacle", action="append", default=None, metavar="SPEC",
                    help="obstacle in domain coordinates, repeatable: sphere:CY,CX,R | box:Y0:Y1,X0:X1 | none (default: sphere:50,50,10)")
     p.add_argument("--obstacle-mask", default=None, metavar="FILE.npy", help="[Y, X] fluid mask (1 = fluid) for exactly this grid")
     p.add_argument("--pressure-solver", default="auto", choices=("auto", "direct", "cg"), help="pressure solve of the solver step")
+    if warm_start:
+        p.add_argument("--cg-warm-start", action="store_true",
+                       help="start every CG pressure solve from the previous frame's pressure (large grids; ignored with the direct solve)")
 
 
 def scene_from_args(params):

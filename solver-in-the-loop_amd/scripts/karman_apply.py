@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """Inference roll-out with the trained corrector -- flags of /root/reference/karman-2d/karman_apply.py:
 20-31, loop :138-158 (simulator.step -> model.predict correction -> write denTf/velTf/corTf frames).
-Solver step + CNN run on the GPU (SolRollout, one frame per call so that every frame can be written)."""
+Solver step + CNN run on the GPU (make_rollout: SolRollout, or LargeGridRollout beyond the one-workgroup grids such as -r 128; one frame
+per call so that every frame can be written)."""
 import argparse
 import pickle
 
@@ -26,7 +27,7 @@ def main(argv=None):
     p.add_argument("-o", "--output", default="/tmp/phiflow/run", help="path to an output directory")
     p.add_argument("--stats", default="/tmp/phiflow/data/dataStats.pickle", help="path to datastats")
     p.add_argument("--model", default="/tmp/phiflow/tf/model.pt", help="path to a trained model")
-    add_scene_args(p)
+    add_scene_args(p, warm_start=True)
     params = vars(p.parse_args(argv))
     select_gpu(params["gpu"])
     log = logger()
@@ -63,7 +64,14 @@ def main(argv=None):
     masks = ops.SceneMasks(active, inflow, velBCy.reshape(Y + 1, X), velBCyMask.reshape(Y + 1, X),
                            pressure_solver=params["pressure_solver"])
     log.info("pressure solver: %s" % masks.pressure_solver)
-    ro = sol_amd.SolRollout(model, masks, 1, Y, X, dom.dx[1], data_stats["std"][1], data_stats["ext.std"][0])
+    large = ops.beyond_one_workgroup(Y, X)
+    warm = bool(params["cg_warm_start"]) and large and masks.pressure_solver == "cg"
+    if params["cg_warm_start"] and not warm:
+        log.info("--cg-warm-start ignored: %s" % ("the direct pressure solve has no iteration to start" if large and masks.pressure_solver == "direct"
+                                                  else "it belongs to the CG solve of the large grids"))
+    # (a CG scene runs eagerly, every solve stops at convergence; a direct-solve scene replays one captured step)
+    ro = sol_amd.make_rollout(model, masks, 1, Y, X, dom.dx[1], data_stats["std"][1], data_stats["ext.std"][0],
+                              use_graph=masks.pressure_solver == "direct", cg_warm_start=warm)
     f = lambda a: torch.as_tensor(np.ascontiguousarray(a), dtype=torch.float32, device="cuda").contiguous()
     vy0, vx0 = scene.split_staggered(np.asarray(vn, dtype=np.float32))
     d, vy, vx = f(np.asarray(d0)[..., 0]), f(vy0), f(vx0)
@@ -74,14 +82,21 @@ def main(argv=None):
 
     zero = np.zeros((1, Y + 1, X + 1, 2), dtype=np.float32)
     scene.scene_write(path, [d.reshape(1, Y, X, 1).cpu().numpy(), stag(vy, vx), zero], ["denTf", "velTf", "corTf"], 0)
+    cor = (torch.zeros_like(vy), torch.zeros_like(vx))
     for i in range(1, params["simsteps"]):
-        py, px = vy.clone(), vx.clone()
-        # uncorrected step (for the written correction field) and corrected step
-        cfg = ops.karman_cfg(1, Y, X, dom.dx[1], res=res, masks=masks)
-        with torch.no_grad():
-            _, sy, sx = ops.karman_step(d, py, px, re, cfg, masks)
-        ro.run(d, vy, vx, re, 1)
-        scene.scene_write(path, [d.reshape(1, Y, X, 1).cpu().numpy(), stag(vy, vx), stag(vy - sy, vx - sx)], ["denTf", "velTf", "corTf"], i)
+        if large:
+            # the roll-out hands out the correction it applied: no second, uncorrected solver step per frame
+            ro.run(d, vy, vx, re, 1, corr=cor)
+            cy, cx = cor
+        else:
+            py, px = vy.clone(), vx.clone()
+            # uncorrected step (for the written correction field) and corrected step
+            cfg = ops.karman_cfg(1, Y, X, dom.dx[1], res=res, masks=masks)
+            with torch.no_grad():
+                _, sy, sx = ops.karman_step(d, py, px, re, cfg, masks)
+            ro.run(d, vy, vx, re, 1)
+            cy, cx = vy - sy, vx - sx
+        scene.scene_write(path, [d.reshape(1, Y, X, 1).cpu().numpy(), stag(vy, vx), stag(cy, cx)], ["denTf", "velTf", "corTf"], i)
         if i % 100 == 0:
             log.info("step {:06d}".format(i))
     return path

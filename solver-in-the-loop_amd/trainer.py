@@ -266,6 +266,121 @@ class SolRollout:
         return iters.reshape(nsteps, self.B)
 
 
+class LargeGridRollout:
+    """SolRollout's call surface for domains BEYOND the one-workgroup solver grids (ops.beyond_one_workgroup), X a multiple of 64 -- the
+    reference's 256 x 128 grid: the no-grad roll-out of karman_apply.py:138-158 with a model LargeGridTrainer wrote.  Networks: mars_moon
+    and mercury.  One step is three groups of library launches and nothing else: the large-grid solver step, which writes the scaled
+    features itself (ops.karman_step_large(feat=...), direct or CG pressure solve as SceneMasks decided for the scene), the network's
+    forward launches (NetSchedule2D(train=False); weights packed once per run) and the correction (ops.karman_correct), followed by
+    one kernel copy of the new state over the old one: the state ping-pongs between two internal buffers A -> B and the copy B -> A
+    closes the step, so every step reads and writes the same addresses.
+
+    use_graph=True (direct-solve scenes): that step is captured once (_lib.capture_graph: kernel nodes only) and replayed nsteps times.
+    On a CG scene run() is eager, so that every solve stops at convergence: a captured step would issue the launches of the WHOLE
+    cg_max_iter budget per solve (converged iterations fall through; LargeGridTrainer's docstring), hundreds of launches a roll-out
+    step has no use for -- use_graph=True raises there.  cg_warm_start=True (CG scenes; ignored with the direct solve): a solve starts
+    from the previous step's pressure, kept in `p_guess` [B,Y,X] across steps and run() calls (zero at first; reset_guess() clears it);
+    a simulation whose guess is not finite starts from zero.  After run(), `solve_info` holds "iterations" / "converged" [nsteps, B] on
+    a CG scene."""
+
+    def __init__(self, net, masks, B, Y, X, dx, std_v, std_re, dt=1.0, res=None, in_std_v=None, out_std_v=None,
+                 conv_precision="split", use_graph=True, cg_warm_start=False, **solver):
+        if not ops.beyond_one_workgroup(Y, X):
+            raise ValueError("LargeGridRollout: a %dx%d domain is served by the one-workgroup roll-out -- use SolRollout (make_rollout picks)" % (Y, X))
+        if X % 64 != 0:
+            raise ValueError("LargeGridRollout: the convolutions of a large domain take rows of X %% 64 == 0 cells (got %dx%d); "
+                             "no roll-out class serves this grid (KarmanFlow.step advances it without the network)" % (Y, X))
+        cg = masks.pressure_solver == "cg"
+        if cg and use_graph:
+            raise ValueError("LargeGridRollout: use_graph=True on a scene with the CG pressure solve -- the iteration count of a solve is "
+                             "not known at capture time, so a captured step issues the launches of the whole cg_max_iter budget per solve; "
+                             "a roll-out runs such a scene eagerly and stops every solve at convergence: pass use_graph=False")
+        _lib.require_gpu()
+        from .schedule2d import NetSchedule2D
+        self.lib = _lib.load()
+        self.conv_precision = _conv_precision_code(conv_precision)
+        self.net, self.masks, self.B, self.Y, self.X = net, masks, B, Y, X
+        self.cfg = ops.karman_cfg(B, Y, X, dx, dt=dt, res=res, masks=masks, **solver)
+        self.pressure_solver_used = masks.pressure_solver
+        self.use_graph, self._graph = bool(use_graph), None
+        self.cg_warm_start = bool(cg_warm_start) and cg
+        dev = self.device = net.params.device
+        self._fs3 = (C.c_float * 3)(*[1.0 / float(v) for v in (list(in_std_v if in_std_v is not None else std_v) + [std_re])])
+        self._so = tuple(float(v) for v in (out_std_v if out_std_v is not None else std_v))
+        self._sched = NetSchedule2D(net, B, Y, X, train=False)
+        nd, ny, nx = B * Y * X, B * (Y + 1) * X, B * Y * (X + 1)
+        z = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)
+        views = lambda flat: (flat[:nd].view(B, Y, X), flat[nd:nd + ny].view(B, Y + 1, X), flat[nd + ny:].view(B, Y, X + 1))
+        self._flat = (z(nd + ny + nx), z(nd + ny + nx))          # the state (d | vy | vx): A, the step's input and result, and B
+        self._a, self._b = views(self._flat[0]), views(self._flat[1])
+        self._re = torch.ones(B, dtype=torch.float32, device=dev)
+        self._feat = z(B, Y, X, 4)
+        self._cor = (z(B, Y + 1, X), z(B, Y, X + 1))
+        self.p_guess = z(B, Y, X) if self.cg_warm_start else None
+        nbytes = ops.large_workspace_bytes(self.cfg, masks)
+        self._ws = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=dev)
+        self.solve_info = {}
+        self._info = []
+
+    def reset_guess(self):
+        """forget the previous step's pressure: the next solve starts from zero"""
+        if self.p_guess is not None:
+            check(self.lib.sol_copy_words(stream(), ptr(self.p_guess), None, self.p_guess.numel()))
+
+    def _step(self):
+        info = {}
+        ops.karman_step_large(*self._a, self._re, self.cfg, self.masks, self._ws, info, feat=self._feat, feat_scale=self._fs3,
+                              p_guess=self.p_guess, out=self._b)
+        out, _ = self._sched.forward(self._feat)
+        ops.karman_correct(out, self._b[1], self._b[2], self._so, self._cor)
+        _lib.dcopy_(self._flat[0], self._flat[1])
+        self._info.append(info)
+
+    def run(self, d, vy, vx, re, nsteps, corr=None):
+        """Advances (d, vy, vx) in place by nsteps; returns the CG iterations [nsteps, B] (zeros with the direct solve).
+        corr = (cor_y [B,Y+1,X], cor_x [B,Y,X+1]): receive the correction the LAST step applied (zero on the uncorrected row / column)."""
+        B, Y, X = self.B, self.Y, self.X
+        assert d.shape == (B, Y, X) and vy.shape == (B, Y + 1, X) and vx.shape == (B, Y, X + 1) and re.shape == (B,)
+        assert corr is None or (corr[0].shape == vy.shape and corr[1].shape == vx.shape)
+        self._info = []
+        with torch.no_grad(), _conv_precision_scope(self.conv_precision):
+            self._sched.begin_step()                      # the weights, packed once per run
+            if self.use_graph and self._graph is None and nsteps > 0:
+                side = torch.cuda.Stream()
+                side.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(side):
+                    self._step()                          # (on the zero state of a fresh object: nothing of it is kept)
+                torch.cuda.current_stream().wait_stream(side)
+                torch.cuda.synchronize()
+                self._graph = _lib.capture_graph(self._step, "LargeGridRollout")
+                self._info = []
+            for dst, src in zip(self._a + (self._re,), (d, vy, vx, re)):
+                _lib.dcopy_(dst, src)
+            for _ in range(nsteps):
+                if self._graph is not None:
+                    self._graph.replay()
+                else:
+                    self._step()
+            for dst, src in zip((d, vy, vx), self._a):
+                _lib.dcopy_(dst, src)
+            if corr is not None and nsteps > 0:
+                _lib.dcopy_(corr[0], self._cor[0])
+                _lib.dcopy_(corr[1], self._cor[1])
+        if self.pressure_solver_used == "cg" and nsteps > 0:
+            self.solve_info = {k: torch.stack([t[k] for t in self._info]) for k in ("iterations", "converged")}
+            return self.solve_info["iterations"]
+        return torch.zeros(nsteps, B, dtype=torch.int32, device=d.device)
+
+
+def make_rollout(net, masks, B, Y, X, dx, std_v, std_re, **kw):
+    """SolRollout for the one-workgroup solver grids, LargeGridRollout beyond them (use_graph / cg_warm_start belong to the latter)."""
+    if ops.beyond_one_workgroup(Y, X):
+        return LargeGridRollout(net, masks, B, Y, X, dx, std_v, std_re, **kw)
+    for k in ("use_graph", "cg_warm_start"):
+        kw.pop(k, None)
+    return SolRollout(net, masks, B, Y, X, dx, std_v, std_re, **kw)
+
+
 class GraphTrainer(_AdamDP):
     """The SolTrainer call surface for networks the C++ trainer has no fused schedule for (`model_mercury`,
     karman_train.py:92-99 / `eval('model_'+...)` at :394).  The unrolled step of karman_train.py:397-457 runs as a HAND-WRITTEN
