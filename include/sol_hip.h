@@ -84,7 +84,7 @@ int sol_abi_sizes(int32_t* karman_cfg, int32_t* burgers_cfg, int32_t* train_cfg)
  *   k3d_bww_jobs (2)    karman-3d: the five depth slices of a 32 -> 32 Conv3D weight gradient (sol_conv3d_bwd_weight*) as ONE launch of ONE round of
  *                       workgroups (51 per slice; other block partition: sums equal to round-off); 1: one launch of five rounds of 32-row
  *                       workgroups (bit-identical to 0); 0: five launches
- *   bww_chunk (0), bww_side (1), streams (1), cpt (0), conv_split3 (0), dbg_skip (0), step_prof (0): experiments, debugging */
+ *   cpt (0), conv_split3 (0), dbg_skip (0), step_prof (0): experiments, debugging */
 int sol_set_option(const char* name, int32_t value);
 int sol_get_option(const char* name, int32_t* value);
 
@@ -398,9 +398,8 @@ int sol_train_fwd_bwd(const sol_train_cfg* cfg, void* stream,
 
 /* The same step as a replayable hipGraph: one host call per training step instead of ~1000 kernel
  * launches.  All pointers are baked in at creation (re-create when a buffer moves); new data is
- * fed by copying into the same buffers.  (Option `streams` > 1 splits the batch into chains of
- * simulations on separate internal HIP streams; measured slower on MI355X, default 1.)
- * One training call at a time per process (the chains share an internal stream pool).          */
+ * fed by copying into the same buffers.  sol_train_graph_launch replays it on the caller's stream;
+ * the library opens no streams of its own for training.                                        */
 typedef struct sol_train_graph sol_train_graph;
 int sol_train_graph_create(const sol_train_cfg* cfg, const float* params,
                            const float* d0, const float* vy0, const float* vx0, const float* re,

@@ -162,11 +162,11 @@ ABI_VERSION = 216     # sol_version() of the library these bindings were written
 _ENV_OPTIONS = {
     "SOL_CONV_NO_SB": ("conv_precision", 2), "SOL_CONV_NO_FP16": ("conv_precision", 1), "SOL_CONV_SPLIT3": ("conv_split3", 1),
     "SOL_CONV_NO_R3": ("conv_r3", 0), "SOL_CONV_NO_THIN": ("conv_thin", 0), "SOL_CONV_NO_BWW32": ("conv_bww32", 0),
-    "SOL_CORRECT_NO_FUSE": ("correct_fuse", 0), "SOL_BWW_NO_FUSE": ("bww_fuse", 0), "SOL_BWW_NO_SIDE": ("bww_side", 0),
+    "SOL_CORRECT_NO_FUSE": ("correct_fuse", 0), "SOL_BWW_NO_FUSE": ("bww_fuse", 0),
     "SOL_DENSITY_INLINE": ("density_mode", 1), "SOL_DENSITY_NO_FUSE": ("density_mode", 2), "SOL_STEP_PROF": ("step_prof", 1),
     "SOL_CNN_NO_PERSISTENT": ("cnn_persistent", 0), "SOL_CONV_NO_DX": ("conv_dx", 0), "SOL_CONV_NO_THIN_VALU": ("conv_thin_valu", 0),
 }
-_ENV_INT_OPTIONS = {"SOL_FWD_BANDS": "fwd_bands", "SOL_CONV_THIN_VALU": "conv_thin_valu", "SOL_BWW_CHUNK": "bww_chunk", "SOL_STREAMS": "streams", "SOL_CPT": "cpt", "SOL_DBG_SKIP": "dbg_skip"}
+_ENV_INT_OPTIONS = {"SOL_FWD_BANDS": "fwd_bands", "SOL_CONV_THIN_VALU": "conv_thin_valu", "SOL_CPT": "cpt", "SOL_DBG_SKIP": "dbg_skip"}
 
 
 def load():

@@ -232,16 +232,12 @@ struct SolOptions {
     int conv_bww32;       // 1: 32x32x2 fp32 MFMA weight gradient (strict path)
     int correct_fuse;     // 1: correction + loss in the last CNN layer's epilogue
     int bww_fuse;         // 1: 32->32 weight gradients ride in the solver-adjoint launches
-    int bww_chunk;        // 0: one weight-gradient launch per layer over all unrolled steps; n: chunks of n steps
-    int bww_side;         // 1: chunked weight gradients on a side stream
-    int streams;          // sub-batch chains on separate streams (measured slower; default 1)
     int density_mode;     // 0: density advection rides in the next solver launch; 1: inline in the step kernel; 2: one chain launch after the unroll
     int cpt;              // 0: automatic strip height of the CG kernels, 8 / 16: forced
     int dbg_skip;         // timing experiments only
     int step_prof;        // debugging: synchronous phase times of the solver step kernels on stderr
     int cnn_persistent;   // 1: the ten 32 -> 32 layers of a CNN pass as ONE persistent launch (cnn_chain.hip) where the shape allows it; default 0:
                           //    measured equal to the per-layer launches end to end, kept as a verified experiment
-    int graph_stream;     // 1: sol_train_graph_launch replays on an internal stream fenced by events against the caller's stream
     int k3d_fused_tf;     // 1 (default): the sine transforms of the karman-3d pressure solve as LDS-resident plane / column-slab kernels; 0: batched GEMMs
     int k3d_conv_rows;    // rows per workgroup of the one-launch Conv3D kernel: 8 (k_conv3d_sb8, 64 x 32 wave tiles), 6 (k_conv3d_sb6, 32 x 32), 3 (k_conv3d_sb, 16 x 32)
     int k3d_conv_fused;   // 1 (default): 32 -> 32 Conv3D layers with W == 64 and a known operand absmax as ONE launch (conv3d_sb.hip); 0: five passes of the 2-D kernel

@@ -34,8 +34,8 @@ SolOptions& sol_opt() {
     static SolOptions o = [] {
         SolOptions d{};
         d.conv_precision = 0; d.conv_split3 = 0; d.conv_r3 = 1; d.conv_thin = 1; d.conv_bww32 = 1;
-        d.correct_fuse = 1; d.bww_fuse = 1; d.bww_chunk = 0; d.bww_side = 1; d.streams = 1;
-        d.density_mode = 0; d.cpt = 0; d.dbg_skip = 0; d.step_prof = 0; d.cnn_persistent = 0; d.graph_stream = 0; d.k3d_tile = 0; d.k3d_fused_tf = 1; d.k3d_conv_fused = 1; d.k3d_conv_rows = 8; d.conv_dx = 11; d.k3d_mfma_tf = 1; d.conv_thin_valu = 1; d.seed_fuse = 1; d.fwd_bands = 1; d.conv_thin_t3 = 1; d.k3d_bww_jobs = 2; d.k3d_conv_persist = 0; d.k3d_adj_tile = 1; d.k2d_adj_tile = 1;
+        d.correct_fuse = 1; d.bww_fuse = 1;
+        d.density_mode = 0; d.cpt = 0; d.dbg_skip = 0; d.step_prof = 0; d.cnn_persistent = 0; d.k3d_tile = 0; d.k3d_fused_tf = 1; d.k3d_conv_fused = 1; d.k3d_conv_rows = 8; d.conv_dx = 11; d.k3d_mfma_tf = 1; d.conv_thin_valu = 1; d.seed_fuse = 1; d.fwd_bands = 1; d.conv_thin_t3 = 1; d.k3d_bww_jobs = 2; d.k3d_conv_persist = 0; d.k3d_adj_tile = 1; d.k2d_adj_tile = 1;
         return d;
     }();
     return o;
@@ -47,10 +47,9 @@ const OptName OPT_NAMES[] = {
     {"conv_precision", &SolOptions::conv_precision, 0, 2}, {"conv_split3", &SolOptions::conv_split3, 0, 1},
     {"conv_r3", &SolOptions::conv_r3, 0, 1}, {"conv_thin", &SolOptions::conv_thin, 0, 1}, {"conv_bww32", &SolOptions::conv_bww32, 0, 1},
     {"correct_fuse", &SolOptions::correct_fuse, 0, 1}, {"bww_fuse", &SolOptions::bww_fuse, 0, 1},
-    {"bww_chunk", &SolOptions::bww_chunk, 0, 1024}, {"bww_side", &SolOptions::bww_side, 0, 1}, {"streams", &SolOptions::streams, 1, 8},
     {"density_mode", &SolOptions::density_mode, 0, 2}, {"cpt", &SolOptions::cpt, 0, 16}, {"dbg_skip", &SolOptions::dbg_skip, 0, 1 << 30},
     {"step_prof", &SolOptions::step_prof, 0, 1}, {"cnn_persistent", &SolOptions::cnn_persistent, 0, 1},
-    {"graph_stream", &SolOptions::graph_stream, 0, 1}, {"k3d_tile", &SolOptions::k3d_tile, 0, 1}, {"k3d_fused_tf", &SolOptions::k3d_fused_tf, 0, 1}, {"k3d_conv_fused", &SolOptions::k3d_conv_fused, 0, 1}, {"k3d_conv_rows", &SolOptions::k3d_conv_rows, 3, 8},
+    {"k3d_tile", &SolOptions::k3d_tile, 0, 1}, {"k3d_fused_tf", &SolOptions::k3d_fused_tf, 0, 1}, {"k3d_conv_fused", &SolOptions::k3d_conv_fused, 0, 1}, {"k3d_conv_rows", &SolOptions::k3d_conv_rows, 3, 8},
     {"conv_dx", &SolOptions::conv_dx, 0, 15}, {"conv_thin_valu", &SolOptions::conv_thin_valu, 0, 2}, {"k3d_mfma_tf", &SolOptions::k3d_mfma_tf, 0, 1},
     {"seed_fuse", &SolOptions::seed_fuse, 0, 1}, {"fwd_bands", &SolOptions::fwd_bands, 0, 1}, {"conv_thin_t3", &SolOptions::conv_thin_t3, 0, 1}, {"k3d_bww_jobs", &SolOptions::k3d_bww_jobs, 0, 2}, {"k3d_conv_persist", &SolOptions::k3d_conv_persist, 0, 1}, {"k3d_adj_tile", &SolOptions::k3d_adj_tile, 0, 1}, {"k2d_adj_tile", &SolOptions::k2d_adj_tile, 0, 1},
 };
@@ -132,7 +131,6 @@ extern "C" int sol_prof_end(int32_t max_classes, char* names, double* total_us, 
 namespace {
 
 constexpr int NL = 12;   // conv layers of model_mars_moon
-int pick_bww_chunk(int ms);
 inline int layer_cin(int l) { return l == 0 ? 3 : 32; }
 inline int layer_cout(int l) { return l == NL - 1 ? 2 : 32; }
 inline int64_t layer_koff(int l) {
@@ -442,7 +440,7 @@ size_t carve_ws(const sol_train_cfg* c, float* base, Ws& w, bool training) {
     w.amax_act = reinterpret_cast<uint32_t*>(take(w.amax_words));
     w.amax_dz = reinterpret_cast<uint32_t*>(take(training ? w.amax_words : 0));
     // hand-off regions of the persistent CNN chain: sized by the image height the CNN kernels see (X in transposed-CNN mode) and
-    // carved only while the option is on (like bww_chunk, the option then enters the workspace size: a workspace sized with
+    // carved only while the option is on (the option then enters the workspace size: a workspace sized with
     // the option off is refused, not overrun, when it is switched on later)
     w.chain_words = sol_opt().cnn_persistent ? sol_cnn_chain_flag_words(B, cnn_transposed(Y, X) ? X : Y, 10) : 0;
     w.chain_flags = reinterpret_cast<uint32_t*>(take((training ? (size_t)ms * 2 : (size_t)ROLLOUT_AMAX_SETS) * w.chain_words));   // roll-out: forward pass only
@@ -454,7 +452,7 @@ size_t carve_ws(const sol_train_cfg* c, float* base, Ws& w, bool training) {
         w.wf[l] = take(sol_conv5x5_packed_floats(cin == 3 ? 4 : cin, cout, SOL_CONV_FWD));
         w.wb[l] = take(sol_conv5x5_packed_floats(cout == 2 ? 4 : cout, cin, SOL_CONV_BWD_DATA));
         w.bias[l] = take(32);
-        w.part_floats[l] = training ? sol_bww_batched_ws_floats(pick_bww_chunk(ms), B, cnn_transposed(Y, X) ? X : Y, cin == 3 ? 4 : cin, cout) : 0;
+        w.part_floats[l] = training ? sol_bww_batched_ws_floats(ms, B, cnn_transposed(Y, X) ? X : Y, cin == 3 ? 4 : cin, cout) : 0;
         w.part[l] = take(w.part_floats[l]);
     }
     w.adam_scale = take(64);
@@ -557,50 +555,6 @@ extern "C" size_t sol_rollout_workspace_bytes(const sol_train_cfg* cfg) {
 
 namespace {
 
-// ---- sub-batch chains on their own HIP streams ----------------------------------------------
-// The simulations of a batch are independent through the whole unroll (only the weight gradient is
-// summed at the end), and the solver kernels occupy one CU per simulation for hundreds of
-// microseconds while the conv kernels want the whole chip.  The batch is therefore split into S
-// chains (S | B; env SOL_STREAMS, default 1) that run on S streams: the solver step of one simulation overlaps
-// with the convolutions of the others, and the prologue/epilogue of one conv launch with the MFMA
-// phase of another.  Each chain has its own workspace slice and weight-gradient partials.
-struct StreamPool {
-    hipStream_t s[8];
-    hipEvent_t fork, join[8];
-    bool ok;
-};
-StreamPool* pool() {
-    static StreamPool p = [] {
-        StreamPool q{};
-        q.ok = true;
-        for (int k = 0; k < 8; ++k) {
-            q.ok &= hipStreamCreateWithFlags(&q.s[k], hipStreamNonBlocking) == hipSuccess;
-            q.ok &= hipEventCreateWithFlags(&q.join[k], hipEventDisableTiming) == hipSuccess;
-        }
-        q.ok &= hipEventCreateWithFlags(&q.fork, hipEventDisableTiming) == hipSuccess;
-        return q;
-    }();
-    return &p;
-}
-
-// Default: ONE weight-gradient launch per layer over all unrolled steps, after the sweep (chunk = msteps).
-// SOL_BWW_CHUNK=n covers n steps per launch on a side stream, meant to fill the ~250 CUs that idle while the
-// one-workgroup-per-simulation solver adjoint runs; measured on MI355X/ROCm 7.2 it does NOT overlap
-// (39.8 ms vs 38.3 ms per step, eager and graph alike), so it is off.
-int pick_bww_chunk(int ms) {
-    int ch = sol_opt().bww_chunk;
-    if (ch <= 0 || ch > ms) ch = ms;
-    return ch;
-}
-
-int pick_chains(int B) {
-    int want = sol_opt().streams;   // default 1; measured on MI355X/ROCm 7.2: concurrent chains are SLOWER (57 -> 105..167 ms/step), see DESIGN.md
-    if (want < 1) want = 1;
-    if (want > 8) want = 8;
-    while (B % want) --want;
-    return want;
-}
-
 struct TrainIO {
     const float *params, *d0, *vy0, *vx0, *re, *active, *inflow, *bcv, *bcm, *gt_vy, *gt_vx;
     int64_t bc_stride;
@@ -611,19 +565,19 @@ struct TrainIO {
 // The weight gradients of the 32 -> 32 layers of unrolled step i ride in the solver-adjoint launch of step i (k_karman_bwd_bww at 128x64,
 // k_karman_bwd_bww_small at 64x32 -- there the CNN runs on the transposed images, rows = B * X).  Returns the image rows per gradient
 // workgroup (32 / 16: sized to last about as long as the adjoint), or 0 where the per-layer launches after the sweep are used.
-// run_chain and the reduce at the end (which must know the partial layout) both ask here.
-int train_fused_rb(const sol_train_cfg* c, const Ws& w, int ms) {
+// unrolled_step and the reduce at the end (which must know the partial layout) both ask here.
+int train_fused_rb(const sol_train_cfg* c, const Ws& w) {
     const sol_karman_cfg* kc = &c->karman;
     const bool tr = cnn_transposed(kc->Y, kc->X);
     const int cY = tr ? kc->X : kc->Y, cX = tr ? kc->Y : kc->X;
-    if (pick_bww_chunk(ms) != ms || cX != 64 || !sol_opt().bww_fuse || sol_opt().conv_precision != 0) return 0;
+    if (cX != 64 || !sol_opt().bww_fuse || sol_opt().conv_precision != 0) return 0;
     const int rb = sol_karman_bwd_fusable(kc) ? 32 : (sol_karman_bwd_fusable_small(kc) ? 16 : 0);
     if (!rb || (kc->B * cY) % rb != 0 || sol_bww_step_ws_floats(kc->B, cY, rb) > w.part_floats[1]) return 0;
     return rb;
 }
 
-// forward unroll + reverse sweep of the simulations [b0, b0 + c.karman.B) on stream hs
-int run_chain(const sol_train_cfg* c, const Ws& w, const Ws& shared, int Btot, int b0, hipStream_t hs, const TrainIO& io) {
+// forward unroll + reverse sweep of the whole batch on stream hs
+int unrolled_step(const sol_train_cfg* c, const Ws& w, hipStream_t hs, const TrainIO& io) {
     void* stream = hs;
     const sol_karman_cfg* kc = &c->karman;
     const int B = kc->B, Y = kc->Y, X = kc->X, ms = c->msteps;
@@ -631,25 +585,16 @@ int run_chain(const sol_train_cfg* c, const Ws& w, const Ws& shared, int Btot, i
     const int cY = tr ? X : Y, cX = tr ? Y : X;
     const float fscale[3] = {1.f / in_s0(c), 1.f / in_s1(c), 1.f / c->std_re};
     const int egrid = (int)((w.st_vy + w.st_vx + 255) / 256);
-    const size_t gVy = (size_t)Btot * w.nVy, gVx = (size_t)Btot * w.nVx;       // per-step stride of the gt frames
-    const float* d0 = io.d0 + (size_t)b0 * w.N;
-    const float* vy0 = io.vy0 + (size_t)b0 * w.nVy;
-    const float* vx0 = io.vx0 + (size_t)b0 * w.nVx;
-    const float* re = io.re + b0;
-    const float* bcv = io.bcv + (size_t)b0 * io.bc_stride;
-    const float* bcm = io.bcm + (size_t)b0 * io.bc_stride;
-    const float* gt_vy = io.gt_vy + (size_t)b0 * w.nVy;
-    const float* gt_vx = io.gt_vx + (size_t)b0 * w.nVx;
+    const size_t gVy = (size_t)B * w.nVy, gVx = (size_t)B * w.nVx;       // per-step stride of the gt frames
+    const float *d0 = io.d0, *vy0 = io.vy0, *vx0 = io.vx0, *re = io.re, *bcv = io.bcv, *bcm = io.bcm, *gt_vy = io.gt_vy, *gt_vx = io.gt_vx;
     const float sl = c->lrelu_slope;
-    Ws wn = w;                         // packed weights / padded biases are shared by all chains
-    for (int l = 0; l < NL; ++l) { wn.wf[l] = shared.wf[l]; wn.wb[l] = shared.wb[l]; wn.bias[l] = shared.bias[l]; }
 
     // ---------------- forward unroll ----------------
     const bool dens_inline = sol_opt().density_mode == 1;
     const bool dens_fused = !dens_inline && io.d_final && sol_karman_bwd_fusable(kc) && sol_opt().density_mode == 0;
     // 64x32: one density advection per launch of the REVERSE sweep (k_karman_bwd_bww_small), msteps launches for msteps advections
     const bool dens_ride_bwd = !dens_inline && !dens_fused && io.d_final && sol_opt().density_mode == 0 && sol_karman_bwd_fusable_small(kc) &&
-                               train_fused_rb(c, w, ms) != 0;
+                               train_fused_rb(c, w) != 0;
     for (int i = 0; i < ms; ++i) {
         const float* din = i == 0 ? d0 : w.d + (size_t)(i - 1) * w.st_d;
         const float* vyin = i == 0 ? vy0 : w.vy + (size_t)(i - 1) * w.st_vy;
@@ -667,7 +612,7 @@ int run_chain(const sol_train_cfg* c, const Ws& w, const Ws& shared, int Btot, i
         // otherwise the whole chain is one launch after the unroll (sol_density_chain below).
         float* svy_i = w.svy + (size_t)i * w.st_vy;
         float* svx_i = w.svx + (size_t)i * w.st_vx;
-        int32_t* it_i = io.iters_fwd ? io.iters_fwd + (size_t)i * Btot + b0 : nullptr;
+        int32_t* it_i = io.iters_fwd ? io.iters_fwd + (size_t)i * B : nullptr;
         const bool bands = !dens_inline && !tr && sol_karman_fwd_bands_usable(kc);
         if (dens_fused && i >= 1) {
             const float* dprev = i == 1 ? d0 : w.d + (size_t)(i - 2) * w.st_d;
@@ -683,32 +628,32 @@ int run_chain(const sol_train_cfg* c, const Ws& w, const Ws& shared, int Btot, i
         float* act[11];
         for (int k = 0; k < 11; ++k) act[k] = w.acts + ((size_t)i * 11 + k) * w.cells * 32;
         if (sol_conv_correct_fusable(cX, B * cY)) {            // correction + loss ride in the epilogue of the last CNN layer
-            const Correct corr{vycur, vxcur, gt_vy + (size_t)i * gVy, gt_vx + (size_t)i * gVx, shared.loss_acc + (size_t)i * SOL_LOSS_ACC_WORDS};
-            if (int e = net_forward(c, stream, wn, feat_cnn, act, w.O, w.amax_act + (size_t)i * 11 * SOL_AMAX_SLOTS, &corr, w.chain_flags + (size_t)(2 * i) * w.chain_words)) return e;
+            const Correct corr{vycur, vxcur, gt_vy + (size_t)i * gVy, gt_vx + (size_t)i * gVx, w.loss_acc + (size_t)i * SOL_LOSS_ACC_WORDS};
+            if (int e = net_forward(c, stream, w, feat_cnn, act, w.O, w.amax_act + (size_t)i * 11 * SOL_AMAX_SLOTS, &corr, w.chain_flags + (size_t)(2 * i) * w.chain_words)) return e;
         } else {
-            if (int e = net_forward(c, stream, wn, feat_cnn, act, w.O, w.amax_act + (size_t)i * 11 * SOL_AMAX_SLOTS, nullptr, w.chain_flags + (size_t)(2 * i) * w.chain_words)) return e;
+            if (int e = net_forward(c, stream, w, feat_cnn, act, w.O, w.amax_act + (size_t)i * 11 * SOL_AMAX_SLOTS, nullptr, w.chain_flags + (size_t)(2 * i) * w.chain_words)) return e;
             SOL_LAUNCH(k_correct_loss, dim3(egrid), dim3(256), 0, hs, vycur, vxcur, w.O,
                                gt_vy + (size_t)i * gVy, gt_vx + (size_t)i * gVx,
-                               out_s0(c), out_s1(c), c->std_v0, c->std_v1, shared.loss_acc + (size_t)i * SOL_LOSS_ACC_WORDS, B, Y, X, tr ? 1 : 0);
+                               out_s0(c), out_s1(c), c->std_v0, c->std_v1, w.loss_acc + (size_t)i * SOL_LOSS_ACC_WORDS, B, Y, X, tr ? 1 : 0);
             SOL_LAUNCH_CHECK();
         }
     }
     MemList fin;
     if (dens_inline) {
-        if (io.d_final) fin.copy(io.d_final + (size_t)b0 * w.N, w.d + (size_t)(ms - 1) * w.st_d, w.st_d * sizeof(float));
+        if (io.d_final) fin.copy(io.d_final, w.d + (size_t)(ms - 1) * w.st_d, w.st_d * sizeof(float));
     } else if (dens_fused) {
         // steps 0 .. ms-2 were advected inside the solver launches; the last one has no launch to ride with
         const float* dprev = ms == 1 ? d0 : w.d + (size_t)(ms - 2) * w.st_d;
         if (int e = sol_density_step(kc, stream, dprev, w.svy + (size_t)(ms - 1) * w.st_vy, w.svx + (size_t)(ms - 1) * w.st_vx, io.inflow,
-                                     io.d_final + (size_t)b0 * w.N)) return e;
+                                     io.d_final)) return e;
     } else if (io.d_final && !dens_ride_bwd) {
         // all saved velocities exist now: the whole density chain is ONE launch (one workgroup per simulation, ~0.3 ms)
         // on the main stream (as a concurrent graph branch it takes 6 CUs away from the 256-workgroup conv launches)
         if (int e = sol_density_chain(kc, stream, ms, d0, w.svy, w.svx, (long)w.st_vy, (long)w.st_vx, io.inflow, nullptr, (long)w.st_d,
-                                      io.d_final + (size_t)b0 * w.N)) return e;
+                                      io.d_final)) return e;
     }
-    if (io.vy_final) fin.copy(io.vy_final + (size_t)b0 * w.nVy, w.vy + (size_t)(ms - 1) * w.st_vy, w.st_vy * sizeof(float));
-    if (io.vx_final) fin.copy(io.vx_final + (size_t)b0 * w.nVx, w.vx + (size_t)(ms - 1) * w.st_vx, w.st_vx * sizeof(float));
+    if (io.vy_final) fin.copy(io.vy_final, w.vy + (size_t)(ms - 1) * w.st_vy, w.st_vy * sizeof(float));
+    if (io.vx_final) fin.copy(io.vx_final, w.vx + (size_t)(ms - 1) * w.st_vx, w.st_vx * sizeof(float));
     if (int e = fin.launch(hs)) return e;
 
     // ---------------- reverse sweep ----------------
@@ -718,14 +663,10 @@ int run_chain(const sol_train_cfg* c, const Ws& w, const Ws& shared, int Btot, i
     int cur = 0;
     const size_t cl32 = w.cells * 32;
     const long seg32 = (long)(11 * cl32);
-    const int CH = pick_bww_chunk(ms);
     // weight gradients of the 32 -> 32 layers ride in the solver-adjoint launches (see k_karman_bwd_bww): 32 rows per workgroup
-    const int FRB = train_fused_rb(c, w, ms);
+    const int FRB = train_fused_rb(c, w);
     const bool fuse = FRB != 0;
     const int wg_per = fuse ? (B * cY) / FRB : 1;
-    const bool use_side = CH < ms && pool()->ok && sol_opt().bww_side;
-    hipStream_t side = pool()->s[7];
-    bool side_used = false;
     for (int i = ms - 1; i >= 0; --i) {
         float* gvy = w.gvy[cur];
         float* gvx = w.gvx[cur];
@@ -745,7 +686,7 @@ int run_chain(const sol_train_cfg* c, const Ws& w, const Ws& shared, int Btot, i
         // the adjoint launch of step i+1 has consumed) -- one launch less per unrolled step.  Otherwise: k_seed, in place on gvy[cur].
         const bool seed_fused = !tr && cX == 64 && sol_opt().seed_fuse;
         if (seed_fused) {
-            if (int e = sol_conv5x5_seed(stream, wn.wb[11], act[10], D[10], B, cY, cX, sl, am(10), vycur, vxcur, gt_vy + (size_t)i * gVy, gt_vx + (size_t)i * gVx,
+            if (int e = sol_conv5x5_seed(stream, w.wb[11], act[10], D[10], B, cY, cX, sl, am(10), vycur, vxcur, gt_vy + (size_t)i * gVy, gt_vx + (size_t)i * gVx,
                                          i == ms - 1 ? nullptr : w.gvy[cur], i == ms - 1 ? nullptr : w.gvx[cur], w.gvy[cur ^ 1], w.gvx[cur ^ 1], dO2,
                                          out_s0(c), out_s1(c), c->std_v0, c->std_v1, 1.f / (float)ms)) return e;
             gvy = w.gvy[cur ^ 1];
@@ -755,46 +696,38 @@ int run_chain(const sol_train_cfg* c, const Ws& w, const Ws& shared, int Btot, i
                                gt_vy + (size_t)i * gVy, gt_vx + (size_t)i * gVx,
                                out_s0(c), out_s1(c), c->std_v0, c->std_v1, 1.f / (float)ms, w.dO4, dO2, i == ms - 1 ? 1 : 0, B, Y, X, tr ? 1 : 0);
             SOL_LAUNCH_CHECK();
-            if (int e = sol_conv5x5_scaled(stream, w.dO4, wn.wb[11], nullptr, nullptr, act[10], D[10], B, cY, cX, 4, 32, SOL_EPI_DLRELU, sl, nullptr, am(10))) return e;
+            if (int e = sol_conv5x5_scaled(stream, w.dO4, w.wb[11], nullptr, nullptr, act[10], D[10], B, cY, cX, 4, 32, SOL_EPI_DLRELU, sl, nullptr, am(10))) return e;
         }
         if (sol_cnn_chain_usable(B, cY, cX)) {
             // the ten backward-data convolutions as ONE persistent launch
             ChainLayer L[10];
             for (int k = 4, n = 0; k >= 0; --k) {
-                L[n++] = ChainLayer{sol_conv_packed_wsh(wn.wb[2 + 2 * k], 32), nullptr, nullptr, act[1 + 2 * k], D[1 + 2 * k], am(1 + 2 * k), SOL_EPI_DLRELU};
-                L[n++] = ChainLayer{sol_conv_packed_wsh(wn.wb[1 + 2 * k], 32), nullptr, D[2 + 2 * k], act[2 * k], D[2 * k], am(2 * k), SOL_EPI_DLRELU};
+                L[n++] = ChainLayer{sol_conv_packed_wsh(w.wb[2 + 2 * k], 32), nullptr, nullptr, act[1 + 2 * k], D[1 + 2 * k], am(1 + 2 * k), SOL_EPI_DLRELU};
+                L[n++] = ChainLayer{sol_conv_packed_wsh(w.wb[1 + 2 * k], 32), nullptr, D[2 + 2 * k], act[2 * k], D[2 * k], am(2 * k), SOL_EPI_DLRELU};
             }
             if (int e = sol_cnn_chain_launch(hs, L, 10, D[10], w.chain_flags + (size_t)(2 * i + 1) * w.chain_words, w.chain_ctl, B, cY, cX, sl)) return e;
         } else
         for (int k = 4; k >= 0; --k) {
             const float* h = act[2 * k];
             const float* a = act[1 + 2 * k];
-            if (int e = sol_conv5x5_scaled(stream, D[2 + 2 * k], wn.wb[2 + 2 * k], nullptr, nullptr, a, D[1 + 2 * k], B, cY, cX, 32, 32, SOL_EPI_DLRELU, sl,
+            if (int e = sol_conv5x5_scaled(stream, D[2 + 2 * k], w.wb[2 + 2 * k], nullptr, nullptr, a, D[1 + 2 * k], B, cY, cX, 32, 32, SOL_EPI_DLRELU, sl,
                                            am(2 + 2 * k), am(1 + 2 * k))) return e;
-            if (int e = sol_conv5x5_scaled(stream, D[1 + 2 * k], wn.wb[1 + 2 * k], nullptr, D[2 + 2 * k], h, D[2 * k], B, cY, cX, 32, 32, SOL_EPI_DLRELU, sl,
+            if (int e = sol_conv5x5_scaled(stream, D[1 + 2 * k], w.wb[1 + 2 * k], nullptr, D[2 + 2 * k], h, D[2 * k], B, cY, cX, 32, 32, SOL_EPI_DLRELU, sl,
                                            am(1 + 2 * k), am(2 * k))) return e;
         }
-        if (i % CH == 0) {
-            // every dz of steps [i, i+CH) is final: their weight gradients go to the side stream
-            const int n = (i + CH <= ms ? CH : ms - i), first = (i + CH >= ms) ? 1 : 0;
-            hipStream_t bs = hs;
-            if (use_side) {
-                SOL_HIP_CHECK(hipEventRecord(pool()->fork, hs));
-                SOL_HIP_CHECK(hipStreamWaitEvent(side, pool()->fork, 0));
-                bs = side;
-                side_used = true;
-            }
+        if (i == 0) {
+            // every dz of all ms steps is final: one weight-gradient launch per layer over the whole unroll
             const float* feat_i = w.feat + (size_t)i * w.cells * 4;
             const float* acts_i = w.acts + (size_t)i * 11 * cl32;
             const float* dz_i = w.dzb + (size_t)i * 11 * cl32;
             // (cin_real = 3: the features are (v_y, v_x, Re) + one zero channel, whose gradient rows the thin kernel then skips)
-            if (int e = sol_bww_batched(bs, feat_i, dz_i, w.part[0], n, CH, first, (long)(w.cells * 4), seg32, B, cY, cX, 4, 32, nullptr, nullptr, 0, 0, 3)) return e;
+            if (int e = sol_bww_batched(hs, feat_i, dz_i, w.part[0], ms, ms, 1, (long)(w.cells * 4), seg32, B, cY, cX, 4, 32, nullptr, nullptr, 0, 0, 3)) return e;
             const long amseg = 11 * SOL_AMAX_SLOTS;      // absmax slots: [step][11][SOL_AMAX_SLOTS]
             for (int l = 1; l <= 10 && !fuse; ++l)
-                if (int e = sol_bww_batched(bs, acts_i + (size_t)(l - 1) * cl32, dz_i + (size_t)l * cl32, w.part[l], n, CH, first, seg32, seg32, B, cY, cX, 32, 32,
+                if (int e = sol_bww_batched(hs, acts_i + (size_t)(l - 1) * cl32, dz_i + (size_t)l * cl32, w.part[l], ms, ms, 1, seg32, seg32, B, cY, cX, 32, 32,
                                             w.amax_act + ((size_t)i * 11 + (l - 1)) * SOL_AMAX_SLOTS, w.amax_dz + ((size_t)i * 11 + l) * SOL_AMAX_SLOTS,
                                             amseg, amseg)) return e;
-            if (int e = sol_bww_batched(bs, acts_i + (size_t)10 * cl32, w.dO2 + (size_t)i * w.cells * 2, w.part[11], n, CH, first, seg32, (long)(w.cells * 2), B, cY, cX, 32, 2)) return e;
+            if (int e = sol_bww_batched(hs, acts_i + (size_t)10 * cl32, w.dO2 + (size_t)i * w.cells * 2, w.part[11], ms, ms, 1, seg32, (long)(w.cells * 2), B, cY, cX, 32, 2)) return e;
         }
         BwArgs jobs[10];
         if (fuse) {       // this step's dz tensors are complete: one job per 32 -> 32 layer
@@ -808,101 +741,73 @@ int run_chain(const sol_train_cfg* c, const Ws& w, const Ws& shared, int Btot, i
         if (dens_ride_bwd) {          // density advection s = ms - 1 - i (forward order) rides in this step's launch
             const int sd = ms - 1 - i;
             ride = SolDensRide{sd == 0 ? d0 : w.d + (size_t)(sd - 1) * w.st_d, w.svy + (size_t)sd * w.st_vy, w.svx + (size_t)sd * w.st_vx, io.inflow,
-                               sd == ms - 1 ? io.d_final + (size_t)b0 * w.N : w.d + (size_t)sd * w.st_d};
+                               sd == ms - 1 ? io.d_final : w.d + (size_t)sd * w.st_d};
         }
         if (i > 0) {
-            if (int e = sol_conv5x5_scaled(stream, D[0], wn.wb[0], nullptr, nullptr, nullptr, w.dF, B, cY, cX, 32, 2, SOL_EPI_NONE, sl, am(0), nullptr)) return e;
+            if (int e = sol_conv5x5_scaled(stream, D[0], w.wb[0], nullptr, nullptr, nullptr, w.dF, B, cY, cX, 32, 2, SOL_EPI_NONE, sl, am(0), nullptr)) return e;
             const float* dF = w.dF;
             FeatOrder feat_order(tr);       // the adjoint reads the feature gradient in the CNN's (transposed) cell order
             if (int e = sol_karman_step_bwd_fused(kc, stream, w.svy + (size_t)i * w.st_vy, w.svx + (size_t)i * w.st_vx, re, io.active,
                                                   bcm, io.bc_stride, gvy, gvx, dF, fscale, seed_fused ? w.gvy[cur] : w.gvy[cur ^ 1], seed_fused ? w.gvx[cur] : w.gvx[cur ^ 1],
-                                                  io.iters_bwd ? io.iters_bwd + (size_t)i * Btot + b0 : nullptr,
+                                                  io.iters_bwd ? io.iters_bwd + (size_t)i * B : nullptr,
                                                   jobs, fuse ? 10 : 0, wg_per, dens_ride_bwd ? &ride : nullptr)) return e;
             if (!seed_fused) cur ^= 1;        // (seed fused: G lives in gvy[cur ^ 1], the adjoint's output goes back to gvy[cur] -- no toggle)
         } else if (fuse) {
             if (int e = sol_bww_jobs_launch(stream, jobs, 10, wg_per, kc, dens_ride_bwd ? &ride : nullptr)) return e;     // step 0 has no adjoint to ride with
         }
     }
-    if (side_used) {      // join the side stream
-        SOL_HIP_CHECK(hipEventRecord(pool()->join[7], side));
-        SOL_HIP_CHECK(hipStreamWaitEvent(hs, pool()->join[7], 0));
-    }
     return SOL_OK;
 }
 
 int train_fwd_bwd_impl(const sol_train_cfg* cfg, hipStream_t hs, const TrainIO& io, void* workspace, size_t workspace_bytes, float* grads) {
     const int B = cfg->karman.B, Y = cfg->karman.Y, X = cfg->karman.X, ms = cfg->msteps;
-    const int S = pick_chains(B);
-    sol_train_cfg sub = *cfg;
-    sub.karman.B = B / S;
-    Ws w[8];
-    const size_t sub_bytes = carve_ws(&sub, nullptr, w[0], true);
-    if (workspace_bytes < sub_bytes * S)
-        return sol_set_error(SOL_ERR_WORKSPACE, "workspace too small: %zu < %zu bytes", workspace_bytes, sub_bytes * S);
-    for (int k = 0; k < S; ++k) carve_ws(&sub, reinterpret_cast<float*>(static_cast<char*>(workspace) + k * sub_bytes), w[k], true);
+    Ws w;
+    const size_t need = carve_ws(cfg, static_cast<float*>(workspace), w, true);
+    if (workspace_bytes < need)
+        return sol_set_error(SOL_ERR_WORKSPACE, "workspace too small: %zu < %zu bytes", workspace_bytes, need);
     if (int e = sol_init_karman_kernels()) return e;
     if (int e = sol_init_conv_kernels()) return e;
-    StreamPool* sp = pool();
-    if (S > 1 && !sp->ok) return sol_set_error(SOL_ERR_HIP, "could not create the internal HIP streams/events");
 
-    if (int e = pack_all(cfg, hs, io.params, w[0], true)) return e;
-    for (int k = 0; k < S; ++k) {
-        MemList z;
-        if (k == 0) z.zero(io.iters_bwd, B * sizeof(int32_t));                       // step 0 needs no adjoint  (io.loss_steps: every entry is written by k_loss_finish)
-        z.zero(w[k].dO4, w[k].cells * 4 * sizeof(float));
-        if (k == 0) z.zero(w[0].loss_acc, (size_t)ms * SOL_LOSS_ACC_WORDS * sizeof(unsigned long long));   // every chain adds into chain 0's accumulators
-        z.zero(w[k].amax_act, 2 * w[k].amax_words * sizeof(uint32_t));                 // activation + gradient absmax slots
-        if (sol_karman_fwd_bands_usable(&sub.karman)) z.zero(w[k].xchg, w[k].xchg_words * sizeof(uint32_t));   // (the launches restore the zeros themselves; this covers an aborted step)
-        const bool chain = sol_cnn_chain_usable(sub.karman.B, cnn_transposed(Y, X) ? X : Y, cnn_transposed(Y, X) ? Y : X);
-        // hand-off regions of the persistent CNN launches: zero ONCE (tag 0 = "never written"); afterwards the tags do the work
-        if (chain) z.zero_once(w[k].chain_flags, (size_t)ms * 2 * w[k].chain_words * sizeof(uint32_t), w[k].chain_ctl + 1, w[k].chain_magic);
-        if (int e = z.launch(hs)) return e;
-        if (chain) {
-            SOL_LAUNCH(k_chain_tick, dim3(1), dim3(64), 0, hs, w[k].chain_ctl, w[k].chain_magic);
-            SOL_LAUNCH_CHECK();
-        }
-    }
-    if (S == 1) {
-        if (int e = run_chain(&sub, w[0], w[0], B, 0, hs, io)) return e;
-    } else {
-        SOL_HIP_CHECK(hipEventRecord(sp->fork, hs));
-        for (int k = 0; k < S; ++k) {
-            SOL_HIP_CHECK(hipStreamWaitEvent(sp->s[k], sp->fork, 0));
-            if (int e = run_chain(&sub, w[k], w[0], B, k * (B / S), sp->s[k], io)) return e;
-            SOL_HIP_CHECK(hipEventRecord(sp->join[k], sp->s[k]));
-            SOL_HIP_CHECK(hipStreamWaitEvent(hs, sp->join[k], 0));
-        }
-    }
-    SOL_LAUNCH(k_loss_finish, dim3((ms + 63) / 64), dim3(64), 0, hs, (const unsigned long long*)w[0].loss_acc, io.loss_steps, ms);
-    SOL_LAUNCH_CHECK();
-    // all twelve layers of a chain in two launches (chain k > 0 accumulates onto chain k-1: one pair of launches per chain)
+    if (int e = pack_all(cfg, hs, io.params, w, true)) return e;
+    MemList z;
+    z.zero(io.iters_bwd, B * sizeof(int32_t));                       // step 0 needs no adjoint  (io.loss_steps: every entry is written by k_loss_finish)
+    z.zero(w.dO4, w.cells * 4 * sizeof(float));
+    z.zero(w.loss_acc, (size_t)ms * SOL_LOSS_ACC_WORDS * sizeof(unsigned long long));
+    z.zero(w.amax_act, 2 * w.amax_words * sizeof(uint32_t));                 // activation + gradient absmax slots
+    if (sol_karman_fwd_bands_usable(&cfg->karman)) z.zero(w.xchg, w.xchg_words * sizeof(uint32_t));   // (the launches restore the zeros themselves; this covers an aborted step)
     const bool trn = cnn_transposed(Y, X);
-    const int fused_rb = train_fused_rb(&sub, w[0], ms);
-    for (int k = 0; k < S; ++k) {
-        float *part[NL], *dw[NL], *db[NL];
-        int rows[NL], rbs[NL], cins[NL], couts[NL];
-        for (int l = 0; l < NL; ++l) {
-            const int cin = layer_cin(l), cout = layer_cout(l);
-            const int64_t koff = layer_koff(l), boff = koff + 25 * cin * cout;
-            const bool fused = l >= 1 && l <= 10 && fused_rb != 0;
-            part[l] = w[k].part[l]; dw[l] = grads + koff; db[l] = grads + boff; cins[l] = cin; couts[l] = cout;
-            rows[l] = (fused ? 1 : pick_bww_chunk(ms)) * (B / S) * (trn ? X : Y);
-            rbs[l] = fused ? fused_rb : 0;
-        }
-        if (int e = sol_bww_reduce_layers(hs, NL, part, dw, db, rows, rbs, cins, couts, k > 0 ? 1 : 0, trn ? 1 : 0)) return e;
+    const bool chain = sol_cnn_chain_usable(B, trn ? X : Y, trn ? Y : X);
+    // hand-off regions of the persistent CNN launches: zero ONCE (tag 0 = "never written"); afterwards the tags do the work
+    if (chain) z.zero_once(w.chain_flags, (size_t)ms * 2 * w.chain_words * sizeof(uint32_t), w.chain_ctl + 1, w.chain_magic);
+    if (int e = z.launch(hs)) return e;
+    if (chain) {
+        SOL_LAUNCH(k_chain_tick, dim3(1), dim3(64), 0, hs, w.chain_ctl, w.chain_magic);
+        SOL_LAUNCH_CHECK();
     }
-    return SOL_OK;
+    if (int e = unrolled_step(cfg, w, hs, io)) return e;
+    SOL_LAUNCH(k_loss_finish, dim3((ms + 63) / 64), dim3(64), 0, hs, (const unsigned long long*)w.loss_acc, io.loss_steps, ms);
+    SOL_LAUNCH_CHECK();
+    // all twelve layers in two launches
+    const int fused_rb = train_fused_rb(cfg, w);
+    float *part[NL], *dw[NL], *db[NL];
+    int rows[NL], rbs[NL], cins[NL], couts[NL];
+    for (int l = 0; l < NL; ++l) {
+        const int cin = layer_cin(l), cout = layer_cout(l);
+        const int64_t koff = layer_koff(l), boff = koff + 25 * cin * cout;
+        const bool fused = l >= 1 && l <= 10 && fused_rb != 0;
+        part[l] = w.part[l]; dw[l] = grads + koff; db[l] = grads + boff; cins[l] = cin; couts[l] = cout;
+        rows[l] = (fused ? 1 : ms) * B * (trn ? X : Y);
+        rbs[l] = fused ? fused_rb : 0;
+    }
+    return sol_bww_reduce_layers(hs, NL, part, dw, db, rows, rbs, cins, couts, 0, trn ? 1 : 0);
 }
 
 }  // namespace
 
 extern "C" size_t sol_train_workspace_bytes(const sol_train_cfg* cfg) {
     if (!cfg || cfg->karman.B < 1) return 0;
-    const int S = pick_chains(cfg->karman.B);
-    sol_train_cfg sub = *cfg;
-    sub.karman.B = cfg->karman.B / S;
     Ws w;
-    return carve_ws(&sub, nullptr, w, true) * S;
+    return carve_ws(cfg, nullptr, w, true);
 }
 
 extern "C" int sol_train_fwd_bwd(const sol_train_cfg* cfg, void* stream, const float* params,
@@ -1089,7 +994,6 @@ extern "C" int sol_train_graph_create(const sol_train_cfg* cfg, const float* par
                 workspace && grads && loss_steps && out, "sol_train_graph_create: NULL pointer argument");
     if (int e = sol_init_karman_kernels()) return e;
     if (int e = sol_init_conv_kernels()) return e;
-    if (!pool()->ok) return sol_set_error(SOL_ERR_HIP, "could not create the internal HIP streams/events");
     TrainIO io{params, d0, vy0, vx0, re, active, inflow, velBCy, velBCyMask, gt_vy, gt_vx, bc_batch_stride,
                loss_steps, d_final, vy_final, vx_final, iters_fwd, iters_bwd};
     hipStream_t cs;
@@ -1114,19 +1018,7 @@ extern "C" int sol_train_graph_create(const sol_train_cfg* cfg, const float* par
 
 extern "C" int sol_train_graph_launch(sol_train_graph* g, void* stream) {
     SOL_REQUIRE(g && g->exec, "sol_train_graph_launch: NULL graph");
-    hipStream_t s = (hipStream_t)stream;
-    if (sol_opt().graph_stream) {
-        // replay on an internal non-blocking stream, fenced against the caller's stream with two events
-        StreamPool* sp = pool();
-        SOL_REQUIRE(sp->ok, "internal streams unavailable");
-        SOL_HIP_CHECK(hipEventRecord(sp->fork, s));
-        SOL_HIP_CHECK(hipStreamWaitEvent(sp->s[6], sp->fork, 0));
-        SOL_HIP_CHECK(hipGraphLaunch(g->exec, sp->s[6]));
-        SOL_HIP_CHECK(hipEventRecord(sp->join[6], sp->s[6]));
-        SOL_HIP_CHECK(hipStreamWaitEvent(s, sp->join[6], 0));
-        return SOL_OK;
-    }
-    SOL_HIP_CHECK(hipGraphLaunch(g->exec, s));
+    SOL_HIP_CHECK(hipGraphLaunch(g->exec, (hipStream_t)stream));
     return SOL_OK;
 }
 

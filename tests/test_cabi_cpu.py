@@ -118,7 +118,7 @@ def test_options_table_and_abi_checks(lib):
     kc, bc, tc = C.c_int32(), C.c_int32(), C.c_int32()
     assert lib.sol_abi_sizes(C.byref(kc), C.byref(bc), C.byref(tc)) == 0
     assert (kc.value, bc.value, tc.value) == (C.sizeof(_lib.KarmanCfg), C.sizeof(_lib.BurgersCfg), C.sizeof(_lib.TrainCfg))
-    defaults = {"conv_precision": 0, "cnn_persistent": 0, "bww_fuse": 1, "correct_fuse": 1, "density_mode": 0, "streams": 1, "bww_chunk": 0}
+    defaults = {"conv_precision": 0, "cnn_persistent": 0, "bww_fuse": 1, "correct_fuse": 1, "density_mode": 0}
     for k, v in defaults.items():
         if not any(os.environ.get(e) for e, (o_, _) in _lib._ENV_OPTIONS.items() if o_ == k):
             assert _lib.get_option(k) == v, k
@@ -128,12 +128,28 @@ def test_options_table_and_abi_checks(lib):
     with pytest.raises(sol_amd.SolError, match="unknown option"):
         _lib.set_option("bogus", 1)
     with pytest.raises(sol_amd.SolError, match="must be in"):
-        _lib.set_option("streams", 99)
-    # no getenv left in the library sources
+        _lib.set_option("density_mode", 9)
+    # the retired trainer experiments (stream chains, chunked side-stream weight gradient, replay stream) are unknown names now
+    for name in ("streams", "bww_chunk", "bww_side", "graph_stream"):
+        with pytest.raises(sol_amd.SolError, match="unknown option"):
+            _lib.set_option(name, 1)
+        with pytest.raises(sol_amd.SolError, match="unknown option"):
+            _lib.get_option(name)
+    for env in ("SOL_STREAMS", "SOL_BWW_CHUNK", "SOL_BWW_NO_SIDE"):
+        assert env not in _lib._ENV_OPTIONS and env not in _lib._ENV_INT_OPTIONS, env
+    # no getenv left in the library sources, and one stream creation: the capture stream of sol_train_graph_create
     csrc = os.path.join(os.path.dirname(sol_amd.__file__), "csrc")
+    streams_created = 0
     for f in os.listdir(csrc):
         with open(os.path.join(csrc, f)) as fh:
-            assert "getenv" not in fh.read(), f
+            text = fh.read()
+        assert "getenv" not in text, f
+        streams_created += text.count("hipStreamCreate")
+    assert streams_created == 1
+    # the training workspace of the two trainer shapes of tools/lib_bitcompare.py: the layout did not move when the chains went
+    for (B, Y, X, ms), nbytes in (((6, 128, 64, 32), 4889875456), ((3, 64, 32, 4), 134179328)):
+        tc = _lib.TrainCfg(ops.karman_cfg(B, Y, X, 1.5625), ms, 0.2, 0.2, 1.0, 0.3)
+        assert lib.sol_train_workspace_bytes(C.byref(tc)) == nbytes, (B, Y, X, ms)
 
 
 def test_sol32_fixture_is_the_bench_workload(golden_dir):
