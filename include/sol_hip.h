@@ -265,7 +265,7 @@ int sol_karman_step_bwd(const sol_karman_cfg* cfg, void* stream,
  *   (for v_y rows) ... see sol_burgers_cfg; then v += dt*f.
  * ---------------------------------------------------------------------------------- */
 typedef struct sol_burgers_cfg {
-    int32_t B, Y, X;        /* cells; staggered arrays v_y [B,Y+1,X], v_x [B,Y,X+1]  (<= 64) */
+    int32_t B, Y, X;        /* cells; staggered arrays v_y [B,Y+1,X], v_x [B,Y,X+1]  (<= 64; *_large: <= 1024) */
     float dx, dt;
 } sol_burgers_cfg;
 
@@ -285,13 +285,28 @@ int sol_burgers_step_bwd(const sol_burgers_cfg* cfg, void* stream,
                          const float* g_vy_out, const float* g_vx_out,
                          float* g_vy_in, float* g_vx_in);
 
-/* Forward-only Burgers step for grids beyond the one-workgroup kernels (up to 1024 x 1024): the reference generates its
- * training data at 128 x 128 (burgers/Makefile:19-29, `burgers.py -r 128`; PhiFlow Burgers.step on the CPU there).  Same
- * arguments as sol_burgers_step_fwd plus a workspace of sol_burgers_step_large_workspace_bytes(cfg).  Not differentiable. */
+/* Burgers step for grids beyond the one-workgroup kernels (up to 1024 x 1024): the reference generates its training data at
+ * 128 x 128 (burgers/Makefile:19-29, `burgers.py -r 128`; PhiFlow Burgers.step on the CPU there).  Same arguments as
+ * sol_burgers_step_fwd plus a workspace of sol_burgers_step_large_workspace_bytes(cfg).  The step's input velocity is what its
+ * adjoint, sol_burgers_step_bwd_large below, takes. */
 size_t sol_burgers_step_large_workspace_bytes(const sol_burgers_cfg* cfg);
 int sol_burgers_step_fwd_large(const sol_burgers_cfg* cfg, void* stream, const float* vy_in, const float* vx_in,
                                const float* f_y, const float* f_x, const float* circ_yp1, const float* circ_x,
                                const float* circ_y, const float* circ_xp1, float* vy_out, float* vx_out,
+                               void* workspace, size_t workspace_bytes);
+
+/* Adjoint of sol_burgers_step_fwd_large with respect to the input velocity (d f = dt * g_out is the caller's): arguments as
+ * sol_burgers_step_bwd plus a workspace.  Seven kernel launches on `stream` and nothing else (no memset / memcpy, no host
+ * synchronisation), so the call can be captured: clear, the forward's four circulant products on the cotangent (the circulants are
+ * symmetric), the advection adjoint as an order-independent scatter in 64-bit fixed point (bit-reproducible; a non-finite cotangent
+ * makes every input gradient of ITS simulation NaN), conversion to fp32.  B <= 65535, 2 <= Y, X <= 1024; g_vy_in / g_vx_in must not
+ * alias the inputs.  With F = (Y+1) X + Y (X+1) faces and r(n) = n rounded up to a multiple of 256, the workspace is
+ * r(8 B F) + 2 r(4 B F) + r(256 B) + 256 bytes (accumulators, g_a, one product, absmax slots, alignment of `workspace`);
+ * sol_burgers_step_bwd_large_workspace_bytes returns 0 for a cfg the adjoint does not take. */
+size_t sol_burgers_step_bwd_large_workspace_bytes(const sol_burgers_cfg* cfg);
+int sol_burgers_step_bwd_large(const sol_burgers_cfg* cfg, void* stream, const float* vy_in, const float* vx_in,
+                               const float* circ_yp1, const float* circ_x, const float* circ_y, const float* circ_xp1,
+                               const float* g_vy_out, const float* g_vx_out, float* g_vy_in, float* g_vx_in,
                                void* workspace, size_t workspace_bytes);
 
 /* ------------------------------------------------------------------------------------

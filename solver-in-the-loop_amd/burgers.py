@@ -21,14 +21,30 @@ def to_feature_noforce(smokestates):
     return torch.cat([s.velocity.staggered_tensor()[:, :-1, :-1, 0:2] for s in smokestates], dim=-1)
 
 
-class BurgersTest:
-    """BurgersTest(Burgers): step(v, dt) / step_with_f(v, f, dt); viscosity = default_viscosity = 0.1."""
+def _ws_key(B, Y, X, device):
+    """key of a reserved large-grid workspace: the device by type and INDEX ("cuda" and "cuda:0" are one device)"""
+    d = torch.device(device)
+    return (int(B), int(Y), int(X), d.type, torch.cuda.current_device() if d.type == "cuda" and d.index is None else d.index)
 
-    def __init__(self, default_viscosity=0.1, viscosity=None, diffusion_substeps=1):
+
+class BurgersTest:
+    """BurgersTest(Burgers): step(v, dt) / step_with_f(v, f, dt); viscosity = default_viscosity = 0.1.
+    large_grid_grad: on grids beyond the one-workgroup kernels (max(Y, X) > ops.BURGERS_LDS_MAX) the step is differentiable only when this
+    is True (ops.burgers_step_large with its adjoint); the default refuses a step whose input requires a gradient there."""
+
+    def __init__(self, default_viscosity=0.1, viscosity=None, diffusion_substeps=1, large_grid_grad=False):
         if diffusion_substeps != 1:
             raise NotImplementedError("the periodic (spectral) diffusion has no substeps")
         self.viscosity = default_viscosity if viscosity is None else viscosity
-        self._circ = {}
+        self.large_grid_grad = bool(large_grid_grad)
+        self._circ, self._ws = {}, {}
+
+    def reserve(self, B, Y, X, device):
+        """Allocates the large-grid step's workspace for this shape now (both directions): a trainer / roll-out that captures its step
+        calls this at construction, so the captured launches see a static address.  No-op on one-workgroup grids."""
+        if max(Y, X) > ops.BURGERS_LDS_MAX and _ws_key(B, Y, X, device) not in self._ws:
+            nbytes = ops.burgers_large_workspace_bytes(BurgersCfg(B, Y, X, 1.0, 1.0))
+            self._ws[_ws_key(B, Y, X, device)] = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=device)
 
     def _run(self, v, f, dt):
         Y, X = v.domain.resolution
@@ -45,10 +61,16 @@ class BurgersTest:
             fy = f.velocity.data[0].data.reshape(B, Y + 1, X)
             fx = f.velocity.data[1].data.reshape(B, Y, X + 1)
         if max(Y, X) > ops.BURGERS_LDS_MAX:
-            # beyond the one-workgroup kernels (data generation at the reference's 128 x 128): forward-only multi-workgroup path
-            if torch.is_grad_enabled() and (vy.requires_grad or vx.requires_grad):
-                raise NotImplementedError("the large-grid Burgers step (%dx%d) is forward only" % (Y, X))
-            oy, ox = ops.burgers_step_large(vy, vx, fy, fx, cfg, self._circ[key])
+            # beyond the one-workgroup kernels (the reference's 128 x 128 data): the multi-workgroup step
+            if not self.large_grid_grad and torch.is_grad_enabled() and (vy.requires_grad or vx.requires_grad):
+                raise NotImplementedError("the large-grid Burgers step (%dx%d) is differentiable on request: construct "
+                                          "BurgersTest(large_grid_grad=True)" % (Y, X))
+            ws = self._ws.get(_ws_key(B, Y, X, vy.device))
+            if self.large_grid_grad:
+                oy, ox = ops.burgers_step_large(vy, vx, fy, fx, cfg, self._circ[key], ws)
+            else:
+                with torch.no_grad():
+                    oy, ox = ops.burgers_step_large(vy, vx, fy, fx, cfg, self._circ[key], ws)
         else:
             oy, ox = ops.burgers_step(vy, vx, fy, fx, cfg, self._circ[key])
         return v.copied_with(velocity=StaggeredGrid([oy.reshape(B, Y + 1, X, 1), ox.reshape(B, Y, X + 1, 1)], v.velocity.box))
@@ -135,6 +157,15 @@ def randfreq(shape, rng, power=8):
     return f / (f.std() + 1e-30)
 
 
+def _check_net_shape(who, Y, X):
+    """The shapes the correction network's launches take for H = Y, W = X (sol_conv5x5, sol_conv5x5_bwd_weight): refused here, at
+    construction, instead of by the first convolution of the first step."""
+    if not ((X <= 64 and 64 % X == 0 and Y % (64 // X) == 0) or (X > 64 and X % 64 == 0)) or Y < 2 or X < 2 or max(Y, X) > 1024:
+        raise _lib.SolError("%s: resolution %dx%d is not supported: the network's convolutions take rows of X <= 64 cells with 64 %% X == 0 "
+                            "and Y %% (64 / X) == 0, or rows wider than 64 cells that are a multiple of 64 cells wide; 2 <= Y, X <= 1024"
+                            % (who, Y, X))
+
+
 # ---- fused trainer: the whole unrolled step (burgers_train.py:379-437) as ONE hipGraph ----------------------------------
 class BurgersTrainer:
     """Unrolled solver-in-the-loop training step of the Burgers path (/root/reference/burgers/burgers_train.py:379-437):
@@ -158,8 +189,14 @@ class BurgersTrainer:
         self.schedule, self._sched = schedule, None
         self.net, self.dom, self.B, self.ms, self.dt, self.noforce = net, domain, int(batch_size), int(msteps), float(dt), bool(noforce)
         dev = net.params.device
-        Y, X = domain.resolution
-        self.sim = BurgersTest(default_viscosity=viscosity)
+        Y, X = (int(n) for n in domain.resolution)
+        _check_net_shape("BurgersTrainer", Y, X)
+        self.large = max(Y, X) > ops.BURGERS_LDS_MAX          # beyond the one-workgroup kernels: sol_burgers_step_fwd_large / _bwd_large
+        self.sim = BurgersTest(default_viscosity=viscosity, large_grid_grad=True)
+        if self.large:
+            _lib.require_gpu()
+            self.sim.reserve(self.B, Y, X, dev)               # autograd schedule: the steps' workspace; manual schedule: self._ws below
+            self._ws = self.sim._ws[_ws_key(self.B, Y, X, dev)]
         self.std_v = torch.as_tensor(std_v, dtype=torch.float32, device=dev).reshape(2)
         self._std_v_host = tuple(float(v) for v in np.asarray(std_v, dtype=np.float64).reshape(2))
         if noforce:
@@ -185,7 +222,9 @@ class BurgersTrainer:
             fr = None if self.noforce else F.BurgersVelocitySMAC(self.dom, velocity=self.forc[k], batch_size=self.B)
             st = self.sim.step(st, dt=self.dt) if self.noforce else self.sim.step_with_f(st, fr, dt=self.dt)
             feat = to_feature_noforce([st]) if self.noforce else to_feature([st], [fr])
-            corr = to_staggered(self.net(feat / self.std_in) * self.std_v, self.dom.box)
+            # (large grids, scaled=True: the forward launches of the manual schedule on rows that are a multiple of 64 pixels wide, so both
+            #  schedules see the same activations and LeakyReLU masks there; the one-workgroup grids keep ops.conv5x5 as before)
+            corr = to_staggered(self.net(feat / self.std_in, scaled=self.large) * self.std_v, self.dom.box)
             st = st.copied_with(velocity=st.velocity + corr)
             # l2_loss((gt.staggered - prd.staggered) / std_v), burgers_train.py:421-428, channel by channel: one kernel per step, no torch
             # reduction (a multi-workgroup torch .sum() puts a memset node into the captured graph: ops.L2LossFn)
@@ -195,7 +234,8 @@ class BurgersTrainer:
 
     def _schedule_step(self):
         """burgers_train.py:379-437 differentiated by hand.  Forward, per unrolled step k: sol_burgers_step_fwd on (v, f_k) (the step's INPUT
-        velocity is what its adjoint needs) -> features = (v, f_k at the low faces) / std_in -> the network's forward launches
+        velocity is what its adjoint needs; sol_burgers_step_fwd_large / _bwd_large with the workspace of the constructor on
+        domains beyond the one-workgroup kernels) -> features = (v, f_k at the low faces) / std_in -> the network's forward launches
         (schedule2d.NetSchedule2D) -> v += std_v * to_staggered(out) -> loss_k and d loss_k / d v_k in one pass over the padded staggered
         tensors (sol_l2_loss_fwd_bwd; the padding only adds the constant the reference's l2_loss sees there).  Reverse, k = n-1 .. 0:
         G = d loss_k / d v_k + (adjoint of step k+1) -> d out = std_v * G at the corrected faces -> network reverse sweep (weight gradients
@@ -218,8 +258,12 @@ class BurgersTrainer:
             if not self.noforce:
                 fy, fx = self.forc[k][:, :, :X, 0].contiguous(), self.forc[k][:, :Y, :, 1].contiguous()
             oy, ox = torch.empty_like(vy), torch.empty_like(vx)
-            check(lib.sol_burgers_step_fwd(C.byref(cfg), stream(), ptr(vy), ptr(vx), ptr(fy), ptr(fx), ptr(circ[0]), ptr(circ[1]), ptr(circ[2]), ptr(circ[3]),
-                                           ptr(oy), ptr(ox)))
+            if self.large:
+                check(lib.sol_burgers_step_fwd_large(C.byref(cfg), stream(), ptr(vy), ptr(vx), ptr(fy), ptr(fx), ptr(circ[0]), ptr(circ[1]), ptr(circ[2]),
+                                                     ptr(circ[3]), ptr(oy), ptr(ox), ptr(self._ws), self._ws.numel() * 4))
+            else:
+                check(lib.sol_burgers_step_fwd(C.byref(cfg), stream(), ptr(vy), ptr(vx), ptr(fy), ptr(fx), ptr(circ[0]), ptr(circ[1]), ptr(circ[2]),
+                                               ptr(circ[3]), ptr(oy), ptr(ox)))
             chans = [oy[:, :Y], ox[:, :, :X]]
             if not self.noforce:
                 chans += [fy[:, :Y], fx[:, :, :X]]
@@ -245,8 +289,12 @@ class BurgersTrainer:
             G[0][:, :Y].add_(dx[..., 0], alpha=1.0 / sin[0])
             G[1][:, :, :X].add_(dx[..., 1], alpha=1.0 / sin[1])
             oy, ox = torch.empty_like(iy), torch.empty_like(ix)
-            check(lib.sol_burgers_step_bwd(C.byref(cfg), stream(), ptr(iy), ptr(ix), ptr(circ[0]), ptr(circ[1]), ptr(circ[2]), ptr(circ[3]),
-                                           ptr(G[0]), ptr(G[1]), ptr(oy), ptr(ox)))
+            if self.large:
+                check(lib.sol_burgers_step_bwd_large(C.byref(cfg), stream(), ptr(iy), ptr(ix), ptr(circ[0]), ptr(circ[1]), ptr(circ[2]), ptr(circ[3]),
+                                                     ptr(G[0]), ptr(G[1]), ptr(oy), ptr(ox), ptr(self._ws), self._ws.numel() * 4))
+            else:
+                check(lib.sol_burgers_step_bwd(C.byref(cfg), stream(), ptr(iy), ptr(ix), ptr(circ[0]), ptr(circ[1]), ptr(circ[2]), ptr(circ[3]),
+                                               ptr(G[0]), ptr(G[1]), ptr(oy), ptr(ox)))
             gin = (oy, ox)
             keep[k] = None
         _lib.dcopy_(self.loss, _lib.stack0(losses).sum() / ms)
@@ -321,8 +369,9 @@ class BurgersRollout:
         _lib.require_gpu()
         self.net, self.dom, self.B, self.dt, self.noforce = net, domain, int(batch_size), float(dt), bool(noforce)
         dev = net.params.device
-        Y, X = domain.resolution
+        Y, X = (int(n) for n in domain.resolution)
         self.sim = BurgersTest(default_viscosity=viscosity)
+        self.sim.reserve(self.B, Y, X, dev)         # large grids: the step's workspace, a static address under capture
         self.std_v = torch.as_tensor(std_v, dtype=torch.float32, device=dev).reshape(2)
         self.std_in = self.std_v if noforce else torch.cat([self.std_v, torch.as_tensor(std_f, dtype=torch.float32, device=dev).reshape(2)])
         z = lambda: torch.zeros(self.B, Y + 1, X + 1, 2, dtype=torch.float32, device=dev)

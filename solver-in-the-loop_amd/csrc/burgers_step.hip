@@ -9,7 +9,7 @@
 // host (out = Cy * f * Cx^T): no FFT library, and the adjoint is the same operator.
 // PhiFlow-1.x quirk kept on purpose: the periodic staggered
 // components keep the duplicated +1 face and every wrap-around is modulo the ARRAY length.
-#include "common.hpp"
+#include "fixed_scatter.hpp"
 
 namespace {
 
@@ -232,10 +232,10 @@ __global__ void __launch_bounds__(NT) k_burgers_bwd(BArgs a) {
 }
 
 // ------------------------------------------------------------------------------------
-// Large grids (forward only): the reference generates its Burgers training data at 128 x 128 (burgers/Makefile:19-29,
-// `burgers.py -r 128`), beyond the one-workgroup-in-LDS kernels above.  Same arithmetic on global memory with the whole chip:
-// one launch for the advection, two tiled products for the separable circulant diffusion per component, force added by the
-// second.  Not differentiable (the reference does not train through its hi-res data either).
+// Large grids: the reference generates its Burgers training data at 128 x 128 (burgers/Makefile:19-29, `burgers.py -r 128`), beyond
+// the one-workgroup-in-LDS kernels above.  Same arithmetic on global memory with the whole chip: one launch for the advection, two
+// tiled products for the separable circulant diffusion per component, force added by the second.  The adjoint follows the forward
+// kernels below (sol_burgers_step_bwd_large): the same products on the cotangent, then an order-independent fixed-point scatter.
 // ------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) k_burgers_adv_large(int B, int Y, int X, float dtdx, const float* __restrict__ vy_in,
                                                            const float* __restrict__ vx_in, float* __restrict__ ay, float* __restrict__ ax) {
@@ -269,9 +269,11 @@ __global__ void __launch_bounds__(256) k_burgers_adv_large(int B, int Y, int X, 
 //   SIDE 0:  out[j][i] = sum_k in[j][k] * R[i][k]          (in [H][W], R [W][W])
 //   SIDE 1:  out[j][i] = sum_k Lm[j][k] * in[k][i] (+ dt f) (Lm [H][H], in [H][W])
 // summed over k in ascending order like diffuse2 above (same rounding as the one-workgroup kernel).
-template <int SIDE>
+// PUB (the adjoint's last product per component): also publishes max|out| of simulation b into gmax[b][FX_SLOTS] (fixed_scatter.hpp).
+template <int SIDE, bool PUB = false>
 __global__ void __launch_bounds__(256) k_burgers_circ_large(int H, int W, const float* __restrict__ in, const float* __restrict__ M,
-                                                            float* __restrict__ out, const float* __restrict__ f, float dt) {
+                                                            float* __restrict__ out, const float* __restrict__ f, float dt,
+                                                            unsigned* __restrict__ gmax = nullptr) {
     __shared__ float ta[16][17], tb[16][17];
     const int b = blockIdx.z, tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
     const int i = blockIdx.x * 16 + tx, j = blockIdx.y * 16 + ty;
@@ -296,6 +298,145 @@ __global__ void __launch_bounds__(256) k_burgers_circ_large(int H, int W, const 
         const size_t o = (size_t)b * H * W + (size_t)j * W + i;
         out[o] = (SIDE == 1 && f) ? s + dt * f[o] : s;
     }
+    if constexpr (PUB) {
+        const bool in_range = i < W && j < H;
+        const float a = in_range ? fabsf(s) : 0.f;
+        fx_publish_max(gmax + b * FX_SLOTS, a, !(a <= 3.402823466e38f));      // inf or nan (fmaxf would drop a NaN)
+    }
+}
+
+// ---- adjoint of the large-grid step ----------------------------------------------------------------------------------------------
+// out = Cl (SL(v, v) Cr^T) (+ dt f).  The circulants are symmetric, so g_a = Cl (g_out Cr^T) is the forward's two products; the last
+// one of each component publishes max|g_a|.  The advection adjoint scatters g_a through the gathers of k_burgers_adv_large into int64
+// fixed-point accumulators (fixed_scatter.hpp: order independent, so the gradient is reproducible bit for bit; a non-finite g_a turns
+// every input gradient of its simulation into NaN).  Sequence: k_burgers_lb_clear, 4 x k_burgers_circ_large, k_burgers_adv_large_bwd,
+// k_burgers_lb_convert.
+struct BLArgs {
+    int Y, X;
+    float dtdx;
+    const float *vy, *vx;          // the step's saved input
+    const float *gay, *gax;        // g_a
+    long long *gcy, *gcx;          // accumulators [B][nVy], [B][nVx] (contiguous: y components of all simulations, then x)
+    unsigned* gmax;                // [B][FX_SLOTS]
+    float *giy, *gix;              // result
+};
+
+__global__ void __launch_bounds__(256) k_burgers_lb_clear(BLArgs a) {
+    const int nVy = (a.Y + 1) * a.X, nVx = a.Y * (a.X + 1);
+    const int b = blockIdx.y;
+    long long* zy = a.gcy + (size_t)b * nVy;
+    long long* zx = a.gcx + (size_t)b * nVx;
+    for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < nVy + nVx; e += gridDim.x * blockDim.x) {
+        if (e < nVy) zy[e] = 0ll;
+        else zx[e - nVy] = 0ll;
+    }
+    if (blockIdx.x == 0 && threadIdx.x < FX_SLOTS) a.gmax[b * FX_SLOTS + threadIdx.x] = 0u;
+}
+
+// Adjoint of one advected face of component C (0: v_y [Y+1][X], 1: v_x [Y][X+1]) at (j, i), gs = g_a there: the nine terms of
+// k_burgers_bwd.  The departure point is recomputed from the saved input with k_burgers_adv_large's expressions.  What feeds floorf there
+// is ONE rounded product (-u * dtdx, u either a loaded value or 0.25f times a sum of four): nothing a fused multiply-add could absorb, so
+// the forward kernel's floors do not depend on contraction; contraction is off here so that this routine's products are those rounded
+// values too, whatever surrounds it -- both kernels take the same floorf decisions (fixed_scatter.hpp on what happened in 3-D otherwise).
+// The bilinear WEIGHTS may still differ by an ulp between the two kernels: the forward, under the compiler's default contraction, may
+// fuse the product into the subtraction of its floor, which this routine cannot.  A weight is continuous in the departure point, so
+// that ulp moves the gradient by an ulp; only a differing floor would move it by O(1).
+template <int C>
+__device__ __forceinline__ void burgers_adv_adj_point(const BLArgs& a, const float* Vy, const float* Vx, long long* Gy, long long* Gx,
+                                                      float qs, int j, int i, float gs) {
+#pragma clang fp contract(off)
+    const int Y = a.Y, X = a.X, XP = X + 1;
+    float uy, ux;
+    int ja = 0, jb = 0, ia = 0, ib = 0;
+    if (C == 0) {
+        uy = Vy[j * X + i];
+        ja = wrap(j - 1, Y); jb = wrap(j, Y);
+        ux = 0.25f * (Vx[ja * XP + i] + Vx[ja * XP + i + 1] + Vx[jb * XP + i] + Vx[jb * XP + i + 1]);
+    } else {
+        ux = Vx[j * XP + i];
+        ia = wrap(i - 1, X); ib = wrap(i, X);
+        uy = 0.25f * (Vy[j * X + ia] + Vy[j * X + ib] + Vy[(j + 1) * X + ia] + Vy[(j + 1) * X + ib]);
+    }
+    const int H = Y + (C == 0), W = X + (C == 1);          // every wrap is modulo the ARRAY length (PhiFlow-1.x quirk of the forward)
+    const float* F = C == 0 ? Vy : Vx;
+    long long* G = C == 0 ? Gy : Gx;
+    const BilP s = bil_wrap(H, W, j, -uy * a.dtdx, i, -ux * a.dtdx);
+    const float f00 = F[s.j0 * W + s.i0], f01 = F[s.j0 * W + s.i1];
+    const float f10 = F[s.j1 * W + s.i0], f11 = F[s.j1 * W + s.i1];
+    fx_add(&G[s.j0 * W + s.i0], (1.f - s.wy) * (1.f - s.wx) * gs, qs);
+    fx_add(&G[s.j0 * W + s.i1], (1.f - s.wy) * s.wx * gs, qs);
+    fx_add(&G[s.j1 * W + s.i0], s.wy * (1.f - s.wx) * gs, qs);
+    fx_add(&G[s.j1 * W + s.i1], s.wy * s.wx * gs, qs);
+    const float ddy = (1.f - s.wx) * (f10 - f00) + s.wx * (f11 - f01);
+    const float ddx = (1.f - s.wy) * (f01 - f00) + s.wy * (f11 - f10);
+    if (C == 0) {
+        const float guy = -a.dtdx * gs * ddy, gux = -0.25f * a.dtdx * gs * ddx;
+        fx_add(&Gy[j * X + i], guy, qs);
+        fx_add(&Gx[ja * XP + i], gux, qs);
+        fx_add(&Gx[ja * XP + i + 1], gux, qs);
+        fx_add(&Gx[jb * XP + i], gux, qs);
+        fx_add(&Gx[jb * XP + i + 1], gux, qs);
+    } else {
+        const float gux = -a.dtdx * gs * ddx, guy = -0.25f * a.dtdx * gs * ddy;
+        fx_add(&Gx[j * XP + i], gux, qs);
+        fx_add(&Gy[j * X + ia], guy, qs);
+        fx_add(&Gy[j * X + ib], guy, qs);
+        fx_add(&Gy[(j + 1) * X + ia], guy, qs);
+        fx_add(&Gy[(j + 1) * X + ib], guy, qs);
+    }
+}
+
+__global__ void __launch_bounds__(256) k_burgers_adv_large_bwd(BLArgs a) {
+    const int X = a.X, XP = X + 1, nVy = (a.Y + 1) * X, nVx = a.Y * XP;
+    const int b = blockIdx.y;
+    const float* Vy = a.vy + (size_t)b * nVy;
+    const float* Vx = a.vx + (size_t)b * nVx;
+    long long* Gy = a.gcy + (size_t)b * nVy;
+    long long* Gx = a.gcx + (size_t)b * nVx;
+    float qs, qi;
+    fx_scale(a.gmax + b * FX_SLOTS, qs, qi);
+    for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < nVy + nVx; k += gridDim.x * blockDim.x) {
+        if (k < nVy) {
+            const float g = a.gay[(size_t)b * nVy + k];
+            if (g != 0.f) burgers_adv_adj_point<0>(a, Vy, Vx, Gy, Gx, qs, k / X, k % X, g);
+        } else {
+            const int q = k - nVy;
+            const float g = a.gax[(size_t)b * nVx + q];
+            if (g != 0.f) burgers_adv_adj_point<1>(a, Vy, Vx, Gy, Gx, qs, q / XP, q % XP, g);
+        }
+    }
+}
+
+__global__ void __launch_bounds__(256) k_burgers_lb_convert(BLArgs a) {
+    const int nVy = (a.Y + 1) * a.X, nVx = a.Y * (a.X + 1);
+    const int b = blockIdx.y;
+    float qs, qi;
+    fx_scale(a.gmax + b * FX_SLOTS, qs, qi);
+    for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < nVy + nVx; e += gridDim.x * blockDim.x) {
+        if (e < nVy) a.giy[(size_t)b * nVy + e] = fx_get(a.gcy + (size_t)b * nVy, e, qi);
+        else a.gix[(size_t)b * nVx + e - nVy] = fx_get(a.gcx + (size_t)b * nVx, e - nVy, qi);
+    }
+}
+
+// the adjoint's buffers: accumulators (int64), g_a and the product's intermediate (fp32), the absmax slots; 256-byte granules
+struct BLLayout {
+    long long* gc;
+    float *ga, *t;
+    unsigned* gmax;
+    size_t bytes;
+};
+BLLayout bl_layout(const sol_burgers_cfg* c, void* ws) {
+    const size_t B = c->B, Y = c->Y, X = c->X, faces = (Y + 1) * X + Y * (X + 1);
+    char* w = ws ? reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(ws) + 255) / 256 * 256) : nullptr;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { char* p = w ? w + off : nullptr; off += align_up(bytes, 256); return p; };
+    BLLayout l{};
+    l.gc = reinterpret_cast<long long*>(take(B * faces * sizeof(long long)));
+    l.ga = reinterpret_cast<float*>(take(B * faces * sizeof(float)));
+    l.t = reinterpret_cast<float*>(take(B * faces * sizeof(float)));
+    l.gmax = reinterpret_cast<unsigned*>(take(B * FX_SLOTS * sizeof(unsigned)));
+    l.bytes = off + 256;                       // + the alignment of the caller's pointer
+    return l;
 }
 
 int bcheck(const sol_burgers_cfg* c) {
@@ -346,7 +487,7 @@ extern "C" int sol_burgers_step_bwd(const sol_burgers_cfg* cfg, void* stream, co
     return blaunch(k_burgers_bwd, cfg, stream, a);
 }
 
-// ---- large-grid forward step (data generation at the reference's 128 x 128 hi-res setting, burgers/Makefile:19-29) ----
+// ---- large-grid step (data generation at the reference's 128 x 128 hi-res setting, burgers/Makefile:19-29) ----
 extern "C" size_t sol_burgers_step_large_workspace_bytes(const sol_burgers_cfg* cfg) {
     if (!cfg || cfg->B < 1 || cfg->Y < 2 || cfg->X < 2) return 0;
     const size_t nVy = (size_t)(cfg->Y + 1) * cfg->X, nVx = (size_t)cfg->Y * (cfg->X + 1);
@@ -375,14 +516,69 @@ extern "C" int sol_burgers_step_fwd_large(const sol_burgers_cfg* cfg, void* stre
     SOL_LAUNCH_CHECK();
     auto tiles = [](int H, int W, int B_) { return dim3((W + 15) / 16, (H + 15) / 16, B_); };
     // v_y: [Y+1][X]:  T = A * Cx^T, out = Cyp1 * T (+ dt f_y)
-    SOL_LAUNCH(k_burgers_circ_large<0>, tiles(Y + 1, X, B), dim3(256), 0, hs, Y + 1, X, (const float*)ay, circ_x, ty, (const float*)nullptr, 0.f);
+    SOL_LAUNCH(k_burgers_circ_large<0>, tiles(Y + 1, X, B), dim3(256), 0, hs, Y + 1, X, (const float*)ay, circ_x, ty, (const float*)nullptr, 0.f, (unsigned*)nullptr);
     SOL_LAUNCH_CHECK();
-    SOL_LAUNCH(k_burgers_circ_large<1>, tiles(Y + 1, X, B), dim3(256), 0, hs, Y + 1, X, (const float*)ty, circ_yp1, vy_out, f_y, cfg->dt);
+    SOL_LAUNCH(k_burgers_circ_large<1>, tiles(Y + 1, X, B), dim3(256), 0, hs, Y + 1, X, (const float*)ty, circ_yp1, vy_out, f_y, cfg->dt, (unsigned*)nullptr);
     SOL_LAUNCH_CHECK();
     // v_x: [Y][X+1]:  T = A * Cxp1^T, out = Cy * T (+ dt f_x)
-    SOL_LAUNCH(k_burgers_circ_large<0>, tiles(Y, X + 1, B), dim3(256), 0, hs, Y, X + 1, (const float*)ax, circ_xp1, tx, (const float*)nullptr, 0.f);
+    SOL_LAUNCH(k_burgers_circ_large<0>, tiles(Y, X + 1, B), dim3(256), 0, hs, Y, X + 1, (const float*)ax, circ_xp1, tx, (const float*)nullptr, 0.f, (unsigned*)nullptr);
     SOL_LAUNCH_CHECK();
-    SOL_LAUNCH(k_burgers_circ_large<1>, tiles(Y, X + 1, B), dim3(256), 0, hs, Y, X + 1, (const float*)tx, circ_y, vx_out, f_x, cfg->dt);
+    SOL_LAUNCH(k_burgers_circ_large<1>, tiles(Y, X + 1, B), dim3(256), 0, hs, Y, X + 1, (const float*)tx, circ_y, vx_out, f_x, cfg->dt, (unsigned*)nullptr);
+    SOL_LAUNCH_CHECK();
+    return SOL_OK;
+}
+
+// ---- adjoint of the large-grid step: kernel launches only (no memset / memcpy nodes, no host synchronisation), so it can be captured ----
+extern "C" size_t sol_burgers_step_bwd_large_workspace_bytes(const sol_burgers_cfg* cfg) {
+    if (!cfg || cfg->B < 1 || cfg->Y < 2 || cfg->X < 2 || cfg->Y > 1024 || cfg->X > 1024) return 0;
+    return bl_layout(cfg, nullptr).bytes;
+}
+
+extern "C" int sol_burgers_step_bwd_large(const sol_burgers_cfg* cfg, void* stream, const float* vy_in, const float* vx_in,
+                                          const float* circ_yp1, const float* circ_x, const float* circ_y, const float* circ_xp1,
+                                          const float* g_vy_out, const float* g_vx_out, float* g_vy_in, float* g_vx_in,
+                                          void* workspace, size_t workspace_bytes) {
+    SOL_REQUIRE(cfg != nullptr, "cfg is NULL");
+    SOL_REQUIRE(cfg->B >= 1 && cfg->B <= 65535 && cfg->Y >= 2 && cfg->X >= 2 && cfg->Y <= 1024 && cfg->X <= 1024,
+                "burgers (large, adjoint): need 1 <= B <= 65535, 2 <= Y,X <= 1024 (got %d,%d,%d)", cfg->B, cfg->Y, cfg->X);
+    SOL_REQUIRE(cfg->dx > 0.f, "dx must be > 0");
+    SOL_REQUIRE(vy_in && vx_in && circ_yp1 && circ_x && circ_y && circ_xp1 && g_vy_out && g_vx_out && g_vy_in && g_vx_in && workspace,
+                "sol_burgers_step_bwd_large: NULL pointer");
+    const size_t need = bl_layout(cfg, nullptr).bytes;
+    SOL_REQUIRE(workspace_bytes >= need, "sol_burgers_step_bwd_large: workspace too small (%zu < %zu bytes)", workspace_bytes, need);
+    SOL_REQUIRE(g_vy_in != g_vx_in && g_vy_in != vy_in && g_vy_in != vx_in && g_vx_in != vy_in && g_vx_in != vx_in,
+                "sol_burgers_step_bwd_large: g_vy_in / g_vx_in must be buffers of their own");
+    const int B = cfg->B, Y = cfg->Y, X = cfg->X;
+    const size_t nVy = (size_t)(Y + 1) * X, nVx = (size_t)Y * (X + 1), faces = nVy + nVx;
+    const BLLayout l = bl_layout(cfg, workspace);
+    BLArgs a{};
+    a.Y = Y; a.X = X; a.dtdx = cfg->dt / cfg->dx;
+    a.vy = vy_in; a.vx = vx_in;
+    a.gay = l.ga; a.gax = l.ga + B * nVy;
+    a.gcy = l.gc; a.gcx = l.gc + B * nVy;
+    a.gmax = l.gmax;
+    a.giy = g_vy_in; a.gix = g_vx_in;
+    float* gay = l.ga;
+    float* gax = l.ga + B * nVy;
+    float* ty = l.t;
+    float* tx = l.t + B * nVy;
+    hipStream_t hs = (hipStream_t)stream;
+    const dim3 gF((unsigned)((faces + 255) / 256), B);
+    SOL_LAUNCH(k_burgers_lb_clear, gF, dim3(256), 0, hs, a);
+    SOL_LAUNCH_CHECK();
+    auto tiles = [](int H, int W, int B_) { return dim3((W + 15) / 16, (H + 15) / 16, B_); };
+    // diffusion adjoint, the forward's operator: g_a = Cl (g Cr^T); the second product of each component publishes max|g_a|
+    SOL_LAUNCH(k_burgers_circ_large<0>, tiles(Y + 1, X, B), dim3(256), 0, hs, Y + 1, X, g_vy_out, circ_x, ty, (const float*)nullptr, 0.f, (unsigned*)nullptr);
+    SOL_LAUNCH_CHECK();
+    SOL_LAUNCH((k_burgers_circ_large<1, true>), tiles(Y + 1, X, B), dim3(256), 0, hs, Y + 1, X, (const float*)ty, circ_yp1, gay, (const float*)nullptr, 0.f, l.gmax);
+    SOL_LAUNCH_CHECK();
+    SOL_LAUNCH(k_burgers_circ_large<0>, tiles(Y, X + 1, B), dim3(256), 0, hs, Y, X + 1, g_vx_out, circ_xp1, tx, (const float*)nullptr, 0.f, (unsigned*)nullptr);
+    SOL_LAUNCH_CHECK();
+    SOL_LAUNCH((k_burgers_circ_large<1, true>), tiles(Y, X + 1, B), dim3(256), 0, hs, Y, X + 1, (const float*)tx, circ_y, gax, (const float*)nullptr, 0.f, l.gmax);
+    SOL_LAUNCH_CHECK();
+    SOL_LAUNCH(k_burgers_adv_large_bwd, gF, dim3(256), 0, hs, a);
+    SOL_LAUNCH_CHECK();
+    SOL_LAUNCH(k_burgers_lb_convert, gF, dim3(256), 0, hs, a);
     SOL_LAUNCH_CHECK();
     return SOL_OK;
 }

@@ -101,6 +101,15 @@ class ConvNet:
             return self(x)
 
 
+def _conv_form(x, scaled, nslots):
+    """conv(x, w, b, residual, lrelu, slope, i, o): ops.conv5x5, or -- scaled=True on rows that are a multiple of 64 pixels wide -- the
+    launches of schedule2d.NetSchedule2D's forward (ops.conv5x5_scaled; i / o: the absmax slot sets of the layer's input / output)."""
+    if not (scaled and x.shape[2] % 64 == 0):
+        return lambda x_, w, b, r, act, s, i, o: ops.conv5x5(x_, w, b, r, act, s)
+    am = torch.zeros(nslots, ops.AMAX_SLOTS, dtype=torch.int32, device=x.device)
+    return lambda x_, w, b, r, act, s, i, o: ops.conv5x5_scaled(x_, w, b, r, act, s, None if i is None else am[i], None if o is None else am[o])
+
+
 class MarsMoon(ConvNet):
     """model_mars_moon, karman_train.py:101-138: 12 convs, 260,354 parameters."""
     name = "mars_moon"
@@ -109,14 +118,15 @@ class MarsMoon(ConvNet):
     def channels(cin, cout):
         return [cin] + [32] * 11 + [cout]
 
-    def __call__(self, x, flat=None):
+    def __call__(self, x, flat=None, scaled=False):
         p = self.tensors(flat)
         s = self.slope
-        h = ops.conv5x5(x, p[0], p[1], None, True, s)
+        conv = _conv_form(x, scaled, 11)
+        h = conv(x, p[0], p[1], None, True, s, None, 0)
         for k in range(5):
-            a = ops.conv5x5(h, p[2 + 4 * k], p[3 + 4 * k], None, True, s)
-            h = ops.conv5x5(a, p[4 + 4 * k], p[5 + 4 * k], h, True, s)
-        return ops.conv5x5(h, p[22], p[23], None, False, s)
+            a = conv(h, p[2 + 4 * k], p[3 + 4 * k], None, True, s, 2 * k, 2 * k + 1)
+            h = conv(a, p[4 + 4 * k], p[5 + 4 * k], h, True, s, 2 * k + 1, 2 * k + 2)
+        return conv(h, p[22], p[23], None, False, s, 10, None)
 
 
 class Mercury(ConvNet):
@@ -130,14 +140,15 @@ class Mercury(ConvNet):
     def channels(cin, cout):
         return [cin, 32, 64, cout]
 
-    def __call__(self, x, flat=None):
+    def __call__(self, x, flat=None, scaled=False):
         p = self.tensors(flat)
-        h = ops.conv5x5(x, p[0], p[1], None, True, 0.0)
+        conv = _conv_form(x, scaled, 3)
+        h = conv(x, p[0], p[1], None, True, 0.0, None, 0)
         b3a, b3b = ops.split_flat(p[3], (0, 32, 64))           # (1-D halves: not plain slices, see ConvNet.tensors)
-        ha = ops.conv5x5(h, p[2][..., :32].contiguous(), b3a, None, True, 0.0)
-        hb = ops.conv5x5(h, p[2][..., 32:].contiguous(), b3b, None, True, 0.0)
-        oa = ops.conv5x5(ha, p[4][:, :, :32].contiguous(), p[5], None, False, 0.0)
-        return ops.conv5x5(hb, p[4][:, :, 32:].contiguous(), torch.zeros_like(p[5]), oa, False, 0.0)
+        ha = conv(h, p[2][..., :32].contiguous(), b3a, None, True, 0.0, 0, 1)
+        hb = conv(h, p[2][..., 32:].contiguous(), b3b, None, True, 0.0, 0, 2)
+        oa = conv(ha, p[4][:, :, :32].contiguous(), p[5], None, False, 0.0, 1, None)
+        return conv(hb, p[4][:, :, 32:].contiguous(), torch.zeros_like(p[5]), oa, False, 0.0, 2, None)
 
 
 def model_mercury(tensor_in=None, cin=3, cout=2, seed=0, device="cuda"):

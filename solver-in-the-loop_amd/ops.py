@@ -410,6 +410,37 @@ def conv5x5(x, w, b, residual=None, lrelu=False, slope=0.3):
     return Conv5x5Fn.apply(x, w, b, residual, lrelu, slope)
 
 
+class Conv5x5ScaledFn(Conv5x5Fn):
+    """Conv5x5Fn whose forward launch is sol_conv5x5_scaled with the absmax slots handed from layer to layer -- the launch
+    schedule2d.NetSchedule2D's forward makes on 64-pixel rows (fp16 three-product kernels on the 32-channel layers), so that an autograd
+    composition and the hand-written schedule see the same activations, LeakyReLU masks included.  The backward is Conv5x5Fn's."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, residual, lrelu, slope, xmax, ymax):
+        _lib.require_gpu()
+        cin, cout = w.shape[2], w.shape[3]
+        x = _lib.f32(x); w = _lib.f32(w); b = _lib.f32(b)
+        cin_k = 4 if cin <= 4 else 32
+        assert cin in (1, 2, 3, 4, 32), "conv5x5 supports <=4 or 32 input channels"
+        ctx.cin_w = cin
+        xk = _pad_channels(x, cin_k)
+        packed = _pack(w, cin, cout, CONV_FWD)
+        res = None if residual is None else _lib.f32(residual)
+        y = conv5x5_scaled_raw(xk, packed, b, res, None, cout, EPI_LRELU if lrelu else EPI_NONE, slope, xmax, ymax)
+        ctx.save_for_backward(xk, w, y)
+        ctx.meta = (cin, cout, cin_k, lrelu, slope, residual is not None)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        return Conv5x5Fn.backward(ctx, gy) + (None, None)
+
+
+def conv5x5_scaled(x, w, b, residual=None, lrelu=False, slope=0.3, xmax=None, ymax=None):
+    """conv5x5 through sol_conv5x5_scaled: xmax / ymax are rows of an [n, AMAX_SLOTS] int32 tensor zeroed by the caller (or None)."""
+    return Conv5x5ScaledFn.apply(x, w, b, residual, lrelu, slope, xmax, ymax)
+
+
 # --------------------------------------------------------------------------------------
 # Burgers step
 # --------------------------------------------------------------------------------------
@@ -462,23 +493,69 @@ def burgers_step(vy, vx, fy, fx, cfg, circ):
     return BurgersStepFn.apply(vy, vx, fy, fx, cfg, circ)
 
 
-BURGERS_LDS_MAX = 64      # largest grid edge of the one-workgroup (differentiable) Burgers kernels
+BURGERS_LDS_MAX = 64      # largest grid edge of the one-workgroup Burgers kernels
 
 
-def burgers_step_large(vy, vx, fy, fx, cfg, circ, workspace=None):
-    """Forward-only Burgers step for grids beyond the one-workgroup kernels (the reference's 128 x 128 data generation,
-    /root/reference/burgers/Makefile:19-29): sol_burgers_step_fwd_large.  Returns (vy, vx) after the step."""
-    _lib.require_gpu()
+def burgers_large_workspace_bytes(cfg):
+    """Bytes of a workspace that serves sol_burgers_step_fwd_large AND sol_burgers_step_bwd_large (they never run at the same time)."""
     lib = _lib.load()
-    vy, vx = _lib.f32(vy), _lib.f32(vx)
-    fy = None if fy is None else _lib.f32(fy)
-    fx = None if fx is None else _lib.f32(fx)
+    return max(lib.sol_burgers_step_large_workspace_bytes(C.byref(cfg)), lib.sol_burgers_step_bwd_large_workspace_bytes(C.byref(cfg)))
+
+
+def _burgers_large_fwd(vy, vx, fy, fx, cfg, circ, workspace):
+    lib = _lib.load()
     workspace = _workspace(lib.sol_burgers_step_large_workspace_bytes(C.byref(cfg)), workspace, vy.device)
     oy, ox = torch.empty_like(vy), torch.empty_like(vx)
     check(lib.sol_burgers_step_fwd_large(C.byref(cfg), stream(), ptr(vy), ptr(vx), ptr(fy), ptr(fx),
                                          ptr(circ[0]), ptr(circ[1]), ptr(circ[2]), ptr(circ[3]), ptr(oy), ptr(ox),
                                          ptr(workspace), workspace.numel() * 4))
     return oy, ox
+
+
+def burgers_step_large_bwd(vy, vx, gy, gx, cfg, circ, workspace=None):
+    """Adjoint of the large-grid Burgers step (sol_burgers_step_bwd_large): (g_vy_in, g_vx_in) from the step's input velocity and the
+    gradient with respect to its output velocity."""
+    lib = _lib.load()
+    workspace = _workspace(lib.sol_burgers_step_bwd_large_workspace_bytes(C.byref(cfg)), workspace, vy.device)
+    oy, ox = torch.empty_like(vy), torch.empty_like(vx)
+    check(lib.sol_burgers_step_bwd_large(C.byref(cfg), stream(), ptr(vy), ptr(vx), ptr(circ[0]), ptr(circ[1]), ptr(circ[2]), ptr(circ[3]),
+                                         ptr(gy), ptr(gx), ptr(oy), ptr(ox), ptr(workspace), workspace.numel() * 4))
+    return oy, ox
+
+
+class BurgersStepLargeFn(torch.autograd.Function):
+    """The large-grid Burgers step with its hand-written adjoint (sol_burgers_step_fwd_large / sol_burgers_step_bwd_large)."""
+
+    @staticmethod
+    def forward(ctx, vy, vx, fy, fx, cfg, circ, workspace):
+        oy, ox = _burgers_large_fwd(vy, vx, fy, fx, cfg, circ, workspace)
+        ctx.save_for_backward(vy, vx)
+        ctx.cfg, ctx.circ, ctx.workspace, ctx.has_f = cfg, circ, workspace, fy is not None
+        return oy, ox
+
+    @staticmethod
+    def backward(ctx, gy, gx):
+        vy, vx = ctx.saved_tensors
+        gy = torch.zeros_like(vy) if gy is None else gy.contiguous()
+        gx = torch.zeros_like(vx) if gx is None else gx.contiguous()
+        oy, ox = burgers_step_large_bwd(vy, vx, gy, gx, ctx.cfg, ctx.circ, ctx.workspace)
+        dt = ctx.cfg.dt
+        return oy, ox, (gy * dt if ctx.has_f else None), (gx * dt if ctx.has_f else None), None, None, None
+
+
+def burgers_step_large(vy, vx, fy, fx, cfg, circ, workspace=None):
+    """Burgers step for grids beyond the one-workgroup kernels (the reference's 128 x 128 data generation,
+    /root/reference/burgers/Makefile:19-29): sol_burgers_step_fwd_large.  Returns (vy, vx) after the step.  When grad is enabled and an
+    input requires a gradient the call goes through BurgersStepLargeFn (same forward launches; the adjoint is
+    sol_burgers_step_bwd_large, d f = dt * g); otherwise nothing is kept.  `workspace` (optional, fp32 words) serves both directions when
+    it holds burgers_large_workspace_bytes(cfg)."""
+    _lib.require_gpu()
+    vy, vx = _lib.f32(vy), _lib.f32(vx)
+    fy = None if fy is None else _lib.f32(fy)
+    fx = None if fx is None else _lib.f32(fx)
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (vy, vx, fy, fx)):
+        return BurgersStepLargeFn.apply(vy, vx, fy, fx, cfg, circ, workspace)
+    return _burgers_large_fwd(vy, vx, fy, fx, cfg, circ, workspace)
 
 
 class SplitFlatFn(torch.autograd.Function):

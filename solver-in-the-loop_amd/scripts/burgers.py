@@ -3,8 +3,8 @@
 HIP Burgers step (state on the GPU, one launch per frame).  Forcing: sol_amd.burgers.SinForces (the reference's 20
 SinPotential forces + ForcingPhysics, recalled semantics behind --force-variant), or hi-res force / velocity files
 down-sampled by -d (--initvH / --loadfH, the reference's hires -> lores chain, Makefile:35-49).
-Grids up to 64 x 64 run the one-workgroup (differentiable) kernel, larger ones -- the reference's 128 x 128 hi-res set,
-burgers/Makefile:19-29 -- the forward-only multi-workgroup step."""
+Grids up to 64 x 64 run the one-workgroup kernel, larger ones -- the reference's 128 x 128 hi-res set,
+burgers/Makefile:19-29 -- the multi-workgroup step (no gradient is taken here)."""
 import argparse
 import glob
 import pickle

@@ -3,7 +3,8 @@
 /root/reference/burgers/burgers_train.py (flags :22-44, unroll :379-417, loss :419-437, loop :465-500).
 The unrolled graph is composed from the differentiable HIP ops (BurgersTest.step_with_f = fused periodic advection + spectral
 diffusion kernel, 5x5 convs on the matrix cores) by torch autograd and captured ONCE into a hipGraph over static buffers
-(sol_amd.BurgersTrainer); --no-graph steps the same composition eagerly.  The optimizer is the TF1-Adam kernel."""
+(sol_amd.BurgersTrainer); --no-graph steps the same composition eagerly.  The optimizer is the TF1-Adam kernel.
+`-s 1` trains at the resolution of the data, 128 x 128 included (the large-grid step and its adjoint)."""
 import argparse
 import os
 import pickle

@@ -2,7 +2,7 @@
 through PyTorch-ROCm custom ops with a hand-written backward for each solver op").
 
 The ops call the same entry points of libsol_hip.so as ops.py (ctypes, raw device pointers; no torch types cross the C
-ABI) and carry the hand-written adjoints (sol_karman_step_bwd, sol_burgers_step_bwd, sol_conv5x5 backward-data / -weight)
+ABI) and carry the hand-written adjoints (sol_karman_step_bwd, sol_burgers_step_bwd / _bwd_large, sol_conv5x5 backward-data / -weight)
 through torch.library.register_autograd, so they compose with any other PyTorch op and show up in the dispatcher
 (torch.ops.sol.karman_step, .conv5x5, .burgers_step, .adam_tf_step).  Scene constants (masks, solver blobs, the cfg
 struct) are not tensors: they are registered once with register_scene() and referred to by an integer handle."""
@@ -107,6 +107,8 @@ def _burgers(vy, vx, fy, fx, dx, dt, nu):
     B, Yp1, X = vy.shape
     cfg = _lib.BurgersCfg(B, Yp1 - 1, X, float(dx), float(dt))
     circ = ops.burgers_circ(Yp1 - 1, X, dt * nu, vy.device)
+    if max(Yp1 - 1, X) > ops.BURGERS_LDS_MAX:       # beyond the one-workgroup kernels: the multi-launch step and its adjoint
+        return ops.burgers_step_large(vy, vx, fy, fx, cfg, circ)
     return ops.BurgersStepFn.apply(vy, vx, fy, fx, cfg, circ)
 
 
