@@ -312,11 +312,7 @@ __global__ void __launch_bounds__(768) k_cnn_chain(ChainArgs a) {
 #pragma unroll
         for (int n = 0; n < 2; ++n) total[n] = (f32x4){0.f, 0.f, 0.f, 0.f};
         SOL_CHSTAMP(l, 0);
-#ifdef CH_EXP_NOHALO                                    // timing experiment only (wrong results): what the layer costs without the exchange
-        const bool exch = false;
-#else
         const bool exch = l > 0;
-#endif
         // hand-off of layer l-1's output: parity buffer (l-1)&1, tag 1 + (((l-1)/2 + epoch) mod 3)
         const unsigned tag_in = chain_tag(l - 1);
         const int par_in = (l - 1) & 1;
@@ -399,9 +395,6 @@ __global__ void __launch_bounds__(768) k_cnn_chain(ChainArgs a) {
                             const unsigned t0 = ((g4.x >> 16) & 1u) | ((g4.y >> 15) & 2u), t1 = ((g4.z >> 16) & 1u) | ((g4.w >> 15) & 2u);
                             ok = ok && (!(h_flag[n] & 2) || (t0 == tag_in && t1 == tag_in)) && (!(h_flag[n] & 4) || (unsigned)(hrm[n] >> 32) == tag_in);
                         }
-#ifdef CH_EXP_NOCHECK                                    // timing experiment only: never wait for a neighbour (results may be stale)
-                        ok = true;
-#endif
                         if (__all(ok)) break;
                         if (++spins > CH_SPIN_LIMIT) {            // a neighbour never delivered (not resident?): flag the launch and go on
                             if (lane == 0) atomicOr(a.err, 1u);

@@ -333,37 +333,21 @@ inline int sol_lds_optin(std::atomic<unsigned long long>& done, std::initializer
 // 4-byte write-through stores -- the thin layers' strided channels, the velocity correction -- measured SLOWER: 10.5 -> 11.0 us per launch); not for read-modify-write sequences of
 // one thread on one address (the compiler does not see these stores in its vmcnt bookkeeping: extra stores only make its waits more
 // conservative, but it will not order a later load of the same address behind them; the 16-byte form carries its own wait states).
-// SOL_WT_STORES=0 (A/B builds): plain stores everywhere.
-#ifndef SOL_WT_STORES
-#define SOL_WT_STORES 1
-#endif
 typedef float sol_f32x4 __attribute__((ext_vector_type(4)));
 typedef float sol_f32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ void st_wt(float4* p, const float4& v) {
-#if SOL_WT_STORES
     const sol_f32x4 q = {v.x, v.y, v.z, v.w};
     // s_nop 1: a VMEM store of more than 8 bytes followed by a VALU write of its data VGPRs needs 2 wait states on gfx940+; the
     // compiler's hazard recognizer does not look inside inline asm (without it: an unrolled store loop reused the data registers
     // at once and the weight-gradient partials came out wrong, tests/test_gpu_parity.py::test_conv5x5_against_oracle)
     asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" :: "v"(p), "v"(q) : "memory");
-#else
-    *p = v;
-#endif
 }
 __device__ __forceinline__ void st_wt(float2* p, const float2& v) {
-#if SOL_WT_STORES
     const sol_f32x2 q = {v.x, v.y};
     asm volatile("global_store_dwordx2 %0, %1, off sc1" :: "v"(p), "v"(q) : "memory");
-#else
-    *p = v;
-#endif
 }
 __device__ __forceinline__ void st_wt(float* p, float v) {
-#if SOL_WT_STORES
     asm volatile("global_store_dword %0, %1, off sc1" :: "v"(p), "v"(v) : "memory");
-#else
-    *p = v;
-#endif
 }
 
 // wave64 all-reduce (every lane gets the sum)
@@ -425,11 +409,7 @@ __device__ __forceinline__ void loss_publish_last(float lsum, unsigned long long
 // image rows: a convolution's halo rows, and the rows the previous layer's launch wrote, are then in the SAME L2 except
 // at the 8 block seams.  (n not a multiple of 8: identity.)
 __device__ __forceinline__ int xcd_tile(int w, int n) {
-#ifdef SOL_NO_XCD_REMAP
-    return w;
-#else
     return (n & 7) == 0 ? (w & 7) * (n >> 3) + (w >> 3) : w;
-#endif
 }
 
 // Workgroup all-reduce through LDS.  `red` holds 2 x 32 floats; `slot` alternates 0/1

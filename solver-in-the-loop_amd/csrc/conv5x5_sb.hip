@@ -93,7 +93,6 @@ __global__ void k_pack_sb(const float* __restrict__ w, unsigned short* __restric
 // KIND 2: fp16, three products, per-tensor power-of-two scaling (needs a.xmax)
 // -DSOL_CONV_PROF (tools/conv_phase_probe.py builds such a library next to the product one): phase stamps (100 MHz
 // s_memrealtime, thread 0 of every workgroup, 16 per workgroup) into the buffer set with sol_conv_prof_set().
-// -DSOL_CONV_TRUNC=0|1|2 (tools/conv_variants.py): return at kernel entry / after the prologue / after the tap-row loop.
 #ifdef SOL_CONV_PROF
 __device__ long long* g_conv_prof = nullptr;        // [cap launches][grid][16] stamps; g_conv_prof_ctl = {launch counter, cap}
 __device__ unsigned g_conv_prof_ctl[2] = {0u, 1u};
@@ -105,9 +104,6 @@ extern "C" int sol_conv_prof_set(long long* buf, unsigned cap) {
 #define SOL_CSTAMP(k) do { if (NT == 2 && KIND == 2 && threadIdx.x == 0 && cv_prof) cv_prof[(k)] = __builtin_amdgcn_s_memrealtime(); } while (0)
 #else
 #define SOL_CSTAMP(k) do { } while (0)
-#endif
-#ifndef SOL_CONV_TRUNC
-#define SOL_CONV_TRUNC 9
 #endif
 
 template <int NT, int KIND>
@@ -121,7 +117,6 @@ __global__ void __launch_bounds__(768) k_conv5x5_sb(ConvArgs a, int nrows) {
     constexpr int WBUF = 5 * NPL * WPL;           // bytes per tap-row weight phase
     constexpr int AMAX_LDS = 4 * SLOT + 2 * WBUF;  // behind the ring and the weight buffers: workgroup max|y|, wave counter; loss_publish_last's 4 + 12 words
     extern __shared__ __align__(16) unsigned char smem_sb[];
-    if (SOL_CONV_TRUNC == 0) return;
 #ifdef SOL_CONV_PROF
     long long* __restrict__ cv_prof = g_conv_prof;            // read once into scalar registers (a reload per stamp costs ~0.5 us each)
     if (cv_prof) cv_prof += ((size_t)(g_conv_prof_ctl[0] % g_conv_prof_ctl[1]) * gridDim.x + blockIdx.x) * 16;
@@ -236,7 +231,6 @@ __global__ void __launch_bounds__(768) k_conv5x5_sb(ConvArgs a, int nrows) {
     }
     SB_BARRIER();
     SOL_CSTAMP(1);
-    if (SOL_CONV_TRUNC == 1) return;
 
     f32x4 acc[NT], acl[NT];                           // acl: KIND 2 accumulator of the 2^-11 weighted cross terms
 #pragma unroll
@@ -265,17 +259,9 @@ __global__ void __launch_bounds__(768) k_conv5x5_sb(ConvArgs a, int nrows) {
         asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
                      : "=&s"(keep) : "v"(src), "s"(lo));
     };
-#ifndef SOL_CONV_LATE_EPI                             // (A/B switch: 14.85 -> 14.77 ms per training step)
-    constexpr bool EPI_PREFETCH = true;
-#else
-    constexpr bool EPI_PREFETCH = false;
-#endif
+    // (against loading them in the epilogue, where they are used: 14.85 -> 14.77 ms per training step)
 
-#ifndef SOL_CONV_STAGE_AT
-#define SOL_CONV_STAGE_AT 1, 3
-#endif
-    constexpr int STAGE_AT[2] = {SOL_CONV_STAGE_AT};
-    constexpr int STAGE_ROW_AT = STAGE_AT[0], STAGE_W_AT = STAGE_AT[1];   // after which tap (dx) the row / the weights are written
+    constexpr int STAGE_ROW_AT = 1, STAGE_W_AT = 3;   // after which tap (dx) the row / the weights are written
     // one tap row: requests (row, weights) of tap row `nxt` into (hin, win) -- nxt < 0: nothing --, runs the five taps, writes
     // (hout, wout) = row G0+dy+1 and the weights of tap row dy+1 to LDS
     auto tap_row = [&](const int dy, const int nxt, float4& hin, uint4& wi0, uint4& wi1, uint4& wi2,
@@ -284,7 +270,7 @@ __global__ void __launch_bounds__(768) k_conv5x5_sb(ConvArgs a, int nrows) {
         // requested AFTER the last staging store of tap row 3: the compiler's wait counts are conservative across the
         // staging branches, and a request before them was waited for (a round trip in the open) when the weights were written
         auto epi_prefetch = [&]() __attribute__((always_inline)) {
-            if (EPI_PREFETCH && tvalid && a.CO == OP) {
+            if (tvalid && a.CO == OP) {
 #pragma unroll
                 for (int n = 0; n < EF4; ++n) {
                     const int e = lane + n * 64, px = e / (OP / 4), c4 = e % (OP / 4);
@@ -311,17 +297,6 @@ __global__ void __launch_bounds__(768) k_conv5x5_sb(ConvArgs a, int nrows) {
             auto load_ops = [&](int dx, uint4 (&ar)[NPL], uint4 (&br)[NT][NPL]) {
                 const int hc = pcc + dx;
                 const unsigned char* ap = hrow + hc * 64 + ((g ^ swzb(hc)) << 4);
-#ifdef SOL_CONV_EXP_NOLDS                             // experiment (tools/conv_variants.py): operands from registers, no ds_read
-                unsigned fake = 0x2c112e37u + (unsigned)(size_t)ap * 0x00010001u + dx;
-                asm volatile("" : "+v"(fake));
-#pragma unroll
-                for (int pl = 0; pl < NPL; ++pl) ar[pl] = make_uint4(fake, fake ^ 0x01000100u, fake + 0x00030002u, fake ^ 0x00100010u);
-#pragma unroll
-                for (int n = 0; n < NT; ++n)
-#pragma unroll
-                    for (int pl = 0; pl < NPL; ++pl) br[n][pl] = make_uint4(fake ^ 0x02000200u, fake, fake ^ 0x00010100u, fake + 0x00010001u);
-                return;
-#endif
 #pragma unroll
                 for (int pl = 0; pl < NPL; ++pl) ar[pl] = *reinterpret_cast<const uint4*>(ap + pl * PLANE);
 #pragma unroll
@@ -338,15 +313,6 @@ __global__ void __launch_bounds__(768) k_conv5x5_sb(ConvArgs a, int nrows) {
             for (int dx = dx0; dx < dx1; ++dx) {
                 if (dx < 4) load_ops(dx + 1, ao[(dx + 1) & 1], bo[(dx + 1) & 1]);
                 __builtin_amdgcn_sched_barrier(0);     // keep the prefetch ds_reads above this tap's MFMAs
-#ifdef SOL_CONV_EXP_NOMFMA                            // experiment: the ds_reads are consumed, no MFMA issued
-#pragma unroll
-                for (int pl = 0; pl < NPL; ++pl) {
-                    { const uint4 q = ao[dx & 1][pl]; asm volatile("" :: "v"(q.x), "v"(q.y), "v"(q.z), "v"(q.w)); }
-#pragma unroll
-                    for (int n = 0; n < NT; ++n) { const uint4 q = bo[dx & 1][n][pl]; asm volatile("" :: "v"(q.x), "v"(q.y), "v"(q.z), "v"(q.w)); }
-                }
-                continue;
-#endif
                 if constexpr (KIND == 2) {
                     const f16x8 a1 = __builtin_bit_cast(f16x8, ao[dx & 1][0]), a2 = __builtin_bit_cast(f16x8, ao[dx & 1][NPL - 1]);
 #pragma unroll
@@ -390,7 +356,6 @@ __global__ void __launch_bounds__(768) k_conv5x5_sb(ConvArgs a, int nrows) {
         tap_row(3, -1, hvA, wA0, wA1, wA2, hvB, wB0, wB1, wB2);
         tap_row(4, -1, hvA, wA0, wA1, wA2, hvB, wB0, wB1, wB2);
     }
-    if (SOL_CONV_TRUNC == 2) { if (acc[0][0] + acc[NT - 1][3] == 1.2345f) a.y[tid] = acl[0][1]; return; }
     if constexpr (KIND == 2) {
 #pragma unroll
         for (int n = 0; n < NT; ++n)
@@ -410,7 +375,7 @@ __global__ void __launch_bounds__(768) k_conv5x5_sb(ConvArgs a, int nrows) {
             for (int r = 0; r < 4; ++r) tb[(4 * g + r) * OP + n * 16 + li] = acc[n][r] + bias;
         }
         // same-wave LDS round trip: the compiler's s_waitcnt lgkmcnt orders write -> read
-        if (EPI_PREFETCH) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's LDS-DMA of res / act has landed
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's LDS-DMA of res / act has landed
         if (tvalid) {
             constexpr int F4 = 16 * OP / 4 / 64;          // float4 per lane
 #pragma unroll
@@ -419,12 +384,12 @@ __global__ void __launch_bounds__(768) k_conv5x5_sb(ConvArgs a, int nrows) {
                 const int px = e / (OP / 4), c4 = e % (OP / 4);
                 float4 v = *reinterpret_cast<const float4*>(&tb[px * OP + c4 * 4]);
                 const size_t o4 = ((size_t)gy * W + x0 + wave * 16 + px) * (OP / 4) + c4;
-                if (a.res) { const float4 q = EPI_PREFETCH ? *reinterpret_cast<const float4*>(pf + n * 1024 + lane * 16) : reinterpret_cast<const float4*>(a.res)[o4]; v.x += q.x; v.y += q.y; v.z += q.z; v.w += q.w; }
+                if (a.res) { const float4 q = *reinterpret_cast<const float4*>(pf + n * 1024 + lane * 16); v.x += q.x; v.y += q.y; v.z += q.z; v.w += q.w; }
                 if (a.epi == SOL_EPI_LRELU) {
                     v.x = v.x > 0.f ? v.x : a.slope * v.x; v.y = v.y > 0.f ? v.y : a.slope * v.y;
                     v.z = v.z > 0.f ? v.z : a.slope * v.z; v.w = v.w > 0.f ? v.w : a.slope * v.w;
                 } else if (a.epi == SOL_EPI_DLRELU) {
-                    const float4 q = EPI_PREFETCH ? *reinterpret_cast<const float4*>(pf + (EF4 + n) * 1024 + lane * 16) : reinterpret_cast<const float4*>(a.act)[o4];
+                    const float4 q = *reinterpret_cast<const float4*>(pf + (EF4 + n) * 1024 + lane * 16);
                     v.x *= q.x > 0.f ? 1.f : a.slope; v.y *= q.y > 0.f ? 1.f : a.slope;
                     v.z *= q.z > 0.f ? 1.f : a.slope; v.w *= q.w > 0.f ? 1.f : a.slope;
                 }

@@ -521,14 +521,8 @@ __device__ __forceinline__ int pcg_solve(const Own& o, int Y, int X, const unsig
 //     x = G (b - U_S E_SS x_S),   x_S = (I + G_SS E_SS)^-1 (G b)_S            (precond.direct_solver_blob)
 // One forward 2-D transform of b, the spectral coefficients of the window-sized correction added in
 // spectral space, one inverse transform.  ~7 MFLOP per solve instead of ~56 preconditioned CG
-// iterations; no reductions, 13 barriers.  The transforms are 16 x 64-column (or 128-row x 16) register
-// tiles per wave whose coefficients Q[k][16 values] are WAVE UNIFORM: they are fetched with
-// s_load_dwordx16 and used as SGPR-pair operands of v_pk_fma_f32, the data element comes from one
-// conflict-free ds_read_b32 per 8 packed FMAs (rows padded to 65 floats serve row and column access).
-// The blob is constant for the lifetime of the kernel: reading it through the CONSTANT address space is what lets
-// the compiler scalarise the wave-uniform coefficient loads even though the kernel has stored to global memory.
-typedef const float __attribute__((address_space(4)))* fd_cfp;
-typedef const f2 __attribute__((address_space(4)))* fd_cf2p;
+// iterations; no reductions, 13 barriers.  The transforms run on the fp32 matrix cores (below); the LDS
+// rows are padded to 65 floats, which serves row and column access without bank conflicts.
 struct FdView {
     const float *Qy, *Qx, *ilT, *KpT, *QxW;
     const int* sidx;
@@ -536,10 +530,7 @@ struct FdView {
 };
 constexpr int FD_Y = 128, FD_X = 64, FD_LD = 65, FD_WIN = 16, FD_ULD = 17;
 constexpr int FD_BUF = FD_Y * FD_LD;   // floats per transform buffer
-#ifndef SOL_FD_MFMA
-#define SOL_FD_MFMA 1                  // the sine transforms of fd_solve on the fp32 matrix cores (0: the packed-VALU forms, for A/B builds)
-#endif
-constexpr int FD_QYS = SOL_FD_MFMA ? 32 : FD_Y / 16;   // VGPRs of the wave's Qy coefficient slice, loaded at kernel start
+constexpr int FD_QYS = 32;             // VGPRs of the wave's Qy coefficient slice (fd_load_ay), loaded at kernel start
 
 __device__ __forceinline__ FdView fd_view(const float* __restrict__ blob) {
     const int* h = reinterpret_cast<const int*>(blob);
@@ -557,65 +548,12 @@ __device__ __forceinline__ FdView fd_view(const float* __restrict__ blob) {
 // s_k = v_k + v_{NK-1-k}, d_k = v_k - v_{NK-1-k} (k < NK/2):
 //     out[j]      = sum_k Q[k][j] * (j even ? s_k : d_k)
 //     out[NK-1-j] = sum_k (-1)^k Q[k][j] * (j even ? d_k : s_k)
-// i.e. HALF the multiply-adds and only the [NK/2 x NK/2] corner of Q is read (16 KB of Qy, 4 KB of Qx: the
-// wave-uniform s_load stream stays inside the scalar cache).  A thread produces the 8 outputs j = 8*g8 + r and
-// their 8 mirrors NK-1-j:  lo[q] = (out[8g8+2q], out[8g8+2q+1]),  hi[q] = (out[NK-1-(8g8+2q)], out[NK-1-(8g8+2q+1)]).
-// Input element k of the thread is bp[k * SK].
-template <int NK, int SK>
-__device__ __forceinline__ void fd_trans(const float* __restrict__ Q, const float* bp, int g8, f2 (&lo)[4], f2 (&hi)[4]) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) { lo[q] = (f2){0.f, 0.f}; hi[q] = (f2){0.f, 0.f}; }
-    fd_cfp Qg = (fd_cfp)(Q + 8 * g8);
-#pragma unroll 4
-    for (int k = 0; k < NK / 2; k += 2) {
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-            const float va = bp[(k + kk) * SK], vb = bp[(NK - 1 - k - kk) * SK];
-            const float sk = va + vb, dk = va - vb;
-            const f2 sd = {sk, dk};
-            const f2 ds = kk == 0 ? (f2){dk, sk} : (f2){-dk, -sk};      // (-1)^k
-            fd_cf2p qr = (fd_cf2p)(Qg + (size_t)(k + kk) * NK);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) { lo[q] += qr[q] * sd; hi[q] += qr[q] * ds; }
-        }
-    }
-}
-
-// Same transform with the wave's coefficient slice Q[k < NK/2][8*g8 .. 8*g8+7] held in VGPRs (element 8k+r in register
-// (8k+r) >> 6, lane (8k+r) & 63; loaded once per kernel by fd_load_slice) and moved to SGPR pairs with v_readlane: the
-// 16 KB corner of Qy does not stay in the scalar cache, and an s_load miss costs more than 8 extra VALU instructions.
-template <int NK>
-__device__ __forceinline__ void fd_load_slice(const float* __restrict__ Q, int g8, float (&sl)[NK / 16]) {
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int j = 0; j < NK / 16; ++j) sl[j] = Q[(size_t)(8 * j + (lane >> 3)) * NK + 8 * g8 + (lane & 7)];
-}
-template <int NK, int SK>
-__device__ __forceinline__ void fd_trans_rl(const float (&sl)[NK / 16], const float* bp, f2 (&lo)[4], f2 (&hi)[4]) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) { lo[q] = (f2){0.f, 0.f}; hi[q] = (f2){0.f, 0.f}; }
-#pragma unroll
-    for (int k = 0; k < NK / 2; ++k) {
-        const float va = bp[k * SK], vb = bp[(NK - 1 - k) * SK];
-        const float sk = va + vb, dk = va - vb;
-        const f2 sd = {sk, dk};
-        const f2 ds = (k & 1) == 0 ? (f2){dk, sk} : (f2){-dk, -sk};      // (-1)^k
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int e = 8 * k + 2 * q;
-            const float q0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, sl[e >> 6]), e & 63));
-            const float q1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, sl[(e + 1) >> 6]), (e + 1) & 63));
-            const f2 qq = {q0, q1};
-            lo[q] += qq * sd;
-            hi[q] += qq * ds;
-        }
-    }
-}
+// i.e. HALF the multiply-adds and only the [NK/2 x NK/2] corner of Q is read.
 
 // ---- the four sine transforms of a solve on the fp32 matrix cores (v_mfma_f32_32x32x2_f32) ----------------------------------
 // Same peak as the packed VALU, but the operands arrive as plain vector registers: no wave-uniform coefficient stream (v_readlane /
-// s_load per packed FMA), which is what the VALU forms above are bound by (8.0 us for the two forward transforms of a solve against
-// 2.6 us of multiply-adds).  Eight waves = eight 32 x 32 output tiles:
+// s_load per packed FMA), which is what the packed-VALU transforms of rounds 1-3 (v_pk_fma_f32 with SGPR-pair coefficients) were bound
+// by: 8.0 us for the two forward transforms of a solve against 2.6 us of multiply-adds.  Eight waves = eight 32 x 32 output tiles:
 //   y transform (128 rows, symmetry as above): four products [32 j' x 64 k] . [64 k x 64 c], wave = (product p, column half):
 //       p = 0: rows j = 2j'      = sum_k Q[k][j] s_k          p = 2: rows 127 - 2j'       = sum_k (-1)^k Q[k][2j'] d_k
 //       p = 1: rows j = 2j' + 1  = sum_k Q[k][j] d_k          p = 3: rows 127 - (2j' + 1) = sum_k (-1)^k Q[k][2j'+1] s_k
@@ -688,11 +626,7 @@ __device__ __forceinline__ float fd_prefetch(const float* __restrict__ blob, int
 }
 
 __device__ __forceinline__ void fd_load_qys(const float* __restrict__ Qy, int w, float (&qys)[FD_QYS]) {
-#if SOL_FD_MFMA
     fd_load_ay(Qy, w, qys);
-#else
-    fd_load_slice<FD_Y>(Qy, w, qys);
-#endif
 }
 
 // rhs in rf[] (strip layout: rows 16*wave + k, column lane); returns the solution as a [128][64] LDS array (inside buf,
@@ -730,16 +664,12 @@ __device__ __forceinline__ float* fd_solve(const float* __restrict__ blob, const
     float* B0 = buf;
     float* B1 = buf + FD_BUF;
     float* U = B0;                       // [128][17]  u / t2w
-    float* XP = B0 + 2304;               // [2][256]   partial window values
     float* XS = B0 + 2816;               // [SP]       gathered x0 on S
     float* CP = B0 + 3072;               // [2][256]   partial K' x_S
     float* W2 = B0 + 3584;               // [16][16]   -E_SS x_S scattered into the window
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int m = tid & 127, cb = __builtin_amdgcn_readfirstlane(tid >> 7);
-#if !SOL_FD_MFMA
-    f2 lo[4], hi[4];
-#endif
     // this thread's 16 spectral coefficients: index 2q+e -> column 8cb+2q+e, 8+2q+e -> column 63-(8cb+2q+e)
     float t2[16], il[16];
     int col[16];
@@ -754,7 +684,6 @@ __device__ __forceinline__ float* fd_solve(const float* __restrict__ blob, const
 #pragma unroll
         for (int k = 0; k < 16; ++k) B0[(16 * w + k) * FD_LD + lane] = rf[k];
     }
-#if SOL_FD_MFMA
     float bx[32];
     float* XP8 = B0 + 4096;              // [8 waves][256] partial window values (MFMA form)
     // window products on v_mfma_f32_16x16x4_f32 (wave = 16 rows m; B operand lane: column lane & 15, k = lane >> 4).  Two request groups, so
@@ -787,32 +716,9 @@ __device__ __forceinline__ float* fd_solve(const float* __restrict__ blob, const
         B1[m * FD_LD + col[e]] = t2[e];
     }
     __syncthreads();                     // B1 = T2, B0 free
-#else
-    __syncthreads();
-    fd_trans_rl<FD_Y, FD_LD>(qys, B0 + lane, lo, hi);          // rows 8w+r and 127-(8w+r), column lane
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const int r0 = 8 * w + 2 * q;
-        B0[r0 * FD_LD + lane] = lo[q].x; B0[(r0 + 1) * FD_LD + lane] = lo[q].y;
-        B0[(FD_Y - 1 - r0) * FD_LD + lane] = hi[q].x; B0[(FD_Y - 2 - r0) * FD_LD + lane] = hi[q].y;
-    }
-    __syncthreads();
-    fd_trans<FD_X, 1>(F.Qx, B0 + m * FD_LD, cb, lo, hi);       // row m, columns 8cb+r and 63-(8cb+r)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) { t2[2 * q] = lo[q].x; t2[2 * q + 1] = lo[q].y; t2[8 + 2 * q] = hi[q].x; t2[8 + 2 * q + 1] = hi[q].y; }
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-        il[e] = F.ilT[col[e] * FD_Y + m];
-        t2[e] *= il[e];
-        B1[m * FD_LD + col[e]] = t2[e];
-    }
-    __syncthreads();                     // B1 = T2, B0 free
-#endif
     FD_STAMP(9);
 
     // ---- window values of G b:  u = T2 Qx[:, win] ;  x0w = Qy[win, :] u ----------------------
-#if SOL_FD_MFMA
     {
         typedef float fd_f4 __attribute__((ext_vector_type(4)));
         fd_f4 acc = {0.f, 0.f, 0.f, 0.f};
@@ -823,26 +729,8 @@ __device__ __forceinline__ float* fd_solve(const float* __restrict__ blob, const
 #pragma unroll
         for (int r = 0; r < 4; ++r) up[r * FD_ULD] = acc[r];
     }
-#else
-    {
-        f2 u0 = {0.f, 0.f}, u1 = {0.f, 0.f};
-        fd_cfp Qc = (fd_cfp)(F.QxW + 4 * cb);           // QxW[c][i'] = Qx[c][wx0 + i']: 64 B per c
-        const float* bp = B1 + m * FD_LD;
-#pragma unroll 8
-        for (int c = 0; c < FD_X; ++c) {
-            const float v = bp[c];
-            const f2 vv = {v, v};
-            fd_cfp qr = Qc + (size_t)c * FD_WIN;
-            u0 += (f2){qr[0], qr[1]} * vv;
-            u1 += (f2){qr[2], qr[3]} * vv;
-        }
-        float* up = U + m * FD_ULD + 4 * cb;
-        up[0] = u0.x; up[1] = u0.y; up[2] = u1.x; up[3] = u1.y;
-    }
-#endif
     __syncthreads();
     FD_STAMP(10);
-#if SOL_FD_MFMA
     {
         typedef float fd_f4 __attribute__((ext_vector_type(4)));
         fd_f4 acc = {0.f, 0.f, 0.f, 0.f};
@@ -873,24 +761,6 @@ __device__ __forceinline__ float* fd_solve(const float* __restrict__ blob, const
         }
         XS[tid] = v;
     }
-#else
-    {
-        const int h = tid >> 8, t = tid & 255, jw = t >> 4, iw = t & 15;
-        const float* qrow = F.Qy + (size_t)(F.wy0 + jw) * FD_Y + 64 * h;
-        const float* up = U + (64 * h) * FD_ULD + iw;
-        float s = 0.f;
-#pragma unroll 8
-        for (int mm = 0; mm < 64; ++mm) s += qrow[mm] * up[mm * FD_ULD];
-        XP[h * 256 + t] = s;
-        if (tid < 256) W2[tid] = 0.f;
-    }
-    __syncthreads();
-    FD_STAMP(11);
-    if (tid < F.SP) {
-        const int si = F.sidx[tid];
-        XS[tid] = si >= 0 ? XP[si] + XP[256 + si] : 0.f;
-    }
-#endif
     __syncthreads();
     // ---- c = K' x0_S  (two halves of the sum), scattered with a minus sign into the window -----
     if (tid < 2 * F.SP) {
@@ -910,7 +780,6 @@ __device__ __forceinline__ float* fd_solve(const float* __restrict__ blob, const
     }
     __syncthreads();
     // ---- spectral coefficients of the correction: t2w = Qy[:, win] W2 ; T2 += (t2w Qx[win, :]) / lam
-#if SOL_FD_MFMA
     {
         typedef float fd_f4 __attribute__((ext_vector_type(4)));
         fd_f4 acc = {0.f, 0.f, 0.f, 0.f};
@@ -921,28 +790,8 @@ __device__ __forceinline__ float* fd_solve(const float* __restrict__ blob, const
 #pragma unroll
         for (int r = 0; r < 4; ++r) up[r * FD_ULD] = acc[r];
     }
-#else
-    {
-        f2 a0 = {0.f, 0.f}, a1 = {0.f, 0.f};
-        float qw[FD_WIN];
-#pragma unroll
-        for (int jw = 0; jw < FD_WIN; ++jw) qw[jw] = F.Qy[(size_t)(F.wy0 + jw) * FD_Y + m];
-        __builtin_amdgcn_sched_barrier(0);              // all 16 requests in flight before the first use (1.6 -> 0.7 us)
-#pragma unroll
-        for (int jw = 0; jw < FD_WIN; ++jw) {
-            const float qv = qw[jw];
-            const float4 wv = *reinterpret_cast<const float4*>(W2 + jw * FD_WIN + 4 * cb);
-            const f2 qq = {qv, qv};
-            a0 += qq * (f2){wv.x, wv.y};
-            a1 += qq * (f2){wv.z, wv.w};
-        }
-        float* up = U + m * FD_ULD + 4 * cb;
-        up[0] = a0.x; up[1] = a0.y; up[2] = a1.x; up[3] = a1.y;
-    }
-#endif
     __syncthreads();
     FD_STAMP(13);
-#if SOL_FD_MFMA
     {
         // S[m][c] = sum_i' t2w[m][i'] Qx[wx0+i'][c] on the matrix cores (wave = rows 16w .. 16w+15, four 16-column tiles) -> XS2 (= B0 behind
         // the small scratch arrays ... B0 is free but U / W2 live in its head: the products go to B1's free twin rows, see below)
@@ -969,66 +818,15 @@ __device__ __forceinline__ float* fd_solve(const float* __restrict__ blob, const
             B1[m * FD_LD + col[e]] = t2[e];
         }
     }
-#else
-    {
-        // T2[m][c] += il * sum_i' t2w[m][i'] Qx[wx0+i'][c] for this thread's 16 columns (8 contiguous + their 8 mirrors)
-        f2 al[4], ah[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) { al[q] = (f2){0.f, 0.f}; ah[q] = (f2){0.f, 0.f}; }
-        fd_cfp Ql = (fd_cfp)(F.Qx + (size_t)F.wx0 * FD_X + 8 * cb);
-        fd_cfp Qh = (fd_cfp)(F.Qx + (size_t)F.wx0 * FD_X + (FD_X - 8 - 8 * cb));
-        const float* up = U + m * FD_ULD;
-#pragma unroll 4
-        for (int iw = 0; iw < FD_WIN; ++iw) {
-            const float v = up[iw];
-            const f2 vv = {v, v};
-            fd_cfp ql = Ql + (size_t)iw * FD_X;
-            fd_cfp qh = Qh + (size_t)iw * FD_X;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                al[q] += (f2){ql[2 * q], ql[2 * q + 1]} * vv;
-                ah[q] += (f2){qh[7 - 2 * q], qh[6 - 2 * q]} * vv;       // columns 63-(8cb+2q), 62-(8cb+2q)
-            }
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            t2[2 * q] += il[2 * q] * al[q].x; t2[2 * q + 1] += il[2 * q + 1] * al[q].y;
-            t2[8 + 2 * q] += il[8 + 2 * q] * ah[q].x; t2[8 + 2 * q + 1] += il[8 + 2 * q + 1] * ah[q].y;
-        }
-#pragma unroll
-        for (int e = 0; e < 16; ++e) B1[m * FD_LD + col[e]] = t2[e];
-    }
-#endif
     __syncthreads();
     FD_STAMP(14);
     // ---- inverse transform: x = Qy (T2 Qx), written to B1 as [128][64] for the caller ---------------
-#if SOL_FD_MFMA
     fd_mfma_x(bx, B1, B0, w);
     __syncthreads();                     // B0 = T3; every read of B1 (T2) is done
     FD_STAMP(15);
     fd_mfma_y<FD_X>(qys, B0, B1, w);
     __syncthreads();                     // solution complete in LDS
     return B1;
-#else
-    fd_trans<FD_X, 1>(F.Qx, B1 + m * FD_LD, cb, lo, hi);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const int c0 = 8 * cb + 2 * q;
-        B0[m * FD_LD + c0] = lo[q].x; B0[m * FD_LD + c0 + 1] = lo[q].y;
-        B0[m * FD_LD + FD_X - 1 - c0] = hi[q].x; B0[m * FD_LD + FD_X - 2 - c0] = hi[q].y;
-    }
-    __syncthreads();                     // B0 = T3; every read of B1 (T2) is done
-    FD_STAMP(15);
-    fd_trans_rl<FD_Y, FD_LD>(qys, B0 + lane, lo, hi);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const int r0 = 8 * w + 2 * q;
-        B1[r0 * FD_X + lane] = lo[q].x; B1[(r0 + 1) * FD_X + lane] = lo[q].y;
-        B1[(FD_Y - 1 - r0) * FD_X + lane] = hi[q].x; B1[(FD_Y - 2 - r0) * FD_X + lane] = hi[q].y;
-    }
-    __syncthreads();                     // solution complete in LDS
-    return B1;
-#endif
 }
 
 __device__ __forceinline__ float* fd_solve(const float* __restrict__ blob, const float (&qys)[FD_QYS], float* buf, const float (&rf)[16], long long* prof) {
@@ -1109,7 +907,7 @@ __device__ __forceinline__ float* fd_solve_small(const float* __restrict__ blob,
     // and trip -- A operand lane (m = lane & 15, k = lane >> 4) = At[k][m0 + m], B operand = Bm[k][n0 + n], both contiguous LDS reads; tile
     // element r of a lane: row m0 + 4 (lane >> 4) + r, column n0 + (lane & 15).  The 4 x 4 register-tile form below kept half of the 256
     // threads busy in the large products and spent two LDS reads per 16 multiply-adds.
-    const bool mfma_ok = SOL_FD_MFMA && (Y & 15) == 0 && (X & 15) == 0;
+    const bool mfma_ok = (Y & 15) == 0 && (X & 15) == 0;
     auto mm = [&](const float* At, int lda, const float* Bm, int ldb, float* C, int ldc, int M, int N, int K, int mode, const float* S) {
         if (mfma_ok) {
             typedef float fd_f4 __attribute__((ext_vector_type(4)));
@@ -2208,14 +2006,12 @@ __global__ void __launch_bounds__(512) k_karman_bwd_bww(StepArgs a, BwPack bw) {
         // XCD-aware job order (workgroup u runs on XCD u % 8): the 32-row blocks of image rows 96x .. 96x+95 -- what XCD x's
         // convolution workgroups wrote (xcd_tile) -- are handed to the gradient workgroups of XCD x, layer after layer
         int idx = (int)blockIdx.x - a.B, job = idx / bw.wg_per, sub = idx % bw.wg_per;
-#ifndef SOL_NO_XCD_REMAP
         if ((bw.wg_per & 7) == 0) {
             const int u = (int)blockIdx.x, x = u & 7, per = bw.wg_per >> 3;
             const int s = (u - (a.B + ((x - a.B) & 7))) >> 3;          // rank of this workgroup among the gradient workgroups of XCD x
             job = s / per;
             sub = x * per + s % per;
         }
-#endif
         const bool stamp = a.prof && threadIdx.x == 0 && (idx == 0 || (int)blockIdx.x == (int)gridDim.x - 1);   // step_prof only
         if (stamp) a.prof[idx == 0 ? 16 : 18] = wall_clock64();
         sbk::bww_sb_body<2>(bw.a[job], sub, reinterpret_cast<unsigned char*>(smem));

@@ -13,13 +13,8 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 __host__ __device__ __forceinline__ int swzb(int idx) { return ((idx >> 2) & 1) << 1; }
 // chunk swizzles of the weight-gradient staging planes (bww_sb_body): see the layout comment there
-#ifdef BW_SWZ_READS_ONLY      // A/B switch (tools/ab_lib.py): the swizzles of rounds 1-4, conflict-free for the reads only
-__host__ __device__ __forceinline__ int bw_swx(int ch) { return ch & 15; }
-__host__ __device__ __forceinline__ int bw_swz(int ch) { return (ch >> 1) & 7; }
-#else
 __host__ __device__ __forceinline__ int bw_swx(int ch) { return ((ch ^ (ch >> 2)) & 3) | ((((ch >> 2) ^ (ch >> 4)) & 1) << 2) | (((ch >> 3) & 1) << 3); }
 __host__ __device__ __forceinline__ int bw_swz(int ch) { return (((ch >> 1) ^ (ch >> 4)) & 1) | (((ch >> 2) & 3) << 1); }
-#endif
 
 // two fp32 -> packed pair of bf16 (round to nearest even), low half = first element
 __device__ __forceinline__ unsigned pk_bf16(float x, float y) {
@@ -88,27 +83,9 @@ __device__ __forceinline__ void split2u(float x, float y, float scale, unsigned&
 // Both are linear over GF(2) in the channel bits b0..b4:  x: (b0^b2, b1^b3, b2^b4, b3);  dz: (b1^b4, b2, b3)  [dz rows are 128 B:
 // b0 selects the half of the bank row].  A lane group's two chunk bases differ by 1 (g, g+1): the sets stay disjoint because the
 // channel pairs that differ by the pre-image of 1 (li ^ 1 for x, li ^ 2 for dz) lie in the same half of the group.
-#ifndef BWW_B_UPFRONT
-#define BWW_B_UPFRONT 1
-#endif
-#ifndef BWW_PHASE_SHIFT
-#define BWW_PHASE_SHIFT 1
-#endif
-#ifndef BWW_PIPE        // KIND 2: rows are staged ONE ROW FURTHER AHEAD (x row gr + 2 / dz row gr + 4 during row gr) and a wave reads the operand
-#define BWW_PIPE 0      // fragments of row gr + 1 at the TAIL of row gr, in front of the row barrier: the first MFMA of a row waits for no LDS round trip
-#endif
-#ifndef BWW_REQ_LATE    // BWW_PIPE: the dz role (which stages at the head of the row, on the row's critical path) issues its requests BEHIND its staging
-#define BWW_REQ_LATE 1
-#endif
-#ifndef BWW_PIN_ORDER
-#define BWW_PIN_ORDER 1
-#endif
-#ifndef BWW_Z_ROTATE     // KIND 2: the dz fragments live in registers ACROSS rows (row gr's tap row dy is row gr+1's tap row dy+1): one new
-#define BWW_Z_ROTATE 1   // fragment pair is read per row instead of five (0: all five re-read from the ring every row, rounds 4-6)
-#endif
-#ifndef BWW_DBG        // timing experiments (tools/ab_lib.py variants + tools/bww3d_time.py; results invalid): 1 no MFMAs, 2 no staging (the
-#define BWW_DBG 0      // requests die with it), 4 no row barrier, 8 no requests.  Measured per 32 -> 32 Conv3D layer at 128 x 64 x 64 (five
-#endif                 // passes + reduce, 464 us): 187 / 345 / 404 / 354 us; staging interleaved into the MFMA stream (branch-free, one basic block): 460 us
+// Removal experiments of the row loop (timing only), per 32 -> 32 Conv3D layer at 128 x 64 x 64 (five passes + reduce, 464 us): no MFMAs
+// 187 us, no staging (the requests die with it) 345, no row barrier 404, no requests 354; staging interleaved into the MFMA stream
+// (branch-free, one basic block): 460 us.
 // -DBWW_PROF (tools/bww_row_probe.py): per-WAVE s_memtime stamps (low 32 bits), six per image row, kept in the unused LDS behind the KIND-2
 // ring (81,920 .. 122,880) and dumped before the fold: [workgroup][wave][row][8] into the buffer set with sol_bww_prof_set().
 #ifdef BWW_PROF
@@ -190,7 +167,6 @@ __device__ __forceinline__ void bww_sb_body(const BwArgs& a, const int blk, unsi
     // WIDE: the halo item of x row gx_row (dz role: a dropped request of the same shape)
     auto request_halo = [&](int gx_row, float4& h) __attribute__((always_inline)) {
         if constexpr (WIDE) {
-            if (BWW_DBG & 8) { h = make_float4(1e-3f, 2e-3f, -1e-3f, 5e-4f); return; }
             const f32x4 e = row_ptr(xrole ? gx_row : r0)[hoff];
             h = make_float4(e[0], e[1], e[2], e[3]);
         }
@@ -200,7 +176,6 @@ __device__ __forceinline__ void bww_sb_body(const BwArgs& a, const int blk, unsi
         // (global address space spelled out: a pointer made from the opaque integer is generic, and flat loads also count in
         // lgkmcnt -- the LDS-only barriers below would wait for them)
         const auto rp = row_ptr(gr);
-        if (BWW_DBG & 8) { v0 = v1 = make_float4(1e-3f, 2e-3f, -1e-3f, 5e-4f); return; }
         const f32x4 q0 = rp[(2 * pxg) * 8 + c4], q1 = rp[(2 * pxg + 1) * 8 + c4];
         v0 = make_float4(q0[0], q0[1], q0[2], q0[3]);
         v1 = make_float4(q1[0], q1[1], q1[2], q1[3]);
@@ -264,10 +239,9 @@ __device__ __forceinline__ void bww_sb_body(const BwArgs& a, const int blk, unsi
     // ---- prologue: dz rows r0-2 .. r0+2 and x row r0 go to LDS; the items of x rows r0+1, r0+2 / dz rows r0+3, r0+4 are
     //      requested into the register sets B and C (three rows of look-ahead: the operands come from HBM -- forward activations
     //      and gradients written hundreds of launches ago -- and a row of MFMA work covers about half of that round trip).
-    //      PIPE (KIND 2): everything one row further -- x rows r0, r0+1 and dz rows r0-2 .. r0+3 staged, sets B / C = x rows r0+2, r0+3 /
-    //      dz rows r0+4, r0+5 ----
-    constexpr bool PIPE = KIND == 2 && BWW_B_UPFRONT && BWW_Z_ROTATE && BWW_PIPE;
-    constexpr int XD = PIPE ? 2 : 1, ZD = PIPE ? 4 : 3;          // row gr stages x row gr + XD and dz row gr + ZD
+    //      (KIND 2 with everything one row further ahead -- x row gr + 2 / dz row gr + 4 staged during row gr, the fragments of row gr + 1
+    //      read at the tail of row gr so that a row's first MFMA waits for no LDS round trip -- was built and did not ship) ----
+    constexpr int XD = 1, ZD = 3;                                // row gr stages x row gr + XD and dz row gr + ZD
     float4 sA0, sA1, sB0, sB1, sC0, sC1;
     sA0 = sA1 = sB0 = sB1 = sC0 = sC1 = make_float4(0.f, 0.f, 0.f, 0.f);
     float4 hP, hQ;                                               // WIDE: the halo items of x rows gr + XD (staged in row gr) and gr + XD + 1
@@ -275,6 +249,8 @@ __device__ __forceinline__ void bww_sb_body(const BwArgs& a, const int blk, unsi
     {
         constexpr int NZ0 = ZD + 2;                              // dz rows staged here: r0-2 .. r0+ZD-1
         float4 pv[NZ0][2], ph[XD];
+        // (the x role's three loops over the XD = 1 rows staged here stay loops: written as plain statements they fold before the
+        //  unroller runs, and the prologue's address arithmetic and register assignment come out in another order)
 #pragma unroll
         for (int k = 0; k < XD; ++k) request_halo(r0 + k < r1 ? r0 + k : r0, ph[k]);
         if (xrole) {
@@ -317,31 +293,21 @@ __device__ __forceinline__ void bww_sb_body(const BwArgs& a, const int blk, unsi
     const int c0 = 4 * kb + g;
     const int swx_l = bw_swx(16 * mt + li), swz_l = bw_swz(16 * nt + li);      // this lane's channel rows of the x / dz operands
 
-    // KIND 2, BWW_Z_ROTATE: Bz[dy] = this lane's fragments of dz row gr + 2 - dy.  Row gr + 1 meets the same dz rows one tap row further
-    // down, so the set is SHIFTED at the head of a row and only Bz[0] (dz row gr + 2, staged during the previous row) is read: 6
-    // ds_reads (13 -> 5 KB) per wave and row instead of 14 -- the operand reads of a row were 106 KB per CU, ~900 clocks of the LDS
-    // pipe in front of every row's first MFMA.  Same products in the same order: bit-identical sums.
+    // KIND 2: the dz fragments of ALL five tap rows live in registers, ACROSS rows (40 VGPRs): Bz[dy] = this lane's fragments of dz row
+    // gr + 2 - dy.  Row gr + 1 meets the same dz rows one tap row further down, so the set is SHIFTED at the head of a row and only Bz[0]
+    // (dz row gr + 2, staged during the previous row) is read: one exposed LDS round trip per row instead of one per tap row in front of
+    // every group of 15 MFMAs, and 6 ds_reads (13 -> 5 KB) per wave and row instead of the 14 of re-reading all five from the ring
+    // (rounds 4-6) -- the operand reads of a row were 106 KB per CU, ~900 clocks of the LDS pipe in front of every row's first MFMA.
+    // Same products in the same order: bit-identical sums.  (Rows outside the image: the read hits a valid ring slot and is dropped.)
     uint4 Bz[5][NPL];
     auto read_z = [&](int gz, uint4 (&dst)[NPL]) __attribute__((always_inline)) {
         const unsigned char* zs = ZS + ((gz + 6) % 6) * BW_ZST + (16 * nt + li) * 128 + ((c0 ^ swz_l) << 4);
 #pragma unroll
         for (int pl = 0; pl < NPL; ++pl) dst[pl] = *reinterpret_cast<const uint4*>(zs + pl * BW_ZPL);
     };
-    // PIPE: the raw x fragments (16 + 8 bytes per plane) of the NEXT row and the dz fragments of dz row gr + 3, read at the tail of row gr
-    uint4 Aq[NPL], Bn[NPL];
-    uint2 Ae[NPL];
-    auto read_x = [&](int gx) __attribute__((always_inline)) {
-        const unsigned char* xs = XS + (gx & 1) * BW_XST + (16 * mt + li) * 256;
-#pragma unroll
-        for (int pl = 0; pl < NPL; ++pl) {
-            Aq[pl] = *reinterpret_cast<const uint4*>(xs + pl * BW_XPL + ((c0 ^ swx_l) << 4));
-            Ae[pl] = *reinterpret_cast<const uint2*>(xs + pl * BW_XPL + (((c0 + 1) ^ swx_l) << 4));
-        }
-    };
-    if constexpr (KIND == 2 && BWW_B_UPFRONT && BWW_Z_ROTATE) {
+    if constexpr (KIND == 2) {
 #pragma unroll
         for (int dy = 0; dy < 4; ++dy) read_z(r0 + 1 - dy, Bz[dy]);      // rows r0+1 .. r0-2: do_row(r0) shifts them to dy = 1 .. 4
-        if constexpr (PIPE) { read_x(r0); read_z(r0 + 2, Bn); }
     }
 
     // one image row: request the items of x row gr+XD+2 / dz row gr+ZD+2 into (i0, i1), run the 25 taps of row gr, write the items
@@ -353,35 +319,29 @@ __device__ __forceinline__ void bww_sb_body(const BwArgs& a, const int blk, unsi
 #ifdef BWW_PROF
         { const unsigned t_ = (unsigned)__builtin_amdgcn_s_memrealtime(); if (lane == 0 && gr - r0 < 40) bww_st[(gr - r0) * 8 + 6] = t_; }      // 100 MHz: the clock the CU holds
 #endif
-        const bool req_late = PIPE && BWW_REQ_LATE && !xrole;            // (wave uniform)
         request_halo(gr + XD + 1 < r1 ? gr + XD + 1 : r0, hi);
-        if (!req_late) request(gr + XD + 2 < r1 ? gr + XD + 2 : r0, gr + ZD + 2, i0, i1);
+        request(gr + XD + 2 < r1 ? gr + XD + 2 : r0, gr + ZD + 2, i0, i1);
         __builtin_amdgcn_sched_barrier(0);
         // Phase shift between the two waves of a SIMD (waves w and w + 4): the dz role stages its row at the HEAD of the iteration, the x role
         // at its tail -- one wave's split / ds_write phase then lies under the other wave's MFMA block instead of both staging (matrix pipe
         // idle) and both multiplying at the same time.  Legal: the slot written (dz row gr+ZD) is read by nobody during this iteration.
-        // Same-box A/B, three alternations (tools/ab_lib.py): 0 (both late) 11.554, 1 (dz early) 11.430, 2 (x early) 11.612, 3 (both early) 11.521 ms per step.
-        if (BWW_PHASE_SHIFT == 1 && !xrole) {
-            if (!(BWW_DBG & 2) && z_in_range(gr + ZD)) stage(gr + XD, gr + ZD, o0, o1, ho);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        if (BWW_PHASE_SHIFT == 2 && xrole) {            // (variant: the x role stages early, the dz role late)
-            if (!(BWW_DBG & 2) && gr + XD < r1) stage(gr + XD, gr + ZD, o0, o1, ho);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        if (BWW_PHASE_SHIFT == 3) {                     // (variant: both roles stage early)
-            if (!(BWW_DBG & 2) && (xrole ? gr + XD < r1 : z_in_range(gr + ZD))) stage(gr + XD, gr + ZD, o0, o1, ho);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        if (req_late) {
-            request(gr + XD + 2 < r1 ? gr + XD + 2 : r0, gr + ZD + 2, i0, i1);
+        // Same-box A/B, three alternations (tools/ab_lib.py): both late 11.554, dz early (this) 11.430, x early 11.612, both early 11.521 ms per step.
+        if (!xrole) {
+            if (z_in_range(gr + ZD)) stage(gr + XD, gr + ZD, o0, o1, ho);
             __builtin_amdgcn_sched_barrier(0);
         }
 
         // x operand of this lane: pixels 8*c0 .. 8*c0+11 (halo coordinates) of channel 16*mt + li, three planes
         uint4 A[NPL][5];
         {
-            if constexpr (!PIPE) read_x(gr);            // (PIPE: read at the tail of the previous row)
+            uint4 Aq[NPL];                              // the raw fragments: 16 + 8 bytes per plane
+            uint2 Ae[NPL];
+            const unsigned char* xs = XS + (gr & 1) * BW_XST + (16 * mt + li) * 256;
+#pragma unroll
+            for (int pl = 0; pl < NPL; ++pl) {
+                Aq[pl] = *reinterpret_cast<const uint4*>(xs + pl * BW_XPL + ((c0 ^ swx_l) << 4));
+                Ae[pl] = *reinterpret_cast<const uint2*>(xs + pl * BW_XPL + (((c0 + 1) ^ swx_l) << 4));
+            }
 #pragma unroll
             for (int pl = 0; pl < NPL; ++pl) {
                 const uint4 q = Aq[pl];
@@ -395,44 +355,32 @@ __device__ __forceinline__ void bww_sb_body(const BwArgs& a, const int blk, unsi
                                       __builtin_amdgcn_alignbit(e.x, q.w, 16), __builtin_amdgcn_alignbit(e.y, e.x, 16));
             }
         }
-        if constexpr (KIND == 2 && BWW_B_UPFRONT) {
-            // the dz fragments of ALL five tap rows are in registers at the head of the row (40 VGPRs): one exposed LDS
-            // round trip per row instead of one per tap row in front of every group of 15 MFMAs (rows outside the image: the read
-            // hits a valid ring slot and is dropped)
-            uint4 (&Bv)[5][NPL] = Bz;
+        if constexpr (KIND == 2) {
             BWW_STAMP(gr, 1);                           // (early staging issued; the stamp itself waits for lgkmcnt(0): LDS writes done)
-            if constexpr (BWW_Z_ROTATE) {
 #pragma unroll
-                for (int dy = 4; dy > 0; --dy)
+            for (int dy = 4; dy > 0; --dy)
 #pragma unroll
-                    for (int pl = 0; pl < NPL; ++pl) Bv[dy][pl] = Bv[dy - 1][pl];
-                if constexpr (PIPE) {
-#pragma unroll
-                    for (int pl = 0; pl < NPL; ++pl) Bv[0][pl] = Bn[pl];
-                } else read_z(gr + 2, Bv[0]);
-            } else {
-#pragma unroll
-                for (int dy = 0; dy < 5; ++dy) read_z(gr + 2 - dy, Bv[dy]);
-            }
+                for (int pl = 0; pl < NPL; ++pl) Bz[dy][pl] = Bz[dy - 1][pl];
+            read_z(gr + 2, Bz[0]);
             __builtin_amdgcn_sched_barrier(0);
             BWW_STAMP(gr, 2);                           // operand fragments in registers
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int dy = 0; dy < 5; ++dy) {
                 const int yz = y + 2 - dy;
-                if (yz < 0 || yz >= H || (BWW_DBG & 1)) continue;        // workgroup uniform
+                if (yz < 0 || yz >= H) continue;                        // workgroup uniform
                 constexpr int QA[3] = {1, 0, 0}, QB[3] = {0, 1, 0};     // a2 b1, a1 b2, a1 b1
 #pragma unroll
                 for (int pr = 0; pr < 3; ++pr)
 #pragma unroll
                     for (int dx = 0; dx < 5; ++dx) {
-                        acc[dy * 5 + dx] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, A[QA[pr]][dx]), __builtin_bit_cast(f16x8, Bv[dy][QB[pr]]),
+                        acc[dy * 5 + dx] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, A[QA[pr]][dx]), __builtin_bit_cast(f16x8, Bz[dy][QB[pr]]),
                                                                                   acc[dy * 5 + dx], 0, 0, 0);
                         // SOURCE ORDER pinned: the scheduler emitted the three groups of five as a snake (dx 0..4, 4..0, 0..4), i.e. two
                         // pairs of back-to-back DEPENDENT MFMAs per tap row; a dependent 16x16x32 MFMA issues ~4 slots after its
                         // producer (round-robin over five accumulators hides that, the snake does not: 21.6 instead of 16 clocks per
                         // MFMA while a wave has the matrix pipe to itself, tools/bww_row_probe.py)
-                        if (BWW_PIN_ORDER) __builtin_amdgcn_sched_barrier(0);
+                        __builtin_amdgcn_sched_barrier(0);
                     }
             }
         } else {
@@ -443,40 +391,22 @@ __device__ __forceinline__ void bww_sb_body(const BwArgs& a, const int blk, unsi
                 const int gz = gr + 2 - dy;
                 const unsigned char* zs = ZS + ((gz + 6) % 6) * BW_ZST + (16 * nt + li) * 128 + ((c0 ^ swz_l) << 4);
                 uint4 Bv[NPL];
-    #pragma unroll
+#pragma unroll
                 for (int pl = 0; pl < NPL; ++pl) Bv[pl] = *reinterpret_cast<const uint4*>(zs + pl * BW_ZPL);
-                if constexpr (KIND == 2) {
-                    constexpr int QA[3] = {1, 0, 0}, QB[3] = {0, 1, 0};     // a2 b1, a1 b2, a1 b1
-    #pragma unroll
-                    for (int pr = 0; pr < 3; ++pr)
-    #pragma unroll
-                        for (int dx = 0; dx < 5; ++dx)
-                            acc[dy * 5 + dx] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, A[QA[pr]][dx]), __builtin_bit_cast(f16x8, Bv[QB[pr]]),
-                                                                                      acc[dy * 5 + dx], 0, 0, 0);
-                } else {
-    #pragma unroll
-                    for (int pr = 0; pr < 6; ++pr)
-    #pragma unroll
-                        for (int dx = 0; dx < 5; ++dx)
-                            acc[dy * 5 + dx] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, A[PA[pr]][dx]), __builtin_bit_cast(bf16x8, Bv[PB[pr]]),
-                                                                                       acc[dy * 5 + dx], 0, 0, 0);
-                }
+#pragma unroll
+                for (int pr = 0; pr < 6; ++pr)
+#pragma unroll
+                    for (int dx = 0; dx < 5; ++dx)
+                        acc[dy * 5 + dx] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, A[PA[pr]][dx]), __builtin_bit_cast(bf16x8, Bv[PB[pr]]),
+                                                                                   acc[dy * 5 + dx], 0, 0, 0);
             }
-}
+        }
         __builtin_amdgcn_sched_barrier(0);
         BWW_STAMP(gr, 3);                               // last MFMA issued
         __builtin_amdgcn_sched_barrier(0);
-        if (!(BWW_DBG & 2) && (xrole ? ((BWW_PHASE_SHIFT & 2) == 0 && gr + XD < r1) : ((BWW_PHASE_SHIFT & 1) == 0 && z_in_range(gr + ZD)))) stage(gr + XD, gr + ZD, o0, o1, ho);
-        if constexpr (PIPE) {
-            // operands of row gr + 1: x row gr + 1 and dz row gr + 3 were staged during row gr - 1 (visible since its barrier); the slots written
-            // during THIS row (x row gr + 2, dz row gr + 4) are other slots.  The x role waits for the barrier here anyway; for the dz role the
-            // round trip replaces the one that stood in front of its MFMA block.
-            __builtin_amdgcn_sched_barrier(0);
-            read_x(gr + 1);
-            read_z(gr + 3, Bn);
-        }
+        if (xrole && gr + XD < r1) stage(gr + XD, gr + ZD, o0, o1, ho);
         BWW_STAMP(gr, 4);                               // late staging written (lgkmcnt(0))
-        if (!(BWW_DBG & 4)) BW_BARRIER();
+        BW_BARRIER();
         BWW_STAMP(gr, 5);
     };
     // (six rows per trip: at the loop's back edge the compiler's wait-count pass gives up on the requests in flight and waits
@@ -506,9 +436,10 @@ __device__ __forceinline__ void bww_sb_body(const BwArgs& a, const int blk, unsi
     // ---- fold the two pixel halves through LDS and add into this block's partial slice --------
     // All 512 threads move 16-byte pieces (4 consecutive co of one ci) into the block's partial slice.  Accumulating launches first
     // request ALL of the thread's thirteen old pieces (the slice was written an unrolled step ago: HBM-cold), then add and store --
-    // as a load-add-store loop the compiler kept one or two requests in flight.  BWW_OLD_EARLY: the requests go out BEFORE the fold
+    // as a load-add-store loop the compiler kept one or two requests in flight.  The requests go out BEFORE the fold
     // (they depend on nothing it does), and the fold's two barriers are LDS-only, so the cold round trip lies under the fold's
-    // LDS traffic instead of behind it.
+    // LDS traffic instead of behind it: against requests behind the fold, same-box A/B (tools/ab_lib.py, three alternations)
+    // 11.437 -> 11.392 ms per C3 step, karman-3d neutral; same sums bit for bit.
     float* pw = a.partial + (size_t)blk * (25 * 1024);
     constexpr int NP = (4 * 25 * 64 + 511) / 512;       // 13 (the last one for threads < 256)
     auto dst_of = [&](int e) {
@@ -526,15 +457,7 @@ __device__ __forceinline__ void bww_sb_body(const BwArgs& a, const int blk, unsi
         }
         __builtin_amdgcn_sched_barrier(0);
     };
-#ifndef BWW_OLD_EARLY      // same-box A/B (tools/ab_lib.py, three alternations): 11.437 -> 11.392 ms per C3 step, karman-3d neutral; same sums bit for bit
-#define BWW_OLD_EARLY 1
-#endif
-#if BWW_OLD_EARLY
-#define BW_FOLD_BARRIER() BW_BARRIER()
     request_old();
-#else
-#define BW_FOLD_BARRIER() __syncthreads()
-#endif
     float* red = reinterpret_cast<float*>(smem_sb);      // [4 waves][25 taps][256]
     if (kb == 1) {
 #pragma unroll
@@ -542,7 +465,7 @@ __device__ __forceinline__ void bww_sb_body(const BwArgs& a, const int blk, unsi
 #pragma unroll
             for (int r = 0; r < 4; ++r) red[((wave & 3) * 25 + tp) * 256 + (4 * g + r) * 16 + li] = acc[tp][r];
     }
-    BW_FOLD_BARRIER();
+    BW_BARRIER();
     if (kb == 0) {      // second pixel half added in LDS, scaled: red = this block's complete [tile][tap][16 ci][16 co] sums
 #pragma unroll
         for (int tp = 0; tp < 25; ++tp)
@@ -552,15 +475,12 @@ __device__ __forceinline__ void bww_sb_body(const BwArgs& a, const int blk, unsi
                 *q = (acc[tp][r] + *q) * out_scale;
             }
     }
-    BW_FOLD_BARRIER();
+    BW_BARRIER();
     {
         // (round 6, measured: the read-modify-write as no-return global_atomic_add_f32 -- the L2 does it, one add per address and launch, still bit
         //  reproducible -- 12.97 vs 11.12 ms per step: 100 KB of dword atomics per workgroup take ~58 us longer than load - add - store)
         // (round 6, measured: pulling the old slice into the L2 with one dword per line and thread under the MFMAs of the last six rows made the
         //  step SLOWER, 11.76 vs 11.67 ms over three alternations: the requests compete with the row loads the MFMAs are waiting for)
-#if !BWW_OLD_EARLY
-        request_old();
-#endif
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int k = 0; k < NP; ++k) {

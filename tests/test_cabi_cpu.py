@@ -138,12 +138,18 @@ def test_options_table_and_abi_checks(lib):
     for env in ("SOL_STREAMS", "SOL_BWW_CHUNK", "SOL_BWW_NO_SIDE"):
         assert env not in _lib._ENV_OPTIONS and env not in _lib._ENV_INT_OPTIONS, env
     # no getenv left in the library sources, and one stream creation: the capture stream of sol_train_graph_create
+    # the settled compile-time A/B switches of the kernels are gone as well; a comment that recalls one describes it in words
+    retired_macros = ("BW_SWZ_READS_ONLY", "BWW_B_UPFRONT", "BWW_PHASE_SHIFT", "BWW_PIPE", "BWW_REQ_LATE", "BWW_PIN_ORDER", "BWW_Z_ROTATE",
+                      "BWW_DBG", "BWW_OLD_EARLY", "SOL_FD_MFMA", "SOL_NO_XCD_REMAP", "SOL_WT_STORES", "SOL_CONV_TRUNC", "SOL_CONV_LATE_EPI",
+                      "SOL_CONV_EXP_", "SOL_CONV_STAGE_AT", "DX_ACL2", "CH_EXP_")
     csrc = os.path.join(os.path.dirname(sol_amd.__file__), "csrc")
     streams_created = 0
     for f in os.listdir(csrc):
         with open(os.path.join(csrc, f)) as fh:
             text = fh.read()
         assert "getenv" not in text, f
+        for name in retired_macros:
+            assert name not in text, (f, name)
         streams_created += text.count("hipStreamCreate")
     assert streams_created == 1
     # the training workspace of the two trainer shapes of tools/lib_bitcompare.py: the layout did not move when the chains went

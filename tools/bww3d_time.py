@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Time of one 32 -> 32 Conv3D weight gradient (sol_conv3d_bwd_weight: five passes + reduce) at 128 x 64 x 64.
-Usage: python tools/bww3d_time.py   (SOL_HIP_LIB selects a tools/ab_lib.py variant, e.g. the BWW_DBG removal experiments)"""
+Usage: python tools/bww3d_time.py   (SOL_HIP_LIB selects a tools/ab_lib.py variant)"""
 import json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)

@@ -1,8 +1,11 @@
 #!/usr/bin/env python
 """A/B timing of library variants on the 32 -> 32 convolution launch (C3 shape), GPU-bound (50 launches per graph replay).
-    python tools/conv_variants.py --build NAME "-DSOL_CONV_TRUNC=1"   -> lib/libvar_NAME.so (conv5x5_sb.hip recompiled with the flags; no GPU)
+    python tools/conv_variants.py --build NAME "-DSOL_CONV_PROF"      -> lib/libvar_NAME.so (conv5x5_sb.hip recompiled with the given flags; no GPU.
+                                                                         tools/ab_lib.py --build makes variants of any source, with its product flags)
     python tools/conv_variants.py libA.so libB.so ...                 (on the GPU box; each library is timed in its own process)
-Round-1 result (us per launch, lrelu + absmax): return at entry 1.74 | + prologue 3.3 | + tap-row loop 10.0 | full 12.5."""
+Prints four epilogue timings per library and the variant's error against a float64 convolution.
+Round-1 result with kernels that returned early (us per launch, lrelu + absmax): return at entry 1.74 | + prologue 3.3 | + tap-row loop 10.0 |
+full 12.5.  Those truncation macros have left the kernel; the parent of the commit "Retire settled A/B switches from the kernels" rebuilds them."""
 import os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
