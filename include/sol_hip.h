@@ -143,6 +143,13 @@ int sol_karman_direct_supported(int32_t Y, int32_t X);
  * (grid, window origin/size, number of perturbed cells: they size the launches).  `workspace`: DEVICE scratch of
  * sol_karman_step_large_workspace_bytes(cfg) bytes. */
 size_t sol_karman_step_large_workspace_bytes(const sol_karman_cfg* cfg);
+/* The same, sized from the HOST header of the blob in cfg.direct.  The direct entry points of the large-grid step read the header's
+ * magic word: "FD02" = the one-window blob above, "FDS1" = the SCATTERED blob (precond.scattered_solver_blob: the support set S of the
+ * obstacle -- solid cells and their neighbours, at most 4096 -- as a row list R, a column list C and a slot index per cell; any scene,
+ * however spread out).  The scattered solve runs box forward, U = T2 Qx[:,C], X0 = Qy[R,:] U, the capacitance product on the rows of K'
+ * split over workgroups (fixed summation order, no atomics), V = Qy[:,R] W2, T1 = V Qx[C,:], scale-add, box back; its scratch follows
+ * |R| and |C|, so size the workspace with this function (for an FD02 header or NULL it returns sol_karman_step_large_workspace_bytes). */
+size_t sol_karman_step_large_workspace_bytes_for(const sol_karman_cfg* cfg, const int32_t* direct_header_host);
 int sol_karman_step_fwd_large(const sol_karman_cfg* cfg, void* stream,
                               const float* d_in, const float* vy_in, const float* vx_in,
                               const float* re, const float* active, const float* inflow,
@@ -196,6 +203,10 @@ int sol_karman_correct(void* stream, const float* out, float* vy, float* vx, flo
 int sol_karman_pressure_solve_large(const sol_karman_cfg* cfg, void* stream, const float* active, const float* rhs, float* p,
                                     const float* box_blob, const int32_t* box_header_host, int32_t* cg_info,
                                     void* workspace, size_t workspace_bytes);
+/* The direct step's pressure solve alone, for either blob of cfg.direct (one window or scattered): M p = rhs; rhs, p [B,Y,X] (rhs is read
+ * only).  `workspace`: sol_karman_step_large_workspace_bytes_for(cfg, direct_header_host) bytes serve.  No iteration, capturable. */
+int sol_karman_pressure_solve_large_direct(const sol_karman_cfg* cfg, void* stream, const float* rhs, float* p,
+                                           const int32_t* direct_header_host, void* workspace, size_t workspace_bytes);
 
 /* Adjoint of the large-grid step with respect to its input velocity, for both solvers (csrc/karman_large_bwd.hip).  The solver is
  * chosen by the cfg: cfg.direct set = the direct solve (direct_header_host required; box_blob / box_header_host / cg_info are not read
@@ -212,6 +223,8 @@ int sol_karman_pressure_solve_large(const sol_karman_cfg* cfg, void* stream, con
  *     synchronises, an eager call stops issuing iterations (checked every 16) once every simulation has converged.
  *     `workspace`: DEVICE scratch of sol_karman_step_bwd_large_workspace_bytes(cfg) bytes (covers either solver as the cfg selects it). */
 size_t sol_karman_step_bwd_large_workspace_bytes(const sol_karman_cfg* cfg);
+/* the same, sized from the host header of cfg.direct (required for a scattered blob, see sol_karman_step_large_workspace_bytes_for) */
+size_t sol_karman_step_bwd_large_workspace_bytes_for(const sol_karman_cfg* cfg, const int32_t* direct_header_host);
 int sol_karman_step_fwd_large_saved(const sol_karman_cfg* cfg, void* stream,
                                     const float* d_in, const float* vy_in, const float* vx_in,
                                     const float* re, const float* active, const float* inflow,

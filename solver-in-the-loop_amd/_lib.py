@@ -65,6 +65,9 @@ _SIGS = {
     "sol_prof_end": (C.c_int, [C.c_int32, C.c_char_p, C.POINTER(C.c_double), C.POINTER(C.c_int32)]),
     "sol_karman_direct_supported": (C.c_int, [C.c_int32] * 2),
     "sol_karman_step_large_workspace_bytes": (C.c_size_t, [_P]),
+    "sol_karman_step_large_workspace_bytes_for": (C.c_size_t, [_P, _P]),
+    "sol_karman_step_bwd_large_workspace_bytes_for": (C.c_size_t, [_P, _P]),
+    "sol_karman_pressure_solve_large_direct": (C.c_int, [_P] * 6 + [C.c_size_t]),
     "sol_karman_step_fwd_large": (C.c_int, [_P] * 10 + [C.c_int64] + [_P] * 7 + [C.c_size_t]),
     "sol_karman_step_large_cg_workspace_bytes": (C.c_size_t, [_P]),
     "sol_karman_step_fwd_large_cg": (C.c_int, [_P] * 10 + [C.c_int64] + [_P] * 9 + [C.c_size_t]),

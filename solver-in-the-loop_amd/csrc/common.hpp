@@ -50,15 +50,17 @@ int sol_large_project(const sol_karman_cfg* c, hipStream_t s, const SolLargeStep
 int sol_large_box_forward(hipStream_t s, int B, int Y, int X, const float* blob, const float* src, float* T1, float* T2, const int* skip);
 int sol_large_box_back(hipStream_t s, int B, int Y, int X, const float* blob, const float* T2, float* T1, float* dst, const int* skip);
 // the step's pressure solve M x = b for either solver (pcg.hip; shared by the forward entry points and the adjoint, karman_large_bwd.hip):
-// direct = the capacitance solve on cfg.direct (hdr: host copy of its header, sol_large_direct_check), else the preconditioned CG with the
+// direct = the capacitance solve on cfg.direct (hdr: host copy of its header, sol_large_direct_check; its magic word selects the one-window
+// form of precond.direct_solver_blob or the scattered form of precond.scattered_solver_blob), else the preconditioned CG with the
 // empty-box solve of box_blob, reporting to cg_info [2][B] (sol_large_cg_check).  ws: sol_large_solver_bytes(c, direct) bytes; the caller
 // writes b to sol_large_solver_rhs(c, direct, ws) (overwritten); *x = the buffer inside ws that holds the solution.  x0 (CG only): NULL, or
 // the initial guess [B][Y][X] of a warm-started solve (a simulation whose guess is not finite starts from zero).
 size_t sol_large_direct_floats(const sol_karman_cfg* c);
+size_t sol_large_direct_floats(const sol_karman_cfg* c, const int32_t* hdr);      // sized from the blob's host header (scattered solve: U, V, X0, W2 follow |R|, |C|)
 int sol_large_direct_check(const sol_karman_cfg* c, const char* who, const int32_t* hdr);
 int sol_large_direct_solve(hipStream_t s, const sol_karman_cfg* c, const int32_t* hdr, float* base);
 int sol_large_cg_check(const sol_karman_cfg* c, const char* who, const float* box_blob, const int32_t* hdr, const int32_t* cg_info, const void* workspace);
-size_t sol_large_solver_bytes(const sol_karman_cfg* c, bool direct);
+size_t sol_large_solver_bytes(const sol_karman_cfg* c, bool direct, const int32_t* hdr = nullptr);
 float* sol_large_solver_rhs(const sol_karman_cfg* c, bool direct, void* ws);
 int pressure_solve_any2d(hipStream_t s, const sol_karman_cfg* c, bool direct, const int32_t* hdr, const float* box_blob, const float* active,
                          int32_t* cg_info, void* ws, float** x, const float* x0 = nullptr);

@@ -9,7 +9,9 @@
 //   k_l_div       rhs = -div
 //   pressure      DIRECT solve: x = G (b - U_S E_SS x_S) with the sine-transform diagonalisation of the rectangle and
 //                 the capacitance correction of the obstacle (precond.direct_solver_blob, window 16/32/64): eight small
-//                 fp32 GEMMs (k_l_gemm) + gather / K' / scatter kernels
+//                 fp32 GEMMs (k_l_gemm) + gather / K' / scatter kernels; or, for obstacles beyond one window, the SCATTERED form of the
+//                 same correction on the support set's row and column lists (precond.scattered_solver_blob, magic "FDS1": scattered_solve,
+//                 k_l_capacitance_sc) -- sol_large_direct_check / _solve dispatch on the blob's magic word
 //   k_l_project   v -= mask * grad p  (+ fused to_feature)
 // and, for a roll-out with the trained corrector (trainer.LargeGridRollout), the correction launch after the network:
 //   k_l_correct   v_y, v_x += out_std * to_staggered(network output)  (+ the applied correction as a field of its own)
@@ -274,6 +276,61 @@ __global__ void k_l_capacitance(const float* __restrict__ x0w, const float* __re
     }
 }
 
+// ---- scattered direct solve (precond.scattered_solver_blob): the capacitance product for support sets of a thousand cells and more ----
+// c = K' xs with xs gathered from X0 [RP][CP], W2[sidx] = -c.  grid = (SP / 64, B): a workgroup owns 64 rows of K' (= 64 columns of the
+// stored K'^T) and walks all SP entries of xs (staged in LDS).  Lane = (q phase 0..3, four consecutive columns): a wave reads four rows
+// of K'^T per step as 16-byte loads (16 lanes x 16 B = 256 contiguous bytes per row), wave w takes the fixed q range [w, w + 1) * SP / 4.
+// The sixteen partials per column (4 waves x 4 phases) are added in a fixed order through LDS: no atomics, the same bits on every call.
+// A matrix-vector product has one right-hand side per simulation: nothing for the matrix cores to tile, the kernel is a streaming read
+// of K' (5.9 MB at SP = 1216) spread over SP / 64 x B compute units.
+constexpr int SC_TILE = 64;          // columns of K'^T per workgroup
+constexpr int SC_MAXSP = 4096;       // precond.FDS_MAX_SUPPORT
+__global__ void __launch_bounds__(256) k_l_capacitance_sc(const float* __restrict__ X0, const float* __restrict__ KpT, const int* __restrict__ sidx,
+                                                          float* __restrict__ W2, int SP, int nW) {
+    __shared__ float xs[SC_MAXSP];
+    __shared__ float part[16][SC_TILE];
+    const int b = blockIdx.y, s0 = blockIdx.x * SC_TILE;
+    const float* x0 = X0 + (size_t)b * nW;
+    for (int t = threadIdx.x; t < SP; t += 256) {
+        const int si = sidx[t];
+        xs[t] = (si >= 0 && si < nW) ? x0[si] : 0.f;
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, col = (lane & 15) * 4, ph = lane >> 4;
+    const int q0 = wave * (SP >> 2), q1 = q0 + (SP >> 2);            // SP % 64 == 0: a multiple of 16 rows per wave
+    const float* k = KpT + (size_t)s0 + col;
+    float4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 4
+    for (int q = q0 + ph; q < q1; q += 4) {
+        const float4 kv = *reinterpret_cast<const float4*>(k + (size_t)q * SP);
+        const float x = xs[q];
+        acc.x += kv.x * x; acc.y += kv.y * x; acc.z += kv.z * x; acc.w += kv.w * x;
+    }
+    *reinterpret_cast<float4*>(&part[wave * 4 + ph][col]) = acc;
+    __syncthreads();
+    if (threadIdx.x < SC_TILE) {
+        const int si = sidx[s0 + threadIdx.x];
+        if (si >= 0 && si < nW) {
+            float c = 0.f;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) c += part[r][threadIdx.x];
+            W2[(size_t)b * nW + si] = -c;
+        }
+    }
+}
+
+__global__ void __launch_bounds__(256) k_l_copy(float* __restrict__ dst, const float* __restrict__ src, size_t n) {
+    for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (size_t)gridDim.x * 256) dst[e] = src[e];
+}
+__global__ void __launch_bounds__(256) k_l_zero(float* __restrict__ p, size_t n) {
+    for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (size_t)gridDim.x * 256) p[e] = 0.f;
+}
+
+constexpr int FDL_MAGIC = 0x46443032;      // "FD02": precond.direct_solver_blob (one window)
+constexpr int FDS_MAGIC = 0x46445331;      // "FDS1": precond.scattered_solver_blob (row list x column list)
+struct HeaderSc { int Y, X, nR, nC, nS, SP, RP, CP; };
+inline HeaderSc header_sc(const int32_t* hdr) { return HeaderSc{hdr[1], hdr[2], hdr[3], hdr[4], hdr[5], hdr[6], hdr[7], hdr[8]}; }
+
 struct Header { int Y, X, wy0, wx0, nS, SP, win; };
 
 int gemm(hipStream_t s, int batch, const float* A, int lda, long sA, const float* Bm, int ldb, long sB, float* C, int ldc, long sC,
@@ -353,9 +410,79 @@ size_t sol_large_direct_floats(const sol_karman_cfg* c) {
     const size_t B = c->B, Y = c->Y, X = c->X;
     return B * (3 * Y * X + 2 * Y * 64 + 2 * 64 * 64);
 }
+// the same for the blob whose host header is hdr: the scattered solve keeps U, V as Y x CP and X0, W2 as RP x CP (NULL or FD02: the window form)
+size_t sol_large_direct_floats(const sol_karman_cfg* c, const int32_t* hdr) {
+    if (!hdr || hdr[0] != FDS_MAGIC) return sol_large_direct_floats(c);
+    const HeaderSc h = header_sc(hdr);
+    const size_t B = c->B, Y = c->Y, X = c->X, RP = h.RP > 0 ? h.RP : 0, CP = h.CP > 0 ? h.CP : 0;
+    return B * (3 * Y * X + 2 * Y * CP + 2 * RP * CP);
+}
+
+namespace {
+
+inline size_t pad4(size_t n) { return (n + 3) / 4 * 4; }
+// words of a scattered blob with this header (precond.scattered_solver_blob's layout)
+size_t scattered_words(const HeaderSc& h) {
+    const size_t Y = h.Y, X = h.X, SP = h.SP, RP = h.RP, CP = h.CP;
+    return FDL_HEADER + pad4(Y * Y + X * X + X * Y) + SP * SP + RP + CP + SP + 2 * RP * Y + 2 * X * CP;
+}
+
+int scattered_check(const sol_karman_cfg* c, const char* who, const int32_t* hdr) {
+    const HeaderSc h = header_sc(hdr);
+    SOL_REQUIRE(h.Y == c->Y && h.X == c->X, "%s: the scattered direct-solver blob is for a %dx%d grid, cfg is %dx%d", who, h.Y, h.X, c->Y, c->X);
+    SOL_REQUIRE(h.nS >= 1 && h.SP >= h.nS && h.SP <= SC_MAXSP && h.SP % SC_TILE == 0 && h.nR >= 1 && h.nR <= h.Y && h.nC >= 1 && h.nC <= h.X &&
+                    h.RP >= h.nR && h.RP % 4 == 0 && h.RP < h.nR + 4 && h.CP >= h.nC && h.CP % 4 == 0 && h.CP < h.nC + 4 &&
+                    (long)h.nR * h.nC >= h.nS,
+                "%s: scattered direct-solver blob header is inconsistent", who);
+    SOL_REQUIRE((size_t)c->direct_n >= scattered_words(h), "%s: cfg.direct_n = %d words, the scattered direct-solver blob of this header has %zu",
+                who, c->direct_n, scattered_words(h));
+    SOL_REQUIRE(c->B <= 65535, "%s: B <= 65535 with the scattered direct solve (got %d)", who, c->B);
+    return SOL_OK;
+}
+
+// M p = T0 as sol_large_direct_solve, the window replaced by the row list R and the column list C of the support set:
+//   box forward;  U = T2 Qx[:,C];  X0 = Qy[R,:] U;  W2 = 0, W2[S] = -K' X0[S];  V = Qy[:,R] W2;  T1 = V Qx[C,:];  T2 += T1 / lam;  box back
+// layout from `base`: T0 (rhs in, pressure out), T1, T2, U, V (Y x CP each), X0, W2 (RP x CP each)
+int scattered_solve(hipStream_t s, const sol_karman_cfg* c, const int32_t* hdr, float* base) {
+    const HeaderSc h = header_sc(hdr);
+    const int B = c->B, Y = c->Y, X = c->X, N = Y * X, SP = h.SP, RP = h.RP, CP = h.CP;
+    const float* Qy = c->direct + FDL_HEADER;
+    const float* Qx = Qy + (size_t)Y * Y;
+    const float* ilT = Qx + (size_t)X * X;             // [X][Y]
+    const float* KpT = c->direct + FDL_HEADER + pad4((size_t)Y * Y + (size_t)X * X + (size_t)X * Y);      // 16-byte aligned rows
+    const int* sidx = reinterpret_cast<const int*>(KpT + (size_t)SP * SP) + RP + CP;                      // behind the row and column lists
+    const float* QyR = reinterpret_cast<const float*>(sidx + SP);     // [RP][Y]
+    const float* QxC = QyR + (size_t)RP * Y;                          // [X][CP]
+    const float* QyRt = QxC + (size_t)X * CP;                         // [Y][RP]
+    const float* QxCr = QyRt + (size_t)Y * RP;                        // [CP][X]
+    float* w = base;
+    float* T0 = w; w += (size_t)B * N;
+    float* T1 = w; w += (size_t)B * N;
+    float* T2 = w; w += (size_t)B * N;
+    float* U = w; w += (size_t)B * Y * CP;
+    float* V = w; w += (size_t)B * Y * CP;
+    float* X0 = w; w += (size_t)B * RP * CP;
+    float* W2 = w; w += (size_t)B * RP * CP;
+    const long sN = N, sU = (long)Y * CP, sW = (long)RP * CP;
+    if (int e = sol_large_box_forward(s, B, Y, X, c->direct, T0, T1, T2, nullptr)) return e;
+    if (int e = gemm(s, B, T2, X, sN, QxC, CP, 0, U, CP, sU, Y, CP, X, 0)) return e;
+    if (int e = gemm(s, B, QyR, Y, 0, U, CP, sU, X0, CP, sW, RP, CP, Y, 0)) return e;
+    // the workspace is the caller's: every call clears W2 before the support entries are written
+    const size_t nw = (size_t)B * sW, nb = (nw + 255) / 256;
+    SOL_LAUNCH(k_l_zero, dim3((unsigned)(nb < 1024 ? nb : 1024)), dim3(256), 0, s, W2, nw);
+    SOL_LAUNCH(k_l_capacitance_sc, dim3(SP / SC_TILE, B), dim3(256), 0, s, (const float*)X0, KpT, sidx, W2, SP, (int)sW);
+    SOL_LAUNCH_CHECK();
+    if (int e = gemm(s, B, QyRt, RP, 0, W2, CP, sW, V, CP, sU, Y, CP, RP, 0)) return e;
+    if (int e = gemm(s, B, V, CP, sU, QxCr, X, 0, T1, X, sN, Y, X, CP, 0)) return e;
+    SOL_LAUNCH(k_l_scale, dim3((N + 255) / 256, B), dim3(256), 0, s, T2, (const float*)T1, ilT, Y, X, (const int*)nullptr);
+    return sol_large_box_back(s, B, Y, X, c->direct, T2, T1, T0, nullptr);
+}
+
+}  // namespace
 
 int sol_large_direct_check(const sol_karman_cfg* c, const char* who, const int32_t* hdr) {
     SOL_REQUIRE(c->direct && c->direct_n > 0, "%s needs the direct-solver blob (cfg.direct)", who);
+    if (hdr && hdr[0] == FDS_MAGIC) return scattered_check(c, who, hdr);
     SOL_REQUIRE(hdr && hdr[0] == 0x46443032, "%s: direct_header_host must be the first 16 words of the blob (host copy)", who);
     const Header h{hdr[1], hdr[2], hdr[3], hdr[4], hdr[5], hdr[6], hdr[7]};
     SOL_REQUIRE(h.SP >= h.nS && h.SP <= 4096 && h.wy0 >= 0 && h.wx0 >= 0 && h.wy0 + h.win <= c->Y && h.wx0 + h.win <= c->X,
@@ -367,6 +494,7 @@ int sol_large_direct_check(const sol_karman_cfg* c, const char* who, const int32
 
 // M p = T0 by the empty-box solve of the rhs with the capacitance correction on its spectral coefficients; p overwrites T0 (= base)
 int sol_large_direct_solve(hipStream_t s, const sol_karman_cfg* c, const int32_t* hdr, float* base) {
+    if (hdr[0] == FDS_MAGIC) return scattered_solve(s, c, hdr, base);
     const Header h{hdr[1], hdr[2], hdr[3], hdr[4], hdr[5], hdr[6], hdr[7]};
     const int B = c->B, Y = c->Y, X = c->X, N = Y * X, win = h.win, SP = h.SP;
     // blob sections
@@ -408,6 +536,13 @@ extern "C" size_t sol_karman_step_large_workspace_bytes(const sol_karman_cfg* c)
     return floats * sizeof(float);
 }
 
+extern "C" size_t sol_karman_step_large_workspace_bytes_for(const sol_karman_cfg* c, const int32_t* direct_header_host) {
+    if (!c) return 0;
+    const size_t B = c->B, Y = c->Y, X = c->X;
+    const size_t floats = B * ((Y + 1) * X + Y * (X + 1)) + sol_large_direct_floats(c, direct_header_host) + 256;
+    return floats * sizeof(float);
+}
+
 extern "C" int sol_karman_step_fwd_large(const sol_karman_cfg* c, void* stream,
                                          const float* d_in, const float* vy_in, const float* vx_in,
                                          const float* re, const float* active, const float* inflow,
@@ -422,9 +557,9 @@ extern "C" int sol_karman_step_fwd_large(const sol_karman_cfg* c, void* stream,
     SOL_REQUIRE((d_in && inflow) || !d_out, "density output requested without d_in/inflow");
     SOL_REQUIRE(!feat_out || feat_scale, "feat_out requires feat_scale");
     SOL_REQUIRE(c->direct && c->direct_n > 0, "sol_karman_step_fwd_large needs the direct-solver blob (cfg.direct)");
-    SOL_REQUIRE(workspace_bytes >= sol_karman_step_large_workspace_bytes(c), "workspace too small");
     SOL_REQUIRE(vy_in != vy_out && vx_in != vx_out && d_in != d_out, "sol_karman_step_fwd_large: outputs must not alias the inputs");
     if (int e = sol_large_direct_check(c, "sol_karman_step_fwd_large", direct_header_host)) return e;
+    SOL_REQUIRE(workspace_bytes >= sol_karman_step_large_workspace_bytes_for(c, direct_header_host), "workspace too small");
     const size_t B = c->B, Y = c->Y, X = c->X;
     // workspace carve: sv_y, sv_x, the solver's buffers
     float* w = static_cast<float*>(workspace);
@@ -442,6 +577,27 @@ extern "C" int sol_karman_correct(void* stream, const float* out, float* vy, flo
     const size_t n = (size_t)B * Y * X, nb = (n + 255) / 256;
     SOL_LAUNCH(k_l_correct, dim3((unsigned)(nb < 4096 ? nb : 4096)), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const float2*>(out), vy, vx,
                cor_y, cor_x, n, Y, X, s0, s1);
+    SOL_LAUNCH_CHECK();
+    return SOL_OK;
+}
+
+extern "C" int sol_karman_pressure_solve_large_direct(const sol_karman_cfg* c, void* stream, const float* rhs, float* p,
+                                                      const int32_t* direct_header_host, void* workspace, size_t workspace_bytes) {
+    const char* who = "sol_karman_pressure_solve_large_direct";
+    SOL_REQUIRE(c != nullptr, "cfg is NULL");
+    SOL_REQUIRE(c->B >= 1 && c->Y >= 16 && c->X >= 16, "%s: B >= 1, Y, X >= 16 (got %d, %d, %d)", who, c->B, c->Y, c->X);
+    SOL_REQUIRE(rhs && p && workspace, "%s: NULL pointer argument", who);
+    SOL_REQUIRE(p != rhs, "%s: outputs must not alias the inputs", who);
+    if (int e = sol_large_direct_check(c, who, direct_header_host)) return e;
+    const size_t need = sol_large_direct_floats(c, direct_header_host) * sizeof(float);
+    SOL_REQUIRE(workspace_bytes >= need, "%s: workspace too small (%zu < %zu bytes)", who, workspace_bytes, need);
+    hipStream_t s = (hipStream_t)stream;
+    float* base = static_cast<float*>(workspace);
+    const size_t n = (size_t)c->B * c->Y * c->X, nb = (n + 255) / 256;
+    const unsigned g = (unsigned)(nb < 4096 ? nb : 4096);
+    SOL_LAUNCH(k_l_copy, dim3(g), dim3(256), 0, s, base, rhs, n);
+    if (int e = sol_large_direct_solve(s, c, direct_header_host, base)) return e;
+    SOL_LAUNCH(k_l_copy, dim3(g), dim3(256), 0, s, p, (const float*)base, n);
     SOL_LAUNCH_CHECK();
     return SOL_OK;
 }

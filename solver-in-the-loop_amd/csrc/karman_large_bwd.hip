@@ -242,7 +242,7 @@ struct BwdLayout {
     void* solver;
     size_t bytes;
 };
-BwdLayout bwd_layout(const sol_karman_cfg* c, bool direct, void* ws) {
+BwdLayout bwd_layout(const sol_karman_cfg* c, bool direct, void* ws, const int32_t* hdr = nullptr) {
     const size_t B = c->B, Y = c->Y, X = c->X, faces = (Y + 1) * X + Y * (X + 1);
     char* w = ws ? reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(ws) + 255) / 256 * 256) : nullptr;
     size_t off = 0;
@@ -251,7 +251,7 @@ BwdLayout bwd_layout(const sol_karman_cfg* c, bool direct, void* ws) {
     l.gc = reinterpret_cast<long long*>(take(B * faces * sizeof(long long)));
     l.ga = reinterpret_cast<float*>(take(B * faces * sizeof(float)));
     l.gmax = reinterpret_cast<unsigned*>(take(B * FX_SLOTS * sizeof(unsigned)));
-    l.solver = take(sol_large_solver_bytes(c, direct));
+    l.solver = take(sol_large_solver_bytes(c, direct, hdr));
     l.bytes = off + 256;                       // + the alignment of the caller's pointer
     return l;
 }
@@ -270,6 +270,11 @@ extern "C" size_t sol_karman_step_bwd_large_workspace_bytes(const sol_karman_cfg
     return bwd_layout(c, c->direct != nullptr, nullptr).bytes;
 }
 
+extern "C" size_t sol_karman_step_bwd_large_workspace_bytes_for(const sol_karman_cfg* c, const int32_t* direct_header_host) {
+    if (!c || c->B < 1 || c->Y < 1 || c->X < 1) return 0;
+    return bwd_layout(c, c->direct != nullptr, nullptr, direct_header_host).bytes;
+}
+
 extern "C" int sol_karman_step_fwd_large_saved(const sol_karman_cfg* c, void* stream,
                                                const float* d_in, const float* vy_in, const float* vx_in,
                                                const float* re, const float* active, const float* inflow,
@@ -286,7 +291,7 @@ extern "C" int sol_karman_step_fwd_large_saved(const sol_karman_cfg* c, void* st
     SOL_REQUIRE((d_in && inflow) || !d_out, "%s: density output requested without d_in / inflow", who);
     if (direct) { if (int e = sol_large_direct_check(c, who, direct_header_host)) return e; }
     else if (int e = sol_large_cg_check(c, who, box_blob, box_header_host, cg_info, workspace)) return e;
-    const size_t need = sol_large_solver_bytes(c, direct) + 256;
+    const size_t need = sol_large_solver_bytes(c, direct, direct ? direct_header_host : nullptr) + 256;
     SOL_REQUIRE(workspace_bytes >= need, "%s: workspace too small (%zu < %zu bytes)", who, workspace_bytes, need);
     const void* outs[] = {d_out, vy_out, vx_out, saved_vy, saved_vx, cg_info};
     const void* ins[] = {d_in, vy_in, vx_in, re, active, inflow, velBCy, velBCyMask, box_blob};
@@ -312,7 +317,7 @@ extern "C" int sol_karman_step_bwd_large(const sol_karman_cfg* c, void* stream,
                 "%s: NULL pointer argument", who);
     if (direct) { if (int e = sol_large_direct_check(c, who, direct_header_host)) return e; }
     else if (int e = sol_large_cg_check(c, who, box_blob, box_header_host, cg_info, workspace)) return e;
-    const size_t need = bwd_layout(c, direct, nullptr).bytes;
+    const size_t need = bwd_layout(c, direct, nullptr, direct ? direct_header_host : nullptr).bytes;
     SOL_REQUIRE(workspace_bytes >= need, "%s: workspace too small (%zu < %zu bytes)", who, workspace_bytes, need);
     const void* outs[] = {g_vy_in, g_vx_in, cg_info};
     const void* ins[] = {saved_vy, saved_vx, re, active, velBCyMask, g_vy_out, g_vx_out, box_blob};
@@ -322,7 +327,7 @@ extern "C" int sol_karman_step_bwd_large(const sol_karman_cfg* c, void* stream,
     const int B = c->B, Y = c->Y, X = c->X, N = Y * X;
     const size_t nVy = (size_t)(Y + 1) * X, nVx = (size_t)Y * (X + 1), faces = nVy + nVx;
     hipStream_t s = (hipStream_t)stream;
-    const BwdLayout l = bwd_layout(c, direct, workspace);
+    const BwdLayout l = bwd_layout(c, direct, workspace, direct ? direct_header_host : nullptr);
     LBArgs a{};
     a.B = B; a.Y = Y; a.X = X; a.dtdx = c->dt / c->dx; a.adt = c->dt * c->res * c->res; a.grad_pad = c->grad_pad;
     a.re = re; a.active = active; a.bcm = velBCyMask; a.bc_stride = bc_batch_stride;

@@ -405,8 +405,8 @@ __global__ void __launch_bounds__(PCG_T) large_copy(float* __restrict__ dst, con
 // ---- karman-2d large grids: the pressure solve the caller selects, M x = b, on a solver workspace of sol_large_solver_bytes ----
 // direct: the capacitance solve on cfg.direct (hdr = its host header); else PCG with the empty-box solve of box_blob as preconditioner,
 // reporting to cg_info [2][B].  The caller writes b into sol_large_solver_rhs(...) (overwritten); *x = the buffer that holds the solution.
-size_t sol_large_solver_bytes(const sol_karman_cfg* c, bool direct) {
-    return direct ? sol_large_direct_floats(c) * sizeof(float) + 256 : large_layout(c, nullptr, false).bytes;
+size_t sol_large_solver_bytes(const sol_karman_cfg* c, bool direct, const int32_t* hdr) {
+    return direct ? sol_large_direct_floats(c, hdr) * sizeof(float) + 256 : large_layout(c, nullptr, false).bytes;
 }
 
 float* sol_large_solver_rhs(const sol_karman_cfg* c, bool direct, void* ws) {

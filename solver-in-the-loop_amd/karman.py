@@ -115,9 +115,10 @@ class KarmanFlow:
                  obstacles=None, active=None):
         # the reference's plug point: None = this build's default ("auto": the direct solver where the grid and the
         # scene allow it, else the two-level preconditioned CG), or one of "direct" / "cg"
-        if pressure_solver not in (None, "auto", "direct", "cg"):
-            raise NotImplementedError("pressure_solver must be None, 'auto', 'direct' or 'cg': the pressure solve is fused "
-                                      "into the LDS-resident solver step of libsol_hip.so")
+        # "direct_scattered" (opt-in, large grids only): the direct solve for obstacles beyond one window (precond.scattered_solver_blob)
+        if pressure_solver not in (None,) + ops.PRESSURE_SOLVERS:
+            raise NotImplementedError("pressure_solver must be None, 'auto', 'direct', 'cg' or 'direct_scattered': the pressure solve is "
+                                      "fused into the solver step of libsol_hip.so")
         self._pressure_solver = pressure_solver or "auto"
         if make_input_divfree or not make_output_divfree:
             raise NotImplementedError("only (make_input_divfree=False, make_output_divfree=True) is on the reference path")
@@ -214,7 +215,7 @@ class KarmanFlow:
         vy = smoke.velocity.data[0].data.reshape(B, Y + 1, X)
         vx = smoke.velocity.data[1].data.reshape(B, Y, X + 1)
         info = {}
-        self.pressure_solver_used = masks.pressure_solver        # "direct" or "cg" (SceneMasks' choice for this grid and scene)
+        self.pressure_solver_used = masks.pressure_solver        # "direct", "cg" (SceneMasks' choice for this grid and scene) or "direct_scattered"
         if masks.large:
             # beyond the one-workgroup kernels (data generation at 256 x 128, karman.py:98-159): the multi-launch path, direct solve
             # where the scene's blob builds, else the preconditioned CG (solve_info: iterations / converged per simulation, and

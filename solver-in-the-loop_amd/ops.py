@@ -41,6 +41,14 @@ def beyond_one_workgroup(Y, X):
     return Y * X > 8192 or X > 64
 
 
+PRESSURE_SOLVERS = ("auto", "direct", "cg", "direct_scattered")
+
+
+def is_direct(pressure_solver):
+    """True for the solvers without iteration (SceneMasks.pressure_solver "direct" or "direct_scattered"): capturable, no cg_info."""
+    return pressure_solver in ("direct", "direct_scattered")
+
+
 class SceneMasks:
     """Device-resident constant masks of a scene: active (1 - obstacle), inflow rate, velBCy,
     velBCyMask (reference: KarmanFlow.__init__ karman_train.py:166-171 and :366-373)."""
@@ -65,9 +73,21 @@ class SceneMasks:
         self.direct = None
         self.direct_header = None
         want = os.environ.get("SOL_PRESSURE_SOLVER", pressure_solver)
-        if want not in ("auto", "direct", "cg"):
-            raise ValueError("pressure_solver must be 'auto', 'direct' or 'cg' (got %r)" % (want,))
-        if want != "cg" and (self.large or _lib.load().sol_karman_direct_supported(Y, X)):
+        if want not in PRESSURE_SOLVERS:
+            raise ValueError("pressure_solver must be 'auto', 'direct', 'cg' or 'direct_scattered' (got %r)" % (want,))
+        if want == "direct_scattered":
+            # opt-in: the capacitance solve on the support set's row and column lists (no window), large grids only
+            if not self.large:
+                raise ValueError("pressure_solver='direct_scattered' serves the large-grid path only (grids beyond the one-workgroup "
+                                 "kernels, ops.beyond_one_workgroup); %dx%d is not large: use 'auto', 'direct' or 'cg'" % (Y, X))
+            from .precond import scattered_solver_blob
+            blob = scattered_solver_blob(self.active.reshape(Y, X).cpu().numpy())
+            if blob is None:
+                raise ValueError("the scattered direct pressure solver does not support this scene (%dx%d): no obstacle, more than "
+                                 "4096 support cells, or an ill-conditioned capacitance system" % (Y, X))
+            self.direct = torch.from_numpy(blob).to(device)
+            self.direct_header = np.ascontiguousarray(blob[:16].view(np.int32))
+        elif want != "cg" and (self.large or _lib.load().sol_karman_direct_supported(Y, X)):
             from .precond import direct_solver_blob
             blob = direct_solver_blob(self.active.reshape(Y, X).cpu().numpy(), max_window=64 if self.large else 16)
             if blob is not None:
@@ -84,15 +104,20 @@ class SceneMasks:
             blob = box_solver_blob(Y, X)
             self.box = torch.from_numpy(blob).to(device)
             self.box_header = np.ascontiguousarray(blob[:16].view(np.int32))
-        self.pressure_solver = "direct" if self.direct is not None else "cg"
+        self.pressure_solver = want if want == "direct_scattered" else ("direct" if self.direct is not None else "cg")
 
 
 def large_workspace_bytes(cfg, masks):
-    """Device scratch of the large-grid step for the scene's solver (direct or CG)."""
+    """Device scratch of the large-grid step for the scene's solver (direct, scattered direct or CG)."""
     lib = _lib.load()
     if masks.direct is None:
         return lib.sol_karman_step_large_cg_workspace_bytes(C.byref(cfg))
-    return lib.sol_karman_step_large_workspace_bytes(C.byref(cfg))
+    return lib.sol_karman_step_large_workspace_bytes_for(C.byref(cfg), _hdr(masks.direct_header))
+
+
+def large_bwd_workspace_bytes(cfg, masks):
+    """Device scratch of the large-grid adjoint (sol_karman_step_bwd_large) for the scene's solver."""
+    return _lib.load().sol_karman_step_bwd_large_workspace_bytes_for(C.byref(cfg), _hdr(masks.direct_header))
 
 
 def _hdr(a):
@@ -165,7 +190,7 @@ def karman_step_large_bwd(svy, svx, re, gvy, gvx, cfg, masks, workspace=None, in
     """Adjoint of the large-grid step (sol_karman_step_bwd_large): (g_vy_in, g_vx_in) from the saved post-diffusion velocity and the
     gradient with respect to the step's output velocity.  With the CG solve, `info` receives "iterations_bwd" / "converged_bwd"."""
     lib = _lib.load()
-    workspace = _workspace(lib.sol_karman_step_bwd_large_workspace_bytes(C.byref(cfg)), workspace, svy.device)
+    workspace = _workspace(large_bwd_workspace_bytes(cfg, masks), workspace, svy.device)
     oy, ox = torch.empty_like(svy), torch.empty_like(svx)
     cg_info = _cg_info(masks, cfg.B, svy.device)
     check(lib.sol_karman_step_bwd_large(
@@ -242,15 +267,23 @@ def karman_correct(out, vy, vx, s, cor=None):
 
 
 def pressure_solve_large(rhs, cfg, masks, workspace=None, info=None):
-    """The large-grid CG step's pressure solve alone (sol_karman_pressure_solve_large): p [B,Y,X] with M p = rhs, M = -A of the
-    scene's mask (precond.scene_matrix).  `info` receives "iterations" / "converged" (device int32 [B])."""
+    """The large-grid step's pressure solve alone: p [B,Y,X] with M p = rhs, M = -A of the scene's mask (precond.scene_matrix).  CG scenes:
+    sol_karman_pressure_solve_large, `info` receives "iterations" / "converged" (device int32 [B]).  Scenes with
+    pressure_solver="direct_scattered": sol_karman_pressure_solve_large_direct (no iteration, `info` stays empty)."""
     _lib.require_gpu()
     lib = _lib.load()
-    if masks.box is None:
-        raise ValueError("pressure_solve_large needs a scene prepared for the large-grid CG solve (SceneMasks.pressure_solver == 'cg')")
     rhs = _lib.f32(rhs)
     B, Y, X = cfg.B, cfg.Y, cfg.X
     assert rhs.shape == (B, Y, X)
+    if masks.pressure_solver == "direct_scattered":
+        workspace = _workspace(large_workspace_bytes(cfg, masks), workspace, rhs.device)
+        p = torch.empty_like(rhs)
+        check(lib.sol_karman_pressure_solve_large_direct(C.byref(cfg), stream(), ptr(rhs), ptr(p), _hdr(masks.direct_header),
+                                                         ptr(workspace), workspace.numel() * 4))
+        return p
+    if masks.box is None:
+        raise ValueError("pressure_solve_large needs a scene prepared for the large-grid CG solve (SceneMasks.pressure_solver == 'cg') "
+                         "or for the scattered direct solve ('direct_scattered')")
     workspace = _workspace(lib.sol_karman_step_large_cg_workspace_bytes(C.byref(cfg)), workspace, rhs.device)
     p = torch.empty_like(rhs)
     cg_info = _cg_info(masks, B, rhs.device)

@@ -226,3 +226,116 @@ def direct_solve_reference(blob, b):
     w2 = w2.reshape(FD_WIN, FD_WIN)
     T2 = T2 + il * (Qy[:, wy0:wy0 + FD_WIN] @ w2 @ Qx[wx0:wx0 + FD_WIN, :])
     return Qy @ T2 @ Qx
+
+
+# ---------------------------------------------------------------------------------------------
+# Scattered direct solver: the same capacitance correction without the window
+# ---------------------------------------------------------------------------------------------
+# The correction needs G b only ON S and adds a term that lives only ON S.  With R the distinct rows of S and C its distinct
+# columns, (G b)_S is a gather from X0 = Qy[R,:] T2 Qx[:,C] (|R| x |C|) and the correction enters the spectral coefficients as
+# Qy[:,R] W2 Qx[C,:]: direct_solver_blob's algorithm with a row list and a column list where that one has two contiguous ranges
+# (csrc/karman_large.hip: scattered_solve).  Any scene whose support set has at most 4096 cells qualifies, however spread out.
+FDS_MAGIC = 0x46445331         # "FDS1"
+FDS_MAX_SUPPORT = 4096
+
+
+def _pad4(n):
+    return (int(n) + 3) // 4 * 4
+
+
+def scattered_solver_blob(active, dtype=np.float32):
+    """float32 blob of the scattered direct solver (SceneMasks(pressure_solver="direct_scattered"), large grids only), or None when
+    the scene has no perturbation, more than 4096 support cells, or an ill-conditioned capacitance system (cond > 1e6).
+
+    layout (32-bit words): header[16] = {magic "FDS1", Y, X, nR, nC, nS, SP, RP, CP, ...} (RP, CP = |R|, |C| padded to multiples of
+    4, SP = nS padded to a multiple of 64);  Qy[Y*Y];  Qx[X*X];  invlamT[X*Y];  zero words up to a multiple of 4 (16-byte rows of
+    K'^T);  KpT[SP*SP] (K' = E_SS (I + G_SS E_SS)^-1 transposed, zero padded);  rows[RP], cols[CP] int32 (-1 = padding);
+    sidx[SP] int32 (row-slot * CP + column-slot of a support cell in X0 / W2, -1 = padding);  the slabs the GEMMs read, zero in the
+    padding:  QyR[RP*Y] = Qy[R,:];  QxC[X*CP] = Qx[:,C];  QyRt[Y*RP] = Qy[:,R];  QxCr[CP*X] = Qx[C,:].
+    dtype=np.float64 (host checks only, never a device blob): the same words unrounded, integers stored as float64 values."""
+    act = (np.asarray(active, dtype=np.float64) != 0).astype(np.float64)
+    Y, X = act.shape
+    ent = _perturbation(act)
+    if not ent:
+        return None
+    S = np.array(sorted({r for r, _ in ent}), dtype=np.int64)
+    nS = len(S)
+    if nS > FDS_MAX_SUPPORT:
+        return None
+    js, is_ = S // X, S % X
+    R, rslot = np.unique(js, return_inverse=True)
+    Cc, cslot = np.unique(is_, return_inverse=True)
+    nR, nC = len(R), len(Cc)
+    RP, CP = _pad4(nR), _pad4(nC)
+    SP = (nS + 63) // 64 * 64
+    pos = {int(s): n for n, s in enumerate(S)}
+    ESS = np.zeros((nS, nS))
+    for (r, c), v in ent.items():
+        ESS[pos[r], pos[c]] = v
+    Qy, Qx = dst_matrix(Y), dst_matrix(X)
+    lam = (2 - 2 * np.cos(np.pi * np.arange(1, Y + 1) / (Y + 1)))[:, None] + (2 - 2 * np.cos(np.pi * np.arange(1, X + 1) / (X + 1)))[None, :]
+    Fy, Fx = Qy[js, :], Qx[is_, :]                                # [nS, Y], [nS, X]
+    F = (Fy[:, :, None] * Fx[:, None, :]).reshape(nS, Y * X)
+    GSS = (F / lam.reshape(1, Y * X)) @ F.T                       # one GEMM, as direct_solver_blob forms it
+    del F
+    cap = np.eye(nS) + GSS @ ESS
+    if np.linalg.cond(cap) > 1e6:
+        return None
+    Kp = ESS @ np.linalg.inv(cap)
+    KpT = np.zeros((SP, SP))
+    KpT[:nS, :nS] = Kp.T
+    rows = np.full(RP, -1, dtype=np.int32); rows[:nR] = R
+    cols = np.full(CP, -1, dtype=np.int32); cols[:nC] = Cc
+    sidx = np.full(SP, -1, dtype=np.int32)
+    sidx[:nS] = (rslot * CP + cslot).astype(np.int32)
+    QyR = np.zeros((RP, Y)); QyR[:nR] = Qy[R, :]
+    QxC = np.zeros((X, CP)); QxC[:, :nC] = Qx[:, Cc]
+    header = np.zeros(FD_HEADER, dtype=np.int32)
+    header[:9] = [FDS_MAGIC, Y, X, nR, nC, nS, SP, RP, CP]
+    lead = Y * Y + X * X + X * Y
+    assert dtype in (np.float32, np.float64)
+    flt = lambda a: np.ascontiguousarray(a).astype(dtype).ravel()
+    words = (lambda a: a.view(np.float32)) if dtype == np.float32 else (lambda a: a.astype(np.float64))
+    parts = [words(header), flt(Qy), flt(Qx), flt((1.0 / lam).T), np.zeros(_pad4(lead) - lead, dtype=dtype), flt(KpT),
+             words(rows), words(cols), words(sidx), flt(QyR), flt(QxC), flt(QyR.T), flt(QxC.T)]
+    return np.concatenate(parts)
+
+
+def scattered_sections(blob):
+    """The sections of a scattered_solver_blob as a dict of views (header fields by name, matrices in their shapes)."""
+    ints = (lambda a: a.view(np.int32)) if blob.dtype == np.float32 else (lambda a: a.astype(np.int32))
+    hdr = ints(blob[:FD_HEADER])
+    assert hdr[0] == FDS_MAGIC
+    Y, X, nR, nC, nS, SP, RP, CP = (int(v) for v in hdr[1:9])
+    s = dict(Y=Y, X=X, nR=nR, nC=nC, nS=nS, SP=SP, RP=RP, CP=CP)
+    o = FD_HEADER
+
+    def take(name, n, shape, integer=False):
+        nonlocal o
+        a = blob[o:o + n]
+        s[name] = (ints(a) if integer else a).reshape(shape)
+        o += n
+
+    take("Qy", Y * Y, (Y, Y)); take("Qx", X * X, (X, X)); take("ilT", X * Y, (X, Y))
+    o = FD_HEADER + _pad4(o - FD_HEADER)
+    take("KpT", SP * SP, (SP, SP))
+    take("rows", RP, (RP,), True); take("cols", CP, (CP,), True); take("sidx", SP, (SP,), True)
+    take("QyR", RP * Y, (RP, Y)); take("QxC", X * CP, (X, CP)); take("QyRt", Y * RP, (Y, RP)); take("QxCr", CP * X, (CP, X))
+    s["words"] = o
+    return s
+
+
+def scattered_solve_reference(blob, b):
+    """float64 numpy restatement of the device algorithm on a scattered_solver_blob (b [Y, X]); used by the CPU tests.  On the device's
+    float32 blob the result carries the rounding of its matrices; on a dtype=np.float64 blob it is the algorithm alone."""
+    s = scattered_sections(blob)
+    f = lambda k: s[k].astype(np.float64)
+    Qy, Qx, il, sidx = f("Qy"), f("Qx"), f("ilT").T, s["sidx"]
+    T2 = (Qy @ b @ Qx) * il
+    x0 = f("QyR") @ (T2 @ f("QxC"))                              # [RP, CP]
+    xs = np.where(sidx >= 0, x0.ravel()[np.maximum(sidx, 0)], 0.0)
+    c = f("KpT").T @ xs
+    w2 = np.zeros(s["RP"] * s["CP"])
+    w2[sidx[sidx >= 0]] = -c[sidx >= 0]
+    T2 = T2 + il * ((f("QyRt") @ w2.reshape(s["RP"], s["CP"])) @ f("QxCr"))
+    return Qy @ T2 @ Qx

@@ -24,7 +24,8 @@ def add_scene_args(p, warm_start=False):
     p.add_argument("--obstacle", action="append", default=None, metavar="SPEC",
                    help="obstacle in domain coordinates, repeatable: sphere:CY,CX,R | box:Y0:Y1,X0:X1 | none (default: sphere:50,50,10)")
     p.add_argument("--obstacle-mask", default=None, metavar="FILE.npy", help="[Y, X] fluid mask (1 = fluid) for exactly this grid")
-    p.add_argument("--pressure-solver", default="auto", choices=("auto", "direct", "cg"), help="pressure solve of the solver step")
+    p.add_argument("--pressure-solver", default="auto", choices=("auto", "direct", "cg", "direct_scattered"),
+                   help="pressure solve of the solver step (direct_scattered: the direct solve for obstacles beyond one window, large grids only)")
     if warm_start:
         p.add_argument("--cg-warm-start", action="store_true",
                        help="start every CG pressure solve from the previous frame's pressure (large grids; ignored with the direct solve)")

@@ -67,11 +67,11 @@ def main(argv=None):
     large = ops.beyond_one_workgroup(Y, X)
     warm = bool(params["cg_warm_start"]) and large and masks.pressure_solver == "cg"
     if params["cg_warm_start"] and not warm:
-        log.info("--cg-warm-start ignored: %s" % ("the direct pressure solve has no iteration to start" if large and masks.pressure_solver == "direct"
+        log.info("--cg-warm-start ignored: %s" % ("the direct pressure solve has no iteration to start" if large and ops.is_direct(masks.pressure_solver)
                                                   else "it belongs to the CG solve of the large grids"))
     # (a CG scene runs eagerly, every solve stops at convergence; a direct-solve scene replays one captured step)
     ro = sol_amd.make_rollout(model, masks, 1, Y, X, dom.dx[1], data_stats["std"][1], data_stats["ext.std"][0],
-                              use_graph=masks.pressure_solver == "direct", cg_warm_start=warm)
+                              use_graph=ops.is_direct(masks.pressure_solver), cg_warm_start=warm)
     f = lambda a: torch.as_tensor(np.ascontiguousarray(a), dtype=torch.float32, device="cuda").contiguous()
     vy0, vx0 = scene.split_staggered(np.asarray(vn, dtype=np.float32))
     d, vy, vx = f(np.asarray(d0)[..., 0]), f(vy0), f(vx0)

@@ -275,7 +275,7 @@ class LargeGridRollout:
     one kernel copy of the new state over the old one: the state ping-pongs between two internal buffers A -> B and the copy B -> A
     closes the step, so every step reads and writes the same addresses.
 
-    use_graph=True (direct-solve scenes): that step is captured once (_lib.capture_graph: kernel nodes only) and replayed nsteps times.
+    use_graph=True (direct-solve scenes, "direct" or "direct_scattered"): that step is captured once (_lib.capture_graph: kernel nodes only) and replayed nsteps times.
     On a CG scene run() is eager, so that every solve stops at convergence: a captured step would issue the launches of the WHOLE
     cg_max_iter budget per solve (converged iterations fall through; LargeGridTrainer's docstring), hundreds of launches a roll-out
     step has no use for -- use_graph=True raises there.  cg_warm_start=True (CG scenes; ignored with the direct solve): a solve starts
@@ -589,7 +589,7 @@ class LargeGridTrainer(GraphTrainer):
     64 (the reference's 256 x 128 data-generation grid).  The schedule IS GraphTrainer._unrolled_schedule (forward
     unroll, correction, ops.l2_loss_fwd_bwd, reverse sweep with NetSchedule2D.backward -- weight gradients of W = 64 * tiles rows: the
     wide form of sol_conv5x5_bwd_weight --, epilogue); this class only supplies the large-grid solver pair: _solver_fwd =
-    ops.karman_step_large_saved (direct or CG pressure solve, as SceneMasks decides for the scene and `pressure_solver`) + the scaled
+    ops.karman_step_large_saved (direct, scattered direct or CG pressure solve, as SceneMasks decides for the scene and `pressure_solver`) + the scaled
     features assembled in torch, _solver_bwd = feature gradient / in_std added to the cotangent on the faces to_feature reads +
     ops.karman_step_large_bwd, _schedule_setup = their workspaces.  Networks: mars_moon and mercury.
 
@@ -620,7 +620,7 @@ class LargeGridTrainer(GraphTrainer):
         cfg, mk, dev = self._kcfg, self._mk, self.device
         ws = lambda n: torch.empty((int(n) + 3) // 4, dtype=torch.float32, device=dev)
         self._ws_fwd = ws(ops.large_workspace_bytes(cfg, mk))
-        self._ws_bwd = ws(self.lib.sol_karman_step_bwd_large_workspace_bytes(C.byref(cfg)))
+        self._ws_bwd = ws(ops.large_bwd_workspace_bytes(cfg, mk))
         self._zplane = torch.zeros(self.B, self.Y, self.X, dtype=torch.float32, device=dev)      # the fourth (padding) input channel
         self.pressure_solver_used = mk.pressure_solver
 
