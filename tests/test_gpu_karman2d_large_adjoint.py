@@ -22,25 +22,11 @@ import sol_oracle as o
 from sol_amd import _lib, fluid, karman, ops
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from large2d_scenes import CG_RTOL, DEV, PLATE, TOL_FIELD, TOL_GRAD, TWO, active_of, f32, geometry, masks, rel, state
+from large2d_scenes import (CG_RTOL, DEV, PLATE, TOL_FIELD, TOL_GRAD, TRIM, TWO, active_of, check_grads, f32, geometry, masks, rel, state,
+                            trimmed_rel)
 
 pytestmark = pytest.mark.gpu
-TRIM = 1e-3                                          # a cap, not a tuning knob (module docstring)
 Y, X = 256, 128
-
-
-def trimmed_rel(a, b, frac=TRIM):
-    """relative L2 of a against b after leaving out the floor(frac * n) entries with the largest |a - b| (the norm of b is taken over
-    the entries kept) -> (value, entries left out, largest deviation left out)"""
-    a = torch.as_tensor(np.asarray(a.detach().cpu() if isinstance(a, torch.Tensor) else a), dtype=torch.float64).reshape(-1)
-    b = torch.as_tensor(np.asarray(b.detach().cpu() if isinstance(b, torch.Tensor) else b), dtype=torch.float64).reshape(-1)
-    dev = (a - b).abs()
-    k = int(frac * dev.numel())
-    if k == 0:
-        return float(dev.norm() / (b.norm() + 1e-300)), 0, 0.0
-    order = torch.argsort(dev)
-    keep, drop = order[:-k], order[-k:]
-    return float(dev[keep].norm() / (b[keep].norm() + 1e-300)), k, float(dev[drop].max())
 
 
 def scene_of(specs):
@@ -75,20 +61,6 @@ def hip_grad(st, g, mk, w, info=None, **kw):
     ((out[1] * f32(w[0])).sum() + (out[2] * f32(w[1])).sum()).backward()
     torch.cuda.synchronize()
     return tuple(t.detach() for t in out), (hy.grad, hx.grad)
-
-
-def check_grads(got, ref, trimmed, what):
-    for name, a, b in zip(("g_vy", "g_vx"), got, ref):
-        full = rel(a, b)
-        if trimmed:
-            v, k, worst = trimmed_rel(a, b)
-            print("%s %s: rel L2 %.3e untrimmed, %.3e after leaving out %d of %d entries (largest deviation left out %.3e)"
-                  % (what, name, full, v, k, b.numel(), worst))
-            assert k <= int(TRIM * b.numel())
-            assert v < TOL_GRAD, (what, name, v, full)
-        else:
-            print("%s %s: rel L2 %.3e" % (what, name, full))
-            assert full < TOL_GRAD, (what, name, full)
 
 
 def fluid_of(st, B):
