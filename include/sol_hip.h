@@ -372,6 +372,24 @@ int sol_conv5x5_scaled(void* stream, const float* x, const float* packed, const 
                        int32_t B, int32_t H, int32_t W, int32_t cin, int32_t cout,
                        int32_t epilogue, float slope, const uint32_t* x_absmax, uint32_t* y_absmax);
 
+/* sol_conv5x5_scaled on PITCHED rows: the tensors x, residual, act_ref and y are [B,H,W,c] buffers whose rows hold WV <= W pixels of
+ * data followed by W - WV pad pixels, W (the pitch) a multiple of 64 and 1 <= WV <= W -- the layout in which an image of any width
+ * WV runs on the 64-pixel-tile kernels (pitch 64 * ceil(WV / 64)).
+ *   - Columns >= WV of x, residual and act_ref are ZERO.  This is the caller's duty and is not checked: with zero pad columns the
+ *     SAME-padding halo of the valid columns is what a dense [B,H,WV,c] image has, so the valid columns of y are the dense result.
+ *   - Columns >= WV of y are WRITTEN as 0.0f (every pad pixel is stored; the caller never clears an output buffer), so y can be
+ *     the next layer's x as it is.
+ *   - y_absmax covers the valid columns only.
+ * x_absmax / y_absmax may be NULL; the kernel choice then follows sol_conv5x5.  WV == W launches exactly what sol_conv5x5_scaled
+ * launches; WV < W launches the column-masked instantiation of that same kernel.  Rejected before any launch: W % 64 != 0, WV < 1,
+ * WV > W, NULL x / packed / y.
+ * The weight gradient needs no such form: with x and dz zero in the pad columns, sol_conv5x5_bwd_weight at the pitch W returns the
+ * dense image's dw and db (the pad pixels contribute exact zeros). */
+int sol_conv5x5_cols(void* stream, const float* x, const float* packed, const float* bias,
+                     const float* residual, const float* act_ref, float* y,
+                     int32_t B, int32_t H, int32_t W, int32_t WV, int32_t cin, int32_t cout,
+                     int32_t epilogue, float slope, const uint32_t* x_absmax, uint32_t* y_absmax);
+
 /* dW[5,5,cin,cout] += sum_px x[px+tap] * dz[px];  db[cout] += sum_px dz[px].
  * `partial` is a caller workspace of sol_conv5x5_bwd_weight_ws_floats() floats that the
  * caller zeroes once and may reuse to ACCUMULATE over many calls (the unrolled steps share

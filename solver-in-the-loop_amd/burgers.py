@@ -157,9 +157,14 @@ def randfreq(shape, rng, power=8):
     return f / (f.std() + 1e-30)
 
 
-def _check_net_shape(who, Y, X):
+def _check_net_shape(who, Y, X, any_width=False):
     """The shapes the correction network's launches take for H = Y, W = X (sol_conv5x5, sol_conv5x5_bwd_weight): refused here, at
-    construction, instead of by the first convolution of the first step."""
+    construction, instead of by the first convolution of the first step.  any_width=True: every width runs, in pitched rows
+    (schedule2d.NetSchedule2D(any_width=True)); only the solver's own limits remain."""
+    if any_width:
+        if Y < 2 or X < 2 or max(Y, X) > 1024:
+            raise _lib.SolError("%s: resolution %dx%d is not supported: 2 <= Y, X <= 1024" % (who, Y, X))
+        return
     if not ((X <= 64 and 64 % X == 0 and Y % (64 // X) == 0) or (X > 64 and X % 64 == 0)) or Y < 2 or X < 2 or max(Y, X) > 1024:
         raise _lib.SolError("%s: resolution %dx%d is not supported: the network's convolutions take rows of X <= 64 cells with 64 %% X == 0 "
                             "and Y %% (64 / X) == 0, or rows wider than 64 cells that are a multiple of 64 cells wide; 2 <= Y, X <= 1024"
@@ -179,18 +184,24 @@ class BurgersTrainer:
     velo: [msteps+1, B, Y+1, X+1, 2] staggered frames (frame 0 = start state, frames 1.. = targets), forc: [msteps, B, Y+1, X+1, 2]
     (ignored with noforce) -- what BurgersDataset.getData(consecutive_frames=msteps) returns, stacked."""
 
-    def __init__(self, net, domain, batch_size, msteps, dt, std_v, std_f=None, noforce=False, use_graph=True, viscosity=0.1, schedule="manual"):
-        """schedule: "manual" (default since round 6) = the unrolled step as a HAND-WRITTEN schedule over the C ABI (_schedule_step: forward
+    def __init__(self, net, domain, batch_size, msteps, dt, std_v, std_f=None, noforce=False, use_graph=True, viscosity=0.1, schedule="manual",
+                 any_width=False):
+        """any_width=True: domains whose width the convolutions refuse (e.g. 24x100, 48x48) train too -- the network's launches run in
+        pitched rows (schedule2d.NetSchedule2D(any_width=True)); the manual schedule only.
+        schedule: "manual" (default since round 6) = the unrolled step as a HAND-WRITTEN schedule over the C ABI (_schedule_step: forward
         unroll keeping the step inputs and the network's activations, reverse sweep with the weight gradients accumulated over the steps;
         no autograd graph), "autograd" = the torch-autograd composition of the differentiable HIP ops (rounds 2-5; the cross-check)."""
         from . import fluid
         if schedule not in ("manual", "autograd"):
             raise ValueError("schedule must be 'manual' or 'autograd'")
-        self.schedule, self._sched = schedule, None
+        if any_width and schedule == "autograd":
+            raise ValueError("BurgersTrainer: any_width=True runs the hand-written schedule only; schedule='autograd' (the composition "
+                             "over ops.conv5x5) takes no pitched rows")
+        self.schedule, self._sched, self.any_width = schedule, None, bool(any_width)
         self.net, self.dom, self.B, self.ms, self.dt, self.noforce = net, domain, int(batch_size), int(msteps), float(dt), bool(noforce)
         dev = net.params.device
         Y, X = (int(n) for n in domain.resolution)
-        _check_net_shape("BurgersTrainer", Y, X)
+        _check_net_shape("BurgersTrainer", Y, X, self.any_width)
         self.large = max(Y, X) > ops.BURGERS_LDS_MAX          # beyond the one-workgroup kernels: sol_burgers_step_fwd_large / _bwd_large
         self.sim = BurgersTest(default_viscosity=viscosity, large_grid_grad=True)
         if self.large:
@@ -245,7 +256,7 @@ class BurgersTrainer:
         Y, X = self.dom.resolution
         B, ms, dev = self.B, self.ms, self.velo.device
         if self._sched is None:
-            self._sched = NetSchedule2D(self.net, B, Y, X)
+            self._sched = NetSchedule2D(self.net, B, Y, X, any_width=self.any_width)
             self._circ = ops.burgers_circ(Y, X, self.dt * self.sim.viscosity, dev)
             self._bcfg = BurgersCfg(B, Y, X, float(self.dom.dx[1]), float(self.dt))
         sch, circ, cfg = self._sched, self._circ, self._bcfg
@@ -364,7 +375,9 @@ class BurgersRollout:
     replays.  `vel` / `corr` are the static staggered tensors [B,Y+1,X+1,2] holding the state after the step and its
     correction (what the script writes as velTf / corTf)."""
 
-    def __init__(self, net, domain, batch_size, dt, std_v, std_f=None, noforce=False, use_graph=True, viscosity=0.1):
+    def __init__(self, net, domain, batch_size, dt, std_v, std_f=None, noforce=False, use_graph=True, viscosity=0.1, any_width=False):
+        """any_width=True: the network's twelve launches go through schedule2d.NetSchedule2D(train=False, any_width=True) -- a width the
+        convolutions refuse runs in pitched rows; the solver step and the correction stay dense."""
         from . import fluid
         _lib.require_gpu()
         self.net, self.dom, self.B, self.dt, self.noforce = net, domain, int(batch_size), float(dt), bool(noforce)
@@ -377,6 +390,17 @@ class BurgersRollout:
         z = lambda: torch.zeros(self.B, Y + 1, X + 1, 2, dtype=torch.float32, device=dev)
         self.vel, self.corr, self.f_step, self.f_feat = z(), z(), z(), z()
         self.use_graph, self._graph, self._fluid = bool(use_graph), None, fluid
+        self._sched = None
+        if any_width:
+            from .schedule2d import NetSchedule2D
+            _check_net_shape("BurgersRollout", Y, X, True)
+            self._sched = NetSchedule2D(net, self.B, Y, X, train=False, any_width=True)
+
+    def _predict(self, x):
+        if self._sched is None:
+            return self.net.predict(x)
+        self._sched.begin_step()                      # the CURRENT weights, one pack launch per step (net.predict packs per convolution)
+        return self._sched.forward(x)[0]
 
     def _one(self):
         from .karman import to_staggered
@@ -389,7 +413,7 @@ class BurgersRollout:
             else:
                 st = self.sim.step_with_f(st, F.BurgersVelocitySMAC(self.dom, velocity=self.f_step, batch_size=self.B), dt=self.dt)
                 feat = to_feature([st], [F.BurgersVelocitySMAC(self.dom, velocity=self.f_feat, batch_size=self.B)])
-            cv = to_staggered(self.net.predict(feat / self.std_in) * self.std_v, self.dom.box)
+            cv = to_staggered(self._predict(feat / self.std_in) * self.std_v, self.dom.box)
             _lib.dcopy_(self.corr, cv.staggered_tensor())      # (kernel copies: no memcpy nodes in the captured graph)
             _lib.dcopy_(self.vel, (st.velocity + cv).staggered_tensor())
 

@@ -83,6 +83,9 @@ struct ConvArgs {
     int epi;
     float slope;
     int TW, RPW, tiles_x;
+    int WV;            // pitched rows (sol_conv5x5_cols): valid pixels per row, W = the pitch; 0: dense rows.  Read by the MASK instantiations only, which the
+                       // host picks when 0 < WV < W: they store 0.0f at the pixels of columns >= WV and keep them out of the published absmax.
+                       // (Sits in what was alignment padding in front of the pointers below: no other field moved.)
     const void* wsb;   // split-bf16 weight planes (second section of the packed buffer), cin == 32 only
     const void* wsh;   // split-fp16 weight planes + header (third section), cin == 32 only
     const unsigned* xmax;   // [SOL_AMAX_SLOTS] slots, max over them = bits of max|x| (non-negative float) -> fp16 path; NULL: bf16 path
@@ -104,6 +107,8 @@ struct ConvArgs {
     int CI;                         // input channels per pixel of x as the caller declared them (0: not stated).  Kernels that read a fixed number of
                                     // channels per pixel whatever the caller meant (k_conv5x5_thin32: eight float4 = 32) check it before they are chosen
 };
+// the host's choice between a kernel and its column-masked instantiation (ConvArgs::WV)
+inline bool sol_conv_masked(const ConvArgs& a) { return a.WV > 0 && a.WV < a.W; }
 // correction mode: offsets of the faces of CNN pixel (image row jj, pixel px) inside a simulation's v_y / v_x, and of the face without
 // a correction that this pixel also owns for the loss (v_y row Y, v_x column X of the SOLVER grid), or -1
 struct CorrFaces { int oy, ox, ey, ex; };

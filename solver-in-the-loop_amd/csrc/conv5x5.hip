@@ -51,7 +51,10 @@ __global__ void k_pack(const float* __restrict__ w, float* __restrict__ packed, 
 // forward / backward-data kernel
 // ------------------------------------------------------------------------------------
 // ConvArgs: common.hpp
-template <int CIN, int NT>
+// MASK (here and in every kernel below that takes it): pitched rows, a.WV < a.W valid pixels per row (ConvArgs::WV, sol_conv5x5_cols) --
+// the pixels of columns >= a.WV are stored as 0.0f and stay out of the published absmax.  A separate instantiation: the unmasked
+// kernels keep their code.
+template <int CIN, int NT, bool MASK = false>
 __global__ void __launch_bounds__(256) k_conv5x5(ConvArgs a) {
     constexpr int CP = CIN == 4 ? 4 : 36;   // LDS pixel stride in floats
     constexpr int OP = NT * 16;
@@ -178,7 +181,11 @@ __global__ void __launch_bounds__(256) k_conv5x5(ConvArgs a) {
         for (int n = 0; n < NT; ++n) {
             const float bias = a.bias ? a.bias[n * 16 + li] : 0.f;
 #pragma unroll
-            for (int r = 0; r < 4; ++r) tb[(4 * g + r) * OP + n * 16 + li] = acc[n][r] + bias;
+            for (int r = 0; r < 4; ++r) {
+                float v = acc[n][r] + bias;
+                if (MASK && x0 + wave * 16 + 4 * g + r >= a.WV) v = 0.f;      // pad pixel: zero before the transposition (residual / act_ref are zero there)
+                tb[(4 * g + r) * OP + n * 16 + li] = v;
+            }
         }
         constexpr int F4 = 16 * OP / 4 / 64;          // float4 per lane
 #pragma unroll
@@ -214,6 +221,7 @@ __global__ void __launch_bounds__(256) k_conv5x5(ConvArgs a) {
                 if (a.res) v += a.res[o];
                 if (a.epi == SOL_EPI_LRELU) v = v > 0.f ? v : a.slope * v;
                 else if (a.epi == SOL_EPI_DLRELU) v *= (a.act[o] > 0.f ? 1.f : a.slope);
+                if (MASK && x0 + cc >= a.WV) v = 0.f;
                 vmax = fmaxf(vmax, fabsf(v));
                 a.y[o] = v;
             }
@@ -235,7 +243,7 @@ __global__ void __launch_bounds__(256) k_conv5x5(ConvArgs a) {
 // CU): seven halo rows, one weight block, wave = (row, 16-pixel segment).  Rows of the stack that belong to another image than the output row
 // (the stack is cut anywhere, also between two images) contribute zeros: the test is wave uniform, one v_cndmask per MFMA operand.
 // Arithmetic and summation order per output pixel are k_conv5x5<4, NT>'s (same MFMA sequence over the taps): bit-identical results.
-template <int NT>
+template <int NT, bool MASK = false>
 __global__ void __launch_bounds__(768) k_conv5x5_t3(ConvArgs a) {
     constexpr int CP = 4, OP = NT * 16, W = 64, HW = W + 4, NR = 3, NH = NR + 4, NTHR = 768;
     extern __shared__ __align__(16) float smem[];
@@ -340,7 +348,11 @@ __global__ void __launch_bounds__(768) k_conv5x5_t3(ConvArgs a) {
     for (int n = 0; n < NT; ++n) {
         const float bias = a.bias ? a.bias[n * 16 + li] : 0.f;
 #pragma unroll
-        for (int r = 0; r < 4; ++r) tb[(4 * g + r) * OP + n * 16 + li] = acc[n][r] + bias;
+        for (int r = 0; r < 4; ++r) {
+            float v = acc[n][r] + bias;
+            if (MASK && seg * 16 + 4 * g + r >= a.WV) v = 0.f;      // pad pixel: zero before the transposition (residual / act_ref are zero there)
+            tb[(4 * g + r) * OP + n * 16 + li] = v;
+        }
     }
 #pragma unroll
     for (int n = 0; n < F4; ++n) {
@@ -393,7 +405,7 @@ static size_t conv_t3_lds(int OP) {
 // ------------------------------------------------------------------------------------
 __device__ __forceinline__ int swz(int pix) { return ((pix >> 1) & 3) << 1; }
 
-template <int NT>
+template <int NT, bool MASK = false>
 __global__ void __launch_bounds__(256) k_conv5x5_c32(ConvArgs a) {
     constexpr int OP = NT * 16;
     extern __shared__ __align__(16) float smem[];
@@ -512,6 +524,7 @@ __global__ void __launch_bounds__(256) k_conv5x5_c32(ConvArgs a) {
             if (a.res) v += a.res[o];
             if (a.epi == SOL_EPI_LRELU) v = v > 0.f ? v : a.slope * v;
             else if (a.epi == SOL_EPI_DLRELU) v *= (a.act[o] > 0.f ? 1.f : a.slope);
+            if (MASK && x0 + cc >= a.WV) v = 0.f;
             vmax = fmaxf(vmax, fabsf(v));
             a.y[o] = v;
         }
@@ -529,7 +542,7 @@ __global__ void __launch_bounds__(256) k_conv5x5_c32(ConvArgs a) {
 // the weights of a whole tap row (5 taps, 20 KB) are double buffered: ONE barrier per 5 taps
 // (5 per launch instead of 25) and 80 back-to-back MFMAs per wave between barriers.
 // ------------------------------------------------------------------------------------
-template <int NT>
+template <int NT, bool MASK = false>
 __global__ void __launch_bounds__(768) k_conv5x5_r3(ConvArgs a, int ntiles) {
     constexpr int OP = NT * 16;
     constexpr int HWP = 68;                       // halo pixels per row (64 + 4)
@@ -668,7 +681,11 @@ __global__ void __launch_bounds__(768) k_conv5x5_r3(ConvArgs a, int ntiles) {
         for (int n = 0; n < NT; ++n) {
             const float bias = a.bias ? a.bias[n * 16 + li] : 0.f;
 #pragma unroll
-            for (int r = 0; r < 4; ++r) tb[(4 * g + r) * OP + n * 16 + li] = acc[n][r] + bias;
+            for (int r = 0; r < 4; ++r) {
+                float v = acc[n][r] + bias;
+                if (MASK && x0 + wave * 16 + 4 * g + r >= a.WV) v = 0.f;      // pad pixel: zero before the transposition (residual / act_ref are zero there)
+                tb[(4 * g + r) * OP + n * 16 + li] = v;
+            }
         }
         // same-wave LDS round trip: the compiler's s_waitcnt lgkmcnt orders write -> read
         if (tvalid) {
@@ -707,6 +724,7 @@ __global__ void __launch_bounds__(768) k_conv5x5_r3(ConvArgs a, int ntiles) {
             if (a.res) v += a.res[o];
             if (a.epi == SOL_EPI_LRELU) v = v > 0.f ? v : a.slope * v;
             else if (a.epi == SOL_EPI_DLRELU) v *= (a.act[o] > 0.f ? 1.f : a.slope);
+            if (MASK && x0 + cc >= a.WV) v = 0.f;
             a.y[o] = v;
         }
     }
@@ -1273,20 +1291,24 @@ extern "C" int sol_conv5x5_pack_jobs(void* stream, int32_t n, const float* const
 
 int sol_init_conv_kernels() {
     static std::atomic<unsigned long long> optin{0};
-    return sol_lds_optin(optin, {SOL_K(k_conv5x5_r3<1>), SOL_K(k_conv5x5_r3<2>), SOL_K(k_conv5x5_c32<1>), SOL_K(k_conv5x5_c32<2>)}, "conv kernels");
+    return sol_lds_optin(optin, {SOL_K(k_conv5x5_r3<1>), SOL_K(k_conv5x5_r3<2>), SOL_K(k_conv5x5_c32<1>), SOL_K(k_conv5x5_c32<2>),
+                                 SOL_K((k_conv5x5_r3<1, true>)), SOL_K((k_conv5x5_r3<2, true>)), SOL_K((k_conv5x5_c32<1, true>)), SOL_K((k_conv5x5_c32<2, true>))}, "conv kernels");
 }
 
 static int conv_impl(void* stream, const float* x, const float* packed, const float* bias,
                      const float* residual, const float* act_ref, float* y,
                      int32_t B, int32_t H, int32_t W, int32_t cin, int32_t cout,
-                     int32_t epilogue, float slope, const uint32_t* x_absmax, uint32_t* y_absmax) {
+                     int32_t epilogue, float slope, const uint32_t* x_absmax, uint32_t* y_absmax, int32_t WV = 0) {
+    // WV: valid pixels per row of pitch W (sol_conv5x5_cols), 0 = dense rows.  0 < WV < W selects the MASK instantiation of the kernel
+    // the dense launch would take -- nothing else changes
     if (int e = check_shape(B, H, W, cin, cout)) return e;
     SOL_REQUIRE(x && packed && y, "sol_conv5x5: NULL pointer");
     SOL_REQUIRE(epilogue != SOL_EPI_DLRELU || act_ref, "sol_conv5x5: SOL_EPI_DLRELU needs act_ref");
     if (int e = sol_init_conv_kernels()) return e;
     ConvArgs a{};
     a.x = x; a.wp = packed; a.bias = bias; a.res = residual; a.act = act_ref; a.y = y;
-    a.B = B; a.H = H; a.W = W; a.CO = cout; a.CI = cin; a.epi = epilogue; a.slope = slope;
+    a.B = B; a.H = H; a.W = W; a.CO = cout; a.CI = cin; a.epi = epilogue; a.slope = slope; a.WV = WV;
+    const bool mask = sol_conv_masked(a);
     a.TW = W < 64 ? W : 64;
     a.RPW = 64 / a.TW;
     a.tiles_x = W / a.TW;
@@ -1312,7 +1334,10 @@ static int conv_impl(void* stream, const float* x, const float* packed, const fl
         const int ntiles = B * H * (W / 64);
         const size_t ldsr = ((size_t)3 * 2 * 68 * 32 + 2 * (size_t)5 * NT * 16 * 32) * sizeof(float);
         const int grid3 = (ntiles + 2) / 3;
-        if (NT == 2) {
+        if (mask) {
+            if (NT == 2) SOL_LAUNCH((k_conv5x5_r3<2, true>), dim3(grid3), dim3(768), ldsr, s, a, ntiles);
+            else SOL_LAUNCH((k_conv5x5_r3<1, true>), dim3(grid3), dim3(768), ldsr, s, a, ntiles);
+        } else if (NT == 2) {
             SOL_LAUNCH((k_conv5x5_r3<2>), dim3(grid3), dim3(768), ldsr, s, a, ntiles);
         } else {
             SOL_LAUNCH((k_conv5x5_r3<1>), dim3(grid3), dim3(768), ldsr, s, a, ntiles);
@@ -1320,15 +1345,26 @@ static int conv_impl(void* stream, const float* x, const float* packed, const fl
     }
     else if (cin == 32) {
         const size_t lds32 = ((size_t)(a.RPW + 4) * (a.TW + 4) * 32 + 2 * (size_t)NT * 16 * 32) * sizeof(float);
-        if (NT == 2) {
+        if (mask) {
+            if (NT == 2) SOL_LAUNCH((k_conv5x5_c32<2, true>), dim3(grid), dim3(256), lds32, s, a);
+            else SOL_LAUNCH((k_conv5x5_c32<1, true>), dim3(grid), dim3(256), lds32, s, a);
+        } else if (NT == 2) {
             SOL_LAUNCH((k_conv5x5_c32<2>), dim3(grid), dim3(256), lds32, s, a);
         } else {
             SOL_LAUNCH((k_conv5x5_c32<1>), dim3(grid), dim3(256), lds32, s, a);
         }
     }
     else if (conv_t3_usable(B, H, W, cin, pad_out(cout)) && cout == pad_out(cout)) {
-        if (NT == 2) SOL_LAUNCH((k_conv5x5_t3<2>), dim3((B * H + 2) / 3), dim3(768), conv_t3_lds(32), s, a);
+        if (mask) {
+            if (NT == 2) SOL_LAUNCH((k_conv5x5_t3<2, true>), dim3((B * H + 2) / 3), dim3(768), conv_t3_lds(32), s, a);
+            else SOL_LAUNCH((k_conv5x5_t3<1, true>), dim3((B * H + 2) / 3), dim3(768), conv_t3_lds(16), s, a);
+        }
+        else if (NT == 2) SOL_LAUNCH((k_conv5x5_t3<2>), dim3((B * H + 2) / 3), dim3(768), conv_t3_lds(32), s, a);
         else SOL_LAUNCH((k_conv5x5_t3<1>), dim3((B * H + 2) / 3), dim3(768), conv_t3_lds(16), s, a);
+    }
+    else if (mask) {
+        if (NT == 2) SOL_LAUNCH((k_conv5x5<4, 2, true>), dim3(grid), dim3(256), lds, s, a);
+        else SOL_LAUNCH((k_conv5x5<4, 1, true>), dim3(grid), dim3(256), lds, s, a);
     }
     else if (cin == 4 && NT == 2) SOL_LAUNCH((k_conv5x5<4, 2>), dim3(grid), dim3(256), lds, s, a);
     else SOL_LAUNCH((k_conv5x5<4, 1>), dim3(grid), dim3(256), lds, s, a);
@@ -1399,6 +1435,18 @@ extern "C" int sol_conv5x5_scaled(void* stream, const float* x, const float* pac
                                   int32_t B, int32_t H, int32_t W, int32_t cin, int32_t cout,
                                   int32_t epilogue, float slope, const uint32_t* x_absmax, uint32_t* y_absmax) {
     return conv_impl(stream, x, packed, bias, residual, act_ref, y, B, H, W, cin, cout, epilogue, slope, x_absmax, y_absmax);
+}
+
+// Pitched rows (include/sol_hip.h): sol_conv5x5_scaled on rows of pitch W of which the first WV pixels are data.  The kernel is the one
+// the dense launch takes; with WV < W its MASK instantiation stores zeros at the pad pixels and keeps them out of y_absmax.
+extern "C" int sol_conv5x5_cols(void* stream, const float* x, const float* packed, const float* bias,
+                                const float* residual, const float* act_ref, float* y,
+                                int32_t B, int32_t H, int32_t W, int32_t WV, int32_t cin, int32_t cout,
+                                int32_t epilogue, float slope, const uint32_t* x_absmax, uint32_t* y_absmax) {
+    SOL_REQUIRE(x && packed && y, "sol_conv5x5_cols: NULL pointer (x, packed and y are required)");
+    SOL_REQUIRE(W >= 64 && W % 64 == 0, "sol_conv5x5_cols: the row pitch W must be a multiple of 64 (got %d)", W);
+    SOL_REQUIRE(WV >= 1 && WV <= W, "sol_conv5x5_cols: the valid width WV must lie in [1, W] (got WV=%d, W=%d)", WV, W);
+    return conv_impl(stream, x, packed, bias, residual, act_ref, y, B, H, W, cin, cout, epilogue, slope, x_absmax, y_absmax, WV == W ? 0 : WV);
 }
 
 // column tiles of an image row for the weight gradient: one up to 64 pixels, W / 64 beyond

@@ -68,7 +68,9 @@ __device__ unsigned g_dx_prof_ctl[2] = {0u, 1u};
 // SPLIT (COT = 1 only): a 32 -> 32 layer as TWO workgroups per tile, each with one 16-channel half of the output -- for the small launches
 // (one row per workgroup, 96..128 tiles on 256 CUs): a workgroup then stages half the weights (50 instead of 100 KB; the weights are
 // 70 % of what a one-row workgroup pulls through its CU's 64 B/clock vector-memory path) and the launch uses twice the CUs.
-template <int R, int COT, bool SPLIT = false>
+// MASK: pitched rows (ConvArgs::WV < W, sol_conv5x5_cols) -- a lane holds four channels of ONE pixel, so the pad pixels' values are replaced by
+// 0.0f in the lane's registers before the absmax and the store; a separate instantiation.
+template <int R, int COT, bool SPLIT = false, bool MASK = false>
 __global__ void __launch_bounds__(512) k_conv5x5_dx(const float* __restrict__ arg_x, const void* __restrict__ arg_wsh, const unsigned* __restrict__ arg_xmax,
                                                       int nrows, int arg_H, int arg_W, int arg_tiles_x, int arg_hshift, ConvArgs a) {
     // What the prologue needs before its first request -- the three operand pointers and the tile geometry -- are LEADING scalar
@@ -304,6 +306,7 @@ __global__ void __launch_bounds__(512) k_conv5x5_dx(const float* __restrict__ ar
                 v.x *= actv[j].x > 0.f ? 1.f : a.slope; v.y *= actv[j].y > 0.f ? 1.f : a.slope;
                 v.z *= actv[j].z > 0.f ? 1.f : a.slope; v.w *= actv[j].w > 0.f ? 1.f : a.slope;
             }
+            if (MASK && x0 + pcc >= a.WV) v = make_float4(0.f, 0.f, 0.f, 0.f);
             vmax = fmaxf(vmax, fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))));
             st_wt(reinterpret_cast<float4*>(a.y) + out_f4(j), v);      // write-through (common.hpp): no dirty lines left for the end-of-kernel release
         }
@@ -355,6 +358,7 @@ __global__ void __launch_bounds__(512) k_conv5x5_dx(const float* __restrict__ ar
                     if (a.res) v += a.res[o];
                     if (a.epi == SOL_EPI_LRELU) v = v > 0.f ? v : a.slope * v;
                     else if (a.epi == SOL_EPI_DLRELU) v *= (a.act[o] > 0.f ? 1.f : a.slope);
+                    if (MASK && i >= a.WV) v = 0.f;
                     vmax = fmaxf(vmax, fabsf(v));
                     a.y[o] = v;
                 }
@@ -531,12 +535,26 @@ int sol_conv_dx_launch(hipStream_t s, const ConvArgs& a_in, int ntiles) {
     for (int k = 0; k < 20; ++k) if ((1 << k) == a.H) a.RPW = k;
     static std::atomic<unsigned long long> optin{0};
     if (int e = sol_lds_optin(optin, {SOL_K((k_conv5x5_dx<1, 2>)), SOL_K((k_conv5x5_dx<3, 2>)), SOL_K((k_conv5x5_dx<1, 1>)), SOL_K((k_conv5x5_dx<3, 1>)),
-                                         SOL_K((k_conv5x5_dx<1, 1, true>))}, "k_conv5x5_dx")) return e;
+                                         SOL_K((k_conv5x5_dx<1, 1, true>)),
+                                         SOL_K((k_conv5x5_dx<1, 2, false, true>)), SOL_K((k_conv5x5_dx<3, 2, false, true>)), SOL_K((k_conv5x5_dx<1, 1, false, true>)),
+                                         SOL_K((k_conv5x5_dx<3, 1, false, true>)), SOL_K((k_conv5x5_dx<1, 1, true, true>))}, "k_conv5x5_dx")) return e;
     const bool thin = a.CO <= 16;
     const int nrows = ntiles / a.tiles_x;                 // global image rows B*H
     const int R = dx_rows_per_wg(nrows, a.tiles_x);
     int grid = ((nrows + R - 1) / R) * a.tiles_x;
     if (grid > 64) grid = (grid + 7) / 8 * 8;             // XCD-aware tile order needs a multiple of 8 (xcd_tile); padding tiles own no rows
+    if (sol_conv_masked(a)) {                             // pitched rows: the same choice among the MASK instantiations (never the correction mode)
+        SOL_REQUIRE(!a.cvy, "k_conv5x5_dx: the correction epilogue takes dense rows");
+        if (!thin && R == 1 && (sol_opt().conv_dx & 8))
+            SOL_LAUNCH((k_conv5x5_dx<1, 1, true, true>), dim3(2 * grid), dim3(512), dx_lds(1, 1), s, a.x, a.wsh, a.xmax, nrows, a.H, a.W, a.tiles_x, a.RPW, a);
+        else if (thin) {
+            if (R == 3) SOL_LAUNCH((k_conv5x5_dx<3, 1, false, true>), dim3(grid), dim3(512), dx_lds(3, 1), s, a.x, a.wsh, a.xmax, nrows, a.H, a.W, a.tiles_x, a.RPW, a);
+            else SOL_LAUNCH((k_conv5x5_dx<1, 1, false, true>), dim3(grid), dim3(512), dx_lds(1, 1), s, a.x, a.wsh, a.xmax, nrows, a.H, a.W, a.tiles_x, a.RPW, a);
+        } else if (R == 3) SOL_LAUNCH((k_conv5x5_dx<3, 2, false, true>), dim3(grid), dim3(512), dx_lds(3, 2), s, a.x, a.wsh, a.xmax, nrows, a.H, a.W, a.tiles_x, a.RPW, a);
+        else SOL_LAUNCH((k_conv5x5_dx<1, 2, false, true>), dim3(grid), dim3(512), dx_lds(1, 2), s, a.x, a.wsh, a.xmax, nrows, a.H, a.W, a.tiles_x, a.RPW, a);
+        SOL_LAUNCH_CHECK();
+        return SOL_OK;
+    }
     if (!thin && R == 1 && (sol_opt().conv_dx & 8))
         SOL_LAUNCH((k_conv5x5_dx<1, 1, true>), dim3(2 * grid), dim3(512), dx_lds(1, 1), s, a.x, a.wsh, a.xmax, nrows, a.H, a.W, a.tiles_x, a.RPW, a);
     else if (thin) {

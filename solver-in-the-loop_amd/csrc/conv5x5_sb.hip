@@ -106,7 +106,8 @@ extern "C" int sol_conv_prof_set(long long* buf, unsigned cap) {
 #define SOL_CSTAMP(k) do { } while (0)
 #endif
 
-template <int NT, int KIND>
+// MASK: pitched rows (ConvArgs::WV < W, sol_conv5x5_cols) -- pad pixels are stored as 0.0f and stay out of a.ymax; a separate instantiation
+template <int NT, int KIND, bool MASK = false>
 __global__ void __launch_bounds__(768) k_conv5x5_sb(ConvArgs a, int nrows) {
     constexpr int OP = NT * 16;
     constexpr int HWP = 68;                       // halo pixels per row (64 + 4)
@@ -372,7 +373,11 @@ __global__ void __launch_bounds__(768) k_conv5x5_sb(ConvArgs a, int nrows) {
         for (int n = 0; n < NT; ++n) {
             const float bias = a.bias ? biasv[n] : 0.f;
 #pragma unroll
-            for (int r = 0; r < 4; ++r) tb[(4 * g + r) * OP + n * 16 + li] = acc[n][r] + bias;
+            for (int r = 0; r < 4; ++r) {
+                float v = acc[n][r] + bias;
+                if (MASK && x0 + wave * 16 + 4 * g + r >= a.WV) v = 0.f;      // pad pixel: zero before the transposition (residual / act_ref are zero there)
+                tb[(4 * g + r) * OP + n * 16 + li] = v;
+            }
         }
         // same-wave LDS round trip: the compiler's s_waitcnt lgkmcnt orders write -> read
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's LDS-DMA of res / act has landed
@@ -436,6 +441,7 @@ __global__ void __launch_bounds__(768) k_conv5x5_sb(ConvArgs a, int nrows) {
                 if (a.res) v += a.res[o];
                 if (a.epi == SOL_EPI_LRELU) v = v > 0.f ? v : a.slope * v;
                 else if (a.epi == SOL_EPI_DLRELU) v *= (a.act[o] > 0.f ? 1.f : a.slope);
+                if (MASK && x0 + cc >= a.WV) v = 0.f;
                 vmax = fmaxf(vmax, fabsf(v));
                 a.y[o] = v;
             }
@@ -547,7 +553,9 @@ int init_sb_kernels() {
     // static LDS (the conv kernels' epilogue-prefetch regions) counts against the same 160 KB
     static std::atomic<unsigned long long> optin{0};
     return sol_lds_optin(optin, {SOL_K(k_conv5x5_bww_sb<0>), SOL_K(k_conv5x5_bww_sb<2>), SOL_K(k_conv5x5_bww_sb_jobs<0>), SOL_K(k_conv5x5_bww_sb_jobs<2>), SOL_K(k_conv5x5_bww_sb_wide<0>), SOL_K(k_conv5x5_sb<1, 0>), SOL_K(k_conv5x5_sb<2, 0>),
-                                 SOL_K(k_conv5x5_sb<1, 1>), SOL_K(k_conv5x5_sb<2, 1>), SOL_K(k_conv5x5_sb<1, 2>), SOL_K(k_conv5x5_sb<2, 2>)},
+                                 SOL_K(k_conv5x5_sb<1, 1>), SOL_K(k_conv5x5_sb<2, 1>), SOL_K(k_conv5x5_sb<1, 2>), SOL_K(k_conv5x5_sb<2, 2>),
+                                 SOL_K((k_conv5x5_sb<1, 0, true>)), SOL_K((k_conv5x5_sb<2, 0, true>)), SOL_K((k_conv5x5_sb<1, 1, true>)), SOL_K((k_conv5x5_sb<2, 1, true>)),
+                                 SOL_K((k_conv5x5_sb<1, 2, true>)), SOL_K((k_conv5x5_sb<2, 2, true>))},
                          "split conv kernels", true);
 }
 
@@ -605,6 +613,18 @@ int sol_conv_sb_launch(hipStream_t s, const ConvArgs& a, int NT, int ntiles) {
     int grid3 = ((nrows + 2) / 3) * a.tiles_x;        // three consecutive rows of one column block per workgroup
     if (grid3 > 64) grid3 = (grid3 + 7) / 8 * 8;      // XCD-aware tile order needs a multiple of 8 (xcd_tile); padding tiles own no rows
     const size_t lds = sb_lds(NT * 16);
+    if (sol_conv_masked(a)) {                         // pitched rows: the same choice among the MASK instantiations
+        if (a.xmax) {
+            if (NT == 2) SOL_LAUNCH((k_conv5x5_sb<2, 2, true>), dim3(grid3), dim3(768), lds, s, a, nrows);
+            else SOL_LAUNCH((k_conv5x5_sb<1, 2, true>), dim3(grid3), dim3(768), lds, s, a, nrows);
+        }
+        else if (NT == 2 && nprod == 6) SOL_LAUNCH((k_conv5x5_sb<2, 0, true>), dim3(grid3), dim3(768), lds, s, a, nrows);
+        else if (NT == 2) SOL_LAUNCH((k_conv5x5_sb<2, 1, true>), dim3(grid3), dim3(768), lds, s, a, nrows);
+        else if (nprod == 6) SOL_LAUNCH((k_conv5x5_sb<1, 0, true>), dim3(grid3), dim3(768), lds, s, a, nrows);
+        else SOL_LAUNCH((k_conv5x5_sb<1, 1, true>), dim3(grid3), dim3(768), lds, s, a, nrows);
+        SOL_LAUNCH_CHECK();
+        return SOL_OK;
+    }
     if (a.xmax) {                                     // per-tensor absmax known: fp16 three-product kernels
         if (NT == 2) SOL_LAUNCH((k_conv5x5_sb<2, 2>), dim3(grid3), dim3(768), lds, s, a, nrows);
         else SOL_LAUNCH((k_conv5x5_sb<1, 2>), dim3(grid3), dim3(768), lds, s, a, nrows);

@@ -35,7 +35,8 @@ constexpr int TH_NROWS = 7;
 constexpr int TH_PART = 15 * 64 * 16;            // [unit][pixel][4 floats]
 constexpr int TH_LDS = TH_NROWS * TH_ROW + TH_PART + 128;    // + {absmax word, ticket, loss ticket, pad x3, 16 wave slots}
 
-template <int CON, int NW>                       // CON: output channels computed, 2 (CO <= 2) or 4 (CO <= 4); NW: waves per workgroup, 16 or 8
+// MASK: pitched rows (ConvArgs::WV < 64 valid pixels, sol_conv5x5_cols) -- pad pixels are stored as 0.0f and stay out of a.ymax; a separate instantiation
+template <int CON, int NW, bool MASK = false>    // CON: output channels computed, 2 (CO <= 2) or 4 (CO <= 4); NW: waves per workgroup, 16 or 8
 __global__ void __launch_bounds__(NW * 64) k_conv5x5_thin32(ConvArgs a, int nrows) {
     extern __shared__ __align__(16) unsigned char smem_th[];
     unsigned char* const rows = smem_th;
@@ -164,7 +165,11 @@ __global__ void __launch_bounds__(NW * 64) k_conv5x5_thin32(ConvArgs a, int nrow
             float* yp = a.y + ((size_t)gy * W + lane) * a.CO;
 #pragma unroll
             for (int c = 0; c < CON; ++c)
-                if (c < a.CO) { yp[c] = oc[c]; vmax = fmaxf(vmax, fabsf(oc[c])); }
+                if (c < a.CO) {
+                    const float v = MASK && lane >= a.WV ? 0.f : oc[c];
+                    yp[c] = v;
+                    vmax = fmaxf(vmax, fabsf(v));
+                }
         }
     }
     // workgroup uniform: wave sums -> LDS slots -> the last wave's fixed-order sum -> ONE exact integer add per workgroup (loss_add_exact)
@@ -187,11 +192,25 @@ bool sol_conv_thin32_usable(const ConvArgs& a, int NT) {
 int sol_conv_thin32_launch(hipStream_t s, const ConvArgs& a, int ntiles) {
     SOL_REQUIRE(a.CI == 32 && a.W == 64 && a.CO >= 1 && a.CO <= 4 && a.wp, "k_conv5x5_thin32: 32 input channels, 64-pixel rows, <= 4 output channels (got %d, %d, %d)", a.CI, a.W, a.CO);
     static std::atomic<unsigned long long> optin{0};
-    if (int e = sol_lds_optin(optin, {SOL_K((k_conv5x5_thin32<2, 16>)), SOL_K((k_conv5x5_thin32<4, 16>)), SOL_K((k_conv5x5_thin32<2, 8>)), SOL_K((k_conv5x5_thin32<4, 8>))}, "k_conv5x5_thin32")) return e;
+    if (int e = sol_lds_optin(optin, {SOL_K((k_conv5x5_thin32<2, 16>)), SOL_K((k_conv5x5_thin32<4, 16>)), SOL_K((k_conv5x5_thin32<2, 8>)), SOL_K((k_conv5x5_thin32<4, 8>)),
+                                         SOL_K((k_conv5x5_thin32<2, 16, true>)), SOL_K((k_conv5x5_thin32<4, 16, true>)), SOL_K((k_conv5x5_thin32<2, 8, true>)), SOL_K((k_conv5x5_thin32<4, 8, true>))},
+                              "k_conv5x5_thin32")) return e;
     const int nrows = ntiles;                             // tiles_x == 1: one tile per image row
     int grid = (nrows + 2) / 3;
     if (grid > 64) grid = (grid + 7) / 8 * 8;             // XCD-aware tile order (xcd_tile); padding workgroups own no rows
     const bool w8 = sol_opt().conv_thin_valu == 2;     // (A/B: eight waves, two units each)
+    if (sol_conv_masked(a)) {                          // pitched rows: the same choice among the MASK instantiations (never the correction mode)
+        SOL_REQUIRE(!a.cvy, "k_conv5x5_thin32: the correction epilogue takes dense rows");
+        if (a.CO <= 2) {
+            if (w8) SOL_LAUNCH((k_conv5x5_thin32<2, 8, true>), dim3(grid), dim3(512), TH_LDS, s, a, nrows);
+            else SOL_LAUNCH((k_conv5x5_thin32<2, 16, true>), dim3(grid), dim3(1024), TH_LDS, s, a, nrows);
+        } else {
+            if (w8) SOL_LAUNCH((k_conv5x5_thin32<4, 8, true>), dim3(grid), dim3(512), TH_LDS, s, a, nrows);
+            else SOL_LAUNCH((k_conv5x5_thin32<4, 16, true>), dim3(grid), dim3(1024), TH_LDS, s, a, nrows);
+        }
+        SOL_LAUNCH_CHECK();
+        return SOL_OK;
+    }
     if (a.CO <= 2) {
         if (w8) SOL_LAUNCH((k_conv5x5_thin32<2, 8>), dim3(grid), dim3(512), TH_LDS, s, a, nrows);
         else SOL_LAUNCH((k_conv5x5_thin32<2, 16>), dim3(grid), dim3(1024), TH_LDS, s, a, nrows);

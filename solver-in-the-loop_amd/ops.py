@@ -395,6 +395,19 @@ def conv5x5_scaled_raw(x, packed, bias, residual, act_ref, cout, epilogue, slope
     return y
 
 
+def conv5x5_cols_raw(x, packed, bias, residual, act_ref, cout, epilogue, slope, wv, x_absmax=None, y_absmax=None, y=None):
+    """sol_conv5x5_cols: sol_conv5x5_scaled on pitched rows -- x [B,H,W,cin] with W % 64 == 0 of which the first `wv` columns are data
+    and the rest ZERO (the caller's duty, also for residual / act_ref); the pad columns of y are written as zeros and stay out of
+    y_absmax.  y: an output buffer to write into (default: a new one)."""
+    lib = _lib.load()
+    B, H, W, cin = x.shape
+    if y is None:
+        y = torch.empty(B, H, W, cout, dtype=torch.float32, device=x.device)
+    check(lib.sol_conv5x5_cols(stream(), ptr(x), ptr(packed), ptr(bias), ptr(residual), ptr(act_ref), ptr(y),
+                               B, H, W, int(wv), cin, cout, epilogue, float(slope), ptr(x_absmax), ptr(y_absmax)))
+    return y
+
+
 class Conv5x5Fn(torch.autograd.Function):
     """y = act(conv5x5_same(x, w) + b (+ residual)), NHWC, w in Keras HWIO layout."""
 

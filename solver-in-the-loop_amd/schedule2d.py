@@ -37,16 +37,35 @@ def _int_array(vals):
     return (C.c_int32 * len(vals))(*[int(v) for v in vals])
 
 
+def row_pitch(H, W):
+    """Pixels per row of the buffers an [H, W] image runs in: W itself for the shapes the convolutions take as they are (check_shape of
+    csrc/conv5x5.hip: W >= 4 divides 64 with H % (64 / W) == 0, or W is a multiple of 64), else the next multiple of 64 -- the pitched
+    layout of NetSchedule2D(any_width=True) / sol_conv5x5_cols."""
+    H, W = int(H), int(W)
+    if W >= 4 and (W % 64 == 0 or (W <= 64 and 64 % W == 0 and H % (64 // W) == 0)):
+        return W
+    return 64 * ((W + 63) // 64)
+
+
 class NetSchedule2D:
-    def __init__(self, net, B, H, W, train=True):
+    def __init__(self, net, B, H, W, train=True, any_width=False):
         """train=False (a roll-out: forward only): no weight-gradient partial buffers, no backward-data packs, and the absmax slots of the
-        forward are persistent buffers cleared by one library launch per call (no torch fill between the launches)."""
+        forward are persistent buffers cleared by one library launch per call (no torch fill between the launches).
+
+        any_width=True: a width the convolutions refuse (row_pitch(H, W) != W) runs in PITCHED rows -- every activation, absmax slot set
+        and dz is a [B,H,P,c] buffer with P = row_pitch(H, W) whose columns >= W are zero.  The input is copied into the valid columns of
+        a zero-initialised [B,H,P,4] buffer, every convolution is sol_conv5x5_cols (the 64-pixel-tile kernels with a column-masked
+        epilogue: the pad columns of every output are written as zeros, so the next layer reads them as its SAME padding), and the
+        weight gradient is the unchanged sol_conv5x5_bwd_weight at the pitch (zero pad columns of x and dz add exact zeros to dw / db).
+        forward / backward take and return DENSE [B,H,W,c] tensors.  With any_width=False nothing changes."""
         if net.name not in ("mars_moon", "mercury"):
             raise _lib.SolError("NetSchedule2D: no hand-written schedule for network %r" % net.name)
         _lib.require_gpu()
         self.lib = lib = _lib.load()
         self.net, self.B, self.H, self.W = net, int(B), int(H), int(W)
-        self.scaled = self.W % 64 == 0               # 64-pixel rows: the split-precision kernels + absmax hand-over
+        self.P = row_pitch(H, W) if any_width else self.W      # pixels per buffer row
+        self.pitched = self.P != self.W
+        self.scaled = self.P % 64 == 0               # 64-pixel rows: the split-precision kernels + absmax hand-over
         self.train = bool(train)
         if net.cin > 4:
             raise _lib.SolError("NetSchedule2D: at most 4 input channels (got %d)" % net.cin)
@@ -61,7 +80,7 @@ class NetSchedule2D:
         for cin, cout in dims:
             u = _Unit()
             u.cin, u.cout, u.cin_k = cin, cout, (4 if cin <= 4 else 32)
-            u.ws = int(lib.sol_conv5x5_bwd_weight_ws_floats(self.B, self.H, self.W, u.cin_k, cout)) if self.train else 0
+            u.ws = int(lib.sol_conv5x5_bwd_weight_ws_floats(self.B, self.H, self.P, u.cin_k, cout)) if self.train else 0
             total += (u.ws + 3) // 4 * 4
             u.pf = f(lib.sol_conv5x5_packed_floats(cin, cout, ops.CONV_FWD))
             u.pb = f(lib.sol_conv5x5_packed_floats(cout, cin, ops.CONV_BWD_DATA)) if self.train else None
@@ -72,6 +91,10 @@ class NetSchedule2D:
             u.part = self._partials[off:off + u.ws]
             off += (u.ws + 3) // 4 * 4
         self._zero_bias = torch.zeros(net.cout, dtype=torch.float32, device=dev)
+        if self.pitched:
+            # the dense input / output gradient land in the valid columns of these; nothing ever writes their pad columns or spare channels
+            self._xin = torch.zeros(self.B, self.H, self.P, 4, dtype=torch.float32, device=dev)
+            self._gin = torch.zeros(self.B, self.H, self.P, 4, dtype=torch.float32, device=dev) if self.train else None
         # kernels / biases: views of the flat parameter buffer (updated in place by Adam: the addresses are stable), or persistent copies of the
         # halves of model_mercury's 32 -> 64 / 64 -> 2 kernels (refreshed by begin_step)
         p = [t.detach() for t in net.tensors()]
@@ -98,7 +121,7 @@ class NetSchedule2D:
                            _int_array([u.cout for u in self.units] + [u.cin for u in self.units]), _int_array([ops.CONV_FWD] * n + [ops.CONV_BWD_DATA] * n),
                            _ptr_array([u.pf for u in self.units] + [u.pb for u in self.units]))
         self._reduce_args = (n, _ptr_array([u.part for u in self.units]), _ptr_array([u.dw for u in self.units]), _ptr_array([u.db for u in self.units]),
-                             self.B, self.H, self.W, _int_array([u.cin for u in self.units]), _int_array([u.cout for u in self.units]), 0)
+                             self.B, self.H, self.P, _int_array([u.cin for u in self.units]), _int_array([u.cout for u in self.units]), 0)
 
     # ---- once per training step -------------------------------------------------------------------------------------------
     def begin_step(self):
@@ -116,7 +139,10 @@ class NetSchedule2D:
         B, H, W, cin = x.shape
         y = torch.empty(B, H, W, cout, dtype=torch.float32, device=x.device)
         sl = float(self.net.slope)
-        if self.scaled:
+        if self.pitched:
+            check(self.lib.sol_conv5x5_cols(stream(), ptr(x), ptr(packed), ptr(bias), ptr(residual), ptr(act_ref), ptr(y),
+                                            B, H, W, self.W, cin, cout, epi, sl, ptr(xmax), ptr(ymax)))
+        elif self.scaled:
             check(self.lib.sol_conv5x5_scaled(stream(), ptr(x), ptr(packed), ptr(bias), ptr(residual), ptr(act_ref), ptr(y),
                                               B, H, W, cin, cout, epi, sl, ptr(xmax), ptr(ymax)))
         else:
@@ -126,7 +152,7 @@ class NetSchedule2D:
 
     def _bww(self, u, xk, dz):
         """u.part += the weight-gradient partial sums of this step"""
-        check(self.lib.sol_conv5x5_bwd_weight(stream(), ptr(xk), ptr(dz), ptr(u.part), self.B, self.H, self.W, u.cin_k, u.cout))
+        check(self.lib.sol_conv5x5_bwd_weight(stream(), ptr(xk), ptr(dz), ptr(u.part), self.B, self.H, self.P, u.cin_k, u.cout))
 
     def _slots(self, n, dev):
         if not self.train and self.scaled:          # forward only: the persistent slots, cleared by a library launch
@@ -134,10 +160,25 @@ class NetSchedule2D:
             return self._fwd_slots
         return torch.zeros(n, ops.AMAX_SLOTS, dtype=torch.int32, device=dev) if self.scaled else [None] * n
 
+    # ---- pitched rows: dense <-> pitched copies (kernels: _lib.dcopy_ is a strided copy_ or sol_copy_words, never a memcpy node) ----
+    def _pad_in(self, buf, x):
+        """buf[:, :, :W, :c] = x [B,H,W,c]; the pad columns and the spare channels of buf stay zero"""
+        _lib.dcopy_(buf[:, :, :self.W, :x.shape[-1]], x)
+        return buf
+
+    def _crop(self, y):
+        """dense [B,H,W,c] copy of the valid columns of y [B,H,P,c]"""
+        return _lib.dcopy_(torch.empty(self.B, self.H, self.W, y.shape[-1], dtype=torch.float32, device=y.device), y[:, :, :self.W])
+
     # ---- forward ------------------------------------------------------------------------------------------------------------
     def forward(self, x):
         """x [B,H,W,cin] -> (out [B,H,W,cout], state for backward)"""
-        xk = ops._pad_channels(_lib.f32(x.detach()), 4)
+        if self.pitched:
+            xk = self._pad_in(self._xin, _lib.f32(x.detach()))
+            if self.train:
+                xk = _lib.dclone(xk)                  # the reverse sweep reads this step's input after later steps have overwritten the buffer
+        else:
+            xk = ops._pad_channels(_lib.f32(x.detach()), 4)
         U, L, N = self.units, ops.EPI_LRELU, ops.EPI_NONE
         if self.net.name == "mars_moon":
             am = self._slots(11, xk.device)
@@ -155,6 +196,8 @@ class NetSchedule2D:
             oa = self._conv(ha, U[3].pf, U[3].b, None, None, self.net.cout, N, am[1], None)
             out = self._conv(hb, U[4].pf, U[4].b, oa, None, self.net.cout, N, am[2], None)
             acts = [h, ha, hb]
+        if self.pitched:
+            out = self._crop(out)
         return out, (xk, am, acts)
 
     # ---- reverse sweep ------------------------------------------------------------------------------------------------------
@@ -166,7 +209,11 @@ class NetSchedule2D:
         xk, am, acts = state
         U, D, N = self.units, ops.EPI_DLRELU, ops.EPI_NONE
         g = _lib.f32(g_out).contiguous()
-        g4 = ops._pad_channels(g, 4)
+        if self.pitched:
+            g4 = self._pad_in(self._gin, g)
+            g = g4[..., :g.shape[-1]].contiguous()    # [B,H,P,cout], zero pad columns: the last layer's dz
+        else:
+            g4 = ops._pad_channels(g, 4)
         if self.net.name == "mars_moon":
             zm = self._slots(11, xk.device)
             self._bww(U[11], acts[10], g)
@@ -178,7 +225,8 @@ class NetSchedule2D:
                 self._bww(U[1 + 2 * k], hprev, dz1)
                 dz = self._conv(dz1, U[1 + 2 * k].pb, None, dz, hprev, 32, D, zm[2 * k + 1], zm[2 * k])
             self._bww(U[0], xk, dz)
-            return self._conv(dz, U[0].pb, None, None, None, U[0].cin, N, zm[0], None)
+            dx = self._conv(dz, U[0].pb, None, None, None, U[0].cin, N, zm[0], None)
+            return self._crop(dx) if self.pitched else dx
         h, ha, hb = acts
         zm = self._slots(3, xk.device)
         self._bww(U[3], ha, g)
@@ -190,7 +238,8 @@ class NetSchedule2D:
         t = self._conv(dha, U[1].pb, None, None, None, 32, N, zm[1], None)
         dh = self._conv(dhb, U[2].pb, None, t, h, 32, D, zm[2], zm[0])
         self._bww(U[0], xk, dh)
-        return self._conv(dh, U[0].pb, None, None, None, U[0].cin, N, zm[0], None)
+        dx = self._conv(dh, U[0].pb, None, None, None, U[0].cin, N, zm[0], None)
+        return self._crop(dx) if self.pitched else dx
 
     # ---- once per training step ---------------------------------------------------------------------------------------------
     def end_step(self):

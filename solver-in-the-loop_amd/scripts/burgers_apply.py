@@ -31,6 +31,7 @@ def main(argv=None):
     p.add_argument("--model", default="/tmp/phiflow/tf/model.pt", help="path to a trained model")
     p.add_argument("--seed", default=0, type=int, help="seed of the random initial velocity (without --initvH)")
     p.add_argument("--no-graph", action="store_true", help="step eagerly instead of replaying a captured hipGraph")
+    p.add_argument("--any-width", action="store_true", help="run the correction network on rows of any width (pitched rows with column-masked convolutions) instead of refusing a width the convolutions do not take")
     params = vars(p.parse_args(argv))
     select_gpu(params["gpu"])
     log = logger()
@@ -63,7 +64,7 @@ def main(argv=None):
     model.summary(print_fn=log.info)
     std_f = None if params["noforce"] else data_stats["std"][1]
     ro = sol_amd.BurgersRollout(model, dom, 1, params["dt"], data_stats["std"][0], std_f, noforce=params["noforce"],
-                                use_graph=not params["no_graph"])
+                                use_graph=not params["no_graph"], any_width=params["any_width"])
     ro.reset(v0)
     fc = None if params["noforce"] else np.asarray(down(scene.read_zipped_array(fc_files[0])), dtype=np.float32)
     scene.scene_write(path, [ro.vel.cpu().numpy(), ro.corr.cpu().numpy()], ["velTf", "corTf"], 0)

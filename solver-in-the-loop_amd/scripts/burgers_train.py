@@ -43,6 +43,7 @@ def main(argv=None):
     p.add_argument("--inittf", default=None)
     p.add_argument("--tf", default="/tmp/phiflow/tf")
     p.add_argument("--no-graph", action="store_true", help="step the unrolled graph eagerly instead of replaying a captured hipGraph")
+    p.add_argument("--any-width", action="store_true", help="run the correction network on rows of any width (pitched rows with column-masked convolutions) instead of refusing a width the convolutions do not take")
     params = vars(p.parse_args(argv))
     select_gpu(params["gpu"])
     log = logger(params["log"])
@@ -73,7 +74,7 @@ def main(argv=None):
     else:
         model.set_weights(sol_amd.ConvNet.load(params["tf"] + "/model_epoch{:04d}.pt".format(params["resume"]), device="cpu").get_weights())
     trainer = sol_amd.BurgersTrainer(model, dom, B, ms, dt, dataset.dataStats["std"][0], dataset.dataStats["std"][1],
-                                     noforce=params["noforce"], use_graph=not params["no_graph"])
+                                     noforce=params["noforce"], use_graph=not params["no_graph"], any_width=params["any_width"])
     current_lr = params["lr"]
     l2 = None
     for j in range(params["epochs"]):

@@ -27,6 +27,7 @@ def main(argv=None):
     p.add_argument("-o", "--output", default="/tmp/phiflow/run", help="path to an output directory")
     p.add_argument("--stats", default="/tmp/phiflow/data/dataStats.pickle", help="path to datastats")
     p.add_argument("--model", default="/tmp/phiflow/tf/model.pt", help="path to a trained model")
+    p.add_argument("--any-width", action="store_true", help="run the correction network on rows of any width (pitched rows with column-masked convolutions) instead of refusing a width the convolutions do not take")
     add_scene_args(p, warm_start=True)
     params = vars(p.parse_args(argv))
     select_gpu(params["gpu"])
@@ -71,7 +72,7 @@ def main(argv=None):
                                                   else "it belongs to the CG solve of the large grids"))
     # (a CG scene runs eagerly, every solve stops at convergence; a direct-solve scene replays one captured step)
     ro = sol_amd.make_rollout(model, masks, 1, Y, X, dom.dx[1], data_stats["std"][1], data_stats["ext.std"][0],
-                              use_graph=ops.is_direct(masks.pressure_solver), cg_warm_start=warm)
+                              use_graph=ops.is_direct(masks.pressure_solver), cg_warm_start=warm, any_width=params["any_width"])
     f = lambda a: torch.as_tensor(np.ascontiguousarray(a), dtype=torch.float32, device="cuda").contiguous()
     vy0, vx0 = scene.split_staggered(np.asarray(vn, dtype=np.float32))
     d, vy, vx = f(np.asarray(d0)[..., 0]), f(vy0), f(vx0)

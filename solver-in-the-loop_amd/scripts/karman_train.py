@@ -49,6 +49,7 @@ def main(argv=None):
     p.add_argument("--tf", default="/tmp/phiflow/tf", help="path to an output dir (model, logs, etc.)")
     p.add_argument("--host-feed", action="store_true", help="assemble every batch on the host and copy it (the reference's feed_dict path) "
                                                             "instead of gathering from the device-resident set")
+    p.add_argument("--any-width", action="store_true", help="run the correction network on rows of any width (pitched rows with column-masked convolutions) instead of refusing a width the convolutions do not take")
     add_scene_args(p)
     params = vars(p.parse_args(argv))
     select_gpu(params["gpu"])
@@ -136,7 +137,7 @@ def main(argv=None):
                                  clip_grad=params["clip_grad"],
                                  in_std_v=dataset.dataStats["in.std"][1] if "in.std" in dataset.dataStats else None,
                                  out_std_v=dataset.dataStats["out.std"] if "out.std" in dataset.dataStats else None,
-                                 pressure_solver=params["pressure_solver"], **flow_kwargs(rec))
+                                 pressure_solver=params["pressure_solver"], any_width=params["any_width"], **flow_kwargs(rec))
     # persistent device buffers: the captured hipGraph keeps their addresses, new data is copied in
     f32 = lambda shape: torch.empty(shape, dtype=torch.float32, device=dev)
     d0, vy0, vx0, re = f32((Bl, Y, X)), f32((Bl, Y + 1, X)), f32((Bl, Y, X + 1)), f32((Bl,))

@@ -284,10 +284,13 @@ class LargeGridRollout:
     a CG scene."""
 
     def __init__(self, net, masks, B, Y, X, dx, std_v, std_re, dt=1.0, res=None, in_std_v=None, out_std_v=None,
-                 conv_precision="split", use_graph=True, cg_warm_start=False, **solver):
+                 conv_precision="split", use_graph=True, cg_warm_start=False, any_width=False, **solver):
+        """any_width=True: X need not be a multiple of 64 -- the network runs in pitched rows (NetSchedule2D(any_width=True): the features
+        are copied into zero-padded rows of 64 * ceil(X / 64) pixels and the output is cropped; the solver step and the correction stay
+        dense)."""
         if not ops.beyond_one_workgroup(Y, X):
             raise ValueError("LargeGridRollout: a %dx%d domain is served by the one-workgroup roll-out -- use SolRollout (make_rollout picks)" % (Y, X))
-        if X % 64 != 0:
+        if X % 64 != 0 and not any_width:
             raise ValueError("LargeGridRollout: the convolutions of a large domain take rows of X %% 64 == 0 cells (got %dx%d); "
                              "no roll-out class serves this grid (KarmanFlow.step advances it without the network)" % (Y, X))
         cg = masks.pressure_solver == "cg"
@@ -307,7 +310,8 @@ class LargeGridRollout:
         dev = self.device = net.params.device
         self._fs3 = (C.c_float * 3)(*[1.0 / float(v) for v in (list(in_std_v if in_std_v is not None else std_v) + [std_re])])
         self._so = tuple(float(v) for v in (out_std_v if out_std_v is not None else std_v))
-        self._sched = NetSchedule2D(net, B, Y, X, train=False)
+        self.any_width = bool(any_width)
+        self._sched = NetSchedule2D(net, B, Y, X, train=False, any_width=self.any_width)
         nd, ny, nx = B * Y * X, B * (Y + 1) * X, B * Y * (X + 1)
         z = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)
         views = lambda flat: (flat[:nd].view(B, Y, X), flat[nd:nd + ny].view(B, Y + 1, X), flat[nd + ny:].view(B, Y, X + 1))
@@ -373,10 +377,10 @@ class LargeGridRollout:
 
 
 def make_rollout(net, masks, B, Y, X, dx, std_v, std_re, **kw):
-    """SolRollout for the one-workgroup solver grids, LargeGridRollout beyond them (use_graph / cg_warm_start belong to the latter)."""
+    """SolRollout for the one-workgroup solver grids, LargeGridRollout beyond them (use_graph / cg_warm_start / any_width belong to the latter)."""
     if ops.beyond_one_workgroup(Y, X):
         return LargeGridRollout(net, masks, B, Y, X, dx, std_v, std_re, **kw)
-    for k in ("use_graph", "cg_warm_start"):
+    for k in ("use_graph", "cg_warm_start", "any_width"):
         kw.pop(k, None)
     return SolRollout(net, masks, B, Y, X, dx, std_v, std_re, **kw)
 
@@ -501,12 +505,13 @@ class GraphTrainer(_AdamDP):
             _lib.dcopy_(dst, src)
 
     _adjoint_of_first_step = True
+    _any_width = False                  # LargeGridTrainer(any_width=True): the network's launches in pitched rows (NetSchedule2D)
 
     def _schedule_setup(self):
         """Once, on the first run of the schedule: the network's launches, the scene's device masks, the solver configuration"""
         from .schedule2d import NetSchedule2D
         B, Y, X = self.B, self.Y, self.X
-        self._sched = NetSchedule2D(self.net, B, Y, X)
+        self._sched = NetSchedule2D(self.net, B, Y, X, any_width=self._any_width)
         self._mk = self.sim._masks(self.dom, self.bcv, self.bcm, self.device)
         self._kcfg = ops.karman_cfg(B, Y, X, self.dom.dx[1], dt=self.dt, res=self.res, masks=self._mk, **self.sim._solver)
         self._fs = [1.0 / float(v) for v in self._scale_in_host]
@@ -599,18 +604,24 @@ class LargeGridTrainer(GraphTrainer):
     convergence and is fully supported.  After a step `solve_info` holds "iterations" / "converged" [msteps, B] and "iterations_bwd" /
     "converged_bwd" [msteps - 1, B] (the first unrolled step's input receives no gradient: its solver adjoint is not run) for CG scenes."""
 
-    def __init__(self, net, B, Y, X, msteps, std_v, std_re, **kw):
+    def __init__(self, net, B, Y, X, msteps, std_v, std_re, any_width=False, **kw):
+        """any_width=True: X need not be a multiple of 64 -- the network's forward and reverse launches run in pitched rows of
+        64 * ceil(X / 64) pixels (NetSchedule2D(any_width=True): column-masked convolutions, the weight gradient at the pitch); the solver
+        pair, the correction and the loss stay dense."""
+        if any_width and kw.get("schedule", "manual") == "autograd":
+            raise ValueError("LargeGridTrainer: any_width=True runs the hand-written schedule only; schedule='autograd' (the composition "
+                             "over ops.conv5x5) takes no pitched rows")
         if kw.get("schedule", "manual") != "manual":
             raise ValueError("LargeGridTrainer runs the hand-written schedule only (schedule='manual')")
+        self._any_width = bool(any_width)       # (before the base constructor: _check_grid reads it)
         super().__init__(net, B, Y, X, msteps, std_v, std_re, **kw)
         self.solve_info = {}
 
-    @staticmethod
-    def _check_grid(Y, X):
+    def _check_grid(self, Y, X):
         if not ops.beyond_one_workgroup(Y, X):
             raise ValueError("LargeGridTrainer: a %dx%d domain is served by the one-workgroup trainers -- use SolTrainer (mars_moon) or "
                              "GraphTrainer (make_trainer picks)" % (Y, X))
-        if X % 64 != 0:
+        if X % 64 != 0 and not self._any_width:
             raise ValueError("LargeGridTrainer: the convolutions of a large domain take rows of X %% 64 == 0 cells (got %dx%d)" % (Y, X))
 
     _adjoint_of_first_step = False
@@ -661,7 +672,8 @@ def make_trainer(net, masks, B, Y, X, msteps, dx, std_v, std_re, **kw):
     if net.name == "mars_moon":
         # the C++ schedule takes its scene and its pressure solver from `masks` alone (obstacles / active / pressure_solver
         # describe them for GraphTrainer's KarmanFlow)
-        for k in ("obstacles", "active", "pressure_solver"):
+        for k in ("obstacles", "active", "pressure_solver", "any_width"):
             kw.pop(k, None)
         return SolTrainer(net, masks, B, Y, X, msteps, dx, std_v, std_re, **kw)
+    kw.pop("any_width", None)           # (the one-workgroup grids: the keyword belongs to LargeGridTrainer)
     return GraphTrainer(net, B, Y, X, msteps, std_v, std_re, dx=dx, masks=masks, **kw)     # unknown keywords raise TypeError
