@@ -78,6 +78,9 @@ int sol_abi_sizes(int32_t* karman_cfg, int32_t* burgers_cfg, int32_t* train_cfg)
  *                       flushed with one global atomic per non-zero cell; 0: every contribution is a global atomic.  Same results bit for bit
  *   k2d_adj_tile (1)    karman-2d large grids: the advection adjoint's fixed-point scatter goes through an int64 LDS window per workgroup (16 x 16 cells
  *                       + halo 4), flushed with one global atomic per non-zero cell; 0: every contribution is a global atomic.  Same results bit for bit
+ *   k2d_dens_adj_tile (1) karman-2d, any grid: the density adjoint's fixed-point scatter (sol_karman_density_bwd) goes through an int64 LDS window per
+ *                       workgroup (16 x 16 cells + halo 4), flushed with one global atomic per non-zero cell; 0: every contribution is a global atomic.
+ *                       Same results bit for bit
  *   k3d_conv_persist (0) karman-3d: 1 = the one-launch Conv3D kernel as 256 workgroups of consecutive eight-row tiles (the next tile's rows and weight
  *                       sets requested during the last tap rows of the tile) when the tile count is a multiple of 256; same results bit for bit,
  *                       measured slower (register spills), kept as a tested experiment
@@ -240,6 +243,30 @@ int sol_karman_step_bwd_large(const sol_karman_cfg* cfg, void* stream,
                               const int32_t* direct_header_host,
                               const float* box_blob, const int32_t* box_header_host, int32_t* cg_info,
                               void* workspace, size_t workspace_bytes);
+
+/* Adjoint of the step's marker DENSITY, for every grid the 2-D step runs on (csrc/karman_density_bwd.hip; any Y, X >= 2, B <= 65535): the
+ * gradient of a loss on d_out with respect to d_in and, through the departure points of the density's advection, to the step's input
+ * velocity.  The entry points above carry no density gradient; this one is a separate set of launches that a caller adds when its loss
+ * looks at the density.  It needs the step's input density d_in [B,Y,X], the saved post-diffusion velocity of the forward step
+ * (sol_karman_step_fwd or sol_karman_step_fwd_large_saved) and g_d_out [B,Y,X]; `inflow` [Y,X] is read only with cfg.inflow_before (the
+ * advected field is then d_in + inflow) and may be NULL otherwise.  Per cell (j,i), c = saved velocity, g = g_d_out[j,i]:
+ *     uy = (cy[j,i] + cy[j+1,i]) / 2, ux = (cx[j,i] + cx[j,i+1]) / 2; (oy, ox) = -(uy, ux) dt/dx; (fy, fx) = floor; (wy, wx) = o - f
+ *     g_d_in[j+fy+dj, i+fx+di] += by(dj) bx(di) g   inside the grid (the zero ghost ring takes nothing)
+ *     gU_y[j,i] = -dt/dx g s_y,  gU_x[j,i] = -dt/dx g s_x   with the bilinear slopes s of the gathered field
+ *   then g_c = the cell-to-face transpose of gU (g_cy[jf,i] = (gU_y[jf-1,i] + gU_y[jf,i]) / 2, out-of-range cells zero; g_cx likewise) and
+ *     g_vy_in = (I + alpha L^T)((1 - velBCyMask) g_cy),  g_vx_in = (I + alpha L^T) g_cx,  alpha = dt res^2 / re[b]
+ * as the velocity adjoints apply it.  The scatter into g_d_in is 64-bit fixed point (order independent: results are bit-reproducible; LDS
+ * window per 16 x 16 tile, option k2d_dens_adj_tile), scaled by max|g_d_out| of the simulation; a non-finite g_d_out makes EVERY gradient
+ * of that simulation NaN.  g_d_in [B,Y,X] is written.  accumulate = 0: g_vy_in / g_vx_in are written; accumulate = 1: the density's part
+ * is ADDED onto them (the velocity adjoint wrote there first; one fp32 add per face, deterministic).  Outputs must not alias inputs or
+ * each other.  No synchronisation, no allocation, nothing read on the host: capturable.  `workspace`: DEVICE scratch of
+ * sol_karman_density_bwd_workspace_bytes(cfg) bytes.  The gradient with respect to `re` is not computed. */
+size_t sol_karman_density_bwd_workspace_bytes(const sol_karman_cfg* cfg);
+int sol_karman_density_bwd(const sol_karman_cfg* cfg, void* stream,
+                           const float* d_in, const float* inflow, const float* saved_vy, const float* saved_vx,
+                           const float* re, const float* velBCyMask, int64_t bc_batch_stride,
+                           const float* g_d_out, float* g_d_in, float* g_vy_in, float* g_vx_in, int accumulate,
+                           void* workspace, size_t workspace_bytes);
 
 /* active  [Y,X]  1 - obstacle mask (cell centres inside Obstacle geometries -> 0)
  * inflow  [Y,X]  inflow rate mask (Inflow(box[5:10,25:75]) -> 1 inside)

@@ -271,6 +271,8 @@ struct SolOptions {
                           //    stencil phases on row bands with recomputed halos, the direct solve on band 0's CU, two hand-offs through global memory); 0: one workgroup
     int k2d_adj_tile;     // 1 (default): the large-grid karman-2d advection adjoint scatters into an int64 LDS window per workgroup tile (k_lb_advect_adj_tile);
                           //    0: global atomics only (k_lb_advect_adj).  Same results bit for bit
+    int k2d_dens_adj_tile;// 1 (default): the karman-2d density adjoint (karman_density_bwd.hip) scatters its field term into an int64 LDS window per 16 x 16-cell
+                          //    tile (k_kd_advect_adj_tile); 0: global atomics only (k_kd_advect_adj).  Same results bit for bit
     int k3d_tile;         // 1: karman-3d advection from LDS tiles holding the full z column + halo; 0 (default, measured faster at B <= 2): wave-per-column gathers from global memory
 };
 SolOptions& sol_opt();

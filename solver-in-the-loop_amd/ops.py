@@ -201,7 +201,8 @@ def karman_step_large_bwd(svy, svx, re, gvy, gvx, cfg, masks, workspace=None, in
     return oy, ox
 
 
-def karman_step_large(d, vy, vx, re, cfg, masks, workspace=None, info=None, feat=None, feat_scale=None, p_guess=None, out=None):
+def karman_step_large(d, vy, vx, re, cfg, masks, workspace=None, info=None, feat=None, feat_scale=None, p_guess=None, out=None,
+                      density_grad=False):
     """The step for grids beyond the one-workgroup kernels (data generation at 256 x 128,
     /root/reference/karman-2d/karman.py:98-159): sol_karman_step_fwd_large (direct solve) or sol_karman_step_fwd_large_cg (CG solve,
     masks.pressure_solver == "cg").  Returns (d, vy, vx) after the step; with the CG solve, `info` (a dict) receives "iterations" and
@@ -211,7 +212,9 @@ def karman_step_large(d, vy, vx, re, cfg, masks, workspace=None, info=None, feat
     No-grad extras (a roll-out, trainer.LargeGridRollout): `feat` [B,Y,X,4] receives the network's input, to_feature of the new velocity
     times `feat_scale` (three factors, 1 / std; channel 3 is zero); `p_guess` [B,Y,X] warm-starts the CG solve
     (sol_karman_step_fwd_large_cg_warm: read as the initial guess, overwritten with the step's pressure) and is an error on a scene with
-    the direct solver; `out` = (d, vy, vx) buffers to write instead of fresh tensors (they must not be the inputs)."""
+    the direct solver; `out` = (d, vy, vx) buffers to write instead of fresh tensors (they must not be the inputs).
+    density_grad=True (opt-in): the density output is differentiable too (KarmanStepDensFn: same forward launches; the differentiable
+    form is taken when any of d, vy, vx requires a gradient)."""
     if p_guess is not None and masks.direct is not None:
         raise ValueError("karman_step_large: p_guess warm-starts the CG pressure solve; this scene runs the direct solver (no iteration to start)")
     _lib.require_gpu()
@@ -220,9 +223,11 @@ def karman_step_large(d, vy, vx, re, cfg, masks, workspace=None, info=None, feat
     B, Y, X = cfg.B, cfg.Y, cfg.X
     assert vy.shape == (B, Y + 1, X) and vx.shape == (B, Y, X + 1) and d.shape == (B, Y, X) and re.shape == (B,)
     extras = feat is not None or p_guess is not None or out is not None
-    if torch.is_grad_enabled() and (vy.requires_grad or vx.requires_grad):
+    if torch.is_grad_enabled() and (vy.requires_grad or vx.requires_grad or (density_grad and d.requires_grad)):
         if extras:
             raise ValueError("karman_step_large: feat / p_guess / out belong to the no-grad step (the differentiable step keeps its own state)")
+        if density_grad:
+            return KarmanStepDensFn.apply(d, vy, vx, re, cfg, masks, workspace, info)
         return KarmanStepLargeFn.apply(d, vy, vx, re, cfg, masks, workspace, info)
     if (feat is None) != (feat_scale is None):
         raise ValueError("karman_step_large: feat and feat_scale go together")
@@ -298,52 +303,136 @@ def _scale3(vals):
     return (C.c_float * 3)(*[float(v) for v in vals])
 
 
+def _step_fwd_saved(d, vy, vx, re, cfg, masks, info):
+    """The one-workgroup forward step (sol_karman_step_fwd): ((d, vy, vx) after the step, saved vy, saved vx)"""
+    _lib.require_gpu()
+    lib = _lib.load()
+    d, vy, vx, re = (_lib.f32(t) for t in (d, vy, vx, re))
+    B, Y, X = cfg.B, cfg.Y, cfg.X
+    assert vy.shape == (B, Y + 1, X) and vx.shape == (B, Y, X + 1) and d.shape == (B, Y, X) and re.shape == (B,)
+    d_out = torch.empty_like(d)
+    vy_out = torch.empty_like(vy)
+    vx_out = torch.empty_like(vx)
+    svy = torch.empty_like(vy)
+    svx = torch.empty_like(vx)
+    iters = torch.empty(B, dtype=torch.int32, device=vy.device)
+    check(lib.sol_karman_step_fwd(C.byref(cfg), stream(), ptr(d), ptr(vy), ptr(vx), ptr(re),
+                                  ptr(masks.active), ptr(masks.inflow), ptr(masks.velBCy), ptr(masks.velBCyMask),
+                                  masks.bc_stride, ptr(d_out), ptr(vy_out), ptr(vx_out), ptr(svy), ptr(svx),
+                                  None, None, ptr(iters)))
+    if info is not None:
+        info["iterations"] = iters
+    return (d_out, vy_out, vx_out), svy, svx
+
+
+def _step_bwd(svy, svx, re, gvy, gvx, cfg, masks, info):
+    """The one-workgroup velocity adjoint (sol_karman_step_bwd); a missing cotangent counts as zero"""
+    lib = _lib.load()
+    gvy = torch.zeros_like(svy) if gvy is None else gvy.contiguous()
+    gvx = torch.zeros_like(svx) if gvx is None else gvx.contiguous()
+    oy = torch.empty_like(svy)
+    ox = torch.empty_like(svx)
+    iters = torch.empty(cfg.B, dtype=torch.int32, device=svy.device)
+    check(lib.sol_karman_step_bwd(C.byref(cfg), stream(), ptr(svy), ptr(svx), ptr(re), ptr(masks.active),
+                                  ptr(masks.velBCyMask), masks.bc_stride, ptr(gvy), ptr(gvx), None, None,
+                                  ptr(oy), ptr(ox), ptr(iters)))
+    if info is not None:
+        info["iterations_bwd"] = iters
+    return oy, ox
+
+
 class KarmanStepFn(torch.autograd.Function):
     """(d, vy, vx) [B,Y,X] / [B,Y+1,X] / [B,Y,X+1] -> one simulator_lo.step(...)."""
 
     @staticmethod
     def forward(ctx, d, vy, vx, re, cfg, masks, info):
         _lib.require_gpu()
-        lib = _lib.load()
-        d, vy, vx, re = (_lib.f32(t) for t in (d, vy, vx, re))
-        B, Y, X = cfg.B, cfg.Y, cfg.X
-        assert vy.shape == (B, Y + 1, X) and vx.shape == (B, Y, X + 1) and d.shape == (B, Y, X) and re.shape == (B,)
-        d_out = torch.empty_like(d)
-        vy_out = torch.empty_like(vy)
-        vx_out = torch.empty_like(vx)
-        svy = torch.empty_like(vy)
-        svx = torch.empty_like(vx)
-        iters = torch.empty(B, dtype=torch.int32, device=vy.device)
-        check(lib.sol_karman_step_fwd(C.byref(cfg), stream(), ptr(d), ptr(vy), ptr(vx), ptr(re),
-                                      ptr(masks.active), ptr(masks.inflow), ptr(masks.velBCy), ptr(masks.velBCyMask),
-                                      masks.bc_stride, ptr(d_out), ptr(vy_out), ptr(vx_out), ptr(svy), ptr(svx),
-                                      None, None, ptr(iters)))
+        re = _lib.f32(re)
+        outs, svy, svx = _step_fwd_saved(d, vy, vx, re, cfg, masks, info)
         ctx.save_for_backward(svy, svx, re)
         ctx.cfg, ctx.masks, ctx.info = cfg, masks, info
-        if info is not None:
-            info["iterations"] = iters
-        ctx.mark_non_differentiable(d_out)
-        return d_out, vy_out, vx_out
+        ctx.mark_non_differentiable(outs[0])
+        return outs
 
     @staticmethod
     def backward(ctx, _gd, gvy, gvx):
-        lib = _lib.load()
         svy, svx, re = ctx.saved_tensors
-        cfg, masks = ctx.cfg, ctx.masks
-        gvy = torch.zeros_like(svy) if gvy is None else gvy.contiguous()
-        gvx = torch.zeros_like(svx) if gvx is None else gvx.contiguous()
-        oy = torch.empty_like(svy)
-        ox = torch.empty_like(svx)
-        iters = torch.empty(cfg.B, dtype=torch.int32, device=svy.device)
-        check(lib.sol_karman_step_bwd(C.byref(cfg), stream(), ptr(svy), ptr(svx), ptr(re), ptr(masks.active),
-                                      ptr(masks.velBCyMask), masks.bc_stride, ptr(gvy), ptr(gvx), None, None,
-                                      ptr(oy), ptr(ox), ptr(iters)))
-        if ctx.info is not None:
-            ctx.info["iterations_bwd"] = iters
+        oy, ox = _step_bwd(svy, svx, re, gvy, gvx, ctx.cfg, ctx.masks, ctx.info)
         return None, oy, ox, None, None, None, None
 
 
-def karman_step(d, vy, vx, re, cfg, masks, info=None):
+def density_bwd_workspace_bytes(cfg):
+    """Device scratch of the density adjoint (sol_karman_density_bwd)."""
+    return _lib.load().sol_karman_density_bwd_workspace_bytes(C.byref(cfg))
+
+
+def karman_density_bwd(d, svy, svx, re, g_d, cfg, masks, g_vy=None, g_vx=None, workspace=None):
+    """Adjoint of the step's marker density (sol_karman_density_bwd), on any grid: (g_d_in, g_vy_in, g_vx_in) from the step's input
+    density `d`, the saved post-diffusion velocity and the gradient `g_d` with respect to the step's output density.  g_vy / g_vx (both
+    or neither): buffers that already hold the velocity adjoint's result; the density's part is added onto them in place (one fp32 add
+    per face) and they are returned.  Without them the density's part alone is written to fresh tensors."""
+    _lib.require_gpu()
+    lib = _lib.load()
+    if (g_vy is None) != (g_vx is None):
+        raise ValueError("karman_density_bwd: g_vy and g_vx go together")
+    B, Y, X = cfg.B, cfg.Y, cfg.X
+    d, svy, svx, re, g_d = (_lib.f32(t) for t in (d, svy, svx, re, g_d))
+    if d.shape != (B, Y, X) or g_d.shape != (B, Y, X) or svy.shape != (B, Y + 1, X) or svx.shape != (B, Y, X + 1) or re.shape != (B,):
+        raise ValueError("karman_density_bwd: d, g_d %s / %s, svy %s, svx %s, re %s are not [B,Y,X], [B,Y+1,X], [B,Y,X+1], [B] of the cfg (%d, %d, %d)"
+                         % (tuple(d.shape), tuple(g_d.shape), tuple(svy.shape), tuple(svx.shape), tuple(re.shape), B, Y, X))
+    accumulate = g_vy is not None
+    if accumulate and (g_vy.shape != svy.shape or g_vx.shape != svx.shape):
+        raise ValueError("karman_density_bwd: g_vy / g_vx must have the velocity's shapes")
+    oy, ox = (g_vy, g_vx) if accumulate else (torch.empty_like(svy), torch.empty_like(svx))
+    od = torch.empty_like(d)
+    workspace = _workspace(density_bwd_workspace_bytes(cfg), workspace, d.device)
+    check(lib.sol_karman_density_bwd(C.byref(cfg), stream(), ptr(d), ptr(masks.inflow), ptr(svy), ptr(svx), ptr(re), ptr(masks.velBCyMask),
+                                     masks.bc_stride, ptr(g_d), ptr(od), ptr(oy), ptr(ox), int(accumulate), ptr(workspace),
+                                     workspace.numel() * 4))
+    return od, oy, ox
+
+
+class KarmanStepDensFn(torch.autograd.Function):
+    """The step on any grid with a differentiable density output (opt-in, density_grad=True): the forward launches of KarmanStepFn /
+    KarmanStepLargeFn; backward returns (g_d_in, g_vy_in, g_vx_in).  The velocity adjoint (with its pressure solve) runs only when a
+    velocity cotangent arrived, the density adjoint (sol_karman_density_bwd, added onto the velocity adjoint's result) only when a
+    density cotangent did."""
+
+    @staticmethod
+    def forward(ctx, d, vy, vx, re, cfg, masks, workspace, info):
+        _lib.require_gpu()
+        d, re = _lib.f32(d), _lib.f32(re)
+        if masks.large:
+            outs, svy, svx = karman_step_large_saved(d, vy, vx, re, cfg, masks, workspace, info)
+        else:
+            outs, svy, svx = _step_fwd_saved(d, vy, vx, re, cfg, masks, info)
+        ctx.save_for_backward(d, svy, svx, re)
+        ctx.cfg, ctx.masks, ctx.info = cfg, masks, info
+        ctx.set_materialize_grads(False)
+        return outs
+
+    @staticmethod
+    def backward(ctx, gd, gvy, gvx):
+        d, svy, svx, re = ctx.saved_tensors
+        cfg, masks = ctx.cfg, ctx.masks
+        od = oy = ox = None
+        if gvy is not None or gvx is not None:
+            if masks.large:
+                gvy = torch.zeros_like(svy) if gvy is None else gvy.contiguous()
+                gvx = torch.zeros_like(svx) if gvx is None else gvx.contiguous()
+                oy, ox = karman_step_large_bwd(svy, svx, re, gvy, gvx, cfg, masks, info=ctx.info)
+            else:
+                oy, ox = _step_bwd(svy, svx, re, gvy, gvx, cfg, masks, ctx.info)
+        if gd is not None:
+            od, oy, ox = karman_density_bwd(d, svy, svx, re, gd, cfg, masks, oy, ox)
+        return od, oy, ox, None, None, None, None, None
+
+
+def karman_step(d, vy, vx, re, cfg, masks, info=None, density_grad=False):
+    """One step on a one-workgroup grid.  density_grad=True (opt-in): the density output is differentiable too (KarmanStepDensFn), taken
+    when any of d, vy, vx requires a gradient."""
+    if density_grad and torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (d, vy, vx)):
+        return KarmanStepDensFn.apply(d, vy, vx, re, cfg, masks, None, info)
     return KarmanStepFn.apply(d, vy, vx, re, cfg, masks, info)
 
 

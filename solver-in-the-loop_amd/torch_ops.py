@@ -4,7 +4,8 @@ through PyTorch-ROCm custom ops with a hand-written backward for each solver op"
 The ops call the same entry points of libsol_hip.so as ops.py (ctypes, raw device pointers; no torch types cross the C
 ABI) and carry the hand-written adjoints (sol_karman_step_bwd, sol_burgers_step_bwd / _bwd_large, sol_conv5x5 backward-data / -weight)
 through torch.library.register_autograd, so they compose with any other PyTorch op and show up in the dispatcher
-(torch.ops.sol.karman_step, .conv5x5, .burgers_step, .adam_tf_step).  Scene constants (masks, solver blobs, the cfg
+(torch.ops.sol.karman_step, .conv5x5, .burgers_step, .adam_tf_step; .karman_step_dens = karman_step with a differentiable density
+output, over sol_karman_density_bwd).  Scene constants (masks, solver blobs, the cfg
 struct) are not tensors: they are registered once with register_scene() and referred to by an integer handle."""
 import ctypes as C
 
@@ -16,6 +17,8 @@ from ._lib import check, ptr, stream
 _SCENES = {}
 _LIB = torch.library.Library("sol", "DEF")
 _LIB.define("karman_step(Tensor d, Tensor vy, Tensor vx, Tensor re, int scene) -> (Tensor, Tensor, Tensor)")
+_LIB.define("karman_step_dens(Tensor d, Tensor vy, Tensor vx, Tensor re, int scene) -> (Tensor, Tensor, Tensor)")
+_LIB.define("karman_density_bwd(Tensor d, Tensor svy, Tensor svx, Tensor re, Tensor gd, int scene) -> (Tensor, Tensor, Tensor)")
 _LIB.define("karman_step_bwd(Tensor svy, Tensor svx, Tensor re, Tensor gvy, Tensor gvx, int scene) -> (Tensor, Tensor)")
 _LIB.define("karman_step_fwd_saved(Tensor d, Tensor vy, Tensor vx, Tensor re, int scene) -> (Tensor, Tensor, Tensor, Tensor, Tensor)")
 _LIB.define("conv5x5(Tensor x, Tensor w, Tensor b, Tensor? residual, bool lrelu, float slope) -> Tensor")
@@ -98,6 +101,43 @@ class _KarmanFn(torch.autograd.Function):
 
 
 _LIB.impl("karman_step", lambda d, vy, vx, re, scene: _KarmanFn.apply(d, vy, vx, re, scene), "AutogradCUDA")
+
+
+# karman_step with a differentiable density output (opt-in; karman_step itself keeps the density out of the graph)
+def _karman_density_bwd(d, svy, svx, re, gd, scene):
+    cfg, masks = _SCENES[scene]
+    return ops.karman_density_bwd(d, svy.contiguous(), svx.contiguous(), re, gd.contiguous(), cfg, masks)
+
+
+_LIB.impl("karman_density_bwd", _karman_density_bwd, "CUDA")
+_LIB.impl("karman_step_dens", _karman_step, "CUDA")
+
+
+class _KarmanDensFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, d, vy, vx, re, scene):
+        d = _lib.f32(d)
+        d_out, vy_out, vx_out, svy, svx = torch.ops.sol.karman_step_fwd_saved(d, vy, vx, re, scene)
+        ctx.save_for_backward(d, svy, svx, re)
+        ctx.scene = scene
+        ctx.set_materialize_grads(False)
+        return d_out, vy_out, vx_out
+
+    @staticmethod
+    def backward(ctx, gd, gvy, gvx):
+        d, svy, svx, re = ctx.saved_tensors
+        od = oy = ox = None
+        if gvy is not None or gvx is not None:        # a density-only loss does not pay for the pressure solve
+            gvy = torch.zeros_like(svy) if gvy is None else gvy
+            gvx = torch.zeros_like(svx) if gvx is None else gvx
+            oy, ox = torch.ops.sol.karman_step_bwd(svy, svx, re, gvy, gvx, ctx.scene)
+        if gd is not None:
+            cfg, masks = _SCENES[ctx.scene]
+            od, oy, ox = ops.karman_density_bwd(d, svy, svx, re, gd.contiguous(), cfg, masks, oy, ox)      # added onto the velocity adjoint's result
+        return od, oy, ox, None, None
+
+
+_LIB.impl("karman_step_dens", lambda d, vy, vx, re, scene: _KarmanDensFn.apply(d, vy, vx, re, scene), "AutogradCUDA")
 
 # conv / burgers: the autograd.Functions of ops.py already are the hand-written forward + backward pairs
 _LIB.impl("conv5x5", lambda x, w, b, residual, lrelu, slope: ops.Conv5x5Fn.apply(x, w, b, residual, lrelu, slope), "AutogradCUDA")
