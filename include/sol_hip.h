@@ -260,13 +260,42 @@ int sol_karman_step_bwd_large(const sol_karman_cfg* cfg, void* stream,
  * of that simulation NaN.  g_d_in [B,Y,X] is written.  accumulate = 0: g_vy_in / g_vx_in are written; accumulate = 1: the density's part
  * is ADDED onto them (the velocity adjoint wrote there first; one fp32 add per face, deterministic).  Outputs must not alias inputs or
  * each other.  No synchronisation, no allocation, nothing read on the host: capturable.  `workspace`: DEVICE scratch of
- * sol_karman_density_bwd_workspace_bytes(cfg) bytes.  The gradient with respect to `re` is not computed. */
+ * sol_karman_density_bwd_workspace_bytes(cfg) bytes.  The gradient with respect to `re`: the _re forms below. */
 size_t sol_karman_density_bwd_workspace_bytes(const sol_karman_cfg* cfg);
 int sol_karman_density_bwd(const sol_karman_cfg* cfg, void* stream,
                            const float* d_in, const float* inflow, const float* saved_vy, const float* saved_vx,
                            const float* re, const float* velBCyMask, int64_t bc_batch_stride,
                            const float* g_d_out, float* g_d_in, float* g_vy_in, float* g_vx_in, int accumulate,
                            void* workspace, size_t workspace_bytes);
+
+/* Gradient with respect to the REYNOLDS NUMBER (csrc/karman_re_bwd.hip).  The step diffuses u = v_in + alpha L v_in with alpha = dt res^2 /
+ * re[b], L the replicate-padded 5-point Laplacian; with g' the cotangent of u -- what the adjoints above apply (I + alpha L^T) to: the
+ * velocity adjoint's g_c ((1 - velBCyMask) g_c on v_y), the density adjoint's cell-to-face transpose of gU --
+ *     g_re[b] = -(dt res^2 / re[b]^2) * sum over the faces of v_y and v_x of  g'_e (L v_in)_e
+ * The _re forms take every argument of the plain call and, after `workspace_bytes`, the step's INPUT velocity vy_in [B,Y+1,X], vx_in
+ * [B,Y,X+1] (not the saved post-diffusion one), g_re [B] and accumulate_re (0: g_re is written; 1: added onto with one fp32 add -- the
+ * density's part after the velocity's).  They issue the plain call's launches (g_vy_in, g_vx_in, g_d_in are the plain call's bits) and two
+ * more: fp32 terms, fp64 products and sums in a fixed order whose workgroup count depends on Y, X alone, no floating-point atomics -- g_re
+ * is bit-reproducible and independent of the device.  A non-finite cotangent of simulation b makes g_re[b] NaN like its other gradients.
+ * sol_karman_step_bwd_large_re serves EVERY grid with Y, X >= 16, the one-workgroup grids included (their saved velocity is the same
+ * field; scene blobs as for a large grid: the direct blob, or the box blob for the CG solve); sol_karman_density_bwd_re any Y, X >= 2.
+ * The workspace is the plain call's plus the partial sums.  vy_in / vx_in / g_re must not alias an output / an input.  Capturable. */
+size_t sol_karman_step_bwd_large_re_workspace_bytes_for(const sol_karman_cfg* cfg, const int32_t* direct_header_host);
+int sol_karman_step_bwd_large_re(const sol_karman_cfg* cfg, void* stream,
+                                 const float* saved_vy, const float* saved_vx, const float* re, const float* active,
+                                 const float* velBCyMask, int64_t bc_batch_stride,
+                                 const float* g_vy_out, const float* g_vx_out, float* g_vy_in, float* g_vx_in,
+                                 const int32_t* direct_header_host,
+                                 const float* box_blob, const int32_t* box_header_host, int32_t* cg_info,
+                                 void* workspace, size_t workspace_bytes,
+                                 const float* vy_in, const float* vx_in, float* g_re, int accumulate_re);
+size_t sol_karman_density_bwd_re_workspace_bytes(const sol_karman_cfg* cfg);
+int sol_karman_density_bwd_re(const sol_karman_cfg* cfg, void* stream,
+                              const float* d_in, const float* inflow, const float* saved_vy, const float* saved_vx,
+                              const float* re, const float* velBCyMask, int64_t bc_batch_stride,
+                              const float* g_d_out, float* g_d_in, float* g_vy_in, float* g_vx_in, int accumulate,
+                              void* workspace, size_t workspace_bytes,
+                              const float* vy_in, const float* vx_in, float* g_re, int accumulate_re);
 
 /* active  [Y,X]  1 - obstacle mask (cell centres inside Obstacle geometries -> 0)
  * inflow  [Y,X]  inflow rate mask (Inflow(box[5:10,25:75]) -> 1 inside)

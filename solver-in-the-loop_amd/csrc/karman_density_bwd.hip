@@ -11,7 +11,10 @@
 //   k_kd_diffuse_adj   g_c = the cell-to-face transpose of gU (a centre velocity is the mean of its two faces), gathered on the fly, then
 //                      the diffusion / boundary-condition adjoint of k_lb_diffuse_adj: g_vy_in = (I + alpha L^T)((1 - bcm) g_cy),
 //                      g_vx_in = (I + alpha L^T) g_cx, written or added onto the velocity adjoint's result; converts g_d_in back to fp32
+// sol_karman_density_bwd_re: the same launches (density_bwd), then the reduction of that g' against L v_in to the density path's part of
+// the gradient with respect to the Reynolds number (karman_re_bwd.hip).
 #include "fixed_scatter.hpp"
+#include "karman_re.hpp"
 
 namespace {
 
@@ -156,15 +159,10 @@ __global__ void __launch_bounds__(256) k_kd_diffuse_adj(KDArgs a) {
     const float* uy = a.gUy + (size_t)b * N;
     const float* ux = a.gUx + (size_t)b * N;
     const float* m = a.bcm + (size_t)b * a.bc_stride;
-    // g' = g_c . (1 - bcm) at face (jf, i) of v_y, g_c at face (j, iF) of v_x: out-of-range cells count as zero
-    auto gy = [&](int jf, int i) {
-        const float lo = jf > 0 ? uy[(jf - 1) * X + i] : 0.f, hi = jf < Y ? uy[jf * X + i] : 0.f;
-        return 0.5f * (lo + hi) * (1.f - m[jf * X + i]);
-    };
-    auto gx = [&](int j, int iF) {
-        const float lo = iF > 0 ? ux[j * X + iF - 1] : 0.f, hi = iF < X ? ux[j * X + iF] : 0.f;
-        return 0.5f * (lo + hi);
-    };
+    // g' = g_c . (1 - bcm) at face (jf, i) of v_y, g_c at face (j, iF) of v_x: out-of-range cells count as zero (karman_re.hpp: shared with
+    // the Reynolds-number reduction)
+    auto gy = [&](int jf, int i) { return kd_face_y(uy, m, Y, X, jf, i); };
+    auto gx = [&](int j, int iF) { return kd_face_x(ux, X, j, iF); };
     // g' + alpha L^T g' as k_lb_diffuse_adj forms it: the transposed replicate-padded Laplacian in gather form (a direction that leaves the
     // array contributes g' of the face itself; neighbours in the order y +, y -, x +, x -), ONE fused multiply-add, spelled out
     for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < nVy + nVx + N; e += gridDim.x * blockDim.x) {
@@ -225,25 +223,31 @@ extern "C" size_t sol_karman_density_bwd_workspace_bytes(const sol_karman_cfg* c
     return kd_layout(c, nullptr).bytes;
 }
 
-extern "C" int sol_karman_density_bwd(const sol_karman_cfg* c, void* stream,
-                                      const float* d_in, const float* inflow, const float* saved_vy, const float* saved_vx,
-                                      const float* re, const float* velBCyMask, int64_t bc_batch_stride,
-                                      const float* g_d_out, float* g_d_in, float* g_vy_in, float* g_vx_in, int accumulate,
-                                      void* workspace, size_t workspace_bytes) {
-    const char* who = "sol_karman_density_bwd";
+namespace {
+
+// the launches of sol_karman_density_bwd; with rx, followed by the Reynolds-number reduction over the gU they leave in the workspace
+// (sol_karman_density_bwd_re): g_d_in / g_vy_in / g_vx_in are the same launches' results either way
+int density_bwd(const char* who, const sol_karman_cfg* c, void* stream,
+                const float* d_in, const float* inflow, const float* saved_vy, const float* saved_vx,
+                const float* re, const float* velBCyMask, int64_t bc_batch_stride,
+                const float* g_d_out, float* g_d_in, float* g_vy_in, float* g_vx_in, int accumulate,
+                void* workspace, size_t workspace_bytes, const ReExtra* rx) {
     SOL_REQUIRE(c != nullptr, "%s: cfg is NULL", who);
     SOL_REQUIRE(c->B >= 1 && c->B <= 65535 && c->Y >= 2 && c->X >= 2, "%s: B in [1, 65535], Y, X >= 2 (got %d, %d, %d)", who, c->B, c->Y, c->X);
     SOL_REQUIRE((size_t)c->Y * c->X < ((size_t)1 << 28), "%s: grid too large for 32-bit face indices", who);
     SOL_REQUIRE(d_in && saved_vy && saved_vx && re && velBCyMask && g_d_out && g_d_in && g_vy_in && g_vx_in && workspace,
                 "%s: NULL pointer argument", who);
     SOL_REQUIRE(inflow || !c->inflow_before, "%s: cfg.inflow_before needs the inflow mask (the advected field is d_in + inflow)", who);
-    const size_t need = kd_layout(c, nullptr).bytes;
+    SOL_REQUIRE(!rx || (rx->vy_in && rx->vx_in && rx->g_re), "%s: NULL pointer argument", who);
+    const size_t plain = kd_layout(c, nullptr).bytes;
+    const size_t need = plain + (rx ? sol_re_partial_bytes(c) : 0);
     SOL_REQUIRE(workspace_bytes >= need, "%s: workspace too small (%zu < %zu bytes)", who, workspace_bytes, need);
-    const void* outs[] = {g_d_in, g_vy_in, g_vx_in};
-    const void* ins[] = {d_in, inflow, saved_vy, saved_vx, re, velBCyMask, g_d_out};
+    const void* outs[] = {g_d_in, g_vy_in, g_vx_in, rx ? rx->g_re : nullptr};
+    const void* ins[] = {d_in, inflow, saved_vy, saved_vx, re, velBCyMask, g_d_out, rx ? rx->vy_in : nullptr, rx ? rx->vx_in : nullptr};
     for (const void* o : outs)
-        for (const void* i : ins) SOL_REQUIRE(o != i, "%s: outputs must not alias the inputs", who);
+        for (const void* i : ins) SOL_REQUIRE(!o || o != i, "%s: outputs must not alias the inputs", who);
     SOL_REQUIRE(g_d_in != g_vy_in && g_d_in != g_vx_in && g_vy_in != g_vx_in, "%s: g_d_in, g_vy_in and g_vx_in must be buffers of their own", who);
+    SOL_REQUIRE(!rx || (rx->g_re != g_d_in && rx->g_re != g_vy_in && rx->g_re != g_vx_in), "%s: g_re must be a buffer of its own", who);
     const int B = c->B, Y = c->Y, X = c->X, N = Y * X;
     const size_t items = (size_t)(Y + 1) * X + (size_t)Y * (X + 1) + N;
     hipStream_t s = (hipStream_t)stream;
@@ -264,5 +268,41 @@ extern "C" int sol_karman_density_bwd(const sol_karman_cfg* c, void* stream,
     }
     SOL_LAUNCH(k_kd_diffuse_adj, dim3((unsigned)((items + 255) / 256), B), dim3(256), 0, s, a);
     SOL_LAUNCH_CHECK();
-    return SOL_OK;
+    if (!rx) return SOL_OK;
+    // g' of the Reynolds-number gradient = the face values k_kd_diffuse_adj has just formed from gU (kd_face_y / kd_face_x); the partial
+    // sums lie behind the plain adjoint's part of the workspace
+    ReIn in{};
+    in.src = RE_GU;
+    in.gUy = l.gUy; in.gUx = l.gUx; in.gmax = l.gmax; in.bcm = velBCyMask; in.bc_stride = bc_batch_stride;
+    in.vy_in = rx->vy_in; in.vx_in = rx->vx_in; in.re = re;
+    in.partial = reinterpret_cast<double*>(reinterpret_cast<char*>(l.gD) + (plain - 256));
+    in.g_re = rx->g_re; in.accumulate = rx->accumulate;
+    return sol_re_reduce(s, c, in);
+}
+
+}  // namespace
+
+extern "C" int sol_karman_density_bwd(const sol_karman_cfg* c, void* stream,
+                                      const float* d_in, const float* inflow, const float* saved_vy, const float* saved_vx,
+                                      const float* re, const float* velBCyMask, int64_t bc_batch_stride,
+                                      const float* g_d_out, float* g_d_in, float* g_vy_in, float* g_vx_in, int accumulate,
+                                      void* workspace, size_t workspace_bytes) {
+    return density_bwd("sol_karman_density_bwd", c, stream, d_in, inflow, saved_vy, saved_vx, re, velBCyMask, bc_batch_stride, g_d_out,
+                       g_d_in, g_vy_in, g_vx_in, accumulate, workspace, workspace_bytes, nullptr);
+}
+
+extern "C" size_t sol_karman_density_bwd_re_workspace_bytes(const sol_karman_cfg* c) {
+    const size_t plain = sol_karman_density_bwd_workspace_bytes(c);
+    return plain ? plain + sol_re_partial_bytes(c) : 0;
+}
+
+extern "C" int sol_karman_density_bwd_re(const sol_karman_cfg* c, void* stream,
+                                         const float* d_in, const float* inflow, const float* saved_vy, const float* saved_vx,
+                                         const float* re, const float* velBCyMask, int64_t bc_batch_stride,
+                                         const float* g_d_out, float* g_d_in, float* g_vy_in, float* g_vx_in, int accumulate,
+                                         void* workspace, size_t workspace_bytes,
+                                         const float* vy_in, const float* vx_in, float* g_re, int accumulate_re) {
+    const ReExtra rx{vy_in, vx_in, g_re, accumulate_re};
+    return density_bwd("sol_karman_density_bwd_re", c, stream, d_in, inflow, saved_vy, saved_vx, re, velBCyMask, bc_batch_stride, g_d_out,
+                       g_d_in, g_vy_in, g_vx_in, accumulate, workspace, workspace_bytes, &rx);
 }

@@ -15,7 +15,10 @@
 //                     global memory) and flushes one vector atomic per non-zero window cell.
 //   k_lb_diffuse_adj  g_in = (I + alpha L^T)(g_c . (1 - bcm)) for v_y, (I + alpha L^T) g_c for v_x: gather form of the transposed
 //                     replicate-padded Laplacian; converts the fixed-point g_c back to fp32 as it reads it
+// sol_karman_step_bwd_large_re: the same launches (bwd_large), then the reduction of g' = g_c . (1 - bcm) against L v_in to the gradient
+// with respect to the Reynolds number (karman_re_bwd.hip); it serves the one-workgroup grids too (any Y, X >= 16).
 #include "fixed_scatter.hpp"
+#include "karman_re.hpp"
 #include "large2d.hpp"
 
 namespace {
@@ -303,27 +306,33 @@ extern "C" int sol_karman_step_fwd_large_saved(const sol_karman_cfg* c, void* st
     return sol_large_step(c, (hipStream_t)stream, io, saved_vy, saved_vx, direct, direct_header_host, box_blob, cg_info, solver);
 }
 
-extern "C" int sol_karman_step_bwd_large(const sol_karman_cfg* c, void* stream,
-                                         const float* saved_vy, const float* saved_vx, const float* re, const float* active,
-                                         const float* velBCyMask, int64_t bc_batch_stride,
-                                         const float* g_vy_out, const float* g_vx_out, float* g_vy_in, float* g_vx_in,
-                                         const int32_t* direct_header_host,
-                                         const float* box_blob, const int32_t* box_header_host, int32_t* cg_info,
-                                         void* workspace, size_t workspace_bytes) {
-    const char* who = "sol_karman_step_bwd_large";
+namespace {
+
+// the launches of sol_karman_step_bwd_large; with rx, followed by the Reynolds-number reduction over the g_c they leave in the workspace
+// (sol_karman_step_bwd_large_re): g_vy_in / g_vx_in are the same launches' results either way
+int bwd_large(const char* who, const sol_karman_cfg* c, void* stream,
+              const float* saved_vy, const float* saved_vx, const float* re, const float* active,
+              const float* velBCyMask, int64_t bc_batch_stride,
+              const float* g_vy_out, const float* g_vx_out, float* g_vy_in, float* g_vx_in,
+              const int32_t* direct_header_host,
+              const float* box_blob, const int32_t* box_header_host, int32_t* cg_info,
+              void* workspace, size_t workspace_bytes, const ReExtra* rx) {
     if (int e = common_check(c, who)) return e;
+    SOL_REQUIRE(!rx || (rx->vy_in && rx->vx_in && rx->g_re), "%s: NULL pointer argument", who);
     const bool direct = c->direct != nullptr;
     SOL_REQUIRE(saved_vy && saved_vx && re && active && velBCyMask && g_vy_out && g_vx_out && g_vy_in && g_vx_in && workspace,
                 "%s: NULL pointer argument", who);
     if (direct) { if (int e = sol_large_direct_check(c, who, direct_header_host)) return e; }
     else if (int e = sol_large_cg_check(c, who, box_blob, box_header_host, cg_info, workspace)) return e;
-    const size_t need = bwd_layout(c, direct, nullptr, direct ? direct_header_host : nullptr).bytes;
+    const size_t plain = bwd_layout(c, direct, nullptr, direct ? direct_header_host : nullptr).bytes;
+    const size_t need = plain + (rx ? sol_re_partial_bytes(c) : 0);
     SOL_REQUIRE(workspace_bytes >= need, "%s: workspace too small (%zu < %zu bytes)", who, workspace_bytes, need);
-    const void* outs[] = {g_vy_in, g_vx_in, cg_info};
-    const void* ins[] = {saved_vy, saved_vx, re, active, velBCyMask, g_vy_out, g_vx_out, box_blob};
+    const void* outs[] = {g_vy_in, g_vx_in, cg_info, rx ? rx->g_re : nullptr};
+    const void* ins[] = {saved_vy, saved_vx, re, active, velBCyMask, g_vy_out, g_vx_out, box_blob, rx ? rx->vy_in : nullptr, rx ? rx->vx_in : nullptr};
     for (const void* o : outs)
         for (const void* i : ins) SOL_REQUIRE(!o || o != i, "%s: outputs must not alias the inputs", who);
     SOL_REQUIRE(g_vy_in != g_vx_in, "%s: g_vy_in and g_vx_in must be buffers of their own", who);
+    SOL_REQUIRE(!rx || (rx->g_re != g_vy_in && rx->g_re != g_vx_in && (void*)rx->g_re != (void*)cg_info), "%s: g_re must be a buffer of its own", who);
     const int B = c->B, Y = c->Y, X = c->X, N = Y * X;
     const size_t nVy = (size_t)(Y + 1) * X, nVx = (size_t)Y * (X + 1), faces = nVy + nVx;
     hipStream_t s = (hipStream_t)stream;
@@ -352,5 +361,45 @@ extern "C" int sol_karman_step_bwd_large(const sol_karman_cfg* c, void* stream,
     }
     SOL_LAUNCH(k_lb_diffuse_adj, dim3(gF, B), dim3(256), 0, s, a);
     SOL_LAUNCH_CHECK();
-    return SOL_OK;
+    if (!rx) return SOL_OK;
+    // g' of the Reynolds-number gradient = the fixed-point g_c that k_lb_diffuse_adj has just read (. (1 - bcm) on v_y); the partial sums
+    // lie behind the plain adjoint's part of the workspace
+    ReIn in{};
+    in.src = RE_FIXED;
+    in.gcy = a.gcy; in.gcx = a.gcx; in.gmax = a.gmax; in.bcm = velBCyMask; in.bc_stride = bc_batch_stride;
+    in.vy_in = rx->vy_in; in.vx_in = rx->vx_in; in.re = re;
+    in.partial = reinterpret_cast<double*>(reinterpret_cast<char*>(l.gc) + (plain - 256));
+    in.g_re = rx->g_re; in.accumulate = rx->accumulate;
+    return sol_re_reduce(s, c, in);
+}
+
+}  // namespace
+
+extern "C" int sol_karman_step_bwd_large(const sol_karman_cfg* c, void* stream,
+                                         const float* saved_vy, const float* saved_vx, const float* re, const float* active,
+                                         const float* velBCyMask, int64_t bc_batch_stride,
+                                         const float* g_vy_out, const float* g_vx_out, float* g_vy_in, float* g_vx_in,
+                                         const int32_t* direct_header_host,
+                                         const float* box_blob, const int32_t* box_header_host, int32_t* cg_info,
+                                         void* workspace, size_t workspace_bytes) {
+    return bwd_large("sol_karman_step_bwd_large", c, stream, saved_vy, saved_vx, re, active, velBCyMask, bc_batch_stride, g_vy_out, g_vx_out,
+                     g_vy_in, g_vx_in, direct_header_host, box_blob, box_header_host, cg_info, workspace, workspace_bytes, nullptr);
+}
+
+extern "C" size_t sol_karman_step_bwd_large_re_workspace_bytes_for(const sol_karman_cfg* c, const int32_t* direct_header_host) {
+    const size_t plain = sol_karman_step_bwd_large_workspace_bytes_for(c, direct_header_host);
+    return plain ? plain + sol_re_partial_bytes(c) : 0;
+}
+
+extern "C" int sol_karman_step_bwd_large_re(const sol_karman_cfg* c, void* stream,
+                                            const float* saved_vy, const float* saved_vx, const float* re, const float* active,
+                                            const float* velBCyMask, int64_t bc_batch_stride,
+                                            const float* g_vy_out, const float* g_vx_out, float* g_vy_in, float* g_vx_in,
+                                            const int32_t* direct_header_host,
+                                            const float* box_blob, const int32_t* box_header_host, int32_t* cg_info,
+                                            void* workspace, size_t workspace_bytes,
+                                            const float* vy_in, const float* vx_in, float* g_re, int accumulate_re) {
+    const ReExtra rx{vy_in, vx_in, g_re, accumulate_re};
+    return bwd_large("sol_karman_step_bwd_large_re", c, stream, saved_vy, saved_vx, re, active, velBCyMask, bc_batch_stride, g_vy_out, g_vx_out,
+                     g_vy_in, g_vx_in, direct_header_host, box_blob, box_header_host, cg_info, workspace, workspace_bytes, &rx);
 }

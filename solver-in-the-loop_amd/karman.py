@@ -112,7 +112,10 @@ class KarmanFlow:
 
     def __init__(self, pressure_solver=None, make_input_divfree=False, make_output_divfree=True,
                  cg_rtol=1e-6, cg_atol=1e-9, cg_max_iter=2000, grad_pad="replicate", inflow_order="after",
-                 obstacles=None, active=None, density_grad=False):
+                 obstacles=None, active=None, density_grad=False, re_grad=False):
+        # re_grad=True (opt-in): a tensor `re` given to step() that requires a gradient receives one (ops.KarmanStepReFn: fit the
+        # viscosity to observed frames, a loss term on Re); the default treats re as data
+        self._re_grad = bool(re_grad)
         # density_grad=True (opt-in): step() keeps the density in the autograd graph (ops.KarmanStepDensFn: a loss on dens frames
         # differentiates with respect to the initial density and velocity); the default treats it as a passive tracer, as the reference's loss does
         self._density_grad = bool(density_grad)
@@ -226,9 +229,10 @@ class KarmanFlow:
             n = ops.large_workspace_bytes(cfg, masks)
             if getattr(self, "_large_ws", None) is None or self._large_ws[0] != (B, Y, X, str(dev)) or self._large_ws[1].numel() * 4 < n:
                 self._large_ws = ((B, Y, X, str(dev)), torch.empty((n + 3) // 4, dtype=torch.float32, device=dev))
-            d2, vy2, vx2 = ops.karman_step_large(d, vy, vx, re_t, cfg, masks, self._large_ws[1], info, density_grad=self._density_grad)
+            d2, vy2, vx2 = ops.karman_step_large(d, vy, vx, re_t, cfg, masks, self._large_ws[1], info, density_grad=self._density_grad,
+                                                 re_grad=self._re_grad)
         else:
-            d2, vy2, vx2 = ops.karman_step(d, vy, vx, re_t, cfg, masks, info, density_grad=self._density_grad)
+            d2, vy2, vx2 = ops.karman_step(d, vy, vx, re_t, cfg, masks, info, density_grad=self._density_grad, re_grad=self._re_grad)
         self.solve_info = info
         return smoke.copied_with(density=d2.reshape(B, Y, X, 1),
                                  velocity=StaggeredGrid([vy2.reshape(B, Y + 1, X, 1), vx2.reshape(B, Y, X + 1, 1)],

@@ -106,6 +106,20 @@ class SceneMasks:
             self.box_header = np.ascontiguousarray(blob[:16].view(np.int32))
         self.pressure_solver = want if want == "direct_scattered" else ("direct" if self.direct is not None else "cg")
 
+    def staged_box(self):
+        """(box blob, its host header) for the CG solve of the staged adjoint (sol_karman_step_bwd_large*), None for a scene with a
+        direct blob.  A large CG scene built it in __init__; a one-workgroup CG scene needs it only under re_grad (the staged adjoint
+        runs there instead of the fused one) and prepares it on first use."""
+        if self.direct is not None:
+            return None, None
+        if self.box is None:
+            from .precond import box_solver_blob
+            Y, X = self.active.shape[-2:]
+            blob = box_solver_blob(Y, X)
+            self.box = torch.from_numpy(blob).to(self.active.device)
+            self.box_header = np.ascontiguousarray(blob[:16].view(np.int32))
+        return self.box, self.box_header
+
 
 def large_workspace_bytes(cfg, masks):
     """Device scratch of the large-grid step for the scene's solver (direct, scattered direct or CG)."""
@@ -202,7 +216,7 @@ def karman_step_large_bwd(svy, svx, re, gvy, gvx, cfg, masks, workspace=None, in
 
 
 def karman_step_large(d, vy, vx, re, cfg, masks, workspace=None, info=None, feat=None, feat_scale=None, p_guess=None, out=None,
-                      density_grad=False):
+                      density_grad=False, re_grad=False):
     """The step for grids beyond the one-workgroup kernels (data generation at 256 x 128,
     /root/reference/karman-2d/karman.py:98-159): sol_karman_step_fwd_large (direct solve) or sol_karman_step_fwd_large_cg (CG solve,
     masks.pressure_solver == "cg").  Returns (d, vy, vx) after the step; with the CG solve, `info` (a dict) receives "iterations" and
@@ -214,7 +228,9 @@ def karman_step_large(d, vy, vx, re, cfg, masks, workspace=None, info=None, feat
     (sol_karman_step_fwd_large_cg_warm: read as the initial guess, overwritten with the step's pressure) and is an error on a scene with
     the direct solver; `out` = (d, vy, vx) buffers to write instead of fresh tensors (they must not be the inputs).
     density_grad=True (opt-in): the density output is differentiable too (KarmanStepDensFn: same forward launches; the differentiable
-    form is taken when any of d, vy, vx requires a gradient)."""
+    form is taken when any of d, vy, vx requires a gradient).
+    re_grad=True (opt-in): a tensor `re` that requires a gradient receives one (KarmanStepReFn: same forward launches, the step's input
+    velocity saved as well; composes with density_grad).  Without the flag `re` is data."""
     if p_guess is not None and masks.direct is not None:
         raise ValueError("karman_step_large: p_guess warm-starts the CG pressure solve; this scene runs the direct solver (no iteration to start)")
     _lib.require_gpu()
@@ -223,9 +239,12 @@ def karman_step_large(d, vy, vx, re, cfg, masks, workspace=None, info=None, feat
     B, Y, X = cfg.B, cfg.Y, cfg.X
     assert vy.shape == (B, Y + 1, X) and vx.shape == (B, Y, X + 1) and d.shape == (B, Y, X) and re.shape == (B,)
     extras = feat is not None or p_guess is not None or out is not None
-    if torch.is_grad_enabled() and (vy.requires_grad or vx.requires_grad or (density_grad and d.requires_grad)):
+    want_re = re_grad and re.requires_grad
+    if torch.is_grad_enabled() and (vy.requires_grad or vx.requires_grad or (density_grad and d.requires_grad) or want_re):
         if extras:
             raise ValueError("karman_step_large: feat / p_guess / out belong to the no-grad step (the differentiable step keeps its own state)")
+        if want_re:
+            return KarmanStepReFn.apply(d, vy, vx, re, cfg, masks, workspace, info, bool(density_grad))
         if density_grad:
             return KarmanStepDensFn.apply(d, vy, vx, re, cfg, masks, workspace, info)
         return KarmanStepLargeFn.apply(d, vy, vx, re, cfg, masks, workspace, info)
@@ -428,9 +447,125 @@ class KarmanStepDensFn(torch.autograd.Function):
         return od, oy, ox, None, None, None, None, None
 
 
-def karman_step(d, vy, vx, re, cfg, masks, info=None, density_grad=False):
+def large_bwd_re_workspace_bytes(cfg, masks):
+    """Device scratch of the staged adjoint with the Reynolds-number gradient (sol_karman_step_bwd_large_re) for the scene's solver."""
+    return _lib.load().sol_karman_step_bwd_large_re_workspace_bytes_for(C.byref(cfg), _hdr(masks.direct_header))
+
+
+def density_bwd_re_workspace_bytes(cfg):
+    """Device scratch of the density adjoint with the Reynolds-number gradient (sol_karman_density_bwd_re)."""
+    return _lib.load().sol_karman_density_bwd_re_workspace_bytes(C.byref(cfg))
+
+
+def _require_staged(cfg, who):
+    if cfg.Y < 16 or cfg.X < 16:
+        raise SolError("%s: the gradient with respect to re runs the staged adjoint (sol_karman_step_bwd_large_re), which takes grids "
+                       "with Y, X >= 16; this one is %dx%d" % (who, cfg.Y, cfg.X))
+
+
+def _g_re(g_re, B, device):
+    """(buffer, accumulate): a fresh [B] buffer to write, or the caller's to add onto"""
+    if g_re is None:
+        return torch.empty(B, dtype=torch.float32, device=device), 0
+    if g_re.shape != (B,):
+        raise ValueError("g_re must be [B] = (%d,), got %s" % (B, tuple(g_re.shape)))
+    return g_re, 1
+
+
+def karman_step_large_bwd_re(svy, svx, re, gvy, gvx, vy_in, vx_in, cfg, masks, g_re=None, workspace=None, info=None):
+    """The staged velocity adjoint with the gradient with respect to re (sol_karman_step_bwd_large_re), on every grid with Y, X >= 16 --
+    the one-workgroup grids included: (g_vy_in, g_vx_in, g_re) from the saved post-diffusion velocity, the cotangent of the step's output
+    velocity and the step's INPUT velocity.  g_vy_in / g_vx_in are karman_step_large_bwd's bits.  g_re [B]: a buffer to add onto (one
+    fp32 add), else a fresh one is written."""
+    _require_staged(cfg, "karman_step_large_bwd_re")
+    _lib.require_gpu()
+    lib = _lib.load()
+    svy, svx, re, gvy, gvx, vy_in, vx_in = (_lib.f32(t) for t in (svy, svx, re, gvy, gvx, vy_in, vx_in))
+    if vy_in.shape != svy.shape or vx_in.shape != svx.shape:
+        raise ValueError("karman_step_large_bwd_re: vy_in / vx_in must have the velocity's shapes")
+    box, box_header = masks.staged_box()
+    workspace = _workspace(large_bwd_re_workspace_bytes(cfg, masks), workspace, svy.device)
+    oy, ox = torch.empty_like(svy), torch.empty_like(svx)
+    out, acc = _g_re(g_re, cfg.B, svy.device)
+    cg_info = _cg_info(masks, cfg.B, svy.device)
+    check(lib.sol_karman_step_bwd_large_re(
+        C.byref(cfg), stream(), ptr(svy), ptr(svx), ptr(re), ptr(masks.active), ptr(masks.velBCyMask), masks.bc_stride,
+        ptr(gvy), ptr(gvx), ptr(oy), ptr(ox), _hdr(masks.direct_header), ptr(box), _hdr(box_header), ptr(cg_info),
+        ptr(workspace), workspace.numel() * 4, ptr(vy_in), ptr(vx_in), ptr(out), acc))
+    _publish_cg(info, cg_info, "_bwd")
+    return oy, ox, out
+
+
+def karman_density_bwd_re(d, svy, svx, re, g_d, vy_in, vx_in, cfg, masks, g_vy=None, g_vx=None, g_re=None, workspace=None):
+    """karman_density_bwd with the gradient with respect to re (sol_karman_density_bwd_re): (g_d_in, g_vy_in, g_vx_in, g_re).  The first
+    three are karman_density_bwd's bits; g_re [B]: a buffer to add onto (the velocity adjoint's part), else a fresh one is written."""
+    _lib.require_gpu()
+    lib = _lib.load()
+    if (g_vy is None) != (g_vx is None):
+        raise ValueError("karman_density_bwd_re: g_vy and g_vx go together")
+    B, Y, X = cfg.B, cfg.Y, cfg.X
+    d, svy, svx, re, g_d, vy_in, vx_in = (_lib.f32(t) for t in (d, svy, svx, re, g_d, vy_in, vx_in))
+    if (d.shape != (B, Y, X) or g_d.shape != (B, Y, X) or svy.shape != (B, Y + 1, X) or svx.shape != (B, Y, X + 1) or re.shape != (B,)
+            or vy_in.shape != svy.shape or vx_in.shape != svx.shape):
+        raise ValueError("karman_density_bwd_re: d, g_d %s / %s, svy, vy_in %s / %s, svx, vx_in %s / %s, re %s are not [B,Y,X], [B,Y+1,X], "
+                         "[B,Y,X+1], [B] of the cfg (%d, %d, %d)" % (tuple(d.shape), tuple(g_d.shape), tuple(svy.shape), tuple(vy_in.shape),
+                                                                     tuple(svx.shape), tuple(vx_in.shape), tuple(re.shape), B, Y, X))
+    accumulate = g_vy is not None
+    if accumulate and (g_vy.shape != svy.shape or g_vx.shape != svx.shape):
+        raise ValueError("karman_density_bwd_re: g_vy / g_vx must have the velocity's shapes")
+    oy, ox = (g_vy, g_vx) if accumulate else (torch.empty_like(svy), torch.empty_like(svx))
+    od = torch.empty_like(d)
+    out, acc = _g_re(g_re, B, d.device)
+    workspace = _workspace(density_bwd_re_workspace_bytes(cfg), workspace, d.device)
+    check(lib.sol_karman_density_bwd_re(C.byref(cfg), stream(), ptr(d), ptr(masks.inflow), ptr(svy), ptr(svx), ptr(re), ptr(masks.velBCyMask),
+                                        masks.bc_stride, ptr(g_d), ptr(od), ptr(oy), ptr(ox), int(accumulate), ptr(workspace),
+                                        workspace.numel() * 4, ptr(vy_in), ptr(vx_in), ptr(out), acc))
+    return od, oy, ox, out
+
+
+class KarmanStepReFn(torch.autograd.Function):
+    """The step on any grid with Y, X >= 16, differentiable with respect to re as well (opt-in, re_grad=True): the forward launches of
+    KarmanStepFn / KarmanStepLargeFn, with the step's input velocity saved beside the post-diffusion one; backward returns
+    (g_d_in | None, g_vy_in, g_vx_in, g_re).  The velocity half is the STAGED adjoint on every grid (sol_karman_step_bwd_large_re: the
+    fused one-workgroup adjoint hands no diffusion cotangent out); with `density` the density half (sol_karman_density_bwd_re) adds
+    its part onto g_v*_in and g_re.  As in KarmanStepDensFn each half runs only when its cotangent arrived."""
+
+    @staticmethod
+    def forward(ctx, d, vy, vx, re, cfg, masks, workspace, info, density):
+        _require_staged(cfg, "re_grad")
+        _lib.require_gpu()
+        d, vy, vx, re = (_lib.f32(t) for t in (d, vy, vx, re))
+        if masks.large:
+            outs, svy, svx = karman_step_large_saved(d, vy, vx, re, cfg, masks, workspace, info)
+        else:
+            outs, svy, svx = _step_fwd_saved(d, vy, vx, re, cfg, masks, info)
+        ctx.save_for_backward(d, vy, vx, svy, svx, re)
+        ctx.cfg, ctx.masks, ctx.info, ctx.density = cfg, masks, info, density
+        if not density:
+            ctx.mark_non_differentiable(outs[0])
+        ctx.set_materialize_grads(False)
+        return outs
+
+    @staticmethod
+    def backward(ctx, gd, gvy, gvx):
+        d, vy, vx, svy, svx, re = ctx.saved_tensors
+        cfg, masks = ctx.cfg, ctx.masks
+        od = oy = ox = g_re = None
+        if gvy is not None or gvx is not None:
+            gvy = torch.zeros_like(svy) if gvy is None else gvy.contiguous()
+            gvx = torch.zeros_like(svx) if gvx is None else gvx.contiguous()
+            oy, ox, g_re = karman_step_large_bwd_re(svy, svx, re, gvy, gvx, vy, vx, cfg, masks, info=ctx.info)
+        if ctx.density and gd is not None:
+            od, oy, ox, g_re = karman_density_bwd_re(d, svy, svx, re, gd, vy, vx, cfg, masks, oy, ox, g_re)
+        return od, oy, ox, g_re, None, None, None, None, None
+
+
+def karman_step(d, vy, vx, re, cfg, masks, info=None, density_grad=False, re_grad=False):
     """One step on a one-workgroup grid.  density_grad=True (opt-in): the density output is differentiable too (KarmanStepDensFn), taken
-    when any of d, vy, vx requires a gradient."""
+    when any of d, vy, vx requires a gradient.  re_grad=True (opt-in): a tensor `re` that requires a gradient receives one
+    (KarmanStepReFn; grids with Y, X >= 16; composes with density_grad).  Without the flag `re` is data."""
+    if re_grad and torch.is_grad_enabled() and isinstance(re, torch.Tensor) and re.requires_grad:
+        return KarmanStepReFn.apply(d, vy, vx, re, cfg, masks, None, info, bool(density_grad))
     if density_grad and torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (d, vy, vx)):
         return KarmanStepDensFn.apply(d, vy, vx, re, cfg, masks, None, info)
     return KarmanStepFn.apply(d, vy, vx, re, cfg, masks, info)

@@ -5,7 +5,7 @@ The ops call the same entry points of libsol_hip.so as ops.py (ctypes, raw devic
 ABI) and carry the hand-written adjoints (sol_karman_step_bwd, sol_burgers_step_bwd / _bwd_large, sol_conv5x5 backward-data / -weight)
 through torch.library.register_autograd, so they compose with any other PyTorch op and show up in the dispatcher
 (torch.ops.sol.karman_step, .conv5x5, .burgers_step, .adam_tf_step; .karman_step_dens = karman_step with a differentiable density
-output, over sol_karman_density_bwd).  Scene constants (masks, solver blobs, the cfg
+output, over sol_karman_density_bwd; .karman_step_re = karman_step differentiable with respect to re as well, over the _re adjoints).  Scene constants (masks, solver blobs, the cfg
 struct) are not tensors: they are registered once with register_scene() and referred to by an integer handle."""
 import ctypes as C
 
@@ -18,6 +18,7 @@ _SCENES = {}
 _LIB = torch.library.Library("sol", "DEF")
 _LIB.define("karman_step(Tensor d, Tensor vy, Tensor vx, Tensor re, int scene) -> (Tensor, Tensor, Tensor)")
 _LIB.define("karman_step_dens(Tensor d, Tensor vy, Tensor vx, Tensor re, int scene) -> (Tensor, Tensor, Tensor)")
+_LIB.define("karman_step_re(Tensor d, Tensor vy, Tensor vx, Tensor re, int scene, bool density=False) -> (Tensor, Tensor, Tensor)")
 _LIB.define("karman_density_bwd(Tensor d, Tensor svy, Tensor svx, Tensor re, Tensor gd, int scene) -> (Tensor, Tensor, Tensor)")
 _LIB.define("karman_step_bwd(Tensor svy, Tensor svx, Tensor re, Tensor gvy, Tensor gvx, int scene) -> (Tensor, Tensor)")
 _LIB.define("karman_step_fwd_saved(Tensor d, Tensor vy, Tensor vx, Tensor re, int scene) -> (Tensor, Tensor, Tensor, Tensor, Tensor)")
@@ -138,6 +139,17 @@ class _KarmanDensFn(torch.autograd.Function):
 
 
 _LIB.impl("karman_step_dens", lambda d, vy, vx, re, scene: _KarmanDensFn.apply(d, vy, vx, re, scene), "AutogradCUDA")
+
+
+# karman_step differentiable with respect to re too (opt-in; in karman_step and karman_step_dens re is data); density: d_out stays in the
+# graph as in karman_step_dens.  The autograd.Function of ops.py is the hand-written forward + backward pair (grids with Y, X >= 16)
+def _karman_step_re(d, vy, vx, re, scene, density=False):
+    cfg, masks = _SCENES[scene]
+    return ops.KarmanStepReFn.apply(d, vy, vx, re, cfg, masks, None, None, bool(density))
+
+
+_LIB.impl("karman_step_re", lambda d, vy, vx, re, scene, density=False: _karman_step(d, vy, vx, re, scene), "CUDA")
+_LIB.impl("karman_step_re", _karman_step_re, "AutogradCUDA")
 
 # conv / burgers: the autograd.Functions of ops.py already are the hand-written forward + backward pairs
 _LIB.impl("conv5x5", lambda x, w, b, residual, lrelu, slope: ops.Conv5x5Fn.apply(x, w, b, residual, lrelu, slope), "AutogradCUDA")
