@@ -113,10 +113,10 @@ class KarmanFlow:
     def __init__(self, pressure_solver=None, make_input_divfree=False, make_output_divfree=True,
                  cg_rtol=1e-6, cg_atol=1e-9, cg_max_iter=2000, grad_pad="replicate", inflow_order="after",
                  obstacles=None, active=None, density_grad=False, re_grad=False):
-        # re_grad=True (opt-in): a tensor `re` given to step() that requires a gradient receives one (ops.KarmanStepReFn: fit the
+        # re_grad=True (opt-in): a tensor `re` given to step() that requires a gradient receives one (ops.KarmanStepFn's re mode: fit the
         # viscosity to observed frames, a loss term on Re); the default treats re as data
         self._re_grad = bool(re_grad)
-        # density_grad=True (opt-in): step() keeps the density in the autograd graph (ops.KarmanStepDensFn: a loss on dens frames
+        # density_grad=True (opt-in): step() keeps the density in the autograd graph (ops.KarmanStepFn's density mode: a loss on dens frames
         # differentiates with respect to the initial density and velocity); the default treats it as a passive tracer, as the reference's loss does
         self._density_grad = bool(density_grad)
         # the reference's plug point: None = this build's default ("auto": the direct solver where the grid and the
@@ -225,7 +225,7 @@ class KarmanFlow:
         if masks.large:
             # beyond the one-workgroup kernels (data generation at 256 x 128, karman.py:98-159): the multi-launch path, direct solve
             # where the scene's blob builds, else the preconditioned CG (solve_info: iterations / converged per simulation, and
-            # iterations_bwd / converged_bwd after backward()); differentiable like the small path (ops.KarmanStepLargeFn)
+            # iterations_bwd / converged_bwd after backward()); differentiable like the small path (ops.KarmanStepFn)
             n = ops.large_workspace_bytes(cfg, masks)
             if getattr(self, "_large_ws", None) is None or self._large_ws[0] != (B, Y, X, str(dev)) or self._large_ws[1].numel() * 4 < n:
                 self._large_ws = ((B, Y, X, str(dev)), torch.empty((n + 3) // 4, dtype=torch.float32, device=dev))

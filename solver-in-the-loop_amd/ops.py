@@ -155,8 +155,8 @@ def _publish_cg(info, cg_info, suffix=""):
         info["iterations" + suffix], info["converged" + suffix] = cg_info[0], cg_info[1]
 
 
-def _large_fwd(d, vy, vx, re, cfg, masks, outs=None):
-    """Outputs of the large-grid forward step (fresh unless given) and the fourteen arguments its entry points begin with"""
+def _step_fwd_args(d, vy, vx, re, cfg, masks, outs=None):
+    """Outputs of the forward step (fresh unless given) and the fourteen arguments each of its entry points begins with"""
     if outs is None:
         outs = torch.empty_like(d), torch.empty_like(vy), torch.empty_like(vx)
     head = (C.byref(cfg), stream(), ptr(d), ptr(vy), ptr(vx), ptr(re), ptr(masks.active), ptr(masks.inflow), ptr(masks.velBCy),
@@ -164,55 +164,32 @@ def _large_fwd(d, vy, vx, re, cfg, masks, outs=None):
     return outs, head
 
 
-class KarmanStepLargeFn(torch.autograd.Function):
-    """The large-grid step with its hand-written adjoint (sol_karman_step_fwd_large_saved / sol_karman_step_bwd_large), for the scene's
-    solver (direct or CG).  Differentiable with respect to the velocity; the density is a passive tracer."""
-
-    @staticmethod
-    def forward(ctx, d, vy, vx, re, cfg, masks, workspace, info):
-        outs, svy, svx = karman_step_large_saved(d, vy, vx, re, cfg, masks, workspace, info)
-        ctx.save_for_backward(svy, svx, re)
-        ctx.cfg, ctx.masks, ctx.info = cfg, masks, info
-        ctx.mark_non_differentiable(outs[0])
-        return outs
-
-    @staticmethod
-    def backward(ctx, _gd, gvy, gvx):
-        svy, svx, re = ctx.saved_tensors
-        gvy = torch.zeros_like(svy) if gvy is None else gvy.contiguous()
-        gvx = torch.zeros_like(svx) if gvx is None else gvx.contiguous()
-        oy, ox = karman_step_large_bwd(svy, svx, re, gvy, gvx, ctx.cfg, ctx.masks, info=ctx.info)
-        return None, oy, ox, None, None, None, None, None
-
-
-def karman_step_large_saved(d, vy, vx, re, cfg, masks, workspace=None, info=None):
-    """The differentiable form of the large-grid step without autograd (sol_karman_step_fwd_large_saved): ((d, vy, vx) after the step,
-    saved vy, saved vx) -- the post-diffusion velocity karman_step_large_bwd takes.  `info` as in karman_step_large."""
+def karman_step_saved(d, vy, vx, re, cfg, masks, workspace=None, info=None):
+    """The differentiable form of the step without autograd, on any grid: ((d, vy, vx) after the step, saved vy, saved vx) -- the
+    post-diffusion velocity the adjoints take.  A one-workgroup grid runs sol_karman_step_fwd (`info` receives "iterations"), a grid
+    beyond them (masks.large) sol_karman_step_fwd_large_saved with `workspace` and `info` as in karman_step_large."""
+    _lib.require_gpu()
     lib = _lib.load()
-    d, vy, vx = d.contiguous(), vy.contiguous(), vx.contiguous()
-    workspace = _workspace(large_workspace_bytes(cfg, masks), workspace, vy.device)
-    outs, head = _large_fwd(d, vy, vx, re, cfg, masks)
+    d, vy, vx, re = (_lib.f32(t) for t in (d, vy, vx, re))
+    B, Y, X = cfg.B, cfg.Y, cfg.X
+    assert vy.shape == (B, Y + 1, X) and vx.shape == (B, Y, X + 1) and d.shape == (B, Y, X) and re.shape == (B,)
+    outs, head = _step_fwd_args(d, vy, vx, re, cfg, masks)
     svy, svx = torch.empty_like(vy), torch.empty_like(vx)
-    cg_info = _cg_info(masks, cfg.B, vy.device)
-    check(lib.sol_karman_step_fwd_large_saved(*head, ptr(svy), ptr(svx), _hdr(masks.direct_header), ptr(masks.box),
-                                              _hdr(masks.box_header), ptr(cg_info), ptr(workspace), workspace.numel() * 4))
-    _publish_cg(info, cg_info)
+    if masks.large:
+        workspace = _workspace(large_workspace_bytes(cfg, masks), workspace, vy.device)
+        cg_info = _cg_info(masks, B, vy.device)
+        check(lib.sol_karman_step_fwd_large_saved(*head, ptr(svy), ptr(svx), _hdr(masks.direct_header), ptr(masks.box),
+                                                  _hdr(masks.box_header), ptr(cg_info), ptr(workspace), workspace.numel() * 4))
+        _publish_cg(info, cg_info)
+    else:
+        iters = None if info is None else torch.empty(B, dtype=torch.int32, device=vy.device)      # the kernel only stores to it
+        check(lib.sol_karman_step_fwd(*head, ptr(svy), ptr(svx), None, None, ptr(iters)))
+        if info is not None:
+            info["iterations"] = iters
     return outs, svy, svx
 
 
-def karman_step_large_bwd(svy, svx, re, gvy, gvx, cfg, masks, workspace=None, info=None):
-    """Adjoint of the large-grid step (sol_karman_step_bwd_large): (g_vy_in, g_vx_in) from the saved post-diffusion velocity and the
-    gradient with respect to the step's output velocity.  With the CG solve, `info` receives "iterations_bwd" / "converged_bwd"."""
-    lib = _lib.load()
-    workspace = _workspace(large_bwd_workspace_bytes(cfg, masks), workspace, svy.device)
-    oy, ox = torch.empty_like(svy), torch.empty_like(svx)
-    cg_info = _cg_info(masks, cfg.B, svy.device)
-    check(lib.sol_karman_step_bwd_large(
-        C.byref(cfg), stream(), ptr(svy), ptr(svx), ptr(re), ptr(masks.active), ptr(masks.velBCyMask), masks.bc_stride,
-        ptr(gvy), ptr(gvx), ptr(oy), ptr(ox), _hdr(masks.direct_header), ptr(masks.box), _hdr(masks.box_header), ptr(cg_info),
-        ptr(workspace), workspace.numel() * 4))
-    _publish_cg(info, cg_info, "_bwd")
-    return oy, ox
+karman_step_large_saved = karman_step_saved      # the name the large-grid callers know it by (trainer.LargeGridTrainer, tools)
 
 
 def karman_step_large(d, vy, vx, re, cfg, masks, workspace=None, info=None, feat=None, feat_scale=None, p_guess=None, out=None,
@@ -220,34 +197,29 @@ def karman_step_large(d, vy, vx, re, cfg, masks, workspace=None, info=None, feat
     """The step for grids beyond the one-workgroup kernels (data generation at 256 x 128,
     /root/reference/karman-2d/karman.py:98-159): sol_karman_step_fwd_large (direct solve) or sol_karman_step_fwd_large_cg (CG solve,
     masks.pressure_solver == "cg").  Returns (d, vy, vx) after the step; with the CG solve, `info` (a dict) receives "iterations" and
-    "converged", device int32 [B] each.  When grad is enabled and vy or vx requires a gradient the call goes through KarmanStepLargeFn
+    "converged", device int32 [B] each.  When grad is enabled and vy or vx requires a gradient the call goes through KarmanStepFn
     (same forward launches, plus the saved post-diffusion velocity) and `info` also receives "iterations_bwd" / "converged_bwd" after
     backward(); otherwise nothing is kept.
     No-grad extras (a roll-out, trainer.LargeGridRollout): `feat` [B,Y,X,4] receives the network's input, to_feature of the new velocity
     times `feat_scale` (three factors, 1 / std; channel 3 is zero); `p_guess` [B,Y,X] warm-starts the CG solve
     (sol_karman_step_fwd_large_cg_warm: read as the initial guess, overwritten with the step's pressure) and is an error on a scene with
     the direct solver; `out` = (d, vy, vx) buffers to write instead of fresh tensors (they must not be the inputs).
-    density_grad=True (opt-in): the density output is differentiable too (KarmanStepDensFn: same forward launches; the differentiable
-    form is taken when any of d, vy, vx requires a gradient).
-    re_grad=True (opt-in): a tensor `re` that requires a gradient receives one (KarmanStepReFn: same forward launches, the step's input
-    velocity saved as well; composes with density_grad).  Without the flag `re` is data."""
+    density_grad=True (opt-in): the density output is differentiable too (KarmanStepFn's density mode: same forward launches; the
+    differentiable form is taken when any of d, vy, vx requires a gradient).
+    re_grad=True (opt-in): a tensor `re` that requires a gradient receives one (KarmanStepFn's re mode: same forward launches, the step's
+    input velocity saved as well; composes with density_grad).  Without the flag `re` is data."""
     if p_guess is not None and masks.direct is not None:
         raise ValueError("karman_step_large: p_guess warm-starts the CG pressure solve; this scene runs the direct solver (no iteration to start)")
+    differentiable, density, want_re = _step_mode(d, vy, vx, re, cfg, density_grad, re_grad)
     _lib.require_gpu()
     lib = _lib.load()
     d, vy, vx, re = (_lib.f32(t) for t in (d, vy, vx, re))
     B, Y, X = cfg.B, cfg.Y, cfg.X
     assert vy.shape == (B, Y + 1, X) and vx.shape == (B, Y, X + 1) and d.shape == (B, Y, X) and re.shape == (B,)
-    extras = feat is not None or p_guess is not None or out is not None
-    want_re = re_grad and re.requires_grad
-    if torch.is_grad_enabled() and (vy.requires_grad or vx.requires_grad or (density_grad and d.requires_grad) or want_re):
-        if extras:
+    if differentiable:
+        if feat is not None or p_guess is not None or out is not None:
             raise ValueError("karman_step_large: feat / p_guess / out belong to the no-grad step (the differentiable step keeps its own state)")
-        if want_re:
-            return KarmanStepReFn.apply(d, vy, vx, re, cfg, masks, workspace, info, bool(density_grad))
-        if density_grad:
-            return KarmanStepDensFn.apply(d, vy, vx, re, cfg, masks, workspace, info)
-        return KarmanStepLargeFn.apply(d, vy, vx, re, cfg, masks, workspace, info)
+        return KarmanStepFn.apply(d, vy, vx, re, cfg, masks, workspace, info, density, want_re)
     if (feat is None) != (feat_scale is None):
         raise ValueError("karman_step_large: feat and feat_scale go together")
     if feat is not None and (feat.shape != (B, Y, X, 4) or feat.device != vy.device):
@@ -256,12 +228,12 @@ def karman_step_large(d, vy, vx, re, cfg, masks, workspace=None, info=None, feat
         raise ValueError("karman_step_large: p_guess must be [B,Y,X] = %s on %s (got %s on %s)" % ((B, Y, X), vy.device, tuple(p_guess.shape), p_guess.device))
     workspace = _workspace(large_workspace_bytes(cfg, masks), workspace, vy.device)
     if out is None:
-        outs, head = _large_fwd(d, vy, vx, re, cfg, masks)
+        outs, head = _step_fwd_args(d, vy, vx, re, cfg, masks)
     else:
         outs = tuple(out)
         if [tuple(t.shape) for t in outs] != [tuple(t.shape) for t in (d, vy, vx)]:
             raise ValueError("karman_step_large: out must be (d, vy, vx) buffers of the inputs' shapes")
-        head = _large_fwd(d, vy, vx, re, cfg, masks, outs)[1]
+        head = _step_fwd_args(d, vy, vx, re, cfg, masks, outs)[1]
     fs = None if feat_scale is None else (feat_scale if isinstance(feat_scale, C.Array) else _scale3(feat_scale))
     cg_info = _cg_info(masks, B, vy.device)
     if cg_info is None:
@@ -322,33 +294,9 @@ def _scale3(vals):
     return (C.c_float * 3)(*[float(v) for v in vals])
 
 
-def _step_fwd_saved(d, vy, vx, re, cfg, masks, info):
-    """The one-workgroup forward step (sol_karman_step_fwd): ((d, vy, vx) after the step, saved vy, saved vx)"""
-    _lib.require_gpu()
-    lib = _lib.load()
-    d, vy, vx, re = (_lib.f32(t) for t in (d, vy, vx, re))
-    B, Y, X = cfg.B, cfg.Y, cfg.X
-    assert vy.shape == (B, Y + 1, X) and vx.shape == (B, Y, X + 1) and d.shape == (B, Y, X) and re.shape == (B,)
-    d_out = torch.empty_like(d)
-    vy_out = torch.empty_like(vy)
-    vx_out = torch.empty_like(vx)
-    svy = torch.empty_like(vy)
-    svx = torch.empty_like(vx)
-    iters = torch.empty(B, dtype=torch.int32, device=vy.device)
-    check(lib.sol_karman_step_fwd(C.byref(cfg), stream(), ptr(d), ptr(vy), ptr(vx), ptr(re),
-                                  ptr(masks.active), ptr(masks.inflow), ptr(masks.velBCy), ptr(masks.velBCyMask),
-                                  masks.bc_stride, ptr(d_out), ptr(vy_out), ptr(vx_out), ptr(svy), ptr(svx),
-                                  None, None, ptr(iters)))
-    if info is not None:
-        info["iterations"] = iters
-    return (d_out, vy_out, vx_out), svy, svx
-
-
 def _step_bwd(svy, svx, re, gvy, gvx, cfg, masks, info):
-    """The one-workgroup velocity adjoint (sol_karman_step_bwd); a missing cotangent counts as zero"""
+    """The one-workgroup velocity adjoint (sol_karman_step_bwd), pressure solve fused in"""
     lib = _lib.load()
-    gvy = torch.zeros_like(svy) if gvy is None else gvy.contiguous()
-    gvx = torch.zeros_like(svx) if gvx is None else gvx.contiguous()
     oy = torch.empty_like(svy)
     ox = torch.empty_like(svx)
     iters = torch.empty(cfg.B, dtype=torch.int32, device=svy.device)
@@ -360,96 +308,14 @@ def _step_bwd(svy, svx, re, gvy, gvx, cfg, masks, info):
     return oy, ox
 
 
-class KarmanStepFn(torch.autograd.Function):
-    """(d, vy, vx) [B,Y,X] / [B,Y+1,X] / [B,Y,X+1] -> one simulator_lo.step(...)."""
-
-    @staticmethod
-    def forward(ctx, d, vy, vx, re, cfg, masks, info):
-        _lib.require_gpu()
-        re = _lib.f32(re)
-        outs, svy, svx = _step_fwd_saved(d, vy, vx, re, cfg, masks, info)
-        ctx.save_for_backward(svy, svx, re)
-        ctx.cfg, ctx.masks, ctx.info = cfg, masks, info
-        ctx.mark_non_differentiable(outs[0])
-        return outs
-
-    @staticmethod
-    def backward(ctx, _gd, gvy, gvx):
-        svy, svx, re = ctx.saved_tensors
-        oy, ox = _step_bwd(svy, svx, re, gvy, gvx, ctx.cfg, ctx.masks, ctx.info)
-        return None, oy, ox, None, None, None, None
+def large_bwd_re_workspace_bytes(cfg, masks):
+    """Device scratch of the staged adjoint with the Reynolds-number gradient (sol_karman_step_bwd_large_re) for the scene's solver."""
+    return _lib.load().sol_karman_step_bwd_large_re_workspace_bytes_for(C.byref(cfg), _hdr(masks.direct_header))
 
 
 def density_bwd_workspace_bytes(cfg):
     """Device scratch of the density adjoint (sol_karman_density_bwd)."""
     return _lib.load().sol_karman_density_bwd_workspace_bytes(C.byref(cfg))
-
-
-def karman_density_bwd(d, svy, svx, re, g_d, cfg, masks, g_vy=None, g_vx=None, workspace=None):
-    """Adjoint of the step's marker density (sol_karman_density_bwd), on any grid: (g_d_in, g_vy_in, g_vx_in) from the step's input
-    density `d`, the saved post-diffusion velocity and the gradient `g_d` with respect to the step's output density.  g_vy / g_vx (both
-    or neither): buffers that already hold the velocity adjoint's result; the density's part is added onto them in place (one fp32 add
-    per face) and they are returned.  Without them the density's part alone is written to fresh tensors."""
-    _lib.require_gpu()
-    lib = _lib.load()
-    if (g_vy is None) != (g_vx is None):
-        raise ValueError("karman_density_bwd: g_vy and g_vx go together")
-    B, Y, X = cfg.B, cfg.Y, cfg.X
-    d, svy, svx, re, g_d = (_lib.f32(t) for t in (d, svy, svx, re, g_d))
-    if d.shape != (B, Y, X) or g_d.shape != (B, Y, X) or svy.shape != (B, Y + 1, X) or svx.shape != (B, Y, X + 1) or re.shape != (B,):
-        raise ValueError("karman_density_bwd: d, g_d %s / %s, svy %s, svx %s, re %s are not [B,Y,X], [B,Y+1,X], [B,Y,X+1], [B] of the cfg (%d, %d, %d)"
-                         % (tuple(d.shape), tuple(g_d.shape), tuple(svy.shape), tuple(svx.shape), tuple(re.shape), B, Y, X))
-    accumulate = g_vy is not None
-    if accumulate and (g_vy.shape != svy.shape or g_vx.shape != svx.shape):
-        raise ValueError("karman_density_bwd: g_vy / g_vx must have the velocity's shapes")
-    oy, ox = (g_vy, g_vx) if accumulate else (torch.empty_like(svy), torch.empty_like(svx))
-    od = torch.empty_like(d)
-    workspace = _workspace(density_bwd_workspace_bytes(cfg), workspace, d.device)
-    check(lib.sol_karman_density_bwd(C.byref(cfg), stream(), ptr(d), ptr(masks.inflow), ptr(svy), ptr(svx), ptr(re), ptr(masks.velBCyMask),
-                                     masks.bc_stride, ptr(g_d), ptr(od), ptr(oy), ptr(ox), int(accumulate), ptr(workspace),
-                                     workspace.numel() * 4))
-    return od, oy, ox
-
-
-class KarmanStepDensFn(torch.autograd.Function):
-    """The step on any grid with a differentiable density output (opt-in, density_grad=True): the forward launches of KarmanStepFn /
-    KarmanStepLargeFn; backward returns (g_d_in, g_vy_in, g_vx_in).  The velocity adjoint (with its pressure solve) runs only when a
-    velocity cotangent arrived, the density adjoint (sol_karman_density_bwd, added onto the velocity adjoint's result) only when a
-    density cotangent did."""
-
-    @staticmethod
-    def forward(ctx, d, vy, vx, re, cfg, masks, workspace, info):
-        _lib.require_gpu()
-        d, re = _lib.f32(d), _lib.f32(re)
-        if masks.large:
-            outs, svy, svx = karman_step_large_saved(d, vy, vx, re, cfg, masks, workspace, info)
-        else:
-            outs, svy, svx = _step_fwd_saved(d, vy, vx, re, cfg, masks, info)
-        ctx.save_for_backward(d, svy, svx, re)
-        ctx.cfg, ctx.masks, ctx.info = cfg, masks, info
-        ctx.set_materialize_grads(False)
-        return outs
-
-    @staticmethod
-    def backward(ctx, gd, gvy, gvx):
-        d, svy, svx, re = ctx.saved_tensors
-        cfg, masks = ctx.cfg, ctx.masks
-        od = oy = ox = None
-        if gvy is not None or gvx is not None:
-            if masks.large:
-                gvy = torch.zeros_like(svy) if gvy is None else gvy.contiguous()
-                gvx = torch.zeros_like(svx) if gvx is None else gvx.contiguous()
-                oy, ox = karman_step_large_bwd(svy, svx, re, gvy, gvx, cfg, masks, info=ctx.info)
-            else:
-                oy, ox = _step_bwd(svy, svx, re, gvy, gvx, cfg, masks, ctx.info)
-        if gd is not None:
-            od, oy, ox = karman_density_bwd(d, svy, svx, re, gd, cfg, masks, oy, ox)
-        return od, oy, ox, None, None, None, None, None
-
-
-def large_bwd_re_workspace_bytes(cfg, masks):
-    """Device scratch of the staged adjoint with the Reynolds-number gradient (sol_karman_step_bwd_large_re) for the scene's solver."""
-    return _lib.load().sol_karman_step_bwd_large_re_workspace_bytes_for(C.byref(cfg), _hdr(masks.direct_header))
 
 
 def density_bwd_re_workspace_bytes(cfg):
@@ -463,13 +329,49 @@ def _require_staged(cfg, who):
                        "with Y, X >= 16; this one is %dx%d" % (who, cfg.Y, cfg.X))
 
 
-def _g_re(g_re, B, device):
-    """(buffer, accumulate): a fresh [B] buffer to write, or the caller's to add onto"""
-    if g_re is None:
-        return torch.empty(B, dtype=torch.float32, device=device), 0
-    if g_re.shape != (B,):
-        raise ValueError("g_re must be [B] = (%d,), got %s" % (B, tuple(g_re.shape)))
-    return g_re, 1
+def _re_tail(who, re_in, svy, svx, B):
+    """The four arguments an _re entry point takes after its plain sibling's, from re_in = (vy_in, vx_in, g_re): the step's INPUT
+    velocity, and g_re [B], the caller's buffer to add onto (one fp32 add) or None for a fresh one to write  ->  (arguments, g_re)"""
+    vy_in, vx_in, g_re = re_in
+    vy_in, vx_in = _lib.f32(vy_in), _lib.f32(vx_in)
+    if vy_in.shape != svy.shape or vx_in.shape != svx.shape:
+        raise ValueError("%s: vy_in / vx_in must have the velocity's shapes" % who)
+    accumulate = g_re is not None
+    if not accumulate:
+        g_re = torch.empty(B, dtype=torch.float32, device=svy.device)
+    elif g_re.shape != (B,):
+        raise ValueError("%s: g_re must be [B] = (%d,), got %s" % (who, B, tuple(g_re.shape)))
+    return (ptr(vy_in), ptr(vx_in), ptr(g_re), int(accumulate)), g_re
+
+
+def _large_bwd(who, svy, svx, re, gvy, gvx, cfg, masks, workspace, info, re_in=None):
+    """karman_step_large_bwd (re_in None) and karman_step_large_bwd_re (re_in = (vy_in, vx_in, g_re)): the _re entry point takes its
+    plain sibling's arguments and four more"""
+    if re_in is not None:
+        _require_staged(cfg, who)
+    _lib.require_gpu()
+    lib = _lib.load()
+    svy, svx, re, gvy, gvx = (_lib.f32(t) for t in (svy, svx, re, gvy, gvx))
+    if re_in is None:
+        entry, nbytes, tail, g_re = lib.sol_karman_step_bwd_large, large_bwd_workspace_bytes(cfg, masks), (), None
+    else:
+        entry, nbytes = lib.sol_karman_step_bwd_large_re, large_bwd_re_workspace_bytes(cfg, masks)
+        tail, g_re = _re_tail(who, re_in, svy, svx, cfg.B)
+    box, box_header = masks.staged_box()
+    workspace = _workspace(nbytes, workspace, svy.device)
+    oy, ox = torch.empty_like(svy), torch.empty_like(svx)
+    cg_info = _cg_info(masks, cfg.B, svy.device)
+    check(entry(C.byref(cfg), stream(), ptr(svy), ptr(svx), ptr(re), ptr(masks.active), ptr(masks.velBCyMask), masks.bc_stride,
+                ptr(gvy), ptr(gvx), ptr(oy), ptr(ox), _hdr(masks.direct_header), ptr(box), _hdr(box_header), ptr(cg_info),
+                ptr(workspace), workspace.numel() * 4, *tail))
+    _publish_cg(info, cg_info, "_bwd")
+    return (oy, ox) if re_in is None else (oy, ox, g_re)
+
+
+def karman_step_large_bwd(svy, svx, re, gvy, gvx, cfg, masks, workspace=None, info=None):
+    """Adjoint of the large-grid step (sol_karman_step_bwd_large): (g_vy_in, g_vx_in) from the saved post-diffusion velocity and the
+    gradient with respect to the step's output velocity.  With the CG solve, `info` receives "iterations_bwd" / "converged_bwd"."""
+    return _large_bwd("karman_step_large_bwd", svy, svx, re, gvy, gvx, cfg, masks, workspace, info)
 
 
 def karman_step_large_bwd_re(svy, svx, re, gvy, gvx, vy_in, vx_in, cfg, masks, g_re=None, workspace=None, info=None):
@@ -477,70 +379,80 @@ def karman_step_large_bwd_re(svy, svx, re, gvy, gvx, vy_in, vx_in, cfg, masks, g
     the one-workgroup grids included: (g_vy_in, g_vx_in, g_re) from the saved post-diffusion velocity, the cotangent of the step's output
     velocity and the step's INPUT velocity.  g_vy_in / g_vx_in are karman_step_large_bwd's bits.  g_re [B]: a buffer to add onto (one
     fp32 add), else a fresh one is written."""
-    _require_staged(cfg, "karman_step_large_bwd_re")
+    return _large_bwd("karman_step_large_bwd_re", svy, svx, re, gvy, gvx, cfg, masks, workspace, info, (vy_in, vx_in, g_re))
+
+
+def _density_bwd(who, d, svy, svx, re, g_d, cfg, masks, g_vy, g_vx, workspace, re_in=None):
+    """karman_density_bwd (re_in None) and karman_density_bwd_re (re_in = (vy_in, vx_in, g_re)), paired as in _large_bwd"""
     _lib.require_gpu()
     lib = _lib.load()
-    svy, svx, re, gvy, gvx, vy_in, vx_in = (_lib.f32(t) for t in (svy, svx, re, gvy, gvx, vy_in, vx_in))
-    if vy_in.shape != svy.shape or vx_in.shape != svx.shape:
-        raise ValueError("karman_step_large_bwd_re: vy_in / vx_in must have the velocity's shapes")
-    box, box_header = masks.staged_box()
-    workspace = _workspace(large_bwd_re_workspace_bytes(cfg, masks), workspace, svy.device)
-    oy, ox = torch.empty_like(svy), torch.empty_like(svx)
-    out, acc = _g_re(g_re, cfg.B, svy.device)
-    cg_info = _cg_info(masks, cfg.B, svy.device)
-    check(lib.sol_karman_step_bwd_large_re(
-        C.byref(cfg), stream(), ptr(svy), ptr(svx), ptr(re), ptr(masks.active), ptr(masks.velBCyMask), masks.bc_stride,
-        ptr(gvy), ptr(gvx), ptr(oy), ptr(ox), _hdr(masks.direct_header), ptr(box), _hdr(box_header), ptr(cg_info),
-        ptr(workspace), workspace.numel() * 4, ptr(vy_in), ptr(vx_in), ptr(out), acc))
-    _publish_cg(info, cg_info, "_bwd")
-    return oy, ox, out
+    if (g_vy is None) != (g_vx is None):
+        raise ValueError("%s: g_vy and g_vx go together" % who)
+    B, Y, X = cfg.B, cfg.Y, cfg.X
+    d, svy, svx, re, g_d = (_lib.f32(t) for t in (d, svy, svx, re, g_d))
+    for name, t, shape in (("d", d, (B, Y, X)), ("g_d", g_d, (B, Y, X)), ("svy", svy, (B, Y + 1, X)), ("svx", svx, (B, Y, X + 1)), ("re", re, (B,))):
+        if t.shape != shape:
+            raise ValueError("%s: %s is %s, not %s of the cfg (B, Y, X) = (%d, %d, %d)" % (who, name, tuple(t.shape), shape, B, Y, X))
+    accumulate = g_vy is not None
+    if accumulate and (g_vy.shape != svy.shape or g_vx.shape != svx.shape):
+        raise ValueError("%s: g_vy / g_vx must have the velocity's shapes" % who)
+    if re_in is None:
+        entry, nbytes, tail, g_re = lib.sol_karman_density_bwd, density_bwd_workspace_bytes(cfg), (), None
+    else:
+        entry, nbytes = lib.sol_karman_density_bwd_re, density_bwd_re_workspace_bytes(cfg)
+        tail, g_re = _re_tail(who, re_in, svy, svx, B)
+    oy, ox = (g_vy, g_vx) if accumulate else (torch.empty_like(svy), torch.empty_like(svx))
+    od = torch.empty_like(d)
+    workspace = _workspace(nbytes, workspace, d.device)
+    check(entry(C.byref(cfg), stream(), ptr(d), ptr(masks.inflow), ptr(svy), ptr(svx), ptr(re), ptr(masks.velBCyMask), masks.bc_stride,
+                ptr(g_d), ptr(od), ptr(oy), ptr(ox), int(accumulate), ptr(workspace), workspace.numel() * 4, *tail))
+    return (od, oy, ox) if re_in is None else (od, oy, ox, g_re)
+
+
+def karman_density_bwd(d, svy, svx, re, g_d, cfg, masks, g_vy=None, g_vx=None, workspace=None):
+    """Adjoint of the step's marker density (sol_karman_density_bwd), on any grid: (g_d_in, g_vy_in, g_vx_in) from the step's input
+    density `d`, the saved post-diffusion velocity and the gradient `g_d` with respect to the step's output density.  g_vy / g_vx (both
+    or neither): buffers that already hold the velocity adjoint's result; the density's part is added onto them in place (one fp32 add
+    per face) and they are returned.  Without them the density's part alone is written to fresh tensors."""
+    return _density_bwd("karman_density_bwd", d, svy, svx, re, g_d, cfg, masks, g_vy, g_vx, workspace)
 
 
 def karman_density_bwd_re(d, svy, svx, re, g_d, vy_in, vx_in, cfg, masks, g_vy=None, g_vx=None, g_re=None, workspace=None):
     """karman_density_bwd with the gradient with respect to re (sol_karman_density_bwd_re): (g_d_in, g_vy_in, g_vx_in, g_re).  The first
     three are karman_density_bwd's bits; g_re [B]: a buffer to add onto (the velocity adjoint's part), else a fresh one is written."""
-    _lib.require_gpu()
-    lib = _lib.load()
-    if (g_vy is None) != (g_vx is None):
-        raise ValueError("karman_density_bwd_re: g_vy and g_vx go together")
-    B, Y, X = cfg.B, cfg.Y, cfg.X
-    d, svy, svx, re, g_d, vy_in, vx_in = (_lib.f32(t) for t in (d, svy, svx, re, g_d, vy_in, vx_in))
-    if (d.shape != (B, Y, X) or g_d.shape != (B, Y, X) or svy.shape != (B, Y + 1, X) or svx.shape != (B, Y, X + 1) or re.shape != (B,)
-            or vy_in.shape != svy.shape or vx_in.shape != svx.shape):
-        raise ValueError("karman_density_bwd_re: d, g_d %s / %s, svy, vy_in %s / %s, svx, vx_in %s / %s, re %s are not [B,Y,X], [B,Y+1,X], "
-                         "[B,Y,X+1], [B] of the cfg (%d, %d, %d)" % (tuple(d.shape), tuple(g_d.shape), tuple(svy.shape), tuple(vy_in.shape),
-                                                                     tuple(svx.shape), tuple(vx_in.shape), tuple(re.shape), B, Y, X))
-    accumulate = g_vy is not None
-    if accumulate and (g_vy.shape != svy.shape or g_vx.shape != svx.shape):
-        raise ValueError("karman_density_bwd_re: g_vy / g_vx must have the velocity's shapes")
-    oy, ox = (g_vy, g_vx) if accumulate else (torch.empty_like(svy), torch.empty_like(svx))
-    od = torch.empty_like(d)
-    out, acc = _g_re(g_re, B, d.device)
-    workspace = _workspace(density_bwd_re_workspace_bytes(cfg), workspace, d.device)
-    check(lib.sol_karman_density_bwd_re(C.byref(cfg), stream(), ptr(d), ptr(masks.inflow), ptr(svy), ptr(svx), ptr(re), ptr(masks.velBCyMask),
-                                        masks.bc_stride, ptr(g_d), ptr(od), ptr(oy), ptr(ox), int(accumulate), ptr(workspace),
-                                        workspace.numel() * 4, ptr(vy_in), ptr(vx_in), ptr(out), acc))
-    return od, oy, ox, out
+    return _density_bwd("karman_density_bwd_re", d, svy, svx, re, g_d, cfg, masks, g_vy, g_vx, workspace, (vy_in, vx_in, g_re))
 
 
-class KarmanStepReFn(torch.autograd.Function):
-    """The step on any grid with Y, X >= 16, differentiable with respect to re as well (opt-in, re_grad=True): the forward launches of
-    KarmanStepFn / KarmanStepLargeFn, with the step's input velocity saved beside the post-diffusion one; backward returns
-    (g_d_in | None, g_vy_in, g_vx_in, g_re).  The velocity half is the STAGED adjoint on every grid (sol_karman_step_bwd_large_re: the
-    fused one-workgroup adjoint hands no diffusion cotangent out); with `density` the density half (sol_karman_density_bwd_re) adds
-    its part onto g_v*_in and g_re.  As in KarmanStepDensFn each half runs only when its cotangent arrived."""
+def _velocity_bwd(svy, svx, re, gvy, gvx, cfg, masks, info, vel_in=None):
+    """The velocity half of the step's adjoint: (g_vy_in, g_vx_in, g_re | None).  vel_in = (vy, vx), the step's input velocity, asks for
+    the gradient with respect to re as well: the staged adjoint on every grid (karman_step_large_bwd_re; the fused one-workgroup adjoint
+    hands no diffusion cotangent out).  Without it: the fused adjoint on a one-workgroup grid, karman_step_large_bwd beyond.  A missing
+    cotangent counts as zero."""
+    gvy = torch.zeros_like(svy) if gvy is None else gvy.contiguous()
+    gvx = torch.zeros_like(svx) if gvx is None else gvx.contiguous()
+    if vel_in is not None:
+        return karman_step_large_bwd_re(svy, svx, re, gvy, gvx, *vel_in, cfg, masks, info=info)
+    if masks.large:
+        return karman_step_large_bwd(svy, svx, re, gvy, gvx, cfg, masks, info=info) + (None,)
+    return _step_bwd(svy, svx, re, gvy, gvx, cfg, masks, info) + (None,)
+
+
+class KarmanStepFn(torch.autograd.Function):
+    """(d, vy, vx) [B,Y,X] / [B,Y+1,X] / [B,Y,X+1] -> one simulator_lo.step(...) on any grid, with its hand-written adjoints; the forward
+    launches are karman_step_saved's in every mode.  Plain: differentiable with respect to the velocity, the density is a passive
+    tracer.  `density` (opt-in, density_grad=True): the density output is differentiable too (karman_density_bwd, added onto the
+    velocity adjoint's result).  `want_re` (opt-in, re_grad=True; grids with Y, X >= 16): differentiable with respect to re as well, the
+    step's input velocity saved beside the post-diffusion one (_step_mode and torch.ops.sol.karman_step_re check the grid).  backward returns (g_d_in | None, g_vy_in, g_vx_in, g_re | None); the
+    velocity half (with its pressure solve) runs only when a velocity cotangent arrived, the density half only when a density cotangent
+    did."""
 
     @staticmethod
-    def forward(ctx, d, vy, vx, re, cfg, masks, workspace, info, density):
-        _require_staged(cfg, "re_grad")
+    def forward(ctx, d, vy, vx, re, cfg, masks, workspace, info, density, want_re):
         _lib.require_gpu()
         d, vy, vx, re = (_lib.f32(t) for t in (d, vy, vx, re))
-        if masks.large:
-            outs, svy, svx = karman_step_large_saved(d, vy, vx, re, cfg, masks, workspace, info)
-        else:
-            outs, svy, svx = _step_fwd_saved(d, vy, vx, re, cfg, masks, info)
-        ctx.save_for_backward(d, vy, vx, svy, svx, re)
-        ctx.cfg, ctx.masks, ctx.info, ctx.density = cfg, masks, info, density
+        outs, svy, svx = karman_step_saved(d, vy, vx, re, cfg, masks, workspace, info)
+        ctx.save_for_backward(svy, svx, re, *((d, vy, vx) if want_re else (d,) if density else ()))
+        ctx.cfg, ctx.masks, ctx.info, ctx.density, ctx.want_re = cfg, masks, info, density, want_re
         if not density:
             ctx.mark_non_differentiable(outs[0])
         ctx.set_materialize_grads(False)
@@ -548,27 +460,42 @@ class KarmanStepReFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gd, gvy, gvx):
-        d, vy, vx, svy, svx, re = ctx.saved_tensors
+        svy, svx, re, *inputs = ctx.saved_tensors
         cfg, masks = ctx.cfg, ctx.masks
+        vel_in = tuple(inputs[1:]) if ctx.want_re else None
         od = oy = ox = g_re = None
         if gvy is not None or gvx is not None:
-            gvy = torch.zeros_like(svy) if gvy is None else gvy.contiguous()
-            gvx = torch.zeros_like(svx) if gvx is None else gvx.contiguous()
-            oy, ox, g_re = karman_step_large_bwd_re(svy, svx, re, gvy, gvx, vy, vx, cfg, masks, info=ctx.info)
-        if ctx.density and gd is not None:
-            od, oy, ox, g_re = karman_density_bwd_re(d, svy, svx, re, gd, vy, vx, cfg, masks, oy, ox, g_re)
-        return od, oy, ox, g_re, None, None, None, None, None
+            oy, ox, g_re = _velocity_bwd(svy, svx, re, gvy, gvx, cfg, masks, ctx.info, vel_in)
+        if ctx.density and gd is not None:        # added onto the velocity half's buffers and g_re
+            if vel_in is None:
+                od, oy, ox = karman_density_bwd(inputs[0], svy, svx, re, gd, cfg, masks, oy, ox)
+            else:
+                od, oy, ox, g_re = karman_density_bwd_re(inputs[0], svy, svx, re, gd, *vel_in, cfg, masks, oy, ox, g_re)
+        return od, oy, ox, g_re, None, None, None, None, None, None
+
+
+def _step_mode(d, vy, vx, re, cfg, density_grad, re_grad):
+    """(differentiable?, density, want_re) of a call of karman_step / karman_step_large, from its inputs as given and its two flags.
+    re_grad with an `re` that requires no gradient is the plain mode.  A grid the staged adjoint does not take is refused here, before
+    any device call."""
+    needs = lambda t: isinstance(t, torch.Tensor) and t.requires_grad
+    density = bool(density_grad)
+    want_re = bool(re_grad) and torch.is_grad_enabled() and needs(re)
+    if want_re:
+        _require_staged(cfg, "re_grad")
+    return torch.is_grad_enabled() and (needs(vy) or needs(vx) or (density and needs(d)) or want_re), density, want_re
 
 
 def karman_step(d, vy, vx, re, cfg, masks, info=None, density_grad=False, re_grad=False):
-    """One step on a one-workgroup grid.  density_grad=True (opt-in): the density output is differentiable too (KarmanStepDensFn), taken
-    when any of d, vy, vx requires a gradient.  re_grad=True (opt-in): a tensor `re` that requires a gradient receives one
-    (KarmanStepReFn; grids with Y, X >= 16; composes with density_grad).  Without the flag `re` is data."""
-    if re_grad and torch.is_grad_enabled() and isinstance(re, torch.Tensor) and re.requires_grad:
-        return KarmanStepReFn.apply(d, vy, vx, re, cfg, masks, None, info, bool(density_grad))
-    if density_grad and torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (d, vy, vx)):
-        return KarmanStepDensFn.apply(d, vy, vx, re, cfg, masks, None, info)
-    return KarmanStepFn.apply(d, vy, vx, re, cfg, masks, info)
+    """One step on a one-workgroup grid.  density_grad=True (opt-in): the density output is differentiable too (KarmanStepFn's density
+    mode), taken when any of d, vy, vx requires a gradient.  re_grad=True (opt-in): a tensor `re` that requires a gradient receives one
+    (KarmanStepFn's re mode; grids with Y, X >= 16; composes with density_grad).  Without the flag `re` is data."""
+    differentiable, density, want_re = _step_mode(d, vy, vx, re, cfg, density_grad, re_grad)
+    if not differentiable:
+        return karman_step_saved(d, vy, vx, re, cfg, masks, None, info)[0]
+    _lib.require_gpu()
+    d, vy, vx, re = (_lib.f32(t) for t in (d, vy, vx, re))
+    return KarmanStepFn.apply(d, vy, vx, re, cfg, masks, None, info, density, want_re)
 
 
 # --------------------------------------------------------------------------------------
@@ -723,46 +650,6 @@ def circulant_diffusion_matrix(n, amount):
     return col[idx]
 
 
-class BurgersStepFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, vy, vx, fy, fx, cfg, circ):
-        _lib.require_gpu()
-        lib = _lib.load()
-        vy = _lib.f32(vy); vx = _lib.f32(vx)
-        fy = None if fy is None else _lib.f32(fy)
-        fx = None if fx is None else _lib.f32(fx)
-        oy = torch.empty_like(vy)
-        ox = torch.empty_like(vx)
-        check(lib.sol_burgers_step_fwd(C.byref(cfg), stream(), ptr(vy), ptr(vx), ptr(fy), ptr(fx),
-                                       ptr(circ[0]), ptr(circ[1]), ptr(circ[2]), ptr(circ[3]), ptr(oy), ptr(ox)))
-        ctx.save_for_backward(vy, vx)
-        ctx.cfg, ctx.circ, ctx.has_f = cfg, circ, fy is not None
-        return oy, ox
-
-    @staticmethod
-    def backward(ctx, gy, gx):
-        lib = _lib.load()
-        vy, vx = ctx.saved_tensors
-        cfg, circ = ctx.cfg, ctx.circ
-        gy = gy.contiguous(); gx = gx.contiguous()
-        oy = torch.empty_like(vy)
-        ox = torch.empty_like(vx)
-        check(lib.sol_burgers_step_bwd(C.byref(cfg), stream(), ptr(vy), ptr(vx),
-                                       ptr(circ[0]), ptr(circ[1]), ptr(circ[2]), ptr(circ[3]),
-                                       ptr(gy), ptr(gx), ptr(oy), ptr(ox)))
-        dt = cfg.dt
-        return oy, ox, (gy * dt if ctx.has_f else None), (gx * dt if ctx.has_f else None), None, None
-
-
-def burgers_circ(Y, X, amount, device="cuda"):
-    mk = lambda n: torch.as_tensor(circulant_diffusion_matrix(n, amount), dtype=torch.float32, device=device).contiguous()
-    return (mk(Y + 1), mk(X), mk(Y), mk(X + 1))
-
-
-def burgers_step(vy, vx, fy, fx, cfg, circ):
-    return BurgersStepFn.apply(vy, vx, fy, fx, cfg, circ)
-
-
 BURGERS_LDS_MAX = 64      # largest grid edge of the one-workgroup Burgers kernels
 
 
@@ -772,13 +659,16 @@ def burgers_large_workspace_bytes(cfg):
     return max(lib.sol_burgers_step_large_workspace_bytes(C.byref(cfg)), lib.sol_burgers_step_bwd_large_workspace_bytes(C.byref(cfg)))
 
 
-def _burgers_large_fwd(vy, vx, fy, fx, cfg, circ, workspace):
+def _burgers_fwd(vy, vx, fy, fx, cfg, circ, large, workspace):
+    """(vy, vx) after the step: sol_burgers_step_fwd, or (large) sol_burgers_step_fwd_large with its workspace"""
     lib = _lib.load()
-    workspace = _workspace(lib.sol_burgers_step_large_workspace_bytes(C.byref(cfg)), workspace, vy.device)
     oy, ox = torch.empty_like(vy), torch.empty_like(vx)
-    check(lib.sol_burgers_step_fwd_large(C.byref(cfg), stream(), ptr(vy), ptr(vx), ptr(fy), ptr(fx),
-                                         ptr(circ[0]), ptr(circ[1]), ptr(circ[2]), ptr(circ[3]), ptr(oy), ptr(ox),
-                                         ptr(workspace), workspace.numel() * 4))
+    head = (C.byref(cfg), stream(), ptr(vy), ptr(vx), ptr(fy), ptr(fx), ptr(circ[0]), ptr(circ[1]), ptr(circ[2]), ptr(circ[3]), ptr(oy), ptr(ox))
+    if large:
+        workspace = _workspace(lib.sol_burgers_step_large_workspace_bytes(C.byref(cfg)), workspace, vy.device)
+        check(lib.sol_burgers_step_fwd_large(*head, ptr(workspace), workspace.numel() * 4))
+    else:
+        check(lib.sol_burgers_step_fwd(*head))
     return oy, ox
 
 
@@ -793,39 +683,58 @@ def burgers_step_large_bwd(vy, vx, gy, gx, cfg, circ, workspace=None):
     return oy, ox
 
 
-class BurgersStepLargeFn(torch.autograd.Function):
-    """The large-grid Burgers step with its hand-written adjoint (sol_burgers_step_fwd_large / sol_burgers_step_bwd_large)."""
+class BurgersStepFn(torch.autograd.Function):
+    """The Burgers step with its hand-written adjoint: sol_burgers_step_fwd / sol_burgers_step_bwd on a one-workgroup grid, `large`:
+    sol_burgers_step_fwd_large / sol_burgers_step_bwd_large.  d f = dt * g."""
 
     @staticmethod
-    def forward(ctx, vy, vx, fy, fx, cfg, circ, workspace):
-        oy, ox = _burgers_large_fwd(vy, vx, fy, fx, cfg, circ, workspace)
+    def forward(ctx, vy, vx, fy, fx, cfg, circ, large, workspace):
+        oy, ox = _burgers_fwd(vy, vx, fy, fx, cfg, circ, large, workspace)
         ctx.save_for_backward(vy, vx)
-        ctx.cfg, ctx.circ, ctx.workspace, ctx.has_f = cfg, circ, workspace, fy is not None
+        ctx.cfg, ctx.circ, ctx.large, ctx.workspace, ctx.has_f = cfg, circ, large, workspace, fy is not None
+        ctx.set_materialize_grads(False)
         return oy, ox
 
     @staticmethod
     def backward(ctx, gy, gx):
         vy, vx = ctx.saved_tensors
-        gy = torch.zeros_like(vy) if gy is None else gy.contiguous()
+        cfg, circ = ctx.cfg, ctx.circ
+        gy = torch.zeros_like(vy) if gy is None else gy.contiguous()         # a missing cotangent counts as zero
         gx = torch.zeros_like(vx) if gx is None else gx.contiguous()
-        oy, ox = burgers_step_large_bwd(vy, vx, gy, gx, ctx.cfg, ctx.circ, ctx.workspace)
-        dt = ctx.cfg.dt
-        return oy, ox, (gy * dt if ctx.has_f else None), (gx * dt if ctx.has_f else None), None, None, None
+        if ctx.large:
+            oy, ox = burgers_step_large_bwd(vy, vx, gy, gx, cfg, circ, ctx.workspace)
+        else:
+            oy, ox = torch.empty_like(vy), torch.empty_like(vx)
+            check(_lib.load().sol_burgers_step_bwd(C.byref(cfg), stream(), ptr(vy), ptr(vx), ptr(circ[0]), ptr(circ[1]), ptr(circ[2]), ptr(circ[3]),
+                                                   ptr(gy), ptr(gx), ptr(oy), ptr(ox)))
+        return oy, ox, (gy * cfg.dt if ctx.has_f else None), (gx * cfg.dt if ctx.has_f else None), None, None, None, None
+
+
+def burgers_circ(Y, X, amount, device="cuda"):
+    mk = lambda n: torch.as_tensor(circulant_diffusion_matrix(n, amount), dtype=torch.float32, device=device).contiguous()
+    return (mk(Y + 1), mk(X), mk(Y), mk(X + 1))
+
+
+def _burgers_inputs(vy, vx, fy, fx):
+    _lib.require_gpu()
+    return _lib.f32(vy), _lib.f32(vx), None if fy is None else _lib.f32(fy), None if fx is None else _lib.f32(fx)
+
+
+def burgers_step(vy, vx, fy, fx, cfg, circ):
+    """Burgers step on a one-workgroup grid (edges up to BURGERS_LDS_MAX), differentiable through BurgersStepFn."""
+    return BurgersStepFn.apply(*_burgers_inputs(vy, vx, fy, fx), cfg, circ, False, None)
 
 
 def burgers_step_large(vy, vx, fy, fx, cfg, circ, workspace=None):
     """Burgers step for grids beyond the one-workgroup kernels (the reference's 128 x 128 data generation,
     /root/reference/burgers/Makefile:19-29): sol_burgers_step_fwd_large.  Returns (vy, vx) after the step.  When grad is enabled and an
-    input requires a gradient the call goes through BurgersStepLargeFn (same forward launches; the adjoint is
+    input requires a gradient the call goes through BurgersStepFn (same forward launches; the adjoint is
     sol_burgers_step_bwd_large, d f = dt * g); otherwise nothing is kept.  `workspace` (optional, fp32 words) serves both directions when
     it holds burgers_large_workspace_bytes(cfg)."""
-    _lib.require_gpu()
-    vy, vx = _lib.f32(vy), _lib.f32(vx)
-    fy = None if fy is None else _lib.f32(fy)
-    fx = None if fx is None else _lib.f32(fx)
+    vy, vx, fy, fx = _burgers_inputs(vy, vx, fy, fx)
     if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (vy, vx, fy, fx)):
-        return BurgersStepLargeFn.apply(vy, vx, fy, fx, cfg, circ, workspace)
-    return _burgers_large_fwd(vy, vx, fy, fx, cfg, circ, workspace)
+        return BurgersStepFn.apply(vy, vx, fy, fx, cfg, circ, True, workspace)
+    return _burgers_fwd(vy, vx, fy, fx, cfg, circ, True, workspace)
 
 
 class SplitFlatFn(torch.autograd.Function):

@@ -1,14 +1,13 @@
 """torch.library registration of the C-ABI ops: `torch.ops.sol.*` (north star: "exposed to Python
 through PyTorch-ROCm custom ops with a hand-written backward for each solver op").
 
-The ops call the same entry points of libsol_hip.so as ops.py (ctypes, raw device pointers; no torch types cross the C
-ABI) and carry the hand-written adjoints (sol_karman_step_bwd, sol_burgers_step_bwd / _bwd_large, sol_conv5x5 backward-data / -weight)
-through torch.library.register_autograd, so they compose with any other PyTorch op and show up in the dispatcher
-(torch.ops.sol.karman_step, .conv5x5, .burgers_step, .adam_tf_step; .karman_step_dens = karman_step with a differentiable density
-output, over sol_karman_density_bwd; .karman_step_re = karman_step differentiable with respect to re as well, over the _re adjoints).  Scene constants (masks, solver blobs, the cfg
-struct) are not tensors: they are registered once with register_scene() and referred to by an integer handle."""
-import ctypes as C
-
+The ops call the wrappers of ops.py (ctypes over libsol_hip.so, raw device pointers; no torch types cross the C ABI) and carry its
+hand-written adjoints (ops.KarmanStepFn, ops.BurgersStepFn, ops.Conv5x5Fn: sol_karman_step_bwd / _bwd_large, sol_burgers_step_bwd /
+_bwd_large, sol_conv5x5 backward-data / -weight) under the AutogradCUDA key, so they compose with any other PyTorch op and show up in the
+dispatcher (torch.ops.sol.karman_step, .conv5x5, .burgers_step, .adam_tf_step; .karman_step_dens = karman_step with a differentiable
+density output, over sol_karman_density_bwd; .karman_step_re = karman_step differentiable with respect to re as well, over the _re
+adjoints).  Scene constants (masks, solver blobs, the cfg struct) are not tensors: they are registered once with register_scene() and
+referred to by an integer handle."""
 import torch
 
 from . import _lib, ops
@@ -39,117 +38,47 @@ def register_scene(cfg, masks):
 
 def _karman_fwd_saved(d, vy, vx, re, scene):
     cfg, masks = _SCENES[scene]
-    lib = _lib.load()
-    d, vy, vx, re = (_lib.f32(t) for t in (d, vy, vx, re))
-    d_out, vy_out, vx_out = torch.empty_like(d), torch.empty_like(vy), torch.empty_like(vx)
-    svy, svx = torch.empty_like(vy), torch.empty_like(vx)
-    if masks.large:         # beyond the one-workgroup kernels: the multi-launch step of the scene's solver (direct or CG)
-        nbytes = ops.large_workspace_bytes(cfg, masks)
-        ws = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=vy.device)
-        cg_info = torch.empty(2, cfg.B, dtype=torch.int32, device=vy.device) if masks.direct is None else None
-        check(lib.sol_karman_step_fwd_large_saved(
-            C.byref(cfg), stream(), ptr(d), ptr(vy), ptr(vx), ptr(re), ptr(masks.active), ptr(masks.inflow), ptr(masks.velBCy),
-            ptr(masks.velBCyMask), masks.bc_stride, ptr(d_out), ptr(vy_out), ptr(vx_out), ptr(svy), ptr(svx),
-            ops._hdr(masks.direct_header), ptr(masks.box), ops._hdr(masks.box_header), ptr(cg_info), ptr(ws), ws.numel() * 4))
-        return d_out, vy_out, vx_out, svy, svx
-    check(lib.sol_karman_step_fwd(C.byref(cfg), stream(), ptr(d), ptr(vy), ptr(vx), ptr(re), ptr(masks.active), ptr(masks.inflow),
-                                  ptr(masks.velBCy), ptr(masks.velBCyMask), masks.bc_stride, ptr(d_out), ptr(vy_out), ptr(vx_out),
-                                  ptr(svy), ptr(svx), None, None, None))
-    return d_out, vy_out, vx_out, svy, svx
+    outs, svy, svx = ops.karman_step_saved(d, vy, vx, re, cfg, masks)
+    return (*outs, svy, svx)
 
 
 def _karman_bwd(svy, svx, re, gvy, gvx, scene):
     cfg, masks = _SCENES[scene]
-    lib = _lib.load()
-    gvy, gvx = gvy.contiguous(), gvx.contiguous()
-    if masks.large:
-        return ops.karman_step_large_bwd(svy.contiguous(), svx.contiguous(), _lib.f32(re), gvy, gvx, cfg, masks)
-    oy, ox = torch.empty_like(svy), torch.empty_like(svx)
-    check(lib.sol_karman_step_bwd(C.byref(cfg), stream(), ptr(svy), ptr(svx), ptr(re), ptr(masks.active), ptr(masks.velBCyMask),
-                                  masks.bc_stride, ptr(gvy), ptr(gvx), None, None, ptr(oy), ptr(ox), None))
-    return oy, ox
+    return ops._velocity_bwd(svy.contiguous(), svx.contiguous(), _lib.f32(re), gvy, gvx, cfg, masks, None)[:2]
 
 
-def _karman_step(d, vy, vx, re, scene):
+def _karman_density_bwd(d, svy, svx, re, gd, scene):
     cfg, masks = _SCENES[scene]
-    if masks.large:         # no gradient wanted: the plain forward entry points, nothing saved
-        with torch.no_grad():
-            return ops.karman_step_large(d, vy, vx, re, cfg, masks)
-    return _karman_fwd_saved(d, vy, vx, re, scene)[:3]
+    return ops.karman_density_bwd(d, svy, svx, re, gd, cfg, masks)
+
+
+def _karman_step(d, vy, vx, re, scene, density=False):
+    """no gradient wanted: the plain forward entry points, nothing kept"""
+    cfg, masks = _SCENES[scene]
+    with torch.no_grad():
+        return (ops.karman_step_large if masks.large else ops.karman_step)(d, vy, vx, re, cfg, masks)
 
 
 _LIB.impl("karman_step_fwd_saved", _karman_fwd_saved, "CUDA")
 _LIB.impl("karman_step_bwd", _karman_bwd, "CUDA")
-_LIB.impl("karman_step", _karman_step, "CUDA")
-
-
-class _KarmanFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, d, vy, vx, re, scene):
-        d_out, vy_out, vx_out, svy, svx = torch.ops.sol.karman_step_fwd_saved(d, vy, vx, re, scene)
-        ctx.save_for_backward(svy, svx, re)
-        ctx.scene = scene
-        ctx.mark_non_differentiable(d_out)
-        return d_out, vy_out, vx_out
-
-    @staticmethod
-    def backward(ctx, _gd, gvy, gvx):
-        svy, svx, re = ctx.saved_tensors
-        gvy = torch.zeros_like(svy) if gvy is None else gvy
-        gvx = torch.zeros_like(svx) if gvx is None else gvx
-        oy, ox = torch.ops.sol.karman_step_bwd(svy, svx, re, gvy, gvx, ctx.scene)
-        return None, oy, ox, None, None
-
-
-_LIB.impl("karman_step", lambda d, vy, vx, re, scene: _KarmanFn.apply(d, vy, vx, re, scene), "AutogradCUDA")
-
-
-# karman_step with a differentiable density output (opt-in; karman_step itself keeps the density out of the graph)
-def _karman_density_bwd(d, svy, svx, re, gd, scene):
-    cfg, masks = _SCENES[scene]
-    return ops.karman_density_bwd(d, svy.contiguous(), svx.contiguous(), re, gd.contiguous(), cfg, masks)
-
-
 _LIB.impl("karman_density_bwd", _karman_density_bwd, "CUDA")
-_LIB.impl("karman_step_dens", _karman_step, "CUDA")
 
 
-class _KarmanDensFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, d, vy, vx, re, scene):
-        d = _lib.f32(d)
-        d_out, vy_out, vx_out, svy, svx = torch.ops.sol.karman_step_fwd_saved(d, vy, vx, re, scene)
-        ctx.save_for_backward(d, svy, svx, re)
-        ctx.scene = scene
-        ctx.set_materialize_grads(False)
-        return d_out, vy_out, vx_out
-
-    @staticmethod
-    def backward(ctx, gd, gvy, gvx):
-        d, svy, svx, re = ctx.saved_tensors
-        od = oy = ox = None
-        if gvy is not None or gvx is not None:        # a density-only loss does not pay for the pressure solve
-            gvy = torch.zeros_like(svy) if gvy is None else gvy
-            gvx = torch.zeros_like(svx) if gvx is None else gvx
-            oy, ox = torch.ops.sol.karman_step_bwd(svy, svx, re, gvy, gvx, ctx.scene)
-        if gd is not None:
-            cfg, masks = _SCENES[ctx.scene]
-            od, oy, ox = ops.karman_density_bwd(d, svy, svx, re, gd.contiguous(), cfg, masks, oy, ox)      # added onto the velocity adjoint's result
-        return od, oy, ox, None, None
-
-
-_LIB.impl("karman_step_dens", lambda d, vy, vx, re, scene: _KarmanDensFn.apply(d, vy, vx, re, scene), "AutogradCUDA")
-
-
-# karman_step differentiable with respect to re too (opt-in; in karman_step and karman_step_dens re is data); density: d_out stays in the
-# graph as in karman_step_dens.  The autograd.Function of ops.py is the hand-written forward + backward pair (grids with Y, X >= 16)
-def _karman_step_re(d, vy, vx, re, scene, density=False):
+# the step's three differentiable forms are the modes of ops.KarmanStepFn, the hand-written forward + backward pair: karman_step (the
+# density is a passive tracer, re is data), karman_step_dens (opt-in: the density output is differentiable too) and karman_step_re
+# (opt-in: differentiable with respect to re as well, grids with Y, X >= 16; density: d_out stays in the graph as in karman_step_dens)
+def _karman_fn(d, vy, vx, re, scene, density, want_re):
     cfg, masks = _SCENES[scene]
-    return ops.KarmanStepReFn.apply(d, vy, vx, re, cfg, masks, None, None, bool(density))
+    if want_re:
+        ops._require_staged(cfg, "re_grad")
+    return ops.KarmanStepFn.apply(d, vy, vx, re, cfg, masks, None, None, density, want_re)
 
 
-_LIB.impl("karman_step_re", lambda d, vy, vx, re, scene, density=False: _karman_step(d, vy, vx, re, scene), "CUDA")
-_LIB.impl("karman_step_re", _karman_step_re, "AutogradCUDA")
+for _op in ("karman_step", "karman_step_dens", "karman_step_re"):
+    _LIB.impl(_op, _karman_step, "CUDA")
+_LIB.impl("karman_step", lambda d, vy, vx, re, scene: _karman_fn(d, vy, vx, re, scene, False, False), "AutogradCUDA")
+_LIB.impl("karman_step_dens", lambda d, vy, vx, re, scene: _karman_fn(d, vy, vx, re, scene, True, False), "AutogradCUDA")
+_LIB.impl("karman_step_re", lambda d, vy, vx, re, scene, density=False: _karman_fn(d, vy, vx, re, scene, bool(density), True), "AutogradCUDA")
 
 # conv / burgers: the autograd.Functions of ops.py already are the hand-written forward + backward pairs
 _LIB.impl("conv5x5", lambda x, w, b, residual, lrelu, slope: ops.Conv5x5Fn.apply(x, w, b, residual, lrelu, slope), "AutogradCUDA")
@@ -161,7 +90,7 @@ def _burgers(vy, vx, fy, fx, dx, dt, nu):
     circ = ops.burgers_circ(Yp1 - 1, X, dt * nu, vy.device)
     if max(Yp1 - 1, X) > ops.BURGERS_LDS_MAX:       # beyond the one-workgroup kernels: the multi-launch step and its adjoint
         return ops.burgers_step_large(vy, vx, fy, fx, cfg, circ)
-    return ops.BurgersStepFn.apply(vy, vx, fy, fx, cfg, circ)
+    return ops.burgers_step(vy, vx, fy, fx, cfg, circ)
 
 
 _LIB.impl("burgers_step", _burgers, "AutogradCUDA")

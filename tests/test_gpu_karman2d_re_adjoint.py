@@ -44,7 +44,7 @@ def saved(st, cfg, mk):
     """(d, vy, vx, re) on the device and the saved post-diffusion velocity of the forward step"""
     h = tuple(f32(t) for t in st)
     with torch.no_grad():
-        _, svy, svx = ops.karman_step_large_saved(*h, cfg, mk) if mk.large else ops._step_fwd_saved(*h, cfg, mk, None)
+        _, svy, svx = ops.karman_step_saved(*h, cfg, mk)
     return h, svy, svx
 
 
@@ -269,8 +269,9 @@ def test_torch_op_equals_the_ops_path_and_the_defaults_did_not_move(Y, X, B):
     # the flag off: re is data, and the step's results are the same launches' bits
     hs = leaves(st)
     plain = step_ops(*hs, cfg, mk)
-    loss_of(plain, w, "velocity").backward()
-    torch.cuda.synchronize()
+    with _lib.profile() as plain_launches:
+        loss_of(plain, w, "velocity").backward()
+        torch.cuda.synchronize()
     assert hs[3].grad is None and hs[1].grad is not None
     for a, b in zip(plain, oa):
         assert torch.equal(a.detach(), b.detach())
@@ -283,7 +284,16 @@ def test_torch_op_equals_the_ops_path_and_the_defaults_did_not_move(Y, X, B):
     assert hf[3].grad is None and torch.equal(hf[1].grad, hs[1].grad)
     # re_grad with an re that requires no gradient: the plain path
     hn = leaves(st[:3]) + (f32(st[3]),)
-    assert type(step_ops(*hn, cfg, mk, re_grad=True)[1].grad_fn).__name__.startswith("KarmanStep" + ("Large" if mk.large else "") + "Fn")
+    out = step_ops(*hn, cfg, mk, re_grad=True)
+    assert len(out[1].grad_fn.saved_tensors) == 3
+    with _lib.profile() as p:
+        loss_of(out, w, "velocity").backward()
+        torch.cuda.synchronize()
+    launches = {k.strip("()"): v[0] for k, v in p.kernels.items()}
+    has = lambda prefix: any(k.startswith(prefix) for k in launches)
+    assert launches == {k.strip("()"): v[0] for k, v in plain_launches.kernels.items()}, launches
+    assert not has("k_re_") and has("k_lb_") == mk.large and has("k_karman_bwd") == (not mk.large), launches
+    assert hn[3].grad is None and torch.equal(hn[1].grad, hs[1].grad) and torch.equal(hn[2].grad, hs[2].grad)
 
 
 # ---- 6. identification ------------------------------------------------------------------------------------------------------------------

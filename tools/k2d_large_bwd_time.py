@@ -4,7 +4,7 @@ profiles/k2d_large_bwd_time.json.
 
 At 256 x 128, B = 1 and 6, for the default sphere (direct solve) and two cylinders in tandem (CG solve), all in ONE process and on a
 spun-up state: the plain forward step in us (ops.karman_step_large under no_grad: the launch sequence of the data-generation path,
-the yardstick), the forward step that keeps the post-diffusion velocity (KarmanStepLargeFn.forward), the adjoint alone
+the yardstick), the forward step that keeps the post-diffusion velocity (KarmanStepFn.forward, ops.karman_step_saved), the adjoint alone
 (ops.karman_step_large_bwd on the saved state with a fixed random cotangent), with both scatter forms (LDS tile window, option
 k2d_adj_tile = 1, and global atomics only), HIP events around eager calls; the CG iterations of both solves; and the adjoint's
 kernel split (sol_prof_begin / sol_prof_end: per-kernel device time summed over the repetitions, us per call of the adjoint).

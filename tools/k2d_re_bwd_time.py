@@ -64,7 +64,7 @@ def scene(Y, X, B):
     gen = torch.Generator().manual_seed(1)
     rn = lambda *s: torch.randn(*s, generator=gen)
     st = (torch.rand(B, Y, X, generator=gen).to(DEV), (1.0 + 0.1 * rn(B, Y + 1, X)).to(DEV), (0.1 * rn(B, Y, X + 1)).to(DEV))
-    fwd = (lambda *s: ops.karman_step_large_saved(*s, re, cfg, mk)) if mk.large else (lambda *s: ops._step_fwd_saved(*s, re, cfg, mk, None))
+    fwd = lambda *s: ops.karman_step_saved(*s, re, cfg, mk)
     with torch.no_grad():
         st = fwd(*st)[0]                  # spun-up state
         st = fwd(*st)[0]
