@@ -451,7 +451,11 @@ int sol_conv5x5_cols(void* stream, const float* x, const float* packed, const fl
  * caller zeroes once and may reuse to ACCUMULATE over many calls (the unrolled steps share
  * the weights); sol_conv5x5_bwd_weight_reduce() folds it into dw/db.
  * W: 4 <= W <= 64 with W % 4 == 0, or a multiple of 64 (W / 64 column tiles per row block, each
- * with its own slice of `partial`: the workspace grows by that factor).                    */
+ * with its own slice of `partial`: the workspace grows by that factor).
+ * THE REDUCE FOLDS IN PLACE: despite the `const`, sol_conv5x5_bwd_weight_reduce (and _reduce_jobs, and
+ * sol_conv5x5_bwd_weight_segments_reduce) write chunk sums of 16 row blocks back into `partial` whenever it
+ * holds more than 16 blocks.  After a reduce the contents of `partial` are unspecified: zero it (or launch
+ * with overwrite) before the next accumulation, and reduce a copy if the partial sums are still needed. */
 size_t sol_conv5x5_bwd_weight_ws_floats(int32_t B, int32_t H, int32_t W, int32_t cin, int32_t cout);
 int sol_conv5x5_bwd_weight(void* stream, const float* x, const float* dz, float* partial,
                            int32_t B, int32_t H, int32_t W, int32_t cin, int32_t cout);
@@ -463,6 +467,29 @@ int sol_conv5x5_bwd_weight_reduce(void* stream, const float* partial, float* dw_
  * db[k] may point into a flat gradient buffer (Keras get_weights() order).  cin[k] = real input channels of layer k.            */
 int sol_conv5x5_bwd_weight_reduce_jobs(void* stream, int32_t n, float* const* partial, float* const* dw_hwio, float* const* db,
                                        int32_t B, int32_t H, int32_t W, const int32_t* cin, const int32_t* cout, int32_t accumulate);
+
+/* The scaled, segmented form that the fused trainers launch, W <= 64: `nseg` tensors of [B,H,W,c] (the unrolled steps of one layer)
+ * in ONE launch.  Segment s reads x + s * x_seg and dz + s * dz_seg (strides in floats); the rows of all segments form one sequence
+ * of nseg * B * H rows that is cut into row blocks of 8 rows, or of ceil(rows / 256) rows (ceil(rows / 1024) for cin == 4 or
+ * cout == 2) beyond 4096 rows.  `partial`: sol_conv5x5_bwd_weight_segments_ws_floats() floats.
+ *   overwrite  1: every word of `partial` that the reduce reads is stored (no zeroing needed); 0: added to, as sol_conv5x5_bwd_weight.
+ *   x_absmax / dz_absmax (both or NULL): SOL_ABSMAX_SLOTS slots per segment, segment s at x_absmax + s * absmax_seg (uint32 words).
+ *              With both given, (cin, cout) == (32, 32), W == 64, conv_precision 0 and B * H a multiple of the row block, the products
+ *              are three fp16 MFMA products of operands scaled PER SEGMENT; a row block that would hold rows of two segments takes
+ *              the six-product bf16 body instead, which reads no slots.  Slots may over-report the maximum: that costs fp16 range, not
+ *              mantissa bits (elements below 2^-19 of the REPORTED maximum lose their low part); slots that under-report it
+ *              overflow fp16.
+ *   cin_real   1..3 with cin == 4, cout == 32, W == 64: the channels of x beyond cin_real are zero padding and their gradient rows
+ *              are NOT computed (nor stored under overwrite): reduce with cin = cin_real.  0: all cin channels are data.
+ * Rejected before any launch: nseg < 1, W > 64, and everything sol_conv5x5_bwd_weight rejects.
+ * sol_conv5x5_bwd_weight_segments_reduce: partial -> dw_hwio [5,5,cin,cout], db [cout] for the same (nseg, B, H); cin = real input
+ * channels (1..32).  Folds in place (see above). */
+size_t sol_conv5x5_bwd_weight_segments_ws_floats(int32_t nseg, int32_t B, int32_t H, int32_t cin, int32_t cout);
+int sol_conv5x5_bwd_weight_segments(void* stream, const float* x, const float* dz, float* partial, int32_t nseg, int64_t x_seg, int64_t dz_seg,
+                                    int32_t overwrite, int32_t B, int32_t H, int32_t W, int32_t cin, int32_t cout,
+                                    const uint32_t* x_absmax, const uint32_t* dz_absmax, int64_t absmax_seg, int32_t cin_real);
+int sol_conv5x5_bwd_weight_segments_reduce(void* stream, float* partial, float* dw_hwio, float* db, int32_t nseg, int32_t B, int32_t H,
+                                           int32_t cin, int32_t cout, int32_t accumulate);
 
 /* ------------------------------------------------------------------------------------
  * Whole training step: the unrolled msteps graph of karman_train.py:397-457

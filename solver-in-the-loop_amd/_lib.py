@@ -104,6 +104,9 @@ _SIGS = {
     "sol_conv5x5_bwd_weight_ws_floats": (C.c_size_t, [C.c_int32] * 5),
     "sol_conv5x5_bwd_weight": (C.c_int, [_P] * 4 + [C.c_int32] * 5),
     "sol_conv5x5_bwd_weight_reduce": (C.c_int, [_P] * 4 + [C.c_int32] * 6),
+    "sol_conv5x5_bwd_weight_segments_ws_floats": (C.c_size_t, [C.c_int32] * 5),
+    "sol_conv5x5_bwd_weight_segments": (C.c_int, [_P] * 4 + [C.c_int32, C.c_int64, C.c_int64] + [C.c_int32] * 6 + [_P, _P, C.c_int64, C.c_int32]),
+    "sol_conv5x5_bwd_weight_segments_reduce": (C.c_int, [_P] * 4 + [C.c_int32] * 6),
     "sol_train_workspace_bytes": (C.c_size_t, [C.POINTER(TrainCfg)]),
     "sol_train_fwd_bwd": (C.c_int, [C.POINTER(TrainCfg), _P] + [_P] * 9 + [C.c_int64] + [_P] * 3 + [C.c_size_t] + [_P] * 7),
     "sol_train_graph_create": (C.c_int, [C.POINTER(TrainCfg)] + [_P] * 9 + [C.c_int64] + [_P] * 3 + [C.c_size_t] + [_P] * 7 + [C.POINTER(C.c_void_p)]),

@@ -165,6 +165,9 @@ def _check_net_shape(who, Y, X, any_width=False):
         if Y < 2 or X < 2 or max(Y, X) > 1024:
             raise _lib.SolError("%s: resolution %dx%d is not supported: 2 <= Y, X <= 1024" % (who, Y, X))
         return
+    if X < 4:       # 64 % 2 == 0, but sol_conv5x5 and sol_conv5x5_bwd_weight take rows of at least 4 cells
+        raise _lib.SolError("%s: resolution %dx%d is not supported: the network's convolutions take rows of at least 4 cells (X = %d); "
+                            "any_width=True runs narrower rows in pitched form" % (who, Y, X, X))
     if not ((X <= 64 and 64 % X == 0 and Y % (64 // X) == 0) or (X > 64 and X % 64 == 0)) or Y < 2 or X < 2 or max(Y, X) > 1024:
         raise _lib.SolError("%s: resolution %dx%d is not supported: the network's convolutions take rows of X <= 64 cells with 64 %% X == 0 "
                             "and Y %% (64 / X) == 0, or rows wider than 64 cells that are a multiple of 64 cells wide; 2 <= Y, X <= 1024"

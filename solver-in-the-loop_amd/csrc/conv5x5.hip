@@ -1667,6 +1667,32 @@ extern "C" int sol_conv5x5_bwd_weight_reduce_jobs(void* stream, int32_t n, float
     return sol_bww_reduce_layers(stream, n, partial, dw_hwio, db, rows, rb, ci, co, accumulate, 0, bww_tiles(W));
 }
 
+// ---- the scaled, segmented launch of the trainers through the C ABI (include/sol_hip.h): forwarders, no kernel or caller of their own ----
+extern "C" size_t sol_conv5x5_bwd_weight_segments_ws_floats(int32_t nseg, int32_t B, int32_t H, int32_t cin, int32_t cout) {
+    if (nseg < 1 || B < 1 || H < 1) return 0;
+    return sol_bww_batched_ws_floats(nseg, B, H, cin, cout);
+}
+
+extern "C" int sol_conv5x5_bwd_weight_segments(void* stream, const float* x, const float* dz, float* partial, int32_t nseg, int64_t x_seg, int64_t dz_seg,
+                                               int32_t overwrite, int32_t B, int32_t H, int32_t W, int32_t cin, int32_t cout,
+                                               const uint32_t* x_absmax, const uint32_t* dz_absmax, int64_t absmax_seg, int32_t cin_real) {
+    SOL_REQUIRE(nseg >= 1, "sol_conv5x5_bwd_weight_segments: nseg must be at least 1 (got %d)", nseg);
+    SOL_REQUIRE(W <= 64, "sol_conv5x5_bwd_weight_segments: the segmented form takes rows of W <= 64 pixels (got W = %d)", W);
+    SOL_REQUIRE(x_seg >= 0 && dz_seg >= 0 && absmax_seg >= 0, "sol_conv5x5_bwd_weight_segments: negative segment stride");
+    SOL_REQUIRE(cin_real >= 0 && cin_real <= cin, "sol_conv5x5_bwd_weight_segments: cin_real must lie in [0, cin] (got %d, cin = %d)", cin_real, cin);
+    return sol_bww_batched(stream, x, dz, partial, nseg, nseg, overwrite ? 1 : 0, (long)x_seg, (long)dz_seg, B, H, W, cin, cout,
+                           x_absmax, dz_absmax, (long)absmax_seg, (long)absmax_seg, cin_real);
+}
+
+extern "C" int sol_conv5x5_bwd_weight_segments_reduce(void* stream, float* partial, float* dw_hwio, float* db, int32_t nseg, int32_t B, int32_t H,
+                                                      int32_t cin, int32_t cout, int32_t accumulate) {
+    SOL_REQUIRE(partial && dw_hwio && db, "sol_conv5x5_bwd_weight_segments_reduce: NULL pointer");
+    SOL_REQUIRE(nseg >= 1 && B >= 1 && H >= 1, "sol_conv5x5_bwd_weight_segments_reduce: nseg, B, H must be at least 1 (got %d, %d, %d)", nseg, B, H);
+    float* parts[1] = {partial}; float* dws[1] = {dw_hwio}; float* dbs[1] = {db};
+    const int rows[1] = {nseg * B * H}, rbs[1] = {0}, ci[1] = {cin}, co[1] = {cout};
+    return sol_bww_reduce_layers(stream, 1, parts, dws, dbs, rows, rbs, ci, co, accumulate, 0, 1);
+}
+
 int sol_bww_step_reduce(void* stream, const float* partial, float* dw_hwio, float* db, int B, int H, int rb, int cin, int cout, int accumulate) {
     return bww_reduce(stream, partial, dw_hwio, db, B * H, rb, cin, cout, accumulate);
 }
