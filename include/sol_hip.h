@@ -81,6 +81,9 @@ int sol_abi_sizes(int32_t* karman_cfg, int32_t* burgers_cfg, int32_t* train_cfg)
  *   k2d_dens_adj_tile (1) karman-2d, any grid: the density adjoint's fixed-point scatter (sol_karman_density_bwd) goes through an int64 LDS window per
  *                       workgroup (16 x 16 cells + halo 4), flushed with one global atomic per non-zero cell; 0: every contribution is a global atomic.
  *                       Same results bit for bit
+ *   k3d_dens_adj_tile (1) karman-3d: the density adjoint's fixed-point scatter (sol_karman3d_density_bwd) goes through an int64 LDS window per
+ *                       workgroup (4 x 4 columns + halo 2, all k), flushed with one global atomic per non-zero cell; 0, or a window beyond
+ *                       64 KB (Z > 128): every contribution is a global atomic.  Same results bit for bit
  *   k3d_conv_persist (0) karman-3d: 1 = the one-launch Conv3D kernel as 256 workgroups of consecutive eight-row tiles (the next tile's rows and weight
  *                       sets requested during the last tap rows of the tile) when the tile count is a multiple of 256; same results bit for bit,
  *                       measured slower (register spills), kept as a tested experiment
@@ -674,6 +677,50 @@ int sol_karman3d_step_bwd(const sol_karman3d_cfg* cfg, void* stream,
                           const float* g_vy_out, const float* g_vx_out, const float* g_vz_out,
                           float* g_vy_in, float* g_vx_in, float* g_vz_in,
                           const int32_t* direct_header_host, void* workspace, size_t workspace_bytes);
+/* Adjoint of the 3-D step's marker DENSITY (csrc/karman3d_density_bwd.hip; Y, X, Z >= 8, even face count, B <= 65535): the 3-D twin of
+ * sol_karman_density_bwd, a separate set of launches (no pressure solve) that a caller adds when its loss looks at the density.  It needs
+ * the step's input density d_in [B,Y,X,Z], the saved post-diffusion velocity of the forward step and g_d_out [B,Y,X,Z]; `inflow` [Y,X,Z]
+ * is read only with cfg.inflow_before (the advected field is then d_in + inflow) and may be NULL otherwise.  Per cell, c = saved velocity,
+ * g = g_d_out there: the centre velocity is the mean of the two faces per axis, o = -u dt/dx, f = floor(o), w = o - f;
+ *     g_d_in[cell + f + corner] += w(corner) g   inside the grid (the zero ghost ring takes nothing)
+ *     gU_a[cell] = -dt/dx g d(sample)/d(offset_a)   for the three axes, with the trilinear slopes of the gathered field
+ *   then g_c = the cell-to-face transpose of gU (a face takes half of each adjacent cell, out-of-range cells zero) and
+ *     g_vy_in = (I + alpha L^T)((1 - velBCyMask) g_cy),  g_vx_in = (I + alpha L^T) g_cx,  g_vz_in = (I + alpha L^T) g_cz,  alpha = dt res^2 / re[b]
+ * with the replicate-padded 7-point Laplacian.  The scatter into g_d_in is 64-bit fixed point (order independent: results are
+ * bit-reproducible; LDS window per tile of 4 x 4 columns, option k3d_dens_adj_tile), scaled by max|g_d_out| of the simulation; a non-finite
+ * g_d_out makes EVERY gradient of that simulation NaN.  g_d_in is written.  accumulate = 0: g_v*_in are written; accumulate = 1: the
+ * density's part is ADDED onto them (the velocity adjoint wrote there first; one fp32 add per face, deterministic).  Outputs must not alias
+ * inputs or each other.  Kernel launches only: capturable.  `workspace`: DEVICE scratch of sol_karman3d_density_bwd_workspace_bytes(cfg)
+ * bytes, 16-byte aligned. */
+size_t sol_karman3d_density_bwd_workspace_bytes(const sol_karman3d_cfg* cfg);
+int sol_karman3d_density_bwd(const sol_karman3d_cfg* cfg, void* stream,
+                             const float* d_in, const float* inflow, const float* saved_vy, const float* saved_vx, const float* saved_vz,
+                             const float* re, const float* velBCyMask, int64_t bc_batch_stride,
+                             const float* g_d_out, float* g_d_in, float* g_vy_in, float* g_vx_in, float* g_vz_in, int accumulate,
+                             void* workspace, size_t workspace_bytes);
+/* Gradient of the 3-D step with respect to the REYNOLDS NUMBER (csrc/karman3d_re_bwd.hip), as the 2-D _re forms: with g' the cotangent of
+ * u = v_in + alpha L v_in -- the velocity adjoint's g_c ((1 - velBCyMask) g_c on v_y), the density adjoint's cell-to-face transpose of gU --
+ *     g_re[b] = -(dt res^2 / re[b]^2) * sum over the faces of v_y, v_x and v_z of  g'_e (L v_in)_e
+ * The _re forms take every argument of the plain call and, after `workspace_bytes`, the step's INPUT velocity vy_in / vx_in / vz_in (not
+ * the saved post-diffusion one), g_re [B] and accumulate_re (0: g_re is written; 1: added onto with one fp32 add).  They issue the plain
+ * call's launches (the other gradients are the plain call's bits) and two more: fp32 terms, fp64 products and sums in a fixed order whose
+ * workgroup count depends on the grid alone, no floating-point atomics.  A non-finite cotangent of simulation b makes g_re[b] NaN.  The
+ * workspace is the plain call's plus the partial sums.  v*_in / g_re must not alias an output / an input.  Capturable. */
+size_t sol_karman3d_step_bwd_re_workspace_bytes(const sol_karman3d_cfg* cfg);
+int sol_karman3d_step_bwd_re(const sol_karman3d_cfg* cfg, void* stream,
+                             const float* saved_vy, const float* saved_vx, const float* saved_vz,
+                             const float* re, const float* active, const float* velBCyMask, int64_t bc_batch_stride,
+                             const float* g_vy_out, const float* g_vx_out, const float* g_vz_out,
+                             float* g_vy_in, float* g_vx_in, float* g_vz_in,
+                             const int32_t* direct_header_host, void* workspace, size_t workspace_bytes,
+                             const float* vy_in, const float* vx_in, const float* vz_in, float* g_re, int accumulate_re);
+size_t sol_karman3d_density_bwd_re_workspace_bytes(const sol_karman3d_cfg* cfg);
+int sol_karman3d_density_bwd_re(const sol_karman3d_cfg* cfg, void* stream,
+                                const float* d_in, const float* inflow, const float* saved_vy, const float* saved_vx, const float* saved_vz,
+                                const float* re, const float* velBCyMask, int64_t bc_batch_stride,
+                                const float* g_d_out, float* g_d_in, float* g_vy_in, float* g_vx_in, float* g_vz_in, int accumulate,
+                                void* workspace, size_t workspace_bytes,
+                                const float* vy_in, const float* vx_in, const float* vz_in, float* g_re, int accumulate_re);
 /* The step's pressure solve alone: M p = rhs with M = -A for the scene's `active` mask (the solver cfg->pressure_solver selects;
  * the CG solve reports to cfg->cg_info).  rhs, p [B,Y,X,Z] (rhs is read only); workspace: sol_karman3d_step_workspace_bytes(cfg). */
 int sol_karman3d_pressure_solve(const sol_karman3d_cfg* cfg, void* stream, const float* active, const float* rhs, float* p,

@@ -274,6 +274,8 @@ struct SolOptions {
     int k2d_dens_adj_tile;// 1 (default): the karman-2d density adjoint (karman_density_bwd.hip) scatters its field term into an int64 LDS window per 16 x 16-cell
                           //    tile (k_kd_advect_adj_tile); 0: global atomics only (k_kd_advect_adj).  Same results bit for bit
     int k3d_tile;         // 1: karman-3d advection from LDS tiles holding the full z column + halo; 0 (default, measured faster at B <= 2): wave-per-column gathers from global memory
+    int k3d_dens_adj_tile;// 1 (default): the karman-3d density adjoint (karman3d_density_bwd.hip) scatters its field term into an int64 LDS window per tile of
+                          //    4 x 4 columns (k3d_advect_adj_tile); 0: global atomics only (k3d_advect_adj).  Same results bit for bit
 };
 SolOptions& sol_opt();
 

@@ -20,8 +20,11 @@
 //                   correction of the obstacle cells (precond3d.direct_solver_blob3d): 12 transform passes + k3_capacitance
 //   k3_project      v -= mask * grad p, fused to_feature (4 channels: three components + Re)
 // The adjoint of the step (sol_karman3d_step_bwd: k3b_* kernels, second half of this file) reverses these stages; its
-// advection scatter runs in 64-bit fixed point and is bit-reproducible.
+// advection scatter runs in 64-bit fixed point and is bit-reproducible.  sol_karman3d_step_bwd_re: the same launches, then the gradient
+// with respect to the Reynolds number from the g_c they leave behind (karman3d_re_bwd.hip).  The adjoint of the marker density is a set
+// of launches of its own (karman3d_density_bwd.hip).
 #include "fixed_scatter.hpp"
+#include "karman3d_re.hpp"
 
 namespace {
 
@@ -1141,18 +1144,34 @@ extern "C" size_t sol_karman3d_step_bwd_workspace_bytes(const sol_karman3d_cfg* 
     return floats * sizeof(float) + k3_pcg_workspace_bytes(c);
 }
 
-extern "C" int sol_karman3d_step_bwd(const sol_karman3d_cfg* c, void* stream,
-                                     const float* saved_vy, const float* saved_vx, const float* saved_vz,
-                                     const float* re, const float* active, const float* velBCyMask, int64_t bc_batch_stride,
-                                     const float* g_vy_out, const float* g_vx_out, const float* g_vz_out,
-                                     float* g_vy_in, float* g_vx_in, float* g_vz_in,
-                                     const int32_t* direct_header_host, void* workspace, size_t workspace_bytes) {
+namespace {
+
+// the launches of sol_karman3d_step_bwd; with rx, followed by the Reynolds-number reduction over the fixed-point g_c they leave in the
+// workspace (sol_karman3d_step_bwd_re; k3b_diffuse_adj only reads g_c): g_v*_in are the same launches' results either way
+int step_bwd3d(const char* who, const sol_karman3d_cfg* c, void* stream,
+               const float* saved_vy, const float* saved_vx, const float* saved_vz,
+               const float* re, const float* active, const float* velBCyMask, int64_t bc_batch_stride,
+               const float* g_vy_out, const float* g_vx_out, const float* g_vz_out,
+               float* g_vy_in, float* g_vx_in, float* g_vz_in,
+               const int32_t* direct_header_host, void* workspace, size_t workspace_bytes, const Re3Extra* rx) {
     SOL_REQUIRE(c != nullptr, "cfg is NULL");
-    SOL_REQUIRE(c->B >= 1 && c->Y >= 8 && c->X >= 8 && c->Z >= 8 && c->B <= 65535, "sol_karman3d_step_bwd: B >= 1, Y, X, Z >= 8");
+    SOL_REQUIRE(c->B >= 1 && c->Y >= 8 && c->X >= 8 && c->Z >= 8 && c->B <= 65535, "%s: B >= 1, Y, X, Z >= 8", who);
     SOL_REQUIRE(saved_vy && saved_vx && saved_vz && re && active && velBCyMask && g_vy_out && g_vx_out && g_vz_out && g_vy_in && g_vx_in && g_vz_in && workspace,
-                "sol_karman3d_step_bwd: NULL pointer argument");
+                "%s: NULL pointer argument", who);
+    SOL_REQUIRE(!rx || (rx->vy_in && rx->vx_in && rx->vz_in && rx->g_re), "%s: NULL pointer argument", who);
     if (int e = check_blob3d(c, direct_header_host)) return e;
-    SOL_REQUIRE(workspace_bytes >= sol_karman3d_step_bwd_workspace_bytes(c), "workspace too small");
+    const size_t plain_bytes = sol_karman3d_step_bwd_workspace_bytes(c);
+    SOL_REQUIRE(workspace_bytes >= plain_bytes + (rx ? sol_re3_partial_bytes(c) : 0), "workspace too small");
+    if (rx) {
+        const void* outs[] = {g_vy_in, g_vx_in, g_vz_in};
+        const void* ins[] = {rx->vy_in, rx->vx_in, rx->vz_in};
+        for (const void* o : outs) {
+            SOL_REQUIRE(o != (const void*)rx->g_re, "%s: g_re must be a buffer of its own", who);
+            for (const void* i : ins) SOL_REQUIRE(o != i, "%s: outputs must not alias the inputs", who);
+        }
+        for (const void* i : ins) SOL_REQUIRE(i != (const void*)rx->g_re, "%s: outputs must not alias the inputs", who);
+        SOL_REQUIRE((const void*)rx->g_re != (const void*)re, "%s: outputs must not alias the inputs", who);
+    }
     const int B = c->B, Y = c->Y, X = c->X, Z = c->Z, N = Y * X * Z;
     hipStream_t s = (hipStream_t)stream;
     const size_t nVy = (size_t)(Y + 1) * X * Z, nVx = (size_t)Y * (X + 1) * Z, nVz = (size_t)Y * X * (Z + 1), faces = nVy + nVx + nVz;
@@ -1161,9 +1180,9 @@ extern "C" int sol_karman3d_step_bwd(const sol_karman3d_cfg* c, void* stream,
     a.B = B; a.Y = Y; a.X = X; a.Z = Z; a.dtdx = c->dt / c->dx; a.adt = c->dt * c->res * c->res; a.grad_pad = c->grad_pad;
     a.re = re; a.active = active; a.bcm = velBCyMask; a.bc_stride = bc_batch_stride;
     a.svy = saved_vy; a.svx = saved_vx; a.svz = saved_vz; a.goy = g_vy_out; a.gox = g_vx_out; a.goz = g_vz_out;
-    SOL_REQUIRE(faces % 2 == 0, "sol_karman3d_step_bwd: odd face count (%zu): even X, Z expected", faces);
+    SOL_REQUIRE(faces % 2 == 0, "%s: odd face count (%zu): even X, Z expected", who, faces);
     // per-simulation layout of g_c: [b][y faces | x faces | z faces] int64 -- k3b_rhs clears simulation b's block
-    SOL_REQUIRE(reinterpret_cast<uintptr_t>(workspace) % 16 == 0, "sol_karman3d_step_bwd: workspace must be 16-byte aligned");
+    SOL_REQUIRE(reinterpret_cast<uintptr_t>(workspace) % 16 == 0, "%s: workspace must be 16-byte aligned", who);
     long long* gc = reinterpret_cast<long long*>(w); w += 2 * B * faces;
     a.gcy = gc; a.gcx = gc + B * nVy; a.gcz = a.gcx + B * nVx;
     a.gay = w; w += B * nVy; a.gax = w; w += B * nVx; a.gaz = w; w += B * nVz;
@@ -1192,7 +1211,45 @@ extern "C" int sol_karman3d_step_bwd(const sol_karman3d_cfg* c, void* stream,
     SOL_LAUNCH(k3b_advect_adj, dim3(grid_for((size_t)((Y + 1) * X + Y * (X + 1) + Y * X) * 64), B), dim3(256), 0, s, a);
     SOL_LAUNCH(k3b_diffuse_adj, dim3(grid_for(faces), B), dim3(256), 0, s, a);
     SOL_LAUNCH_CHECK();
-    return SOL_OK;
+    if (!rx) return SOL_OK;
+    // g' of the Reynolds-number gradient = what k3b_diffuse_adj has just read: fx_get(g_c) (. (1 - bcm) on v_y); the partial sums lie behind
+    // the plain adjoint's workspace
+    Re3In in{};
+    in.src = RE3_FIXED;
+    in.gcy = a.gcy; in.gcx = a.gcx; in.gcz = a.gcz; in.gmax = a.gmax; in.bcm = velBCyMask; in.bc_stride = bc_batch_stride;
+    in.vy_in = rx->vy_in; in.vx_in = rx->vx_in; in.vz_in = rx->vz_in; in.re = re;
+    in.partial = sol_re3_partial_at(workspace, plain_bytes);
+    in.g_re = rx->g_re; in.accumulate = rx->accumulate;
+    return sol_re3_reduce(s, c, in);
+}
+
+}  // namespace
+
+extern "C" int sol_karman3d_step_bwd(const sol_karman3d_cfg* c, void* stream,
+                                     const float* saved_vy, const float* saved_vx, const float* saved_vz,
+                                     const float* re, const float* active, const float* velBCyMask, int64_t bc_batch_stride,
+                                     const float* g_vy_out, const float* g_vx_out, const float* g_vz_out,
+                                     float* g_vy_in, float* g_vx_in, float* g_vz_in,
+                                     const int32_t* direct_header_host, void* workspace, size_t workspace_bytes) {
+    return step_bwd3d("sol_karman3d_step_bwd", c, stream, saved_vy, saved_vx, saved_vz, re, active, velBCyMask, bc_batch_stride,
+                      g_vy_out, g_vx_out, g_vz_out, g_vy_in, g_vx_in, g_vz_in, direct_header_host, workspace, workspace_bytes, nullptr);
+}
+
+extern "C" size_t sol_karman3d_step_bwd_re_workspace_bytes(const sol_karman3d_cfg* c) {
+    if (!c) return 0;
+    return sol_karman3d_step_bwd_workspace_bytes(c) + sol_re3_partial_bytes(c);
+}
+
+extern "C" int sol_karman3d_step_bwd_re(const sol_karman3d_cfg* c, void* stream,
+                                        const float* saved_vy, const float* saved_vx, const float* saved_vz,
+                                        const float* re, const float* active, const float* velBCyMask, int64_t bc_batch_stride,
+                                        const float* g_vy_out, const float* g_vx_out, const float* g_vz_out,
+                                        float* g_vy_in, float* g_vx_in, float* g_vz_in,
+                                        const int32_t* direct_header_host, void* workspace, size_t workspace_bytes,
+                                        const float* vy_in, const float* vx_in, const float* vz_in, float* g_re, int accumulate_re) {
+    const Re3Extra rx{vy_in, vx_in, vz_in, g_re, accumulate_re};
+    return step_bwd3d("sol_karman3d_step_bwd_re", c, stream, saved_vy, saved_vx, saved_vz, re, active, velBCyMask, bc_batch_stride,
+                      g_vy_out, g_vx_out, g_vz_out, g_vy_in, g_vx_in, g_vz_in, direct_header_host, workspace, workspace_bytes, &rx);
 }
 
 extern "C" int sol_karman3d_pressure_solve(const sol_karman3d_cfg* c, void* stream, const float* active, const float* rhs, float* p,

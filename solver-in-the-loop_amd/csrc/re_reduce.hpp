@@ -1,7 +1,7 @@
 // Gradient with respect to the Reynolds number of an explicit-diffusion step, u = v_in + alpha L v_in with alpha = dt res^2 / re[b]:
 //     g_re[b] = -(dt res^2 / re[b]^2) * sum over the faces e of every component of  g'_e (L v_in)_e
 // g' = the cotangent the step's diffusion adjoint applies (I + alpha L^T) to, L = the replicate-padded (2 D + 1)-point Laplacian.  This
-// header is the dimension-independent part (used by karman_re_bwd.hip for D = 2): the forward Laplacian at one element, the order-fixed
+// header is the dimension-independent part (used by karman_re_bwd.hip for D = 2, karman3d_re_bwd.hip for D = 3): the forward Laplacian at one element, the order-fixed
 // workgroup sum and the final sum.  A caller supplies g' and the component arrays.
 //   Order     every sum is taken in a FIXED order -- a thread over its strided share, the 64 lanes of a wave by an xor butterfly, the
 //             waves of the workgroup through LDS in wave order, the workgroups' partial sums in index order -- and the number of workgroups

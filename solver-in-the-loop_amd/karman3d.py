@@ -109,13 +109,19 @@ class Karman3DFlow:
 
     cg_rtol / cg_atol / cg_max_iter: the CG solve of a scene with pressure_solver == "cg" (names and tolerances of the 2-D
     KarmanFlow; cg_max_iter is the fixed launch budget).  After a forward step on such a scene `solve_info` holds "iterations"
-    and "converged" (device int32 [B]); the adjoint adds "iterations_bwd" and "converged_bwd".  The direct solve reports nothing."""
+    and "converged" (device int32 [B]); the adjoint adds "iterations_bwd" and "converged_bwd".  The direct solve reports nothing.
+
+    density_grad=True (opt-in): the density output of `step` is differentiable too (sol_karman3d_density_bwd: launches of their own, no
+    pressure solve, added onto the velocity adjoint's result).  re_grad=True (opt-in): a tensor `re` that requires a gradient receives
+    one (sol_karman3d_step_bwd_re / sol_karman3d_density_bwd_re; the step's input velocity is saved as well).  With both off the step
+    launches what it always did: the density is a passive tracer and `re` is data."""
 
     def __init__(self, scene, batch_size, dt=1.0, res=None, grad_pad="replicate", inflow_order="after",
-                 cg_rtol=1e-6, cg_atol=1e-9, cg_max_iter=CG_MAX_ITER3D):
+                 cg_rtol=1e-6, cg_atol=1e-9, cg_max_iter=CG_MAX_ITER3D, density_grad=False, re_grad=False):
         _lib.require_gpu()
         self.lib = _lib.load()
         self.scene, self.B = scene, batch_size
+        self.density_grad, self.re_grad = bool(density_grad), bool(re_grad)
         s = scene
         self.cg = s.pressure_solver == "cg"
         self.cfg = Karman3DCfg(batch_size, s.Y, s.X, s.Z, float(s.dx), float(dt), float(s.X if res is None else res),
@@ -157,17 +163,45 @@ class Karman3DFlow:
             self.solve_info = {"iterations": info[:, 0], "converged": info[:, 1]}
         return tuple(out)
 
-    def _bwd(self, saved, re, gvy, gvx, gvz):
+    def _ws(self, nbytes):
+        """the workspace, grown to nbytes where a call needs more than the step and its velocity adjoint (the opt-in adjoints)"""
+        if nbytes > self.workspace_bytes:
+            self.workspace = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=self.scene.active.device)
+            self.workspace_bytes = nbytes
+        return self.workspace
+
+    def _re_tail(self, saved, vel_in, g_re):
+        """the five arguments an _re entry point takes after its plain sibling's: the step's INPUT velocity, g_re [B] (the caller's buffer
+        to add onto, or None for a fresh one to write) and accumulate_re  ->  (arguments, g_re)"""
+        vel_in = [_lib.f32(t) for t in vel_in]
+        if [t.shape for t in vel_in] != [t.shape for t in saved]:
+            raise ValueError("the step's input velocity must have the saved velocity's shapes")
+        accumulate = g_re is not None
+        if not accumulate:
+            g_re = torch.empty(self.B, dtype=torch.float32, device=saved[0].device)
+        elif g_re.shape != (self.B,):
+            raise ValueError("g_re must be [B] = (%d,), got %s" % (self.B, tuple(g_re.shape)))
+        return (ptr(vel_in[0]), ptr(vel_in[1]), ptr(vel_in[2]), ptr(g_re), int(accumulate)), g_re
+
+    def _bwd(self, saved, re, gvy, gvx, gvz, vel_in=None, g_re=None):
+        """the velocity adjoint (sol_karman3d_step_bwd); vel_in = the step's input velocity: also the gradient with respect to re
+        (sol_karman3d_step_bwd_re; the velocity gradients are the plain call's bits) -> [g_vy, g_vx, g_vz] (+ [g_re])"""
         s = self.scene
         gi = [torch.empty_like(t) for t in saved]
         info = self._cg_info()
-        check(self.lib.sol_karman3d_step_bwd(C.byref(self.cfg), stream(), ptr(saved[0]), ptr(saved[1]), ptr(saved[2]), ptr(re),
-                                             ptr(s.active), ptr(s.velBCyMask), s.bc_stride, ptr(gvy), ptr(gvx), ptr(gvz),
-                                             ptr(gi[0]), ptr(gi[1]), ptr(gi[2]),
-                                             s.direct_header.ctypes.data_as(C.c_void_p), ptr(self.workspace), self.workspace_bytes))
+        if vel_in is None:
+            entry, tail = self.lib.sol_karman3d_step_bwd, ()
+        else:
+            entry = self.lib.sol_karman3d_step_bwd_re
+            self._ws(self.lib.sol_karman3d_step_bwd_re_workspace_bytes(C.byref(self.cfg)))
+            tail, g_re = self._re_tail(saved, vel_in, g_re)
+        check(entry(C.byref(self.cfg), stream(), ptr(saved[0]), ptr(saved[1]), ptr(saved[2]), ptr(re),
+                    ptr(s.active), ptr(s.velBCyMask), s.bc_stride, ptr(gvy), ptr(gvx), ptr(gvz),
+                    ptr(gi[0]), ptr(gi[1]), ptr(gi[2]),
+                    s.direct_header.ctypes.data_as(C.c_void_p), ptr(self.workspace), self.workspace_bytes, *tail))
         if info is not None:
             self.solve_info = dict(self.solve_info, iterations_bwd=info[:, 0], converged_bwd=info[:, 1])
-        return gi
+        return gi if vel_in is None else gi + [g_re]
 
     def pressure_solve(self, rhs):
         """The step's pressure solve alone (sol_karman3d_pressure_solve): p with M p = rhs, M = -A for the scene's mask; rhs [B,Y,X,Z].
@@ -186,47 +220,109 @@ class Karman3DFlow:
     def step(self, d, vy, vx, vz, re, feat_out=None, feat_scale=None):
         """(d, vy, vx, vz) -> new tensors after one solver step.  Differentiable with respect to the velocity (the density is
         a passive tracer) when a velocity input requires grad; feat_out [B,Y,X,Z,4] (optional, no-grad use) receives the
-        scaled features."""
+        scaled features.  With density_grad the density output is differentiable too (taken when any of d, vy, vx, vz requires a
+        gradient); with re_grad a tensor `re` that requires a gradient receives one."""
         d, vy, vx, vz, re = (_lib.f32(t) for t in (d, vy, vx, vz, re))
-        if torch.is_grad_enabled() and (vy.requires_grad or vx.requires_grad or vz.requires_grad):
+        grad = torch.is_grad_enabled()
+        want_re = self.re_grad and grad and re.requires_grad
+        if grad and (vy.requires_grad or vx.requires_grad or vz.requires_grad or (self.density_grad and d.requires_grad) or want_re):
             if feat_out is not None:
                 raise ValueError("feat_out is the fused no-grad feature output: build the features with to_feature3d() when training")
-            return _Karman3DStepFn.apply(self, d, vy, vx, vz, re)
+            return _Karman3DStepFn.apply(self, d, vy, vx, vz, re, self.density_grad, want_re)
         return self._fwd(d, vy, vx, vz, re, None, feat_out, feat_scale)
 
 
+def density_bwd(sim, d_in, saved, re, g_d, g_v=None, vel_in=None, g_re=None):
+    """Adjoint of the 3-D step's marker density (sol_karman3d_density_bwd), the direct call: (g_d_in, g_vy_in, g_vx_in, g_vz_in) from the
+    step's input density `d_in`, the saved post-diffusion velocity `saved` = (svy, svx, svz), `re` and the gradient `g_d` with respect
+    to the step's output density; `sim` = the Karman3DFlow (scene, cfg, workspace).  g_v = (g_vy, g_vx, g_vz): buffers that already hold
+    the velocity adjoint's result; the density's part is added onto them in place (one fp32 add per face) and they are returned.  Without
+    them the density's part alone is written to fresh tensors.  vel_in = (vy, vx, vz), the step's INPUT velocity: the gradient with
+    respect to re as well (sol_karman3d_density_bwd_re), returned fifth; g_re [B]: a buffer to add onto, else a fresh one is written."""
+    _lib.require_gpu()
+    s, B = sim.scene, sim.B
+    Y, X, Z = s.Y, s.X, s.Z
+    d_in, re, g_d = (_lib.f32(t) for t in (d_in, re, g_d))
+    saved = [_lib.f32(t) for t in saved]
+    shapes = (("d_in", d_in, (B, Y, X, Z)), ("g_d", g_d, (B, Y, X, Z)), ("svy", saved[0], (B, Y + 1, X, Z)), ("svx", saved[1], (B, Y, X + 1, Z)),
+              ("svz", saved[2], (B, Y, X, Z + 1)), ("re", re, (B,)))
+    for name, t, shape in shapes:
+        if t.shape != shape:
+            raise ValueError("density_bwd: %s is %s, not %s of the scene" % (name, tuple(t.shape), shape))
+    accumulate = g_v is not None
+    if accumulate and [t.shape for t in g_v] != [t.shape for t in saved]:
+        raise ValueError("density_bwd: g_v must have the velocity's shapes")
+    if vel_in is None:
+        entry, nbytes, tail = sim.lib.sol_karman3d_density_bwd, sim.lib.sol_karman3d_density_bwd_workspace_bytes(C.byref(sim.cfg)), ()
+    else:
+        entry, nbytes = sim.lib.sol_karman3d_density_bwd_re, sim.lib.sol_karman3d_density_bwd_re_workspace_bytes(C.byref(sim.cfg))
+        tail, g_re = sim._re_tail(saved, vel_in, g_re)
+    gi = list(g_v) if accumulate else [torch.empty_like(t) for t in saved]
+    od = torch.empty_like(d_in)
+    ws = sim._ws(nbytes)
+    check(entry(C.byref(sim.cfg), stream(), ptr(d_in), ptr(s.inflow), ptr(saved[0]), ptr(saved[1]), ptr(saved[2]), ptr(re),
+                ptr(s.velBCyMask), s.bc_stride, ptr(g_d), ptr(od), ptr(gi[0]), ptr(gi[1]), ptr(gi[2]), int(accumulate),
+                ptr(ws), sim.workspace_bytes, *tail))
+    return (od, *gi) if vel_in is None else (od, *gi, g_re)
+
+
 class _Karman3DStepFn(torch.autograd.Function):
+    """One solver step with its hand-written adjoints; the forward launches are the same in every mode.  Plain: differentiable with
+    respect to the velocity, the density is a passive tracer, re is data.  `density` (opt-in): the density output is differentiable too
+    (density_bwd, added onto the velocity adjoint's result).  `want_re` (opt-in): differentiable with respect to re as well, the step's
+    input velocity saved beside the post-diffusion one.  In the opt-in modes the velocity half (with its pressure solve) runs only when a
+    velocity cotangent arrived, the density half only when a density cotangent did; both together accumulate."""
+
     @staticmethod
-    def forward(ctx, sim, d, vy, vx, vz, re):
-        saved = [torch.empty_like(t) for t in (vy, vx, vz)]
-        out = sim._fwd(d, vy.contiguous(), vx.contiguous(), vz.contiguous(), re, saved)
-        ctx.sim = sim
-        ctx.save_for_backward(re, *saved)
-        ctx.mark_non_differentiable(out[0])
+    def forward(ctx, sim, d, vy, vx, vz, re, density, want_re):
+        vel = [vy.contiguous(), vx.contiguous(), vz.contiguous()]
+        saved = [torch.empty_like(t) for t in vel]
+        out = sim._fwd(d, vel[0], vel[1], vel[2], re, saved)
+        ctx.sim, ctx.density, ctx.want_re = sim, density, want_re
+        ctx.save_for_backward(re, *saved, *((d,) if density else ()), *(vel if want_re else ()))
+        if not density:
+            ctx.mark_non_differentiable(out[0])
+        ctx.set_materialize_grads(False)
         return out
 
     @staticmethod
-    def backward(ctx, _gd, gvy, gvx, gvz):
-        re, sy, sx, sz = ctx.saved_tensors
+    def backward(ctx, gd, gvy, gvx, gvz):
+        re, sy, sx, sz, *rest = ctx.saved_tensors
+        saved = (sy, sx, sz)
+        d_in = rest[0] if ctx.density else None
+        vel_in = tuple(rest[-3:]) if ctx.want_re else None
         z = lambda g, t: torch.zeros_like(t) if g is None else g.contiguous()
-        gi = ctx.sim._bwd((sy, sx, sz), re, z(gvy, sy), z(gvx, sx), z(gvz, sz))
-        return None, None, gi[0], gi[1], gi[2], None
+        od = g_re = gi = None
+        if not (ctx.density or ctx.want_re) or gvy is not None or gvx is not None or gvz is not None:
+            res = ctx.sim._bwd(saved, re, z(gvy, sy), z(gvx, sx), z(gvz, sz), vel_in)
+            gi, g_re = res[:3], (res[3] if vel_in is not None else None)
+        if ctx.density and gd is not None:          # added onto the velocity half's buffers and g_re
+            res = density_bwd(ctx.sim, d_in, saved, re, gd.contiguous(), gi, vel_in, g_re)
+            od, gi, g_re = res[0], res[1:4], (res[4] if vel_in is not None else None)
+        gi = gi if gi is not None else (None, None, None)
+        return None, od, gi[0], gi[1], gi[2], g_re, None, None
 
 
 class _ToFeature3DFn(torch.autograd.Function):
     """to_feature3d as one node with a backward made of kernels only: the autograd backward of `vy[:, :Y]` is zeros + a copy into a
     narrow, and with B = 1 that narrow is contiguous -- a hipMemcpyAsync, i.e. a memcpy node per unrolled step in the captured trainer
-    (refused by sol_graph_check).  Here: zero-padding of the strided channel slices (fill + strided copy kernels)."""
+    (refused by sol_graph_check).  Here: zero-padding of the strided channel slices (fill + strided copy kernels).  A tensor `re` that
+    requires a gradient stays in the graph: its gradient is the sum of the fourth channel's per simulation (taken only then)."""
 
     @staticmethod
     def forward(ctx, vy, vx, vz, re):
         Y, X, Z = vx.shape[1], vy.shape[2], vy.shape[3]
+        ctx.re_meta = (re.shape, re.dtype)
         st = torch.stack([vy[:, :Y], vx[:, :, :X], vz[..., :Z]], dim=-1)
         return torch.cat([st, re.reshape(-1, 1, 1, 1, 1).expand(-1, Y, X, Z, 1).to(st.dtype)], dim=-1)
 
     @staticmethod
     def backward(ctx, g):
-        return _lib.pad_high(g[..., 0], 1), _lib.pad_high(g[..., 1], 2), _lib.pad_high(g[..., 2], 3), None
+        g_re = None
+        if ctx.needs_input_grad[3]:
+            shape, dtype = ctx.re_meta
+            g_re = g[..., 3].sum(dim=(1, 2, 3)).reshape(shape).to(dtype)
+        return _lib.pad_high(g[..., 0], 1), _lib.pad_high(g[..., 1], 2), _lib.pad_high(g[..., 2], 3), g_re
 
 
 def to_feature3d(vy, vx, vz, re):

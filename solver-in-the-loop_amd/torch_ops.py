@@ -23,6 +23,9 @@ _LIB.define("karman_step_bwd(Tensor svy, Tensor svx, Tensor re, Tensor gvy, Tens
 _LIB.define("karman_step_fwd_saved(Tensor d, Tensor vy, Tensor vx, Tensor re, int scene) -> (Tensor, Tensor, Tensor, Tensor, Tensor)")
 _LIB.define("conv5x5(Tensor x, Tensor w, Tensor b, Tensor? residual, bool lrelu, float slope) -> Tensor")
 _LIB.define("karman3d_step(Tensor d, Tensor vy, Tensor vx, Tensor vz, Tensor re, int scene) -> (Tensor, Tensor, Tensor, Tensor)")
+_LIB.define("karman3d_step_dens(Tensor d, Tensor vy, Tensor vx, Tensor vz, Tensor re, int scene) -> (Tensor, Tensor, Tensor, Tensor)")
+_LIB.define("karman3d_step_re(Tensor d, Tensor vy, Tensor vx, Tensor vz, Tensor re, int scene, bool density=False) -> (Tensor, Tensor, Tensor, Tensor)")
+_LIB.define("karman3d_density_bwd(Tensor d, Tensor svy, Tensor svx, Tensor svz, Tensor re, Tensor gd, int scene) -> (Tensor, Tensor, Tensor, Tensor)")
 _LIB.define("conv3d(Tensor x, Tensor w, Tensor b, Tensor? residual, bool lrelu, float slope) -> Tensor")
 _LIB.define("burgers_step(Tensor vy, Tensor vx, Tensor? fy, Tensor? fx, float dx, float dt, float nu) -> (Tensor, Tensor)")
 _LIB.define("l2_loss(Tensor vy, Tensor vx, Tensor gt_vy, Tensor gt_vx, float std_vy, float std_vx) -> Tensor")
@@ -118,9 +121,23 @@ def register_scene3d(sim):
     return h
 
 
-def _karman3d_step(d, vy, vx, vz, re, scene):
+# the step's three differentiable forms are the modes of karman3d._Karman3DStepFn, as for the 2-D step: karman3d_step (the density is a
+# passive tracer, re is data), karman3d_step_dens (opt-in: the density output is differentiable too) and karman3d_step_re (opt-in:
+# differentiable with respect to re as well; density: d_out stays in the graph as in karman3d_step_dens)
+def _karman3d_fn(d, vy, vx, vz, re, scene, density, want_re):
     from . import karman3d as k3
-    return k3._Karman3DStepFn.apply(_SIMS3D[scene], _lib.f32(d), _lib.f32(vy), _lib.f32(vx), _lib.f32(vz), _lib.f32(re))
+    re = _lib.f32(re)
+    want_re = want_re and torch.is_grad_enabled() and re.requires_grad
+    return k3._Karman3DStepFn.apply(_SIMS3D[scene], _lib.f32(d), _lib.f32(vy), _lib.f32(vx), _lib.f32(vz), re, density, want_re)
+
+
+def _karman3d_step(d, vy, vx, vz, re, scene):
+    return _karman3d_fn(d, vy, vx, vz, re, scene, False, False)
+
+
+def _karman3d_density_bwd(d, svy, svx, svz, re, gd, scene):
+    from . import karman3d as k3
+    return k3.density_bwd(_SIMS3D[scene], d, (svy, svx, svz), re, gd)
 
 
 def _conv3d(x, w, b, residual, lrelu, slope):
@@ -129,4 +146,7 @@ def _conv3d(x, w, b, residual, lrelu, slope):
 
 
 _LIB.impl("karman3d_step", _karman3d_step, "AutogradCUDA")
+_LIB.impl("karman3d_step_dens", lambda d, vy, vx, vz, re, scene: _karman3d_fn(d, vy, vx, vz, re, scene, True, False), "AutogradCUDA")
+_LIB.impl("karman3d_step_re", lambda d, vy, vx, vz, re, scene, density=False: _karman3d_fn(d, vy, vx, vz, re, scene, bool(density), True), "AutogradCUDA")
+_LIB.impl("karman3d_density_bwd", _karman3d_density_bwd, "CUDA")
 _LIB.impl("conv3d", _conv3d, "AutogradCUDA")
