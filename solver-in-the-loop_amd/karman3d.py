@@ -9,12 +9,16 @@ Layout: density [B,Y,X,Z], v_y [B,Y+1,X,Z], v_x [B,Y,X+1,Z], v_z [B,Y,X,Z+1] (y 
 tensors [B,Y,X,Z,C].  Everything calls libsol_hip.so (csrc/karman3d.hip); there is no CPU implementation.
 
 Training (SOL-n, the reverse sweep of karman_train.py:397-457 in 3-D): `Karman3DTrainer` runs a hand-written schedule over the C ABI
-(forward unroll + reverse sweep, no autograd graph; `schedule="autograd"` keeps the torch composition as the cross-check).  For other hosts
+(forward unroll + reverse sweep, no autograd graph; `schedule="autograd"` keeps the torch composition as the cross-check).  How the network
+is launched -- its packed weights, the twelve forward launches, the reverse sweep and the weight-gradient partials -- is written once, in
+schedule3d.NetSchedule3D: the trainer, the autograd node of `MarsMoon3D.__call__` and `Karman3DRollout` (train=False) all run one, and it re-packs
+when `MarsMoon3D.params_key()` has moved.  For other hosts
 `Karman3DFlow.step` and `conv3d` are also torch.autograd Functions over the HIP adjoints (sol_karman3d_step_bwd; Conv3D backward-data = sol_conv3d on flipped weights, weight gradient
 = five passes of the 2-D weight-gradient kernels), composed by `Karman3DTrainer` exactly as the reference composes its graph.
 """
 import ctypes as C
 import math
+import weakref
 
 import numpy as np
 import torch
@@ -363,60 +367,30 @@ class MarsMoon3D:
             else:
                 parts.append(torch.zeros(s, dtype=torch.float64))
         self.params = torch.cat(parts).to(device=device, dtype=torch.float32).contiguous()
-        self._packed = None
+        self._generation = 0
+        self._schedules = {}
 
-    def train_packs(self):
-        """Per layer (forward-packed, backward-data-packed) weights, built once and reused by every unrolled step of a
-        training step (the weights only change between steps: whoever updates them resets `_tpacks`)."""
-        key = self._params_key()
-        if getattr(self, "_tpacks", None) is None or getattr(self, "_tpacks_key", None) != key:
-            t = self.tensors()
-            self._tpacks = []
-            for l in range(12):
-                cin, cout = self.chans[l], self.chans[l + 1]
-                cin_k = 4 if cin <= 4 else 32
-                w = t[2 * l].detach()
-                wf = w if cin_k == cin else torch.nn.functional.pad(w, (0, 0, 0, cin_k - cin))   # the forward kernels read cin_k input channels (as pack())
-                self._tpacks.append((_pack3d(wf, cin_k, cout, 0), _pack3d(w, cout, cin, 1)))
-            # the two thin-INPUT layers (first layer 4 -> 32; the output layer's data gradient cout -> 32) as ONE 2-D launch with the depth
-            # taps packed into the channel axis (sol_conv3d_thin): packed for the convolution that is RUN
-            self._kpacks = None
-            self._kpacks_out = None
-            if self.thin_kpack and self.cin <= 4 and self.cout <= 4:
-                self._kpacks = (_pack3d_thin(t[0].detach(), self.cin, 0), _pack3d_thin(t[22].detach(), self.cout, 1))
-                # ... and into the OUTPUT channel axis (sol_conv3d_thin_out): the output layer's forward, the first layer's data gradient
-                self._kpacks_out = (_pack3d_thin_out(t[22].detach(), self.cout, 0), _pack3d_thin_out(t[0].detach(), self.cin, 1))
-            self._tpacks_key = key
-        return self._tpacks
-
-    thin_kpack = True          # False: the thin-input layers as five passes of the 2-D fp32-MFMA kernel (sol_conv3d), rounds 3-6
-
-    thin_out_kpack = True      # False: the 32 -> (<= 4) layers on the eight-row Conv3D kernel with one channel tile (k_conv3d_sb8<1, 0>), rounds 4-6
-
-    def thin_out_packs(self):
-        """(output layer forward, first layer backward-data) packed for sol_conv3d_thin_out, or None"""
-        self.train_packs()
-        return self._kpacks_out if self.thin_out_kpack else None
-
-    def thin_packs(self):
-        """(first layer forward, output layer backward-data) packed for sol_conv3d_thin, or None (thin_kpack off / more than four channels)"""
-        self.train_packs()
-        return self._kpacks
-
-    def _params_key(self):
-        """Identity of the weight buffer's CONTENT as far as torch can see it: an optimizer that updates `params` in place through
-        torch bumps `_version`; the library's own Adam (ctypes) does not -- Karman3DTrainer.apply_gradients resets the caches itself."""
-        return (self.params.data_ptr(), self.params._version)
+    def params_key(self):
+        """Identity of the weight buffer's CONTENT, the ONE staleness rule of the packed weights: a schedule (schedule3d.NetSchedule3D)
+        re-packs when this differs from the key it packed at.  An optimizer that updates `params` in place through torch bumps
+        `_version`; writes torch does not see (the library's own Adam, ctypes) are announced with invalidate()."""
+        return (self.params.data_ptr(), self.params._version, self._generation)
 
     def invalidate(self):
-        """Drop the packed-weight caches.  MUST be called by whoever changes the CONTENT of `params` in a way torch's version counter does
-        not see: writes through `params.data` (`p.data.add_()`, `load_state_dict`-style `.data.copy_`), ctypes / HIP writes into the
-        buffer (the library's own Adam: Karman3DTrainer.apply_gradients calls this), external kernels.  `set_weights` calls it itself;
-        in-place torch ops on `params` bump `_version` and need nothing."""
-        self._packed = None
-        self._packed_thin = None
-        self._packed_thin_out = None
-        self._tpacks = None
+        """Mark every schedule's packed weights stale.  MUST be called by whoever changes the CONTENT of `params` in a way torch's version
+        counter does not see: writes through `params.data` (`p.data.add_()`, `load_state_dict`-style `.data.copy_`), ctypes / HIP writes
+        into the buffer (the library's own Adam: Karman3DTrainer.apply_gradients calls this), external kernels.  `set_weights` calls it
+        itself; in-place torch ops on `params` bump `_version` and need nothing."""
+        self._generation += 1
+
+    def schedule(self, B, Y, X, Z):
+        """the training schedule (launch sequence, packed weights, weight-gradient partials) of this network at one shape, built once
+        (it refers back to the net weakly: no reference cycle, the buffers go with the net)"""
+        from .schedule3d import NetSchedule3D
+        key = (int(B), int(Y), int(X), int(Z))
+        if key not in self._schedules:
+            self._schedules[key] = NetSchedule3D(weakref.proxy(self), *key)
+        return self._schedules[key]
 
     fused_backward = True      # one autograd node with a hand-written reverse sweep (False: one node per layer, torch glue)
 
@@ -426,7 +400,7 @@ class MarsMoon3D:
         if self.fused_backward:
             return _MarsMoon3DFn.apply(x, self.params, self)
         p = self.tensors()
-        pk = self.train_packs()
+        pk = self.schedule(*x.shape[:4]).layer_packs()
         sl = self.slope
         h = conv3d_fn(x, p[0], p[1], None, True, sl, pk[0])
         for k in range(5):
@@ -438,7 +412,8 @@ class MarsMoon3D:
         """The eleven 32-channel activations h0, a1, h1, ..., a5, h5 of the forward pass (no gradient; the same launches as
         __call__) -- for checks that need the LeakyReLU masks the backward pass will use."""
         with torch.no_grad():
-            return _MarsMoon3DFn.run_forward(self, x)[3]
+            _, (_, _, acts) = self.schedule(*x.shape[:4]).forward(x)
+        return acts
 
     @property
     def n_params(self):
@@ -457,46 +432,6 @@ class MarsMoon3D:
         with torch.no_grad():
             self.params.copy_(torch.as_tensor(flat, device=self.params.device))
         self.invalidate()
-
-    def pack_thin(self):
-        """the first layer packed for sol_conv3d_thin (inference path; cached like pack()), or None"""
-        if not (self.thin_kpack and self.cin <= 4):
-            return None
-        key = self._params_key()
-        if getattr(self, "_packed_thin", None) is None or getattr(self, "_packed_thin_key", None) != key:
-            self._packed_thin_key = key
-            self._packed_thin = _pack3d_thin(self.tensors()[0].detach(), self.cin, 0)
-        return self._packed_thin
-
-    def pack_thin_out(self):
-        """the output layer packed for sol_conv3d_thin_out (inference path; cached like pack()), or None"""
-        if not (self.thin_kpack and self.thin_out_kpack and self.cout <= 4):
-            return None
-        key = self._params_key()
-        if getattr(self, "_packed_thin_out", None) is None or getattr(self, "_packed_thin_out_key", None) != key:
-            self._packed_thin_out_key = key
-            self._packed_thin_out = _pack3d_thin_out(self.tensors()[22].detach(), self.cout, 0)
-        return self._packed_thin_out
-
-    def pack(self):
-        """(packed weights, padded biases) per layer in the layout the conv kernels consume; cached until set_weights."""
-        key = self._params_key()
-        if self._packed is None or getattr(self, "_packed_key", None) != key:
-            self._packed_key = key
-            lib = _lib.load()
-            t = self.tensors()
-            self._packed = []
-            for l in range(12):
-                cin, cout = self.chans[l], self.chans[l + 1]
-                cin_k = 4 if cin <= 4 else 32
-                w = t[2 * l]
-                if cin_k != cin:
-                    w = torch.nn.functional.pad(w, (0, 0, 0, cin_k - cin))
-                w = w.contiguous()
-                buf = torch.empty(lib.sol_conv3d_packed_floats(cin_k, cout), dtype=torch.float32, device=w.device)
-                check(lib.sol_conv3d_pack(stream(), ptr(w), cin_k, cout, 0, ptr(buf)))
-                self._packed.append((buf, t[2 * l + 1].contiguous(), cin_k, cout))
-        return self._packed
 
 
 def conv3d(x, packed, bias, residual, cout, lrelu, slope, x_absmax=None, y_absmax=None, out=None, act_ref=None):
@@ -539,25 +474,27 @@ def conv3d_thin_out(x, packed, bias, cout, x_absmax=None, out=None, ws=None):
     return y
 
 
-def _pack3d_thin_out(w, cr, mode):
+def _pack3d_thin_out(w, cr, mode, out=None):
     """sol_conv3d_thin_out_pack: w = the FORWARD kernel ([5,5,5,32,cr] for mode 0, [5,5,5,cr,32] for mode 1 = backward-data), cr <= 4"""
     lib = _lib.load()
-    buf = torch.empty(lib.sol_conv3d_thin_packed_floats(), dtype=torch.float32, device=w.device)
+    buf = out if out is not None else torch.empty(lib.sol_conv3d_thin_packed_floats(), dtype=torch.float32, device=w.device)
     check(lib.sol_conv3d_thin_out_pack(stream(), ptr(w.contiguous()), cr, mode, ptr(buf)))
     return buf
 
 
-def _pack3d_thin(w, cin_run, mode):
+def _pack3d_thin(w, cin_run, mode, out=None):
     """w: the FORWARD kernel ([5,5,5,cin_run,32] for mode 0, [5,5,5,32,cin_run] for mode 1 = backward-data)"""
     lib = _lib.load()
-    buf = torch.empty(lib.sol_conv3d_thin_packed_floats(), dtype=torch.float32, device=w.device)
+    buf = out if out is not None else torch.empty(lib.sol_conv3d_thin_packed_floats(), dtype=torch.float32, device=w.device)
     check(lib.sol_conv3d_thin_pack(stream(), ptr(w.contiguous()), cin_run, mode, ptr(buf)))
     return buf
 
 
-def _pack3d(w, cin_run, cout_run, mode):
+def _pack3d(w, cin_run, cout_run, mode, out=None):
+    """sol_conv3d_pack of the FORWARD kernel w for a convolution that runs cin_run -> cout_run channels (mode 1: backward-data);
+    out: the buffer to pack into (a schedule's persistent one), else a fresh one"""
     lib = _lib.load()
-    buf = torch.empty(lib.sol_conv3d_packed_floats(cin_run, cout_run), dtype=torch.float32, device=w.device)
+    buf = out if out is not None else torch.empty(lib.sol_conv3d_packed_floats(cin_run, cout_run), dtype=torch.float32, device=w.device)
     check(lib.sol_conv3d_pack(stream(), ptr(w.contiguous()), cin_run, cout_run, mode, ptr(buf)))
     return buf
 
@@ -573,6 +510,26 @@ def _pad_ch(x, c):
     return x.contiguous() if x.shape[-1] == c else torch.nn.functional.pad(x, (0, c - x.shape[-1])).contiguous()
 
 
+def _acc_buffers(name, acc, shape_key, alloc):
+    """(buffers, first, last) of a weight-gradient call.  acc = (state dict, first, last): the partial sums of a reverse sweep live in the
+    caller's state dict -- alloc() fills a fresh one --, they belong to ONE shape and to a sequence that was opened with first=True (the C
+    entry point cannot see the size of `partial`, so a mismatch would overrun it or add onto stale sums).  acc = None: one call on its own."""
+    if acc is None:
+        return alloc(), True, True
+    st, first, last = acc
+    if "part" in st:
+        if st.get("shape") != shape_key:
+            raise _lib.SolError("%s: the accumulation state was allocated for %s, this call has %s" % (name, st.get("shape"), shape_key))
+        if not first and not st.get("open"):
+            raise _lib.SolError("%s: first=False on a state whose sequence is not open (the previous sweep ended with last=True)" % name)
+    else:
+        if not first:
+            raise _lib.SolError("%s: the first call on a fresh accumulation state must have first=True (nothing to add onto yet)" % name)
+        st.update(alloc(), shape=shape_key)
+    st["open"] = not last
+    return st, first, last
+
+
 def conv3d_thin_bwd_weight(x4, dz, cin, zmax=None, acc=None, thin_out=False):
     """dW [5,5,5,cin,32], db [32] of a thin-input layer y = conv3d(x, W) + b from x4 [B,D,H,W,4] (zero padded) and dz [B,D,H,W,32], W == 64:
     sol_conv3d_thin_bwd_weight_acc -- the depth taps packed into the channel axis, ONE pass of the 2-D 32 -> 32 weight-gradient kernel.
@@ -584,24 +541,11 @@ def conv3d_thin_bwd_weight(x4, dz, cin, zmax=None, acc=None, thin_out=False):
     assert c == 4 and dz.shape[-1] == 32 and W == 64
     dev = x4.device
     shape_key = ("thin_out" if thin_out else "thin", B, D, H, W, cin, str(dev))
-    if acc is not None and "part" in acc[0]:
-        if acc[0].get("shape") != shape_key:
-            raise _lib.SolError("conv3d_thin_bwd_weight: the accumulation state was allocated for %s, this call has %s" % (acc[0].get("shape"), shape_key))
-        if not acc[1] and not acc[0].get("open"):
-            raise _lib.SolError("conv3d_thin_bwd_weight: first=False on a state whose sequence is not open (the previous sweep ended with last=True)")
-        part, dW, db, ws = (acc[0][k] for k in ("part", "dW", "db", "ws"))
-    else:
-        if acc is not None and not acc[1]:
-            raise _lib.SolError("conv3d_thin_bwd_weight: the first call on a fresh accumulation state must have first=True (nothing to add onto yet)")
-        part = torch.empty(lib.sol_conv3d_thin_bwd_weight_ws_floats(B, D, H, W), dtype=torch.float32, device=dev)
-        ws = torch.empty(lib.sol_conv3d_thin_ws_floats(B, D, H, W), dtype=torch.float32, device=dev)
-        dW = torch.empty((5, 5, 5, 32, cin) if thin_out else (5, 5, 5, cin, 32), dtype=torch.float32, device=dev)
-        db = torch.empty(cin if thin_out else 32, dtype=torch.float32, device=dev)
-        if acc is not None:
-            acc[0].update(part=part, dW=dW, db=db, ws=ws, shape=shape_key)
-    first, last = (True, True) if acc is None else (acc[1], acc[2])
-    if acc is not None:
-        acc[0]["open"] = not last
+    f = lambda *n: torch.empty(*n, dtype=torch.float32, device=dev)
+    st, first, last = _acc_buffers("conv3d_thin_bwd_weight", acc, shape_key, lambda: dict(
+        part=f(lib.sol_conv3d_thin_bwd_weight_ws_floats(B, D, H, W)), ws=f(lib.sol_conv3d_thin_ws_floats(B, D, H, W)),
+        dW=f(5, 5, 5, 32, cin) if thin_out else f(5, 5, 5, cin, 32), db=f(cin if thin_out else 32)))
+    part, dW, db, ws = (st[k] for k in ("part", "dW", "db", "ws"))
     if thin_out:
         check(lib.sol_conv3d_thin_out_bwd_weight_acc(stream(), ptr(dz), ptr(zmax), ptr(x4), ptr(ws), ptr(part), ptr(dW), ptr(db), B, D, H, W, cin,
                                                      0 if first else 1, 1 if last else 0))
@@ -624,23 +568,10 @@ def conv3d_bwd_weight(xk, dz, cin, cout, xmax=None, zmax=None, acc=None):
     dzk = _pad_ch(dz, co_k)
     dev = xk.device
     shape_key = (B, D, H, W, cin_k, co_k, cin, str(dev))
-    if acc is not None and "part" in acc[0]:
-        # the partial sums of a reverse sweep live in the caller's state dict: they belong to ONE shape and to a sequence that was opened
-        # with first=True (the C entry point cannot see the size of `partial`, so a mismatch would overrun it or add onto stale sums)
-        if acc[0].get("shape") != shape_key:
-            raise _lib.SolError("conv3d_bwd_weight: the accumulation state was allocated for %s, this call has %s" % (acc[0].get("shape"), shape_key))
-        if not acc[1] and not acc[0].get("open"):
-            raise _lib.SolError("conv3d_bwd_weight: first=False on a state whose sequence is not open (the previous sweep ended with last=True)")
-        part, dW, db, scratch = (acc[0][k] for k in ("part", "dW", "db", "scratch"))
-    else:
-        if acc is not None and not acc[1]:
-            raise _lib.SolError("conv3d_bwd_weight: the first call on a fresh accumulation state must have first=True (nothing to add onto yet)")
-        part = torch.empty(lib.sol_conv3d_bwd_weight_ws_floats(B, D, H, W, cin_k, co_k), dtype=torch.float32, device=dev)
-        dW = torch.empty(5, 5, 5, cin, co_k, dtype=torch.float32, device=dev)
-        db = torch.empty(co_k, dtype=torch.float32, device=dev)
-        scratch = torch.empty(5 * co_k, dtype=torch.float32, device=dev)
-        if acc is not None:
-            acc[0].update(part=part, dW=dW, db=db, scratch=scratch, shape=shape_key)
+    f = lambda *n: torch.empty(*n, dtype=torch.float32, device=dev)
+    st, first, last = _acc_buffers("conv3d_bwd_weight", acc, shape_key, lambda: dict(
+        part=f(lib.sol_conv3d_bwd_weight_ws_floats(B, D, H, W, cin_k, co_k)), dW=f(5, 5, 5, cin, co_k), db=f(co_k), scratch=f(5 * co_k)))
+    part, dW, db, scratch = (st[k] for k in ("part", "dW", "db", "scratch"))
     both32 = cin_k == 32 and co_k == 32
     # (the slot tensors must outlive the call: a temporary inside ptr(...) is freed -- and its block handed to the next
     # allocation -- before the launch is even enqueued)
@@ -648,8 +579,6 @@ def conv3d_bwd_weight(xk, dz, cin, cout, xmax=None, zmax=None, acc=None):
     xmax = (xmax if xmax is not None else _absmax(xk)) if both32 else None
     zmax = (zmax if zmax is not None and dzk is dz else _absmax(dzk)) if both32 else None
     if acc is not None:
-        _, first, last = acc
-        acc[0]["open"] = not last
         check(lib.sol_conv3d_bwd_weight_acc(stream(), ptr(xk), ptr(dzk), ptr(xmax), ptr(zmax), ptr(part), ptr(dW), ptr(db), ptr(scratch),
                                             B, D, H, W, cin_k, co_k, cin, co_k, 0 if first else 1, 1 if last else 0))
         if not last:
@@ -678,9 +607,9 @@ class _Conv3DFn(torch.autograd.Function):
         ctx.packed_bwd = packs[1] if packs is not None else None
         res = None if residual is None else _lib.f32(residual)
         # the operand's absmax selects the fp16 three-product kernels (and, for 32 -> 32 layers, the one-launch 5x5x5 kernel)
-        if MarsMoon3D.thin_kpack and cin <= 4 and cout == 32 and res is None:      # the depth-packed one-launch form, as the fused network runs it
+        if cin <= 4 and cout == 32 and res is None:      # the depth-packed one-launch form, as the fused network runs it
             y = conv3d_thin(xk, _pack3d_thin(_lib.f32(w), cin, 0), _lib.f32(b), lrelu, slope)
-        elif MarsMoon3D.thin_kpack and MarsMoon3D.thin_out_kpack and cin == 32 and cout <= 4 and res is None and not lrelu:      # ... and the thin-output form
+        elif cin == 32 and cout <= 4 and res is None and not lrelu:      # ... and the thin-output form
             y = conv3d_thin_out(xk, _pack3d_thin_out(_lib.f32(w), cout, 0), _lib.f32(b), cout, _absmax(xk))
         else:
             y = conv3d(xk, packed, _lib.f32(b), res, cout, lrelu, slope, _absmax(xk) if cin_k == 32 else None)
@@ -695,9 +624,9 @@ class _Conv3DFn(torch.autograd.Function):
         dz = gy.contiguous()
         if lrelu:
             dz = dz * torch.where(y > 0, torch.ones_like(y), torch.full_like(y, slope))
-        if MarsMoon3D.thin_kpack and cin <= 4 and cout == 32 and xk.shape[3] == 64:
+        if cin <= 4 and cout == 32 and xk.shape[3] == 64:
             dW, db = conv3d_thin_bwd_weight(xk, dz, cin)
-        elif MarsMoon3D.thin_kpack and cin == 32 and cout <= 4 and xk.shape[3] == 64:
+        elif cin == 32 and cout <= 4 and xk.shape[3] == 64:
             dW, db = conv3d_thin_bwd_weight(_pad_ch(dz, 4), xk, cout, thin_out=True)
         else:
             dW, db = conv3d_bwd_weight(xk, dz, cin, cout)
@@ -705,9 +634,9 @@ class _Conv3DFn(torch.autograd.Function):
         co_k = 4 if cout <= 4 else 32
         packed = ctx.packed_bwd if ctx.packed_bwd is not None else _pack3d(_lib.f32(w), cout, cin, 1)
         dzk = _pad_ch(dz, co_k)
-        if MarsMoon3D.thin_kpack and cout <= 4 and cin == 32:
+        if cout <= 4 and cin == 32:
             dx = conv3d_thin(dzk, _pack3d_thin(_lib.f32(w), cout, 1), None, False, slope)
-        elif MarsMoon3D.thin_kpack and MarsMoon3D.thin_out_kpack and cin <= 4 and cout == 32:
+        elif cin <= 4 and cout == 32:
             dx = conv3d_thin_out(dzk, _pack3d_thin_out(_lib.f32(w), cin, 1), None, 4, _absmax(dzk))[..., :cin]
         else:
             dx = conv3d(dzk, packed, None, None, cin, False, slope, _absmax(dzk) if co_k == 32 else None)
@@ -715,96 +644,25 @@ class _Conv3DFn(torch.autograd.Function):
 
 
 class _MarsMoon3DFn(torch.autograd.Function):
-    """model_mars_moon (3-D) as ONE autograd node.  Forward: the twelve sol_conv3d launches, every layer handing the absmax slots
-    it published to its consumer (no pass over a tensor just to find its maximum).  Reverse sweep, written out by hand
-    (karman_train.py:101-138 differentiated): per layer the weight gradient (sol_conv3d_bwd_weight) and ONE data-gradient launch
-    whose epilogue adds the skip gradient of the residual block and multiplies by LeakyReLU'(saved activation)
-    (SOL_EPI_DLRELU) -- the compare / where / multiply / add / absmax passes of the per-layer form are gone."""
-
-    @staticmethod
-    def run_forward(net, x):
-        """(out, xk, amax, acts): the twelve launches; acts = the eleven 32-channel activations h0, a1, h1, ..., a5, h5"""
-        _lib.require_gpu()
-        p = [t.detach() for t in net.tensors()]
-        pk = net.train_packs()
-        sl, cout = net.slope, net.cout
-        xk = _pad_ch(_lib.f32(x.detach()), 4)
-        amax = torch.zeros(11, 256, dtype=torch.int32, device=xk.device)       # absmax slots of the eleven 32-channel activations
-        kp = net.thin_packs()
-        acts = [conv3d_thin(xk, kp[0], p[1], True, sl, amax[0]) if kp else conv3d(xk, pk[0][0], p[1], None, 32, True, sl, None, amax[0])]
-        for k in range(5):
-            a = conv3d(acts[-1], pk[1 + 2 * k][0], p[3 + 4 * k], None, 32, True, sl, amax[2 * k], amax[2 * k + 1])
-            acts.append(a)
-            acts.append(conv3d(a, pk[2 + 2 * k][0], p[5 + 4 * k], acts[-2], 32, True, sl, amax[2 * k + 1], amax[2 * k + 2]))
-        ko = net.thin_out_packs()
-        if ko:
-            out = conv3d_thin_out(acts[-1], ko[0], p[23], cout, amax[10])
-        else:
-            out = conv3d(acts[-1], pk[11][0], p[23], None, cout, False, sl, amax[10], None)
-        return out, xk, amax, acts
+    """model_mars_moon (3-D) as ONE autograd node over the net's schedule of the input's shape (schedule3d.NetSchedule3D): its twelve forward
+    launches and its hand-written reverse sweep, the weight gradients of this one call reduced at once."""
 
     @staticmethod
     def forward(ctx, x, params, net):
-        out, xk, amax, acts = _MarsMoon3DFn.run_forward(net, x)
-        ctx.net = net
+        ctx.net, ctx.sch = net, net.schedule(*x.shape[:4])
+        out, (xk, amax, acts) = ctx.sch.forward(x)
         ctx.save_for_backward(xk, amax, *acts)
         return out
 
     @staticmethod
-    def run_backward(net, xk, amax, acts, g_out, acc=None):
-        """(dx [B,Y,X,Z,4 (padded input channels)], flat gradient in get_weights() order) of the network for the output gradient g_out:
-        the reverse sweep written out by hand (used by the autograd node below and by Karman3DTrainer's hand-written schedule).
-        acc = (list of 12 per-layer state dicts, first, last): the weight gradients are ACCUMULATED over the calls of an unrolled reverse
-        sweep inside the kernels' partial buffers and reduced once, with the last call (conv3d_bwd_weight); the flat gradient is None before."""
-        A = (lambda l: None) if acc is None else (lambda l: (acc[0][l], acc[1], acc[2]))
-        pk = net.train_packs()
-        sl, cin, cout = net.slope, net.cin, net.cout
-        grads = [None] * 24
-        zm = torch.zeros(11, 256, dtype=torch.int32, device=xk.device)         # absmax slots of the eleven pre-activation gradients
-        g = _lib.f32(g_out).contiguous()                      # [.., cout], or already zero padded to 4 channels (the trainer's fused glue)
-        kp = net.thin_packs()
-        if g.shape[-1] == 4 and cout != 4:
-            g4, gc = g, None
-        else:
-            g4, gc = (_pad_ch(g, 4) if kp else None), g
-        if kp and g.shape[3] == 64:
-            grads[22], grads[23] = conv3d_thin_bwd_weight(g4, acts[10], cout, zmax=amax[10], acc=A(11), thin_out=True)
-        else:
-            gc = gc if gc is not None else g4[..., :cout].contiguous()
-            grads[22], grads[23] = conv3d_bwd_weight(acts[10], gc, 32, cout, xmax=amax[10], acc=A(11))
-        # d loss / d (pre-activation of the last residual block's output) = conv3d(g, flip(w11)^T) * lrelu'(h5)
-        if kp:
-            dz = conv3d_thin(g4, kp[1], None, False, sl, zm[10], act_ref=acts[10])
-        else:
-            dz = conv3d(g4 if g4 is not None else _pad_ch(gc, 4), pk[11][1], None, None, 32, False, sl, None, zm[10], act_ref=acts[10])
-        for k in range(4, -1, -1):
-            a, hprev = acts[1 + 2 * k], acts[2 * k]
-            # block k: h_k = lrelu(conv_b(a) + h_{k-1}), a = lrelu(conv_a(h_{k-1}))
-            grads[4 + 4 * k], grads[5 + 4 * k] = conv3d_bwd_weight(a, dz, 32, 32, xmax=amax[2 * k + 1], zmax=zm[2 * k + 2], acc=A(2 + 2 * k))
-            dz1 = conv3d(dz, pk[2 + 2 * k][1], None, None, 32, False, sl, zm[2 * k + 2], zm[2 * k + 1], act_ref=a)
-            grads[2 + 4 * k], grads[3 + 4 * k] = conv3d_bwd_weight(hprev, dz1, 32, 32, xmax=amax[2 * k], zmax=zm[2 * k + 1], acc=A(1 + 2 * k))
-            dz = conv3d(dz1, pk[1 + 2 * k][1], None, dz, 32, False, sl, zm[2 * k + 1], zm[2 * k], act_ref=hprev)
-        if kp and xk.shape[3] == 64 and cin <= 4:
-            grads[0], grads[1] = conv3d_thin_bwd_weight(xk, dz, cin, zmax=zm[0], acc=A(0))
-        else:
-            grads[0], grads[1] = conv3d_bwd_weight(xk, dz, cin, 32, acc=A(0))
-        ko = net.thin_out_packs()
-        if ko and xk.shape[-1] == 4:
-            dx = conv3d_thin_out(dz, ko[1], None, 4, zm[0])           # (channels >= cin of the packed kernel are zero)
-        else:
-            dx = conv3d(dz, pk[0][1], None, None, xk.shape[-1], False, sl, zm[0], None)
-        return dx, (None if grads[0] is None else torch.cat([t.reshape(-1) for t in grads]))
-
-    @staticmethod
     def backward(ctx, g_out):
-        net = ctx.net
         xk, amax, *acts = ctx.saved_tensors
-        dx, flat = _MarsMoon3DFn.run_backward(net, xk, amax, acts, g_out)
-        return dx[..., :net.cin], flat, None
+        dx, flat = ctx.sch.backward((xk, amax, acts), g_out)
+        return dx[..., :ctx.net.cin], flat, None
 
 
 def conv3d_fn(x, w, b, residual=None, lrelu=False, slope=0.3, packs=None):
-    """packs: optional (forward-packed, backward-data-packed) weight buffers of this layer (MarsMoon3D.train_packs)."""
+    """packs: optional (forward-packed, backward-data-packed) weight buffers of this layer (NetSchedule3D.layer_packs)."""
     return _Conv3DFn.apply(x, w, b, residual, lrelu, slope, packs)
 
 
@@ -863,6 +721,7 @@ class Karman3DTrainer:
         if schedule not in ("manual", "autograd"):
             raise ValueError("schedule must be 'manual' or 'autograd'")
         self.schedule = schedule
+        self.sch = net.schedule(B, Y, X, Z)     # the network's launches, packed weights and weight-gradient partials at this shape
 
     def _unrolled(self):
         if self.schedule == "manual":
@@ -882,10 +741,10 @@ class Karman3DTrainer:
         (to_feature's adjoint) -> solver adjoint (sol_karman3d_step_bwd)."""
         from .ops import l2_loss_fwd_bwd
         d, vy, vx, vz, re = self._in
-        net, sim, ms = self.net, self.sim, self.ms
+        net, sim, sch, ms = self.net, self.sim, self.sch, self.ms
         sc = self.scene
         B, Y, X, Z = self.B, sc.Y, sc.X, sc.Z
-        net._tpacks = None                          # the weights moved since the last step: re-pack once (inside the graph when captured)
+        sch.begin_step()                            # the weights moved since the last step: re-pack once (inside the graph when captured)
         fs = [1.0 / t for t in self._std_in_host]          # (host copies: a .tolist() of a device tensor is a synchronising copy -- illegal inside a capture)
         sv = self._std_v_host
         v = (vy, vx, vz)
@@ -895,17 +754,16 @@ class Karman3DTrainer:
             saved = [torch.empty_like(t) for t in v]
             feat = torch.empty(B, Y, X, Z, 4, dtype=torch.float32, device=vy.device)
             d, *v = sim._fwd(d, v[0], v[1], v[2], re, saved, feat, fs)
-            out, xk, amax, acts = _MarsMoon3DFn.run_forward(net, feat)
+            out, state = sch.forward(feat)
             check(self.lib.sol_karman3d_correct(stream(), ptr(out), net.cout, sv[0], sv[1], sv[2], ptr(v[0]), ptr(v[1]), ptr(v[2]), B, Y, X, Z))
             li, gi = l2_loss_fwd_bwd(v, tuple(g[i] for g in self._gt), sv, gscale=1.0 / ms)
             losses.append(li.reshape(()))
-            keep.append((saved, xk, amax, acts, gi))
+            keep.append((saved, state, gi))
         flat = None
         gin = None
-        wstate = [dict() for _ in range(12)]         # per layer: the weight-gradient partials of the whole reverse sweep (reduced once, at i = 0)
         inv_in = fs[:3]
         for i in range(ms - 1, -1, -1):
-            saved, xk, amax, acts, G = keep[i]
+            saved, state, G = keep[i]
             # G += gin and the adjoint of  v += std * to_staggered(out):  d out[..., c] = std_c * G_c restricted to the faces that received a correction
             # (one launch, zero padded to the four channels the thin-layer launches read; glue="torch": the elementwise composition of rounds 5-6)
             fused_glue = self.glue == "fused" and net.cout == 3
@@ -918,7 +776,7 @@ class Karman3DTrainer:
                     for c in range(3):
                         G[c].add_(gin[c])
                 dO = torch.stack([G[0][:, :Y] * sv[0], G[1][:, :, :X] * sv[1], G[2][..., :Z] * sv[2]], dim=-1)
-            dx, gflat = _MarsMoon3DFn.run_backward(net, xk, amax, acts, dO, acc=(wstate, i == ms - 1, i == 0))
+            dx, gflat = sch.backward(state, dO, i == ms - 1, i == 0)      # (the weight gradients accumulate over the sweep: reduced once, at i = 0)
             flat = gflat if gflat is not None else flat
             # adjoint of the feature map (the three components at the low faces of every cell, divided by std_in; the Re channel has no gradient)
             if fused_glue and dx.shape[-1] == 4:
@@ -943,7 +801,7 @@ class Karman3DTrainer:
         hand-written schedule (test_karman3d_manual_schedule_equals_autograd_composition) and the form of rounds 3-4."""
         d, vy, vx, vz, re = self._in
         self.net.params.grad = None
-        self.net._tpacks = None                     # the weights moved since the last step: re-pack once (inside the graph when captured)
+        self.sch.begin_step()                       # the weights moved since the last step: re-pack once (inside the graph when captured)
         v = (_lib.dclone(vy).requires_grad_(True), vx, vz)     # the state enters the graph (the step's autograd Function needs a grad-requiring input)
         losses = []
         for i in range(self.ms):
@@ -1000,7 +858,7 @@ class Karman3DTrainer:
         p = self.net.params.detach()
         check(self.lib.sol_adam_tf_step(stream(), ptr(p), ptr(self._grads), ptr(self.m), ptr(self.v),
                                         self.net.n_params, self.t, float(lr), self.beta1, self.beta2, self.eps, 0.0, None, 0, None))
-        self.net.invalidate()                       # both pack caches are stale now (the forward packs AND the training packs)
+        self.net.invalidate()                       # every schedule's packs are stale now (torch does not see this write)
 
     def train_step(self, d, vy, vx, vz, re, gts, lr):
         """One training step on this rank's simulations; returns the GLOBAL loss tensor (the sum over all ranks' simulations)."""
@@ -1013,6 +871,7 @@ class Karman3DRollout:
 
     def __init__(self, net, scene, B, std_v, std_re, dt=1.0, res=None, conv_precision="split", **solver):
         from .trainer import _conv_precision_code
+        from .schedule3d import NetSchedule3D
         _lib.require_gpu()
         self.lib = _lib.load()
         self.net, self.scene, self.B = net, scene, B
@@ -1022,43 +881,15 @@ class Karman3DRollout:
         self.conv_precision = _conv_precision_code(conv_precision)
         dev = scene.active.device
         Y, X, Z = scene.Y, scene.X, scene.Z
-        f = lambda c: torch.empty(B, Y, X, Z, c, dtype=torch.float32, device=dev)
-        self.feat = f(4)
-        self.h = [f(32), f(32), f(32)]          # block input / intermediate / block output, rotated
-        self.out = f(net.cout)
-        self.amax = torch.zeros(12, 256, dtype=torch.int32, device=dev)      # absmax slots of the 32-channel activations
+        self.feat = torch.empty(B, Y, X, Z, 4, dtype=torch.float32, device=dev)
+        self.sch = NetSchedule3D(net, B, Y, X, Z, train=False)      # forward only, in its own persistent buffers
+        self.out = self.sch.out
 
     def correction(self):
         """self.feat -> self.out (the network), publishing / consuming the per-tensor absmax of every 32-channel tensor."""
         from .trainer import _conv_precision_scope
         with _conv_precision_scope(self.conv_precision):
-            return self._correction()
-
-    def _correction(self):
-        pk = self.net.pack()
-        sl = self.net.slope
-        self.amax.zero_()
-        am = lambda k: self.amax[k]
-        h, a, n = self.h
-        kp = self.net.pack_thin()
-        if kp is not None:
-            if getattr(self, "_thin_ws", None) is None:
-                self._thin_ws = torch.empty(self.lib.sol_conv3d_thin_ws_floats(*self.feat.shape[:4]), dtype=torch.float32, device=self.feat.device)
-            conv3d_thin(self.feat, kp, pk[0][1], True, sl, am(0), out=h, ws=self._thin_ws)
-        else:
-            conv3d(self.feat, pk[0][0], pk[0][1], None, 32, True, sl, None, am(0), out=h)
-        for k in range(5):
-            conv3d(h, pk[1 + 2 * k][0], pk[1 + 2 * k][1], None, 32, True, sl, am(2 * k), am(2 * k + 1), out=a)
-            conv3d(a, pk[2 + 2 * k][0], pk[2 + 2 * k][1], h, 32, True, sl, am(2 * k + 1), am(2 * k + 2), out=n)
-            h, n = n, h
-        ko = self.net.pack_thin_out()
-        if ko is not None:
-            if getattr(self, "_thin_ws", None) is None:
-                self._thin_ws = torch.empty(self.lib.sol_conv3d_thin_ws_floats(*self.feat.shape[:4]), dtype=torch.float32, device=self.feat.device)
-            conv3d_thin_out(h, ko, pk[11][1], self.net.cout, am(10), out=self.out, ws=self._thin_ws)
-        else:
-            conv3d(h, pk[11][0], pk[11][1], None, self.net.cout, False, sl, am(10), None, out=self.out)
-        return self.out
+            return self.sch.forward(self.feat)[0]
 
     def step(self, d, vy, vx, vz, re):
         d, vy, vx, vz = self.sim.step(d, vy, vx, vz, re, feat_out=self.feat, feat_scale=self.feat_scale)

@@ -689,7 +689,7 @@ def test_karman3d_training_step_gradient_by_finite_differences():
         for sgn in (1.0, -1.0):
             with torch.no_grad():
                 net.params.copy_((p0.double() + sgn * eps * u).float())
-            net._tpacks = None
+            net.invalidate()
             vals.append(float(tr.fwd_bwd(*st, re, gts)))
         res[eps] = (vals[0] - vals[1]) / (2 * eps)
     with torch.no_grad():
@@ -976,3 +976,68 @@ def test_karman3d_fused_reverse_sweep_glue_equals_the_torch_composition(shape):
     f, t = res["fused"], res["torch"]
     assert np.isfinite(f[0]) and torch.equal(f[1], t[1])
     assert float(f[2].abs().max()) > 0 and rel(f[2], t[2]) < 2e-6, rel(f[2], t[2])
+
+
+@pytest.mark.parametrize("shape", [(1, 4, 64, 64), (2, 5, 16, 16)])
+def test_rollout_schedule_forward_equals_training_forward_bit_for_bit(shape):
+    """NetSchedule3D(train=False), the roll-out's form of the network (persistent rotating buffers, forward packs only), against the training
+    form behind net(x) / net.activations(x): one launch sequence, so the output and the last block's output agree bit for bit -- at 64-pixel
+    rows (one-launch Conv3D kernels) and at 16 (five-pass forms).  A second input through the same persistent buffers equals a fresh
+    schedule's result: nothing of the first call survives in the slots or the rotating tensors."""
+    import make_golden as mg
+    from sol_amd.schedule3d import NetSchedule3D
+    B, D, H, W = shape
+    gen = torch.Generator().manual_seed(23)
+    xs = [torch.randn(B, D, H, W, 4, generator=gen, dtype=torch.float32).to(DEV) for _ in range(2)]
+    net = k3.MarsMoon3D(device=DEV)
+    net.set_weights([p.numpy() for p in mg.k3d_params()])
+    ro = NetSchedule3D(net, B, D, H, W, train=False)
+    for i, x in enumerate(xs):
+        out, (_, _, acts) = ro.forward(x)
+        with torch.no_grad():
+            ref = net(x)
+        assert out is ro.out and torch.equal(out, ref), (i, rel(out, ref))
+        assert torch.equal(acts[-1], net.activations(x)[-1]), i
+        assert float(out.abs().max()) > 0
+    fresh, (_, _, facts) = NetSchedule3D(net, B, D, H, W, train=False).forward(xs[1])
+    assert torch.equal(ro.out, fresh) and torch.equal(acts[-1], facts[-1])
+    assert not torch.equal(fresh, NetSchedule3D(net, B, D, H, W, train=False).forward(xs[0])[0])
+    with pytest.raises(sol_amd._lib.SolError, match="forward pass only"):
+        ro.backward((None, None, None), fresh)
+
+
+def test_packed_weights_follow_the_parameters_across_objects_sharing_one_net():
+    """One staleness rule (MarsMoon3D.params_key): a roll-out whose packs are warm, then a training step on the SAME net (the library's Adam
+    writes the parameters behind torch's back; apply_gradients announces it) -- the roll-out's next step is the step of a fresh roll-out on a
+    fresh net holding get_weights(), bit for bit, and differs from the step before training.  The same for net(x) after a write through
+    `params.data` followed by invalidate()."""
+    B, Y, X, Z = 1, 16, 8, 8
+    std_v = (0.2, 0.25, 0.3)
+    sc = k3.Scene3D(Y, X, Z, device=DEV)
+    gen = torch.Generator().manual_seed(29)
+    r = lambda *s: torch.randn(*s, generator=gen, dtype=torch.float32).to(DEV)
+    st = (torch.rand(B, Y, X, Z, generator=gen, dtype=torch.float32).to(DEV), 1.0 + 0.2 * r(B, Y + 1, X, Z), 0.2 * r(B, Y, X + 1, Z), 0.2 * r(B, Y, X, Z + 1))
+    re = f32(o.RE_TRAIN[:B])
+    gts = [(1.0 + 0.2 * r(B, Y + 1, X, Z), 0.2 * r(B, Y, X + 1, Z), 0.2 * r(B, Y, X, Z + 1))]
+
+    def fresh_copy():
+        twin = k3.MarsMoon3D(seed=1, device=DEV)
+        twin.set_weights(net.get_weights())
+        return twin
+
+    net = k3.MarsMoon3D(seed=3, device=DEV)
+    ro = k3.Karman3DRollout(net, sc, B, std_v, o.STD_RE)
+    before = [t.clone() for t in ro.step(*st, re)]                      # the roll-out's packs are warm now
+    tr = k3.Karman3DTrainer(net, sc, B, 1, std_v, o.STD_RE)
+    tr.train_step(*st, re, gts, lr=1e-3)
+    after = ro.step(*st, re)
+    ref = k3.Karman3DRollout(fresh_copy(), sc, B, std_v, o.STD_RE).step(*st, re)
+    for a, b, c in zip(after[1:], ref[1:], before[1:]):
+        assert torch.equal(a, b) and not torch.equal(a, c)
+    x = r(B, Y, X, Z, 4)
+    with torch.no_grad():
+        y0 = net(x)
+        net.params.data.add_(0.01 * r(net.n_params))                    # torch's version counter does not see this write
+        net.invalidate()
+        y1 = net(x)
+        assert torch.equal(y1, fresh_copy()(x)) and not torch.equal(y1, y0)

@@ -100,3 +100,11 @@ def test_cabi_exports_the_3d_entry_points():
     assert 6 * 2 * 128 * 64 * 64 * 4 < nb < 6.3 * 2 * 128 * 64 * 64 * 4          # three components + three cell buffers
     assert lib.sol_conv3d_packed_floats(32, 32) >= 5 * lib.sol_conv5x5_packed_floats(32, 32, 0)
     assert sol_amd._lib.get_option("k3d_tile") == 0
+
+
+def test_schedule3d_imports_without_a_gpu_and_has_no_cpu_form():
+    """schedule3d is host code over the C ABI: importable anywhere, but a NetSchedule3D is refused without a GPU (and for parameters that
+    are not on one), as schedule2d.NetSchedule2D is."""
+    from sol_amd import schedule3d
+    with pytest.raises(sol_amd.SolError):
+        schedule3d.NetSchedule3D(k3.MarsMoon3D(device="cpu"), 1, 16, 8, 8)
