@@ -300,6 +300,77 @@ int sol_karman_density_bwd_re(const sol_karman_cfg* cfg, void* stream,
                               void* workspace, size_t workspace_bytes,
                               const float* vy_in, const float* vx_in, float* g_re, int accumulate_re);
 
+/* BUOYANCY on the large-grid step (csrc/karman_buoyancy.hip; multi-launch path only): the marker density pushes the velocity, as PhiFlow's
+ * IncompressibleFlow.step does with buoyancy_factor != 0.  F = (fy, fx) is a force per unit density (PhiFlow's -gravity * buoyancy_factor
+ * with Gravity() = -9.81 along y gives F = (9.81 beta, 0)); it travels as two floats, sol_karman_cfg is unchanged.  With c the
+ * post-diffusion velocity, one step is
+ *     d_out = SL(d_in [+ inflow], c) [+ inflow dt]                                                          (unchanged)
+ *     a_y[jf,i] = mask_y[jf,i] * ( SL_y(c)[jf,i] + dt F_y * (dz(jf-1,i) + dz(jf,i)) / 2 )   jf = 0..Y
+ *     a_x[j,if] = mask_x[j,if] * ( SL_x(c)[j,if] + dt F_x * (dz(j,if-1) + dz(j,if)) / 2 )   if = 0..X
+ *     dz = d_out inside the grid, 0 outside (the zero ghost ring the density's advection uses)
+ *     v_out = a - mask * grad( solve(div a) )                                                               (unchanged)
+ * The force acts on the step's OUTPUT density, the inflow already in it (advect, effects, buoyancy, projection: PhiFlow 1.5.1's order as
+ * recalled, unpinned -- DESIGN.md section 4.7).  fp32 spelling of a face: fl(v + fl(fl(dt*F) * fl(0.5f * (d0 + d1)))) * mask, no
+ * contraction; fl(dt*F) is formed on the host.  A component whose force is zero is not touched; F = (0, 0) issues the plain call's
+ * launches and gives its bits.  One extra streaming launch (k_l_buoyancy) between the advection and the divergence, for the direct, the
+ * scattered-direct and the CG solve alike.  A non-zero force needs d_in, inflow and d_out.
+ *   sol_karman_step_fwd_large_saved_buoy: sol_karman_step_fwd_large_saved with the force.
+ *   sol_karman_step_fwd_large_buoy: the no-grad step with features, either solver as the cfg selects it (cfg.direct set: arguments as
+ *     sol_karman_step_fwd_large, the box / cg arguments and p_inout unread and p_inout must be NULL; cfg.direct NULL: as
+ *     sol_karman_step_fwd_large_cg, p_inout given = the warm-started form), workspace as for that plain call.
+ * Adjoint.  With g_a the cotangent of a that the velocity adjoint forms (it carries the face mask),
+ *     g_dsum[j,i] = g_d_out[j,i] + dt F_y (g_ay[j,i] + g_ay[j+1,i]) / 2 + dt F_x (g_ax[j,i] + g_ax[j,i+1]) / 2
+ * and then the two existing adjoints, unchanged: the velocity adjoint's scatter and diffusion adjoint on g_a, the density adjoint on g_dsum.
+ *   sol_karman_step_bwd_large_buoy / _buoy_re: every argument of sol_karman_step_bwd_large / _re, then fy, fx, g_d_out [B,Y,X] (the
+ *     cotangent of the step's output density; NULL = zero) and g_dsum [B,Y,X] (written).  They issue the plain call's launches (g_vy_in,
+ *     g_vx_in, g_re are the plain call's bits) and one more (k_lb_buoyancy_adj: a gather, no atomics, fixed order, bit-reproducible); same
+ *     workspace as the plain call.  The caller then runs sol_karman_density_bwd(_re) with g_dsum as its g_d_out and accumulate = 1.  A
+ *     non-finite g_a of a simulation makes ALL of that simulation's g_dsum NaN, so the density adjoint poisons g_d_in and, through the
+ *     accumulation, every other gradient of the simulation.  g_dsum must not alias another argument.
+ *   sol_karman_buoyancy_add / _add_bwd: the term alone and its exact transpose, any Y, X >= 1, for tests and callers that compose by hand:
+ *     vy, vx (in place) = (v + f * face average of d) * mask with f = (fy_dt, fx_dt) = dt F;  g_dsum = g_d_out (NULL = zero) + the
+ *     transpose applied to (mask g_vy, mask g_vx).
+ * None of these synchronises, allocates or reads anything on the host: capturable. */
+int sol_karman_step_fwd_large_saved_buoy(const sol_karman_cfg* cfg, void* stream,
+                                         const float* d_in, const float* vy_in, const float* vx_in,
+                                         const float* re, const float* active, const float* inflow,
+                                         const float* velBCy, const float* velBCyMask, int64_t bc_batch_stride,
+                                         float* d_out, float* vy_out, float* vx_out, float* saved_vy, float* saved_vx,
+                                         const int32_t* direct_header_host,
+                                         const float* box_blob, const int32_t* box_header_host, int32_t* cg_info,
+                                         void* workspace, size_t workspace_bytes, float fy, float fx);
+int sol_karman_step_fwd_large_buoy(const sol_karman_cfg* cfg, void* stream,
+                                   const float* d_in, const float* vy_in, const float* vx_in,
+                                   const float* re, const float* active, const float* inflow,
+                                   const float* velBCy, const float* velBCyMask, int64_t bc_batch_stride,
+                                   float* d_out, float* vy_out, float* vx_out,
+                                   float* feat_out, const float* feat_scale,
+                                   const int32_t* direct_header_host,
+                                   const float* box_blob, const int32_t* box_header_host, int32_t* cg_info,
+                                   float* p_inout, void* workspace, size_t workspace_bytes, float fy, float fx);
+int sol_karman_step_bwd_large_buoy(const sol_karman_cfg* cfg, void* stream,
+                                   const float* saved_vy, const float* saved_vx, const float* re, const float* active,
+                                   const float* velBCyMask, int64_t bc_batch_stride,
+                                   const float* g_vy_out, const float* g_vx_out, float* g_vy_in, float* g_vx_in,
+                                   const int32_t* direct_header_host,
+                                   const float* box_blob, const int32_t* box_header_host, int32_t* cg_info,
+                                   void* workspace, size_t workspace_bytes,
+                                   float fy, float fx, const float* g_d_out, float* g_dsum);
+int sol_karman_step_bwd_large_buoy_re(const sol_karman_cfg* cfg, void* stream,
+                                      const float* saved_vy, const float* saved_vx, const float* re, const float* active,
+                                      const float* velBCyMask, int64_t bc_batch_stride,
+                                      const float* g_vy_out, const float* g_vx_out, float* g_vy_in, float* g_vx_in,
+                                      const int32_t* direct_header_host,
+                                      const float* box_blob, const int32_t* box_header_host, int32_t* cg_info,
+                                      void* workspace, size_t workspace_bytes,
+                                      const float* vy_in, const float* vx_in, float* g_re, int accumulate_re,
+                                      float fy, float fx, const float* g_d_out, float* g_dsum);
+int sol_karman_buoyancy_add(void* stream, int32_t B, int32_t Y, int32_t X, const float* active, const float* d,
+                            float fy_dt, float fx_dt, float* vy, float* vx);
+int sol_karman_buoyancy_add_bwd(void* stream, int32_t B, int32_t Y, int32_t X, const float* active,
+                                const float* g_vy, const float* g_vx, float fy_dt, float fx_dt,
+                                const float* g_d_out, float* g_dsum);
+
 /* active  [Y,X]  1 - obstacle mask (cell centres inside Obstacle geometries -> 0)
  * inflow  [Y,X]  inflow rate mask (Inflow(box[5:10,25:75]) -> 1 inside)
  * velBCy, velBCyMask  [Y+1,X] (bc_batch_stride 0) or [B,Y+1,X] (stride (Y+1)*X)

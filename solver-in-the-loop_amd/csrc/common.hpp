@@ -44,7 +44,16 @@ struct SolLargeStep {
     int64_t bc_stride;
     float *d_out, *vy_out, *vx_out, *feat_out;
     const float* feat_scale;
+    float buoy_y = 0.f, buoy_x = 0.f;      // dt F of the buoyancy term (karman_buoyancy.hip); both zero = none: the plain step's launches
 };
+// the buoyancy term onto the advected velocity (f = dt F; nothing is launched for f = (0, 0)) and its transpose (karman_buoyancy.hip):
+// g_dsum = g_d_out (NULL = zero) + the face-to-cell transpose of (gy, gx); gmax = the absmax slots of k_lb_ga or NULL (poisoning)
+int sol_buoyancy_add(hipStream_t s, int B, int Y, int X, const float* active, const float* d, float fy, float fx, float* vy, float* vx);
+int sol_buoyancy_adj(hipStream_t s, int B, int Y, int X, const float* active, const float* gy, const float* gx, const unsigned* gmax,
+                     float fy, float fx, const float* g_d_out, float* g_dsum);
+// sol_karman_step_fwd_large under the caller's name (karman_large.hip): the direct-solve step with features, shared with its buoyant form
+int sol_large_direct_step(const char* who, const sol_karman_cfg* c, void* stream, const SolLargeStep& io, const int32_t* direct_header_host,
+                          void* workspace, size_t workspace_bytes);
 int sol_large_front(const sol_karman_cfg* c, hipStream_t s, const SolLargeStep& io, float* svy, float* svx, float* rhs);
 int sol_large_project(const sol_karman_cfg* c, hipStream_t s, const SolLargeStep& io, const float* p);
 int sol_large_box_forward(hipStream_t s, int B, int Y, int X, const float* blob, const float* src, float* T1, float* T2, const int* skip);

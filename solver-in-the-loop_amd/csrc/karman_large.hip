@@ -366,6 +366,9 @@ int sol_large_front(const sol_karman_cfg* c, hipStream_t s, const SolLargeStep& 
     const int B = c->B, N = c->Y * c->X, faces = (c->Y + 1) * c->X + c->Y * (c->X + 1);
     SOL_LAUNCH(k_l_diffuse, dim3((faces + 255) / 256, B), dim3(256), 0, s, a);
     SOL_LAUNCH(k_l_advect, dim3((faces + N + 255) / 256, B), dim3(256), 0, s, a);
+    // buoyancy (optional; io.buoy = dt F): the step's output density pushes the advected velocity (karman_buoyancy.hip)
+    SOL_REQUIRE((io.buoy_y == 0.f && io.buoy_x == 0.f) || (io.d_in && io.inflow && io.d_out), "a buoyancy force needs the density: d_in, inflow and d_out");
+    if (int e = sol_buoyancy_add(s, B, c->Y, c->X, io.active, io.d_out, io.buoy_y, io.buoy_x, io.vy_out, io.vx_out)) return e;
     SOL_LAUNCH(k_l_div, dim3((N + 255) / 256, B), dim3(256), 0, s, a);
     SOL_LAUNCH_CHECK();
     return SOL_OK;
@@ -543,6 +546,27 @@ extern "C" size_t sol_karman_step_large_workspace_bytes_for(const sol_karman_cfg
     return floats * sizeof(float);
 }
 
+// the direct-solve step of sol_karman_step_fwd_large (and of its buoyant form, sol_karman_step_fwd_large_buoy in pcg.hip)
+int sol_large_direct_step(const char* who, const sol_karman_cfg* c, void* stream, const SolLargeStep& io, const int32_t* direct_header_host,
+                          void* workspace, size_t workspace_bytes) {
+    SOL_REQUIRE(c != nullptr, "cfg is NULL");
+    SOL_REQUIRE(c->B >= 1 && c->Y >= 16 && c->X >= 16, "%s: B >= 1, Y, X >= 16 (got %d, %d, %d)", who, c->B, c->Y, c->X);
+    SOL_REQUIRE(io.vy_in && io.vx_in && io.re && io.active && io.velBCy && io.velBCyMask && io.vy_out && io.vx_out && workspace,
+                "%s: NULL pointer argument", who);
+    SOL_REQUIRE((io.d_in && io.inflow) || !io.d_out, "density output requested without d_in/inflow");
+    SOL_REQUIRE(!io.feat_out || io.feat_scale, "feat_out requires feat_scale");
+    SOL_REQUIRE(c->direct && c->direct_n > 0, "%s needs the direct-solver blob (cfg.direct)", who);
+    SOL_REQUIRE(io.vy_in != io.vy_out && io.vx_in != io.vx_out && io.d_in != io.d_out, "%s: outputs must not alias the inputs", who);
+    if (int e = sol_large_direct_check(c, who, direct_header_host)) return e;
+    SOL_REQUIRE(workspace_bytes >= sol_karman_step_large_workspace_bytes_for(c, direct_header_host), "workspace too small");
+    const size_t B = c->B, Y = c->Y, X = c->X;
+    // workspace carve: sv_y, sv_x, the solver's buffers
+    float* w = static_cast<float*>(workspace);
+    float* svy = w; w += B * (Y + 1) * X;
+    float* svx = w; w += B * Y * (X + 1);
+    return sol_large_step(c, (hipStream_t)stream, io, svy, svx, true, direct_header_host, nullptr, nullptr, w);
+}
+
 extern "C" int sol_karman_step_fwd_large(const sol_karman_cfg* c, void* stream,
                                          const float* d_in, const float* vy_in, const float* vx_in,
                                          const float* re, const float* active, const float* inflow,
@@ -551,22 +575,8 @@ extern "C" int sol_karman_step_fwd_large(const sol_karman_cfg* c, void* stream,
                                          float* feat_out, const float* feat_scale,
                                          const int32_t* direct_header_host,
                                          void* workspace, size_t workspace_bytes) {
-    SOL_REQUIRE(c != nullptr, "cfg is NULL");
-    SOL_REQUIRE(c->B >= 1 && c->Y >= 16 && c->X >= 16, "sol_karman_step_fwd_large: B >= 1, Y, X >= 16 (got %d, %d, %d)", c->B, c->Y, c->X);
-    SOL_REQUIRE(vy_in && vx_in && re && active && velBCy && velBCyMask && vy_out && vx_out && workspace, "sol_karman_step_fwd_large: NULL pointer argument");
-    SOL_REQUIRE((d_in && inflow) || !d_out, "density output requested without d_in/inflow");
-    SOL_REQUIRE(!feat_out || feat_scale, "feat_out requires feat_scale");
-    SOL_REQUIRE(c->direct && c->direct_n > 0, "sol_karman_step_fwd_large needs the direct-solver blob (cfg.direct)");
-    SOL_REQUIRE(vy_in != vy_out && vx_in != vx_out && d_in != d_out, "sol_karman_step_fwd_large: outputs must not alias the inputs");
-    if (int e = sol_large_direct_check(c, "sol_karman_step_fwd_large", direct_header_host)) return e;
-    SOL_REQUIRE(workspace_bytes >= sol_karman_step_large_workspace_bytes_for(c, direct_header_host), "workspace too small");
-    const size_t B = c->B, Y = c->Y, X = c->X;
-    // workspace carve: sv_y, sv_x, the solver's buffers
-    float* w = static_cast<float*>(workspace);
-    float* svy = w; w += B * (Y + 1) * X;
-    float* svx = w; w += B * Y * (X + 1);
     const SolLargeStep io{d_in, vy_in, vx_in, re, active, inflow, velBCy, velBCyMask, bc_batch_stride, d_out, vy_out, vx_out, feat_out, feat_scale};
-    return sol_large_step(c, (hipStream_t)stream, io, svy, svx, true, direct_header_host, nullptr, nullptr, w);
+    return sol_large_direct_step("sol_karman_step_fwd_large", c, stream, io, direct_header_host, workspace, workspace_bytes);
 }
 
 extern "C" int sol_karman_correct(void* stream, const float* out, float* vy, float* vx, float* cor_y, float* cor_x,

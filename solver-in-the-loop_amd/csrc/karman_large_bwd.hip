@@ -1,5 +1,6 @@
 // Adjoint of the large-grid karman-2d step (karman_large.hip) with respect to its input velocity, for both pressure solvers.
-// The density is a passive tracer: no adjoint, as on the one-workgroup path.  The chain is the 2-D projection of the 3-D adjoint
+// The density is a passive tracer here: its own adjoint is karman_density_bwd.hip, and the buoyant step's coupling (the density pushes the
+// velocity) is the one extra launch of sol_karman_step_bwd_large_buoy (karman_buoyancy.hip).  The chain is the 2-D projection of the 3-D adjoint
 // (karman3d.hip, "Adjoint of the 3-D step"); stages in reverse order of the forward step:
 //   k_lb_rhs          q = G^T (mask . g_out)                  adjoint of  out = v~ - mask . G p.  Boundary faces: with replicate padding
 //                                                              their pressure gradient is zero (they do not depend on p), with dirichlet0
@@ -278,15 +279,17 @@ extern "C" size_t sol_karman_step_bwd_large_workspace_bytes_for(const sol_karman
     return bwd_layout(c, c->direct != nullptr, nullptr, direct_header_host).bytes;
 }
 
-extern "C" int sol_karman_step_fwd_large_saved(const sol_karman_cfg* c, void* stream,
-                                               const float* d_in, const float* vy_in, const float* vx_in,
-                                               const float* re, const float* active, const float* inflow,
-                                               const float* velBCy, const float* velBCyMask, int64_t bc_batch_stride,
-                                               float* d_out, float* vy_out, float* vx_out, float* saved_vy, float* saved_vx,
-                                               const int32_t* direct_header_host,
-                                               const float* box_blob, const int32_t* box_header_host, int32_t* cg_info,
-                                               void* workspace, size_t workspace_bytes) {
-    const char* who = "sol_karman_step_fwd_large_saved";
+namespace {
+
+// sol_karman_step_fwd_large_saved, and with a force F = (fy, fx) its buoyant form (karman_buoyancy.hip)
+int fwd_large_saved(const char* who, const sol_karman_cfg* c, void* stream,
+                    const float* d_in, const float* vy_in, const float* vx_in,
+                    const float* re, const float* active, const float* inflow,
+                    const float* velBCy, const float* velBCyMask, int64_t bc_batch_stride,
+                    float* d_out, float* vy_out, float* vx_out, float* saved_vy, float* saved_vx,
+                    const int32_t* direct_header_host,
+                    const float* box_blob, const int32_t* box_header_host, int32_t* cg_info,
+                    void* workspace, size_t workspace_bytes, float fy, float fx) {
     if (int e = common_check(c, who)) return e;
     const bool direct = c->direct != nullptr;
     SOL_REQUIRE(vy_in && vx_in && re && active && velBCy && velBCyMask && vy_out && vx_out && saved_vy && saved_vx && workspace,
@@ -302,13 +305,53 @@ extern "C" int sol_karman_step_fwd_large_saved(const sol_karman_cfg* c, void* st
         for (const void* i : ins) SOL_REQUIRE(!o || o != i, "%s: outputs must not alias the inputs", who);
     SOL_REQUIRE(saved_vy != vy_out && saved_vx != vx_out && saved_vy != saved_vx, "%s: saved_vy / saved_vx must be buffers of their own", who);
     void* solver = reinterpret_cast<void*>((reinterpret_cast<uintptr_t>(workspace) + 255) / 256 * 256);
-    const SolLargeStep io{d_in, vy_in, vx_in, re, active, inflow, velBCy, velBCyMask, bc_batch_stride, d_out, vy_out, vx_out, nullptr, nullptr};
+    SOL_REQUIRE(fy - fy == 0.f && fx - fx == 0.f, "%s: the force must be finite (got %g, %g)", who, (double)fy, (double)fx);
+    SOL_REQUIRE((fy == 0.f && fx == 0.f) || (d_in && inflow && d_out), "%s: a non-zero force needs d_in, inflow and d_out", who);
+    SolLargeStep io{d_in, vy_in, vx_in, re, active, inflow, velBCy, velBCyMask, bc_batch_stride, d_out, vy_out, vx_out, nullptr, nullptr};
+    io.buoy_y = c->dt * fy; io.buoy_x = c->dt * fx;
     return sol_large_step(c, (hipStream_t)stream, io, saved_vy, saved_vx, direct, direct_header_host, box_blob, cg_info, solver);
+}
+
+}  // namespace
+
+extern "C" int sol_karman_step_fwd_large_saved(const sol_karman_cfg* c, void* stream,
+                                               const float* d_in, const float* vy_in, const float* vx_in,
+                                               const float* re, const float* active, const float* inflow,
+                                               const float* velBCy, const float* velBCyMask, int64_t bc_batch_stride,
+                                               float* d_out, float* vy_out, float* vx_out, float* saved_vy, float* saved_vx,
+                                               const int32_t* direct_header_host,
+                                               const float* box_blob, const int32_t* box_header_host, int32_t* cg_info,
+                                               void* workspace, size_t workspace_bytes) {
+    const char* who = "sol_karman_step_fwd_large_saved";
+    return fwd_large_saved(who, c, stream, d_in, vy_in, vx_in, re, active, inflow, velBCy, velBCyMask, bc_batch_stride, d_out, vy_out, vx_out,
+                           saved_vy, saved_vx, direct_header_host, box_blob, box_header_host, cg_info, workspace, workspace_bytes, 0.f, 0.f);
+}
+
+extern "C" int sol_karman_step_fwd_large_saved_buoy(const sol_karman_cfg* c, void* stream,
+                                                    const float* d_in, const float* vy_in, const float* vx_in,
+                                                    const float* re, const float* active, const float* inflow,
+                                                    const float* velBCy, const float* velBCyMask, int64_t bc_batch_stride,
+                                                    float* d_out, float* vy_out, float* vx_out, float* saved_vy, float* saved_vx,
+                                                    const int32_t* direct_header_host,
+                                                    const float* box_blob, const int32_t* box_header_host, int32_t* cg_info,
+                                                    void* workspace, size_t workspace_bytes, float fy, float fx) {
+    const char* who = "sol_karman_step_fwd_large_saved_buoy";
+    return fwd_large_saved(who, c, stream, d_in, vy_in, vx_in, re, active, inflow, velBCy, velBCyMask, bc_batch_stride, d_out, vy_out, vx_out,
+                           saved_vy, saved_vx, direct_header_host, box_blob, box_header_host, cg_info, workspace, workspace_bytes, fy, fx);
 }
 
 namespace {
 
-// the launches of sol_karman_step_bwd_large; with rx, followed by the Reynolds-number reduction over the g_c they leave in the workspace
+// the buoyant step's extra (sol_karman_step_bwd_large_buoy): the force, the cotangent of the step's output density (NULL = zero) and where
+// g_dsum [B,Y,X] goes -- what the caller hands to the density adjoint as ITS g_d_out
+struct BuoyExtra {
+    float fy, fx;
+    const float* g_d_out;
+    float* g_dsum;
+};
+
+// the launches of sol_karman_step_bwd_large; with bx, followed by the transpose of the buoyancy term over the g_a they leave in the
+// workspace (k_lb_buoyancy_adj, karman_buoyancy.hip); with rx, followed by the Reynolds-number reduction over the g_c they leave in the workspace
 // (sol_karman_step_bwd_large_re): g_vy_in / g_vx_in are the same launches' results either way
 int bwd_large(const char* who, const sol_karman_cfg* c, void* stream,
               const float* saved_vy, const float* saved_vx, const float* re, const float* active,
@@ -316,9 +359,11 @@ int bwd_large(const char* who, const sol_karman_cfg* c, void* stream,
               const float* g_vy_out, const float* g_vx_out, float* g_vy_in, float* g_vx_in,
               const int32_t* direct_header_host,
               const float* box_blob, const int32_t* box_header_host, int32_t* cg_info,
-              void* workspace, size_t workspace_bytes, const ReExtra* rx) {
+              void* workspace, size_t workspace_bytes, const ReExtra* rx, const BuoyExtra* bx = nullptr) {
     if (int e = common_check(c, who)) return e;
     SOL_REQUIRE(!rx || (rx->vy_in && rx->vx_in && rx->g_re), "%s: NULL pointer argument", who);
+    SOL_REQUIRE(!bx || bx->g_dsum, "%s: NULL pointer argument (g_dsum)", who);
+    SOL_REQUIRE(!bx || (bx->fy - bx->fy == 0.f && bx->fx - bx->fx == 0.f), "%s: the force must be finite", who);
     const bool direct = c->direct != nullptr;
     SOL_REQUIRE(saved_vy && saved_vx && re && active && velBCyMask && g_vy_out && g_vx_out && g_vy_in && g_vx_in && workspace,
                 "%s: NULL pointer argument", who);
@@ -327,12 +372,15 @@ int bwd_large(const char* who, const sol_karman_cfg* c, void* stream,
     const size_t plain = bwd_layout(c, direct, nullptr, direct ? direct_header_host : nullptr).bytes;
     const size_t need = plain + (rx ? sol_re_partial_bytes(c) : 0);
     SOL_REQUIRE(workspace_bytes >= need, "%s: workspace too small (%zu < %zu bytes)", who, workspace_bytes, need);
-    const void* outs[] = {g_vy_in, g_vx_in, cg_info, rx ? rx->g_re : nullptr};
-    const void* ins[] = {saved_vy, saved_vx, re, active, velBCyMask, g_vy_out, g_vx_out, box_blob, rx ? rx->vy_in : nullptr, rx ? rx->vx_in : nullptr};
+    const void* outs[] = {g_vy_in, g_vx_in, cg_info, rx ? rx->g_re : nullptr, bx ? bx->g_dsum : nullptr};
+    const void* ins[] = {saved_vy, saved_vx, re, active, velBCyMask, g_vy_out, g_vx_out, box_blob, rx ? rx->vy_in : nullptr, rx ? rx->vx_in : nullptr,
+                         bx ? bx->g_d_out : nullptr};
     for (const void* o : outs)
         for (const void* i : ins) SOL_REQUIRE(!o || o != i, "%s: outputs must not alias the inputs", who);
     SOL_REQUIRE(g_vy_in != g_vx_in, "%s: g_vy_in and g_vx_in must be buffers of their own", who);
     SOL_REQUIRE(!rx || (rx->g_re != g_vy_in && rx->g_re != g_vx_in && (void*)rx->g_re != (void*)cg_info), "%s: g_re must be a buffer of its own", who);
+    SOL_REQUIRE(!bx || (bx->g_dsum != g_vy_in && bx->g_dsum != g_vx_in && (void*)bx->g_dsum != (void*)cg_info && (!rx || bx->g_dsum != rx->g_re)),
+                "%s: g_dsum must be a buffer of its own", who);
     const int B = c->B, Y = c->Y, X = c->X, N = Y * X;
     const size_t nVy = (size_t)(Y + 1) * X, nVx = (size_t)Y * (X + 1), faces = nVy + nVx;
     hipStream_t s = (hipStream_t)stream;
@@ -361,6 +409,9 @@ int bwd_large(const char* who, const sol_karman_cfg* c, void* stream,
     }
     SOL_LAUNCH(k_lb_diffuse_adj, dim3(gF, B), dim3(256), 0, s, a);
     SOL_LAUNCH_CHECK();
+    // g_dsum = g_d_out + dt F . (face-to-cell transpose of g_a); a poisoned simulation (gmax) gets NaN throughout
+    if (bx)
+        if (int e = sol_buoyancy_adj(s, B, Y, X, active, a.gay, a.gax, a.gmax, c->dt * bx->fy, c->dt * bx->fx, bx->g_d_out, bx->g_dsum)) return e;
     if (!rx) return SOL_OK;
     // g' of the Reynolds-number gradient = the fixed-point g_c that k_lb_diffuse_adj has just read (. (1 - bcm) on v_y); the partial sums
     // lie behind the plain adjoint's part of the workspace
@@ -402,4 +453,34 @@ extern "C" int sol_karman_step_bwd_large_re(const sol_karman_cfg* c, void* strea
     const ReExtra rx{vy_in, vx_in, g_re, accumulate_re};
     return bwd_large("sol_karman_step_bwd_large_re", c, stream, saved_vy, saved_vx, re, active, velBCyMask, bc_batch_stride, g_vy_out, g_vx_out,
                      g_vy_in, g_vx_in, direct_header_host, box_blob, box_header_host, cg_info, workspace, workspace_bytes, &rx);
+}
+
+// The adjoint of the BUOYANT large-grid step (sol_karman_step_fwd_large_saved_buoy): sol_karman_step_bwd_large's launches, then
+// k_lb_buoyancy_adj.  The caller runs sol_karman_density_bwd (accumulate = 1) on g_dsum next.
+extern "C" int sol_karman_step_bwd_large_buoy(const sol_karman_cfg* c, void* stream,
+                                              const float* saved_vy, const float* saved_vx, const float* re, const float* active,
+                                              const float* velBCyMask, int64_t bc_batch_stride,
+                                              const float* g_vy_out, const float* g_vx_out, float* g_vy_in, float* g_vx_in,
+                                              const int32_t* direct_header_host,
+                                              const float* box_blob, const int32_t* box_header_host, int32_t* cg_info,
+                                              void* workspace, size_t workspace_bytes,
+                                              float fy, float fx, const float* g_d_out, float* g_dsum) {
+    const BuoyExtra bx{fy, fx, g_d_out, g_dsum};
+    return bwd_large("sol_karman_step_bwd_large_buoy", c, stream, saved_vy, saved_vx, re, active, velBCyMask, bc_batch_stride, g_vy_out, g_vx_out,
+                     g_vy_in, g_vx_in, direct_header_host, box_blob, box_header_host, cg_info, workspace, workspace_bytes, nullptr, &bx);
+}
+
+extern "C" int sol_karman_step_bwd_large_buoy_re(const sol_karman_cfg* c, void* stream,
+                                                 const float* saved_vy, const float* saved_vx, const float* re, const float* active,
+                                                 const float* velBCyMask, int64_t bc_batch_stride,
+                                                 const float* g_vy_out, const float* g_vx_out, float* g_vy_in, float* g_vx_in,
+                                                 const int32_t* direct_header_host,
+                                                 const float* box_blob, const int32_t* box_header_host, int32_t* cg_info,
+                                                 void* workspace, size_t workspace_bytes,
+                                                 const float* vy_in, const float* vx_in, float* g_re, int accumulate_re,
+                                                 float fy, float fx, const float* g_d_out, float* g_dsum) {
+    const ReExtra rx{vy_in, vx_in, g_re, accumulate_re};
+    const BuoyExtra bx{fy, fx, g_d_out, g_dsum};
+    return bwd_large("sol_karman_step_bwd_large_buoy_re", c, stream, saved_vy, saved_vx, re, active, velBCyMask, bc_batch_stride, g_vy_out, g_vx_out,
+                     g_vy_in, g_vx_in, direct_header_host, box_blob, box_header_host, cg_info, workspace, workspace_bytes, &rx, &bx);
 }

@@ -520,6 +520,31 @@ extern "C" int sol_karman_step_fwd_large_cg_warm(const sol_karman_cfg* c, void* 
     return large_cg_step(who, c, stream, io, box_blob, box_header_host, cg_info, p_inout, workspace, workspace_bytes);
 }
 
+// The no-grad step with the buoyancy force F = (fy, fx) (karman_buoyancy.hip), for either solver as the cfg selects it: cfg.direct set =
+// sol_karman_step_fwd_large's launches, else sol_karman_step_fwd_large_cg's (p_inout given: _cg_warm's), with k_l_buoyancy between the
+// advection and the divergence.  F = (0, 0): the plain call's launches and bits.
+extern "C" int sol_karman_step_fwd_large_buoy(const sol_karman_cfg* c, void* stream,
+                                              const float* d_in, const float* vy_in, const float* vx_in,
+                                              const float* re, const float* active, const float* inflow,
+                                              const float* velBCy, const float* velBCyMask, int64_t bc_batch_stride,
+                                              float* d_out, float* vy_out, float* vx_out,
+                                              float* feat_out, const float* feat_scale,
+                                              const int32_t* direct_header_host,
+                                              const float* box_blob, const int32_t* box_header_host, int32_t* cg_info,
+                                              float* p_inout, void* workspace, size_t workspace_bytes, float fy, float fx) {
+    const char* who = "sol_karman_step_fwd_large_buoy";
+    SOL_REQUIRE(c != nullptr, "%s: cfg is NULL", who);
+    SOL_REQUIRE(fy - fy == 0.f && fx - fx == 0.f, "%s: the force must be finite (got %g, %g)", who, (double)fy, (double)fx);
+    SOL_REQUIRE((fy == 0.f && fx == 0.f) || (d_in && inflow && d_out), "%s: a non-zero force needs d_in, inflow and d_out", who);
+    SolLargeStep io{d_in, vy_in, vx_in, re, active, inflow, velBCy, velBCyMask, bc_batch_stride, d_out, vy_out, vx_out, feat_out, feat_scale};
+    io.buoy_y = c->dt * fy; io.buoy_x = c->dt * fx;
+    if (c->direct) {
+        SOL_REQUIRE(!p_inout, "%s: p_inout warm-starts the CG solve; this cfg selects the direct solve", who);
+        return sol_large_direct_step(who, c, stream, io, direct_header_host, workspace, workspace_bytes);
+    }
+    return large_cg_step(who, c, stream, io, box_blob, box_header_host, cg_info, p_inout, workspace, workspace_bytes);
+}
+
 extern "C" int sol_karman_pressure_solve_large(const sol_karman_cfg* c, void* stream, const float* active, const float* rhs, float* p,
                                                const float* box_blob, const int32_t* box_header_host, int32_t* cg_info,
                                                void* workspace, size_t workspace_bytes) {

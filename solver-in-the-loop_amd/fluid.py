@@ -161,7 +161,8 @@ class Fluid:
         self.density = self._centered(density, (batch_size, Y, X, 1), device)
         self.velocity = self._staggered(velocity, batch_size, Y, X, device)
         if buoyancy_factor != 0:
-            raise NotImplementedError("buoyancy is unused on the reference path (buoyancy_factor=0)")
+            raise NotImplementedError("the Fluid state carries no buoyancy (buoyancy_factor=0 on the reference path); the force belongs to the "
+                                      "simulator: KarmanFlow(buoyancy_factor=..., gravity=...) on a large grid")
 
     def _centered(self, v, shape, device):
         if isinstance(v, CenteredGrid):

@@ -112,7 +112,13 @@ class KarmanFlow:
 
     def __init__(self, pressure_solver=None, make_input_divfree=False, make_output_divfree=True,
                  cg_rtol=1e-6, cg_atol=1e-9, cg_max_iter=2000, grad_pad="replicate", inflow_order="after",
-                 obstacles=None, active=None, density_grad=False, re_grad=False):
+                 obstacles=None, active=None, density_grad=False, re_grad=False, buoyancy=None, buoyancy_factor=None,
+                 gravity=(-9.81, 0.0)):
+        # buoyancy=(fy, fx), a force per unit density, or PhiFlow's spelling buoyancy_factor=beta with gravity=(gy, gx): F = -gravity * beta
+        # (ops.buoyancy_force).  The step's output density pushes the velocity; large grids only (step() raises SolError on a grid the
+        # one-workgroup kernels serve).  The default is off: the density is a passive tracer and every launch is what it was.
+        f = ops.buoyancy_force(buoyancy, buoyancy_factor, gravity)
+        self._buoyancy = f if ops._buoyant(f) else None
         # re_grad=True (opt-in): a tensor `re` given to step() that requires a gradient receives one (ops.KarmanStepFn's re mode: fit the
         # viscosity to observed frames, a loss term on Re); the default treats re as data
         self._re_grad = bool(re_grad)
@@ -222,6 +228,9 @@ class KarmanFlow:
         vx = smoke.velocity.data[1].data.reshape(B, Y, X + 1)
         info = {}
         self.pressure_solver_used = masks.pressure_solver        # "direct", "cg" (SceneMasks' choice for this grid and scene) or "direct_scattered"
+        if self._buoyancy is not None and not masks.large:
+            raise _lib.SolError("KarmanFlow: the buoyancy force is built on the multi-launch (large-grid) step only; a %dx%d grid runs the "
+                                "fused one-workgroup kernels (not ops.beyond_one_workgroup), which have no buoyancy term" % (Y, X))
         if masks.large:
             # beyond the one-workgroup kernels (data generation at 256 x 128, karman.py:98-159): the multi-launch path, direct solve
             # where the scene's blob builds, else the preconditioned CG (solve_info: iterations / converged per simulation, and
@@ -230,7 +239,7 @@ class KarmanFlow:
             if getattr(self, "_large_ws", None) is None or self._large_ws[0] != (B, Y, X, str(dev)) or self._large_ws[1].numel() * 4 < n:
                 self._large_ws = ((B, Y, X, str(dev)), torch.empty((n + 3) // 4, dtype=torch.float32, device=dev))
             d2, vy2, vx2 = ops.karman_step_large(d, vy, vx, re_t, cfg, masks, self._large_ws[1], info, density_grad=self._density_grad,
-                                                 re_grad=self._re_grad)
+                                                 re_grad=self._re_grad, buoyancy=self._buoyancy)
         else:
             d2, vy2, vx2 = ops.karman_step(d, vy, vx, re_t, cfg, masks, info, density_grad=self._density_grad, re_grad=self._re_grad)
         self.solve_info = info

@@ -164,10 +164,43 @@ def _step_fwd_args(d, vy, vx, re, cfg, masks, outs=None):
     return outs, head
 
 
-def karman_step_saved(d, vy, vx, re, cfg, masks, workspace=None, info=None):
+def buoyancy_force(buoyancy=None, buoyancy_factor=None, gravity=(-9.81, 0.0)):
+    """The force per unit density F = (fy, fx) of the buoyant step, or None (off).  `buoyancy`: F itself, one number (fy) or a pair;
+    else PhiFlow's spelling, F = -gravity * buoyancy_factor (Gravity() = -9.81 along y: F = (9.81 beta, 0)).  A force of (0, 0) is kept
+    as given: the entry points take it and issue the plain launches."""
+    if buoyancy is not None and buoyancy_factor is not None:
+        raise ValueError("give buoyancy=(fy, fx) or buoyancy_factor (with gravity), not both")
+    if buoyancy is None and buoyancy_factor is None:
+        return None
+    if buoyancy is None:
+        g = (float(gravity), 0.0) if np.isscalar(gravity) else tuple(float(v) for v in gravity)
+        if len(g) != 2:
+            raise ValueError("gravity must be (gy, gx), got %r" % (gravity,))
+        buoyancy = (-g[0] * float(buoyancy_factor), -g[1] * float(buoyancy_factor))
+    f = (float(buoyancy), 0.0) if np.isscalar(buoyancy) else tuple(float(v) for v in buoyancy)
+    if len(f) != 2 or not all(np.isfinite(f)):
+        raise ValueError("buoyancy must be a finite force (fy, fx), got %r" % (buoyancy,))
+    return f
+
+
+def _buoyant(buoyancy):
+    """True for a force that moves the velocity: the density is then part of the dynamics"""
+    return buoyancy is not None and (buoyancy[0] != 0.0 or buoyancy[1] != 0.0)
+
+
+def _require_large_for_buoyancy(masks, Y, X, who):
+    if not masks.large:
+        raise SolError("%s: the buoyancy force is built on the multi-launch (large-grid) step only; a %dx%d grid runs the fused "
+                       "one-workgroup kernels (not ops.beyond_one_workgroup), which have no buoyancy term" % (who, Y, X))
+
+
+def karman_step_saved(d, vy, vx, re, cfg, masks, workspace=None, info=None, buoyancy=None):
     """The differentiable form of the step without autograd, on any grid: ((d, vy, vx) after the step, saved vy, saved vx) -- the
     post-diffusion velocity the adjoints take.  A one-workgroup grid runs sol_karman_step_fwd (`info` receives "iterations"), a grid
-    beyond them (masks.large) sol_karman_step_fwd_large_saved with `workspace` and `info` as in karman_step_large."""
+    beyond them (masks.large) sol_karman_step_fwd_large_saved with `workspace` and `info` as in karman_step_large.
+    buoyancy = (fy, fx) (large grids only): sol_karman_step_fwd_large_saved_buoy, the density pushes the velocity."""
+    if buoyancy is not None:
+        _require_large_for_buoyancy(masks, cfg.Y, cfg.X, "karman_step_saved")
     _lib.require_gpu()
     lib = _lib.load()
     d, vy, vx, re = (_lib.f32(t) for t in (d, vy, vx, re))
@@ -178,8 +211,9 @@ def karman_step_saved(d, vy, vx, re, cfg, masks, workspace=None, info=None):
     if masks.large:
         workspace = _workspace(large_workspace_bytes(cfg, masks), workspace, vy.device)
         cg_info = _cg_info(masks, B, vy.device)
-        check(lib.sol_karman_step_fwd_large_saved(*head, ptr(svy), ptr(svx), _hdr(masks.direct_header), ptr(masks.box),
-                                                  _hdr(masks.box_header), ptr(cg_info), ptr(workspace), workspace.numel() * 4))
+        entry, tail = (lib.sol_karman_step_fwd_large_saved, ()) if buoyancy is None else (lib.sol_karman_step_fwd_large_saved_buoy, tuple(buoyancy))
+        check(entry(*head, ptr(svy), ptr(svx), _hdr(masks.direct_header), ptr(masks.box),
+                    _hdr(masks.box_header), ptr(cg_info), ptr(workspace), workspace.numel() * 4, *tail))
         _publish_cg(info, cg_info)
     else:
         iters = None if info is None else torch.empty(B, dtype=torch.int32, device=vy.device)      # the kernel only stores to it
@@ -193,7 +227,7 @@ karman_step_large_saved = karman_step_saved      # the name the large-grid calle
 
 
 def karman_step_large(d, vy, vx, re, cfg, masks, workspace=None, info=None, feat=None, feat_scale=None, p_guess=None, out=None,
-                      density_grad=False, re_grad=False):
+                      density_grad=False, re_grad=False, buoyancy=None):
     """The step for grids beyond the one-workgroup kernels (data generation at 256 x 128,
     /root/reference/karman-2d/karman.py:98-159): sol_karman_step_fwd_large (direct solve) or sol_karman_step_fwd_large_cg (CG solve,
     masks.pressure_solver == "cg").  Returns (d, vy, vx) after the step; with the CG solve, `info` (a dict) receives "iterations" and
@@ -207,10 +241,15 @@ def karman_step_large(d, vy, vx, re, cfg, masks, workspace=None, info=None, feat
     density_grad=True (opt-in): the density output is differentiable too (KarmanStepFn's density mode: same forward launches; the
     differentiable form is taken when any of d, vy, vx requires a gradient).
     re_grad=True (opt-in): a tensor `re` that requires a gradient receives one (KarmanStepFn's re mode: same forward launches, the step's
-    input velocity saved as well; composes with density_grad).  Without the flag `re` is data."""
+    input velocity saved as well; composes with density_grad).  Without the flag `re` is data.
+    buoyancy = (fy, fx) (see buoyancy_force): the step's output density pushes the velocity (sol_karman_step_fwd_large_buoy, one launch
+    more; every no-grad extra above still applies).  With a non-zero force the density is part of the dynamics: the differentiable form
+    keeps it in the graph as density_grad would (KarmanStepFn's buoyant mode)."""
+    if buoyancy is not None:
+        _require_large_for_buoyancy(masks, cfg.Y, cfg.X, "karman_step_large")
     if p_guess is not None and masks.direct is not None:
         raise ValueError("karman_step_large: p_guess warm-starts the CG pressure solve; this scene runs the direct solver (no iteration to start)")
-    differentiable, density, want_re = _step_mode(d, vy, vx, re, cfg, density_grad, re_grad)
+    differentiable, density, want_re = _step_mode(d, vy, vx, re, cfg, density_grad, re_grad, buoyancy)
     _lib.require_gpu()
     lib = _lib.load()
     d, vy, vx, re = (_lib.f32(t) for t in (d, vy, vx, re))
@@ -219,7 +258,7 @@ def karman_step_large(d, vy, vx, re, cfg, masks, workspace=None, info=None, feat
     if differentiable:
         if feat is not None or p_guess is not None or out is not None:
             raise ValueError("karman_step_large: feat / p_guess / out belong to the no-grad step (the differentiable step keeps its own state)")
-        return KarmanStepFn.apply(d, vy, vx, re, cfg, masks, workspace, info, density, want_re)
+        return KarmanStepFn.apply(d, vy, vx, re, cfg, masks, workspace, info, density, want_re, buoyancy if _buoyant(buoyancy) else None)
     if (feat is None) != (feat_scale is None):
         raise ValueError("karman_step_large: feat and feat_scale go together")
     if feat is not None and (feat.shape != (B, Y, X, 4) or feat.device != vy.device):
@@ -236,7 +275,10 @@ def karman_step_large(d, vy, vx, re, cfg, masks, workspace=None, info=None, feat
         head = _step_fwd_args(d, vy, vx, re, cfg, masks, outs)[1]
     fs = None if feat_scale is None else (feat_scale if isinstance(feat_scale, C.Array) else _scale3(feat_scale))
     cg_info = _cg_info(masks, B, vy.device)
-    if cg_info is None:
+    if buoyancy is not None:
+        check(lib.sol_karman_step_fwd_large_buoy(*head, ptr(feat), fs, _hdr(masks.direct_header), ptr(masks.box), _hdr(masks.box_header),
+                                                 ptr(cg_info), ptr(p_guess), ptr(workspace), workspace.numel() * 4, *buoyancy))
+    elif cg_info is None:
         check(lib.sol_karman_step_fwd_large(*head, ptr(feat), fs, _hdr(masks.direct_header), ptr(workspace), workspace.numel() * 4))
     elif p_guess is None:
         check(lib.sol_karman_step_fwd_large_cg(*head, ptr(feat), fs, ptr(masks.box), _hdr(masks.box_header), ptr(cg_info),
@@ -423,6 +465,72 @@ def karman_density_bwd_re(d, svy, svx, re, g_d, vy_in, vx_in, cfg, masks, g_vy=N
     return _density_bwd("karman_density_bwd_re", d, svy, svx, re, g_d, cfg, masks, g_vy, g_vx, workspace, (vy_in, vx_in, g_re))
 
 
+def karman_buoyancy_add(d, vy, vx, active, f):
+    """The buoyancy term alone, in place (sol_karman_buoyancy_add): vy [B,Y+1,X], vx [B,Y,X+1] = (v + f * face average of d) * face mask,
+    d [B,Y,X] with a zero ghost ring, active [Y,X], f = (fy dt, fx dt); a component with f = 0 is not touched.  Any Y, X >= 1."""
+    _lib.require_gpu()
+    B, Y, X = d.shape
+    if vy.shape != (B, Y + 1, X) or vx.shape != (B, Y, X + 1) or active.numel() != Y * X:
+        raise ValueError("karman_buoyancy_add: d %s, vy %s, vx %s, active %s are not [B,Y,X], [B,Y+1,X], [B,Y,X+1], [Y,X]"
+                         % (tuple(d.shape), tuple(vy.shape), tuple(vx.shape), tuple(active.shape)))
+    check(_lib.load().sol_karman_buoyancy_add(stream(), B, Y, X, ptr(active), ptr(d), float(f[0]), float(f[1]), ptr(vy), ptr(vx)))
+    return vy, vx
+
+
+def karman_buoyancy_add_bwd(gvy, gvx, active, f, gd=None):
+    """The exact transpose of karman_buoyancy_add (sol_karman_buoyancy_add_bwd): g_dsum [B,Y,X] = gd (None = zero) + f . (face-to-cell
+    transpose of the masked gvy [B,Y+1,X], gvx [B,Y,X+1]).  A gather in a fixed order: bit-reproducible."""
+    _lib.require_gpu()
+    B, Y, X = gvx.shape[0], gvx.shape[1], gvy.shape[2]
+    if gvy.shape != (B, Y + 1, X) or gvx.shape != (B, Y, X + 1) or active.numel() != Y * X or (gd is not None and gd.shape != (B, Y, X)):
+        raise ValueError("karman_buoyancy_add_bwd: gvy %s, gvx %s, active %s are not [B,Y+1,X], [B,Y,X+1], [Y,X] (gd: [B,Y,X])"
+                         % (tuple(gvy.shape), tuple(gvx.shape), tuple(active.shape)))
+    out = torch.empty(B, Y, X, dtype=torch.float32, device=gvy.device)
+    check(_lib.load().sol_karman_buoyancy_add_bwd(stream(), B, Y, X, ptr(active), ptr(gvy), ptr(gvx), float(f[0]), float(f[1]), ptr(gd), ptr(out)))
+    return out
+
+
+def karman_step_large_bwd_buoy(d, svy, svx, re, gvy, gvx, gd, cfg, masks, buoyancy, vel_in=None, workspace=None, info=None,
+                               density_workspace=None):
+    """Adjoint of the BUOYANT large-grid step (karman_step_saved(..., buoyancy=F)): (g_d_in, g_vy_in, g_vx_in) -- with vel_in = (vy, vx),
+    the step's input velocity, (g_d_in, g_vy_in, g_vx_in, g_re) -- from the step's input density `d`, the saved post-diffusion velocity and
+    the cotangents gvy, gvx, gd of its outputs (None = zero).  With a velocity cotangent: sol_karman_step_bwd_large_buoy(_re) (the plain
+    velocity adjoint's launches, then g_dsum = gd + dt F . transpose of the face average of g_a), then the density adjoint on g_dsum,
+    added onto the velocity adjoint's result.  Without one (a density-only loss) no pressure solve runs: the density adjoint on gd alone.
+    No cotangent at all: every result is None.  workspace / density_workspace: scratch of the velocity / the density adjoint."""
+    _require_large_for_buoyancy(masks, cfg.Y, cfg.X, "karman_step_large_bwd_buoy")
+    who = "karman_step_large_bwd_buoy"
+    if gvy is None and gvx is None and gd is None:
+        return (None,) * (3 if vel_in is None else 4)
+    if vel_in is not None:
+        _require_staged(cfg, who)
+    _lib.require_gpu()
+    lib = _lib.load()
+    d, svy, svx, re = (_lib.f32(t) for t in (d, svy, svx, re))
+    gd = None if gd is None else _lib.f32(gd)
+    oy = ox = g_re = None
+    g_dsum = gd
+    if gvy is not None or gvx is not None:
+        gvy = torch.zeros_like(svy) if gvy is None else _lib.f32(gvy)
+        gvx = torch.zeros_like(svx) if gvx is None else _lib.f32(gvx)
+        if vel_in is None:
+            entry, nbytes, tail = lib.sol_karman_step_bwd_large_buoy, large_bwd_workspace_bytes(cfg, masks), ()
+        else:
+            entry, nbytes = lib.sol_karman_step_bwd_large_buoy_re, large_bwd_re_workspace_bytes(cfg, masks)
+            tail, g_re = _re_tail(who, tuple(vel_in) + (None,), svy, svx, cfg.B)
+        box, box_header = masks.staged_box()
+        workspace = _workspace(nbytes, workspace, svy.device)
+        oy, ox, g_dsum = torch.empty_like(svy), torch.empty_like(svx), torch.empty_like(d)
+        cg_info = _cg_info(masks, cfg.B, svy.device)
+        check(entry(C.byref(cfg), stream(), ptr(svy), ptr(svx), ptr(re), ptr(masks.active), ptr(masks.velBCyMask), masks.bc_stride,
+                    ptr(gvy), ptr(gvx), ptr(oy), ptr(ox), _hdr(masks.direct_header), ptr(box), _hdr(box_header), ptr(cg_info),
+                    ptr(workspace), workspace.numel() * 4, *tail, float(buoyancy[0]), float(buoyancy[1]), ptr(gd), ptr(g_dsum)))
+        _publish_cg(info, cg_info, "_bwd")
+    if vel_in is None:
+        return karman_density_bwd(d, svy, svx, re, g_dsum, cfg, masks, oy, ox, density_workspace)
+    return karman_density_bwd_re(d, svy, svx, re, g_dsum, *vel_in, cfg, masks, oy, ox, g_re, density_workspace)
+
+
 def _velocity_bwd(svy, svx, re, gvy, gvx, cfg, masks, info, vel_in=None):
     """The velocity half of the step's adjoint: (g_vy_in, g_vx_in, g_re | None).  vel_in = (vy, vx), the step's input velocity, asks for
     the gradient with respect to re as well: the staged adjoint on every grid (karman_step_large_bwd_re; the fused one-workgroup adjoint
@@ -444,15 +552,18 @@ class KarmanStepFn(torch.autograd.Function):
     velocity adjoint's result).  `want_re` (opt-in, re_grad=True; grids with Y, X >= 16): differentiable with respect to re as well, the
     step's input velocity saved beside the post-diffusion one (_step_mode and torch.ops.sol.karman_step_re check the grid).  backward returns (g_d_in | None, g_vy_in, g_vx_in, g_re | None); the
     velocity half (with its pressure solve) runs only when a velocity cotangent arrived, the density half only when a density cotangent
-    did."""
+    did.  `buoyancy` = (fy, fx), a non-zero force (large grids; else None): the buoyant step -- the density is part of the dynamics, so
+    it is in the graph whatever `density` says; a velocity-only loss yields a density gradient too (karman_step_large_bwd_buoy), a
+    density-only loss still runs no pressure solve."""
 
     @staticmethod
-    def forward(ctx, d, vy, vx, re, cfg, masks, workspace, info, density, want_re):
+    def forward(ctx, d, vy, vx, re, cfg, masks, workspace, info, density, want_re, buoyancy=None):
         _lib.require_gpu()
         d, vy, vx, re = (_lib.f32(t) for t in (d, vy, vx, re))
-        outs, svy, svx = karman_step_saved(d, vy, vx, re, cfg, masks, workspace, info)
+        density = bool(density) or buoyancy is not None
+        outs, svy, svx = karman_step_saved(d, vy, vx, re, cfg, masks, workspace, info, buoyancy)
         ctx.save_for_backward(svy, svx, re, *((d, vy, vx) if want_re else (d,) if density else ()))
-        ctx.cfg, ctx.masks, ctx.info, ctx.density, ctx.want_re = cfg, masks, info, density, want_re
+        ctx.cfg, ctx.masks, ctx.info, ctx.density, ctx.want_re, ctx.buoyancy = cfg, masks, info, density, want_re, buoyancy
         if not density:
             ctx.mark_non_differentiable(outs[0])
         ctx.set_materialize_grads(False)
@@ -464,6 +575,10 @@ class KarmanStepFn(torch.autograd.Function):
         cfg, masks = ctx.cfg, ctx.masks
         vel_in = tuple(inputs[1:]) if ctx.want_re else None
         od = oy = ox = g_re = None
+        if ctx.buoyancy is not None:
+            gvy, gvx, gd = (None if g is None else g.contiguous() for g in (gvy, gvx, gd))
+            res = karman_step_large_bwd_buoy(inputs[0], svy, svx, re, gvy, gvx, gd, cfg, masks, ctx.buoyancy, vel_in, info=ctx.info)
+            return res[0], res[1], res[2], (res[3] if vel_in is not None else None), None, None, None, None, None, None, None
         if gvy is not None or gvx is not None:
             oy, ox, g_re = _velocity_bwd(svy, svx, re, gvy, gvx, cfg, masks, ctx.info, vel_in)
         if ctx.density and gd is not None:        # added onto the velocity half's buffers and g_re
@@ -471,15 +586,15 @@ class KarmanStepFn(torch.autograd.Function):
                 od, oy, ox = karman_density_bwd(inputs[0], svy, svx, re, gd, cfg, masks, oy, ox)
             else:
                 od, oy, ox, g_re = karman_density_bwd_re(inputs[0], svy, svx, re, gd, *vel_in, cfg, masks, oy, ox, g_re)
-        return od, oy, ox, g_re, None, None, None, None, None, None
+        return od, oy, ox, g_re, None, None, None, None, None, None, None
 
 
-def _step_mode(d, vy, vx, re, cfg, density_grad, re_grad):
+def _step_mode(d, vy, vx, re, cfg, density_grad, re_grad, buoyancy=None):
     """(differentiable?, density, want_re) of a call of karman_step / karman_step_large, from its inputs as given and its two flags.
     re_grad with an `re` that requires no gradient is the plain mode.  A grid the staged adjoint does not take is refused here, before
     any device call."""
     needs = lambda t: isinstance(t, torch.Tensor) and t.requires_grad
-    density = bool(density_grad)
+    density = bool(density_grad) or _buoyant(buoyancy)          # a force that moves the velocity: the density is always in the graph
     want_re = bool(re_grad) and torch.is_grad_enabled() and needs(re)
     if want_re:
         _require_staged(cfg, "re_grad")

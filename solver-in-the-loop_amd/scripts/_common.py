@@ -47,6 +47,35 @@ def scene_from_args(params):
     return None
 
 
+def add_buoyancy_arg(p):
+    """--buoyancy FY[,FX] of karman.py, karman_train.py and karman_apply.py"""
+    p.add_argument("--buoyancy", default=None, metavar="FY[,FX]",
+                   help="buoyancy force per unit density: the density pushes the velocity (large grids only; PhiFlow's buoyancy_factor b "
+                        "is FY = 9.81 b).  Stored with the data like the scene; absent: off")
+
+
+def buoyancy_from_args(params):
+    """(fy, fx) of --buoyancy FY[,FX], or None when the flag is absent."""
+    from sol_amd import ops
+    if params.get("buoyancy") is None:
+        return None
+    try:
+        vals = [float(v) for v in str(params["buoyancy"]).split(",")]
+        if len(vals) not in (1, 2):
+            raise ValueError
+        return ops.buoyancy_force(tuple(vals + [0.0])[:2])
+    except ValueError:
+        raise SystemExit("bad --buoyancy %r: expected FY or FY,FX (finite numbers)" % (params["buoyancy"],))
+
+
+def agreed_buoyancy(recorded, flag, where):
+    """The force of a run that reads data: what the data recorded (None: off), unless --buoyancy says otherwise -- a contradiction."""
+    norm = lambda f: None if f is None or (f[0] == 0.0 and f[1] == 0.0) else (float(f[0]), float(f[1]))
+    if flag is not None and norm(flag) != norm(recorded):
+        raise SystemExit("--buoyancy %s contradicts the force recorded in %s (%s)" % (flag, where, recorded))
+    return norm(recorded)
+
+
 def flow_kwargs(rec):
     """KarmanFlow / GraphTrainer keywords of a scene_record (None: the default scene)."""
     from sol_amd import karman

@@ -3,14 +3,16 @@
 :138-159 on the fused HIP solver step (one kernel launch per frame, state stays on the GPU).
 -r <= 64 runs the fused one-workgroup-per-simulation kernel; larger grids (the reference's 256x128 `-r 128`
 reference solutions, Makefile:19-28) run the multi-launch path (nothing is kept for a backward pass here): the direct pressure solver where the scene's blob builds,
-else the preconditioned CG.  --obstacle / --obstacle-mask choose the scene (recorded in params.pickle as "scene")."""
+else the preconditioned CG.  --obstacle / --obstacle-mask choose the scene (recorded in params.pickle as "scene").  --buoyancy FY[,FX]
+(large grids only): the density pushes the velocity; recorded in params.pickle as "buoyancy" (a pair, or None: off), so that training and
+roll-out pick it up from the data."""
 import argparse
 import pickle
 
 import numpy as np
 import torch
 
-from _common import add_scene_args, flow_kwargs, logger, scene_from_args, select_gpu
+from _common import add_buoyancy_arg, add_scene_args, buoyancy_from_args, flow_kwargs, logger, scene_from_args, select_gpu
 import sol_amd
 from sol_amd import ops, scene
 
@@ -31,6 +33,7 @@ def main(argv=None):
     p.add_argument("-l", "--len", default=100, type=int, help="length of the reference axis")
     p.add_argument("--seed", default=0, type=int, help="seed for random number generator")
     add_scene_args(p)
+    add_buoyancy_arg(p)
     params = vars(p.parse_args(argv))
     select_gpu(params["gpu"])
     log = logger()
@@ -38,7 +41,8 @@ def main(argv=None):
     Y, X = 2 * res, res
     dom = sol_amd.Domain([Y, X], box=sol_amd.box[0:params["len"] * 2, 0:params["len"]])
     rec = scene_from_args(params)
-    sim = sol_amd.KarmanFlow(pressure_solver=params["pressure_solver"], **flow_kwargs(rec))
+    params["buoyancy"] = buoyancy_from_args(params)
+    sim = sol_amd.KarmanFlow(pressure_solver=params["pressure_solver"], buoyancy=params["buoyancy"], **flow_kwargs(rec))
     params["scene"] = sim.scene()
     d0 = scene.downsample(scene.read_zipped_array(params["initdH"]), params["scale"]) if params["initdH"] else np.zeros((1, Y, X, 1))
     if params["initvH"]:

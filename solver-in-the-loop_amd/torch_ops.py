@@ -6,7 +6,8 @@ hand-written adjoints (ops.KarmanStepFn, ops.BurgersStepFn, ops.Conv5x5Fn: sol_k
 _bwd_large, sol_conv5x5 backward-data / -weight) under the AutogradCUDA key, so they compose with any other PyTorch op and show up in the
 dispatcher (torch.ops.sol.karman_step, .conv5x5, .burgers_step, .adam_tf_step; .karman_step_dens = karman_step with a differentiable
 density output, over sol_karman_density_bwd; .karman_step_re = karman_step differentiable with respect to re as well, over the _re
-adjoints).  Scene constants (masks, solver blobs, the cfg struct) are not tensors: they are registered once with register_scene() and
+adjoints; .karman_step_buoy = the large-grid step with the buoyancy force (fy, fx): the density pushes the velocity and is always in the
+graph).  Scene constants (masks, solver blobs, the cfg struct) are not tensors: they are registered once with register_scene() and
 referred to by an integer handle."""
 import torch
 
@@ -18,6 +19,7 @@ _LIB = torch.library.Library("sol", "DEF")
 _LIB.define("karman_step(Tensor d, Tensor vy, Tensor vx, Tensor re, int scene) -> (Tensor, Tensor, Tensor)")
 _LIB.define("karman_step_dens(Tensor d, Tensor vy, Tensor vx, Tensor re, int scene) -> (Tensor, Tensor, Tensor)")
 _LIB.define("karman_step_re(Tensor d, Tensor vy, Tensor vx, Tensor re, int scene, bool density=False) -> (Tensor, Tensor, Tensor)")
+_LIB.define("karman_step_buoy(Tensor d, Tensor vy, Tensor vx, Tensor re, int scene, float fy, float fx, bool re_grad=False) -> (Tensor, Tensor, Tensor)")
 _LIB.define("karman_density_bwd(Tensor d, Tensor svy, Tensor svx, Tensor re, Tensor gd, int scene) -> (Tensor, Tensor, Tensor)")
 _LIB.define("karman_step_bwd(Tensor svy, Tensor svx, Tensor re, Tensor gvy, Tensor gvx, int scene) -> (Tensor, Tensor)")
 _LIB.define("karman_step_fwd_saved(Tensor d, Tensor vy, Tensor vx, Tensor re, int scene) -> (Tensor, Tensor, Tensor, Tensor, Tensor)")
@@ -74,7 +76,24 @@ def _karman_fn(d, vy, vx, re, scene, density, want_re):
     cfg, masks = _SCENES[scene]
     if want_re:
         ops._require_staged(cfg, "re_grad")
-    return ops.KarmanStepFn.apply(d, vy, vx, re, cfg, masks, None, None, density, want_re)
+    return ops.KarmanStepFn.apply(d, vy, vx, re, cfg, masks, None, None, density, want_re, None)
+
+
+# karman_step_buoy: the buoyant mode of ops.KarmanStepFn (large grids; a force of (0, 0) is the plain step, density in the graph)
+def _karman_buoy(d, vy, vx, re, scene, fy, fx, re_grad=False):
+    cfg, masks = _SCENES[scene]
+    with torch.no_grad():
+        return ops.karman_step_large(d, vy, vx, re, cfg, masks, buoyancy=(float(fy), float(fx)))
+
+
+def _karman_buoy_fn(d, vy, vx, re, scene, fy, fx, re_grad=False):
+    cfg, masks = _SCENES[scene]
+    f = ops.buoyancy_force((fy, fx))
+    ops._require_large_for_buoyancy(masks, cfg.Y, cfg.X, "torch.ops.sol.karman_step_buoy")
+    want_re = bool(re_grad) and torch.is_grad_enabled() and re.requires_grad
+    if want_re:
+        ops._require_staged(cfg, "re_grad")
+    return ops.KarmanStepFn.apply(d, vy, vx, re, cfg, masks, None, None, True, want_re, f if ops._buoyant(f) else None)
 
 
 for _op in ("karman_step", "karman_step_dens", "karman_step_re"):
@@ -82,6 +101,9 @@ for _op in ("karman_step", "karman_step_dens", "karman_step_re"):
 _LIB.impl("karman_step", lambda d, vy, vx, re, scene: _karman_fn(d, vy, vx, re, scene, False, False), "AutogradCUDA")
 _LIB.impl("karman_step_dens", lambda d, vy, vx, re, scene: _karman_fn(d, vy, vx, re, scene, True, False), "AutogradCUDA")
 _LIB.impl("karman_step_re", lambda d, vy, vx, re, scene, density=False: _karman_fn(d, vy, vx, re, scene, bool(density), True), "AutogradCUDA")
+
+_LIB.impl("karman_step_buoy", _karman_buoy, "CUDA")
+_LIB.impl("karman_step_buoy", _karman_buoy_fn, "AutogradCUDA")
 
 # conv / burgers: the autograd.Functions of ops.py already are the hand-written forward + backward pairs
 _LIB.impl("conv5x5", lambda x, w, b, residual, lrelu, slope: ops.Conv5x5Fn.apply(x, w, b, residual, lrelu, slope), "AutogradCUDA")

@@ -66,6 +66,15 @@ def _refuse_large_grid(who, Y, X):
                          "KarmanFlow.step / ops.karman_step_large" % (who, Y, X))
 
 
+def _refuse_buoyancy(who, buoyancy):
+    """SolTrainer and GraphTrainer run the fused one-workgroup solver kernels, which have no buoyancy term: a non-zero force is refused
+    at construction (LargeGridTrainer(buoyancy=...) trains with it on a large grid).  -> None"""
+    if ops._buoyant(ops.buoyancy_force(buoyancy)):
+        raise ValueError("%s: buoyancy=%r -- the buoyancy force is built on the multi-launch (large-grid) solver step only; this trainer "
+                         "runs the fused one-workgroup kernels.  Train with it on a large grid (LargeGridTrainer)" % (who, buoyancy))
+    return None
+
+
 def _train_cfg(kc, msteps, net, std_v, std_re, in_std_v, out_std_v):
     """TrainCfg with its normalisation fields.  --pretf (karman_train.py:351-355,416-421): separate input / output normalisation of a
     pre-trained supervised model; 0.0 pairs stand for "as std_v"."""
@@ -129,7 +138,7 @@ class SolTrainer(_AdamDP):
     def __init__(self, net, masks, B, Y, X, msteps, dx, std_v, std_re, dt=1.0, res=None,
                  clip_grad=False, beta1=0.9, beta2=0.999, eps=1e-8, group=None, use_graph=True,
                  cg_rtol=1e-6, cg_atol=1e-9, cg_max_iter=2000, grad_pad="replicate", inflow_order="after",
-                 conv_precision="split", comm=None, in_std_v=None, out_std_v=None):
+                 conv_precision="split", comm=None, in_std_v=None, out_std_v=None, buoyancy=None):
         """conv_precision: arithmetic of the 32-channel convolutions (library option `conv_precision`):
         "split" (default) fp32-equivalent fp16x3 / bf16x6 operand splits on the 16-bit matrix pipe, "bf16x6",
         or "fp32" = strict fp32 MFMA.  The option is process wide in the library; every call of this trainer sets
@@ -137,6 +146,7 @@ class SolTrainer(_AdamDP):
         one process.  None keeps whatever the option table holds
         (e.g. a SOL_CONV_NO_SB / SOL_CONV_NO_FP16 debugging override applied when the library was loaded)."""
         _refuse_large_grid("SolTrainer", Y, X)
+        _refuse_buoyancy("SolTrainer", buoyancy)
         _lib.require_gpu()
         self.lib = _lib.load()
         self.conv_precision = _conv_precision_code(conv_precision)
@@ -284,10 +294,13 @@ class LargeGridRollout:
     a CG scene."""
 
     def __init__(self, net, masks, B, Y, X, dx, std_v, std_re, dt=1.0, res=None, in_std_v=None, out_std_v=None,
-                 conv_precision="split", use_graph=True, cg_warm_start=False, any_width=False, **solver):
+                 conv_precision="split", use_graph=True, cg_warm_start=False, any_width=False, buoyancy=None, **solver):
         """any_width=True: X need not be a multiple of 64 -- the network runs in pitched rows (NetSchedule2D(any_width=True): the features
         are copied into zero-padded rows of 64 * ceil(X / 64) pixels and the output is cropped; the solver step and the correction stay
-        dense)."""
+        dense).  buoyancy=(fy, fx) (ops.buoyancy_force): the density pushes the velocity -- the solver step is the buoyant one
+        (sol_karman_step_fwd_large_buoy: one launch more, captured with the rest; direct and CG scenes, warm start included)."""
+        f = ops.buoyancy_force(buoyancy)
+        self.buoyancy = f if ops._buoyant(f) else None
         if not ops.beyond_one_workgroup(Y, X):
             raise ValueError("LargeGridRollout: a %dx%d domain is served by the one-workgroup roll-out -- use SolRollout (make_rollout picks)" % (Y, X))
         if X % 64 != 0 and not any_width:
@@ -334,7 +347,7 @@ class LargeGridRollout:
     def _step(self):
         info = {}
         ops.karman_step_large(*self._a, self._re, self.cfg, self.masks, self._ws, info, feat=self._feat, feat_scale=self._fs3,
-                              p_guess=self.p_guess, out=self._b)
+                              p_guess=self.p_guess, out=self._b, buoyancy=self.buoyancy)
         out, _ = self._sched.forward(self._feat)
         ops.karman_correct(out, self._b[1], self._b[2], self._so, self._cor)
         _lib.dcopy_(self._flat[0], self._flat[1])
@@ -382,6 +395,9 @@ def make_rollout(net, masks, B, Y, X, dx, std_v, std_re, **kw):
         return LargeGridRollout(net, masks, B, Y, X, dx, std_v, std_re, **kw)
     for k in ("use_graph", "cg_warm_start", "any_width"):
         kw.pop(k, None)
+    if ops._buoyant(ops.buoyancy_force(kw.pop("buoyancy", None))):
+        raise ValueError("make_rollout: the buoyancy force is built on the multi-launch (large-grid) solver step only; a %dx%d grid runs "
+                         "the one-workgroup roll-out (SolRollout), which has no buoyancy term" % (Y, X))
     return SolRollout(net, masks, B, Y, X, dx, std_v, std_re, **kw)
 
 
@@ -400,7 +416,8 @@ class GraphTrainer(_AdamDP):
     def __init__(self, net, B, Y, X, msteps, std_v, std_re, res=None, clip_grad=False, beta1=0.9, beta2=0.999, eps=1e-8,
                  group=None, use_graph=True, comm=None, in_std_v=None, out_std_v=None, pressure_solver=None,
                  dx=None, dt=1.0, masks=None, cg_rtol=1e-6, cg_atol=1e-9, cg_max_iter=2000, grad_pad="replicate",
-                 inflow_order="after", conv_precision="split", schedule="manual", obstacles=None, active=None):
+                 inflow_order="after", conv_precision="split", schedule="manual", obstacles=None, active=None,
+                 buoyancy=None):
         """dx: cell size (default 100 / X, the reference's `--len 100`); the domain is box[0:Y*dx, 0:X*dx] as the scripts
         build it (karman_train.py:363: box[0:len*2, 0:len]).  obstacles / active: the scene of KarmanFlow (default: the reference's
         sphere).  masks: optional SceneMasks of the caller -- its boundary arrays are used; its scene must be the one KarmanFlow
@@ -412,6 +429,7 @@ class GraphTrainer(_AdamDP):
         self._sched = None
         self._cg_fwd, self._cg_bwd = [], []       # what the solver launches of a step report (LargeGridTrainer, CG scenes)
         self._check_grid(Y, X)
+        self.buoyancy = self._check_buoyancy(buoyancy)
         from . import fluid, karman
         _lib.require_gpu()
         self.lib = _lib.load()
@@ -451,6 +469,10 @@ class GraphTrainer(_AdamDP):
     @staticmethod
     def _check_grid(Y, X):
         _refuse_large_grid("GraphTrainer", Y, X)
+
+    @staticmethod
+    def _check_buoyancy(buoyancy):
+        return _refuse_buoyancy("GraphTrainer", buoyancy)
 
     def _unrolled(self):
         if self.schedule == "manual":
@@ -607,7 +629,12 @@ class LargeGridTrainer(GraphTrainer):
     def __init__(self, net, B, Y, X, msteps, std_v, std_re, any_width=False, **kw):
         """any_width=True: X need not be a multiple of 64 -- the network's forward and reverse launches run in pitched rows of
         64 * ceil(X / 64) pixels (NetSchedule2D(any_width=True): column-masked convolutions, the weight gradient at the pitch); the solver
-        pair, the correction and the loss stay dense."""
+        pair, the correction and the loss stay dense.
+        buoyancy=(fy, fx) (keyword; ops.buoyancy_force): the density pushes the velocity.  The schedule is unchanged; the solver pair is the
+        buoyant one: _solver_fwd = ops.karman_step_saved(buoyancy=...) and also keeps each step's input density, _solver_bwd =
+        ops.karman_step_large_bwd_buoy (the buoyant velocity adjoint, then the density adjoint), which carries g_d_in to the next (earlier)
+        step as that step's g_d_out.  The loss looks at the velocity only, so the last step's g_d_out is zero; the carried gradient is
+        reset at the head of every run, so a replayed graph is self-contained."""
         if any_width and kw.get("schedule", "manual") == "autograd":
             raise ValueError("LargeGridTrainer: any_width=True runs the hand-written schedule only; schedule='autograd' (the composition "
                              "over ops.conv5x5) takes no pitched rows")
@@ -626,9 +653,17 @@ class LargeGridTrainer(GraphTrainer):
 
     _adjoint_of_first_step = False
 
+    @staticmethod
+    def _check_buoyancy(buoyancy):
+        f = ops.buoyancy_force(buoyancy)
+        return f if ops._buoyant(f) else None
+
     def _schedule_setup(self):
         super()._schedule_setup()
         cfg, mk, dev = self._kcfg, self._mk, self.device
+        self._d_in, self._g_d = [], None                    # buoyant mode: the steps' input densities; the carried density gradient
+        if self.buoyancy is not None:
+            self._ws_bwd_d = torch.empty((int(ops.density_bwd_workspace_bytes(cfg)) + 3) // 4, dtype=torch.float32, device=dev)
         ws = lambda n: torch.empty((int(n) + 3) // 4, dtype=torch.float32, device=dev)
         self._ws_fwd = ws(ops.large_workspace_bytes(cfg, mk))
         self._ws_bwd = ws(ops.large_bwd_workspace_bytes(cfg, mk))
@@ -639,8 +674,11 @@ class LargeGridTrainer(GraphTrainer):
         B, Y, X, fs = self.B, self.Y, self.X, self._fs
         if not self._cg_fwd:                                  # first unrolled step of this run: one Reynolds-number plane serves them all
             self._re_plane = (re * fs[2]).reshape(B, 1, 1).expand(B, Y, X)
+            self._d_in, self._g_d = [], None                  # head of a run: nothing is carried over from the previous one
         info = {}
-        (d2, vy2, vx2), svy, svx = ops.karman_step_large_saved(d, vy, vx, re, self._kcfg, self._mk, self._ws_fwd, info)
+        if self.buoyancy is not None:
+            self._d_in.append(d)
+        (d2, vy2, vx2), svy, svx = ops.karman_step_large_saved(d, vy, vx, re, self._kcfg, self._mk, self._ws_fwd, info, self.buoyancy)
         self._cg_fwd.append(info)
         # to_feature / in_std (karman_train.py:77-86, 413-416), padded to the four channels the first layer's kernels read
         feat = torch.stack([vy2[:, :Y] * fs[0], vx2[:, :, :X] * fs[1], self._re_plane, self._zplane], dim=-1)
@@ -652,6 +690,12 @@ class LargeGridTrainer(GraphTrainer):
         G[1][:, :, :X].add_(dfeat[..., 1], alpha=fs[1])
         info = {}
         self._cg_bwd.append(info)
+        if self.buoyancy is not None:
+            # the reverse sweep visits the steps last to first (the first step's adjoint is not run): the input densities come off the end
+            d_in = self._d_in.pop()
+            self._g_d, oy, ox = ops.karman_step_large_bwd_buoy(d_in, svy, svx, re, G[0], G[1], self._g_d, self._kcfg, self._mk, self.buoyancy,
+                                                               workspace=self._ws_bwd, info=info, density_workspace=self._ws_bwd_d)
+            return oy, ox
         return ops.karman_step_large_bwd(svy, svx, re, G[0], G[1], self._kcfg, self._mk, workspace=self._ws_bwd, info=info)
 
     def _fwd_bwd(self, *a, **kw):
