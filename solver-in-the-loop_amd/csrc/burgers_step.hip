@@ -427,15 +427,9 @@ struct BLLayout {
 };
 BLLayout bl_layout(const sol_burgers_cfg* c, void* ws) {
     const size_t B = c->B, Y = c->Y, X = c->X, faces = (Y + 1) * X + Y * (X + 1);
-    char* w = ws ? reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(ws) + 255) / 256 * 256) : nullptr;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { char* p = w ? w + off : nullptr; off += align_up(bytes, 256); return p; };
-    BLLayout l{};
-    l.gc = reinterpret_cast<long long*>(take(B * faces * sizeof(long long)));
-    l.ga = reinterpret_cast<float*>(take(B * faces * sizeof(float)));
-    l.t = reinterpret_cast<float*>(take(B * faces * sizeof(float)));
-    l.gmax = reinterpret_cast<unsigned*>(take(B * FX_SLOTS * sizeof(unsigned)));
-    l.bytes = off + 256;                       // + the alignment of the caller's pointer
+    Carve w(ws);
+    BLLayout l{w.take<long long>(B * faces), w.take<float>(B * faces), w.take<float>(B * faces), w.take<unsigned>(B * FX_SLOTS)};
+    l.bytes = w.bytes();
     return l;
 }
 
@@ -544,13 +538,12 @@ extern "C" int sol_burgers_step_bwd_large(const sol_burgers_cfg* cfg, void* stre
     SOL_REQUIRE(cfg->dx > 0.f, "dx must be > 0");
     SOL_REQUIRE(vy_in && vx_in && circ_yp1 && circ_x && circ_y && circ_xp1 && g_vy_out && g_vx_out && g_vy_in && g_vx_in && workspace,
                 "sol_burgers_step_bwd_large: NULL pointer");
-    const size_t need = bl_layout(cfg, nullptr).bytes;
-    SOL_REQUIRE(workspace_bytes >= need, "sol_burgers_step_bwd_large: workspace too small (%zu < %zu bytes)", workspace_bytes, need);
+    const BLLayout l = bl_layout(cfg, workspace);
+    SOL_REQUIRE(workspace_bytes >= l.bytes, "sol_burgers_step_bwd_large: workspace too small (%zu < %zu bytes)", workspace_bytes, l.bytes);
     SOL_REQUIRE(g_vy_in != g_vx_in && g_vy_in != vy_in && g_vy_in != vx_in && g_vx_in != vy_in && g_vx_in != vx_in,
                 "sol_burgers_step_bwd_large: g_vy_in / g_vx_in must be buffers of their own");
     const int B = cfg->B, Y = cfg->Y, X = cfg->X;
     const size_t nVy = (size_t)(Y + 1) * X, nVx = (size_t)Y * (X + 1), faces = nVy + nVx;
-    const BLLayout l = bl_layout(cfg, workspace);
     BLArgs a{};
     a.Y = Y; a.X = X; a.dtdx = cfg->dt / cfg->dx;
     a.vy = vy_in; a.vx = vx_in;

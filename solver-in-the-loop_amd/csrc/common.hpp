@@ -9,6 +9,7 @@
 #include <initializer_list>
 
 #include "../../include/sol_hip.h"
+#include "carve.hpp"
 
 int sol_set_error(int code, const char* fmt, ...);
 int sol_init_karman_kernels();
@@ -51,9 +52,6 @@ struct SolLargeStep {
 int sol_buoyancy_add(hipStream_t s, int B, int Y, int X, const float* active, const float* d, float fy, float fx, float* vy, float* vx);
 int sol_buoyancy_adj(hipStream_t s, int B, int Y, int X, const float* active, const float* gy, const float* gx, const unsigned* gmax,
                      float fy, float fx, const float* g_d_out, float* g_dsum);
-// sol_karman_step_fwd_large under the caller's name (karman_large.hip): the direct-solve step with features, shared with its buoyant form
-int sol_large_direct_step(const char* who, const sol_karman_cfg* c, void* stream, const SolLargeStep& io, const int32_t* direct_header_host,
-                          void* workspace, size_t workspace_bytes);
 int sol_large_front(const sol_karman_cfg* c, hipStream_t s, const SolLargeStep& io, float* svy, float* svx, float* rhs);
 int sol_large_project(const sol_karman_cfg* c, hipStream_t s, const SolLargeStep& io, const float* p);
 int sol_large_box_forward(hipStream_t s, int B, int Y, int X, const float* blob, const float* src, float* T1, float* T2, const int* skip);
@@ -64,8 +62,7 @@ int sol_large_box_back(hipStream_t s, int B, int Y, int X, const float* blob, co
 // empty-box solve of box_blob, reporting to cg_info [2][B] (sol_large_cg_check).  ws: sol_large_solver_bytes(c, direct) bytes; the caller
 // writes b to sol_large_solver_rhs(c, direct, ws) (overwritten); *x = the buffer inside ws that holds the solution.  x0 (CG only): NULL, or
 // the initial guess [B][Y][X] of a warm-started solve (a simulation whose guess is not finite starts from zero).
-size_t sol_large_direct_floats(const sol_karman_cfg* c);
-size_t sol_large_direct_floats(const sol_karman_cfg* c, const int32_t* hdr);      // sized from the blob's host header (scattered solve: U, V, X0, W2 follow |R|, |C|)
+size_t sol_large_direct_bytes(const sol_karman_cfg* c, const int32_t* hdr);       // the direct solve's buffers, sized from the blob's host header (NULL: the one-window form)
 int sol_large_direct_check(const sol_karman_cfg* c, const char* who, const int32_t* hdr);
 int sol_large_direct_solve(hipStream_t s, const sol_karman_cfg* c, const int32_t* hdr, float* base);
 int sol_large_cg_check(const sol_karman_cfg* c, const char* who, const float* box_blob, const int32_t* hdr, const int32_t* cg_info, const void* workspace);

@@ -1068,12 +1068,49 @@ __global__ void __launch_bounds__(256) k3b_diffuse_adj(K3BArgs a) {
 
 extern "C" int32_t sol_abi_size_karman3d(void) { return (int32_t)sizeof(sol_karman3d_cfg); }
 
+namespace {
+
+// the solver's buffers, the tail of both steps' layouts: rhs, two transform buffers, 256 floats of slack, then the CG solve's vectors and
+// slabs (k3_layout in pcg.hip; nothing for the direct solve)
+struct K3Solver { float *R, *T1, *T2; void* pcg; };
+K3Solver k3_solver_take(Carve& w, const sol_karman3d_cfg* c) {
+    const size_t BN = (size_t)c->B * c->Y * c->X * c->Z;
+    K3Solver v{w.take<float>(BN), w.take<float>(BN), w.take<float>(BN), nullptr};
+    w.take<float>(256);
+    v.pcg = w.take<char>(k3_pcg_workspace_bytes(c));
+    return v;
+}
+
+// the forward step's workspace, float-dense from the caller's pointer: three diffused components, then the solver's buffers
+struct K3Fwd { float *svy, *svx, *svz; K3Solver sol; size_t bytes; };
+K3Fwd k3_fwd_layout(const sol_karman3d_cfg* c, void* ws) {
+    const size_t B = c->B, Y = c->Y, X = c->X, Z = c->Z;
+    Carve w = Carve::packed(ws);
+    K3Fwd l{w.take<float>(B * (Y + 1) * X * Z), w.take<float>(B * Y * (X + 1) * Z), w.take<float>(B * Y * X * (Z + 1)), k3_solver_take(w, c)};
+    l.bytes = w.bytes();
+    return l;
+}
+
+// the adjoint's workspace, float-dense from the caller's (16-byte aligned) pointer: g_c (int64 fixed point, [b][y faces | x faces | z faces]
+// per simulation -- k3b_rhs clears simulation b's block), g_a (fp32) per component, the absmax slots, the solver's buffers; with re, the
+// partial sums of the Reynolds-number reduction behind them
+struct K3Bwd { long long* gc; float *gay, *gax, *gaz; unsigned* gmax; K3Solver sol; double* partial; size_t bytes; };
+K3Bwd k3_bwd_layout(const sol_karman3d_cfg* c, bool re, void* ws) {
+    const size_t B = c->B, Y = c->Y, X = c->X, Z = c->Z;
+    const size_t nVy = (Y + 1) * X * Z, nVx = Y * (X + 1) * Z, nVz = Y * X * (Z + 1);
+    Carve w = Carve::packed(ws);
+    K3Bwd l{w.take<long long>(B * (nVy + nVx + nVz)), w.take<float>(B * nVy), w.take<float>(B * nVx), w.take<float>(B * nVz),
+            w.take<unsigned>(B * FX_SLOTS), k3_solver_take(w, c)};
+    l.bytes = w.bytes();
+    if (re) l.partial = sol_re3_partial_behind(w, c, &l.bytes);
+    return l;
+}
+
+}  // namespace
+
 extern "C" size_t sol_karman3d_step_workspace_bytes(const sol_karman3d_cfg* c) {
     if (!c) return 0;
-    const size_t B = c->B, Y = c->Y, X = c->X, Z = c->Z;
-    // three diffused components + rhs + two transform buffers (+ the CG solve's vectors and slabs)
-    const size_t floats = B * ((Y + 1) * X * Z + Y * (X + 1) * Z + Y * X * (Z + 1) + 3 * Y * X * Z) + 256;
-    return floats * sizeof(float) + k3_pcg_workspace_bytes(c);
+    return k3_fwd_layout(c, nullptr).bytes;
 }
 
 extern "C" int sol_karman3d_step_fwd(const sol_karman3d_cfg* c, void* stream,
@@ -1092,19 +1129,13 @@ extern "C" int sol_karman3d_step_fwd(const sol_karman3d_cfg* c, void* stream,
     SOL_REQUIRE((d_in && inflow) || !d_out, "density output requested without d_in / inflow");
     SOL_REQUIRE(!feat_out || feat_scale, "feat_out requires feat_scale");
     if (int e = check_blob3d(c, direct_header_host)) return e;
-    SOL_REQUIRE(workspace_bytes >= sol_karman3d_step_workspace_bytes(c), "workspace too small");
+    const K3Fwd l = k3_fwd_layout(c, workspace);
+    SOL_REQUIRE(workspace_bytes >= l.bytes, "workspace too small");
     SOL_REQUIRE(vy_in != vy_out && vx_in != vx_out && vz_in != vz_out && (d_in != d_out || !d_out), "sol_karman3d_step_fwd: outputs must not alias the inputs");
     const int B = c->B, Y = c->Y, X = c->X, Z = c->Z, N = Y * X * Z;
     hipStream_t s = (hipStream_t)stream;
-    float* w = static_cast<float*>(workspace);
     const size_t nVy = (size_t)(Y + 1) * X * Z, nVx = (size_t)Y * (X + 1) * Z, nVz = (size_t)Y * X * (Z + 1);
-    float* svy = w; w += B * nVy;
-    float* svx = w; w += B * nVx;
-    float* svz = w; w += B * nVz;
-    float* R = w; w += (size_t)B * N;
-    float* T1 = w; w += (size_t)B * N;
-    float* T2 = w; w += (size_t)B * N;
-    void* pcg_ws = w + 256;
+    float *svy = l.svy, *svx = l.svx, *svz = l.svz, *R = l.sol.R, *T1 = l.sol.T1, *T2 = l.sol.T2;
     if (saved_vy) { svy = saved_vy; svx = saved_vx; svz = saved_vz; }     // training: the post-diffusion velocity is the only state the adjoint needs
 
     K3Args a{};
@@ -1129,7 +1160,7 @@ extern "C" int sol_karman3d_step_fwd(const sol_karman3d_cfg* c, void* stream,
     SOL_LAUNCH_CHECK();
 
     float* res = nullptr;
-    if (int e = pressure_solve_any3d(s, c, direct_header_host, active, R, T1, T2, pcg_ws, &res)) return e;
+    if (int e = pressure_solve_any3d(s, c, direct_header_host, active, R, T1, T2, l.sol.pcg, &res)) return e;
     a.p = res;
     SOL_LAUNCH(k3_project, dim3(grid_for(faces), B), dim3(256), 0, s, a);
     SOL_LAUNCH_CHECK();
@@ -1138,10 +1169,7 @@ extern "C" int sol_karman3d_step_fwd(const sol_karman3d_cfg* c, void* stream,
 
 extern "C" size_t sol_karman3d_step_bwd_workspace_bytes(const sol_karman3d_cfg* c) {
     if (!c) return 0;
-    const size_t B = c->B, Y = c->Y, X = c->X, Z = c->Z;
-    // g_a (fp32) and g_c (int64 fixed point), three components each + rhs + two transform buffers + the absmax slots
-    const size_t floats = B * (3 * ((Y + 1) * X * Z + Y * (X + 1) * Z + Y * X * (Z + 1)) + 3 * Y * X * Z + FX_SLOTS) + 256;
-    return floats * sizeof(float) + k3_pcg_workspace_bytes(c);
+    return k3_bwd_layout(c, false, nullptr).bytes;
 }
 
 namespace {
@@ -1160,8 +1188,8 @@ int step_bwd3d(const char* who, const sol_karman3d_cfg* c, void* stream,
                 "%s: NULL pointer argument", who);
     SOL_REQUIRE(!rx || (rx->vy_in && rx->vx_in && rx->vz_in && rx->g_re), "%s: NULL pointer argument", who);
     if (int e = check_blob3d(c, direct_header_host)) return e;
-    const size_t plain_bytes = sol_karman3d_step_bwd_workspace_bytes(c);
-    SOL_REQUIRE(workspace_bytes >= plain_bytes + (rx ? sol_re3_partial_bytes(c) : 0), "workspace too small");
+    const K3Bwd l = k3_bwd_layout(c, rx != nullptr, workspace);
+    SOL_REQUIRE(workspace_bytes >= l.bytes, "workspace too small");
     if (rx) {
         const void* outs[] = {g_vy_in, g_vx_in, g_vz_in};
         const void* ins[] = {rx->vy_in, rx->vx_in, rx->vz_in};
@@ -1175,27 +1203,20 @@ int step_bwd3d(const char* who, const sol_karman3d_cfg* c, void* stream,
     const int B = c->B, Y = c->Y, X = c->X, Z = c->Z, N = Y * X * Z;
     hipStream_t s = (hipStream_t)stream;
     const size_t nVy = (size_t)(Y + 1) * X * Z, nVx = (size_t)Y * (X + 1) * Z, nVz = (size_t)Y * X * (Z + 1), faces = nVy + nVx + nVz;
-    float* w = static_cast<float*>(workspace);
     K3BArgs a{};
     a.B = B; a.Y = Y; a.X = X; a.Z = Z; a.dtdx = c->dt / c->dx; a.adt = c->dt * c->res * c->res; a.grad_pad = c->grad_pad;
     a.re = re; a.active = active; a.bcm = velBCyMask; a.bc_stride = bc_batch_stride;
     a.svy = saved_vy; a.svx = saved_vx; a.svz = saved_vz; a.goy = g_vy_out; a.gox = g_vx_out; a.goz = g_vz_out;
     SOL_REQUIRE(faces % 2 == 0, "%s: odd face count (%zu): even X, Z expected", who, faces);
-    // per-simulation layout of g_c: [b][y faces | x faces | z faces] int64 -- k3b_rhs clears simulation b's block
     SOL_REQUIRE(reinterpret_cast<uintptr_t>(workspace) % 16 == 0, "%s: workspace must be 16-byte aligned", who);
-    long long* gc = reinterpret_cast<long long*>(w); w += 2 * B * faces;
-    a.gcy = gc; a.gcx = gc + B * nVy; a.gcz = a.gcx + B * nVx;
-    a.gay = w; w += B * nVy; a.gax = w; w += B * nVx; a.gaz = w; w += B * nVz;
-    a.gmax = reinterpret_cast<unsigned*>(w); w += (size_t)B * FX_SLOTS;
-    float* R = w; w += (size_t)B * N;
-    float* T1 = w; w += (size_t)B * N;
-    float* T2 = w; w += (size_t)B * N;
-    void* pcg_ws = w + 256;
-    a.rhs = R; a.giy = g_vy_in; a.gix = g_vx_in; a.giz = g_vz_in;
+    a.gcy = l.gc; a.gcx = l.gc + B * nVy; a.gcz = a.gcx + B * nVx;
+    a.gay = l.gay; a.gax = l.gax; a.gaz = l.gaz;
+    a.gmax = l.gmax;
+    a.rhs = l.sol.R; a.giy = g_vy_in; a.gix = g_vx_in; a.giz = g_vz_in;
     SOL_LAUNCH(k3b_rhs, dim3(grid_for(N), B), dim3(256), 0, s, a);
     SOL_LAUNCH_CHECK();
     float* res = nullptr;
-    if (int e = pressure_solve_any3d(s, c, direct_header_host, active, R, T1, T2, pcg_ws, &res)) return e;
+    if (int e = pressure_solve_any3d(s, c, direct_header_host, active, l.sol.R, l.sol.T1, l.sol.T2, l.sol.pcg, &res)) return e;
     a.gdiv = res;
     {   // wave per column, a few columns per wave: 1 024 workgroups at most publish into the 64 absmax slots
         const size_t cols = (size_t)(Y + 1) * X + (size_t)Y * (X + 1) + (size_t)Y * X;
@@ -1212,13 +1233,12 @@ int step_bwd3d(const char* who, const sol_karman3d_cfg* c, void* stream,
     SOL_LAUNCH(k3b_diffuse_adj, dim3(grid_for(faces), B), dim3(256), 0, s, a);
     SOL_LAUNCH_CHECK();
     if (!rx) return SOL_OK;
-    // g' of the Reynolds-number gradient = what k3b_diffuse_adj has just read: fx_get(g_c) (. (1 - bcm) on v_y); the partial sums lie behind
-    // the plain adjoint's workspace
+    // g' of the Reynolds-number gradient = what k3b_diffuse_adj has just read: fx_get(g_c) (. (1 - bcm) on v_y)
     Re3In in{};
     in.src = RE3_FIXED;
     in.gcy = a.gcy; in.gcx = a.gcx; in.gcz = a.gcz; in.gmax = a.gmax; in.bcm = velBCyMask; in.bc_stride = bc_batch_stride;
     in.vy_in = rx->vy_in; in.vx_in = rx->vx_in; in.vz_in = rx->vz_in; in.re = re;
-    in.partial = sol_re3_partial_at(workspace, plain_bytes);
+    in.partial = l.partial;
     in.g_re = rx->g_re; in.accumulate = rx->accumulate;
     return sol_re3_reduce(s, c, in);
 }
@@ -1237,7 +1257,7 @@ extern "C" int sol_karman3d_step_bwd(const sol_karman3d_cfg* c, void* stream,
 
 extern "C" size_t sol_karman3d_step_bwd_re_workspace_bytes(const sol_karman3d_cfg* c) {
     if (!c) return 0;
-    return sol_karman3d_step_bwd_workspace_bytes(c) + sol_re3_partial_bytes(c);
+    return k3_bwd_layout(c, true, nullptr).bytes;
 }
 
 extern "C" int sol_karman3d_step_bwd_re(const sol_karman3d_cfg* c, void* stream,
@@ -1258,17 +1278,14 @@ extern "C" int sol_karman3d_pressure_solve(const sol_karman3d_cfg* c, void* stre
     SOL_REQUIRE(c->B >= 1 && c->Y >= 8 && c->X >= 8 && c->Z >= 8 && c->B <= 65535, "sol_karman3d_pressure_solve: B >= 1, Y, X, Z >= 8");
     SOL_REQUIRE(active && rhs && p && workspace, "sol_karman3d_pressure_solve: NULL pointer argument");
     if (int e = check_blob3d(c, direct_header_host)) return e;
-    SOL_REQUIRE(workspace_bytes >= sol_karman3d_step_workspace_bytes(c), "workspace too small");
+    const K3Fwd l = k3_fwd_layout(c, workspace);          // the step's layout: its solver part is used
+    SOL_REQUIRE(workspace_bytes >= l.bytes, "workspace too small");
     const int B = c->B;
-    const size_t N = (size_t)c->Y * c->X * c->Z, faces = (size_t)(c->Y + 1) * c->X * c->Z + (size_t)c->Y * (c->X + 1) * c->Z + (size_t)c->Y * c->X * (c->Z + 1);
+    const size_t N = (size_t)c->Y * c->X * c->Z;
     hipStream_t s = (hipStream_t)stream;
-    float* w = static_cast<float*>(workspace) + B * faces;          // the step's layout: R, T1, T2 after the three components
-    float* R = w; w += B * N;
-    float* T1 = w; w += B * N;
-    float* T2 = w; w += B * N;
-    SOL_LAUNCH(k3_fill, dim3(grid_for(B * N)), dim3(256), 0, s, R, rhs, B * N);
+    SOL_LAUNCH(k3_fill, dim3(grid_for(B * N)), dim3(256), 0, s, l.sol.R, rhs, B * N);
     float* res = nullptr;
-    if (int e = pressure_solve_any3d(s, c, direct_header_host, active, R, T1, T2, w + 256, &res)) return e;
+    if (int e = pressure_solve_any3d(s, c, direct_header_host, active, l.sol.R, l.sol.T1, l.sol.T2, l.sol.pcg, &res)) return e;
     SOL_LAUNCH(k3_fill, dim3(grid_for(B * N)), dim3(256), 0, s, p, (const float*)res, B * N);
     SOL_LAUNCH_CHECK();
     return SOL_OK;

@@ -252,25 +252,21 @@ __global__ void __launch_bounds__(256) k3d_diffuse_adj(K3DArgs a) {
     }
 }
 
-// the workspace: g_d_in accumulators (int64), gU_y, gU_x, gU_z (fp32), the absmax slots; 256-byte granules
+// the workspace: g_d_in accumulators (int64), gU_y, gU_x, gU_z (fp32), the absmax slots; 256-byte granules; with re, the partial sums of
+// the Reynolds-number reduction behind them
 struct K3DLayout {
     long long* gD;
     float *gUy, *gUx, *gUz;
     unsigned* gmax;
+    double* partial;
     size_t bytes;
 };
-K3DLayout k3d_layout(const sol_karman3d_cfg* c, void* ws) {
+K3DLayout k3d_layout(const sol_karman3d_cfg* c, bool re, void* ws) {
     const size_t B = c->B, N = (size_t)c->Y * c->X * c->Z;
-    char* w = ws ? reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(ws) + 255) / 256 * 256) : nullptr;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { char* p = w ? w + off : nullptr; off += align_up(bytes, 256); return p; };
-    K3DLayout l{};
-    l.gD = reinterpret_cast<long long*>(take(B * N * sizeof(long long)));
-    l.gUy = reinterpret_cast<float*>(take(B * N * sizeof(float)));
-    l.gUx = reinterpret_cast<float*>(take(B * N * sizeof(float)));
-    l.gUz = reinterpret_cast<float*>(take(B * N * sizeof(float)));
-    l.gmax = reinterpret_cast<unsigned*>(take(B * FX_SLOTS * sizeof(unsigned)));
-    l.bytes = off + 256;                       // + the alignment of the caller's pointer
+    Carve w(ws);
+    K3DLayout l{w.take<long long>(B * N), w.take<float>(B * N), w.take<float>(B * N), w.take<float>(B * N), w.take<unsigned>(B * FX_SLOTS)};
+    l.bytes = w.bytes();
+    if (re) l.partial = sol_re3_partial_behind(w, c, &l.bytes);
     return l;
 }
 
@@ -296,9 +292,8 @@ int density_bwd3d(const char* who, const sol_karman3d_cfg* c, void* stream,
     const size_t N = (size_t)Y * X * Z, faces = (size_t)(Y + 1) * X * Z + (size_t)Y * (X + 1) * Z + (size_t)Y * X * (Z + 1);
     SOL_REQUIRE(faces % 2 == 0, "%s: odd face count (%zu): even X, Z expected", who, faces);
     SOL_REQUIRE(reinterpret_cast<uintptr_t>(workspace) % 16 == 0, "%s: workspace must be 16-byte aligned", who);
-    const size_t plain = k3d_layout(c, nullptr).bytes;
-    const size_t need = plain + (rx ? sol_re3_partial_bytes(c) : 0);
-    SOL_REQUIRE(workspace_bytes >= need, "%s: workspace too small (%zu < %zu bytes)", who, workspace_bytes, need);
+    const K3DLayout l = k3d_layout(c, rx != nullptr, workspace);
+    SOL_REQUIRE(workspace_bytes >= l.bytes, "%s: workspace too small (%zu < %zu bytes)", who, workspace_bytes, l.bytes);
     const void* outs[] = {g_d_in, g_vy_in, g_vx_in, g_vz_in, rx ? rx->g_re : nullptr};
     const void* ins[] = {d_in, inflow, saved_vy, saved_vx, saved_vz, re, velBCyMask, g_d_out,
                          rx ? rx->vy_in : nullptr, rx ? rx->vx_in : nullptr, rx ? rx->vz_in : nullptr};
@@ -307,7 +302,6 @@ int density_bwd3d(const char* who, const sol_karman3d_cfg* c, void* stream,
     for (int p = 0; p < 5; ++p)
         for (int q = p + 1; q < 5; ++q) SOL_REQUIRE(!outs[q] || outs[p] != outs[q], "%s: g_d_in, g_v*_in and g_re must be buffers of their own", who);
     hipStream_t s = (hipStream_t)stream;
-    const K3DLayout l = k3d_layout(c, workspace);
     K3DArgs a{};
     a.B = B; a.Y = Y; a.X = X; a.Z = Z; a.dtdx = c->dt / c->dx; a.adt = c->dt * c->res * c->res;
     a.inflow_before = c->inflow_before; a.accumulate = accumulate != 0;
@@ -326,13 +320,12 @@ int density_bwd3d(const char* who, const sol_karman3d_cfg* c, void* stream,
     SOL_LAUNCH(k3d_diffuse_adj, dim3(grid_of(faces + N), B), dim3(256), 0, s, a);
     SOL_LAUNCH_CHECK();
     if (!rx) return SOL_OK;
-    // g' of the Reynolds-number gradient = the face values k3d_diffuse_adj has just formed from gU; the partial sums lie behind the plain
-    // adjoint's part of the workspace
+    // g' of the Reynolds-number gradient = the face values k3d_diffuse_adj has just formed from gU
     Re3In in{};
     in.src = RE3_GU;
     in.gUy = l.gUy; in.gUx = l.gUx; in.gUz = l.gUz; in.gmax = l.gmax; in.bcm = velBCyMask; in.bc_stride = bc_batch_stride;
     in.vy_in = rx->vy_in; in.vx_in = rx->vx_in; in.vz_in = rx->vz_in; in.re = re;
-    in.partial = sol_re3_partial_at(workspace, plain);
+    in.partial = l.partial;
     in.g_re = rx->g_re; in.accumulate = rx->accumulate;
     return sol_re3_reduce(s, c, in);
 }
@@ -341,7 +334,7 @@ int density_bwd3d(const char* who, const sol_karman3d_cfg* c, void* stream,
 
 extern "C" size_t sol_karman3d_density_bwd_workspace_bytes(const sol_karman3d_cfg* c) {
     if (!shape_ok(c)) return 0;
-    return k3d_layout(c, nullptr).bytes;
+    return k3d_layout(c, false, nullptr).bytes;
 }
 
 extern "C" int sol_karman3d_density_bwd(const sol_karman3d_cfg* c, void* stream,
@@ -354,8 +347,8 @@ extern "C" int sol_karman3d_density_bwd(const sol_karman3d_cfg* c, void* stream,
 }
 
 extern "C" size_t sol_karman3d_density_bwd_re_workspace_bytes(const sol_karman3d_cfg* c) {
-    const size_t plain = sol_karman3d_density_bwd_workspace_bytes(c);
-    return plain ? plain + sol_re3_partial_bytes(c) : 0;
+    if (!shape_ok(c)) return 0;
+    return k3d_layout(c, true, nullptr).bytes;
 }
 
 extern "C" int sol_karman3d_density_bwd_re(const sol_karman3d_cfg* c, void* stream,

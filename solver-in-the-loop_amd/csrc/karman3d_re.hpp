@@ -41,7 +41,7 @@ struct Re3In {
     const float* bcm;                    // velBCyMask
     long bc_stride;
     const float *vy_in, *vx_in, *vz_in, *re;      // the step's INPUT velocity and Reynolds numbers
-    double* partial;                     // [B][re_nblk(faces)] scratch (sol_re3_partial_bytes, sol_re3_partial_at)
+    double* partial;                     // [B][re_nblk(faces)] scratch (sol_re3_partial_behind)
     float* g_re;                         // [B]
     int accumulate;                      // 1: one fp32 add onto g_re
 };
@@ -53,11 +53,9 @@ struct Re3Extra {
     int accumulate;
 };
 
-// bytes of the partial sums for cfg's grid and batch, behind a plain call's workspace of `plain` bytes (256-byte granule; includes the
-// eight bytes that align the doubles), and where they start
-size_t sol_re3_partial_bytes(const sol_karman3d_cfg* c);
-inline double* sol_re3_partial_at(void* workspace, size_t plain) {
-    return reinterpret_cast<double*>((reinterpret_cast<uintptr_t>(workspace) + plain + 7) / 8 * 8);
-}
+// the partial sums for cfg's grid and batch as the optional last member of an adjoint's layout (carve.hpp): behind the plain call's
+// part `plain`, on the next eight bytes past plain.bytes() of the caller's pointer; *bytes = the layout's bytes with them (256-byte
+// granule; includes the eight bytes that align the doubles)
+double* sol_re3_partial_behind(const Carve& plain, const sol_karman3d_cfg* c, size_t* bytes);
 // the two launches (k3_re_partial, k3_re_final) on stream s: no synchronisation, no allocation, nothing read on the host
 int sol_re3_reduce(hipStream_t s, const sol_karman3d_cfg* c, const Re3In& in);

@@ -80,7 +80,12 @@ size_t faces_of(const sol_karman3d_cfg* c) {
 
 }  // namespace
 
-size_t sol_re3_partial_bytes(const sol_karman3d_cfg* c) { return align_up((size_t)c->B * re_nblk(faces_of(c)) * sizeof(double) + 8, 256); }
+double* sol_re3_partial_behind(const Carve& plain, const sol_karman3d_cfg* c, size_t* bytes) {
+    Carve w(plain.end(), 8, 8);
+    double* partial = w.take<double>((size_t)c->B * re_nblk(faces_of(c)));
+    *bytes = plain.bytes() + align_up(w.bytes(), 256);
+    return partial;
+}
 
 int sol_re3_reduce(hipStream_t s, const sol_karman3d_cfg* c, const Re3In& in) {
     Re3Args a{};

@@ -195,24 +195,21 @@ __global__ void __launch_bounds__(256) k_kd_diffuse_adj(KDArgs a) {
     }
 }
 
-// the workspace: g_d_in accumulators (int64), gU_y, gU_x (fp32), the absmax slots; 256-byte granules
+// the workspace: g_d_in accumulators (int64), gU_y, gU_x (fp32), the absmax slots, with re the partial sums of the Reynolds-number
+// reduction; 256-byte granules
 struct KDLayout {
     long long* gD;
     float *gUy, *gUx;
     unsigned* gmax;
+    double* partial;
     size_t bytes;
 };
-KDLayout kd_layout(const sol_karman_cfg* c, void* ws) {
+KDLayout kd_layout(const sol_karman_cfg* c, bool re, void* ws) {
     const size_t B = c->B, N = (size_t)c->Y * c->X;
-    char* w = ws ? reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(ws) + 255) / 256 * 256) : nullptr;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { char* p = w ? w + off : nullptr; off += align_up(bytes, 256); return p; };
-    KDLayout l{};
-    l.gD = reinterpret_cast<long long*>(take(B * N * sizeof(long long)));
-    l.gUy = reinterpret_cast<float*>(take(B * N * sizeof(float)));
-    l.gUx = reinterpret_cast<float*>(take(B * N * sizeof(float)));
-    l.gmax = reinterpret_cast<unsigned*>(take(B * FX_SLOTS * sizeof(unsigned)));
-    l.bytes = off + 256;                       // + the alignment of the caller's pointer
+    Carve w(ws);
+    KDLayout l{w.take<long long>(B * N), w.take<float>(B * N), w.take<float>(B * N), w.take<unsigned>(B * FX_SLOTS)};
+    if (re) l.partial = sol_re_partial_take(w, c);
+    l.bytes = w.bytes();
     return l;
 }
 
@@ -220,7 +217,7 @@ KDLayout kd_layout(const sol_karman_cfg* c, void* ws) {
 
 extern "C" size_t sol_karman_density_bwd_workspace_bytes(const sol_karman_cfg* c) {
     if (!c || c->B < 1 || c->Y < 1 || c->X < 1) return 0;
-    return kd_layout(c, nullptr).bytes;
+    return kd_layout(c, false, nullptr).bytes;
 }
 
 namespace {
@@ -239,9 +236,8 @@ int density_bwd(const char* who, const sol_karman_cfg* c, void* stream,
                 "%s: NULL pointer argument", who);
     SOL_REQUIRE(inflow || !c->inflow_before, "%s: cfg.inflow_before needs the inflow mask (the advected field is d_in + inflow)", who);
     SOL_REQUIRE(!rx || (rx->vy_in && rx->vx_in && rx->g_re), "%s: NULL pointer argument", who);
-    const size_t plain = kd_layout(c, nullptr).bytes;
-    const size_t need = plain + (rx ? sol_re_partial_bytes(c) : 0);
-    SOL_REQUIRE(workspace_bytes >= need, "%s: workspace too small (%zu < %zu bytes)", who, workspace_bytes, need);
+    const KDLayout l = kd_layout(c, rx != nullptr, workspace);
+    SOL_REQUIRE(workspace_bytes >= l.bytes, "%s: workspace too small (%zu < %zu bytes)", who, workspace_bytes, l.bytes);
     const void* outs[] = {g_d_in, g_vy_in, g_vx_in, rx ? rx->g_re : nullptr};
     const void* ins[] = {d_in, inflow, saved_vy, saved_vx, re, velBCyMask, g_d_out, rx ? rx->vy_in : nullptr, rx ? rx->vx_in : nullptr};
     for (const void* o : outs)
@@ -251,7 +247,6 @@ int density_bwd(const char* who, const sol_karman_cfg* c, void* stream,
     const int B = c->B, Y = c->Y, X = c->X, N = Y * X;
     const size_t items = (size_t)(Y + 1) * X + (size_t)Y * (X + 1) + N;
     hipStream_t s = (hipStream_t)stream;
-    const KDLayout l = kd_layout(c, workspace);
     KDArgs a{};
     a.B = B; a.Y = Y; a.X = X; a.dtdx = c->dt / c->dx; a.adt = c->dt * c->res * c->res;
     a.inflow_before = c->inflow_before; a.accumulate = accumulate != 0;
@@ -269,13 +264,12 @@ int density_bwd(const char* who, const sol_karman_cfg* c, void* stream,
     SOL_LAUNCH(k_kd_diffuse_adj, dim3((unsigned)((items + 255) / 256), B), dim3(256), 0, s, a);
     SOL_LAUNCH_CHECK();
     if (!rx) return SOL_OK;
-    // g' of the Reynolds-number gradient = the face values k_kd_diffuse_adj has just formed from gU (kd_face_y / kd_face_x); the partial
-    // sums lie behind the plain adjoint's part of the workspace
+    // g' of the Reynolds-number gradient = the face values k_kd_diffuse_adj has just formed from gU (kd_face_y / kd_face_x)
     ReIn in{};
     in.src = RE_GU;
     in.gUy = l.gUy; in.gUx = l.gUx; in.gmax = l.gmax; in.bcm = velBCyMask; in.bc_stride = bc_batch_stride;
     in.vy_in = rx->vy_in; in.vx_in = rx->vx_in; in.re = re;
-    in.partial = reinterpret_cast<double*>(reinterpret_cast<char*>(l.gD) + (plain - 256));
+    in.partial = l.partial;
     in.g_re = rx->g_re; in.accumulate = rx->accumulate;
     return sol_re_reduce(s, c, in);
 }
@@ -292,8 +286,8 @@ extern "C" int sol_karman_density_bwd(const sol_karman_cfg* c, void* stream,
 }
 
 extern "C" size_t sol_karman_density_bwd_re_workspace_bytes(const sol_karman_cfg* c) {
-    const size_t plain = sol_karman_density_bwd_workspace_bytes(c);
-    return plain ? plain + sol_re_partial_bytes(c) : 0;
+    if (!c || c->B < 1 || c->Y < 1 || c->X < 1) return 0;
+    return kd_layout(c, true, nullptr).bytes;
 }
 
 extern "C" int sol_karman_density_bwd_re(const sol_karman_cfg* c, void* stream,

@@ -17,6 +17,7 @@
 //   k_l_correct   v_y, v_x += out_std * to_staggered(network output)  (+ the applied correction as a field of its own)
 // The adjoint of this path lives in karman_large_bwd.hip; it reads the post-diffusion velocity (sv_y, sv_x) that
 // sol_karman_step_fwd_large_saved hands out and runs the same pressure solve (pressure_solve_any2d, pcg.hip).
+// The host side of the step -- its six entry points, their checks and their workspace -- is large_fwd in pcg.hip.
 #include "large2d.hpp"
 
 namespace {
@@ -408,20 +409,27 @@ int sol_large_box_back(hipStream_t s, int B, int Y, int X, const float* blob, co
 }
 
 // ---- the direct pressure solve on its own buffers (shared by the forward step and the adjoint, karman_large_bwd.hip) ----
-// layout from `base`: T0 (rhs in, pressure out), T1, T2 (spectral coefficients), window scratch (u, t2w: Y*64 each; x0w, W2: 64*64 each)
-size_t sol_large_direct_floats(const sol_karman_cfg* c) {
+namespace {
+
+// float-dense from `base`: T0 (rhs in, pressure out), T1, T2 (spectral coefficients, stored TRANSPOSED [X][Y] as ilT), then the scratch
+// of the capacitance correction: U, V [Y][64] and X0, W2 [64][64] per simulation in the one-window form whatever the window (hdr NULL or
+// FD02), [Y][CP] and [RP][CP] in the scattered form (hdr FDS1)
+struct DirectLayout { float *T0, *T1, *T2, *U, *V, *X0, *W2; size_t bytes; };
+DirectLayout direct_layout(const sol_karman_cfg* c, const int32_t* hdr, void* base) {
     const size_t B = c->B, Y = c->Y, X = c->X;
-    return B * (3 * Y * X + 2 * Y * 64 + 2 * 64 * 64);
-}
-// the same for the blob whose host header is hdr: the scattered solve keeps U, V as Y x CP and X0, W2 as RP x CP (NULL or FD02: the window form)
-size_t sol_large_direct_floats(const sol_karman_cfg* c, const int32_t* hdr) {
-    if (!hdr || hdr[0] != FDS_MAGIC) return sol_large_direct_floats(c);
-    const HeaderSc h = header_sc(hdr);
-    const size_t B = c->B, Y = c->Y, X = c->X, RP = h.RP > 0 ? h.RP : 0, CP = h.CP > 0 ? h.CP : 0;
-    return B * (3 * Y * X + 2 * Y * CP + 2 * RP * CP);
+    size_t uv = Y * 64, xw = 64 * 64;
+    if (hdr && hdr[0] == FDS_MAGIC) {
+        const HeaderSc h = header_sc(hdr);
+        const size_t RP = h.RP > 0 ? h.RP : 0, CP = h.CP > 0 ? h.CP : 0;
+        uv = Y * CP; xw = RP * CP;
+    }
+    Carve w = Carve::packed(base);
+    DirectLayout l{w.take<float>(B * Y * X), w.take<float>(B * Y * X), w.take<float>(B * Y * X), w.take<float>(B * uv), w.take<float>(B * uv),
+                   w.take<float>(B * xw), w.take<float>(B * xw)};
+    l.bytes = w.bytes();
+    return l;
 }
 
-namespace {
 
 inline size_t pad4(size_t n) { return (n + 3) / 4 * 4; }
 // words of a scattered blob with this header (precond.scattered_solver_blob's layout)
@@ -445,7 +453,6 @@ int scattered_check(const sol_karman_cfg* c, const char* who, const int32_t* hdr
 
 // M p = T0 as sol_large_direct_solve, the window replaced by the row list R and the column list C of the support set:
 //   box forward;  U = T2 Qx[:,C];  X0 = Qy[R,:] U;  W2 = 0, W2[S] = -K' X0[S];  V = Qy[:,R] W2;  T1 = V Qx[C,:];  T2 += T1 / lam;  box back
-// layout from `base`: T0 (rhs in, pressure out), T1, T2, U, V (Y x CP each), X0, W2 (RP x CP each)
 int scattered_solve(hipStream_t s, const sol_karman_cfg* c, const int32_t* hdr, float* base) {
     const HeaderSc h = header_sc(hdr);
     const int B = c->B, Y = c->Y, X = c->X, N = Y * X, SP = h.SP, RP = h.RP, CP = h.CP;
@@ -458,14 +465,8 @@ int scattered_solve(hipStream_t s, const sol_karman_cfg* c, const int32_t* hdr, 
     const float* QxC = QyR + (size_t)RP * Y;                          // [X][CP]
     const float* QyRt = QxC + (size_t)X * CP;                         // [Y][RP]
     const float* QxCr = QyRt + (size_t)Y * RP;                        // [CP][X]
-    float* w = base;
-    float* T0 = w; w += (size_t)B * N;
-    float* T1 = w; w += (size_t)B * N;
-    float* T2 = w; w += (size_t)B * N;
-    float* U = w; w += (size_t)B * Y * CP;
-    float* V = w; w += (size_t)B * Y * CP;
-    float* X0 = w; w += (size_t)B * RP * CP;
-    float* W2 = w; w += (size_t)B * RP * CP;
+    const DirectLayout l = direct_layout(c, hdr, base);
+    float *T0 = l.T0, *T1 = l.T1, *T2 = l.T2, *U = l.U, *V = l.V, *X0 = l.X0, *W2 = l.W2;
     const long sN = N, sU = (long)Y * CP, sW = (long)RP * CP;
     if (int e = sol_large_box_forward(s, B, Y, X, c->direct, T0, T1, T2, nullptr)) return e;
     if (int e = gemm(s, B, T2, X, sN, QxC, CP, 0, U, CP, sU, Y, CP, X, 0)) return e;
@@ -482,6 +483,8 @@ int scattered_solve(hipStream_t s, const sol_karman_cfg* c, const int32_t* hdr, 
 }
 
 }  // namespace
+
+size_t sol_large_direct_bytes(const sol_karman_cfg* c, const int32_t* hdr) { return direct_layout(c, hdr, nullptr).bytes; }
 
 int sol_large_direct_check(const sol_karman_cfg* c, const char* who, const int32_t* hdr) {
     SOL_REQUIRE(c->direct && c->direct_n > 0, "%s needs the direct-solver blob (cfg.direct)", who);
@@ -507,14 +510,8 @@ int sol_large_direct_solve(hipStream_t s, const sol_karman_cfg* c, const int32_t
     const float* KpT = ilT + (size_t)X * Y;
     const int* sidx = reinterpret_cast<const int*>(KpT + (size_t)SP * SP);
     const float* QxW = reinterpret_cast<const float*>(sidx + SP);     // [X][win]
-    float* w = base;
-    float* T0 = w; w += (size_t)B * N;                 // rhs / T3 / pressure
-    float* T1 = w; w += (size_t)B * N;
-    float* T2 = w; w += (size_t)B * N;                 // spectral coefficients, stored TRANSPOSED [X][Y] (matches ilT)
-    float* U = w; w += (size_t)B * Y * 64;             // [Y][win]
-    float* V = w; w += (size_t)B * Y * 64;
-    float* X0 = w; w += (size_t)B * 64 * 64;           // [win][win]
-    float* W2 = w; w += (size_t)B * 64 * 64;
+    const DirectLayout l = direct_layout(c, hdr, base);
+    float *T0 = l.T0, *T1 = l.T1, *T2 = l.T2, *U = l.U, *V = l.V, *X0 = l.X0, *W2 = l.W2;      // U, V: [Y][win], X0, W2: [win][win]
     const long sN = N, sU = (long)Y * 64, sW = 64 * 64;
     if (int e = sol_large_box_forward(s, B, Y, X, c->direct, T0, T1, T2, nullptr)) return e;
     // window values of G b: U = T2 Qx[:, win] ; X0 = Qy[win, :] U
@@ -529,54 +526,6 @@ int sol_large_direct_solve(hipStream_t s, const sol_karman_cfg* c, const int32_t
     SOL_LAUNCH(k_l_scale, dim3((N + 255) / 256, B), dim3(256), 0, s, T2, (const float*)T1, ilT, Y, X, (const int*)nullptr);
     // p = Qy (T2 Qx)
     return sol_large_box_back(s, B, Y, X, c->direct, T2, T1, T0, nullptr);
-}
-
-extern "C" size_t sol_karman_step_large_workspace_bytes(const sol_karman_cfg* c) {
-    if (!c) return 0;
-    const size_t B = c->B, Y = c->Y, X = c->X;
-    // sv_y, sv_x, then the direct solve's buffers
-    const size_t floats = B * ((Y + 1) * X + Y * (X + 1)) + sol_large_direct_floats(c) + 256;
-    return floats * sizeof(float);
-}
-
-extern "C" size_t sol_karman_step_large_workspace_bytes_for(const sol_karman_cfg* c, const int32_t* direct_header_host) {
-    if (!c) return 0;
-    const size_t B = c->B, Y = c->Y, X = c->X;
-    const size_t floats = B * ((Y + 1) * X + Y * (X + 1)) + sol_large_direct_floats(c, direct_header_host) + 256;
-    return floats * sizeof(float);
-}
-
-// the direct-solve step of sol_karman_step_fwd_large (and of its buoyant form, sol_karman_step_fwd_large_buoy in pcg.hip)
-int sol_large_direct_step(const char* who, const sol_karman_cfg* c, void* stream, const SolLargeStep& io, const int32_t* direct_header_host,
-                          void* workspace, size_t workspace_bytes) {
-    SOL_REQUIRE(c != nullptr, "cfg is NULL");
-    SOL_REQUIRE(c->B >= 1 && c->Y >= 16 && c->X >= 16, "%s: B >= 1, Y, X >= 16 (got %d, %d, %d)", who, c->B, c->Y, c->X);
-    SOL_REQUIRE(io.vy_in && io.vx_in && io.re && io.active && io.velBCy && io.velBCyMask && io.vy_out && io.vx_out && workspace,
-                "%s: NULL pointer argument", who);
-    SOL_REQUIRE((io.d_in && io.inflow) || !io.d_out, "density output requested without d_in/inflow");
-    SOL_REQUIRE(!io.feat_out || io.feat_scale, "feat_out requires feat_scale");
-    SOL_REQUIRE(c->direct && c->direct_n > 0, "%s needs the direct-solver blob (cfg.direct)", who);
-    SOL_REQUIRE(io.vy_in != io.vy_out && io.vx_in != io.vx_out && io.d_in != io.d_out, "%s: outputs must not alias the inputs", who);
-    if (int e = sol_large_direct_check(c, who, direct_header_host)) return e;
-    SOL_REQUIRE(workspace_bytes >= sol_karman_step_large_workspace_bytes_for(c, direct_header_host), "workspace too small");
-    const size_t B = c->B, Y = c->Y, X = c->X;
-    // workspace carve: sv_y, sv_x, the solver's buffers
-    float* w = static_cast<float*>(workspace);
-    float* svy = w; w += B * (Y + 1) * X;
-    float* svx = w; w += B * Y * (X + 1);
-    return sol_large_step(c, (hipStream_t)stream, io, svy, svx, true, direct_header_host, nullptr, nullptr, w);
-}
-
-extern "C" int sol_karman_step_fwd_large(const sol_karman_cfg* c, void* stream,
-                                         const float* d_in, const float* vy_in, const float* vx_in,
-                                         const float* re, const float* active, const float* inflow,
-                                         const float* velBCy, const float* velBCyMask, int64_t bc_batch_stride,
-                                         float* d_out, float* vy_out, float* vx_out,
-                                         float* feat_out, const float* feat_scale,
-                                         const int32_t* direct_header_host,
-                                         void* workspace, size_t workspace_bytes) {
-    const SolLargeStep io{d_in, vy_in, vx_in, re, active, inflow, velBCy, velBCyMask, bc_batch_stride, d_out, vy_out, vx_out, feat_out, feat_scale};
-    return sol_large_direct_step("sol_karman_step_fwd_large", c, stream, io, direct_header_host, workspace, workspace_bytes);
 }
 
 extern "C" int sol_karman_correct(void* stream, const float* out, float* vy, float* vx, float* cor_y, float* cor_x,
@@ -599,7 +548,7 @@ extern "C" int sol_karman_pressure_solve_large_direct(const sol_karman_cfg* c, v
     SOL_REQUIRE(rhs && p && workspace, "%s: NULL pointer argument", who);
     SOL_REQUIRE(p != rhs, "%s: outputs must not alias the inputs", who);
     if (int e = sol_large_direct_check(c, who, direct_header_host)) return e;
-    const size_t need = sol_large_direct_floats(c, direct_header_host) * sizeof(float);
+    const size_t need = sol_large_direct_bytes(c, direct_header_host);
     SOL_REQUIRE(workspace_bytes >= need, "%s: workspace too small (%zu < %zu bytes)", who, workspace_bytes, need);
     hipStream_t s = (hipStream_t)stream;
     float* base = static_cast<float*>(workspace);

@@ -238,25 +238,22 @@ __global__ void __launch_bounds__(256) k_lb_diffuse_adj(LBArgs a) {
     }
 }
 
-// the adjoint's own buffers in front of the solver's part: g_c (int64), g_a (fp32), the absmax slots; 256-byte granules
+// the adjoint's own buffers in front of the solver's part: g_c (int64), g_a (fp32), the absmax slots; with re, the partial sums of the
+// Reynolds-number reduction behind it; 256-byte granules
 struct BwdLayout {
     long long* gc;
     float* ga;
     unsigned* gmax;
     void* solver;
+    double* partial;
     size_t bytes;
 };
-BwdLayout bwd_layout(const sol_karman_cfg* c, bool direct, void* ws, const int32_t* hdr = nullptr) {
+BwdLayout bwd_layout(const sol_karman_cfg* c, bool direct, bool re, void* ws, const int32_t* hdr = nullptr) {
     const size_t B = c->B, Y = c->Y, X = c->X, faces = (Y + 1) * X + Y * (X + 1);
-    char* w = ws ? reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(ws) + 255) / 256 * 256) : nullptr;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { char* p = w ? w + off : nullptr; off += align_up(bytes, 256); return p; };
-    BwdLayout l{};
-    l.gc = reinterpret_cast<long long*>(take(B * faces * sizeof(long long)));
-    l.ga = reinterpret_cast<float*>(take(B * faces * sizeof(float)));
-    l.gmax = reinterpret_cast<unsigned*>(take(B * FX_SLOTS * sizeof(unsigned)));
-    l.solver = take(sol_large_solver_bytes(c, direct, hdr));
-    l.bytes = off + 256;                       // + the alignment of the caller's pointer
+    Carve w(ws);
+    BwdLayout l{w.take<long long>(B * faces), w.take<float>(B * faces), w.take<unsigned>(B * FX_SLOTS), w.take<char>(sol_large_solver_bytes(c, direct, hdr))};
+    if (re) l.partial = sol_re_partial_take(w, c);
+    l.bytes = w.bytes();
     return l;
 }
 
@@ -271,73 +268,12 @@ int common_check(const sol_karman_cfg* c, const char* who) {
 
 extern "C" size_t sol_karman_step_bwd_large_workspace_bytes(const sol_karman_cfg* c) {
     if (!c || c->B < 1 || c->Y < 1 || c->X < 1) return 0;
-    return bwd_layout(c, c->direct != nullptr, nullptr).bytes;
+    return bwd_layout(c, c->direct != nullptr, false, nullptr).bytes;
 }
 
 extern "C" size_t sol_karman_step_bwd_large_workspace_bytes_for(const sol_karman_cfg* c, const int32_t* direct_header_host) {
     if (!c || c->B < 1 || c->Y < 1 || c->X < 1) return 0;
-    return bwd_layout(c, c->direct != nullptr, nullptr, direct_header_host).bytes;
-}
-
-namespace {
-
-// sol_karman_step_fwd_large_saved, and with a force F = (fy, fx) its buoyant form (karman_buoyancy.hip)
-int fwd_large_saved(const char* who, const sol_karman_cfg* c, void* stream,
-                    const float* d_in, const float* vy_in, const float* vx_in,
-                    const float* re, const float* active, const float* inflow,
-                    const float* velBCy, const float* velBCyMask, int64_t bc_batch_stride,
-                    float* d_out, float* vy_out, float* vx_out, float* saved_vy, float* saved_vx,
-                    const int32_t* direct_header_host,
-                    const float* box_blob, const int32_t* box_header_host, int32_t* cg_info,
-                    void* workspace, size_t workspace_bytes, float fy, float fx) {
-    if (int e = common_check(c, who)) return e;
-    const bool direct = c->direct != nullptr;
-    SOL_REQUIRE(vy_in && vx_in && re && active && velBCy && velBCyMask && vy_out && vx_out && saved_vy && saved_vx && workspace,
-                "%s: NULL pointer argument", who);
-    SOL_REQUIRE((d_in && inflow) || !d_out, "%s: density output requested without d_in / inflow", who);
-    if (direct) { if (int e = sol_large_direct_check(c, who, direct_header_host)) return e; }
-    else if (int e = sol_large_cg_check(c, who, box_blob, box_header_host, cg_info, workspace)) return e;
-    const size_t need = sol_large_solver_bytes(c, direct, direct ? direct_header_host : nullptr) + 256;
-    SOL_REQUIRE(workspace_bytes >= need, "%s: workspace too small (%zu < %zu bytes)", who, workspace_bytes, need);
-    const void* outs[] = {d_out, vy_out, vx_out, saved_vy, saved_vx, cg_info};
-    const void* ins[] = {d_in, vy_in, vx_in, re, active, inflow, velBCy, velBCyMask, box_blob};
-    for (const void* o : outs)
-        for (const void* i : ins) SOL_REQUIRE(!o || o != i, "%s: outputs must not alias the inputs", who);
-    SOL_REQUIRE(saved_vy != vy_out && saved_vx != vx_out && saved_vy != saved_vx, "%s: saved_vy / saved_vx must be buffers of their own", who);
-    void* solver = reinterpret_cast<void*>((reinterpret_cast<uintptr_t>(workspace) + 255) / 256 * 256);
-    SOL_REQUIRE(fy - fy == 0.f && fx - fx == 0.f, "%s: the force must be finite (got %g, %g)", who, (double)fy, (double)fx);
-    SOL_REQUIRE((fy == 0.f && fx == 0.f) || (d_in && inflow && d_out), "%s: a non-zero force needs d_in, inflow and d_out", who);
-    SolLargeStep io{d_in, vy_in, vx_in, re, active, inflow, velBCy, velBCyMask, bc_batch_stride, d_out, vy_out, vx_out, nullptr, nullptr};
-    io.buoy_y = c->dt * fy; io.buoy_x = c->dt * fx;
-    return sol_large_step(c, (hipStream_t)stream, io, saved_vy, saved_vx, direct, direct_header_host, box_blob, cg_info, solver);
-}
-
-}  // namespace
-
-extern "C" int sol_karman_step_fwd_large_saved(const sol_karman_cfg* c, void* stream,
-                                               const float* d_in, const float* vy_in, const float* vx_in,
-                                               const float* re, const float* active, const float* inflow,
-                                               const float* velBCy, const float* velBCyMask, int64_t bc_batch_stride,
-                                               float* d_out, float* vy_out, float* vx_out, float* saved_vy, float* saved_vx,
-                                               const int32_t* direct_header_host,
-                                               const float* box_blob, const int32_t* box_header_host, int32_t* cg_info,
-                                               void* workspace, size_t workspace_bytes) {
-    const char* who = "sol_karman_step_fwd_large_saved";
-    return fwd_large_saved(who, c, stream, d_in, vy_in, vx_in, re, active, inflow, velBCy, velBCyMask, bc_batch_stride, d_out, vy_out, vx_out,
-                           saved_vy, saved_vx, direct_header_host, box_blob, box_header_host, cg_info, workspace, workspace_bytes, 0.f, 0.f);
-}
-
-extern "C" int sol_karman_step_fwd_large_saved_buoy(const sol_karman_cfg* c, void* stream,
-                                                    const float* d_in, const float* vy_in, const float* vx_in,
-                                                    const float* re, const float* active, const float* inflow,
-                                                    const float* velBCy, const float* velBCyMask, int64_t bc_batch_stride,
-                                                    float* d_out, float* vy_out, float* vx_out, float* saved_vy, float* saved_vx,
-                                                    const int32_t* direct_header_host,
-                                                    const float* box_blob, const int32_t* box_header_host, int32_t* cg_info,
-                                                    void* workspace, size_t workspace_bytes, float fy, float fx) {
-    const char* who = "sol_karman_step_fwd_large_saved_buoy";
-    return fwd_large_saved(who, c, stream, d_in, vy_in, vx_in, re, active, inflow, velBCy, velBCyMask, bc_batch_stride, d_out, vy_out, vx_out,
-                           saved_vy, saved_vx, direct_header_host, box_blob, box_header_host, cg_info, workspace, workspace_bytes, fy, fx);
+    return bwd_layout(c, c->direct != nullptr, false, nullptr, direct_header_host).bytes;
 }
 
 namespace {
@@ -369,9 +305,8 @@ int bwd_large(const char* who, const sol_karman_cfg* c, void* stream,
                 "%s: NULL pointer argument", who);
     if (direct) { if (int e = sol_large_direct_check(c, who, direct_header_host)) return e; }
     else if (int e = sol_large_cg_check(c, who, box_blob, box_header_host, cg_info, workspace)) return e;
-    const size_t plain = bwd_layout(c, direct, nullptr, direct ? direct_header_host : nullptr).bytes;
-    const size_t need = plain + (rx ? sol_re_partial_bytes(c) : 0);
-    SOL_REQUIRE(workspace_bytes >= need, "%s: workspace too small (%zu < %zu bytes)", who, workspace_bytes, need);
+    const BwdLayout l = bwd_layout(c, direct, rx != nullptr, workspace, direct ? direct_header_host : nullptr);
+    SOL_REQUIRE(workspace_bytes >= l.bytes, "%s: workspace too small (%zu < %zu bytes)", who, workspace_bytes, l.bytes);
     const void* outs[] = {g_vy_in, g_vx_in, cg_info, rx ? rx->g_re : nullptr, bx ? bx->g_dsum : nullptr};
     const void* ins[] = {saved_vy, saved_vx, re, active, velBCyMask, g_vy_out, g_vx_out, box_blob, rx ? rx->vy_in : nullptr, rx ? rx->vx_in : nullptr,
                          bx ? bx->g_d_out : nullptr};
@@ -384,7 +319,6 @@ int bwd_large(const char* who, const sol_karman_cfg* c, void* stream,
     const int B = c->B, Y = c->Y, X = c->X, N = Y * X;
     const size_t nVy = (size_t)(Y + 1) * X, nVx = (size_t)Y * (X + 1), faces = nVy + nVx;
     hipStream_t s = (hipStream_t)stream;
-    const BwdLayout l = bwd_layout(c, direct, workspace, direct ? direct_header_host : nullptr);
     LBArgs a{};
     a.B = B; a.Y = Y; a.X = X; a.dtdx = c->dt / c->dx; a.adt = c->dt * c->res * c->res; a.grad_pad = c->grad_pad;
     a.re = re; a.active = active; a.bcm = velBCyMask; a.bc_stride = bc_batch_stride;
@@ -413,13 +347,12 @@ int bwd_large(const char* who, const sol_karman_cfg* c, void* stream,
     if (bx)
         if (int e = sol_buoyancy_adj(s, B, Y, X, active, a.gay, a.gax, a.gmax, c->dt * bx->fy, c->dt * bx->fx, bx->g_d_out, bx->g_dsum)) return e;
     if (!rx) return SOL_OK;
-    // g' of the Reynolds-number gradient = the fixed-point g_c that k_lb_diffuse_adj has just read (. (1 - bcm) on v_y); the partial sums
-    // lie behind the plain adjoint's part of the workspace
+    // g' of the Reynolds-number gradient = the fixed-point g_c that k_lb_diffuse_adj has just read (. (1 - bcm) on v_y)
     ReIn in{};
     in.src = RE_FIXED;
     in.gcy = a.gcy; in.gcx = a.gcx; in.gmax = a.gmax; in.bcm = velBCyMask; in.bc_stride = bc_batch_stride;
     in.vy_in = rx->vy_in; in.vx_in = rx->vx_in; in.re = re;
-    in.partial = reinterpret_cast<double*>(reinterpret_cast<char*>(l.gc) + (plain - 256));
+    in.partial = l.partial;
     in.g_re = rx->g_re; in.accumulate = rx->accumulate;
     return sol_re_reduce(s, c, in);
 }
@@ -438,8 +371,8 @@ extern "C" int sol_karman_step_bwd_large(const sol_karman_cfg* c, void* stream,
 }
 
 extern "C" size_t sol_karman_step_bwd_large_re_workspace_bytes_for(const sol_karman_cfg* c, const int32_t* direct_header_host) {
-    const size_t plain = sol_karman_step_bwd_large_workspace_bytes_for(c, direct_header_host);
-    return plain ? plain + sol_re_partial_bytes(c) : 0;
+    if (!c || c->B < 1 || c->Y < 1 || c->X < 1) return 0;
+    return bwd_layout(c, c->direct != nullptr, true, nullptr, direct_header_host).bytes;
 }
 
 extern "C" int sol_karman_step_bwd_large_re(const sol_karman_cfg* c, void* stream,

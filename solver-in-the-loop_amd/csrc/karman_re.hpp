@@ -32,7 +32,7 @@ struct ReIn {
     const float *bcm;                    // velBCyMask
     long bc_stride;
     const float *vy_in, *vx_in, *re;     // the step's INPUT velocity and Reynolds numbers
-    double* partial;                     // [B][re_nblk(faces)] scratch, sol_re_partial_bytes
+    double* partial;                     // [B][re_nblk(faces)] scratch, sol_re_partial_take
     float* g_re;                         // [B]
     int accumulate;                      // 1: one fp32 add onto g_re
 };
@@ -44,7 +44,7 @@ struct ReExtra {
     int accumulate;
 };
 
-// bytes of the partial sums for cfg's grid and batch (256-byte granule)
-size_t sol_re_partial_bytes(const sol_karman_cfg* c);
+// the partial sums for cfg's grid and batch as the optional last member of an adjoint's layout (carve.hpp)
+double* sol_re_partial_take(Carve& w, const sol_karman_cfg* c);
 // the two launches (k_re_partial, k_re_final) on stream s: no synchronisation, no allocation, nothing read on the host
 int sol_re_reduce(hipStream_t s, const sol_karman_cfg* c, const ReIn& in);

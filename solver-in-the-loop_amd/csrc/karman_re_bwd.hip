@@ -63,7 +63,7 @@ size_t faces_of(const sol_karman_cfg* c) { return (size_t)(c->Y + 1) * c->X + (s
 
 }  // namespace
 
-size_t sol_re_partial_bytes(const sol_karman_cfg* c) { return align_up((size_t)c->B * re_nblk(faces_of(c)) * sizeof(double), 256); }
+double* sol_re_partial_take(Carve& w, const sol_karman_cfg* c) { return w.take<double>((size_t)c->B * re_nblk(faces_of(c))); }
 
 int sol_re_reduce(hipStream_t s, const sol_karman_cfg* c, const ReIn& in) {
     ReArgs a{};

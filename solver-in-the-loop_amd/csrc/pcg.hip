@@ -29,6 +29,8 @@
 // back to the host every poll_every iterations and stops issuing iterations once all B simulations are done -- data generation runs
 // thousands of eager steps with the PhiFlow budget of 2000.  The results do not depend on where it stops: a finished simulation's state
 // is frozen either way.  The 3-D user passes 0 and always issues the full budget.
+//
+// Also here, next to sol_large_step: large_fwd, the one host path of the large-grid 2-D forward step for both solvers (six entry points).
 #include "common.hpp"
 
 namespace {
@@ -240,15 +242,6 @@ __global__ void __launch_bounds__(PCG_T) pcg_dot(PcgArgs a, const float* __restr
     pcg_publish(rz, a.nwg, acc);
 }
 
-// bump allocator over a caller's workspace (ws == NULL: sizes only); every buffer starts on 256 bytes
-struct Carve {
-    char* w;
-    size_t off = 0;
-    explicit Carve(void* ws) : w(ws ? reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(ws) + 255) / 256 * 256) : nullptr) {}
-    template <class T> T* take(size_t n) { T* p = w ? reinterpret_cast<T*>(w + off) : nullptr; off += (n * sizeof(T) + 255) / 256 * 256; return p; }
-    size_t bytes() const { return off + 256; }     // + the alignment of the caller's pointer
-};
-
 // the CG buffers: slabs, done words, x, the two p buffers, q (the caller sets r, active, info and the tolerances)
 PcgArgs pcg_carve(Carve& w, size_t B, size_t N) {
     PcgArgs a{};
@@ -372,15 +365,6 @@ int sol_large_cg_check(const sol_karman_cfg* c, const char* who, const float* bo
 
 namespace {
 
-// checks shared by the two entry points (before any launch)
-int large_check(const sol_karman_cfg* c, const char* who, const float* box_blob, const int32_t* hdr, const int32_t* cg_info,
-                const void* workspace, size_t workspace_bytes) {
-    if (int e = sol_large_cg_check(c, who, box_blob, hdr, cg_info, workspace)) return e;
-    SOL_REQUIRE(workspace_bytes >= large_layout(c, nullptr).bytes, "%s: workspace too small (%zu < %zu bytes)", who, workspace_bytes,
-                large_layout(c, nullptr).bytes);
-    return SOL_OK;
-}
-
 // M x = b by PCG; b (= l.a.r) is overwritten with the residual
 int large_solve(hipStream_t s, const sol_karman_cfg* c, const float* blob, const float* active, const Large& l, int32_t* info,
                 const float* x0 = nullptr) {
@@ -406,7 +390,7 @@ __global__ void __launch_bounds__(PCG_T) large_copy(float* __restrict__ dst, con
 // direct: the capacitance solve on cfg.direct (hdr = its host header); else PCG with the empty-box solve of box_blob as preconditioner,
 // reporting to cg_info [2][B].  The caller writes b into sol_large_solver_rhs(...) (overwritten); *x = the buffer that holds the solution.
 size_t sol_large_solver_bytes(const sol_karman_cfg* c, bool direct, const int32_t* hdr) {
-    return direct ? sol_large_direct_floats(c, hdr) * sizeof(float) + 256 : large_layout(c, nullptr, false).bytes;
+    return direct ? sol_large_direct_bytes(c, hdr) + 256 : large_layout(c, nullptr, false).bytes;
 }
 
 float* sol_large_solver_rhs(const sol_karman_cfg* c, bool direct, void* ws) {
@@ -461,38 +445,101 @@ int k3_pcg_solve(hipStream_t s, const sol_karman3d_cfg* c, const float* active, 
     return SOL_OK;
 }
 
-extern "C" size_t sol_karman_step_large_cg_workspace_bytes(const sol_karman_cfg* c) {
-    if (!c || c->B < 1 || c->Y < 1 || c->X < 1) return 0;
-    return large_layout(c, nullptr).bytes;
-}
-
+// ---- karman-2d large grids: the forward step, ONE host path behind the six entry points ----
 namespace {
 
-// sol_karman_step_fwd_large_cg and its warm-started form (p_inout: NULL, or the guess in / the step's pressure out)
-int large_cg_step(const char* who, const sol_karman_cfg* c, void* stream, const SolLargeStep& io, const float* box_blob,
-                  const int32_t* box_header_host, int32_t* cg_info, float* p_inout, void* workspace, size_t workspace_bytes) {
-    if (int e = large_check(c, who, box_blob, box_header_host, cg_info, workspace, workspace_bytes)) return e;
-    SOL_REQUIRE(io.vy_in && io.vx_in && io.re && io.active && io.velBCy && io.velBCyMask && io.vy_out && io.vx_out, "%s: NULL pointer argument", who);
+// the step's workspace: sv_y, sv_x (with_sv; else the caller keeps them), then the solver's part
+struct FwdLayout { float *svy, *svx; void* solver; size_t bytes; };
+FwdLayout fwd_layout(const sol_karman_cfg* c, bool direct, const int32_t* hdr, bool with_sv, void* ws) {
+    FwdLayout l{};
+    if (!with_sv) {             // the solver's part alone, from the next 256 bytes
+        Carve w(ws, 1, 256);
+        l.solver = w.take<char>(sol_large_solver_bytes(c, direct, direct ? hdr : nullptr));
+        l.bytes = w.bytes();
+    } else if (direct) {        // float-dense from the caller's pointer, 256 floats of slack behind
+        const size_t B = c->B, Y = c->Y, X = c->X;
+        Carve w = Carve::packed(ws);
+        l.svy = w.take<float>(B * (Y + 1) * X);
+        l.svx = w.take<float>(B * Y * (X + 1));
+        l.solver = w.take<char>(sol_large_direct_bytes(c, hdr));
+        w.take<float>(256);
+        l.bytes = w.bytes();
+    } else {                    // 256-byte granules; the solver's part starts at the rhs buffer
+        const Large g = large_layout(c, ws);
+        l.svy = g.svy; l.svx = g.svx; l.solver = g.a.r; l.bytes = g.bytes;
+    }
+    return l;
+}
+
+// which solve, and what it reads: direct = the capacitance solve on cfg.direct with its host header, else the preconditioned CG with the
+// empty-box blob, its host header and the report cg_info [2][B]; p_inout (CG only): NULL, or the initial guess in / the step's pressure out
+struct LargeSolver { bool direct; const int32_t* direct_header_host; const float* box_blob; const int32_t* box_header_host; int32_t* cg_info; float* p_inout; };
+// the training forms: where the post-diffusion velocity goes for the adjoint (without: into the workspace)
+struct LargeSaved { float *vy, *vx; };
+
+int large_fwd(const char* who, const sol_karman_cfg* c, void* stream, SolLargeStep io, const LargeSolver& sv, const LargeSaved* keep,
+              void* workspace, size_t workspace_bytes, float fy = 0.f, float fx = 0.f) {
+    const LargeSaved saved = keep ? *keep : LargeSaved{};
+    SOL_REQUIRE(c != nullptr, "%s: cfg is NULL", who);
+    SOL_REQUIRE(c->B >= 1 && c->B <= 65535 && c->Y >= 16 && c->X >= 16, "%s: B in [1, 65535], Y, X >= 16 (got %d, %d, %d)", who, c->B, c->Y, c->X);
+    SOL_REQUIRE((size_t)c->Y * c->X < ((size_t)1 << 30), "%s: grid too large", who);
+    SOL_REQUIRE(!saved.vy || (size_t)c->Y * c->X < ((size_t)1 << 28), "%s: grid too large for 32-bit face indices", who);
+    SOL_REQUIRE(io.vy_in && io.vx_in && io.re && io.active && io.velBCy && io.velBCyMask && io.vy_out && io.vx_out && workspace &&
+                    (!keep || (saved.vy && saved.vx)), "%s: NULL pointer argument", who);
     SOL_REQUIRE((io.d_in && io.inflow) || !io.d_out, "%s: density output requested without d_in / inflow", who);
     SOL_REQUIRE(!io.feat_out || io.feat_scale, "%s: feat_out requires feat_scale", who);
-    SOL_REQUIRE(io.vy_in != io.vy_out && io.vx_in != io.vx_out && (io.d_in != io.d_out || !io.d_out), "%s: outputs must not alias the inputs", who);
-    const void* outs[] = {io.d_out, io.vy_out, io.vx_out, io.feat_out, cg_info, p_inout};
-    const void* ins[] = {io.d_in, io.vy_in, io.vx_in, io.re, io.active, io.inflow, io.velBCy, io.velBCyMask, box_blob};
+    SOL_REQUIRE(fy - fy == 0.f && fx - fx == 0.f, "%s: the force must be finite (got %g, %g)", who, (double)fy, (double)fx);
+    SOL_REQUIRE((fy == 0.f && fx == 0.f) || (io.d_in && io.inflow && io.d_out), "%s: a non-zero force needs d_in, inflow and d_out", who);
+    io.buoy_y = c->dt * fy; io.buoy_x = c->dt * fx;
+    SOL_REQUIRE(!sv.direct || !sv.p_inout, "%s: p_inout warm-starts the CG solve; this cfg selects the direct solve", who);
+    if (sv.direct) { if (int e = sol_large_direct_check(c, who, sv.direct_header_host)) return e; }
+    else if (int e = sol_large_cg_check(c, who, sv.box_blob, sv.box_header_host, sv.cg_info, workspace)) return e;
+    const FwdLayout l = fwd_layout(c, sv.direct, sv.direct_header_host, !saved.vy, workspace);
+    SOL_REQUIRE(workspace_bytes >= l.bytes, "%s: workspace too small (%zu < %zu bytes)", who, workspace_bytes, l.bytes);
+    const void* outs[] = {io.d_out, io.vy_out, io.vx_out, io.feat_out, saved.vy, saved.vx, sv.cg_info, sv.p_inout};
+    const void* ins[] = {io.d_in, io.vy_in, io.vx_in, io.re, io.active, io.inflow, io.velBCy, io.velBCyMask, sv.box_blob};
     for (const void* o : outs)
         for (const void* i : ins) SOL_REQUIRE(!o || o != i, "%s: outputs must not alias the inputs", who);
+    // (kept from the direct step that carves its own sv: it never took a call without any density pointer)
+    SOL_REQUIRE(!sv.direct || saved.vy || io.d_in || io.d_out, "%s: outputs must not alias the inputs (d_in and d_out are both NULL)", who);
+    SOL_REQUIRE(!saved.vy || (saved.vy != io.vy_out && saved.vx != io.vx_out && saved.vy != saved.vx), "%s: saved_vy / saved_vx must be buffers of their own", who);
     hipStream_t s = (hipStream_t)stream;
-    const Large l = large_layout(c, workspace);
-    if (int e = sol_large_step(c, s, io, l.svy, l.svx, false, nullptr, box_blob, cg_info, l.a.r, p_inout)) return e;
-    if (p_inout) {
+    if (int e = sol_large_step(c, s, io, saved.vy ? saved.vy : l.svy, saved.vx ? saved.vx : l.svx, sv.direct, sv.direct_header_host, sv.box_blob,
+                               sv.cg_info, l.solver, sv.p_inout)) return e;
+    if (sv.p_inout) {
         const size_t n = (size_t)c->B * c->Y * c->X;
         const size_t nb = (n + PCG_T - 1) / PCG_T;
-        SOL_LAUNCH(large_copy, dim3((unsigned)(nb < 4096 ? nb : 4096)), dim3(PCG_T), 0, s, p_inout, (const float*)l.a.x, n);
+        SOL_LAUNCH(large_copy, dim3((unsigned)(nb < 4096 ? nb : 4096)), dim3(PCG_T), 0, s, sv.p_inout, (const float*)large_layout(c, l.solver, false).a.x, n);
         SOL_LAUNCH_CHECK();
     }
     return SOL_OK;
 }
 
 }  // namespace
+
+extern "C" size_t sol_karman_step_large_workspace_bytes_for(const sol_karman_cfg* c, const int32_t* direct_header_host) {
+    if (!c) return 0;
+    return fwd_layout(c, true, direct_header_host, true, nullptr).bytes;
+}
+
+extern "C" size_t sol_karman_step_large_workspace_bytes(const sol_karman_cfg* c) { return sol_karman_step_large_workspace_bytes_for(c, nullptr); }
+
+extern "C" size_t sol_karman_step_large_cg_workspace_bytes(const sol_karman_cfg* c) {
+    if (!c || c->B < 1 || c->Y < 1 || c->X < 1) return 0;
+    return fwd_layout(c, false, nullptr, true, nullptr).bytes;
+}
+
+extern "C" int sol_karman_step_fwd_large(const sol_karman_cfg* c, void* stream,
+                                         const float* d_in, const float* vy_in, const float* vx_in,
+                                         const float* re, const float* active, const float* inflow,
+                                         const float* velBCy, const float* velBCyMask, int64_t bc_batch_stride,
+                                         float* d_out, float* vy_out, float* vx_out,
+                                         float* feat_out, const float* feat_scale,
+                                         const int32_t* direct_header_host,
+                                         void* workspace, size_t workspace_bytes) {
+    const SolLargeStep io{d_in, vy_in, vx_in, re, active, inflow, velBCy, velBCyMask, bc_batch_stride, d_out, vy_out, vx_out, feat_out, feat_scale};
+    return large_fwd("sol_karman_step_fwd_large", c, stream, io, {true, direct_header_host}, nullptr, workspace, workspace_bytes);
+}
 
 extern "C" int sol_karman_step_fwd_large_cg(const sol_karman_cfg* c, void* stream,
                                             const float* d_in, const float* vy_in, const float* vx_in,
@@ -503,7 +550,7 @@ extern "C" int sol_karman_step_fwd_large_cg(const sol_karman_cfg* c, void* strea
                                             const float* box_blob, const int32_t* box_header_host, int32_t* cg_info,
                                             void* workspace, size_t workspace_bytes) {
     const SolLargeStep io{d_in, vy_in, vx_in, re, active, inflow, velBCy, velBCyMask, bc_batch_stride, d_out, vy_out, vx_out, feat_out, feat_scale};
-    return large_cg_step("sol_karman_step_fwd_large_cg", c, stream, io, box_blob, box_header_host, cg_info, nullptr, workspace, workspace_bytes);
+    return large_fwd("sol_karman_step_fwd_large_cg", c, stream, io, {false, nullptr, box_blob, box_header_host, cg_info}, nullptr, workspace, workspace_bytes);
 }
 
 extern "C" int sol_karman_step_fwd_large_cg_warm(const sol_karman_cfg* c, void* stream,
@@ -517,7 +564,7 @@ extern "C" int sol_karman_step_fwd_large_cg_warm(const sol_karman_cfg* c, void* 
     const char* who = "sol_karman_step_fwd_large_cg_warm";
     SOL_REQUIRE(p_inout != nullptr, "%s: NULL pointer argument (p_inout: the initial guess in, the step's pressure out)", who);
     const SolLargeStep io{d_in, vy_in, vx_in, re, active, inflow, velBCy, velBCyMask, bc_batch_stride, d_out, vy_out, vx_out, feat_out, feat_scale};
-    return large_cg_step(who, c, stream, io, box_blob, box_header_host, cg_info, p_inout, workspace, workspace_bytes);
+    return large_fwd(who, c, stream, io, {false, nullptr, box_blob, box_header_host, cg_info, p_inout}, nullptr, workspace, workspace_bytes);
 }
 
 // The no-grad step with the buoyancy force F = (fy, fx) (karman_buoyancy.hip), for either solver as the cfg selects it: cfg.direct set =
@@ -532,29 +579,52 @@ extern "C" int sol_karman_step_fwd_large_buoy(const sol_karman_cfg* c, void* str
                                               const int32_t* direct_header_host,
                                               const float* box_blob, const int32_t* box_header_host, int32_t* cg_info,
                                               float* p_inout, void* workspace, size_t workspace_bytes, float fy, float fx) {
-    const char* who = "sol_karman_step_fwd_large_buoy";
-    SOL_REQUIRE(c != nullptr, "%s: cfg is NULL", who);
-    SOL_REQUIRE(fy - fy == 0.f && fx - fx == 0.f, "%s: the force must be finite (got %g, %g)", who, (double)fy, (double)fx);
-    SOL_REQUIRE((fy == 0.f && fx == 0.f) || (d_in && inflow && d_out), "%s: a non-zero force needs d_in, inflow and d_out", who);
-    SolLargeStep io{d_in, vy_in, vx_in, re, active, inflow, velBCy, velBCyMask, bc_batch_stride, d_out, vy_out, vx_out, feat_out, feat_scale};
-    io.buoy_y = c->dt * fy; io.buoy_x = c->dt * fx;
-    if (c->direct) {
-        SOL_REQUIRE(!p_inout, "%s: p_inout warm-starts the CG solve; this cfg selects the direct solve", who);
-        return sol_large_direct_step(who, c, stream, io, direct_header_host, workspace, workspace_bytes);
-    }
-    return large_cg_step(who, c, stream, io, box_blob, box_header_host, cg_info, p_inout, workspace, workspace_bytes);
+    const SolLargeStep io{d_in, vy_in, vx_in, re, active, inflow, velBCy, velBCyMask, bc_batch_stride, d_out, vy_out, vx_out, feat_out, feat_scale};
+    return large_fwd("sol_karman_step_fwd_large_buoy", c, stream, io, {c && c->direct, direct_header_host, box_blob, box_header_host, cg_info, p_inout},
+                     nullptr, workspace, workspace_bytes, fy, fx);
+}
+
+// The training forms (the adjoint is sol_karman_step_bwd_large*, karman_large_bwd.hip): the post-diffusion velocity goes to the caller's
+// saved_vy / saved_vx, the workspace holds the solver's part alone; no features
+extern "C" int sol_karman_step_fwd_large_saved(const sol_karman_cfg* c, void* stream,
+                                               const float* d_in, const float* vy_in, const float* vx_in,
+                                               const float* re, const float* active, const float* inflow,
+                                               const float* velBCy, const float* velBCyMask, int64_t bc_batch_stride,
+                                               float* d_out, float* vy_out, float* vx_out, float* saved_vy, float* saved_vx,
+                                               const int32_t* direct_header_host,
+                                               const float* box_blob, const int32_t* box_header_host, int32_t* cg_info,
+                                               void* workspace, size_t workspace_bytes) {
+    const SolLargeStep io{d_in, vy_in, vx_in, re, active, inflow, velBCy, velBCyMask, bc_batch_stride, d_out, vy_out, vx_out, nullptr, nullptr};
+    const LargeSaved keep{saved_vy, saved_vx};
+    return large_fwd("sol_karman_step_fwd_large_saved", c, stream, io, {c && c->direct, direct_header_host, box_blob, box_header_host, cg_info}, &keep,
+                     workspace, workspace_bytes);
+}
+
+extern "C" int sol_karman_step_fwd_large_saved_buoy(const sol_karman_cfg* c, void* stream,
+                                                    const float* d_in, const float* vy_in, const float* vx_in,
+                                                    const float* re, const float* active, const float* inflow,
+                                                    const float* velBCy, const float* velBCyMask, int64_t bc_batch_stride,
+                                                    float* d_out, float* vy_out, float* vx_out, float* saved_vy, float* saved_vx,
+                                                    const int32_t* direct_header_host,
+                                                    const float* box_blob, const int32_t* box_header_host, int32_t* cg_info,
+                                                    void* workspace, size_t workspace_bytes, float fy, float fx) {
+    const SolLargeStep io{d_in, vy_in, vx_in, re, active, inflow, velBCy, velBCyMask, bc_batch_stride, d_out, vy_out, vx_out, nullptr, nullptr};
+    const LargeSaved keep{saved_vy, saved_vx};
+    return large_fwd("sol_karman_step_fwd_large_saved_buoy", c, stream, io, {c && c->direct, direct_header_host, box_blob, box_header_host, cg_info}, &keep,
+                     workspace, workspace_bytes, fy, fx);
 }
 
 extern "C" int sol_karman_pressure_solve_large(const sol_karman_cfg* c, void* stream, const float* active, const float* rhs, float* p,
                                                const float* box_blob, const int32_t* box_header_host, int32_t* cg_info,
                                                void* workspace, size_t workspace_bytes) {
     const char* who = "sol_karman_pressure_solve_large";
-    if (int e = large_check(c, who, box_blob, box_header_host, cg_info, workspace, workspace_bytes)) return e;
+    if (int e = sol_large_cg_check(c, who, box_blob, box_header_host, cg_info, workspace)) return e;
+    const Large l = large_layout(c, workspace);
+    SOL_REQUIRE(workspace_bytes >= l.bytes, "%s: workspace too small (%zu < %zu bytes)", who, workspace_bytes, l.bytes);
     SOL_REQUIRE(active && rhs && p, "%s: NULL pointer argument", who);
     SOL_REQUIRE(p != rhs && p != active && p != box_blob && (const void*)cg_info != rhs && (const void*)cg_info != active,
                 "%s: outputs must not alias the inputs", who);
     hipStream_t s = (hipStream_t)stream;
-    const Large l = large_layout(c, workspace);
     const size_t n = (size_t)c->B * c->Y * c->X;
     const size_t nb = (n + PCG_T - 1) / PCG_T;
     const unsigned g = (unsigned)(nb < 4096 ? nb : 4096);

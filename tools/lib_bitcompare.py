@@ -2,8 +2,9 @@
 """Does a library variant (tools/ab_lib.py --build NAME ...) compute the SAME BITS as the product library?  Two karman-2d training steps
 (loss, gradient, final state), the CG pressure solves (the 2-D large step eager and replayed, its solve alone, the 3-D step and its
 adjoint: fields and cg_info) and the adjoints' fixed-point scatter with the LDS window and with global atomics only (the 2-D large-grid
-adjoint, direct on the default sphere and CG on two cylinders, B = 2; the 3-D direct-solve adjoint at 128 x 64 x 64, B = 1) per library
-in fresh processes (SOL_HIP_LIB), SHA-1 of every result, one verdict per leg.
+adjoint, direct on the default sphere and CG on two cylinders, B = 2; the 3-D direct-solve adjoint at 128 x 64 x 64, B = 1) and every
+host path that sizes and carves a workspace at the smallest shapes of the GPU tests (the large-grid 2-D step through its six forward entry
+points and its adjoints with each solver, the Burgers large step and adjoint, the 3-D density and Re adjoints) per library in fresh processes (SOL_HIP_LIB), SHA-1 of every result, one verdict per leg.
     python tools/lib_bitcompare.py NAME [NAME2 ...]        (on the GPU box)"""
 import hashlib
 import json
@@ -117,6 +118,63 @@ if "--child" in sys.argv:
         outs = sim.step(st3[0], *v, re3)
         return [sha(t) for t in torch.autograd.grad(outs[1:], v, w3)]
     out["adj3d_direct_128x64x64"] = tiled("k3d_adj_tile", run3d)
+
+    # every host path that sizes and carves a workspace (csrc/carve.hpp), at the smallest shapes of the GPU tests (tests/buoyancy_cases.py,
+    # tests/karman3d_adjoint_cases.py, test_gpu_burgers_large_adjoint.py): the six forward entry points of the large-grid 2-D step with
+    # each solver, the velocity, density and Re adjoints, the Burgers large step and adjoint, the 3-D density and Re adjoints
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import buoyancy_cases as bc
+    import karman3d_adjoint_cases as kc
+    from large2d_scenes import CG_RTOL, f32, masks
+    shas = lambda ts: [sha(t) for t in ts]
+    force = bc.FORCES[1]
+    for name, solver in (("sphere_130", "direct"), ("two_144", "cg"), ("two_144", "direct_scattered")):
+        Y, X, _, order, _ = bc.SCENES[name]
+        g = bc.geometry_of(name)
+        mk = masks(g, solver)
+        cfg = ops.karman_cfg(bc.B, Y, X, g.dx, masks=mk, cg_rtol=CG_RTOL, inflow_order=order)
+        d, vy, vx, re = (f32(t) for t in bc.start_state(name))
+        wd, wy, wx = (f32(t) for t in bc.cotangents(name, "both"))
+        leg, info = {}, {}
+        with torch.no_grad():
+            feat = torch.zeros(bc.B, Y, X, 4, dtype=torch.float32, device=dev)
+            leg["step"] = shas(ops.karman_step_large(d, vy, vx, re, cfg, mk, info=info, feat=feat, feat_scale=(5.0, 4.0, 1e-5)) + (feat,))
+            leg["step_buoy"] = shas(ops.karman_step_large(d, vy, vx, re, cfg, mk, feat=feat, feat_scale=(5.0, 4.0, 1e-5), buoyancy=force) + (feat,))
+            if solver == "cg":
+                guess = torch.zeros(bc.B, Y, X, dtype=torch.float32, device=dev)
+                for k in range(2):          # cold guess, then the first call's pressure as the guess
+                    leg["step_warm%d" % k] = shas(ops.karman_step_large(d, vy, vx, re, cfg, mk, info=info, p_guess=guess) + (guess,)) + [info["iterations"].tolist()]
+            st, svy, svx = ops.karman_step_saved(d, vy, vx, re, cfg, mk)
+            leg["saved"] = shas(st + (svy, svx))
+            sb, sby, sbx = ops.karman_step_saved(d, vy, vx, re, cfg, mk, buoyancy=force)
+            leg["saved_buoy"] = shas(sb + (sby, sbx))
+        leg["bwd"] = shas(ops.karman_step_large_bwd(svy, svx, re, wy, wx, cfg, mk))
+        leg["bwd_re"] = shas(ops.karman_step_large_bwd_re(svy, svx, re, wy, wx, vy, vx, cfg, mk))
+        leg["density_bwd"] = shas(ops.karman_density_bwd(d, svy, svx, re, wd, cfg, mk))
+        leg["density_bwd_re"] = shas(ops.karman_density_bwd_re(d, svy, svx, re, wd, vy, vx, cfg, mk))
+        leg["bwd_buoy"] = shas(ops.karman_step_large_bwd_buoy(d, sby, sbx, re, wy, wx, wd, cfg, mk, force))
+        leg["bwd_buoy_re"] = shas(ops.karman_step_large_bwd_buoy(d, sby, sbx, re, wy, wx, wd, cfg, mk, force, vel_in=(vy, vx)))
+        out["large2d_%s_%s" % (name, solver)] = leg
+
+    for Y, X in ((70, 36), (24, 100)):
+        gen = torch.Generator().manual_seed(3)
+        rn = lambda *s: torch.randn(*s, generator=gen).to(dev)
+        vy, vx, fy, fx, wy, wx = (a * rn(2, Y + 1, X) if k % 2 == 0 else a * rn(2, Y, X + 1) for k, a in enumerate((0.3, 0.3, 0.2, 0.2, 1.0, 1.0)))
+        cfg, circ = sol_amd._lib.BurgersCfg(2, Y, X, 32.0 / Y, 0.1), ops.burgers_circ(Y, X, 0.01)
+        with torch.no_grad():
+            fwd = ops.burgers_step_large(vy, vx, fy, fx, cfg, circ)
+        out["burgers_large_%dx%d" % (Y, X)] = shas(fwd + tuple(ops.burgers_step_large_bwd(vy, vx, wy, wx, cfg, circ)))
+
+    for name, solver in (("16_comb", "direct"), ("16_comb", "cg"), ("20_comb", "direct")):
+        c = kc.case(name)
+        _, Y, X, Z = c["shape"]
+        sim = karman3d.Karman3DFlow(karman3d.Scene3D(Y, X, Z, device=dev, pressure_solver=solver), c["shape"][0], dt=c["dt"],
+                                    density_grad=True, re_grad=True, **c["kw"])
+        d, v, re = kc.state(name)
+        hs = [f32(t).requires_grad_(True) for t in (d, *v, re)]
+        outs = sim.step(*hs)
+        ((outs[0] * f32(kc.w_dens(name))).sum() + sum((a * f32(w)).sum() for a, w in zip(outs[1:], kc.w_vel(name)))).backward()
+        out["adj3d_density_re_%s_%s" % (name, solver)] = shas(list(outs) + [h.grad for h in hs])
     print(json.dumps(out))
     sys.exit(0)
 names = ["product"] + [a for a in sys.argv[1:] if not a.startswith("--")]
