@@ -792,6 +792,62 @@ int sol_karman3d_density_bwd_re(const sol_karman3d_cfg* cfg, void* stream,
                                 const float* g_d_out, float* g_d_in, float* g_vy_in, float* g_vx_in, float* g_vz_in, int accumulate,
                                 void* workspace, size_t workspace_bytes,
                                 const float* vy_in, const float* vx_in, const float* vz_in, float* g_re, int accumulate_re);
+/* BUOYANCY on the karman-3d step (csrc/karman3d_buoyancy.hip): the definition of "BUOYANCY on the large-grid step" above with a third axis.
+ * F = (fy, fx, fz) is a force per unit density (PhiFlow's -gravity * buoyancy_factor with Gravity() = -9.81 along y gives
+ * F = (9.81 beta, 0, 0)); it travels as three floats, sol_karman3d_cfg is unchanged.  With c the post-diffusion velocity, one step is
+ *     d_out = SL(d_in [+ inflow], c) [+ inflow dt]                                                                  (unchanged)
+ *     a_y[jf,i,k] = mask_y * ( SL_y(c) + dt F_y * (dz(jf-1,i,k) + dz(jf,i,k)) / 2 )   jf = 0..Y     (a_x, a_z likewise along their axis)
+ *     dz = d_out inside the grid, 0 outside (the zero ghost ring the density's advection uses)
+ *     v_out = a - mask * grad( solve(div a) )                                                                       (unchanged)
+ * The force acts on the step's OUTPUT density, the inflow already in it (advect, effects, buoyancy, projection: PhiFlow 1.5.1's order as
+ * recalled, unpinned -- DESIGN.md sections 4.7 and 4.8).  fp32 spelling of a face: fl(v + fl(fl(dt*F) * fl(0.5f * (d0 + d1)))) * mask, no
+ * contraction; fl(dt*F) is formed on the host.  A component whose force is zero is not touched; F = (0, 0, 0) issues the plain call's
+ * launches and gives its bits.  One extra streaming launch (k3_buoyancy) between the advection and the divergence, for the direct and the
+ * CG solve, both advection kernels and both inflow orders alike.
+ *   sol_karman3d_step_fwd_buoy: every argument of sol_karman3d_step_fwd, then fy, fx, fz.  A non-zero force needs d_in, inflow and d_out;
+ *     saved_* (training) and feat_out (roll-out) as in the plain call; same workspace.
+ * Adjoint.  With g_a the cotangent of a that the velocity adjoint forms (k3b_gva; it carries the face mask),
+ *     g_dsum[j,i,k] = g_d_out[j,i,k] + dt F_y (g_ay[j,i,k] + g_ay[j+1,i,k]) / 2 + dt F_x (g_ax[j,i,k] + g_ax[j,i+1,k]) / 2
+ *                                    + dt F_z (g_az[j,i,k] + g_az[j,i,k+1]) / 2
+ * and then the two existing adjoints, unchanged: the velocity adjoint's scatter and diffusion adjoint on g_a, the density adjoint on g_dsum.
+ *   sol_karman3d_step_bwd_buoy / _buoy_re: every argument of sol_karman3d_step_bwd / _re, then fy, fx, fz, g_d_out [B,Y,X,Z] (the cotangent
+ *     of the step's output density; NULL = zero) and g_dsum [B,Y,X,Z] (written).  They issue the plain call's launches (g_v*_in, g_re are the
+ *     plain call's bits) and one more (k3b_buoyancy_adj: a gather, no atomics, fixed order, bit-reproducible); same workspace as the plain
+ *     call.  The caller then runs sol_karman3d_density_bwd(_re) with g_dsum as its g_d_out and accumulate = 1.  A non-finite g_a of a
+ *     simulation makes ALL of that simulation's g_dsum NaN, so the density adjoint poisons g_d_in and, through the accumulation, every other
+ *     gradient of the simulation.  g_dsum must not alias another argument.
+ *   sol_karman3d_buoyancy_add / _add_bwd: the term alone and its exact transpose, any Y, X, Z >= 1, for tests and callers that compose by
+ *     hand: vy, vx, vz (in place) = (v + f * face average of d) * mask with f = (fy_dt, fx_dt, fz_dt) = dt F;  g_dsum = g_d_out (NULL =
+ *     zero) + the transpose applied to (mask g_vy, mask g_vx, mask g_vz).
+ * None of these synchronises, allocates or reads anything on the host: capturable. */
+int sol_karman3d_step_fwd_buoy(const sol_karman3d_cfg* cfg, void* stream,
+                               const float* d_in, const float* vy_in, const float* vx_in, const float* vz_in,
+                               const float* re, const float* active, const float* inflow,
+                               const float* velBCy, const float* velBCyMask, int64_t bc_batch_stride,
+                               float* d_out, float* vy_out, float* vx_out, float* vz_out,
+                               float* saved_vy, float* saved_vx, float* saved_vz,
+                               float* feat_out, const float* feat_scale, const int32_t* direct_header_host,
+                               void* workspace, size_t workspace_bytes, float fy, float fx, float fz);
+int sol_karman3d_step_bwd_buoy(const sol_karman3d_cfg* cfg, void* stream,
+                               const float* saved_vy, const float* saved_vx, const float* saved_vz,
+                               const float* re, const float* active, const float* velBCyMask, int64_t bc_batch_stride,
+                               const float* g_vy_out, const float* g_vx_out, const float* g_vz_out,
+                               float* g_vy_in, float* g_vx_in, float* g_vz_in,
+                               const int32_t* direct_header_host, void* workspace, size_t workspace_bytes,
+                               float fy, float fx, float fz, const float* g_d_out, float* g_dsum);
+int sol_karman3d_step_bwd_buoy_re(const sol_karman3d_cfg* cfg, void* stream,
+                                  const float* saved_vy, const float* saved_vx, const float* saved_vz,
+                                  const float* re, const float* active, const float* velBCyMask, int64_t bc_batch_stride,
+                                  const float* g_vy_out, const float* g_vx_out, const float* g_vz_out,
+                                  float* g_vy_in, float* g_vx_in, float* g_vz_in,
+                                  const int32_t* direct_header_host, void* workspace, size_t workspace_bytes,
+                                  const float* vy_in, const float* vx_in, const float* vz_in, float* g_re, int accumulate_re,
+                                  float fy, float fx, float fz, const float* g_d_out, float* g_dsum);
+int sol_karman3d_buoyancy_add(void* stream, int32_t B, int32_t Y, int32_t X, int32_t Z, const float* active, const float* d,
+                              float fy_dt, float fx_dt, float fz_dt, float* vy, float* vx, float* vz);
+int sol_karman3d_buoyancy_add_bwd(void* stream, int32_t B, int32_t Y, int32_t X, int32_t Z, const float* active,
+                                  const float* g_vy, const float* g_vx, const float* g_vz, float fy_dt, float fx_dt, float fz_dt,
+                                  const float* g_d_out, float* g_dsum);
 /* The step's pressure solve alone: M p = rhs with M = -A for the scene's `active` mask (the solver cfg->pressure_solver selects;
  * the CG solve reports to cfg->cg_info).  rhs, p [B,Y,X,Z] (rhs is read only); workspace: sol_karman3d_step_workspace_bytes(cfg). */
 int sol_karman3d_pressure_solve(const sol_karman3d_cfg* cfg, void* stream, const float* active, const float* rhs, float* p,

@@ -80,6 +80,13 @@ int k3_apply_G(hipStream_t s, const sol_karman3d_cfg* c, const float* src, float
 size_t k3_pcg_workspace_bytes(const sol_karman3d_cfg* c);
 int k3_pcg_check(const sol_karman3d_cfg* c, const int32_t* hdr);
 int k3_pcg_solve(hipStream_t s, const sol_karman3d_cfg* c, const float* active, float* b, float* t1, float* t2, void* ws, float** x_out);
+// the karman-3d buoyancy term onto the advected velocity (f = dt F; nothing is launched for f = (0, 0, 0)) and its transpose
+// (karman3d_buoyancy.hip): g_dsum = g_d_out (NULL = zero) + the face-to-cell transpose of (gy, gx, gz); gmax = the absmax slots of
+// k3b_gva or NULL (poisoning)
+int k3_buoyancy_add(hipStream_t s, int B, int Y, int X, int Z, const float* active, const float* d, float fy, float fx, float fz,
+                    float* vy, float* vx, float* vz);
+int k3_buoyancy_adj(hipStream_t s, int B, int Y, int X, int Z, const float* active, const float* gy, const float* gx, const float* gz,
+                    const unsigned* gmax, float fy, float fx, float fz, const float* g_d_out, float* g_dsum);
 
 // forward / backward-data convolution arguments (conv5x5.hip, conv5x5_sb.hip)
 struct ConvArgs {

@@ -14,6 +14,7 @@
 //                   trilinear gather and every cross-component average of the tile is served from LDS, lanes run along z
 //                   (conflict free, coalesced stores); samples that leave the halo (CFL > 1) fall back to global reads.
 //                   (k3_advect: the same arithmetic straight from global memory -- option k3d_tile = 0, and any Z > 64.)
+//   (k3_buoyancy    optional, sol_karman3d_step_fwd_buoy: the step's output density pushes the advected velocity -- karman3d_buoyancy.hip)
 //   k3_div          rhs = -div
 //   pressure        DIRECT solve x = G (b - U_S E_SS x_S), x_S = (I + G_SS E_SS)^-1 (G b)_S with G = the empty-box Dirichlet
 //                   Laplacian diagonalised by three sine transforms (batched fp32 GEMMs along z, x, y) and the capacitance
@@ -24,6 +25,7 @@
 // with respect to the Reynolds number from the g_c they leave behind (karman3d_re_bwd.hip).  The adjoint of the marker density is a set
 // of launches of its own (karman3d_density_bwd.hip).
 #include "fixed_scatter.hpp"
+#include "karman3d_mask.hpp"
 #include "karman3d_re.hpp"
 
 namespace {
@@ -76,14 +78,7 @@ __global__ void __launch_bounds__(256) k3_diffuse(K3Args a) {
     }
 }
 
-// ---- hard-BC face masks from the `active` cell mask ('boundary' extrapolation: outside the OPEN domain = edge value) ----
-__device__ __forceinline__ float acc_at(const float* act, int Y, int X, int Z, int j, int i, int k) {
-    return act[((size_t)clampi(j, 0, Y - 1) * X + clampi(i, 0, X - 1)) * Z + clampi(k, 0, Z - 1)] != 0.f ? 1.f : 0.f;
-}
-template <int AX>
-__device__ __forceinline__ float face_mask(const float* act, int Y, int X, int Z, int j, int i, int k) {
-    return acc_at(act, Y, X, Z, j - (AX == 0), i - (AX == 1), k - (AX == 2)) * acc_at(act, Y, X, Z, j, i, k);
-}
+// (hard-BC face masks from the `active` cell mask: acc_at, face_mask<AX> of karman3d_mask.hpp)
 
 // ---- readers of the diffused components: straight from global memory, or from the workgroup's LDS tile ----------------
 struct GlobalReader {
@@ -1113,25 +1108,32 @@ extern "C" size_t sol_karman3d_step_workspace_bytes(const sol_karman3d_cfg* c) {
     return k3_fwd_layout(c, nullptr).bytes;
 }
 
-extern "C" int sol_karman3d_step_fwd(const sol_karman3d_cfg* c, void* stream,
-                                     const float* d_in, const float* vy_in, const float* vx_in, const float* vz_in,
-                                     const float* re, const float* active, const float* inflow,
-                                     const float* velBCy, const float* velBCyMask, int64_t bc_batch_stride,
-                                     float* d_out, float* vy_out, float* vx_out, float* vz_out,
-                                     float* saved_vy, float* saved_vx, float* saved_vz,
-                                     float* feat_out, const float* feat_scale, const int32_t* direct_header_host,
-                                     void* workspace, size_t workspace_bytes) {
+namespace {
+
+// the launches of sol_karman3d_step_fwd; with a non-zero force F = (fy, fx, fz) (sol_karman3d_step_fwd_buoy), k3_buoyancy between the
+// advection and the divergence (karman3d_buoyancy.hip): the step's output density pushes the advected velocity
+int step_fwd3d(const char* who, const sol_karman3d_cfg* c, void* stream,
+               const float* d_in, const float* vy_in, const float* vx_in, const float* vz_in,
+               const float* re, const float* active, const float* inflow,
+               const float* velBCy, const float* velBCyMask, int64_t bc_batch_stride,
+               float* d_out, float* vy_out, float* vx_out, float* vz_out,
+               float* saved_vy, float* saved_vx, float* saved_vz,
+               float* feat_out, const float* feat_scale, const int32_t* direct_header_host,
+               void* workspace, size_t workspace_bytes, float fy, float fx, float fz) {
     SOL_REQUIRE(c != nullptr, "cfg is NULL");
     SOL_REQUIRE((saved_vy && saved_vx && saved_vz) || (!saved_vy && !saved_vx && !saved_vz), "saved_vy / saved_vx / saved_vz: all three or none");
-    SOL_REQUIRE(c->B >= 1 && c->Y >= 8 && c->X >= 8 && c->Z >= 8 && c->B <= 65535, "sol_karman3d_step_fwd: B >= 1, Y, X, Z >= 8 (got %d, %d, %d, %d)", c->B, c->Y, c->X, c->Z);
-    SOL_REQUIRE((size_t)(c->Y + 1) * (c->X + 1) * (c->Z + 1) * 3 < ((size_t)1 << 31), "sol_karman3d_step_fwd: grid too large for 32-bit face indices");
-    SOL_REQUIRE(vy_in && vx_in && vz_in && re && active && velBCy && velBCyMask && vy_out && vx_out && vz_out && workspace, "sol_karman3d_step_fwd: NULL pointer argument");
+    SOL_REQUIRE(c->B >= 1 && c->Y >= 8 && c->X >= 8 && c->Z >= 8 && c->B <= 65535, "%s: B >= 1, Y, X, Z >= 8 (got %d, %d, %d, %d)", who, c->B, c->Y, c->X, c->Z);
+    SOL_REQUIRE((size_t)(c->Y + 1) * (c->X + 1) * (c->Z + 1) * 3 < ((size_t)1 << 31), "%s: grid too large for 32-bit face indices", who);
+    SOL_REQUIRE(vy_in && vx_in && vz_in && re && active && velBCy && velBCyMask && vy_out && vx_out && vz_out && workspace, "%s: NULL pointer argument", who);
     SOL_REQUIRE((d_in && inflow) || !d_out, "density output requested without d_in / inflow");
     SOL_REQUIRE(!feat_out || feat_scale, "feat_out requires feat_scale");
+    SOL_REQUIRE(fy - fy == 0.f && fx - fx == 0.f && fz - fz == 0.f, "%s: the force must be finite (got %g, %g, %g)", who, (double)fy, (double)fx, (double)fz);
+    const bool buoyant = fy != 0.f || fx != 0.f || fz != 0.f;
+    SOL_REQUIRE(!buoyant || (d_in && inflow && d_out), "%s: a non-zero force needs d_in, inflow and d_out", who);
     if (int e = check_blob3d(c, direct_header_host)) return e;
     const K3Fwd l = k3_fwd_layout(c, workspace);
     SOL_REQUIRE(workspace_bytes >= l.bytes, "workspace too small");
-    SOL_REQUIRE(vy_in != vy_out && vx_in != vx_out && vz_in != vz_out && (d_in != d_out || !d_out), "sol_karman3d_step_fwd: outputs must not alias the inputs");
+    SOL_REQUIRE(vy_in != vy_out && vx_in != vx_out && vz_in != vz_out && (d_in != d_out || !d_out), "%s: outputs must not alias the inputs", who);
     const int B = c->B, Y = c->Y, X = c->X, Z = c->Z, N = Y * X * Z;
     hipStream_t s = (hipStream_t)stream;
     const size_t nVy = (size_t)(Y + 1) * X * Z, nVx = (size_t)Y * (X + 1) * Z, nVz = (size_t)Y * X * (Z + 1);
@@ -1156,6 +1158,9 @@ extern "C" int sol_karman3d_step_fwd(const sol_karman3d_cfg* c, void* stream,
     } else {
         SOL_LAUNCH(k3_advect, dim3(grid_for((size_t)((Y + 1) * X + Y * (X + 1) + 2 * Y * X) * 64), B), dim3(256), 0, s, a);
     }
+    // buoyancy (f = fl(dt F); nothing is launched for F = 0): k3_div and k3_project read v*_out, which k3_buoyancy updates in place
+    if (buoyant)
+        if (int e = k3_buoyancy_add(s, B, Y, X, Z, active, d_out, c->dt * fy, c->dt * fx, c->dt * fz, vy_out, vx_out, vz_out)) return e;
     SOL_LAUNCH(k3_div, dim3(grid_for(N), B), dim3(256), 0, s, a);
     SOL_LAUNCH_CHECK();
 
@@ -1167,6 +1172,36 @@ extern "C" int sol_karman3d_step_fwd(const sol_karman3d_cfg* c, void* stream,
     return SOL_OK;
 }
 
+}  // namespace
+
+extern "C" int sol_karman3d_step_fwd(const sol_karman3d_cfg* c, void* stream,
+                                     const float* d_in, const float* vy_in, const float* vx_in, const float* vz_in,
+                                     const float* re, const float* active, const float* inflow,
+                                     const float* velBCy, const float* velBCyMask, int64_t bc_batch_stride,
+                                     float* d_out, float* vy_out, float* vx_out, float* vz_out,
+                                     float* saved_vy, float* saved_vx, float* saved_vz,
+                                     float* feat_out, const float* feat_scale, const int32_t* direct_header_host,
+                                     void* workspace, size_t workspace_bytes) {
+    return step_fwd3d("sol_karman3d_step_fwd", c, stream, d_in, vy_in, vx_in, vz_in, re, active, inflow, velBCy, velBCyMask, bc_batch_stride,
+                      d_out, vy_out, vx_out, vz_out, saved_vy, saved_vx, saved_vz, feat_out, feat_scale, direct_header_host,
+                      workspace, workspace_bytes, 0.f, 0.f, 0.f);
+}
+
+// The step with the buoyancy force F = (fy, fx, fz): sol_karman3d_step_fwd's launches with k3_buoyancy between the advection and the
+// divergence.  F = 0: the plain call's launches and bits.
+extern "C" int sol_karman3d_step_fwd_buoy(const sol_karman3d_cfg* c, void* stream,
+                                          const float* d_in, const float* vy_in, const float* vx_in, const float* vz_in,
+                                          const float* re, const float* active, const float* inflow,
+                                          const float* velBCy, const float* velBCyMask, int64_t bc_batch_stride,
+                                          float* d_out, float* vy_out, float* vx_out, float* vz_out,
+                                          float* saved_vy, float* saved_vx, float* saved_vz,
+                                          float* feat_out, const float* feat_scale, const int32_t* direct_header_host,
+                                          void* workspace, size_t workspace_bytes, float fy, float fx, float fz) {
+    return step_fwd3d("sol_karman3d_step_fwd_buoy", c, stream, d_in, vy_in, vx_in, vz_in, re, active, inflow, velBCy, velBCyMask, bc_batch_stride,
+                      d_out, vy_out, vx_out, vz_out, saved_vy, saved_vx, saved_vz, feat_out, feat_scale, direct_header_host,
+                      workspace, workspace_bytes, fy, fx, fz);
+}
+
 extern "C" size_t sol_karman3d_step_bwd_workspace_bytes(const sol_karman3d_cfg* c) {
     if (!c) return 0;
     return k3_bwd_layout(c, false, nullptr).bytes;
@@ -1174,19 +1209,30 @@ extern "C" size_t sol_karman3d_step_bwd_workspace_bytes(const sol_karman3d_cfg* 
 
 namespace {
 
-// the launches of sol_karman3d_step_bwd; with rx, followed by the Reynolds-number reduction over the fixed-point g_c they leave in the
+// the buoyant step's extra (sol_karman3d_step_bwd_buoy): the force, the cotangent of the step's output density (NULL = zero) and where
+// g_dsum [B,Y,X,Z] goes -- what the caller hands to the density adjoint as ITS g_d_out
+struct Buoy3Extra {
+    float fy, fx, fz;
+    const float* g_d_out;
+    float* g_dsum;
+};
+
+// the launches of sol_karman3d_step_bwd; with bx, followed by the transpose of the buoyancy term over the g_a they leave in the workspace
+// (k3b_buoyancy_adj, karman3d_buoyancy.hip); with rx, followed by the Reynolds-number reduction over the fixed-point g_c they leave in the
 // workspace (sol_karman3d_step_bwd_re; k3b_diffuse_adj only reads g_c): g_v*_in are the same launches' results either way
 int step_bwd3d(const char* who, const sol_karman3d_cfg* c, void* stream,
                const float* saved_vy, const float* saved_vx, const float* saved_vz,
                const float* re, const float* active, const float* velBCyMask, int64_t bc_batch_stride,
                const float* g_vy_out, const float* g_vx_out, const float* g_vz_out,
                float* g_vy_in, float* g_vx_in, float* g_vz_in,
-               const int32_t* direct_header_host, void* workspace, size_t workspace_bytes, const Re3Extra* rx) {
+               const int32_t* direct_header_host, void* workspace, size_t workspace_bytes, const Re3Extra* rx, const Buoy3Extra* bx = nullptr) {
     SOL_REQUIRE(c != nullptr, "cfg is NULL");
     SOL_REQUIRE(c->B >= 1 && c->Y >= 8 && c->X >= 8 && c->Z >= 8 && c->B <= 65535, "%s: B >= 1, Y, X, Z >= 8", who);
     SOL_REQUIRE(saved_vy && saved_vx && saved_vz && re && active && velBCyMask && g_vy_out && g_vx_out && g_vz_out && g_vy_in && g_vx_in && g_vz_in && workspace,
                 "%s: NULL pointer argument", who);
     SOL_REQUIRE(!rx || (rx->vy_in && rx->vx_in && rx->vz_in && rx->g_re), "%s: NULL pointer argument", who);
+    SOL_REQUIRE(!bx || bx->g_dsum, "%s: NULL pointer argument (g_dsum)", who);
+    SOL_REQUIRE(!bx || (bx->fy - bx->fy == 0.f && bx->fx - bx->fx == 0.f && bx->fz - bx->fz == 0.f), "%s: the force must be finite", who);
     if (int e = check_blob3d(c, direct_header_host)) return e;
     const K3Bwd l = k3_bwd_layout(c, rx != nullptr, workspace);
     SOL_REQUIRE(workspace_bytes >= l.bytes, "workspace too small");
@@ -1199,6 +1245,11 @@ int step_bwd3d(const char* who, const sol_karman3d_cfg* c, void* stream,
         }
         for (const void* i : ins) SOL_REQUIRE(i != (const void*)rx->g_re, "%s: outputs must not alias the inputs", who);
         SOL_REQUIRE((const void*)rx->g_re != (const void*)re, "%s: outputs must not alias the inputs", who);
+    }
+    if (bx) {
+        const void* others[] = {saved_vy, saved_vx, saved_vz, re, active, velBCyMask, g_vy_out, g_vx_out, g_vz_out, g_vy_in, g_vx_in, g_vz_in, bx->g_d_out,
+                                rx ? rx->vy_in : nullptr, rx ? rx->vx_in : nullptr, rx ? rx->vz_in : nullptr, rx ? rx->g_re : nullptr, c->cg_info};
+        for (const void* o : others) SOL_REQUIRE((const void*)bx->g_dsum != o, "%s: g_dsum must be a buffer of its own", who);
     }
     const int B = c->B, Y = c->Y, X = c->X, Z = c->Z, N = Y * X * Z;
     hipStream_t s = (hipStream_t)stream;
@@ -1232,6 +1283,10 @@ int step_bwd3d(const char* who, const sol_karman3d_cfg* c, void* stream,
     SOL_LAUNCH(k3b_advect_adj, dim3(grid_for((size_t)((Y + 1) * X + Y * (X + 1) + Y * X) * 64), B), dim3(256), 0, s, a);
     SOL_LAUNCH(k3b_diffuse_adj, dim3(grid_for(faces), B), dim3(256), 0, s, a);
     SOL_LAUNCH_CHECK();
+    // g_dsum = g_d_out + dt F . (face-to-cell transpose of g_a); a poisoned simulation (gmax) gets NaN throughout.  g_a and the absmax slots
+    // are as k3b_gva left them: the scatter reads g_a, k3b_diffuse_adj reads g_c, neither writes them
+    if (bx)
+        if (int e = k3_buoyancy_adj(s, B, Y, X, Z, active, a.gay, a.gax, a.gaz, a.gmax, c->dt * bx->fy, c->dt * bx->fx, c->dt * bx->fz, bx->g_d_out, bx->g_dsum)) return e;
     if (!rx) return SOL_OK;
     // g' of the Reynolds-number gradient = what k3b_diffuse_adj has just read: fx_get(g_c) (. (1 - bcm) on v_y)
     Re3In in{};
@@ -1270,6 +1325,34 @@ extern "C" int sol_karman3d_step_bwd_re(const sol_karman3d_cfg* c, void* stream,
     const Re3Extra rx{vy_in, vx_in, vz_in, g_re, accumulate_re};
     return step_bwd3d("sol_karman3d_step_bwd_re", c, stream, saved_vy, saved_vx, saved_vz, re, active, velBCyMask, bc_batch_stride,
                       g_vy_out, g_vx_out, g_vz_out, g_vy_in, g_vx_in, g_vz_in, direct_header_host, workspace, workspace_bytes, &rx);
+}
+
+// The adjoint of the BUOYANT step (sol_karman3d_step_fwd_buoy): sol_karman3d_step_bwd(_re)'s launches, then k3b_buoyancy_adj.  The caller
+// runs sol_karman3d_density_bwd(_re) (accumulate = 1) on g_dsum next.
+extern "C" int sol_karman3d_step_bwd_buoy(const sol_karman3d_cfg* c, void* stream,
+                                          const float* saved_vy, const float* saved_vx, const float* saved_vz,
+                                          const float* re, const float* active, const float* velBCyMask, int64_t bc_batch_stride,
+                                          const float* g_vy_out, const float* g_vx_out, const float* g_vz_out,
+                                          float* g_vy_in, float* g_vx_in, float* g_vz_in,
+                                          const int32_t* direct_header_host, void* workspace, size_t workspace_bytes,
+                                          float fy, float fx, float fz, const float* g_d_out, float* g_dsum) {
+    const Buoy3Extra bx{fy, fx, fz, g_d_out, g_dsum};
+    return step_bwd3d("sol_karman3d_step_bwd_buoy", c, stream, saved_vy, saved_vx, saved_vz, re, active, velBCyMask, bc_batch_stride,
+                      g_vy_out, g_vx_out, g_vz_out, g_vy_in, g_vx_in, g_vz_in, direct_header_host, workspace, workspace_bytes, nullptr, &bx);
+}
+
+extern "C" int sol_karman3d_step_bwd_buoy_re(const sol_karman3d_cfg* c, void* stream,
+                                             const float* saved_vy, const float* saved_vx, const float* saved_vz,
+                                             const float* re, const float* active, const float* velBCyMask, int64_t bc_batch_stride,
+                                             const float* g_vy_out, const float* g_vx_out, const float* g_vz_out,
+                                             float* g_vy_in, float* g_vx_in, float* g_vz_in,
+                                             const int32_t* direct_header_host, void* workspace, size_t workspace_bytes,
+                                             const float* vy_in, const float* vx_in, const float* vz_in, float* g_re, int accumulate_re,
+                                             float fy, float fx, float fz, const float* g_d_out, float* g_dsum) {
+    const Re3Extra rx{vy_in, vx_in, vz_in, g_re, accumulate_re};
+    const Buoy3Extra bx{fy, fx, fz, g_d_out, g_dsum};
+    return step_bwd3d("sol_karman3d_step_bwd_buoy_re", c, stream, saved_vy, saved_vx, saved_vz, re, active, velBCyMask, bc_batch_stride,
+                      g_vy_out, g_vx_out, g_vz_out, g_vy_in, g_vx_in, g_vz_in, direct_header_host, workspace, workspace_bytes, &rx, &bx);
 }
 
 extern "C" int sol_karman3d_pressure_solve(const sol_karman3d_cfg* c, void* stream, const float* active, const float* rhs, float* p,

@@ -58,6 +58,31 @@ def velocity_bc_masks3d(Y, X, Z):
     return vn, np.copy(vn)
 
 
+def buoyancy_force3d(buoyancy=None, buoyancy_factor=None, gravity=(-9.81, 0.0, 0.0)):
+    """The force per unit density F = (fy, fx, fz) of the buoyant 3-D step, or None (off): ops.buoyancy_force's conventions with a third
+    component.  `buoyancy`: F itself, one number (fy) or up to three (missing components are 0); else PhiFlow's spelling, F = -gravity *
+    buoyancy_factor (Gravity() = -9.81 along y: F = (9.81 beta, 0, 0)).  A force of (0, 0, 0) is kept as given: the entry points take it
+    and issue the plain launches."""
+    if buoyancy is not None and buoyancy_factor is not None:
+        raise ValueError("give buoyancy=(fy, fx, fz) or buoyancy_factor (with gravity), not both")
+    if buoyancy is None and buoyancy_factor is None:
+        return None
+    if buoyancy is None:
+        g = (float(gravity), 0.0, 0.0) if np.isscalar(gravity) else tuple(float(v) for v in gravity)
+        if len(g) != 3:
+            raise ValueError("gravity must be (gy, gx, gz), got %r" % (gravity,))
+        buoyancy = tuple(-c * float(buoyancy_factor) for c in g)
+    f = (float(buoyancy),) if np.isscalar(buoyancy) else tuple(float(v) for v in buoyancy)
+    if not 1 <= len(f) <= 3 or not all(np.isfinite(f)):
+        raise ValueError("buoyancy must be a finite force (fy, fx, fz), got %r" % (buoyancy,))
+    return f + (0.0,) * (3 - len(f))
+
+
+def _buoyant3d(buoyancy):
+    """True for a force that moves the velocity: the density is then part of the dynamics"""
+    return buoyancy is not None and any(v != 0.0 for v in buoyancy)
+
+
 PRESSURE_SOLVERS3D = ("auto", "direct", "cg")
 CG_MAX_ITER3D = 120             # launch budget of the CG solve: 28-87 iterations measured at rtol 1e-6 (DESIGN 4.8)
 
@@ -118,14 +143,22 @@ class Karman3DFlow:
     density_grad=True (opt-in): the density output of `step` is differentiable too (sol_karman3d_density_bwd: launches of their own, no
     pressure solve, added onto the velocity adjoint's result).  re_grad=True (opt-in): a tensor `re` that requires a gradient receives
     one (sol_karman3d_step_bwd_re / sol_karman3d_density_bwd_re; the step's input velocity is saved as well).  With both off the step
-    launches what it always did: the density is a passive tracer and `re` is data."""
+    launches what it always did: the density is a passive tracer and `re` is data.
+
+    buoyancy=(fy, fx, fz), a force per unit density, or PhiFlow's spelling buoyancy_factor=beta with gravity=(gy, gx, gz): F = -gravity *
+    beta (buoyancy_force3d).  The step's OUTPUT density pushes the velocity (sol_karman3d_step_fwd_buoy: one launch more); the density is
+    then part of the dynamics and always in the graph, whatever density_grad says (_Karman3DStepFn's buoyant mode).  A force of zero, or
+    none: the plain step."""
 
     def __init__(self, scene, batch_size, dt=1.0, res=None, grad_pad="replicate", inflow_order="after",
-                 cg_rtol=1e-6, cg_atol=1e-9, cg_max_iter=CG_MAX_ITER3D, density_grad=False, re_grad=False):
+                 cg_rtol=1e-6, cg_atol=1e-9, cg_max_iter=CG_MAX_ITER3D, density_grad=False, re_grad=False,
+                 buoyancy=None, buoyancy_factor=None, gravity=(-9.81, 0.0, 0.0)):
         _lib.require_gpu()
         self.lib = _lib.load()
         self.scene, self.B = scene, batch_size
         self.density_grad, self.re_grad = bool(density_grad), bool(re_grad)
+        f = buoyancy_force3d(buoyancy, buoyancy_factor, gravity)
+        self.buoyancy = f if _buoyant3d(f) else None
         s = scene
         self.cg = s.pressure_solver == "cg"
         self.cfg = Karman3DCfg(batch_size, s.Y, s.X, s.Z, float(s.dx), float(dt), float(s.X if res is None else res),
@@ -146,7 +179,8 @@ class Karman3DFlow:
         self.cfg.cg_info = info.data_ptr()
         return info
 
-    def _fwd(self, d, vy, vx, vz, re, saved=None, feat_out=None, feat_scale=None):
+    def _fwd(self, d, vy, vx, vz, re, saved=None, feat_out=None, feat_scale=None, buoyancy=None):
+        """one forward step; buoyancy = (fy, fx, fz): sol_karman3d_step_fwd_buoy (a force of zero issues the plain call's launches)"""
         s, B = self.scene, self.B
         Y, X, Z = s.Y, s.X, s.Z
         assert d.shape == (B, Y, X, Z) and vy.shape == (B, Y + 1, X, Z) and vx.shape == (B, Y, X + 1, Z) and vz.shape == (B, Y, X, Z + 1)
@@ -158,11 +192,12 @@ class Karman3DFlow:
             fs = (C.c_float * 4)(*[float(v) for v in feat_scale])
         sv = saved if saved is not None else (None, None, None)
         info = self._cg_info()
-        check(self.lib.sol_karman3d_step_fwd(C.byref(self.cfg), stream(), ptr(d), ptr(vy), ptr(vx), ptr(vz), ptr(re),
-                                             ptr(s.active), ptr(s.inflow), ptr(s.velBCy), ptr(s.velBCyMask), s.bc_stride,
-                                             ptr(out[0]), ptr(out[1]), ptr(out[2]), ptr(out[3]), ptr(sv[0]), ptr(sv[1]), ptr(sv[2]),
-                                             ptr(feat_out), fs,
-                                             s.direct_header.ctypes.data_as(C.c_void_p), ptr(self.workspace), self.workspace_bytes))
+        entry, tail = (self.lib.sol_karman3d_step_fwd, ()) if buoyancy is None else (self.lib.sol_karman3d_step_fwd_buoy, tuple(float(v) for v in buoyancy))
+        check(entry(C.byref(self.cfg), stream(), ptr(d), ptr(vy), ptr(vx), ptr(vz), ptr(re),
+                    ptr(s.active), ptr(s.inflow), ptr(s.velBCy), ptr(s.velBCyMask), s.bc_stride,
+                    ptr(out[0]), ptr(out[1]), ptr(out[2]), ptr(out[3]), ptr(sv[0]), ptr(sv[1]), ptr(sv[2]),
+                    ptr(feat_out), fs,
+                    s.direct_header.ctypes.data_as(C.c_void_p), ptr(self.workspace), self.workspace_bytes, *tail))
         if info is not None:
             self.solve_info = {"iterations": info[:, 0], "converged": info[:, 1]}
         return tuple(out)
@@ -187,25 +222,38 @@ class Karman3DFlow:
             raise ValueError("g_re must be [B] = (%d,), got %s" % (self.B, tuple(g_re.shape)))
         return (ptr(vel_in[0]), ptr(vel_in[1]), ptr(vel_in[2]), ptr(g_re), int(accumulate)), g_re
 
-    def _bwd(self, saved, re, gvy, gvx, gvz, vel_in=None, g_re=None):
+    def _bwd(self, saved, re, gvy, gvx, gvz, vel_in=None, g_re=None, buoyancy=None, g_d=None):
         """the velocity adjoint (sol_karman3d_step_bwd); vel_in = the step's input velocity: also the gradient with respect to re
-        (sol_karman3d_step_bwd_re; the velocity gradients are the plain call's bits) -> [g_vy, g_vx, g_vz] (+ [g_re])"""
+        (sol_karman3d_step_bwd_re; the velocity gradients are the plain call's bits) -> [g_vy, g_vx, g_vz] (+ [g_re]).
+        buoyancy = (fy, fx, fz): the buoyant step's (sol_karman3d_step_bwd_buoy(_re): the same launches and bits, then the transpose of the
+        force term); g_d [B,Y,X,Z] = the cotangent of the step's output density (None = zero) -> ... + [g_dsum], which the caller hands to
+        density_bwd as its g_d, accumulating onto the velocity gradients returned here."""
         s = self.scene
         gi = [torch.empty_like(t) for t in saved]
         info = self._cg_info()
+        buoy = buoyancy is not None
         if vel_in is None:
-            entry, tail = self.lib.sol_karman3d_step_bwd, ()
+            entry, tail = (self.lib.sol_karman3d_step_bwd_buoy if buoy else self.lib.sol_karman3d_step_bwd), ()
         else:
-            entry = self.lib.sol_karman3d_step_bwd_re
+            entry = self.lib.sol_karman3d_step_bwd_buoy_re if buoy else self.lib.sol_karman3d_step_bwd_re
             self._ws(self.lib.sol_karman3d_step_bwd_re_workspace_bytes(C.byref(self.cfg)))
             tail, g_re = self._re_tail(saved, vel_in, g_re)
+        g_dsum = None
+        if buoy:
+            if g_d is not None:
+                g_d = _lib.f32(g_d)
+                if g_d.shape != (self.B, s.Y, s.X, s.Z):
+                    raise ValueError("g_d must be [B,Y,X,Z] = %s, got %s" % ((self.B, s.Y, s.X, s.Z), tuple(g_d.shape)))
+            g_dsum = torch.empty(self.B, s.Y, s.X, s.Z, dtype=torch.float32, device=saved[0].device)
+            tail = tuple(tail) + tuple(float(v) for v in buoyancy) + (ptr(g_d), ptr(g_dsum))
         check(entry(C.byref(self.cfg), stream(), ptr(saved[0]), ptr(saved[1]), ptr(saved[2]), ptr(re),
                     ptr(s.active), ptr(s.velBCyMask), s.bc_stride, ptr(gvy), ptr(gvx), ptr(gvz),
                     ptr(gi[0]), ptr(gi[1]), ptr(gi[2]),
                     s.direct_header.ctypes.data_as(C.c_void_p), ptr(self.workspace), self.workspace_bytes, *tail))
         if info is not None:
             self.solve_info = dict(self.solve_info, iterations_bwd=info[:, 0], converged_bwd=info[:, 1])
-        return gi if vel_in is None else gi + [g_re]
+        res = gi if vel_in is None else gi + [g_re]
+        return res + [g_dsum] if buoy else res
 
     def pressure_solve(self, rhs):
         """The step's pressure solve alone (sol_karman3d_pressure_solve): p with M p = rhs, M = -A for the scene's mask; rhs [B,Y,X,Z].
@@ -225,15 +273,17 @@ class Karman3DFlow:
         """(d, vy, vx, vz) -> new tensors after one solver step.  Differentiable with respect to the velocity (the density is
         a passive tracer) when a velocity input requires grad; feat_out [B,Y,X,Z,4] (optional, no-grad use) receives the
         scaled features.  With density_grad the density output is differentiable too (taken when any of d, vy, vx, vz requires a
-        gradient); with re_grad a tensor `re` that requires a gradient receives one."""
+        gradient); with re_grad a tensor `re` that requires a gradient receives one.  With a buoyancy force the density is part of the
+        dynamics: every output is differentiable with respect to the density and the velocity."""
         d, vy, vx, vz, re = (_lib.f32(t) for t in (d, vy, vx, vz, re))
         grad = torch.is_grad_enabled()
         want_re = self.re_grad and grad and re.requires_grad
-        if grad and (vy.requires_grad or vx.requires_grad or vz.requires_grad or (self.density_grad and d.requires_grad) or want_re):
+        density = self.density_grad or self.buoyancy is not None
+        if grad and (vy.requires_grad or vx.requires_grad or vz.requires_grad or (density and d.requires_grad) or want_re):
             if feat_out is not None:
                 raise ValueError("feat_out is the fused no-grad feature output: build the features with to_feature3d() when training")
-            return _Karman3DStepFn.apply(self, d, vy, vx, vz, re, self.density_grad, want_re)
-        return self._fwd(d, vy, vx, vz, re, None, feat_out, feat_scale)
+            return _Karman3DStepFn.apply(self, d, vy, vx, vz, re, density, want_re, self.buoyancy)
+        return self._fwd(d, vy, vx, vz, re, None, feat_out, feat_scale, self.buoyancy)
 
 
 def density_bwd(sim, d_in, saved, re, g_d, g_v=None, vel_in=None, g_re=None):
@@ -275,14 +325,19 @@ class _Karman3DStepFn(torch.autograd.Function):
     respect to the velocity, the density is a passive tracer, re is data.  `density` (opt-in): the density output is differentiable too
     (density_bwd, added onto the velocity adjoint's result).  `want_re` (opt-in): differentiable with respect to re as well, the step's
     input velocity saved beside the post-diffusion one.  In the opt-in modes the velocity half (with its pressure solve) runs only when a
-    velocity cotangent arrived, the density half only when a density cotangent did; both together accumulate."""
+    velocity cotangent arrived, the density half only when a density cotangent did; both together accumulate.
+    `buoyancy` = (fy, fx, fz), a non-zero force (else None): the buoyant step -- the density is part of the dynamics, so it is in the graph
+    whatever `density` says.  Whenever any cotangent arrives the velocity half runs through its buoyant entry (Karman3DFlow._bwd: the
+    plain launches and the transpose of the force term, g_dsum = g_d + dt F . transpose(g_a)), then the density half on g_dsum, accumulating:
+    a velocity-only loss yields a density gradient too."""
 
     @staticmethod
-    def forward(ctx, sim, d, vy, vx, vz, re, density, want_re):
+    def forward(ctx, sim, d, vy, vx, vz, re, density, want_re, buoyancy=None):
         vel = [vy.contiguous(), vx.contiguous(), vz.contiguous()]
         saved = [torch.empty_like(t) for t in vel]
-        out = sim._fwd(d, vel[0], vel[1], vel[2], re, saved)
-        ctx.sim, ctx.density, ctx.want_re = sim, density, want_re
+        density = bool(density) or buoyancy is not None
+        out = sim._fwd(d, vel[0], vel[1], vel[2], re, saved, buoyancy=buoyancy)
+        ctx.sim, ctx.density, ctx.want_re, ctx.buoyancy = sim, density, want_re, buoyancy
         ctx.save_for_backward(re, *saved, *((d,) if density else ()), *(vel if want_re else ()))
         if not density:
             ctx.mark_non_differentiable(out[0])
@@ -297,6 +352,12 @@ class _Karman3DStepFn(torch.autograd.Function):
         vel_in = tuple(rest[-3:]) if ctx.want_re else None
         z = lambda g, t: torch.zeros_like(t) if g is None else g.contiguous()
         od = g_re = gi = None
+        if ctx.buoyancy is not None:
+            if gd is None and gvy is None and gvx is None and gvz is None:
+                return (None,) * 9
+            res = ctx.sim._bwd(saved, re, z(gvy, sy), z(gvx, sx), z(gvz, sz), vel_in, buoyancy=ctx.buoyancy, g_d=None if gd is None else gd.contiguous())
+            res = density_bwd(ctx.sim, d_in, saved, re, res[-1], res[:3], vel_in, res[3] if vel_in is not None else None)
+            return None, res[0], res[1], res[2], res[3], (res[4] if vel_in is not None else None), None, None, None
         if not (ctx.density or ctx.want_re) or gvy is not None or gvx is not None or gvz is not None:
             res = ctx.sim._bwd(saved, re, z(gvy, sy), z(gvx, sx), z(gvz, sz), vel_in)
             gi, g_re = res[:3], (res[3] if vel_in is not None else None)
@@ -304,7 +365,7 @@ class _Karman3DStepFn(torch.autograd.Function):
             res = density_bwd(ctx.sim, d_in, saved, re, gd.contiguous(), gi, vel_in, g_re)
             od, gi, g_re = res[0], res[1:4], (res[4] if vel_in is not None else None)
         gi = gi if gi is not None else (None, None, None)
-        return None, od, gi[0], gi[1], gi[2], g_re, None, None
+        return None, od, gi[0], gi[1], gi[2], g_re, None, None, None
 
 
 class _ToFeature3DFn(torch.autograd.Function):
@@ -678,12 +739,16 @@ class Karman3DTrainer:
     (sol_adam_tf_step).  gts: [msteps] of (vy, vx, vz) ground-truth frames."""
 
     def __init__(self, net, scene, B, msteps, std_v, std_re, dt=1.0, res=None, beta1=0.9, beta2=0.999, eps=1e-8, conv_precision="split",
-                 use_graph=False, group=None, comm=None, schedule="manual", glue="fused", **solver):
+                 use_graph=False, group=None, comm=None, schedule="manual", glue="fused", buoyancy=None, **solver):
         """schedule: "manual" (default) = the hand-written forward unroll + reverse sweep over the C ABI (_unrolled_schedule), "autograd" = the
         torch-autograd composition of the differentiable HIP ops (rounds 3-4; kept as the cross-check).
         use_graph: capture the whole forward unroll + reverse sweep ONCE into a hipGraph over static input buffers (the
         TF1 "build the graph, sess.run many" shape, as trainer.GraphTrainer does for the 2-D mercury model): a step then
-        copies the batch in and replays ~3000 launches with one host call."""
+        copies the batch in and replays ~3000 launches with one host call.
+        buoyancy=(fy, fx, fz) (buoyancy_force3d): the density pushes the velocity.  The schedule is unchanged; the solver pair is the buoyant
+        one: the forward step is sol_karman3d_step_fwd_buoy and each step's input density is kept, the reverse sweep runs the buoyant
+        velocity adjoint (g_dsum), then the density adjoint accumulating onto the velocity gradients, which carries the density cotangent
+        to the next (earlier) step (None at the last step: the loss does not look at the density).  Off, or zero: today's launches."""
         from .trainer import _conv_precision_code
         from .dist import DPStep
         _lib.require_gpu()
@@ -691,7 +756,8 @@ class Karman3DTrainer:
         self.net, self.scene, self.B, self.ms = net, scene, B, msteps
         assert glue in ("fused", "torch")
         self.glue = glue          # reverse-sweep glue of the manual schedule: sol_karman3d_correct_bwd / _feature_bwd, or the torch elementwise composition
-        self.sim = Karman3DFlow(scene, B, dt=dt, res=res, **solver)
+        self.sim = Karman3DFlow(scene, B, dt=dt, res=res, buoyancy=buoyancy, **solver)
+        self.buoyancy = self.sim.buoyancy
         dev = scene.active.device
         self.std_v = torch.tensor([float(v) for v in std_v], dtype=torch.float32, device=dev)
         self._std_v_host = tuple(float(v) for v in std_v)
@@ -749,11 +815,14 @@ class Karman3DTrainer:
         sv = self._std_v_host
         v = (vy, vx, vz)
         keep = []                                   # per step: (saved velocities, network state, d loss_i / d v_i)
+        d_ins = []                                  # buoyant mode: the steps' input densities
         losses = []
         for i in range(ms):
             saved = [torch.empty_like(t) for t in v]
             feat = torch.empty(B, Y, X, Z, 4, dtype=torch.float32, device=vy.device)
-            d, *v = sim._fwd(d, v[0], v[1], v[2], re, saved, feat, fs)
+            if self.buoyancy is not None:
+                d_ins.append(d)
+            d, *v = sim._fwd(d, v[0], v[1], v[2], re, saved, feat, fs, self.buoyancy)
             out, state = sch.forward(feat)
             check(self.lib.sol_karman3d_correct(stream(), ptr(out), net.cout, sv[0], sv[1], sv[2], ptr(v[0]), ptr(v[1]), ptr(v[2]), B, Y, X, Z))
             li, gi = l2_loss_fwd_bwd(v, tuple(g[i] for g in self._gt), sv, gscale=1.0 / ms)
@@ -761,6 +830,7 @@ class Karman3DTrainer:
             keep.append((saved, state, gi))
         flat = None
         gin = None
+        g_d = None                                  # buoyant mode: the density cotangent carried from step i + 1 to step i
         inv_in = fs[:3]
         for i in range(ms - 1, -1, -1):
             saved, state, G = keep[i]
@@ -785,7 +855,12 @@ class Karman3DTrainer:
                 G[0][:, :Y].add_(dx[..., 0], alpha=inv_in[0])
                 G[1][:, :, :X].add_(dx[..., 1], alpha=inv_in[1])
                 G[2][..., :Z].add_(dx[..., 2], alpha=inv_in[2])
-            gin = sim._bwd(saved, re, G[0], G[1], G[2])
+            if self.buoyancy is not None:
+                *gv, g_dsum = sim._bwd(saved, re, G[0], G[1], G[2], buoyancy=self.buoyancy, g_d=g_d)
+                g_d, *gin = density_bwd(sim, d_ins[i], saved, re, g_dsum, gv)
+                d_ins[i] = None
+            else:
+                gin = sim._bwd(saved, re, G[0], G[1], G[2])
             keep[i] = None                          # (eager runs: the step's activations can go)
         losses = _lib.stack0(losses)
         loss = losses.sum() / ms
@@ -869,13 +944,15 @@ class Karman3DRollout:
     """No-grad roll-out: nsteps x [solver step -> features / std -> CNN -> velocity += std * correction]
     (karman_apply.py:138-158 / the forward half of karman_train.py:397-426, three components)."""
 
-    def __init__(self, net, scene, B, std_v, std_re, dt=1.0, res=None, conv_precision="split", **solver):
+    def __init__(self, net, scene, B, std_v, std_re, dt=1.0, res=None, conv_precision="split", buoyancy=None, **solver):
+        """buoyancy=(fy, fx, fz) (buoyancy_force3d): the density pushes the velocity (the solver step is sol_karman3d_step_fwd_buoy)"""
         from .trainer import _conv_precision_code
         from .schedule3d import NetSchedule3D
         _lib.require_gpu()
         self.lib = _lib.load()
         self.net, self.scene, self.B = net, scene, B
-        self.sim = Karman3DFlow(scene, B, dt=dt, res=res, **solver)
+        self.sim = Karman3DFlow(scene, B, dt=dt, res=res, buoyancy=buoyancy, **solver)
+        self.buoyancy = self.sim.buoyancy
         self.std_v = tuple(float(v) for v in std_v)
         self.feat_scale = [1.0 / self.std_v[0], 1.0 / self.std_v[1], 1.0 / self.std_v[2], 1.0 / float(std_re)]
         self.conv_precision = _conv_precision_code(conv_precision)

@@ -47,30 +47,36 @@ def scene_from_args(params):
     return None
 
 
-def add_buoyancy_arg(p):
-    """--buoyancy FY[,FX] of karman.py, karman_train.py and karman_apply.py"""
-    p.add_argument("--buoyancy", default=None, metavar="FY[,FX]",
-                   help="buoyancy force per unit density: the density pushes the velocity (large grids only; PhiFlow's buoyancy_factor b "
-                        "is FY = 9.81 b).  Stored with the data like the scene; absent: off")
+_BUOYANCY_SPELLING = {2: "FY[,FX]", 3: "FY[,FX[,FZ]]"}
 
 
-def buoyancy_from_args(params):
-    """(fy, fx) of --buoyancy FY[,FX], or None when the flag is absent."""
-    from sol_amd import ops
+def add_buoyancy_arg(p, ncomp=2):
+    """--buoyancy FY[,FX] of karman.py, karman_train.py and karman_apply.py; ncomp=3: --buoyancy FY[,FX[,FZ]] of karman3d.py"""
+    p.add_argument("--buoyancy", default=None, metavar=_BUOYANCY_SPELLING[ncomp],
+                   help="buoyancy force per unit density: the density pushes the velocity (%sPhiFlow's buoyancy_factor b "
+                        "is FY = 9.81 b).  Stored with the data like the scene; absent: off" % ("large grids only; " if ncomp == 2 else ""))
+
+
+def buoyancy_from_args(params, ncomp=2):
+    """(fy, fx) of --buoyancy FY[,FX] -- ncomp=3: (fy, fx, fz) of --buoyancy FY[,FX[,FZ]] --, or None when the flag is absent."""
     if params.get("buoyancy") is None:
         return None
     try:
         vals = [float(v) for v in str(params["buoyancy"]).split(",")]
-        if len(vals) not in (1, 2):
+        if not 1 <= len(vals) <= ncomp:
             raise ValueError
+        if ncomp == 3:
+            from sol_amd import karman3d
+            return karman3d.buoyancy_force3d(tuple(vals))
+        from sol_amd import ops
         return ops.buoyancy_force(tuple(vals + [0.0])[:2])
     except ValueError:
-        raise SystemExit("bad --buoyancy %r: expected FY or FY,FX (finite numbers)" % (params["buoyancy"],))
+        raise SystemExit("bad --buoyancy %r: expected %s (finite numbers)" % (params["buoyancy"], "FY or FY,FX" if ncomp == 2 else "FY, FY,FX or FY,FX,FZ"))
 
 
 def agreed_buoyancy(recorded, flag, where):
     """The force of a run that reads data: what the data recorded (None: off), unless --buoyancy says otherwise -- a contradiction."""
-    norm = lambda f: None if f is None or (f[0] == 0.0 and f[1] == 0.0) else (float(f[0]), float(f[1]))
+    norm = lambda f: None if f is None or all(v == 0.0 for v in f) else tuple(float(v) for v in f)
     if flag is not None and norm(flag) != norm(recorded):
         raise SystemExit("--buoyancy %s contradicts the force recorded in %s (%s)" % (flag, where, recorded))
     return norm(recorded)

@@ -5,14 +5,16 @@ with a trained 3-D corrector, and a SOL-n training demo on frames generated on t
 The reference has no 3-D script (/root/reference/README.md:37-38); the flags follow karman-2d/karman.py:33-47 and
 karman_apply.py:20-31 (-r res of the reference axis -> grid 2r x r x r, --re, -t steps, -s skip, -o output, --model) so that
 the 2-D workflow carries over.  Frames are written like the 2-D scenes: dens_%06d.npz [1,Y,X,Z,1], velo_%06d.npz
-[1,Y+1,X+1,Z+1,3] (staggered tensor, zero padded at the high ends, components reversed on disk as PhiFlow does)."""
+[1,Y+1,X+1,Z+1,3] (staggered tensor, zero padded at the high ends, components reversed on disk as PhiFlow does).
+--buoyancy FY[,FX[,FZ]]: the density pushes the velocity (generation, --model roll-out and --train-sol alike); recorded in params.pickle
+and in the model file as "buoyancy" (a triple, or None: off), so that a roll-out of the trained corrector picks it up."""
 import argparse
 import pickle
 
 import numpy as np
 import torch
 
-from _common import logger, select_gpu
+from _common import add_buoyancy_arg, agreed_buoyancy, buoyancy_from_args, logger, select_gpu
 import sol_amd
 from sol_amd import karman3d as k3, scene, synthetic
 
@@ -43,7 +45,9 @@ def main(argv=None):
     p.add_argument("--obstacle-mask", default=None, help="[Y,X,Z] .npy mask of the scene (1 = fluid, 0 = solid) instead of the sphere")
     p.add_argument("--pressure-solver", default="auto", choices=k3.PRESSURE_SOLVERS3D,
                    help="direct (capacitance blob), cg (preconditioned CG, any mask) or auto (direct where it builds)")
+    add_buoyancy_arg(p, ncomp=3)
     params = vars(p.parse_args(argv))
+    params["buoyancy"] = buoyancy_from_args(params, ncomp=3)
     select_gpu(params["gpu"])
     log = logger()
     res = params["res"]
@@ -51,7 +55,11 @@ def main(argv=None):
     dev = "cuda"
     active = np.load(params["obstacle_mask"]) if params["obstacle_mask"] else None
     sc = k3.Scene3D(Y, X, Z, length=float(params["len"]), device=dev, active=active, pressure_solver=params["pressure_solver"])
-    sim = k3.Karman3DFlow(sc, 1)
+    blob = torch.load(params["model"], map_location="cpu") if params["model"] else None
+    if blob is not None and "buoyancy" in blob:     # the force the corrector was trained with; a model without the record takes the flag
+        params["buoyancy"] = agreed_buoyancy(blob["buoyancy"], params["buoyancy"], params["model"])
+    buoyancy = params["buoyancy"]
+    sim = k3.Karman3DFlow(sc, 1, buoyancy=buoyancy)
     f = lambda a: torch.as_tensor(a, dtype=torch.float32, device=dev).contiguous()
     # karman.py:106-110 in 3-D: uniform flow along y + a sideways poke behind the obstacle
     vy = np.ones((1, Y + 1, X, Z), dtype=np.float32)
@@ -68,12 +76,12 @@ def main(argv=None):
             pickle.dump(params, fh)
     log.info(params)
     log.info("pressure solver: %s" % sc.pressure_solver)
+    log.info("buoyancy: %s" % (buoyancy,))
     net = ro = None
-    if params["model"]:
-        blob = torch.load(params["model"], map_location="cpu")
+    if blob is not None:
         net = k3.MarsMoon3D(device=dev)
         net.set_weights([w.numpy() for w in blob["weights"]])
-        ro = k3.Karman3DRollout(net, sc, 1, blob["std_v"], blob["std_re"])
+        ro = k3.Karman3DRollout(net, sc, 1, blob["std_v"], blob["std_re"], buoyancy=buoyancy)
     frames = []
     with torch.no_grad():
         for i in range(1, params["simsteps"]):
@@ -95,7 +103,7 @@ def main(argv=None):
         w = net.get_weights()
         w[22] = w[22] * 0.01
         net.set_weights(w)
-        tr = k3.Karman3DTrainer(net, sc, 1, ms, std_v, max(params["re"], 1.0), use_graph=True)
+        tr = k3.Karman3DTrainer(net, sc, 1, ms, std_v, max(params["re"], 1.0), use_graph=True, buoyancy=buoyancy)
         rng = np.random.default_rng(params["seed"])
         for it in range(params["train_steps"]):
             k = int(rng.integers(0, len(frames) - ms))
@@ -104,7 +112,7 @@ def main(argv=None):
             log.info("train step {:04d}: loss={}".format(it + 1, loss))
         if path:
             torch.save({"name": net.name, "weights": [torch.as_tensor(a) for a in net.get_weights()], "std_v": std_v,
-                        "std_re": max(params["re"], 1.0)}, path + "/model3d.pt")
+                        "std_re": max(params["re"], 1.0), "buoyancy": buoyancy}, path + "/model3d.pt")
     return path if path else loss
 
 

@@ -7,7 +7,7 @@ _bwd_large, sol_conv5x5 backward-data / -weight) under the AutogradCUDA key, so 
 dispatcher (torch.ops.sol.karman_step, .conv5x5, .burgers_step, .adam_tf_step; .karman_step_dens = karman_step with a differentiable
 density output, over sol_karman_density_bwd; .karman_step_re = karman_step differentiable with respect to re as well, over the _re
 adjoints; .karman_step_buoy = the large-grid step with the buoyancy force (fy, fx): the density pushes the velocity and is always in the
-graph).  Scene constants (masks, solver blobs, the cfg struct) are not tensors: they are registered once with register_scene() and
+graph; .karman3d_step_buoy = the same for the 3-D step, force (fy, fx, fz)).  Scene constants (masks, solver blobs, the cfg struct) are not tensors: they are registered once with register_scene() and
 referred to by an integer handle."""
 import torch
 
@@ -27,6 +27,7 @@ _LIB.define("conv5x5(Tensor x, Tensor w, Tensor b, Tensor? residual, bool lrelu,
 _LIB.define("karman3d_step(Tensor d, Tensor vy, Tensor vx, Tensor vz, Tensor re, int scene) -> (Tensor, Tensor, Tensor, Tensor)")
 _LIB.define("karman3d_step_dens(Tensor d, Tensor vy, Tensor vx, Tensor vz, Tensor re, int scene) -> (Tensor, Tensor, Tensor, Tensor)")
 _LIB.define("karman3d_step_re(Tensor d, Tensor vy, Tensor vx, Tensor vz, Tensor re, int scene, bool density=False) -> (Tensor, Tensor, Tensor, Tensor)")
+_LIB.define("karman3d_step_buoy(Tensor d, Tensor vy, Tensor vx, Tensor vz, Tensor re, int scene, float fy, float fx, float fz, bool re_grad=False) -> (Tensor, Tensor, Tensor, Tensor)")
 _LIB.define("karman3d_density_bwd(Tensor d, Tensor svy, Tensor svx, Tensor svz, Tensor re, Tensor gd, int scene) -> (Tensor, Tensor, Tensor, Tensor)")
 _LIB.define("conv3d(Tensor x, Tensor w, Tensor b, Tensor? residual, bool lrelu, float slope) -> Tensor")
 _LIB.define("burgers_step(Tensor vy, Tensor vx, Tensor? fy, Tensor? fx, float dx, float dt, float nu) -> (Tensor, Tensor)")
@@ -150,11 +151,26 @@ def _karman3d_fn(d, vy, vx, vz, re, scene, density, want_re):
     from . import karman3d as k3
     re = _lib.f32(re)
     want_re = want_re and torch.is_grad_enabled() and re.requires_grad
-    return k3._Karman3DStepFn.apply(_SIMS3D[scene], _lib.f32(d), _lib.f32(vy), _lib.f32(vx), _lib.f32(vz), re, density, want_re)
+    return k3._Karman3DStepFn.apply(_SIMS3D[scene], _lib.f32(d), _lib.f32(vy), _lib.f32(vx), _lib.f32(vz), re, density, want_re, None)
 
 
 def _karman3d_step(d, vy, vx, vz, re, scene):
     return _karman3d_fn(d, vy, vx, vz, re, scene, False, False)
+
+
+# karman3d_step_buoy: the buoyant mode of karman3d._Karman3DStepFn (a force of (0, 0, 0) is the plain step, density in the graph)
+def _karman3d_buoy(d, vy, vx, vz, re, scene, fy, fx, fz, re_grad=False):
+    with torch.no_grad():
+        return _SIMS3D[scene]._fwd(*(_lib.f32(t) for t in (d, vy, vx, vz, re)), buoyancy=(float(fy), float(fx), float(fz)))
+
+
+def _karman3d_buoy_fn(d, vy, vx, vz, re, scene, fy, fx, fz, re_grad=False):
+    from . import karman3d as k3
+    f = k3.buoyancy_force3d((fy, fx, fz))
+    re = _lib.f32(re)
+    want_re = bool(re_grad) and torch.is_grad_enabled() and re.requires_grad
+    return k3._Karman3DStepFn.apply(_SIMS3D[scene], _lib.f32(d), _lib.f32(vy), _lib.f32(vx), _lib.f32(vz), re, True, want_re,
+                                    f if k3._buoyant3d(f) else None)
 
 
 def _karman3d_density_bwd(d, svy, svx, svz, re, gd, scene):
@@ -170,5 +186,7 @@ def _conv3d(x, w, b, residual, lrelu, slope):
 _LIB.impl("karman3d_step", _karman3d_step, "AutogradCUDA")
 _LIB.impl("karman3d_step_dens", lambda d, vy, vx, vz, re, scene: _karman3d_fn(d, vy, vx, vz, re, scene, True, False), "AutogradCUDA")
 _LIB.impl("karman3d_step_re", lambda d, vy, vx, vz, re, scene, density=False: _karman3d_fn(d, vy, vx, vz, re, scene, bool(density), True), "AutogradCUDA")
+_LIB.impl("karman3d_step_buoy", _karman3d_buoy, "CUDA")
+_LIB.impl("karman3d_step_buoy", _karman3d_buoy_fn, "AutogradCUDA")
 _LIB.impl("karman3d_density_bwd", _karman3d_density_bwd, "CUDA")
 _LIB.impl("conv3d", _conv3d, "AutogradCUDA")
