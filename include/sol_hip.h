@@ -371,6 +371,31 @@ int sol_karman_buoyancy_add_bwd(void* stream, int32_t B, int32_t Y, int32_t X, c
                                 const float* g_vy, const float* g_vx, float fy_dt, float fx_dt,
                                 const float* g_d_out, float* g_dsum);
 
+/* DIFFUSION SUBSTEPS of the karman-2d step (csrc/karman_diffuse_sub.hip; diffusion_substeps = n on the Python surface, PhiFlow's
+ * diffuse(field, amount, substeps)).  The step diffuses the velocity with one explicit stencil v += alpha Lap(v), alpha = dt res^2 / Re,
+ * which is a convex combination only while alpha <= 1/4; beyond that it amplifies the checkerboard mode.  With n substeps the velocity is
+ * diffused n times by alpha / n and the boundary blend comes once, after the last one (the reference's order: diffuse, then blend,
+ * karman_train.py:177-181); the rest of the step is unchanged.  Write M = I + (alpha / n) L, L the 5-point Laplacian with replicate
+ * padding on each face grid.  Then
+ *     step_n(d, v; alpha) = step_1(d, M^(n-1) v; alpha / n)
+ * so no existing kernel, entry point or struct changes: the caller computes M^(n-1) v with the entry point below and runs the existing
+ * step on a copy of the cfg whose res is float32(res / sqrt(n)); the entry point forms its coefficient from the cfg it is given by the
+ * step's own expression, (dt * res * res) / re[b], so on that same copy all n substeps share one coefficient bit for bit.
+ * Adjoint: L is symmetric on both face grids, so M^(n-1) is its own transpose -- the existing adjoint on the scaled cfg yields the
+ * cotangent of M^(n-1) v and the same entry point applied to it yields the cotangent of v; no scatter, no atomics.  The density is not
+ * diffused.  Gradient in re: the factors commute, d(M^n v)/d alpha = L M^(n-1) v, so the existing re reduction on the scaled cfg, given
+ * M^(n-1) v as its input velocity, yields 1/n of the gradient: the caller multiplies by n.
+ *   sol_karman_diffuse_sub: vy_out, vx_out = (I + a_b L)^m (vy_in, vx_in), a_b = cfg.dt * cfg.res^2 / re[b], m >= 1; of the cfg only B,
+ *     Y, X, dt and res are read; Y, X >= 16.  chunk: substeps per launch, 1 .. sol_karman_diffuse_sub_max() (0 = that maximum); a launch
+ *     runs its substeps in LDS on tiles with a halo (temporal blocking).  Every substep is fmaf(a_b, lap, c) with lap summed in the
+ *     step's order, so the result does not depend on chunk: m launches of one substep and one launch of m substeps give equal bits.
+ *     More than one launch ping-pongs through `workspace` (sol_karman_diffuse_sub_workspace_bytes(cfg, m, chunk); 0 bytes and NULL for a
+ *     single launch).  The outputs must not alias the inputs.  Does not synchronise, allocate or read device memory on the host: capturable. */
+int32_t sol_karman_diffuse_sub_max(void);
+size_t sol_karman_diffuse_sub_workspace_bytes(const sol_karman_cfg* cfg, int32_t m, int32_t chunk);
+int sol_karman_diffuse_sub(const sol_karman_cfg* cfg, void* stream, const float* vy_in, const float* vx_in, const float* re,
+                           float* vy_out, float* vx_out, int32_t m, int32_t chunk, void* workspace, size_t workspace_bytes);
+
 /* active  [Y,X]  1 - obstacle mask (cell centres inside Obstacle geometries -> 0)
  * inflow  [Y,X]  inflow rate mask (Inflow(box[5:10,25:75]) -> 1 inside)
  * velBCy, velBCyMask  [Y+1,X] (bc_batch_stride 0) or [B,Y+1,X] (stride (Y+1)*X)

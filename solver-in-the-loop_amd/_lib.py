@@ -89,6 +89,9 @@ _SIGS = {
     "sol_karman_step_bwd_large_buoy_re": (C.c_int, [_P] * 7 + [C.c_int64] + [_P] * 9 + [C.c_size_t] + [_P] * 3 + [C.c_int] + [C.c_float] * 2 + [_P] * 2),
     "sol_karman_buoyancy_add": (C.c_int, [_P] + [C.c_int32] * 3 + [_P] * 2 + [C.c_float] * 2 + [_P] * 2),
     "sol_karman_buoyancy_add_bwd": (C.c_int, [_P] + [C.c_int32] * 3 + [_P] * 3 + [C.c_float] * 2 + [_P] * 2),
+    "sol_karman_diffuse_sub_max": (C.c_int32, []),
+    "sol_karman_diffuse_sub_workspace_bytes": (C.c_size_t, [_P, C.c_int32, C.c_int32]),
+    "sol_karman_diffuse_sub": (C.c_int, [_P] * 7 + [C.c_int32] * 2 + [_P, C.c_size_t]),
     "sol_karman_precond_supported": (C.c_int, [C.c_int32, C.c_int32]),
     "sol_karman_step_fwd": (C.c_int, [C.POINTER(KarmanCfg), _P] + [_P] * 8 + [C.c_int64] + [_P] * 6 + [C.POINTER(C.c_float), _P]),
     "sol_karman_step_bwd": (C.c_int, [C.POINTER(KarmanCfg), _P] + [_P] * 5 + [C.c_int64] + [_P] * 3 + [C.POINTER(C.c_float)] + [_P] * 3),

@@ -113,7 +113,12 @@ class KarmanFlow:
     def __init__(self, pressure_solver=None, make_input_divfree=False, make_output_divfree=True,
                  cg_rtol=1e-6, cg_atol=1e-9, cg_max_iter=2000, grad_pad="replicate", inflow_order="after",
                  obstacles=None, active=None, density_grad=False, re_grad=False, buoyancy=None, buoyancy_factor=None,
-                 gravity=(-9.81, 0.0)):
+                 gravity=(-9.81, 0.0), diffusion_substeps=1):
+        # diffusion_substeps=n (PhiFlow's diffuse(field, amount, substeps)): the velocity is diffused by n explicit substeps of alpha / n,
+        # alpha = dt res^2 / Re, the boundary blend after the last one.  The single stencil is stable only while alpha <= 1/4
+        # (ops.min_diffusion_substeps gives the n a run needs); grids with Y, X >= 16; composes with density_grad, re_grad and buoyancy.
+        # The default 1 issues the launches it always did.
+        self._nsub = ops.diffusion_substeps_arg(diffusion_substeps, "KarmanFlow: diffusion_substeps")
         # buoyancy=(fy, fx), a force per unit density, or PhiFlow's spelling buoyancy_factor=beta with gravity=(gy, gx): F = -gravity * beta
         # (ops.buoyancy_force).  The step's output density pushes the velocity; large grids only (step() raises SolError on a grid the
         # one-workgroup kernels serve).  The default is off: the density is a passive tracer and every launch is what it was.
@@ -239,9 +244,10 @@ class KarmanFlow:
             if getattr(self, "_large_ws", None) is None or self._large_ws[0] != (B, Y, X, str(dev)) or self._large_ws[1].numel() * 4 < n:
                 self._large_ws = ((B, Y, X, str(dev)), torch.empty((n + 3) // 4, dtype=torch.float32, device=dev))
             d2, vy2, vx2 = ops.karman_step_large(d, vy, vx, re_t, cfg, masks, self._large_ws[1], info, density_grad=self._density_grad,
-                                                 re_grad=self._re_grad, buoyancy=self._buoyancy)
+                                                 re_grad=self._re_grad, buoyancy=self._buoyancy, diffusion_substeps=self._nsub)
         else:
-            d2, vy2, vx2 = ops.karman_step(d, vy, vx, re_t, cfg, masks, info, density_grad=self._density_grad, re_grad=self._re_grad)
+            d2, vy2, vx2 = ops.karman_step(d, vy, vx, re_t, cfg, masks, info, density_grad=self._density_grad, re_grad=self._re_grad,
+                                           diffusion_substeps=self._nsub)
         self.solve_info = info
         return smoke.copied_with(density=d2.reshape(B, Y, X, 1),
                                  velocity=StaggeredGrid([vy2.reshape(B, Y + 1, X, 1), vx2.reshape(B, Y, X + 1, 1)],

@@ -194,11 +194,111 @@ def _require_large_for_buoyancy(masks, Y, X, who):
                        "one-workgroup kernels (not ops.beyond_one_workgroup), which have no buoyancy term" % (who, Y, X))
 
 
-def karman_step_saved(d, vy, vx, re, cfg, masks, workspace=None, info=None, buoyancy=None):
+# --------------------------------------------------------------------------------------
+# diffusion substeps (include/sol_hip.h, "DIFFUSION SUBSTEPS"; csrc/karman_diffuse_sub.hip)
+# --------------------------------------------------------------------------------------
+def diffusion_substeps_arg(n, who="diffusion_substeps"):
+    """n as an int >= 1; anything else (a float, a bool, None, n < 1) raises ValueError"""
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)):
+        raise ValueError("%s must be an integer >= 1 (got %r)" % (who, n))
+    if n < 1:
+        raise ValueError("%s must be an integer >= 1 (got %d)" % (who, n))
+    return int(n)
+
+
+def min_diffusion_substeps(re_min, res, dt=1.0):
+    """The smallest n with dt res^2 / (n re_min) <= 1/4: the explicit diffusion stencil v += a Lap(v) is a convex combination of a face
+    and its four neighbours exactly while a <= 1/4; beyond it the checkerboard mode grows.  re_min: the smallest Reynolds number of the
+    run."""
+    re_min, res, dt = float(re_min), float(res), float(dt)
+    if not (re_min > 0 and res > 0 and dt > 0) or not np.isfinite(dt * res * res / re_min):
+        raise ValueError("min_diffusion_substeps: re_min, res and dt must be positive and finite (got %r, %r, %r)" % (re_min, res, dt))
+    alpha = dt * res * res / re_min
+    n = max(1, int(np.ceil(4.0 * alpha)))
+    while alpha / n > 0.25:
+        n += 1
+    while n > 1 and alpha / (n - 1) <= 0.25:
+        n -= 1
+    return n
+
+
+def diffusion_sub_cfg(cfg, n):
+    """The cfg the existing step, its adjoints and the pre-diffusion run on under diffusion_substeps = n: a copy whose res is
+    float32(res / sqrt(n)), so that their own expression dt * res * res / re[b] is the substep's coefficient; n = 1: cfg itself."""
+    if n == 1:
+        return cfg
+    c = KarmanCfg.from_buffer_copy(cfg)
+    c.res = float(np.float32(float(cfg.res) / np.sqrt(float(n))))
+    c._keep = getattr(cfg, "_keep", None)
+    return c
+
+
+def _require_sub_grid(cfg, who):
+    if cfg.Y < 16 or cfg.X < 16:
+        raise SolError("%s: diffusion substeps (sol_karman_diffuse_sub) take grids with Y, X >= 16; this one is %dx%d" % (who, cfg.Y, cfg.X))
+
+
+def diffuse_sub_max():
+    """S_MAX: the most substeps one launch of sol_karman_diffuse_sub runs"""
+    return int(_lib.load().sol_karman_diffuse_sub_max())
+
+
+def diffuse_sub_workspace_bytes(cfg, nsub, chunk=None):
+    """Device scratch of karman_diffuse_sub(.., cfg, nsub, chunk): 0 when its nsub - 1 substeps fit one launch"""
+    if nsub <= 1:
+        return 0
+    return _lib.load().sol_karman_diffuse_sub_workspace_bytes(C.byref(cfg), nsub - 1, 0 if chunk is None else int(chunk))
+
+
+def karman_diffuse_sub(vy, vx, re, cfg, nsub, chunk=None, workspace=None):
+    """The pre-diffusion of a step with diffusion_substeps = nsub (sol_karman_diffuse_sub): (vy, vx) -> M^(nsub-1) (vy, vx), M = I +
+    (alpha / nsub) L with alpha = dt res^2 / re of `cfg` (the step's own, unscaled cfg) and L the 5-point Laplacian with replicate padding.
+    M^(nsub-1) is symmetric: applied to a cotangent this is also the adjoint.  chunk: the most substeps per launch, 1 .. diffuse_sub_max()
+    (None = that maximum, the measured default: profiles/k2d_substeps_time.json); the bits do not depend on it.  nsub = 1: no launch, the inputs are returned."""
+    n = diffusion_substeps_arg(nsub, "karman_diffuse_sub: nsub")
+    if chunk is not None and (isinstance(chunk, bool) or not isinstance(chunk, (int, np.integer)) or not 1 <= chunk <= diffuse_sub_max()):
+        raise ValueError("karman_diffuse_sub: chunk must be None or an integer in [1, %d] (got %r)" % (diffuse_sub_max(), chunk))
+    _lib.require_gpu()
+    vy, vx, re = (_lib.f32(t) for t in (vy, vx, re))
+    if n == 1:
+        return vy, vx
+    _require_sub_grid(cfg, "karman_diffuse_sub")
+    B, Y, X = cfg.B, cfg.Y, cfg.X
+    if vy.shape != (B, Y + 1, X) or vx.shape != (B, Y, X + 1) or re.shape != (B,):
+        raise ValueError("karman_diffuse_sub: vy %s, vx %s, re %s are not [B,Y+1,X], [B,Y,X+1], [B] of the cfg (B, Y, X) = (%d, %d, %d)"
+                         % (tuple(vy.shape), tuple(vx.shape), tuple(re.shape), B, Y, X))
+    sc = diffusion_sub_cfg(cfg, n)
+    nbytes = diffuse_sub_workspace_bytes(sc, n, chunk)
+    ws = _workspace(nbytes, workspace, vy.device) if nbytes else None
+    oy, ox = torch.empty_like(vy), torch.empty_like(vx)
+    check(_lib.load().sol_karman_diffuse_sub(C.byref(sc), stream(), ptr(vy), ptr(vx), ptr(re), ptr(oy), ptr(ox), n - 1,
+                                             0 if chunk is None else int(chunk), ptr(ws), 0 if ws is None else ws.numel() * 4))
+    return oy, ox
+
+
+def _sub_adjoint(oy, ox, g_re, re, cfg, nsub):
+    """The tail of an adjoint under diffusion_substeps = nsub: (oy, ox) and g_re (any of them None) are what the existing adjoints
+    returned on diffusion_sub_cfg(cfg, nsub) -- the cotangent of M^(nsub-1) v and 1/nsub of the gradient in re.  -> (g_vy, g_vx, g_re):
+    the cotangent taken through M^(nsub-1) (karman_diffuse_sub: the operator is symmetric) and g_re times nsub (one fp32 multiply)."""
+    if nsub > 1:
+        if oy is not None:
+            oy, ox = karman_diffuse_sub(oy, ox, re, cfg, nsub)
+        if g_re is not None:
+            g_re = g_re * float(nsub)
+    return oy, ox, g_re
+
+
+def karman_step_saved(d, vy, vx, re, cfg, masks, workspace=None, info=None, buoyancy=None, diffusion_substeps=1):
     """The differentiable form of the step without autograd, on any grid: ((d, vy, vx) after the step, saved vy, saved vx) -- the
     post-diffusion velocity the adjoints take.  A one-workgroup grid runs sol_karman_step_fwd (`info` receives "iterations"), a grid
     beyond them (masks.large) sol_karman_step_fwd_large_saved with `workspace` and `info` as in karman_step_large.
-    buoyancy = (fy, fx) (large grids only): sol_karman_step_fwd_large_saved_buoy, the density pushes the velocity."""
+    buoyancy = (fy, fx) (large grids only): sol_karman_step_fwd_large_saved_buoy, the density pushes the velocity.
+    diffusion_substeps = n > 1 (grids with Y, X >= 16): karman_diffuse_sub, then the same launches on diffusion_sub_cfg(cfg, n)."""
+    n = diffusion_substeps_arg(diffusion_substeps)
+    if n > 1:
+        _require_sub_grid(cfg, "karman_step_saved")
+        pvy, pvx = karman_diffuse_sub(vy, vx, re, cfg, n)
+        return karman_step_saved(d, pvy, pvx, re, diffusion_sub_cfg(cfg, n), masks, workspace, info, buoyancy)
     if buoyancy is not None:
         _require_large_for_buoyancy(masks, cfg.Y, cfg.X, "karman_step_saved")
     _lib.require_gpu()
@@ -227,7 +327,7 @@ karman_step_large_saved = karman_step_saved      # the name the large-grid calle
 
 
 def karman_step_large(d, vy, vx, re, cfg, masks, workspace=None, info=None, feat=None, feat_scale=None, p_guess=None, out=None,
-                      density_grad=False, re_grad=False, buoyancy=None):
+                      density_grad=False, re_grad=False, buoyancy=None, diffusion_substeps=1):
     """The step for grids beyond the one-workgroup kernels (data generation at 256 x 128,
     /root/reference/karman-2d/karman.py:98-159): sol_karman_step_fwd_large (direct solve) or sol_karman_step_fwd_large_cg (CG solve,
     masks.pressure_solver == "cg").  Returns (d, vy, vx) after the step; with the CG solve, `info` (a dict) receives "iterations" and
@@ -244,7 +344,13 @@ def karman_step_large(d, vy, vx, re, cfg, masks, workspace=None, info=None, feat
     input velocity saved as well; composes with density_grad).  Without the flag `re` is data.
     buoyancy = (fy, fx) (see buoyancy_force): the step's output density pushes the velocity (sol_karman_step_fwd_large_buoy, one launch
     more; every no-grad extra above still applies).  With a non-zero force the density is part of the dynamics: the differentiable form
-    keeps it in the graph as density_grad would (KarmanStepFn's buoyant mode)."""
+    keeps it in the graph as density_grad would (KarmanStepFn's buoyant mode).
+    diffusion_substeps = n > 1: the velocity is diffused by n explicit substeps of alpha / n, the boundary blend after the last one
+    (karman_diffuse_sub, one launch per diffuse_sub_max() substeps, then the launches above on diffusion_sub_cfg(cfg, n)); composes with
+    every mode and extra above.  n = 1 issues the launches and gives the bits of a call without the keyword."""
+    nsub = diffusion_substeps_arg(diffusion_substeps)
+    if nsub > 1:
+        _require_sub_grid(cfg, "karman_step_large")
     if buoyancy is not None:
         _require_large_for_buoyancy(masks, cfg.Y, cfg.X, "karman_step_large")
     if p_guess is not None and masks.direct is not None:
@@ -258,7 +364,11 @@ def karman_step_large(d, vy, vx, re, cfg, masks, workspace=None, info=None, feat
     if differentiable:
         if feat is not None or p_guess is not None or out is not None:
             raise ValueError("karman_step_large: feat / p_guess / out belong to the no-grad step (the differentiable step keeps its own state)")
-        return KarmanStepFn.apply(d, vy, vx, re, cfg, masks, workspace, info, density, want_re, buoyancy if _buoyant(buoyancy) else None)
+        return KarmanStepFn.apply(d, vy, vx, re, cfg, masks, workspace, info, density, want_re, buoyancy if _buoyant(buoyancy) else None, nsub)
+    if nsub > 1:
+        pvy, pvx = karman_diffuse_sub(vy, vx, re, cfg, nsub)
+        return karman_step_large(d, pvy, pvx, re, diffusion_sub_cfg(cfg, nsub), masks, workspace, info, feat, feat_scale, p_guess, out,
+                                 buoyancy=buoyancy)
     if (feat is None) != (feat_scale is None):
         raise ValueError("karman_step_large: feat and feat_scale go together")
     if feat is not None and (feat.shape != (B, Y, X, 4) or feat.device != vy.device):
@@ -410,18 +520,28 @@ def _large_bwd(who, svy, svx, re, gvy, gvx, cfg, masks, workspace, info, re_in=N
     return (oy, ox) if re_in is None else (oy, ox, g_re)
 
 
-def karman_step_large_bwd(svy, svx, re, gvy, gvx, cfg, masks, workspace=None, info=None):
+def karman_step_large_bwd(svy, svx, re, gvy, gvx, cfg, masks, workspace=None, info=None, diffusion_substeps=1):
     """Adjoint of the large-grid step (sol_karman_step_bwd_large): (g_vy_in, g_vx_in) from the saved post-diffusion velocity and the
-    gradient with respect to the step's output velocity.  With the CG solve, `info` receives "iterations_bwd" / "converged_bwd"."""
-    return _large_bwd("karman_step_large_bwd", svy, svx, re, gvy, gvx, cfg, masks, workspace, info)
+    gradient with respect to the step's output velocity.  With the CG solve, `info` receives "iterations_bwd" / "converged_bwd".
+    diffusion_substeps = n: the adjoint of karman_step_saved(.., diffusion_substeps=n) -- the same launches on diffusion_sub_cfg(cfg, n),
+    then karman_diffuse_sub on their result (`cfg` is the step's own, unscaled one)."""
+    n = diffusion_substeps_arg(diffusion_substeps)
+    oy, ox = _large_bwd("karman_step_large_bwd", svy, svx, re, gvy, gvx, diffusion_sub_cfg(cfg, n), masks, workspace, info)
+    return _sub_adjoint(oy, ox, None, re, cfg, n)[:2]
 
 
-def karman_step_large_bwd_re(svy, svx, re, gvy, gvx, vy_in, vx_in, cfg, masks, g_re=None, workspace=None, info=None):
+def karman_step_large_bwd_re(svy, svx, re, gvy, gvx, vy_in, vx_in, cfg, masks, g_re=None, workspace=None, info=None, diffusion_substeps=1):
     """The staged velocity adjoint with the gradient with respect to re (sol_karman_step_bwd_large_re), on every grid with Y, X >= 16 --
     the one-workgroup grids included: (g_vy_in, g_vx_in, g_re) from the saved post-diffusion velocity, the cotangent of the step's output
     velocity and the step's INPUT velocity.  g_vy_in / g_vx_in are karman_step_large_bwd's bits.  g_re [B]: a buffer to add onto (one
-    fp32 add), else a fresh one is written."""
-    return _large_bwd("karman_step_large_bwd_re", svy, svx, re, gvy, gvx, cfg, masks, workspace, info, (vy_in, vx_in, g_re))
+    fp32 add), else a fresh one is written.
+    diffusion_substeps = n > 1: as in karman_step_large_bwd; vy_in / vx_in are then the PRE-DIFFUSED input, karman_diffuse_sub(vy, vx, re,
+    cfg, n), and the reduction's result is multiplied by n (a g_re to add onto is not taken: it would be scaled too)."""
+    n = diffusion_substeps_arg(diffusion_substeps)
+    if n > 1 and g_re is not None:
+        raise ValueError("karman_step_large_bwd_re: with diffusion_substeps > 1 the gradient in re is written to a fresh tensor (g_re=None)")
+    oy, ox, g = _large_bwd("karman_step_large_bwd_re", svy, svx, re, gvy, gvx, diffusion_sub_cfg(cfg, n), masks, workspace, info, (vy_in, vx_in, g_re))
+    return _sub_adjoint(oy, ox, g, re, cfg, n)
 
 
 def _density_bwd(who, d, svy, svx, re, g_d, cfg, masks, g_vy, g_vx, workspace, re_in=None):
@@ -491,13 +611,25 @@ def karman_buoyancy_add_bwd(gvy, gvx, active, f, gd=None):
 
 
 def karman_step_large_bwd_buoy(d, svy, svx, re, gvy, gvx, gd, cfg, masks, buoyancy, vel_in=None, workspace=None, info=None,
-                               density_workspace=None):
+                               density_workspace=None, diffusion_substeps=1):
     """Adjoint of the BUOYANT large-grid step (karman_step_saved(..., buoyancy=F)): (g_d_in, g_vy_in, g_vx_in) -- with vel_in = (vy, vx),
     the step's input velocity, (g_d_in, g_vy_in, g_vx_in, g_re) -- from the step's input density `d`, the saved post-diffusion velocity and
     the cotangents gvy, gvx, gd of its outputs (None = zero).  With a velocity cotangent: sol_karman_step_bwd_large_buoy(_re) (the plain
     velocity adjoint's launches, then g_dsum = gd + dt F . transpose of the face average of g_a), then the density adjoint on g_dsum,
     added onto the velocity adjoint's result.  Without one (a density-only loss) no pressure solve runs: the density adjoint on gd alone.
-    No cotangent at all: every result is None.  workspace / density_workspace: scratch of the velocity / the density adjoint."""
+    No cotangent at all: every result is None.  workspace / density_workspace: scratch of the velocity / the density adjoint.
+    diffusion_substeps = n > 1: the same launches on diffusion_sub_cfg(cfg, n) (vel_in is then the PRE-DIFFUSED input velocity,
+    karman_diffuse_sub(vy, vx, re, cfg, n)), then karman_diffuse_sub on the velocity cotangent and g_re times n."""
+    n = diffusion_substeps_arg(diffusion_substeps)
+    res = _large_bwd_buoy(d, svy, svx, re, gvy, gvx, gd, diffusion_sub_cfg(cfg, n), masks, buoyancy, vel_in, workspace, info, density_workspace)
+    if n == 1:
+        return res
+    oy, ox, g_re = _sub_adjoint(res[1], res[2], res[3] if vel_in is not None else None, re, cfg, n)
+    return (res[0], oy, ox) if vel_in is None else (res[0], oy, ox, g_re)
+
+
+def _large_bwd_buoy(d, svy, svx, re, gvy, gvx, gd, cfg, masks, buoyancy, vel_in, workspace, info, density_workspace):
+    """the launches of karman_step_large_bwd_buoy on the cfg as given"""
     _require_large_for_buoyancy(masks, cfg.Y, cfg.X, "karman_step_large_bwd_buoy")
     who = "karman_step_large_bwd_buoy"
     if gvy is None and gvx is None and gd is None:
@@ -554,13 +686,22 @@ class KarmanStepFn(torch.autograd.Function):
     velocity half (with its pressure solve) runs only when a velocity cotangent arrived, the density half only when a density cotangent
     did.  `buoyancy` = (fy, fx), a non-zero force (large grids; else None): the buoyant step -- the density is part of the dynamics, so
     it is in the graph whatever `density` says; a velocity-only loss yields a density gradient too (karman_step_large_bwd_buoy), a
-    density-only loss still runs no pressure solve."""
+    density-only loss still runs no pressure solve.  `nsub` (diffusion_substeps = n > 1; grids with Y, X >= 16): n explicit diffusion
+    substeps -- karman_diffuse_sub before the forward launches, and on the velocity cotangent after the backward ones, both on the scaled
+    cfg (diffusion_sub_cfg); g_re times n.  Composes with every other mode; nsub = 1 launches nothing new."""
 
     @staticmethod
-    def forward(ctx, d, vy, vx, re, cfg, masks, workspace, info, density, want_re, buoyancy=None):
+    def forward(ctx, d, vy, vx, re, cfg, masks, workspace, info, density, want_re, buoyancy=None, nsub=1):
         _lib.require_gpu()
         d, vy, vx, re = (_lib.f32(t) for t in (d, vy, vx, re))
         density = bool(density) or buoyancy is not None
+        # diffusion substeps (nsub > 1; one more mode, composing with the others): the existing launches on the scaled cfg, applied to the
+        # pre-diffused velocity M^(nsub-1) v -- which is also the "input velocity" the re mode saves; backward ends with _sub_adjoint
+        ctx.cfg_full, ctx.nsub = cfg, nsub
+        if nsub > 1:
+            _require_sub_grid(cfg, "diffusion_substeps")
+            vy, vx = karman_diffuse_sub(vy, vx, re, cfg, nsub)
+            cfg = diffusion_sub_cfg(cfg, nsub)
         outs, svy, svx = karman_step_saved(d, vy, vx, re, cfg, masks, workspace, info, buoyancy)
         ctx.save_for_backward(svy, svx, re, *((d, vy, vx) if want_re else (d,) if density else ()))
         ctx.cfg, ctx.masks, ctx.info, ctx.density, ctx.want_re, ctx.buoyancy = cfg, masks, info, density, want_re, buoyancy
@@ -577,8 +718,9 @@ class KarmanStepFn(torch.autograd.Function):
         od = oy = ox = g_re = None
         if ctx.buoyancy is not None:
             gvy, gvx, gd = (None if g is None else g.contiguous() for g in (gvy, gvx, gd))
-            res = karman_step_large_bwd_buoy(inputs[0], svy, svx, re, gvy, gvx, gd, cfg, masks, ctx.buoyancy, vel_in, info=ctx.info)
-            return res[0], res[1], res[2], (res[3] if vel_in is not None else None), None, None, None, None, None, None, None
+            res = _large_bwd_buoy(inputs[0], svy, svx, re, gvy, gvx, gd, cfg, masks, ctx.buoyancy, vel_in, None, ctx.info, None)
+            oy, ox, g_re = _sub_adjoint(res[1], res[2], res[3] if vel_in is not None else None, re, ctx.cfg_full, ctx.nsub)
+            return res[0], oy, ox, g_re, None, None, None, None, None, None, None, None
         if gvy is not None or gvx is not None:
             oy, ox, g_re = _velocity_bwd(svy, svx, re, gvy, gvx, cfg, masks, ctx.info, vel_in)
         if ctx.density and gd is not None:        # added onto the velocity half's buffers and g_re
@@ -586,7 +728,8 @@ class KarmanStepFn(torch.autograd.Function):
                 od, oy, ox = karman_density_bwd(inputs[0], svy, svx, re, gd, cfg, masks, oy, ox)
             else:
                 od, oy, ox, g_re = karman_density_bwd_re(inputs[0], svy, svx, re, gd, *vel_in, cfg, masks, oy, ox, g_re)
-        return od, oy, ox, g_re, None, None, None, None, None, None, None
+        oy, ox, g_re = _sub_adjoint(oy, ox, g_re, re, ctx.cfg_full, ctx.nsub)
+        return od, oy, ox, g_re, None, None, None, None, None, None, None, None
 
 
 def _step_mode(d, vy, vx, re, cfg, density_grad, re_grad, buoyancy=None):
@@ -601,16 +744,20 @@ def _step_mode(d, vy, vx, re, cfg, density_grad, re_grad, buoyancy=None):
     return torch.is_grad_enabled() and (needs(vy) or needs(vx) or (density and needs(d)) or want_re), density, want_re
 
 
-def karman_step(d, vy, vx, re, cfg, masks, info=None, density_grad=False, re_grad=False):
+def karman_step(d, vy, vx, re, cfg, masks, info=None, density_grad=False, re_grad=False, diffusion_substeps=1):
     """One step on a one-workgroup grid.  density_grad=True (opt-in): the density output is differentiable too (KarmanStepFn's density
     mode), taken when any of d, vy, vx requires a gradient.  re_grad=True (opt-in): a tensor `re` that requires a gradient receives one
-    (KarmanStepFn's re mode; grids with Y, X >= 16; composes with density_grad).  Without the flag `re` is data."""
+    (KarmanStepFn's re mode; grids with Y, X >= 16; composes with density_grad).  Without the flag `re` is data.
+    diffusion_substeps = n > 1 (grids with Y, X >= 16): karman_diffuse_sub, then the fused kernel on diffusion_sub_cfg(cfg, n)."""
+    nsub = diffusion_substeps_arg(diffusion_substeps)
+    if nsub > 1:
+        _require_sub_grid(cfg, "karman_step")
     differentiable, density, want_re = _step_mode(d, vy, vx, re, cfg, density_grad, re_grad)
     if not differentiable:
-        return karman_step_saved(d, vy, vx, re, cfg, masks, None, info)[0]
+        return karman_step_saved(d, vy, vx, re, cfg, masks, None, info, diffusion_substeps=nsub)[0]
     _lib.require_gpu()
     d, vy, vx, re = (_lib.f32(t) for t in (d, vy, vx, re))
-    return KarmanStepFn.apply(d, vy, vx, re, cfg, masks, None, info, density, want_re)
+    return KarmanStepFn.apply(d, vy, vx, re, cfg, masks, None, info, density, want_re, None, nsub)
 
 
 # --------------------------------------------------------------------------------------

@@ -82,6 +82,40 @@ def agreed_buoyancy(recorded, flag, where):
     return norm(recorded)
 
 
+def add_substeps_arg(p, auto=True):
+    """--diffusion-substeps N|auto of karman.py (auto: the smallest stable count for the run's Reynolds numbers); the scripts that read
+    data take N only and default to what the data recorded"""
+    p.add_argument("--diffusion-substeps", default=None, metavar="N|auto" if auto else "N",
+                   help="explicit diffusion substeps per solver step (the single stencil is stable only while dt res^2 / Re <= 1/4)%s.  "
+                        "Stored with the data like the scene; absent: %s"
+                        % ("; auto: the smallest stable count (min_diffusion_substeps) for the run's Reynolds numbers" if auto else "",
+                           "1" if auto else "what the data recorded"))
+
+
+def substeps_from_args(params, re_numbers=None, res=None, dt=1.0):
+    """n of --diffusion-substeps: an integer >= 1, `auto` (re_numbers given: ops.min_diffusion_substeps over them), or None when absent"""
+    from sol_amd import ops
+    v = params.get("diffusion_substeps")
+    if v is None:
+        return None
+    if str(v).strip().lower() == "auto":
+        if re_numbers is None:
+            raise SystemExit("--diffusion-substeps auto belongs to data generation; this script takes the count from the data (or N)")
+        return ops.min_diffusion_substeps(min(float(r) for r in re_numbers), res, dt)
+    try:
+        return ops.diffusion_substeps_arg(int(str(v)), "--diffusion-substeps")
+    except ValueError:
+        raise SystemExit("bad --diffusion-substeps %r: expected an integer >= 1%s" % (v, " or 'auto'" if re_numbers is not None else ""))
+
+
+def agreed_substeps(recorded, flag, where):
+    """The substep count of a run that reads data: what the data recorded (None / absent: 1), unless the flag says otherwise -- a contradiction."""
+    rec = 1 if recorded is None else int(recorded)
+    if flag is not None and int(flag) != rec:
+        raise SystemExit("--diffusion-substeps %s contradicts the count recorded in %s (%s)" % (flag, where, rec))
+    return rec
+
+
 def flow_kwargs(rec):
     """KarmanFlow / GraphTrainer keywords of a scene_record (None: the default scene)."""
     from sol_amd import karman

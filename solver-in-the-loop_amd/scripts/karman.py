@@ -5,14 +5,16 @@
 reference solutions, Makefile:19-28) run the multi-launch path (nothing is kept for a backward pass here): the direct pressure solver where the scene's blob builds,
 else the preconditioned CG.  --obstacle / --obstacle-mask choose the scene (recorded in params.pickle as "scene").  --buoyancy FY[,FX]
 (large grids only): the density pushes the velocity; recorded in params.pickle as "buoyancy" (a pair, or None: off), so that training and
-roll-out pick it up from the data."""
+roll-out pick it up from the data.  --diffusion-substeps N|auto: explicit diffusion substeps per step (auto: the smallest count for which
+dt res^2 / (n Re) <= 1/4, ops.min_diffusion_substeps); recorded in params.pickle as "diffusion_substeps" (an integer, 1: the single stencil)."""
 import argparse
 import pickle
 
 import numpy as np
 import torch
 
-from _common import add_buoyancy_arg, add_scene_args, buoyancy_from_args, flow_kwargs, logger, scene_from_args, select_gpu
+from _common import (add_buoyancy_arg, add_scene_args, add_substeps_arg, buoyancy_from_args, flow_kwargs, logger, scene_from_args, select_gpu,
+                     substeps_from_args)
 import sol_amd
 from sol_amd import ops, scene
 
@@ -34,6 +36,7 @@ def main(argv=None):
     p.add_argument("--seed", default=0, type=int, help="seed for random number generator")
     add_scene_args(p)
     add_buoyancy_arg(p)
+    add_substeps_arg(p)
     params = vars(p.parse_args(argv))
     select_gpu(params["gpu"])
     log = logger()
@@ -42,7 +45,9 @@ def main(argv=None):
     dom = sol_amd.Domain([Y, X], box=sol_amd.box[0:params["len"] * 2, 0:params["len"]])
     rec = scene_from_args(params)
     params["buoyancy"] = buoyancy_from_args(params)
-    sim = sol_amd.KarmanFlow(pressure_solver=params["pressure_solver"], buoyancy=params["buoyancy"], **flow_kwargs(rec))
+    params["diffusion_substeps"] = substeps_from_args(params, [params["re"]], res) or 1
+    sim = sol_amd.KarmanFlow(pressure_solver=params["pressure_solver"], buoyancy=params["buoyancy"],
+                             diffusion_substeps=params["diffusion_substeps"], **flow_kwargs(rec))
     params["scene"] = sim.scene()
     d0 = scene.downsample(scene.read_zipped_array(params["initdH"]), params["scale"]) if params["initdH"] else np.zeros((1, Y, X, 1))
     if params["initvH"]:

@@ -9,7 +9,8 @@ import pickle
 import numpy as np
 import torch
 
-from _common import add_buoyancy_arg, add_scene_args, agreed_buoyancy, buoyancy_from_args, flow_kwargs, logger, scene_from_args, select_gpu
+from _common import (add_buoyancy_arg, add_scene_args, add_substeps_arg, agreed_buoyancy, agreed_substeps, buoyancy_from_args, flow_kwargs, logger,
+                     scene_from_args, select_gpu, substeps_from_args)
 import sol_amd
 from sol_amd import ops, scene
 
@@ -30,6 +31,7 @@ def main(argv=None):
     p.add_argument("--any-width", action="store_true", help="run the correction network on rows of any width (pitched rows with column-masked convolutions) instead of refusing a width the convolutions do not take")
     add_scene_args(p, warm_start=True)
     add_buoyancy_arg(p)
+    add_substeps_arg(p, auto=False)
     params = vars(p.parse_args(argv))
     select_gpu(params["gpu"])
     log = logger()
@@ -65,6 +67,10 @@ def main(argv=None):
     buoyancy = agreed_buoyancy(data_stats["buoyancy"], buoyancy_from_args(params), params["stats"]) if "buoyancy" in data_stats \
         else buoyancy_from_args(params)
     log.info("buoyancy: %s" % (buoyancy,))
+    # the diffusion substeps likewise (dataStats "diffusion_substeps"; stats without the record take the flag, else 1)
+    nsub = agreed_substeps(data_stats["diffusion_substeps"], substeps_from_args(params), params["stats"]) if "diffusion_substeps" in data_stats \
+        else (substeps_from_args(params) or 1)
+    log.info("diffusion substeps: %d" % nsub)
     active, inflow = sim.scene_arrays(dom)
     velBCy, velBCyMask = sol_amd.velocity_bc_masks(Y, X)
     masks = ops.SceneMasks(active, inflow, velBCy.reshape(Y + 1, X), velBCyMask.reshape(Y + 1, X),
@@ -78,7 +84,7 @@ def main(argv=None):
     # (a CG scene runs eagerly, every solve stops at convergence; a direct-solve scene replays one captured step)
     ro = sol_amd.make_rollout(model, masks, 1, Y, X, dom.dx[1], data_stats["std"][1], data_stats["ext.std"][0],
                               use_graph=ops.is_direct(masks.pressure_solver), cg_warm_start=warm, any_width=params["any_width"],
-                              buoyancy=buoyancy)
+                              buoyancy=buoyancy, diffusion_substeps=nsub)
     f = lambda a: torch.as_tensor(np.ascontiguousarray(a), dtype=torch.float32, device="cuda").contiguous()
     vy0, vx0 = scene.split_staggered(np.asarray(vn, dtype=np.float32))
     d, vy, vx = f(np.asarray(d0)[..., 0]), f(vy0), f(vx0)

@@ -64,7 +64,7 @@ def flow_stepper(sim, dom, B, Y, X, res):
 
 
 def main(argv=None):
-    from _common import add_scene_args, flow_kwargs, logger, scene_from_args, select_gpu
+    from _common import add_scene_args, add_substeps_arg, agreed_substeps, flow_kwargs, logger, scene_from_args, select_gpu, substeps_from_args
     import sol_amd
     from sol_amd import scene, synthetic
     p = argparse.ArgumentParser(description="Parameter Parser", formatter_class=argparse.ArgumentDefaultsHelpFormatter)
@@ -81,6 +81,7 @@ def main(argv=None):
     p.add_argument("--seed", default=11, type=int, help="--synthetic: seed of the initial state")
     p.add_argument("-o", "--output", default=None, help="directory for re_fit.json (default: --input, or the current directory)")
     add_scene_args(p)
+    add_substeps_arg(p, auto=False)
     params = vars(p.parse_args(argv))
     if (params["input"] is None) == (not params["synthetic"]):
         raise SystemExit("give --input DIR or --synthetic")
@@ -96,11 +97,13 @@ def main(argv=None):
         Y, X = 2 * res, res
         re_true = synthetic.reynolds(B).tolist()
         first = tuple(f(t) for t in synthetic.state(B, Y, X, params["seed"]))
+        nsub = substeps_from_args(params) or 1
     else:
         with open(os.path.join(params["input"], "params.pickle"), "rb") as fh:
             meta = pickle.load(fh)
         res, length, B = meta["res"], meta.get("len", 100), 1
         rec = rec if rec is not None else meta.get("scene")
+        nsub = agreed_substeps(meta.get("diffusion_substeps"), substeps_from_args(params), "params.pickle")      # the count the frames were generated with
         names = sorted(n for n in os.listdir(params["input"]) if n.startswith("velo_") and n.endswith(".npz"))
         start = int(names[0][5:11]) if params["start"] is None else params["start"]
         re_true = [float(meta["re"])]
@@ -113,7 +116,7 @@ def main(argv=None):
             vy, vx = scene.split_staggered(v)
             loaded.append((f(d), f(vy), f(vx)))
     dom = sol_amd.Domain([Y, X], box=sol_amd.box[0:length * 2, 0:length])
-    sim = sol_amd.KarmanFlow(pressure_solver=params["pressure_solver"], re_grad=True, **flow_kwargs(rec))
+    sim = sol_amd.KarmanFlow(pressure_solver=params["pressure_solver"], re_grad=True, diffusion_substeps=nsub, **flow_kwargs(rec))
     step = flow_stepper(sim, dom, B, Y, X, res)
     if params["synthetic"]:
         loaded = [first]
@@ -121,7 +124,7 @@ def main(argv=None):
             for _ in range(K - 1):
                 loaded.append(step(*loaded[-1], f(re_true)))
     re0 = [params["re0"]] * B if params["re0"] else [4.0 * r for r in re_true]
-    log.info("%dx%d, B = %d, %d frames, pressure solver %s, start Re %s" % (Y, X, B, K, params["pressure_solver"], re0))
+    log.info("%dx%d, B = %d, %d frames, pressure solver %s, diffusion substeps %d, start Re %s" % (Y, X, B, K, params["pressure_solver"], nsub, re0))
     re_fit, history = fit_re(step, loaded, re0, params["iters"], params["lr"], log.info)
     result = {"grid": [Y, X], "frames": K, "iters": params["iters"], "lr": params["lr"], "re_start": re0, "re_fit": re_fit.cpu().tolist(),
               "re_recorded": re_true, "log_ratio": [math.log(a / b) for a, b in zip(re_fit.cpu().tolist(), re_true)],

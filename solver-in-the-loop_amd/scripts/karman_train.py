@@ -17,7 +17,8 @@ import time
 import numpy as np
 import torch
 
-from _common import add_buoyancy_arg, add_scene_args, agreed_buoyancy, buoyancy_from_args, flow_kwargs, logger, scene_from_args, select_gpu
+from _common import (add_buoyancy_arg, add_scene_args, add_substeps_arg, agreed_buoyancy, agreed_substeps, buoyancy_from_args, flow_kwargs, logger,
+                     scene_from_args, select_gpu, substeps_from_args)
 import sol_amd
 from sol_amd import ops, scene
 
@@ -52,6 +53,7 @@ def main(argv=None):
     p.add_argument("--any-width", action="store_true", help="run the correction network on rows of any width (pitched rows with column-masked convolutions) instead of refusing a width the convolutions do not take")
     add_scene_args(p)
     add_buoyancy_arg(p)
+    add_substeps_arg(p, auto=False)
     params = vars(p.parse_args(argv))
     select_gpu(params["gpu"])
     rank, world, local = sol_amd.dist.init_from_env()
@@ -76,12 +78,14 @@ def main(argv=None):
     # the scene: recorded by karman.py in every simulation's params.pickle (sets without the record: the default sphere); they
     # must agree, and an explicit --obstacle / --obstacle-mask must agree with them
     # the buoyancy force travels the same way ("buoyancy" in params.pickle; absent: off)
-    rec_set, buoy_set = None, []
+    # and so do the diffusion substeps ("diffusion_substeps" in params.pickle; absent: 1)
+    rec_set, buoy_set, sub_set = None, [], []
     for s in dataset.dataSims:
         with open(s + "/params.pickle", "rb") as f:
             pk = pickle.load(f)
         r = pk.get("scene") or sol_amd.karman.scene_record()
         buoy_set.append(agreed_buoyancy(pk.get("buoyancy"), None, s))
+        sub_set.append(agreed_substeps(pk.get("diffusion_substeps"), None, s))
         if rec_set is not None and not sol_amd.karman.scenes_equal(r, rec_set):
             raise SystemExit("the simulations of the training set disagree on the scene: %s has %s, others %s"
                              % (s, sol_amd.karman.describe_scene(r), sol_amd.karman.describe_scene(rec_set)))
@@ -96,6 +100,10 @@ def main(argv=None):
         raise SystemExit("the simulations of the training set disagree on the buoyancy force: %s" % sorted(set(buoy_set), key=str))
     buoyancy = agreed_buoyancy(buoy_set[0] if buoy_set else None, buoyancy_from_args(params), "the training set")
     log.info("buoyancy: %s" % (buoyancy,))
+    if len(set(sub_set)) > 1:
+        raise SystemExit("the simulations of the training set disagree on the diffusion substeps: %s" % sorted(set(sub_set)))
+    nsub = agreed_substeps(sub_set[0] if sub_set else None, substeps_from_args(params), "the training set")
+    log.info("diffusion substeps: %d" % nsub)
     if params["pretf"]:
         # karman_train.py:351-355: the supervised model's own input / output normalisation travels in stats.pickle next to it
         with open(os.path.dirname(params["pretf"]) + "/stats.pickle", "rb") as f:
@@ -134,6 +142,7 @@ def main(argv=None):
     os.makedirs(params["tf"], exist_ok=True)
     dataset.dataStats.setdefault("scene", rec)
     dataset.dataStats.setdefault("buoyancy", buoyancy)
+    dataset.dataStats.setdefault("diffusion_substeps", nsub)
     if params["resume"] < 1:
         if rank == 0:
             with open(params["tf"] + "/dataStats.pickle", "wb") as f:
@@ -147,7 +156,7 @@ def main(argv=None):
                                  in_std_v=dataset.dataStats["in.std"][1] if "in.std" in dataset.dataStats else None,
                                  out_std_v=dataset.dataStats["out.std"] if "out.std" in dataset.dataStats else None,
                                  pressure_solver=params["pressure_solver"], any_width=params["any_width"], buoyancy=buoyancy,
-                                 **flow_kwargs(rec))
+                                 diffusion_substeps=nsub, **flow_kwargs(rec))
     # persistent device buffers: the captured hipGraph keeps their addresses, new data is copied in
     f32 = lambda shape: torch.empty(shape, dtype=torch.float32, device=dev)
     d0, vy0, vx0, re = f32((Bl, Y, X)), f32((Bl, Y + 1, X)), f32((Bl, Y, X + 1)), f32((Bl,))

@@ -7,7 +7,8 @@ _bwd_large, sol_conv5x5 backward-data / -weight) under the AutogradCUDA key, so 
 dispatcher (torch.ops.sol.karman_step, .conv5x5, .burgers_step, .adam_tf_step; .karman_step_dens = karman_step with a differentiable
 density output, over sol_karman_density_bwd; .karman_step_re = karman_step differentiable with respect to re as well, over the _re
 adjoints; .karman_step_buoy = the large-grid step with the buoyancy force (fy, fx): the density pushes the velocity and is always in the
-graph; .karman3d_step_buoy = the same for the 3-D step, force (fy, fx, fz)).  Scene constants (masks, solver blobs, the cfg struct) are not tensors: they are registered once with register_scene() and
+graph; .karman_step_sub = karman_step with nsub explicit diffusion substeps, composing with the density, re and buoyancy modes;
+.karman3d_step_buoy = the same for the 3-D step, force (fy, fx, fz)).  Scene constants (masks, solver blobs, the cfg struct) are not tensors: they are registered once with register_scene() and
 referred to by an integer handle."""
 import torch
 
@@ -20,6 +21,7 @@ _LIB.define("karman_step(Tensor d, Tensor vy, Tensor vx, Tensor re, int scene) -
 _LIB.define("karman_step_dens(Tensor d, Tensor vy, Tensor vx, Tensor re, int scene) -> (Tensor, Tensor, Tensor)")
 _LIB.define("karman_step_re(Tensor d, Tensor vy, Tensor vx, Tensor re, int scene, bool density=False) -> (Tensor, Tensor, Tensor)")
 _LIB.define("karman_step_buoy(Tensor d, Tensor vy, Tensor vx, Tensor re, int scene, float fy, float fx, bool re_grad=False) -> (Tensor, Tensor, Tensor)")
+_LIB.define("karman_step_sub(Tensor d, Tensor vy, Tensor vx, Tensor re, int scene, int nsub, bool density=False, bool re_grad=False, float fy=0.0, float fx=0.0) -> (Tensor, Tensor, Tensor)")
 _LIB.define("karman_density_bwd(Tensor d, Tensor svy, Tensor svx, Tensor re, Tensor gd, int scene) -> (Tensor, Tensor, Tensor)")
 _LIB.define("karman_step_bwd(Tensor svy, Tensor svx, Tensor re, Tensor gvy, Tensor gvx, int scene) -> (Tensor, Tensor)")
 _LIB.define("karman_step_fwd_saved(Tensor d, Tensor vy, Tensor vx, Tensor re, int scene) -> (Tensor, Tensor, Tensor, Tensor, Tensor)")
@@ -77,7 +79,7 @@ def _karman_fn(d, vy, vx, re, scene, density, want_re):
     cfg, masks = _SCENES[scene]
     if want_re:
         ops._require_staged(cfg, "re_grad")
-    return ops.KarmanStepFn.apply(d, vy, vx, re, cfg, masks, None, None, density, want_re, None)
+    return ops.KarmanStepFn.apply(d, vy, vx, re, cfg, masks, None, None, density, want_re, None, 1)
 
 
 # karman_step_buoy: the buoyant mode of ops.KarmanStepFn (large grids; a force of (0, 0) is the plain step, density in the graph)
@@ -94,7 +96,7 @@ def _karman_buoy_fn(d, vy, vx, re, scene, fy, fx, re_grad=False):
     want_re = bool(re_grad) and torch.is_grad_enabled() and re.requires_grad
     if want_re:
         ops._require_staged(cfg, "re_grad")
-    return ops.KarmanStepFn.apply(d, vy, vx, re, cfg, masks, None, None, True, want_re, f if ops._buoyant(f) else None)
+    return ops.KarmanStepFn.apply(d, vy, vx, re, cfg, masks, None, None, True, want_re, f if ops._buoyant(f) else None, 1)
 
 
 for _op in ("karman_step", "karman_step_dens", "karman_step_re"):
@@ -105,6 +107,40 @@ _LIB.impl("karman_step_re", lambda d, vy, vx, re, scene, density=False: _karman_
 
 _LIB.impl("karman_step_buoy", _karman_buoy, "CUDA")
 _LIB.impl("karman_step_buoy", _karman_buoy_fn, "AutogradCUDA")
+
+
+# karman_step_sub: the step with nsub explicit diffusion substeps (ops.KarmanStepFn's substep mode; grids with Y, X >= 16), composing
+# with the other modes: density (d_out in the graph), re_grad, and on large grids a buoyancy force (fy, fx)
+def _karman_sub_args(scene, nsub, fy, fx):
+    cfg, masks = _SCENES[scene]
+    n = ops.diffusion_substeps_arg(nsub, "torch.ops.sol.karman_step_sub: nsub")
+    if n > 1:
+        ops._require_sub_grid(cfg, "torch.ops.sol.karman_step_sub")
+    f = ops.buoyancy_force((fy, fx))
+    f = f if ops._buoyant(f) else None
+    if f is not None:
+        ops._require_large_for_buoyancy(masks, cfg.Y, cfg.X, "torch.ops.sol.karman_step_sub")
+    return cfg, masks, n, f
+
+
+def _karman_sub(d, vy, vx, re, scene, nsub, density=False, re_grad=False, fy=0.0, fx=0.0):
+    cfg, masks, n, f = _karman_sub_args(scene, nsub, fy, fx)
+    with torch.no_grad():
+        if masks.large:
+            return ops.karman_step_large(d, vy, vx, re, cfg, masks, buoyancy=f, diffusion_substeps=n)
+        return ops.karman_step(d, vy, vx, re, cfg, masks, diffusion_substeps=n)
+
+
+def _karman_sub_fn(d, vy, vx, re, scene, nsub, density=False, re_grad=False, fy=0.0, fx=0.0):
+    cfg, masks, n, f = _karman_sub_args(scene, nsub, fy, fx)
+    want_re = bool(re_grad) and torch.is_grad_enabled() and re.requires_grad
+    if want_re:
+        ops._require_staged(cfg, "re_grad")
+    return ops.KarmanStepFn.apply(d, vy, vx, re, cfg, masks, None, None, bool(density), want_re, f, n)
+
+
+_LIB.impl("karman_step_sub", _karman_sub, "CUDA")
+_LIB.impl("karman_step_sub", _karman_sub_fn, "AutogradCUDA")
 
 # conv / burgers: the autograd.Functions of ops.py already are the hand-written forward + backward pairs
 _LIB.impl("conv5x5", lambda x, w, b, residual, lrelu, slope: ops.Conv5x5Fn.apply(x, w, b, residual, lrelu, slope), "AutogradCUDA")

@@ -75,6 +75,18 @@ def _refuse_buoyancy(who, buoyancy):
     return None
 
 
+def _refuse_substeps(who, diffusion_substeps, Y, X):
+    """SolTrainer, GraphTrainer and SolRollout run a solver step that lives inside the library's own schedule (the fused one-workgroup
+    kernels, the C-side graph): there is no place for the pre-diffusion launch.  diffusion_substeps > 1 is refused at construction
+    (LargeGridTrainer / LargeGridRollout take it on a large grid; KarmanFlow.step on every grid with Y, X >= 16).  -> 1"""
+    if ops.diffusion_substeps_arg(diffusion_substeps, "%s: diffusion_substeps" % who) > 1:
+        raise ValueError("%s: diffusion_substeps=%d -- diffusion substeps are built on the multi-launch (large-grid) trainers and roll-out "
+                         "only; on a %dx%d grid this class runs the fused one-workgroup solver step inside the library's own schedule.  "
+                         "Use LargeGridTrainer / LargeGridRollout on a large grid, or KarmanFlow(diffusion_substeps=...).step"
+                         % (who, diffusion_substeps, Y, X))
+    return 1
+
+
 def _train_cfg(kc, msteps, net, std_v, std_re, in_std_v, out_std_v):
     """TrainCfg with its normalisation fields.  --pretf (karman_train.py:351-355,416-421): separate input / output normalisation of a
     pre-trained supervised model; 0.0 pairs stand for "as std_v"."""
@@ -138,7 +150,7 @@ class SolTrainer(_AdamDP):
     def __init__(self, net, masks, B, Y, X, msteps, dx, std_v, std_re, dt=1.0, res=None,
                  clip_grad=False, beta1=0.9, beta2=0.999, eps=1e-8, group=None, use_graph=True,
                  cg_rtol=1e-6, cg_atol=1e-9, cg_max_iter=2000, grad_pad="replicate", inflow_order="after",
-                 conv_precision="split", comm=None, in_std_v=None, out_std_v=None, buoyancy=None):
+                 conv_precision="split", comm=None, in_std_v=None, out_std_v=None, buoyancy=None, diffusion_substeps=1):
         """conv_precision: arithmetic of the 32-channel convolutions (library option `conv_precision`):
         "split" (default) fp32-equivalent fp16x3 / bf16x6 operand splits on the 16-bit matrix pipe, "bf16x6",
         or "fp32" = strict fp32 MFMA.  The option is process wide in the library; every call of this trainer sets
@@ -147,6 +159,7 @@ class SolTrainer(_AdamDP):
         (e.g. a SOL_CONV_NO_SB / SOL_CONV_NO_FP16 debugging override applied when the library was loaded)."""
         _refuse_large_grid("SolTrainer", Y, X)
         _refuse_buoyancy("SolTrainer", buoyancy)
+        _refuse_substeps("SolTrainer", diffusion_substeps, Y, X)
         _lib.require_gpu()
         self.lib = _lib.load()
         self.conv_precision = _conv_precision_code(conv_precision)
@@ -254,7 +267,8 @@ class SolRollout:
     """No-grad roll-out of solver step + CNN correction (karman_apply.py:138-158)."""
 
     def __init__(self, net, masks, B, Y, X, dx, std_v, std_re, dt=1.0, res=None, in_std_v=None, out_std_v=None,
-                 conv_precision="split", **solver):
+                 conv_precision="split", diffusion_substeps=1, **solver):
+        _refuse_substeps("SolRollout", diffusion_substeps, Y, X)
         _lib.require_gpu()
         self.lib = _lib.load()
         self.conv_precision = _conv_precision_code(conv_precision)
@@ -294,11 +308,15 @@ class LargeGridRollout:
     a CG scene."""
 
     def __init__(self, net, masks, B, Y, X, dx, std_v, std_re, dt=1.0, res=None, in_std_v=None, out_std_v=None,
-                 conv_precision="split", use_graph=True, cg_warm_start=False, any_width=False, buoyancy=None, **solver):
+                 conv_precision="split", use_graph=True, cg_warm_start=False, any_width=False, buoyancy=None, diffusion_substeps=1,
+                 **solver):
         """any_width=True: X need not be a multiple of 64 -- the network runs in pitched rows (NetSchedule2D(any_width=True): the features
         are copied into zero-padded rows of 64 * ceil(X / 64) pixels and the output is cropped; the solver step and the correction stay
         dense).  buoyancy=(fy, fx) (ops.buoyancy_force): the density pushes the velocity -- the solver step is the buoyant one
-        (sol_karman_step_fwd_large_buoy: one launch more, captured with the rest; direct and CG scenes, warm start included)."""
+        (sol_karman_step_fwd_large_buoy: one launch more, captured with the rest; direct and CG scenes, warm start included).
+        diffusion_substeps=n: n explicit diffusion substeps per solver step (ops.karman_step_large(diffusion_substeps=n): the
+        pre-diffusion launches are part of the captured step)."""
+        self.diffusion_substeps = ops.diffusion_substeps_arg(diffusion_substeps, "LargeGridRollout: diffusion_substeps")
         f = ops.buoyancy_force(buoyancy)
         self.buoyancy = f if ops._buoyant(f) else None
         if not ops.beyond_one_workgroup(Y, X):
@@ -347,7 +365,7 @@ class LargeGridRollout:
     def _step(self):
         info = {}
         ops.karman_step_large(*self._a, self._re, self.cfg, self.masks, self._ws, info, feat=self._feat, feat_scale=self._fs3,
-                              p_guess=self.p_guess, out=self._b, buoyancy=self.buoyancy)
+                              p_guess=self.p_guess, out=self._b, buoyancy=self.buoyancy, diffusion_substeps=self.diffusion_substeps)
         out, _ = self._sched.forward(self._feat)
         ops.karman_correct(out, self._b[1], self._b[2], self._so, self._cor)
         _lib.dcopy_(self._flat[0], self._flat[1])
@@ -398,6 +416,7 @@ def make_rollout(net, masks, B, Y, X, dx, std_v, std_re, **kw):
     if ops._buoyant(ops.buoyancy_force(kw.pop("buoyancy", None))):
         raise ValueError("make_rollout: the buoyancy force is built on the multi-launch (large-grid) solver step only; a %dx%d grid runs "
                          "the one-workgroup roll-out (SolRollout), which has no buoyancy term" % (Y, X))
+    kw["diffusion_substeps"] = _refuse_substeps("make_rollout", kw.get("diffusion_substeps", 1), Y, X)
     return SolRollout(net, masks, B, Y, X, dx, std_v, std_re, **kw)
 
 
@@ -417,7 +436,7 @@ class GraphTrainer(_AdamDP):
                  group=None, use_graph=True, comm=None, in_std_v=None, out_std_v=None, pressure_solver=None,
                  dx=None, dt=1.0, masks=None, cg_rtol=1e-6, cg_atol=1e-9, cg_max_iter=2000, grad_pad="replicate",
                  inflow_order="after", conv_precision="split", schedule="manual", obstacles=None, active=None,
-                 buoyancy=None):
+                 buoyancy=None, diffusion_substeps=1):
         """dx: cell size (default 100 / X, the reference's `--len 100`); the domain is box[0:Y*dx, 0:X*dx] as the scripts
         build it (karman_train.py:363: box[0:len*2, 0:len]).  obstacles / active: the scene of KarmanFlow (default: the reference's
         sphere).  masks: optional SceneMasks of the caller -- its boundary arrays are used; its scene must be the one KarmanFlow
@@ -430,6 +449,7 @@ class GraphTrainer(_AdamDP):
         self._cg_fwd, self._cg_bwd = [], []       # what the solver launches of a step report (LargeGridTrainer, CG scenes)
         self._check_grid(Y, X)
         self.buoyancy = self._check_buoyancy(buoyancy)
+        self.diffusion_substeps = self._check_substeps(diffusion_substeps, Y, X)
         from . import fluid, karman
         _lib.require_gpu()
         self.lib = _lib.load()
@@ -473,6 +493,10 @@ class GraphTrainer(_AdamDP):
     @staticmethod
     def _check_buoyancy(buoyancy):
         return _refuse_buoyancy("GraphTrainer", buoyancy)
+
+    @staticmethod
+    def _check_substeps(diffusion_substeps, Y, X):
+        return _refuse_substeps("GraphTrainer", diffusion_substeps, Y, X)
 
     def _unrolled(self):
         if self.schedule == "manual":
@@ -634,7 +658,10 @@ class LargeGridTrainer(GraphTrainer):
         buoyant one: _solver_fwd = ops.karman_step_saved(buoyancy=...) and also keeps each step's input density, _solver_bwd =
         ops.karman_step_large_bwd_buoy (the buoyant velocity adjoint, then the density adjoint), which carries g_d_in to the next (earlier)
         step as that step's g_d_out.  The loss looks at the velocity only, so the last step's g_d_out is zero; the carried gradient is
-        reset at the head of every run, so a replayed graph is self-contained."""
+        reset at the head of every run, so a replayed graph is self-contained.
+        diffusion_substeps=n (keyword): n explicit diffusion substeps per solver step -- _solver_fwd / _solver_bwd pass it to
+        ops.karman_step_saved and ops.karman_step_large_bwd(_buoy): the pre-diffusion launches on the input velocity and on the adjoint's
+        result are part of the (captured) schedule."""
         if any_width and kw.get("schedule", "manual") == "autograd":
             raise ValueError("LargeGridTrainer: any_width=True runs the hand-written schedule only; schedule='autograd' (the composition "
                              "over ops.conv5x5) takes no pitched rows")
@@ -658,6 +685,10 @@ class LargeGridTrainer(GraphTrainer):
         f = ops.buoyancy_force(buoyancy)
         return f if ops._buoyant(f) else None
 
+    @staticmethod
+    def _check_substeps(diffusion_substeps, Y, X):
+        return ops.diffusion_substeps_arg(diffusion_substeps, "LargeGridTrainer: diffusion_substeps")
+
     def _schedule_setup(self):
         super()._schedule_setup()
         cfg, mk, dev = self._kcfg, self._mk, self.device
@@ -678,7 +709,8 @@ class LargeGridTrainer(GraphTrainer):
         info = {}
         if self.buoyancy is not None:
             self._d_in.append(d)
-        (d2, vy2, vx2), svy, svx = ops.karman_step_large_saved(d, vy, vx, re, self._kcfg, self._mk, self._ws_fwd, info, self.buoyancy)
+        (d2, vy2, vx2), svy, svx = ops.karman_step_large_saved(d, vy, vx, re, self._kcfg, self._mk, self._ws_fwd, info, self.buoyancy,
+                                                                         self.diffusion_substeps)
         self._cg_fwd.append(info)
         # to_feature / in_std (karman_train.py:77-86, 413-416), padded to the four channels the first layer's kernels read
         feat = torch.stack([vy2[:, :Y] * fs[0], vx2[:, :, :X] * fs[1], self._re_plane, self._zplane], dim=-1)
@@ -694,9 +726,11 @@ class LargeGridTrainer(GraphTrainer):
             # the reverse sweep visits the steps last to first (the first step's adjoint is not run): the input densities come off the end
             d_in = self._d_in.pop()
             self._g_d, oy, ox = ops.karman_step_large_bwd_buoy(d_in, svy, svx, re, G[0], G[1], self._g_d, self._kcfg, self._mk, self.buoyancy,
-                                                               workspace=self._ws_bwd, info=info, density_workspace=self._ws_bwd_d)
+                                                               workspace=self._ws_bwd, info=info, density_workspace=self._ws_bwd_d,
+                                                               diffusion_substeps=self.diffusion_substeps)
             return oy, ox
-        return ops.karman_step_large_bwd(svy, svx, re, G[0], G[1], self._kcfg, self._mk, workspace=self._ws_bwd, info=info)
+        return ops.karman_step_large_bwd(svy, svx, re, G[0], G[1], self._kcfg, self._mk, workspace=self._ws_bwd, info=info,
+                                         diffusion_substeps=self.diffusion_substeps)
 
     def _fwd_bwd(self, *a, **kw):
         loss = super()._fwd_bwd(*a, **kw)
@@ -718,6 +752,7 @@ def make_trainer(net, masks, B, Y, X, msteps, dx, std_v, std_re, **kw):
         # describe them for GraphTrainer's KarmanFlow)
         for k in ("obstacles", "active", "pressure_solver", "any_width"):
             kw.pop(k, None)
+        kw["diffusion_substeps"] = _refuse_substeps("make_trainer", kw.get("diffusion_substeps", 1), Y, X)
         return SolTrainer(net, masks, B, Y, X, msteps, dx, std_v, std_re, **kw)
     kw.pop("any_width", None)           # (the one-workgroup grids: the keyword belongs to LargeGridTrainer)
     return GraphTrainer(net, B, Y, X, msteps, std_v, std_re, dx=dx, masks=masks, **kw)     # unknown keywords raise TypeError
