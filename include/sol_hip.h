@@ -873,6 +873,31 @@ int sol_karman3d_buoyancy_add(void* stream, int32_t B, int32_t Y, int32_t X, int
 int sol_karman3d_buoyancy_add_bwd(void* stream, int32_t B, int32_t Y, int32_t X, int32_t Z, const float* active,
                                   const float* g_vy, const float* g_vx, const float* g_vz, float fy_dt, float fx_dt, float fz_dt,
                                   const float* g_d_out, float* g_dsum);
+/* DIFFUSION SUBSTEPS of the karman-3d step (csrc/karman3d_diffuse_sub.hip; diffusion_substeps = n on the Python surface): the definition
+ * of "DIFFUSION SUBSTEPS" above with a third axis.  The single stencil v += alpha Lap(v), alpha = dt res^2 / Re (k3_diffuse), is a convex
+ * combination only while alpha <= 1/6.  With M = I + (alpha / n) L, L the 7-point Laplacian with replicate padding on each of the three
+ * face grids [Y+1,X,Z], [Y,X+1,Z], [Y,X,Z+1],
+ *     step_n(d, v; alpha) = step_1(d, M^(n-1) v; alpha / n)
+ * -- n substeps of alpha / n, the boundary blend once, after the last one; the density is not diffused.  No existing kernel, entry point
+ * or struct changes: the caller computes M^(n-1) v with the entry point below and runs the existing step on a copy of the cfg whose res
+ * is float32(res / sqrt(n)) (res enters every 3-D kernel through dt * res * res alone); the entry point forms its coefficient from the cfg
+ * it is given by the step's own expression, (dt * res * res) / re[b].  re itself is not scaled: the fused feature output keeps carrying
+ * the true Reynolds number.  Adjoint: L is symmetric on every face grid, so the existing adjoints on the scaled cfg yield the cotangent of
+ * M^(n-1) v and the same entry point applied to it yields the cotangent of v.  Gradient in re: the existing _re reductions on the scaled
+ * cfg, given M^(n-1) v as their input velocity, yield 1/n of the gradient: the caller multiplies by n.
+ *   sol_karman3d_diffuse_sub: v*_out = (I + a_b L)^m v*_in, a_b = cfg.dt * cfg.res^2 / re[b], m in [1, 4096]; of the cfg only B, Y, X, Z,
+ *     dt and res are read; Y >= 16, X, Z >= 8, B <= 65535.  chunk: substeps per launch, 1 .. sol_karman3d_diffuse_sub_max() (0 = that
+ *     maximum); a launch covers the three components and the batch and runs its substeps in LDS on tiles with a halo (temporal blocking).
+ *     Every substep is fmaf(a_b, lap, c) with lap summed in the step's order, so the result does not depend on chunk: m launches of one
+ *     substep and one launch of m substeps give equal bits.  More than one launch ping-pongs through `workspace`
+ *     (sol_karman3d_diffuse_sub_workspace_bytes(cfg, m, chunk): two velocity triples; 0 bytes and NULL for a single launch).  The outputs
+ *     must not alias the inputs or each other.  Does not synchronise, allocate or read device memory on the host: capturable. */
+int32_t sol_karman3d_diffuse_sub_max(void);
+size_t sol_karman3d_diffuse_sub_workspace_bytes(const sol_karman3d_cfg* cfg, int32_t m, int32_t chunk);
+int sol_karman3d_diffuse_sub(const sol_karman3d_cfg* cfg, void* stream,
+                             const float* vy_in, const float* vx_in, const float* vz_in, const float* re,
+                             float* vy_out, float* vx_out, float* vz_out,
+                             int32_t m, int32_t chunk, void* workspace, size_t workspace_bytes);
 /* The step's pressure solve alone: M p = rhs with M = -A for the scene's `active` mask (the solver cfg->pressure_solver selects;
  * the CG solve reports to cfg->cg_info).  rhs, p [B,Y,X,Z] (rhs is read only); workspace: sol_karman3d_step_workspace_bytes(cfg). */
 int sol_karman3d_pressure_solve(const sol_karman3d_cfg* cfg, void* stream, const float* active, const float* rhs, float* p,

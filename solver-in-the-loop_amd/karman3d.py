@@ -83,6 +83,74 @@ def _buoyant3d(buoyancy):
     return buoyancy is not None and any(v != 0.0 for v in buoyancy)
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# diffusion substeps (include/sol_hip.h, "DIFFUSION SUBSTEPS of the karman-3d step"; csrc/karman3d_diffuse_sub.hip)
+# ---------------------------------------------------------------------------------------------------------------------
+def min_diffusion_substeps3d(re_min, res, dt=1.0):
+    """The smallest n with dt res^2 / (n re_min) <= 1/6: the explicit 3-D diffusion stencil v += a Lap(v) is a convex combination of a
+    face and its six neighbours exactly while a <= 1/6 (the 2-D bound, ops.min_diffusion_substeps, is 1/4).  re_min: the smallest
+    Reynolds number of the run."""
+    re_min, res, dt = float(re_min), float(res), float(dt)
+    if not (re_min > 0 and res > 0 and dt > 0) or not np.isfinite(dt * res * res / re_min):
+        raise ValueError("min_diffusion_substeps3d: re_min, res and dt must be positive and finite (got %r, %r, %r)" % (re_min, res, dt))
+    alpha = dt * res * res / re_min
+    n = max(1, int(np.ceil(6.0 * alpha)))
+    while alpha / n > 1.0 / 6.0:
+        n += 1
+    while n > 1 and alpha / (n - 1) <= 1.0 / 6.0:
+        n -= 1
+    return n
+
+
+def diffusion_sub_res(res, n):
+    """`res` of the cfg the existing launches and the pre-diffusion run on under diffusion_substeps = n: float32(res / sqrt(n)), so that
+    their own expression dt * res * res / re[b] is the substep's coefficient (ops.diffusion_sub_cfg's idea; res enters the 3-D kernels
+    through that product alone).  re is NOT scaled: the feature channel keeps the true Reynolds number.  n = 1: res itself."""
+    return float(res) if n == 1 else float(np.float32(float(res) / np.sqrt(float(n))))
+
+
+def diffuse_sub_max3d():
+    """S_MAX: the most substeps one launch of sol_karman3d_diffuse_sub runs"""
+    return int(_lib.load().sol_karman3d_diffuse_sub_max())
+
+
+# substeps per launch of the pre-diffusion where the caller names none (1 .. diffuse_sub_max3d()); the bits do not depend on it.
+# Measured at 128 x 64 x 64, B = 1 (tools/k3d_substeps_time.py -> profiles/k3d_substeps_time.json): two substeps fused tie with two
+# launches of one, three fused LOSE to three launches of one (supposed, not measured: the box of three faces a side is 3.6 times the
+# tile's volume and leaves two workgroups a CU) -- so one substep per launch is the default; the fused path stays for callers that name a chunk.
+DIFFUSE_SUB_CHUNK3D = 1
+
+
+def diffuse_sub(sim, vy, vx, vz, re, nsub, chunk=None):
+    """The pre-diffusion of a step with diffusion_substeps = nsub (sol_karman3d_diffuse_sub): (vy, vx, vz) -> M^(nsub-1) (vy, vx, vz),
+    M = I + (alpha / nsub) L with alpha = dt res^2 / re of `sim` (a Karman3DFlow: its own, unscaled res) and L the 7-point Laplacian with
+    replicate padding on each face grid.  M^(nsub-1) is symmetric: applied to a cotangent this is also the adjoint.  chunk: the most
+    substeps per launch, 1 .. diffuse_sub_max3d() (None = DIFFUSE_SUB_CHUNK3D); the bits do not depend on it.  More than one launch
+    ping-pongs through sim's pre-diffusion workspace (Karman3DFlow._sub_workspace: the static one of sim's own count, else a buffer of this
+    call alone).  nsub = 1: no launch, the inputs are returned."""
+    from .ops import diffusion_substeps_arg
+    n = diffusion_substeps_arg(nsub, "diffuse_sub: nsub")
+    smax = diffuse_sub_max3d()
+    chunk = DIFFUSE_SUB_CHUNK3D if chunk is None else chunk
+    if isinstance(chunk, bool) or not isinstance(chunk, (int, np.integer)) or not 1 <= chunk <= smax:
+        raise ValueError("diffuse_sub: chunk must be None or an integer in [1, %d] (got %r)" % (smax, chunk))
+    _lib.require_gpu()
+    vy, vx, vz, re = (_lib.f32(t) for t in (vy, vx, vz, re))
+    if n == 1:
+        return vy, vx, vz
+    s, B = sim.scene, sim.B
+    Y, X, Z = s.Y, s.X, s.Z
+    if vy.shape != (B, Y + 1, X, Z) or vx.shape != (B, Y, X + 1, Z) or vz.shape != (B, Y, X, Z + 1) or re.shape != (B,):
+        raise ValueError("diffuse_sub: vy %s, vx %s, vz %s, re %s are not [B,Y+1,X,Z], [B,Y,X+1,Z], [B,Y,X,Z+1], [B] of the scene (B, Y, X, Z) = "
+                         "(%d, %d, %d, %d)" % (tuple(vy.shape), tuple(vx.shape), tuple(vz.shape), tuple(re.shape), B, Y, X, Z))
+    cfg = sim.sub_cfg(n)
+    ws, nbytes = sim._sub_workspace(cfg, n - 1, int(chunk))
+    out = [torch.empty_like(t) for t in (vy, vx, vz)]
+    check(sim.lib.sol_karman3d_diffuse_sub(C.byref(cfg), stream(), ptr(vy), ptr(vx), ptr(vz), ptr(re), ptr(out[0]), ptr(out[1]), ptr(out[2]),
+                                           n - 1, int(chunk), ptr(ws), nbytes))
+    return tuple(out)
+
+
 PRESSURE_SOLVERS3D = ("auto", "direct", "cg")
 CG_MAX_ITER3D = 120             # launch budget of the CG solve: 28-87 iterations measured at rtol 1e-6 (DESIGN 4.8)
 
@@ -148,11 +216,19 @@ class Karman3DFlow:
     buoyancy=(fy, fx, fz), a force per unit density, or PhiFlow's spelling buoyancy_factor=beta with gravity=(gy, gx, gz): F = -gravity *
     beta (buoyancy_force3d).  The step's OUTPUT density pushes the velocity (sol_karman3d_step_fwd_buoy: one launch more); the density is
     then part of the dynamics and always in the graph, whatever density_grad says (_Karman3DStepFn's buoyant mode).  A force of zero, or
-    none: the plain step."""
+    none: the plain step.
+
+    diffusion_substeps=n (PhiFlow's diffuse(field, amount, substeps)): the velocity is diffused by n explicit substeps of alpha / n, alpha
+    = dt res^2 / Re, the boundary blend after the last one.  The single stencil is stable only while alpha <= 1/6
+    (min_diffusion_substeps3d gives the n a run needs).  `step` then runs diffuse_sub (M^(n-1) v) and the launches above on a cfg whose
+    res is diffusion_sub_res(res, n); composes with density_grad, re_grad, buoyancy, both solvers and feat_out (whose fourth channel stays
+    the true re).  The default 1 issues the launches it always did."""
 
     def __init__(self, scene, batch_size, dt=1.0, res=None, grad_pad="replicate", inflow_order="after",
                  cg_rtol=1e-6, cg_atol=1e-9, cg_max_iter=CG_MAX_ITER3D, density_grad=False, re_grad=False,
-                 buoyancy=None, buoyancy_factor=None, gravity=(-9.81, 0.0, 0.0)):
+                 buoyancy=None, buoyancy_factor=None, gravity=(-9.81, 0.0, 0.0), diffusion_substeps=1):
+        from .ops import diffusion_substeps_arg
+        self.nsub = diffusion_substeps_arg(diffusion_substeps, "Karman3DFlow: diffusion_substeps")
         _lib.require_gpu()
         self.lib = _lib.load()
         self.scene, self.B = scene, batch_size
@@ -169,18 +245,46 @@ class Karman3DFlow:
         self.workspace = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=s.active.device)
         self.workspace_bytes = nbytes
         self.solve_info = {}
+        # the pre-diffusion's ping-pong buffers for this simulator's own count: allocated once, here, and never replaced (a captured graph
+        # bakes their address in)
+        nbytes = self.lib.sol_karman3d_diffuse_sub_workspace_bytes(C.byref(self.cfg), self.nsub - 1, DIFFUSE_SUB_CHUNK3D) if self.nsub > 1 else 0
+        self._sub_ws = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=s.active.device) if nbytes else None
+        self._sub_ws_bytes = nbytes
 
-    def _cg_info(self):
-        """a fresh device report [B][2] for the next call (a captured graph keeps its own), or None for the direct solve"""
+    def _sub_workspace(self, cfg, m, chunk):
+        """(workspace, bytes) of sol_karman3d_diffuse_sub(cfg, m substeps, chunk): (None, 0) for a single launch, the simulator's static
+        buffer where it is large enough (its own count), else a buffer of this call alone (another count through diffuse_sub or the torch
+        op on a simulator built without one: the static buffer is never grown or replaced)"""
+        nbytes = self.lib.sol_karman3d_diffuse_sub_workspace_bytes(C.byref(cfg), m, chunk)
+        if nbytes == 0:
+            return None, 0
+        if nbytes <= self._sub_ws_bytes:
+            return self._sub_ws, self._sub_ws_bytes
+        return torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=self.scene.active.device), nbytes
+
+    def sub_cfg(self, n):
+        """The cfg the existing launches (_fwd, _bwd, density_bwd) and the pre-diffusion run on under diffusion_substeps = n: a COPY whose
+        res is diffusion_sub_res(res, n), so that their own dt res^2 / re[b] is the substep's coefficient alpha / n; n = 1: the
+        simulator's own cfg.  The simulator's cfg is never modified."""
+        if n == 1:
+            return self.cfg
+        c = Karman3DCfg.from_buffer_copy(self.cfg)
+        c.res = diffusion_sub_res(self.cfg.res, n)
+        return c
+
+    def _cg_info(self, cfg):
+        """a fresh device report [B][2] for the next call on `cfg` (a captured graph keeps its own), or None for the direct solve"""
         if not self.cg:
-            self.cfg.cg_info = None
+            cfg.cg_info = None
             return None
         info = torch.empty(self.B, 2, dtype=torch.int32, device=self.scene.active.device)      # (every solve writes it)
-        self.cfg.cg_info = info.data_ptr()
+        cfg.cg_info = info.data_ptr()
         return info
 
-    def _fwd(self, d, vy, vx, vz, re, saved=None, feat_out=None, feat_scale=None, buoyancy=None):
-        """one forward step; buoyancy = (fy, fx, fz): sol_karman3d_step_fwd_buoy (a force of zero issues the plain call's launches)"""
+    def _fwd(self, d, vy, vx, vz, re, saved=None, feat_out=None, feat_scale=None, buoyancy=None, nsub=1):
+        """one forward step; buoyancy = (fy, fx, fz): sol_karman3d_step_fwd_buoy (a force of zero issues the plain call's launches);
+        nsub: the launches run on sub_cfg(nsub) (the caller has pre-diffused the velocity: _fwd_sub)"""
+        cfg = self.sub_cfg(nsub)
         s, B = self.scene, self.B
         Y, X, Z = s.Y, s.X, s.Z
         assert d.shape == (B, Y, X, Z) and vy.shape == (B, Y + 1, X, Z) and vx.shape == (B, Y, X + 1, Z) and vz.shape == (B, Y, X, Z + 1)
@@ -191,9 +295,9 @@ class Karman3DFlow:
             assert feat_out.shape == (B, Y, X, Z, 4) and feat_out.is_contiguous()
             fs = (C.c_float * 4)(*[float(v) for v in feat_scale])
         sv = saved if saved is not None else (None, None, None)
-        info = self._cg_info()
+        info = self._cg_info(cfg)
         entry, tail = (self.lib.sol_karman3d_step_fwd, ()) if buoyancy is None else (self.lib.sol_karman3d_step_fwd_buoy, tuple(float(v) for v in buoyancy))
-        check(entry(C.byref(self.cfg), stream(), ptr(d), ptr(vy), ptr(vx), ptr(vz), ptr(re),
+        check(entry(C.byref(cfg), stream(), ptr(d), ptr(vy), ptr(vx), ptr(vz), ptr(re),
                     ptr(s.active), ptr(s.inflow), ptr(s.velBCy), ptr(s.velBCyMask), s.bc_stride,
                     ptr(out[0]), ptr(out[1]), ptr(out[2]), ptr(out[3]), ptr(sv[0]), ptr(sv[1]), ptr(sv[2]),
                     ptr(feat_out), fs,
@@ -222,15 +326,16 @@ class Karman3DFlow:
             raise ValueError("g_re must be [B] = (%d,), got %s" % (self.B, tuple(g_re.shape)))
         return (ptr(vel_in[0]), ptr(vel_in[1]), ptr(vel_in[2]), ptr(g_re), int(accumulate)), g_re
 
-    def _bwd(self, saved, re, gvy, gvx, gvz, vel_in=None, g_re=None, buoyancy=None, g_d=None):
+    def _bwd(self, saved, re, gvy, gvx, gvz, vel_in=None, g_re=None, buoyancy=None, g_d=None, nsub=1):
         """the velocity adjoint (sol_karman3d_step_bwd); vel_in = the step's input velocity: also the gradient with respect to re
         (sol_karman3d_step_bwd_re; the velocity gradients are the plain call's bits) -> [g_vy, g_vx, g_vz] (+ [g_re]).
         buoyancy = (fy, fx, fz): the buoyant step's (sol_karman3d_step_bwd_buoy(_re): the same launches and bits, then the transpose of the
         force term); g_d [B,Y,X,Z] = the cotangent of the step's output density (None = zero) -> ... + [g_dsum], which the caller hands to
         density_bwd as its g_d, accumulating onto the velocity gradients returned here."""
         s = self.scene
+        cfg = self.sub_cfg(nsub)            # (nsub > 1: `saved` / vel_in are the pre-diffused step's; the result is the cotangent of M^(n-1) v, g_re 1/n)
         gi = [torch.empty_like(t) for t in saved]
-        info = self._cg_info()
+        info = self._cg_info(cfg)
         buoy = buoyancy is not None
         if vel_in is None:
             entry, tail = (self.lib.sol_karman3d_step_bwd_buoy if buoy else self.lib.sol_karman3d_step_bwd), ()
@@ -246,7 +351,7 @@ class Karman3DFlow:
                     raise ValueError("g_d must be [B,Y,X,Z] = %s, got %s" % ((self.B, s.Y, s.X, s.Z), tuple(g_d.shape)))
             g_dsum = torch.empty(self.B, s.Y, s.X, s.Z, dtype=torch.float32, device=saved[0].device)
             tail = tuple(tail) + tuple(float(v) for v in buoyancy) + (ptr(g_d), ptr(g_dsum))
-        check(entry(C.byref(self.cfg), stream(), ptr(saved[0]), ptr(saved[1]), ptr(saved[2]), ptr(re),
+        check(entry(C.byref(cfg), stream(), ptr(saved[0]), ptr(saved[1]), ptr(saved[2]), ptr(re),
                     ptr(s.active), ptr(s.velBCyMask), s.bc_stride, ptr(gvy), ptr(gvx), ptr(gvz),
                     ptr(gi[0]), ptr(gi[1]), ptr(gi[2]),
                     s.direct_header.ctypes.data_as(C.c_void_p), ptr(self.workspace), self.workspace_bytes, *tail))
@@ -262,7 +367,7 @@ class Karman3DFlow:
         rhs = _lib.f32(rhs)
         assert rhs.shape == (self.B, s.Y, s.X, s.Z)
         p = torch.empty_like(rhs)
-        info = self._cg_info()
+        info = self._cg_info(self.cfg)
         check(self.lib.sol_karman3d_pressure_solve(C.byref(self.cfg), stream(), ptr(s.active), ptr(rhs), ptr(p),
                                                    s.direct_header.ctypes.data_as(C.c_void_p), ptr(self.workspace), self.workspace_bytes))
         if info is not None:
@@ -282,17 +387,26 @@ class Karman3DFlow:
         if grad and (vy.requires_grad or vx.requires_grad or vz.requires_grad or (density and d.requires_grad) or want_re):
             if feat_out is not None:
                 raise ValueError("feat_out is the fused no-grad feature output: build the features with to_feature3d() when training")
-            return _Karman3DStepFn.apply(self, d, vy, vx, vz, re, density, want_re, self.buoyancy)
-        return self._fwd(d, vy, vx, vz, re, None, feat_out, feat_scale, self.buoyancy)
+            return _Karman3DStepFn.apply(self, d, vy, vx, vz, re, density, want_re, self.buoyancy, self.nsub)
+        return self._fwd_sub(d, vy, vx, vz, re, None, feat_out, feat_scale, self.buoyancy, self.nsub)
+
+    def _fwd_sub(self, d, vy, vx, vz, re, saved=None, feat_out=None, feat_scale=None, buoyancy=None, nsub=1):
+        """_fwd under diffusion_substeps = nsub: the pre-diffusion (diffuse_sub), then _fwd's launches on the scaled cfg; nsub = 1: _fwd"""
+        if nsub > 1:
+            vy, vx, vz = diffuse_sub(self, vy, vx, vz, re, nsub)
+        return self._fwd(d, vy, vx, vz, re, saved, feat_out, feat_scale, buoyancy, nsub)
 
 
-def density_bwd(sim, d_in, saved, re, g_d, g_v=None, vel_in=None, g_re=None):
+def density_bwd(sim, d_in, saved, re, g_d, g_v=None, vel_in=None, g_re=None, nsub=1):
     """Adjoint of the 3-D step's marker density (sol_karman3d_density_bwd), the direct call: (g_d_in, g_vy_in, g_vx_in, g_vz_in) from the
     step's input density `d_in`, the saved post-diffusion velocity `saved` = (svy, svx, svz), `re` and the gradient `g_d` with respect
     to the step's output density; `sim` = the Karman3DFlow (scene, cfg, workspace).  g_v = (g_vy, g_vx, g_vz): buffers that already hold
     the velocity adjoint's result; the density's part is added onto them in place (one fp32 add per face) and they are returned.  Without
     them the density's part alone is written to fresh tensors.  vel_in = (vy, vx, vz), the step's INPUT velocity: the gradient with
-    respect to re as well (sol_karman3d_density_bwd_re), returned fifth; g_re [B]: a buffer to add onto, else a fresh one is written."""
+    respect to re as well (sol_karman3d_density_bwd_re), returned fifth; g_re [B]: a buffer to add onto, else a fresh one is written.
+    nsub (diffusion substeps: _Karman3DStepFn, the trainer): the launches run on sim.sub_cfg(nsub); `saved` / vel_in are then those of
+    the pre-diffused velocity, the velocity gradients are the cotangent of M^(n-1) v and g_re is 1/n of the gradient -- a g_re to add onto
+    must hold such a part too (the factor n is applied once, afterwards)."""
     _lib.require_gpu()
     s, B = sim.scene, sim.B
     Y, X, Z = s.Y, s.X, s.Z
@@ -314,7 +428,7 @@ def density_bwd(sim, d_in, saved, re, g_d, g_v=None, vel_in=None, g_re=None):
     gi = list(g_v) if accumulate else [torch.empty_like(t) for t in saved]
     od = torch.empty_like(d_in)
     ws = sim._ws(nbytes)
-    check(entry(C.byref(sim.cfg), stream(), ptr(d_in), ptr(s.inflow), ptr(saved[0]), ptr(saved[1]), ptr(saved[2]), ptr(re),
+    check(entry(C.byref(sim.sub_cfg(nsub)), stream(), ptr(d_in), ptr(s.inflow), ptr(saved[0]), ptr(saved[1]), ptr(saved[2]), ptr(re),
                 ptr(s.velBCyMask), s.bc_stride, ptr(g_d), ptr(od), ptr(gi[0]), ptr(gi[1]), ptr(gi[2]), int(accumulate),
                 ptr(ws), sim.workspace_bytes, *tail))
     return (od, *gi) if vel_in is None else (od, *gi, g_re)
@@ -329,14 +443,21 @@ class _Karman3DStepFn(torch.autograd.Function):
     `buoyancy` = (fy, fx, fz), a non-zero force (else None): the buoyant step -- the density is part of the dynamics, so it is in the graph
     whatever `density` says.  Whenever any cotangent arrives the velocity half runs through its buoyant entry (Karman3DFlow._bwd: the
     plain launches and the transpose of the force term, g_dsum = g_d + dt F . transpose(g_a)), then the density half on g_dsum, accumulating:
-    a velocity-only loss yields a density gradient too."""
+    a velocity-only loss yields a density gradient too.
+    `nsub` (diffusion_substeps = n > 1): n explicit diffusion substeps, one more mode that composes with the others -- diffuse_sub before
+    the forward launches, which then run on the scaled cfg (Karman3DFlow.sub_cfg) on the pre-diffused velocity M^(n-1) v; that is also
+    the "input velocity" the re mode saves.  Backward: the adjoints above on the scaled cfg, then diffuse_sub on the velocity cotangent
+    (the operator is symmetric) and g_re times n (one fp32 multiply).  nsub = 1 launches nothing new."""
 
     @staticmethod
-    def forward(ctx, sim, d, vy, vx, vz, re, density, want_re, buoyancy=None):
+    def forward(ctx, sim, d, vy, vx, vz, re, density, want_re, buoyancy=None, nsub=1):
         vel = [vy.contiguous(), vx.contiguous(), vz.contiguous()]
+        if nsub > 1:
+            vel = list(diffuse_sub(sim, vel[0], vel[1], vel[2], re, nsub))
         saved = [torch.empty_like(t) for t in vel]
         density = bool(density) or buoyancy is not None
-        out = sim._fwd(d, vel[0], vel[1], vel[2], re, saved, buoyancy=buoyancy)
+        out = sim._fwd(d, vel[0], vel[1], vel[2], re, saved, buoyancy=buoyancy, nsub=nsub)
+        ctx.nsub = nsub
         ctx.sim, ctx.density, ctx.want_re, ctx.buoyancy = sim, density, want_re, buoyancy
         ctx.save_for_backward(re, *saved, *((d,) if density else ()), *(vel if want_re else ()))
         if not density:
@@ -346,6 +467,19 @@ class _Karman3DStepFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gd, gvy, gvx, gvz):
+        n, sim = ctx.nsub, ctx.sim
+        od, gy, gx, gz, g_re = _Karman3DStepFn._adjoints(ctx, gd, gvy, gvx, gvz)
+        if n > 1:           # (gy, gx, gz) is the cotangent of M^(n-1) v and g_re 1/n of the gradient: see the class comment
+            if gy is not None:
+                gy, gx, gz = diffuse_sub(sim, gy, gx, gz, ctx.saved_tensors[0], n)
+            if g_re is not None:
+                g_re = g_re * float(n)
+        return None, od, gy, gx, gz, g_re, None, None, None, None
+
+    @staticmethod
+    def _adjoints(ctx, gd, gvy, gvx, gvz):
+        """(g_d, g_vy, g_vx, g_vz, g_re) of forward's launches on the scaled cfg: under nsub > 1 the cotangent of M^(n-1) v and 1/n of g_re"""
+        n = ctx.nsub
         re, sy, sx, sz, *rest = ctx.saved_tensors
         saved = (sy, sx, sz)
         d_in = rest[0] if ctx.density else None
@@ -354,18 +488,18 @@ class _Karman3DStepFn(torch.autograd.Function):
         od = g_re = gi = None
         if ctx.buoyancy is not None:
             if gd is None and gvy is None and gvx is None and gvz is None:
-                return (None,) * 9
-            res = ctx.sim._bwd(saved, re, z(gvy, sy), z(gvx, sx), z(gvz, sz), vel_in, buoyancy=ctx.buoyancy, g_d=None if gd is None else gd.contiguous())
-            res = density_bwd(ctx.sim, d_in, saved, re, res[-1], res[:3], vel_in, res[3] if vel_in is not None else None)
-            return None, res[0], res[1], res[2], res[3], (res[4] if vel_in is not None else None), None, None, None
+                return (None,) * 5
+            res = ctx.sim._bwd(saved, re, z(gvy, sy), z(gvx, sx), z(gvz, sz), vel_in, buoyancy=ctx.buoyancy, g_d=None if gd is None else gd.contiguous(), nsub=n)
+            res = density_bwd(ctx.sim, d_in, saved, re, res[-1], res[:3], vel_in, res[3] if vel_in is not None else None, nsub=n)
+            return res[0], res[1], res[2], res[3], (res[4] if vel_in is not None else None)
         if not (ctx.density or ctx.want_re) or gvy is not None or gvx is not None or gvz is not None:
-            res = ctx.sim._bwd(saved, re, z(gvy, sy), z(gvx, sx), z(gvz, sz), vel_in)
+            res = ctx.sim._bwd(saved, re, z(gvy, sy), z(gvx, sx), z(gvz, sz), vel_in, nsub=n)
             gi, g_re = res[:3], (res[3] if vel_in is not None else None)
         if ctx.density and gd is not None:          # added onto the velocity half's buffers and g_re
-            res = density_bwd(ctx.sim, d_in, saved, re, gd.contiguous(), gi, vel_in, g_re)
+            res = density_bwd(ctx.sim, d_in, saved, re, gd.contiguous(), gi, vel_in, g_re, nsub=n)
             od, gi, g_re = res[0], res[1:4], (res[4] if vel_in is not None else None)
         gi = gi if gi is not None else (None, None, None)
-        return None, od, gi[0], gi[1], gi[2], g_re, None, None, None
+        return od, gi[0], gi[1], gi[2], g_re
 
 
 class _ToFeature3DFn(torch.autograd.Function):
@@ -739,7 +873,7 @@ class Karman3DTrainer:
     (sol_adam_tf_step).  gts: [msteps] of (vy, vx, vz) ground-truth frames."""
 
     def __init__(self, net, scene, B, msteps, std_v, std_re, dt=1.0, res=None, beta1=0.9, beta2=0.999, eps=1e-8, conv_precision="split",
-                 use_graph=False, group=None, comm=None, schedule="manual", glue="fused", buoyancy=None, **solver):
+                 use_graph=False, group=None, comm=None, schedule="manual", glue="fused", buoyancy=None, diffusion_substeps=1, **solver):
         """schedule: "manual" (default) = the hand-written forward unroll + reverse sweep over the C ABI (_unrolled_schedule), "autograd" = the
         torch-autograd composition of the differentiable HIP ops (rounds 3-4; kept as the cross-check).
         use_graph: capture the whole forward unroll + reverse sweep ONCE into a hipGraph over static input buffers (the
@@ -748,7 +882,11 @@ class Karman3DTrainer:
         buoyancy=(fy, fx, fz) (buoyancy_force3d): the density pushes the velocity.  The schedule is unchanged; the solver pair is the buoyant
         one: the forward step is sol_karman3d_step_fwd_buoy and each step's input density is kept, the reverse sweep runs the buoyant
         velocity adjoint (g_dsum), then the density adjoint accumulating onto the velocity gradients, which carries the density cotangent
-        to the next (earlier) step (None at the last step: the loss does not look at the density).  Off, or zero: today's launches."""
+        to the next (earlier) step (None at the last step: the loss does not look at the density).  Off, or zero: today's launches.
+        diffusion_substeps=n (Karman3DFlow): n explicit diffusion substeps per solver step.  Manual schedule: diffuse_sub (M^(n-1) v) before
+        each step's solver launch, the solver pair on the scaled cfg, and diffuse_sub on the velocity cotangent after each step's adjoint
+        in the reverse sweep; the autograd schedule takes it through Karman3DFlow.step.  Kernel launches only, the ping-pong buffers are
+        the simulator's static ones: use_graph stays a graph of kernel nodes.  n = 1: today's launches."""
         from .trainer import _conv_precision_code
         from .dist import DPStep
         _lib.require_gpu()
@@ -756,8 +894,8 @@ class Karman3DTrainer:
         self.net, self.scene, self.B, self.ms = net, scene, B, msteps
         assert glue in ("fused", "torch")
         self.glue = glue          # reverse-sweep glue of the manual schedule: sol_karman3d_correct_bwd / _feature_bwd, or the torch elementwise composition
-        self.sim = Karman3DFlow(scene, B, dt=dt, res=res, buoyancy=buoyancy, **solver)
-        self.buoyancy = self.sim.buoyancy
+        self.sim = Karman3DFlow(scene, B, dt=dt, res=res, buoyancy=buoyancy, diffusion_substeps=diffusion_substeps, **solver)
+        self.buoyancy, self.nsub = self.sim.buoyancy, self.sim.nsub
         dev = scene.active.device
         self.std_v = torch.tensor([float(v) for v in std_v], dtype=torch.float32, device=dev)
         self._std_v_host = tuple(float(v) for v in std_v)
@@ -822,7 +960,7 @@ class Karman3DTrainer:
             feat = torch.empty(B, Y, X, Z, 4, dtype=torch.float32, device=vy.device)
             if self.buoyancy is not None:
                 d_ins.append(d)
-            d, *v = sim._fwd(d, v[0], v[1], v[2], re, saved, feat, fs, self.buoyancy)
+            d, *v = sim._fwd_sub(d, v[0], v[1], v[2], re, saved, feat, fs, self.buoyancy, self.nsub)
             out, state = sch.forward(feat)
             check(self.lib.sol_karman3d_correct(stream(), ptr(out), net.cout, sv[0], sv[1], sv[2], ptr(v[0]), ptr(v[1]), ptr(v[2]), B, Y, X, Z))
             li, gi = l2_loss_fwd_bwd(v, tuple(g[i] for g in self._gt), sv, gscale=1.0 / ms)
@@ -856,11 +994,13 @@ class Karman3DTrainer:
                 G[1][:, :, :X].add_(dx[..., 1], alpha=inv_in[1])
                 G[2][..., :Z].add_(dx[..., 2], alpha=inv_in[2])
             if self.buoyancy is not None:
-                *gv, g_dsum = sim._bwd(saved, re, G[0], G[1], G[2], buoyancy=self.buoyancy, g_d=g_d)
-                g_d, *gin = density_bwd(sim, d_ins[i], saved, re, g_dsum, gv)
+                *gv, g_dsum = sim._bwd(saved, re, G[0], G[1], G[2], buoyancy=self.buoyancy, g_d=g_d, nsub=self.nsub)
+                g_d, *gin = density_bwd(sim, d_ins[i], saved, re, g_dsum, gv, nsub=self.nsub)
                 d_ins[i] = None
             else:
-                gin = sim._bwd(saved, re, G[0], G[1], G[2])
+                gin = sim._bwd(saved, re, G[0], G[1], G[2], nsub=self.nsub)
+            if self.nsub > 1 and i > 0:             # the cotangent of M^(n-1) v -> the cotangent of v (the operator is symmetric); nobody reads step 0's
+                gin = list(diffuse_sub(sim, gin[0], gin[1], gin[2], re, self.nsub))
             keep[i] = None                          # (eager runs: the step's activations can go)
         losses = _lib.stack0(losses)
         loss = losses.sum() / ms
@@ -944,15 +1084,16 @@ class Karman3DRollout:
     """No-grad roll-out: nsteps x [solver step -> features / std -> CNN -> velocity += std * correction]
     (karman_apply.py:138-158 / the forward half of karman_train.py:397-426, three components)."""
 
-    def __init__(self, net, scene, B, std_v, std_re, dt=1.0, res=None, conv_precision="split", buoyancy=None, **solver):
-        """buoyancy=(fy, fx, fz) (buoyancy_force3d): the density pushes the velocity (the solver step is sol_karman3d_step_fwd_buoy)"""
+    def __init__(self, net, scene, B, std_v, std_re, dt=1.0, res=None, conv_precision="split", buoyancy=None, diffusion_substeps=1, **solver):
+        """buoyancy=(fy, fx, fz) (buoyancy_force3d): the density pushes the velocity (the solver step is sol_karman3d_step_fwd_buoy)
+        diffusion_substeps=n (Karman3DFlow): n explicit diffusion substeps per solver step; the features keep the true re"""
         from .trainer import _conv_precision_code
         from .schedule3d import NetSchedule3D
         _lib.require_gpu()
         self.lib = _lib.load()
         self.net, self.scene, self.B = net, scene, B
-        self.sim = Karman3DFlow(scene, B, dt=dt, res=res, buoyancy=buoyancy, **solver)
-        self.buoyancy = self.sim.buoyancy
+        self.sim = Karman3DFlow(scene, B, dt=dt, res=res, buoyancy=buoyancy, diffusion_substeps=diffusion_substeps, **solver)
+        self.buoyancy, self.nsub = self.sim.buoyancy, self.sim.nsub
         self.std_v = tuple(float(v) for v in std_v)
         self.feat_scale = [1.0 / self.std_v[0], 1.0 / self.std_v[1], 1.0 / self.std_v[2], 1.0 / float(std_re)]
         self.conv_precision = _conv_precision_code(conv_precision)

@@ -82,18 +82,19 @@ def agreed_buoyancy(recorded, flag, where):
     return norm(recorded)
 
 
-def add_substeps_arg(p, auto=True):
+def add_substeps_arg(p, auto=True, bound="1/4"):
     """--diffusion-substeps N|auto of karman.py (auto: the smallest stable count for the run's Reynolds numbers); the scripts that read
-    data take N only and default to what the data recorded"""
+    data take N only and default to what the data recorded.  bound: the single stencil's stability bound in the help text (karman3d.py: 1/6)"""
     p.add_argument("--diffusion-substeps", default=None, metavar="N|auto" if auto else "N",
-                   help="explicit diffusion substeps per solver step (the single stencil is stable only while dt res^2 / Re <= 1/4)%s.  "
+                   help="explicit diffusion substeps per solver step (the single stencil is stable only while dt res^2 / Re <= %s)%s.  "
                         "Stored with the data like the scene; absent: %s"
-                        % ("; auto: the smallest stable count (min_diffusion_substeps) for the run's Reynolds numbers" if auto else "",
+                        % (bound, "; auto: the smallest stable count (min_diffusion_substeps) for the run's Reynolds numbers" if auto else "",
                            "1" if auto else "what the data recorded"))
 
 
-def substeps_from_args(params, re_numbers=None, res=None, dt=1.0):
-    """n of --diffusion-substeps: an integer >= 1, `auto` (re_numbers given: ops.min_diffusion_substeps over them), or None when absent"""
+def substeps_from_args(params, re_numbers=None, res=None, dt=1.0, minimum=None):
+    """n of --diffusion-substeps: an integer >= 1, `auto` (re_numbers given: ops.min_diffusion_substeps over them -- or `minimum`, a function
+    of the same arguments: karman3d.min_diffusion_substeps3d), or None when absent"""
     from sol_amd import ops
     v = params.get("diffusion_substeps")
     if v is None:
@@ -101,7 +102,7 @@ def substeps_from_args(params, re_numbers=None, res=None, dt=1.0):
     if str(v).strip().lower() == "auto":
         if re_numbers is None:
             raise SystemExit("--diffusion-substeps auto belongs to data generation; this script takes the count from the data (or N)")
-        return ops.min_diffusion_substeps(min(float(r) for r in re_numbers), res, dt)
+        return (minimum or ops.min_diffusion_substeps)(min(float(r) for r in re_numbers), res, dt)
     try:
         return ops.diffusion_substeps_arg(int(str(v)), "--diffusion-substeps")
     except ValueError:

@@ -7,14 +7,17 @@ karman_apply.py:20-31 (-r res of the reference axis -> grid 2r x r x r, --re, -t
 the 2-D workflow carries over.  Frames are written like the 2-D scenes: dens_%06d.npz [1,Y,X,Z,1], velo_%06d.npz
 [1,Y+1,X+1,Z+1,3] (staggered tensor, zero padded at the high ends, components reversed on disk as PhiFlow does).
 --buoyancy FY[,FX[,FZ]]: the density pushes the velocity (generation, --model roll-out and --train-sol alike); recorded in params.pickle
-and in the model file as "buoyancy" (a triple, or None: off), so that a roll-out of the trained corrector picks it up."""
+and in the model file as "buoyancy" (a triple, or None: off), so that a roll-out of the trained corrector picks it up.
+--diffusion-substeps N|auto: the velocity is diffused by N explicit substeps per solver step (the single stencil is stable only while
+dt res^2 / Re <= 1/6; auto: karman3d.min_diffusion_substeps3d of --re), for generation, --model roll-out and --train-sol alike; recorded
+in params.pickle and in the model file as "diffusion_substeps" and picked up from there like the force."""
 import argparse
 import pickle
 
 import numpy as np
 import torch
 
-from _common import add_buoyancy_arg, agreed_buoyancy, buoyancy_from_args, logger, select_gpu
+from _common import add_buoyancy_arg, add_substeps_arg, agreed_buoyancy, agreed_substeps, buoyancy_from_args, logger, select_gpu, substeps_from_args
 import sol_amd
 from sol_amd import karman3d as k3, scene, synthetic
 
@@ -28,7 +31,9 @@ def staggered3d(vy, vx, vz):
     return t
 
 
-def main(argv=None):
+def parse_params(argv=None):
+    """The flags, with "buoyancy" as a triple (or None) and "diffusion_substeps" as N, `auto` resolved from --re, or None when absent.
+    Touches no device."""
     p = argparse.ArgumentParser(description="Parameter Parser", formatter_class=argparse.ArgumentDefaultsHelpFormatter)
     p.add_argument("--gpu", default="0", help="visible GPUs")
     p.add_argument("-o", "--output", default=None, help="path to an output directory")
@@ -46,8 +51,30 @@ def main(argv=None):
     p.add_argument("--pressure-solver", default="auto", choices=k3.PRESSURE_SOLVERS3D,
                    help="direct (capacitance blob), cg (preconditioned CG, any mask) or auto (direct where it builds)")
     add_buoyancy_arg(p, ncomp=3)
+    add_substeps_arg(p, bound="1/6")
     params = vars(p.parse_args(argv))
     params["buoyancy"] = buoyancy_from_args(params, ncomp=3)
+    params["diffusion_substeps"] = substeps_from_args(params, [params["re"]], params["res"], minimum=k3.min_diffusion_substeps3d)
+    return params
+
+
+def apply_model_record(params, record=None):
+    """The run's parameters as recorded in params.pickle: parse_params' with the force and the substep count the run uses.  record: the
+    dict of the --model file (None: no model) -- the force and the count the corrector was trained with win, a flag that contradicts them
+    is an error, and a model without a record takes the flag.  No flag and no record: no force, one substep."""
+    params = dict(params)
+    if record is not None and "buoyancy" in record:
+        params["buoyancy"] = agreed_buoyancy(record["buoyancy"], params["buoyancy"], params["model"])
+    if record is not None and "diffusion_substeps" in record:
+        params["diffusion_substeps"] = agreed_substeps(record["diffusion_substeps"], params["diffusion_substeps"], params["model"])
+    params["diffusion_substeps"] = params["diffusion_substeps"] or 1
+    return params
+
+
+def main(argv=None):
+    params = parse_params(argv)
+    blob = torch.load(params["model"], map_location="cpu") if params["model"] else None
+    params = apply_model_record(params, blob)
     select_gpu(params["gpu"])
     log = logger()
     res = params["res"]
@@ -55,11 +82,8 @@ def main(argv=None):
     dev = "cuda"
     active = np.load(params["obstacle_mask"]) if params["obstacle_mask"] else None
     sc = k3.Scene3D(Y, X, Z, length=float(params["len"]), device=dev, active=active, pressure_solver=params["pressure_solver"])
-    blob = torch.load(params["model"], map_location="cpu") if params["model"] else None
-    if blob is not None and "buoyancy" in blob:     # the force the corrector was trained with; a model without the record takes the flag
-        params["buoyancy"] = agreed_buoyancy(blob["buoyancy"], params["buoyancy"], params["model"])
-    buoyancy = params["buoyancy"]
-    sim = k3.Karman3DFlow(sc, 1, buoyancy=buoyancy)
+    buoyancy, nsub = params["buoyancy"], params["diffusion_substeps"]
+    sim = k3.Karman3DFlow(sc, 1, buoyancy=buoyancy, diffusion_substeps=nsub)
     f = lambda a: torch.as_tensor(a, dtype=torch.float32, device=dev).contiguous()
     # karman.py:106-110 in 3-D: uniform flow along y + a sideways poke behind the obstacle
     vy = np.ones((1, Y + 1, X, Z), dtype=np.float32)
@@ -77,11 +101,12 @@ def main(argv=None):
     log.info(params)
     log.info("pressure solver: %s" % sc.pressure_solver)
     log.info("buoyancy: %s" % (buoyancy,))
+    log.info("diffusion substeps: %d" % nsub)
     net = ro = None
     if blob is not None:
         net = k3.MarsMoon3D(device=dev)
         net.set_weights([w.numpy() for w in blob["weights"]])
-        ro = k3.Karman3DRollout(net, sc, 1, blob["std_v"], blob["std_re"], buoyancy=buoyancy)
+        ro = k3.Karman3DRollout(net, sc, 1, blob["std_v"], blob["std_re"], buoyancy=buoyancy, diffusion_substeps=nsub)
     frames = []
     with torch.no_grad():
         for i in range(1, params["simsteps"]):
@@ -103,7 +128,7 @@ def main(argv=None):
         w = net.get_weights()
         w[22] = w[22] * 0.01
         net.set_weights(w)
-        tr = k3.Karman3DTrainer(net, sc, 1, ms, std_v, max(params["re"], 1.0), use_graph=True, buoyancy=buoyancy)
+        tr = k3.Karman3DTrainer(net, sc, 1, ms, std_v, max(params["re"], 1.0), use_graph=True, buoyancy=buoyancy, diffusion_substeps=nsub)
         rng = np.random.default_rng(params["seed"])
         for it in range(params["train_steps"]):
             k = int(rng.integers(0, len(frames) - ms))
@@ -112,7 +137,7 @@ def main(argv=None):
             log.info("train step {:04d}: loss={}".format(it + 1, loss))
         if path:
             torch.save({"name": net.name, "weights": [torch.as_tensor(a) for a in net.get_weights()], "std_v": std_v,
-                        "std_re": max(params["re"], 1.0), "buoyancy": buoyancy}, path + "/model3d.pt")
+                        "std_re": max(params["re"], 1.0), "buoyancy": buoyancy, "diffusion_substeps": nsub}, path + "/model3d.pt")
     return path if path else loss
 
 

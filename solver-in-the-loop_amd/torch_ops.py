@@ -8,7 +8,8 @@ dispatcher (torch.ops.sol.karman_step, .conv5x5, .burgers_step, .adam_tf_step; .
 density output, over sol_karman_density_bwd; .karman_step_re = karman_step differentiable with respect to re as well, over the _re
 adjoints; .karman_step_buoy = the large-grid step with the buoyancy force (fy, fx): the density pushes the velocity and is always in the
 graph; .karman_step_sub = karman_step with nsub explicit diffusion substeps, composing with the density, re and buoyancy modes;
-.karman3d_step_buoy = the same for the 3-D step, force (fy, fx, fz)).  Scene constants (masks, solver blobs, the cfg struct) are not tensors: they are registered once with register_scene() and
+.karman3d_step_buoy = the same for the 3-D step, force (fy, fx, fz); .karman3d_step_sub = the 3-D step with nsub explicit diffusion
+substeps, composing with its density, re and buoyancy modes).  Scene constants (masks, solver blobs, the cfg struct) are not tensors: they are registered once with register_scene() and
 referred to by an integer handle."""
 import torch
 
@@ -30,6 +31,7 @@ _LIB.define("karman3d_step(Tensor d, Tensor vy, Tensor vx, Tensor vz, Tensor re,
 _LIB.define("karman3d_step_dens(Tensor d, Tensor vy, Tensor vx, Tensor vz, Tensor re, int scene) -> (Tensor, Tensor, Tensor, Tensor)")
 _LIB.define("karman3d_step_re(Tensor d, Tensor vy, Tensor vx, Tensor vz, Tensor re, int scene, bool density=False) -> (Tensor, Tensor, Tensor, Tensor)")
 _LIB.define("karman3d_step_buoy(Tensor d, Tensor vy, Tensor vx, Tensor vz, Tensor re, int scene, float fy, float fx, float fz, bool re_grad=False) -> (Tensor, Tensor, Tensor, Tensor)")
+_LIB.define("karman3d_step_sub(Tensor d, Tensor vy, Tensor vx, Tensor vz, Tensor re, int scene, int nsub, bool density=False, bool re_grad=False, float fy=0.0, float fx=0.0, float fz=0.0) -> (Tensor, Tensor, Tensor, Tensor)")
 _LIB.define("karman3d_density_bwd(Tensor d, Tensor svy, Tensor svx, Tensor svz, Tensor re, Tensor gd, int scene) -> (Tensor, Tensor, Tensor, Tensor)")
 _LIB.define("conv3d(Tensor x, Tensor w, Tensor b, Tensor? residual, bool lrelu, float slope) -> Tensor")
 _LIB.define("burgers_step(Tensor vy, Tensor vx, Tensor? fy, Tensor? fx, float dx, float dt, float nu) -> (Tensor, Tensor)")
@@ -182,12 +184,14 @@ def register_scene3d(sim):
 
 # the step's three differentiable forms are the modes of karman3d._Karman3DStepFn, as for the 2-D step: karman3d_step (the density is a
 # passive tracer, re is data), karman3d_step_dens (opt-in: the density output is differentiable too) and karman3d_step_re (opt-in:
-# differentiable with respect to re as well; density: d_out stays in the graph as in karman3d_step_dens)
+# differentiable with respect to re as well; density: d_out stays in the graph as in karman3d_step_dens).  They run the registered
+# simulator's own diffusion_substeps (1 unless it was built with another count); karman3d_step_sub names the count per call
 def _karman3d_fn(d, vy, vx, vz, re, scene, density, want_re):
     from . import karman3d as k3
     re = _lib.f32(re)
     want_re = want_re and torch.is_grad_enabled() and re.requires_grad
-    return k3._Karman3DStepFn.apply(_SIMS3D[scene], _lib.f32(d), _lib.f32(vy), _lib.f32(vx), _lib.f32(vz), re, density, want_re, None)
+    sim = _SIMS3D[scene]
+    return k3._Karman3DStepFn.apply(sim, _lib.f32(d), _lib.f32(vy), _lib.f32(vx), _lib.f32(vz), re, density, want_re, None, sim.nsub)
 
 
 def _karman3d_step(d, vy, vx, vz, re, scene):
@@ -197,7 +201,8 @@ def _karman3d_step(d, vy, vx, vz, re, scene):
 # karman3d_step_buoy: the buoyant mode of karman3d._Karman3DStepFn (a force of (0, 0, 0) is the plain step, density in the graph)
 def _karman3d_buoy(d, vy, vx, vz, re, scene, fy, fx, fz, re_grad=False):
     with torch.no_grad():
-        return _SIMS3D[scene]._fwd(*(_lib.f32(t) for t in (d, vy, vx, vz, re)), buoyancy=(float(fy), float(fx), float(fz)))
+        sim = _SIMS3D[scene]
+        return sim._fwd_sub(*(_lib.f32(t) for t in (d, vy, vx, vz, re)), buoyancy=(float(fy), float(fx), float(fz)), nsub=sim.nsub)
 
 
 def _karman3d_buoy_fn(d, vy, vx, vz, re, scene, fy, fx, fz, re_grad=False):
@@ -205,8 +210,32 @@ def _karman3d_buoy_fn(d, vy, vx, vz, re, scene, fy, fx, fz, re_grad=False):
     f = k3.buoyancy_force3d((fy, fx, fz))
     re = _lib.f32(re)
     want_re = bool(re_grad) and torch.is_grad_enabled() and re.requires_grad
-    return k3._Karman3DStepFn.apply(_SIMS3D[scene], _lib.f32(d), _lib.f32(vy), _lib.f32(vx), _lib.f32(vz), re, True, want_re,
-                                    f if k3._buoyant3d(f) else None)
+    sim = _SIMS3D[scene]
+    return k3._Karman3DStepFn.apply(sim, _lib.f32(d), _lib.f32(vy), _lib.f32(vx), _lib.f32(vz), re, True, want_re,
+                                    f if k3._buoyant3d(f) else None, sim.nsub)
+
+
+# karman3d_step_sub: the step with nsub explicit diffusion substeps (karman3d._Karman3DStepFn's substep mode), composing with the other
+# modes: density (d_out in the graph), re_grad and a buoyancy force (fy, fx, fz)
+def _karman3d_sub_args(nsub, fy, fx, fz):
+    from . import karman3d as k3
+    n = ops.diffusion_substeps_arg(nsub, "torch.ops.sol.karman3d_step_sub: nsub")
+    f = k3.buoyancy_force3d((fy, fx, fz))
+    return n, (f if k3._buoyant3d(f) else None)
+
+
+def _karman3d_sub(d, vy, vx, vz, re, scene, nsub, density=False, re_grad=False, fy=0.0, fx=0.0, fz=0.0):
+    n, f = _karman3d_sub_args(nsub, fy, fx, fz)
+    with torch.no_grad():
+        return _SIMS3D[scene]._fwd_sub(*(_lib.f32(t) for t in (d, vy, vx, vz, re)), buoyancy=f, nsub=n)
+
+
+def _karman3d_sub_fn(d, vy, vx, vz, re, scene, nsub, density=False, re_grad=False, fy=0.0, fx=0.0, fz=0.0):
+    from . import karman3d as k3
+    n, f = _karman3d_sub_args(nsub, fy, fx, fz)
+    re = _lib.f32(re)
+    want_re = bool(re_grad) and torch.is_grad_enabled() and re.requires_grad
+    return k3._Karman3DStepFn.apply(_SIMS3D[scene], _lib.f32(d), _lib.f32(vy), _lib.f32(vx), _lib.f32(vz), re, bool(density), want_re, f, n)
 
 
 def _karman3d_density_bwd(d, svy, svx, svz, re, gd, scene):
@@ -224,5 +253,7 @@ _LIB.impl("karman3d_step_dens", lambda d, vy, vx, vz, re, scene: _karman3d_fn(d,
 _LIB.impl("karman3d_step_re", lambda d, vy, vx, vz, re, scene, density=False: _karman3d_fn(d, vy, vx, vz, re, scene, bool(density), True), "AutogradCUDA")
 _LIB.impl("karman3d_step_buoy", _karman3d_buoy, "CUDA")
 _LIB.impl("karman3d_step_buoy", _karman3d_buoy_fn, "AutogradCUDA")
+_LIB.impl("karman3d_step_sub", _karman3d_sub, "CUDA")
+_LIB.impl("karman3d_step_sub", _karman3d_sub_fn, "AutogradCUDA")
 _LIB.impl("karman3d_density_bwd", _karman3d_density_bwd, "CUDA")
 _LIB.impl("conv3d", _conv3d, "AutogradCUDA")
