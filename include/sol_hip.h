@@ -81,6 +81,9 @@ int sol_abi_sizes(int32_t* karman_cfg, int32_t* burgers_cfg, int32_t* train_cfg)
  *   k2d_dens_adj_tile (1) karman-2d, any grid: the density adjoint's fixed-point scatter (sol_karman_density_bwd) goes through an int64 LDS window per
  *                       workgroup (16 x 16 cells + halo 4), flushed with one global atomic per non-zero cell; 0: every contribution is a global atomic.
  *                       Same results bit for bit
+ *   k2d_mc_tile (1)     karman-2d large grids: the MacCormack advection ("MACCORMACK ADVECTION" below) as one launch on 16 x 32 tiles with the
+ *                       semi-Lagrangian values of a halo of 2 in LDS (a corner beyond the halo is evaluated on the fly); 0: two launches through
+ *                       the workspace.  Same results bit for bit
  *   k3d_dens_adj_tile (1) karman-3d: the density adjoint's fixed-point scatter (sol_karman3d_density_bwd) goes through an int64 LDS window per
  *                       workgroup (4 x 4 columns + halo 2, all k), flushed with one global atomic per non-zero cell; 0, or a window beyond
  *                       64 KB (Z > 128): every contribution is a global atomic.  Same results bit for bit
@@ -395,6 +398,107 @@ int32_t sol_karman_diffuse_sub_max(void);
 size_t sol_karman_diffuse_sub_workspace_bytes(const sol_karman_cfg* cfg, int32_t m, int32_t chunk);
 int sol_karman_diffuse_sub(const sol_karman_cfg* cfg, void* stream, const float* vy_in, const float* vx_in, const float* re,
                            float* vy_out, float* vx_out, int32_t m, int32_t chunk, void* workspace, size_t workspace_bytes);
+
+/* MACCORMACK ADVECTION on the large-grid step (csrc/karman_maccormack.hip; multi-launch path only; advection = "mac_cormack" on the
+ * Python surface, PhiFlow's advect.mac_cormack(field, velocity, dt, correction_strength)).  The plain step advects semi-Lagrangian
+ * (k_l_advect), whose numerical diffusion is the coarse solver's largest error.  c is the post-diffusion velocity (sv_y, sv_x); f is one
+ * advected array: c_y on its faces, c_x on its faces, or the density on cells (with inflow added first when cfg.inflow_before); u is c
+ * interpolated to the array's sample point with exactly the expressions of k_l_advect; S_g(x) is the bilinear sample of array g in the
+ * array's own extrapolation mode: index clamp for the velocity, one ring of zero ghost cells for the density.
+ *     h(x)   = S_f(x - u dt)                     the semi-Lagrangian value, unmasked, no inflow added
+ *     b(x)   = S_h(x + u dt)                     h carried back, same u, same extrapolation mode
+ *     cor(x) = h(x) + (s/2) (f(x) - b(x))        s = correction_strength, 0 <= s <= 1
+ *     lo, hi = min, max of the four values the FIRST gather read (after clamping; ghost zeros count)
+ *     out(x) = cor(x) if lo <= cor(x) <= hi else h(x)
+ * then as in the plain step: velocity times the hard-BC face mask, density + inflow dt when the inflow comes after.  TIE RULE: the compare
+ * is inclusive on both sides and has no tolerance (cor == lo or cor == hi keeps cor); a NaN cor reverts to h.  fp32 spelling: h is the
+ * bilinear expression of k_l_advect with contraction off, cor = fl(h + fl(fl(0.5f s) * fl(f - b))).
+ * The three-term form is PhiFlow 1.5's mac_cormack, the revert-to-semi-Lagrangian limiter is Selle et al. 2008 / PhiFlow 2: both as
+ * RECALLED -- parity with PhiFlow is unpinned, as for the buoyancy term.
+ * The gradient is the derivative with every decision frozen as the forward step took it: the floorf's, the clamps and the limiter (what
+ * torch.where gives a reference).  Where a point reverted, its adjoint is the plain semi-Lagrangian one.  For a cotangent g of out (the
+ * velocity's is g_a) and kept = 1 where cor was kept:  g_b = -(s/2) kept g;  g_f += (s/2) kept g;  g_h = g + (g_b scattered through the
+ * four corners of the gather at x + u dt);  g_u += +(dt/dx) g_b dS_h/d(offset);  then the semi-Lagrangian adjoint applied to g_h in place
+ * of g.  h is recomputed from the saved c: the forward step saves nothing new.  Every scattered sum (g_h included) is 64-bit fixed point
+ * with the one scale of its cotangent (csrc/fixed_scatter.hpp): bit-reproducible; a non-finite cotangent poisons its simulation as in the
+ * plain adjoints.  Options: k2d_mc_tile (forward), k2d_adj_tile / k2d_dens_adj_tile (the adjoints' LDS windows), equal bits either way.
+ *   sol_karman_step_fwd_large_adv / _saved_adv: every argument of the _buoy form, then advection (0 semi-Lagrangian: that form's launches
+ *     and bits; 1 MacCormack) and correction_strength (checked to lie in [0, 1] for either).  A zero force is the unbuoyant step.  Workspace:
+ *     the *_adv_workspace_bytes_for function of the entry point (advection = 0: the plain size).
+ *   sol_karman_step_bwd_large_adv / _adv_re, sol_karman_density_bwd_adv / _adv_re: every argument of the _buoy / _buoy_re form (of the
+ *     plain / _re form for the density), then the same two.  Workspace: sol_karman_step_bwd_large_adv_workspace_bytes_for(cfg, header,
+ *     with_re, advection), sol_karman_density_bwd_adv_workspace_bytes(cfg, with_re, advection).  The density forms take Y, X >= 16 under
+ *     advection = 1.
+ *   sol_karman_advect / sol_karman_advect_bwd: the stage alone and its transpose, any Y, X >= 16, for tests and callers that compose by
+ *     hand: (d_in, sv_y, sv_x) -> (d_out, a_y, a_x) masked / with inflow as above; cotangents of those -> (g_d_in, g_sv_y, g_sv_x).
+ *     tile_window: 1 = LDS windows, 0 = global atomics only.  Workspaces: sol_karman_advect_workspace_bytes(cfg, advection) (0 bytes and
+ *     NULL for advection = 0), sol_karman_advect_bwd_workspace_bytes(cfg).
+ * None of these synchronises, allocates or reads anything on the host: capturable.  karman-3d and the one-workgroup kernels advect
+ * semi-Lagrangian only. */
+size_t sol_karman_advect_workspace_bytes(const sol_karman_cfg* cfg, int32_t advection);
+int sol_karman_advect(const sol_karman_cfg* cfg, void* stream, const float* d_in, const float* svy, const float* svx,
+                      const float* active, const float* inflow, int32_t advection, float correction_strength,
+                      float* d_out, float* ay, float* ax, void* workspace, size_t workspace_bytes);
+size_t sol_karman_advect_bwd_workspace_bytes(const sol_karman_cfg* cfg);
+int sol_karman_advect_bwd(const sol_karman_cfg* cfg, void* stream, const float* d_in, const float* svy, const float* svx,
+                          const float* active, const float* inflow, int32_t advection, float correction_strength,
+                          const float* g_d_out, const float* g_ay, const float* g_ax,
+                          float* g_d_in, float* g_svy, float* g_svx, int32_t tile_window, void* workspace, size_t workspace_bytes);
+size_t sol_karman_step_fwd_large_adv_workspace_bytes_for(const sol_karman_cfg* cfg, const int32_t* direct_header_host, int32_t advection);
+size_t sol_karman_step_fwd_large_saved_adv_workspace_bytes_for(const sol_karman_cfg* cfg, const int32_t* direct_header_host, int32_t advection);
+int sol_karman_step_fwd_large_adv(const sol_karman_cfg* cfg, void* stream,
+                                  const float* d_in, const float* vy_in, const float* vx_in,
+                                  const float* re, const float* active, const float* inflow,
+                                  const float* velBCy, const float* velBCyMask, int64_t bc_batch_stride,
+                                  float* d_out, float* vy_out, float* vx_out,
+                                  float* feat_out, const float* feat_scale,
+                                  const int32_t* direct_header_host,
+                                  const float* box_blob, const int32_t* box_header_host, int32_t* cg_info,
+                                  float* p_inout, void* workspace, size_t workspace_bytes, float fy, float fx,
+                                  int32_t advection, float correction_strength);
+int sol_karman_step_fwd_large_saved_adv(const sol_karman_cfg* cfg, void* stream,
+                                        const float* d_in, const float* vy_in, const float* vx_in,
+                                        const float* re, const float* active, const float* inflow,
+                                        const float* velBCy, const float* velBCyMask, int64_t bc_batch_stride,
+                                        float* d_out, float* vy_out, float* vx_out, float* saved_vy, float* saved_vx,
+                                        const int32_t* direct_header_host,
+                                        const float* box_blob, const int32_t* box_header_host, int32_t* cg_info,
+                                        void* workspace, size_t workspace_bytes, float fy, float fx,
+                                        int32_t advection, float correction_strength);
+size_t sol_karman_step_bwd_large_adv_workspace_bytes_for(const sol_karman_cfg* cfg, const int32_t* direct_header_host, int32_t with_re,
+                                                         int32_t advection);
+int sol_karman_step_bwd_large_adv(const sol_karman_cfg* cfg, void* stream,
+                                  const float* saved_vy, const float* saved_vx, const float* re, const float* active,
+                                  const float* velBCyMask, int64_t bc_batch_stride,
+                                  const float* g_vy_out, const float* g_vx_out, float* g_vy_in, float* g_vx_in,
+                                  const int32_t* direct_header_host,
+                                  const float* box_blob, const int32_t* box_header_host, int32_t* cg_info,
+                                  void* workspace, size_t workspace_bytes,
+                                  float fy, float fx, const float* g_d_out, float* g_dsum,
+                                  int32_t advection, float correction_strength);
+int sol_karman_step_bwd_large_adv_re(const sol_karman_cfg* cfg, void* stream,
+                                     const float* saved_vy, const float* saved_vx, const float* re, const float* active,
+                                     const float* velBCyMask, int64_t bc_batch_stride,
+                                     const float* g_vy_out, const float* g_vx_out, float* g_vy_in, float* g_vx_in,
+                                     const int32_t* direct_header_host,
+                                     const float* box_blob, const int32_t* box_header_host, int32_t* cg_info,
+                                     void* workspace, size_t workspace_bytes,
+                                     const float* vy_in, const float* vx_in, float* g_re, int accumulate_re,
+                                     float fy, float fx, const float* g_d_out, float* g_dsum,
+                                     int32_t advection, float correction_strength);
+size_t sol_karman_density_bwd_adv_workspace_bytes(const sol_karman_cfg* cfg, int32_t with_re, int32_t advection);
+int sol_karman_density_bwd_adv(const sol_karman_cfg* cfg, void* stream,
+                               const float* d_in, const float* inflow, const float* saved_vy, const float* saved_vx,
+                               const float* re, const float* velBCyMask, int64_t bc_batch_stride,
+                               const float* g_d_out, float* g_d_in, float* g_vy_in, float* g_vx_in, int accumulate,
+                               void* workspace, size_t workspace_bytes, int32_t advection, float correction_strength);
+int sol_karman_density_bwd_adv_re(const sol_karman_cfg* cfg, void* stream,
+                                  const float* d_in, const float* inflow, const float* saved_vy, const float* saved_vx,
+                                  const float* re, const float* velBCyMask, int64_t bc_batch_stride,
+                                  const float* g_d_out, float* g_d_in, float* g_vy_in, float* g_vx_in, int accumulate,
+                                  void* workspace, size_t workspace_bytes,
+                                  const float* vy_in, const float* vx_in, float* g_re, int accumulate_re,
+                                  int32_t advection, float correction_strength);
 
 /* active  [Y,X]  1 - obstacle mask (cell centres inside Obstacle geometries -> 0)
  * inflow  [Y,X]  inflow rate mask (Inflow(box[5:10,25:75]) -> 1 inside)

@@ -92,6 +92,22 @@ _SIGS = {
     "sol_karman_diffuse_sub_max": (C.c_int32, []),
     "sol_karman_diffuse_sub_workspace_bytes": (C.c_size_t, [_P, C.c_int32, C.c_int32]),
     "sol_karman_diffuse_sub": (C.c_int, [_P] * 7 + [C.c_int32] * 2 + [_P, C.c_size_t]),
+    # MacCormack advection (csrc/karman_maccormack.hip): the _adv forms = the _buoy forms' arguments + (advection, correction_strength)
+    "sol_karman_advect_workspace_bytes": (C.c_size_t, [_P, C.c_int32]),
+    "sol_karman_advect": (C.c_int, [_P] * 7 + [C.c_int32, C.c_float] + [_P] * 4 + [C.c_size_t]),
+    "sol_karman_advect_bwd_workspace_bytes": (C.c_size_t, [_P]),
+    "sol_karman_advect_bwd": (C.c_int, [_P] * 7 + [C.c_int32, C.c_float] + [_P] * 6 + [C.c_int32, _P, C.c_size_t]),
+    "sol_karman_step_fwd_large_adv_workspace_bytes_for": (C.c_size_t, [_P, _P, C.c_int32]),
+    "sol_karman_step_fwd_large_saved_adv_workspace_bytes_for": (C.c_size_t, [_P, _P, C.c_int32]),
+    "sol_karman_step_fwd_large_adv": (C.c_int, [_P] * 10 + [C.c_int64] + [_P] * 11 + [C.c_size_t] + [C.c_float] * 2 + [C.c_int32, C.c_float]),
+    "sol_karman_step_fwd_large_saved_adv": (C.c_int, [_P] * 10 + [C.c_int64] + [_P] * 10 + [C.c_size_t] + [C.c_float] * 2 + [C.c_int32, C.c_float]),
+    "sol_karman_step_bwd_large_adv_workspace_bytes_for": (C.c_size_t, [_P, _P, C.c_int32, C.c_int32]),
+    "sol_karman_step_bwd_large_adv": (C.c_int, [_P] * 7 + [C.c_int64] + [_P] * 9 + [C.c_size_t] + [C.c_float] * 2 + [_P] * 2 + [C.c_int32, C.c_float]),
+    "sol_karman_step_bwd_large_adv_re": (C.c_int, [_P] * 7 + [C.c_int64] + [_P] * 9 + [C.c_size_t] + [_P] * 3 + [C.c_int] + [C.c_float] * 2 + [_P] * 2
+                                         + [C.c_int32, C.c_float]),
+    "sol_karman_density_bwd_adv_workspace_bytes": (C.c_size_t, [_P, C.c_int32, C.c_int32]),
+    "sol_karman_density_bwd_adv": (C.c_int, [_P] * 8 + [C.c_int64] + [_P] * 4 + [C.c_int, _P, C.c_size_t] + [C.c_int32, C.c_float]),
+    "sol_karman_density_bwd_adv_re": (C.c_int, [_P] * 8 + [C.c_int64] + [_P] * 4 + [C.c_int, _P, C.c_size_t] + [_P] * 3 + [C.c_int] + [C.c_int32, C.c_float]),
     "sol_karman_precond_supported": (C.c_int, [C.c_int32, C.c_int32]),
     "sol_karman_step_fwd": (C.c_int, [C.POINTER(KarmanCfg), _P] + [_P] * 8 + [C.c_int64] + [_P] * 6 + [C.POINTER(C.c_float), _P]),
     "sol_karman_step_bwd": (C.c_int, [C.POINTER(KarmanCfg), _P] + [_P] * 5 + [C.c_int64] + [_P] * 3 + [C.POINTER(C.c_float)] + [_P] * 3),

@@ -46,7 +46,26 @@ struct SolLargeStep {
     float *d_out, *vy_out, *vx_out, *feat_out;
     const float* feat_scale;
     float buoy_y = 0.f, buoy_x = 0.f;      // dt F of the buoyancy term (karman_buoyancy.hip); both zero = none: the plain step's launches
+    int advection = 0;                     // 0: k_l_advect (semi-Lagrangian); 1: the MacCormack advection (karman_maccormack.hip) with
+    float mc_strength = 1.f;               //    this correction strength on the workspace part mc_ws (sol_mc_bytes)
+    void* mc_ws = nullptr;
 };
+// the advection launch alone: k_l_advect on a given post-diffusion velocity (karman_large.hip), and the MacCormack form of it
+// (karman_maccormack.hip: d_out NULL = the velocity alone; ws holds sol_mc_bytes); sol_mc_check: the two arguments of the _adv entry points
+int sol_large_advect(const sol_karman_cfg* c, hipStream_t s, const float* d_in, const float* svy, const float* svx, const float* active,
+                     const float* inflow, float* d_out, float* vy_out, float* vx_out);
+size_t sol_mc_bytes(const sol_karman_cfg* c);
+int sol_mc_advect(const sol_karman_cfg* c, hipStream_t s, float strength, const float* d_in, const float* svy, const float* svx, const float* active,
+                  const float* inflow, float* d_out, float* vy_out, float* vx_out, void* ws);
+int sol_mc_check(const char* who, int32_t advection, float strength);
+// the MacCormack advection adjoints in place of k_lb_advect_adj* (g_a, its max in gmax -> added onto the cleared int64 g_c) and of
+// k_kd_advect_adj* (g_d_out, its max in gmax -> added onto the cleared int64 gD, gU written); ws holds sol_mc_adj_bytes; tile: LDS windows
+// or global atomics only (equal bits); mc = false: the semi-Lagrangian adjoint by the same kernels
+size_t sol_mc_adj_bytes(const sol_karman_cfg* c);
+int sol_mc_adj_vel(const sol_karman_cfg* c, hipStream_t s, bool mc, float strength, const float* svy, const float* svx, const float* gay, const float* gax,
+                   const unsigned* gmax, long long* gcy, long long* gcx, void* ws, bool tile);
+int sol_mc_adj_den(const sol_karman_cfg* c, hipStream_t s, bool mc, float strength, const float* d_in, const float* inflow, const float* svy, const float* svx,
+                   const float* g_d_out, const unsigned* gmax, long long* gD, float* gUy, float* gUx, void* ws, bool tile);
 // the buoyancy term onto the advected velocity (f = dt F; nothing is launched for f = (0, 0)) and its transpose (karman_buoyancy.hip):
 // g_dsum = g_d_out (NULL = zero) + the face-to-cell transpose of (gy, gx); gmax = the absmax slots of k_lb_ga or NULL (poisoning)
 int sol_buoyancy_add(hipStream_t s, int B, int Y, int X, const float* active, const float* d, float fy, float fx, float* vy, float* vx);
@@ -289,6 +308,8 @@ struct SolOptions {
     int k3d_tile;         // 1: karman-3d advection from LDS tiles holding the full z column + halo; 0 (default, measured faster at B <= 2): wave-per-column gathers from global memory
     int k3d_dens_adj_tile;// 1 (default): the karman-3d density adjoint (karman3d_density_bwd.hip) scatters its field term into an int64 LDS window per tile of
                           //    4 x 4 columns (k3d_advect_adj_tile); 0: global atomics only (k3d_advect_adj).  Same results bit for bit
+    int k2d_mc_tile;      // 1 (default): the MacCormack advection of the large-grid karman-2d step (karman_maccormack.hip) as one launch on tiles with the
+                          //    semi-Lagrangian values of a halo in LDS (k_mc_tile); 0: two launches through the workspace (k_mc_hat, k_mc_out).  Same results bit for bit
 };
 SolOptions& sol_opt();
 

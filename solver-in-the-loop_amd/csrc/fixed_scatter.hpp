@@ -10,7 +10,9 @@
 //               simulation and read back by every later kernel (fx_scale).
 //   Range       int64 leaves 2^25 above max|g_a| for a single contribution.  A FINITE contribution beyond that saturates in __float2ll_rn:
 //               the back-trace term is g_a times a DIFFERENCE of the saved velocity times dt/dx, so that takes |dv| dt/dx > 3e7 -- a
-//               simulation that has long blown up.
+//               simulation that has long blown up.  The MacCormack adjoint (karman_maccormack.hip) keeps this one scale for its second
+//               accumulator too: g_h = g_a + the scattered g_b has |g_h| <= max|g_a| (1 + s/2 x fan-in), a small multiple of max|g_a| and
+//               far inside the 2^25 of headroom, so the statement above holds for every contribution of both stages.
 //   Resolution  2^-37 max|g_a| per contribution.
 //   Poisoning   a NON-FINITE g_a publishes the bits of a NaN, the largest value the integer maximum can see; fx_scale turns that into
 //               "scatter nothing (qs = 0), convert back to NaN (qi = NaN)": EVERY input gradient of that simulation is NaN -- as fp32

@@ -202,13 +202,15 @@ struct KDLayout {
     float *gUy, *gUx;
     unsigned* gmax;
     double* partial;
+    void* mc;                           // the _adv forms with the MacCormack advection: what sol_mc_adj_den takes, behind everything else
     size_t bytes;
 };
-KDLayout kd_layout(const sol_karman_cfg* c, bool re, void* ws) {
+KDLayout kd_layout(const sol_karman_cfg* c, bool re, void* ws, bool mc = false) {
     const size_t B = c->B, N = (size_t)c->Y * c->X;
     Carve w(ws);
     KDLayout l{w.take<long long>(B * N), w.take<float>(B * N), w.take<float>(B * N), w.take<unsigned>(B * FX_SLOTS)};
     if (re) l.partial = sol_re_partial_take(w, c);
+    if (mc) l.mc = w.take<char>(sol_mc_adj_bytes(c));
     l.bytes = w.bytes();
     return l;
 }
@@ -222,21 +224,31 @@ extern "C" size_t sol_karman_density_bwd_workspace_bytes(const sol_karman_cfg* c
 
 namespace {
 
+// the _adv forms' extra: which advection the forward step ran (1: MacCormack, karman_maccormack.hip) and its correction strength
+struct AdvExtra {
+    int32_t advection;
+    float strength;
+};
+
 // the launches of sol_karman_density_bwd; with rx, followed by the Reynolds-number reduction over the gU they leave in the workspace
 // (sol_karman_density_bwd_re): g_d_in / g_vy_in / g_vx_in are the same launches' results either way
 int density_bwd(const char* who, const sol_karman_cfg* c, void* stream,
                 const float* d_in, const float* inflow, const float* saved_vy, const float* saved_vx,
                 const float* re, const float* velBCyMask, int64_t bc_batch_stride,
                 const float* g_d_out, float* g_d_in, float* g_vy_in, float* g_vx_in, int accumulate,
-                void* workspace, size_t workspace_bytes, const ReExtra* rx) {
+                void* workspace, size_t workspace_bytes, const ReExtra* rx, const AdvExtra* ax = nullptr) {
     SOL_REQUIRE(c != nullptr, "%s: cfg is NULL", who);
+    if (ax)
+        if (int e = sol_mc_check(who, ax->advection, ax->strength)) return e;
+    const bool mc = ax && ax->advection == 1;
+    SOL_REQUIRE(!mc || (c->Y >= 16 && c->X >= 16), "%s: the MacCormack advection is built on grids with Y, X >= 16 (got %d, %d)", who, c ? c->Y : 0, c ? c->X : 0);
     SOL_REQUIRE(c->B >= 1 && c->B <= 65535 && c->Y >= 2 && c->X >= 2, "%s: B in [1, 65535], Y, X >= 2 (got %d, %d, %d)", who, c->B, c->Y, c->X);
     SOL_REQUIRE((size_t)c->Y * c->X < ((size_t)1 << 28), "%s: grid too large for 32-bit face indices", who);
     SOL_REQUIRE(d_in && saved_vy && saved_vx && re && velBCyMask && g_d_out && g_d_in && g_vy_in && g_vx_in && workspace,
                 "%s: NULL pointer argument", who);
     SOL_REQUIRE(inflow || !c->inflow_before, "%s: cfg.inflow_before needs the inflow mask (the advected field is d_in + inflow)", who);
     SOL_REQUIRE(!rx || (rx->vy_in && rx->vx_in && rx->g_re), "%s: NULL pointer argument", who);
-    const KDLayout l = kd_layout(c, rx != nullptr, workspace);
+    const KDLayout l = kd_layout(c, rx != nullptr, workspace, mc);
     SOL_REQUIRE(workspace_bytes >= l.bytes, "%s: workspace too small (%zu < %zu bytes)", who, workspace_bytes, l.bytes);
     const void* outs[] = {g_d_in, g_vy_in, g_vx_in, rx ? rx->g_re : nullptr};
     const void* ins[] = {d_in, inflow, saved_vy, saved_vx, re, velBCyMask, g_d_out, rx ? rx->vy_in : nullptr, rx ? rx->vx_in : nullptr};
@@ -255,7 +267,10 @@ int density_bwd(const char* who, const sol_karman_cfg* c, void* stream,
     a.gD = l.gD; a.gUy = l.gUy; a.gUx = l.gUx; a.gmax = l.gmax;
     a.gdi = g_d_in; a.giy = g_vy_in; a.gix = g_vx_in;
     SOL_LAUNCH(k_kd_clear, dim3(FX_SLOTS, B), dim3(256), 0, s, a);
-    if (sol_opt().k2d_dens_adj_tile) {
+    if (mc) {
+        if (int e = sol_mc_adj_den(c, s, true, ax->strength, d_in, inflow, saved_vy, saved_vx, g_d_out, l.gmax, l.gD, l.gUy, l.gUx, l.mc,
+                                   sol_opt().k2d_dens_adj_tile != 0)) return e;
+    } else if (sol_opt().k2d_dens_adj_tile) {
         const int ntj = (Y + KD_T - 1) / KD_T, nti = (X + KD_T - 1) / KD_T;
         SOL_LAUNCH(k_kd_advect_adj_tile, dim3(ntj * nti, B), dim3(256), 0, s, a, nti);
     } else {
@@ -299,4 +314,34 @@ extern "C" int sol_karman_density_bwd_re(const sol_karman_cfg* c, void* stream,
     const ReExtra rx{vy_in, vx_in, g_re, accumulate_re};
     return density_bwd("sol_karman_density_bwd_re", c, stream, d_in, inflow, saved_vy, saved_vx, re, velBCyMask, bc_batch_stride, g_d_out,
                        g_d_in, g_vy_in, g_vx_in, accumulate, workspace, workspace_bytes, &rx);
+}
+
+// The _adv forms: every argument of the plain / _re form, then the advection the forward step ran (0: semi-Lagrangian -- that form's
+// launches and bits; 1: MacCormack -- sol_mc_adj_den in place of k_kd_advect_adj*, grids with Y, X >= 16) and its correction strength.
+extern "C" size_t sol_karman_density_bwd_adv_workspace_bytes(const sol_karman_cfg* c, int32_t with_re, int32_t advection) {
+    if (!c || c->B < 1 || c->Y < 1 || c->X < 1) return 0;
+    return kd_layout(c, with_re != 0, nullptr, advection == 1).bytes;
+}
+
+extern "C" int sol_karman_density_bwd_adv(const sol_karman_cfg* c, void* stream,
+                                          const float* d_in, const float* inflow, const float* saved_vy, const float* saved_vx,
+                                          const float* re, const float* velBCyMask, int64_t bc_batch_stride,
+                                          const float* g_d_out, float* g_d_in, float* g_vy_in, float* g_vx_in, int accumulate,
+                                          void* workspace, size_t workspace_bytes, int32_t advection, float correction_strength) {
+    const AdvExtra ax{advection, correction_strength};
+    return density_bwd("sol_karman_density_bwd_adv", c, stream, d_in, inflow, saved_vy, saved_vx, re, velBCyMask, bc_batch_stride, g_d_out,
+                       g_d_in, g_vy_in, g_vx_in, accumulate, workspace, workspace_bytes, nullptr, &ax);
+}
+
+extern "C" int sol_karman_density_bwd_adv_re(const sol_karman_cfg* c, void* stream,
+                                             const float* d_in, const float* inflow, const float* saved_vy, const float* saved_vx,
+                                             const float* re, const float* velBCyMask, int64_t bc_batch_stride,
+                                             const float* g_d_out, float* g_d_in, float* g_vy_in, float* g_vx_in, int accumulate,
+                                             void* workspace, size_t workspace_bytes,
+                                             const float* vy_in, const float* vx_in, float* g_re, int accumulate_re,
+                                             int32_t advection, float correction_strength) {
+    const ReExtra rx{vy_in, vx_in, g_re, accumulate_re};
+    const AdvExtra ax{advection, correction_strength};
+    return density_bwd("sol_karman_density_bwd_adv_re", c, stream, d_in, inflow, saved_vy, saved_vx, re, velBCyMask, bc_batch_stride, g_d_out,
+                       g_d_in, g_vy_in, g_vx_in, accumulate, workspace, workspace_bytes, &rx, &ax);
 }

@@ -366,11 +366,24 @@ int sol_large_front(const sol_karman_cfg* c, hipStream_t s, const SolLargeStep& 
     const LArgs a = large_args(c, io, svy, svx, rhs, nullptr);
     const int B = c->B, N = c->Y * c->X, faces = (c->Y + 1) * c->X + c->Y * (c->X + 1);
     SOL_LAUNCH(k_l_diffuse, dim3((faces + 255) / 256, B), dim3(256), 0, s, a);
-    SOL_LAUNCH(k_l_advect, dim3((faces + N + 255) / 256, B), dim3(256), 0, s, a);
+    if (io.advection == 0) SOL_LAUNCH(k_l_advect, dim3((faces + N + 255) / 256, B), dim3(256), 0, s, a);
+    else if (int e = sol_mc_advect(c, s, io.mc_strength, io.d_in, svy, svx, io.active, io.inflow, io.d_out, io.vy_out, io.vx_out, io.mc_ws)) return e;
     // buoyancy (optional; io.buoy = dt F): the step's output density pushes the advected velocity (karman_buoyancy.hip)
     SOL_REQUIRE((io.buoy_y == 0.f && io.buoy_x == 0.f) || (io.d_in && io.inflow && io.d_out), "a buoyancy force needs the density: d_in, inflow and d_out");
     if (int e = sol_buoyancy_add(s, B, c->Y, c->X, io.active, io.d_out, io.buoy_y, io.buoy_x, io.vy_out, io.vx_out)) return e;
     SOL_LAUNCH(k_l_div, dim3((N + 255) / 256, B), dim3(256), 0, s, a);
+    SOL_LAUNCH_CHECK();
+    return SOL_OK;
+}
+
+// k_l_advect alone on a given post-diffusion velocity (sol_karman_advect with advection = 0, karman_maccormack.hip)
+int sol_large_advect(const sol_karman_cfg* c, hipStream_t s, const float* d_in, const float* svy, const float* svx, const float* active,
+                     const float* inflow, float* d_out, float* vy_out, float* vx_out) {
+    SolLargeStep io{};
+    io.d_in = d_in; io.active = active; io.inflow = inflow; io.d_out = d_out; io.vy_out = vy_out; io.vx_out = vx_out;
+    const LArgs a = large_args(c, io, const_cast<float*>(svy), const_cast<float*>(svx), nullptr, nullptr);
+    const int items = (c->Y + 1) * c->X + c->Y * (c->X + 1) + c->Y * c->X;
+    SOL_LAUNCH(k_l_advect, dim3((items + 255) / 256, c->B), dim3(256), 0, s, a);
     SOL_LAUNCH_CHECK();
     return SOL_OK;
 }

@@ -246,13 +246,15 @@ struct BwdLayout {
     unsigned* gmax;
     void* solver;
     double* partial;
+    void* mc;                           // the _adv forms with the MacCormack advection: what sol_mc_adj_vel takes, behind everything else
     size_t bytes;
 };
-BwdLayout bwd_layout(const sol_karman_cfg* c, bool direct, bool re, void* ws, const int32_t* hdr = nullptr) {
+BwdLayout bwd_layout(const sol_karman_cfg* c, bool direct, bool re, void* ws, const int32_t* hdr = nullptr, bool mc = false) {
     const size_t B = c->B, Y = c->Y, X = c->X, faces = (Y + 1) * X + Y * (X + 1);
     Carve w(ws);
     BwdLayout l{w.take<long long>(B * faces), w.take<float>(B * faces), w.take<unsigned>(B * FX_SLOTS), w.take<char>(sol_large_solver_bytes(c, direct, hdr))};
     if (re) l.partial = sol_re_partial_take(w, c);
+    if (mc) l.mc = w.take<char>(sol_mc_adj_bytes(c));
     l.bytes = w.bytes();
     return l;
 }
@@ -286,6 +288,12 @@ struct BuoyExtra {
     float* g_dsum;
 };
 
+// the _adv forms' extra: which advection the forward step ran (1: MacCormack, karman_maccormack.hip) and its correction strength
+struct AdvExtra {
+    int32_t advection;
+    float strength;
+};
+
 // the launches of sol_karman_step_bwd_large; with bx, followed by the transpose of the buoyancy term over the g_a they leave in the
 // workspace (k_lb_buoyancy_adj, karman_buoyancy.hip); with rx, followed by the Reynolds-number reduction over the g_c they leave in the workspace
 // (sol_karman_step_bwd_large_re): g_vy_in / g_vx_in are the same launches' results either way
@@ -295,8 +303,11 @@ int bwd_large(const char* who, const sol_karman_cfg* c, void* stream,
               const float* g_vy_out, const float* g_vx_out, float* g_vy_in, float* g_vx_in,
               const int32_t* direct_header_host,
               const float* box_blob, const int32_t* box_header_host, int32_t* cg_info,
-              void* workspace, size_t workspace_bytes, const ReExtra* rx, const BuoyExtra* bx = nullptr) {
+              void* workspace, size_t workspace_bytes, const ReExtra* rx, const BuoyExtra* bx = nullptr, const AdvExtra* ax = nullptr) {
     if (int e = common_check(c, who)) return e;
+    if (ax)
+        if (int e = sol_mc_check(who, ax->advection, ax->strength)) return e;
+    const bool mc = ax && ax->advection == 1;
     SOL_REQUIRE(!rx || (rx->vy_in && rx->vx_in && rx->g_re), "%s: NULL pointer argument", who);
     SOL_REQUIRE(!bx || bx->g_dsum, "%s: NULL pointer argument (g_dsum)", who);
     SOL_REQUIRE(!bx || (bx->fy - bx->fy == 0.f && bx->fx - bx->fx == 0.f), "%s: the force must be finite", who);
@@ -305,7 +316,7 @@ int bwd_large(const char* who, const sol_karman_cfg* c, void* stream,
                 "%s: NULL pointer argument", who);
     if (direct) { if (int e = sol_large_direct_check(c, who, direct_header_host)) return e; }
     else if (int e = sol_large_cg_check(c, who, box_blob, box_header_host, cg_info, workspace)) return e;
-    const BwdLayout l = bwd_layout(c, direct, rx != nullptr, workspace, direct ? direct_header_host : nullptr);
+    const BwdLayout l = bwd_layout(c, direct, rx != nullptr, workspace, direct ? direct_header_host : nullptr, mc);
     SOL_REQUIRE(workspace_bytes >= l.bytes, "%s: workspace too small (%zu < %zu bytes)", who, workspace_bytes, l.bytes);
     const void* outs[] = {g_vy_in, g_vx_in, cg_info, rx ? rx->g_re : nullptr, bx ? bx->g_dsum : nullptr};
     const void* ins[] = {saved_vy, saved_vx, re, active, velBCyMask, g_vy_out, g_vx_out, box_blob, rx ? rx->vy_in : nullptr, rx ? rx->vx_in : nullptr,
@@ -335,7 +346,9 @@ int bwd_large(const char* who, const sol_karman_cfg* c, void* stream,
     if (int e = pressure_solve_any2d(s, c, direct, direct_header_host, box_blob, active, cg_info, l.solver, &q)) return e;
     a.gdiv = q;
     SOL_LAUNCH(k_lb_ga, dim3(gF, B), dim3(256), 0, s, a);
-    if (sol_opt().k2d_adj_tile) {
+    if (mc) {
+        if (int e = sol_mc_adj_vel(c, s, true, ax->strength, saved_vy, saved_vx, a.gay, a.gax, a.gmax, a.gcy, a.gcx, l.mc, sol_opt().k2d_adj_tile != 0)) return e;
+    } else if (sol_opt().k2d_adj_tile) {
         const int ntj = (Y + LB_T - 1) / LB_T, nti = (X + LB_T - 1) / LB_T;
         SOL_LAUNCH(k_lb_advect_adj_tile, dim3(ntj * nti, B), dim3(256), 0, s, a, nti);
     } else {
@@ -416,4 +429,44 @@ extern "C" int sol_karman_step_bwd_large_buoy_re(const sol_karman_cfg* c, void* 
     const BuoyExtra bx{fy, fx, g_d_out, g_dsum};
     return bwd_large("sol_karman_step_bwd_large_buoy_re", c, stream, saved_vy, saved_vx, re, active, velBCyMask, bc_batch_stride, g_vy_out, g_vx_out,
                      g_vy_in, g_vx_in, direct_header_host, box_blob, box_header_host, cg_info, workspace, workspace_bytes, &rx, &bx);
+}
+
+// The _adv forms: every argument of the _buoy / _buoy_re form, then the advection the forward step ran (0: semi-Lagrangian -- that form's
+// launches and bits; 1: MacCormack -- sol_mc_adj_vel in place of k_lb_advect_adj*) and its correction strength.  A zero force with
+// g_d_out = NULL is the unbuoyant adjoint plus one launch that writes g_dsum = 0.
+extern "C" size_t sol_karman_step_bwd_large_adv_workspace_bytes_for(const sol_karman_cfg* c, const int32_t* direct_header_host, int32_t with_re, int32_t advection) {
+    if (!c || c->B < 1 || c->Y < 1 || c->X < 1) return 0;
+    return bwd_layout(c, c->direct != nullptr, with_re != 0, nullptr, direct_header_host, advection == 1).bytes;
+}
+
+extern "C" int sol_karman_step_bwd_large_adv(const sol_karman_cfg* c, void* stream,
+                                             const float* saved_vy, const float* saved_vx, const float* re, const float* active,
+                                             const float* velBCyMask, int64_t bc_batch_stride,
+                                             const float* g_vy_out, const float* g_vx_out, float* g_vy_in, float* g_vx_in,
+                                             const int32_t* direct_header_host,
+                                             const float* box_blob, const int32_t* box_header_host, int32_t* cg_info,
+                                             void* workspace, size_t workspace_bytes,
+                                             float fy, float fx, const float* g_d_out, float* g_dsum,
+                                             int32_t advection, float correction_strength) {
+    const BuoyExtra bx{fy, fx, g_d_out, g_dsum};
+    const AdvExtra ax{advection, correction_strength};
+    return bwd_large("sol_karman_step_bwd_large_adv", c, stream, saved_vy, saved_vx, re, active, velBCyMask, bc_batch_stride, g_vy_out, g_vx_out,
+                     g_vy_in, g_vx_in, direct_header_host, box_blob, box_header_host, cg_info, workspace, workspace_bytes, nullptr, &bx, &ax);
+}
+
+extern "C" int sol_karman_step_bwd_large_adv_re(const sol_karman_cfg* c, void* stream,
+                                                const float* saved_vy, const float* saved_vx, const float* re, const float* active,
+                                                const float* velBCyMask, int64_t bc_batch_stride,
+                                                const float* g_vy_out, const float* g_vx_out, float* g_vy_in, float* g_vx_in,
+                                                const int32_t* direct_header_host,
+                                                const float* box_blob, const int32_t* box_header_host, int32_t* cg_info,
+                                                void* workspace, size_t workspace_bytes,
+                                                const float* vy_in, const float* vx_in, float* g_re, int accumulate_re,
+                                                float fy, float fx, const float* g_d_out, float* g_dsum,
+                                                int32_t advection, float correction_strength) {
+    const ReExtra rx{vy_in, vx_in, g_re, accumulate_re};
+    const BuoyExtra bx{fy, fx, g_d_out, g_dsum};
+    const AdvExtra ax{advection, correction_strength};
+    return bwd_large("sol_karman_step_bwd_large_adv_re", c, stream, saved_vy, saved_vx, re, active, velBCyMask, bc_batch_stride, g_vy_out, g_vx_out,
+                     g_vy_in, g_vx_in, direct_header_host, box_blob, box_header_host, cg_info, workspace, workspace_bytes, &rx, &bx, &ax);
 }

@@ -477,9 +477,28 @@ struct LargeSolver { bool direct; const int32_t* direct_header_host; const float
 // the training forms: where the post-diffusion velocity goes for the adjoint (without: into the workspace)
 struct LargeSaved { float *vy, *vx; };
 
+// the _adv forms: which advection (0: semi-Lagrangian, the plain launches; 1: MacCormack, karman_maccormack.hip) and its correction strength
+struct LargeAdv { int32_t advection; float strength; };
+
+// the workspace of an _adv step: the plain step's (fwd_layout), then -- with the MacCormack advection -- the part its launches take
+// (sol_mc_bytes, carved by sol_mc_advect from the end of the step's part)
+struct FwdAdvLayout { FwdLayout step; void* mc; size_t bytes; };
+FwdAdvLayout fwd_adv_layout(const sol_karman_cfg* c, bool direct, const int32_t* hdr, bool with_sv, bool mc, void* ws) {
+    FwdAdvLayout l{fwd_layout(c, direct, hdr, with_sv, ws), nullptr, 0};
+    l.bytes = l.step.bytes;
+    if (mc) {
+        l.mc = ws ? static_cast<char*>(ws) + l.step.bytes : nullptr;
+        l.bytes += sol_mc_bytes(c);
+    }
+    return l;
+}
+
 int large_fwd(const char* who, const sol_karman_cfg* c, void* stream, SolLargeStep io, const LargeSolver& sv, const LargeSaved* keep,
-              void* workspace, size_t workspace_bytes, float fy = 0.f, float fx = 0.f) {
+              void* workspace, size_t workspace_bytes, float fy = 0.f, float fx = 0.f, const LargeAdv* adv = nullptr) {
     const LargeSaved saved = keep ? *keep : LargeSaved{};
+    if (adv)
+        if (int e = sol_mc_check(who, adv->advection, adv->strength)) return e;
+    const bool mc = adv && adv->advection == 1;
     SOL_REQUIRE(c != nullptr, "%s: cfg is NULL", who);
     SOL_REQUIRE(c->B >= 1 && c->B <= 65535 && c->Y >= 16 && c->X >= 16, "%s: B in [1, 65535], Y, X >= 16 (got %d, %d, %d)", who, c->B, c->Y, c->X);
     SOL_REQUIRE((size_t)c->Y * c->X < ((size_t)1 << 30), "%s: grid too large", who);
@@ -494,8 +513,10 @@ int large_fwd(const char* who, const sol_karman_cfg* c, void* stream, SolLargeSt
     SOL_REQUIRE(!sv.direct || !sv.p_inout, "%s: p_inout warm-starts the CG solve; this cfg selects the direct solve", who);
     if (sv.direct) { if (int e = sol_large_direct_check(c, who, sv.direct_header_host)) return e; }
     else if (int e = sol_large_cg_check(c, who, sv.box_blob, sv.box_header_host, sv.cg_info, workspace)) return e;
-    const FwdLayout l = fwd_layout(c, sv.direct, sv.direct_header_host, !saved.vy, workspace);
-    SOL_REQUIRE(workspace_bytes >= l.bytes, "%s: workspace too small (%zu < %zu bytes)", who, workspace_bytes, l.bytes);
+    const FwdAdvLayout al = fwd_adv_layout(c, sv.direct, sv.direct_header_host, !saved.vy, mc, workspace);
+    const FwdLayout& l = al.step;
+    SOL_REQUIRE(workspace_bytes >= al.bytes, "%s: workspace too small (%zu < %zu bytes)", who, workspace_bytes, al.bytes);
+    if (mc) { io.advection = 1; io.mc_strength = adv->strength; io.mc_ws = al.mc; }
     const void* outs[] = {io.d_out, io.vy_out, io.vx_out, io.feat_out, saved.vy, saved.vx, sv.cg_info, sv.p_inout};
     const void* ins[] = {io.d_in, io.vy_in, io.vx_in, io.re, io.active, io.inflow, io.velBCy, io.velBCyMask, sv.box_blob};
     for (const void* o : outs)
@@ -612,6 +633,51 @@ extern "C" int sol_karman_step_fwd_large_saved_buoy(const sol_karman_cfg* c, voi
     const LargeSaved keep{saved_vy, saved_vx};
     return large_fwd("sol_karman_step_fwd_large_saved_buoy", c, stream, io, {c && c->direct, direct_header_host, box_blob, box_header_host, cg_info}, &keep,
                      workspace, workspace_bytes, fy, fx);
+}
+
+// The _adv forms of the two _buoy forward steps: every argument of theirs, then the advection (0: semi-Lagrangian -- the _buoy call's
+// launches and bits; 1: MacCormack, karman_maccormack.hip) and its correction strength in [0, 1].  The workspace of advection = 1 is the
+// _buoy form's plus sol_karman_advect_workspace_bytes (the *_adv_workspace_bytes_for functions).
+extern "C" size_t sol_karman_step_fwd_large_adv_workspace_bytes_for(const sol_karman_cfg* c, const int32_t* direct_header_host, int32_t advection) {
+    if (!c || c->B < 1 || c->Y < 1 || c->X < 1) return 0;
+    return fwd_adv_layout(c, c->direct != nullptr, direct_header_host, true, advection == 1, nullptr).bytes;
+}
+
+extern "C" size_t sol_karman_step_fwd_large_saved_adv_workspace_bytes_for(const sol_karman_cfg* c, const int32_t* direct_header_host, int32_t advection) {
+    if (!c || c->B < 1 || c->Y < 1 || c->X < 1) return 0;
+    return fwd_adv_layout(c, c->direct != nullptr, direct_header_host, false, advection == 1, nullptr).bytes;
+}
+
+extern "C" int sol_karman_step_fwd_large_adv(const sol_karman_cfg* c, void* stream,
+                                             const float* d_in, const float* vy_in, const float* vx_in,
+                                             const float* re, const float* active, const float* inflow,
+                                             const float* velBCy, const float* velBCyMask, int64_t bc_batch_stride,
+                                             float* d_out, float* vy_out, float* vx_out,
+                                             float* feat_out, const float* feat_scale,
+                                             const int32_t* direct_header_host,
+                                             const float* box_blob, const int32_t* box_header_host, int32_t* cg_info,
+                                             float* p_inout, void* workspace, size_t workspace_bytes, float fy, float fx,
+                                             int32_t advection, float correction_strength) {
+    const SolLargeStep io{d_in, vy_in, vx_in, re, active, inflow, velBCy, velBCyMask, bc_batch_stride, d_out, vy_out, vx_out, feat_out, feat_scale};
+    const LargeAdv adv{advection, correction_strength};
+    return large_fwd("sol_karman_step_fwd_large_adv", c, stream, io, {c && c->direct, direct_header_host, box_blob, box_header_host, cg_info, p_inout},
+                     nullptr, workspace, workspace_bytes, fy, fx, &adv);
+}
+
+extern "C" int sol_karman_step_fwd_large_saved_adv(const sol_karman_cfg* c, void* stream,
+                                                   const float* d_in, const float* vy_in, const float* vx_in,
+                                                   const float* re, const float* active, const float* inflow,
+                                                   const float* velBCy, const float* velBCyMask, int64_t bc_batch_stride,
+                                                   float* d_out, float* vy_out, float* vx_out, float* saved_vy, float* saved_vx,
+                                                   const int32_t* direct_header_host,
+                                                   const float* box_blob, const int32_t* box_header_host, int32_t* cg_info,
+                                                   void* workspace, size_t workspace_bytes, float fy, float fx,
+                                                   int32_t advection, float correction_strength) {
+    const SolLargeStep io{d_in, vy_in, vx_in, re, active, inflow, velBCy, velBCyMask, bc_batch_stride, d_out, vy_out, vx_out, nullptr, nullptr};
+    const LargeSaved keep{saved_vy, saved_vx};
+    const LargeAdv adv{advection, correction_strength};
+    return large_fwd("sol_karman_step_fwd_large_saved_adv", c, stream, io, {c && c->direct, direct_header_host, box_blob, box_header_host, cg_info}, &keep,
+                     workspace, workspace_bytes, fy, fx, &adv);
 }
 
 extern "C" int sol_karman_pressure_solve_large(const sol_karman_cfg* c, void* stream, const float* active, const float* rhs, float* p,

@@ -113,7 +113,13 @@ class KarmanFlow:
     def __init__(self, pressure_solver=None, make_input_divfree=False, make_output_divfree=True,
                  cg_rtol=1e-6, cg_atol=1e-9, cg_max_iter=2000, grad_pad="replicate", inflow_order="after",
                  obstacles=None, active=None, density_grad=False, re_grad=False, buoyancy=None, buoyancy_factor=None,
-                 gravity=(-9.81, 0.0), diffusion_substeps=1):
+                 gravity=(-9.81, 0.0), diffusion_substeps=1, advection="semi_lagrangian", correction_strength=1.0):
+        # advection="mac_cormack" (PhiFlow's advect.mac_cormack(field, velocity, dt, correction_strength)): velocity and density are advected
+        # by the MacCormack scheme with the revert-to-semi-Lagrangian limiter (include/sol_hip.h, "MACCORMACK ADVECTION"), which keeps what
+        # the semi-Lagrangian step smears; large grids only (step() raises SolError on a grid the one-workgroup kernels serve); composes
+        # with density_grad, re_grad, buoyancy and diffusion_substeps.  The default issues the launches it always did.
+        self._adv = ops.advection_arg(advection, correction_strength, "KarmanFlow: advection")
+        self._advection = dict(advection=advection, correction_strength=float(correction_strength))
         # diffusion_substeps=n (PhiFlow's diffuse(field, amount, substeps)): the velocity is diffused by n explicit substeps of alpha / n,
         # alpha = dt res^2 / Re, the boundary blend after the last one.  The single stencil is stable only while alpha <= 1/4
         # (ops.min_diffusion_substeps gives the n a run needs); grids with Y, X >= 16; composes with density_grad, re_grad and buoyancy.
@@ -236,15 +242,18 @@ class KarmanFlow:
         if self._buoyancy is not None and not masks.large:
             raise _lib.SolError("KarmanFlow: the buoyancy force is built on the multi-launch (large-grid) step only; a %dx%d grid runs the "
                                 "fused one-workgroup kernels (not ops.beyond_one_workgroup), which have no buoyancy term" % (Y, X))
+        if self._adv is not None:
+            ops._require_large_for_advection(masks, Y, X, "KarmanFlow")
         if masks.large:
             # beyond the one-workgroup kernels (data generation at 256 x 128, karman.py:98-159): the multi-launch path, direct solve
             # where the scene's blob builds, else the preconditioned CG (solve_info: iterations / converged per simulation, and
             # iterations_bwd / converged_bwd after backward()); differentiable like the small path (ops.KarmanStepFn)
-            n = ops.large_workspace_bytes(cfg, masks)
+            n = ops.large_workspace_bytes(cfg, masks) if self._adv is None else ops.large_adv_workspace_bytes(cfg, masks)
             if getattr(self, "_large_ws", None) is None or self._large_ws[0] != (B, Y, X, str(dev)) or self._large_ws[1].numel() * 4 < n:
                 self._large_ws = ((B, Y, X, str(dev)), torch.empty((n + 3) // 4, dtype=torch.float32, device=dev))
             d2, vy2, vx2 = ops.karman_step_large(d, vy, vx, re_t, cfg, masks, self._large_ws[1], info, density_grad=self._density_grad,
-                                                 re_grad=self._re_grad, buoyancy=self._buoyancy, diffusion_substeps=self._nsub)
+                                                 re_grad=self._re_grad, buoyancy=self._buoyancy, diffusion_substeps=self._nsub,
+                                                 **({} if self._adv is None else self._advection))
         else:
             d2, vy2, vx2 = ops.karman_step(d, vy, vx, re_t, cfg, masks, info, density_grad=self._density_grad, re_grad=self._re_grad,
                                            diffusion_substeps=self._nsub)

@@ -129,6 +129,23 @@ def large_workspace_bytes(cfg, masks):
     return lib.sol_karman_step_large_workspace_bytes_for(C.byref(cfg), _hdr(masks.direct_header))
 
 
+def large_adv_workspace_bytes(cfg, masks, saved=False):
+    """Device scratch of the large-grid step with advection="mac_cormack" (the _adv entry points; saved: the training form)."""
+    lib = _lib.load()
+    fn = lib.sol_karman_step_fwd_large_saved_adv_workspace_bytes_for if saved else lib.sol_karman_step_fwd_large_adv_workspace_bytes_for
+    return fn(C.byref(cfg), _hdr(masks.direct_header), 1)
+
+
+def large_bwd_adv_workspace_bytes(cfg, masks, re=False):
+    """Device scratch of the large-grid adjoint under advection="mac_cormack" (sol_karman_step_bwd_large_adv / _adv_re)."""
+    return _lib.load().sol_karman_step_bwd_large_adv_workspace_bytes_for(C.byref(cfg), _hdr(masks.direct_header), int(re), 1)
+
+
+def density_bwd_adv_workspace_bytes(cfg, re=False):
+    """Device scratch of the density adjoint under advection="mac_cormack" (sol_karman_density_bwd_adv / _adv_re)."""
+    return _lib.load().sol_karman_density_bwd_adv_workspace_bytes(C.byref(cfg), int(re), 1)
+
+
 def large_bwd_workspace_bytes(cfg, masks):
     """Device scratch of the large-grid adjoint (sol_karman_step_bwd_large) for the scene's solver."""
     return _lib.load().sol_karman_step_bwd_large_workspace_bytes_for(C.byref(cfg), _hdr(masks.direct_header))
@@ -192,6 +209,86 @@ def _require_large_for_buoyancy(masks, Y, X, who):
     if not masks.large:
         raise SolError("%s: the buoyancy force is built on the multi-launch (large-grid) step only; a %dx%d grid runs the fused "
                        "one-workgroup kernels (not ops.beyond_one_workgroup), which have no buoyancy term" % (who, Y, X))
+
+
+# --------------------------------------------------------------------------------------
+# advection scheme (include/sol_hip.h, "MACCORMACK ADVECTION on the large-grid step"; csrc/karman_maccormack.hip)
+# --------------------------------------------------------------------------------------
+ADVECTIONS = ("semi_lagrangian", "mac_cormack")
+
+
+def advection_arg(advection="semi_lagrangian", correction_strength=1.0, who="advection"):
+    """The pair of keywords as the calls below carry it: None for "semi_lagrangian" (the existing entry points, launches and bits), the
+    correction strength s as a float for "mac_cormack".  An unknown name, or an s outside [0, 1] or not finite, raises ValueError (s is
+    checked for either scheme)."""
+    if advection not in ADVECTIONS:
+        raise ValueError("%s must be one of %s (got %r)" % (who, ", ".join(ADVECTIONS), advection))
+    if isinstance(correction_strength, bool) or not isinstance(correction_strength, (int, float, np.integer, np.floating)):
+        raise ValueError("correction_strength must be a number in [0, 1] (got %r)" % (correction_strength,))
+    s = float(correction_strength)
+    if not (np.isfinite(s) and 0.0 <= s <= 1.0):
+        raise ValueError("correction_strength must be finite and lie in [0, 1] (got %r)" % (correction_strength,))
+    return s if advection == "mac_cormack" else None
+
+
+def _require_large_for_advection(masks, Y, X, who):
+    if not masks.large:
+        raise SolError("%s: the mac_cormack advection is built on the multi-launch (large-grid) step only; a %dx%d grid runs the fused "
+                       "one-workgroup kernels (not ops.beyond_one_workgroup), which advect semi-Lagrangian" % (who, Y, X))
+
+
+def _adv_grid(cfg, who):
+    if cfg.Y < 16 or cfg.X < 16:
+        raise SolError("%s: the advection stage (sol_karman_advect) takes grids with Y, X >= 16; this one is %dx%d" % (who, cfg.Y, cfg.X))
+
+
+def _adv_inputs(who, cfg, d, svy, svx, active, inflow):
+    B, Y, X = cfg.B, cfg.Y, cfg.X
+    d, svy, svx, active, inflow = (_lib.f32(t) for t in (d, svy, svx, active, inflow))
+    if d.shape != (B, Y, X) or svy.shape != (B, Y + 1, X) or svx.shape != (B, Y, X + 1) or active.numel() != Y * X or inflow.numel() != Y * X:
+        raise ValueError("%s: d %s, svy %s, svx %s, active %s, inflow %s are not [B,Y,X], [B,Y+1,X], [B,Y,X+1], [Y,X], [Y,X] of the cfg "
+                         "(B, Y, X) = (%d, %d, %d)" % (who, tuple(d.shape), tuple(svy.shape), tuple(svx.shape), tuple(active.shape),
+                                                      tuple(inflow.shape), B, Y, X))
+    return d, svy, svx, active, inflow
+
+
+def karman_advect(d, svy, svx, cfg, active, inflow, advection="semi_lagrangian", correction_strength=1.0, workspace=None):
+    """The advection stage of the large-grid step alone (sol_karman_advect; any Y, X >= 16): (d, svy, svx) -- the density and the
+    post-diffusion velocity -- -> (d_out, a_y, a_x): the advected density (+ inflow as cfg.inflow_before says) and the advected velocity
+    times the hard-BC face masks of `active` [Y,X].  advection = "mac_cormack": the MacCormack scheme with the revert-to-semi-Lagrangian
+    limiter (form selected by the option k2d_mc_tile, equal bits)."""
+    s = advection_arg(advection, correction_strength, "karman_advect: advection")
+    _adv_grid(cfg, "karman_advect")
+    _lib.require_gpu()
+    lib = _lib.load()
+    d, svy, svx, active, inflow = _adv_inputs("karman_advect", cfg, d, svy, svx, active, inflow)
+    nbytes = lib.sol_karman_advect_workspace_bytes(C.byref(cfg), int(s is not None))
+    ws = _workspace(nbytes, workspace, d.device) if nbytes else None
+    outs = torch.empty_like(d), torch.empty_like(svy), torch.empty_like(svx)
+    check(lib.sol_karman_advect(C.byref(cfg), stream(), ptr(d), ptr(svy), ptr(svx), ptr(active), ptr(inflow), int(s is not None),
+                                1.0 if s is None else s, *(ptr(t) for t in outs), ptr(ws), 0 if ws is None else ws.numel() * 4))
+    return outs
+
+
+def karman_advect_bwd(d, svy, svx, cfg, active, inflow, g_d, g_ay, g_ax, advection="semi_lagrangian", correction_strength=1.0,
+                      tile=True, workspace=None):
+    """The transpose of karman_advect (sol_karman_advect_bwd): the cotangents of (d_out, a_y, a_x) -> (g_d_in, g_svy, g_svx), every
+    decision of the forward stage (floor, clamp, limiter) frozen.  64-bit fixed-point scatter: bit-reproducible; tile=False takes global
+    atomics only (equal bits).  A non-finite cotangent makes every gradient of its simulation NaN."""
+    s = advection_arg(advection, correction_strength, "karman_advect_bwd: advection")
+    _adv_grid(cfg, "karman_advect_bwd")
+    _lib.require_gpu()
+    lib = _lib.load()
+    d, svy, svx, active, inflow = _adv_inputs("karman_advect_bwd", cfg, d, svy, svx, active, inflow)
+    g_d, g_ay, g_ax = (_lib.f32(t) for t in (g_d, g_ay, g_ax))
+    if g_d.shape != d.shape or g_ay.shape != svy.shape or g_ax.shape != svx.shape:
+        raise ValueError("karman_advect_bwd: the cotangents must have the shapes of d, svy, svx")
+    ws = _workspace(lib.sol_karman_advect_bwd_workspace_bytes(C.byref(cfg)), workspace, d.device)
+    outs = torch.empty_like(d), torch.empty_like(svy), torch.empty_like(svx)
+    check(lib.sol_karman_advect_bwd(C.byref(cfg), stream(), ptr(d), ptr(svy), ptr(svx), ptr(active), ptr(inflow), int(s is not None),
+                                    1.0 if s is None else s, ptr(g_d), ptr(g_ay), ptr(g_ax), *(ptr(t) for t in outs), int(bool(tile)),
+                                    ptr(ws), ws.numel() * 4))
+    return outs
 
 
 # --------------------------------------------------------------------------------------
@@ -288,17 +385,23 @@ def _sub_adjoint(oy, ox, g_re, re, cfg, nsub):
     return oy, ox, g_re
 
 
-def karman_step_saved(d, vy, vx, re, cfg, masks, workspace=None, info=None, buoyancy=None, diffusion_substeps=1):
+def karman_step_saved(d, vy, vx, re, cfg, masks, workspace=None, info=None, buoyancy=None, diffusion_substeps=1,
+                      advection="semi_lagrangian", correction_strength=1.0):
     """The differentiable form of the step without autograd, on any grid: ((d, vy, vx) after the step, saved vy, saved vx) -- the
     post-diffusion velocity the adjoints take.  A one-workgroup grid runs sol_karman_step_fwd (`info` receives "iterations"), a grid
     beyond them (masks.large) sol_karman_step_fwd_large_saved with `workspace` and `info` as in karman_step_large.
     buoyancy = (fy, fx) (large grids only): sol_karman_step_fwd_large_saved_buoy, the density pushes the velocity.
-    diffusion_substeps = n > 1 (grids with Y, X >= 16): karman_diffuse_sub, then the same launches on diffusion_sub_cfg(cfg, n)."""
+    diffusion_substeps = n > 1 (grids with Y, X >= 16): karman_diffuse_sub, then the same launches on diffusion_sub_cfg(cfg, n).
+    advection = "mac_cormack" (large grids only): sol_karman_step_fwd_large_saved_adv, the MacCormack advection of velocity and density
+    with correction_strength in [0, 1]; "semi_lagrangian" issues the launches and gives the bits of a call without the keyword."""
     n = diffusion_substeps_arg(diffusion_substeps)
+    adv = advection_arg(advection, correction_strength, "karman_step_saved: advection")
+    if adv is not None:
+        _require_large_for_advection(masks, cfg.Y, cfg.X, "karman_step_saved")
     if n > 1:
         _require_sub_grid(cfg, "karman_step_saved")
         pvy, pvx = karman_diffuse_sub(vy, vx, re, cfg, n)
-        return karman_step_saved(d, pvy, pvx, re, diffusion_sub_cfg(cfg, n), masks, workspace, info, buoyancy)
+        return karman_step_saved(d, pvy, pvx, re, diffusion_sub_cfg(cfg, n), masks, workspace, info, buoyancy, 1, advection, correction_strength)
     if buoyancy is not None:
         _require_large_for_buoyancy(masks, cfg.Y, cfg.X, "karman_step_saved")
     _lib.require_gpu()
@@ -309,9 +412,11 @@ def karman_step_saved(d, vy, vx, re, cfg, masks, workspace=None, info=None, buoy
     outs, head = _step_fwd_args(d, vy, vx, re, cfg, masks)
     svy, svx = torch.empty_like(vy), torch.empty_like(vx)
     if masks.large:
-        workspace = _workspace(large_workspace_bytes(cfg, masks), workspace, vy.device)
+        workspace = _workspace(large_workspace_bytes(cfg, masks) if adv is None else large_adv_workspace_bytes(cfg, masks, True), workspace, vy.device)
         cg_info = _cg_info(masks, B, vy.device)
         entry, tail = (lib.sol_karman_step_fwd_large_saved, ()) if buoyancy is None else (lib.sol_karman_step_fwd_large_saved_buoy, tuple(buoyancy))
+        if adv is not None:
+            entry, tail = lib.sol_karman_step_fwd_large_saved_adv, (tuple(buoyancy) if buoyancy is not None else (0.0, 0.0)) + (1, adv)
         check(entry(*head, ptr(svy), ptr(svx), _hdr(masks.direct_header), ptr(masks.box),
                     _hdr(masks.box_header), ptr(cg_info), ptr(workspace), workspace.numel() * 4, *tail))
         _publish_cg(info, cg_info)
@@ -327,7 +432,7 @@ karman_step_large_saved = karman_step_saved      # the name the large-grid calle
 
 
 def karman_step_large(d, vy, vx, re, cfg, masks, workspace=None, info=None, feat=None, feat_scale=None, p_guess=None, out=None,
-                      density_grad=False, re_grad=False, buoyancy=None, diffusion_substeps=1):
+                      density_grad=False, re_grad=False, buoyancy=None, diffusion_substeps=1, advection="semi_lagrangian", correction_strength=1.0):
     """The step for grids beyond the one-workgroup kernels (data generation at 256 x 128,
     /root/reference/karman-2d/karman.py:98-159): sol_karman_step_fwd_large (direct solve) or sol_karman_step_fwd_large_cg (CG solve,
     masks.pressure_solver == "cg").  Returns (d, vy, vx) after the step; with the CG solve, `info` (a dict) receives "iterations" and
@@ -347,8 +452,15 @@ def karman_step_large(d, vy, vx, re, cfg, masks, workspace=None, info=None, feat
     keeps it in the graph as density_grad would (KarmanStepFn's buoyant mode).
     diffusion_substeps = n > 1: the velocity is diffused by n explicit substeps of alpha / n, the boundary blend after the last one
     (karman_diffuse_sub, one launch per diffuse_sub_max() substeps, then the launches above on diffusion_sub_cfg(cfg, n)); composes with
-    every mode and extra above.  n = 1 issues the launches and gives the bits of a call without the keyword."""
+    every mode and extra above.  n = 1 issues the launches and gives the bits of a call without the keyword.
+    advection = "mac_cormack", correction_strength = s in [0, 1]: velocity and density are advected by the MacCormack scheme with the
+    revert-to-semi-Lagrangian limiter (sol_karman_step_fwd_large_adv; the differentiable form through KarmanStepFn's adv mode, whose
+    adjoint freezes the limiter's decisions); composes with every mode and extra above.  "semi_lagrangian" issues the launches and gives
+    the bits of a call without the keyword."""
     nsub = diffusion_substeps_arg(diffusion_substeps)
+    adv = advection_arg(advection, correction_strength, "karman_step_large: advection")
+    if adv is not None:
+        _require_large_for_advection(masks, cfg.Y, cfg.X, "karman_step_large")
     if nsub > 1:
         _require_sub_grid(cfg, "karman_step_large")
     if buoyancy is not None:
@@ -364,18 +476,18 @@ def karman_step_large(d, vy, vx, re, cfg, masks, workspace=None, info=None, feat
     if differentiable:
         if feat is not None or p_guess is not None or out is not None:
             raise ValueError("karman_step_large: feat / p_guess / out belong to the no-grad step (the differentiable step keeps its own state)")
-        return KarmanStepFn.apply(d, vy, vx, re, cfg, masks, workspace, info, density, want_re, buoyancy if _buoyant(buoyancy) else None, nsub)
+        return KarmanStepFn.apply(d, vy, vx, re, cfg, masks, workspace, info, density, want_re, buoyancy if _buoyant(buoyancy) else None, nsub, adv)
     if nsub > 1:
         pvy, pvx = karman_diffuse_sub(vy, vx, re, cfg, nsub)
         return karman_step_large(d, pvy, pvx, re, diffusion_sub_cfg(cfg, nsub), masks, workspace, info, feat, feat_scale, p_guess, out,
-                                 buoyancy=buoyancy)
+                                 buoyancy=buoyancy, advection=advection, correction_strength=correction_strength)
     if (feat is None) != (feat_scale is None):
         raise ValueError("karman_step_large: feat and feat_scale go together")
     if feat is not None and (feat.shape != (B, Y, X, 4) or feat.device != vy.device):
         raise ValueError("karman_step_large: feat must be [B,Y,X,4] = %s on %s (got %s on %s)" % ((B, Y, X, 4), vy.device, tuple(feat.shape), feat.device))
     if p_guess is not None and (p_guess.shape != (B, Y, X) or p_guess.device != vy.device):
         raise ValueError("karman_step_large: p_guess must be [B,Y,X] = %s on %s (got %s on %s)" % ((B, Y, X), vy.device, tuple(p_guess.shape), p_guess.device))
-    workspace = _workspace(large_workspace_bytes(cfg, masks), workspace, vy.device)
+    workspace = _workspace(large_workspace_bytes(cfg, masks) if adv is None else large_adv_workspace_bytes(cfg, masks), workspace, vy.device)
     if out is None:
         outs, head = _step_fwd_args(d, vy, vx, re, cfg, masks)
     else:
@@ -385,7 +497,11 @@ def karman_step_large(d, vy, vx, re, cfg, masks, workspace=None, info=None, feat
         head = _step_fwd_args(d, vy, vx, re, cfg, masks, outs)[1]
     fs = None if feat_scale is None else (feat_scale if isinstance(feat_scale, C.Array) else _scale3(feat_scale))
     cg_info = _cg_info(masks, B, vy.device)
-    if buoyancy is not None:
+    if adv is not None:
+        check(lib.sol_karman_step_fwd_large_adv(*head, ptr(feat), fs, _hdr(masks.direct_header), ptr(masks.box), _hdr(masks.box_header),
+                                                ptr(cg_info), ptr(p_guess), ptr(workspace), workspace.numel() * 4,
+                                                *(buoyancy if buoyancy is not None else (0.0, 0.0)), 1, adv))
+    elif buoyancy is not None:
         check(lib.sol_karman_step_fwd_large_buoy(*head, ptr(feat), fs, _hdr(masks.direct_header), ptr(masks.box), _hdr(masks.box_header),
                                                  ptr(cg_info), ptr(p_guess), ptr(workspace), workspace.numel() * 4, *buoyancy))
     elif cg_info is None:
@@ -520,17 +636,70 @@ def _large_bwd(who, svy, svx, re, gvy, gvx, cfg, masks, workspace, info, re_in=N
     return (oy, ox) if re_in is None else (oy, ox, g_re)
 
 
-def karman_step_large_bwd(svy, svx, re, gvy, gvx, cfg, masks, workspace=None, info=None, diffusion_substeps=1):
+def _large_bwd_adv(d, svy, svx, re, gvy, gvx, gd, cfg, masks, buoyancy, adv, vel_in, workspace, info, density_workspace, density=True):
+    """The adjoint under advection="mac_cormack" (adv = the correction strength) on the cfg as given, in _large_bwd_buoy's shape:
+    sol_karman_step_bwd_large_adv(_re) when a velocity cotangent arrived (force (0, 0) without buoyancy), then -- `density`: the density
+    is in the graph -- sol_karman_density_bwd_adv(_re) on g_dsum, added onto its result.  -> (g_d_in, g_vy_in, g_vx_in[, g_re])"""
+    who = "karman_step_large_bwd (mac_cormack)"
+    _require_large_for_advection(masks, cfg.Y, cfg.X, who)
+    if gvy is None and gvx is None and (gd is None or not density):
+        return (None,) * (3 if vel_in is None else 4)
+    if vel_in is not None:
+        _require_staged(cfg, who)
+    _lib.require_gpu()
+    lib = _lib.load()
+    svy, svx, re = (_lib.f32(t) for t in (svy, svx, re))
+    gd = None if gd is None or not density else _lib.f32(gd)
+    force = (0.0, 0.0) if buoyancy is None else (float(buoyancy[0]), float(buoyancy[1]))
+    od = oy = ox = g_re = None
+    g_dsum = gd
+    if gvy is not None or gvx is not None:
+        gvy = torch.zeros_like(svy) if gvy is None else _lib.f32(gvy)
+        gvx = torch.zeros_like(svx) if gvx is None else _lib.f32(gvx)
+        if vel_in is None:
+            entry, tail = lib.sol_karman_step_bwd_large_adv, ()
+        else:
+            entry = lib.sol_karman_step_bwd_large_adv_re
+            tail, g_re = _re_tail(who, tuple(vel_in) + (None,), svy, svx, cfg.B)
+        box, box_header = masks.staged_box()
+        workspace = _workspace(large_bwd_adv_workspace_bytes(cfg, masks, vel_in is not None), workspace, svy.device)
+        oy, ox = torch.empty_like(svy), torch.empty_like(svx)
+        g_dsum = torch.empty(cfg.B, cfg.Y, cfg.X, dtype=torch.float32, device=svy.device)
+        cg_info = _cg_info(masks, cfg.B, svy.device)
+        check(entry(C.byref(cfg), stream(), ptr(svy), ptr(svx), ptr(re), ptr(masks.active), ptr(masks.velBCyMask), masks.bc_stride,
+                    ptr(gvy), ptr(gvx), ptr(oy), ptr(ox), _hdr(masks.direct_header), ptr(box), _hdr(box_header), ptr(cg_info),
+                    ptr(workspace), workspace.numel() * 4, *tail, force[0], force[1], ptr(gd), ptr(g_dsum), 1, adv))
+        _publish_cg(info, cg_info, "_bwd")
+        if gd is None and force == (0.0, 0.0):
+            g_dsum = None              # nothing reaches the density: its adjoint is skipped
+    if density and g_dsum is not None:
+        res = _density_bwd(who, d, svy, svx, re, g_dsum, cfg, masks, oy, ox, density_workspace,
+                           None if vel_in is None else tuple(vel_in) + (g_re,), adv)
+        od, oy, ox = res[:3]
+        if vel_in is not None:
+            g_re = res[3]
+    return (od, oy, ox) if vel_in is None else (od, oy, ox, g_re)
+
+
+def karman_step_large_bwd(svy, svx, re, gvy, gvx, cfg, masks, workspace=None, info=None, diffusion_substeps=1,
+                          advection="semi_lagrangian", correction_strength=1.0):
     """Adjoint of the large-grid step (sol_karman_step_bwd_large): (g_vy_in, g_vx_in) from the saved post-diffusion velocity and the
     gradient with respect to the step's output velocity.  With the CG solve, `info` receives "iterations_bwd" / "converged_bwd".
     diffusion_substeps = n: the adjoint of karman_step_saved(.., diffusion_substeps=n) -- the same launches on diffusion_sub_cfg(cfg, n),
-    then karman_diffuse_sub on their result (`cfg` is the step's own, unscaled one)."""
+    then karman_diffuse_sub on their result (`cfg` is the step's own, unscaled one).
+    advection = "mac_cormack": the adjoint of the step with that advection (sol_karman_step_bwd_large_adv), the velocity's part -- the
+    density's is karman_density_bwd with the same keywords."""
     n = diffusion_substeps_arg(diffusion_substeps)
+    adv = advection_arg(advection, correction_strength, "karman_step_large_bwd: advection")
+    if adv is not None:
+        res = _large_bwd_adv(None, svy, svx, re, gvy, gvx, None, diffusion_sub_cfg(cfg, n), masks, None, adv, None, workspace, info, None, density=False)
+        return _sub_adjoint(res[1], res[2], None, re, cfg, n)[:2]
     oy, ox = _large_bwd("karman_step_large_bwd", svy, svx, re, gvy, gvx, diffusion_sub_cfg(cfg, n), masks, workspace, info)
     return _sub_adjoint(oy, ox, None, re, cfg, n)[:2]
 
 
-def karman_step_large_bwd_re(svy, svx, re, gvy, gvx, vy_in, vx_in, cfg, masks, g_re=None, workspace=None, info=None, diffusion_substeps=1):
+def karman_step_large_bwd_re(svy, svx, re, gvy, gvx, vy_in, vx_in, cfg, masks, g_re=None, workspace=None, info=None, diffusion_substeps=1,
+                             advection="semi_lagrangian", correction_strength=1.0):
     """The staged velocity adjoint with the gradient with respect to re (sol_karman_step_bwd_large_re), on every grid with Y, X >= 16 --
     the one-workgroup grids included: (g_vy_in, g_vx_in, g_re) from the saved post-diffusion velocity, the cotangent of the step's output
     velocity and the step's INPUT velocity.  g_vy_in / g_vx_in are karman_step_large_bwd's bits.  g_re [B]: a buffer to add onto (one
@@ -540,12 +709,22 @@ def karman_step_large_bwd_re(svy, svx, re, gvy, gvx, vy_in, vx_in, cfg, masks, g
     n = diffusion_substeps_arg(diffusion_substeps)
     if n > 1 and g_re is not None:
         raise ValueError("karman_step_large_bwd_re: with diffusion_substeps > 1 the gradient in re is written to a fresh tensor (g_re=None)")
+    adv = advection_arg(advection, correction_strength, "karman_step_large_bwd_re: advection")
+    if adv is not None:           # sol_karman_step_bwd_large_adv_re
+        if g_re is not None:
+            raise ValueError("karman_step_large_bwd_re: with advection='mac_cormack' the gradient in re is written to a fresh tensor (g_re=None)")
+        res = _large_bwd_adv(None, svy, svx, re, gvy, gvx, None, diffusion_sub_cfg(cfg, n), masks, None, adv, (vy_in, vx_in), workspace, info, None,
+                             density=False)
+        return _sub_adjoint(res[1], res[2], res[3], re, cfg, n)
     oy, ox, g = _large_bwd("karman_step_large_bwd_re", svy, svx, re, gvy, gvx, diffusion_sub_cfg(cfg, n), masks, workspace, info, (vy_in, vx_in, g_re))
     return _sub_adjoint(oy, ox, g, re, cfg, n)
 
 
-def _density_bwd(who, d, svy, svx, re, g_d, cfg, masks, g_vy, g_vx, workspace, re_in=None):
-    """karman_density_bwd (re_in None) and karman_density_bwd_re (re_in = (vy_in, vx_in, g_re)), paired as in _large_bwd"""
+def _density_bwd(who, d, svy, svx, re, g_d, cfg, masks, g_vy, g_vx, workspace, re_in=None, adv=None):
+    """karman_density_bwd (re_in None) and karman_density_bwd_re (re_in = (vy_in, vx_in, g_re)), paired as in _large_bwd; adv = the
+    correction strength of advection="mac_cormack": the _adv entry points"""
+    if adv is not None:
+        _adv_grid(cfg, who)
     _lib.require_gpu()
     lib = _lib.load()
     if (g_vy is None) != (g_vx is None):
@@ -563,6 +742,9 @@ def _density_bwd(who, d, svy, svx, re, g_d, cfg, masks, g_vy, g_vx, workspace, r
     else:
         entry, nbytes = lib.sol_karman_density_bwd_re, density_bwd_re_workspace_bytes(cfg)
         tail, g_re = _re_tail(who, re_in, svy, svx, B)
+    if adv is not None:
+        entry = lib.sol_karman_density_bwd_adv if re_in is None else lib.sol_karman_density_bwd_adv_re
+        nbytes, tail = density_bwd_adv_workspace_bytes(cfg, re_in is not None), tuple(tail) + (1, adv)
     oy, ox = (g_vy, g_vx) if accumulate else (torch.empty_like(svy), torch.empty_like(svx))
     od = torch.empty_like(d)
     workspace = _workspace(nbytes, workspace, d.device)
@@ -571,18 +753,22 @@ def _density_bwd(who, d, svy, svx, re, g_d, cfg, masks, g_vy, g_vx, workspace, r
     return (od, oy, ox) if re_in is None else (od, oy, ox, g_re)
 
 
-def karman_density_bwd(d, svy, svx, re, g_d, cfg, masks, g_vy=None, g_vx=None, workspace=None):
+def karman_density_bwd(d, svy, svx, re, g_d, cfg, masks, g_vy=None, g_vx=None, workspace=None, advection="semi_lagrangian", correction_strength=1.0):
     """Adjoint of the step's marker density (sol_karman_density_bwd), on any grid: (g_d_in, g_vy_in, g_vx_in) from the step's input
     density `d`, the saved post-diffusion velocity and the gradient `g_d` with respect to the step's output density.  g_vy / g_vx (both
     or neither): buffers that already hold the velocity adjoint's result; the density's part is added onto them in place (one fp32 add
-    per face) and they are returned.  Without them the density's part alone is written to fresh tensors."""
-    return _density_bwd("karman_density_bwd", d, svy, svx, re, g_d, cfg, masks, g_vy, g_vx, workspace)
+    per face) and they are returned.  Without them the density's part alone is written to fresh tensors.
+    advection = "mac_cormack" (grids with Y, X >= 16): the adjoint of the MacCormack-advected density (sol_karman_density_bwd_adv)."""
+    adv = advection_arg(advection, correction_strength, "karman_density_bwd: advection")
+    return _density_bwd("karman_density_bwd", d, svy, svx, re, g_d, cfg, masks, g_vy, g_vx, workspace, None, adv)
 
 
-def karman_density_bwd_re(d, svy, svx, re, g_d, vy_in, vx_in, cfg, masks, g_vy=None, g_vx=None, g_re=None, workspace=None):
+def karman_density_bwd_re(d, svy, svx, re, g_d, vy_in, vx_in, cfg, masks, g_vy=None, g_vx=None, g_re=None, workspace=None,
+                          advection="semi_lagrangian", correction_strength=1.0):
     """karman_density_bwd with the gradient with respect to re (sol_karman_density_bwd_re): (g_d_in, g_vy_in, g_vx_in, g_re).  The first
     three are karman_density_bwd's bits; g_re [B]: a buffer to add onto (the velocity adjoint's part), else a fresh one is written."""
-    return _density_bwd("karman_density_bwd_re", d, svy, svx, re, g_d, cfg, masks, g_vy, g_vx, workspace, (vy_in, vx_in, g_re))
+    adv = advection_arg(advection, correction_strength, "karman_density_bwd_re: advection")
+    return _density_bwd("karman_density_bwd_re", d, svy, svx, re, g_d, cfg, masks, g_vy, g_vx, workspace, (vy_in, vx_in, g_re), adv)
 
 
 def karman_buoyancy_add(d, vy, vx, active, f):
@@ -611,7 +797,7 @@ def karman_buoyancy_add_bwd(gvy, gvx, active, f, gd=None):
 
 
 def karman_step_large_bwd_buoy(d, svy, svx, re, gvy, gvx, gd, cfg, masks, buoyancy, vel_in=None, workspace=None, info=None,
-                               density_workspace=None, diffusion_substeps=1):
+                               density_workspace=None, diffusion_substeps=1, advection="semi_lagrangian", correction_strength=1.0):
     """Adjoint of the BUOYANT large-grid step (karman_step_saved(..., buoyancy=F)): (g_d_in, g_vy_in, g_vx_in) -- with vel_in = (vy, vx),
     the step's input velocity, (g_d_in, g_vy_in, g_vx_in, g_re) -- from the step's input density `d`, the saved post-diffusion velocity and
     the cotangents gvy, gvx, gd of its outputs (None = zero).  With a velocity cotangent: sol_karman_step_bwd_large_buoy(_re) (the plain
@@ -619,9 +805,16 @@ def karman_step_large_bwd_buoy(d, svy, svx, re, gvy, gvx, gd, cfg, masks, buoyan
     added onto the velocity adjoint's result.  Without one (a density-only loss) no pressure solve runs: the density adjoint on gd alone.
     No cotangent at all: every result is None.  workspace / density_workspace: scratch of the velocity / the density adjoint.
     diffusion_substeps = n > 1: the same launches on diffusion_sub_cfg(cfg, n) (vel_in is then the PRE-DIFFUSED input velocity,
-    karman_diffuse_sub(vy, vx, re, cfg, n)), then karman_diffuse_sub on the velocity cotangent and g_re times n."""
+    karman_diffuse_sub(vy, vx, re, cfg, n)), then karman_diffuse_sub on the velocity cotangent and g_re times n.
+    advection = "mac_cormack", correction_strength = s: the adjoint of the step with that advection -- the same chain over
+    sol_karman_step_bwd_large_adv(_re) and sol_karman_density_bwd_adv(_re)."""
     n = diffusion_substeps_arg(diffusion_substeps)
-    res = _large_bwd_buoy(d, svy, svx, re, gvy, gvx, gd, diffusion_sub_cfg(cfg, n), masks, buoyancy, vel_in, workspace, info, density_workspace)
+    adv = advection_arg(advection, correction_strength, "karman_step_large_bwd_buoy: advection")
+    if adv is not None:           # the _adv entry points: the same chain with the MacCormack advection's adjoints
+        _require_large_for_buoyancy(masks, cfg.Y, cfg.X, "karman_step_large_bwd_buoy")
+        res = _large_bwd_adv(d, svy, svx, re, gvy, gvx, gd, diffusion_sub_cfg(cfg, n), masks, buoyancy, adv, vel_in, workspace, info, density_workspace)
+    else:
+        res = _large_bwd_buoy(d, svy, svx, re, gvy, gvx, gd, diffusion_sub_cfg(cfg, n), masks, buoyancy, vel_in, workspace, info, density_workspace)
     if n == 1:
         return res
     oy, ox, g_re = _sub_adjoint(res[1], res[2], res[3] if vel_in is not None else None, re, cfg, n)
@@ -691,7 +884,7 @@ class KarmanStepFn(torch.autograd.Function):
     cfg (diffusion_sub_cfg); g_re times n.  Composes with every other mode; nsub = 1 launches nothing new."""
 
     @staticmethod
-    def forward(ctx, d, vy, vx, re, cfg, masks, workspace, info, density, want_re, buoyancy=None, nsub=1):
+    def forward(ctx, d, vy, vx, re, cfg, masks, workspace, info, density, want_re, buoyancy=None, nsub=1, adv=None):
         _lib.require_gpu()
         d, vy, vx, re = (_lib.f32(t) for t in (d, vy, vx, re))
         density = bool(density) or buoyancy is not None
@@ -702,7 +895,11 @@ class KarmanStepFn(torch.autograd.Function):
             _require_sub_grid(cfg, "diffusion_substeps")
             vy, vx = karman_diffuse_sub(vy, vx, re, cfg, nsub)
             cfg = diffusion_sub_cfg(cfg, nsub)
-        outs, svy, svx = karman_step_saved(d, vy, vx, re, cfg, masks, workspace, info, buoyancy)
+        # adv (advection="mac_cormack": its correction strength; large grids): the _adv forward launches, and in backward the chain of
+        # _large_bwd_adv in every mode
+        ctx.adv = adv
+        outs, svy, svx = karman_step_saved(d, vy, vx, re, cfg, masks, workspace, info, buoyancy,
+                                           **({} if adv is None else {"advection": "mac_cormack", "correction_strength": adv}))
         ctx.save_for_backward(svy, svx, re, *((d, vy, vx) if want_re else (d,) if density else ()))
         ctx.cfg, ctx.masks, ctx.info, ctx.density, ctx.want_re, ctx.buoyancy = cfg, masks, info, density, want_re, buoyancy
         if not density:
@@ -716,11 +913,17 @@ class KarmanStepFn(torch.autograd.Function):
         cfg, masks = ctx.cfg, ctx.masks
         vel_in = tuple(inputs[1:]) if ctx.want_re else None
         od = oy = ox = g_re = None
+        if ctx.adv is not None:
+            gvy, gvx, gd = (None if g is None else g.contiguous() for g in (gvy, gvx, gd))
+            res = _large_bwd_adv(inputs[0] if ctx.density else None, svy, svx, re, gvy, gvx, gd, cfg, masks, ctx.buoyancy, ctx.adv, vel_in, None,
+                                 ctx.info, None, density=ctx.density)
+            oy, ox, g_re = _sub_adjoint(res[1], res[2], res[3] if vel_in is not None else None, re, ctx.cfg_full, ctx.nsub)
+            return res[0], oy, ox, g_re, None, None, None, None, None, None, None, None, None
         if ctx.buoyancy is not None:
             gvy, gvx, gd = (None if g is None else g.contiguous() for g in (gvy, gvx, gd))
             res = _large_bwd_buoy(inputs[0], svy, svx, re, gvy, gvx, gd, cfg, masks, ctx.buoyancy, vel_in, None, ctx.info, None)
             oy, ox, g_re = _sub_adjoint(res[1], res[2], res[3] if vel_in is not None else None, re, ctx.cfg_full, ctx.nsub)
-            return res[0], oy, ox, g_re, None, None, None, None, None, None, None, None
+            return res[0], oy, ox, g_re, None, None, None, None, None, None, None, None, None
         if gvy is not None or gvx is not None:
             oy, ox, g_re = _velocity_bwd(svy, svx, re, gvy, gvx, cfg, masks, ctx.info, vel_in)
         if ctx.density and gd is not None:        # added onto the velocity half's buffers and g_re
@@ -729,7 +932,7 @@ class KarmanStepFn(torch.autograd.Function):
             else:
                 od, oy, ox, g_re = karman_density_bwd_re(inputs[0], svy, svx, re, gd, *vel_in, cfg, masks, oy, ox, g_re)
         oy, ox, g_re = _sub_adjoint(oy, ox, g_re, re, ctx.cfg_full, ctx.nsub)
-        return od, oy, ox, g_re, None, None, None, None, None, None, None, None
+        return od, oy, ox, g_re, None, None, None, None, None, None, None, None, None
 
 
 def _step_mode(d, vy, vx, re, cfg, density_grad, re_grad, buoyancy=None):

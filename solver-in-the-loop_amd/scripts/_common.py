@@ -82,6 +82,38 @@ def agreed_buoyancy(recorded, flag, where):
     return norm(recorded)
 
 
+def add_advection_arg(p, generates=True):
+    """--advection semi_lagrangian|mac_cormack and --mc-strength S of karman.py; the scripts that read data default to what the data recorded"""
+    p.add_argument("--advection", default=None, choices=["semi_lagrangian", "mac_cormack"],
+                   help="advection scheme of the solver step (mac_cormack: large grids only; keeps what the semi-Lagrangian step smears).  "
+                        "Stored with the data like the scene; absent: %s" % ("semi_lagrangian" if generates else "what the data recorded"))
+    p.add_argument("--mc-strength", default=None, type=float, metavar="S",
+                   help="correction strength of mac_cormack, 0 <= S <= 1; absent: %s" % ("1" if generates else "what the data recorded"))
+
+
+def advection_from_args(params):
+    """(name, strength) of --advection / --mc-strength with None for an absent flag; a strength outside [0, 1] ends the run"""
+    from sol_amd import ops
+    name, s = params.get("advection"), params.get("mc_strength")
+    try:
+        ops.advection_arg(name or "semi_lagrangian", 1.0 if s is None else s, "--advection")
+    except ValueError as e:
+        raise SystemExit("bad --advection / --mc-strength: %s" % e)
+    return name, s
+
+
+def agreed_advection(recorded, flags, where):
+    """The advection of a run that reads data, as KarmanFlow / trainer keywords: what the data recorded ("advection", "correction_strength";
+    absent: semi_lagrangian), unless the flags say otherwise -- a contradiction.  recorded: a dict with those keys, or None."""
+    rec = recorded or {}
+    name, s = rec.get("advection") or "semi_lagrangian", float(1.0 if rec.get("correction_strength") is None else rec["correction_strength"])
+    if flags[0] is not None and flags[0] != name:
+        raise SystemExit("--advection %s contradicts the scheme recorded in %s (%s)" % (flags[0], where, name))
+    if flags[1] is not None and name == "mac_cormack" and float(flags[1]) != s:
+        raise SystemExit("--mc-strength %s contradicts the strength recorded in %s (%s)" % (flags[1], where, s))
+    return {"advection": name, "correction_strength": s}
+
+
 def add_substeps_arg(p, auto=True, bound="1/4"):
     """--diffusion-substeps N|auto of karman.py (auto: the smallest stable count for the run's Reynolds numbers); the scripts that read
     data take N only and default to what the data recorded.  bound: the single stencil's stability bound in the help text (karman3d.py: 1/6)"""

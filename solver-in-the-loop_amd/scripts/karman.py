@@ -6,15 +6,17 @@ reference solutions, Makefile:19-28) run the multi-launch path (nothing is kept 
 else the preconditioned CG.  --obstacle / --obstacle-mask choose the scene (recorded in params.pickle as "scene").  --buoyancy FY[,FX]
 (large grids only): the density pushes the velocity; recorded in params.pickle as "buoyancy" (a pair, or None: off), so that training and
 roll-out pick it up from the data.  --diffusion-substeps N|auto: explicit diffusion substeps per step (auto: the smallest count for which
-dt res^2 / (n Re) <= 1/4, ops.min_diffusion_substeps); recorded in params.pickle as "diffusion_substeps" (an integer, 1: the single stencil)."""
+dt res^2 / (n Re) <= 1/4, ops.min_diffusion_substeps); recorded in params.pickle as "diffusion_substeps" (an integer, 1: the single stencil).
+--advection semi_lagrangian|mac_cormack, --mc-strength S (mac_cormack: large grids only): the advection scheme of the step; recorded in
+params.pickle as "advection" and "correction_strength", picked up from there by training, roll-out and the Re fit."""
 import argparse
 import pickle
 
 import numpy as np
 import torch
 
-from _common import (add_buoyancy_arg, add_scene_args, add_substeps_arg, buoyancy_from_args, flow_kwargs, logger, scene_from_args, select_gpu,
-                     substeps_from_args)
+from _common import (add_advection_arg, add_buoyancy_arg, add_scene_args, add_substeps_arg, advection_from_args, buoyancy_from_args, flow_kwargs,
+                     logger, scene_from_args, select_gpu, substeps_from_args)
 import sol_amd
 from sol_amd import ops, scene
 
@@ -37,6 +39,7 @@ def main(argv=None):
     add_scene_args(p)
     add_buoyancy_arg(p)
     add_substeps_arg(p)
+    add_advection_arg(p)
     params = vars(p.parse_args(argv))
     select_gpu(params["gpu"])
     log = logger()
@@ -46,8 +49,11 @@ def main(argv=None):
     rec = scene_from_args(params)
     params["buoyancy"] = buoyancy_from_args(params)
     params["diffusion_substeps"] = substeps_from_args(params, [params["re"]], res) or 1
+    name, strength = advection_from_args(params)
+    params["advection"], params["correction_strength"] = name or "semi_lagrangian", 1.0 if strength is None else float(strength)
     sim = sol_amd.KarmanFlow(pressure_solver=params["pressure_solver"], buoyancy=params["buoyancy"],
-                             diffusion_substeps=params["diffusion_substeps"], **flow_kwargs(rec))
+                             diffusion_substeps=params["diffusion_substeps"], advection=params["advection"],
+                             correction_strength=params["correction_strength"], **flow_kwargs(rec))
     params["scene"] = sim.scene()
     d0 = scene.downsample(scene.read_zipped_array(params["initdH"]), params["scale"]) if params["initdH"] else np.zeros((1, Y, X, 1))
     if params["initvH"]:

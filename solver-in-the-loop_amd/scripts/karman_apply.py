@@ -9,7 +9,7 @@ import pickle
 import numpy as np
 import torch
 
-from _common import (add_buoyancy_arg, add_scene_args, add_substeps_arg, agreed_buoyancy, agreed_substeps, buoyancy_from_args, flow_kwargs, logger,
+from _common import (add_advection_arg, advection_from_args, agreed_advection, add_buoyancy_arg, add_scene_args, add_substeps_arg, agreed_buoyancy, agreed_substeps, buoyancy_from_args, flow_kwargs, logger,
                      scene_from_args, select_gpu, substeps_from_args)
 import sol_amd
 from sol_amd import ops, scene
@@ -32,6 +32,7 @@ def main(argv=None):
     add_scene_args(p, warm_start=True)
     add_buoyancy_arg(p)
     add_substeps_arg(p, auto=False)
+    add_advection_arg(p, generates=False)
     params = vars(p.parse_args(argv))
     select_gpu(params["gpu"])
     log = logger()
@@ -71,6 +72,11 @@ def main(argv=None):
     nsub = agreed_substeps(data_stats["diffusion_substeps"], substeps_from_args(params), params["stats"]) if "diffusion_substeps" in data_stats \
         else (substeps_from_args(params) or 1)
     log.info("diffusion substeps: %d" % nsub)
+    # and the advection scheme (dataStats "advection" / "correction_strength"; absent: semi_lagrangian, or the flags)
+    flags_adv = advection_from_args(params)
+    advection = agreed_advection(data_stats, flags_adv, params["stats"]) if "advection" in data_stats \
+        else agreed_advection({"advection": flags_adv[0], "correction_strength": flags_adv[1]}, (None, None), "the flags")
+    log.info("advection: %s" % (advection,))
     active, inflow = sim.scene_arrays(dom)
     velBCy, velBCyMask = sol_amd.velocity_bc_masks(Y, X)
     masks = ops.SceneMasks(active, inflow, velBCy.reshape(Y + 1, X), velBCyMask.reshape(Y + 1, X),
@@ -84,7 +90,7 @@ def main(argv=None):
     # (a CG scene runs eagerly, every solve stops at convergence; a direct-solve scene replays one captured step)
     ro = sol_amd.make_rollout(model, masks, 1, Y, X, dom.dx[1], data_stats["std"][1], data_stats["ext.std"][0],
                               use_graph=ops.is_direct(masks.pressure_solver), cg_warm_start=warm, any_width=params["any_width"],
-                              buoyancy=buoyancy, diffusion_substeps=nsub)
+                              buoyancy=buoyancy, diffusion_substeps=nsub, **advection)
     f = lambda a: torch.as_tensor(np.ascontiguousarray(a), dtype=torch.float32, device="cuda").contiguous()
     vy0, vx0 = scene.split_staggered(np.asarray(vn, dtype=np.float32))
     d, vy, vx = f(np.asarray(d0)[..., 0]), f(vy0), f(vx0)

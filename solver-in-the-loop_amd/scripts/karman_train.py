@@ -17,7 +17,7 @@ import time
 import numpy as np
 import torch
 
-from _common import (add_buoyancy_arg, add_scene_args, add_substeps_arg, agreed_buoyancy, agreed_substeps, buoyancy_from_args, flow_kwargs, logger,
+from _common import (add_advection_arg, advection_from_args, agreed_advection, add_buoyancy_arg, add_scene_args, add_substeps_arg, agreed_buoyancy, agreed_substeps, buoyancy_from_args, flow_kwargs, logger,
                      scene_from_args, select_gpu, substeps_from_args)
 import sol_amd
 from sol_amd import ops, scene
@@ -54,6 +54,7 @@ def main(argv=None):
     add_scene_args(p)
     add_buoyancy_arg(p)
     add_substeps_arg(p, auto=False)
+    add_advection_arg(p, generates=False)
     params = vars(p.parse_args(argv))
     select_gpu(params["gpu"])
     rank, world, local = sol_amd.dist.init_from_env()
@@ -79,13 +80,15 @@ def main(argv=None):
     # must agree, and an explicit --obstacle / --obstacle-mask must agree with them
     # the buoyancy force travels the same way ("buoyancy" in params.pickle; absent: off)
     # and so do the diffusion substeps ("diffusion_substeps" in params.pickle; absent: 1)
-    rec_set, buoy_set, sub_set = None, [], []
+    # and the advection scheme ("advection" / "correction_strength" in params.pickle; absent: semi_lagrangian)
+    rec_set, buoy_set, sub_set, adv_set = None, [], [], []
     for s in dataset.dataSims:
         with open(s + "/params.pickle", "rb") as f:
             pk = pickle.load(f)
         r = pk.get("scene") or sol_amd.karman.scene_record()
         buoy_set.append(agreed_buoyancy(pk.get("buoyancy"), None, s))
         sub_set.append(agreed_substeps(pk.get("diffusion_substeps"), None, s))
+        adv_set.append(tuple(sorted(agreed_advection(pk, (None, None), s).items())))
         if rec_set is not None and not sol_amd.karman.scenes_equal(r, rec_set):
             raise SystemExit("the simulations of the training set disagree on the scene: %s has %s, others %s"
                              % (s, sol_amd.karman.describe_scene(r), sol_amd.karman.describe_scene(rec_set)))
@@ -104,6 +107,10 @@ def main(argv=None):
         raise SystemExit("the simulations of the training set disagree on the diffusion substeps: %s" % sorted(set(sub_set)))
     nsub = agreed_substeps(sub_set[0] if sub_set else None, substeps_from_args(params), "the training set")
     log.info("diffusion substeps: %d" % nsub)
+    if len(set(adv_set)) > 1:
+        raise SystemExit("the simulations of the training set disagree on the advection scheme: %s" % sorted(set(adv_set)))
+    advection = agreed_advection(dict(adv_set[0]) if adv_set else None, advection_from_args(params), "the training set")
+    log.info("advection: %s" % (advection,))
     if params["pretf"]:
         # karman_train.py:351-355: the supervised model's own input / output normalisation travels in stats.pickle next to it
         with open(os.path.dirname(params["pretf"]) + "/stats.pickle", "rb") as f:
@@ -143,6 +150,8 @@ def main(argv=None):
     dataset.dataStats.setdefault("scene", rec)
     dataset.dataStats.setdefault("buoyancy", buoyancy)
     dataset.dataStats.setdefault("diffusion_substeps", nsub)
+    dataset.dataStats.setdefault("advection", advection["advection"])
+    dataset.dataStats.setdefault("correction_strength", advection["correction_strength"])
     if params["resume"] < 1:
         if rank == 0:
             with open(params["tf"] + "/dataStats.pickle", "wb") as f:
@@ -156,7 +165,7 @@ def main(argv=None):
                                  in_std_v=dataset.dataStats["in.std"][1] if "in.std" in dataset.dataStats else None,
                                  out_std_v=dataset.dataStats["out.std"] if "out.std" in dataset.dataStats else None,
                                  pressure_solver=params["pressure_solver"], any_width=params["any_width"], buoyancy=buoyancy,
-                                 diffusion_substeps=nsub, **flow_kwargs(rec))
+                                 diffusion_substeps=nsub, **advection, **flow_kwargs(rec))
     # persistent device buffers: the captured hipGraph keeps their addresses, new data is copied in
     f32 = lambda shape: torch.empty(shape, dtype=torch.float32, device=dev)
     d0, vy0, vx0, re = f32((Bl, Y, X)), f32((Bl, Y + 1, X)), f32((Bl, Y, X + 1)), f32((Bl,))

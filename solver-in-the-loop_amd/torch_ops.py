@@ -8,6 +8,7 @@ dispatcher (torch.ops.sol.karman_step, .conv5x5, .burgers_step, .adam_tf_step; .
 density output, over sol_karman_density_bwd; .karman_step_re = karman_step differentiable with respect to re as well, over the _re
 adjoints; .karman_step_buoy = the large-grid step with the buoyancy force (fy, fx): the density pushes the velocity and is always in the
 graph; .karman_step_sub = karman_step with nsub explicit diffusion substeps, composing with the density, re and buoyancy modes;
+.karman_step_adv = the large-grid step with the advection named per call (1: MacCormack with correction strength s), composing with all of them;
 .karman3d_step_buoy = the same for the 3-D step, force (fy, fx, fz); .karman3d_step_sub = the 3-D step with nsub explicit diffusion
 substeps, composing with its density, re and buoyancy modes).  Scene constants (masks, solver blobs, the cfg struct) are not tensors: they are registered once with register_scene() and
 referred to by an integer handle."""
@@ -23,6 +24,7 @@ _LIB.define("karman_step_dens(Tensor d, Tensor vy, Tensor vx, Tensor re, int sce
 _LIB.define("karman_step_re(Tensor d, Tensor vy, Tensor vx, Tensor re, int scene, bool density=False) -> (Tensor, Tensor, Tensor)")
 _LIB.define("karman_step_buoy(Tensor d, Tensor vy, Tensor vx, Tensor re, int scene, float fy, float fx, bool re_grad=False) -> (Tensor, Tensor, Tensor)")
 _LIB.define("karman_step_sub(Tensor d, Tensor vy, Tensor vx, Tensor re, int scene, int nsub, bool density=False, bool re_grad=False, float fy=0.0, float fx=0.0) -> (Tensor, Tensor, Tensor)")
+_LIB.define("karman_step_adv(Tensor d, Tensor vy, Tensor vx, Tensor re, int scene, int advection, float s=1.0, int nsub=1, bool density=False, bool re_grad=False, float fy=0.0, float fx=0.0) -> (Tensor, Tensor, Tensor)")
 _LIB.define("karman_density_bwd(Tensor d, Tensor svy, Tensor svx, Tensor re, Tensor gd, int scene) -> (Tensor, Tensor, Tensor)")
 _LIB.define("karman_step_bwd(Tensor svy, Tensor svx, Tensor re, Tensor gvy, Tensor gvx, int scene) -> (Tensor, Tensor)")
 _LIB.define("karman_step_fwd_saved(Tensor d, Tensor vy, Tensor vx, Tensor re, int scene) -> (Tensor, Tensor, Tensor, Tensor, Tensor)")
@@ -143,6 +145,39 @@ def _karman_sub_fn(d, vy, vx, re, scene, nsub, density=False, re_grad=False, fy=
 
 _LIB.impl("karman_step_sub", _karman_sub, "CUDA")
 _LIB.impl("karman_step_sub", _karman_sub_fn, "AutogradCUDA")
+
+
+# karman_step_adv: the step with the advection named per call (0 semi-Lagrangian, 1 MacCormack with correction strength s; ops.KarmanStepFn's
+# adv mode, large grids), composing with every other mode: nsub diffusion substeps, density, re_grad, a buoyancy force (fy, fx)
+def _karman_adv_args(scene, advection, s, nsub, fy, fx, who="torch.ops.sol.karman_step_adv"):
+    if advection not in (0, 1):
+        raise ValueError("%s: advection must be 0 (semi_lagrangian) or 1 (mac_cormack), got %r" % (who, advection))
+    adv = ops.advection_arg(ops.ADVECTIONS[advection], s, who + ": advection")
+    cfg, masks, n, f = _karman_sub_args(scene, nsub, fy, fx)
+    if adv is not None:
+        ops._require_large_for_advection(masks, cfg.Y, cfg.X, who)
+    kw = {} if adv is None else {"advection": "mac_cormack", "correction_strength": adv}
+    return cfg, masks, n, f, adv, kw
+
+
+def _karman_adv(d, vy, vx, re, scene, advection, s=1.0, nsub=1, density=False, re_grad=False, fy=0.0, fx=0.0):
+    cfg, masks, n, f, adv, kw = _karman_adv_args(scene, advection, s, nsub, fy, fx)
+    with torch.no_grad():
+        if masks.large:
+            return ops.karman_step_large(d, vy, vx, re, cfg, masks, buoyancy=f, diffusion_substeps=n, **kw)
+        return ops.karman_step(d, vy, vx, re, cfg, masks, diffusion_substeps=n)
+
+
+def _karman_adv_fn(d, vy, vx, re, scene, advection, s=1.0, nsub=1, density=False, re_grad=False, fy=0.0, fx=0.0):
+    cfg, masks, n, f, adv, kw = _karman_adv_args(scene, advection, s, nsub, fy, fx)
+    want_re = bool(re_grad) and torch.is_grad_enabled() and re.requires_grad
+    if want_re:
+        ops._require_staged(cfg, "re_grad")
+    return ops.KarmanStepFn.apply(d, vy, vx, re, cfg, masks, None, None, bool(density), want_re, f, n, adv)
+
+
+_LIB.impl("karman_step_adv", _karman_adv, "CUDA")
+_LIB.impl("karman_step_adv", _karman_adv_fn, "AutogradCUDA")
 
 # conv / burgers: the autograd.Functions of ops.py already are the hand-written forward + backward pairs
 _LIB.impl("conv5x5", lambda x, w, b, residual, lrelu, slope: ops.Conv5x5Fn.apply(x, w, b, residual, lrelu, slope), "AutogradCUDA")

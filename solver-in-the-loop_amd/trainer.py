@@ -75,6 +75,16 @@ def _refuse_buoyancy(who, buoyancy):
     return None
 
 
+def _refuse_advection(who, advection, correction_strength=1.0):
+    """SolTrainer, GraphTrainer and SolRollout run the fused one-workgroup solver kernels, which advect semi-Lagrangian: "mac_cormack" is
+    refused at construction (LargeGridTrainer / LargeGridRollout take it on a large grid).  -> None"""
+    if ops.advection_arg(advection, correction_strength, "%s: advection" % who) is not None:
+        raise ValueError("%s: advection=%r -- the mac_cormack advection is built on the multi-launch (large-grid) solver step only; this "
+                         "class runs the fused one-workgroup kernels.  Use it on a large grid (LargeGridTrainer / LargeGridRollout)"
+                         % (who, advection))
+    return None
+
+
 def _refuse_substeps(who, diffusion_substeps, Y, X):
     """SolTrainer, GraphTrainer and SolRollout run a solver step that lives inside the library's own schedule (the fused one-workgroup
     kernels, the C-side graph): there is no place for the pre-diffusion launch.  diffusion_substeps > 1 is refused at construction
@@ -150,7 +160,8 @@ class SolTrainer(_AdamDP):
     def __init__(self, net, masks, B, Y, X, msteps, dx, std_v, std_re, dt=1.0, res=None,
                  clip_grad=False, beta1=0.9, beta2=0.999, eps=1e-8, group=None, use_graph=True,
                  cg_rtol=1e-6, cg_atol=1e-9, cg_max_iter=2000, grad_pad="replicate", inflow_order="after",
-                 conv_precision="split", comm=None, in_std_v=None, out_std_v=None, buoyancy=None, diffusion_substeps=1):
+                 conv_precision="split", comm=None, in_std_v=None, out_std_v=None, buoyancy=None, diffusion_substeps=1,
+                 advection="semi_lagrangian", correction_strength=1.0):
         """conv_precision: arithmetic of the 32-channel convolutions (library option `conv_precision`):
         "split" (default) fp32-equivalent fp16x3 / bf16x6 operand splits on the 16-bit matrix pipe, "bf16x6",
         or "fp32" = strict fp32 MFMA.  The option is process wide in the library; every call of this trainer sets
@@ -160,6 +171,7 @@ class SolTrainer(_AdamDP):
         _refuse_large_grid("SolTrainer", Y, X)
         _refuse_buoyancy("SolTrainer", buoyancy)
         _refuse_substeps("SolTrainer", diffusion_substeps, Y, X)
+        _refuse_advection("SolTrainer", advection, correction_strength)
         _lib.require_gpu()
         self.lib = _lib.load()
         self.conv_precision = _conv_precision_code(conv_precision)
@@ -267,8 +279,9 @@ class SolRollout:
     """No-grad roll-out of solver step + CNN correction (karman_apply.py:138-158)."""
 
     def __init__(self, net, masks, B, Y, X, dx, std_v, std_re, dt=1.0, res=None, in_std_v=None, out_std_v=None,
-                 conv_precision="split", diffusion_substeps=1, **solver):
+                 conv_precision="split", diffusion_substeps=1, advection="semi_lagrangian", correction_strength=1.0, **solver):
         _refuse_substeps("SolRollout", diffusion_substeps, Y, X)
+        _refuse_advection("SolRollout", advection, correction_strength)
         _lib.require_gpu()
         self.lib = _lib.load()
         self.conv_precision = _conv_precision_code(conv_precision)
@@ -309,14 +322,17 @@ class LargeGridRollout:
 
     def __init__(self, net, masks, B, Y, X, dx, std_v, std_re, dt=1.0, res=None, in_std_v=None, out_std_v=None,
                  conv_precision="split", use_graph=True, cg_warm_start=False, any_width=False, buoyancy=None, diffusion_substeps=1,
-                 **solver):
+                 advection="semi_lagrangian", correction_strength=1.0, **solver):
         """any_width=True: X need not be a multiple of 64 -- the network runs in pitched rows (NetSchedule2D(any_width=True): the features
         are copied into zero-padded rows of 64 * ceil(X / 64) pixels and the output is cropped; the solver step and the correction stay
         dense).  buoyancy=(fy, fx) (ops.buoyancy_force): the density pushes the velocity -- the solver step is the buoyant one
         (sol_karman_step_fwd_large_buoy: one launch more, captured with the rest; direct and CG scenes, warm start included).
         diffusion_substeps=n: n explicit diffusion substeps per solver step (ops.karman_step_large(diffusion_substeps=n): the
-        pre-diffusion launches are part of the captured step)."""
+        pre-diffusion launches are part of the captured step).  advection="mac_cormack", correction_strength=s: the solver step advects
+        by the MacCormack scheme (sol_karman_step_fwd_large_adv; captured with the rest)."""
         self.diffusion_substeps = ops.diffusion_substeps_arg(diffusion_substeps, "LargeGridRollout: diffusion_substeps")
+        adv = ops.advection_arg(advection, correction_strength, "LargeGridRollout: advection")
+        self.advection = {} if adv is None else {"advection": "mac_cormack", "correction_strength": adv}
         f = ops.buoyancy_force(buoyancy)
         self.buoyancy = f if ops._buoyant(f) else None
         if not ops.beyond_one_workgroup(Y, X):
@@ -352,7 +368,7 @@ class LargeGridRollout:
         self._feat = z(B, Y, X, 4)
         self._cor = (z(B, Y + 1, X), z(B, Y, X + 1))
         self.p_guess = z(B, Y, X) if self.cg_warm_start else None
-        nbytes = ops.large_workspace_bytes(self.cfg, masks)
+        nbytes = ops.large_adv_workspace_bytes(self.cfg, masks) if self.advection else ops.large_workspace_bytes(self.cfg, masks)
         self._ws = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=dev)
         self.solve_info = {}
         self._info = []
@@ -365,7 +381,8 @@ class LargeGridRollout:
     def _step(self):
         info = {}
         ops.karman_step_large(*self._a, self._re, self.cfg, self.masks, self._ws, info, feat=self._feat, feat_scale=self._fs3,
-                              p_guess=self.p_guess, out=self._b, buoyancy=self.buoyancy, diffusion_substeps=self.diffusion_substeps)
+                              p_guess=self.p_guess, out=self._b, buoyancy=self.buoyancy, diffusion_substeps=self.diffusion_substeps,
+                              **self.advection)
         out, _ = self._sched.forward(self._feat)
         ops.karman_correct(out, self._b[1], self._b[2], self._so, self._cor)
         _lib.dcopy_(self._flat[0], self._flat[1])
@@ -417,6 +434,9 @@ def make_rollout(net, masks, B, Y, X, dx, std_v, std_re, **kw):
         raise ValueError("make_rollout: the buoyancy force is built on the multi-launch (large-grid) solver step only; a %dx%d grid runs "
                          "the one-workgroup roll-out (SolRollout), which has no buoyancy term" % (Y, X))
     kw["diffusion_substeps"] = _refuse_substeps("make_rollout", kw.get("diffusion_substeps", 1), Y, X)
+    if ops.advection_arg(kw.pop("advection", "semi_lagrangian"), kw.pop("correction_strength", 1.0), "make_rollout: advection") is not None:
+        raise ValueError("make_rollout: the mac_cormack advection is built on the multi-launch (large-grid) solver step only; a %dx%d grid "
+                         "runs the one-workgroup roll-out (SolRollout), which advects semi-Lagrangian" % (Y, X))
     return SolRollout(net, masks, B, Y, X, dx, std_v, std_re, **kw)
 
 
@@ -436,7 +456,7 @@ class GraphTrainer(_AdamDP):
                  group=None, use_graph=True, comm=None, in_std_v=None, out_std_v=None, pressure_solver=None,
                  dx=None, dt=1.0, masks=None, cg_rtol=1e-6, cg_atol=1e-9, cg_max_iter=2000, grad_pad="replicate",
                  inflow_order="after", conv_precision="split", schedule="manual", obstacles=None, active=None,
-                 buoyancy=None, diffusion_substeps=1):
+                 buoyancy=None, diffusion_substeps=1, advection="semi_lagrangian", correction_strength=1.0):
         """dx: cell size (default 100 / X, the reference's `--len 100`); the domain is box[0:Y*dx, 0:X*dx] as the scripts
         build it (karman_train.py:363: box[0:len*2, 0:len]).  obstacles / active: the scene of KarmanFlow (default: the reference's
         sphere).  masks: optional SceneMasks of the caller -- its boundary arrays are used; its scene must be the one KarmanFlow
@@ -450,6 +470,7 @@ class GraphTrainer(_AdamDP):
         self._check_grid(Y, X)
         self.buoyancy = self._check_buoyancy(buoyancy)
         self.diffusion_substeps = self._check_substeps(diffusion_substeps, Y, X)
+        self.advection = self._check_advection(advection, correction_strength)      # {} or the two keywords of the large-grid solver pair
         from . import fluid, karman
         _lib.require_gpu()
         self.lib = _lib.load()
@@ -497,6 +518,11 @@ class GraphTrainer(_AdamDP):
     @staticmethod
     def _check_substeps(diffusion_substeps, Y, X):
         return _refuse_substeps("GraphTrainer", diffusion_substeps, Y, X)
+
+    @staticmethod
+    def _check_advection(advection, correction_strength):
+        _refuse_advection("GraphTrainer", advection, correction_strength)
+        return {}
 
     def _unrolled(self):
         if self.schedule == "manual":
@@ -661,7 +687,10 @@ class LargeGridTrainer(GraphTrainer):
         reset at the head of every run, so a replayed graph is self-contained.
         diffusion_substeps=n (keyword): n explicit diffusion substeps per solver step -- _solver_fwd / _solver_bwd pass it to
         ops.karman_step_saved and ops.karman_step_large_bwd(_buoy): the pre-diffusion launches on the input velocity and on the adjoint's
-        result are part of the (captured) schedule."""
+        result are part of the (captured) schedule.
+        advection="mac_cormack", correction_strength=s (keywords): the solver pair advects by the MacCormack scheme --
+        ops.karman_step_saved and ops.karman_step_large_bwd(_buoy) with the same keywords (the _adv entry points; their workspaces are
+        sized here, so a captured step allocates nothing)."""
         if any_width and kw.get("schedule", "manual") == "autograd":
             raise ValueError("LargeGridTrainer: any_width=True runs the hand-written schedule only; schedule='autograd' (the composition "
                              "over ops.conv5x5) takes no pitched rows")
@@ -689,15 +718,22 @@ class LargeGridTrainer(GraphTrainer):
     def _check_substeps(diffusion_substeps, Y, X):
         return ops.diffusion_substeps_arg(diffusion_substeps, "LargeGridTrainer: diffusion_substeps")
 
+    @staticmethod
+    def _check_advection(advection, correction_strength):
+        adv = ops.advection_arg(advection, correction_strength, "LargeGridTrainer: advection")
+        return {} if adv is None else {"advection": "mac_cormack", "correction_strength": adv}
+
     def _schedule_setup(self):
         super()._schedule_setup()
         cfg, mk, dev = self._kcfg, self._mk, self.device
         self._d_in, self._g_d = [], None                    # buoyant mode: the steps' input densities; the carried density gradient
+        mc = bool(self.advection)
         if self.buoyancy is not None:
-            self._ws_bwd_d = torch.empty((int(ops.density_bwd_workspace_bytes(cfg)) + 3) // 4, dtype=torch.float32, device=dev)
+            nd = ops.density_bwd_adv_workspace_bytes(cfg) if mc else ops.density_bwd_workspace_bytes(cfg)
+            self._ws_bwd_d = torch.empty((int(nd) + 3) // 4, dtype=torch.float32, device=dev)
         ws = lambda n: torch.empty((int(n) + 3) // 4, dtype=torch.float32, device=dev)
-        self._ws_fwd = ws(ops.large_workspace_bytes(cfg, mk))
-        self._ws_bwd = ws(ops.large_bwd_workspace_bytes(cfg, mk))
+        self._ws_fwd = ws(ops.large_adv_workspace_bytes(cfg, mk, True) if mc else ops.large_workspace_bytes(cfg, mk))
+        self._ws_bwd = ws(ops.large_bwd_adv_workspace_bytes(cfg, mk) if mc else ops.large_bwd_workspace_bytes(cfg, mk))
         self._zplane = torch.zeros(self.B, self.Y, self.X, dtype=torch.float32, device=dev)      # the fourth (padding) input channel
         self.pressure_solver_used = mk.pressure_solver
 
@@ -710,7 +746,7 @@ class LargeGridTrainer(GraphTrainer):
         if self.buoyancy is not None:
             self._d_in.append(d)
         (d2, vy2, vx2), svy, svx = ops.karman_step_large_saved(d, vy, vx, re, self._kcfg, self._mk, self._ws_fwd, info, self.buoyancy,
-                                                                         self.diffusion_substeps)
+                                                                         self.diffusion_substeps, **self.advection)
         self._cg_fwd.append(info)
         # to_feature / in_std (karman_train.py:77-86, 413-416), padded to the four channels the first layer's kernels read
         feat = torch.stack([vy2[:, :Y] * fs[0], vx2[:, :, :X] * fs[1], self._re_plane, self._zplane], dim=-1)
@@ -727,10 +763,10 @@ class LargeGridTrainer(GraphTrainer):
             d_in = self._d_in.pop()
             self._g_d, oy, ox = ops.karman_step_large_bwd_buoy(d_in, svy, svx, re, G[0], G[1], self._g_d, self._kcfg, self._mk, self.buoyancy,
                                                                workspace=self._ws_bwd, info=info, density_workspace=self._ws_bwd_d,
-                                                               diffusion_substeps=self.diffusion_substeps)
+                                                               diffusion_substeps=self.diffusion_substeps, **self.advection)
             return oy, ox
         return ops.karman_step_large_bwd(svy, svx, re, G[0], G[1], self._kcfg, self._mk, workspace=self._ws_bwd, info=info,
-                                         diffusion_substeps=self.diffusion_substeps)
+                                         diffusion_substeps=self.diffusion_substeps, **self.advection)
 
     def _fwd_bwd(self, *a, **kw):
         loss = super()._fwd_bwd(*a, **kw)
@@ -753,6 +789,7 @@ def make_trainer(net, masks, B, Y, X, msteps, dx, std_v, std_re, **kw):
         for k in ("obstacles", "active", "pressure_solver", "any_width"):
             kw.pop(k, None)
         kw["diffusion_substeps"] = _refuse_substeps("make_trainer", kw.get("diffusion_substeps", 1), Y, X)
+        _refuse_advection("make_trainer", kw.get("advection", "semi_lagrangian"), kw.get("correction_strength", 1.0))
         return SolTrainer(net, masks, B, Y, X, msteps, dx, std_v, std_re, **kw)
     kw.pop("any_width", None)           # (the one-workgroup grids: the keyword belongs to LargeGridTrainer)
     return GraphTrainer(net, B, Y, X, msteps, std_v, std_re, dx=dx, masks=masks, **kw)     # unknown keywords raise TypeError
