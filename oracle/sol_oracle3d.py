@@ -64,7 +64,9 @@ class Karman3DGeometry:
 
     def __post_init__(self):
         Y, X, Z = self.Y, self.X, self.Z
-        assert Y == 2 * X and Z == X, "karman-3d domain is box[0:2*len, 0:len, 0:len] with res (2*res, res, res)"
+        # any grid: dx = length / X as in Scene3D, the domain is box[0:Y*dx, 0:X*dx, 0:Z*dx] and the inflow box and the obstacle keep
+        # their physical definitions; res (2*res, res, res) is the scene's own box[0:2*len, 0:len, 0:len]
+        assert min(Y, X, Z) >= 1
         self.dx = self.length / X
         c = [(np.arange(n) + 0.5) * self.dx for n in (Y, X, Z)]
         YC, XC, ZC = np.meshgrid(*c, indexing="ij")
