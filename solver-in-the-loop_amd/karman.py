@@ -118,18 +118,15 @@ class KarmanFlow:
         # by the MacCormack scheme with the revert-to-semi-Lagrangian limiter (include/sol_hip.h, "MACCORMACK ADVECTION"), which keeps what
         # the semi-Lagrangian step smears; large grids only (step() raises SolError on a grid the one-workgroup kernels serve); composes
         # with density_grad, re_grad, buoyancy and diffusion_substeps.  The default issues the launches it always did.
-        self._adv = ops.advection_arg(advection, correction_strength, "KarmanFlow: advection")
-        self._advection = dict(advection=advection, correction_strength=float(correction_strength))
         # diffusion_substeps=n (PhiFlow's diffuse(field, amount, substeps)): the velocity is diffused by n explicit substeps of alpha / n,
         # alpha = dt res^2 / Re, the boundary blend after the last one.  The single stencil is stable only while alpha <= 1/4
-        # (ops.min_diffusion_substeps gives the n a run needs); grids with Y, X >= 16; composes with density_grad, re_grad and buoyancy.
-        # The default 1 issues the launches it always did.
-        self._nsub = ops.diffusion_substeps_arg(diffusion_substeps, "KarmanFlow: diffusion_substeps")
+        # (ops.min_diffusion_substeps gives the n a run needs); grids with Y, X >= 16.
         # buoyancy=(fy, fx), a force per unit density, or PhiFlow's spelling buoyancy_factor=beta with gravity=(gy, gx): F = -gravity * beta
-        # (ops.buoyancy_force).  The step's output density pushes the velocity; large grids only (step() raises SolError on a grid the
-        # one-workgroup kernels serve).  The default is off: the density is a passive tracer and every launch is what it was.
-        f = ops.buoyancy_force(buoyancy, buoyancy_factor, gravity)
-        self._buoyancy = f if ops._buoyant(f) else None
+        # (ops.buoyancy_force).  The step's output density pushes the velocity; large grids only, like mac_cormack.
+        # All three compose with each other and with density_grad and re_grad (ops.StepPhysics, built and validated once, here); the
+        # defaults issue the launches they always did.
+        self._physics = ops.StepPhysics.of(buoyancy, buoyancy_factor, gravity, diffusion_substeps, advection, correction_strength, "KarmanFlow")
+        self._buoyancy, self._nsub, self._adv = self._physics
         # re_grad=True (opt-in): a tensor `re` given to step() that requires a gradient receives one (ops.KarmanStepFn's re mode: fit the
         # viscosity to observed frames, a loss term on Re); the default treats re as data
         self._re_grad = bool(re_grad)
@@ -239,24 +236,19 @@ class KarmanFlow:
         vx = smoke.velocity.data[1].data.reshape(B, Y, X + 1)
         info = {}
         self.pressure_solver_used = masks.pressure_solver        # "direct", "cg" (SceneMasks' choice for this grid and scene) or "direct_scattered"
-        if self._buoyancy is not None and not masks.large:
-            raise _lib.SolError("KarmanFlow: the buoyancy force is built on the multi-launch (large-grid) step only; a %dx%d grid runs the "
-                                "fused one-workgroup kernels (not ops.beyond_one_workgroup), which have no buoyancy term" % (Y, X))
-        if self._adv is not None:
-            ops._require_large_for_advection(masks, Y, X, "KarmanFlow")
+        self._physics.require(cfg, masks, "KarmanFlow")
         if masks.large:
             # beyond the one-workgroup kernels (data generation at 256 x 128, karman.py:98-159): the multi-launch path, direct solve
             # where the scene's blob builds, else the preconditioned CG (solve_info: iterations / converged per simulation, and
             # iterations_bwd / converged_bwd after backward()); differentiable like the small path (ops.KarmanStepFn)
-            n = ops.large_workspace_bytes(cfg, masks) if self._adv is None else ops.large_adv_workspace_bytes(cfg, masks)
+            n = ops.large_workspace_bytes(cfg, masks, self._physics)
             if getattr(self, "_large_ws", None) is None or self._large_ws[0] != (B, Y, X, str(dev)) or self._large_ws[1].numel() * 4 < n:
                 self._large_ws = ((B, Y, X, str(dev)), torch.empty((n + 3) // 4, dtype=torch.float32, device=dev))
             d2, vy2, vx2 = ops.karman_step_large(d, vy, vx, re_t, cfg, masks, self._large_ws[1], info, density_grad=self._density_grad,
-                                                 re_grad=self._re_grad, buoyancy=self._buoyancy, diffusion_substeps=self._nsub,
-                                                 **({} if self._adv is None else self._advection))
+                                                 re_grad=self._re_grad, physics=self._physics)
         else:
             d2, vy2, vx2 = ops.karman_step(d, vy, vx, re_t, cfg, masks, info, density_grad=self._density_grad, re_grad=self._re_grad,
-                                           diffusion_substeps=self._nsub)
+                                           physics=self._physics)
         self.solve_info = info
         return smoke.copied_with(density=d2.reshape(B, Y, X, 1),
                                  velocity=StaggeredGrid([vy2.reshape(B, Y + 1, X, 1), vx2.reshape(B, Y, X + 1, 1)],

@@ -5,7 +5,9 @@ These are the composable building blocks behind the reference-shaped Python surf
 Every function here calls libsol_hip.so; there is no CPU implementation.
 """
 import ctypes as C
+import functools
 import os
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -121,34 +123,29 @@ class SceneMasks:
         return self.box, self.box_header
 
 
-def large_workspace_bytes(cfg, masks):
-    """Device scratch of the large-grid step for the scene's solver (direct, scattered direct or CG)."""
+def _mac(physics):
+    """1 for a StepPhysics with advection="mac_cormack", else 0 (None: the plain step): the `advection` argument of the size functions"""
+    return int(physics is not None and physics.adv is not None)
+
+
+def large_workspace_bytes(cfg, masks, physics=None, saved=False):
+    """Device scratch of the large-grid step for the scene's solver (direct, scattered direct or CG) under `physics` (a StepPhysics;
+    None: the plain step); saved: of karman_step_saved, the training form.  The _adv size functions serve every mode: with advection = 0
+    they return the plain functions' bytes (tests/test_workspace_bytes_cpu.py)."""
     lib = _lib.load()
-    if masks.direct is None:
-        return lib.sol_karman_step_large_cg_workspace_bytes(C.byref(cfg))
-    return lib.sol_karman_step_large_workspace_bytes_for(C.byref(cfg), _hdr(masks.direct_header))
+    fn = lib.sol_karman_step_fwd_large_saved_adv_workspace_bytes_for if saved and _mac(physics) else lib.sol_karman_step_fwd_large_adv_workspace_bytes_for
+    return fn(C.byref(cfg), _hdr(masks.direct_header), _mac(physics))
 
 
-def large_adv_workspace_bytes(cfg, masks, saved=False):
-    """Device scratch of the large-grid step with advection="mac_cormack" (the _adv entry points; saved: the training form)."""
-    lib = _lib.load()
-    fn = lib.sol_karman_step_fwd_large_saved_adv_workspace_bytes_for if saved else lib.sol_karman_step_fwd_large_adv_workspace_bytes_for
-    return fn(C.byref(cfg), _hdr(masks.direct_header), 1)
+def large_bwd_workspace_bytes(cfg, masks, physics=None, re=False):
+    """Device scratch of the large-grid velocity adjoint (sol_karman_step_bwd_large and its siblings) for the scene's solver under
+    `physics`; re: with the gradient with respect to the Reynolds number (the _re entry points)."""
+    return _lib.load().sol_karman_step_bwd_large_adv_workspace_bytes_for(C.byref(cfg), _hdr(masks.direct_header), int(re), _mac(physics))
 
 
-def large_bwd_adv_workspace_bytes(cfg, masks, re=False):
-    """Device scratch of the large-grid adjoint under advection="mac_cormack" (sol_karman_step_bwd_large_adv / _adv_re)."""
-    return _lib.load().sol_karman_step_bwd_large_adv_workspace_bytes_for(C.byref(cfg), _hdr(masks.direct_header), int(re), 1)
-
-
-def density_bwd_adv_workspace_bytes(cfg, re=False):
-    """Device scratch of the density adjoint under advection="mac_cormack" (sol_karman_density_bwd_adv / _adv_re)."""
-    return _lib.load().sol_karman_density_bwd_adv_workspace_bytes(C.byref(cfg), int(re), 1)
-
-
-def large_bwd_workspace_bytes(cfg, masks):
-    """Device scratch of the large-grid adjoint (sol_karman_step_bwd_large) for the scene's solver."""
-    return _lib.load().sol_karman_step_bwd_large_workspace_bytes_for(C.byref(cfg), _hdr(masks.direct_header))
+def density_bwd_workspace_bytes(cfg, physics=None, re=False):
+    """Device scratch of the density adjoint (sol_karman_density_bwd and its siblings) under `physics`; re: the _re entry points."""
+    return _lib.load().sol_karman_density_bwd_adv_workspace_bytes(C.byref(cfg), int(re), _mac(physics))
 
 
 def _hdr(a):
@@ -205,12 +202,6 @@ def _buoyant(buoyancy):
     return buoyancy is not None and (buoyancy[0] != 0.0 or buoyancy[1] != 0.0)
 
 
-def _require_large_for_buoyancy(masks, Y, X, who):
-    if not masks.large:
-        raise SolError("%s: the buoyancy force is built on the multi-launch (large-grid) step only; a %dx%d grid runs the fused "
-                       "one-workgroup kernels (not ops.beyond_one_workgroup), which have no buoyancy term" % (who, Y, X))
-
-
 # --------------------------------------------------------------------------------------
 # advection scheme (include/sol_hip.h, "MACCORMACK ADVECTION on the large-grid step"; csrc/karman_maccormack.hip)
 # --------------------------------------------------------------------------------------
@@ -229,12 +220,6 @@ def advection_arg(advection="semi_lagrangian", correction_strength=1.0, who="adv
     if not (np.isfinite(s) and 0.0 <= s <= 1.0):
         raise ValueError("correction_strength must be finite and lie in [0, 1] (got %r)" % (correction_strength,))
     return s if advection == "mac_cormack" else None
-
-
-def _require_large_for_advection(masks, Y, X, who):
-    if not masks.large:
-        raise SolError("%s: the mac_cormack advection is built on the multi-launch (large-grid) step only; a %dx%d grid runs the fused "
-                       "one-workgroup kernels (not ops.beyond_one_workgroup), which advect semi-Lagrangian" % (who, Y, X))
 
 
 def _adv_grid(cfg, who):
@@ -335,6 +320,82 @@ def _require_sub_grid(cfg, who):
         raise SolError("%s: diffusion substeps (sol_karman_diffuse_sub) take grids with Y, X >= 16; this one is %dx%d" % (who, cfg.Y, cfg.X))
 
 
+class StepPhysics(NamedTuple):
+    """The physics of one 2-D step beyond the plain one, as every internal call carries it.  The default is the plain step: the launches
+    and the bits of a call without any of the keywords.
+    buoyancy = (fy, fx), a force per unit density (large grids only), or None: the step's output density pushes the velocity
+    (sol_karman_step_fwd_large_buoy / _saved_buoy: one launch more).  With a force that moves the velocity the density is part of the
+    dynamics: a differentiable step keeps it in the graph whatever density_grad says, and a velocity-only loss yields a density gradient.
+    nsub = n >= 1, the diffusion substeps (grids with Y, X >= 16): the velocity is diffused by n explicit substeps of alpha / n, the
+    boundary blend after the last one -- karman_diffuse_sub, then the step's launches on diffusion_sub_cfg(cfg, n).
+    adv = the correction strength s in [0, 1] of advection="mac_cormack" (large grids only), or None for "semi_lagrangian": velocity and
+    density are advected by the MacCormack scheme with the revert-to-semi-Lagrangian limiter (the _adv entry points; the adjoint freezes
+    the limiter's decisions).
+    The three compose with each other, with density_grad and re_grad, and with the no-grad extras of karman_step_large."""
+    buoyancy: Optional[tuple] = None
+    nsub: int = 1
+    adv: Optional[float] = None
+
+    @classmethod
+    def of(cls, buoyancy=None, buoyancy_factor=None, gravity=(-9.81, 0.0), diffusion_substeps=1, advection="semi_lagrangian",
+           correction_strength=1.0, who="the step", keep_zero_force=False):
+        """From the user-facing keywords, validated (ValueError): diffusion_substeps_arg, advection_arg (s is checked under either
+        scheme), buoyancy_force.  A force of (0, 0) becomes None, the plain step; keep_zero_force (the direct calls karman_step_large,
+        karman_step_saved, karman_step_large_bwd_buoy) keeps it as given: their buoyant entry points take it and issue the plain launches."""
+        n = diffusion_substeps_arg(diffusion_substeps, "%s: diffusion_substeps" % who)
+        adv = advection_arg(advection, correction_strength, "%s: advection" % who)
+        f = buoyancy_force(buoyancy, buoyancy_factor, gravity)
+        return cls(f if keep_zero_force or _buoyant(f) else None, n, adv)
+
+    def moving(self):
+        """self, a kept force of (0, 0) normalised to None: what a differentiable step runs on"""
+        return self if self.buoyancy is None or _buoyant(self.buoyancy) else self._replace(buoyancy=None)
+
+    def require(self, cfg, masks, who):
+        """The grid checks (SolError), before any device call: substeps take Y, X >= 16; the buoyancy force and the mac_cormack advection
+        are built on the large-grid step only (masks.large)."""
+        if self.nsub > 1:
+            _require_sub_grid(cfg, who)
+        if self.buoyancy is not None and not masks.large:
+            raise SolError("%s: the buoyancy force is built on the multi-launch (large-grid) step only; a %dx%d grid runs the fused "
+                           "one-workgroup kernels (not ops.beyond_one_workgroup), which have no buoyancy term" % (who, cfg.Y, cfg.X))
+        if self.adv is not None and not masks.large:
+            raise SolError("%s: the mac_cormack advection is built on the multi-launch (large-grid) step only; a %dx%d grid runs the fused "
+                           "one-workgroup kernels (not ops.beyond_one_workgroup), which advect semi-Lagrangian" % (who, cfg.Y, cfg.X))
+
+    @property
+    def mode(self):
+        """Which family of entry points runs the step and its velocity adjoint: "_adv", "_buoy" or "" (plain)"""
+        return "_adv" if self.adv is not None else "_buoy" if self.buoyancy is not None else ""
+
+    @property
+    def force_tail(self):
+        """The arguments a _buoy or _adv entry point ends with: the force ((0, 0) without one), then advection = 1 and s"""
+        f = (0.0, 0.0) if self.buoyancy is None else (float(self.buoyancy[0]), float(self.buoyancy[1]))
+        return f if self.adv is None else f + (1, self.adv)
+
+    @property
+    def advection_kw(self):
+        """{} or the two advection keywords of the public calls"""
+        return {} if self.adv is None else {"advection": "mac_cormack", "correction_strength": self.adv}
+
+
+@functools.lru_cache(maxsize=64, typed=True)
+def _physics_of(who, buoyancy, diffusion_substeps, advection, correction_strength, keep_zero_force):
+    return StepPhysics.of(buoyancy, None, None, diffusion_substeps, advection, correction_strength, who, keep_zero_force)
+
+
+def _physics(physics, who, buoyancy=None, diffusion_substeps=1, advection="semi_lagrangian", correction_strength=1.0, keep_zero_force=False):
+    """The StepPhysics of a public call: `physics` where the caller built one (it then replaces the keywords), else from the keywords --
+    built and validated once per distinct set of them (a loop of steps passes the same ones at every call), not per call"""
+    if physics is not None:
+        return physics
+    try:
+        return _physics_of(who, buoyancy, diffusion_substeps, advection, correction_strength, keep_zero_force)
+    except TypeError:               # an unhashable spelling (a force given as a list): built per call
+        return _physics_of.__wrapped__(who, buoyancy, diffusion_substeps, advection, correction_strength, keep_zero_force)
+
+
 def diffuse_sub_max():
     """S_MAX: the most substeps one launch of sol_karman_diffuse_sub runs"""
     return int(_lib.load().sol_karman_diffuse_sub_max())
@@ -385,44 +446,58 @@ def _sub_adjoint(oy, ox, g_re, re, cfg, nsub):
     return oy, ox, g_re
 
 
+def _pre_diffuse(vy, vx, re, cfg, nsub):
+    """The head of a step with diffusion_substeps = nsub: (vy, vx, cfg) its launches run on -- M^(nsub-1) (vy, vx) (karman_diffuse_sub)
+    and diffusion_sub_cfg(cfg, nsub); nsub = 1: the arguments, no launch"""
+    if nsub == 1:
+        return vy, vx, cfg
+    return karman_diffuse_sub(vy, vx, re, cfg, nsub) + (diffusion_sub_cfg(cfg, nsub),)
+
+
+def _fwd_large(head, cfg, masks, ph, workspace, info, saved=None, feat=None, fs=None, p_guess=None):
+    """The one launch of the large-grid forward step: sol_karman_step_fwd_large + the scene's solver and ph.mode.  saved = (svy, svx):
+    the training form (_saved, _saved_buoy, _saved_adv); else the roll-out form with its extras (the plain step keeps an entry point
+    per solver: the direct one, _cg, and _cg_warm with p_guess; _buoy and _adv take either solver and the guess).  `head`: of
+    _step_fwd_args; `info` receives the CG solve's counts."""
+    dev = masks.active.device
+    ws = _workspace(large_workspace_bytes(cfg, masks, ph, saved is not None), workspace, dev)
+    cg_info = _cg_info(masks, cfg.B, dev)
+    mode = ph.mode
+    solver = (_hdr(masks.direct_header), ptr(masks.box), _hdr(masks.box_header), ptr(cg_info))
+    tail = (ptr(ws), ws.numel() * 4) + (ph.force_tail if mode else ())
+    if saved is not None:
+        name, args = "_saved" + mode, (ptr(saved[0]), ptr(saved[1]), *solver, *tail)
+    elif mode:
+        name, args = mode, (ptr(feat), fs, *solver, ptr(p_guess), *tail)
+    elif cg_info is None:
+        name, args = "", (ptr(feat), fs, solver[0], *tail)
+    else:
+        name, args = ("_cg", (ptr(feat), fs, *solver[1:], *tail)) if p_guess is None else ("_cg_warm", (ptr(feat), fs, *solver[1:], ptr(p_guess), *tail))
+    check(getattr(_lib.load(), "sol_karman_step_fwd_large" + name)(*head, *args))
+    _publish_cg(info, cg_info)
+
+
 def karman_step_saved(d, vy, vx, re, cfg, masks, workspace=None, info=None, buoyancy=None, diffusion_substeps=1,
-                      advection="semi_lagrangian", correction_strength=1.0):
+                      advection="semi_lagrangian", correction_strength=1.0, physics=None):
     """The differentiable form of the step without autograd, on any grid: ((d, vy, vx) after the step, saved vy, saved vx) -- the
     post-diffusion velocity the adjoints take.  A one-workgroup grid runs sol_karman_step_fwd (`info` receives "iterations"), a grid
     beyond them (masks.large) sol_karman_step_fwd_large_saved with `workspace` and `info` as in karman_step_large.
-    buoyancy = (fy, fx) (large grids only): sol_karman_step_fwd_large_saved_buoy, the density pushes the velocity.
-    diffusion_substeps = n > 1 (grids with Y, X >= 16): karman_diffuse_sub, then the same launches on diffusion_sub_cfg(cfg, n).
-    advection = "mac_cormack" (large grids only): sol_karman_step_fwd_large_saved_adv, the MacCormack advection of velocity and density
-    with correction_strength in [0, 1]; "semi_lagrangian" issues the launches and gives the bits of a call without the keyword."""
-    n = diffusion_substeps_arg(diffusion_substeps)
-    adv = advection_arg(advection, correction_strength, "karman_step_saved: advection")
-    if adv is not None:
-        _require_large_for_advection(masks, cfg.Y, cfg.X, "karman_step_saved")
-    if n > 1:
-        _require_sub_grid(cfg, "karman_step_saved")
-        pvy, pvx = karman_diffuse_sub(vy, vx, re, cfg, n)
-        return karman_step_saved(d, pvy, pvx, re, diffusion_sub_cfg(cfg, n), masks, workspace, info, buoyancy, 1, advection, correction_strength)
-    if buoyancy is not None:
-        _require_large_for_buoyancy(masks, cfg.Y, cfg.X, "karman_step_saved")
+    buoyancy, diffusion_substeps, advection, correction_strength: see StepPhysics (physics: one built by the caller, in their place)."""
+    ph = _physics(physics, "karman_step_saved", buoyancy=buoyancy, diffusion_substeps=diffusion_substeps, advection=advection,
+                  correction_strength=correction_strength, keep_zero_force=True)
+    ph.require(cfg, masks, "karman_step_saved")
     _lib.require_gpu()
-    lib = _lib.load()
     d, vy, vx, re = (_lib.f32(t) for t in (d, vy, vx, re))
     B, Y, X = cfg.B, cfg.Y, cfg.X
     assert vy.shape == (B, Y + 1, X) and vx.shape == (B, Y, X + 1) and d.shape == (B, Y, X) and re.shape == (B,)
+    vy, vx, cfg = _pre_diffuse(vy, vx, re, cfg, ph.nsub)
     outs, head = _step_fwd_args(d, vy, vx, re, cfg, masks)
     svy, svx = torch.empty_like(vy), torch.empty_like(vx)
     if masks.large:
-        workspace = _workspace(large_workspace_bytes(cfg, masks) if adv is None else large_adv_workspace_bytes(cfg, masks, True), workspace, vy.device)
-        cg_info = _cg_info(masks, B, vy.device)
-        entry, tail = (lib.sol_karman_step_fwd_large_saved, ()) if buoyancy is None else (lib.sol_karman_step_fwd_large_saved_buoy, tuple(buoyancy))
-        if adv is not None:
-            entry, tail = lib.sol_karman_step_fwd_large_saved_adv, (tuple(buoyancy) if buoyancy is not None else (0.0, 0.0)) + (1, adv)
-        check(entry(*head, ptr(svy), ptr(svx), _hdr(masks.direct_header), ptr(masks.box),
-                    _hdr(masks.box_header), ptr(cg_info), ptr(workspace), workspace.numel() * 4, *tail))
-        _publish_cg(info, cg_info)
+        _fwd_large(head, cfg, masks, ph, workspace, info, saved=(svy, svx))
     else:
         iters = None if info is None else torch.empty(B, dtype=torch.int32, device=vy.device)      # the kernel only stores to it
-        check(lib.sol_karman_step_fwd(*head, ptr(svy), ptr(svx), None, None, ptr(iters)))
+        check(_lib.load().sol_karman_step_fwd(*head, ptr(svy), ptr(svx), None, None, ptr(iters)))
         if info is not None:
             info["iterations"] = iters
     return outs, svy, svx
@@ -432,7 +507,8 @@ karman_step_large_saved = karman_step_saved      # the name the large-grid calle
 
 
 def karman_step_large(d, vy, vx, re, cfg, masks, workspace=None, info=None, feat=None, feat_scale=None, p_guess=None, out=None,
-                      density_grad=False, re_grad=False, buoyancy=None, diffusion_substeps=1, advection="semi_lagrangian", correction_strength=1.0):
+                      density_grad=False, re_grad=False, buoyancy=None, diffusion_substeps=1, advection="semi_lagrangian", correction_strength=1.0,
+                      physics=None):
     """The step for grids beyond the one-workgroup kernels (data generation at 256 x 128,
     /root/reference/karman-2d/karman.py:98-159): sol_karman_step_fwd_large (direct solve) or sol_karman_step_fwd_large_cg (CG solve,
     masks.pressure_solver == "cg").  Returns (d, vy, vx) after the step; with the CG solve, `info` (a dict) receives "iterations" and
@@ -447,47 +523,29 @@ def karman_step_large(d, vy, vx, re, cfg, masks, workspace=None, info=None, feat
     differentiable form is taken when any of d, vy, vx requires a gradient).
     re_grad=True (opt-in): a tensor `re` that requires a gradient receives one (KarmanStepFn's re mode: same forward launches, the step's
     input velocity saved as well; composes with density_grad).  Without the flag `re` is data.
-    buoyancy = (fy, fx) (see buoyancy_force): the step's output density pushes the velocity (sol_karman_step_fwd_large_buoy, one launch
-    more; every no-grad extra above still applies).  With a non-zero force the density is part of the dynamics: the differentiable form
-    keeps it in the graph as density_grad would (KarmanStepFn's buoyant mode).
-    diffusion_substeps = n > 1: the velocity is diffused by n explicit substeps of alpha / n, the boundary blend after the last one
-    (karman_diffuse_sub, one launch per diffuse_sub_max() substeps, then the launches above on diffusion_sub_cfg(cfg, n)); composes with
-    every mode and extra above.  n = 1 issues the launches and gives the bits of a call without the keyword.
-    advection = "mac_cormack", correction_strength = s in [0, 1]: velocity and density are advected by the MacCormack scheme with the
-    revert-to-semi-Lagrangian limiter (sol_karman_step_fwd_large_adv; the differentiable form through KarmanStepFn's adv mode, whose
-    adjoint freezes the limiter's decisions); composes with every mode and extra above.  "semi_lagrangian" issues the launches and gives
-    the bits of a call without the keyword."""
-    nsub = diffusion_substeps_arg(diffusion_substeps)
-    adv = advection_arg(advection, correction_strength, "karman_step_large: advection")
-    if adv is not None:
-        _require_large_for_advection(masks, cfg.Y, cfg.X, "karman_step_large")
-    if nsub > 1:
-        _require_sub_grid(cfg, "karman_step_large")
-    if buoyancy is not None:
-        _require_large_for_buoyancy(masks, cfg.Y, cfg.X, "karman_step_large")
+    buoyancy (see buoyancy_force), diffusion_substeps, advection, correction_strength: see StepPhysics; each composes with every mode
+    and extra above (physics: a StepPhysics built by the caller, in their place)."""
+    ph = _physics(physics, "karman_step_large", buoyancy=buoyancy, diffusion_substeps=diffusion_substeps, advection=advection,
+                  correction_strength=correction_strength, keep_zero_force=True)
+    ph.require(cfg, masks, "karman_step_large")
     if p_guess is not None and masks.direct is not None:
         raise ValueError("karman_step_large: p_guess warm-starts the CG pressure solve; this scene runs the direct solver (no iteration to start)")
-    differentiable, density, want_re = _step_mode(d, vy, vx, re, cfg, density_grad, re_grad, buoyancy)
+    differentiable, density, want_re = _step_mode(d, vy, vx, re, cfg, density_grad, re_grad, ph)
     _lib.require_gpu()
-    lib = _lib.load()
     d, vy, vx, re = (_lib.f32(t) for t in (d, vy, vx, re))
     B, Y, X = cfg.B, cfg.Y, cfg.X
     assert vy.shape == (B, Y + 1, X) and vx.shape == (B, Y, X + 1) and d.shape == (B, Y, X) and re.shape == (B,)
     if differentiable:
         if feat is not None or p_guess is not None or out is not None:
             raise ValueError("karman_step_large: feat / p_guess / out belong to the no-grad step (the differentiable step keeps its own state)")
-        return KarmanStepFn.apply(d, vy, vx, re, cfg, masks, workspace, info, density, want_re, buoyancy if _buoyant(buoyancy) else None, nsub, adv)
-    if nsub > 1:
-        pvy, pvx = karman_diffuse_sub(vy, vx, re, cfg, nsub)
-        return karman_step_large(d, pvy, pvx, re, diffusion_sub_cfg(cfg, nsub), masks, workspace, info, feat, feat_scale, p_guess, out,
-                                 buoyancy=buoyancy, advection=advection, correction_strength=correction_strength)
+        return KarmanStepFn.apply(d, vy, vx, re, cfg, masks, workspace, info, density, want_re, ph.moving())
+    vy, vx, cfg = _pre_diffuse(vy, vx, re, cfg, ph.nsub)
     if (feat is None) != (feat_scale is None):
         raise ValueError("karman_step_large: feat and feat_scale go together")
     if feat is not None and (feat.shape != (B, Y, X, 4) or feat.device != vy.device):
         raise ValueError("karman_step_large: feat must be [B,Y,X,4] = %s on %s (got %s on %s)" % ((B, Y, X, 4), vy.device, tuple(feat.shape), feat.device))
     if p_guess is not None and (p_guess.shape != (B, Y, X) or p_guess.device != vy.device):
         raise ValueError("karman_step_large: p_guess must be [B,Y,X] = %s on %s (got %s on %s)" % ((B, Y, X), vy.device, tuple(p_guess.shape), p_guess.device))
-    workspace = _workspace(large_workspace_bytes(cfg, masks) if adv is None else large_adv_workspace_bytes(cfg, masks), workspace, vy.device)
     if out is None:
         outs, head = _step_fwd_args(d, vy, vx, re, cfg, masks)
     else:
@@ -496,23 +554,7 @@ def karman_step_large(d, vy, vx, re, cfg, masks, workspace=None, info=None, feat
             raise ValueError("karman_step_large: out must be (d, vy, vx) buffers of the inputs' shapes")
         head = _step_fwd_args(d, vy, vx, re, cfg, masks, outs)[1]
     fs = None if feat_scale is None else (feat_scale if isinstance(feat_scale, C.Array) else _scale3(feat_scale))
-    cg_info = _cg_info(masks, B, vy.device)
-    if adv is not None:
-        check(lib.sol_karman_step_fwd_large_adv(*head, ptr(feat), fs, _hdr(masks.direct_header), ptr(masks.box), _hdr(masks.box_header),
-                                                ptr(cg_info), ptr(p_guess), ptr(workspace), workspace.numel() * 4,
-                                                *(buoyancy if buoyancy is not None else (0.0, 0.0)), 1, adv))
-    elif buoyancy is not None:
-        check(lib.sol_karman_step_fwd_large_buoy(*head, ptr(feat), fs, _hdr(masks.direct_header), ptr(masks.box), _hdr(masks.box_header),
-                                                 ptr(cg_info), ptr(p_guess), ptr(workspace), workspace.numel() * 4, *buoyancy))
-    elif cg_info is None:
-        check(lib.sol_karman_step_fwd_large(*head, ptr(feat), fs, _hdr(masks.direct_header), ptr(workspace), workspace.numel() * 4))
-    elif p_guess is None:
-        check(lib.sol_karman_step_fwd_large_cg(*head, ptr(feat), fs, ptr(masks.box), _hdr(masks.box_header), ptr(cg_info),
-                                               ptr(workspace), workspace.numel() * 4))
-    else:
-        check(lib.sol_karman_step_fwd_large_cg_warm(*head, ptr(feat), fs, ptr(masks.box), _hdr(masks.box_header), ptr(cg_info),
-                                                    ptr(p_guess), ptr(workspace), workspace.numel() * 4))
-    _publish_cg(info, cg_info)
+    _fwd_large(head, cfg, masks, ph, workspace, info, feat=feat, fs=fs, p_guess=p_guess)
     return outs
 
 
@@ -576,21 +618,6 @@ def _step_bwd(svy, svx, re, gvy, gvx, cfg, masks, info):
     return oy, ox
 
 
-def large_bwd_re_workspace_bytes(cfg, masks):
-    """Device scratch of the staged adjoint with the Reynolds-number gradient (sol_karman_step_bwd_large_re) for the scene's solver."""
-    return _lib.load().sol_karman_step_bwd_large_re_workspace_bytes_for(C.byref(cfg), _hdr(masks.direct_header))
-
-
-def density_bwd_workspace_bytes(cfg):
-    """Device scratch of the density adjoint (sol_karman_density_bwd)."""
-    return _lib.load().sol_karman_density_bwd_workspace_bytes(C.byref(cfg))
-
-
-def density_bwd_re_workspace_bytes(cfg):
-    """Device scratch of the density adjoint with the Reynolds-number gradient (sol_karman_density_bwd_re)."""
-    return _lib.load().sol_karman_density_bwd_re_workspace_bytes(C.byref(cfg))
-
-
 def _require_staged(cfg, who):
     if cfg.Y < 16 or cfg.X < 16:
         raise SolError("%s: the gradient with respect to re runs the staged adjoint (sol_karman_step_bwd_large_re), which takes grids "
@@ -612,121 +639,71 @@ def _re_tail(who, re_in, svy, svx, B):
     return (ptr(vy_in), ptr(vx_in), ptr(g_re), int(accumulate)), g_re
 
 
-def _large_bwd(who, svy, svx, re, gvy, gvx, cfg, masks, workspace, info, re_in=None):
-    """karman_step_large_bwd (re_in None) and karman_step_large_bwd_re (re_in = (vy_in, vx_in, g_re)): the _re entry point takes its
-    plain sibling's arguments and four more"""
-    if re_in is not None:
-        _require_staged(cfg, who)
-    _lib.require_gpu()
-    lib = _lib.load()
-    svy, svx, re, gvy, gvx = (_lib.f32(t) for t in (svy, svx, re, gvy, gvx))
-    if re_in is None:
-        entry, nbytes, tail, g_re = lib.sol_karman_step_bwd_large, large_bwd_workspace_bytes(cfg, masks), (), None
-    else:
-        entry, nbytes = lib.sol_karman_step_bwd_large_re, large_bwd_re_workspace_bytes(cfg, masks)
-        tail, g_re = _re_tail(who, re_in, svy, svx, cfg.B)
+def _velocity_bwd(who, svy, svx, re, gvy, gvx, gd, cfg, masks, ph, re_in, workspace, info, fused):
+    """The velocity half of the step's adjoint on the cfg as given, the one launch site of sol_karman_step_bwd_large + ph.mode (+ _re with
+    re_in = (vy_in, vx_in, g_re)): -> (g_vy_in, g_vx_in, g_re | None, g_dsum | None).  A missing cotangent counts as zero.  The _buoy and
+    _adv entry points (the latter with a force of (0, 0) when there is none) also write g_dsum = gd + dt F . transpose of the face
+    average of the cotangent, what the density half then runs on; under mac_cormack with neither a force nor gd nothing reaches the
+    density and g_dsum is None.  The plain ones hand gd through.  fused (the autograd step): a one-workgroup grid without re_in runs
+    sol_karman_step_bwd, the pressure solve fused in."""
+    gvy = torch.zeros_like(svy) if gvy is None else _lib.f32(gvy)
+    gvx = torch.zeros_like(svx) if gvx is None else _lib.f32(gvx)
+    mode = ph.mode
+    if fused and re_in is None and not mode and not masks.large:
+        return _step_bwd(svy, svx, re, gvy, gvx, cfg, masks, info) + (None, gd)
+    tail, g_re = ((), None) if re_in is None else _re_tail(who, re_in, svy, svx, cfg.B)
+    g_dsum = gd
+    if mode:
+        g_dsum = torch.empty(cfg.B, cfg.Y, cfg.X, dtype=torch.float32, device=svy.device)
+        force = ph.force_tail
+        tail += force[:2] + (ptr(gd), ptr(g_dsum)) + force[2:]
     box, box_header = masks.staged_box()
-    workspace = _workspace(nbytes, workspace, svy.device)
+    workspace = _workspace(large_bwd_workspace_bytes(cfg, masks, ph, re_in is not None), workspace, svy.device)
     oy, ox = torch.empty_like(svy), torch.empty_like(svx)
     cg_info = _cg_info(masks, cfg.B, svy.device)
+    entry = getattr(_lib.load(), "sol_karman_step_bwd_large" + mode + ("" if re_in is None else "_re"))
     check(entry(C.byref(cfg), stream(), ptr(svy), ptr(svx), ptr(re), ptr(masks.active), ptr(masks.velBCyMask), masks.bc_stride,
                 ptr(gvy), ptr(gvx), ptr(oy), ptr(ox), _hdr(masks.direct_header), ptr(box), _hdr(box_header), ptr(cg_info),
                 ptr(workspace), workspace.numel() * 4, *tail))
     _publish_cg(info, cg_info, "_bwd")
-    return (oy, ox) if re_in is None else (oy, ox, g_re)
-
-
-def _large_bwd_adv(d, svy, svx, re, gvy, gvx, gd, cfg, masks, buoyancy, adv, vel_in, workspace, info, density_workspace, density=True):
-    """The adjoint under advection="mac_cormack" (adv = the correction strength) on the cfg as given, in _large_bwd_buoy's shape:
-    sol_karman_step_bwd_large_adv(_re) when a velocity cotangent arrived (force (0, 0) without buoyancy), then -- `density`: the density
-    is in the graph -- sol_karman_density_bwd_adv(_re) on g_dsum, added onto its result.  -> (g_d_in, g_vy_in, g_vx_in[, g_re])"""
-    who = "karman_step_large_bwd (mac_cormack)"
-    _require_large_for_advection(masks, cfg.Y, cfg.X, who)
-    if gvy is None and gvx is None and (gd is None or not density):
-        return (None,) * (3 if vel_in is None else 4)
-    if vel_in is not None:
-        _require_staged(cfg, who)
-    _lib.require_gpu()
-    lib = _lib.load()
-    svy, svx, re = (_lib.f32(t) for t in (svy, svx, re))
-    gd = None if gd is None or not density else _lib.f32(gd)
-    force = (0.0, 0.0) if buoyancy is None else (float(buoyancy[0]), float(buoyancy[1]))
-    od = oy = ox = g_re = None
-    g_dsum = gd
-    if gvy is not None or gvx is not None:
-        gvy = torch.zeros_like(svy) if gvy is None else _lib.f32(gvy)
-        gvx = torch.zeros_like(svx) if gvx is None else _lib.f32(gvx)
-        if vel_in is None:
-            entry, tail = lib.sol_karman_step_bwd_large_adv, ()
-        else:
-            entry = lib.sol_karman_step_bwd_large_adv_re
-            tail, g_re = _re_tail(who, tuple(vel_in) + (None,), svy, svx, cfg.B)
-        box, box_header = masks.staged_box()
-        workspace = _workspace(large_bwd_adv_workspace_bytes(cfg, masks, vel_in is not None), workspace, svy.device)
-        oy, ox = torch.empty_like(svy), torch.empty_like(svx)
-        g_dsum = torch.empty(cfg.B, cfg.Y, cfg.X, dtype=torch.float32, device=svy.device)
-        cg_info = _cg_info(masks, cfg.B, svy.device)
-        check(entry(C.byref(cfg), stream(), ptr(svy), ptr(svx), ptr(re), ptr(masks.active), ptr(masks.velBCyMask), masks.bc_stride,
-                    ptr(gvy), ptr(gvx), ptr(oy), ptr(ox), _hdr(masks.direct_header), ptr(box), _hdr(box_header), ptr(cg_info),
-                    ptr(workspace), workspace.numel() * 4, *tail, force[0], force[1], ptr(gd), ptr(g_dsum), 1, adv))
-        _publish_cg(info, cg_info, "_bwd")
-        if gd is None and force == (0.0, 0.0):
-            g_dsum = None              # nothing reaches the density: its adjoint is skipped
-    if density and g_dsum is not None:
-        res = _density_bwd(who, d, svy, svx, re, g_dsum, cfg, masks, oy, ox, density_workspace,
-                           None if vel_in is None else tuple(vel_in) + (g_re,), adv)
-        od, oy, ox = res[:3]
-        if vel_in is not None:
-            g_re = res[3]
-    return (od, oy, ox) if vel_in is None else (od, oy, ox, g_re)
+    if ph.adv is not None and gd is None and force[:2] == (0.0, 0.0):
+        g_dsum = None
+    return oy, ox, g_re, g_dsum
 
 
 def karman_step_large_bwd(svy, svx, re, gvy, gvx, cfg, masks, workspace=None, info=None, diffusion_substeps=1,
-                          advection="semi_lagrangian", correction_strength=1.0):
-    """Adjoint of the large-grid step (sol_karman_step_bwd_large): (g_vy_in, g_vx_in) from the saved post-diffusion velocity and the
-    gradient with respect to the step's output velocity.  With the CG solve, `info` receives "iterations_bwd" / "converged_bwd".
-    diffusion_substeps = n: the adjoint of karman_step_saved(.., diffusion_substeps=n) -- the same launches on diffusion_sub_cfg(cfg, n),
-    then karman_diffuse_sub on their result (`cfg` is the step's own, unscaled one).
-    advection = "mac_cormack": the adjoint of the step with that advection (sol_karman_step_bwd_large_adv), the velocity's part -- the
-    density's is karman_density_bwd with the same keywords."""
-    n = diffusion_substeps_arg(diffusion_substeps)
-    adv = advection_arg(advection, correction_strength, "karman_step_large_bwd: advection")
-    if adv is not None:
-        res = _large_bwd_adv(None, svy, svx, re, gvy, gvx, None, diffusion_sub_cfg(cfg, n), masks, None, adv, None, workspace, info, None, density=False)
-        return _sub_adjoint(res[1], res[2], None, re, cfg, n)[:2]
-    oy, ox = _large_bwd("karman_step_large_bwd", svy, svx, re, gvy, gvx, diffusion_sub_cfg(cfg, n), masks, workspace, info)
-    return _sub_adjoint(oy, ox, None, re, cfg, n)[:2]
+                          advection="semi_lagrangian", correction_strength=1.0, physics=None):
+    """Adjoint of the large-grid step, the velocity's part (sol_karman_step_bwd_large; under advection="mac_cormack" _adv): (g_vy_in,
+    g_vx_in) from the saved post-diffusion velocity and the gradient with respect to the step's output velocity.  With the CG solve,
+    `info` receives "iterations_bwd" / "converged_bwd".  diffusion_substeps = n: the adjoint of karman_step_saved(.., diffusion_substeps=n),
+    `cfg` the step's own, unscaled one (see _step_adjoint).  The density's part is karman_density_bwd with the same keywords."""
+    ph = _physics(physics, "karman_step_large_bwd", diffusion_substeps=diffusion_substeps, advection=advection, correction_strength=correction_strength)
+    return _step_adjoint("karman_step_large_bwd", None, svy, svx, re, None, gvy, gvx, cfg, masks, ph, False, None, None, workspace, info)[1:3]
 
 
 def karman_step_large_bwd_re(svy, svx, re, gvy, gvx, vy_in, vx_in, cfg, masks, g_re=None, workspace=None, info=None, diffusion_substeps=1,
-                             advection="semi_lagrangian", correction_strength=1.0):
+                             advection="semi_lagrangian", correction_strength=1.0, physics=None):
     """The staged velocity adjoint with the gradient with respect to re (sol_karman_step_bwd_large_re), on every grid with Y, X >= 16 --
     the one-workgroup grids included: (g_vy_in, g_vx_in, g_re) from the saved post-diffusion velocity, the cotangent of the step's output
     velocity and the step's INPUT velocity.  g_vy_in / g_vx_in are karman_step_large_bwd's bits.  g_re [B]: a buffer to add onto (one
     fp32 add), else a fresh one is written.
     diffusion_substeps = n > 1: as in karman_step_large_bwd; vy_in / vx_in are then the PRE-DIFFUSED input, karman_diffuse_sub(vy, vx, re,
-    cfg, n), and the reduction's result is multiplied by n (a g_re to add onto is not taken: it would be scaled too)."""
-    n = diffusion_substeps_arg(diffusion_substeps)
-    if n > 1 and g_re is not None:
+    cfg, n), and the reduction's result is multiplied by n (a g_re to add onto is not taken: it would be scaled too; nor is one under
+    advection="mac_cormack")."""
+    ph = _physics(physics, "karman_step_large_bwd_re", diffusion_substeps=diffusion_substeps, advection=advection, correction_strength=correction_strength)
+    if ph.nsub > 1 and g_re is not None:
         raise ValueError("karman_step_large_bwd_re: with diffusion_substeps > 1 the gradient in re is written to a fresh tensor (g_re=None)")
-    adv = advection_arg(advection, correction_strength, "karman_step_large_bwd_re: advection")
-    if adv is not None:           # sol_karman_step_bwd_large_adv_re
-        if g_re is not None:
-            raise ValueError("karman_step_large_bwd_re: with advection='mac_cormack' the gradient in re is written to a fresh tensor (g_re=None)")
-        res = _large_bwd_adv(None, svy, svx, re, gvy, gvx, None, diffusion_sub_cfg(cfg, n), masks, None, adv, (vy_in, vx_in), workspace, info, None,
-                             density=False)
-        return _sub_adjoint(res[1], res[2], res[3], re, cfg, n)
-    oy, ox, g = _large_bwd("karman_step_large_bwd_re", svy, svx, re, gvy, gvx, diffusion_sub_cfg(cfg, n), masks, workspace, info, (vy_in, vx_in, g_re))
-    return _sub_adjoint(oy, ox, g, re, cfg, n)
+    if ph.adv is not None and g_re is not None:
+        raise ValueError("karman_step_large_bwd_re: with advection='mac_cormack' the gradient in re is written to a fresh tensor (g_re=None)")
+    return _step_adjoint("karman_step_large_bwd_re", None, svy, svx, re, None, gvy, gvx, cfg, masks, ph, False, (vy_in, vx_in), g_re, workspace, info)[1:]
 
 
-def _density_bwd(who, d, svy, svx, re, g_d, cfg, masks, g_vy, g_vx, workspace, re_in=None, adv=None):
-    """karman_density_bwd (re_in None) and karman_density_bwd_re (re_in = (vy_in, vx_in, g_re)), paired as in _large_bwd; adv = the
-    correction strength of advection="mac_cormack": the _adv entry points"""
-    if adv is not None:
+def _density_bwd(who, d, svy, svx, re, g_d, cfg, masks, g_vy, g_vx, workspace, re_in=None, ph=StepPhysics()):
+    """The density half of the step's adjoint on the cfg as given, the one launch site of sol_karman_density_bwd (+ _adv under
+    ph.adv, + _re with re_in = (vy_in, vx_in, g_re)): -> (g_d_in, g_vy_in, g_vx_in[, g_re]), added onto g_vy / g_vx and g_re where given"""
+    if ph.adv is not None:
         _adv_grid(cfg, who)
     _lib.require_gpu()
-    lib = _lib.load()
     if (g_vy is None) != (g_vx is None):
         raise ValueError("%s: g_vy and g_vx go together" % who)
     B, Y, X = cfg.B, cfg.Y, cfg.X
@@ -737,17 +714,13 @@ def _density_bwd(who, d, svy, svx, re, g_d, cfg, masks, g_vy, g_vx, workspace, r
     accumulate = g_vy is not None
     if accumulate and (g_vy.shape != svy.shape or g_vx.shape != svx.shape):
         raise ValueError("%s: g_vy / g_vx must have the velocity's shapes" % who)
-    if re_in is None:
-        entry, nbytes, tail, g_re = lib.sol_karman_density_bwd, density_bwd_workspace_bytes(cfg), (), None
-    else:
-        entry, nbytes = lib.sol_karman_density_bwd_re, density_bwd_re_workspace_bytes(cfg)
-        tail, g_re = _re_tail(who, re_in, svy, svx, B)
-    if adv is not None:
-        entry = lib.sol_karman_density_bwd_adv if re_in is None else lib.sol_karman_density_bwd_adv_re
-        nbytes, tail = density_bwd_adv_workspace_bytes(cfg, re_in is not None), tuple(tail) + (1, adv)
+    tail, g_re = ((), None) if re_in is None else _re_tail(who, re_in, svy, svx, B)
+    if ph.adv is not None:
+        tail += (1, ph.adv)
     oy, ox = (g_vy, g_vx) if accumulate else (torch.empty_like(svy), torch.empty_like(svx))
     od = torch.empty_like(d)
-    workspace = _workspace(nbytes, workspace, d.device)
+    workspace = _workspace(density_bwd_workspace_bytes(cfg, ph, re_in is not None), workspace, d.device)
+    entry = getattr(_lib.load(), "sol_karman_density_bwd" + ("" if ph.adv is None else "_adv") + ("" if re_in is None else "_re"))
     check(entry(C.byref(cfg), stream(), ptr(d), ptr(masks.inflow), ptr(svy), ptr(svx), ptr(re), ptr(masks.velBCyMask), masks.bc_stride,
                 ptr(g_d), ptr(od), ptr(oy), ptr(ox), int(accumulate), ptr(workspace), workspace.numel() * 4, *tail))
     return (od, oy, ox) if re_in is None else (od, oy, ox, g_re)
@@ -759,16 +732,16 @@ def karman_density_bwd(d, svy, svx, re, g_d, cfg, masks, g_vy=None, g_vx=None, w
     or neither): buffers that already hold the velocity adjoint's result; the density's part is added onto them in place (one fp32 add
     per face) and they are returned.  Without them the density's part alone is written to fresh tensors.
     advection = "mac_cormack" (grids with Y, X >= 16): the adjoint of the MacCormack-advected density (sol_karman_density_bwd_adv)."""
-    adv = advection_arg(advection, correction_strength, "karman_density_bwd: advection")
-    return _density_bwd("karman_density_bwd", d, svy, svx, re, g_d, cfg, masks, g_vy, g_vx, workspace, None, adv)
+    ph = _physics(None, "karman_density_bwd", advection=advection, correction_strength=correction_strength)
+    return _density_bwd("karman_density_bwd", d, svy, svx, re, g_d, cfg, masks, g_vy, g_vx, workspace, None, ph)
 
 
 def karman_density_bwd_re(d, svy, svx, re, g_d, vy_in, vx_in, cfg, masks, g_vy=None, g_vx=None, g_re=None, workspace=None,
                           advection="semi_lagrangian", correction_strength=1.0):
     """karman_density_bwd with the gradient with respect to re (sol_karman_density_bwd_re): (g_d_in, g_vy_in, g_vx_in, g_re).  The first
     three are karman_density_bwd's bits; g_re [B]: a buffer to add onto (the velocity adjoint's part), else a fresh one is written."""
-    adv = advection_arg(advection, correction_strength, "karman_density_bwd_re: advection")
-    return _density_bwd("karman_density_bwd_re", d, svy, svx, re, g_d, cfg, masks, g_vy, g_vx, workspace, (vy_in, vx_in, g_re), adv)
+    ph = _physics(None, "karman_density_bwd_re", advection=advection, correction_strength=correction_strength)
+    return _density_bwd("karman_density_bwd_re", d, svy, svx, re, g_d, cfg, masks, g_vy, g_vx, workspace, (vy_in, vx_in, g_re), ph)
 
 
 def karman_buoyancy_add(d, vy, vx, active, f):
@@ -796,112 +769,75 @@ def karman_buoyancy_add_bwd(gvy, gvx, active, f, gd=None):
     return out
 
 
-def karman_step_large_bwd_buoy(d, svy, svx, re, gvy, gvx, gd, cfg, masks, buoyancy, vel_in=None, workspace=None, info=None,
-                               density_workspace=None, diffusion_substeps=1, advection="semi_lagrangian", correction_strength=1.0):
-    """Adjoint of the BUOYANT large-grid step (karman_step_saved(..., buoyancy=F)): (g_d_in, g_vy_in, g_vx_in) -- with vel_in = (vy, vx),
-    the step's input velocity, (g_d_in, g_vy_in, g_vx_in, g_re) -- from the step's input density `d`, the saved post-diffusion velocity and
-    the cotangents gvy, gvx, gd of its outputs (None = zero).  With a velocity cotangent: sol_karman_step_bwd_large_buoy(_re) (the plain
-    velocity adjoint's launches, then g_dsum = gd + dt F . transpose of the face average of g_a), then the density adjoint on g_dsum,
-    added onto the velocity adjoint's result.  Without one (a density-only loss) no pressure solve runs: the density adjoint on gd alone.
-    No cotangent at all: every result is None.  workspace / density_workspace: scratch of the velocity / the density adjoint.
-    diffusion_substeps = n > 1: the same launches on diffusion_sub_cfg(cfg, n) (vel_in is then the PRE-DIFFUSED input velocity,
-    karman_diffuse_sub(vy, vx, re, cfg, n)), then karman_diffuse_sub on the velocity cotangent and g_re times n.
-    advection = "mac_cormack", correction_strength = s: the adjoint of the step with that advection -- the same chain over
-    sol_karman_step_bwd_large_adv(_re) and sol_karman_density_bwd_adv(_re)."""
-    n = diffusion_substeps_arg(diffusion_substeps)
-    adv = advection_arg(advection, correction_strength, "karman_step_large_bwd_buoy: advection")
-    if adv is not None:           # the _adv entry points: the same chain with the MacCormack advection's adjoints
-        _require_large_for_buoyancy(masks, cfg.Y, cfg.X, "karman_step_large_bwd_buoy")
-        res = _large_bwd_adv(d, svy, svx, re, gvy, gvx, gd, diffusion_sub_cfg(cfg, n), masks, buoyancy, adv, vel_in, workspace, info, density_workspace)
-    else:
-        res = _large_bwd_buoy(d, svy, svx, re, gvy, gvx, gd, diffusion_sub_cfg(cfg, n), masks, buoyancy, vel_in, workspace, info, density_workspace)
-    if n == 1:
-        return res
-    oy, ox, g_re = _sub_adjoint(res[1], res[2], res[3] if vel_in is not None else None, re, cfg, n)
-    return (res[0], oy, ox) if vel_in is None else (res[0], oy, ox, g_re)
-
-
-def _large_bwd_buoy(d, svy, svx, re, gvy, gvx, gd, cfg, masks, buoyancy, vel_in, workspace, info, density_workspace):
-    """the launches of karman_step_large_bwd_buoy on the cfg as given"""
-    _require_large_for_buoyancy(masks, cfg.Y, cfg.X, "karman_step_large_bwd_buoy")
-    who = "karman_step_large_bwd_buoy"
+def _step_adjoint(who, d, svy, svx, re, gd, gvy, gvx, cfg, masks, ph, density, vel_in=None, g_re=None, workspace=None, info=None,
+                  density_workspace=None, fused=False):
+    """THE adjoint of one step under ph, behind KarmanStepFn.backward and the direct calls karman_step_large_bwd / _bwd_re / _bwd_buoy:
+    -> (g_d_in, g_vy_in, g_vx_in, g_re), each None where nothing reaches it.  From the step's input density `d`, the saved post-diffusion
+    velocity, the cotangents gd, gvy, gvx of its outputs (None = zero) and `cfg`, the step's own (unscaled) one.
+    - `density`: the density is in the graph (density_grad, or a force that moves the velocity); without it gd is ignored and the density
+      half never runs.
+    - The velocity half (_velocity_bwd, with its pressure solve) runs only when a velocity cotangent arrived.  Without one the density
+      half runs on gd alone; with no cotangent at all every result is None.
+    - The density half (_density_bwd) runs on what the velocity half left for it (g_dsum: gd, plus the force's part under _buoy / _adv)
+      and adds onto the velocity half's buffers and onto g_re.
+    - vel_in = (vy_in, vx_in), the step's input velocity (under substeps the PRE-DIFFUSED one), asks for g_re: the _re entry points on
+      grids with Y, X >= 16.  g_re: a buffer to add onto (plain mode only).
+    - ph.nsub = n > 1: both halves run on diffusion_sub_cfg(cfg, n); the velocity cotangent then goes through karman_diffuse_sub on cfg
+      (M^(n-1) is symmetric) and g_re is multiplied by n, once (_sub_adjoint).
+    `info` receives "iterations_bwd" / "converged_bwd"; workspace / density_workspace: scratch of the two halves; fused: see _velocity_bwd."""
+    ph.require(cfg, masks, who)
+    gd = gd if density else None
+    od = oy = ox = None
     if gvy is None and gvx is None and gd is None:
-        return (None,) * (3 if vel_in is None else 4)
+        return None, None, None, None
     if vel_in is not None:
         _require_staged(cfg, who)
     _lib.require_gpu()
-    lib = _lib.load()
-    d, svy, svx, re = (_lib.f32(t) for t in (d, svy, svx, re))
-    gd = None if gd is None else _lib.f32(gd)
-    oy = ox = g_re = None
-    g_dsum = gd
+    sc = diffusion_sub_cfg(cfg, ph.nsub)
+    svy, svx, re = (_lib.f32(t) for t in (svy, svx, re))
+    g_dsum = gd = None if gd is None else _lib.f32(gd)
     if gvy is not None or gvx is not None:
-        gvy = torch.zeros_like(svy) if gvy is None else _lib.f32(gvy)
-        gvx = torch.zeros_like(svx) if gvx is None else _lib.f32(gvx)
-        if vel_in is None:
-            entry, nbytes, tail = lib.sol_karman_step_bwd_large_buoy, large_bwd_workspace_bytes(cfg, masks), ()
-        else:
-            entry, nbytes = lib.sol_karman_step_bwd_large_buoy_re, large_bwd_re_workspace_bytes(cfg, masks)
-            tail, g_re = _re_tail(who, tuple(vel_in) + (None,), svy, svx, cfg.B)
-        box, box_header = masks.staged_box()
-        workspace = _workspace(nbytes, workspace, svy.device)
-        oy, ox, g_dsum = torch.empty_like(svy), torch.empty_like(svx), torch.empty_like(d)
-        cg_info = _cg_info(masks, cfg.B, svy.device)
-        check(entry(C.byref(cfg), stream(), ptr(svy), ptr(svx), ptr(re), ptr(masks.active), ptr(masks.velBCyMask), masks.bc_stride,
-                    ptr(gvy), ptr(gvx), ptr(oy), ptr(ox), _hdr(masks.direct_header), ptr(box), _hdr(box_header), ptr(cg_info),
-                    ptr(workspace), workspace.numel() * 4, *tail, float(buoyancy[0]), float(buoyancy[1]), ptr(gd), ptr(g_dsum)))
-        _publish_cg(info, cg_info, "_bwd")
-    if vel_in is None:
-        return karman_density_bwd(d, svy, svx, re, g_dsum, cfg, masks, oy, ox, density_workspace)
-    return karman_density_bwd_re(d, svy, svx, re, g_dsum, *vel_in, cfg, masks, oy, ox, g_re, density_workspace)
+        oy, ox, g_re, g_dsum = _velocity_bwd(who, svy, svx, re, gvy, gvx, gd, sc, masks, ph, None if vel_in is None else (*vel_in, g_re),
+                                             workspace, info, fused)
+    if density and g_dsum is not None:
+        od, oy, ox, *g = _density_bwd(who, d, svy, svx, re, g_dsum, sc, masks, oy, ox, density_workspace,
+                                      None if vel_in is None else (*vel_in, g_re), ph)
+        g_re = g[0] if g else None
+    return (od,) + _sub_adjoint(oy, ox, g_re, re, cfg, ph.nsub)
 
 
-def _velocity_bwd(svy, svx, re, gvy, gvx, cfg, masks, info, vel_in=None):
-    """The velocity half of the step's adjoint: (g_vy_in, g_vx_in, g_re | None).  vel_in = (vy, vx), the step's input velocity, asks for
-    the gradient with respect to re as well: the staged adjoint on every grid (karman_step_large_bwd_re; the fused one-workgroup adjoint
-    hands no diffusion cotangent out).  Without it: the fused adjoint on a one-workgroup grid, karman_step_large_bwd beyond.  A missing
-    cotangent counts as zero."""
-    gvy = torch.zeros_like(svy) if gvy is None else gvy.contiguous()
-    gvx = torch.zeros_like(svx) if gvx is None else gvx.contiguous()
-    if vel_in is not None:
-        return karman_step_large_bwd_re(svy, svx, re, gvy, gvx, *vel_in, cfg, masks, info=info)
-    if masks.large:
-        return karman_step_large_bwd(svy, svx, re, gvy, gvx, cfg, masks, info=info) + (None,)
-    return _step_bwd(svy, svx, re, gvy, gvx, cfg, masks, info) + (None,)
+def karman_step_large_bwd_buoy(d, svy, svx, re, gvy, gvx, gd, cfg, masks, buoyancy, vel_in=None, workspace=None, info=None,
+                               density_workspace=None, diffusion_substeps=1, advection="semi_lagrangian", correction_strength=1.0, physics=None):
+    """Adjoint of the BUOYANT large-grid step (karman_step_saved(..., buoyancy=F)), the density in the graph: (g_d_in, g_vy_in, g_vx_in)
+    -- with vel_in = (vy, vx), the step's input velocity, (g_d_in, g_vy_in, g_vx_in, g_re) -- from the step's input density `d`, the
+    saved post-diffusion velocity and the cotangents gvy, gvx, gd of its outputs (None = zero): _step_adjoint, which describes the chain
+    and the other keywords."""
+    ph = _physics(physics, "karman_step_large_bwd_buoy", buoyancy=buoyancy, diffusion_substeps=diffusion_substeps, advection=advection,
+                  correction_strength=correction_strength, keep_zero_force=True)
+    res = _step_adjoint("karman_step_large_bwd_buoy", d, svy, svx, re, gd, gvy, gvx, cfg, masks, ph, True, vel_in, None, workspace, info,
+                        density_workspace)
+    return res if vel_in is not None else res[:3]
 
 
 class KarmanStepFn(torch.autograd.Function):
-    """(d, vy, vx) [B,Y,X] / [B,Y+1,X] / [B,Y,X+1] -> one simulator_lo.step(...) on any grid, with its hand-written adjoints; the forward
-    launches are karman_step_saved's in every mode.  Plain: differentiable with respect to the velocity, the density is a passive
-    tracer.  `density` (opt-in, density_grad=True): the density output is differentiable too (karman_density_bwd, added onto the
-    velocity adjoint's result).  `want_re` (opt-in, re_grad=True; grids with Y, X >= 16): differentiable with respect to re as well, the
-    step's input velocity saved beside the post-diffusion one (_step_mode and torch.ops.sol.karman_step_re check the grid).  backward returns (g_d_in | None, g_vy_in, g_vx_in, g_re | None); the
-    velocity half (with its pressure solve) runs only when a velocity cotangent arrived, the density half only when a density cotangent
-    did.  `buoyancy` = (fy, fx), a non-zero force (large grids; else None): the buoyant step -- the density is part of the dynamics, so
-    it is in the graph whatever `density` says; a velocity-only loss yields a density gradient too (karman_step_large_bwd_buoy), a
-    density-only loss still runs no pressure solve.  `nsub` (diffusion_substeps = n > 1; grids with Y, X >= 16): n explicit diffusion
-    substeps -- karman_diffuse_sub before the forward launches, and on the velocity cotangent after the backward ones, both on the scaled
-    cfg (diffusion_sub_cfg); g_re times n.  Composes with every other mode; nsub = 1 launches nothing new."""
+    """(d, vy, vx) [B,Y,X] / [B,Y+1,X] / [B,Y,X+1] -> one simulator_lo.step(...) on any grid, with its hand-written adjoint; the forward
+    launches are karman_step_saved's and the backward ones _step_adjoint's in every mode.  Plain: differentiable with respect to the
+    velocity, the density is a passive tracer.  `density` (opt-in, density_grad=True): the density output is differentiable too.
+    `want_re` (opt-in, re_grad=True; grids with Y, X >= 16, which _step_mode and the torch.ops.sol steps check): differentiable with
+    respect to re as well, the step's input velocity saved beside the post-diffusion one.  `physics`: the StepPhysics, a force in it one
+    that moves the velocity (StepPhysics.moving) -- the density is then in the graph whatever `density` says.
+    backward returns (g_d_in | None, g_vy_in, g_vx_in, g_re | None)."""
 
     @staticmethod
-    def forward(ctx, d, vy, vx, re, cfg, masks, workspace, info, density, want_re, buoyancy=None, nsub=1, adv=None):
+    def forward(ctx, d, vy, vx, re, cfg, masks, workspace, info, density, want_re, physics):
         _lib.require_gpu()
         d, vy, vx, re = (_lib.f32(t) for t in (d, vy, vx, re))
-        density = bool(density) or buoyancy is not None
-        # diffusion substeps (nsub > 1; one more mode, composing with the others): the existing launches on the scaled cfg, applied to the
-        # pre-diffused velocity M^(nsub-1) v -- which is also the "input velocity" the re mode saves; backward ends with _sub_adjoint
-        ctx.cfg_full, ctx.nsub = cfg, nsub
-        if nsub > 1:
-            _require_sub_grid(cfg, "diffusion_substeps")
-            vy, vx = karman_diffuse_sub(vy, vx, re, cfg, nsub)
-            cfg = diffusion_sub_cfg(cfg, nsub)
-        # adv (advection="mac_cormack": its correction strength; large grids): the _adv forward launches, and in backward the chain of
-        # _large_bwd_adv in every mode
-        ctx.adv = adv
-        outs, svy, svx = karman_step_saved(d, vy, vx, re, cfg, masks, workspace, info, buoyancy,
-                                           **({} if adv is None else {"advection": "mac_cormack", "correction_strength": adv}))
+        density = bool(density) or physics.buoyancy is not None
+        ctx.cfg, ctx.masks, ctx.info, ctx.density, ctx.want_re, ctx.physics = cfg, masks, info, density, want_re, physics
+        # under substeps the pre-diffused velocity M^(nsub-1) v is also the "input velocity" the re mode saves
+        vy, vx, cfg = _pre_diffuse(vy, vx, re, cfg, physics.nsub)
+        outs, svy, svx = karman_step_saved(d, vy, vx, re, cfg, masks, workspace, info, physics=physics._replace(nsub=1))
         ctx.save_for_backward(svy, svx, re, *((d, vy, vx) if want_re else (d,) if density else ()))
-        ctx.cfg, ctx.masks, ctx.info, ctx.density, ctx.want_re, ctx.buoyancy = cfg, masks, info, density, want_re, buoyancy
         if not density:
             ctx.mark_non_differentiable(outs[0])
         ctx.set_materialize_grads(False)
@@ -910,57 +846,36 @@ class KarmanStepFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gd, gvy, gvx):
         svy, svx, re, *inputs = ctx.saved_tensors
-        cfg, masks = ctx.cfg, ctx.masks
-        vel_in = tuple(inputs[1:]) if ctx.want_re else None
-        od = oy = ox = g_re = None
-        if ctx.adv is not None:
-            gvy, gvx, gd = (None if g is None else g.contiguous() for g in (gvy, gvx, gd))
-            res = _large_bwd_adv(inputs[0] if ctx.density else None, svy, svx, re, gvy, gvx, gd, cfg, masks, ctx.buoyancy, ctx.adv, vel_in, None,
-                                 ctx.info, None, density=ctx.density)
-            oy, ox, g_re = _sub_adjoint(res[1], res[2], res[3] if vel_in is not None else None, re, ctx.cfg_full, ctx.nsub)
-            return res[0], oy, ox, g_re, None, None, None, None, None, None, None, None, None
-        if ctx.buoyancy is not None:
-            gvy, gvx, gd = (None if g is None else g.contiguous() for g in (gvy, gvx, gd))
-            res = _large_bwd_buoy(inputs[0], svy, svx, re, gvy, gvx, gd, cfg, masks, ctx.buoyancy, vel_in, None, ctx.info, None)
-            oy, ox, g_re = _sub_adjoint(res[1], res[2], res[3] if vel_in is not None else None, re, ctx.cfg_full, ctx.nsub)
-            return res[0], oy, ox, g_re, None, None, None, None, None, None, None, None, None
-        if gvy is not None or gvx is not None:
-            oy, ox, g_re = _velocity_bwd(svy, svx, re, gvy, gvx, cfg, masks, ctx.info, vel_in)
-        if ctx.density and gd is not None:        # added onto the velocity half's buffers and g_re
-            if vel_in is None:
-                od, oy, ox = karman_density_bwd(inputs[0], svy, svx, re, gd, cfg, masks, oy, ox)
-            else:
-                od, oy, ox, g_re = karman_density_bwd_re(inputs[0], svy, svx, re, gd, *vel_in, cfg, masks, oy, ox, g_re)
-        oy, ox, g_re = _sub_adjoint(oy, ox, g_re, re, ctx.cfg_full, ctx.nsub)
-        return od, oy, ox, g_re, None, None, None, None, None, None, None, None, None
+        res = _step_adjoint("KarmanStepFn.backward", inputs[0] if ctx.density else None, svy, svx, re, gd, gvy, gvx, ctx.cfg, ctx.masks,
+                            ctx.physics, ctx.density, tuple(inputs[1:]) if ctx.want_re else None, info=ctx.info, fused=True)
+        return res + (None,) * 7
 
 
-def _step_mode(d, vy, vx, re, cfg, density_grad, re_grad, buoyancy=None):
+def _step_mode(d, vy, vx, re, cfg, density_grad, re_grad, ph=StepPhysics()):
     """(differentiable?, density, want_re) of a call of karman_step / karman_step_large, from its inputs as given and its two flags.
     re_grad with an `re` that requires no gradient is the plain mode.  A grid the staged adjoint does not take is refused here, before
     any device call."""
     needs = lambda t: isinstance(t, torch.Tensor) and t.requires_grad
-    density = bool(density_grad) or _buoyant(buoyancy)          # a force that moves the velocity: the density is always in the graph
+    density = bool(density_grad) or _buoyant(ph.buoyancy)          # a force that moves the velocity: the density is always in the graph
     want_re = bool(re_grad) and torch.is_grad_enabled() and needs(re)
     if want_re:
         _require_staged(cfg, "re_grad")
     return torch.is_grad_enabled() and (needs(vy) or needs(vx) or (density and needs(d)) or want_re), density, want_re
 
 
-def karman_step(d, vy, vx, re, cfg, masks, info=None, density_grad=False, re_grad=False, diffusion_substeps=1):
+def karman_step(d, vy, vx, re, cfg, masks, info=None, density_grad=False, re_grad=False, diffusion_substeps=1, physics=None):
     """One step on a one-workgroup grid.  density_grad=True (opt-in): the density output is differentiable too (KarmanStepFn's density
     mode), taken when any of d, vy, vx requires a gradient.  re_grad=True (opt-in): a tensor `re` that requires a gradient receives one
     (KarmanStepFn's re mode; grids with Y, X >= 16; composes with density_grad).  Without the flag `re` is data.
     diffusion_substeps = n > 1 (grids with Y, X >= 16): karman_diffuse_sub, then the fused kernel on diffusion_sub_cfg(cfg, n)."""
-    nsub = diffusion_substeps_arg(diffusion_substeps)
-    if nsub > 1:
-        _require_sub_grid(cfg, "karman_step")
+    ph = _physics(physics, "karman_step", diffusion_substeps=diffusion_substeps)
+    ph.require(cfg, masks, "karman_step")
     differentiable, density, want_re = _step_mode(d, vy, vx, re, cfg, density_grad, re_grad)
     if not differentiable:
-        return karman_step_saved(d, vy, vx, re, cfg, masks, None, info, diffusion_substeps=nsub)[0]
+        return karman_step_saved(d, vy, vx, re, cfg, masks, None, info, physics=ph)[0]
     _lib.require_gpu()
     d, vy, vx, re = (_lib.f32(t) for t in (d, vy, vx, re))
-    return KarmanStepFn.apply(d, vy, vx, re, cfg, masks, None, info, density, want_re, None, nsub)
+    return KarmanStepFn.apply(d, vy, vx, re, cfg, masks, None, info, density, want_re, ph)
 
 
 # --------------------------------------------------------------------------------------

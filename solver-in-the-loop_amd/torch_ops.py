@@ -56,7 +56,7 @@ def _karman_fwd_saved(d, vy, vx, re, scene):
 
 def _karman_bwd(svy, svx, re, gvy, gvx, scene):
     cfg, masks = _SCENES[scene]
-    return ops._velocity_bwd(svy.contiguous(), svx.contiguous(), _lib.f32(re), gvy, gvx, cfg, masks, None)[:2]
+    return ops._step_adjoint("torch.ops.sol.karman_step_bwd", None, svy, svx, re, None, gvy, gvx, cfg, masks, ops.StepPhysics(), False, fused=True)[1:3]
 
 
 def _karman_density_bwd(d, svy, svx, re, gd, scene):
@@ -64,43 +64,52 @@ def _karman_density_bwd(d, svy, svx, re, gd, scene):
     return ops.karman_density_bwd(d, svy, svx, re, gd, cfg, masks)
 
 
-def _karman_step(d, vy, vx, re, scene, density=False):
-    """no gradient wanted: the plain forward entry points, nothing kept"""
-    cfg, masks = _SCENES[scene]
-    with torch.no_grad():
-        return (ops.karman_step_large if masks.large else ops.karman_step)(d, vy, vx, re, cfg, masks)
-
-
 _LIB.impl("karman_step_fwd_saved", _karman_fwd_saved, "CUDA")
 _LIB.impl("karman_step_bwd", _karman_bwd, "CUDA")
 _LIB.impl("karman_density_bwd", _karman_density_bwd, "CUDA")
 
 
-# the step's three differentiable forms are the modes of ops.KarmanStepFn, the hand-written forward + backward pair: karman_step (the
-# density is a passive tracer, re is data), karman_step_dens (opt-in: the density output is differentiable too) and karman_step_re
-# (opt-in: differentiable with respect to re as well, grids with Y, X >= 16; density: d_out stays in the graph as in karman_step_dens)
-def _karman_fn(d, vy, vx, re, scene, density, want_re):
+# Every differentiable step op is one mode of ops.KarmanStepFn, the hand-written forward + backward pair, under one ops.StepPhysics:
+#   karman_step        the density is a passive tracer, re is data
+#   karman_step_dens   opt-in: the density output is differentiable too
+#   karman_step_re     opt-in: differentiable with respect to re as well (grids with Y, X >= 16); density: d_out stays in the graph
+#   karman_step_buoy   the buoyant step (large grids; a force of (0, 0) is the plain step, density in the graph)
+#   karman_step_sub    nsub explicit diffusion substeps (grids with Y, X >= 16), composing with density, re_grad and a force (fy, fx)
+#   karman_step_adv    the advection named per call (0 semi-Lagrangian, 1 MacCormack with correction strength s; large grids),
+#                      composing with all of them
+def _physics(scene, who, nsub=1, fy=0.0, fx=0.0, advection=0, s=1.0, keep_zero_force=False):
+    """(cfg, masks, StepPhysics) of an op's arguments, validated and checked against the scene's grid"""
     cfg, masks = _SCENES[scene]
-    if want_re:
-        ops._require_staged(cfg, "re_grad")
-    return ops.KarmanStepFn.apply(d, vy, vx, re, cfg, masks, None, None, density, want_re, None, 1)
+    if advection not in (0, 1):
+        raise ValueError("%s: advection must be 0 (semi_lagrangian) or 1 (mac_cormack), got %r" % (who, advection))
+    ph = ops.StepPhysics.of(buoyancy=(fy, fx), diffusion_substeps=nsub, advection=ops.ADVECTIONS[advection], correction_strength=s, who=who,
+                            keep_zero_force=keep_zero_force)
+    ph.require(cfg, masks, who)
+    return cfg, masks, ph.moving()
 
 
-# karman_step_buoy: the buoyant mode of ops.KarmanStepFn (large grids; a force of (0, 0) is the plain step, density in the graph)
-def _karman_buoy(d, vy, vx, re, scene, fy, fx, re_grad=False):
-    cfg, masks = _SCENES[scene]
+def _step(d, vy, vx, re, cfg, masks, ph):
+    """no gradient wanted: the plain forward entry points, nothing kept"""
     with torch.no_grad():
-        return ops.karman_step_large(d, vy, vx, re, cfg, masks, buoyancy=(float(fy), float(fx)))
+        return (ops.karman_step_large if masks.large else ops.karman_step)(d, vy, vx, re, cfg, masks, physics=ph)
 
 
-def _karman_buoy_fn(d, vy, vx, re, scene, fy, fx, re_grad=False):
-    cfg, masks = _SCENES[scene]
-    f = ops.buoyancy_force((fy, fx))
-    ops._require_large_for_buoyancy(masks, cfg.Y, cfg.X, "torch.ops.sol.karman_step_buoy")
-    want_re = bool(re_grad) and torch.is_grad_enabled() and re.requires_grad
+def _step_fn(d, vy, vx, re, cfg, masks, density, want_re, ph):
     if want_re:
         ops._require_staged(cfg, "re_grad")
-    return ops.KarmanStepFn.apply(d, vy, vx, re, cfg, masks, None, None, True, want_re, f if ops._buoyant(f) else None, 1)
+    return ops.KarmanStepFn.apply(d, vy, vx, re, cfg, masks, None, None, density, want_re, ph)
+
+
+def _want_re(re_grad, re):
+    return bool(re_grad) and torch.is_grad_enabled() and re.requires_grad
+
+
+def _karman_step(d, vy, vx, re, scene, density=False):
+    return _step(d, vy, vx, re, *_SCENES[scene], ops.StepPhysics())
+
+
+def _karman_fn(d, vy, vx, re, scene, density, want_re):
+    return _step_fn(d, vy, vx, re, *_SCENES[scene], density, want_re, ops.StepPhysics())
 
 
 for _op in ("karman_step", "karman_step_dens", "karman_step_re"):
@@ -109,73 +118,40 @@ _LIB.impl("karman_step", lambda d, vy, vx, re, scene: _karman_fn(d, vy, vx, re, 
 _LIB.impl("karman_step_dens", lambda d, vy, vx, re, scene: _karman_fn(d, vy, vx, re, scene, True, False), "AutogradCUDA")
 _LIB.impl("karman_step_re", lambda d, vy, vx, re, scene, density=False: _karman_fn(d, vy, vx, re, scene, bool(density), True), "AutogradCUDA")
 
-_LIB.impl("karman_step_buoy", _karman_buoy, "CUDA")
-_LIB.impl("karman_step_buoy", _karman_buoy_fn, "AutogradCUDA")
 
-
-# karman_step_sub: the step with nsub explicit diffusion substeps (ops.KarmanStepFn's substep mode; grids with Y, X >= 16), composing
-# with the other modes: density (d_out in the graph), re_grad, and on large grids a buoyancy force (fy, fx)
-def _karman_sub_args(scene, nsub, fy, fx):
+def _karman_buoy(d, vy, vx, re, scene, fy, fx, re_grad=False):
     cfg, masks = _SCENES[scene]
-    n = ops.diffusion_substeps_arg(nsub, "torch.ops.sol.karman_step_sub: nsub")
-    if n > 1:
-        ops._require_sub_grid(cfg, "torch.ops.sol.karman_step_sub")
-    f = ops.buoyancy_force((fy, fx))
-    f = f if ops._buoyant(f) else None
-    if f is not None:
-        ops._require_large_for_buoyancy(masks, cfg.Y, cfg.X, "torch.ops.sol.karman_step_sub")
-    return cfg, masks, n, f
+    with torch.no_grad():            # (a force of (0, 0) is kept: the buoyant entry point takes it)
+        return ops.karman_step_large(d, vy, vx, re, cfg, masks, buoyancy=(float(fy), float(fx)))
+
+
+def _karman_buoy_fn(d, vy, vx, re, scene, fy, fx, re_grad=False):
+    cfg, masks, ph = _physics(scene, "torch.ops.sol.karman_step_buoy", 1, fy, fx, keep_zero_force=True)      # (a small grid is refused whatever the force)
+    return _step_fn(d, vy, vx, re, cfg, masks, True, _want_re(re_grad, re), ph)
 
 
 def _karman_sub(d, vy, vx, re, scene, nsub, density=False, re_grad=False, fy=0.0, fx=0.0):
-    cfg, masks, n, f = _karman_sub_args(scene, nsub, fy, fx)
-    with torch.no_grad():
-        if masks.large:
-            return ops.karman_step_large(d, vy, vx, re, cfg, masks, buoyancy=f, diffusion_substeps=n)
-        return ops.karman_step(d, vy, vx, re, cfg, masks, diffusion_substeps=n)
+    return _step(d, vy, vx, re, *_physics(scene, "torch.ops.sol.karman_step_sub", nsub, fy, fx))
 
 
 def _karman_sub_fn(d, vy, vx, re, scene, nsub, density=False, re_grad=False, fy=0.0, fx=0.0):
-    cfg, masks, n, f = _karman_sub_args(scene, nsub, fy, fx)
-    want_re = bool(re_grad) and torch.is_grad_enabled() and re.requires_grad
-    if want_re:
-        ops._require_staged(cfg, "re_grad")
-    return ops.KarmanStepFn.apply(d, vy, vx, re, cfg, masks, None, None, bool(density), want_re, f, n)
-
-
-_LIB.impl("karman_step_sub", _karman_sub, "CUDA")
-_LIB.impl("karman_step_sub", _karman_sub_fn, "AutogradCUDA")
-
-
-# karman_step_adv: the step with the advection named per call (0 semi-Lagrangian, 1 MacCormack with correction strength s; ops.KarmanStepFn's
-# adv mode, large grids), composing with every other mode: nsub diffusion substeps, density, re_grad, a buoyancy force (fy, fx)
-def _karman_adv_args(scene, advection, s, nsub, fy, fx, who="torch.ops.sol.karman_step_adv"):
-    if advection not in (0, 1):
-        raise ValueError("%s: advection must be 0 (semi_lagrangian) or 1 (mac_cormack), got %r" % (who, advection))
-    adv = ops.advection_arg(ops.ADVECTIONS[advection], s, who + ": advection")
-    cfg, masks, n, f = _karman_sub_args(scene, nsub, fy, fx)
-    if adv is not None:
-        ops._require_large_for_advection(masks, cfg.Y, cfg.X, who)
-    kw = {} if adv is None else {"advection": "mac_cormack", "correction_strength": adv}
-    return cfg, masks, n, f, adv, kw
+    cfg, masks, ph = _physics(scene, "torch.ops.sol.karman_step_sub", nsub, fy, fx)
+    return _step_fn(d, vy, vx, re, cfg, masks, bool(density), _want_re(re_grad, re), ph)
 
 
 def _karman_adv(d, vy, vx, re, scene, advection, s=1.0, nsub=1, density=False, re_grad=False, fy=0.0, fx=0.0):
-    cfg, masks, n, f, adv, kw = _karman_adv_args(scene, advection, s, nsub, fy, fx)
-    with torch.no_grad():
-        if masks.large:
-            return ops.karman_step_large(d, vy, vx, re, cfg, masks, buoyancy=f, diffusion_substeps=n, **kw)
-        return ops.karman_step(d, vy, vx, re, cfg, masks, diffusion_substeps=n)
+    return _step(d, vy, vx, re, *_physics(scene, "torch.ops.sol.karman_step_adv", nsub, fy, fx, advection, s))
 
 
 def _karman_adv_fn(d, vy, vx, re, scene, advection, s=1.0, nsub=1, density=False, re_grad=False, fy=0.0, fx=0.0):
-    cfg, masks, n, f, adv, kw = _karman_adv_args(scene, advection, s, nsub, fy, fx)
-    want_re = bool(re_grad) and torch.is_grad_enabled() and re.requires_grad
-    if want_re:
-        ops._require_staged(cfg, "re_grad")
-    return ops.KarmanStepFn.apply(d, vy, vx, re, cfg, masks, None, None, bool(density), want_re, f, n, adv)
+    cfg, masks, ph = _physics(scene, "torch.ops.sol.karman_step_adv", nsub, fy, fx, advection, s)
+    return _step_fn(d, vy, vx, re, cfg, masks, bool(density), _want_re(re_grad, re), ph)
 
 
+_LIB.impl("karman_step_buoy", _karman_buoy, "CUDA")
+_LIB.impl("karman_step_buoy", _karman_buoy_fn, "AutogradCUDA")
+_LIB.impl("karman_step_sub", _karman_sub, "CUDA")
+_LIB.impl("karman_step_sub", _karman_sub_fn, "AutogradCUDA")
 _LIB.impl("karman_step_adv", _karman_adv, "CUDA")
 _LIB.impl("karman_step_adv", _karman_adv_fn, "AutogradCUDA")
 

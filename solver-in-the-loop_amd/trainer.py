@@ -69,7 +69,7 @@ def _refuse_large_grid(who, Y, X):
 def _refuse_buoyancy(who, buoyancy):
     """SolTrainer and GraphTrainer run the fused one-workgroup solver kernels, which have no buoyancy term: a non-zero force is refused
     at construction (LargeGridTrainer(buoyancy=...) trains with it on a large grid).  -> None"""
-    if ops._buoyant(ops.buoyancy_force(buoyancy)):
+    if ops.StepPhysics.of(buoyancy=buoyancy, who=who).buoyancy is not None:
         raise ValueError("%s: buoyancy=%r -- the buoyancy force is built on the multi-launch (large-grid) solver step only; this trainer "
                          "runs the fused one-workgroup kernels.  Train with it on a large grid (LargeGridTrainer)" % (who, buoyancy))
     return None
@@ -78,7 +78,7 @@ def _refuse_buoyancy(who, buoyancy):
 def _refuse_advection(who, advection, correction_strength=1.0):
     """SolTrainer, GraphTrainer and SolRollout run the fused one-workgroup solver kernels, which advect semi-Lagrangian: "mac_cormack" is
     refused at construction (LargeGridTrainer / LargeGridRollout take it on a large grid).  -> None"""
-    if ops.advection_arg(advection, correction_strength, "%s: advection" % who) is not None:
+    if ops.StepPhysics.of(advection=advection, correction_strength=correction_strength, who=who).adv is not None:
         raise ValueError("%s: advection=%r -- the mac_cormack advection is built on the multi-launch (large-grid) solver step only; this "
                          "class runs the fused one-workgroup kernels.  Use it on a large grid (LargeGridTrainer / LargeGridRollout)"
                          % (who, advection))
@@ -89,7 +89,7 @@ def _refuse_substeps(who, diffusion_substeps, Y, X):
     """SolTrainer, GraphTrainer and SolRollout run a solver step that lives inside the library's own schedule (the fused one-workgroup
     kernels, the C-side graph): there is no place for the pre-diffusion launch.  diffusion_substeps > 1 is refused at construction
     (LargeGridTrainer / LargeGridRollout take it on a large grid; KarmanFlow.step on every grid with Y, X >= 16).  -> 1"""
-    if ops.diffusion_substeps_arg(diffusion_substeps, "%s: diffusion_substeps" % who) > 1:
+    if ops.StepPhysics.of(diffusion_substeps=diffusion_substeps, who=who).nsub > 1:
         raise ValueError("%s: diffusion_substeps=%d -- diffusion substeps are built on the multi-launch (large-grid) trainers and roll-out "
                          "only; on a %dx%d grid this class runs the fused one-workgroup solver step inside the library's own schedule.  "
                          "Use LargeGridTrainer / LargeGridRollout on a large grid, or KarmanFlow(diffusion_substeps=...).step"
@@ -330,11 +330,9 @@ class LargeGridRollout:
         diffusion_substeps=n: n explicit diffusion substeps per solver step (ops.karman_step_large(diffusion_substeps=n): the
         pre-diffusion launches are part of the captured step).  advection="mac_cormack", correction_strength=s: the solver step advects
         by the MacCormack scheme (sol_karman_step_fwd_large_adv; captured with the rest)."""
-        self.diffusion_substeps = ops.diffusion_substeps_arg(diffusion_substeps, "LargeGridRollout: diffusion_substeps")
-        adv = ops.advection_arg(advection, correction_strength, "LargeGridRollout: advection")
-        self.advection = {} if adv is None else {"advection": "mac_cormack", "correction_strength": adv}
-        f = ops.buoyancy_force(buoyancy)
-        self.buoyancy = f if ops._buoyant(f) else None
+        ph = self.physics = ops.StepPhysics.of(buoyancy=buoyancy, diffusion_substeps=diffusion_substeps, advection=advection,
+                                               correction_strength=correction_strength, who="LargeGridRollout")
+        self.buoyancy, self.diffusion_substeps, self.advection = ph.buoyancy, ph.nsub, ph.advection_kw
         if not ops.beyond_one_workgroup(Y, X):
             raise ValueError("LargeGridRollout: a %dx%d domain is served by the one-workgroup roll-out -- use SolRollout (make_rollout picks)" % (Y, X))
         if X % 64 != 0 and not any_width:
@@ -368,7 +366,7 @@ class LargeGridRollout:
         self._feat = z(B, Y, X, 4)
         self._cor = (z(B, Y + 1, X), z(B, Y, X + 1))
         self.p_guess = z(B, Y, X) if self.cg_warm_start else None
-        nbytes = ops.large_adv_workspace_bytes(self.cfg, masks) if self.advection else ops.large_workspace_bytes(self.cfg, masks)
+        nbytes = ops.large_workspace_bytes(self.cfg, masks, ph)
         self._ws = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=dev)
         self.solve_info = {}
         self._info = []
@@ -381,8 +379,7 @@ class LargeGridRollout:
     def _step(self):
         info = {}
         ops.karman_step_large(*self._a, self._re, self.cfg, self.masks, self._ws, info, feat=self._feat, feat_scale=self._fs3,
-                              p_guess=self.p_guess, out=self._b, buoyancy=self.buoyancy, diffusion_substeps=self.diffusion_substeps,
-                              **self.advection)
+                              p_guess=self.p_guess, out=self._b, physics=self.physics)
         out, _ = self._sched.forward(self._feat)
         ops.karman_correct(out, self._b[1], self._b[2], self._so, self._cor)
         _lib.dcopy_(self._flat[0], self._flat[1])
@@ -430,11 +427,12 @@ def make_rollout(net, masks, B, Y, X, dx, std_v, std_re, **kw):
         return LargeGridRollout(net, masks, B, Y, X, dx, std_v, std_re, **kw)
     for k in ("use_graph", "cg_warm_start", "any_width"):
         kw.pop(k, None)
-    if ops._buoyant(ops.buoyancy_force(kw.pop("buoyancy", None))):
+    ph = ops.StepPhysics.of(**{k: kw.pop(k) for k in ("buoyancy", "advection", "correction_strength") if k in kw}, who="make_rollout")
+    if ph.buoyancy is not None:
         raise ValueError("make_rollout: the buoyancy force is built on the multi-launch (large-grid) solver step only; a %dx%d grid runs "
                          "the one-workgroup roll-out (SolRollout), which has no buoyancy term" % (Y, X))
     kw["diffusion_substeps"] = _refuse_substeps("make_rollout", kw.get("diffusion_substeps", 1), Y, X)
-    if ops.advection_arg(kw.pop("advection", "semi_lagrangian"), kw.pop("correction_strength", 1.0), "make_rollout: advection") is not None:
+    if ph.adv is not None:
         raise ValueError("make_rollout: the mac_cormack advection is built on the multi-launch (large-grid) solver step only; a %dx%d grid "
                          "runs the one-workgroup roll-out (SolRollout), which advects semi-Lagrangian" % (Y, X))
     return SolRollout(net, masks, B, Y, X, dx, std_v, std_re, **kw)
@@ -468,9 +466,9 @@ class GraphTrainer(_AdamDP):
         self._sched = None
         self._cg_fwd, self._cg_bwd = [], []       # what the solver launches of a step report (LargeGridTrainer, CG scenes)
         self._check_grid(Y, X)
-        self.buoyancy = self._check_buoyancy(buoyancy)
-        self.diffusion_substeps = self._check_substeps(diffusion_substeps, Y, X)
-        self.advection = self._check_advection(advection, correction_strength)      # {} or the two keywords of the large-grid solver pair
+        ph = self.physics = self._check_physics(Y, X, buoyancy=buoyancy, diffusion_substeps=diffusion_substeps, advection=advection,
+                                                correction_strength=correction_strength)
+        self.buoyancy, self.diffusion_substeps, self.advection = ph.buoyancy, ph.nsub, ph.advection_kw
         from . import fluid, karman
         _lib.require_gpu()
         self.lib = _lib.load()
@@ -512,17 +510,12 @@ class GraphTrainer(_AdamDP):
         _refuse_large_grid("GraphTrainer", Y, X)
 
     @staticmethod
-    def _check_buoyancy(buoyancy):
-        return _refuse_buoyancy("GraphTrainer", buoyancy)
-
-    @staticmethod
-    def _check_substeps(diffusion_substeps, Y, X):
-        return _refuse_substeps("GraphTrainer", diffusion_substeps, Y, X)
-
-    @staticmethod
-    def _check_advection(advection, correction_strength):
+    def _check_physics(Y, X, buoyancy, diffusion_substeps, advection, correction_strength):
+        """-> the ops.StepPhysics of the solver pair: here the plain one, everything else refused"""
+        _refuse_buoyancy("GraphTrainer", buoyancy)
+        _refuse_substeps("GraphTrainer", diffusion_substeps, Y, X)
         _refuse_advection("GraphTrainer", advection, correction_strength)
-        return {}
+        return ops.StepPhysics()
 
     def _unrolled(self):
         if self.schedule == "manual":
@@ -680,17 +673,13 @@ class LargeGridTrainer(GraphTrainer):
         """any_width=True: X need not be a multiple of 64 -- the network's forward and reverse launches run in pitched rows of
         64 * ceil(X / 64) pixels (NetSchedule2D(any_width=True): column-masked convolutions, the weight gradient at the pitch); the solver
         pair, the correction and the loss stay dense.
-        buoyancy=(fy, fx) (keyword; ops.buoyancy_force): the density pushes the velocity.  The schedule is unchanged; the solver pair is the
-        buoyant one: _solver_fwd = ops.karman_step_saved(buoyancy=...) and also keeps each step's input density, _solver_bwd =
-        ops.karman_step_large_bwd_buoy (the buoyant velocity adjoint, then the density adjoint), which carries g_d_in to the next (earlier)
+        buoyancy, diffusion_substeps, advection, correction_strength (keywords): the physics of the solver pair, one ops.StepPhysics
+        (which describes them) built at construction and passed to ops.karman_step_saved and ops.karman_step_large_bwd(_buoy) at every
+        step; the schedule is unchanged, the pre-diffusion launches are part of the (captured) schedule and the workspaces are sized
+        here, so a captured step allocates nothing.  With a force _solver_fwd also keeps each step's input density and _solver_bwd =
+        ops.karman_step_large_bwd_buoy (the buoyant velocity adjoint, then the density adjoint) carries g_d_in to the next (earlier)
         step as that step's g_d_out.  The loss looks at the velocity only, so the last step's g_d_out is zero; the carried gradient is
-        reset at the head of every run, so a replayed graph is self-contained.
-        diffusion_substeps=n (keyword): n explicit diffusion substeps per solver step -- _solver_fwd / _solver_bwd pass it to
-        ops.karman_step_saved and ops.karman_step_large_bwd(_buoy): the pre-diffusion launches on the input velocity and on the adjoint's
-        result are part of the (captured) schedule.
-        advection="mac_cormack", correction_strength=s (keywords): the solver pair advects by the MacCormack scheme --
-        ops.karman_step_saved and ops.karman_step_large_bwd(_buoy) with the same keywords (the _adv entry points; their workspaces are
-        sized here, so a captured step allocates nothing)."""
+        reset at the head of every run, so a replayed graph is self-contained."""
         if any_width and kw.get("schedule", "manual") == "autograd":
             raise ValueError("LargeGridTrainer: any_width=True runs the hand-written schedule only; schedule='autograd' (the composition "
                              "over ops.conv5x5) takes no pitched rows")
@@ -710,30 +699,18 @@ class LargeGridTrainer(GraphTrainer):
     _adjoint_of_first_step = False
 
     @staticmethod
-    def _check_buoyancy(buoyancy):
-        f = ops.buoyancy_force(buoyancy)
-        return f if ops._buoyant(f) else None
-
-    @staticmethod
-    def _check_substeps(diffusion_substeps, Y, X):
-        return ops.diffusion_substeps_arg(diffusion_substeps, "LargeGridTrainer: diffusion_substeps")
-
-    @staticmethod
-    def _check_advection(advection, correction_strength):
-        adv = ops.advection_arg(advection, correction_strength, "LargeGridTrainer: advection")
-        return {} if adv is None else {"advection": "mac_cormack", "correction_strength": adv}
+    def _check_physics(Y, X, **keywords):
+        return ops.StepPhysics.of(who="LargeGridTrainer", **keywords)
 
     def _schedule_setup(self):
         super()._schedule_setup()
-        cfg, mk, dev = self._kcfg, self._mk, self.device
+        cfg, mk, dev, ph = self._kcfg, self._mk, self.device, self.physics
         self._d_in, self._g_d = [], None                    # buoyant mode: the steps' input densities; the carried density gradient
-        mc = bool(self.advection)
-        if self.buoyancy is not None:
-            nd = ops.density_bwd_adv_workspace_bytes(cfg) if mc else ops.density_bwd_workspace_bytes(cfg)
-            self._ws_bwd_d = torch.empty((int(nd) + 3) // 4, dtype=torch.float32, device=dev)
         ws = lambda n: torch.empty((int(n) + 3) // 4, dtype=torch.float32, device=dev)
-        self._ws_fwd = ws(ops.large_adv_workspace_bytes(cfg, mk, True) if mc else ops.large_workspace_bytes(cfg, mk))
-        self._ws_bwd = ws(ops.large_bwd_adv_workspace_bytes(cfg, mk) if mc else ops.large_bwd_workspace_bytes(cfg, mk))
+        if self.buoyancy is not None:
+            self._ws_bwd_d = ws(ops.density_bwd_workspace_bytes(cfg, ph))
+        self._ws_fwd = ws(ops.large_workspace_bytes(cfg, mk, ph, saved=True))
+        self._ws_bwd = ws(ops.large_bwd_workspace_bytes(cfg, mk, ph))
         self._zplane = torch.zeros(self.B, self.Y, self.X, dtype=torch.float32, device=dev)      # the fourth (padding) input channel
         self.pressure_solver_used = mk.pressure_solver
 
@@ -745,8 +722,7 @@ class LargeGridTrainer(GraphTrainer):
         info = {}
         if self.buoyancy is not None:
             self._d_in.append(d)
-        (d2, vy2, vx2), svy, svx = ops.karman_step_large_saved(d, vy, vx, re, self._kcfg, self._mk, self._ws_fwd, info, self.buoyancy,
-                                                                         self.diffusion_substeps, **self.advection)
+        (d2, vy2, vx2), svy, svx = ops.karman_step_large_saved(d, vy, vx, re, self._kcfg, self._mk, self._ws_fwd, info, physics=self.physics)
         self._cg_fwd.append(info)
         # to_feature / in_std (karman_train.py:77-86, 413-416), padded to the four channels the first layer's kernels read
         feat = torch.stack([vy2[:, :Y] * fs[0], vx2[:, :, :X] * fs[1], self._re_plane, self._zplane], dim=-1)
@@ -763,10 +739,9 @@ class LargeGridTrainer(GraphTrainer):
             d_in = self._d_in.pop()
             self._g_d, oy, ox = ops.karman_step_large_bwd_buoy(d_in, svy, svx, re, G[0], G[1], self._g_d, self._kcfg, self._mk, self.buoyancy,
                                                                workspace=self._ws_bwd, info=info, density_workspace=self._ws_bwd_d,
-                                                               diffusion_substeps=self.diffusion_substeps, **self.advection)
+                                                               physics=self.physics)
             return oy, ox
-        return ops.karman_step_large_bwd(svy, svx, re, G[0], G[1], self._kcfg, self._mk, workspace=self._ws_bwd, info=info,
-                                         diffusion_substeps=self.diffusion_substeps, **self.advection)
+        return ops.karman_step_large_bwd(svy, svx, re, G[0], G[1], self._kcfg, self._mk, workspace=self._ws_bwd, info=info, physics=self.physics)
 
     def _fwd_bwd(self, *a, **kw):
         loss = super()._fwd_bwd(*a, **kw)

@@ -85,6 +85,48 @@ def test_a_null_cfg_sizes_to_zero():
         assert getattr(lib, f)(None, None) == 0, f
 
 
+def test_the_adv_size_functions_with_advection_0_return_the_plain_bytes_and_the_three_python_sizers_select_by_mode():
+    """ops.large_workspace_bytes / large_bwd_workspace_bytes / density_bwd_workspace_bytes are served by the _adv size functions in every
+    mode: with advection = 0 those must return the plain functions' bytes, for a direct, a scattered-direct and a CG cfg at the three
+    ragged shapes of the large-grid tests.  (The SAVED _adv form with advection = 0 is smaller than the plain step's scratch, which the
+    plain saved step is sized with: the Python sizer takes it under mac_cormack only.)"""
+    import types
+    lib = sol_amd.load()
+    hp = lambda h: None if h is None else h.ctypes.data_as(C.c_void_p)
+    mc = ops.StepPhysics.of(advection="mac_cormack", correction_strength=0.5)
+    for Y, X in ((130, 65), (144, 72), (160, 80)):
+        hs = headers_2d(Y, X)
+        for name in ("fd02_win16", "fd02_win64", "fds1_rp60_cp76", "fds1_rp16_cp12", "none"):
+            h = hs[name]
+            cfg = ops.karman_cfg(2, Y, X, 100.0 / X)
+            if h is not None:
+                cfg.direct, cfg.direct_n = FAKE, 1 << 30
+            r, where = C.byref(cfg), (Y, X, name)
+            mk = types.SimpleNamespace(direct_header=h, direct=None if h is None else FAKE)
+            plain_fwd = lib.sol_karman_step_large_cg_workspace_bytes(r) if h is None else lib.sol_karman_step_large_workspace_bytes_for(r, hp(h))
+            plain_bwd, plain_bwd_re = lib.sol_karman_step_bwd_large_workspace_bytes_for(r, hp(h)), lib.sol_karman_step_bwd_large_re_workspace_bytes_for(r, hp(h))
+            plain_d, plain_d_re = lib.sol_karman_density_bwd_workspace_bytes(r), lib.sol_karman_density_bwd_re_workspace_bytes(r)
+            assert min(plain_fwd, plain_bwd, plain_d) > 0, where
+            # the C side: advection = 0 is the plain layout
+            assert lib.sol_karman_step_fwd_large_adv_workspace_bytes_for(r, hp(h), 0) == plain_fwd, where
+            assert lib.sol_karman_step_bwd_large_adv_workspace_bytes_for(r, hp(h), 0, 0) == plain_bwd, where
+            assert lib.sol_karman_step_bwd_large_adv_workspace_bytes_for(r, hp(h), 1, 0) == plain_bwd_re, where
+            assert lib.sol_karman_density_bwd_adv_workspace_bytes(r, 0, 0) == plain_d, where
+            assert lib.sol_karman_density_bwd_adv_workspace_bytes(r, 1, 0) == plain_d_re, where
+            # the Python sizers: called as ever, and with a physics value that advects semi-Lagrangian, the plain bytes in every form
+            for ph in (None, ops.StepPhysics(), ops.StepPhysics((0.3, -0.2), 2, None)):
+                kw = {} if ph is None else {"physics": ph}
+                assert ops.large_workspace_bytes(cfg, mk, **kw) == ops.large_workspace_bytes(cfg, mk, saved=True, **kw) == plain_fwd, where
+                assert ops.large_bwd_workspace_bytes(cfg, mk, **kw) == plain_bwd and ops.large_bwd_workspace_bytes(cfg, mk, re=True, **kw) == plain_bwd_re, where
+                assert ops.density_bwd_workspace_bytes(cfg, **kw) == plain_d and ops.density_bwd_workspace_bytes(cfg, re=True, **kw) == plain_d_re, where
+            # ... and under mac_cormack the _adv functions' own
+            assert ops.large_workspace_bytes(cfg, mk, mc) == lib.sol_karman_step_fwd_large_adv_workspace_bytes_for(r, hp(h), 1) > plain_fwd, where
+            assert ops.large_workspace_bytes(cfg, mk, mc, saved=True) == lib.sol_karman_step_fwd_large_saved_adv_workspace_bytes_for(r, hp(h), 1), where
+            for re in (0, 1):
+                assert ops.large_bwd_workspace_bytes(cfg, mk, mc, re=bool(re)) == lib.sol_karman_step_bwd_large_adv_workspace_bytes_for(r, hp(h), re, 1), where
+                assert ops.density_bwd_workspace_bytes(cfg, mc, re=bool(re)) == lib.sol_karman_density_bwd_adv_workspace_bytes(r, re, 1), where
+
+
 if __name__ == "__main__":
     if "--record" not in sys.argv:
         sys.exit(__doc__)

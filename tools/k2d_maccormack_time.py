@@ -76,7 +76,8 @@ def main():
     re = torch.tensor([o.RE_TRAIN[0], o.RE_TRAIN[1]], dtype=torch.float32, device="cuda")
     gd, gy, gx = rn(B, Y, X).cuda(), rn(B, Y + 1, X).cuda(), rn(B, Y, X + 1).cuda()
     ws = lambda n: torch.empty((int(n) + 3) // 4, dtype=torch.float32, device="cuda")
-    ws_f, ws_b, ws_d = ws(ops.large_adv_workspace_bytes(cfg, mk, True)), ws(ops.large_bwd_adv_workspace_bytes(cfg, mk)), ws(ops.density_bwd_adv_workspace_bytes(cfg))
+    ph = ops.StepPhysics.of(**MC)
+    ws_f, ws_b, ws_d = ws(ops.large_workspace_bytes(cfg, mk, ph, saved=True)), ws(ops.large_bwd_workspace_bytes(cfg, mk, ph)), ws(ops.density_bwd_workspace_bytes(cfg, ph))
     out = {"tool": "k2d_maccormack_time", "grid": [Y, X], "B": B, "solver": mk.pressure_solver, "reps": reps, "calls_per_window": ROUND,
            "device": torch.cuda.get_device_name(0)}
     with torch.no_grad():
@@ -102,7 +103,7 @@ def main():
         out["step"] = r
         # the stage alone: tiled against two launches
         act, infl = mk.active, mk.inflow
-        ws_a = ws(ops.large_adv_workspace_bytes(cfg, mk))          # (holds the stage's part and more)
+        ws_a = ws(ops.large_workspace_bytes(cfg, mk, ph))        # (holds the stage's part and more)
 
         def two():
             _lib.set_option("k2d_mc_tile", 0)

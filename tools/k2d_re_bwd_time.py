@@ -79,8 +79,8 @@ def main():
     # 256 x 128, B = 2: the _re adjoints against the plain ones
     Y, X, B = 256, 128, 2
     mk, cfg, re, st, svy, svx, w = scene(Y, X, B)
-    ws_v = torch.empty((ops.large_bwd_re_workspace_bytes(cfg, mk) + 3) // 4, dtype=torch.float32, device=DEV)
-    ws_d = torch.empty((ops.density_bwd_re_workspace_bytes(cfg) + 3) // 4, dtype=torch.float32, device=DEV)
+    ws_v = torch.empty((ops.large_bwd_workspace_bytes(cfg, mk, re=True) + 3) // 4, dtype=torch.float32, device=DEV)
+    ws_d = torch.empty((ops.density_bwd_workspace_bytes(cfg, re=True) + 3) // 4, dtype=torch.float32, device=DEV)
     vel = lambda: ops.karman_step_large_bwd(svy, svx, re, w[1], w[2], cfg, mk, ws_v)
     vel_re = lambda: ops.karman_step_large_bwd_re(svy, svx, re, w[1], w[2], st[1], st[2], cfg, mk, workspace=ws_v)
     dens = lambda: ops.karman_density_bwd(st[0], svy, svx, re, w[0], cfg, mk, workspace=ws_d)
@@ -101,7 +101,7 @@ def main():
     # 64 x 32, B = 3: the staged adjoint (re_grad) against the fused one-workgroup adjoint (the default)
     Y, X, B = 64, 32, 3
     mk, cfg, re, st, svy, svx, w = scene(Y, X, B)
-    ws_s = torch.empty((ops.large_bwd_re_workspace_bytes(cfg, mk) + 3) // 4, dtype=torch.float32, device=DEV)
+    ws_s = torch.empty((ops.large_bwd_workspace_bytes(cfg, mk, re=True) + 3) // 4, dtype=torch.float32, device=DEV)
     staged = lambda: ops.karman_step_large_bwd_re(svy, svx, re, w[1], w[2], st[1], st[2], cfg, mk, workspace=ws_s)
     fused = lambda: ops._step_bwd(svy, svx, re, w[1], w[2], cfg, mk, None)
     small = {"grid": [Y, X], "B": B, "solver": mk.pressure_solver}
