@@ -63,7 +63,8 @@ class KarmanGeometry:
 
     def __post_init__(self):
         Y, X = self.Y, self.X
-        assert Y == 2 * X, "reference domain is box[0:2*len, 0:len] with res (2*res, res)"
+        # the reference domain is box[0:2*len, 0:len] with res (2*res, res); any other (Y, X) keeps dx = len / X and the physical
+        # definitions of the inflow box, the sphere and the velocity BC: the domain is then [0, Y dx] x [0, X dx]
         self.dx = self.length / X
         yc = (np.arange(Y) + 0.5) * self.dx
         xc = (np.arange(X) + 0.5) * self.dx

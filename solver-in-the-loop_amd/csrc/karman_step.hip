@@ -531,6 +531,10 @@ struct FdView {
 constexpr int FD_Y = 128, FD_X = 64, FD_LD = 65, FD_WIN = 16, FD_ULD = 17;
 constexpr int FD_BUF = FD_Y * FD_LD;   // floats per transform buffer
 constexpr int FD_QYS = 32;             // VGPRs of the wave's Qy coefficient slice (fd_load_ay), loaded at kernel start
+// the grid of the register-tiled fd_solve (its blob is indexed with FD_Y / FD_X strides); every other direct grid is fd_solve_small's.
+// The ONE place that tells the two apart: the host launches the SOLVER == 2 instantiations (fd_solve alone) where this holds and the
+// SOLVER == 3 ones (fd_solve_small alone, karman_step_small.hip) elsewhere; no kernel looks at Y or X to choose.
+inline bool fd_full_grid(int Y, int X) { return Y == FD_Y && X == FD_X; }
 
 __device__ __forceinline__ FdView fd_view(const float* __restrict__ blob) {
     const int* h = reinterpret_cast<const int*>(blob);
@@ -1023,8 +1027,10 @@ __device__ __forceinline__ void cell_coeffs(const Own& o, const unsigned char* a
 // ------------------------------------------------------------------------------------
 // forward
 // ------------------------------------------------------------------------------------
-// SOLVER: 0 = plain CG, 1 = two-level preconditioned CG, 2 = direct (fast diagonalisation); separate instantiations keep
-// each variant's register allocation independent (1 and 2 exist for the 16-cell strips only)
+// SOLVER: 0 = plain CG, 1 = two-level preconditioned CG, 2 = direct at 128 x 64 (fd_solve, register tiled), 3 = direct on small grids
+// (fd_solve_small, LDS resident); separate instantiations keep each variant's register allocation independent (1 and 2 exist for the
+// 16-cell strips only).  The SOLVER == 3 kernels are compiled in a translation unit of their own, karman_step_small.hip, which includes
+// this file with SOL_K2D_SMALL_TU defined and is built WITHOUT the iterative-ILP scheduler strategy: see karman_bwd_body.
 template <int CPT, int SOLVER>
 __device__ __forceinline__ void karman_fwd_body(const StepArgs& a, float* smem) {
     const int b = blockIdx.x, tid = threadIdx.x, nthr = blockDim.x;
@@ -1035,10 +1041,8 @@ __device__ __forceinline__ void karman_fwd_body(const StepArgs& a, float* smem) 
 
     SOL_STAMP(0);
     float fdp = 0.f;
-    if constexpr (SOLVER == 2) {
-        if (Y == FD_Y) fdp = fd_prefetch(a.fd, a.fd_n);
-        else fd_small_stage(a.fd, Y, X, L.fdx);
-    }
+    if constexpr (SOLVER == 2) fdp = fd_prefetch(a.fd, a.fd_n);
+    else if constexpr (SOLVER == 3) fd_small_stage(a.fd, Y, X, L.fdx);
     // ---- phase 1: load inputs (all global loads in flight before the first LDS store) ---
     // 16-byte loads: a dword load costs the texture path as much per wave as a dwordx4 one, and this phase is nothing else
     // (X, Y are multiples of 4, so every array and every batch offset is 16-byte aligned and a v_y quad stays in one row)
@@ -1164,7 +1168,7 @@ __device__ __forceinline__ void karman_fwd_body(const StepArgs& a, float* smem) 
     float qys[FD_QYS];              // direct solver: this wave's slice of Qy (L2-warm: fd_prefetch), in flight behind the setup
 #pragma unroll
     for (int j = 0; j < FD_QYS; ++j) qys[j] = 0.f;
-    if constexpr (SOLVER == 2 && CPT == 16) { if (Y == FD_Y) fd_load_qys(a.fd + 16, __builtin_amdgcn_readfirstlane(tid >> 6), qys); }
+    if constexpr (SOLVER == 2) fd_load_qys(a.fd + 16, __builtin_amdgcn_readfirstlane(tid >> 6), qys);
     const Own o = ownership<CPT>(Y, X);
     float dg[CPT], ac[CPT], r[CPT], x[CPT];
     cell_coeffs<CPT>(o, L.act, Y, X, dg, ac);
@@ -1180,9 +1184,10 @@ __device__ __forceinline__ void karman_fwd_body(const StepArgs& a, float* smem) 
     int it = 0;
     float* Pfd = nullptr;           // direct solver: the solution arrives as an LDS array
     SOL_STAMP(5);
-    if constexpr (SOLVER == 2) {            // host guarantees 128 x 64 (register-tiled) or a small grid (LDS resident)
-        if constexpr (CPT == 16) Pfd = Y == FD_Y ? fd_solve(a.fd, qys, L.Bvy, r, a.prof) : fd_solve_small<CPT>(a.fd, Y, X, o, L.fdx, r);
-        else Pfd = fd_solve_small<CPT>(a.fd, Y, X, o, L.fdx, r);
+    if constexpr (SOLVER == 2) {            // the host launches these instantiations at fd_full_grid(Y, X) only
+        Pfd = fd_solve(a.fd, qys, L.Bvy, r, a.prof);
+    } else if constexpr (SOLVER == 3) {
+        Pfd = fd_solve_small<CPT>(a.fd, Y, X, o, L.fdx, r);
     } else if constexpr (SOLVER == 1) {
         it = X == 64 ? pcg_solve<CPT, true, 32>(o, Y, X, L.act, dg, ac, r, x, L.E, L.red, L.cs, a.cinv, a.rtol2, a.atol2, a.max_iter)
                      : pcg_solve<CPT, false, 8>(o, Y, X, L.act, dg, ac, r, x, L.E, L.red, L.cs, a.cinv, a.rtol2, a.atol2, a.max_iter);
@@ -1195,7 +1200,7 @@ __device__ __forceinline__ void karman_fwd_body(const StepArgs& a, float* smem) 
 
     // ---- phase 6: v -= mask * grad p ;  outputs --------------------------------------
     float* P = L.Bvy;   // region B is free after the advection
-    if constexpr (SOLVER == 2) P = Pfd;
+    if constexpr (SOLVER >= 2) P = Pfd;
     else {
         if (o.owner) {
 #pragma unroll
@@ -1305,12 +1310,14 @@ __device__ __forceinline__ void density_step_body(const DensStep& q, int b) {
         q.d_out[(size_t)b * N + k] = v;
     }
 }
+#ifndef SOL_K2D_SMALL_TU
 __global__ void __launch_bounds__(512) k_karman_fwd_dens(StepArgs a, DensStep q) {
     extern __shared__ __align__(16) float smem[];
     if ((int)blockIdx.x < a.B) karman_fwd_body<16, 2>(a, smem);
     else density_step_body(q, (int)blockIdx.x - a.B);
 }
 __global__ void __launch_bounds__(512) k_density_step(DensStep q) { density_step_body(q, blockIdx.x); }
+#endif
 
 // ------------------------------------------------------------------------------------
 // forward, 128 x 64, direct solver: FOUR workgroups per simulation (round 6)
@@ -1652,6 +1659,7 @@ __device__ __forceinline__ void karman_fwd_solver_wg(const StepArgs& a, float* s
     if (fdp == 1.2345678e-30f && a.iters) a.iters[b] = -2;      // never true: keeps the prefetch loads alive
 }
 
+#ifndef SOL_K2D_SMALL_TU
 __global__ void __launch_bounds__(512) k_karman_fwd_bands(StepArgs a, DensStep q, unsigned* xch) {
     extern __shared__ __align__(16) float smem[];
     const int u = (int)blockIdx.x, nsol = 8 * (BD_N + 1) * ((a.B + 7) >> 3);
@@ -1662,11 +1670,21 @@ __global__ void __launch_bounds__(512) k_karman_fwd_bands(StepArgs a, DensStep q
         else karman_fwd_solver_wg(a, smem, b, xch + (size_t)b * BD_WORDS);
     } else density_step_body(q, u - nsol);
 }
+#endif
 
 // ------------------------------------------------------------------------------------
 // backward (adjoint w.r.t. the input velocity)
 // ------------------------------------------------------------------------------------
 // NT != 0: the body runs on the first NT threads of a larger workgroup whose other waves have ended (k_karman_bwd_bww_small)
+// OBSERVATION (tests/test_gpu_karman2d_small_shapes.py::test_direct_solve_with_16_cell_strips): while one instantiation <16, 2> held
+// fd_solve and fd_solve_small behind `Y == FD_Y`, and this file was built with `--amdgpu-sched-strategy=iterative-ilp`, the adjoint
+// missed the oracle's gradient by 0.2 .. 3 % on EVERY small direct grid under 16-cell strips (48 x 32: 1.2e-2 / 1.5e-2),
+// deterministically, while its forward twin and the 8-cell-strip adjoint -- the same fd_solve_small source -- read 3e-7.  The same
+// source built without the strategy was correct (3.1e-7 / 4.6e-7); with it, an extra __syncthreads() at the head of fd_solve_small made
+// the FORWARD wrong as well (v_x 4e-3), and asking `Y == FD_Y && X == FD_X` instead of `Y == FD_Y` moved the 8-cell-strip results
+// (see also bil_mix above).  Which instructions the strategy misplaces is not known.  So every kernel that inlines fd_solve_small is
+// built without the strategy (karman_step_small.hip), and nothing else is: the strategy is worth 0.5 ms of a 11.7 ms training step at
+// 128 x 64, in the weight-gradient body of k_karman_bwd_bww.
 template <int CPT, int SOLVER, int NT = 0>
 __device__ __forceinline__ void karman_bwd_body(const StepArgs& a, float* smem) {
     constexpr int MAXT = CPT + 1;   // face targets per thread: (Y+1)*X / (Y*X/CPT) <= CPT+1 for Y >= CPT
@@ -1679,10 +1697,8 @@ __device__ __forceinline__ void karman_bwd_body(const StepArgs& a, float* smem) 
 
     SOL_STAMP(0);
     float fdp = 0.f;
-    if constexpr (SOLVER == 2) {
-        if (Y == FD_Y) fdp = fd_prefetch(a.fd, a.fd_n);
-        else fd_small_stage<NT>(a.fd, Y, X, L.fdx);
-    }
+    if constexpr (SOLVER == 2) fdp = fd_prefetch(a.fd, a.fd_n);
+    else if constexpr (SOLVER == 3) fd_small_stage<NT>(a.fd, Y, X, L.fdx);
     // ---- 1: load incoming gradient (+ feature gradient): all global loads in flight first --------
     {
         const float* gy = a.g_vy_out + (size_t)b * nVy;
@@ -1770,7 +1786,7 @@ __device__ __forceinline__ void karman_bwd_body(const StepArgs& a, float* smem) 
     float qys[FD_QYS];
 #pragma unroll
     for (int j = 0; j < FD_QYS; ++j) qys[j] = 0.f;
-    if constexpr (SOLVER == 2 && CPT == 16) { if (Y == FD_Y) fd_load_qys(a.fd + 16, __builtin_amdgcn_readfirstlane(tid >> 6), qys); }
+    if constexpr (SOLVER == 2) fd_load_qys(a.fd + 16, __builtin_amdgcn_readfirstlane(tid >> 6), qys);
     const Own o = ownership<CPT>(Y, X);
     float dg[CPT], ac[CPT], r[CPT], z[CPT];
     cell_coeffs<CPT>(o, L.act, Y, X, dg, ac);
@@ -1791,8 +1807,9 @@ __device__ __forceinline__ void karman_bwd_body(const StepArgs& a, float* smem) 
     float* Pfd = nullptr;
     SOL_STAMP(2);
     if constexpr (SOLVER == 2) {
-        if constexpr (CPT == 16) Pfd = Y == FD_Y ? fd_solve(a.fd, qys, L.Bvy, r, a.prof) : fd_solve_small<CPT, NT>(a.fd, Y, X, o, L.fdx, r);
-        else Pfd = fd_solve_small<CPT, NT>(a.fd, Y, X, o, L.fdx, r);
+        Pfd = fd_solve(a.fd, qys, L.Bvy, r, a.prof);
+    } else if constexpr (SOLVER == 3) {
+        Pfd = fd_solve_small<CPT, NT>(a.fd, Y, X, o, L.fdx, r);
     } else if constexpr (SOLVER == 1) {
         it = X == 64 ? pcg_solve<CPT, true, 32>(o, Y, X, L.act, dg, ac, r, z, L.E, L.red, L.cs, a.cinv, a.rtol2, a.atol2, a.max_iter)
                      : pcg_solve<CPT, false, 8>(o, Y, X, L.act, dg, ac, r, z, L.E, L.red, L.cs, a.cinv, a.rtol2, a.atol2, a.max_iter);
@@ -1805,7 +1822,7 @@ __device__ __forceinline__ void karman_bwd_body(const StepArgs& a, float* smem) 
 
     // ---- 3: g_adv = m * (g + D^T z), kept in registers ---------------------------------
     float* Z = L.Bvy;
-    if constexpr (SOLVER == 2) Z = Pfd;
+    if constexpr (SOLVER >= 2) Z = Pfd;
     else {
         if (o.owner) {
 #pragma unroll
@@ -1992,6 +2009,7 @@ struct BwPack {
     BwArgs a[12];
     int n, wg_per;          // n gradient jobs (layers) of wg_per workgroups each
 };
+#ifndef SOL_K2D_SMALL_TU
 __global__ void __launch_bounds__(512) k_karman_bwd_bww(StepArgs a, BwPack bw) {
     extern __shared__ __align__(16) float smem[];
     // timing experiments (option dbg_skip, results invalid; tools/adjoint_split_experiment.py): 4096 = the gradient workgroups end at once (the
@@ -2018,6 +2036,7 @@ __global__ void __launch_bounds__(512) k_karman_bwd_bww(StepArgs a, BwPack bw) {
         if (stamp) a.prof[idx == 0 ? 17 : 19] = wall_clock64();
     }
 }
+#endif
 
 // The same fusion for the 64 x 32 grid (the reference's own training recipe): its adjoint runs on 256 threads (eight-cell strips,
 // LDS-resident direct solver), the weight-gradient body on 512.  The launch has 512-thread workgroups; in a solver workgroup waves
@@ -2026,17 +2045,54 @@ __global__ void __launch_bounds__(512) k_karman_bwd_bww(StepArgs a, BwPack bw) {
 // The passive density has no forward launch to ride with at this size (the forward kernel is the 256-thread form): ONE of its msteps
 // advections rides in each launch of the REVERSE sweep as q.B more workgroups (all saved velocities exist by then; it was a chain of
 // msteps dependent advections in one launch behind the forward unroll: 162 us of the 64x32 recipe's step).
+#ifdef SOL_K2D_SMALL_TU
 __global__ void __launch_bounds__(512) k_karman_bwd_bww_small(StepArgs a, BwPack bw, DensStep q) {
     extern __shared__ __align__(16) float smem[];
     const int ng = bw.n * bw.wg_per;
     if ((int)blockIdx.x < a.B) {
         if (threadIdx.x >= 256) return;
-        karman_bwd_body<8, 2, 256>(a, smem);
+        karman_bwd_body<8, 3, 256>(a, smem);
     } else if ((int)blockIdx.x < a.B + ng) {
         const int idx = (int)blockIdx.x - a.B;
         sbk::bww_sb_body<2>(bw.a[idx / bw.wg_per], idx % bw.wg_per, reinterpret_cast<unsigned char*>(smem));
     } else density_step_body(q, (int)blockIdx.x - a.B - ng);
 }
+
+}  // namespace
+
+// ---- the host side of this translation unit (karman_step_small.hip): launchers that karman_step.hip's entry points call.  The argument
+//      structs live in an unnamed namespace of a source both units compile, so they cross as untyped pointers.
+int sol_k2d_small_init() {
+    static std::atomic<unsigned long long> optin{0};
+    return sol_lds_optin(optin, {SOL_K(k_karman_fwd<8, 3>), SOL_K(k_karman_bwd<8, 3>), SOL_K(k_karman_fwd<16, 3>), SOL_K(k_karman_bwd<16, 3>),
+                                 SOL_K(k_karman_bwd_bww_small)}, "karman small-grid direct kernels");
+}
+int sol_k2d_small_step(int bwd, int cpt, int B, int threads, size_t lds, void* stream, const void* step_args) {
+    const StepArgs& a = *static_cast<const StepArgs*>(step_args);
+    if (int e = sol_k2d_small_init()) return e;
+    if (bwd) {
+        if (cpt == 16) SOL_LAUNCH_NAMED("k_karman_bwd", k_karman_bwd<16, 3>, dim3(B), dim3(threads), lds, (hipStream_t)stream, a);
+        else SOL_LAUNCH_NAMED("k_karman_bwd", k_karman_bwd<8, 3>, dim3(B), dim3(threads), lds, (hipStream_t)stream, a);
+    } else {
+        if (cpt == 16) SOL_LAUNCH_NAMED("k_karman_fwd", k_karman_fwd<16, 3>, dim3(B), dim3(threads), lds, (hipStream_t)stream, a);
+        else SOL_LAUNCH_NAMED("k_karman_fwd", k_karman_fwd<8, 3>, dim3(B), dim3(threads), lds, (hipStream_t)stream, a);
+    }
+    SOL_LAUNCH_CHECK();
+    return SOL_OK;
+}
+int sol_k2d_small_bww(int grid, size_t lds, void* stream, const void* step_args, const void* pack, const void* dens) {
+    if (int e = sol_k2d_small_init()) return e;
+    SOL_LAUNCH(k_karman_bwd_bww_small, dim3(grid), dim3(512), lds, (hipStream_t)stream, *static_cast<const StepArgs*>(step_args),
+               *static_cast<const BwPack*>(pack), *static_cast<const DensStep*>(dens));
+    SOL_LAUNCH_CHECK();
+    return SOL_OK;
+}
+#else       // everything below: karman_step.hip proper
+}  // namespace
+int sol_k2d_small_init();
+int sol_k2d_small_step(int bwd, int cpt, int B, int threads, size_t lds, void* stream, const void* step_args);
+int sol_k2d_small_bww(int grid, size_t lds, void* stream, const void* step_args, const void* pack, const void* dens);
+namespace {
 
 // ------------------------------------------------------------------------------------
 // Passive tracer chain (training path)
@@ -2140,6 +2196,16 @@ bool precond_ok(int Y, int X) {
     return (X == 64 && nc / 4 == 32) || (X == 32 && nc / 4 == 8);
 }
 
+// the grids the direct pressure solver is built for: the one rule of check_cfg and of sol_karman_direct_supported.  128 x 64 runs the
+// register-tiled fd_solve; fd_solve_small takes at most 2048 cells with Y % 16 == 0 and X in {16, 32, 64} (its 4 x 4 register-tile
+// products would take Y % 8 == 0 as well, but nothing has held them to a reference there, so they stay refused).  Y == FD_Y with
+// X != FD_X stays excluded: 128 x 16, the one such grid of at most 2048 cells, does not fit the LDS, so nothing could hold it to a
+// reference.  (The host picks the solver with fd_full_grid: both extents.)
+bool direct_ok(int Y, int X) {
+    if (Y == FD_Y) return X == FD_X;
+    return fd_small_floats(Y, X) > 0 && Y % 16 == 0 && (X == 16 || X == 32 || X == 64);
+}
+
 int check_cfg(const sol_karman_cfg* c) {
     SOL_REQUIRE(c != nullptr, "cfg is NULL");
     SOL_REQUIRE(c->B >= 1, "B must be >= 1 (got %d)", c->B);
@@ -2150,7 +2216,7 @@ int check_cfg(const sol_karman_cfg* c) {
     SOL_REQUIRE(lds_bytes(c->Y, c->X, cpt) <= 160 * 1024, "grid %dx%d does not fit the 160 KiB LDS", c->Y, c->X);
     SOL_REQUIRE(c->dx > 0.f && c->cg_max_iter >= 0, "dx must be > 0 and cg_max_iter >= 0");
     if (c->direct) {
-        SOL_REQUIRE((c->Y == FD_Y && c->X == FD_X && cpt == 16) || fd_small_floats(c->Y, c->X) > 0,
+        SOL_REQUIRE(direct_ok(c->Y, c->X) && (!fd_full_grid(c->Y, c->X) || cpt == 16),
                     "the direct pressure solver is built for 128x64 and for grids of at most 2048 cells with Y %% 16 == 0, X >= 16 (got %dx%d)", c->Y, c->X);
         SOL_REQUIRE(c->direct_n >= 16 + c->Y * c->Y + c->X * c->X + c->X * c->Y + 64 * 64 + 64 + c->X * FD_WIN,
                     "direct_n = %d is too small for a direct-solver blob", c->direct_n);
@@ -2196,9 +2262,10 @@ int sol_karman_feat_transposed(int on) {
 // one-time: allow the full 160 KiB of dynamic LDS (not a stream operation -> done outside graph capture)
 int sol_init_karman_kernels() {
     static std::atomic<unsigned long long> optin{0};
-    return sol_lds_optin(optin, {SOL_K(k_karman_fwd<8, 0>), SOL_K(k_karman_bwd<8, 0>), SOL_K(k_karman_fwd<8, 2>), SOL_K(k_karman_bwd<8, 2>),
+    if (int e = sol_k2d_small_init()) return e;
+    return sol_lds_optin(optin, {SOL_K(k_karman_fwd<8, 0>), SOL_K(k_karman_bwd<8, 0>),
                                  SOL_K(k_karman_fwd<16, 0>), SOL_K(k_karman_bwd<16, 0>), SOL_K(k_karman_fwd<16, 1>), SOL_K(k_karman_bwd<16, 1>),
-                                 SOL_K(k_karman_fwd<16, 2>), SOL_K(k_karman_bwd<16, 2>), SOL_K(k_karman_bwd_bww), SOL_K(k_karman_fwd_dens), SOL_K(k_karman_bwd_bww_small), SOL_K(k_karman_fwd_bands)},
+                                 SOL_K(k_karman_fwd<16, 2>), SOL_K(k_karman_bwd<16, 2>), SOL_K(k_karman_bwd_bww), SOL_K(k_karman_fwd_dens), SOL_K(k_karman_fwd_bands)},
                          "karman kernels");
 }
 
@@ -2250,6 +2317,17 @@ int launch_step(K kernel, int cpt, const sol_karman_cfg* c, void* stream, const 
     return SOL_OK;
 }
 
+// the same for the small-grid direct kernels (SOLVER == 3), which live in karman_step_small.hip
+int launch_small_direct(bool bwd, int cpt, const sol_karman_cfg* c, void* stream, const StepArgs& a0) {
+    const int threads = (int)align_up((size_t)(c->Y / cpt) * c->X, 64);
+    StepArgs a = a0;
+    const bool prof = sol_opt().step_prof != 0;
+    if (prof) a.prof = prof_buffer();
+    if (int e = sol_k2d_small_step(bwd, cpt, c->B, threads, lds_bytes(c->Y, c->X, cpt), stream, &a)) return e;
+    if (prof && a.prof) return prof_print((hipStream_t)stream, a, false);
+    return SOL_OK;
+}
+
 }  // namespace
 
 // internal (train.hip): the msteps density advections of the unrolled loop as one launch
@@ -2275,7 +2353,7 @@ int sol_density_chain(const sol_karman_cfg* c, void* stream, int ms, const float
 
 extern "C" int sol_karman_precond_supported(int32_t Y, int32_t X) { return precond_ok(Y, X) ? 1 : 0; }
 extern "C" int sol_karman_direct_supported(int32_t Y, int32_t X) {
-    return ((Y == FD_Y && X == FD_X) || (fd_small_floats(Y, X) > 0 && Y % 16 == 0 && (X == 16 || X == 32 || X == 64))) ? 1 : 0;
+    return direct_ok(Y, X) ? 1 : 0;
 }
 
 static int step_fwd_impl(const sol_karman_cfg* cfg, void* stream,
@@ -2314,7 +2392,7 @@ static int step_fwd_impl(const sol_karman_cfg* cfg, void* stream,
         return SOL_OK;
     }
     if (dens_d_out) {   // density workgroups of the PREVIOUS step ride in this launch (direct-solver kernels only)
-        SOL_REQUIRE(cpt == 16 && a.fd && dens_d_in && dens_svy && dens_svx && inflow, "fused solver + density launch: unsupported configuration");
+        SOL_REQUIRE(cpt == 16 && a.fd && fd_full_grid(cfg->Y, cfg->X) && dens_d_in && dens_svy && dens_svx && inflow, "fused solver + density launch: unsupported configuration");
         if (int e = sol_init_karman_kernels()) return e;
         DensStep q{cfg->B, cfg->Y, cfg->X, cfg->inflow_before, cfg->dt / cfg->dx, cfg->dt, dens_d_in, dens_svy, dens_svx, inflow, dens_d_out};
         if (sol_opt().step_prof) a.prof = prof_buffer();
@@ -2323,7 +2401,8 @@ static int step_fwd_impl(const sol_karman_cfg* cfg, void* stream,
         if (a.prof) return prof_print((hipStream_t)stream, a, false);
         return SOL_OK;
     }
-    if (cpt != 16) return a.fd ? launch_step(k_karman_fwd<8, 2>, 8, cfg, stream, a) : launch_step(k_karman_fwd<8, 0>, 8, cfg, stream, a);
+    if (a.fd && !fd_full_grid(cfg->Y, cfg->X)) return launch_small_direct(false, cpt, cfg, stream, a);
+    if (cpt != 16) return launch_step(k_karman_fwd<8, 0>, 8, cfg, stream, a);       // (check_cfg: a blob at 128 x 64 comes with 16-cell strips)
     if (a.fd) return launch_step(k_karman_fwd<16, 2>, 16, cfg, stream, a);
     if (a.cinv) return launch_step(k_karman_fwd<16, 1>, 16, cfg, stream, a);
     return launch_step(k_karman_fwd<16, 0>, 16, cfg, stream, a);
@@ -2398,16 +2477,15 @@ static int step_bwd_impl(const sol_karman_cfg* cfg, void* stream,
         if (cpt == 8) {
             DensStep q{};
             if (dens) q = DensStep{cfg->B, cfg->Y, cfg->X, cfg->inflow_before, cfg->dt / cfg->dx, cfg->dt, dens->d_in, dens->svy, dens->svx, dens->inflow, dens->d_out};
-            SOL_LAUNCH(k_karman_bwd_bww_small, dim3(cfg->B + nbw * wg_per + (dens ? cfg->B : 0)), dim3(512), lds, (hipStream_t)stream, a, pk, q);
-            SOL_LAUNCH_CHECK();
-            return SOL_OK;
+            return sol_k2d_small_bww(cfg->B + nbw * wg_per + (dens ? cfg->B : 0), lds, stream, &a, &pk, &q);
         }
         SOL_LAUNCH(k_karman_bwd_bww, dim3(cfg->B + nbw * wg_per), dim3(512), lds, (hipStream_t)stream, a, pk);
         SOL_LAUNCH_CHECK();
         if (a.prof) return prof_print((hipStream_t)stream, a, true);
         return SOL_OK;
     }
-    if (cpt != 16) return a.fd ? launch_step(k_karman_bwd<8, 2>, 8, cfg, stream, a) : launch_step(k_karman_bwd<8, 0>, 8, cfg, stream, a);
+    if (a.fd && !fd_full_grid(cfg->Y, cfg->X)) return launch_small_direct(true, cpt, cfg, stream, a);
+    if (cpt != 16) return launch_step(k_karman_bwd<8, 0>, 8, cfg, stream, a);
     if (a.fd) return launch_step(k_karman_bwd<16, 2>, 16, cfg, stream, a);
     if (a.cinv) return launch_step(k_karman_bwd<16, 1>, 16, cfg, stream, a);
     return launch_step(k_karman_bwd<16, 0>, 16, cfg, stream, a);
@@ -2444,9 +2522,7 @@ int sol_bww_jobs_launch(void* stream, const BwArgs* bw, int nbw, int wg_per, con
     pk.n = nbw; pk.wg_per = wg_per;
     if (dens) {         // with a density advection riding along (64x32 training path)
         const DensStep q{cfg->B, cfg->Y, cfg->X, cfg->inflow_before, cfg->dt / cfg->dx, cfg->dt, dens->d_in, dens->svy, dens->svx, dens->inflow, dens->d_out};
-        SOL_LAUNCH(k_karman_bwd_bww_small, dim3(nbw * wg_per + cfg->B), dim3(512), (size_t)sbk::BW_LDS, (hipStream_t)stream, a, pk, q);
-        SOL_LAUNCH_CHECK();
-        return SOL_OK;
+        return sol_k2d_small_bww(nbw * wg_per + cfg->B, (size_t)sbk::BW_LDS, stream, &a, &pk, &q);
     }
     SOL_LAUNCH(k_karman_bwd_bww, dim3(nbw * wg_per), dim3(512), (size_t)sbk::BW_LDS, (hipStream_t)stream, a, pk);
     SOL_LAUNCH_CHECK();
@@ -2460,3 +2536,4 @@ int sol_karman_bwd_fusable(const sol_karman_cfg* cfg) {
 int sol_karman_bwd_fusable_small(const sol_karman_cfg* cfg) {
     return cfg && cfg->direct && cfg->Y == 64 && cfg->X == 32 && pick_cpt(cfg) == 8;
 }
+#endif      // SOL_K2D_SMALL_TU
