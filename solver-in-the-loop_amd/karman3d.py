@@ -19,6 +19,7 @@ when `MarsMoon3D.params_key()` has moved.  For other hosts
 import ctypes as C
 import math
 import weakref
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -81,6 +82,42 @@ def buoyancy_force3d(buoyancy=None, buoyancy_factor=None, gravity=(-9.81, 0.0, 0
 def _buoyant3d(buoyancy):
     """True for a force that moves the velocity: the density is then part of the dynamics"""
     return buoyancy is not None and any(v != 0.0 for v in buoyancy)
+
+
+class StepPhysics3D(NamedTuple):
+    """The physics of one 3-D step beyond the plain one, as every internal call carries it (the sibling of ops.StepPhysics).  The default
+    is the plain step: the launches and the bits of a call without either keyword.  The two compose with each other, with density_grad
+    and re_grad, both solvers and feat_out (whose fourth channel stays the true re).
+    buoyancy = (fy, fx, fz), a force per unit density, or None: the step's OUTPUT density pushes the velocity (sol_karman3d_step_fwd_buoy:
+    one launch more).  The density is then part of the dynamics: a differentiable step keeps it in the graph whatever density_grad says.
+    nsub = n >= 1, the diffusion substeps (PhiFlow's diffuse(field, amount, substeps)): n explicit substeps of alpha / n, alpha = dt res^2
+    / Re, the boundary blend after the last one -- diffuse_sub (M^(n-1) v), then the step's launches on Karman3DFlow.sub_cfg(n).  The
+    single stencil is stable only while alpha <= 1/6 (min_diffusion_substeps3d gives the n a run needs)."""
+    buoyancy: Optional[tuple] = None
+    nsub: int = 1
+
+    @classmethod
+    def of(cls, buoyancy=None, buoyancy_factor=None, gravity=(-9.81, 0.0, 0.0), diffusion_substeps=1, who="diffusion_substeps", keep_zero_force=False):
+        """From the user-facing keywords, validated (ValueError) by buoyancy_force3d and ops.diffusion_substeps_arg (`who` is how its message
+        names the count).  A force of (0, 0, 0) becomes None, the plain step; keep_zero_force (torch.ops.sol.karman3d_step_buoy without a
+        gradient) keeps it as given: the _buoy entry point takes it and issues the plain launches."""
+        from .ops import diffusion_substeps_arg
+        n = diffusion_substeps_arg(diffusion_substeps, who)
+        f = buoyancy_force3d(buoyancy, buoyancy_factor, gravity)
+        return cls(f if keep_zero_force or _buoyant3d(f) else None, n)
+
+    def moving(self):
+        """self, a kept force of (0, 0, 0) normalised to None: what a differentiable step runs on"""
+        return self if self.buoyancy is None or _buoyant3d(self.buoyancy) else self._replace(buoyancy=None)
+
+    mode = property(lambda self: "" if self.buoyancy is None else "_buoy", doc='the entry points of the step and its velocity adjoint: "" or "_buoy"')
+    force_tail = property(lambda self: () if self.buoyancy is None else tuple(float(v) for v in self.buoyancy),
+                          doc="the three floats a _buoy entry point takes after its plain sibling's arguments; () in the plain mode")
+
+
+def _adjoint_entry(lib, half, mode="", re=False):
+    """The lookup of an adjoint's entry point, sol_karman3d_<half><mode>[_re]: half "step_bwd" (mode: StepPhysics3D.mode) or "density_bwd" (none)"""
+    return getattr(lib, "sol_karman3d_" + half + mode + ("_re" if re else ""))
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -208,33 +245,24 @@ class Karman3DFlow:
     KarmanFlow; cg_max_iter is the fixed launch budget).  After a forward step on such a scene `solve_info` holds "iterations"
     and "converged" (device int32 [B]); the adjoint adds "iterations_bwd" and "converged_bwd".  The direct solve reports nothing.
 
-    density_grad=True (opt-in): the density output of `step` is differentiable too (sol_karman3d_density_bwd: launches of their own, no
-    pressure solve, added onto the velocity adjoint's result).  re_grad=True (opt-in): a tensor `re` that requires a gradient receives
-    one (sol_karman3d_step_bwd_re / sol_karman3d_density_bwd_re; the step's input velocity is saved as well).  With both off the step
-    launches what it always did: the density is a passive tracer and `re` is data.
+    density_grad=True (opt-in): the density output of `step` is differentiable too.  re_grad=True (opt-in): a tensor `re` that requires
+    a gradient receives one.  With both off the density is a passive tracer and `re` is data (_step_adjoint3d describes the modes).
 
     buoyancy=(fy, fx, fz), a force per unit density, or PhiFlow's spelling buoyancy_factor=beta with gravity=(gy, gx, gz): F = -gravity *
-    beta (buoyancy_force3d).  The step's OUTPUT density pushes the velocity (sol_karman3d_step_fwd_buoy: one launch more); the density is
-    then part of the dynamics and always in the graph, whatever density_grad says (_Karman3DStepFn's buoyant mode).  A force of zero, or
-    none: the plain step.
+    beta (buoyancy_force3d), and diffusion_substeps=n are kept as `self.physics`, one StepPhysics3D built here (see there; a force of
+    zero is none).  The defaults issue the launches the step always did."""
 
-    diffusion_substeps=n (PhiFlow's diffuse(field, amount, substeps)): the velocity is diffused by n explicit substeps of alpha / n, alpha
-    = dt res^2 / Re, the boundary blend after the last one.  The single stencil is stable only while alpha <= 1/6
-    (min_diffusion_substeps3d gives the n a run needs).  `step` then runs diffuse_sub (M^(n-1) v) and the launches above on a cfg whose
-    res is diffusion_sub_res(res, n); composes with density_grad, re_grad, buoyancy, both solvers and feat_out (whose fourth channel stays
-    the true re).  The default 1 issues the launches it always did."""
+    buoyancy = property(lambda self: self.physics.buoyancy)
+    nsub = property(lambda self: self.physics.nsub)
 
     def __init__(self, scene, batch_size, dt=1.0, res=None, grad_pad="replicate", inflow_order="after",
                  cg_rtol=1e-6, cg_atol=1e-9, cg_max_iter=CG_MAX_ITER3D, density_grad=False, re_grad=False,
                  buoyancy=None, buoyancy_factor=None, gravity=(-9.81, 0.0, 0.0), diffusion_substeps=1):
-        from .ops import diffusion_substeps_arg
-        self.nsub = diffusion_substeps_arg(diffusion_substeps, "Karman3DFlow: diffusion_substeps")
+        self.physics = StepPhysics3D.of(buoyancy, buoyancy_factor, gravity, diffusion_substeps, "Karman3DFlow: diffusion_substeps")
         _lib.require_gpu()
         self.lib = _lib.load()
         self.scene, self.B = scene, batch_size
         self.density_grad, self.re_grad = bool(density_grad), bool(re_grad)
-        f = buoyancy_force3d(buoyancy, buoyancy_factor, gravity)
-        self.buoyancy = f if _buoyant3d(f) else None
         s = scene
         self.cg = s.pressure_solver == "cg"
         self.cfg = Karman3DCfg(batch_size, s.Y, s.X, s.Z, float(s.dx), float(dt), float(s.X if res is None else res),
@@ -281,10 +309,14 @@ class Karman3DFlow:
         cfg.cg_info = info.data_ptr()
         return info
 
-    def _fwd(self, d, vy, vx, vz, re, saved=None, feat_out=None, feat_scale=None, buoyancy=None, nsub=1):
-        """one forward step; buoyancy = (fy, fx, fz): sol_karman3d_step_fwd_buoy (a force of zero issues the plain call's launches);
-        nsub: the launches run on sub_cfg(nsub) (the caller has pre-diffused the velocity: _fwd_sub)"""
-        cfg = self.sub_cfg(nsub)
+    def _forward(self, ph, d, vy, vx, vz, re, saved=None, feat_out=None, feat_scale=None, pre_diffuse=True):
+        """THE forward launch site: one step under the StepPhysics3D `ph`  ->  ((d, vy, vx, vz) after the step, the velocity the launches
+        read).  ph.nsub > 1: the pre-diffusion (diffuse_sub; not with pre_diffuse=False: the caller has run it), then the launches on
+        sub_cfg(ph.nsub) -- the velocity handed back is then M^(n-1) v, "the input velocity" the re mode saves.  ph.buoyancy:
+        sol_karman3d_step_fwd_buoy (a kept force of zero issues the plain call's launches)."""
+        if pre_diffuse and ph.nsub > 1:
+            vy, vx, vz = diffuse_sub(self, vy, vx, vz, re, ph.nsub)
+        cfg = self.sub_cfg(ph.nsub)
         s, B = self.scene, self.B
         Y, X, Z = s.Y, s.X, s.Z
         assert d.shape == (B, Y, X, Z) and vy.shape == (B, Y + 1, X, Z) and vx.shape == (B, Y, X + 1, Z) and vz.shape == (B, Y, X, Z + 1)
@@ -296,15 +328,23 @@ class Karman3DFlow:
             fs = (C.c_float * 4)(*[float(v) for v in feat_scale])
         sv = saved if saved is not None else (None, None, None)
         info = self._cg_info(cfg)
-        entry, tail = (self.lib.sol_karman3d_step_fwd, ()) if buoyancy is None else (self.lib.sol_karman3d_step_fwd_buoy, tuple(float(v) for v in buoyancy))
+        entry = getattr(self.lib, "sol_karman3d_step_fwd" + ph.mode)
         check(entry(C.byref(cfg), stream(), ptr(d), ptr(vy), ptr(vx), ptr(vz), ptr(re),
                     ptr(s.active), ptr(s.inflow), ptr(s.velBCy), ptr(s.velBCyMask), s.bc_stride,
-                    ptr(out[0]), ptr(out[1]), ptr(out[2]), ptr(out[3]), ptr(sv[0]), ptr(sv[1]), ptr(sv[2]),
-                    ptr(feat_out), fs,
-                    s.direct_header.ctypes.data_as(C.c_void_p), ptr(self.workspace), self.workspace_bytes, *tail))
+                    ptr(out[0]), ptr(out[1]), ptr(out[2]), ptr(out[3]), ptr(sv[0]), ptr(sv[1]), ptr(sv[2]), ptr(feat_out), fs,
+                    s.direct_header.ctypes.data_as(C.c_void_p), ptr(self.workspace), self.workspace_bytes, *ph.force_tail))
         if info is not None:
             self.solve_info = {"iterations": info[:, 0], "converged": info[:, 1]}
-        return tuple(out)
+        return tuple(out), (vy, vx, vz)
+
+    def _fwd(self, d, vy, vx, vz, re, saved=None, feat_out=None, feat_scale=None, buoyancy=None, nsub=1, physics=None, pre_diffuse=False):
+        """the step's outputs of _forward's launches alone (the caller has pre-diffused the velocity); `physics` replaces buoyancy= / nsub="""
+        ph = physics if physics is not None else StepPhysics3D(buoyancy, nsub)
+        return self._forward(ph, d, vy, vx, vz, re, saved, feat_out, feat_scale, pre_diffuse)[0]
+
+    def _fwd_sub(self, *args, **kw):
+        """_fwd with the pre-diffusion"""
+        return self._fwd(*args, pre_diffuse=True, **kw)
 
     def _ws(self, nbytes):
         """the workspace, grown to nbytes where a call needs more than the step and its velocity adjoint (the opt-in adjoints)"""
@@ -326,21 +366,21 @@ class Karman3DFlow:
             raise ValueError("g_re must be [B] = (%d,), got %s" % (self.B, tuple(g_re.shape)))
         return (ptr(vel_in[0]), ptr(vel_in[1]), ptr(vel_in[2]), ptr(g_re), int(accumulate)), g_re
 
-    def _bwd(self, saved, re, gvy, gvx, gvz, vel_in=None, g_re=None, buoyancy=None, g_d=None, nsub=1):
-        """the velocity adjoint (sol_karman3d_step_bwd); vel_in = the step's input velocity: also the gradient with respect to re
-        (sol_karman3d_step_bwd_re; the velocity gradients are the plain call's bits) -> [g_vy, g_vx, g_vz] (+ [g_re]).
+    def _bwd(self, saved, re, gvy, gvx, gvz, vel_in=None, g_re=None, buoyancy=None, g_d=None, nsub=1, physics=None):
+        """the velocity adjoint, the direct call (sol_karman3d_step_bwd); vel_in = the step's input velocity: also the gradient with respect
+        to re (sol_karman3d_step_bwd_re; the velocity gradients are the plain call's bits) -> [g_vy, g_vx, g_vz] (+ [g_re]).
         buoyancy = (fy, fx, fz): the buoyant step's (sol_karman3d_step_bwd_buoy(_re): the same launches and bits, then the transpose of the
         force term); g_d [B,Y,X,Z] = the cotangent of the step's output density (None = zero) -> ... + [g_dsum], which the caller hands to
-        density_bwd as its g_d, accumulating onto the velocity gradients returned here."""
+        density_bwd as its g_d, accumulating onto the velocity gradients returned here.  `physics` replaces buoyancy= / nsub=.
+        _step_adjoint3d composes this with density_bwd and the substep tail, and is the one place that takes this list apart."""
         s = self.scene
-        cfg = self.sub_cfg(nsub)            # (nsub > 1: `saved` / vel_in are the pre-diffused step's; the result is the cotangent of M^(n-1) v, g_re 1/n)
+        ph = physics if physics is not None else StepPhysics3D(buoyancy, nsub)
+        cfg = self.sub_cfg(ph.nsub)         # (nsub > 1: `saved` / vel_in are the pre-diffused step's; the result is the cotangent of M^(n-1) v, g_re 1/n)
         gi = [torch.empty_like(t) for t in saved]
         info = self._cg_info(cfg)
-        buoy = buoyancy is not None
-        if vel_in is None:
-            entry, tail = (self.lib.sol_karman3d_step_bwd_buoy if buoy else self.lib.sol_karman3d_step_bwd), ()
-        else:
-            entry = self.lib.sol_karman3d_step_bwd_buoy_re if buoy else self.lib.sol_karman3d_step_bwd_re
+        buoy = ph.buoyancy is not None
+        entry, tail = _adjoint_entry(self.lib, "step_bwd", ph.mode, vel_in is not None), ()
+        if vel_in is not None:
             self._ws(self.lib.sol_karman3d_step_bwd_re_workspace_bytes(C.byref(self.cfg)))
             tail, g_re = self._re_tail(saved, vel_in, g_re)
         g_dsum = None
@@ -350,7 +390,7 @@ class Karman3DFlow:
                 if g_d.shape != (self.B, s.Y, s.X, s.Z):
                     raise ValueError("g_d must be [B,Y,X,Z] = %s, got %s" % ((self.B, s.Y, s.X, s.Z), tuple(g_d.shape)))
             g_dsum = torch.empty(self.B, s.Y, s.X, s.Z, dtype=torch.float32, device=saved[0].device)
-            tail = tuple(tail) + tuple(float(v) for v in buoyancy) + (ptr(g_d), ptr(g_dsum))
+            tail = tuple(tail) + ph.force_tail + (ptr(g_d), ptr(g_dsum))
         check(entry(C.byref(cfg), stream(), ptr(saved[0]), ptr(saved[1]), ptr(saved[2]), ptr(re),
                     ptr(s.active), ptr(s.velBCyMask), s.bc_stride, ptr(gvy), ptr(gvx), ptr(gvz),
                     ptr(gi[0]), ptr(gi[1]), ptr(gi[2]),
@@ -375,26 +415,18 @@ class Karman3DFlow:
         return p
 
     def step(self, d, vy, vx, vz, re, feat_out=None, feat_scale=None):
-        """(d, vy, vx, vz) -> new tensors after one solver step.  Differentiable with respect to the velocity (the density is
-        a passive tracer) when a velocity input requires grad; feat_out [B,Y,X,Z,4] (optional, no-grad use) receives the
-        scaled features.  With density_grad the density output is differentiable too (taken when any of d, vy, vx, vz requires a
-        gradient); with re_grad a tensor `re` that requires a gradient receives one.  With a buoyancy force the density is part of the
-        dynamics: every output is differentiable with respect to the density and the velocity."""
+        """(d, vy, vx, vz) -> new tensors after one solver step.  Differentiable with respect to the velocity when a velocity input requires
+        grad -- and to the density (density_grad, or a buoyancy force: taken when any of d, vy, vx, vz requires a gradient) and to a tensor
+        `re` that requires one (re_grad): _step_adjoint3d.  feat_out [B,Y,X,Z,4] (optional, no-grad use) receives the scaled features."""
         d, vy, vx, vz, re = (_lib.f32(t) for t in (d, vy, vx, vz, re))
         grad = torch.is_grad_enabled()
         want_re = self.re_grad and grad and re.requires_grad
-        density = self.density_grad or self.buoyancy is not None
+        density = self.density_grad or self.physics.buoyancy is not None
         if grad and (vy.requires_grad or vx.requires_grad or vz.requires_grad or (density and d.requires_grad) or want_re):
             if feat_out is not None:
                 raise ValueError("feat_out is the fused no-grad feature output: build the features with to_feature3d() when training")
-            return _Karman3DStepFn.apply(self, d, vy, vx, vz, re, density, want_re, self.buoyancy, self.nsub)
-        return self._fwd_sub(d, vy, vx, vz, re, None, feat_out, feat_scale, self.buoyancy, self.nsub)
-
-    def _fwd_sub(self, d, vy, vx, vz, re, saved=None, feat_out=None, feat_scale=None, buoyancy=None, nsub=1):
-        """_fwd under diffusion_substeps = nsub: the pre-diffusion (diffuse_sub), then _fwd's launches on the scaled cfg; nsub = 1: _fwd"""
-        if nsub > 1:
-            vy, vx, vz = diffuse_sub(self, vy, vx, vz, re, nsub)
-        return self._fwd(d, vy, vx, vz, re, saved, feat_out, feat_scale, buoyancy, nsub)
+            return _Karman3DStepFn.apply(self, d, vy, vx, vz, re, density, want_re, self.physics)
+        return self._forward(self.physics, d, vy, vx, vz, re, None, feat_out, feat_scale)[0]
 
 
 def density_bwd(sim, d_in, saved, re, g_d, g_v=None, vel_in=None, g_re=None, nsub=1):
@@ -404,9 +436,9 @@ def density_bwd(sim, d_in, saved, re, g_d, g_v=None, vel_in=None, g_re=None, nsu
     the velocity adjoint's result; the density's part is added onto them in place (one fp32 add per face) and they are returned.  Without
     them the density's part alone is written to fresh tensors.  vel_in = (vy, vx, vz), the step's INPUT velocity: the gradient with
     respect to re as well (sol_karman3d_density_bwd_re), returned fifth; g_re [B]: a buffer to add onto, else a fresh one is written.
-    nsub (diffusion substeps: _Karman3DStepFn, the trainer): the launches run on sim.sub_cfg(nsub); `saved` / vel_in are then those of
+    nsub (diffusion substeps: StepPhysics3D.nsub): the launches run on sim.sub_cfg(nsub); `saved` / vel_in are then those of
     the pre-diffused velocity, the velocity gradients are the cotangent of M^(n-1) v and g_re is 1/n of the gradient -- a g_re to add onto
-    must hold such a part too (the factor n is applied once, afterwards)."""
+    must hold such a part too (the factor n is applied once, afterwards: _step_adjoint3d)."""
     _lib.require_gpu()
     s, B = sim.scene, sim.B
     Y, X, Z = s.Y, s.X, s.Z
@@ -420,10 +452,10 @@ def density_bwd(sim, d_in, saved, re, g_d, g_v=None, vel_in=None, g_re=None, nsu
     accumulate = g_v is not None
     if accumulate and [t.shape for t in g_v] != [t.shape for t in saved]:
         raise ValueError("density_bwd: g_v must have the velocity's shapes")
-    if vel_in is None:
-        entry, nbytes, tail = sim.lib.sol_karman3d_density_bwd, sim.lib.sol_karman3d_density_bwd_workspace_bytes(C.byref(sim.cfg)), ()
-    else:
-        entry, nbytes = sim.lib.sol_karman3d_density_bwd_re, sim.lib.sol_karman3d_density_bwd_re_workspace_bytes(C.byref(sim.cfg))
+    want_re = vel_in is not None
+    entry, tail = _adjoint_entry(sim.lib, "density_bwd", re=want_re), ()
+    nbytes = (sim.lib.sol_karman3d_density_bwd_re_workspace_bytes if want_re else sim.lib.sol_karman3d_density_bwd_workspace_bytes)(C.byref(sim.cfg))
+    if want_re:
         tail, g_re = sim._re_tail(saved, vel_in, g_re)
     gi = list(g_v) if accumulate else [torch.empty_like(t) for t in saved]
     od = torch.empty_like(d_in)
@@ -434,31 +466,54 @@ def density_bwd(sim, d_in, saved, re, g_d, g_v=None, vel_in=None, g_re=None, nsu
     return (od, *gi) if vel_in is None else (od, *gi, g_re)
 
 
+def _step_adjoint3d(sim, ph, density, d_in, saved, re, gd, gv, vel_in=None, through_substeps=True):
+    """THE adjoint of one step of `sim` under the StepPhysics3D `ph` (a moving force or none: StepPhysics3D.moving): the velocity half
+    (Karman3DFlow._bwd, with the pressure solve), the density half (density_bwd) and the substep tail are composed here and nowhere else
+    (_Karman3DStepFn.backward, the reverse sweep of Karman3DTrainer).  `saved` = the post-diffusion velocity the forward kept, d_in = the
+    step's input density (the density half reads it), gd / gv = (gvy, gvx, gvz) = the cotangents of the step's outputs, None where none
+    arrived; vel_in = the velocity the forward launches read: the gradient in re as well (the _re entries, the opt-in `want_re`)
+    ->  (g_d, g_vy, g_vx, g_vz, g_re), None where nothing reaches it.
+    Plain (no force, `density` and vel_in off): the velocity half runs unconditionally; the density is a passive tracer, re is data.
+    `density` or vel_in: the velocity half runs only when a velocity cotangent arrived, the density half only when gd did (`density`);
+    both together accumulate onto the velocity half's buffers and g_re.
+    A force: whenever any cotangent arrived the velocity half runs through its buoyant entry (zeros for a missing velocity cotangent, gd =
+    None a null pointer; the plain launches and the transpose of the force term, g_dsum = g_d + dt F . transpose(g_a)), then the density
+    half on g_dsum, accumulating: a velocity-only loss yields a density gradient too.  No cotangent at all: nothing is launched.
+    ph.nsub = n > 1: both halves ran on the scaled cfg, their velocity result is the cotangent of M^(n-1) v and g_re 1/n of the gradient;
+    the tail is diffuse_sub on that cotangent (the operator is symmetric; not with through_substeps=False, for a caller that does not
+    read it) and g_re times n (one fp32 multiply)."""
+    moving, want_re = ph.buoyancy is not None, vel_in is not None
+    some_v = any(g is not None for g in gv)
+    gd = None if gd is None else gd.contiguous()
+    gi = g_re = od = None
+    if (moving and gd is not None) or some_v or not (moving or density or want_re):
+        res = sim._bwd(saved, re, *(torch.zeros_like(t) if g is None else g.contiguous() for g, t in zip(gv, saved)), vel_in=vel_in,
+                       g_d=gd if moving else None, physics=ph)
+        gi, g_re = res[:3], (res[3] if want_re else None)
+        gd = res[-1] if moving else gd                  # g_dsum
+    if (moving or density) and gd is not None:
+        od, *gi = density_bwd(sim, d_in, saved, re, gd, gi, vel_in, g_re, nsub=ph.nsub)
+        g_re = gi.pop() if want_re else None
+    if ph.nsub > 1:
+        if through_substeps and gi is not None:
+            gi = diffuse_sub(sim, gi[0], gi[1], gi[2], re, ph.nsub)
+        if g_re is not None:
+            g_re = g_re * float(ph.nsub)
+    return (od, *(gi if gi is not None else (None,) * 3), g_re)
+
+
 class _Karman3DStepFn(torch.autograd.Function):
-    """One solver step with its hand-written adjoints; the forward launches are the same in every mode.  Plain: differentiable with
-    respect to the velocity, the density is a passive tracer, re is data.  `density` (opt-in): the density output is differentiable too
-    (density_bwd, added onto the velocity adjoint's result).  `want_re` (opt-in): differentiable with respect to re as well, the step's
-    input velocity saved beside the post-diffusion one.  In the opt-in modes the velocity half (with its pressure solve) runs only when a
-    velocity cotangent arrived, the density half only when a density cotangent did; both together accumulate.
-    `buoyancy` = (fy, fx, fz), a non-zero force (else None): the buoyant step -- the density is part of the dynamics, so it is in the graph
-    whatever `density` says.  Whenever any cotangent arrives the velocity half runs through its buoyant entry (Karman3DFlow._bwd: the
-    plain launches and the transpose of the force term, g_dsum = g_d + dt F . transpose(g_a)), then the density half on g_dsum, accumulating:
-    a velocity-only loss yields a density gradient too.
-    `nsub` (diffusion_substeps = n > 1): n explicit diffusion substeps, one more mode that composes with the others -- diffuse_sub before
-    the forward launches, which then run on the scaled cfg (Karman3DFlow.sub_cfg) on the pre-diffused velocity M^(n-1) v; that is also
-    the "input velocity" the re mode saves.  Backward: the adjoints above on the scaled cfg, then diffuse_sub on the velocity cotangent
-    (the operator is symmetric) and g_re times n (one fp32 multiply).  nsub = 1 launches nothing new."""
+    """One solver step under a StepPhysics3D with its hand-written adjoint: Karman3DFlow._forward, which also hands back the velocity its
+    launches read ("the input velocity" the `want_re` mode saves beside the post-diffusion one), and _step_adjoint3d, which describes the
+    modes.  `density`: the density output stays in the graph (always under a force)."""
 
     @staticmethod
-    def forward(ctx, sim, d, vy, vx, vz, re, density, want_re, buoyancy=None, nsub=1):
+    def forward(ctx, sim, d, vy, vx, vz, re, density, want_re, ph=StepPhysics3D()):
         vel = [vy.contiguous(), vx.contiguous(), vz.contiguous()]
-        if nsub > 1:
-            vel = list(diffuse_sub(sim, vel[0], vel[1], vel[2], re, nsub))
         saved = [torch.empty_like(t) for t in vel]
-        density = bool(density) or buoyancy is not None
-        out = sim._fwd(d, vel[0], vel[1], vel[2], re, saved, buoyancy=buoyancy, nsub=nsub)
-        ctx.nsub = nsub
-        ctx.sim, ctx.density, ctx.want_re, ctx.buoyancy = sim, density, want_re, buoyancy
+        density = bool(density) or ph.buoyancy is not None
+        out, vel = sim._forward(ph, d, *vel, re, saved)
+        ctx.sim, ctx.density, ctx.want_re, ctx.physics = sim, density, want_re, ph
         ctx.save_for_backward(re, *saved, *((d,) if density else ()), *(vel if want_re else ()))
         if not density:
             ctx.mark_non_differentiable(out[0])
@@ -467,39 +522,10 @@ class _Karman3DStepFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gd, gvy, gvx, gvz):
-        n, sim = ctx.nsub, ctx.sim
-        od, gy, gx, gz, g_re = _Karman3DStepFn._adjoints(ctx, gd, gvy, gvx, gvz)
-        if n > 1:           # (gy, gx, gz) is the cotangent of M^(n-1) v and g_re 1/n of the gradient: see the class comment
-            if gy is not None:
-                gy, gx, gz = diffuse_sub(sim, gy, gx, gz, ctx.saved_tensors[0], n)
-            if g_re is not None:
-                g_re = g_re * float(n)
-        return None, od, gy, gx, gz, g_re, None, None, None, None
-
-    @staticmethod
-    def _adjoints(ctx, gd, gvy, gvx, gvz):
-        """(g_d, g_vy, g_vx, g_vz, g_re) of forward's launches on the scaled cfg: under nsub > 1 the cotangent of M^(n-1) v and 1/n of g_re"""
-        n = ctx.nsub
         re, sy, sx, sz, *rest = ctx.saved_tensors
-        saved = (sy, sx, sz)
         d_in = rest[0] if ctx.density else None
         vel_in = tuple(rest[-3:]) if ctx.want_re else None
-        z = lambda g, t: torch.zeros_like(t) if g is None else g.contiguous()
-        od = g_re = gi = None
-        if ctx.buoyancy is not None:
-            if gd is None and gvy is None and gvx is None and gvz is None:
-                return (None,) * 5
-            res = ctx.sim._bwd(saved, re, z(gvy, sy), z(gvx, sx), z(gvz, sz), vel_in, buoyancy=ctx.buoyancy, g_d=None if gd is None else gd.contiguous(), nsub=n)
-            res = density_bwd(ctx.sim, d_in, saved, re, res[-1], res[:3], vel_in, res[3] if vel_in is not None else None, nsub=n)
-            return res[0], res[1], res[2], res[3], (res[4] if vel_in is not None else None)
-        if not (ctx.density or ctx.want_re) or gvy is not None or gvx is not None or gvz is not None:
-            res = ctx.sim._bwd(saved, re, z(gvy, sy), z(gvx, sx), z(gvz, sz), vel_in, nsub=n)
-            gi, g_re = res[:3], (res[3] if vel_in is not None else None)
-        if ctx.density and gd is not None:          # added onto the velocity half's buffers and g_re
-            res = density_bwd(ctx.sim, d_in, saved, re, gd.contiguous(), gi, vel_in, g_re, nsub=n)
-            od, gi, g_re = res[0], res[1:4], (res[4] if vel_in is not None else None)
-        gi = gi if gi is not None else (None, None, None)
-        return od, gi[0], gi[1], gi[2], g_re
+        return (None, *_step_adjoint3d(ctx.sim, ctx.physics, ctx.density, d_in, (sy, sx, sz), re, gd, (gvy, gvx, gvz), vel_in), None, None, None)
 
 
 class _ToFeature3DFn(torch.autograd.Function):
@@ -872,6 +898,9 @@ class Karman3DTrainer:
     components), reverse sweep through the HIP adjoints by torch autograd, TF-Adam on the flat parameter buffer
     (sol_adam_tf_step).  gts: [msteps] of (vy, vx, vz) ground-truth frames."""
 
+    buoyancy = property(lambda self: self.sim.physics.buoyancy)
+    nsub = property(lambda self: self.sim.physics.nsub)
+
     def __init__(self, net, scene, B, msteps, std_v, std_re, dt=1.0, res=None, beta1=0.9, beta2=0.999, eps=1e-8, conv_precision="split",
                  use_graph=False, group=None, comm=None, schedule="manual", glue="fused", buoyancy=None, diffusion_substeps=1, **solver):
         """schedule: "manual" (default) = the hand-written forward unroll + reverse sweep over the C ABI (_unrolled_schedule), "autograd" = the
@@ -879,14 +908,10 @@ class Karman3DTrainer:
         use_graph: capture the whole forward unroll + reverse sweep ONCE into a hipGraph over static input buffers (the
         TF1 "build the graph, sess.run many" shape, as trainer.GraphTrainer does for the 2-D mercury model): a step then
         copies the batch in and replays ~3000 launches with one host call.
-        buoyancy=(fy, fx, fz) (buoyancy_force3d): the density pushes the velocity.  The schedule is unchanged; the solver pair is the buoyant
-        one: the forward step is sol_karman3d_step_fwd_buoy and each step's input density is kept, the reverse sweep runs the buoyant
-        velocity adjoint (g_dsum), then the density adjoint accumulating onto the velocity gradients, which carries the density cotangent
-        to the next (earlier) step (None at the last step: the loss does not look at the density).  Off, or zero: today's launches.
-        diffusion_substeps=n (Karman3DFlow): n explicit diffusion substeps per solver step.  Manual schedule: diffuse_sub (M^(n-1) v) before
-        each step's solver launch, the solver pair on the scaled cfg, and diffuse_sub on the velocity cotangent after each step's adjoint
-        in the reverse sweep; the autograd schedule takes it through Karman3DFlow.step.  Kernel launches only, the ping-pong buffers are
-        the simulator's static ones: use_graph stays a graph of kernel nodes.  n = 1: today's launches."""
+        buoyancy=(fy, fx, fz), diffusion_substeps=n: the StepPhysics3D of the simulator (self.sim.physics).  The schedule is unchanged; the
+        solver pair is Karman3DFlow._forward and _step_adjoint3d under it: with a force each step's input density is kept and the density
+        cotangent is carried to the next (earlier) step (None at the last step: the loss does not look at the density).  Kernel launches
+        only, the pre-diffusion's ping-pong buffers are the simulator's static ones: use_graph stays a graph of kernel nodes."""
         from .trainer import _conv_precision_code
         from .dist import DPStep
         _lib.require_gpu()
@@ -895,7 +920,6 @@ class Karman3DTrainer:
         assert glue in ("fused", "torch")
         self.glue = glue          # reverse-sweep glue of the manual schedule: sol_karman3d_correct_bwd / _feature_bwd, or the torch elementwise composition
         self.sim = Karman3DFlow(scene, B, dt=dt, res=res, buoyancy=buoyancy, diffusion_substeps=diffusion_substeps, **solver)
-        self.buoyancy, self.nsub = self.sim.buoyancy, self.sim.nsub
         dev = scene.active.device
         self.std_v = torch.tensor([float(v) for v in std_v], dtype=torch.float32, device=dev)
         self._std_v_host = tuple(float(v) for v in std_v)
@@ -952,26 +976,25 @@ class Karman3DTrainer:
         fs = [1.0 / t for t in self._std_in_host]          # (host copies: a .tolist() of a device tensor is a synchronising copy -- illegal inside a capture)
         sv = self._std_v_host
         v = (vy, vx, vz)
-        keep = []                                   # per step: (saved velocities, network state, d loss_i / d v_i)
-        d_ins = []                                  # buoyant mode: the steps' input densities
+        ph, buoyant = sim.physics, sim.physics.buoyancy is not None
+        keep = []                                   # per step: (saved velocities, network state, d loss_i / d v_i, input density (buoyant mode))
         losses = []
         for i in range(ms):
             saved = [torch.empty_like(t) for t in v]
             feat = torch.empty(B, Y, X, Z, 4, dtype=torch.float32, device=vy.device)
-            if self.buoyancy is not None:
-                d_ins.append(d)
-            d, *v = sim._fwd_sub(d, v[0], v[1], v[2], re, saved, feat, fs, self.buoyancy, self.nsub)
+            d_in = d if buoyant else None
+            d, *v = sim._forward(ph, d, v[0], v[1], v[2], re, saved, feat, fs)[0]
             out, state = sch.forward(feat)
             check(self.lib.sol_karman3d_correct(stream(), ptr(out), net.cout, sv[0], sv[1], sv[2], ptr(v[0]), ptr(v[1]), ptr(v[2]), B, Y, X, Z))
             li, gi = l2_loss_fwd_bwd(v, tuple(g[i] for g in self._gt), sv, gscale=1.0 / ms)
             losses.append(li.reshape(()))
-            keep.append((saved, state, gi))
+            keep.append((saved, state, gi, d_in))
         flat = None
         gin = None
         g_d = None                                  # buoyant mode: the density cotangent carried from step i + 1 to step i
         inv_in = fs[:3]
         for i in range(ms - 1, -1, -1):
-            saved, state, G = keep[i]
+            saved, state, G, d_in = keep[i]
             # G += gin and the adjoint of  v += std * to_staggered(out):  d out[..., c] = std_c * G_c restricted to the faces that received a correction
             # (one launch, zero padded to the four channels the thin-layer launches read; glue="torch": the elementwise composition of rounds 5-6)
             fused_glue = self.glue == "fused" and net.cout == 3
@@ -993,14 +1016,8 @@ class Karman3DTrainer:
                 G[0][:, :Y].add_(dx[..., 0], alpha=inv_in[0])
                 G[1][:, :, :X].add_(dx[..., 1], alpha=inv_in[1])
                 G[2][..., :Z].add_(dx[..., 2], alpha=inv_in[2])
-            if self.buoyancy is not None:
-                *gv, g_dsum = sim._bwd(saved, re, G[0], G[1], G[2], buoyancy=self.buoyancy, g_d=g_d, nsub=self.nsub)
-                g_d, *gin = density_bwd(sim, d_ins[i], saved, re, g_dsum, gv, nsub=self.nsub)
-                d_ins[i] = None
-            else:
-                gin = sim._bwd(saved, re, G[0], G[1], G[2], nsub=self.nsub)
-            if self.nsub > 1 and i > 0:             # the cotangent of M^(n-1) v -> the cotangent of v (the operator is symmetric); nobody reads step 0's
-                gin = list(diffuse_sub(sim, gin[0], gin[1], gin[2], re, self.nsub))
+            # (nobody reads step 0's input cotangent: it is not taken through the pre-diffusion)
+            g_d, *gin, _ = _step_adjoint3d(sim, ph, buoyant, d_in, saved, re, g_d, G, through_substeps=i > 0)
             keep[i] = None                          # (eager runs: the step's activations can go)
         losses = _lib.stack0(losses)
         loss = losses.sum() / ms
@@ -1084,16 +1101,17 @@ class Karman3DRollout:
     """No-grad roll-out: nsteps x [solver step -> features / std -> CNN -> velocity += std * correction]
     (karman_apply.py:138-158 / the forward half of karman_train.py:397-426, three components)."""
 
+    buoyancy = property(lambda self: self.sim.physics.buoyancy)
+    nsub = property(lambda self: self.sim.physics.nsub)
+
     def __init__(self, net, scene, B, std_v, std_re, dt=1.0, res=None, conv_precision="split", buoyancy=None, diffusion_substeps=1, **solver):
-        """buoyancy=(fy, fx, fz) (buoyancy_force3d): the density pushes the velocity (the solver step is sol_karman3d_step_fwd_buoy)
-        diffusion_substeps=n (Karman3DFlow): n explicit diffusion substeps per solver step; the features keep the true re"""
+        """buoyancy=(fy, fx, fz), diffusion_substeps=n: the StepPhysics3D of the simulator (self.sim.physics); the features keep the true re"""
         from .trainer import _conv_precision_code
         from .schedule3d import NetSchedule3D
         _lib.require_gpu()
         self.lib = _lib.load()
         self.net, self.scene, self.B = net, scene, B
         self.sim = Karman3DFlow(scene, B, dt=dt, res=res, buoyancy=buoyancy, diffusion_substeps=diffusion_substeps, **solver)
-        self.buoyancy, self.nsub = self.sim.buoyancy, self.sim.nsub
         self.std_v = tuple(float(v) for v in std_v)
         self.feat_scale = [1.0 / self.std_v[0], 1.0 / self.std_v[1], 1.0 / self.std_v[2], 1.0 / float(std_re)]
         self.conv_precision = _conv_precision_code(conv_precision)

@@ -193,60 +193,31 @@ def register_scene3d(sim):
     return h
 
 
-# the step's three differentiable forms are the modes of karman3d._Karman3DStepFn, as for the 2-D step: karman3d_step (the density is a
-# passive tracer, re is data), karman3d_step_dens (opt-in: the density output is differentiable too) and karman3d_step_re (opt-in:
-# differentiable with respect to re as well; density: d_out stays in the graph as in karman3d_step_dens).  They run the registered
-# simulator's own diffusion_substeps (1 unless it was built with another count); karman3d_step_sub names the count per call
-def _karman3d_fn(d, vy, vx, vz, re, scene, density, want_re):
+# Every differentiable 3-D step op is one mode of karman3d._Karman3DStepFn under one karman3d.StepPhysics3D, as for the 2-D step (all but
+# karman3d_step_sub run the registered simulator's own diffusion_substeps; the first three take no force):
+#   karman3d_step        the density is a passive tracer, re is data
+#   karman3d_step_dens   opt-in: the density output is differentiable too
+#   karman3d_step_re    opt-in: differentiable with respect to re as well; density: d_out stays in the graph
+#   karman3d_step_buoy   the buoyant step, force (fy, fx, fz), density in the graph; (0, 0, 0) is the plain step (without a gradient the
+#                        force is kept as given: the _buoy entry point issues the plain launches)
+#   karman3d_step_sub    nsub explicit diffusion substeps named per call, composing with density, re_grad and a force (fy, fx, fz)
+def _physics3d(scene, op, nsub=None, force=None, keep_zero_force=False):
+    """the StepPhysics3D of an op's arguments, validated; nsub=None: the registered simulator's own count"""
     from . import karman3d as k3
-    re = _lib.f32(re)
-    want_re = want_re and torch.is_grad_enabled() and re.requires_grad
-    sim = _SIMS3D[scene]
-    return k3._Karman3DStepFn.apply(sim, _lib.f32(d), _lib.f32(vy), _lib.f32(vx), _lib.f32(vz), re, density, want_re, None, sim.nsub)
+    return k3.StepPhysics3D.of(force, diffusion_substeps=_SIMS3D[scene].nsub if nsub is None else nsub, who="torch.ops.sol.%s: nsub" % op,
+                               keep_zero_force=keep_zero_force)
 
 
-def _karman3d_step(d, vy, vx, vz, re, scene):
-    return _karman3d_fn(d, vy, vx, vz, re, scene, False, False)
+def _karman3d_apply(scene, tensors, density, re_grad, ph):
+    from . import karman3d as k3
+    d, vy, vx, vz, re = (_lib.f32(t) for t in tensors)
+    return k3._Karman3DStepFn.apply(_SIMS3D[scene], d, vy, vx, vz, re, bool(density), _want_re(re_grad, re), ph.moving())
 
 
-# karman3d_step_buoy: the buoyant mode of karman3d._Karman3DStepFn (a force of (0, 0, 0) is the plain step, density in the graph)
-def _karman3d_buoy(d, vy, vx, vz, re, scene, fy, fx, fz, re_grad=False):
+def _karman3d_nograd(scene, tensors, ph):
+    """no gradient wanted: the forward launches, nothing kept"""
     with torch.no_grad():
-        sim = _SIMS3D[scene]
-        return sim._fwd_sub(*(_lib.f32(t) for t in (d, vy, vx, vz, re)), buoyancy=(float(fy), float(fx), float(fz)), nsub=sim.nsub)
-
-
-def _karman3d_buoy_fn(d, vy, vx, vz, re, scene, fy, fx, fz, re_grad=False):
-    from . import karman3d as k3
-    f = k3.buoyancy_force3d((fy, fx, fz))
-    re = _lib.f32(re)
-    want_re = bool(re_grad) and torch.is_grad_enabled() and re.requires_grad
-    sim = _SIMS3D[scene]
-    return k3._Karman3DStepFn.apply(sim, _lib.f32(d), _lib.f32(vy), _lib.f32(vx), _lib.f32(vz), re, True, want_re,
-                                    f if k3._buoyant3d(f) else None, sim.nsub)
-
-
-# karman3d_step_sub: the step with nsub explicit diffusion substeps (karman3d._Karman3DStepFn's substep mode), composing with the other
-# modes: density (d_out in the graph), re_grad and a buoyancy force (fy, fx, fz)
-def _karman3d_sub_args(nsub, fy, fx, fz):
-    from . import karman3d as k3
-    n = ops.diffusion_substeps_arg(nsub, "torch.ops.sol.karman3d_step_sub: nsub")
-    f = k3.buoyancy_force3d((fy, fx, fz))
-    return n, (f if k3._buoyant3d(f) else None)
-
-
-def _karman3d_sub(d, vy, vx, vz, re, scene, nsub, density=False, re_grad=False, fy=0.0, fx=0.0, fz=0.0):
-    n, f = _karman3d_sub_args(nsub, fy, fx, fz)
-    with torch.no_grad():
-        return _SIMS3D[scene]._fwd_sub(*(_lib.f32(t) for t in (d, vy, vx, vz, re)), buoyancy=f, nsub=n)
-
-
-def _karman3d_sub_fn(d, vy, vx, vz, re, scene, nsub, density=False, re_grad=False, fy=0.0, fx=0.0, fz=0.0):
-    from . import karman3d as k3
-    n, f = _karman3d_sub_args(nsub, fy, fx, fz)
-    re = _lib.f32(re)
-    want_re = bool(re_grad) and torch.is_grad_enabled() and re.requires_grad
-    return k3._Karman3DStepFn.apply(_SIMS3D[scene], _lib.f32(d), _lib.f32(vy), _lib.f32(vx), _lib.f32(vz), re, bool(density), want_re, f, n)
+        return _SIMS3D[scene]._forward(ph, *(_lib.f32(t) for t in tensors))[0]
 
 
 def _karman3d_density_bwd(d, svy, svx, svz, re, gd, scene):
@@ -259,12 +230,19 @@ def _conv3d(x, w, b, residual, lrelu, slope):
     return k3._Conv3DFn.apply(x, w, b, residual, lrelu, slope, None)
 
 
-_LIB.impl("karman3d_step", _karman3d_step, "AutogradCUDA")
-_LIB.impl("karman3d_step_dens", lambda d, vy, vx, vz, re, scene: _karman3d_fn(d, vy, vx, vz, re, scene, True, False), "AutogradCUDA")
-_LIB.impl("karman3d_step_re", lambda d, vy, vx, vz, re, scene, density=False: _karman3d_fn(d, vy, vx, vz, re, scene, bool(density), True), "AutogradCUDA")
-_LIB.impl("karman3d_step_buoy", _karman3d_buoy, "CUDA")
-_LIB.impl("karman3d_step_buoy", _karman3d_buoy_fn, "AutogradCUDA")
-_LIB.impl("karman3d_step_sub", _karman3d_sub, "CUDA")
-_LIB.impl("karman3d_step_sub", _karman3d_sub_fn, "AutogradCUDA")
+_LIB.impl("karman3d_step", lambda d, vy, vx, vz, re, scene: _karman3d_apply(scene, (d, vy, vx, vz, re), False, False, _physics3d(scene, "karman3d_step")),
+          "AutogradCUDA")
+_LIB.impl("karman3d_step_dens", lambda d, vy, vx, vz, re, scene: _karman3d_apply(scene, (d, vy, vx, vz, re), True, False, _physics3d(scene, "karman3d_step_dens")),
+          "AutogradCUDA")
+_LIB.impl("karman3d_step_re", lambda d, vy, vx, vz, re, scene, density=False:
+          _karman3d_apply(scene, (d, vy, vx, vz, re), density, True, _physics3d(scene, "karman3d_step_re")), "AutogradCUDA")
+_LIB.impl("karman3d_step_buoy", lambda d, vy, vx, vz, re, scene, fy, fx, fz, re_grad=False:
+          _karman3d_nograd(scene, (d, vy, vx, vz, re), _physics3d(scene, "karman3d_step_buoy", None, (fy, fx, fz), keep_zero_force=True)), "CUDA")
+_LIB.impl("karman3d_step_buoy", lambda d, vy, vx, vz, re, scene, fy, fx, fz, re_grad=False:
+          _karman3d_apply(scene, (d, vy, vx, vz, re), True, re_grad, _physics3d(scene, "karman3d_step_buoy", None, (fy, fx, fz))), "AutogradCUDA")
+_LIB.impl("karman3d_step_sub", lambda d, vy, vx, vz, re, scene, nsub, density=False, re_grad=False, fy=0.0, fx=0.0, fz=0.0:
+          _karman3d_nograd(scene, (d, vy, vx, vz, re), _physics3d(scene, "karman3d_step_sub", nsub, (fy, fx, fz))), "CUDA")
+_LIB.impl("karman3d_step_sub", lambda d, vy, vx, vz, re, scene, nsub, density=False, re_grad=False, fy=0.0, fx=0.0, fz=0.0:
+          _karman3d_apply(scene, (d, vy, vx, vz, re), density, re_grad, _physics3d(scene, "karman3d_step_sub", nsub, (fy, fx, fz))), "AutogradCUDA")
 _LIB.impl("karman3d_density_bwd", _karman3d_density_bwd, "CUDA")
 _LIB.impl("conv3d", _conv3d, "AutogradCUDA")
