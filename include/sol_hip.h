@@ -433,8 +433,8 @@ int sol_karman_diffuse_sub(const sol_karman_cfg* cfg, void* stream, const float*
  *     hand: (d_in, sv_y, sv_x) -> (d_out, a_y, a_x) masked / with inflow as above; cotangents of those -> (g_d_in, g_sv_y, g_sv_x).
  *     tile_window: 1 = LDS windows, 0 = global atomics only.  Workspaces: sol_karman_advect_workspace_bytes(cfg, advection) (0 bytes and
  *     NULL for advection = 0), sol_karman_advect_bwd_workspace_bytes(cfg).
- * None of these synchronises, allocates or reads anything on the host: capturable.  karman-3d and the one-workgroup kernels advect
- * semi-Lagrangian only. */
+ * None of these synchronises, allocates or reads anything on the host: capturable.  The one-workgroup kernels advect
+ * semi-Lagrangian only; karman-3d has its own form ("MACCORMACK ADVECTION on the karman-3d step" below). */
 size_t sol_karman_advect_workspace_bytes(const sol_karman_cfg* cfg, int32_t advection);
 int sol_karman_advect(const sol_karman_cfg* cfg, void* stream, const float* d_in, const float* svy, const float* svx,
                       const float* active, const float* inflow, int32_t advection, float correction_strength,
@@ -1002,6 +1002,82 @@ int sol_karman3d_diffuse_sub(const sol_karman3d_cfg* cfg, void* stream,
                              const float* vy_in, const float* vx_in, const float* vz_in, const float* re,
                              float* vy_out, float* vx_out, float* vz_out,
                              int32_t m, int32_t chunk, void* workspace, size_t workspace_bytes);
+/* MACCORMACK ADVECTION on the karman-3d step (csrc/karman3d_maccormack.hip; advection = "mac_cormack" on the Python surface): the
+ * definition of "MACCORMACK ADVECTION on the large-grid step" above with a third axis.  c = (sv_y, sv_x, sv_z); f is c_y, c_x or c_z on its
+ * own faces or the density on cells (inflow added first when cfg.inflow_before); u is c at the array's sample point by exactly the
+ * expressions of k3_advect (own component stored, the others averaged over four faces with clamped indices, cells as two-face means);
+ * S_g is the TRILINEAR sample in the array's own mode; lo, hi = min, max of the EIGHT values the first gather read.  Tie rule (inclusive,
+ * no tolerance), NaN rule (a NaN cor reverts to h) and the fp32 spelling cor = fl(h + fl(fl(0.5f s) * fl(f - b))), contraction off, carry
+ * over; h is ONE spelled-out trilinear expression (z pairs first, then x, then y) wherever it is evaluated.  Parity with PhiFlow is
+ * unpinned, as for 2-D.  Forward: two launches (k3m_hat: h of the four arrays to the workspace; k3m_out: b, limiter, mask / inflow) in
+ * place of the advection launch.  Gradient: every decision frozen as the forward took it; h recomputed from the saved c (nothing new is
+ * saved).  Stage A (k3m_vel_adj / k3m_den_adj, global int64 atomics): g_f += (s/2) kept g; g_b = -(s/2) kept g scattered through the eight
+ * corners of the gather at x + u dt into accumulators G_h; g_u += (dt/dx) g_b dS_h/d(offset), a face's onto the nine samples that formed
+ * u, a cell's into gU.  Stage B: the EXISTING semi-Lagrangian adjoint kernels (k3b_advect_adj*, k3d_advect_adj*, their LDS-window options
+ * included) on g_h = g + G_h.  Every scattered sum is 64-bit fixed point with the one scale of its cotangent: bit-reproducible; a
+ * non-finite cotangent poisons its own simulation only.
+ *   sol_karman3d_step_fwd_adv: every argument of sol_karman3d_step_fwd_buoy, then advection (0 semi-Lagrangian: that form's launches, bits
+ *     and workspace size; 1 MacCormack) and correction_strength (checked to lie in [0, 1] for either).  A zero force is the unbuoyant
+ *     step.  Workspace: sol_karman3d_step_fwd_adv_workspace_bytes(cfg, advection).
+ *   sol_karman3d_step_bwd_adv / _adv_re: every argument of the _buoy / _buoy_re form, then the same two; with a zero force g_d_out and
+ *     g_dsum may be NULL.  sol_karman3d_density_bwd_adv / _adv_re: every argument of the plain / _re form, then the same two.  Workspaces:
+ *     sol_karman3d_step_bwd_adv_workspace_bytes / sol_karman3d_density_bwd_adv_workspace_bytes(cfg, with_re, advection).
+ *   sol_karman3d_advect / sol_karman3d_advect_bwd: the stage alone and its transpose, any Y, X, Z >= 8 (odd extents included), for tests
+ *     and callers that compose by hand: (d_in, sv_y, sv_x, sv_z) -> (d_out, a_y, a_x, a_z) masked / with inflow as above; cotangents of
+ *     those -> (g_d_in, g_sv_y, g_sv_x, g_sv_z).  advection = 0 is the plain stage.  tile_window: 1 = the semi-Lagrangian scatters through
+ *     their LDS windows where the grid admits them (velocity: Z <= 64), 0 = global atomics only; equal bits.  Workspaces:
+ *     sol_karman3d_advect_workspace_bytes(cfg, advection) (0 bytes and NULL for advection = 0), sol_karman3d_advect_bwd_workspace_bytes(cfg).
+ * None of these synchronises, allocates or reads anything on the host: capturable. */
+size_t sol_karman3d_advect_workspace_bytes(const sol_karman3d_cfg* cfg, int32_t advection);
+int sol_karman3d_advect(const sol_karman3d_cfg* cfg, void* stream, const float* d_in, const float* svy, const float* svx, const float* svz,
+                        const float* active, const float* inflow, int32_t advection, float correction_strength,
+                        float* d_out, float* ay, float* ax, float* az, void* workspace, size_t workspace_bytes);
+size_t sol_karman3d_advect_bwd_workspace_bytes(const sol_karman3d_cfg* cfg);
+int sol_karman3d_advect_bwd(const sol_karman3d_cfg* cfg, void* stream, const float* d_in, const float* svy, const float* svx, const float* svz,
+                            const float* active, const float* inflow, int32_t advection, float correction_strength,
+                            const float* g_d_out, const float* g_ay, const float* g_ax, const float* g_az,
+                            float* g_d_in, float* g_svy, float* g_svx, float* g_svz, int32_t tile_window, void* workspace, size_t workspace_bytes);
+size_t sol_karman3d_step_fwd_adv_workspace_bytes(const sol_karman3d_cfg* cfg, int32_t advection);
+int sol_karman3d_step_fwd_adv(const sol_karman3d_cfg* cfg, void* stream,
+                              const float* d_in, const float* vy_in, const float* vx_in, const float* vz_in,
+                              const float* re, const float* active, const float* inflow,
+                              const float* velBCy, const float* velBCyMask, int64_t bc_batch_stride,
+                              float* d_out, float* vy_out, float* vx_out, float* vz_out,
+                              float* saved_vy, float* saved_vx, float* saved_vz,
+                              float* feat_out, const float* feat_scale, const int32_t* direct_header_host,
+                              void* workspace, size_t workspace_bytes, float fy, float fx, float fz,
+                              int32_t advection, float correction_strength);
+size_t sol_karman3d_step_bwd_adv_workspace_bytes(const sol_karman3d_cfg* cfg, int32_t with_re, int32_t advection);
+int sol_karman3d_step_bwd_adv(const sol_karman3d_cfg* cfg, void* stream,
+                              const float* saved_vy, const float* saved_vx, const float* saved_vz,
+                              const float* re, const float* active, const float* velBCyMask, int64_t bc_batch_stride,
+                              const float* g_vy_out, const float* g_vx_out, const float* g_vz_out,
+                              float* g_vy_in, float* g_vx_in, float* g_vz_in,
+                              const int32_t* direct_header_host, void* workspace, size_t workspace_bytes,
+                              float fy, float fx, float fz, const float* g_d_out, float* g_dsum,
+                              int32_t advection, float correction_strength);
+int sol_karman3d_step_bwd_adv_re(const sol_karman3d_cfg* cfg, void* stream,
+                                 const float* saved_vy, const float* saved_vx, const float* saved_vz,
+                                 const float* re, const float* active, const float* velBCyMask, int64_t bc_batch_stride,
+                                 const float* g_vy_out, const float* g_vx_out, const float* g_vz_out,
+                                 float* g_vy_in, float* g_vx_in, float* g_vz_in,
+                                 const int32_t* direct_header_host, void* workspace, size_t workspace_bytes,
+                                 const float* vy_in, const float* vx_in, const float* vz_in, float* g_re, int accumulate_re,
+                                 float fy, float fx, float fz, const float* g_d_out, float* g_dsum,
+                                 int32_t advection, float correction_strength);
+size_t sol_karman3d_density_bwd_adv_workspace_bytes(const sol_karman3d_cfg* cfg, int32_t with_re, int32_t advection);
+int sol_karman3d_density_bwd_adv(const sol_karman3d_cfg* cfg, void* stream,
+                                 const float* d_in, const float* inflow, const float* saved_vy, const float* saved_vx, const float* saved_vz,
+                                 const float* re, const float* velBCyMask, int64_t bc_batch_stride,
+                                 const float* g_d_out, float* g_d_in, float* g_vy_in, float* g_vx_in, float* g_vz_in, int accumulate,
+                                 void* workspace, size_t workspace_bytes, int32_t advection, float correction_strength);
+int sol_karman3d_density_bwd_adv_re(const sol_karman3d_cfg* cfg, void* stream,
+                                    const float* d_in, const float* inflow, const float* saved_vy, const float* saved_vx, const float* saved_vz,
+                                    const float* re, const float* velBCyMask, int64_t bc_batch_stride,
+                                    const float* g_d_out, float* g_d_in, float* g_vy_in, float* g_vx_in, float* g_vz_in, int accumulate,
+                                    void* workspace, size_t workspace_bytes,
+                                    const float* vy_in, const float* vx_in, const float* vz_in, float* g_re, int accumulate_re,
+                                    int32_t advection, float correction_strength);
 /* The step's pressure solve alone: M p = rhs with M = -A for the scene's `active` mask (the solver cfg->pressure_solver selects;
  * the CG solve reports to cfg->cg_info).  rhs, p [B,Y,X,Z] (rhs is read only); workspace: sol_karman3d_step_workspace_bytes(cfg). */
 int sol_karman3d_pressure_solve(const sol_karman3d_cfg* cfg, void* stream, const float* active, const float* rhs, float* p,

@@ -168,6 +168,23 @@ _SIGS = {
     "sol_karman3d_step_bwd_buoy": (C.c_int, [C.POINTER(Karman3DCfg), _P] + [_P] * 6 + [C.c_int64] + [_P] * 6 + [_P, _P, C.c_size_t] + [C.c_float] * 3 + [_P] * 2),
     "sol_karman3d_step_bwd_buoy_re": (C.c_int, [C.POINTER(Karman3DCfg), _P] + [_P] * 6 + [C.c_int64] + [_P] * 6 + [_P, _P, C.c_size_t] + [_P] * 4 + [C.c_int]
                                       + [C.c_float] * 3 + [_P] * 2),
+    # MacCormack advection on the karman-3d step: the stage alone, its transpose, and the _adv forms (the _buoy arguments + advection, strength)
+    "sol_karman3d_advect_workspace_bytes": (C.c_size_t, [C.POINTER(Karman3DCfg), C.c_int32]),
+    "sol_karman3d_advect": (C.c_int, [C.POINTER(Karman3DCfg), _P] + [_P] * 6 + [C.c_int32, C.c_float] + [_P] * 5 + [C.c_size_t]),
+    "sol_karman3d_advect_bwd_workspace_bytes": (C.c_size_t, [C.POINTER(Karman3DCfg)]),
+    "sol_karman3d_advect_bwd": (C.c_int, [C.POINTER(Karman3DCfg), _P] + [_P] * 6 + [C.c_int32, C.c_float] + [_P] * 8 + [C.c_int32, _P, C.c_size_t]),
+    "sol_karman3d_step_fwd_adv_workspace_bytes": (C.c_size_t, [C.POINTER(Karman3DCfg), C.c_int32]),
+    "sol_karman3d_step_fwd_adv": (C.c_int, [C.POINTER(Karman3DCfg), _P] + [_P] * 9 + [C.c_int64] + [_P] * 8 + [C.POINTER(C.c_float), _P, _P, C.c_size_t] + [C.c_float] * 3
+                                  + [C.c_int32, C.c_float]),
+    "sol_karman3d_step_bwd_adv_workspace_bytes": (C.c_size_t, [C.POINTER(Karman3DCfg), C.c_int32, C.c_int32]),
+    "sol_karman3d_step_bwd_adv": (C.c_int, [C.POINTER(Karman3DCfg), _P] + [_P] * 6 + [C.c_int64] + [_P] * 6 + [_P, _P, C.c_size_t] + [C.c_float] * 3 + [_P] * 2
+                                  + [C.c_int32, C.c_float]),
+    "sol_karman3d_step_bwd_adv_re": (C.c_int, [C.POINTER(Karman3DCfg), _P] + [_P] * 6 + [C.c_int64] + [_P] * 6 + [_P, _P, C.c_size_t] + [_P] * 4 + [C.c_int]
+                                     + [C.c_float] * 3 + [_P] * 2 + [C.c_int32, C.c_float]),
+    "sol_karman3d_density_bwd_adv_workspace_bytes": (C.c_size_t, [C.POINTER(Karman3DCfg), C.c_int32, C.c_int32]),
+    "sol_karman3d_density_bwd_adv": (C.c_int, [C.POINTER(Karman3DCfg), _P] + [_P] * 7 + [C.c_int64] + [_P] * 5 + [C.c_int, _P, C.c_size_t] + [C.c_int32, C.c_float]),
+    "sol_karman3d_density_bwd_adv_re": (C.c_int, [C.POINTER(Karman3DCfg), _P] + [_P] * 7 + [C.c_int64] + [_P] * 5 + [C.c_int, _P, C.c_size_t] + [_P] * 4 + [C.c_int]
+                                        + [C.c_int32, C.c_float]),
     "sol_karman3d_buoyancy_add": (C.c_int, [_P] + [C.c_int32] * 4 + [_P] * 2 + [C.c_float] * 3 + [_P] * 3),
     "sol_karman3d_buoyancy_add_bwd": (C.c_int, [_P] + [C.c_int32] * 4 + [_P] * 4 + [C.c_float] * 3 + [_P] * 2),
     "sol_karman3d_diffuse_sub_max": (C.c_int32, []),

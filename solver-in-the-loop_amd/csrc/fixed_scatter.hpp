@@ -43,17 +43,30 @@ __device__ __forceinline__ void fx_scale(const unsigned* gmax_b, float& qs, floa
 // atomic per workgroup: thousands of workgroups share the slots and same-address atomics serialise in the L2 (~0.3 us apiece), so a
 // workgroup whose maximum does not exceed what its slot already holds publishes nothing; the maximum is order independent, the filter
 // changes nothing but the number of atomics.
+// (the two pieces of it: what a wave publishes -- the bits of its maximum, of a NaN when it met a non-finite value -- and the workgroup's
+// filtered atomic into its slot)
+__device__ __forceinline__ unsigned fx_wave_bits(float vmax, bool bad) { return amax_wave_max(bad ? 0x7fc00000u : __float_as_uint(vmax)); }
+__device__ __forceinline__ void fx_slot_max(unsigned* slots_b, const unsigned* red) {
+    unsigned mb = 0u;
+    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) mb = max(mb, red[w]);
+    unsigned* slot = &slots_b[blockIdx.x & (FX_SLOTS - 1)];
+    if (mb > __atomic_load_n(slot, __ATOMIC_RELAXED)) atomicMax(slot, mb);
+}
 __device__ __forceinline__ void fx_publish_max(unsigned* slots_b, float vmax, bool bad) {
     __shared__ unsigned red[16];
-    const unsigned wmax = amax_wave_max(bad ? 0x7fc00000u : __float_as_uint(vmax));
+    const unsigned wmax = fx_wave_bits(vmax, bad);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = wmax;
     __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned mb = 0u;
-        for (int w = 0; w < (int)(blockDim.x >> 6); ++w) mb = max(mb, red[w]);
-        unsigned* slot = &slots_b[blockIdx.x & (FX_SLOTS - 1)];
-        if (mb > __atomic_load_n(slot, __ATOMIC_RELAXED)) atomicMax(slot, mb);
-    }
+    if (threadIdx.x == 0) fx_slot_max(slots_b, red);
+}
+// the same for TWO cotangents of one kernel (the stage-alone MacCormack adjoint: velocity and density), one barrier: thread 0 publishes
+// the first, thread 1 the second.  Once per kernel, like fx_publish_max, and not in a kernel that also calls that.
+__device__ __forceinline__ void fx_publish_max2(unsigned* slots_a, float vmax_a, bool bad_a, unsigned* slots_b, float vmax_b, bool bad_b) {
+    __shared__ unsigned red[2][16];
+    const unsigned wa = fx_wave_bits(vmax_a, bad_a), wb = fx_wave_bits(vmax_b, bad_b);
+    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = wa; red[1][threadIdx.x >> 6] = wb; }
+    __syncthreads();
+    if (threadIdx.x < 2) fx_slot_max(threadIdx.x == 0 ? slots_a : slots_b, red[threadIdx.x]);
 }
 
 // one contribution: rounded to the grid first, then an integer add -- to an accumulator in global memory, or to a cell of an LDS window

@@ -14,6 +14,8 @@
 //                   trilinear gather and every cross-component average of the tile is served from LDS, lanes run along z
 //                   (conflict free, coalesced stores); samples that leave the halo (CFL > 1) fall back to global reads.
 //                   (k3_advect: the same arithmetic straight from global memory -- option k3d_tile = 0, and any Z > 64.)
+//   (k3m_hat, k3m_out  optional, sol_karman3d_step_fwd_adv with advection = 1: the MacCormack advection in place of the advection launch --
+//                   karman3d_maccormack.hip; karman3d_advect.hpp holds what it shares with the adjoint below)
 //   (k3_buoyancy    optional, sol_karman3d_step_fwd_buoy: the step's output density pushes the advected velocity -- karman3d_buoyancy.hip)
 //   k3_div          rhs = -div
 //   pressure        DIRECT solve x = G (b - U_S E_SS x_S), x_S = (I + G_SS E_SS)^-1 (G b)_S with G = the empty-box Dirichlet
@@ -25,6 +27,7 @@
 // with respect to the Reynolds number from the g_c they leave behind (karman3d_re_bwd.hip).  The adjoint of the marker density is a set
 // of launches of its own (karman3d_density_bwd.hip).
 #include "fixed_scatter.hpp"
+#include "karman3d_advect.hpp"
 #include "karman3d_mask.hpp"
 #include "karman3d_re.hpp"
 
@@ -80,18 +83,8 @@ __global__ void __launch_bounds__(256) k3_diffuse(K3Args a) {
 
 // (hard-BC face masks from the `active` cell mask: acc_at, face_mask<AX> of karman3d_mask.hpp)
 
-// ---- readers of the diffused components: straight from global memory, or from the workgroup's LDS tile ----------------
-struct GlobalReader {
-    const float *sy, *sx, *sz;
-    const float* act;                 // the scene's `active` cell mask [Y][X][Z]
-    int Y, X, Z;
-    // accessible mask at a cell index that may lie one cell outside the domain ('boundary' extrapolation: edge value)
-    __device__ __forceinline__ float acc(int j, int i, int k) const { return acc_at(act, Y, X, Z, j, i, k); }
-    __device__ __forceinline__ float y(int j, int i, int k) const { return sy[((size_t)j * X + i) * Z + k]; }
-    __device__ __forceinline__ float x(int j, int i, int k) const { return sx[((size_t)j * (X + 1) + i) * Z + k]; }
-    __device__ __forceinline__ float z(int j, int i, int k) const { return sz[((size_t)j * X + i) * (Z + 1) + k]; }
-};
-constexpr int T3 = 8;          // tile edge (cells) in y and x
+// ---- readers of the diffused components: straight from global memory (GlobalReader, karman3d_advect.hpp), or from the workgroup's LDS tile
+constexpr int T3 = 8;         // tile edge (cells) in y and x
 constexpr int HL3 = 2;         // halo cells
 constexpr int TR = T3 + 2 * HL3;      // cell rows / columns of the tile region (12); face arrays have one more along their axis
 struct TileReader {
@@ -136,11 +129,6 @@ __device__ __forceinline__ float tri_clamp(const R& r, int j, float oy, int i, f
     const float c11 = (1.f - wz) * rd(j1, i1, k0) + wz * rd(j1, i1, k1);
     return (1.f - wy) * ((1.f - wx) * c00 + wx * c01) + wy * ((1.f - wx) * c10 + wx * c11);
 }
-struct GR : GlobalReader {
-    __device__ __forceinline__ int g_Y() const { return Y; }
-    __device__ __forceinline__ int g_X() const { return X; }
-    __device__ __forceinline__ int g_Z() const { return Z; }
-};
 struct TRd : TileReader {
     __device__ __forceinline__ int g_Y() const { return g.Y; }
     __device__ __forceinline__ int g_X() const { return g.X; }
@@ -780,21 +768,7 @@ int pressure_solve_any3d(hipStream_t s, const sol_karman3d_cfg* c, const int32_t
 //   k3b_diffuse_adj g_in = (I + alpha L^T)(g_c . (1 - bcm))  (gather form of the transposed replicate-padded Laplacian; converts
 //                  the fixed-point g_c back to fp32 as it reads it)
 // ========================================================================================================================
-struct K3BArgs {
-    int B, Y, X, Z;
-    float dtdx, adt;
-    int grad_pad;
-    const float *re, *active, *bcm;
-    long bc_stride;
-    const float *svy, *svx, *svz;           // saved post-diffusion velocity
-    const float *goy, *gox, *goz;           // gradient w.r.t. the step's output velocity
-    float *gay, *gax, *gaz;                 // g_a
-    long long *gcy, *gcx, *gcz;             // g_c: int64 fixed-point accumulators (zeroed by k3b_rhs before the scatter)
-    unsigned* gmax;                         // [B][FX_SLOTS] bits of max|g_a| per simulation (zeroed by k3b_rhs, published by k3b_gva)
-    float *giy, *gix, *giz;                 // result: gradient w.r.t. the step's input velocity
-    float* rhs;
-    const float* gdiv;
-};
+// (K3BArgs, the adders GAdd / TAdd and advect_adj_point: karman3d_advect.hpp, shared with the MacCormack advection)
 
 template <int AX>
 __device__ __forceinline__ bool boundary_face(int Y, int X, int Z, int j, int i, int k) {
@@ -861,99 +835,6 @@ __global__ void __launch_bounds__(256) k3b_gva(K3BArgs a) {
         }
     }
     fx_publish_max(a.gmax + b * FX_SLOTS, vmax, bad);      // max|g_a| of this simulation -> the scale of the fixed-point scatter
-}
-
-// Where a contribution goes (fx_add).  GAdd: straight into the int64 accumulators in global memory.  TAdd (k3b_advect_adj_tile): into the
-// workgroup's int64 LDS window when the target face lies inside it, else into global memory.
-struct GAdd {
-    long long *gy, *gx, *gz;
-    float qs;
-    int X, Z;
-    __device__ __forceinline__ long long* at(int comp, int jj, int ii, int kk) const {
-        return comp == 0 ? gy + ((size_t)jj * X + ii) * Z + kk : (comp == 1 ? gx + ((size_t)jj * (X + 1) + ii) * Z + kk : gz + ((size_t)jj * X + ii) * (Z + 1) + kk);
-    }
-    __device__ __forceinline__ void operator()(int comp, int jj, int ii, int kk, float v) const { fx_add(at(comp, jj, ii, kk), v, qs); }
-};
-constexpr int K3B_TJ = 4, K3B_TH = 2, K3B_TW = K3B_TJ + 2 * K3B_TH;      // tile of 4 x 4 columns, window of 8 x 8 columns (halo 2: CFL < 2)
-struct TAdd {
-    GAdd g;
-    unsigned long long* L;         // [3][K3B_TW][K3B_TW][ZP]
-    int jw0, iw0, ZP;
-    __device__ __forceinline__ void operator()(int comp, int jj, int ii, int kk, float v) const {
-        const int lj = jj - jw0, li = ii - iw0;
-        if ((unsigned)lj < (unsigned)K3B_TW && (unsigned)li < (unsigned)K3B_TW) fx_add(&L[((comp * K3B_TW + lj) * K3B_TW + li) * ZP + kk], v, g.qs);
-        else g(comp, jj, ii, kk, v);
-    }
-};
-
-// adjoint of one advected face value of component C at (j, i, k): gs = g_a there
-template <int C, class Add>
-__device__ __forceinline__ void advect_adj_point(const K3BArgs& a, const GR& r, const Add& add, int j, int i, int k, float gs) {
-    // no fused multiply-adds here: which products the compiler contracts depends on the kernel this is inlined into, and the two scatter
-    // kernels (global atomics / LDS window) are held to the SAME BITS by the test suite (the integer accumulation is exact, so the only
-    // freedom is in the fp32 contributions themselves)
-#pragma clang fp contract(off)
-    const int Y = a.Y, X = a.X, Z = a.Z;
-    // velocity at the sample point, exactly as the forward pass forms it
-    float uy, ux, uz;
-    int ja, jb, ia, ib, ka, kb;
-    if (C == 0) {
-        ja = max(j - 1, 0); jb = min(j, Y - 1);
-        uy = r.y(j, i, k);
-        ux = 0.25f * (r.x(ja, i, k) + r.x(ja, i + 1, k) + r.x(jb, i, k) + r.x(jb, i + 1, k));
-        uz = 0.25f * (r.z(ja, i, k) + r.z(ja, i, k + 1) + r.z(jb, i, k) + r.z(jb, i, k + 1));
-    } else if (C == 1) {
-        ia = max(i - 1, 0); ib = min(i, X - 1);
-        ux = r.x(j, i, k);
-        uy = 0.25f * (r.y(j, ia, k) + r.y(j, ib, k) + r.y(j + 1, ia, k) + r.y(j + 1, ib, k));
-        uz = 0.25f * (r.z(j, ia, k) + r.z(j, ia, k + 1) + r.z(j, ib, k) + r.z(j, ib, k + 1));
-    } else {
-        ka = max(k - 1, 0); kb = min(k, Z - 1);
-        uz = r.z(j, i, k);
-        uy = 0.25f * (r.y(j, i, ka) + r.y(j, i, kb) + r.y(j + 1, i, ka) + r.y(j + 1, i, kb));
-        ux = 0.25f * (r.x(j, i, ka) + r.x(j, i, kb) + r.x(j, i + 1, ka) + r.x(j, i + 1, kb));
-    }
-    const float oy = -uy * a.dtdx, ox = -ux * a.dtdx, oz = -uz * a.dtdx;
-    const int n0 = Y + (C == 0), n1 = X + (C == 1), n2 = Z + (C == 2);
-    const float fy = floorf(oy), fx = floorf(ox), fz = floorf(oz);
-    const float wy = oy - fy, wx = ox - fx, wz = oz - fz;
-    const int j0 = clampi(j + (int)fy, 0, n0 - 1), j1 = clampi(j + (int)fy + 1, 0, n0 - 1);
-    const int i0 = clampi(i + (int)fx, 0, n1 - 1), i1 = clampi(i + (int)fx + 1, 0, n1 - 1);
-    const int k0 = clampi(k + (int)fz, 0, n2 - 1), k1 = clampi(k + (int)fz + 1, 0, n2 - 1);
-    auto val = [&](int jj, int ii, int kk) { return C == 0 ? r.y(jj, ii, kk) : (C == 1 ? r.x(jj, ii, kk) : r.z(jj, ii, kk)); };
-    float dy = 0.f, dx = 0.f, dz = 0.f;          // d(sample) / d(offset) along each axis
-#pragma unroll
-    for (int cj = 0; cj < 2; ++cj)
-#pragma unroll
-        for (int ci = 0; ci < 2; ++ci)
-#pragma unroll
-            for (int ck = 0; ck < 2; ++ck) {
-                const int jj = cj ? j1 : j0, ii = ci ? i1 : i0, kk = ck ? k1 : k0;
-                const float by = cj ? wy : 1.f - wy, bx = ci ? wx : 1.f - wx, bz = ck ? wz : 1.f - wz;
-                const float v = val(jj, ii, kk);
-                add(C, jj, ii, kk, by * bx * bz * gs);          // field term
-                dy += (cj ? 1.f : -1.f) * bx * bz * v;
-                dx += by * (ci ? 1.f : -1.f) * bz * v;
-                dz += by * bx * (ck ? 1.f : -1.f) * v;
-            }
-    // back-trace term: offset_a = -dtdx * u_a(x0)
-    const float guy = -a.dtdx * gs * dy, gux = -a.dtdx * gs * dx, guz = -a.dtdx * gs * dz;
-    if (C == 0) {
-        add(0, j, i, k, guy);
-        const float qx = 0.25f * gux, qz = 0.25f * guz;
-        add(1, ja, i, k, qx); add(1, ja, i + 1, k, qx); add(1, jb, i, k, qx); add(1, jb, i + 1, k, qx);
-        add(2, ja, i, k, qz); add(2, ja, i, k + 1, qz); add(2, jb, i, k, qz); add(2, jb, i, k + 1, qz);
-    } else if (C == 1) {
-        add(1, j, i, k, gux);
-        const float qy = 0.25f * guy, qz = 0.25f * guz;
-        add(0, j, ia, k, qy); add(0, j, ib, k, qy); add(0, j + 1, ia, k, qy); add(0, j + 1, ib, k, qy);
-        add(2, j, ia, k, qz); add(2, j, ia, k + 1, qz); add(2, j, ib, k, qz); add(2, j, ib, k + 1, qz);
-    } else {
-        add(2, j, i, k, guz);
-        const float qy = 0.25f * guy, qx = 0.25f * gux;
-        add(0, j, i, ka, qy); add(0, j, i, kb, qy); add(0, j + 1, i, ka, qy); add(0, j + 1, i, kb, qy);
-        add(1, j, i, ka, qx); add(1, j, i, kb, qx); add(1, j, i + 1, ka, qx); add(1, j, i + 1, kb, qx);
-    }
 }
 
 __global__ void __launch_bounds__(256) k3b_advect_adj(K3BArgs a) {
@@ -1077,20 +958,22 @@ K3Solver k3_solver_take(Carve& w, const sol_karman3d_cfg* c) {
 }
 
 // the forward step's workspace, float-dense from the caller's pointer: three diffused components, then the solver's buffers
-struct K3Fwd { float *svy, *svx, *svz; K3Solver sol; size_t bytes; };
-K3Fwd k3_fwd_layout(const sol_karman3d_cfg* c, void* ws) {
+// (mc: the _adv form with the MacCormack advection -- what sol_mc3_advect takes, behind everything else)
+struct K3Fwd { float *svy, *svx, *svz; K3Solver sol; size_t bytes; void* mc; };
+K3Fwd k3_fwd_layout(const sol_karman3d_cfg* c, void* ws, bool mc = false) {
     const size_t B = c->B, Y = c->Y, X = c->X, Z = c->Z;
     Carve w = Carve::packed(ws);
     K3Fwd l{w.take<float>(B * (Y + 1) * X * Z), w.take<float>(B * Y * (X + 1) * Z), w.take<float>(B * Y * X * (Z + 1)), k3_solver_take(w, c)};
     l.bytes = w.bytes();
+    l.mc = mc ? k3_behind(ws, &l.bytes, sol_mc3_bytes(c)) : nullptr;
     return l;
 }
 
 // the adjoint's workspace, float-dense from the caller's (16-byte aligned) pointer: g_c (int64 fixed point, [b][y faces | x faces | z faces]
 // per simulation -- k3b_rhs clears simulation b's block), g_a (fp32) per component, the absmax slots, the solver's buffers; with re, the
 // partial sums of the Reynolds-number reduction behind them
-struct K3Bwd { long long* gc; float *gay, *gax, *gaz; unsigned* gmax; K3Solver sol; double* partial; size_t bytes; };
-K3Bwd k3_bwd_layout(const sol_karman3d_cfg* c, bool re, void* ws) {
+struct K3Bwd { long long* gc; float *gay, *gax, *gaz; unsigned* gmax; K3Solver sol; double* partial; size_t bytes; void* mc; };
+K3Bwd k3_bwd_layout(const sol_karman3d_cfg* c, bool re, void* ws, bool mc = false) {
     const size_t B = c->B, Y = c->Y, X = c->X, Z = c->Z;
     const size_t nVy = (Y + 1) * X * Z, nVx = Y * (X + 1) * Z, nVz = Y * X * (Z + 1);
     Carve w = Carve::packed(ws);
@@ -1098,6 +981,7 @@ K3Bwd k3_bwd_layout(const sol_karman3d_cfg* c, bool re, void* ws) {
             w.take<unsigned>(B * FX_SLOTS), k3_solver_take(w, c)};
     l.bytes = w.bytes();
     if (re) l.partial = sol_re3_partial_behind(w, c, &l.bytes);
+    l.mc = mc ? k3_behind(ws, &l.bytes, sol_mc3_adj_vel_bytes(c)) : nullptr;      // (the _adv forms: what sol_mc3_adj_vel takes, behind everything else)
     return l;
 }
 
@@ -1110,6 +994,21 @@ extern "C" size_t sol_karman3d_step_workspace_bytes(const sol_karman3d_cfg* c) {
 
 namespace {
 
+// the semi-Lagrangian advection launch: the LDS-tile kernel where the option asks for it and the tile fits, else wave-per-column gathers
+int launch_advect3d(hipStream_t s, const K3Args& a) {
+    const int B = a.B, Y = a.Y, X = a.X, Z = a.Z;
+    const size_t tile_lds = ((size_t)(TR + 1) * TR * Z + (size_t)TR * (TR + 1) * Z + (size_t)TR * TR * (Z + 1)) * sizeof(float) + (size_t)TR * TR * Z;
+    if (sol_opt().k3d_tile && tile_lds <= 160 * 1024) {
+        static std::atomic<unsigned long long> optin{0};
+        if (int e = sol_lds_optin(optin, {SOL_K(k3_advect_tile)}, "k3_advect_tile")) return e;
+        const int tiles_y = (Y + T3 - 1) / T3, tiles_x = (X + T3 - 1) / T3;
+        SOL_LAUNCH(k3_advect_tile, dim3(tiles_y * tiles_x, B), dim3(ADV_T), tile_lds, s, a, tiles_x);
+    } else {
+        SOL_LAUNCH(k3_advect, dim3(grid_for((size_t)((Y + 1) * X + Y * (X + 1) + 2 * Y * X) * 64), B), dim3(256), 0, s, a);
+    }
+    return SOL_OK;
+}
+
 // the launches of sol_karman3d_step_fwd; with a non-zero force F = (fy, fx, fz) (sol_karman3d_step_fwd_buoy), k3_buoyancy between the
 // advection and the divergence (karman3d_buoyancy.hip): the step's output density pushes the advected velocity
 int step_fwd3d(const char* who, const sol_karman3d_cfg* c, void* stream,
@@ -1119,8 +1018,9 @@ int step_fwd3d(const char* who, const sol_karman3d_cfg* c, void* stream,
                float* d_out, float* vy_out, float* vx_out, float* vz_out,
                float* saved_vy, float* saved_vx, float* saved_vz,
                float* feat_out, const float* feat_scale, const int32_t* direct_header_host,
-               void* workspace, size_t workspace_bytes, float fy, float fx, float fz) {
+               void* workspace, size_t workspace_bytes, float fy, float fx, float fz, int32_t advection = 0, float strength = 1.f) {
     SOL_REQUIRE(c != nullptr, "cfg is NULL");
+    if (int e = sol_mc3_check(who, advection, strength)) return e;
     SOL_REQUIRE((saved_vy && saved_vx && saved_vz) || (!saved_vy && !saved_vx && !saved_vz), "saved_vy / saved_vx / saved_vz: all three or none");
     SOL_REQUIRE(c->B >= 1 && c->Y >= 8 && c->X >= 8 && c->Z >= 8 && c->B <= 65535, "%s: B >= 1, Y, X, Z >= 8 (got %d, %d, %d, %d)", who, c->B, c->Y, c->X, c->Z);
     SOL_REQUIRE((size_t)(c->Y + 1) * (c->X + 1) * (c->Z + 1) * 3 < ((size_t)1 << 31), "%s: grid too large for 32-bit face indices", who);
@@ -1131,7 +1031,7 @@ int step_fwd3d(const char* who, const sol_karman3d_cfg* c, void* stream,
     const bool buoyant = fy != 0.f || fx != 0.f || fz != 0.f;
     SOL_REQUIRE(!buoyant || (d_in && inflow && d_out), "%s: a non-zero force needs d_in, inflow and d_out", who);
     if (int e = check_blob3d(c, direct_header_host)) return e;
-    const K3Fwd l = k3_fwd_layout(c, workspace);
+    const K3Fwd l = k3_fwd_layout(c, workspace, advection == 1);
     SOL_REQUIRE(workspace_bytes >= l.bytes, "workspace too small");
     SOL_REQUIRE(vy_in != vy_out && vx_in != vx_out && vz_in != vz_out && (d_in != d_out || !d_out), "%s: outputs must not alias the inputs", who);
     const int B = c->B, Y = c->Y, X = c->X, Z = c->Z, N = Y * X * Z;
@@ -1149,15 +1049,9 @@ int step_fwd3d(const char* who, const sol_karman3d_cfg* c, void* stream,
     if (feat_scale) { a.fs0 = feat_scale[0]; a.fs1 = feat_scale[1]; a.fs2 = feat_scale[2]; a.fs3 = feat_scale[3]; }
     const size_t faces = nVy + nVx + nVz;
     SOL_LAUNCH(k3_diffuse, dim3(grid_for(faces), B), dim3(256), 0, s, a);
-    const size_t tile_lds = ((size_t)(TR + 1) * TR * Z + (size_t)TR * (TR + 1) * Z + (size_t)TR * TR * (Z + 1)) * sizeof(float) + (size_t)TR * TR * Z;
-    if (sol_opt().k3d_tile && tile_lds <= 160 * 1024) {
-        static std::atomic<unsigned long long> optin{0};
-        if (int e = sol_lds_optin(optin, {SOL_K(k3_advect_tile)}, "k3_advect_tile")) return e;
-        const int tiles_y = (Y + T3 - 1) / T3, tiles_x = (X + T3 - 1) / T3;
-        SOL_LAUNCH(k3_advect_tile, dim3(tiles_y * tiles_x, B), dim3(ADV_T), tile_lds, s, a, tiles_x);
-    } else {
-        SOL_LAUNCH(k3_advect, dim3(grid_for((size_t)((Y + 1) * X + Y * (X + 1) + 2 * Y * X) * 64), B), dim3(256), 0, s, a);
-    }
+    if (advection == 1) {
+        if (int e = sol_mc3_advect(c, s, strength, d_in, svy, svx, svz, active, inflow, d_out, vy_out, vx_out, vz_out, l.mc)) return e;
+    } else if (int e = launch_advect3d(s, a)) return e;
     // buoyancy (f = fl(dt F); nothing is launched for F = 0): k3_div and k3_project read v*_out, which k3_buoyancy updates in place
     if (buoyant)
         if (int e = k3_buoyancy_add(s, B, Y, X, Z, active, d_out, c->dt * fy, c->dt * fx, c->dt * fz, vy_out, vx_out, vz_out)) return e;
@@ -1202,6 +1096,40 @@ extern "C" int sol_karman3d_step_fwd_buoy(const sol_karman3d_cfg* c, void* strea
                       workspace, workspace_bytes, fy, fx, fz);
 }
 
+// The _adv form: every argument of the _buoy form, then the advection (0: semi-Lagrangian -- that form's launches, bits and workspace
+// size; 1: MacCormack -- karman3d_maccormack.hip's launches in place of the advection launch) and its correction strength in [0, 1].
+extern "C" size_t sol_karman3d_step_fwd_adv_workspace_bytes(const sol_karman3d_cfg* c, int32_t advection) {
+    if (!c) return 0;
+    return k3_fwd_layout(c, nullptr, advection == 1).bytes;
+}
+
+extern "C" int sol_karman3d_step_fwd_adv(const sol_karman3d_cfg* c, void* stream,
+                                         const float* d_in, const float* vy_in, const float* vx_in, const float* vz_in,
+                                         const float* re, const float* active, const float* inflow,
+                                         const float* velBCy, const float* velBCyMask, int64_t bc_batch_stride,
+                                         float* d_out, float* vy_out, float* vx_out, float* vz_out,
+                                         float* saved_vy, float* saved_vx, float* saved_vz,
+                                         float* feat_out, const float* feat_scale, const int32_t* direct_header_host,
+                                         void* workspace, size_t workspace_bytes, float fy, float fx, float fz,
+                                         int32_t advection, float correction_strength) {
+    return step_fwd3d("sol_karman3d_step_fwd_adv", c, stream, d_in, vy_in, vx_in, vz_in, re, active, inflow, velBCy, velBCyMask, bc_batch_stride,
+                      d_out, vy_out, vx_out, vz_out, saved_vy, saved_vx, saved_vz, feat_out, feat_scale, direct_header_host,
+                      workspace, workspace_bytes, fy, fx, fz, advection, correction_strength);
+}
+
+// the plain advection launch alone on a given post-diffusion velocity (sol_karman3d_advect with advection = 0, karman3d_maccormack.hip)
+int sol_k3_advect(const sol_karman3d_cfg* c, hipStream_t s, const float* d_in, const float* svy, const float* svx, const float* svz, const float* active,
+                  const float* inflow, float* d_out, float* vy_out, float* vx_out, float* vz_out) {
+    K3Args a{};
+    a.B = c->B; a.Y = c->Y; a.X = c->X; a.Z = c->Z; a.dtdx = c->dt / c->dx; a.dt = c->dt; a.inflow_before = c->inflow_before;
+    a.d_in = d_in; a.active = active; a.inflow = inflow;
+    a.d_out = d_out; a.vy_out = vy_out; a.vx_out = vx_out; a.vz_out = vz_out;
+    a.svy = const_cast<float*>(svy); a.svx = const_cast<float*>(svx); a.svz = const_cast<float*>(svz);      // (the advection kernels only read them)
+    if (int e = launch_advect3d(s, a)) return e;
+    SOL_LAUNCH_CHECK();
+    return SOL_OK;
+}
+
 extern "C" size_t sol_karman3d_step_bwd_workspace_bytes(const sol_karman3d_cfg* c) {
     if (!c) return 0;
     return k3_bwd_layout(c, false, nullptr).bytes;
@@ -1216,6 +1144,19 @@ struct Buoy3Extra {
     const float* g_d_out;
     float* g_dsum;
 };
+// the semi-Lagrangian advection adjoint: g_a scattered onto g_c.  tile: 1 the LDS-window kernel (Z <= 64), 0 global atomics, -1 as option
+// k3d_adj_tile says.  Same bits.
+int launch_advect_adj3d(hipStream_t s, const K3BArgs& a, int tile) {
+    const int B = a.B, Y = a.Y, X = a.X, Z = a.Z;
+    if ((tile < 0 ? sol_opt().k3d_adj_tile != 0 : tile != 0) && Z <= 64) {
+        static std::atomic<unsigned long long> optin_adj{0};
+        if (int e = sol_lds_optin(optin_adj, {SOL_K(k3b_advect_adj_tile)}, "k3b_advect_adj_tile")) return e;
+        const int ntj = (Y + K3B_TJ - 1) / K3B_TJ, nti = (X + K3B_TJ - 1) / K3B_TJ;
+        SOL_LAUNCH(k3b_advect_adj_tile, dim3(ntj * nti, B), dim3(256), (size_t)3 * K3B_TW * K3B_TW * (Z + 1) * 8, s, a, nti);
+    } else
+    SOL_LAUNCH(k3b_advect_adj, dim3(grid_for((size_t)((Y + 1) * X + Y * (X + 1) + Y * X) * 64), B), dim3(256), 0, s, a);
+    return SOL_OK;
+}
 
 // the launches of sol_karman3d_step_bwd; with bx, followed by the transpose of the buoyancy term over the g_a they leave in the workspace
 // (k3b_buoyancy_adj, karman3d_buoyancy.hip); with rx, followed by the Reynolds-number reduction over the fixed-point g_c they leave in the
@@ -1225,8 +1166,11 @@ int step_bwd3d(const char* who, const sol_karman3d_cfg* c, void* stream,
                const float* re, const float* active, const float* velBCyMask, int64_t bc_batch_stride,
                const float* g_vy_out, const float* g_vx_out, const float* g_vz_out,
                float* g_vy_in, float* g_vx_in, float* g_vz_in,
-               const int32_t* direct_header_host, void* workspace, size_t workspace_bytes, const Re3Extra* rx, const Buoy3Extra* bx = nullptr) {
+               const int32_t* direct_header_host, void* workspace, size_t workspace_bytes, const Re3Extra* rx, const Buoy3Extra* bx = nullptr,
+               const Adv3Extra* ax = nullptr) {
     SOL_REQUIRE(c != nullptr, "cfg is NULL");
+    if (ax)
+        if (int e = sol_mc3_check(who, ax->advection, ax->strength)) return e;
     SOL_REQUIRE(c->B >= 1 && c->Y >= 8 && c->X >= 8 && c->Z >= 8 && c->B <= 65535, "%s: B >= 1, Y, X, Z >= 8", who);
     SOL_REQUIRE(saved_vy && saved_vx && saved_vz && re && active && velBCyMask && g_vy_out && g_vx_out && g_vz_out && g_vy_in && g_vx_in && g_vz_in && workspace,
                 "%s: NULL pointer argument", who);
@@ -1234,7 +1178,7 @@ int step_bwd3d(const char* who, const sol_karman3d_cfg* c, void* stream,
     SOL_REQUIRE(!bx || bx->g_dsum, "%s: NULL pointer argument (g_dsum)", who);
     SOL_REQUIRE(!bx || (bx->fy - bx->fy == 0.f && bx->fx - bx->fx == 0.f && bx->fz - bx->fz == 0.f), "%s: the force must be finite", who);
     if (int e = check_blob3d(c, direct_header_host)) return e;
-    const K3Bwd l = k3_bwd_layout(c, rx != nullptr, workspace);
+    const K3Bwd l = k3_bwd_layout(c, rx != nullptr, workspace, ax && ax->advection == 1);
     SOL_REQUIRE(workspace_bytes >= l.bytes, "workspace too small");
     if (rx) {
         const void* outs[] = {g_vy_in, g_vx_in, g_vz_in};
@@ -1274,13 +1218,9 @@ int step_bwd3d(const char* who, const sol_karman3d_cfg* c, void* stream,
         const unsigned g_gva = (unsigned)std::min<size_t>(1024, (cols + 3) / 4);
         SOL_LAUNCH(k3b_gva, dim3(g_gva, B), dim3(256), 0, s, a);
     }
-    if (sol_opt().k3d_adj_tile && Z <= 64) {
-        static std::atomic<unsigned long long> optin_adj{0};
-        if (int e = sol_lds_optin(optin_adj, {SOL_K(k3b_advect_adj_tile)}, "k3b_advect_adj_tile")) return e;
-        const int ntj = (Y + K3B_TJ - 1) / K3B_TJ, nti = (X + K3B_TJ - 1) / K3B_TJ;
-        SOL_LAUNCH(k3b_advect_adj_tile, dim3(ntj * nti, B), dim3(256), (size_t)3 * K3B_TW * K3B_TW * (Z + 1) * 8, s, a, nti);
-    } else
-    SOL_LAUNCH(k3b_advect_adj, dim3(grid_for((size_t)((Y + 1) * X + Y * (X + 1) + Y * X) * 64), B), dim3(256), 0, s, a);
+    if (ax && ax->advection == 1) {
+        if (int e = sol_mc3_adj_vel(c, s, ax->strength, saved_vy, saved_vx, saved_vz, a.gay, a.gax, a.gaz, a.gmax, a.gcy, a.gcx, a.gcz, l.mc, -1)) return e;
+    } else if (int e = launch_advect_adj3d(s, a, -1)) return e;
     SOL_LAUNCH(k3b_diffuse_adj, dim3(grid_for(faces), B), dim3(256), 0, s, a);
     SOL_LAUNCH_CHECK();
     // g_dsum = g_d_out + dt F . (face-to-cell transpose of g_a); a poisoned simulation (gmax) gets NaN throughout.  g_a and the absmax slots
@@ -1353,6 +1293,62 @@ extern "C" int sol_karman3d_step_bwd_buoy_re(const sol_karman3d_cfg* c, void* st
     const Buoy3Extra bx{fy, fx, fz, g_d_out, g_dsum};
     return step_bwd3d("sol_karman3d_step_bwd_buoy_re", c, stream, saved_vy, saved_vx, saved_vz, re, active, velBCyMask, bc_batch_stride,
                       g_vy_out, g_vx_out, g_vz_out, g_vy_in, g_vx_in, g_vz_in, direct_header_host, workspace, workspace_bytes, &rx, &bx);
+}
+
+// The _adv forms: every argument of the _buoy / _buoy_re form, then the advection the forward step ran (0: semi-Lagrangian -- that form's
+// launches, bits and workspace size; 1: MacCormack -- sol_mc3_adj_vel in place of k3b_advect_adj*) and its correction strength.  A zero
+// force is the unbuoyant step: g_d_out and g_dsum may then be NULL (no k3b_buoyancy_adj launch without a g_dsum).
+extern "C" size_t sol_karman3d_step_bwd_adv_workspace_bytes(const sol_karman3d_cfg* c, int32_t with_re, int32_t advection) {
+    if (!c) return 0;
+    return k3_bwd_layout(c, with_re != 0, nullptr, advection == 1).bytes;
+}
+
+extern "C" int sol_karman3d_step_bwd_adv(const sol_karman3d_cfg* c, void* stream,
+                                         const float* saved_vy, const float* saved_vx, const float* saved_vz,
+                                         const float* re, const float* active, const float* velBCyMask, int64_t bc_batch_stride,
+                                         const float* g_vy_out, const float* g_vx_out, const float* g_vz_out,
+                                         float* g_vy_in, float* g_vx_in, float* g_vz_in,
+                                         const int32_t* direct_header_host, void* workspace, size_t workspace_bytes,
+                                         float fy, float fx, float fz, const float* g_d_out, float* g_dsum,
+                                         int32_t advection, float correction_strength) {
+    const Buoy3Extra bx{fy, fx, fz, g_d_out, g_dsum};
+    const Adv3Extra ax{advection, correction_strength};
+    const bool plain = fy == 0.f && fx == 0.f && fz == 0.f && !g_dsum;
+    return step_bwd3d("sol_karman3d_step_bwd_adv", c, stream, saved_vy, saved_vx, saved_vz, re, active, velBCyMask, bc_batch_stride,
+                      g_vy_out, g_vx_out, g_vz_out, g_vy_in, g_vx_in, g_vz_in, direct_header_host, workspace, workspace_bytes, nullptr,
+                      plain ? nullptr : &bx, &ax);
+}
+
+extern "C" int sol_karman3d_step_bwd_adv_re(const sol_karman3d_cfg* c, void* stream,
+                                            const float* saved_vy, const float* saved_vx, const float* saved_vz,
+                                            const float* re, const float* active, const float* velBCyMask, int64_t bc_batch_stride,
+                                            const float* g_vy_out, const float* g_vx_out, const float* g_vz_out,
+                                            float* g_vy_in, float* g_vx_in, float* g_vz_in,
+                                            const int32_t* direct_header_host, void* workspace, size_t workspace_bytes,
+                                            const float* vy_in, const float* vx_in, const float* vz_in, float* g_re, int accumulate_re,
+                                            float fy, float fx, float fz, const float* g_d_out, float* g_dsum,
+                                            int32_t advection, float correction_strength) {
+    const Re3Extra rx{vy_in, vx_in, vz_in, g_re, accumulate_re};
+    const Buoy3Extra bx{fy, fx, fz, g_d_out, g_dsum};
+    const Adv3Extra ax{advection, correction_strength};
+    const bool plain = fy == 0.f && fx == 0.f && fz == 0.f && !g_dsum;
+    return step_bwd3d("sol_karman3d_step_bwd_adv_re", c, stream, saved_vy, saved_vx, saved_vz, re, active, velBCyMask, bc_batch_stride,
+                      g_vy_out, g_vx_out, g_vz_out, g_vy_in, g_vx_in, g_vz_in, direct_header_host, workspace, workspace_bytes, &rx,
+                      plain ? nullptr : &bx, &ax);
+}
+
+// the semi-Lagrangian adjoint of the velocity alone (stage B of the MacCormack adjoint; sol_karman3d_advect_bwd with advection = 0)
+int sol_k3b_advect_adj(const sol_karman3d_cfg* c, hipStream_t s, const float* svy, const float* svx, const float* svz, const float* gay, const float* gax,
+                       const float* gaz, const unsigned* gmax, long long* gcy, long long* gcx, long long* gcz, int tile) {
+    K3BArgs a{};
+    a.B = c->B; a.Y = c->Y; a.X = c->X; a.Z = c->Z; a.dtdx = c->dt / c->dx;
+    a.svy = svy; a.svx = svx; a.svz = svz;
+    a.gay = const_cast<float*>(gay); a.gax = const_cast<float*>(gax); a.gaz = const_cast<float*>(gaz);      // (the scatter kernels only read them)
+    a.gmax = const_cast<unsigned*>(gmax);
+    a.gcy = gcy; a.gcx = gcx; a.gcz = gcz;
+    if (int e = launch_advect_adj3d(s, a, tile)) return e;
+    SOL_LAUNCH_CHECK();
+    return SOL_OK;
 }
 
 extern "C" int sol_karman3d_pressure_solve(const sol_karman3d_cfg* c, void* stream, const float* active, const float* rhs, float* p,

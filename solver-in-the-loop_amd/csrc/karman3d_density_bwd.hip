@@ -16,6 +16,8 @@
 //                      g_vz_in likewise, written or added onto the velocity adjoint's result; converts g_d_in back to fp32
 // sol_karman3d_density_bwd_re: the same launches, then the reduction of that g' against L v_in to the density path's part of the gradient
 // with respect to the Reynolds number (karman3d_re_bwd.hip).
+#include "carve.hpp"
+#include "karman3d_advect.hpp"
 #include "karman3d_re.hpp"
 
 namespace {
@@ -85,7 +87,8 @@ struct DTAdd {
 // adjoint of the advected density of cell (j, i, k) of simulation b.  The departure point is recomputed from the saved field with the
 // forward step's expressions, operation for operation, so floorf decides as it did.  No fused multiply-adds: the two scatter kernels are
 // held to the same bits by the test suite.
-template <class Add>
+// ACC (stage B of the MacCormack adjoint): the back-trace term is added onto what gU holds (stage A's part) instead of written.
+template <bool ACC, class Add>
 __device__ __forceinline__ void k3d_point(const K3DArgs& a, int b, const float* sy, const float* sx, const float* sz, const Add& add, int j, int i, int k) {
 #pragma clang fp contract(off)
     const int Y = a.Y, X = a.X, Z = a.Z;
@@ -126,12 +129,14 @@ __device__ __forceinline__ void k3d_point(const K3DArgs& a, int b, const float* 
         gux = -a.dtdx * g * dx;
         guz = -a.dtdx * g * dz;
     }
-    a.gUy[(size_t)b * N + c] = guy;
-    a.gUx[(size_t)b * N + c] = gux;
-    a.gUz[(size_t)b * N + c] = guz;
+    float *oy = a.gUy + (size_t)b * N + c, *ox = a.gUx + (size_t)b * N + c, *oz = a.gUz + (size_t)b * N + c;
+    *oy = ACC ? *oy + guy : guy;
+    *ox = ACC ? *ox + gux : gux;
+    *oz = ACC ? *oz + guz : guz;
 }
 
 // every contribution a global int64 atomic (option k3d_dens_adj_tile = 0; the reference form of the tile kernel): one z column per wave
+template <bool ACC>
 __global__ void __launch_bounds__(256) k3d_advect_adj(K3DArgs a) {
     const int Y = a.Y, X = a.X, Z = a.Z;
     const size_t N = (size_t)Y * X * Z;
@@ -147,13 +152,14 @@ __global__ void __launch_bounds__(256) k3d_advect_adj(K3DArgs a) {
     const int nwaves = gridDim.x * (blockDim.x >> 6);
     for (int c = wave0; c < Y * X; c += nwaves) {
         const int j = c / X, i = c % X;
-        for (int k = lane; k < Z; k += 64) k3d_point(a, b, sy, sx, sz, add, j, i, k);
+        for (int k = lane; k < Z; k += 64) k3d_point<ACC>(a, b, sy, sx, sz, add, j, i, k);
     }
 }
 
 // The same scatter with an LDS window per workgroup: a workgroup owns 4 x 4 columns (all k), four columns per wave, and accumulates into an
 // 8 x 8-column int64 window: the eight corners of a cell's gather lie within |u| dt/dx + 1 cells of it.  Integer adds commute: the result
 // equals k3d_advect_adj's bit for bit.
+template <bool ACC>
 __global__ void __launch_bounds__(256) k3d_advect_adj_tile(K3DArgs a, int nti) {
     extern __shared__ __align__(16) unsigned long long smem_dens[];
     const int Y = a.Y, X = a.X, Z = a.Z;
@@ -175,7 +181,7 @@ __global__ void __launch_bounds__(256) k3d_advect_adj_tile(K3DArgs a, int nti) {
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     for (int t = wave; t < nC; t += 4) {
         const int j = j0 + t / nI, i = i0 + t % nI;
-        for (int k = lane; k < Z; k += 64) k3d_point(a, b, sy, sx, sz, add, j, i, k);
+        for (int k = lane; k < Z; k += 64) k3d_point<ACC>(a, b, sy, sx, sz, add, j, i, k);
     }
     __syncthreads();
     // (window cells outside the grid never received a contribution: they are zero and their address is never formed)
@@ -260,17 +266,35 @@ struct K3DLayout {
     unsigned* gmax;
     double* partial;
     size_t bytes;
+    void* mc;                           // the _adv forms with the MacCormack advection: what sol_mc3_adj_den takes, behind everything else
 };
-K3DLayout k3d_layout(const sol_karman3d_cfg* c, bool re, void* ws) {
+K3DLayout k3d_layout(const sol_karman3d_cfg* c, bool re, void* ws, bool mc = false) {
     const size_t B = c->B, N = (size_t)c->Y * c->X * c->Z;
     Carve w(ws);
     K3DLayout l{w.take<long long>(B * N), w.take<float>(B * N), w.take<float>(B * N), w.take<float>(B * N), w.take<unsigned>(B * FX_SLOTS)};
     l.bytes = w.bytes();
     if (re) l.partial = sol_re3_partial_behind(w, c, &l.bytes);
+    l.mc = mc ? k3_behind(ws, &l.bytes, sol_mc3_adj_den_bytes(c)) : nullptr;
     return l;
 }
 
 int grid_of(size_t n) { const size_t g = (n + 255) / 256; return (int)(g < 1 ? 1 : (g > 65535 ? 65535 : g)); }
+
+// the semi-Lagrangian advection adjoint of the density.  acc: the back-trace term is added onto gU (stage B of the MacCormack adjoint);
+// tile: 1 the LDS-window kernel where the window fits, 0 global atomics, -1 as option k3d_dens_adj_tile says.  Same bits.
+int launch_advect_adj(hipStream_t s, const K3DArgs& a, bool acc, int tile) {
+    const int B = a.B, Y = a.Y, X = a.X, Z = a.Z;
+    const size_t win = (size_t)K3D_TW * K3D_TW * Z * sizeof(unsigned long long);
+    if ((tile < 0 ? sol_opt().k3d_dens_adj_tile != 0 : tile != 0) && win <= K3D_LDS_MAX) {
+        const int ntj = (Y + K3D_TJ - 1) / K3D_TJ, nti = (X + K3D_TJ - 1) / K3D_TJ;
+        if (acc) SOL_LAUNCH_NAMED("k3d_advect_adj_tile", k3d_advect_adj_tile<true>, dim3(ntj * nti, B), dim3(256), win, s, a, nti);
+        else SOL_LAUNCH_NAMED("k3d_advect_adj_tile", k3d_advect_adj_tile<false>, dim3(ntj * nti, B), dim3(256), win, s, a, nti);
+    } else {
+        if (acc) SOL_LAUNCH_NAMED("k3d_advect_adj", k3d_advect_adj<true>, dim3(grid_of((size_t)Y * X * 64), B), dim3(256), 0, s, a);
+        else SOL_LAUNCH_NAMED("k3d_advect_adj", k3d_advect_adj<false>, dim3(grid_of((size_t)Y * X * 64), B), dim3(256), 0, s, a);
+    }
+    return SOL_OK;
+}
 
 bool shape_ok(const sol_karman3d_cfg* c) { return c && c->B >= 1 && c->B <= 65535 && c->Y >= 8 && c->X >= 8 && c->Z >= 8; }
 
@@ -280,8 +304,10 @@ int density_bwd3d(const char* who, const sol_karman3d_cfg* c, void* stream,
                   const float* d_in, const float* inflow, const float* saved_vy, const float* saved_vx, const float* saved_vz,
                   const float* re, const float* velBCyMask, int64_t bc_batch_stride,
                   const float* g_d_out, float* g_d_in, float* g_vy_in, float* g_vx_in, float* g_vz_in, int accumulate,
-                  void* workspace, size_t workspace_bytes, const Re3Extra* rx) {
+                  void* workspace, size_t workspace_bytes, const Re3Extra* rx, const Adv3Extra* ax = nullptr) {
     SOL_REQUIRE(c != nullptr, "%s: cfg is NULL", who);
+    if (ax)
+        if (int e = sol_mc3_check(who, ax->advection, ax->strength)) return e;
     SOL_REQUIRE(shape_ok(c), "%s: B in [1, 65535], Y, X, Z >= 8 (got %d, %d, %d, %d)", who, c->B, c->Y, c->X, c->Z);
     SOL_REQUIRE((size_t)(c->Y + 1) * (c->X + 1) * (c->Z + 1) < ((size_t)1 << 28), "%s: grid too large for 32-bit face indices", who);
     SOL_REQUIRE(d_in && saved_vy && saved_vx && saved_vz && re && velBCyMask && g_d_out && g_d_in && g_vy_in && g_vx_in && g_vz_in && workspace,
@@ -292,7 +318,7 @@ int density_bwd3d(const char* who, const sol_karman3d_cfg* c, void* stream,
     const size_t N = (size_t)Y * X * Z, faces = (size_t)(Y + 1) * X * Z + (size_t)Y * (X + 1) * Z + (size_t)Y * X * (Z + 1);
     SOL_REQUIRE(faces % 2 == 0, "%s: odd face count (%zu): even X, Z expected", who, faces);
     SOL_REQUIRE(reinterpret_cast<uintptr_t>(workspace) % 16 == 0, "%s: workspace must be 16-byte aligned", who);
-    const K3DLayout l = k3d_layout(c, rx != nullptr, workspace);
+    const K3DLayout l = k3d_layout(c, rx != nullptr, workspace, ax && ax->advection == 1);
     SOL_REQUIRE(workspace_bytes >= l.bytes, "%s: workspace too small (%zu < %zu bytes)", who, workspace_bytes, l.bytes);
     const void* outs[] = {g_d_in, g_vy_in, g_vx_in, g_vz_in, rx ? rx->g_re : nullptr};
     const void* ins[] = {d_in, inflow, saved_vy, saved_vx, saved_vz, re, velBCyMask, g_d_out,
@@ -310,13 +336,9 @@ int density_bwd3d(const char* who, const sol_karman3d_cfg* c, void* stream,
     a.gD = l.gD; a.gUy = l.gUy; a.gUx = l.gUx; a.gUz = l.gUz; a.gmax = l.gmax;
     a.gdi = g_d_in; a.giy = g_vy_in; a.gix = g_vx_in; a.giz = g_vz_in;
     SOL_LAUNCH(k3d_clear, dim3(FX_SLOTS, B), dim3(K3D_CLEAR_T), 0, s, a);
-    const size_t win = (size_t)K3D_TW * K3D_TW * Z * sizeof(unsigned long long);
-    if (sol_opt().k3d_dens_adj_tile && win <= K3D_LDS_MAX) {
-        const int ntj = (Y + K3D_TJ - 1) / K3D_TJ, nti = (X + K3D_TJ - 1) / K3D_TJ;
-        SOL_LAUNCH(k3d_advect_adj_tile, dim3(ntj * nti, B), dim3(256), win, s, a, nti);
-    } else {
-        SOL_LAUNCH(k3d_advect_adj, dim3(grid_of((size_t)Y * X * 64), B), dim3(256), 0, s, a);
-    }
+    if (ax && ax->advection == 1) {
+        if (int e = sol_mc3_adj_den(c, s, ax->strength, d_in, inflow, saved_vy, saved_vx, saved_vz, g_d_out, l.gmax, l.gD, l.gUy, l.gUx, l.gUz, l.mc, -1)) return e;
+    } else if (int e = launch_advect_adj(s, a, false, -1)) return e;
     SOL_LAUNCH(k3d_diffuse_adj, dim3(grid_of(faces + N), B), dim3(256), 0, s, a);
     SOL_LAUNCH_CHECK();
     if (!rx) return SOL_OK;
@@ -360,4 +382,46 @@ extern "C" int sol_karman3d_density_bwd_re(const sol_karman3d_cfg* c, void* stre
     const Re3Extra rx{vy_in, vx_in, vz_in, g_re, accumulate_re};
     return density_bwd3d("sol_karman3d_density_bwd_re", c, stream, d_in, inflow, saved_vy, saved_vx, saved_vz, re, velBCyMask, bc_batch_stride,
                          g_d_out, g_d_in, g_vy_in, g_vx_in, g_vz_in, accumulate, workspace, workspace_bytes, &rx);
+}
+
+// The _adv forms: every argument of the plain / _re form, then the advection the forward step ran (0: semi-Lagrangian -- that form's
+// launches, bits and workspace size; 1: MacCormack -- sol_mc3_adj_den in place of k3d_advect_adj*) and its correction strength.
+extern "C" size_t sol_karman3d_density_bwd_adv_workspace_bytes(const sol_karman3d_cfg* c, int32_t with_re, int32_t advection) {
+    if (!shape_ok(c)) return 0;
+    return k3d_layout(c, with_re != 0, nullptr, advection == 1).bytes;
+}
+
+extern "C" int sol_karman3d_density_bwd_adv(const sol_karman3d_cfg* c, void* stream,
+                                            const float* d_in, const float* inflow, const float* saved_vy, const float* saved_vx, const float* saved_vz,
+                                            const float* re, const float* velBCyMask, int64_t bc_batch_stride,
+                                            const float* g_d_out, float* g_d_in, float* g_vy_in, float* g_vx_in, float* g_vz_in, int accumulate,
+                                            void* workspace, size_t workspace_bytes, int32_t advection, float correction_strength) {
+    const Adv3Extra ax{advection, correction_strength};
+    return density_bwd3d("sol_karman3d_density_bwd_adv", c, stream, d_in, inflow, saved_vy, saved_vx, saved_vz, re, velBCyMask, bc_batch_stride,
+                         g_d_out, g_d_in, g_vy_in, g_vx_in, g_vz_in, accumulate, workspace, workspace_bytes, nullptr, &ax);
+}
+
+extern "C" int sol_karman3d_density_bwd_adv_re(const sol_karman3d_cfg* c, void* stream,
+                                               const float* d_in, const float* inflow, const float* saved_vy, const float* saved_vx, const float* saved_vz,
+                                               const float* re, const float* velBCyMask, int64_t bc_batch_stride,
+                                               const float* g_d_out, float* g_d_in, float* g_vy_in, float* g_vx_in, float* g_vz_in, int accumulate,
+                                               void* workspace, size_t workspace_bytes,
+                                               const float* vy_in, const float* vx_in, const float* vz_in, float* g_re, int accumulate_re,
+                                               int32_t advection, float correction_strength) {
+    const Re3Extra rx{vy_in, vx_in, vz_in, g_re, accumulate_re};
+    const Adv3Extra ax{advection, correction_strength};
+    return density_bwd3d("sol_karman3d_density_bwd_adv_re", c, stream, d_in, inflow, saved_vy, saved_vx, saved_vz, re, velBCyMask, bc_batch_stride,
+                         g_d_out, g_d_in, g_vy_in, g_vx_in, g_vz_in, accumulate, workspace, workspace_bytes, &rx, &ax);
+}
+
+// the semi-Lagrangian adjoint of the density alone (stage B of the MacCormack adjoint; sol_karman3d_advect_bwd with advection = 0)
+int sol_k3d_advect_adj(const sol_karman3d_cfg* c, hipStream_t s, const float* d_in, const float* inflow, const float* svy, const float* svx, const float* svz,
+                       const float* g, const unsigned* gmax, long long* gD, float* gUy, float* gUx, float* gUz, bool add_gU, int tile) {
+    K3DArgs a{};
+    a.B = c->B; a.Y = c->Y; a.X = c->X; a.Z = c->Z; a.dtdx = c->dt / c->dx; a.inflow_before = c->inflow_before;
+    a.d_in = d_in; a.inflow = inflow; a.svy = svy; a.svx = svx; a.svz = svz;
+    a.gdo = g; a.gD = gD; a.gUy = gUy; a.gUx = gUx; a.gUz = gUz; a.gmax = const_cast<unsigned*>(gmax);
+    if (int e = launch_advect_adj(s, a, add_gU, tile)) return e;
+    SOL_LAUNCH_CHECK();
+    return SOL_OK;
 }

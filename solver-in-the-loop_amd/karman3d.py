@@ -115,6 +115,19 @@ class StepPhysics3D(NamedTuple):
                           doc="the three floats a _buoy entry point takes after its plain sibling's arguments; () in the plain mode")
 
 
+def _adv_workspace_bytes(lib, cfg):
+    """the workspace the _adv entry points take under the MacCormack advection, the largest over the step, its velocity adjoint and its
+    density adjoint, with and without re"""
+    c = C.byref(cfg)
+    return max(lib.sol_karman3d_step_fwd_adv_workspace_bytes(c, 1), lib.sol_karman3d_step_bwd_adv_workspace_bytes(c, 1, 1),
+               lib.sol_karman3d_density_bwd_adv_workspace_bytes(c, 1, 1))
+
+
+def _adv_tail(adv):
+    """the two arguments an _adv entry point takes last: advection = 1 and the correction strength `adv` (ops.advection_arg's float)"""
+    return (1, float(adv))
+
+
 def _adjoint_entry(lib, half, mode="", re=False):
     """The lookup of an adjoint's entry point, sol_karman3d_<half><mode>[_re]: half "step_bwd" (mode: StepPhysics3D.mode) or "density_bwd" (none)"""
     return getattr(lib, "sol_karman3d_" + half + mode + ("_re" if re else ""))
@@ -250,15 +263,23 @@ class Karman3DFlow:
 
     buoyancy=(fy, fx, fz), a force per unit density, or PhiFlow's spelling buoyancy_factor=beta with gravity=(gy, gx, gz): F = -gravity *
     beta (buoyancy_force3d), and diffusion_substeps=n are kept as `self.physics`, one StepPhysics3D built here (see there; a force of
-    zero is none).  The defaults issue the launches the step always did."""
+    zero is none).  The defaults issue the launches the step always did.
+
+    advection="mac_cormack", correction_strength=s (0 <= s <= 1): the MacCormack advection (include/sol_hip.h, "MACCORMACK ADVECTION on the
+    karman-3d step") in place of the semi-Lagrangian one, forward and adjoint; validated by ops.advection_arg before the device is asked
+    for and kept as `self.adv` (None for "semi_lagrangian", else the float s) BESIDE the physics value, which has no field for it.  It
+    composes with everything above."""
 
     buoyancy = property(lambda self: self.physics.buoyancy)
     nsub = property(lambda self: self.physics.nsub)
 
     def __init__(self, scene, batch_size, dt=1.0, res=None, grad_pad="replicate", inflow_order="after",
                  cg_rtol=1e-6, cg_atol=1e-9, cg_max_iter=CG_MAX_ITER3D, density_grad=False, re_grad=False,
-                 buoyancy=None, buoyancy_factor=None, gravity=(-9.81, 0.0, 0.0), diffusion_substeps=1):
+                 buoyancy=None, buoyancy_factor=None, gravity=(-9.81, 0.0, 0.0), diffusion_substeps=1,
+                 advection="semi_lagrangian", correction_strength=1.0):
+        from .ops import advection_arg
         self.physics = StepPhysics3D.of(buoyancy, buoyancy_factor, gravity, diffusion_substeps, "Karman3DFlow: diffusion_substeps")
+        self.adv = advection_arg(advection, correction_strength, "Karman3DFlow: advection")
         _lib.require_gpu()
         self.lib = _lib.load()
         self.scene, self.B = scene, batch_size
@@ -270,6 +291,8 @@ class Karman3DFlow:
                                s.direct.numel(), s.direct.data_ptr(),
                                1 if self.cg else 0, int(cg_max_iter), float(cg_rtol), float(cg_atol), None)
         nbytes = max(self.lib.sol_karman3d_step_workspace_bytes(C.byref(self.cfg)), self.lib.sol_karman3d_step_bwd_workspace_bytes(C.byref(self.cfg)))
+        if self.adv is not None:            # the MacCormack launches' parts, every mode: sized once, here (a captured graph bakes the address in)
+            nbytes = max(nbytes, _adv_workspace_bytes(self.lib, self.cfg))
         self.workspace = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=s.active.device)
         self.workspace_bytes = nbytes
         self.solve_info = {}
@@ -309,11 +332,12 @@ class Karman3DFlow:
         cfg.cg_info = info.data_ptr()
         return info
 
-    def _forward(self, ph, d, vy, vx, vz, re, saved=None, feat_out=None, feat_scale=None, pre_diffuse=True):
+    def _forward(self, ph, d, vy, vx, vz, re, saved=None, feat_out=None, feat_scale=None, pre_diffuse=True, adv=None):
         """THE forward launch site: one step under the StepPhysics3D `ph`  ->  ((d, vy, vx, vz) after the step, the velocity the launches
         read).  ph.nsub > 1: the pre-diffusion (diffuse_sub; not with pre_diffuse=False: the caller has run it), then the launches on
         sub_cfg(ph.nsub) -- the velocity handed back is then M^(n-1) v, "the input velocity" the re mode saves.  ph.buoyancy:
-        sol_karman3d_step_fwd_buoy (a kept force of zero issues the plain call's launches)."""
+        sol_karman3d_step_fwd_buoy (a kept force of zero issues the plain call's launches).  adv = s (ops.advection_arg: a float for
+        "mac_cormack", None for "semi_lagrangian"): sol_karman3d_step_fwd_adv with the force, or a zero force, then (1, s)."""
         if pre_diffuse and ph.nsub > 1:
             vy, vx, vz = diffuse_sub(self, vy, vx, vz, re, ph.nsub)
         cfg = self.sub_cfg(ph.nsub)
@@ -328,19 +352,22 @@ class Karman3DFlow:
             fs = (C.c_float * 4)(*[float(v) for v in feat_scale])
         sv = saved if saved is not None else (None, None, None)
         info = self._cg_info(cfg)
-        entry = getattr(self.lib, "sol_karman3d_step_fwd" + ph.mode)
+        entry, tail = getattr(self.lib, "sol_karman3d_step_fwd" + (ph.mode if adv is None else "_adv")), ph.force_tail
+        if adv is not None:
+            self._ws(self.lib.sol_karman3d_step_fwd_adv_workspace_bytes(C.byref(cfg), 1))
+            tail = (tail or (0.0, 0.0, 0.0)) + _adv_tail(adv)
         check(entry(C.byref(cfg), stream(), ptr(d), ptr(vy), ptr(vx), ptr(vz), ptr(re),
                     ptr(s.active), ptr(s.inflow), ptr(s.velBCy), ptr(s.velBCyMask), s.bc_stride,
                     ptr(out[0]), ptr(out[1]), ptr(out[2]), ptr(out[3]), ptr(sv[0]), ptr(sv[1]), ptr(sv[2]), ptr(feat_out), fs,
-                    s.direct_header.ctypes.data_as(C.c_void_p), ptr(self.workspace), self.workspace_bytes, *ph.force_tail))
+                    s.direct_header.ctypes.data_as(C.c_void_p), ptr(self.workspace), self.workspace_bytes, *tail))
         if info is not None:
             self.solve_info = {"iterations": info[:, 0], "converged": info[:, 1]}
         return tuple(out), (vy, vx, vz)
 
-    def _fwd(self, d, vy, vx, vz, re, saved=None, feat_out=None, feat_scale=None, buoyancy=None, nsub=1, physics=None, pre_diffuse=False):
+    def _fwd(self, d, vy, vx, vz, re, saved=None, feat_out=None, feat_scale=None, buoyancy=None, nsub=1, physics=None, pre_diffuse=False, adv=None):
         """the step's outputs of _forward's launches alone (the caller has pre-diffused the velocity); `physics` replaces buoyancy= / nsub="""
         ph = physics if physics is not None else StepPhysics3D(buoyancy, nsub)
-        return self._forward(ph, d, vy, vx, vz, re, saved, feat_out, feat_scale, pre_diffuse)[0]
+        return self._forward(ph, d, vy, vx, vz, re, saved, feat_out, feat_scale, pre_diffuse, adv=adv)[0]
 
     def _fwd_sub(self, *args, **kw):
         """_fwd with the pre-diffusion"""
@@ -366,12 +393,14 @@ class Karman3DFlow:
             raise ValueError("g_re must be [B] = (%d,), got %s" % (self.B, tuple(g_re.shape)))
         return (ptr(vel_in[0]), ptr(vel_in[1]), ptr(vel_in[2]), ptr(g_re), int(accumulate)), g_re
 
-    def _bwd(self, saved, re, gvy, gvx, gvz, vel_in=None, g_re=None, buoyancy=None, g_d=None, nsub=1, physics=None):
+    def _bwd(self, saved, re, gvy, gvx, gvz, vel_in=None, g_re=None, buoyancy=None, g_d=None, nsub=1, physics=None, adv=None):
         """the velocity adjoint, the direct call (sol_karman3d_step_bwd); vel_in = the step's input velocity: also the gradient with respect
         to re (sol_karman3d_step_bwd_re; the velocity gradients are the plain call's bits) -> [g_vy, g_vx, g_vz] (+ [g_re]).
         buoyancy = (fy, fx, fz): the buoyant step's (sol_karman3d_step_bwd_buoy(_re): the same launches and bits, then the transpose of the
         force term); g_d [B,Y,X,Z] = the cotangent of the step's output density (None = zero) -> ... + [g_dsum], which the caller hands to
         density_bwd as its g_d, accumulating onto the velocity gradients returned here.  `physics` replaces buoyancy= / nsub=.
+        adv = s (the MacCormack step's): the _adv entries, sol_karman3d_step_bwd_adv(_re), which take the force (zero, with NULL g_d /
+        g_dsum, where there is none) and then (1, s); the list returned is the same.
         _step_adjoint3d composes this with density_bwd and the substep tail, and is the one place that takes this list apart."""
         s = self.scene
         ph = physics if physics is not None else StepPhysics3D(buoyancy, nsub)
@@ -379,7 +408,9 @@ class Karman3DFlow:
         gi = [torch.empty_like(t) for t in saved]
         info = self._cg_info(cfg)
         buoy = ph.buoyancy is not None
-        entry, tail = _adjoint_entry(self.lib, "step_bwd", ph.mode, vel_in is not None), ()
+        entry, tail = _adjoint_entry(self.lib, "step_bwd", ph.mode if adv is None else "_adv", vel_in is not None), ()
+        if adv is not None:
+            self._ws(self.lib.sol_karman3d_step_bwd_adv_workspace_bytes(C.byref(self.cfg), int(vel_in is not None), 1))
         if vel_in is not None:
             self._ws(self.lib.sol_karman3d_step_bwd_re_workspace_bytes(C.byref(self.cfg)))
             tail, g_re = self._re_tail(saved, vel_in, g_re)
@@ -391,6 +422,10 @@ class Karman3DFlow:
                     raise ValueError("g_d must be [B,Y,X,Z] = %s, got %s" % ((self.B, s.Y, s.X, s.Z), tuple(g_d.shape)))
             g_dsum = torch.empty(self.B, s.Y, s.X, s.Z, dtype=torch.float32, device=saved[0].device)
             tail = tuple(tail) + ph.force_tail + (ptr(g_d), ptr(g_dsum))
+        elif adv is not None:
+            tail = tuple(tail) + (0.0, 0.0, 0.0, None, None)
+        if adv is not None:
+            tail = tuple(tail) + _adv_tail(adv)
         check(entry(C.byref(cfg), stream(), ptr(saved[0]), ptr(saved[1]), ptr(saved[2]), ptr(re),
                     ptr(s.active), ptr(s.velBCyMask), s.bc_stride, ptr(gvy), ptr(gvx), ptr(gvz),
                     ptr(gi[0]), ptr(gi[1]), ptr(gi[2]),
@@ -425,11 +460,11 @@ class Karman3DFlow:
         if grad and (vy.requires_grad or vx.requires_grad or vz.requires_grad or (density and d.requires_grad) or want_re):
             if feat_out is not None:
                 raise ValueError("feat_out is the fused no-grad feature output: build the features with to_feature3d() when training")
-            return _Karman3DStepFn.apply(self, d, vy, vx, vz, re, density, want_re, self.physics)
-        return self._forward(self.physics, d, vy, vx, vz, re, None, feat_out, feat_scale)[0]
+            return _Karman3DStepFn.apply(self, d, vy, vx, vz, re, density, want_re, self.physics, self.adv)
+        return self._forward(self.physics, d, vy, vx, vz, re, None, feat_out, feat_scale, adv=self.adv)[0]
 
 
-def density_bwd(sim, d_in, saved, re, g_d, g_v=None, vel_in=None, g_re=None, nsub=1):
+def density_bwd(sim, d_in, saved, re, g_d, g_v=None, vel_in=None, g_re=None, nsub=1, adv=None):
     """Adjoint of the 3-D step's marker density (sol_karman3d_density_bwd), the direct call: (g_d_in, g_vy_in, g_vx_in, g_vz_in) from the
     step's input density `d_in`, the saved post-diffusion velocity `saved` = (svy, svx, svz), `re` and the gradient `g_d` with respect
     to the step's output density; `sim` = the Karman3DFlow (scene, cfg, workspace).  g_v = (g_vy, g_vx, g_vz): buffers that already hold
@@ -438,7 +473,8 @@ def density_bwd(sim, d_in, saved, re, g_d, g_v=None, vel_in=None, g_re=None, nsu
     respect to re as well (sol_karman3d_density_bwd_re), returned fifth; g_re [B]: a buffer to add onto, else a fresh one is written.
     nsub (diffusion substeps: StepPhysics3D.nsub): the launches run on sim.sub_cfg(nsub); `saved` / vel_in are then those of
     the pre-diffused velocity, the velocity gradients are the cotangent of M^(n-1) v and g_re is 1/n of the gradient -- a g_re to add onto
-    must hold such a part too (the factor n is applied once, afterwards: _step_adjoint3d)."""
+    must hold such a part too (the factor n is applied once, afterwards: _step_adjoint3d).  adv = s (the MacCormack step's): the _adv
+    entries, sol_karman3d_density_bwd_adv(_re), which take (1, s) last."""
     _lib.require_gpu()
     s, B = sim.scene, sim.B
     Y, X, Z = s.Y, s.X, s.Z
@@ -453,10 +489,14 @@ def density_bwd(sim, d_in, saved, re, g_d, g_v=None, vel_in=None, g_re=None, nsu
     if accumulate and [t.shape for t in g_v] != [t.shape for t in saved]:
         raise ValueError("density_bwd: g_v must have the velocity's shapes")
     want_re = vel_in is not None
-    entry, tail = _adjoint_entry(sim.lib, "density_bwd", re=want_re), ()
+    entry, tail = _adjoint_entry(sim.lib, "density_bwd", "" if adv is None else "_adv", want_re), ()
     nbytes = (sim.lib.sol_karman3d_density_bwd_re_workspace_bytes if want_re else sim.lib.sol_karman3d_density_bwd_workspace_bytes)(C.byref(sim.cfg))
+    if adv is not None:
+        nbytes = sim.lib.sol_karman3d_density_bwd_adv_workspace_bytes(C.byref(sim.cfg), int(want_re), 1)
     if want_re:
         tail, g_re = sim._re_tail(saved, vel_in, g_re)
+    if adv is not None:
+        tail = tuple(tail) + _adv_tail(adv)
     gi = list(g_v) if accumulate else [torch.empty_like(t) for t in saved]
     od = torch.empty_like(d_in)
     ws = sim._ws(nbytes)
@@ -466,7 +506,58 @@ def density_bwd(sim, d_in, saved, re, g_d, g_v=None, vel_in=None, g_re=None, nsu
     return (od, *gi) if vel_in is None else (od, *gi, g_re)
 
 
-def _step_adjoint3d(sim, ph, density, d_in, saved, re, gd, gv, vel_in=None, through_substeps=True):
+def _advect3d_inputs(who, sim, d, svy, svx, svz):
+    s, B = sim.scene, sim.B
+    Y, X, Z = s.Y, s.X, s.Z
+    d, svy, svx, svz = (_lib.f32(t) for t in (d, svy, svx, svz))
+    if d.shape != (B, Y, X, Z) or svy.shape != (B, Y + 1, X, Z) or svx.shape != (B, Y, X + 1, Z) or svz.shape != (B, Y, X, Z + 1):
+        raise ValueError("%s: d %s, svy %s, svx %s, svz %s are not [B,Y,X,Z], [B,Y+1,X,Z], [B,Y,X+1,Z], [B,Y,X,Z+1] of the scene (B, Y, X, Z) = "
+                         "(%d, %d, %d, %d)" % (who, tuple(d.shape), tuple(svy.shape), tuple(svx.shape), tuple(svz.shape), B, Y, X, Z))
+    return d, svy, svx, svz
+
+
+def _adv_pair(adv):
+    """(advection, correction_strength) of the stage's entry points from ops.advection_arg's value"""
+    return (0, 1.0) if adv is None else (1, float(adv))
+
+
+def advect3d(sim, d, svy, svx, svz, adv=None):
+    """The advection stage of the 3-D step alone (sol_karman3d_advect) on a given post-diffusion velocity (svy, svx, svz): -> (d_out, a_y,
+    a_x, a_z), the velocity times the hard-BC face masks, the inflow added as the simulator's inflow_order says.  adv: None = the
+    semi-Lagrangian launch of the step, a float s = MacCormack with that correction strength (ops.advection_arg).  Any Y, X, Z >= 8."""
+    _lib.require_gpu()
+    d, svy, svx, svz = _advect3d_inputs("advect3d", sim, d, svy, svx, svz)
+    s = sim.scene
+    advection, strength = _adv_pair(adv)
+    nbytes = sim.lib.sol_karman3d_advect_workspace_bytes(C.byref(sim.cfg), advection)
+    ws = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=d.device) if nbytes else None
+    out = [torch.empty_like(t) for t in (d, svy, svx, svz)]
+    check(sim.lib.sol_karman3d_advect(C.byref(sim.cfg), stream(), ptr(d), ptr(svy), ptr(svx), ptr(svz), ptr(s.active), ptr(s.inflow), advection, strength,
+                                      ptr(out[0]), ptr(out[1]), ptr(out[2]), ptr(out[3]), ptr(ws), nbytes))
+    return tuple(out)
+
+
+def advect3d_bwd(sim, d, svy, svx, svz, g_d, g_ay, g_ax, g_az, adv=None, tile_window=True):
+    """The transpose of advect3d (sol_karman3d_advect_bwd): the cotangents of (d_out, a_y, a_x, a_z) -> (g_d_in, g_svy, g_svx, g_svz), every
+    decision of the forward stage frozen.  tile_window: the semi-Lagrangian scatters go through their LDS windows (False: global atomics
+    only; equal bits)."""
+    _lib.require_gpu()
+    d, svy, svx, svz = _advect3d_inputs("advect3d_bwd", sim, d, svy, svx, svz)
+    g = [_lib.f32(t) for t in (g_d, g_ay, g_ax, g_az)]
+    if [t.shape for t in g] != [t.shape for t in (d, svy, svx, svz)]:
+        raise ValueError("advect3d_bwd: the cotangents must have the shapes of d, svy, svx, svz")
+    s = sim.scene
+    advection, strength = _adv_pair(adv)
+    nbytes = sim.lib.sol_karman3d_advect_bwd_workspace_bytes(C.byref(sim.cfg))
+    ws = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=d.device)
+    out = [torch.empty_like(t) for t in (d, svy, svx, svz)]
+    check(sim.lib.sol_karman3d_advect_bwd(C.byref(sim.cfg), stream(), ptr(d), ptr(svy), ptr(svx), ptr(svz), ptr(s.active), ptr(s.inflow), advection, strength,
+                                          ptr(g[0]), ptr(g[1]), ptr(g[2]), ptr(g[3]), ptr(out[0]), ptr(out[1]), ptr(out[2]), ptr(out[3]),
+                                          int(bool(tile_window)), ptr(ws), nbytes))
+    return tuple(out)
+
+
+def _step_adjoint3d(sim, ph, density, d_in, saved, re, gd, gv, vel_in=None, through_substeps=True, adv=None):
     """THE adjoint of one step of `sim` under the StepPhysics3D `ph` (a moving force or none: StepPhysics3D.moving): the velocity half
     (Karman3DFlow._bwd, with the pressure solve), the density half (density_bwd) and the substep tail are composed here and nowhere else
     (_Karman3DStepFn.backward, the reverse sweep of Karman3DTrainer).  `saved` = the post-diffusion velocity the forward kept, d_in = the
@@ -481,18 +572,20 @@ def _step_adjoint3d(sim, ph, density, d_in, saved, re, gd, gv, vel_in=None, thro
     half on g_dsum, accumulating: a velocity-only loss yields a density gradient too.  No cotangent at all: nothing is launched.
     ph.nsub = n > 1: both halves ran on the scaled cfg, their velocity result is the cotangent of M^(n-1) v and g_re 1/n of the gradient;
     the tail is diffuse_sub on that cotangent (the operator is symmetric; not with through_substeps=False, for a caller that does not
-    read it) and g_re times n (one fp32 multiply)."""
+    read it) and g_re times n (one fp32 multiply).
+    adv = s (ops.advection_arg): the step ran the MacCormack advection; both halves are handed adv= (only then) and run their _adv entries."""
     moving, want_re = ph.buoyancy is not None, vel_in is not None
+    akw = {} if adv is None else {"adv": adv}
     some_v = any(g is not None for g in gv)
     gd = None if gd is None else gd.contiguous()
     gi = g_re = od = None
     if (moving and gd is not None) or some_v or not (moving or density or want_re):
         res = sim._bwd(saved, re, *(torch.zeros_like(t) if g is None else g.contiguous() for g, t in zip(gv, saved)), vel_in=vel_in,
-                       g_d=gd if moving else None, physics=ph)
+                       g_d=gd if moving else None, physics=ph, **akw)
         gi, g_re = res[:3], (res[3] if want_re else None)
         gd = res[-1] if moving else gd                  # g_dsum
     if (moving or density) and gd is not None:
-        od, *gi = density_bwd(sim, d_in, saved, re, gd, gi, vel_in, g_re, nsub=ph.nsub)
+        od, *gi = density_bwd(sim, d_in, saved, re, gd, gi, vel_in, g_re, nsub=ph.nsub, **akw)
         g_re = gi.pop() if want_re else None
     if ph.nsub > 1:
         if through_substeps and gi is not None:
@@ -508,12 +601,12 @@ class _Karman3DStepFn(torch.autograd.Function):
     modes.  `density`: the density output stays in the graph (always under a force)."""
 
     @staticmethod
-    def forward(ctx, sim, d, vy, vx, vz, re, density, want_re, ph=StepPhysics3D()):
+    def forward(ctx, sim, d, vy, vx, vz, re, density, want_re, ph=StepPhysics3D(), adv=None):
         vel = [vy.contiguous(), vx.contiguous(), vz.contiguous()]
         saved = [torch.empty_like(t) for t in vel]
         density = bool(density) or ph.buoyancy is not None
-        out, vel = sim._forward(ph, d, *vel, re, saved)
-        ctx.sim, ctx.density, ctx.want_re, ctx.physics = sim, density, want_re, ph
+        out, vel = sim._forward(ph, d, *vel, re, saved, adv=adv)
+        ctx.sim, ctx.density, ctx.want_re, ctx.physics, ctx.adv = sim, density, want_re, ph, adv
         ctx.save_for_backward(re, *saved, *((d,) if density else ()), *(vel if want_re else ()))
         if not density:
             ctx.mark_non_differentiable(out[0])
@@ -525,7 +618,8 @@ class _Karman3DStepFn(torch.autograd.Function):
         re, sy, sx, sz, *rest = ctx.saved_tensors
         d_in = rest[0] if ctx.density else None
         vel_in = tuple(rest[-3:]) if ctx.want_re else None
-        return (None, *_step_adjoint3d(ctx.sim, ctx.physics, ctx.density, d_in, (sy, sx, sz), re, gd, (gvy, gvx, gvz), vel_in), None, None, None)
+        return (None, *_step_adjoint3d(ctx.sim, ctx.physics, ctx.density, d_in, (sy, sx, sz), re, gd, (gvy, gvx, gvz), vel_in, adv=ctx.adv),
+                None, None, None, None)
 
 
 class _ToFeature3DFn(torch.autograd.Function):
@@ -902,7 +996,8 @@ class Karman3DTrainer:
     nsub = property(lambda self: self.sim.physics.nsub)
 
     def __init__(self, net, scene, B, msteps, std_v, std_re, dt=1.0, res=None, beta1=0.9, beta2=0.999, eps=1e-8, conv_precision="split",
-                 use_graph=False, group=None, comm=None, schedule="manual", glue="fused", buoyancy=None, diffusion_substeps=1, **solver):
+                 use_graph=False, group=None, comm=None, schedule="manual", glue="fused", buoyancy=None, diffusion_substeps=1,
+                 advection="semi_lagrangian", correction_strength=1.0, **solver):
         """schedule: "manual" (default) = the hand-written forward unroll + reverse sweep over the C ABI (_unrolled_schedule), "autograd" = the
         torch-autograd composition of the differentiable HIP ops (rounds 3-4; kept as the cross-check).
         use_graph: capture the whole forward unroll + reverse sweep ONCE into a hipGraph over static input buffers (the
@@ -911,15 +1006,20 @@ class Karman3DTrainer:
         buoyancy=(fy, fx, fz), diffusion_substeps=n: the StepPhysics3D of the simulator (self.sim.physics).  The schedule is unchanged; the
         solver pair is Karman3DFlow._forward and _step_adjoint3d under it: with a force each step's input density is kept and the density
         cotangent is carried to the next (earlier) step (None at the last step: the loss does not look at the density).  Kernel launches
-        only, the pre-diffusion's ping-pong buffers are the simulator's static ones: use_graph stays a graph of kernel nodes."""
+        only, the pre-diffusion's ping-pong buffers are the simulator's static ones: use_graph stays a graph of kernel nodes.
+        advection="mac_cormack", correction_strength=s: the simulator's scheme (self.sim.adv); both schedules hand it to the solver pair.  The
+        MacCormack launches work in the simulator's workspace, sized at construction: kernel nodes only, as before."""
         from .trainer import _conv_precision_code
         from .dist import DPStep
+        from .ops import advection_arg
+        advection_arg(advection, correction_strength, "Karman3DTrainer: advection")       # (refused before the device is asked for)
         _lib.require_gpu()
         self.lib = _lib.load()
         self.net, self.scene, self.B, self.ms = net, scene, B, msteps
         assert glue in ("fused", "torch")
         self.glue = glue          # reverse-sweep glue of the manual schedule: sol_karman3d_correct_bwd / _feature_bwd, or the torch elementwise composition
-        self.sim = Karman3DFlow(scene, B, dt=dt, res=res, buoyancy=buoyancy, diffusion_substeps=diffusion_substeps, **solver)
+        self.sim = Karman3DFlow(scene, B, dt=dt, res=res, buoyancy=buoyancy, diffusion_substeps=diffusion_substeps, advection=advection,
+                                correction_strength=correction_strength, **solver)
         dev = scene.active.device
         self.std_v = torch.tensor([float(v) for v in std_v], dtype=torch.float32, device=dev)
         self._std_v_host = tuple(float(v) for v in std_v)
@@ -977,13 +1077,14 @@ class Karman3DTrainer:
         sv = self._std_v_host
         v = (vy, vx, vz)
         ph, buoyant = sim.physics, sim.physics.buoyancy is not None
-        keep = []                                   # per step: (saved velocities, network state, d loss_i / d v_i, input density (buoyant mode))
+        akw = {} if sim.adv is None else {"adv": sim.adv}      # (the scheme travels beside the physics value, only where it is not the default)
+        keep = []                                # per step: (saved velocities, network state, d loss_i / d v_i, input density (buoyant mode))
         losses = []
         for i in range(ms):
             saved = [torch.empty_like(t) for t in v]
             feat = torch.empty(B, Y, X, Z, 4, dtype=torch.float32, device=vy.device)
             d_in = d if buoyant else None
-            d, *v = sim._forward(ph, d, v[0], v[1], v[2], re, saved, feat, fs)[0]
+            d, *v = sim._forward(ph, d, v[0], v[1], v[2], re, saved, feat, fs, **akw)[0]
             out, state = sch.forward(feat)
             check(self.lib.sol_karman3d_correct(stream(), ptr(out), net.cout, sv[0], sv[1], sv[2], ptr(v[0]), ptr(v[1]), ptr(v[2]), B, Y, X, Z))
             li, gi = l2_loss_fwd_bwd(v, tuple(g[i] for g in self._gt), sv, gscale=1.0 / ms)
@@ -1017,7 +1118,7 @@ class Karman3DTrainer:
                 G[1][:, :, :X].add_(dx[..., 1], alpha=inv_in[1])
                 G[2][..., :Z].add_(dx[..., 2], alpha=inv_in[2])
             # (nobody reads step 0's input cotangent: it is not taken through the pre-diffusion)
-            g_d, *gin, _ = _step_adjoint3d(sim, ph, buoyant, d_in, saved, re, g_d, G, through_substeps=i > 0)
+            g_d, *gin, _ = _step_adjoint3d(sim, ph, buoyant, d_in, saved, re, g_d, G, through_substeps=i > 0, **akw)
             keep[i] = None                          # (eager runs: the step's activations can go)
         losses = _lib.stack0(losses)
         loss = losses.sum() / ms
@@ -1104,14 +1205,19 @@ class Karman3DRollout:
     buoyancy = property(lambda self: self.sim.physics.buoyancy)
     nsub = property(lambda self: self.sim.physics.nsub)
 
-    def __init__(self, net, scene, B, std_v, std_re, dt=1.0, res=None, conv_precision="split", buoyancy=None, diffusion_substeps=1, **solver):
-        """buoyancy=(fy, fx, fz), diffusion_substeps=n: the StepPhysics3D of the simulator (self.sim.physics); the features keep the true re"""
+    def __init__(self, net, scene, B, std_v, std_re, dt=1.0, res=None, conv_precision="split", buoyancy=None, diffusion_substeps=1,
+                 advection="semi_lagrangian", correction_strength=1.0, **solver):
+        """buoyancy=(fy, fx, fz), diffusion_substeps=n: the StepPhysics3D of the simulator (self.sim.physics); the features keep the true re.
+        advection="mac_cormack", correction_strength=s: the simulator's scheme (self.sim.adv)"""
         from .trainer import _conv_precision_code
         from .schedule3d import NetSchedule3D
+        from .ops import advection_arg
+        advection_arg(advection, correction_strength, "Karman3DRollout: advection")       # (refused before the device is asked for)
         _lib.require_gpu()
         self.lib = _lib.load()
         self.net, self.scene, self.B = net, scene, B
-        self.sim = Karman3DFlow(scene, B, dt=dt, res=res, buoyancy=buoyancy, diffusion_substeps=diffusion_substeps, **solver)
+        self.sim = Karman3DFlow(scene, B, dt=dt, res=res, buoyancy=buoyancy, diffusion_substeps=diffusion_substeps, advection=advection,
+                                correction_strength=correction_strength, **solver)
         self.std_v = tuple(float(v) for v in std_v)
         self.feat_scale = [1.0 / self.std_v[0], 1.0 / self.std_v[1], 1.0 / self.std_v[2], 1.0 / float(std_re)]
         self.conv_precision = _conv_precision_code(conv_precision)

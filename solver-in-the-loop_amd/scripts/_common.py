@@ -82,11 +82,12 @@ def agreed_buoyancy(recorded, flag, where):
     return norm(recorded)
 
 
-def add_advection_arg(p, generates=True):
-    """--advection semi_lagrangian|mac_cormack and --mc-strength S of karman.py; the scripts that read data default to what the data recorded"""
+def add_advection_arg(p, generates=True, where="large grids only; "):
+    """--advection semi_lagrangian|mac_cormack and --mc-strength S of karman.py; the scripts that read data default to what the data recorded.
+    where: on which grids mac_cormack runs, for the help text (karman3d.py: every grid, "")"""
     p.add_argument("--advection", default=None, choices=["semi_lagrangian", "mac_cormack"],
-                   help="advection scheme of the solver step (mac_cormack: large grids only; keeps what the semi-Lagrangian step smears).  "
-                        "Stored with the data like the scene; absent: %s" % ("semi_lagrangian" if generates else "what the data recorded"))
+                   help="advection scheme of the solver step (mac_cormack: %skeeps what the semi-Lagrangian step smears).  "
+                        "Stored with the data like the scene; absent: %s" % (where, "semi_lagrangian" if generates else "what the data recorded"))
     p.add_argument("--mc-strength", default=None, type=float, metavar="S",
                    help="correction strength of mac_cormack, 0 <= S <= 1; absent: %s" % ("1" if generates else "what the data recorded"))
 

@@ -10,14 +10,18 @@ the 2-D workflow carries over.  Frames are written like the 2-D scenes: dens_%06
 and in the model file as "buoyancy" (a triple, or None: off), so that a roll-out of the trained corrector picks it up.
 --diffusion-substeps N|auto: the velocity is diffused by N explicit substeps per solver step (the single stencil is stable only while
 dt res^2 / Re <= 1/6; auto: karman3d.min_diffusion_substeps3d of --re), for generation, --model roll-out and --train-sol alike; recorded
-in params.pickle and in the model file as "diffusion_substeps" and picked up from there like the force."""
+in params.pickle and in the model file as "diffusion_substeps" and picked up from there like the force.
+--advection semi_lagrangian|mac_cormack, --mc-strength S: the advection scheme of the solver step (mac_cormack keeps what the
+semi-Lagrangian step smears; S in [0, 1] is its correction strength), for generation, --model roll-out and --train-sol alike; recorded in
+params.pickle and in the model file as "advection" and "correction_strength" and picked up from there like the force."""
 import argparse
 import pickle
 
 import numpy as np
 import torch
 
-from _common import add_buoyancy_arg, add_substeps_arg, agreed_buoyancy, agreed_substeps, buoyancy_from_args, logger, select_gpu, substeps_from_args
+from _common import (add_advection_arg, add_buoyancy_arg, add_substeps_arg, advection_from_args, agreed_advection, agreed_buoyancy, agreed_substeps,
+                     buoyancy_from_args, logger, select_gpu, substeps_from_args)
 import sol_amd
 from sol_amd import karman3d as k3, scene, synthetic
 
@@ -32,8 +36,8 @@ def staggered3d(vy, vx, vz):
 
 
 def parse_params(argv=None):
-    """The flags, with "buoyancy" as a triple (or None) and "diffusion_substeps" as N, `auto` resolved from --re, or None when absent.
-    Touches no device."""
+    """The flags, with "buoyancy" as a triple (or None), "diffusion_substeps" as N, `auto` resolved from --re, or None when absent, and
+    "advection" / "mc_strength" validated (None when absent).  Touches no device."""
     p = argparse.ArgumentParser(description="Parameter Parser", formatter_class=argparse.ArgumentDefaultsHelpFormatter)
     p.add_argument("--gpu", default="0", help="visible GPUs")
     p.add_argument("-o", "--output", default=None, help="path to an output directory")
@@ -52,7 +56,9 @@ def parse_params(argv=None):
                    help="direct (capacitance blob), cg (preconditioned CG, any mask) or auto (direct where it builds)")
     add_buoyancy_arg(p, ncomp=3)
     add_substeps_arg(p, bound="1/6")
+    add_advection_arg(p, where="")
     params = vars(p.parse_args(argv))
+    params["advection"], params["mc_strength"] = advection_from_args(params)
     params["buoyancy"] = buoyancy_from_args(params, ncomp=3)
     params["diffusion_substeps"] = substeps_from_args(params, [params["re"]], params["res"], minimum=k3.min_diffusion_substeps3d)
     return params
@@ -61,13 +67,19 @@ def parse_params(argv=None):
 def apply_model_record(params, record=None):
     """The run's parameters as recorded in params.pickle: parse_params' with the force and the substep count the run uses.  record: the
     dict of the --model file (None: no model) -- the force and the count the corrector was trained with win, a flag that contradicts them
-    is an error, and a model without a record takes the flag.  No flag and no record: no force, one substep."""
+    is an error, and a model without a record takes the flag.  No flag and no record: no force, one substep.  The advection likewise:
+    "advection" and "correction_strength" are the scheme the run uses (the model's record, else the flags, else semi_lagrangian / 1)."""
     params = dict(params)
     if record is not None and "buoyancy" in record:
         params["buoyancy"] = agreed_buoyancy(record["buoyancy"], params["buoyancy"], params["model"])
     if record is not None and "diffusion_substeps" in record:
         params["diffusion_substeps"] = agreed_substeps(record["diffusion_substeps"], params["diffusion_substeps"], params["model"])
     params["diffusion_substeps"] = params["diffusion_substeps"] or 1
+    flags = (params.get("advection"), params.get("mc_strength"))
+    if record is not None and "advection" in record:
+        params.update(agreed_advection(record, flags, params["model"]))
+    else:
+        params.update({"advection": flags[0] or "semi_lagrangian", "correction_strength": 1.0 if flags[1] is None else float(flags[1])})
     return params
 
 
@@ -83,7 +95,8 @@ def main(argv=None):
     active = np.load(params["obstacle_mask"]) if params["obstacle_mask"] else None
     sc = k3.Scene3D(Y, X, Z, length=float(params["len"]), device=dev, active=active, pressure_solver=params["pressure_solver"])
     buoyancy, nsub = params["buoyancy"], params["diffusion_substeps"]
-    sim = k3.Karman3DFlow(sc, 1, buoyancy=buoyancy, diffusion_substeps=nsub)
+    adv = {"advection": params["advection"], "correction_strength": params["correction_strength"]}
+    sim = k3.Karman3DFlow(sc, 1, buoyancy=buoyancy, diffusion_substeps=nsub, **adv)
     f = lambda a: torch.as_tensor(a, dtype=torch.float32, device=dev).contiguous()
     # karman.py:106-110 in 3-D: uniform flow along y + a sideways poke behind the obstacle
     vy = np.ones((1, Y + 1, X, Z), dtype=np.float32)
@@ -102,11 +115,12 @@ def main(argv=None):
     log.info("pressure solver: %s" % sc.pressure_solver)
     log.info("buoyancy: %s" % (buoyancy,))
     log.info("diffusion substeps: %d" % nsub)
+    log.info("advection: %s (correction strength %g)" % (adv["advection"], adv["correction_strength"]))
     net = ro = None
     if blob is not None:
         net = k3.MarsMoon3D(device=dev)
         net.set_weights([w.numpy() for w in blob["weights"]])
-        ro = k3.Karman3DRollout(net, sc, 1, blob["std_v"], blob["std_re"], buoyancy=buoyancy, diffusion_substeps=nsub)
+        ro = k3.Karman3DRollout(net, sc, 1, blob["std_v"], blob["std_re"], buoyancy=buoyancy, diffusion_substeps=nsub, **adv)
     frames = []
     with torch.no_grad():
         for i in range(1, params["simsteps"]):
@@ -128,7 +142,7 @@ def main(argv=None):
         w = net.get_weights()
         w[22] = w[22] * 0.01
         net.set_weights(w)
-        tr = k3.Karman3DTrainer(net, sc, 1, ms, std_v, max(params["re"], 1.0), use_graph=True, buoyancy=buoyancy, diffusion_substeps=nsub)
+        tr = k3.Karman3DTrainer(net, sc, 1, ms, std_v, max(params["re"], 1.0), use_graph=True, buoyancy=buoyancy, diffusion_substeps=nsub, **adv)
         rng = np.random.default_rng(params["seed"])
         for it in range(params["train_steps"]):
             k = int(rng.integers(0, len(frames) - ms))
@@ -137,7 +151,7 @@ def main(argv=None):
             log.info("train step {:04d}: loss={}".format(it + 1, loss))
         if path:
             torch.save({"name": net.name, "weights": [torch.as_tensor(a) for a in net.get_weights()], "std_v": std_v,
-                        "std_re": max(params["re"], 1.0), "buoyancy": buoyancy, "diffusion_substeps": nsub}, path + "/model3d.pt")
+                        "std_re": max(params["re"], 1.0), "buoyancy": buoyancy, "diffusion_substeps": nsub, **adv}, path + "/model3d.pt")
     return path if path else loss
 
 

@@ -10,7 +10,8 @@ adjoints; .karman_step_buoy = the large-grid step with the buoyancy force (fy, f
 graph; .karman_step_sub = karman_step with nsub explicit diffusion substeps, composing with the density, re and buoyancy modes;
 .karman_step_adv = the large-grid step with the advection named per call (1: MacCormack with correction strength s), composing with all of them;
 .karman3d_step_buoy = the same for the 3-D step, force (fy, fx, fz); .karman3d_step_sub = the 3-D step with nsub explicit diffusion
-substeps, composing with its density, re and buoyancy modes).  Scene constants (masks, solver blobs, the cfg struct) are not tensors: they are registered once with register_scene() and
+substeps, composing with its density, re and buoyancy modes; .karman3d_step_adv = the 3-D step with the advection named per call (1:
+MacCormack with correction strength s), composing with all of them).  Scene constants (masks, solver blobs, the cfg struct) are not tensors: they are registered once with register_scene() and
 referred to by an integer handle."""
 import torch
 
@@ -34,6 +35,7 @@ _LIB.define("karman3d_step_dens(Tensor d, Tensor vy, Tensor vx, Tensor vz, Tenso
 _LIB.define("karman3d_step_re(Tensor d, Tensor vy, Tensor vx, Tensor vz, Tensor re, int scene, bool density=False) -> (Tensor, Tensor, Tensor, Tensor)")
 _LIB.define("karman3d_step_buoy(Tensor d, Tensor vy, Tensor vx, Tensor vz, Tensor re, int scene, float fy, float fx, float fz, bool re_grad=False) -> (Tensor, Tensor, Tensor, Tensor)")
 _LIB.define("karman3d_step_sub(Tensor d, Tensor vy, Tensor vx, Tensor vz, Tensor re, int scene, int nsub, bool density=False, bool re_grad=False, float fy=0.0, float fx=0.0, float fz=0.0) -> (Tensor, Tensor, Tensor, Tensor)")
+_LIB.define("karman3d_step_adv(Tensor d, Tensor vy, Tensor vx, Tensor vz, Tensor re, int scene, int advection, float s=1.0, int nsub=1, bool density=False, bool re_grad=False, float fy=0.0, float fx=0.0, float fz=0.0) -> (Tensor, Tensor, Tensor, Tensor)")
 _LIB.define("karman3d_density_bwd(Tensor d, Tensor svy, Tensor svx, Tensor svz, Tensor re, Tensor gd, int scene) -> (Tensor, Tensor, Tensor, Tensor)")
 _LIB.define("conv3d(Tensor x, Tensor w, Tensor b, Tensor? residual, bool lrelu, float slope) -> Tensor")
 _LIB.define("burgers_step(Tensor vy, Tensor vx, Tensor? fy, Tensor? fx, float dx, float dt, float nu) -> (Tensor, Tensor)")
@@ -201,6 +203,19 @@ def register_scene3d(sim):
 #   karman3d_step_buoy   the buoyant step, force (fy, fx, fz), density in the graph; (0, 0, 0) is the plain step (without a gradient the
 #                        force is kept as given: the _buoy entry point issues the plain launches)
 #   karman3d_step_sub    nsub explicit diffusion substeps named per call, composing with density, re_grad and a force (fy, fx, fz)
+#   karman3d_step_adv    the advection named per call (0 semi-Lagrangian: karman3d_step_sub's launches and bits; 1 MacCormack with
+#                        correction strength s), composing with all of them
+# The ops that name no advection run the registered simulator's own (Karman3DFlow.adv).
+_OWN = object()
+
+
+def _adv3d(op, advection, s):
+    """ops.advection_arg of an op's (advection, s): None for 0, the float s for 1"""
+    if advection not in (0, 1):
+        raise ValueError("torch.ops.sol.%s: advection must be 0 (semi_lagrangian) or 1 (mac_cormack), got %r" % (op, advection))
+    return ops.advection_arg(ops.ADVECTIONS[advection], s, "torch.ops.sol.%s: advection" % op)
+
+
 def _physics3d(scene, op, nsub=None, force=None, keep_zero_force=False):
     """the StepPhysics3D of an op's arguments, validated; nsub=None: the registered simulator's own count"""
     from . import karman3d as k3
@@ -208,16 +223,18 @@ def _physics3d(scene, op, nsub=None, force=None, keep_zero_force=False):
                                keep_zero_force=keep_zero_force)
 
 
-def _karman3d_apply(scene, tensors, density, re_grad, ph):
+def _karman3d_apply(scene, tensors, density, re_grad, ph, adv=_OWN):
     from . import karman3d as k3
     d, vy, vx, vz, re = (_lib.f32(t) for t in tensors)
-    return k3._Karman3DStepFn.apply(_SIMS3D[scene], d, vy, vx, vz, re, bool(density), _want_re(re_grad, re), ph.moving())
+    sim = _SIMS3D[scene]
+    return k3._Karman3DStepFn.apply(sim, d, vy, vx, vz, re, bool(density), _want_re(re_grad, re), ph.moving(), sim.adv if adv is _OWN else adv)
 
 
-def _karman3d_nograd(scene, tensors, ph):
+def _karman3d_nograd(scene, tensors, ph, adv=_OWN):
     """no gradient wanted: the forward launches, nothing kept"""
+    sim = _SIMS3D[scene]
     with torch.no_grad():
-        return _SIMS3D[scene]._forward(ph, *(_lib.f32(t) for t in tensors))[0]
+        return sim._forward(ph, *(_lib.f32(t) for t in tensors), adv=sim.adv if adv is _OWN else adv)[0]
 
 
 def _karman3d_density_bwd(d, svy, svx, svz, re, gd, scene):
@@ -244,5 +261,10 @@ _LIB.impl("karman3d_step_sub", lambda d, vy, vx, vz, re, scene, nsub, density=Fa
           _karman3d_nograd(scene, (d, vy, vx, vz, re), _physics3d(scene, "karman3d_step_sub", nsub, (fy, fx, fz))), "CUDA")
 _LIB.impl("karman3d_step_sub", lambda d, vy, vx, vz, re, scene, nsub, density=False, re_grad=False, fy=0.0, fx=0.0, fz=0.0:
           _karman3d_apply(scene, (d, vy, vx, vz, re), density, re_grad, _physics3d(scene, "karman3d_step_sub", nsub, (fy, fx, fz))), "AutogradCUDA")
+_LIB.impl("karman3d_step_adv", lambda d, vy, vx, vz, re, scene, advection, s=1.0, nsub=1, density=False, re_grad=False, fy=0.0, fx=0.0, fz=0.0:
+          _karman3d_nograd(scene, (d, vy, vx, vz, re), _physics3d(scene, "karman3d_step_adv", nsub, (fy, fx, fz)), _adv3d("karman3d_step_adv", advection, s)), "CUDA")
+_LIB.impl("karman3d_step_adv", lambda d, vy, vx, vz, re, scene, advection, s=1.0, nsub=1, density=False, re_grad=False, fy=0.0, fx=0.0, fz=0.0:
+          _karman3d_apply(scene, (d, vy, vx, vz, re), density, re_grad, _physics3d(scene, "karman3d_step_adv", nsub, (fy, fx, fz)),
+                          _adv3d("karman3d_step_adv", advection, s)), "AutogradCUDA")
 _LIB.impl("karman3d_density_bwd", _karman3d_density_bwd, "CUDA")
 _LIB.impl("conv3d", _conv3d, "AutogradCUDA")

@@ -2,8 +2,9 @@
 """Host cost of the karman-3d step's Python layer, this tree against ANOTHER TREE (an export of another commit) on one library: for a
 change of karman3d.py / torch_ops.py that moves no kernel, only the eager calls can move (a captured trainer replays a graph and never
 sees the Python layer).
-    python tools/k3d_step_physics_time.py OTHER_ROOT [rounds] [--out profiles/k3d_step_physics_refactor_speed.json]      (on the GPU box)
-Per round one fresh process per tree, the other tree first, alternating; both load THIS tree's library (SOL_HIP_LIB).  Each process
+    python tools/k3d_step_physics_time.py OTHER_ROOT [rounds] [--own-libs] [--out profiles/k3d_step_physics_refactor_speed.json]      (on the GPU box)
+Per round one fresh process per tree, the other tree first, alternating; both load THIS tree's library (SOL_HIP_LIB) -- with --own-libs
+each tree loads the library built in its own tree (a change that touches the C sources' default path).  Each process
 times, on karman3d_adjoint_cases' 16_comb scene (B = 2, 16 x 8 x 8) and at 32 x 16 x 16 with B = 1 (the default sphere, direct solve):
 the no-grad Karman3DFlow.step; step + backward in the plain, the density_grad + re_grad and the buoyant diffusion_substeps = 3 modes;
 one eager manual Karman3DTrainer.fwd_bwd (msteps = 2).  A host clock around CALLS calls that end in a device synchronise, the median of
@@ -78,10 +79,15 @@ def main():
         k = args.index("--out")
         dst = args[k + 1]
         del args[k:k + 2]
+    own_libs = "--own-libs" in args          # each tree loads the library built in ITS tree: a change of the C sources whose default path must
+    if own_libs:                             # cost what it did (the other tree's library must have been built)
+        args.remove("--own-libs")
     if not 1 <= len(args) <= 2:
         sys.exit(__doc__)
     other, rounds = os.path.abspath(args[0]), int(args[1]) if len(args) > 1 else 6
     env = dict(os.environ, SOL_HIP_LIB=os.path.join(ROOT, "solver-in-the-loop_amd", "lib", "libsol_hip.so"))
+    if own_libs:
+        del env["SOL_HIP_LIB"]
     runs = {"other": {}, "this": {}}
     for r in range(rounds):
         for name, root in (("other", other), ("this", ROOT)):

@@ -1,9 +1,10 @@
 #!/usr/bin/env python
 """Does the Python layer of ANOTHER TREE of this package (an export of another commit) drive the 2-D Karman step to the SAME BITS and
 the SAME LAUNCHES as this tree?  For a change of ops.py / torch_ops.py / trainer.py / karman.py that must not move a result.
-    python tools/tree_bitcompare.py OTHER_ROOT [--suite 3d] [--out verdicts.json]        (on the GPU box; --suite 3d: the 3-D step, child3d below)
+    python tools/tree_bitcompare.py OTHER_ROOT [--suite 3d] [--own-libs] [--out verdicts.json]        (on the GPU box; --suite 3d: the 3-D step, child3d below)
 Each tree is imported in a fresh child process from its own root, through the package's public names only (and _lib.profile for the
-census); both load THIS tree's library (SOL_HIP_LIB), so the C sources of the two trees must be the same.  The cases come from the
+census); both load THIS tree's library (SOL_HIP_LIB), so the C sources of the two trees must be the same -- or, with --own-libs, each
+tree loads the library built in its own tree: a change of the C sources that must leave these cases (the default paths) alone.  The cases come from the
 tables of this tree's GPU tests (tests/buoyancy_cases.py: sphere_130 direct, two_144 cg and direct_scattered, B = 2) and one
 one-workgroup grid, 32 x 16.  Per large-grid scene: force in {none, (0, 0), FORCES[1]} x advection in {semi_lagrangian, mac_cormack
 s = 0.5} x diffusion_substeps in {1, 2}, each through karman_step_large under autograd (density_grad x re_grad x the cotangent sets
@@ -321,10 +322,15 @@ def main():
         k = args.index("--suite")
         suite = args[k + 1]
         del args[k:k + 2]
+    own_libs = "--own-libs" in args          # each tree loads the library built in ITS tree: for a change of the C sources that must not move
+    if own_libs:                             # the cases of this tool (the default paths); the other tree's library must have been built
+        args.remove("--own-libs")
     if len(args) != 1 or suite not in ("2d", "3d"):
         sys.exit(__doc__)
     other = os.path.abspath(args[0])
     env = dict(os.environ, SOL_HIP_LIB=os.path.join(ROOT, "solver-in-the-loop_amd", "lib", "libsol_hip.so"))
+    if own_libs:
+        del env["SOL_HIP_LIB"]
     res = {}
     for name, root in (("other", other), ("this", ROOT)):
         o = subprocess.run([sys.executable, os.path.abspath(__file__), "--child" if suite == "2d" else "--child3d", root], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
