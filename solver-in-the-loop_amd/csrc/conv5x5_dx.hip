@@ -144,8 +144,9 @@ __global__ void __launch_bounds__(512) k_conv5x5_dx(const float* __restrict__ ar
     // image of row G0: H is a power of two in every shipped configuration (a.RPW = log2 H, set by the launcher; -1: one division)
     const int b0 = a.RPW >= 0 ? (G0 >> a.RPW) : G0 / H;
     const int lo0 = b0 * H, hi0 = lo0 + H;
-    // validity of (input slot s, output row j): the input row G0 - 2 + s must lie in the image of output row G0 + j; the three
-    // rows span at most two images, and for one j the valid s form a range
+    // validity of (input slot s, output row j): the input row G0 - 2 + s must lie in the image of output row G0 + j; the R rows
+    // span at most two images -- b0 and the one behind it -- because the launcher gives images of H < 2 rows one-row workgroups
+    // (dx_rows_per_wg; with H = 1 three rows would be three images), and for one j the valid s form a range
     unsigned vmask = 0u;                                        // bit j * 8 + s  (wave uniform: SGPR)
 #pragma unroll
     for (int j = 0; j < R; ++j) {
@@ -515,8 +516,10 @@ extern "C" int sol_conv_dx_prof_set(long long* buf, unsigned cap) {
 }
 #endif
 
-// three rows per workgroup where that fills the chip; one row where the launch is small (< 128 three-row workgroups)
-static int dx_rows_per_wg(int nrows, int tiles_x) { return ((nrows + 2) / 3) * tiles_x >= 128 ? 3 : 1; }
+// three rows per workgroup where that fills the chip; one row where the launch is small (< 128 three-row workgroups) -- and for
+// one-row images (H < 2), whatever their number: a three-row workgroup would span three images, and the kernel's row mask is made
+// for two (k_conv5x5_dx, `vmask`)
+static int dx_rows_per_wg(int nrows, int tiles_x, int H) { return H >= 2 && ((nrows + 2) / 3) * tiles_x >= 128 ? 3 : 1; }
 
 bool sol_conv_dx_usable(const ConvArgs& a, int NT, int ntiles) {
     if (!sol_opt().conv_dx || !a.xmax || !a.wsh || a.W % 64 != 0) return false;
@@ -526,7 +529,7 @@ bool sol_conv_dx_usable(const ConvArgs& a, int NT, int ntiles) {
     // (SOL-32 step at 128x64, B = 6: 13.26 ms against 13.43); in the small launches (one row per workgroup: the 64x32 recipe, roll-outs)
     // the dx form wins (8.94 against 9.04 ms per recipe step; tools/conv_thin_ab.py).
     if (NT != 1 || a.CO > 16 || !(sol_opt().conv_dx & 2)) return false;
-    return (sol_opt().conv_dx & 4) != 0 || dx_rows_per_wg(ntiles / a.tiles_x, a.tiles_x) == 1;
+    return (sol_opt().conv_dx & 4) != 0 || dx_rows_per_wg(ntiles / a.tiles_x, a.tiles_x, a.H) == 1;
 }
 
 int sol_conv_dx_launch(hipStream_t s, const ConvArgs& a_in, int ntiles) {
@@ -540,7 +543,7 @@ int sol_conv_dx_launch(hipStream_t s, const ConvArgs& a_in, int ntiles) {
                                          SOL_K((k_conv5x5_dx<3, 1, false, true>)), SOL_K((k_conv5x5_dx<1, 1, true, true>))}, "k_conv5x5_dx")) return e;
     const bool thin = a.CO <= 16;
     const int nrows = ntiles / a.tiles_x;                 // global image rows B*H
-    const int R = dx_rows_per_wg(nrows, a.tiles_x);
+    const int R = dx_rows_per_wg(nrows, a.tiles_x, a.H);
     int grid = ((nrows + R - 1) / R) * a.tiles_x;
     if (grid > 64) grid = (grid + 7) / 8 * 8;             // XCD-aware tile order needs a multiple of 8 (xcd_tile); padding tiles own no rows
     if (sol_conv_masked(a)) {                             // pitched rows: the same choice among the MASK instantiations (never the correction mode)

@@ -431,11 +431,15 @@ class _option:
         return False
 
 
-@pytest.mark.parametrize("B,ms,use_graph", [(6, 4, False), (6, 4, True), (1, 3, False), (9, 2, False)])
+@pytest.mark.parametrize("B,ms,use_graph", [(6, 4, False), (6, 4, True), (1, 3, False), (9, 2, False),
+                                            (8, 1, False), (16, 1, False), (17, 2, True), (40, 2, False)])
 def test_band_split_forward_launch_equals_the_one_workgroup_kernel_bit_for_bit(B, ms, use_graph):
     """Four workgroups per simulation (stencil phases on row bands with recomputed halos, two hand-offs through global memory) must
     reproduce every bit of the one-workgroup kernel: same arithmetic, same order.  Checked through the trainer (per-step losses,
-    gradient, final velocity and density: the forward states feed all of them), eager and replayed, B not a multiple of 8 included."""
+    gradient, final velocity and density: the forward states feed all of them), eager and replayed, B not a multiple of 8 included.
+    The launch lays its workgroups out in groups of 8 simulations: one and two full groups (B = 8, 16), the first simulation of a
+    third group (17) and the last batch sol_karman_fwd_bands_usable admits (B = 40: 200 band workgroups and 40 density workgroups
+    riding along; B = 41 falls back, tests/test_gpu_train2d_batch_regimes.py holds that path to the oracle)."""
     out = {}
     for bands in (0, 1):
         with _option("fwd_bands", bands):

@@ -251,15 +251,18 @@ def test_train_step_against_golden(golden_dir):
     assert rel(tr.final[0], z["d_final"]) < TOL_FIELD
 
 
-def _oracle_problem(B, Y, X, ms, clip=None):
+def _oracle_problem(B, Y, X, ms, clip=None, with_states=False):
+    """with_states: also the oracle's per-step losses and its final (d, vy, vx), from the same unroll"""
     g = o.geometry(Y, X)
     d, vy, vx = o.synthetic_state(B, Y, X, 1234)
     re = torch.tensor([o.RE_TRAIN[i % 6] for i in range(B)], dtype=torch.float64)
     gts = [o.synthetic_state(B, Y, X, 4321 + i, project_it=False) for i in range(ms)]
     params = [p.clone().requires_grad_(True) for p in o.init_params(0)]
     std_v = (0.2, 0.25)
-    loss = o.unrolled_loss(params, d, vy, vx, re, [s[1] for s in gts], [s[2] for s in gts], g, std_v, o.STD_RE)
+    loss, losses, states = o.unrolled_loss(params, d, vy, vx, re, [s[1] for s in gts], [s[2] for s in gts], g, std_v, o.STD_RE, return_states=True)
     loss.backward()
+    if with_states:
+        return g, d, vy, vx, re, gts, params, std_v, loss, [float(l.detach()) for l in losses], tuple(t.detach() for t in states[-1])
     return g, d, vy, vx, re, gts, params, std_v, loss
 
 
@@ -405,13 +408,43 @@ def test_conv5x5_scaled_fp16_path_against_float64(conv_dx):
     assert torch.equal(y, torch.nn.functional.leaky_relu(bias, 0.3).expand(B, Y, X, cout))
 
 
-@pytest.mark.parametrize("B,H,W", [(6, 128, 64), (3, 32, 64), (2, 5, 64), (1, 7, 128), (4, 3, 64), (1, 1, 64), (5, 2, 64), (3, 4, 64)])
-def test_conv5x5_dx_kernel_every_epilogue_against_float64_and_the_row_per_wave_kernel(B, H, W):
+DX_3ROW, DX_1ROW = "k_conv5x5_dx<3, 2>", "k_conv5x5_dx<1, 1, true>"
+DX_DEFAULT = 11         # option conv_dx as shipped: the dx kernel for the 32 -> 32 layers (1) and the thin one-row launches (2), one-row launches SPLIT (8)
+# (B, H, W, form): the three-row form runs from ceil(B H / 3) (W / 64) >= 128 workgroups on (dx_rows_per_wg, csrc/conv5x5_dx.hip), and a
+# grid above 64 is rounded up to a multiple of 8; tests/test_train2d_batch_regimes_cpu.py asserts every number quoted below
+DX_SHAPES = [
+    (6, 128, 64, DX_3ROW),      # the benchmark's batch: 768 rows, 256 exact workgroups
+    (3, 32, 64, DX_1ROW),       # the transposed 64x32 recipe's shape
+    (2, 5, 64, DX_1ROW),        # this and the four (B, 2..4, 64) below: images no taller, or shorter, than the tap window
+    (1, 7, 128, DX_1ROW),       # two column blocks
+    (4, 3, 64, DX_1ROW),
+    (1, 1, 64, DX_1ROW),        # a one-row image
+    (5, 2, 64, DX_1ROW),
+    (3, 4, 64, DX_1ROW),
+    (3, 128, 64, DX_3ROW),      # 384 rows: exactly 128 three-row workgroups, the threshold
+    (2, 190, 64, DX_1ROW),      # 380 rows: the other side of it; grid 380 -> 384 (padding tiles in the one-row form); H no power of two
+    (4, 128, 64, DX_3ROW),      # 512 rows: the last workgroup owns 2 rows; 171 -> 176 workgroups (5 padding tiles)
+    (5, 128, 64, DX_3ROW),      # 640 rows: the last workgroup owns 1 row; 214 -> 216
+    (2, 200, 64, DX_3ROW),      # H no power of two (the image of a row by one division); tail 1; 134 -> 136
+    (1, 384, 64, DX_3ROW),      # one tall image
+    (2, 97, 128, DX_3ROW),      # two column blocks: 65 row groups x 2 = 130 -> 136; tail 2; odd H
+    (130, 3, 64, DX_3ROW),      # images shorter than the tap window, one per workgroup; 130 -> 136
+    (200, 2, 64, DX_3ROW),      # every workgroup spans two images; 134 -> 136, tail 1
+    (384, 1, 64, DX_1ROW),      # one-row images: three of them would share a three-row workgroup, whose row mask knows two -- the launcher
+]                               # keeps the one-row form for H < 2 (the three-row form there: 4.3e-1 off the float64 convolution, now 7.0e-8)
+
+
+@pytest.mark.parametrize("B,H,W,form", DX_SHAPES, ids=["%d-%d-%d" % s[:3] for s in DX_SHAPES])
+def test_conv5x5_dx_kernel_every_epilogue_against_float64_and_the_row_per_wave_kernel(B, H, W, form):
     """The dx-major 32 -> 32 kernel (csrc/conv5x5_dx.hip: a wave owns a pixel segment of ALL output rows of its workgroup, input
-    rows shared across tap rows) against a float64 convolution and against k_conv5x5_sb<2, 2> for every epilogue form: workgroups
-    that straddle two images (H % 3 != 0), images shorter than the tap window, one-row images, two column blocks (W = 128), the
-    transposed 64x32 recipe's shape, and the small-launch form (one output row per workgroup when the launch has few rows).  Same
-    operand splits and products as the other kernel, another summation order: equal to it to fp32 round-off, not bit for bit."""
+    rows shared across tap rows) against a float64 convolution and against k_conv5x5_sb<2, 2> for every epilogue form.  The shapes
+    (DX_SHAPES says what each is for): workgroups that straddle two images (H % 3 != 0), images shorter than the tap window, one-row
+    images, two column blocks (W = 128), the transposed 64x32 recipe's shape, the small-launch form (one output row per workgroup
+    when the launch has few rows) -- and both forms where the grid is NOT exact: either side of the 128-workgroup threshold, a last
+    workgroup that owns one or two rows, the padding tiles of a grid rounded up to a multiple of 8 (they own no rows), an H that
+    is no power of two in the three-row form, two column blocks with a tail, and many short images.  The launch profiler says which
+    form ran.  Same operand splits and products as the other kernel, another summation order: equal to it to fp32 round-off, not
+    bit for bit."""
     from sol_amd import _lib
     gen = torch.Generator().manual_seed(B * 1000 + H)
     x = torch.randn(B, H, W, 32, generator=gen, dtype=torch.float32).to(DEV)
@@ -432,28 +465,35 @@ def test_conv5x5_dx_kernel_every_epilogue_against_float64_and_the_row_per_wave_k
             elif epi == ops.EPI_DLRELU:
                 ref = ref * torch.where(aa.double() > 0, 1.0, 0.3)
             ys = {}
-            for dx in (1, 0):
+            for dx in (DX_DEFAULT, 1, 0):               # the default form, the one-row form with both channel tiles (the same kernel in big launches), the other kernel
                 _lib.set_option("conv_dx", dx)
                 ym = torch.zeros(ops.AMAX_SLOTS, dtype=torch.int32, device=DEV)
                 ys[dx] = ops.conv5x5_scaled_raw(x, packed, bb, rr, aa, 32, epi, 0.3, xm, ym)
                 assert float(ym.max().view(torch.float32).item()) == float(ys[dx].abs().max()), (name, dx)
-            assert rel(ys[1], ref) < 6e-7 and rel(ys[1], ref) < 1.5 * rel(ys[0], ref) + 1e-8, (name, rel(ys[1], ref), rel(ys[0], ref))
-            assert rel(ys[1], ys[0]) < 6e-7
-            _lib.set_option("conv_dx", 1)
-            with _lib.profile() as p:
-                ops.conv5x5_scaled_raw(x, packed, bb, rr, aa, 32, epi, 0.3, xm, None)
-            assert any(k.strip("()").startswith("k_conv5x5_dx") for k in p.kernels), p.kernels       # the dx kernel did run
+            for dx in (DX_DEFAULT, 1):
+                print("conv_dx %d [%d,%d,%d] %s: %.2e (row-per-wave kernel %.2e)" % (dx, B, H, W, name, rel(ys[dx], ref), rel(ys[0], ref)))
+                assert rel(ys[dx], ref) < 6e-7 and rel(ys[dx], ref) < 1.5 * rel(ys[0], ref) + 1e-8, (name, dx, rel(ys[dx], ref), rel(ys[0], ref))
+                assert rel(ys[dx], ys[0]) < 6e-7
+                _lib.set_option("conv_dx", dx)
+                with _lib.profile() as p:
+                    ops.conv5x5_scaled_raw(x, packed, bb, rr, aa, 32, epi, 0.3, xm, None)
+                ran = [k.strip("()") for k in p.kernels if "k_conv5x5_dx" in k]
+                assert len(ran) == 1, p.kernels                                       # the dx kernel did run
+                assert dx != DX_DEFAULT or ran == [form], (form, p.kernels)           # ... in the form this shape is here for
     finally:
         _lib.set_option("conv_dx", saved)
 
 
-@pytest.mark.parametrize("B,H,W", [(6, 128, 64), (2, 5, 64), (1, 7, 128), (1, 1, 64)])
+@pytest.mark.parametrize("B,H,W", [(6, 128, 64), (2, 5, 64), (1, 7, 128), (1, 1, 64), (4, 128, 64), (2, 97, 128)])
 @pytest.mark.parametrize("cout", [2, 3, 16])
 def test_conv5x5_dx_thin_layers_against_float64_and_the_row_per_wave_kernel(B, H, W, cout):
     """The thin-layer form of the dx-major kernel (k_conv5x5_dx<R, 1>: <= 16 output channels, waves 4..7 stage only; option conv_dx
     bit 1 = in one-row-per-workgroup launches (default), bit 2 = everywhere) against a float64 convolution and k_conv5x5_sb<1, 2>
-    for the strided-store epilogues (the correction-mode epilogue is covered by the trainer and roll-out tests at B = 1)."""
+    for the strided-store epilogues (the correction-mode epilogue is covered by the trainer and roll-out tests at B = 1).
+    (6, 128, 64) is an exact grid of three-row workgroups; (4, 128, 64) has a last workgroup of two rows and five padding tiles
+    (171 -> 176), (2, 97, 128) two column blocks, a tail of two rows and 130 -> 136: k_conv5x5_dx<3, 1> there, <1, 1> in the rest."""
     from sol_amd import _lib
+    thin_form = "k_conv5x5_dx<3, 1>" if (B, H, W) in ((6, 128, 64), (4, 128, 64), (2, 97, 128)) else "k_conv5x5_dx<1, 1>"
     gen = torch.Generator().manual_seed(B * 100 + H + cout)
     x = torch.randn(B, H, W, 32, generator=gen, dtype=torch.float32).to(DEV)
     w = (torch.randn(5, 5, 32, cout, generator=gen, dtype=torch.float32) * 0.05).to(DEV)
@@ -481,6 +521,7 @@ def test_conv5x5_dx_thin_layers_against_float64_and_the_row_per_wave_kernel(B, H
                     ys[dx] = ops.conv5x5_scaled_raw(x, packed, bb, rr, aa, cout, epi, 0.3, xm, ym)
                 assert float(ym.max().view(torch.float32).item()) == float(ys[dx].abs().max()), (name, dx)
                 assert any(("k_conv5x5_dx" in k) == (dx == 7) for k in p.kernels), (dx, p.kernels)
+                assert dx != 7 or [k.strip("()") for k in p.kernels if "k_conv5x5_dx" in k] == [thin_form], (thin_form, p.kernels)
             assert rel(ys[7], ref) < 6e-7 and rel(ys[7], ref) < 1.5 * rel(ys[1], ref) + 1e-8, (name, rel(ys[7], ref), rel(ys[1], ref))
     finally:
         _lib.set_option("conv_dx", saved)
@@ -822,15 +863,21 @@ def test_shard_gradients_sum_to_the_large_batch_gradient():
     assert rel(acc, full.grads) < 1e-5
 
 
-@pytest.mark.parametrize("Y,X,n", [(64, 32, 3), (64, 32, 10), (128, 64, 2), (128, 64, 3), (128, 64, 1)])
-def test_rollout_against_oracle(Y, X, n):
+ROLLOUTS = [(64, 32, 3, 1), (64, 32, 10, 1), (128, 64, 2, 1), (128, 64, 3, 1), (128, 64, 1, 1),
+            (128, 64, 3, 4), (128, 64, 2, 6), (128, 64, 2, 41), (64, 32, 2, 13)]
+
+
+@pytest.mark.parametrize("Y,X,n,B", ROLLOUTS, ids=["%d-%d-%d" % r[:3] + ("-B%d" % r[3] if r[3] > 1 else "") for r in ROLLOUTS])
+def test_rollout_against_oracle(Y, X, n, B):
     """odd / even step counts (the state ping-pongs between the caller's buffers and the workspace), more steps than absmax
     slot sets, and the 128x64 path whose last CNN layer applies the correction itself and whose passive density rides one step
-    behind in the solver launches (even, odd and a single step: the last advection is its own launch)"""
-    B = 1
+    behind in the solver launches (even, odd and a single step: the last advection is its own launch).  More than one simulation,
+    each with its own Reynolds number: B = 4 (three-row convolution launches with a ragged last workgroup and padding tiles), B = 6
+    (the roll-out leg the benchmark reports), B = 41 (beyond the band-split solver launch and the three-row thin-input kernel) and
+    the transposed 64x32 CNN at B = 13 (three-row form, images straddling workgroups)."""
     g = o.geometry(Y, X)
     d, vy, vx = o.synthetic_state(B, Y, X, 21)
-    re = torch.tensor([o.RE_TRAIN[2]], dtype=torch.float64)
+    re = torch.tensor([o.RE_TRAIN[2]] if B == 1 else [o.RE_TRAIN[i % 6] for i in range(B)], dtype=torch.float64)
     params = o.init_params(3)
     std_v = (0.2, 0.2)
     rd, ry, rx = d, vy, vx
