@@ -838,7 +838,18 @@ typedef struct sol_karman3d_cfg {
     int32_t direct_n;       /* number of 32-bit words of `direct`                                        */
     const float* direct;    /* DEVICE blob of the direct pressure solver for the scene's `active` mask
                                (three sine-transform matrices, 1/eigenvalues, capacitance matrix of the
-                               obstacle cells; layout: precond3d.direct_solver_blob3d).  Required.       */
+                               obstacle cells; layout: precond3d.direct_solver_blob3d).  Required.
+                               Two layouts, told apart by the magic in word 0 (32-bit words; N = Y X Z):
+                               "FD33" header[16] = {magic, Y, X, Z, nS, SP}; Qy[Y*Y]; Qx[X*X]; Qz[Z*Z]; invlam[N];
+                                      KpT[SP][SP] (K' transposed, zero padded, SP % 64 == 0); sidx[SP] int32 (cell index
+                                      (j X + i) Z + k, -1 = padding).  nS = 0: the empty box (what the CG solve takes).
+                               "FD3E" (precond3d.extruded_solver_blob3d: an obstacle extruded along z, active[j][i][k] =
+                                      a2[j][i]) header[16] = {magic, Y, X, Z, nS2, SP2}; Qy, Qx, Qz, invlam as above;
+                                      KpT[Z][SP2][SP2] (K'_m of z mode m, transposed, zero padded, SP2 % 32 == 0);
+                                      sidx2[SP2] int32 (in-plane cell index j X + i, -1 = padding).  1 <= nS2 <= SP2 <= 1024,
+                                      SP2 <= Y X, Z <= 128, Z SP2^2 <= 2^26.  Direct solve only (pressure_solver = 0): the
+                                      capacitance product becomes Z products of size SP2 between two sine transforms
+                                      along z of the support columns; same entry points, same workspace sizes.            */
     /* pressure solver (all zero = the direct solve; appended in ABI 216) */
     int32_t pressure_solver;   /* 0: direct (capacitance blob), 1: preconditioned CG (blob with nS = 0)  */
     int32_t cg_max_iter;       /* CG: launch budget in iterations (>= 1); the launch sequence is fixed    */

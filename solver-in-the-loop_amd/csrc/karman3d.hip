@@ -21,6 +21,8 @@
 //   pressure        DIRECT solve x = G (b - U_S E_SS x_S), x_S = (I + G_SS E_SS)^-1 (G b)_S with G = the empty-box Dirichlet
 //                   Laplacian diagonalised by three sine transforms (batched fp32 GEMMs along z, x, y) and the capacitance
 //                   correction of the obstacle cells (precond3d.direct_solver_blob3d): 12 transform passes + k3_capacitance
+//                   (an obstacle extruded along z, blob "FD3E" of precond3d.extruded_solver_blob3d: the correction runs mode by
+//                   mode in the z-spectral basis instead -- k3e_gather_tz, k3e_modes, k3e_tz_apply)
 //   k3_project      v -= mask * grad p, fused to_feature (4 channels: three components + Re)
 // The adjoint of the step (sol_karman3d_step_bwd: k3b_* kernels, second half of this file) reverses these stages; its
 // advection scatter runs in 64-bit fixed point and is bit-reproducible.  sol_karman3d_step_bwd_re: the same launches, then the gradient
@@ -394,6 +396,99 @@ __global__ void __launch_bounds__(256) k3_cap_apply(const float* __restrict__ pa
     rhs[(size_t)b * N + si] -= c;
 }
 
+// ---- capacitance correction of an obstacle EXTRUDED along z (blob "FD3E": precond3d.extruded_solver_blob3d) ---------------
+// active[j][i][k] = a2[j][i]: the pressure matrix separates along z, and in the z-spectral basis mode m has a capacitance
+// matrix K'_m of its own on the in-plane set S2 (sidx2[s] = j * X + i, -1 = padding).  Between the two applications of G:
+//   k3e_gather_tz   x^[b][m][s] = sum_k g[b][sidx2[s]][k] Qz[k][m]        (the support columns into the spectral basis)
+//   k3e_modes       c^[b][m][s] = sum_q KpT[m][q][s] x^[b][m][q]           (Z independent products of size SP2)
+//   k3e_tz_apply    rhs[b][sidx2[s]][k] -= sum_m c^[b][m][s] Qz[m][k]      (back, and the correction itself)
+// The two transform launches take EXC support columns a workgroup, with Qz [Z][Z] and the columns [EXC][Z + 1] in (dynamic) LDS:
+// the columns are loaded from g and stored into rhs with lanes along z (coalesced), the spectral values cross through
+// [b][m][s] scratch so that a mode's vector is contiguous for k3e_modes.  Every sum runs in a fixed order: no atomics.
+constexpr int FD3E_MAGIC = 0x46443345;    // "FD3E"
+constexpr int FD3E_MAX_Z = 128, FD3E_MAX_SP2 = 1024;
+constexpr int EXC = 8;                    // support columns per workgroup of the transform launches (divides SP2, a multiple of 32)
+constexpr int EXB = 8;                    // simulations per pass of k3e_modes over its part of K'_m: one pass, one read, up to B = 8
+inline size_t k3e_lds_bytes(int Z) { return ((size_t)Z * Z + (size_t)EXC * (Z + 1)) * sizeof(float); }
+
+__global__ void __launch_bounds__(256) k3e_gather_tz(const float* __restrict__ g, const float* __restrict__ Qz, const int* __restrict__ sidx2,
+                                                      float* __restrict__ xh, int Z, int SP2, int YX) {
+    extern __shared__ float k3e_lds[];
+    float* Q = k3e_lds;
+    float* col = k3e_lds + Z * Z;
+    const int b = blockIdx.y, s0 = blockIdx.x * EXC, t = threadIdx.x;
+    const float* gb = g + (size_t)b * YX * Z;
+    for (int e = t; e < Z * Z; e += 256) Q[e] = Qz[e];
+    for (int e = t; e < EXC * Z; e += 256) {
+        const int c = e / Z, k = e - c * Z, si = sidx2[s0 + c];
+        col[c * (Z + 1) + k] = (unsigned)si < (unsigned)YX ? gb[(size_t)si * Z + k] : 0.f;
+    }
+    __syncthreads();
+    for (int e = t; e < EXC * Z; e += 256) {
+        const int m = e / EXC, c = e - m * EXC;
+        float a = 0.f;
+        for (int k = 0; k < Z; ++k) a += col[c * (Z + 1) + k] * Q[k * Z + m];
+        xh[((size_t)b * Z + m) * SP2 + s0 + c] = a;
+    }
+}
+
+// grid (SP2 / 32, Z): 32 outputs x 8 slices of the sum over q for one mode, every simulation of the pass in registers (K'_m is read
+// once for up to EXB simulations); the slices fold through LDS in a fixed order
+__global__ void __launch_bounds__(256) k3e_modes(const float* __restrict__ xh, const float* __restrict__ KpT, float* __restrict__ ch, int B, int Z, int SP2) {
+    __shared__ float xs[EXB][FD3E_MAX_SP2];
+    __shared__ float red[8][EXB][32];
+    const int m = blockIdx.y, s0 = blockIdx.x * 32, t = threadIdx.x, sl = t >> 5, ln = t & 31;
+    const float* K = KpT + (size_t)m * SP2 * SP2 + s0 + ln;
+    for (int b0 = 0; b0 < B; b0 += EXB) {
+        const int nb = B - b0 < EXB ? B - b0 : EXB;
+        for (int e = t; e < EXB * SP2; e += 256) {
+            const int bb = e / SP2, q = e - bb * SP2;
+            xs[bb][q] = bb < nb ? xh[((size_t)(b0 + bb) * Z + m) * SP2 + q] : 0.f;
+        }
+        __syncthreads();
+        float acc[EXB];
+#pragma unroll
+        for (int bb = 0; bb < EXB; ++bb) acc[bb] = 0.f;
+        for (int q = sl; q < SP2; q += 8) {
+            const float kv = K[(size_t)q * SP2];
+#pragma unroll
+            for (int bb = 0; bb < EXB; ++bb) acc[bb] += kv * xs[bb][q];
+        }
+#pragma unroll
+        for (int bb = 0; bb < EXB; ++bb) red[sl][bb][ln] = acc[bb];
+        __syncthreads();
+        if (sl < nb) {                       // thread (sl, ln) folds simulation b0 + sl
+            float v = 0.f;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) v += red[k][sl][ln];
+            ch[((size_t)(b0 + sl) * Z + m) * SP2 + s0 + ln] = v;
+        }
+        __syncthreads();
+    }
+}
+
+__global__ void __launch_bounds__(256) k3e_tz_apply(const float* __restrict__ ch, const float* __restrict__ Qz, const int* __restrict__ sidx2,
+                                                     float* __restrict__ rhs, int Z, int SP2, int YX) {
+    extern __shared__ float k3e_lds[];
+    float* Q = k3e_lds;
+    float* col = k3e_lds + Z * Z;
+    const int b = blockIdx.y, s0 = blockIdx.x * EXC, t = threadIdx.x;
+    float* rb = rhs + (size_t)b * YX * Z;
+    for (int e = t; e < Z * Z; e += 256) Q[e] = Qz[e];
+    for (int e = t; e < EXC * Z; e += 256) {
+        const int m = e / EXC, c = e - m * EXC;
+        col[c * (Z + 1) + m] = ch[((size_t)b * Z + m) * SP2 + s0 + c];
+    }
+    __syncthreads();
+    for (int e = t; e < EXC * Z; e += 256) {
+        const int c = e / Z, k = e - c * Z, si = sidx2[s0 + c];
+        if ((unsigned)si >= (unsigned)YX) continue;             // padding
+        float a = 0.f;
+        for (int m = 0; m < Z; ++m) a += col[c * (Z + 1) + m] * Q[m * Z + k];
+        rb[(size_t)si * Z + k] -= a;
+    }
+}
+
 // ---- sine transforms with LDS-resident planes / column slabs (X, Z <= 64, Y <= 128) -----------------------------------
 // k3_tzx: one workgroup = one (x, z) plane of one simulation: out = Qx (F Qz), both products from LDS (the two transforms
 // of a plane cost ONE read and ONE write of the plane instead of two each).  Q symmetric, so the same kernel serves the
@@ -719,11 +814,23 @@ int pressure_solve3d(hipStream_t s, const sol_karman3d_cfg* c, const int32_t* hd
     const int B = c->B, Y = c->Y, X = c->X, Z = c->Z, N = Y * X * Z;
     const int nS = hdr[4], SP = hdr[5];
     const float* KpT = c->direct + FD3_HEADER + (size_t)Y * Y + (size_t)X * X + (size_t)Z * Z + (size_t)N;
-    const int* sidx = reinterpret_cast<const int*>(KpT + (size_t)SP * SP);
     float* res = nullptr;
     if (int e = k3_apply_G(s, c, R, T1, T2, &res, nullptr)) return e;
     *res_out = res;
-    if (nS > 0) {
+    if (hdr[0] == FD3E_MAGIC) {                     // the obstacle extruded along z: nS = |S2| > 0, SP = SP2 (check_blob3d)
+        const float* Qz = c->direct + FD3_HEADER + (size_t)Y * Y + (size_t)X * X;
+        const int* sidx2 = reinterpret_cast<const int*>(KpT + (size_t)Z * SP * SP);
+        static std::atomic<unsigned long long> optin{0};
+        if (int e = sol_lds_optin(optin, {SOL_K(k3e_gather_tz), SOL_K(k3e_tz_apply)}, "k3e_gather_tz")) return e;
+        // scratch, B * Z * SP2 <= B * N floats each: x^ in the buffer G did not return its result in, c^ over G b itself, which is
+        // dead once its support columns are gathered (the second application of G starts from R and rewrites both buffers)
+        float* xh = res == T1 ? T2 : T1;
+        SOL_LAUNCH(k3e_gather_tz, dim3(SP / EXC, B), dim3(256), k3e_lds_bytes(Z), s, (const float*)res, Qz, sidx2, xh, Z, SP, Y * X);
+        SOL_LAUNCH(k3e_modes, dim3(SP / 32, Z), dim3(256), 0, s, (const float*)xh, KpT, res, B, Z, SP);
+        SOL_LAUNCH(k3e_tz_apply, dim3(SP / EXC, B), dim3(256), k3e_lds_bytes(Z), s, (const float*)res, Qz, sidx2, R, Z, SP, Y * X);
+        if (int e = k3_apply_G(s, c, R, T1, T2, &res, nullptr)) return e;
+    } else if (nS > 0) {
+        const int* sidx = reinterpret_cast<const int*>(KpT + (size_t)SP * SP);
         SOL_REQUIRE(SP / CAPQ <= 1024 && SP % 64 == 0, "direct-solver blob: SP = %d does not fit the capacitance kernel", SP);
         float* cpart = res == T1 ? T2 : T1;         // scratch: the buffer G does not return its result in (B * CAPQ * SP <= B * N floats)
         SOL_LAUNCH(k3_capacitance, dim3(SP / 32, CAPQ, B), dim3(256), 0, s, res, KpT, sidx, cpart, SP, N);
@@ -737,11 +844,18 @@ int pressure_solve3d(hipStream_t s, const sol_karman3d_cfg* c, const int32_t* hd
 // validates the blob header against the configuration (shared by the forward and the adjoint entry points)
 int check_blob3d(const sol_karman3d_cfg* c, const int32_t* hdr) {
     SOL_REQUIRE(c->direct && c->direct_n > 0, "the karman-3d step needs the direct-solver blob (cfg.direct, precond3d.direct_solver_blob3d)");
-    SOL_REQUIRE(hdr && hdr[0] == FD3_MAGIC, "direct_header_host must be the first 16 words of the blob (host copy)");
+    SOL_REQUIRE(hdr && (hdr[0] == FD3_MAGIC || hdr[0] == FD3E_MAGIC), "direct_header_host must be the first 16 words of the blob (host copy)");
     const int Y = c->Y, X = c->X, Z = c->Z;
     const size_t N = (size_t)Y * X * Z;
     const int nS = hdr[4], SP = hdr[5];
     SOL_REQUIRE(hdr[1] == Y && hdr[2] == X && hdr[3] == Z, "direct-solver blob is for a %dx%dx%d grid, cfg is %dx%dx%d", hdr[1], hdr[2], hdr[3], Y, X, Z);
+    if (hdr[0] == FD3E_MAGIC) {                     // the obstacle extruded along z: nS = |S2|, SP = SP2, Z matrices of SP2 x SP2
+        SOL_REQUIRE(nS >= 1 && SP >= nS && SP % 32 == 0 && SP <= FD3E_MAX_SP2 && (size_t)SP <= (size_t)Y * X && Z <= FD3E_MAX_Z &&
+                    (size_t)Z * SP * SP <= ((size_t)1 << 26), "extruded direct-solver blob header is inconsistent (nS2 %d, SP2 %d, Z %d)", nS, SP, Z);
+        const size_t want = (size_t)FD3_HEADER + (size_t)Y * Y + (size_t)X * X + (size_t)Z * Z + N + (size_t)Z * SP * SP + SP;
+        SOL_REQUIRE((size_t)c->direct_n == want, "extruded direct-solver blob has %d words, expected %zu", c->direct_n, want);
+        return k3_pcg_check(c, hdr);
+    }
     SOL_REQUIRE(nS >= 0 && SP >= nS && SP % 64 == 0 && SP <= 8192 && (size_t)8 * SP <= N, "direct-solver blob header is inconsistent (nS %d, SP %d)", nS, SP);
     const size_t want = (size_t)FD3_HEADER + (size_t)Y * Y + (size_t)X * X + (size_t)Z * Z + N + (size_t)SP * SP + SP;
     SOL_REQUIRE((size_t)c->direct_n == want, "direct-solver blob has %d words, expected %zu", c->direct_n, want);

@@ -47,6 +47,27 @@ def scene_arrays3d(Y, X, Z, length=100.0, obstacle="sphere"):
     return 1.0 - obst, inflow
 
 
+def extrude_mask(mask2d, Z):
+    """[Y,X] -> [Y,X,Z] float64: the 2-D mask repeated along z (mask[:, :, k] = mask2d for every k): the scenes the extruded direct solve
+    (Scene3D(pressure_solver="direct_extruded")) takes"""
+    m = np.asarray(mask2d, dtype=np.float64)
+    if m.ndim != 2 or isinstance(Z, bool) or not isinstance(Z, (int, np.integer)) or Z < 1:
+        raise ValueError("extrude_mask: mask2d must be [Y,X] and Z a positive integer (got shape %s, Z %r)" % (m.shape, Z))
+    return np.ascontiguousarray(np.broadcast_to(m[:, :, None], m.shape + (int(Z),)))
+
+
+def cylinder_arrays3d(Y, X, Z, length=100.0):
+    """(active, inflow) [Y,X,Z] float64 of the wake scene: scene_arrays3d's inflow box and, in place of the sphere, the disc
+    Sphere([50, 50], 10) of the 2-D scene extruded along z (cell centres inside count, dist^2 <= r^2).  Any grid: dx = length / X, the
+    domain is box[0:Y dx, 0:X dx, 0:Z dx] and the inflow box and the obstacle keep their physical definitions (coordinates of a domain
+    of length 100: `length` sets dx alone), so a coarse or short grid may hold no inflow cell."""
+    dx = length / X
+    yc, xc, zc = ((np.arange(n) + 0.5) * dx for n in (Y, X, Z))
+    inflow = ((yc >= 5.0) & (yc <= 10.0))[:, None, None] & ((xc >= 25.0) & (xc <= 75.0))[None, :, None] & ((zc >= 25.0) & (zc <= 75.0))[None, None, :]
+    disc = ((yc[:, None] - 50.0) ** 2 + (xc[None, :] - 50.0) ** 2) <= 10.0 ** 2
+    return extrude_mask(1.0 - disc, Z), inflow.astype(np.float64)
+
+
 def velocity_bc_masks3d(Y, X, Z):
     """velBCy / velBCyMask of karman_train.py:366-373 with the third axis: the two inflow-side planes and the four lateral
     walls of the flow component, [Y+1,X,Z], values 1."""
@@ -201,7 +222,7 @@ def diffuse_sub(sim, vy, vx, vz, re, nsub, chunk=None):
     return tuple(out)
 
 
-PRESSURE_SOLVERS3D = ("auto", "direct", "cg")
+PRESSURE_SOLVERS3D = ("auto", "direct", "cg", "direct_extruded")
 CG_MAX_ITER3D = 120             # launch budget of the CG solve: 28-87 iterations measured at rtol 1e-6
 
 
@@ -211,10 +232,14 @@ class Scene3D:
     active [Y,X,Z] (1 = fluid, 0 = solid; default: scene_arrays3d's sphere) and inflow [Y,X,Z] (default: its inflow box).
     pressure_solver: "direct" = the capacitance-corrected direct solve (ValueError where precond3d.direct_solver_blob3d refuses
     the mask), "cg" = the preconditioned CG solve (any mask; the blob without capacitance part), "auto" = direct where the blob
-    builds, else CG.  The choice is `self.pressure_solver` ("direct" or "cg")."""
+    builds, else CG.  "direct_extruded" (opt-in; "auto" never picks it) = the direct solve for an obstacle extruded along z, active[j, i, k]
+    = a2[j, i] for every k -- the cylinder of the wake, which the dense blob refuses at 128 x 64 x 64: Z capacitance systems on the in-plane
+    set between two sine transforms of the support columns (precond3d.extruded_solver_blob3d; ValueError with its reason where it refuses:
+    a mask that depends on z, no obstacle, size, conditioning).  The choice is `self.pressure_solver` ("direct", "cg" or
+    "direct_extruded"); everything that takes a scene treats "direct_extruded" as it treats "direct": no iteration, no report, capturable."""
 
     def __init__(self, Y, X, Z, length=100.0, device="cuda", velBCy=None, velBCyMask=None, active=None, inflow=None, pressure_solver="auto"):
-        from .precond3d import direct_solver_blob3d
+        from .precond3d import direct_solver_blob3d, extruded_solver_blob3d
         if pressure_solver not in PRESSURE_SOLVERS3D:
             raise ValueError("pressure_solver must be one of %s, got %r" % (PRESSURE_SOLVERS3D, pressure_solver))
         self.Y, self.X, self.Z = Y, X, Z
@@ -241,10 +266,16 @@ class Scene3D:
         self.inflow = _lib.f32(inflow, device)
         self.velBCy = _lib.f32(bcv, device)
         self.velBCyMask = _lib.f32(bcm, device)
-        blob = direct_solver_blob3d(active) if pressure_solver != "cg" else None
+        if pressure_solver == "direct_extruded":
+            why = []
+            blob = extruded_solver_blob3d(active, why)
+            if blob is None:
+                raise ValueError("pressure_solver='direct_extruded' does not support this scene (%dx%dx%d): %s" % (Y, X, Z, why[0]))
+        else:
+            blob = direct_solver_blob3d(active) if pressure_solver != "cg" else None
         if blob is None and pressure_solver == "direct":
             raise ValueError("the direct pressure solver does not support this scene (%dx%dx%d)" % (Y, X, Z))
-        self.pressure_solver = "direct" if blob is not None else "cg"
+        self.pressure_solver = "direct_extruded" if pressure_solver == "direct_extruded" else ("direct" if blob is not None else "cg")
         if blob is None:
             blob = direct_solver_blob3d(np.ones_like(active))        # the CG preconditioner: the empty-box solve (nS = 0)
         self.direct = torch.from_numpy(blob).to(device)

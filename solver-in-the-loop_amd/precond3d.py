@@ -110,6 +110,145 @@ def direct_solver_blob3d(active):
     return np.concatenate(parts)
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# obstacles extruded along z (the cylinder of the wake): active[j, i, k] = a2[j, i] for every k.  The pressure matrix then
+# separates along z,
+#
+#     M = M2' (x) I_Z + diag(a2) (x) T_Z
+#
+# (M2': the in-plane matrix, diagonal = in-plane accessible neighbours, at least 1 on a solid cell; T_Z: the Dirichlet
+# tridiagonal (2, -1): every fluid cell has two accessible z neighbours, every solid cell is decoupled), and Q_Z diagonalises
+# T_Z with mu_m = 2 - 2 cos(pi (m + 1) / (Z + 1)).  In the z-spectral basis mode m sees M_m = M2' + mu_m diag(a2) against the
+# empty box's T_Y (+) T_X + mu_m, i.e. the perturbation
+#
+#     E_m = E2 - mu_m diag(1 - a2),    E2 = M2' - (T_Y (+) T_X)
+#
+# on the 2-D set S2 of obstacle cells and their in-plane neighbours, and the identity at the head of this file holds mode by
+# mode: K'_m = E_m,SS (I + G_m,SS E_m,SS)^-1 with G_m = (T_Y (+) T_X + mu_m)^-1.  The dense |S| x |S| product (|S| = |S2| Z)
+# becomes Z products of size |S2| between two sine transforms along z of the support columns.
+# ---------------------------------------------------------------------------------------------------------------------
+FD3E_MAGIC = 0x46443345         # "FD3E"
+FD3E_MAX_Z = 128                # the correction kernels hold Q_Z (Z x Z floats) in LDS
+FD3E_MAX_SP2 = 1024             # largest padded in-plane set
+FD3E_MAX_WORDS = 1 << 26        # Z * SP2^2, the words of the per-mode matrices (256 MB)
+FD3E_MAX_COND = 1e6             # the dense blob's rule, per mode
+
+
+def _perturbation2d(a2):
+    """(S2, E2_SS, solid_S): the in-plane set (flat j*X + i, sorted), E2 = M2' - (T_Y (+) T_X) on it, and 1 - a2 on it"""
+    Y, X = a2.shape
+    acc = np.pad(a2, 1, mode="edge")
+    n2 = acc[:-2, 1:-1] + acc[2:, 1:-1] + acc[1:-1, :-2] + acc[1:-1, 2:]
+    d2 = np.where(a2 != 0, n2, np.maximum(n2, 1.0))
+    idx = np.arange(Y * X).reshape(Y, X)
+    sel = (d2 != 4.0) | (a2 == 0)
+    rows, cols, vals = [idx[sel]], [idx[sel]], [d2[sel] - 4.0]
+    for ax in range(2):
+        lo = [slice(None)] * 2
+        hi = [slice(None)] * 2
+        lo[ax] = slice(0, -1)
+        hi[ax] = slice(1, None)
+        a = a2[tuple(lo)] * a2[tuple(hi)]
+        sel = a != 1.0
+        r, c = idx[tuple(lo)][sel], idx[tuple(hi)][sel]
+        rows += [r, c]; cols += [c, r]; vals += [1.0 - a[sel], 1.0 - a[sel]]
+    rows, cols, vals = np.concatenate(rows), np.concatenate(cols), np.concatenate(vals)
+    S2 = np.unique(rows)
+    pos = np.full(Y * X, -1, dtype=np.int64)
+    pos[S2] = np.arange(len(S2))
+    E2 = np.zeros((len(S2), len(S2)))
+    np.add.at(E2, (pos[rows], pos[cols]), vals)
+    return S2, E2, 1.0 - a2.ravel()[S2]
+
+
+def extruded_solver_refusal3d(active):
+    """Why extruded_solver_blob3d refuses `active` (a sentence), or None where it builds.  Cheap: no matrix is formed, so the
+    conditioning rule is not evaluated here."""
+    act = (np.asarray(active, dtype=np.float64) != 0).astype(np.float64)
+    Y, X, Z = act.shape
+    if not np.all(act == act[:, :, :1]):
+        return "the mask depends on z (the extruded solve takes masks with active[j, i, k] = a2[j, i] for every k)"
+    if np.all(act != 0):
+        return "the scene has no obstacle (no solid cell: that scene is the plain direct solve's, nS = 0)"
+    if Z > FD3E_MAX_Z:
+        return "Z = %d is beyond the %d the correction kernels take" % (Z, FD3E_MAX_Z)
+    nS2 = len(_perturbation2d(act[:, :, 0])[0])
+    SP2 = (nS2 + 31) // 32 * 32
+    if SP2 > FD3E_MAX_SP2 or SP2 > Y * X or Z * SP2 * SP2 > FD3E_MAX_WORDS:
+        return ("the obstacle is beyond the size cap (in-plane set %d, padded %d: at most %d, at most Y X = %d, and Z SP2^2 <= 2^26 words)"
+                % (nS2, SP2, FD3E_MAX_SP2, Y * X))
+    return None
+
+
+def extruded_solver_blob3d(active, why=None):
+    """float32 blob of the direct solve for an obstacle extruded along z, or None where the scene does not qualify: the mask
+    depends on z; there is no solid cell (the plain direct solve's scene, nS = 0); a mode's capacitance system has a condition
+    number beyond 1e6; Z > 128; or the size is beyond the cap: SP2 <= 1024, SP2 <= Y X (the device's scratch) and
+    Z SP2^2 <= 2^26 words (256 MB).  `why`: a list that receives the reason of a refusal.
+
+    layout (32-bit words): header[16] = {magic "FD3E", Y, X, Z, nS2, SP2, ...};  Qy[Y*Y];  Qx[X*X];  Qz[Z*Z];  invlam[Y*X*Z]
+    (the positions of the dense blob: the empty-box solve and the CG preconditioner read either);  KpT[Z][SP2][SP2] (K'_m of
+    z mode m, stored transposed, zero padded; SP2 = nS2 rounded up to 32);  sidx2[SP2] int32 (in-plane cell index j*X + i,
+    -1 = padding).  G_m,SS is built from the nS2 rows of Qy (x) Qx, never as a (Y X)^2 matrix."""
+    say = why.append if why is not None else (lambda s: None)
+    reason = extruded_solver_refusal3d(active)
+    if reason is not None:
+        say(reason)
+        return None
+    act = (np.asarray(active, dtype=np.float64) != 0).astype(np.float64)
+    Y, X, Z = act.shape
+    S2, E2, solid = _perturbation2d(act[:, :, 0])
+    nS2 = len(S2)
+    SP2 = (nS2 + 31) // 32 * 32
+    Qy, Qx, Qz = dst_matrix(Y), dst_matrix(X), dst_matrix(Z)
+    lam = rect_eigenvalues(Y, X, Z)
+    R = (Qy[S2 // X, :, None] * Qx[S2 % X, None, :]).reshape(nS2, Y * X)          # rows S2 of Qy (x) Qx
+    KpT = np.zeros((Z, SP2, SP2))
+    eye = np.eye(nS2)
+    for m in range(Z):
+        mu = 2.0 - 2.0 * np.cos(np.pi * (m + 1) / (Z + 1))
+        Em = E2 - mu * np.diag(solid)
+        GSS = (R / lam[:, :, m].reshape(1, Y * X)) @ R.T
+        cap = eye + GSS @ Em
+        cond = np.linalg.cond(cap)
+        if not cond <= FD3E_MAX_COND:
+            say("the capacitance system of z mode %d is ill conditioned (condition number %.3g, at most %.0e)" % (m, cond, FD3E_MAX_COND))
+            return None
+        KpT[m, :nS2, :nS2] = (Em @ np.linalg.inv(cap)).T
+    sidx2 = np.full(SP2, -1, dtype=np.int32)
+    sidx2[:nS2] = S2.astype(np.int32)
+    header = np.zeros(FD3_HEADER, dtype=np.int32)
+    header[:6] = [FD3E_MAGIC, Y, X, Z, nS2, SP2]
+    parts = [header.view(np.float32), Qy.astype(np.float32).ravel(), Qx.astype(np.float32).ravel(), Qz.astype(np.float32).ravel(),
+             (1.0 / lam).astype(np.float32).ravel(), KpT.astype(np.float32).ravel(), sidx2.view(np.float32)]
+    return np.concatenate(parts)
+
+
+def extruded_solve_reference3d(blob, b):
+    """float64 numpy restatement of the device algorithm on the extruded blob: b [Y,X,Z] -> x with M x = b (CPU tests)."""
+    hdr = blob[:FD3_HEADER].view(np.int32)
+    assert hdr[0] == FD3E_MAGIC
+    Y, X, Z, nS2, SP2 = (int(v) for v in hdr[1:6])
+    o = FD3_HEADER
+    Qy = blob[o:o + Y * Y].astype(np.float64).reshape(Y, Y); o += Y * Y
+    Qx = blob[o:o + X * X].astype(np.float64).reshape(X, X); o += X * X
+    Qz = blob[o:o + Z * Z].astype(np.float64).reshape(Z, Z); o += Z * Z
+    il = blob[o:o + Y * X * Z].astype(np.float64).reshape(Y, X, Z); o += Y * X * Z
+    KpT = blob[o:o + Z * SP2 * SP2].astype(np.float64).reshape(Z, SP2, SP2); o += Z * SP2 * SP2
+    sidx2 = blob[o:o + SP2].view(np.int32)
+    q3 = lambda t: np.einsum("am,bc,ke,mce->abk", Qy, Qx, Qz, t, optimize=True)
+    G = lambda t: q3(q3(t) * il)
+    g = G(b).reshape(Y * X, Z)
+    ok = sidx2 >= 0
+    xs = np.where(ok[:, None], g[np.maximum(sidx2, 0)], 0.0)           # support columns [SP2][Z]
+    xh = xs @ Qz                                                        # 1. along z into the spectral basis
+    ch = np.einsum("mqs,qm->sm", KpT, xh)                               # 2. mode by mode: c^[:, m] = K'_m x^[:, m]
+    c = ch @ Qz                                                         # 3. back
+    r = np.array(b, dtype=np.float64).reshape(Y * X, Z)
+    r[sidx2[ok]] -= c[ok]                                               # 4.
+    return G(r.reshape(Y, X, Z))
+
+
 def direct_solve_reference3d(blob, b):
     """float64 numpy restatement of the device algorithm on the blob: b [Y,X,Z] -> x with M x = b (CPU tests)."""
     hdr = blob[:FD3_HEADER].view(np.int32)

@@ -13,7 +13,10 @@ dt res^2 / Re <= 1/6; auto: karman3d.min_diffusion_substeps3d of --re), for gene
 in params.pickle and in the model file as "diffusion_substeps" and picked up from there like the force.
 --advection semi_lagrangian|mac_cormack, --mc-strength S: the advection scheme of the solver step (mac_cormack keeps what the
 semi-Lagrangian step smears; S in [0, 1] is its correction strength), for generation, --model roll-out and --train-sol alike; recorded in
-params.pickle and in the model file as "advection" and "correction_strength" and picked up from there like the force."""
+params.pickle and in the model file as "advection" and "correction_strength" and picked up from there like the force.
+--obstacle sphere|cylinder: the sphere of the scene, or the disc of the 2-D scene extruded along z (karman3d.cylinder_arrays3d: the wake);
+recorded in params.pickle and in the model file as "obstacle" and picked up from there like the force.  --pressure-solver direct_extruded
+solves the cylinder's pressure without iteration (any mask that does not depend on z)."""
 import argparse
 import pickle
 
@@ -24,6 +27,9 @@ from _common import (add_advection_arg, add_buoyancy_arg, add_substeps_arg, adve
                      buoyancy_from_args, logger, select_gpu, substeps_from_args)
 import sol_amd
 from sol_amd import karman3d as k3, scene, synthetic
+from sol_amd.precond3d import extruded_solver_refusal3d
+
+OBSTACLES = ("sphere", "cylinder")
 
 
 def staggered3d(vy, vx, vz):
@@ -52,12 +58,17 @@ def parse_params(argv=None):
     p.add_argument("--lr", default=1e-5, type=float)
     p.add_argument("--seed", default=0, type=int)
     p.add_argument("--obstacle-mask", default=None, help="[Y,X,Z] .npy mask of the scene (1 = fluid, 0 = solid) instead of the sphere")
+    p.add_argument("--obstacle", default=None, choices=OBSTACLES, help="the scene's obstacle: sphere, or cylinder (the disc extruded along z); "
+                   "default: sphere, or what the --model file recorded")
     p.add_argument("--pressure-solver", default="auto", choices=k3.PRESSURE_SOLVERS3D,
-                   help="direct (capacitance blob), cg (preconditioned CG, any mask) or auto (direct where it builds)")
+                   help="direct (capacitance blob), cg (preconditioned CG, any mask), auto (direct where it builds, else cg) or direct_extruded "
+                        "(opt-in: the direct solve for a mask that does not depend on z, such as --obstacle cylinder)")
     add_buoyancy_arg(p, ncomp=3)
     add_substeps_arg(p, bound="1/6")
     add_advection_arg(p, where="")
     params = vars(p.parse_args(argv))
+    if params["obstacle"] is not None and params["obstacle_mask"]:
+        p.error("--obstacle and --obstacle-mask both name the scene's obstacle: give one")
     params["advection"], params["mc_strength"] = advection_from_args(params)
     params["buoyancy"] = buoyancy_from_args(params, ncomp=3)
     params["diffusion_substeps"] = substeps_from_args(params, [params["re"]], params["res"], minimum=k3.min_diffusion_substeps3d)
@@ -68,8 +79,14 @@ def apply_model_record(params, record=None):
     """The run's parameters as recorded in params.pickle: parse_params' with the force and the substep count the run uses.  record: the
     dict of the --model file (None: no model) -- the force and the count the corrector was trained with win, a flag that contradicts them
     is an error, and a model without a record takes the flag.  No flag and no record: no force, one substep.  The advection likewise:
-    "advection" and "correction_strength" are the scheme the run uses (the model's record, else the flags, else semi_lagrangian / 1)."""
+    "advection" and "correction_strength" are the scheme the run uses (the model's record, else the flags, else semi_lagrangian / 1).
+    "obstacle" likewise: the model's record, else the flag, else the sphere (a model without a record was trained on it)."""
     params = dict(params)
+    if record is not None and "obstacle" in record and not params.get("obstacle_mask"):
+        if params.get("obstacle") is not None and params["obstacle"] != record["obstacle"]:
+            raise SystemExit("--obstacle %s contradicts the obstacle recorded in %s (%s)" % (params["obstacle"], params["model"], record["obstacle"]))
+        params["obstacle"] = record["obstacle"]
+    params["obstacle"] = params.get("obstacle") or "sphere"
     if record is not None and "buoyancy" in record:
         params["buoyancy"] = agreed_buoyancy(record["buoyancy"], params["buoyancy"], params["model"])
     if record is not None and "diffusion_substeps" in record:
@@ -93,6 +110,8 @@ def main(argv=None):
     Y, X, Z = 2 * res, res, res
     dev = "cuda"
     active = np.load(params["obstacle_mask"]) if params["obstacle_mask"] else None
+    if active is None and params["obstacle"] == "cylinder":
+        active = k3.cylinder_arrays3d(Y, X, Z, length=float(params["len"]))[0]
     sc = k3.Scene3D(Y, X, Z, length=float(params["len"]), device=dev, active=active, pressure_solver=params["pressure_solver"])
     buoyancy, nsub = params["buoyancy"], params["diffusion_substeps"]
     adv = {"advection": params["advection"], "correction_strength": params["correction_strength"]}
@@ -112,7 +131,11 @@ def main(argv=None):
         with open(path + "/params.pickle", "wb") as fh:
             pickle.dump(params, fh)
     log.info(params)
-    log.info("pressure solver: %s" % sc.pressure_solver)
+    hint = ""
+    if params["pressure_solver"] == "auto" and sc.pressure_solver == "cg" and extruded_solver_refusal3d(sc.active_np) is None:
+        hint = " (the mask does not depend on z: --pressure-solver direct_extruded solves it without iteration)"
+    log.info("pressure solver: %s%s" % (sc.pressure_solver, hint))
+    log.info("obstacle: %s" % (params["obstacle_mask"] or params["obstacle"]))
     log.info("buoyancy: %s" % (buoyancy,))
     log.info("diffusion substeps: %d" % nsub)
     log.info("advection: %s (correction strength %g)" % (adv["advection"], adv["correction_strength"]))
@@ -151,7 +174,7 @@ def main(argv=None):
             log.info("train step {:04d}: loss={}".format(it + 1, loss))
         if path:
             torch.save({"name": net.name, "weights": [torch.as_tensor(a) for a in net.get_weights()], "std_v": std_v,
-                        "std_re": max(params["re"], 1.0), "buoyancy": buoyancy, "diffusion_substeps": nsub, **adv}, path + "/model3d.pt")
+                        "std_re": max(params["re"], 1.0), "buoyancy": buoyancy, "diffusion_substeps": nsub, "obstacle": params["obstacle"], **adv}, path + "/model3d.pt")
     return path if path else loss
 
 
