@@ -84,6 +84,9 @@ int sol_abi_sizes(int32_t* karman_cfg, int32_t* burgers_cfg, int32_t* train_cfg)
  *   k2d_mc_tile (1)     karman-2d large grids: the MacCormack advection ("MACCORMACK ADVECTION" below) as one launch on 16 x 32 tiles with the
  *                       semi-Lagrangian values of a halo of 2 in LDS (a corner beyond the halo is evaluated on the fly); 0: two launches through
  *                       the workspace.  Same results bit for bit
+ *   k2d_solve_one_wg (1) karman-2d, scenes built with multi_launch on a grid of at most 8192 cells with X <= 64: the one-window direct pressure solve as
+ *                       ONE launch, one workgroup per simulation (sol_karman_solve_one_wg_supported); 0: the chain of GEMM launches.  The same fp32
+ *                       sums in another order; measured faster at 64 x 32 and at 128 x 64 (profiles/k2d_multi_launch_small_time.json)
  *   k3d_dens_adj_tile (1) karman-3d: the density adjoint's fixed-point scatter (sol_karman3d_density_bwd) goes through an int64 LDS window per
  *                       workgroup (4 x 4 columns + halo 2, all k), flushed with one global atomic per non-zero cell; 0, or a window beyond
  *                       64 KB (Z > 128): every contribution is a global atomic.  Same results bit for bit
@@ -143,6 +146,11 @@ int sol_karman_precond_supported(int32_t Y, int32_t X);
 /* 1 if the direct pressure solver is built for a Y x X grid (128 x 64, and grids of at most 2048 cells with
  * Y % 16 == 0, X in {16, 32, 64}, e.g. the reference's 64 x 32 training recipe), else 0 */
 int sol_karman_direct_supported(int32_t Y, int32_t X);
+/* 1 if the one-launch form of the multi-launch path's direct pressure solve (one workgroup per simulation, option k2d_solve_one_wg) serves
+ * a Y x X grid with a one-window blob of window `win`: Y, X >= 16, at most 8192 cells, X <= 64, win in {16, 32, 64} within the grid.  It
+ * runs inside every entry point that takes `direct_header_host` when word 8 of that HOST header copy has bit 0 set (the scene was built
+ * with multi_launch: ops.SceneMasks) and the option is 1; otherwise the entry points issue the launches they always did. */
+int sol_karman_solve_one_wg_supported(int32_t Y, int32_t X, int32_t win);
 
 /* Forward step for grids beyond the one-workgroup kernels (the reference generates its data at 256 x 128:
  * karman-2d/karman.py:98-159, Makefile:19-28 `-r 128`).  Same arithmetic and argument meaning as sol_karman_step_fwd,

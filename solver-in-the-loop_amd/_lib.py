@@ -64,6 +64,7 @@ _SIGS = {
     "sol_prof_begin": (C.c_int, []),
     "sol_prof_end": (C.c_int, [C.c_int32, C.c_char_p, C.POINTER(C.c_double), C.POINTER(C.c_int32)]),
     "sol_karman_direct_supported": (C.c_int, [C.c_int32] * 2),
+    "sol_karman_solve_one_wg_supported": (C.c_int, [C.c_int32] * 3),
     "sol_karman_step_large_workspace_bytes": (C.c_size_t, [_P]),
     "sol_karman_step_large_workspace_bytes_for": (C.c_size_t, [_P, _P]),
     "sol_karman_step_bwd_large_workspace_bytes_for": (C.c_size_t, [_P, _P]),

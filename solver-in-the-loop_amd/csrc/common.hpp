@@ -84,6 +84,10 @@ int sol_large_box_back(hipStream_t s, int B, int Y, int X, const float* blob, co
 size_t sol_large_direct_bytes(const sol_karman_cfg* c, const int32_t* hdr);       // the direct solve's buffers, sized from the blob's host header (NULL: the one-window form)
 int sol_large_direct_check(const sol_karman_cfg* c, const char* who, const int32_t* hdr);
 int sol_large_direct_solve(hipStream_t s, const sol_karman_cfg* c, const int32_t* hdr, float* base);
+// karman_solve_small.hip: the same solve for a one-window blob as one launch, one workgroup per simulation; p overwrites rhs at `base`
+bool sol_solve_one_wg_supported(int Y, int X, int win);
+int sol_solve_one_wg(hipStream_t s, const sol_karman_cfg* c, const int32_t* hdr, float* base);
+constexpr int SOL_DIRECT_HDR_FLAGS = 8, SOL_DIRECT_HDR_ONE_WG = 1;      // host header copy, word 8: bit 0 = the scene was built with multi_launch
 int sol_large_cg_check(const sol_karman_cfg* c, const char* who, const float* box_blob, const int32_t* hdr, const int32_t* cg_info, const void* workspace);
 size_t sol_large_solver_bytes(const sol_karman_cfg* c, bool direct, const int32_t* hdr = nullptr);
 float* sol_large_solver_rhs(const sol_karman_cfg* c, bool direct, void* ws);
@@ -310,6 +314,9 @@ struct SolOptions {
                           //    4 x 4 columns (k3d_advect_adj_tile); 0: global atomics only (k3d_advect_adj).  Same results bit for bit
     int k2d_mc_tile;      // 1 (default): the MacCormack advection of the large-grid karman-2d step (karman_maccormack.hip) as one launch on tiles with the
                           //    semi-Lagrangian values of a halo in LDS (k_mc_tile); 0: two launches through the workspace (k_mc_hat, k_mc_out).  Same results bit for bit
+    int k2d_solve_one_wg; // 1 (default, measured faster: 42 against 71 us at 64 x 32 B = 3, 83 against 118 us at 128 x 64 B = 6): the one-window direct pressure solve of a scene built with multi_launch (flag in the host header copy) on a grid of at most
+                          //    8192 cells, X <= 64, as ONE launch, one workgroup per simulation (karman_solve_small.hip); 0: the GEMM chain of
+                          //    sol_large_direct_solve (profiles/k2d_multi_launch_small_time.json).  Same sums in another order
 };
 SolOptions& sol_opt();
 

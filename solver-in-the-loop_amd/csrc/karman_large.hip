@@ -516,6 +516,9 @@ int sol_large_direct_solve(hipStream_t s, const sol_karman_cfg* c, const int32_t
     if (hdr[0] == FDS_MAGIC) return scattered_solve(s, c, hdr, base);
     const Header h{hdr[1], hdr[2], hdr[3], hdr[4], hdr[5], hdr[6], hdr[7]};
     const int B = c->B, Y = c->Y, X = c->X, N = Y * X, win = h.win, SP = h.SP;
+    // a scene built with multi_launch on a grid one workgroup holds: the whole solve as one launch (karman_solve_small.hip)
+    if ((hdr[SOL_DIRECT_HDR_FLAGS] & SOL_DIRECT_HDR_ONE_WG) && sol_opt().k2d_solve_one_wg && sol_solve_one_wg_supported(Y, X, win))
+        return sol_solve_one_wg(s, c, hdr, base);
     // blob sections
     const float* Qy = c->direct + FDL_HEADER;
     const float* Qx = Qy + (size_t)Y * Y;

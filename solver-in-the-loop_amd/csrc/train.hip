@@ -37,6 +37,7 @@ SolOptions& sol_opt() {
         d.correct_fuse = 1; d.bww_fuse = 1;
         d.density_mode = 0; d.cpt = 0; d.dbg_skip = 0; d.step_prof = 0; d.cnn_persistent = 0; d.k3d_tile = 0; d.k3d_fused_tf = 1; d.k3d_conv_fused = 1; d.k3d_conv_rows = 8; d.conv_dx = 11; d.k3d_mfma_tf = 1; d.conv_thin_valu = 1; d.seed_fuse = 1; d.fwd_bands = 1; d.conv_thin_t3 = 1; d.k3d_bww_jobs = 2; d.k3d_conv_persist = 0; d.k3d_adj_tile = 1; d.k2d_adj_tile = 1; d.k2d_dens_adj_tile = 1; d.k3d_dens_adj_tile = 1;
         d.k2d_mc_tile = 1;
+        d.k2d_solve_one_wg = 1;
         return d;
     }();
     return o;
@@ -54,6 +55,7 @@ const OptName OPT_NAMES[] = {
     {"conv_dx", &SolOptions::conv_dx, 0, 15}, {"conv_thin_valu", &SolOptions::conv_thin_valu, 0, 2}, {"k3d_mfma_tf", &SolOptions::k3d_mfma_tf, 0, 1},
     {"seed_fuse", &SolOptions::seed_fuse, 0, 1}, {"fwd_bands", &SolOptions::fwd_bands, 0, 1}, {"conv_thin_t3", &SolOptions::conv_thin_t3, 0, 1}, {"k3d_bww_jobs", &SolOptions::k3d_bww_jobs, 0, 2}, {"k3d_conv_persist", &SolOptions::k3d_conv_persist, 0, 1}, {"k3d_adj_tile", &SolOptions::k3d_adj_tile, 0, 1}, {"k2d_adj_tile", &SolOptions::k2d_adj_tile, 0, 1}, {"k2d_dens_adj_tile", &SolOptions::k2d_dens_adj_tile, 0, 1},
     {"k3d_dens_adj_tile", &SolOptions::k3d_dens_adj_tile, 0, 1}, {"k2d_mc_tile", &SolOptions::k2d_mc_tile, 0, 1},
+    {"k2d_solve_one_wg", &SolOptions::k2d_solve_one_wg, 0, 1},
 };
 }  // namespace
 

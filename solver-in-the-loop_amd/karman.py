@@ -113,7 +113,10 @@ class KarmanFlow:
     def __init__(self, pressure_solver=None, make_input_divfree=False, make_output_divfree=True,
                  cg_rtol=1e-6, cg_atol=1e-9, cg_max_iter=2000, grad_pad="replicate", inflow_order="after",
                  obstacles=None, active=None, density_grad=False, re_grad=False, buoyancy=None, buoyancy_factor=None,
-                 gravity=(-9.81, 0.0), diffusion_substeps=1, advection="semi_lagrangian", correction_strength=1.0):
+                 gravity=(-9.81, 0.0), diffusion_substeps=1, advection="semi_lagrangian", correction_strength=1.0, multi_launch=False):
+        # multi_launch=True (opt-in): the multi-launch path on every grid with Y, X >= 16 (ops.SceneMasks(multi_launch=True)), so that
+        # buoyancy, mac_cormack and "direct_scattered" serve the grids the one-workgroup kernels would take; the default picks as before
+        self._multi_launch = bool(multi_launch)
         # advection="mac_cormack" (PhiFlow's advect.mac_cormack(field, velocity, dt, correction_strength)): velocity and density are advected
         # by the MacCormack scheme with the revert-to-semi-Lagrangian limiter (include/sol_hip.h, "MACCORMACK ADVECTION"), which keeps what
         # the semi-Lagrangian step smears; large grids only (step() raises SolError on a grid the one-workgroup kernels serve); composes
@@ -207,7 +210,7 @@ class KarmanFlow:
         fast = (domain.resolution, domain.box.lower, domain.box.upper, str(device))
         if last is not None and last[0] is velBCy and last[1] is velBCyMask and last[2] == fast:
             return last[3]
-        key = (domain.resolution, domain.box.lower, domain.box.upper, self._digest(velBCy), self._digest(velBCyMask), str(device))
+        key = (domain.resolution, domain.box.lower, domain.box.upper, self._digest(velBCy), self._digest(velBCyMask), str(device), self._multi_launch)
         if key not in self._cache:
             if len(self._cache) >= 8:                       # bounded: every entry holds device buffers and a solver blob
                 self._cache.pop(next(iter(self._cache)))
@@ -217,7 +220,7 @@ class KarmanFlow:
             bcm = np.asarray(velBCyMask, dtype=np.float64).reshape(-1, Y + 1, X)
             if bcv.shape[0] > 1 and np.all(bcv == bcv[0:1]) and np.all(bcm == bcm[0:1]):
                 bcv, bcm = bcv[0:1], bcm[0:1]
-            self._cache[key] = ops.SceneMasks(active, inflow, bcv, bcm, device, pressure_solver=self._pressure_solver)
+            self._cache[key] = ops.SceneMasks(active, inflow, bcv, bcm, device, pressure_solver=self._pressure_solver, multi_launch=self._multi_launch)
         # (holding the two objects keeps their ids from being recycled while they serve as the fast-path key)
         self._last_masks = (velBCy, velBCyMask, fast, self._cache[key])
         return self._cache[key]

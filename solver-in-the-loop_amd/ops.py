@@ -43,6 +43,10 @@ def beyond_one_workgroup(Y, X):
     return Y * X > 8192 or X > 64
 
 
+# word of the direct blob's HOST header copy that carries flags for the launch code (the device blob keeps 0 there), and its bit
+# "built with multi_launch=True": sol_large_direct_solve may run the one-launch solve (csrc/karman_solve_small.hip, option k2d_solve_one_wg)
+DIRECT_HEADER_FLAGS, DIRECT_ONE_WG = 8, 1
+
 PRESSURE_SOLVERS = ("auto", "direct", "cg", "direct_scattered")
 
 
@@ -55,7 +59,9 @@ class SceneMasks:
     """Device-resident constant masks of a scene: active (1 - obstacle), inflow rate, velBCy,
     velBCyMask (reference: KarmanFlow.__init__ karman_train.py:166-171 and :366-373)."""
 
-    def __init__(self, active, inflow, velBCy, velBCyMask, device="cuda", precondition=True, pressure_solver="auto"):
+    def __init__(self, active, inflow, velBCy, velBCyMask, device="cuda", precondition=True, pressure_solver="auto", multi_launch=False):
+        """multi_launch=True (opt-in): the multi-launch path (karman_step_large and everything that keys on `large`) on a grid the
+        one-workgroup kernels would serve, any Y, X >= 16 -- what buoyancy, mac_cormack and "direct_scattered" are built on."""
         self.active = _lib.f32(active, device)
         self.inflow = _lib.f32(inflow, device)
         self.velBCy = _lib.f32(velBCy, device)
@@ -64,7 +70,10 @@ class SceneMasks:
         n = (Y + 1) * X
         assert self.velBCy.numel() % n == 0 and self.velBCy.numel() == self.velBCyMask.numel()
         self.bc_stride = 0 if self.velBCy.numel() == n else n
-        self.large = beyond_one_workgroup(Y, X)      # the multi-launch path (karman_step_large)
+        self.multi_launch = bool(multi_launch)
+        if self.multi_launch and (Y < 16 or X < 16):
+            raise ValueError("SceneMasks: multi_launch=True takes grids with Y, X >= 16 (the multi-launch kernels); this one is %dx%d" % (Y, X))
+        self.large = self.multi_launch or beyond_one_workgroup(Y, X)      # the multi-launch path (karman_step_large)
         # two-level CG preconditioner (host-prepared dense coarse inverse), when the grid allows it
         self.coarse_inv = None
         if precondition and not os.environ.get("SOL_NO_PRECOND") and not self.large and _lib.load().sol_karman_precond_supported(Y, X):
@@ -81,7 +90,8 @@ class SceneMasks:
             # opt-in: the capacitance solve on the support set's row and column lists (no window), large grids only
             if not self.large:
                 raise ValueError("pressure_solver='direct_scattered' serves the large-grid path only (grids beyond the one-workgroup "
-                                 "kernels, ops.beyond_one_workgroup); %dx%d is not large: use 'auto', 'direct' or 'cg'" % (Y, X))
+                                 "kernels, ops.beyond_one_workgroup); %dx%d is not large: use 'auto', 'direct' or 'cg'.  SceneMasks(multi_launch=True) "
+                                 "runs the large-grid path on such a grid" % (Y, X))
             from .precond import scattered_solver_blob
             blob = scattered_solver_blob(self.active.reshape(Y, X).cpu().numpy())
             if blob is None:
@@ -95,6 +105,10 @@ class SceneMasks:
             if blob is not None:
                 self.direct = torch.from_numpy(blob).to(device)
                 self.direct_header = np.ascontiguousarray(blob[:16].view(np.int32))      # host copy: sizes the large-grid launches
+                if self.multi_launch:
+                    # a copy of its own (ascontiguousarray hands back a view of the blob), then the flag: the one-launch solve may serve this scene
+                    self.direct_header = self.direct_header.copy()
+                    self.direct_header[DIRECT_HEADER_FLAGS] |= DIRECT_ONE_WG
         if want == "direct" and self.direct is None:
             raise ValueError("the direct pressure solver does not support this scene (%dx%d)" % (Y, X))
         # large grids without a direct blob ("cg", or a scene the blob refuses): the preconditioned CG solve of the large-grid step
@@ -358,10 +372,12 @@ class StepPhysics(NamedTuple):
             _require_sub_grid(cfg, who)
         if self.buoyancy is not None and not masks.large:
             raise SolError("%s: the buoyancy force is built on the multi-launch (large-grid) step only; a %dx%d grid runs the fused "
-                           "one-workgroup kernels (not ops.beyond_one_workgroup), which have no buoyancy term" % (who, cfg.Y, cfg.X))
+                           "one-workgroup kernels (not ops.beyond_one_workgroup), which have no buoyancy term.  Masks built with "
+                           "multi_launch=True run the multi-launch step on such a grid" % (who, cfg.Y, cfg.X))
         if self.adv is not None and not masks.large:
             raise SolError("%s: the mac_cormack advection is built on the multi-launch (large-grid) step only; a %dx%d grid runs the fused "
-                           "one-workgroup kernels (not ops.beyond_one_workgroup), which advect semi-Lagrangian" % (who, cfg.Y, cfg.X))
+                           "one-workgroup kernels (not ops.beyond_one_workgroup), which advect semi-Lagrangian.  Masks built with "
+                           "multi_launch=True run the multi-launch step on such a grid" % (who, cfg.Y, cfg.X))
 
     @property
     def mode(self):
@@ -598,6 +614,29 @@ def pressure_solve_large(rhs, cfg, masks, workspace=None, info=None):
                                               workspace.numel() * 4))
     _publish_cg(info, cg_info)
     return p
+
+
+def karman_pressure_solve_large(rhs, cfg, masks, workspace=None, info=None):
+    """pressure_solve_large for every solver of the multi-launch path: a scene with a direct blob, one-window or scattered, runs
+    sol_karman_pressure_solve_large_direct (on masks built with multi_launch=True and the option k2d_solve_one_wg the one-launch solve
+    of csrc/karman_solve_small.hip where it serves the grid), a CG scene sol_karman_pressure_solve_large."""
+    if masks.direct is None or masks.pressure_solver == "direct_scattered":
+        return pressure_solve_large(rhs, cfg, masks, workspace, info)
+    if cfg.Y < 16 or cfg.X < 16:
+        raise SolError("karman_pressure_solve_large: the multi-launch direct solve takes grids with Y, X >= 16; this one is %dx%d" % (cfg.Y, cfg.X))
+    _lib.require_gpu()
+    rhs = _lib.f32(rhs)
+    assert rhs.shape == (cfg.B, cfg.Y, cfg.X)
+    workspace = _workspace(large_workspace_bytes(cfg, masks), workspace, rhs.device)
+    p = torch.empty_like(rhs)
+    check(_lib.load().sol_karman_pressure_solve_large_direct(C.byref(cfg), stream(), ptr(rhs), ptr(p), _hdr(masks.direct_header),
+                                                             ptr(workspace), workspace.numel() * 4))
+    return p
+
+
+def solve_one_wg_supported(Y, X, win):
+    """True where the one-launch direct solve (sol_karman_solve_one_wg) serves a Y x X grid with a one-window blob of window `win`"""
+    return bool(_lib.load().sol_karman_solve_one_wg_supported(int(Y), int(X), int(win)))
 
 
 def _scale3(vals):

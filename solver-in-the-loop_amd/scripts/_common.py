@@ -115,6 +115,21 @@ def agreed_advection(recorded, flags, where):
     return {"advection": name, "correction_strength": s}
 
 
+def add_multi_launch_arg(p, generates=True):
+    """--multi-launch of the karman-2d scripts: the multi-launch solver path (KarmanFlow / SceneMasks / trainers with multi_launch=True)
+    on a grid the fused one-workgroup kernels would serve -- what --buoyancy, --advection mac_cormack and --diffusion-substeps need there.
+    Recorded with the data; the scripts that read data take it from there as well."""
+    p.add_argument("--multi-launch", action="store_true",
+                   help="run the multi-launch solver path on a grid the one-workgroup kernels would serve (Y, X >= 16): buoyancy, mac_cormack and "
+                        "diffusion substeps are built on it.  Stored with the data; %s" % ("absent: off" if generates else "also taken from what the data recorded"))
+
+
+def agreed_multi_launch(recorded, flag):
+    """The path of a run that reads data: multi-launch when the data recorded it or the flag asks for it (a choice of kernels, not of
+    physics: nothing to contradict)"""
+    return bool(recorded) or bool(flag)
+
+
 def add_substeps_arg(p, auto=True, bound="1/4"):
     """--diffusion-substeps N|auto of karman.py (auto: the smallest stable count for the run's Reynolds numbers); the scripts that read
     data take N only and default to what the data recorded.  bound: the single stencil's stability bound in the help text (karman3d.py: 1/6)"""

@@ -8,14 +8,16 @@ else the preconditioned CG.  --obstacle / --obstacle-mask choose the scene (reco
 roll-out pick it up from the data.  --diffusion-substeps N|auto: explicit diffusion substeps per step (auto: the smallest count for which
 dt res^2 / (n Re) <= 1/4, ops.min_diffusion_substeps); recorded in params.pickle as "diffusion_substeps" (an integer, 1: the single stencil).
 --advection semi_lagrangian|mac_cormack, --mc-strength S (mac_cormack: large grids only): the advection scheme of the step; recorded in
-params.pickle as "advection" and "correction_strength", picked up from there by training, roll-out and the Re fit."""
+params.pickle as "advection" and "correction_strength", picked up from there by training, roll-out and the Re fit.
+--multi-launch: the multi-launch path on a grid the one-workgroup kernels would serve (-r 16 ... 64, or a width such as -r 48), where
+--buoyancy, mac_cormack and the substeps then work; recorded in params.pickle as "multi_launch" and picked up like them."""
 import argparse
 import pickle
 
 import numpy as np
 import torch
 
-from _common import (add_advection_arg, add_buoyancy_arg, add_scene_args, add_substeps_arg, advection_from_args, buoyancy_from_args, flow_kwargs,
+from _common import (add_advection_arg, add_buoyancy_arg, add_multi_launch_arg, add_scene_args, add_substeps_arg, advection_from_args, buoyancy_from_args, flow_kwargs,
                      logger, scene_from_args, select_gpu, substeps_from_args)
 import sol_amd
 from sol_amd import ops, scene
@@ -40,6 +42,7 @@ def main(argv=None):
     add_buoyancy_arg(p)
     add_substeps_arg(p)
     add_advection_arg(p)
+    add_multi_launch_arg(p)
     params = vars(p.parse_args(argv))
     select_gpu(params["gpu"])
     log = logger()
@@ -53,7 +56,7 @@ def main(argv=None):
     params["advection"], params["correction_strength"] = name or "semi_lagrangian", 1.0 if strength is None else float(strength)
     sim = sol_amd.KarmanFlow(pressure_solver=params["pressure_solver"], buoyancy=params["buoyancy"],
                              diffusion_substeps=params["diffusion_substeps"], advection=params["advection"],
-                             correction_strength=params["correction_strength"], **flow_kwargs(rec))
+                             correction_strength=params["correction_strength"], multi_launch=params["multi_launch"], **flow_kwargs(rec))
     params["scene"] = sim.scene()
     d0 = scene.downsample(scene.read_zipped_array(params["initdH"]), params["scale"]) if params["initdH"] else np.zeros((1, Y, X, 1))
     if params["initvH"]:

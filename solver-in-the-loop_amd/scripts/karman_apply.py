@@ -9,7 +9,7 @@ import pickle
 import numpy as np
 import torch
 
-from _common import (add_advection_arg, advection_from_args, agreed_advection, add_buoyancy_arg, add_scene_args, add_substeps_arg, agreed_buoyancy, agreed_substeps, buoyancy_from_args, flow_kwargs, logger,
+from _common import (add_advection_arg, add_multi_launch_arg, advection_from_args, agreed_advection, agreed_multi_launch, add_buoyancy_arg, add_scene_args, add_substeps_arg, agreed_buoyancy, agreed_substeps, buoyancy_from_args, flow_kwargs, logger,
                      scene_from_args, select_gpu, substeps_from_args)
 import sol_amd
 from sol_amd import ops, scene
@@ -33,6 +33,7 @@ def main(argv=None):
     add_buoyancy_arg(p)
     add_substeps_arg(p, auto=False)
     add_advection_arg(p, generates=False)
+    add_multi_launch_arg(p, generates=False)
     params = vars(p.parse_args(argv))
     select_gpu(params["gpu"])
     log = logger()
@@ -77,12 +78,15 @@ def main(argv=None):
     advection = agreed_advection(data_stats, flags_adv, params["stats"]) if "advection" in data_stats \
         else agreed_advection({"advection": flags_adv[0], "correction_strength": flags_adv[1]}, (None, None), "the flags")
     log.info("advection: %s" % (advection,))
+    # and the multi-launch path (dataStats "multi_launch"; absent: off, or the flag)
+    multi_launch = agreed_multi_launch(data_stats.get("multi_launch"), params["multi_launch"])
+    log.info("multi-launch path: %s" % multi_launch)
     active, inflow = sim.scene_arrays(dom)
     velBCy, velBCyMask = sol_amd.velocity_bc_masks(Y, X)
     masks = ops.SceneMasks(active, inflow, velBCy.reshape(Y + 1, X), velBCyMask.reshape(Y + 1, X),
-                           pressure_solver=params["pressure_solver"])
+                           pressure_solver=params["pressure_solver"], multi_launch=multi_launch)
     log.info("pressure solver: %s" % masks.pressure_solver)
-    large = ops.beyond_one_workgroup(Y, X)
+    large = masks.large
     warm = bool(params["cg_warm_start"]) and large and masks.pressure_solver == "cg"
     if params["cg_warm_start"] and not warm:
         log.info("--cg-warm-start ignored: %s" % ("the direct pressure solve has no iteration to start" if large and ops.is_direct(masks.pressure_solver)
@@ -90,7 +94,7 @@ def main(argv=None):
     # (a CG scene runs eagerly, every solve stops at convergence; a direct-solve scene replays one captured step)
     ro = sol_amd.make_rollout(model, masks, 1, Y, X, dom.dx[1], data_stats["std"][1], data_stats["ext.std"][0],
                               use_graph=ops.is_direct(masks.pressure_solver), cg_warm_start=warm, any_width=params["any_width"],
-                              buoyancy=buoyancy, diffusion_substeps=nsub, **advection)
+                              buoyancy=buoyancy, diffusion_substeps=nsub, multi_launch=multi_launch, **advection)
     f = lambda a: torch.as_tensor(np.ascontiguousarray(a), dtype=torch.float32, device="cuda").contiguous()
     vy0, vx0 = scene.split_staggered(np.asarray(vn, dtype=np.float32))
     d, vy, vx = f(np.asarray(d0)[..., 0]), f(vy0), f(vx0)

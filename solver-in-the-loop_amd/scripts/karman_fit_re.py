@@ -64,7 +64,7 @@ def flow_stepper(sim, dom, B, Y, X, res):
 
 
 def main(argv=None):
-    from _common import add_advection_arg, advection_from_args, agreed_advection, add_scene_args, add_substeps_arg, agreed_substeps, flow_kwargs, logger, scene_from_args, select_gpu, substeps_from_args
+    from _common import add_advection_arg, add_multi_launch_arg, advection_from_args, agreed_advection, agreed_multi_launch, add_scene_args, add_substeps_arg, agreed_substeps, flow_kwargs, logger, scene_from_args, select_gpu, substeps_from_args
     import sol_amd
     from sol_amd import scene, synthetic
     p = argparse.ArgumentParser(description="Parameter Parser", formatter_class=argparse.ArgumentDefaultsHelpFormatter)
@@ -83,6 +83,7 @@ def main(argv=None):
     add_scene_args(p)
     add_substeps_arg(p, auto=False)
     add_advection_arg(p, generates=False)
+    add_multi_launch_arg(p, generates=False)
     params = vars(p.parse_args(argv))
     if (params["input"] is None) == (not params["synthetic"]):
         raise SystemExit("give --input DIR or --synthetic")
@@ -101,6 +102,7 @@ def main(argv=None):
         nsub = substeps_from_args(params) or 1
         fa = advection_from_args(params)
         advection = agreed_advection({"advection": fa[0], "correction_strength": fa[1]}, (None, None), "the flags")
+        multi_launch = agreed_multi_launch(False, params["multi_launch"])
     else:
         with open(os.path.join(params["input"], "params.pickle"), "rb") as fh:
             meta = pickle.load(fh)
@@ -108,6 +110,7 @@ def main(argv=None):
         rec = rec if rec is not None else meta.get("scene")
         nsub = agreed_substeps(meta.get("diffusion_substeps"), substeps_from_args(params), "params.pickle")      # the count the frames were generated with
         advection = agreed_advection(meta, advection_from_args(params), "params.pickle")      # the scheme the frames were generated with
+        multi_launch = agreed_multi_launch(meta.get("multi_launch"), params["multi_launch"])      # the path the frames were generated on
         names = sorted(n for n in os.listdir(params["input"]) if n.startswith("velo_") and n.endswith(".npz"))
         start = int(names[0][5:11]) if params["start"] is None else params["start"]
         re_true = [float(meta["re"])]
@@ -120,7 +123,7 @@ def main(argv=None):
             vy, vx = scene.split_staggered(v)
             loaded.append((f(d), f(vy), f(vx)))
     dom = sol_amd.Domain([Y, X], box=sol_amd.box[0:length * 2, 0:length])
-    sim = sol_amd.KarmanFlow(pressure_solver=params["pressure_solver"], re_grad=True, diffusion_substeps=nsub, **advection, **flow_kwargs(rec))
+    sim = sol_amd.KarmanFlow(pressure_solver=params["pressure_solver"], re_grad=True, diffusion_substeps=nsub, multi_launch=multi_launch, **advection, **flow_kwargs(rec))
     step = flow_stepper(sim, dom, B, Y, X, res)
     if params["synthetic"]:
         loaded = [first]

@@ -17,7 +17,7 @@ import time
 import numpy as np
 import torch
 
-from _common import (add_advection_arg, advection_from_args, agreed_advection, add_buoyancy_arg, add_scene_args, add_substeps_arg, agreed_buoyancy, agreed_substeps, buoyancy_from_args, flow_kwargs, logger,
+from _common import (add_advection_arg, add_multi_launch_arg, advection_from_args, agreed_advection, agreed_multi_launch, add_buoyancy_arg, add_scene_args, add_substeps_arg, agreed_buoyancy, agreed_substeps, buoyancy_from_args, flow_kwargs, logger,
                      scene_from_args, select_gpu, substeps_from_args)
 import sol_amd
 from sol_amd import ops, scene
@@ -55,6 +55,7 @@ def main(argv=None):
     add_buoyancy_arg(p)
     add_substeps_arg(p, auto=False)
     add_advection_arg(p, generates=False)
+    add_multi_launch_arg(p, generates=False)
     params = vars(p.parse_args(argv))
     select_gpu(params["gpu"])
     rank, world, local = sol_amd.dist.init_from_env()
@@ -81,7 +82,8 @@ def main(argv=None):
     # the buoyancy force travels the same way ("buoyancy" in params.pickle; absent: off)
     # and so do the diffusion substeps ("diffusion_substeps" in params.pickle; absent: 1)
     # and the advection scheme ("advection" / "correction_strength" in params.pickle; absent: semi_lagrangian)
-    rec_set, buoy_set, sub_set, adv_set = None, [], [], []
+    # and the multi-launch path ("multi_launch" in params.pickle; absent: off)
+    rec_set, buoy_set, sub_set, adv_set, ml_set = None, [], [], [], []
     for s in dataset.dataSims:
         with open(s + "/params.pickle", "rb") as f:
             pk = pickle.load(f)
@@ -89,6 +91,7 @@ def main(argv=None):
         buoy_set.append(agreed_buoyancy(pk.get("buoyancy"), None, s))
         sub_set.append(agreed_substeps(pk.get("diffusion_substeps"), None, s))
         adv_set.append(tuple(sorted(agreed_advection(pk, (None, None), s).items())))
+        ml_set.append(bool(pk.get("multi_launch")))
         if rec_set is not None and not sol_amd.karman.scenes_equal(r, rec_set):
             raise SystemExit("the simulations of the training set disagree on the scene: %s has %s, others %s"
                              % (s, sol_amd.karman.describe_scene(r), sol_amd.karman.describe_scene(rec_set)))
@@ -111,6 +114,8 @@ def main(argv=None):
         raise SystemExit("the simulations of the training set disagree on the advection scheme: %s" % sorted(set(adv_set)))
     advection = agreed_advection(dict(adv_set[0]) if adv_set else None, advection_from_args(params), "the training set")
     log.info("advection: %s" % (advection,))
+    multi_launch = agreed_multi_launch(any(ml_set), params["multi_launch"])
+    log.info("multi-launch path: %s" % multi_launch)
     if params["pretf"]:
         # karman_train.py:351-355: the supervised model's own input / output normalisation travels in stats.pickle next to it
         with open(os.path.dirname(params["pretf"]) + "/stats.pickle", "rb") as f:
@@ -132,7 +137,7 @@ def main(argv=None):
     active, inflow = simulator_lo.scene_arrays(dom)
     velBCy, velBCyMask = sol_amd.velocity_bc_masks(Y, X)
     masks = ops.SceneMasks(active, inflow, velBCy.reshape(Y + 1, X), velBCyMask.reshape(Y + 1, X), dev,
-                           pressure_solver=params["pressure_solver"])
+                           pressure_solver=params["pressure_solver"], multi_launch=multi_launch)
     log.info("pressure solver: %s" % masks.pressure_solver)
     # eval('model_'+params['model']) (karman_train.py:394): mars_moon runs the C++ schedule (SolTrainer), mercury the
     # hand-written schedule captured into a hipGraph (GraphTrainer); a domain beyond the one-workgroup grids (-s 1 on a -r 128 set):
@@ -152,6 +157,7 @@ def main(argv=None):
     dataset.dataStats.setdefault("diffusion_substeps", nsub)
     dataset.dataStats.setdefault("advection", advection["advection"])
     dataset.dataStats.setdefault("correction_strength", advection["correction_strength"])
+    dataset.dataStats.setdefault("multi_launch", multi_launch)
     if params["resume"] < 1:
         if rank == 0:
             with open(params["tf"] + "/dataStats.pickle", "wb") as f:
@@ -165,7 +171,7 @@ def main(argv=None):
                                  in_std_v=dataset.dataStats["in.std"][1] if "in.std" in dataset.dataStats else None,
                                  out_std_v=dataset.dataStats["out.std"] if "out.std" in dataset.dataStats else None,
                                  pressure_solver=params["pressure_solver"], any_width=params["any_width"], buoyancy=buoyancy,
-                                 diffusion_substeps=nsub, **advection, **flow_kwargs(rec))
+                                 diffusion_substeps=nsub, multi_launch=multi_launch, **advection, **flow_kwargs(rec))
     # persistent device buffers: the captured hipGraph keeps their addresses, new data is copied in
     f32 = lambda shape: torch.empty(shape, dtype=torch.float32, device=dev)
     d0, vy0, vx0, re = f32((Bl, Y, X)), f32((Bl, Y + 1, X)), f32((Bl, Y, X + 1)), f32((Bl,))

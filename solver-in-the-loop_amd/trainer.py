@@ -66,6 +66,25 @@ def _refuse_large_grid(who, Y, X):
                          "KarmanFlow.step / ops.karman_step_large" % (who, Y, X))
 
 
+def _check_multi_launch(who, multi_launch, masks, Y, X):
+    """multi_launch=True asks for the multi-launch solver pair on a grid the one-workgroup kernels would serve: Y, X >= 16, and masks
+    (where the caller gives them) built with the same flag -- the two disagreeing is refused here, at construction.  -> bool"""
+    multi_launch = bool(multi_launch)
+    if multi_launch and (Y < 16 or X < 16):
+        raise ValueError("%s: multi_launch=True takes grids with Y, X >= 16 (the multi-launch kernels); this one is %dx%d" % (who, Y, X))
+    if masks is not None and bool(getattr(masks, "multi_launch", False)) != multi_launch:
+        raise ValueError("%s: multi_launch=%r, but the masks were built with SceneMasks(multi_launch=%r); build both with the same flag"
+                         % (who, multi_launch, bool(getattr(masks, "multi_launch", False))))
+    return multi_launch
+
+
+def _width_served(Y, X, any_width, multi_launch):
+    """Whether the network's launches take rows of X cells: any width under any_width (pitched rows); a multiple of 64 on a large domain;
+    under multi_launch also every width the convolutions take as it is (schedule2d.row_pitch(Y, X) == X: 16, 32, 64 ...)"""
+    from .schedule2d import row_pitch
+    return bool(any_width) or X % 64 == 0 or (multi_launch and row_pitch(Y, X) == X)
+
+
 def _refuse_buoyancy(who, buoyancy):
     """SolTrainer and GraphTrainer run the fused one-workgroup solver kernels, which have no buoyancy term: a non-zero force is refused
     at construction (LargeGridTrainer(buoyancy=...) trains with it on a large grid).  -> None"""
@@ -322,8 +341,10 @@ class LargeGridRollout:
 
     def __init__(self, net, masks, B, Y, X, dx, std_v, std_re, dt=1.0, res=None, in_std_v=None, out_std_v=None,
                  conv_precision="split", use_graph=True, cg_warm_start=False, any_width=False, buoyancy=None, diffusion_substeps=1,
-                 advection="semi_lagrangian", correction_strength=1.0, **solver):
-        """any_width=True: X need not be a multiple of 64 -- the network runs in pitched rows (NetSchedule2D(any_width=True): the features
+                 advection="semi_lagrangian", correction_strength=1.0, multi_launch=False, **solver):
+        """multi_launch=True: a grid the one-workgroup roll-out would serve (Y, X >= 16), on masks built with multi_launch=True; a width
+        the convolutions take as it is (schedule2d.row_pitch(Y, X) == X) runs dense, any other needs any_width=True.
+        any_width=True: X need not be a multiple of 64 -- the network runs in pitched rows (NetSchedule2D(any_width=True): the features
         are copied into zero-padded rows of 64 * ceil(X / 64) pixels and the output is cropped; the solver step and the correction stay
         dense).  buoyancy=(fy, fx) (ops.buoyancy_force): the density pushes the velocity -- the solver step is the buoyant one
         (sol_karman_step_fwd_large_buoy: one launch more, captured with the rest; direct and CG scenes, warm start included).
@@ -333,9 +354,11 @@ class LargeGridRollout:
         ph = self.physics = ops.StepPhysics.of(buoyancy=buoyancy, diffusion_substeps=diffusion_substeps, advection=advection,
                                                correction_strength=correction_strength, who="LargeGridRollout")
         self.buoyancy, self.diffusion_substeps, self.advection = ph.buoyancy, ph.nsub, ph.advection_kw
-        if not ops.beyond_one_workgroup(Y, X):
-            raise ValueError("LargeGridRollout: a %dx%d domain is served by the one-workgroup roll-out -- use SolRollout (make_rollout picks)" % (Y, X))
-        if X % 64 != 0 and not any_width:
+        self.multi_launch = _check_multi_launch("LargeGridRollout", multi_launch, masks, Y, X)
+        if not ops.beyond_one_workgroup(Y, X) and not self.multi_launch:
+            raise ValueError("LargeGridRollout: a %dx%d domain is served by the one-workgroup roll-out -- use SolRollout (make_rollout picks); "
+                             "multi_launch=True runs the multi-launch roll-out on it" % (Y, X))
+        if not _width_served(Y, X, any_width, self.multi_launch):
             raise ValueError("LargeGridRollout: the convolutions of a large domain take rows of X %% 64 == 0 cells (got %dx%d); "
                              "no roll-out class serves this grid (KarmanFlow.step advances it without the network)" % (Y, X))
         cg = masks.pressure_solver == "cg"
@@ -423,8 +446,9 @@ class LargeGridRollout:
 
 def make_rollout(net, masks, B, Y, X, dx, std_v, std_re, **kw):
     """SolRollout for the one-workgroup solver grids, LargeGridRollout beyond them (use_graph / cg_warm_start / any_width belong to the latter)."""
-    if ops.beyond_one_workgroup(Y, X):
+    if ops.beyond_one_workgroup(Y, X) or kw.get("multi_launch"):
         return LargeGridRollout(net, masks, B, Y, X, dx, std_v, std_re, **kw)
+    kw.pop("multi_launch", None)
     for k in ("use_graph", "cg_warm_start", "any_width"):
         kw.pop(k, None)
     ph = ops.StepPhysics.of(**{k: kw.pop(k) for k in ("buoyancy", "advection", "correction_strength") if k in kw}, who="make_rollout")
@@ -669,8 +693,11 @@ class LargeGridTrainer(GraphTrainer):
     convergence and is fully supported.  After a step `solve_info` holds "iterations" / "converged" [msteps, B] and "iterations_bwd" /
     "converged_bwd" [msteps - 1, B] (the first unrolled step's input receives no gradient: its solver adjoint is not run) for CG scenes."""
 
-    def __init__(self, net, B, Y, X, msteps, std_v, std_re, any_width=False, **kw):
-        """any_width=True: X need not be a multiple of 64 -- the network's forward and reverse launches run in pitched rows of
+    def __init__(self, net, B, Y, X, msteps, std_v, std_re, any_width=False, multi_launch=False, **kw):
+        """multi_launch=True: a grid the one-workgroup trainers would serve (Y, X >= 16) -- the scene's masks are built with
+        SceneMasks(multi_launch=True) (masks given by the caller must have been); a width the convolutions take as it is
+        (schedule2d.row_pitch(Y, X) == X) runs dense, any other needs any_width=True.
+        any_width=True: X need not be a multiple of 64 -- the network's forward and reverse launches run in pitched rows of
         64 * ceil(X / 64) pixels (NetSchedule2D(any_width=True): column-masked convolutions, the weight gradient at the pitch); the solver
         pair, the correction and the loss stay dense.
         buoyancy, diffusion_substeps, advection, correction_strength (keywords): the physics of the solver pair, one ops.StepPhysics
@@ -686,14 +713,16 @@ class LargeGridTrainer(GraphTrainer):
         if kw.get("schedule", "manual") != "manual":
             raise ValueError("LargeGridTrainer runs the hand-written schedule only (schedule='manual')")
         self._any_width = bool(any_width)       # (before the base constructor: _check_grid reads it)
+        self.multi_launch = _check_multi_launch("LargeGridTrainer", multi_launch, kw.get("masks"), Y, X)
         super().__init__(net, B, Y, X, msteps, std_v, std_re, **kw)
+        self.sim._multi_launch = self.multi_launch       # the KarmanFlow that builds this trainer's masks (_schedule_setup)
         self.solve_info = {}
 
     def _check_grid(self, Y, X):
-        if not ops.beyond_one_workgroup(Y, X):
+        if not ops.beyond_one_workgroup(Y, X) and not self.multi_launch:
             raise ValueError("LargeGridTrainer: a %dx%d domain is served by the one-workgroup trainers -- use SolTrainer (mars_moon) or "
-                             "GraphTrainer (make_trainer picks)" % (Y, X))
-        if X % 64 != 0 and not self._any_width:
+                             "GraphTrainer (make_trainer picks); multi_launch=True runs this trainer on it" % (Y, X))
+        if not _width_served(Y, X, self._any_width, self.multi_launch):
             raise ValueError("LargeGridTrainer: the convolutions of a large domain take rows of X %% 64 == 0 cells (got %dx%d)" % (Y, X))
 
     _adjoint_of_first_step = False
@@ -756,8 +785,9 @@ class LargeGridTrainer(GraphTrainer):
 def make_trainer(net, masks, B, Y, X, msteps, dx, std_v, std_re, **kw):
     """SolTrainer (the C++ schedule: model_mars_moon), GraphTrainer (every other network) or, for a domain beyond the one-workgroup
     solver grids, LargeGridTrainer (either network)."""
-    if ops.beyond_one_workgroup(Y, X):
+    if ops.beyond_one_workgroup(Y, X) or kw.get("multi_launch"):
         return LargeGridTrainer(net, B, Y, X, msteps, std_v, std_re, dx=dx, masks=masks, **kw)
+    kw.pop("multi_launch", None)
     if net.name == "mars_moon":
         # the C++ schedule takes its scene and its pressure solver from `masks` alone (obstacles / active / pressure_solver
         # describe them for GraphTrainer's KarmanFlow)
