@@ -225,6 +225,32 @@ int sol_karman_pressure_solve_large(const sol_karman_cfg* cfg, void* stream, con
 int sol_karman_pressure_solve_large_direct(const sol_karman_cfg* cfg, void* stream, const float* rhs, float* p,
                                            const int32_t* direct_header_host, void* workspace, size_t workspace_bytes);
 
+/* PERIODIC BOUNDARIES of the large-grid step (csrc/karman_periodic.hip).  A direct blob built with precond's periodic=(py, px) carries
+ * the axes in its header's flags word -- word 8 of an "FD02" blob (one window, or the box blob with nS = 0 that serves an EMPTY periodic
+ * scene: box forward, box back), word 9 of an "FDS1" blob (its word 8 is CP): bit 1 (value 2) = y periodic, bit 2 (value 4) = x
+ * periodic; bit 0 of word 8 stays the host-only one-launch flag.  Every entry point that takes `direct_header_host` reads the bits from
+ * that host copy: clear, it issues the launches it always did; set, its stencil phases run with wrapped indices and its solve runs the
+ * same launches on the blob's Hartley tables (precond.hartley_matrix: symmetric, orthogonal, diagonalises the periodic second difference).
+ *   - Array shapes do not change.  On a periodic axis the last face plane DUPLICATES the first: vy[:, Y, :] = vy[:, 0, :] (y),
+ *     vx[:, :, X] = vx[:, :, 0] (x).  The step never reads the duplicate plane of an input (a NaN there changes nothing) and writes
+ *     the duplicate plane of vy_out / vx_out / saved_vy / saved_vx equal to plane 0 bit for bit.
+ *   - Every index the open step clamps or sends to the density's zero ghost ring -- the replicate-padded Laplacian, the face averages
+ *     of the advecting velocity, the bilinear gathers of v_y, v_x and the density, the face masks, the divergence, the pressure
+ *     gradient -- is taken modulo n over the unique planes 0 .. n-1 (a true modulo: a departure point several periods away lands
+ *     correctly).  The pressure gradient ignores cfg.grad_pad on a periodic axis: there is no boundary face.  The open axis of a
+ *     mixed scene behaves as in the open step (velBC blend, clamp, grad_pad).  velBCy / velBCyMask are read on unique faces only.
+ *   - Adjoint (sol_karman_step_bwd_large): the cotangent of an output duplicate plane is first added onto plane 0's (one fp32 add);
+ *     the duplicate planes of g_vy_in / g_vx_in are exactly zero; the advection scatter stays in 64-bit fixed point with global
+ *     atomics (order independent, bit-reproducible, capturable; the option k2d_adj_tile does not apply).
+ *   - Doubly periodic: the scene must be empty, the matrix is singular, and the solve returns the zero-mean pressure (1/lam = 0 at
+ *     the zero mode; the right-hand side -div has zero mean by construction).
+ *   - Refused (SOL_ERR_ARG) on a periodic scene: the CG solve, advection = 1 (MacCormack), a non-zero buoyancy force, the _re forms.
+ * sol_karman_seam_sync: plane 0 copied onto the duplicate plane of vy [B,Y+1,X] / vx [B,Y,X+1] for the axes in periodic_bits (2 = y,
+ * 4 = x, 6 = both; 0: nothing is launched) -- what follows a launch that leaves the duplicate plane stale (sol_karman_correct).
+ * sol_karman_seam_fold: its adjoint on a cotangent, g[plane 0] += g[duplicate] (one fp32 add), then g[duplicate] = 0.  Any Y, X >= 1. */
+int sol_karman_seam_sync(void* stream, float* vy, float* vx, int32_t B, int32_t Y, int32_t X, int32_t periodic_bits);
+int sol_karman_seam_fold(void* stream, float* g_vy, float* g_vx, int32_t B, int32_t Y, int32_t X, int32_t periodic_bits);
+
 /* Adjoint of the large-grid step with respect to its input velocity, for both solvers (csrc/karman_large_bwd.hip).  The solver is
  * chosen by the cfg: cfg.direct set = the direct solve (direct_header_host required; box_blob / box_header_host / cg_info are not read
  * and may be NULL), cfg.direct NULL = the preconditioned CG (box_blob, box_header_host, cg_info [2][B] required as for

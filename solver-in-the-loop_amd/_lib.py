@@ -74,6 +74,8 @@ _SIGS = {
     "sol_karman_step_fwd_large_cg": (C.c_int, [_P] * 10 + [C.c_int64] + [_P] * 9 + [C.c_size_t]),
     "sol_karman_step_fwd_large_cg_warm": (C.c_int, [_P] * 10 + [C.c_int64] + [_P] * 10 + [C.c_size_t]),
     "sol_karman_correct": (C.c_int, [_P] * 6 + [C.c_int32] * 3 + [C.c_float] * 2),
+    "sol_karman_seam_sync": (C.c_int, [_P] * 3 + [C.c_int32] * 4),
+    "sol_karman_seam_fold": (C.c_int, [_P] * 3 + [C.c_int32] * 4),
     "sol_karman_pressure_solve_large": (C.c_int, [_P] * 9 + [C.c_size_t]),
     "sol_karman_step_bwd_large_workspace_bytes": (C.c_size_t, [_P]),
     "sol_karman_step_fwd_large_saved": (C.c_int, [_P] * 10 + [C.c_int64] + [_P] * 10 + [C.c_size_t]),

@@ -49,6 +49,7 @@ struct SolLargeStep {
     int advection = 0;                     // 0: k_l_advect (semi-Lagrangian); 1: the MacCormack advection (karman_maccormack.hip) with
     float mc_strength = 1.f;               //    this correction strength on the workspace part mc_ws (sol_mc_bytes)
     void* mc_ws = nullptr;
+    int periodic = 0;                      // SOL_DIRECT_HDR_PERIODIC_Y / _X of the direct blob's host header (sol_periodic_bits); 0: the open kernels
 };
 // the advection launch alone: k_l_advect on a given post-diffusion velocity (karman_large.hip), and the MacCormack form of it
 // (karman_maccormack.hip: d_out NULL = the velocity alone; ws holds sol_mc_bytes); sol_mc_check: the two arguments of the _adv entry points
@@ -73,8 +74,8 @@ int sol_buoyancy_adj(hipStream_t s, int B, int Y, int X, const float* active, co
                      float fy, float fx, const float* g_d_out, float* g_dsum);
 int sol_large_front(const sol_karman_cfg* c, hipStream_t s, const SolLargeStep& io, float* svy, float* svx, float* rhs);
 int sol_large_project(const sol_karman_cfg* c, hipStream_t s, const SolLargeStep& io, const float* p);
-int sol_large_box_forward(hipStream_t s, int B, int Y, int X, const float* blob, const float* src, float* T1, float* T2, const int* skip);
-int sol_large_box_back(hipStream_t s, int B, int Y, int X, const float* blob, const float* T2, float* T1, float* dst, const int* skip);
+int sol_large_box_forward(hipStream_t s, int B, int Y, int X, const float* blob, const float* src, float* T1, float* T2, const int* skip, bool wide = false);
+int sol_large_box_back(hipStream_t s, int B, int Y, int X, const float* blob, const float* T2, float* T1, float* dst, const int* skip, bool wide = false);
 // the step's pressure solve M x = b for either solver (pcg.hip; shared by the forward entry points and the adjoint, karman_large_bwd.hip):
 // direct = the capacitance solve on cfg.direct (hdr: host copy of its header, sol_large_direct_check; its magic word selects the one-window
 // form of precond.direct_solver_blob or the scattered form of precond.scattered_solver_blob), else the preconditioned CG with the
@@ -88,6 +89,36 @@ int sol_large_direct_solve(hipStream_t s, const sol_karman_cfg* c, const int32_t
 bool sol_solve_one_wg_supported(int Y, int X, int win);
 int sol_solve_one_wg(hipStream_t s, const sol_karman_cfg* c, const int32_t* hdr, float* base);
 constexpr int SOL_DIRECT_HDR_FLAGS = 8, SOL_DIRECT_HDR_ONE_WG = 1;      // host header copy, word 8: bit 0 = the scene was built with multi_launch
+// periodic domain boundaries (karman_periodic.hip): bits 1 and 2 of the flags word say which axes wrap.  The flags word is word 8 of a
+// one-window or box blob ("FD02") and word 9 of a scattered blob ("FDS1", whose word 8 is CP); precond.py writes the bits into the blob.
+constexpr int SOL_DIRECT_HDR_PERIODIC_Y = 2, SOL_DIRECT_HDR_PERIODIC_X = 4;
+inline int sol_periodic_bits(const int32_t* hdr) {
+    if (!hdr) return 0;
+    return hdr[hdr[0] == 0x46445331 ? 9 : SOL_DIRECT_HDR_FLAGS] & (SOL_DIRECT_HDR_PERIODIC_Y | SOL_DIRECT_HDR_PERIODIC_X);
+}
+// the stencil phases with wrapped indices, called by sol_large_front / sol_large_project when io.periodic != 0
+// the solve's products on a periodic blob (wide = true above): sol_gemm_f32's contract with fp64 accumulators, one rounding per element
+int sol_periodic_gemm(hipStream_t s, int batch, const float* A, int lda, long sA, const float* Bm, int ldb, long sB, float* C, int ldc, long sC,
+                      int M, int N, int K, int accumulate);
+int sol_periodic_front(const sol_karman_cfg* c, hipStream_t s, const SolLargeStep& io, float* svy, float* svx, float* rhs);
+int sol_periodic_project(const sol_karman_cfg* c, hipStream_t s, const SolLargeStep& io, const float* p);
+// the adjoint's stages around its pressure solve (the fields of karman_large_bwd.hip's LBArgs): _rhs = k_lb_rhs's job, _tail = k_lb_ga,
+// the advection scatter (global int64 atomics) and k_lb_diffuse_adj's
+struct SolPeriodicBwd {
+    int B, Y, X, periodic;
+    float dtdx, adt;
+    int grad_pad;
+    const float *re, *active, *bcm;
+    long bc_stride;
+    const float *svy, *svx, *goy, *gox;
+    float *gay, *gax;
+    long long *gcy, *gcx;
+    unsigned* gmax;
+    float *giy, *gix, *rhs;
+    const float* gdiv;
+};
+int sol_periodic_bwd_rhs(hipStream_t s, const SolPeriodicBwd& a);
+int sol_periodic_bwd_tail(hipStream_t s, const SolPeriodicBwd& a);
 int sol_large_cg_check(const sol_karman_cfg* c, const char* who, const float* box_blob, const int32_t* hdr, const int32_t* cg_info, const void* workspace);
 size_t sol_large_solver_bytes(const sol_karman_cfg* c, bool direct, const int32_t* hdr = nullptr);
 float* sol_large_solver_rhs(const sol_karman_cfg* c, bool direct, void* ws);

@@ -335,7 +335,9 @@ inline HeaderSc header_sc(const int32_t* hdr) { return HeaderSc{hdr[1], hdr[2], 
 struct Header { int Y, X, wy0, wx0, nS, SP, win; };
 
 int gemm(hipStream_t s, int batch, const float* A, int lda, long sA, const float* Bm, int ldb, long sB, float* C, int ldc, long sC,
-         int M, int N, int K, int accumulate, const int* skip = nullptr) {
+         int M, int N, int K, int accumulate, const int* skip = nullptr, bool wide = false) {
+    // periodic scenes: the same product with fp64 accumulators (karman_periodic.hip says why); never with a CG solve's done words
+    if (wide) return sol_periodic_gemm(s, batch, A, lda, sA, Bm, ldb, sB, C, ldc, sC, M, N, K, accumulate);
     GArgs g{A, Bm, nullptr, C, M, N, K, lda, ldb, ldc, 0, sA, sB, sC, accumulate, skip};
     SOL_LAUNCH(k_l_gemm, dim3((N + 63) / 64, (M + 63) / 64, batch), dim3(256), 0, s, g);
     SOL_LAUNCH_CHECK();
@@ -363,6 +365,7 @@ int sol_gemm_f32(hipStream_t s, int batch, const float* A, int lda, long sA, con
 
 // ---- the stencil phases around the pressure solve (shared with pcg.hip) ----
 int sol_large_front(const sol_karman_cfg* c, hipStream_t s, const SolLargeStep& io, float* svy, float* svx, float* rhs) {
+    if (io.periodic) return sol_periodic_front(c, s, io, svy, svx, rhs);      // wrapped indices: karman_periodic.hip
     const LArgs a = large_args(c, io, svy, svx, rhs, nullptr);
     const int B = c->B, N = c->Y * c->X, faces = (c->Y + 1) * c->X + c->Y * (c->X + 1);
     SOL_LAUNCH(k_l_diffuse, dim3((faces + 255) / 256, B), dim3(256), 0, s, a);
@@ -389,6 +392,7 @@ int sol_large_advect(const sol_karman_cfg* c, hipStream_t s, const float* d_in, 
 }
 
 int sol_large_project(const sol_karman_cfg* c, hipStream_t s, const SolLargeStep& io, const float* p) {
+    if (io.periodic) return sol_periodic_project(c, s, io, p);
     const LArgs a = large_args(c, io, nullptr, nullptr, nullptr, p);
     const int faces = (c->Y + 1) * c->X + c->Y * (c->X + 1);
     SOL_LAUNCH(k_l_project, dim3((faces + 255) / 256, c->B), dim3(256), 0, s, a);
@@ -399,26 +403,26 @@ int sol_large_project(const sol_karman_cfg* c, hipStream_t s, const SolLargeStep
 // ---- the empty-box solve G = M_r^-1 (sine-transform diagonalisation of the rectangle), in two halves: the direct solve adds its
 // capacitance correction to the spectral coefficients T2 in between, the CG solve applies both halves back to back.  All matrices
 // row-major [Y][X] per simulation; Qy, Qx symmetric.  blob: the sections after the header (Qy, Qx, 1/lam transposed)
-int sol_large_box_forward(hipStream_t s, int B, int Y, int X, const float* blob, const float* src, float* T1, float* T2, const int* skip) {
+int sol_large_box_forward(hipStream_t s, int B, int Y, int X, const float* blob, const float* src, float* T1, float* T2, const int* skip, bool wide) {
     const float* Qy = blob + FDL_HEADER;
     const float* Qx = Qy + (size_t)Y * Y;
     const float* ilT = Qx + (size_t)X * X;             // [X][Y]
     const long sN = (long)Y * X;
     // T1 = Qy src ;  T2 = (T1 Qx) / lam
-    if (int e = gemm(s, B, Qy, Y, 0, src, X, sN, T1, X, sN, Y, X, Y, 0, skip)) return e;
-    if (int e = gemm(s, B, T1, X, sN, Qx, X, 0, T2, X, sN, Y, X, X, 0, skip)) return e;
+    if (int e = gemm(s, B, Qy, Y, 0, src, X, sN, T1, X, sN, Y, X, Y, 0, skip, wide)) return e;
+    if (int e = gemm(s, B, T1, X, sN, Qx, X, 0, T2, X, sN, Y, X, X, 0, skip, wide)) return e;
     SOL_LAUNCH(k_l_scale, dim3((Y * X + 255) / 256, B), dim3(256), 0, s, T2, (const float*)nullptr, ilT, Y, X, skip);
     SOL_LAUNCH_CHECK();
     return SOL_OK;
 }
 
-int sol_large_box_back(hipStream_t s, int B, int Y, int X, const float* blob, const float* T2, float* T1, float* dst, const int* skip) {
+int sol_large_box_back(hipStream_t s, int B, int Y, int X, const float* blob, const float* T2, float* T1, float* dst, const int* skip, bool wide) {
     const float* Qy = blob + FDL_HEADER;
     const float* Qx = Qy + (size_t)Y * Y;
     const long sN = (long)Y * X;
     // dst = Qy (T2 Qx)
-    if (int e = gemm(s, B, T2, X, sN, Qx, X, 0, T1, X, sN, Y, X, X, 0, skip)) return e;
-    return gemm(s, B, Qy, Y, 0, T1, X, sN, dst, X, sN, Y, X, Y, 0, skip);
+    if (int e = gemm(s, B, T2, X, sN, Qx, X, 0, T1, X, sN, Y, X, X, 0, skip, wide)) return e;
+    return gemm(s, B, Qy, Y, 0, T1, X, sN, dst, X, sN, Y, X, Y, 0, skip, wide);
 }
 
 // ---- the direct pressure solve on its own buffers (shared by the forward step and the adjoint, karman_large_bwd.hip) ----
@@ -481,18 +485,19 @@ int scattered_solve(hipStream_t s, const sol_karman_cfg* c, const int32_t* hdr, 
     const DirectLayout l = direct_layout(c, hdr, base);
     float *T0 = l.T0, *T1 = l.T1, *T2 = l.T2, *U = l.U, *V = l.V, *X0 = l.X0, *W2 = l.W2;
     const long sN = N, sU = (long)Y * CP, sW = (long)RP * CP;
-    if (int e = sol_large_box_forward(s, B, Y, X, c->direct, T0, T1, T2, nullptr)) return e;
-    if (int e = gemm(s, B, T2, X, sN, QxC, CP, 0, U, CP, sU, Y, CP, X, 0)) return e;
-    if (int e = gemm(s, B, QyR, Y, 0, U, CP, sU, X0, CP, sW, RP, CP, Y, 0)) return e;
+    const bool wide = sol_periodic_bits(hdr) != 0;      // periodic scenes: fp64 accumulators in every product of the solve
+    if (int e = sol_large_box_forward(s, B, Y, X, c->direct, T0, T1, T2, nullptr, wide)) return e;
+    if (int e = gemm(s, B, T2, X, sN, QxC, CP, 0, U, CP, sU, Y, CP, X, 0, nullptr, wide)) return e;
+    if (int e = gemm(s, B, QyR, Y, 0, U, CP, sU, X0, CP, sW, RP, CP, Y, 0, nullptr, wide)) return e;
     // the workspace is the caller's: every call clears W2 before the support entries are written
     const size_t nw = (size_t)B * sW, nb = (nw + 255) / 256;
     SOL_LAUNCH(k_l_zero, dim3((unsigned)(nb < 1024 ? nb : 1024)), dim3(256), 0, s, W2, nw);
     SOL_LAUNCH(k_l_capacitance_sc, dim3(SP / SC_TILE, B), dim3(256), 0, s, (const float*)X0, KpT, sidx, W2, SP, (int)sW);
     SOL_LAUNCH_CHECK();
-    if (int e = gemm(s, B, QyRt, RP, 0, W2, CP, sW, V, CP, sU, Y, CP, RP, 0)) return e;
-    if (int e = gemm(s, B, V, CP, sU, QxCr, X, 0, T1, X, sN, Y, X, CP, 0)) return e;
+    if (int e = gemm(s, B, QyRt, RP, 0, W2, CP, sW, V, CP, sU, Y, CP, RP, 0, nullptr, wide)) return e;
+    if (int e = gemm(s, B, V, CP, sU, QxCr, X, 0, T1, X, sN, Y, X, CP, 0, nullptr, wide)) return e;
     SOL_LAUNCH(k_l_scale, dim3((N + 255) / 256, B), dim3(256), 0, s, T2, (const float*)T1, ilT, Y, X, (const int*)nullptr);
-    return sol_large_box_back(s, B, Y, X, c->direct, T2, T1, T0, nullptr);
+    return sol_large_box_back(s, B, Y, X, c->direct, T2, T1, T0, nullptr, wide);
 }
 
 }  // namespace
@@ -504,6 +509,13 @@ int sol_large_direct_check(const sol_karman_cfg* c, const char* who, const int32
     if (hdr && hdr[0] == FDS_MAGIC) return scattered_check(c, who, hdr);
     SOL_REQUIRE(hdr && hdr[0] == 0x46443032, "%s: direct_header_host must be the first 16 words of the blob (host copy)", who);
     const Header h{hdr[1], hdr[2], hdr[3], hdr[4], hdr[5], hdr[6], hdr[7]};
+    if (h.nS == 0 && sol_periodic_bits(hdr)) {      // an empty periodic scene: the box blob as its direct blob (box forward, box back)
+        SOL_REQUIRE(h.Y == c->Y && h.X == c->X, "direct-solver blob is for a %dx%d grid, cfg is %dx%d", h.Y, h.X, c->Y, c->X);
+        SOL_REQUIRE(h.SP == 0 && h.win == 0, "direct-solver blob header is inconsistent");
+        SOL_REQUIRE((size_t)c->direct_n >= FDL_HEADER + (size_t)h.Y * h.Y + (size_t)h.X * h.X + (size_t)h.X * h.Y,
+                    "%s: cfg.direct_n = %d words is less than the box blob of this header", who, c->direct_n);
+        return SOL_OK;
+    }
     SOL_REQUIRE(h.SP >= h.nS && h.SP <= 4096 && h.wy0 >= 0 && h.wx0 >= 0 && h.wy0 + h.win <= c->Y && h.wx0 + h.win <= c->X,
                 "direct-solver blob header is inconsistent");
     SOL_REQUIRE(h.Y == c->Y && h.X == c->X, "direct-solver blob is for a %dx%d grid, cfg is %dx%d", h.Y, h.X, c->Y, c->X);
@@ -516,6 +528,11 @@ int sol_large_direct_solve(hipStream_t s, const sol_karman_cfg* c, const int32_t
     if (hdr[0] == FDS_MAGIC) return scattered_solve(s, c, hdr, base);
     const Header h{hdr[1], hdr[2], hdr[3], hdr[4], hdr[5], hdr[6], hdr[7]};
     const int B = c->B, Y = c->Y, X = c->X, N = Y * X, win = h.win, SP = h.SP;
+    if (h.nS == 0) {            // the empty periodic box (sol_large_direct_check): no capacitance part
+        const DirectLayout l = direct_layout(c, hdr, base);
+        if (int e = sol_large_box_forward(s, B, Y, X, c->direct, l.T0, l.T1, l.T2, nullptr, true)) return e;
+        return sol_large_box_back(s, B, Y, X, c->direct, l.T2, l.T1, l.T0, nullptr, true);
+    }
     // a scene built with multi_launch on a grid one workgroup holds: the whole solve as one launch (karman_solve_small.hip)
     if ((hdr[SOL_DIRECT_HDR_FLAGS] & SOL_DIRECT_HDR_ONE_WG) && sol_opt().k2d_solve_one_wg && sol_solve_one_wg_supported(Y, X, win))
         return sol_solve_one_wg(s, c, hdr, base);
@@ -529,19 +546,20 @@ int sol_large_direct_solve(hipStream_t s, const sol_karman_cfg* c, const int32_t
     const DirectLayout l = direct_layout(c, hdr, base);
     float *T0 = l.T0, *T1 = l.T1, *T2 = l.T2, *U = l.U, *V = l.V, *X0 = l.X0, *W2 = l.W2;      // U, V: [Y][win], X0, W2: [win][win]
     const long sN = N, sU = (long)Y * 64, sW = 64 * 64;
-    if (int e = sol_large_box_forward(s, B, Y, X, c->direct, T0, T1, T2, nullptr)) return e;
+    const bool wide = sol_periodic_bits(hdr) != 0;      // periodic scenes: fp64 accumulators in every product of the solve
+    if (int e = sol_large_box_forward(s, B, Y, X, c->direct, T0, T1, T2, nullptr, wide)) return e;
     // window values of G b: U = T2 Qx[:, win] ; X0 = Qy[win, :] U
-    if (int e = gemm(s, B, T2, X, sN, QxW, win, 0, U, win, sU, Y, win, X, 0)) return e;
-    if (int e = gemm(s, B, Qy + (size_t)h.wy0 * Y, Y, 0, U, win, sU, X0, win, sW, win, win, Y, 0)) return e;
+    if (int e = gemm(s, B, T2, X, sN, QxW, win, 0, U, win, sU, Y, win, X, 0, nullptr, wide)) return e;
+    if (int e = gemm(s, B, Qy + (size_t)h.wy0 * Y, Y, 0, U, win, sU, X0, win, sW, win, win, Y, 0, nullptr, wide)) return e;
     // W2 = -scatter(K' gather(X0))
     SOL_LAUNCH(k_l_capacitance, dim3(B), dim3(256), SP * sizeof(float), s, X0, KpT, sidx, W2, SP, win);
     SOL_LAUNCH_CHECK();
     // spectral coefficients of the correction: V = Qy[:, win] W2 ; T2 += ((V Qx[win, :])) / lam
-    if (int e = gemm(s, B, Qy + h.wy0, Y, 0, W2, win, sW, V, win, sU, Y, win, win, 0)) return e;
-    if (int e = gemm(s, B, V, win, sU, Qx + (size_t)h.wx0 * X, X, 0, T1, X, sN, Y, X, win, 0)) return e;
+    if (int e = gemm(s, B, Qy + h.wy0, Y, 0, W2, win, sW, V, win, sU, Y, win, win, 0, nullptr, wide)) return e;
+    if (int e = gemm(s, B, V, win, sU, Qx + (size_t)h.wx0 * X, X, 0, T1, X, sN, Y, X, win, 0, nullptr, wide)) return e;
     SOL_LAUNCH(k_l_scale, dim3((N + 255) / 256, B), dim3(256), 0, s, T2, (const float*)T1, ilT, Y, X, (const int*)nullptr);
     // p = Qy (T2 Qx)
-    return sol_large_box_back(s, B, Y, X, c->direct, T2, T1, T0, nullptr);
+    return sol_large_box_back(s, B, Y, X, c->direct, T2, T1, T0, nullptr, wide);
 }
 
 extern "C" int sol_karman_correct(void* stream, const float* out, float* vy, float* vx, float* cor_y, float* cor_x,

@@ -340,6 +340,20 @@ int bwd_large(const char* who, const sol_karman_cfg* c, void* stream,
     a.giy = g_vy_in; a.gix = g_vx_in;
     a.rhs = sol_large_solver_rhs(c, direct, l.solver);
     const unsigned gN = (unsigned)((N + 255) / 256), gF = (unsigned)((faces + 255) / 256);
+    // periodic axes (the direct blob's header bits): the same five stages with wrapped indices, karman_periodic.hip
+    const int periodic = direct ? sol_periodic_bits(direct_header_host) : 0;
+    SOL_REQUIRE(direct || !sol_periodic_bits(box_header_host), "%s: the CG pressure solve is not built for periodic scenes; use the direct solve", who);
+    if (periodic) {
+        SOL_REQUIRE(!rx && !bx && !mc, "%s: periodic scenes run the plain velocity adjoint only: the gradient in re, the buoyancy force and the "
+                    "mac_cormack advection are not built for them (use sol_karman_step_bwd_large)", who);
+        SolPeriodicBwd pa{B, Y, X, periodic, a.dtdx, a.adt, a.grad_pad, re, active, velBCyMask, (long)bc_batch_stride, saved_vy, saved_vx, g_vy_out, g_vx_out,
+                          a.gay, a.gax, a.gcy, a.gcx, a.gmax, g_vy_in, g_vx_in, a.rhs, nullptr};
+        if (int e = sol_periodic_bwd_rhs(s, pa)) return e;
+        float* pq = nullptr;
+        if (int e = pressure_solve_any2d(s, c, direct, direct_header_host, box_blob, active, cg_info, l.solver, &pq)) return e;
+        pa.gdiv = pq;
+        return sol_periodic_bwd_tail(s, pa);
+    }
     SOL_LAUNCH(k_lb_rhs, dim3(gN, B), dim3(256), 0, s, a);
     SOL_LAUNCH_CHECK();
     float* q = nullptr;

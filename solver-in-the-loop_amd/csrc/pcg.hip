@@ -517,6 +517,11 @@ int large_fwd(const char* who, const sol_karman_cfg* c, void* stream, SolLargeSt
     const FwdLayout& l = al.step;
     SOL_REQUIRE(workspace_bytes >= al.bytes, "%s: workspace too small (%zu < %zu bytes)", who, workspace_bytes, al.bytes);
     if (mc) { io.advection = 1; io.mc_strength = adv->strength; io.mc_ws = al.mc; }
+    io.periodic = sv.direct ? sol_periodic_bits(sv.direct_header_host) : 0;      // periodic axes: the stencil phases of karman_periodic.hip
+    SOL_REQUIRE(sv.direct || !sol_periodic_bits(sv.box_header_host), "%s: the CG pressure solve is not built for periodic scenes; use the direct "
+                "solve (SceneMasks pressure_solver 'auto', 'direct' or 'direct_scattered')", who);
+    SOL_REQUIRE(!io.periodic || (!mc && fy == 0.f && fx == 0.f), "%s: periodic scenes run the plain step only: the mac_cormack advection and the "
+                "buoyancy force are not built for them (use advection = 0 and a zero force)", who);
     const void* outs[] = {io.d_out, io.vy_out, io.vx_out, io.feat_out, saved.vy, saved.vx, sv.cg_info, sv.p_inout};
     const void* ins[] = {io.d_in, io.vy_in, io.vx_in, io.re, io.active, io.inflow, io.velBCy, io.velBCyMask, sv.box_blob};
     for (const void* o : outs)

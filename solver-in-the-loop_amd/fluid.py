@@ -79,7 +79,9 @@ class Domain:
     def __init__(self, resolution, box=None, boundaries=OPEN):
         self.resolution = tuple(int(r) for r in resolution)
         self.box = box if box is not None else Box([0] * len(self.resolution), self.resolution)
-        self.boundaries = boundaries
+        # OPEN, PERIODIC or a pair (by, bx) of them: karman.KarmanFlow runs a periodic axis periodic (ops.boundaries_arg validates it there);
+        # BurgersTest reads the flag as a whole
+        self.boundaries = tuple(boundaries) if isinstance(boundaries, list) else boundaries
 
     @property
     def dx(self):

@@ -76,20 +76,36 @@ def obstacle_spec(obstacles):
     return out
 
 
-def scene_record(obstacles=None, active=None):
+def _with_boundaries(rec, boundaries):
+    """rec plus "boundaries": ("open" | "periodic", "open" | "periodic") -- only when an axis is periodic, so that the record of an open
+    scene stays what it has always been (a record without the key reads as open: record_boundaries)"""
+    if boundaries is not None and any(ops.boundaries_arg(boundaries, "scene_record: boundaries")):
+        rec["boundaries"] = ops.boundaries_name(ops.boundaries_arg(boundaries))
+    return rec
+
+
+def record_boundaries(rec):
+    """The (by, bx) words of a scene record; records written before the key existed are open"""
+    return tuple(rec.get("boundaries", ("open", "open")))
+
+
+def scene_record(obstacles=None, active=None, boundaries=None):
     """Picklable description of a scene (what the scripts store in params.pickle / dataStats.pickle): {"obstacles": canonical spec
-    strings or None, "active": [Y, X] float32 mask or None}.  Neither given: the default sphere."""
+    strings or None, "active": [Y, X] float32 mask or None}.  Neither given: the default sphere.  boundaries (ops.boundaries_arg) with
+    a periodic axis adds "boundaries": (by, bx)."""
     if obstacles is not None and active is not None:
         raise ValueError("give obstacles or an active mask, not both")
     if active is not None:
-        return {"obstacles": None, "active": np.ascontiguousarray(np.asarray(active, dtype=np.float32))}
+        return _with_boundaries({"obstacles": None, "active": np.ascontiguousarray(np.asarray(active, dtype=np.float32))}, boundaries)
     if obstacles is None:
-        return {"obstacles": list(DEFAULT_OBSTACLES), "active": None}
+        return _with_boundaries({"obstacles": list(DEFAULT_OBSTACLES), "active": None}, boundaries)
     obs = parse_obstacles(obstacles) if isinstance(obstacles, str) or (obstacles and isinstance(obstacles[0], str)) else obstacles
-    return {"obstacles": obstacle_spec(obs), "active": None}
+    return _with_boundaries({"obstacles": obstacle_spec(obs), "active": None}, boundaries)
 
 
 def scenes_equal(a, b):
+    if record_boundaries(a) != record_boundaries(b):
+        return False
     if (a["active"] is None) != (b["active"] is None):
         return False
     if a["active"] is not None:
@@ -98,9 +114,11 @@ def scenes_equal(a, b):
 
 
 def describe_scene(rec):
+    by, bx = record_boundaries(rec)
+    tail = "" if (by, bx) == ("open", "open") else "; boundaries y %s, x %s" % (by, bx)
     if rec["active"] is not None:
-        return "mask %dx%d (%d obstacle cells)" % (rec["active"].shape + (int((rec["active"] == 0).sum()),))
-    return ", ".join(rec["obstacles"]) or "none"
+        return "mask %dx%d (%d obstacle cells)" % (rec["active"].shape + (int((rec["active"] == 0).sum()),)) + tail
+    return (", ".join(rec["obstacles"]) or "none") + tail
 
 
 class KarmanFlow:
@@ -113,7 +131,12 @@ class KarmanFlow:
     def __init__(self, pressure_solver=None, make_input_divfree=False, make_output_divfree=True,
                  cg_rtol=1e-6, cg_atol=1e-9, cg_max_iter=2000, grad_pad="replicate", inflow_order="after",
                  obstacles=None, active=None, density_grad=False, re_grad=False, buoyancy=None, buoyancy_factor=None,
-                 gravity=(-9.81, 0.0), diffusion_substeps=1, advection="semi_lagrangian", correction_strength=1.0, multi_launch=False):
+                 gravity=(-9.81, 0.0), diffusion_substeps=1, advection="semi_lagrangian", correction_strength=1.0, multi_launch=False,
+                 boundaries=None):
+        # boundaries: "open", "periodic" or a pair (by, bx) (ops.boundaries_arg); None = the boundaries of the Domain the state given to
+        # step() lives on (fluid.Domain(..., boundaries=)).  A periodic axis runs the multi-launch path with a direct solve
+        # (ops.SceneMasks(boundaries=)); what is not built for periodic scenes raises there or in step(), by name.
+        self._boundaries = None if boundaries is None else ops.boundaries_arg(boundaries, "KarmanFlow: boundaries")
         # multi_launch=True (opt-in): the multi-launch path on every grid with Y, X >= 16 (ops.SceneMasks(multi_launch=True)), so that
         # buoyancy, mac_cormack and "direct_scattered" serve the grids the one-workgroup kernels would take; the default picks as before
         self._multi_launch = bool(multi_launch)
@@ -170,11 +193,18 @@ class KarmanFlow:
         self._cache = {}
         self.solve_info = {}
 
-    def scene(self):
-        """scene_record of this flow's obstacles / mask."""
+    def scene(self, domain=None):
+        """scene_record of this flow's obstacles / mask and boundaries (domain: where boundaries=None takes them from; without it open)."""
+        b = ops.boundaries_name(self.periodic(domain))
         if self.active is not None:
-            return scene_record(active=self.active)
-        return {"obstacles": obstacle_spec(self.obstacles), "active": None}
+            return scene_record(active=self.active, boundaries=b)
+        return _with_boundaries({"obstacles": obstacle_spec(self.obstacles), "active": None}, b)
+
+    def periodic(self, domain=None):
+        """(py, px) this flow runs `domain` with: its own boundaries, else the domain's"""
+        if self._boundaries is not None:
+            return self._boundaries
+        return (False, False) if domain is None else ops.boundaries_arg(getattr(domain, "boundaries", "open"), "Domain: boundaries")
 
     # -- constant masks of the scene for a given domain ----------------------------------
     def scene_arrays(self, domain):
@@ -207,10 +237,11 @@ class KarmanFlow:
     def _masks(self, domain, velBCy, velBCyMask, device):
         # fast path: the same objects as last time (the training loop passes the same two arrays every step)
         last = getattr(self, "_last_masks", None)
-        fast = (domain.resolution, domain.box.lower, domain.box.upper, str(device))
+        periodic = self.periodic(domain)
+        fast = (domain.resolution, domain.box.lower, domain.box.upper, str(device), periodic)
         if last is not None and last[0] is velBCy and last[1] is velBCyMask and last[2] == fast:
             return last[3]
-        key = (domain.resolution, domain.box.lower, domain.box.upper, self._digest(velBCy), self._digest(velBCyMask), str(device), self._multi_launch)
+        key = (domain.resolution, domain.box.lower, domain.box.upper, self._digest(velBCy), self._digest(velBCyMask), str(device), self._multi_launch, periodic)
         if key not in self._cache:
             if len(self._cache) >= 8:                       # bounded: every entry holds device buffers and a solver blob
                 self._cache.pop(next(iter(self._cache)))
@@ -220,7 +251,8 @@ class KarmanFlow:
             bcm = np.asarray(velBCyMask, dtype=np.float64).reshape(-1, Y + 1, X)
             if bcv.shape[0] > 1 and np.all(bcv == bcv[0:1]) and np.all(bcm == bcm[0:1]):
                 bcv, bcm = bcv[0:1], bcm[0:1]
-            self._cache[key] = ops.SceneMasks(active, inflow, bcv, bcm, device, pressure_solver=self._pressure_solver, multi_launch=self._multi_launch)
+            self._cache[key] = ops.SceneMasks(active, inflow, bcv, bcm, device, pressure_solver=self._pressure_solver, multi_launch=self._multi_launch,
+                                               boundaries=ops.boundaries_name(periodic))
         # (holding the two objects keeps their ids from being recycled while they serve as the fast-path key)
         self._last_masks = (velBCy, velBCyMask, fast, self._cache[key])
         return self._cache[key]

@@ -49,6 +49,34 @@ DIRECT_HEADER_FLAGS, DIRECT_ONE_WG = 8, 1
 
 PRESSURE_SOLVERS = ("auto", "direct", "cg", "direct_scattered")
 
+# header flag bits of a direct blob built for periodic axes (precond.PERIODIC_Y / _X, SOL_DIRECT_HDR_PERIODIC_Y / _X): also the
+# `periodic_bits` of karman_seam_sync / karman_seam_fold
+PERIODIC_Y, PERIODIC_X = 2, 4
+BOUNDARIES = ("open", "periodic")
+
+
+def boundaries_arg(b, who="boundaries"):
+    """"open", "periodic" or a pair (by, bx) of those -> (py, px), True for a periodic axis.  One word applies to both axes.  Anything
+    else raises ValueError."""
+    pair = (b, b) if isinstance(b, str) else b
+    try:
+        by, bx = pair
+    except (TypeError, ValueError):
+        raise ValueError("%s must be 'open', 'periodic' or a pair (by, bx) of those (got %r)" % (who, b)) from None
+    for v in (by, bx):
+        if not isinstance(v, str) or v not in BOUNDARIES:
+            raise ValueError("%s must be 'open', 'periodic' or a pair (by, bx) of those (got %r)" % (who, b))
+    return by == "periodic", bx == "periodic"
+
+
+def boundaries_name(periodic):
+    """(py, px) back as the pair of words boundaries_arg takes"""
+    return tuple("periodic" if p else "open" for p in periodic)
+
+
+def periodic_bits(periodic):
+    return PERIODIC_Y * bool(periodic[0]) + PERIODIC_X * bool(periodic[1])
+
 
 def is_direct(pressure_solver):
     """True for the solvers without iteration (SceneMasks.pressure_solver "direct" or "direct_scattered"): capturable, no cg_info."""
@@ -59,9 +87,14 @@ class SceneMasks:
     """Device-resident constant masks of a scene: active (1 - obstacle), inflow rate, velBCy,
     velBCyMask (reference: KarmanFlow.__init__ karman_train.py:166-171 and :366-373)."""
 
-    def __init__(self, active, inflow, velBCy, velBCyMask, device="cuda", precondition=True, pressure_solver="auto", multi_launch=False):
+    def __init__(self, active, inflow, velBCy, velBCyMask, device="cuda", precondition=True, pressure_solver="auto", multi_launch=False,
+                 boundaries="open"):
         """multi_launch=True (opt-in): the multi-launch path (karman_step_large and everything that keys on `large`) on a grid the
-        one-workgroup kernels would serve, any Y, X >= 16 -- what buoyancy, mac_cormack and "direct_scattered" are built on."""
+        one-workgroup kernels would serve, any Y, X >= 16 -- what buoyancy, mac_cormack and "direct_scattered" are built on.
+        boundaries: "open" (default), "periodic" or a pair (by, bx) (boundaries_arg) -> self.periodic = (py, px).  A periodic scene runs
+        the multi-launch path with a direct solve only: its blob carries the axes, and every call that takes the masks follows it."""
+        self.periodic = boundaries_arg(boundaries, "SceneMasks: boundaries")
+        self.periodic_bits = periodic_bits(self.periodic)
         self.active = _lib.f32(active, device)
         self.inflow = _lib.f32(inflow, device)
         self.velBCy = _lib.f32(velBCy, device)
@@ -74,6 +107,9 @@ class SceneMasks:
         if self.multi_launch and (Y < 16 or X < 16):
             raise ValueError("SceneMasks: multi_launch=True takes grids with Y, X >= 16 (the multi-launch kernels); this one is %dx%d" % (Y, X))
         self.large = self.multi_launch or beyond_one_workgroup(Y, X)      # the multi-launch path (karman_step_large)
+        if self.periodic_bits and not self.large:
+            raise ValueError("SceneMasks: periodic boundaries are built on the multi-launch path only; a %dx%d grid runs the fused one-workgroup "
+                             "kernels (not ops.beyond_one_workgroup), which are open on all sides: pass multi_launch=True (Y, X >= 16)" % (Y, X))
         # two-level CG preconditioner (host-prepared dense coarse inverse), when the grid allows it
         self.coarse_inv = None
         if precondition and not os.environ.get("SOL_NO_PRECOND") and not self.large and _lib.load().sol_karman_precond_supported(Y, X):
@@ -86,7 +122,9 @@ class SceneMasks:
         want = os.environ.get("SOL_PRESSURE_SOLVER", pressure_solver)
         if want not in PRESSURE_SOLVERS:
             raise ValueError("pressure_solver must be 'auto', 'direct', 'cg' or 'direct_scattered' (got %r)" % (want,))
-        if want == "direct_scattered":
+        if self.periodic_bits:
+            self._periodic_solver(want, Y, X, device)
+        elif want == "direct_scattered":
             # opt-in: the capacitance solve on the support set's row and column lists (no window), large grids only
             if not self.large:
                 raise ValueError("pressure_solver='direct_scattered' serves the large-grid path only (grids beyond the one-workgroup "
@@ -111,6 +149,8 @@ class SceneMasks:
                     self.direct_header[DIRECT_HEADER_FLAGS] |= DIRECT_ONE_WG
         if want == "direct" and self.direct is None:
             raise ValueError("the direct pressure solver does not support this scene (%dx%d)" % (Y, X))
+        if self.periodic_bits and self.direct_header[0] == 0x46445331:
+            want = "direct_scattered"
         # large grids without a direct blob ("cg", or a scene the blob refuses): the preconditioned CG solve of the large-grid step
         # (sol_karman_step_fwd_large_cg) with the empty-box solve as its preconditioner
         self.box = None
@@ -121,6 +161,29 @@ class SceneMasks:
             self.box = torch.from_numpy(blob).to(device)
             self.box_header = np.ascontiguousarray(blob[:16].view(np.int32))
         self.pressure_solver = want if want == "direct_scattered" else ("direct" if self.direct is not None else "cg")
+
+    def _periodic_solver(self, want, Y, X, device):
+        """The direct blob of a periodic scene: the one-window blob (an empty scene: the box blob with nS = 0) under "auto" / "direct",
+        the scattered blob under "direct_scattered" or where the window refuses (an obstacle across the seam spans the whole axis).
+        There is no CG solve on periodic scenes: "cg" and a scene both blobs refuse raise."""
+        from .precond import direct_solver_blob, scattered_solver_blob
+        if want == "cg":
+            raise ValueError("SceneMasks: pressure_solver='cg' is not built for periodic boundaries; use 'auto', 'direct' or 'direct_scattered'")
+        act = self.active.reshape(Y, X).cpu().numpy()
+        blob = None
+        if want != "direct_scattered":
+            blob = direct_solver_blob(act, max_window=64, periodic=self.periodic)
+        if blob is None and want != "direct":
+            blob = scattered_solver_blob(act, periodic=self.periodic)
+        if blob is None:
+            raise ValueError("SceneMasks: no direct pressure solver takes this periodic scene (%dx%d, pressure_solver=%r): the one-window blob "
+                             "needs the obstacle inside one 64 x 64 window away from the seam, the scattered blob ('direct_scattered') an obstacle "
+                             "with at most 4096 support cells and a well-conditioned capacitance system; periodic scenes have no CG solve to "
+                             "fall back to" % (Y, X, want))
+        self.direct = torch.from_numpy(blob).to(device)
+        self.direct_header = np.ascontiguousarray(blob[:16].view(np.int32)).copy()
+        if self.multi_launch and self.direct_header[0] != 0x46445331 and self.direct_header[5] > 0:
+            self.direct_header[DIRECT_HEADER_FLAGS] |= DIRECT_ONE_WG
 
     def staged_box(self):
         """(box blob, its host header) for the CG solve of the staged adjoint (sol_karman_step_bwd_large*), None for a scene with a
@@ -251,12 +314,19 @@ def _adv_inputs(who, cfg, d, svy, svx, active, inflow):
     return d, svy, svx, active, inflow
 
 
-def karman_advect(d, svy, svx, cfg, active, inflow, advection="semi_lagrangian", correction_strength=1.0, workspace=None):
+def _adv_boundaries(who, boundaries):
+    if any(boundaries_arg(boundaries, "%s: boundaries" % who)):
+        raise SolError("%s: the advection stage alone is not built for periodic boundaries; run the whole step (karman_step_large / "
+                       "karman_step_saved on masks built with boundaries=...), or use boundaries='open'" % who)
+
+
+def karman_advect(d, svy, svx, cfg, active, inflow, advection="semi_lagrangian", correction_strength=1.0, workspace=None, boundaries="open"):
     """The advection stage of the large-grid step alone (sol_karman_advect; any Y, X >= 16): (d, svy, svx) -- the density and the
     post-diffusion velocity -- -> (d_out, a_y, a_x): the advected density (+ inflow as cfg.inflow_before says) and the advected velocity
     times the hard-BC face masks of `active` [Y,X].  advection = "mac_cormack": the MacCormack scheme with the revert-to-semi-Lagrangian
     limiter (form selected by the option k2d_mc_tile, equal bits)."""
     s = advection_arg(advection, correction_strength, "karman_advect: advection")
+    _adv_boundaries("karman_advect", boundaries)
     _adv_grid(cfg, "karman_advect")
     _lib.require_gpu()
     lib = _lib.load()
@@ -270,11 +340,12 @@ def karman_advect(d, svy, svx, cfg, active, inflow, advection="semi_lagrangian",
 
 
 def karman_advect_bwd(d, svy, svx, cfg, active, inflow, g_d, g_ay, g_ax, advection="semi_lagrangian", correction_strength=1.0,
-                      tile=True, workspace=None):
+                      tile=True, workspace=None, boundaries="open"):
     """The transpose of karman_advect (sol_karman_advect_bwd): the cotangents of (d_out, a_y, a_x) -> (g_d_in, g_svy, g_svx), every
     decision of the forward stage (floor, clamp, limiter) frozen.  64-bit fixed-point scatter: bit-reproducible; tile=False takes global
     atomics only (equal bits).  A non-finite cotangent makes every gradient of its simulation NaN."""
     s = advection_arg(advection, correction_strength, "karman_advect_bwd: advection")
+    _adv_boundaries("karman_advect_bwd", boundaries)
     _adv_grid(cfg, "karman_advect_bwd")
     _lib.require_gpu()
     lib = _lib.load()
@@ -361,6 +432,10 @@ class StepPhysics(NamedTuple):
         f = buoyancy_force(buoyancy, buoyancy_factor, gravity)
         return cls(f if keep_zero_force or _buoyant(f) else None, n, adv)
 
+    def on(self, masks):
+        """self as the launches of `masks` take it: a periodic scene has no buoyant entry points, a kept force of (0, 0) becomes None there"""
+        return self.moving() if getattr(masks, "periodic_bits", 0) else self
+
     def moving(self):
         """self, a kept force of (0, 0) normalised to None: what a differentiable step runs on"""
         return self if self.buoyancy is None or _buoyant(self.buoyancy) else self._replace(buoyancy=None)
@@ -370,6 +445,15 @@ class StepPhysics(NamedTuple):
         are built on the large-grid step only (masks.large)."""
         if self.nsub > 1:
             _require_sub_grid(cfg, who)
+        if getattr(masks, "periodic_bits", 0):
+            if _buoyant(self.buoyancy):
+                raise SolError("%s: a buoyancy force is not built for periodic boundaries; use buoyancy=None on a periodic scene, or open boundaries" % who)
+            if self.adv is not None:
+                raise SolError("%s: advection='mac_cormack' is not built for periodic boundaries; use advection='semi_lagrangian' on a periodic "
+                               "scene, or open boundaries" % who)
+            if self.nsub > 1:
+                raise SolError("%s: diffusion_substeps > 1 is not built for periodic boundaries; use diffusion_substeps=1 on a periodic scene, "
+                               "or open boundaries" % who)
         if self.buoyancy is not None and not masks.large:
             raise SolError("%s: the buoyancy force is built on the multi-launch (large-grid) step only; a %dx%d grid runs the fused "
                            "one-workgroup kernels (not ops.beyond_one_workgroup), which have no buoyancy term.  Masks built with "
@@ -493,6 +577,16 @@ def _fwd_large(head, cfg, masks, ph, workspace, info, saved=None, feat=None, fs=
     _publish_cg(info, cg_info)
 
 
+def _refuse_periodic_grads(who, masks, density_grad, re_grad):
+    """density_grad and re_grad on a periodic scene: not built (SolError), whatever requires a gradient"""
+    if getattr(masks, "periodic_bits", 0):
+        if density_grad:
+            raise SolError("%s: density_grad is not built for periodic boundaries; use density_grad=False (the density is a passive tracer "
+                           "there), or open boundaries" % who)
+        if re_grad:
+            raise SolError("%s: re_grad is not built for periodic boundaries; use re_grad=False (re is data there), or open boundaries" % who)
+
+
 def karman_step_saved(d, vy, vx, re, cfg, masks, workspace=None, info=None, buoyancy=None, diffusion_substeps=1,
                       advection="semi_lagrangian", correction_strength=1.0, physics=None):
     """The differentiable form of the step without autograd, on any grid: ((d, vy, vx) after the step, saved vy, saved vx) -- the
@@ -502,6 +596,7 @@ def karman_step_saved(d, vy, vx, re, cfg, masks, workspace=None, info=None, buoy
     ph = _physics(physics, "karman_step_saved", buoyancy=buoyancy, diffusion_substeps=diffusion_substeps, advection=advection,
                   correction_strength=correction_strength, keep_zero_force=True)
     ph.require(cfg, masks, "karman_step_saved")
+    ph = ph.on(masks)
     _lib.require_gpu()
     d, vy, vx, re = (_lib.f32(t) for t in (d, vy, vx, re))
     B, Y, X = cfg.B, cfg.Y, cfg.X
@@ -544,6 +639,8 @@ def karman_step_large(d, vy, vx, re, cfg, masks, workspace=None, info=None, feat
     ph = _physics(physics, "karman_step_large", buoyancy=buoyancy, diffusion_substeps=diffusion_substeps, advection=advection,
                   correction_strength=correction_strength, keep_zero_force=True)
     ph.require(cfg, masks, "karman_step_large")
+    ph = ph.on(masks)
+    _refuse_periodic_grads("karman_step_large", masks, density_grad, re_grad)
     if p_guess is not None and masks.direct is not None:
         raise ValueError("karman_step_large: p_guess warm-starts the CG pressure solve; this scene runs the direct solver (no iteration to start)")
     differentiable, density, want_re = _step_mode(d, vy, vx, re, cfg, density_grad, re_grad, ph)
@@ -586,6 +683,43 @@ def karman_correct(out, vy, vx, s, cor=None):
     if cor is not None and (cy.shape != vy.shape or cx.shape != vx.shape):
         raise ValueError("karman_correct: cor must be (cor_y, cor_x) of the velocity's shapes")
     check(_lib.load().sol_karman_correct(stream(), ptr(out), ptr(vy), ptr(vx), ptr(cy), ptr(cx), B, Y, X, float(s[0]), float(s[1])))
+
+
+def _seam(name, vy, vx, periodic):
+    _lib.require_gpu()
+    bits = periodic if isinstance(periodic, (int, np.integer)) and not isinstance(periodic, bool) else periodic_bits(periodic)
+    B, Y, X = vx.shape[0], vx.shape[1], vy.shape[2]
+    if vy.shape != (B, Y + 1, X) or vx.shape != (B, Y, X + 1) or vy.dtype != torch.float32 or vx.dtype != torch.float32 or \
+            not (vy.is_contiguous() and vx.is_contiguous()):
+        raise ValueError("%s: vy %s, vx %s must be contiguous float32 [B,Y+1,X], [B,Y,X+1]" % (name, tuple(vy.shape), tuple(vx.shape)))
+    check(getattr(_lib.load(), "sol_" + name)(stream(), ptr(vy), ptr(vx), B, Y, X, int(bits)))
+    return vy, vx
+
+
+def karman_seam_sync(vy, vx, periodic):
+    """In place: plane 0 copied onto the duplicate plane of a periodic axis (sol_karman_seam_sync) -- vy[:, Y, :] = vy[:, 0, :] when y is
+    periodic, vx[:, :, X] = vx[:, :, 0] when x is.  periodic: (py, px) (SceneMasks.periodic) or the bits.  What follows karman_correct
+    on a periodic scene, which leaves the duplicate plane stale.  Open scenes: nothing is launched."""
+    return _seam("karman_seam_sync", vy, vx, periodic)
+
+
+def karman_seam_fold(g_vy, g_vx, periodic):
+    """In place, the adjoint of karman_seam_sync on a cotangent (sol_karman_seam_fold): g[plane 0] += g[duplicate], g[duplicate] = 0."""
+    return _seam("karman_seam_fold", g_vy, g_vx, periodic)
+
+
+class SeamSyncFn(torch.autograd.Function):
+    """karman_seam_sync for autograd compositions (out of place): (vy, vx) -> copies with the duplicate planes equal to plane 0; backward
+    = karman_seam_fold on copies of the cotangents"""
+
+    @staticmethod
+    def forward(ctx, vy, vx, bits):
+        ctx.bits = int(bits)
+        return karman_seam_sync(_lib.f32(vy).clone(), _lib.f32(vx).clone(), ctx.bits)
+
+    @staticmethod
+    def backward(ctx, gy, gx):
+        return karman_seam_fold(_lib.f32(gy).contiguous().clone(), _lib.f32(gx).contiguous().clone(), ctx.bits) + (None,)
 
 
 def pressure_solve_large(rhs, cfg, masks, workspace=None, info=None):
@@ -825,6 +959,8 @@ def _step_adjoint(who, d, svy, svx, re, gd, gvy, gvx, cfg, masks, ph, density, v
       (M^(n-1) is symmetric) and g_re is multiplied by n, once (_sub_adjoint).
     `info` receives "iterations_bwd" / "converged_bwd"; workspace / density_workspace: scratch of the two halves; fused: see _velocity_bwd."""
     ph.require(cfg, masks, who)
+    ph = ph.on(masks)
+    _refuse_periodic_grads(who, masks, density, vel_in is not None)
     gd = gd if density else None
     od = oy = ox = None
     if gvy is None and gvx is None and gd is None:
@@ -872,6 +1008,7 @@ class KarmanStepFn(torch.autograd.Function):
         _lib.require_gpu()
         d, vy, vx, re = (_lib.f32(t) for t in (d, vy, vx, re))
         density = bool(density) or physics.buoyancy is not None
+        _refuse_periodic_grads("KarmanStepFn", masks, density, want_re)
         ctx.cfg, ctx.masks, ctx.info, ctx.density, ctx.want_re, ctx.physics = cfg, masks, info, density, want_re, physics
         # under substeps the pre-diffused velocity M^(nsub-1) v is also the "input velocity" the re mode saves
         vy, vx, cfg = _pre_diffuse(vy, vx, re, cfg, physics.nsub)
@@ -909,6 +1046,7 @@ def karman_step(d, vy, vx, re, cfg, masks, info=None, density_grad=False, re_gra
     diffusion_substeps = n > 1 (grids with Y, X >= 16): karman_diffuse_sub, then the fused kernel on diffusion_sub_cfg(cfg, n)."""
     ph = _physics(physics, "karman_step", diffusion_substeps=diffusion_substeps)
     ph.require(cfg, masks, "karman_step")
+    _refuse_periodic_grads("karman_step", masks, density_grad, re_grad)
     differentiable, density, want_re = _step_mode(d, vy, vx, re, cfg, density_grad, re_grad)
     if not differentiable:
         return karman_step_saved(d, vy, vx, re, cfg, masks, None, info, physics=ph)[0]

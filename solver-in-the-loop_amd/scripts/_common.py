@@ -166,13 +166,53 @@ def agreed_substeps(recorded, flag, where):
 
 
 def flow_kwargs(rec):
-    """KarmanFlow / GraphTrainer keywords of a scene_record (None: the default scene)."""
+    """KarmanFlow / GraphTrainer keywords of a scene_record (None: the default scene); a record with periodic boundaries adds them."""
     from sol_amd import karman
     if rec is None:
         return {}
+    kw = {"boundaries": tuple(rec["boundaries"])} if "boundaries" in rec else {}
     if rec["active"] is not None:
-        return {"active": rec["active"]}
-    return {"obstacles": karman.parse_obstacles(rec["obstacles"]) if rec["obstacles"] else []}
+        return dict(kw, active=rec["active"])
+    return dict(kw, obstacles=karman.parse_obstacles(rec["obstacles"]) if rec["obstacles"] else [])
+
+
+BOUNDARIES = {"open": ("open", "open"), "periodic-x": ("open", "periodic")}
+
+
+def add_boundaries_arg(p):
+    """--boundaries open|periodic-x of karman.py: periodic lateral sides (the x axis wraps; the multi-launch path with a direct solve).
+    Recorded in params.pickle ("boundaries", and inside "scene"); the scripts that read data take it from the scene record."""
+    p.add_argument("--boundaries", default=None, choices=sorted(BOUNDARIES),
+                   help="domain boundaries: open on all sides, or periodic along x (needs the multi-launch path: -r 128, or --multi-launch).  "
+                        "Stored with the data like the scene; absent: open")
+
+
+def with_boundaries(rec, params):
+    """The scene record with the --boundaries flag applied (None stays None while the flag is absent or open)"""
+    from sol_amd import karman
+    b = BOUNDARIES[params.get("boundaries") or "open"]
+    if b == ("open", "open"):
+        return rec
+    rec = dict(rec) if rec is not None else karman.scene_record()
+    rec["boundaries"] = b
+    return rec
+
+
+def inherit_boundaries(rec, recorded):
+    """A scene given by flags (which carry no boundaries) takes those of the recorded scene before the two are compared"""
+    if rec is not None and recorded is not None and "boundaries" in recorded and "boundaries" not in rec:
+        rec = dict(rec, boundaries=recorded["boundaries"])
+    return rec
+
+
+def boundaries_name(rec):
+    """"open" or "periodic-x" of a scene record (None: open), as the scripts record it beside the scene"""
+    from sol_amd import karman
+    b = karman.record_boundaries(rec or {})
+    for name, pair in BOUNDARIES.items():
+        if tuple(b) == pair:
+            return name
+    return "%s,%s" % tuple(b)
 
 
 def select_gpu(gpu):

@@ -17,7 +17,7 @@ import pickle
 import numpy as np
 import torch
 
-from _common import (add_advection_arg, add_buoyancy_arg, add_multi_launch_arg, add_scene_args, add_substeps_arg, advection_from_args, buoyancy_from_args, flow_kwargs,
+from _common import (add_boundaries_arg, with_boundaries, add_advection_arg, add_buoyancy_arg, add_multi_launch_arg, add_scene_args, add_substeps_arg, advection_from_args, buoyancy_from_args, flow_kwargs,
                      logger, scene_from_args, select_gpu, substeps_from_args)
 import sol_amd
 from sol_amd import ops, scene
@@ -43,13 +43,15 @@ def main(argv=None):
     add_substeps_arg(p)
     add_advection_arg(p)
     add_multi_launch_arg(p)
+    add_boundaries_arg(p)
     params = vars(p.parse_args(argv))
     select_gpu(params["gpu"])
     log = logger()
     res = params["res"]
     Y, X = 2 * res, res
     dom = sol_amd.Domain([Y, X], box=sol_amd.box[0:params["len"] * 2, 0:params["len"]])
-    rec = scene_from_args(params)
+    rec = with_boundaries(scene_from_args(params), params)
+    params["boundaries"] = params["boundaries"] or "open"
     params["buoyancy"] = buoyancy_from_args(params)
     params["diffusion_substeps"] = substeps_from_args(params, [params["re"]], res) or 1
     name, strength = advection_from_args(params)

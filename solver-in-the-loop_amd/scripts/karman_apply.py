@@ -9,7 +9,7 @@ import pickle
 import numpy as np
 import torch
 
-from _common import (add_advection_arg, add_multi_launch_arg, advection_from_args, agreed_advection, agreed_multi_launch, add_buoyancy_arg, add_scene_args, add_substeps_arg, agreed_buoyancy, agreed_substeps, buoyancy_from_args, flow_kwargs, logger,
+from _common import (inherit_boundaries, add_advection_arg, add_multi_launch_arg, advection_from_args, agreed_advection, agreed_multi_launch, add_buoyancy_arg, add_scene_args, add_substeps_arg, agreed_buoyancy, agreed_substeps, buoyancy_from_args, flow_kwargs, logger,
                      scene_from_args, select_gpu, substeps_from_args)
 import sol_amd
 from sol_amd import ops, scene
@@ -60,6 +60,7 @@ def main(argv=None):
     # the scene: the one the model was trained on (dataStats "scene"), else the flags, else the reference's sphere
     rec = data_stats.get("scene")
     flags = scene_from_args(params)
+    flags = inherit_boundaries(flags, rec)
     if rec is not None and flags is not None and not sol_amd.karman.scenes_equal(rec, flags):
         log.info("--obstacle / --obstacle-mask ignored: the model was trained on the scene of %s" % params["stats"])
     rec = rec if rec is not None else flags
@@ -84,7 +85,8 @@ def main(argv=None):
     active, inflow = sim.scene_arrays(dom)
     velBCy, velBCyMask = sol_amd.velocity_bc_masks(Y, X)
     masks = ops.SceneMasks(active, inflow, velBCy.reshape(Y + 1, X), velBCyMask.reshape(Y + 1, X),
-                           pressure_solver=params["pressure_solver"], multi_launch=multi_launch)
+                           pressure_solver=params["pressure_solver"], multi_launch=multi_launch,
+                           boundaries=sol_amd.karman.record_boundaries(rec or {}))
     log.info("pressure solver: %s" % masks.pressure_solver)
     large = masks.large
     warm = bool(params["cg_warm_start"]) and large and masks.pressure_solver == "cg"

@@ -107,7 +107,7 @@ def main(argv=None):
         with open(os.path.join(params["input"], "params.pickle"), "rb") as fh:
             meta = pickle.load(fh)
         res, length, B = meta["res"], meta.get("len", 100), 1
-        rec = rec if rec is not None else meta.get("scene")
+        rec = rec if rec is not None else meta.get("scene")      # (periodic boundaries travel in the record: KarmanFlow refuses re_grad on them, by name)
         nsub = agreed_substeps(meta.get("diffusion_substeps"), substeps_from_args(params), "params.pickle")      # the count the frames were generated with
         advection = agreed_advection(meta, advection_from_args(params), "params.pickle")      # the scheme the frames were generated with
         multi_launch = agreed_multi_launch(meta.get("multi_launch"), params["multi_launch"])      # the path the frames were generated on

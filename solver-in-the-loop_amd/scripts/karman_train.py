@@ -17,7 +17,7 @@ import time
 import numpy as np
 import torch
 
-from _common import (add_advection_arg, add_multi_launch_arg, advection_from_args, agreed_advection, agreed_multi_launch, add_buoyancy_arg, add_scene_args, add_substeps_arg, agreed_buoyancy, agreed_substeps, buoyancy_from_args, flow_kwargs, logger,
+from _common import (boundaries_name, inherit_boundaries, add_advection_arg, add_multi_launch_arg, advection_from_args, agreed_advection, agreed_multi_launch, add_buoyancy_arg, add_scene_args, add_substeps_arg, agreed_buoyancy, agreed_substeps, buoyancy_from_args, flow_kwargs, logger,
                      scene_from_args, select_gpu, substeps_from_args)
 import sol_amd
 from sol_amd import ops, scene
@@ -96,7 +96,7 @@ def main(argv=None):
             raise SystemExit("the simulations of the training set disagree on the scene: %s has %s, others %s"
                              % (s, sol_amd.karman.describe_scene(r), sol_amd.karman.describe_scene(rec_set)))
         rec_set = r
-    rec = scene_from_args(params)
+    rec = inherit_boundaries(scene_from_args(params), rec_set)
     if rec is not None and rec_set is not None and not sol_amd.karman.scenes_equal(rec, rec_set):
         raise SystemExit("--obstacle / --obstacle-mask (%s) contradict the scene of the training set (%s)"
                          % (sol_amd.karman.describe_scene(rec), sol_amd.karman.describe_scene(rec_set)))
@@ -137,7 +137,8 @@ def main(argv=None):
     active, inflow = simulator_lo.scene_arrays(dom)
     velBCy, velBCyMask = sol_amd.velocity_bc_masks(Y, X)
     masks = ops.SceneMasks(active, inflow, velBCy.reshape(Y + 1, X), velBCyMask.reshape(Y + 1, X), dev,
-                           pressure_solver=params["pressure_solver"], multi_launch=multi_launch)
+                           pressure_solver=params["pressure_solver"], multi_launch=multi_launch,
+                           boundaries=sol_amd.karman.record_boundaries(rec or {}))
     log.info("pressure solver: %s" % masks.pressure_solver)
     # eval('model_'+params['model']) (karman_train.py:394): mars_moon runs the C++ schedule (SolTrainer), mercury the
     # hand-written schedule captured into a hipGraph (GraphTrainer); a domain beyond the one-workgroup grids (-s 1 on a -r 128 set):
@@ -153,6 +154,7 @@ def main(argv=None):
         model.set_weights(sol_amd.ConvNet.load(params["inittf"], device="cpu").get_weights())
     os.makedirs(params["tf"], exist_ok=True)
     dataset.dataStats.setdefault("scene", rec)
+    dataset.dataStats.setdefault("boundaries", boundaries_name(rec))
     dataset.dataStats.setdefault("buoyancy", buoyancy)
     dataset.dataStats.setdefault("diffusion_substeps", nsub)
     dataset.dataStats.setdefault("advection", advection["advection"])

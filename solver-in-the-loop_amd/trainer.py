@@ -12,6 +12,7 @@ gradient over RCCL (the loss is a batch SUM, karman_train.py:430, so summed shar
 equal the large-batch gradient) and an identical Adam update on every rank.
 """
 import ctypes as C
+import types
 
 import torch
 
@@ -116,6 +117,15 @@ def _refuse_substeps(who, diffusion_substeps, Y, X):
     return 1
 
 
+def _refuse_periodic(who, masks, use):
+    """SolTrainer, GraphTrainer and SolRollout run the fused one-workgroup solver kernels, which are open on all sides: masks built with
+    periodic boundaries are refused at construction.  use: the class that serves them."""
+    if getattr(masks, "periodic_bits", 0):
+        raise ValueError("%s: the masks were built with periodic boundaries %r -- periodic scenes run the multi-launch solver pair only; this "
+                         "class runs the fused one-workgroup kernels.  Use %s (multi_launch=True on a grid the one-workgroup kernels would "
+                         "serve)" % (who, ops.boundaries_name(masks.periodic), use))
+
+
 def _train_cfg(kc, msteps, net, std_v, std_re, in_std_v, out_std_v):
     """TrainCfg with its normalisation fields.  --pretf (karman_train.py:351-355,416-421): separate input / output normalisation of a
     pre-trained supervised model; 0.0 pairs stand for "as std_v"."""
@@ -191,6 +201,7 @@ class SolTrainer(_AdamDP):
         _refuse_buoyancy("SolTrainer", buoyancy)
         _refuse_substeps("SolTrainer", diffusion_substeps, Y, X)
         _refuse_advection("SolTrainer", advection, correction_strength)
+        _refuse_periodic("SolTrainer", masks, "LargeGridTrainer")
         _lib.require_gpu()
         self.lib = _lib.load()
         self.conv_precision = _conv_precision_code(conv_precision)
@@ -301,6 +312,7 @@ class SolRollout:
                  conv_precision="split", diffusion_substeps=1, advection="semi_lagrangian", correction_strength=1.0, **solver):
         _refuse_substeps("SolRollout", diffusion_substeps, Y, X)
         _refuse_advection("SolRollout", advection, correction_strength)
+        _refuse_periodic("SolRollout", masks, "LargeGridRollout")
         _lib.require_gpu()
         self.lib = _lib.load()
         self.conv_precision = _conv_precision_code(conv_precision)
@@ -361,6 +373,14 @@ class LargeGridRollout:
         if not _width_served(Y, X, any_width, self.multi_launch):
             raise ValueError("LargeGridRollout: the convolutions of a large domain take rows of X %% 64 == 0 cells (got %dx%d); "
                              "no roll-out class serves this grid (KarmanFlow.step advances it without the network)" % (Y, X))
+        # periodic masks (SceneMasks(boundaries=...)): the plain physics, a direct solve; the correction leaves the duplicate plane of a
+        # periodic axis stale, so the step runs the seam sync after it (captured with the rest)
+        self._periodic_bits = int(getattr(masks, "periodic_bits", 0))
+        if self._periodic_bits:
+            ph.require(types.SimpleNamespace(Y=Y, X=X), masks, "LargeGridRollout")
+            if cg_warm_start:
+                raise ValueError("LargeGridRollout: cg_warm_start=True on a periodic scene -- periodic scenes have no CG solve to warm-start "
+                                 "(they run a direct solve); pass cg_warm_start=False")
         cg = masks.pressure_solver == "cg"
         if cg and use_graph:
             raise ValueError("LargeGridRollout: use_graph=True on a scene with the CG pressure solve -- the iteration count of a solve is "
@@ -405,6 +425,8 @@ class LargeGridRollout:
                               p_guess=self.p_guess, out=self._b, physics=self.physics)
         out, _ = self._sched.forward(self._feat)
         ops.karman_correct(out, self._b[1], self._b[2], self._so, self._cor)
+        if self._periodic_bits:
+            ops.karman_seam_sync(self._b[1], self._b[2], self._periodic_bits)
         _lib.dcopy_(self._flat[0], self._flat[1])
         self._info.append(info)
 
@@ -478,8 +500,10 @@ class GraphTrainer(_AdamDP):
                  group=None, use_graph=True, comm=None, in_std_v=None, out_std_v=None, pressure_solver=None,
                  dx=None, dt=1.0, masks=None, cg_rtol=1e-6, cg_atol=1e-9, cg_max_iter=2000, grad_pad="replicate",
                  inflow_order="after", conv_precision="split", schedule="manual", obstacles=None, active=None,
-                 buoyancy=None, diffusion_substeps=1, advection="semi_lagrangian", correction_strength=1.0):
-        """dx: cell size (default 100 / X, the reference's `--len 100`); the domain is box[0:Y*dx, 0:X*dx] as the scripts
+                 buoyancy=None, diffusion_substeps=1, advection="semi_lagrangian", correction_strength=1.0, boundaries=None):
+        """boundaries: "open" | "periodic" | (by, bx) (ops.boundaries_arg); None = those of `masks`, open without masks.  Periodic
+        boundaries are LargeGridTrainer's (this class refuses them).
+        dx: cell size (default 100 / X, the reference's `--len 100`); the domain is box[0:Y*dx, 0:X*dx] as the scripts
         build it (karman_train.py:363: box[0:len*2, 0:len]).  obstacles / active: the scene of KarmanFlow (default: the reference's
         sphere).  masks: optional SceneMasks of the caller -- its boundary arrays are used; its scene must be the one KarmanFlow
         derives from the domain and the obstacles (checked).  The solver options are those of SolTrainer and are forwarded to
@@ -490,9 +514,17 @@ class GraphTrainer(_AdamDP):
         self._sched = None
         self._cg_fwd, self._cg_bwd = [], []       # what the solver launches of a step report (LargeGridTrainer, CG scenes)
         self._check_grid(Y, X)
+        periodic = getattr(masks, "periodic", (False, False)) if boundaries is None else ops.boundaries_arg(boundaries, "trainer: boundaries")
+        if masks is not None and tuple(getattr(masks, "periodic", (False, False))) != tuple(periodic):
+            raise ValueError("trainer: boundaries=%r, but the masks were built with boundaries=%r; build both with the same boundaries"
+                             % (boundaries, ops.boundaries_name(getattr(masks, "periodic", (False, False)))))
+        self._periodic_bits = ops.periodic_bits(periodic)
+        self._check_boundaries(periodic, pressure_solver)
         ph = self.physics = self._check_physics(Y, X, buoyancy=buoyancy, diffusion_substeps=diffusion_substeps, advection=advection,
                                                 correction_strength=correction_strength)
         self.buoyancy, self.diffusion_substeps, self.advection = ph.buoyancy, ph.nsub, ph.advection_kw
+        if self._periodic_bits:                 # what is not built for periodic scenes is refused here, by name
+            ph.require(types.SimpleNamespace(Y=Y, X=X), types.SimpleNamespace(periodic_bits=self._periodic_bits, large=True), type(self).__name__)
         from . import fluid, karman
         _lib.require_gpu()
         self.lib = _lib.load()
@@ -503,7 +535,8 @@ class GraphTrainer(_AdamDP):
         self.dt = float(dt)
         self.dom = fluid.Domain([Y, X], box=fluid.box[0:Y * dx, 0:X * dx])
         self.sim = karman.KarmanFlow(pressure_solver=pressure_solver, cg_rtol=cg_rtol, cg_atol=cg_atol, cg_max_iter=cg_max_iter,
-                                     grad_pad=grad_pad, inflow_order=inflow_order, obstacles=obstacles, active=active)
+                                     grad_pad=grad_pad, inflow_order=inflow_order, obstacles=obstacles, active=active,
+                                     boundaries=ops.boundaries_name(periodic))
         self.res = X if res is None else res
         if masks is not None:
             import numpy as np
@@ -532,6 +565,9 @@ class GraphTrainer(_AdamDP):
     @staticmethod
     def _check_grid(Y, X):
         _refuse_large_grid("GraphTrainer", Y, X)
+
+    def _check_boundaries(self, periodic, pressure_solver):
+        _refuse_periodic("GraphTrainer", types.SimpleNamespace(periodic_bits=ops.periodic_bits(periodic), periodic=periodic), "LargeGridTrainer")
 
     @staticmethod
     def _check_physics(Y, X, buoyancy, diffusion_substeps, advection, correction_strength):
@@ -570,6 +606,8 @@ class GraphTrainer(_AdamDP):
             out, state = sch.forward(feat)
             vy2[:, :Y].add_(out[..., 0], alpha=so[0])             # to_staggered + add (karman_train.py:88-90, 424-426): the last row / column gets no correction
             vx2[:, :, :X].add_(out[..., 1], alpha=so[1])
+            if self._periodic_bits:                               # the correction left the duplicate plane stale: the loss and the next step see a consistent field
+                ops.karman_seam_sync(vy2, vx2, self._periodic_bits)
             li, gi = ops.l2_loss_fwd_bwd((vy2, vx2), (gt_vy[i], gt_vx[i]), sl, gscale=1.0 / ms)
             losses.append(li.reshape(()))
             keep.append((svy, svx, state, gi))
@@ -580,6 +618,8 @@ class GraphTrainer(_AdamDP):
             if gin is not None:
                 G[0].add_(gin[0])
                 G[1].add_(gin[1])
+            if self._periodic_bits:                               # the seam sync's adjoint: the duplicate plane's cotangent reaches plane 0
+                ops.karman_seam_fold(G[0], G[1], self._periodic_bits)
             dO = torch.stack([G[0][:, :Y] * so[0], G[1][:, :, :X] * so[1]], dim=-1)
             dfeat = sch.backward(state, dO)
             keep[i] = None
@@ -727,6 +767,11 @@ class LargeGridTrainer(GraphTrainer):
 
     _adjoint_of_first_step = False
 
+    def _check_boundaries(self, periodic, pressure_solver):
+        """periodic boundaries: served (the seam sync / fold in the schedule); without a CG solve"""
+        if any(periodic) and pressure_solver == "cg":
+            raise ValueError("LargeGridTrainer: pressure_solver='cg' is not built for periodic boundaries; use 'auto', 'direct' or 'direct_scattered'")
+
     @staticmethod
     def _check_physics(Y, X, **keywords):
         return ops.StepPhysics.of(who="LargeGridTrainer", **keywords)
@@ -791,7 +836,7 @@ def make_trainer(net, masks, B, Y, X, msteps, dx, std_v, std_re, **kw):
     if net.name == "mars_moon":
         # the C++ schedule takes its scene and its pressure solver from `masks` alone (obstacles / active / pressure_solver
         # describe them for GraphTrainer's KarmanFlow)
-        for k in ("obstacles", "active", "pressure_solver", "any_width"):
+        for k in ("obstacles", "active", "pressure_solver", "any_width", "boundaries"):      # (periodic masks: SolTrainer refuses them itself)
             kw.pop(k, None)
         kw["diffusion_substeps"] = _refuse_substeps("make_trainer", kw.get("diffusion_substeps", 1), Y, X)
         _refuse_advection("make_trainer", kw.get("advection", "semi_lagrangian"), kw.get("correction_strength", 1.0))
