@@ -1123,6 +1123,27 @@ int sol_karman3d_density_bwd_adv_re(const sol_karman3d_cfg* cfg, void* stream,
                                     void* workspace, size_t workspace_bytes,
                                     const float* vy_in, const float* vx_in, const float* vz_in, float* g_re, int accumulate_re,
                                     int32_t advection, float correction_strength);
+/* PERIODIC SPANWISE BOUNDARIES on the karman-3d step (csrc/karman3d_periodic.hip; Scene3D(boundaries="periodic-z") on the Python
+ * surface): the text of "PERIODIC BOUNDARIES" above with z as the axis.  A direct blob built periodic (precond3d.periodic_solver_blob3d,
+ * layout "FD33"; precond3d.extruded_solver_blob3d(periodic=True), layout "FD3E") carries the axes in header word 6: SOL_K3_PERIODIC_Z = 8;
+ * 2 and 4 are reserved for y and x and refused.  sol_karman3d_cfg is unchanged; with the word clear every entry issues the launches it
+ * always did.
+ *   Array shapes do not change: v_z [B,Y,X,Z+1], and plane Z is a DUPLICATE of plane 0.  It is never read on input (a NaN there changes
+ *   nothing) and is written equal to plane 0, bit for bit, in vz_out and saved_vz; the adjoint first adds the cotangent of the output
+ *   duplicate plane onto plane 0's (one fp32 add) and returns g_vz_in[..., Z] = 0 exactly.
+ *   Every z index wraps modulo the Z unique planes (a true modulo: a departure point several periods away lands on its plane): the
+ *   Laplacian, the four-face averages of the advecting velocity, the trilinear gathers of the three components and of the density, the
+ *   accessible mask, the divergence and the pressure gradient along z, which has no boundary face (grad_pad is not read there).  floorf
+ *   and the weights are the open kernels'; y and x keep clamp, velBC blend, grad_pad and the zero ghost ring.
+ *   The pressure solve runs the open step's launches on the blob's tables (Q_z = the Hartley matrix, eigenvalues 2 - 2 cos(2 pi m / Z)).
+ *   The z-constant mode is held down by the open y and x axes: the system is non-singular.
+ * sol_karman3d_step_fwd, sol_karman3d_step_bwd and sol_karman3d_pressure_solve dispatch on the word.  On a periodic blob
+ * pressure_solver = 1 (CG) and the _buoy, _adv and _re forms return SOL_ERR_ARG with a message.
+ * sol_karman3d_seam_sync: v_z[..., Z] = v_z[..., 0] (after a correction that leaves the duplicate plane behind).  sol_karman3d_seam_fold,
+ * its adjoint: g[..., 0] += g[..., Z], then g[..., Z] = 0.  periodic_bits = 0: nothing is launched; 2 or 4: SOL_ERR_ARG. */
+#define SOL_K3_PERIODIC_Z 8
+int sol_karman3d_seam_sync(void* stream, float* vz, int32_t B, int32_t Y, int32_t X, int32_t Z, int32_t periodic_bits);
+int sol_karman3d_seam_fold(void* stream, float* g_vz, int32_t B, int32_t Y, int32_t X, int32_t Z, int32_t periodic_bits);
 /* The step's pressure solve alone: M p = rhs with M = -A for the scene's `active` mask (the solver cfg->pressure_solver selects;
  * the CG solve reports to cfg->cg_info).  rhs, p [B,Y,X,Z] (rhs is read only); workspace: sol_karman3d_step_workspace_bytes(cfg). */
 int sol_karman3d_pressure_solve(const sol_karman3d_cfg* cfg, void* stream, const float* active, const float* rhs, float* p,

@@ -194,6 +194,8 @@ _SIGS = {
     "sol_karman3d_diffuse_sub_workspace_bytes": (C.c_size_t, [C.POINTER(Karman3DCfg), C.c_int32, C.c_int32]),
     "sol_karman3d_diffuse_sub": (C.c_int, [C.POINTER(Karman3DCfg), _P] + [_P] * 7 + [C.c_int32] * 2 + [_P, C.c_size_t]),
     "sol_karman3d_pressure_solve": (C.c_int, [C.POINTER(Karman3DCfg), _P, _P, _P, _P, _P, _P, C.c_size_t]),
+    "sol_karman3d_seam_sync": (C.c_int, [_P] * 2 + [C.c_int32] * 5),
+    "sol_karman3d_seam_fold": (C.c_int, [_P] * 2 + [C.c_int32] * 5),
     "sol_karman3d_correct": (C.c_int, [_P, _P, C.c_int32] + [C.c_float] * 3 + [_P] * 3 + [C.c_int32] * 4),
     "sol_karman3d_correct_bwd": (C.c_int, [_P] * 7 + [C.c_float] * 3 + [_P] + [C.c_int32] * 4),
     "sol_karman3d_feature_bwd": (C.c_int, [_P, _P] + [C.c_float] * 3 + [_P] * 3 + [C.c_int32] * 4),

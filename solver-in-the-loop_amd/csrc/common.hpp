@@ -130,7 +130,8 @@ int sol_large_step(const sol_karman_cfg* c, hipStream_t s, const SolLargeStep& i
 // karman-3d pressure solvers (karman3d.hip / pcg.hip): dst = G src with G = the empty-box solve on the blob of cfg->direct
 // (*res = t1 or t2, whichever holds dst; skip = per-simulation done words [B] or NULL); the preconditioned CG solve M x = b (b is
 // overwritten with the residual; *x_out = the solution; active = the [Y,X,Z] mask) in the workspace of k3_pcg_workspace_bytes
-int k3_apply_G(hipStream_t s, const sol_karman3d_cfg* c, const float* src, float* t1, float* t2, float** res_out, const int* skip);
+// (wide: a z-periodic blob -- the six products as sol_periodic_gemm, fp64 accumulators, whatever the transform options say)
+int k3_apply_G(hipStream_t s, const sol_karman3d_cfg* c, const float* src, float* t1, float* t2, float** res_out, const int* skip, bool wide = false);
 size_t k3_pcg_workspace_bytes(const sol_karman3d_cfg* c);
 int k3_pcg_check(const sol_karman3d_cfg* c, const int32_t* hdr);
 int k3_pcg_solve(hipStream_t s, const sol_karman3d_cfg* c, const float* active, float* b, float* t1, float* t2, void* ws, float** x_out);

@@ -38,16 +38,7 @@ namespace {
 constexpr int FD3_HEADER = 16;
 constexpr int FD3_MAGIC = 0x46443333;     // "FD33"
 
-struct K3Args {
-    int B, Y, X, Z;
-    float dtdx, dt, adt;
-    int grad_pad, inflow_before;
-    const float *d_in, *vy_in, *vx_in, *vz_in, *re, *active, *inflow, *bcv, *bcm;
-    long bc_stride;
-    float *d_out, *vy_out, *vx_out, *vz_out, *svy, *svx, *svz, *rhs, *feat;
-    const float* p;
-    float fs0, fs1, fs2, fs3;
-};
+// (K3Args, the arguments of the forward kernels: karman3d_advect.hpp, shared with the z-periodic forms of karman3d_periodic.hip)
 
 // 7-point replicate-padded Laplacian of one component array [n0][n1][n2] at (j, i, k)
 __device__ __forceinline__ float lap7(const float* f, int n0, int n1, int n2, int j, int i, int k) {
@@ -85,32 +76,7 @@ __global__ void __launch_bounds__(256) k3_diffuse(K3Args a) {
 
 // (hard-BC face masks from the `active` cell mask: acc_at, face_mask<AX> of karman3d_mask.hpp)
 
-// ---- readers of the diffused components: straight from global memory (GlobalReader, karman3d_advect.hpp), or from the workgroup's LDS tile
-constexpr int T3 = 8;         // tile edge (cells) in y and x
-constexpr int HL3 = 2;         // halo cells
-constexpr int TR = T3 + 2 * HL3;      // cell rows / columns of the tile region (12); face arrays have one more along their axis
-struct TileReader {
-    GlobalReader g;
-    const float *ly, *lx, *lz;        // LDS: [TR+1][TR][Z], [TR][TR+1][Z], [TR][TR][Z+1]
-    const unsigned char* la;          // LDS: accessible mask of the region's cells [TR][TR][Z] (bytes; rows / columns beyond the domain hold the edge value)
-    int j0, i0;                       // first cell row / column of the region (may be negative: clipped rows are never read)
-    __device__ __forceinline__ float acc(int j, int i, int k) const {
-        const int rj = j - j0, ri = i - i0, kk = clampi(k, 0, g.Z - 1);
-        return ((unsigned)rj < (unsigned)TR && (unsigned)ri < (unsigned)TR) ? (float)la[(rj * TR + ri) * g.Z + kk] : g.acc(j, i, k);
-    }
-    __device__ __forceinline__ float y(int j, int i, int k) const {
-        const int rj = j - j0, ri = i - i0;
-        return ((unsigned)rj <= (unsigned)TR && (unsigned)ri < (unsigned)TR) ? ly[(rj * TR + ri) * g.Z + k] : g.y(j, i, k);
-    }
-    __device__ __forceinline__ float x(int j, int i, int k) const {
-        const int rj = j - j0, ri = i - i0;
-        return ((unsigned)rj < (unsigned)TR && (unsigned)ri <= (unsigned)TR) ? lx[(rj * (TR + 1) + ri) * g.Z + k] : g.x(j, i, k);
-    }
-    __device__ __forceinline__ float z(int j, int i, int k) const {
-        const int rj = j - j0, ri = i - i0;
-        return ((unsigned)rj < (unsigned)TR && (unsigned)ri < (unsigned)TR) ? lz[(rj * TR + ri) * (g.Z + 1) + k] : g.z(j, i, k);
-    }
-};
+// (readers of the diffused components: GlobalReader straight from global memory, TileReader from the workgroup's LDS tile -- karman3d_advect.hpp)
 
 // trilinear sample of component C (0: y faces [Y+1][X][Z], 1: x faces, 2: z faces) at index-space position
 // (j + oy, i + ox, k + oz) of its own lattice, indices clamped ('boundary' extrapolation).  floor() acts on the OFFSET only:
@@ -131,12 +97,6 @@ __device__ __forceinline__ float tri_clamp(const R& r, int j, float oy, int i, f
     const float c11 = (1.f - wz) * rd(j1, i1, k0) + wz * rd(j1, i1, k1);
     return (1.f - wy) * ((1.f - wx) * c00 + wx * c01) + wy * ((1.f - wx) * c10 + wx * c11);
 }
-struct TRd : TileReader {
-    __device__ __forceinline__ int g_Y() const { return g.Y; }
-    __device__ __forceinline__ int g_X() const { return g.X; }
-    __device__ __forceinline__ int g_Z() const { return g.Z; }
-};
-
 // one advected value per call.  kind 0/1/2: face of that component at (j, i, k); kind 3: cell (j, i, k).
 // Velocity at the sample point: the own component is the stored value, the others are the bilinear averages of their four
 // surrounding faces (index clamped: 'boundary' extrapolation of the component grids)  [oracle: advect_mac]
@@ -225,7 +185,6 @@ __global__ void __launch_bounds__(256) k3_advect(K3Args a) {
 
 // One workgroup = tile (ty, tx) of 8 x 8 cells x the full z column of simulation b.  It owns the y faces j0..j0+7 (the last
 // tile row also face Y), the x faces i0..i0+7 (the last tile column also face X), all z faces and cells of its columns.
-constexpr int ADV_T = 1024;      // 16 waves per workgroup: the tile kernel owns a CU (117 KB of LDS), its gathers are latency bound
 __global__ void __launch_bounds__(ADV_T) k3_advect_tile(K3Args a, int tiles_x) {
     extern __shared__ __align__(16) float lds3[];
     const int Y = a.Y, X = a.X, Z = a.Z;
@@ -751,7 +710,7 @@ int grid_for(size_t n) { const size_t g = (n + 255) / 256; return (int)(g < 1 ? 
 // ---- the empty-box solve G = M_r^-1 (three sine transforms each way + the 1/eigenvalue scaling) on the blob's matrices: the direct
 // solve applies it twice around the capacitance correction, the preconditioned CG solve (pcg.hip) once per iteration.
 // dst = G src (src preserved); *res_out = the buffer (t1 or t2) that holds dst.  skip: per-simulation done words [B] or NULL.
-int k3_apply_G(hipStream_t s, const sol_karman3d_cfg* c, const float* src, float* t1, float* t2, float** res_out, const int* skip) {
+int k3_apply_G(hipStream_t s, const sol_karman3d_cfg* c, const float* src, float* t1, float* t2, float** res_out, const int* skip, bool wide) {
     const int B = c->B, Y = c->Y, X = c->X, Z = c->Z, N = Y * X * Z;
     const float* Qy = c->direct + FD3_HEADER;
     const float* Qx = Qy + (size_t)Y * Y;
@@ -760,9 +719,16 @@ int k3_apply_G(hipStream_t s, const sol_karman3d_cfg* c, const float* src, float
     // One sine transform of the whole batch along each axis = one batched GEMM:
     //   z: [(b,j,i)] x Z times Qz;   x: per (b, j): Qx times [X x Z];   y: per b: Qy times [Y x (X Z)]
     // (the GEMMs do not read `skip`: a converged CG solve on a grid without the LDS-resident transforms still pays them)
-    auto tz = [&](const float* in, float* out) { return sol_gemm_f32(s, 1, in, Z, 0, Qz, Z, 0, out, Z, 0, B * Y * X, Z, Z, 0); };
-    auto tx = [&](const float* in, float* out) { return sol_gemm_f32(s, B * Y, Qx, X, 0, in, Z, (long)X * Z, out, Z, (long)X * Z, X, Z, X, 0); };
-    auto ty = [&](const float* in, float* out) { return sol_gemm_f32(s, B, Qy, Y, 0, in, X * Z, (long)N, out, X * Z, (long)N, Y, X * Z, Y, 0); };
+    // (wide, a z-periodic blob: the same products with fp64 accumulators -- with fp32 sums v_z of a periodic cylinder missed the float64
+    // reference)
+    // The correction between the two applications of G (k3_capacitance, k3e_*) keeps its fp32 sums on either blob: it acts on the |S| support
+    // values only, and with G wide the periodic cells read 1.2e-6 ... 1.8e-6 on v_z against the bound of 1e-5.
+    const auto gemm = wide ? sol_periodic_gemm : sol_gemm_f32;
+    // (sol_periodic_gemm takes the batch on grid.z: the x transform's B * Y must fit it)
+    SOL_REQUIRE(!wide || (size_t)B * Y <= 65535, "z-periodic blob: B * Y = %zu is beyond the 65535 batches one transform launch takes", (size_t)B * Y);
+    auto tz = [&](const float* in, float* out) { return gemm(s, 1, in, Z, 0, Qz, Z, 0, out, Z, 0, B * Y * X, Z, Z, 0); };
+    auto tx = [&](const float* in, float* out) { return gemm(s, B * Y, Qx, X, 0, in, Z, (long)X * Z, out, Z, (long)X * Z, X, Z, X, 0); };
+    auto ty = [&](const float* in, float* out) { return gemm(s, B, Qy, Y, 0, in, X * Z, (long)N, out, X * Z, (long)N, Y, X * Z, Y, 0); };
     auto G = [&](const float* src, float* t1, float* t2) -> int {     // t2 = G src  (src is preserved)
         if (int e = tz(src, t1)) return e;
         if (int e = tx(t1, t2)) return e;
@@ -774,7 +740,7 @@ int k3_apply_G(hipStream_t s, const sol_karman3d_cfg* c, const float* src, float
     };
     // LDS-resident form: three launches per application of G (plane-wise z+x transforms, column-slab y transform + scaling +
     // inverse y transform, plane-wise inverse) instead of six batched GEMMs + a scaling pass
-    const bool fused_tf = sol_opt().k3d_fused_tf && X <= 64 && Z <= 64 && Y <= 128 && X % 4 == 0 && Z % 4 == 0 && Y % 16 == 0 && (X * Z) % 32 == 0;
+    const bool fused_tf = !wide && sol_opt().k3d_fused_tf && X <= 64 && Z <= 64 && Y <= 128 && X % 4 == 0 && Z % 4 == 0 && Y % 16 == 0 && (X * Z) % 32 == 0;
     const size_t ty_lds = ((size_t)Y * (Y + 4) + (size_t)Y * 36) * sizeof(float);
     // the matrix-core kernels are instantiated for the shapes that occur: Y in {128, 64, 32}, X, Z in {64, 32}
     const bool mfma_tf = sol_opt().k3d_mfma_tf && fused_tf && (X == 64 || X == 32) && (Z == 64 || Z == 32) && (Y == 128 || Y == 64 || Y == 32);
@@ -815,7 +781,8 @@ int pressure_solve3d(hipStream_t s, const sol_karman3d_cfg* c, const int32_t* hd
     const int nS = hdr[4], SP = hdr[5];
     const float* KpT = c->direct + FD3_HEADER + (size_t)Y * Y + (size_t)X * X + (size_t)Z * Z + (size_t)N;
     float* res = nullptr;
-    if (int e = k3_apply_G(s, c, R, T1, T2, &res, nullptr)) return e;
+    const bool wide = hdr[6] != 0;
+    if (int e = k3_apply_G(s, c, R, T1, T2, &res, nullptr, wide)) return e;
     *res_out = res;
     if (hdr[0] == FD3E_MAGIC) {                     // the obstacle extruded along z: nS = |S2| > 0, SP = SP2 (check_blob3d)
         const float* Qz = c->direct + FD3_HEADER + (size_t)Y * Y + (size_t)X * X;
@@ -828,14 +795,14 @@ int pressure_solve3d(hipStream_t s, const sol_karman3d_cfg* c, const int32_t* hd
         SOL_LAUNCH(k3e_gather_tz, dim3(SP / EXC, B), dim3(256), k3e_lds_bytes(Z), s, (const float*)res, Qz, sidx2, xh, Z, SP, Y * X);
         SOL_LAUNCH(k3e_modes, dim3(SP / 32, Z), dim3(256), 0, s, (const float*)xh, KpT, res, B, Z, SP);
         SOL_LAUNCH(k3e_tz_apply, dim3(SP / EXC, B), dim3(256), k3e_lds_bytes(Z), s, (const float*)res, Qz, sidx2, R, Z, SP, Y * X);
-        if (int e = k3_apply_G(s, c, R, T1, T2, &res, nullptr)) return e;
+        if (int e = k3_apply_G(s, c, R, T1, T2, &res, nullptr, wide)) return e;
     } else if (nS > 0) {
         const int* sidx = reinterpret_cast<const int*>(KpT + (size_t)SP * SP);
         SOL_REQUIRE(SP / CAPQ <= 1024 && SP % 64 == 0, "direct-solver blob: SP = %d does not fit the capacitance kernel", SP);
         float* cpart = res == T1 ? T2 : T1;         // scratch: the buffer G does not return its result in (B * CAPQ * SP <= B * N floats)
         SOL_LAUNCH(k3_capacitance, dim3(SP / 32, CAPQ, B), dim3(256), 0, s, res, KpT, sidx, cpart, SP, N);
         SOL_LAUNCH(k3_cap_apply, dim3((SP + 255) / 256, B), dim3(256), 0, s, cpart, sidx, R, SP, N);
-        if (int e = k3_apply_G(s, c, R, T1, T2, &res, nullptr)) return e;
+        if (int e = k3_apply_G(s, c, R, T1, T2, &res, nullptr, wide)) return e;
     }
     SOL_LAUNCH_CHECK();
     return SOL_OK;
@@ -849,6 +816,8 @@ int check_blob3d(const sol_karman3d_cfg* c, const int32_t* hdr) {
     const size_t N = (size_t)Y * X * Z;
     const int nS = hdr[4], SP = hdr[5];
     SOL_REQUIRE(hdr[1] == Y && hdr[2] == X && hdr[3] == Z, "direct-solver blob is for a %dx%dx%d grid, cfg is %dx%dx%d", hdr[1], hdr[2], hdr[3], Y, X, Z);
+    SOL_REQUIRE(hdr[6] == 0 || hdr[6] == SOL_K3_PERIODIC_Z, "direct-solver blob: periodic flags %d (header word 6): only the z axis (8) is built; a periodic y (2) or x (4) is not", hdr[6]);
+    SOL_REQUIRE(!hdr[6] || c->pressure_solver == 0, "pressure_solver = 1 (CG) is not built for a z-periodic blob: the direct solves are (precond3d.periodic_solver_blob3d, extruded_solver_blob3d)");
     if (hdr[0] == FD3E_MAGIC) {                     // the obstacle extruded along z: nS = |S2|, SP = SP2, Z matrices of SP2 x SP2
         SOL_REQUIRE(nS >= 1 && SP >= nS && SP % 32 == 0 && SP <= FD3E_MAX_SP2 && (size_t)SP <= (size_t)Y * X && Z <= FD3E_MAX_Z &&
                     (size_t)Z * SP * SP <= ((size_t)1 << 26), "extruded direct-solver blob header is inconsistent (nS2 %d, SP2 %d, Z %d)", nS, SP, Z);
@@ -1132,7 +1101,7 @@ int step_fwd3d(const char* who, const sol_karman3d_cfg* c, void* stream,
                float* d_out, float* vy_out, float* vx_out, float* vz_out,
                float* saved_vy, float* saved_vx, float* saved_vz,
                float* feat_out, const float* feat_scale, const int32_t* direct_header_host,
-               void* workspace, size_t workspace_bytes, float fy, float fx, float fz, int32_t advection = 0, float strength = 1.f) {
+               void* workspace, size_t workspace_bytes, float fy, float fx, float fz, int32_t advection = 0, float strength = 1.f, bool plain = false) {
     SOL_REQUIRE(c != nullptr, "cfg is NULL");
     if (int e = sol_mc3_check(who, advection, strength)) return e;
     SOL_REQUIRE((saved_vy && saved_vx && saved_vz) || (!saved_vy && !saved_vx && !saved_vz), "saved_vy / saved_vx / saved_vz: all three or none");
@@ -1145,6 +1114,8 @@ int step_fwd3d(const char* who, const sol_karman3d_cfg* c, void* stream,
     const bool buoyant = fy != 0.f || fx != 0.f || fz != 0.f;
     SOL_REQUIRE(!buoyant || (d_in && inflow && d_out), "%s: a non-zero force needs d_in, inflow and d_out", who);
     if (int e = check_blob3d(c, direct_header_host)) return e;
+    const bool pz = direct_header_host[6] != 0;          // a z-periodic blob: the stencil launches of karman3d_periodic.hip
+    SOL_REQUIRE(!pz || plain, "%s is not built for a z-periodic blob: sol_karman3d_step_fwd is (no buoyancy, no MacCormack advection on periodic scenes)", who);
     const K3Fwd l = k3_fwd_layout(c, workspace, advection == 1);
     SOL_REQUIRE(workspace_bytes >= l.bytes, "workspace too small");
     SOL_REQUIRE(vy_in != vy_out && vx_in != vx_out && vz_in != vz_out && (d_in != d_out || !d_out), "%s: outputs must not alias the inputs", who);
@@ -1162,6 +1133,13 @@ int step_fwd3d(const char* who, const sol_karman3d_cfg* c, void* stream,
     a.d_out = d_out; a.vy_out = vy_out; a.vx_out = vx_out; a.vz_out = vz_out; a.svy = svy; a.svx = svx; a.svz = svz; a.rhs = R; a.feat = feat_out; a.p = T2;
     if (feat_scale) { a.fs0 = feat_scale[0]; a.fs1 = feat_scale[1]; a.fs2 = feat_scale[2]; a.fs3 = feat_scale[3]; }
     const size_t faces = nVy + nVx + nVz;
+    if (pz) {
+        if (int e = sol_k3p_front(s, a)) return e;
+        float* res = nullptr;
+        if (int e = pressure_solve_any3d(s, c, direct_header_host, active, R, T1, T2, l.sol.pcg, &res)) return e;
+        a.p = res;
+        return sol_k3p_project(s, a);
+    }
     SOL_LAUNCH(k3_diffuse, dim3(grid_for(faces), B), dim3(256), 0, s, a);
     if (advection == 1) {
         if (int e = sol_mc3_advect(c, s, strength, d_in, svy, svx, svz, active, inflow, d_out, vy_out, vx_out, vz_out, l.mc)) return e;
@@ -1192,7 +1170,7 @@ extern "C" int sol_karman3d_step_fwd(const sol_karman3d_cfg* c, void* stream,
                                      void* workspace, size_t workspace_bytes) {
     return step_fwd3d("sol_karman3d_step_fwd", c, stream, d_in, vy_in, vx_in, vz_in, re, active, inflow, velBCy, velBCyMask, bc_batch_stride,
                       d_out, vy_out, vx_out, vz_out, saved_vy, saved_vx, saved_vz, feat_out, feat_scale, direct_header_host,
-                      workspace, workspace_bytes, 0.f, 0.f, 0.f);
+                      workspace, workspace_bytes, 0.f, 0.f, 0.f, 0, 1.f, true);
 }
 
 // The step with the buoyancy force F = (fy, fx, fz): sol_karman3d_step_fwd's launches with k3_buoyancy between the advection and the
@@ -1292,6 +1270,8 @@ int step_bwd3d(const char* who, const sol_karman3d_cfg* c, void* stream,
     SOL_REQUIRE(!bx || bx->g_dsum, "%s: NULL pointer argument (g_dsum)", who);
     SOL_REQUIRE(!bx || (bx->fy - bx->fy == 0.f && bx->fx - bx->fx == 0.f && bx->fz - bx->fz == 0.f), "%s: the force must be finite", who);
     if (int e = check_blob3d(c, direct_header_host)) return e;
+    const bool pz = direct_header_host[6] != 0;          // a z-periodic blob: the adjoint launches of karman3d_periodic.hip
+    SOL_REQUIRE(!pz || (!rx && !bx && !ax), "%s is not built for a z-periodic blob: sol_karman3d_step_bwd is (no buoyancy, no MacCormack advection, no gradient in Re on periodic scenes)", who);
     const K3Bwd l = k3_bwd_layout(c, rx != nullptr, workspace, ax && ax->advection == 1);
     SOL_REQUIRE(workspace_bytes >= l.bytes, "workspace too small");
     if (rx) {
@@ -1322,6 +1302,13 @@ int step_bwd3d(const char* who, const sol_karman3d_cfg* c, void* stream,
     a.gay = l.gay; a.gax = l.gax; a.gaz = l.gaz;
     a.gmax = l.gmax;
     a.rhs = l.sol.R; a.giy = g_vy_in; a.gix = g_vx_in; a.giz = g_vz_in;
+    if (pz) {
+        if (int e = sol_k3pb_rhs(s, a)) return e;
+        float* res = nullptr;
+        if (int e = pressure_solve_any3d(s, c, direct_header_host, active, l.sol.R, l.sol.T1, l.sol.T2, l.sol.pcg, &res)) return e;
+        a.gdiv = res;
+        return sol_k3pb_back(s, a, -1);
+    }
     SOL_LAUNCH(k3b_rhs, dim3(grid_for(N), B), dim3(256), 0, s, a);
     SOL_LAUNCH_CHECK();
     float* res = nullptr;

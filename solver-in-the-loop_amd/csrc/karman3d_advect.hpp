@@ -6,6 +6,18 @@
 #include "fixed_scatter.hpp"
 #include "karman3d_mask.hpp"
 
+// the arguments of the forward step's kernels (karman3d.hip; the z-periodic forms of karman3d_periodic.hip take the same value)
+struct K3Args {
+    int B, Y, X, Z;
+    float dtdx, dt, adt;
+    int grad_pad, inflow_before;
+    const float *d_in, *vy_in, *vx_in, *vz_in, *re, *active, *inflow, *bcv, *bcm;
+    long bc_stride;
+    float *d_out, *vy_out, *vx_out, *vz_out, *svy, *svx, *svz, *rhs, *feat;
+    const float* p;
+    float fs0, fs1, fs2, fs3;
+};
+
 namespace {
 
 // ---- reader of the diffused components straight from global memory -------------------------------------------------------------------
@@ -25,6 +37,42 @@ struct GR : GlobalReader {
     __device__ __forceinline__ int g_Z() const { return Z; }
 };
 
+// ---- reader of the diffused components from the workgroup's LDS tile (k3_advect_tile, k3p_advect_tile) ----------------------------------
+constexpr int T3 = 8;         // tile edge (cells) in y and x
+constexpr int HL3 = 2;         // halo cells
+constexpr int TR = T3 + 2 * HL3;      // cell rows / columns of the tile region (12); face arrays have one more along their axis
+constexpr int ADV_T = 1024;      // 16 waves per workgroup: the tile kernel owns a CU (117 KB of LDS), its gathers are latency bound
+struct TileReader {
+    GlobalReader g;
+    const float *ly, *lx, *lz;        // LDS: [TR+1][TR][Z], [TR][TR+1][Z], [TR][TR][Z+1]
+    const unsigned char* la;          // LDS: accessible mask of the region's cells [TR][TR][Z] (bytes; rows / columns beyond the domain hold the edge value)
+    int j0, i0;                       // first cell row / column of the region (may be negative: clipped rows are never read)
+    __device__ __forceinline__ float acc(int j, int i, int k) const {
+        const int rj = j - j0, ri = i - i0, kk = clampi(k, 0, g.Z - 1);
+        return ((unsigned)rj < (unsigned)TR && (unsigned)ri < (unsigned)TR) ? (float)la[(rj * TR + ri) * g.Z + kk] : g.acc(j, i, k);
+    }
+    __device__ __forceinline__ float y(int j, int i, int k) const {
+        const int rj = j - j0, ri = i - i0;
+        return ((unsigned)rj <= (unsigned)TR && (unsigned)ri < (unsigned)TR) ? ly[(rj * TR + ri) * g.Z + k] : g.y(j, i, k);
+    }
+    __device__ __forceinline__ float x(int j, int i, int k) const {
+        const int rj = j - j0, ri = i - i0;
+        return ((unsigned)rj < (unsigned)TR && (unsigned)ri <= (unsigned)TR) ? lx[(rj * (TR + 1) + ri) * g.Z + k] : g.x(j, i, k);
+    }
+    __device__ __forceinline__ float z(int j, int i, int k) const {
+        const int rj = j - j0, ri = i - i0;
+        return ((unsigned)rj < (unsigned)TR && (unsigned)ri < (unsigned)TR) ? lz[(rj * TR + ri) * (g.Z + 1) + k] : g.z(j, i, k);
+    }
+};
+struct TRd : TileReader {
+    __device__ __forceinline__ int g_Y() const { return g.Y; }
+    __device__ __forceinline__ int g_X() const { return g.X; }
+    __device__ __forceinline__ int g_Z() const { return g.Z; }
+};
+
+}  // namespace
+
+// the arguments of the adjoint's kernels (karman3d.hip; the z-periodic forms of karman3d_periodic.hip take the same value)
 struct K3BArgs {
     int B, Y, X, Z;
     float dtdx, adt;
@@ -40,6 +88,8 @@ struct K3BArgs {
     float* rhs;
     const float* gdiv;
 };
+
+namespace {
 
 // Where a contribution goes (fx_add).  GAdd: straight into the int64 accumulators in global memory.  TAdd (k3b_advect_adj_tile): into the
 // workgroup's int64 LDS window when the target face lies inside it, else into global memory.
@@ -181,6 +231,14 @@ int sol_k3_advect(const sol_karman3d_cfg* c, hipStream_t s, const float* d_in, c
                   const float* inflow, float* d_out, float* vy_out, float* vx_out, float* vz_out);
 int sol_k3b_advect_adj(const sol_karman3d_cfg* c, hipStream_t s, const float* svy, const float* svx, const float* svz, const float* gay, const float* gax,
                        const float* gaz, const unsigned* gmax, long long* gcy, long long* gcx, long long* gcz, int tile);
+// karman3d_periodic.hip: the stencil launches of the forward step on a z-periodic blob (header word 6 = SOL_K3_PERIODIC_Z): diffusion,
+// advection and divergence before the pressure solve, the projection after it
+int sol_k3p_front(hipStream_t s, const K3Args& a);
+int sol_k3p_project(hipStream_t s, const K3Args& a);
+// ... and of its adjoint: the right-hand side of the second solve (it also clears the fixed-point accumulators), then, with a.gdiv set,
+// g_a, the fixed-point scatter (tile as above) and the diffusion adjoint
+int sol_k3pb_rhs(hipStream_t s, const K3BArgs& a);
+int sol_k3pb_back(hipStream_t s, const K3BArgs& a, int tile);
 // karman3d_density_bwd.hip: the semi-Lagrangian adjoint of the density: g (its max in gmax) scattered onto the int64 gD, the back-trace
 // term written to gU (add_gU: added onto what gU holds)
 int sol_k3d_advect_adj(const sol_karman3d_cfg* c, hipStream_t s, const float* d_in, const float* inflow, const float* svy, const float* svx, const float* svz,

@@ -68,16 +68,53 @@ def cylinder_arrays3d(Y, X, Z, length=100.0):
     return extrude_mask(1.0 - disc, Z), inflow.astype(np.float64)
 
 
-def velocity_bc_masks3d(Y, X, Z):
+def velocity_bc_masks3d(Y, X, Z, periodic_z=False):
     """velBCy / velBCyMask of karman_train.py:366-373 with the third axis: the two inflow-side planes and the four lateral
-    walls of the flow component, [Y+1,X,Z], values 1."""
+    walls of the flow component, [Y+1,X,Z], values 1.  periodic_z: a periodic span has no z walls -- the two x walls only."""
     vn = np.zeros((Y + 1, X, Z))
     vn[0:2, :, :] = 1.0
     vn[:, 0, :] = 1.0
     vn[:, -1, :] = 1.0
-    vn[:, :, 0] = 1.0
-    vn[:, :, -1] = 1.0
+    if not periodic_z:
+        vn[:, :, 0] = 1.0
+        vn[:, :, -1] = 1.0
     return vn, np.copy(vn)
+
+
+PERIODIC_Z = 8                  # Scene3D.periodic_bits of a z-periodic scene: header word 6 of its blob (precond3d.PERIODIC_Z, SOL_K3_PERIODIC_Z)
+BOUNDARIES3D_MESSAGE = "%s must be 'open', 'periodic-z' or a triple (by, bx, bz) of 'open' / 'periodic' (got %r)"
+
+
+def boundaries_arg3d(b, who="boundaries"):
+    """"open", "periodic-z" or a triple (by, bx, bz) of "open" / "periodic" (the words of ops.boundaries_arg)  ->  (py, px, pz), True for a
+    periodic axis.  Only z is built: a periodic y or x is refused by name.  Anything else raises ValueError."""
+    if isinstance(b, str):
+        if b not in ("open", "periodic-z"):
+            raise ValueError(BOUNDARIES3D_MESSAGE % (who, b))
+        return False, False, b == "periodic-z"
+    try:
+        by, bx, bz = b
+    except (TypeError, ValueError):
+        raise ValueError(BOUNDARIES3D_MESSAGE % (who, b)) from None
+    for v in (by, bx, bz):
+        if not isinstance(v, str) or v not in ("open", "periodic"):
+            raise ValueError(BOUNDARIES3D_MESSAGE % (who, b))
+    for name, v in (("y", by), ("x", bx)):
+        if v == "periodic":
+            raise ValueError("%s: a periodic %s axis is not built for karman-3d: only the spanwise axis is ('periodic-z')" % (who, name))
+    return False, False, bz == "periodic"
+
+
+def boundaries_name3d(periodic):
+    """(py, px, pz) back as a word boundaries_arg3d takes"""
+    return "periodic-z" if periodic[2] else "open"
+
+
+def _not_periodic(scene, what):
+    """ValueError, by name, for what is not built for z-periodic scenes"""
+    if getattr(scene, "periodic_bits", 0):
+        raise ValueError("%s is not built for periodic scenes (Scene3D(boundaries='periodic-z')): the plain step, its velocity adjoint and the "
+                         "pressure solve are" % what)
 
 
 def buoyancy_force3d(buoyancy=None, buoyancy_factor=None, gravity=(-9.81, 0.0, 0.0)):
@@ -200,6 +237,7 @@ def diffuse_sub(sim, vy, vx, vz, re, nsub, chunk=None):
     ping-pongs through sim's pre-diffusion workspace (Karman3DFlow._sub_workspace: the static one of sim's own count, else a buffer of this
     call alone).  nsub = 1: no launch, the inputs are returned."""
     from .ops import diffusion_substeps_arg
+    _not_periodic(getattr(sim, "scene", None), "diffuse_sub")
     n = diffusion_substeps_arg(nsub, "diffuse_sub: nsub")
     smax = diffuse_sub_max3d()
     chunk = DIFFUSE_SUB_CHUNK3D if chunk is None else chunk
@@ -236,12 +274,23 @@ class Scene3D:
     = a2[j, i] for every k -- the cylinder of the wake, which the dense blob refuses at 128 x 64 x 64: Z capacitance systems on the in-plane
     set between two sine transforms of the support columns (precond3d.extruded_solver_blob3d; ValueError with its reason where it refuses:
     a mask that depends on z, no obstacle, size, conditioning).  The choice is `self.pressure_solver` ("direct", "cg" or
-    "direct_extruded"); everything that takes a scene treats "direct_extruded" as it treats "direct": no iteration, no report, capturable."""
+    "direct_extruded"); everything that takes a scene treats "direct_extruded" as it treats "direct": no iteration, no report, capturable.
 
-    def __init__(self, Y, X, Z, length=100.0, device="cuda", velBCy=None, velBCyMask=None, active=None, inflow=None, pressure_solver="auto"):
-        from .precond3d import direct_solver_blob3d, extruded_solver_blob3d
+    boundaries: "open" (default), "periodic-z" or a triple (by, bx, bz) of "open" / "periodic" (boundaries_arg3d; a periodic y or x is
+    refused by name) -> self.periodic = (py, px, pz), self.periodic_bits (0 or PERIODIC_Z).  A z-periodic scene (include/sol_hip.h,
+    "PERIODIC SPANWISE BOUNDARIES"): the default velBC mask has no z walls, and the blob is a periodic one -- "direct": precond3d.
+    periodic_solver_blob3d, "direct_extruded": extruded_solver_blob3d(periodic=True), "auto": the dense direct solve where it builds,
+    else a ValueError that names direct_extruded; "cg" is refused by name.  Array shapes do not change: v_z[..., Z] duplicates plane 0."""
+
+    def __init__(self, Y, X, Z, length=100.0, device="cuda", velBCy=None, velBCyMask=None, active=None, inflow=None, pressure_solver="auto",
+                 boundaries="open"):
+        from .precond3d import direct_solver_blob3d, extruded_solver_blob3d, periodic_solver_blob3d
         if pressure_solver not in PRESSURE_SOLVERS3D:
             raise ValueError("pressure_solver must be one of %s, got %r" % (PRESSURE_SOLVERS3D, pressure_solver))
+        self.periodic = boundaries_arg3d(boundaries, "Scene3D: boundaries")
+        self.periodic_bits = PERIODIC_Z if self.periodic[2] else 0
+        if self.periodic_bits and pressure_solver == "cg":
+            raise ValueError("pressure_solver='cg' is not built for periodic scenes (boundaries=%r): 'direct' and 'direct_extruded' are" % (boundaries,))
         self.Y, self.X, self.Z = Y, X, Z
         self.dx = length / X
         if active is None or inflow is None:
@@ -254,7 +303,7 @@ class Scene3D:
             raise ValueError("active / inflow must be [Y,X,Z] = %s, got %s / %s" % ((Y, X, Z), active.shape, inflow.shape))
         if not np.all((active == 0.0) | (active == 1.0)):
             raise ValueError("active must hold 0 (solid) and 1 (fluid) only")
-        bcv, bcm = velocity_bc_masks3d(Y, X, Z)
+        bcv, bcm = velocity_bc_masks3d(Y, X, Z, self.periodic[2])
         if velBCy is not None:
             bcv, bcm = np.asarray(velBCy, dtype=np.float64), np.asarray(velBCyMask, dtype=np.float64)
         n = (Y + 1) * X * Z
@@ -268,9 +317,15 @@ class Scene3D:
         self.velBCyMask = _lib.f32(bcm, device)
         if pressure_solver == "direct_extruded":
             why = []
-            blob = extruded_solver_blob3d(active, why)
+            blob = extruded_solver_blob3d(active, why, **({"periodic": True} if self.periodic_bits else {}))
             if blob is None:
                 raise ValueError("pressure_solver='direct_extruded' does not support this scene (%dx%dx%d): %s" % (Y, X, Z, why[0]))
+        elif self.periodic_bits:
+            why = []
+            blob = periodic_solver_blob3d(active, why)
+            if blob is None:
+                raise ValueError("the direct pressure solver does not support this z-periodic scene (%dx%dx%d): %s%s" % (
+                    Y, X, Z, why[0], "; pressure_solver='direct_extruded' takes an obstacle extruded along z" if pressure_solver == "auto" else ""))
         else:
             blob = direct_solver_blob3d(active) if pressure_solver != "cg" else None
         if blob is None and pressure_solver == "direct":
@@ -311,6 +366,11 @@ class Karman3DFlow:
         from .ops import advection_arg
         self.physics = StepPhysics3D.of(buoyancy, buoyancy_factor, gravity, diffusion_substeps, "Karman3DFlow: diffusion_substeps")
         self.adv = advection_arg(advection, correction_strength, "Karman3DFlow: advection")
+        if getattr(scene, "periodic_bits", 0):      # what is not built for z-periodic scenes, by name
+            for on, what in ((self.adv is not None, "advection='mac_cormack'"), (self.physics.buoyancy is not None, "a non-zero buoyancy"),
+                             (self.physics.nsub > 1, "diffusion_substeps > 1"), (density_grad, "density_grad"), (re_grad, "re_grad")):
+                if on:
+                    _not_periodic(scene, "Karman3DFlow: " + what)
         _lib.require_gpu()
         self.lib = _lib.load()
         self.scene, self.B = scene, batch_size
@@ -369,6 +429,8 @@ class Karman3DFlow:
         sub_cfg(ph.nsub) -- the velocity handed back is then M^(n-1) v, "the input velocity" the re mode saves.  ph.buoyancy:
         sol_karman3d_step_fwd_buoy (a kept force of zero issues the plain call's launches).  adv = s (ops.advection_arg: a float for
         "mac_cormack", None for "semi_lagrangian"): sol_karman3d_step_fwd_adv with the force, or a zero force, then (1, s)."""
+        if ph.buoyancy is not None or ph.nsub > 1 or adv is not None:
+            _not_periodic(self.scene, "Karman3DFlow: a step with buoyancy, diffusion substeps or MacCormack advection")
         if pre_diffuse and ph.nsub > 1:
             vy, vx, vz = diffuse_sub(self, vy, vx, vz, re, ph.nsub)
         cfg = self.sub_cfg(ph.nsub)
@@ -435,6 +497,8 @@ class Karman3DFlow:
         _step_adjoint3d composes this with density_bwd and the substep tail, and is the one place that takes this list apart."""
         s = self.scene
         ph = physics if physics is not None else StepPhysics3D(buoyancy, nsub)
+        if ph.buoyancy is not None or ph.nsub > 1 or adv is not None or vel_in is not None:
+            _not_periodic(s, "Karman3DFlow: the adjoint of a step with buoyancy, diffusion substeps or MacCormack advection, and the gradient in re (re_grad)")
         cfg = self.sub_cfg(ph.nsub)         # (nsub > 1: `saved` / vel_in are the pre-diffused step's; the result is the cotangent of M^(n-1) v, g_re 1/n)
         gi = [torch.empty_like(t) for t in saved]
         info = self._cg_info(cfg)
@@ -506,6 +570,7 @@ def density_bwd(sim, d_in, saved, re, g_d, g_v=None, vel_in=None, g_re=None, nsu
     the pre-diffused velocity, the velocity gradients are the cotangent of M^(n-1) v and g_re is 1/n of the gradient -- a g_re to add onto
     must hold such a part too (the factor n is applied once, afterwards: _step_adjoint3d).  adv = s (the MacCormack step's): the _adv
     entries, sol_karman3d_density_bwd_adv(_re), which take (1, s) last."""
+    _not_periodic(getattr(sim, "scene", None), "density_bwd")
     _lib.require_gpu()
     s, B = sim.scene, sim.B
     Y, X, Z = s.Y, s.X, s.Z
@@ -556,6 +621,7 @@ def advect3d(sim, d, svy, svx, svz, adv=None):
     """The advection stage of the 3-D step alone (sol_karman3d_advect) on a given post-diffusion velocity (svy, svx, svz): -> (d_out, a_y,
     a_x, a_z), the velocity times the hard-BC face masks, the inflow added as the simulator's inflow_order says.  adv: None = the
     semi-Lagrangian launch of the step, a float s = MacCormack with that correction strength (ops.advection_arg).  Any Y, X, Z >= 8."""
+    _not_periodic(getattr(sim, "scene", None), "advect3d")
     _lib.require_gpu()
     d, svy, svx, svz = _advect3d_inputs("advect3d", sim, d, svy, svx, svz)
     s = sim.scene
@@ -572,6 +638,7 @@ def advect3d_bwd(sim, d, svy, svx, svz, g_d, g_ay, g_ax, g_az, adv=None, tile_wi
     """The transpose of advect3d (sol_karman3d_advect_bwd): the cotangents of (d_out, a_y, a_x, a_z) -> (g_d_in, g_svy, g_svx, g_svz), every
     decision of the forward stage frozen.  tile_window: the semi-Lagrangian scatters go through their LDS windows (False: global atomics
     only; equal bits)."""
+    _not_periodic(getattr(sim, "scene", None), "advect3d_bwd")
     _lib.require_gpu()
     d, svy, svx, svz = _advect3d_inputs("advect3d_bwd", sim, d, svy, svx, svz)
     g = [_lib.f32(t) for t in (g_d, g_ay, g_ax, g_az)]
@@ -651,6 +718,38 @@ class _Karman3DStepFn(torch.autograd.Function):
         vel_in = tuple(rest[-3:]) if ctx.want_re else None
         return (None, *_step_adjoint3d(ctx.sim, ctx.physics, ctx.density, d_in, (sy, sx, sz), re, gd, (gvy, gvx, gvz), vel_in, adv=ctx.adv),
                 None, None, None, None)
+
+
+def _seam3d(entry, scene, vz):
+    if vz.dtype != torch.float32 or not vz.is_contiguous() or vz.dim() != 4 or vz.shape[1:] != (scene.Y, scene.X, scene.Z + 1):
+        raise ValueError("%s: v_z must be a contiguous float32 [B,Y,X,Z+1] tensor of the scene, got %s %s" % (entry, vz.dtype, tuple(vz.shape)))
+    _lib.require_gpu()
+    check(getattr(_lib.load(), entry)(stream(), ptr(vz), vz.shape[0], scene.Y, scene.X, scene.Z, scene.periodic_bits))
+    return vz
+
+
+def seam_sync3d(scene, vz):
+    """In place on a z-periodic scene (sol_karman3d_seam_sync): plane 0 of v_z [B,Y,X,Z+1] copied onto the duplicate plane Z -- after a
+    correction, which leaves the duplicate plane behind.  An open scene: nothing is launched.  Returns vz."""
+    return _seam3d("sol_karman3d_seam_sync", scene, vz)
+
+
+def seam_fold3d(scene, g_vz):
+    """In place, the adjoint of seam_sync3d (sol_karman3d_seam_fold): g[..., 0] += g[..., Z], then g[..., Z] = 0.  Returns g_vz."""
+    return _seam3d("sol_karman3d_seam_fold", scene, g_vz)
+
+
+class _SeamSync3DFn(torch.autograd.Function):
+    """seam_sync3d out of place, with seam_fold3d as its backward (the autograd schedule of Karman3DTrainer)"""
+
+    @staticmethod
+    def forward(ctx, vz, scene):
+        ctx.scene = scene
+        return seam_sync3d(scene, _lib.dclone(vz.contiguous()))
+
+    @staticmethod
+    def backward(ctx, g):
+        return seam_fold3d(ctx.scene, _lib.dclone(g.contiguous())), None
 
 
 class _ToFeature3DFn(torch.autograd.Function):
@@ -1118,6 +1217,8 @@ class Karman3DTrainer:
             d, *v = sim._forward(ph, d, v[0], v[1], v[2], re, saved, feat, fs, **akw)[0]
             out, state = sch.forward(feat)
             check(self.lib.sol_karman3d_correct(stream(), ptr(out), net.cout, sv[0], sv[1], sv[2], ptr(v[0]), ptr(v[1]), ptr(v[2]), B, Y, X, Z))
+            if sc.periodic_bits:                    # the correction left the duplicate plane behind
+                seam_sync3d(sc, v[2])
             li, gi = l2_loss_fwd_bwd(v, tuple(g[i] for g in self._gt), sv, gscale=1.0 / ms)
             losses.append(li.reshape(()))
             keep.append((saved, state, gi, d_in))
@@ -1127,6 +1228,8 @@ class Karman3DTrainer:
         inv_in = fs[:3]
         for i in range(ms - 1, -1, -1):
             saved, state, G, d_in = keep[i]
+            if sc.periodic_bits:                    # the adjoint of the seam sync (gin's duplicate plane is exactly zero: folding G alone is folding G + gin)
+                seam_fold3d(sc, G[2])
             # G += gin and the adjoint of  v += std * to_staggered(out):  d out[..., c] = std_c * G_c restricted to the faces that received a correction
             # (one launch, zero padded to the four channels the thin-layer launches read; glue="torch": the elementwise composition of rounds 5-6)
             fused_glue = self.glue == "fused" and net.cout == 3
@@ -1172,6 +1275,8 @@ class Karman3DTrainer:
             d, *v = self.sim.step(d, v[0], v[1], v[2], re)
             out = self.net(to_feature3d(v[0], v[1], v[2], re) / self.std_in) * self.std_v
             v = tuple(a + c for a, c in zip(v, to_staggered3d(out)))
+            if self.scene.periodic_bits:
+                v = (v[0], v[1], _SeamSync3DFn.apply(v[2], self.scene))
             # (one kernel, no torch reduction: a multi-workgroup torch .sum() puts a memset node into the captured graph, ops.L2LossFn)
             losses.append(ops_l2_loss(v, tuple(g[i] for g in self._gt), self._std_v_host))
         losses = _lib.stack0(losses)
@@ -1270,6 +1375,8 @@ class Karman3DRollout:
         s = self.scene
         check(self.lib.sol_karman3d_correct(stream(), ptr(out), self.net.cout, self.std_v[0], self.std_v[1], self.std_v[2],
                                             ptr(vy), ptr(vx), ptr(vz), self.B, s.Y, s.X, s.Z))
+        if s.periodic_bits:
+            seam_sync3d(s, vz)
         return d, vy, vx, vz
 
     def run(self, d, vy, vx, vz, re, nsteps):

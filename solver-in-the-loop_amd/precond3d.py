@@ -14,7 +14,7 @@ numpy, computed once per scene geometry (about a second at 128 x 64 x 64 with th
 """
 import numpy as np
 
-from .precond import dst_matrix
+from .precond import dst_matrix, hartley_matrix
 
 FD3_MAGIC = 0x46443333          # "FD33"
 FD3_HEADER = 16                 # int32 words
@@ -180,7 +180,7 @@ def extruded_solver_refusal3d(active):
     return None
 
 
-def extruded_solver_blob3d(active, why=None):
+def extruded_solver_blob3d(active, why=None, periodic=False):
     """float32 blob of the direct solve for an obstacle extruded along z, or None where the scene does not qualify: the mask
     depends on z; there is no solid cell (the plain direct solve's scene, nS = 0); a mode's capacitance system has a condition
     number beyond 1e6; Z > 128; or the size is beyond the cap: SP2 <= 1024, SP2 <= Y X (the device's scratch) and
@@ -189,7 +189,11 @@ def extruded_solver_blob3d(active, why=None):
     layout (32-bit words): header[16] = {magic "FD3E", Y, X, Z, nS2, SP2, ...};  Qy[Y*Y];  Qx[X*X];  Qz[Z*Z];  invlam[Y*X*Z]
     (the positions of the dense blob: the empty-box solve and the CG preconditioner read either);  KpT[Z][SP2][SP2] (K'_m of
     z mode m, stored transposed, zero padded; SP2 = nS2 rounded up to 32);  sidx2[SP2] int32 (in-plane cell index j*X + i,
-    -1 = padding).  G_m,SS is built from the nS2 rows of Qy (x) Qx, never as a (Y X)^2 matrix."""
+    -1 = padding).  G_m,SS is built from the nS2 rows of Qy (x) Qx, never as a (Y X)^2 matrix.
+
+    periodic=True: the z axis is periodic.  T_Z is then the circulant second difference, Qz = hartley_matrix(Z), mu_m = 2 - 2 cos(2 pi m /
+    Z) -- mode 0 (mu = 0) is the 2-D problem of the plane -- and header word 6 = PERIODIC_Z; the construction, the conditioning rule and
+    the size caps are the open one's."""
     say = why.append if why is not None else (lambda s: None)
     reason = extruded_solver_refusal3d(active)
     if reason is not None:
@@ -200,13 +204,13 @@ def extruded_solver_blob3d(active, why=None):
     S2, E2, solid = _perturbation2d(act[:, :, 0])
     nS2 = len(S2)
     SP2 = (nS2 + 31) // 32 * 32
-    Qy, Qx, Qz = dst_matrix(Y), dst_matrix(X), dst_matrix(Z)
-    lam = rect_eigenvalues(Y, X, Z)
+    Qy, Qx, Qz = dst_matrix(Y), dst_matrix(X), (hartley_matrix(Z) if periodic else dst_matrix(Z))
+    lam = periodic_eigenvalues3d(Y, X, Z) if periodic else rect_eigenvalues(Y, X, Z)
     R = (Qy[S2 // X, :, None] * Qx[S2 % X, None, :]).reshape(nS2, Y * X)          # rows S2 of Qy (x) Qx
     KpT = np.zeros((Z, SP2, SP2))
     eye = np.eye(nS2)
     for m in range(Z):
-        mu = 2.0 - 2.0 * np.cos(np.pi * (m + 1) / (Z + 1))
+        mu = 2.0 - 2.0 * np.cos(2.0 * np.pi * m / Z) if periodic else 2.0 - 2.0 * np.cos(np.pi * (m + 1) / (Z + 1))
         Em = E2 - mu * np.diag(solid)
         GSS = (R / lam[:, :, m].reshape(1, Y * X)) @ R.T
         cap = eye + GSS @ Em
@@ -219,6 +223,8 @@ def extruded_solver_blob3d(active, why=None):
     sidx2[:nS2] = S2.astype(np.int32)
     header = np.zeros(FD3_HEADER, dtype=np.int32)
     header[:6] = [FD3E_MAGIC, Y, X, Z, nS2, SP2]
+    if periodic:
+        header[6] = PERIODIC_Z
     parts = [header.view(np.float32), Qy.astype(np.float32).ravel(), Qx.astype(np.float32).ravel(), Qz.astype(np.float32).ravel(),
              (1.0 / lam).astype(np.float32).ravel(), KpT.astype(np.float32).ravel(), sidx2.view(np.float32)]
     return np.concatenate(parts)
@@ -271,3 +277,133 @@ def direct_solve_reference3d(blob, b):
         b[sidx[sidx >= 0]] -= c[sidx >= 0]
         g = G(b.reshape(Y, X, Z))
     return g
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# a PERIODIC z axis (Scene3D(boundaries="periodic-z"), csrc/karman3d_periodic.hip).  Cell (j, i, Z - 1) is the neighbour of
+# (j, i, 0): along z the accessible mask wraps instead of taking the edge value, and the empty box's T_Z is the circulant
+# second difference, diagonalised by the Hartley matrix (symmetric, its own inverse: the device's transform launches assume
+# nothing else of Q_Z) with the eigenvalues 2 - 2 cos(2 pi m / Z).  The z-constant mode has the eigenvalue 0 along z, but the
+# two open axes hold it down: lam > 0 everywhere, the solve is non-singular.  The builders of the open box above keep their
+# text (a test pins it); these stand beside them.  Header word 6 carries the axes: PERIODIC_Z = 8; 2 and 4 are reserved for y
+# and x, which nothing builds.
+# ---------------------------------------------------------------------------------------------------------------------
+PERIODIC_Y3, PERIODIC_X3, PERIODIC_Z = 2, 4, 8
+
+
+def periodic_eigenvalues3d(Y, X, Z):
+    """rect_eigenvalues with the z axis periodic"""
+    ev = lambda n: 2.0 - 2.0 * np.cos(np.pi * np.arange(1, n + 1) / (n + 1))
+    return ev(Y)[:, None, None] + ev(X)[None, :, None] + (2.0 - 2.0 * np.cos(2.0 * np.pi * np.arange(Z) / Z))[None, None, :]
+
+
+def _accessible3d(act, periodic):
+    """the accessible mask with one ring around the domain: the edge value along an open axis, the wrapped plane along z when periodic"""
+    acc = np.pad(act, ((1, 1), (1, 1), (0, 0)), mode="edge")
+    return np.pad(acc, ((0, 0), (0, 0), (1, 1)), mode="wrap" if periodic else "edge")
+
+
+def _z_pairs(idx, act, periodic):
+    """(lo, hi, a) per axis: the index arrays of the two cells of every cell pair and the product of their active values; along a periodic
+    z the seam pair (Z - 1, 0) is one of them"""
+    out = []
+    for ax in range(3):
+        lo = [slice(None)] * 3
+        hi = [slice(None)] * 3
+        lo[ax] = slice(0, -1)
+        hi[ax] = slice(1, None)
+        out.append((idx[tuple(lo)], idx[tuple(hi)], act[tuple(lo)] * act[tuple(hi)]))
+    if periodic:
+        out.append((idx[:, :, -1], idx[:, :, 0], act[:, :, -1] * act[:, :, 0]))
+    return out
+
+
+def scene_matrix3d(active, periodic=False):
+    """The pressure matrix M = -A of a scene as a scipy.sparse CSC matrix over the cells (j*X + i)*Z + k (tests; .toarray() for a dense
+    one): diagonal = the number of accessible neighbours (at least 1), -1 between two active neighbours.  periodic: the z axis wraps."""
+    import scipy.sparse as sp
+    act = (np.asarray(active, dtype=np.float64) != 0).astype(np.float64)
+    Y, X, Z = act.shape
+    acc = _accessible3d(act, periodic)
+    n = (acc[:-2, 1:-1, 1:-1] + acc[2:, 1:-1, 1:-1] + acc[1:-1, :-2, 1:-1] + acc[1:-1, 2:, 1:-1] + acc[1:-1, 1:-1, :-2] + acc[1:-1, 1:-1, 2:])
+    idx = np.arange(Y * X * Z).reshape(Y, X, Z)
+    rows, cols, vals = [idx.ravel()], [idx.ravel()], [np.maximum(n, 1.0).ravel()]
+    for lo, hi, a in _z_pairs(idx, act, periodic):
+        rows += [lo.ravel(), hi.ravel()]; cols += [hi.ravel(), lo.ravel()]; vals += [-a.ravel(), -a.ravel()]
+    N = Y * X * Z
+    return sp.csc_matrix((np.concatenate(vals), (np.concatenate(rows), np.concatenate(cols))), shape=(N, N))
+
+
+def _perturbation3d_pz(act):
+    """_perturbation3d with the z axis periodic: the accessible mask wrapped along z, the seam couplings among the pairs"""
+    Y, X, Z = act.shape
+    idx = np.arange(Y * X * Z).reshape(Y, X, Z)
+    acc = _accessible3d(act, True)
+    n = (acc[:-2, 1:-1, 1:-1] + acc[2:, 1:-1, 1:-1] + acc[1:-1, :-2, 1:-1] + acc[1:-1, 2:, 1:-1] + acc[1:-1, 1:-1, :-2] + acc[1:-1, 1:-1, 2:])
+    diag = np.maximum(n, 1.0)
+    sel = diag != 6.0
+    rows, cols, vals = [idx[sel]], [idx[sel]], [diag[sel] - 6.0]
+    for lo, hi, a in _z_pairs(idx, act, True):
+        sel = a != 1.0
+        rows += [lo[sel], hi[sel]]; cols += [hi[sel], lo[sel]]; vals += [1.0 - a[sel], 1.0 - a[sel]]
+    return np.concatenate(rows), np.concatenate(cols), np.concatenate(vals)
+
+
+def periodic_solver_blob3d(active, why=None):
+    """direct_solver_blob3d for a z-periodic scene: the same layout ("FD33") with Qz = hartley_matrix(Z), the periodic eigenvalues, the
+    perturbation of _perturbation3d_pz and header word 6 = PERIODIC_Z.  None where the open builder's rules refuse (`why`: a list that
+    receives the sentence): more than FD3_MAX_S perturbed cells, a perturbation beyond one window -- an obstacle lying across the seam
+    spans the axis, as does an extruded one (extruded_solver_blob3d(periodic=True) takes that) -- or an ill-conditioned capacitance system."""
+    say = why.append if why is not None else (lambda s: None)
+    act = (np.asarray(active, dtype=np.float64) != 0).astype(np.float64)
+    Y, X, Z = act.shape
+    rows, cols, vals = _perturbation3d_pz(act)
+    S = np.unique(rows)
+    nS = len(S)
+    SP = (nS + 63) // 64 * 64
+    if SP > FD3_MAX_S or 8 * SP > Y * X * Z:
+        say("the obstacle perturbs %d cells (padded %d): at most %d and at most an eighth of the grid" % (nS, SP, FD3_MAX_S))
+        return None
+    Qy, Qx, Qz = dst_matrix(Y), dst_matrix(X), hartley_matrix(Z)
+    lam = periodic_eigenvalues3d(Y, X, Z)
+    KpT = np.zeros((SP, SP))
+    if nS:
+        js, is_, ks = S // (X * Z), (S // Z) % X, S % Z
+        wy, wx, wz = (np.arange(v.min(), v.max() + 1) for v in (js, is_, ks))
+        if (len(wy) * len(wx) * len(wz)) ** 2 > 6e7:
+            say("the perturbation does not fit one window (%d x %d x %d cells; an obstacle across the z seam, or extruded along z, spans the axis)"
+                % (len(wy), len(wx), len(wz)))
+            return None
+        Gw = _green_on_window(Qy, Qx, Qz, lam, wy, wx, wz)
+        a, b, c = js - wy[0], is_ - wx[0], ks - wz[0]
+        GSS = Gw[a[:, None], a[None, :], b[:, None], b[None, :], c[:, None], c[None, :]]
+        pos = np.full(Y * X * Z, -1, dtype=np.int64)
+        pos[S] = np.arange(nS)
+        ESS = np.zeros((nS, nS))
+        np.add.at(ESS, (pos[rows], pos[cols]), vals)
+        cap = np.eye(nS) + GSS @ ESS
+        cond = np.linalg.cond(cap)
+        if not cond <= 1e6:
+            say("the capacitance system is ill conditioned (condition number %.3g, at most 1e6)" % cond)
+            return None
+        KpT[:nS, :nS] = (ESS @ np.linalg.inv(cap)).T
+    sidx = np.full(SP, -1, dtype=np.int32)
+    sidx[:nS] = S.astype(np.int32)
+    header = np.zeros(FD3_HEADER, dtype=np.int32)
+    header[:7] = [FD3_MAGIC, Y, X, Z, nS, SP, PERIODIC_Z]
+    parts = [header.view(np.float32), Qy.astype(np.float32).ravel(), Qx.astype(np.float32).ravel(), Qz.astype(np.float32).ravel(),
+             (1.0 / lam).astype(np.float32).ravel(), KpT.astype(np.float32).ravel(), sidx.view(np.float32)]
+    return np.concatenate(parts)
+
+
+def blob_periodic_bits3d(blob):
+    """header word 6 of a blob: 0 (open) or PERIODIC_Z"""
+    return int(np.asarray(blob[:FD3_HEADER]).view(np.int32)[6])
+
+
+def periodic_solve_reference3d(blob, b):
+    """float64 numpy restatement of the device algorithm on a z-periodic blob of either layout: b [Y,X,Z] -> x with M x = b (CPU tests).
+    The device runs the open blobs' launches on the periodic blob's tables; so does this."""
+    hdr = np.asarray(blob[:FD3_HEADER]).view(np.int32)
+    assert hdr[6] == PERIODIC_Z, "not a z-periodic blob (header word 6 = %d)" % hdr[6]
+    return (extruded_solve_reference3d if hdr[0] == FD3E_MAGIC else direct_solve_reference3d)(blob, np.asarray(b, dtype=np.float64))

@@ -16,7 +16,10 @@ semi-Lagrangian step smears; S in [0, 1] is its correction strength), for genera
 params.pickle and in the model file as "advection" and "correction_strength" and picked up from there like the force.
 --obstacle sphere|cylinder: the sphere of the scene, or the disc of the 2-D scene extruded along z (karman3d.cylinder_arrays3d: the wake);
 recorded in params.pickle and in the model file as "obstacle" and picked up from there like the force.  --pressure-solver direct_extruded
-solves the cylinder's pressure without iteration (any mask that does not depend on z)."""
+solves the cylinder's pressure without iteration (any mask that does not depend on z).
+--boundaries open|periodic-z: the spanwise axis periodic (Scene3D(boundaries=): the wake in a box periodic along the span), for generation,
+--model roll-out and --train-sol alike; recorded in params.pickle and in the model file as "boundaries" and picked up from there like the
+force.  With --obstacle cylinder it selects --pressure-solver direct_extruded unless another solver is named (auto names none)."""
 import argparse
 import pickle
 
@@ -30,6 +33,7 @@ from sol_amd import karman3d as k3, scene, synthetic
 from sol_amd.precond3d import extruded_solver_refusal3d
 
 OBSTACLES = ("sphere", "cylinder")
+BOUNDARIES = ("open", "periodic-z")
 
 
 def staggered3d(vy, vx, vz):
@@ -63,6 +67,8 @@ def parse_params(argv=None):
     p.add_argument("--pressure-solver", default="auto", choices=k3.PRESSURE_SOLVERS3D,
                    help="direct (capacitance blob), cg (preconditioned CG, any mask), auto (direct where it builds, else cg) or direct_extruded "
                         "(opt-in: the direct solve for a mask that does not depend on z, such as --obstacle cylinder)")
+    p.add_argument("--boundaries", default=None, choices=BOUNDARIES, help="open, or periodic-z: the spanwise axis periodic; default: open, or what "
+                   "the --model file recorded")
     add_buoyancy_arg(p, ncomp=3)
     add_substeps_arg(p, bound="1/6")
     add_advection_arg(p, where="")
@@ -87,6 +93,13 @@ def apply_model_record(params, record=None):
             raise SystemExit("--obstacle %s contradicts the obstacle recorded in %s (%s)" % (params["obstacle"], params["model"], record["obstacle"]))
         params["obstacle"] = record["obstacle"]
     params["obstacle"] = params.get("obstacle") or "sphere"
+    if record is not None and "boundaries" in record:
+        if params.get("boundaries") is not None and params["boundaries"] != record["boundaries"]:
+            raise SystemExit("--boundaries %s contradicts the boundaries recorded in %s (%s)" % (params["boundaries"], params["model"], record["boundaries"]))
+        params["boundaries"] = record["boundaries"]
+    params["boundaries"] = params.get("boundaries") or "open"
+    if params["boundaries"] == "periodic-z" and params["obstacle"] == "cylinder" and not params.get("obstacle_mask") and params.get("pressure_solver", "auto") == "auto":
+        params["pressure_solver"] = "direct_extruded"       # (the dense periodic blob refuses an obstacle that spans the axis on all but small grids)
     if record is not None and "buoyancy" in record:
         params["buoyancy"] = agreed_buoyancy(record["buoyancy"], params["buoyancy"], params["model"])
     if record is not None and "diffusion_substeps" in record:
@@ -112,7 +125,8 @@ def main(argv=None):
     active = np.load(params["obstacle_mask"]) if params["obstacle_mask"] else None
     if active is None and params["obstacle"] == "cylinder":
         active = k3.cylinder_arrays3d(Y, X, Z, length=float(params["len"]))[0]
-    sc = k3.Scene3D(Y, X, Z, length=float(params["len"]), device=dev, active=active, pressure_solver=params["pressure_solver"])
+    sc = k3.Scene3D(Y, X, Z, length=float(params["len"]), device=dev, active=active, pressure_solver=params["pressure_solver"],
+                    **({} if params["boundaries"] == "open" else {"boundaries": params["boundaries"]}))
     buoyancy, nsub = params["buoyancy"], params["diffusion_substeps"]
     adv = {"advection": params["advection"], "correction_strength": params["correction_strength"]}
     sim = k3.Karman3DFlow(sc, 1, buoyancy=buoyancy, diffusion_substeps=nsub, **adv)
@@ -136,6 +150,7 @@ def main(argv=None):
         hint = " (the mask does not depend on z: --pressure-solver direct_extruded solves it without iteration)"
     log.info("pressure solver: %s%s" % (sc.pressure_solver, hint))
     log.info("obstacle: %s" % (params["obstacle_mask"] or params["obstacle"]))
+    log.info("boundaries: %s" % params["boundaries"])
     log.info("buoyancy: %s" % (buoyancy,))
     log.info("diffusion substeps: %d" % nsub)
     log.info("advection: %s (correction strength %g)" % (adv["advection"], adv["correction_strength"]))
@@ -174,7 +189,7 @@ def main(argv=None):
             log.info("train step {:04d}: loss={}".format(it + 1, loss))
         if path:
             torch.save({"name": net.name, "weights": [torch.as_tensor(a) for a in net.get_weights()], "std_v": std_v,
-                        "std_re": max(params["re"], 1.0), "buoyancy": buoyancy, "diffusion_substeps": nsub, "obstacle": params["obstacle"], **adv}, path + "/model3d.pt")
+                        "std_re": max(params["re"], 1.0), "buoyancy": buoyancy, "diffusion_substeps": nsub, "obstacle": params["obstacle"], "boundaries": params["boundaries"], **adv}, path + "/model3d.pt")
     return path if path else loss
 
 
