@@ -788,6 +788,25 @@ def to_staggered3d(t):
 # ---------------------------------------------------------------------------------------------------------------------
 # model_mars_moon with Conv3D(5) layers
 # ---------------------------------------------------------------------------------------------------------------------
+def net3d_shape_reason(Y, X, Z, train=True):
+    """None where the correction network runs on a [Y, X, Z] grid, else the reason it does not (a pure function: no device, no library).
+    The network's convolutions run over the (X, Z) planes with Z as the row: check_shape of csrc/conv5x5.hip takes rows that divide 64
+    -- 64 / Z image rows then share a tile, so X must be a multiple of 64 / Z -- or that are a multiple of 64 pixels long; the Conv3D entry
+    points need three planes (sol_conv3d: D >= 3); and the batched weight gradients of the reverse sweep take rows up to 64 pixels
+    (bww_launch of csrc/conv5x5.hip), so beyond Z = 64 only the forward network (a roll-out) runs."""
+    Y, X, Z = int(Y), int(X), int(Z)
+    if Y < 3 or X < 1:
+        return "Y = %d, X = %d: the 5 x 5 x 5 convolutions need Y >= 3 planes of X >= 1 rows" % (Y, X)
+    if Z < 4 or not ((Z <= 64 and 64 % Z == 0) or Z % 64 == 0):
+        return "Z = %d: the rows of the (X, Z) planes must be 4, 8, 16, 32 or 64 pixels long, or a multiple of 64" % Z
+    if Z < 64 and X % (64 // Z) != 0:
+        return "X = %d with Z = %d: 64/Z = %d rows of a plane share one tile, so X must be a multiple of 64/Z" % (X, Z, 64 // Z)
+    if train and Z > 64:
+        return ("Z = %d: the weight gradients of the reverse sweep take Z <= 64 (the batched forms of the 5 x 5 weight gradient); "
+                "a roll-out (Karman3DRollout, NetSchedule3D(train=False)) runs at this width" % Z)
+    return None
+
+
 class MarsMoon3D:
     """12 Conv3D(5, padding='same') layers, 32 features, five residual blocks (karman_train.py:101-138 in 3-D): 4 -> 32,
     10 x 32 -> 32, 32 -> 3; 1 308 355 parameters in ONE flat fp32 buffer in Keras get_weights() order (kernels DHWIO).
@@ -1146,6 +1165,9 @@ class Karman3DTrainer:
         _lib.require_gpu()
         self.lib = _lib.load()
         self.net, self.scene, self.B, self.ms = net, scene, B, msteps
+        # the network's launches, packed weights and weight-gradient partials at this shape -- first: a grid the network does not take
+        # (net3d_shape_reason) is refused here, before a simulator or a buffer exists
+        self.sch = net.schedule(B, scene.Y, scene.X, scene.Z)
         assert glue in ("fused", "torch")
         self.glue = glue          # reverse-sweep glue of the manual schedule: sol_karman3d_correct_bwd / _feature_bwd, or the torch elementwise composition
         self.sim = Karman3DFlow(scene, B, dt=dt, res=res, buoyancy=buoyancy, diffusion_substeps=diffusion_substeps, advection=advection,
@@ -1179,7 +1201,6 @@ class Karman3DTrainer:
         if schedule not in ("manual", "autograd"):
             raise ValueError("schedule must be 'manual' or 'autograd'")
         self.schedule = schedule
-        self.sch = net.schedule(B, Y, X, Z)     # the network's launches, packed weights and weight-gradient partials at this shape
 
     def _unrolled(self):
         if self.schedule == "manual":
@@ -1352,6 +1373,8 @@ class Karman3DRollout:
         _lib.require_gpu()
         self.lib = _lib.load()
         self.net, self.scene, self.B = net, scene, B
+        # forward only, in its own persistent buffers -- first: a grid the network does not take (net3d_shape_reason) is refused here
+        self.sch = NetSchedule3D(net, B, scene.Y, scene.X, scene.Z, train=False)
         self.sim = Karman3DFlow(scene, B, dt=dt, res=res, buoyancy=buoyancy, diffusion_substeps=diffusion_substeps, advection=advection,
                                 correction_strength=correction_strength, **solver)
         self.std_v = tuple(float(v) for v in std_v)
@@ -1360,7 +1383,6 @@ class Karman3DRollout:
         dev = scene.active.device
         Y, X, Z = scene.Y, scene.X, scene.Z
         self.feat = torch.empty(B, Y, X, Z, 4, dtype=torch.float32, device=dev)
-        self.sch = NetSchedule3D(net, B, Y, X, Z, train=False)      # forward only, in its own persistent buffers
         self.out = self.sch.out
 
     def correction(self):

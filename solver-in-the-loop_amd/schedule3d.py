@@ -18,7 +18,7 @@ import torch
 
 from . import _lib
 from .karman3d import (_pack3d, _pack3d_thin, _pack3d_thin_out, _pad_ch, conv3d, conv3d_bwd_weight, conv3d_thin, conv3d_thin_bwd_weight,
-                       conv3d_thin_out)
+                       conv3d_thin_out, net3d_shape_reason)
 
 
 class _Unit:
@@ -32,6 +32,9 @@ class NetSchedule3D:
     def __init__(self, net, B, Y, X, Z, train=True):
         """train=False (a roll-out: forward only): no backward-data packs, no weight-gradient state, and forward() runs in persistent
         buffers -- three rotating 32-channel tensors, the output, the absmax slots and one thin-layer workspace."""
+        why = net3d_shape_reason(Y, X, Z, train)          # before anything is allocated or launched
+        if why is not None:
+            raise _lib.SolError("NetSchedule3D(%s) at %d x %d x %d: %s" % ("train=True" if train else "train=False", Y, X, Z, why))
         _lib.require_gpu()
         lib = _lib.load()
         if net.cin > 4 or not net.params.is_cuda:

@@ -117,10 +117,14 @@ def main(argv=None):
     params = parse_params(argv)
     blob = torch.load(params["model"], map_location="cpu") if params["model"] else None
     params = apply_model_record(params, blob)
-    select_gpu(params["gpu"])
-    log = logger()
     res = params["res"]
     Y, X, Z = 2 * res, res, res
+    if blob is not None or params["train_sol"]:       # a grid the corrector does not take: say so before a device is asked for or a frame generated
+        why = k3.net3d_shape_reason(Y, X, Z, train=bool(params["train_sol"]))
+        if why is not None:
+            raise SystemExit("karman3d.py: the correction network does not run at %d x %d x %d -- %s" % (Y, X, Z, why))
+    select_gpu(params["gpu"])
+    log = logger()
     dev = "cuda"
     active = np.load(params["obstacle_mask"]) if params["obstacle_mask"] else None
     if active is None and params["obstacle"] == "cylinder":
