@@ -12,6 +12,18 @@
  *   - every function returns 0 on success, <0 on error; sol_last_error() gives the text
  *     (thread local).  Nothing is allocated inside: all buffers, including workspaces,
  *     are caller-owned DEVICE pointers (fp32 unless noted).
+ *   - workspaces are SCRATCH: their contents on entry are ignored (any bit pattern, NaN and stale results of an earlier call
+ *     included; whatever an entry point needs cleared it clears in its own launches) and their contents on exit are unspecified.
+ *     Every element of every output is written, so outputs may be uninitialised memory too.  The exceptions are named where
+ *     they occur: buffers documented as accumulated onto (`accumulate` flags, g_re / g_vy / g_vx "to add onto"), the warm-start
+ *     guess of sol_karman_step_fwd_large_cg_warm (read, then overwritten with the step's pressure), absmax slots and
+ *     weight-gradient partials the caller zeroes -- none of these is part of a workspace -- and ONE region that is: under the
+ *     opt-in cnn_persistent the hand-off flags of the persistent CNN launches live inside the workspace of sol_train_fwd_bwd /
+ *     sol_rollout, and the library zeroes them once, when a control word in that workspace does not hold the configuration's
+ *     magic value -- stale contents that happen to hold it are the one case where the contents on entry matter, so with that
+ *     option on zero the workspace before its first use (k3d_conv_persist likewise: its flag region is zero before first use).
+ *     tests/test_gpu_poison.py holds the solver steps, adjoints, pressure solves, trainers and roll-outs to this, under the
+ *     default options, with four fill patterns.
  *   - `stream` is a hipStream_t passed as void*; calls are asynchronous on that stream.  The only
  *     process-wide mutable state is the option table behind sol_set_option() (kernel-variant
  *     selection, read at every call) and the launch profiler (sol_prof_begin/end); the library never
