@@ -695,6 +695,24 @@ int sol_conv5x5_cols(void* stream, const float* x, const float* packed, const fl
                      int32_t B, int32_t H, int32_t W, int32_t WV, int32_t cin, int32_t cout,
                      int32_t epilogue, float slope, const uint32_t* x_absmax, uint32_t* y_absmax);
 
+/* CIRCULAR PADDING of the 5x5 convolutions on a periodic scene (csrc/conv_halo.hip).  The convolution kernels pad with zeros; on a
+ * periodic axis the network runs in buffers that carry a two-pixel HALO on either side of that axis instead, and this launch refreshes
+ * the halo between the convolutions.  With py, px in {0, 1} from periodic_bits (2 = y, 4 = x, 6 = both, as for sol_karman_seam_sync; 0:
+ * nothing is launched) an [H, W] image lives in buf [B, H + 4 py, P, C]: valid pixels at rows [2 py, 2 py + H) and columns
+ * [2 px, 2 px + W), the halo two rows / columns on either side, columns >= W + 4 px the zero pad of the pitched layout.  Every
+ * convolution is sol_conv5x5_cols at the pitch P with WV = W + 4 px and H + 4 py rows: its halo outputs (computed with zeros beyond the
+ * buffer edge) are wrong and are overwritten by the next call of this function; its valid outputs are the circular convolution, because
+ * their stencils read halos that hold wrapped copies.
+ *   mode 0 (wrap): every halo cell = the valid cell at its index modulo H / W (a true modulo: any H, W >= 1; with both axes periodic the
+ *                  2x2 corners come from the diagonally opposite corners).
+ *   mode 1 (zero): every halo cell = 0 -- the dz operand of sol_conv5x5_bwd_weight, so that only valid pixels contribute to dw and db
+ *                  (x keeps its wrapped halo: dw[k] = sum over valid p of x[p + k] dz[p]).  The backward-data convolution then takes
+ *                  the WRAPPED dz: the adjoint of a circular convolution is the circular correlation.
+ * Valid cells and pad columns are never written.  C: a multiple of 4 up to 32; P: a multiple of 64, P >= W + 4 px.  One launch, vector
+ * stores, no atomics, no host synchronisation: capturable.  SOL_ERR_ARG with a message: NULL buf, P < W + 4 px, P % 64 != 0, bits other
+ * than 0 / 2 / 4 / 6, a mode other than 0 / 1, a C it does not take. */
+int sol_conv_halo(void* stream, float* buf, int32_t B, int32_t H, int32_t W, int32_t P, int32_t C, int32_t periodic_bits, int32_t mode);
+
 /* dW[5,5,cin,cout] += sum_px x[px+tap] * dz[px];  db[cout] += sum_px dz[px].
  * `partial` is a caller workspace of sol_conv5x5_bwd_weight_ws_floats() floats that the
  * caller zeroes once and may reuse to ACCUMULATE over many calls (the unrolled steps share

@@ -27,6 +27,7 @@ class ConvNet:
     name = "net"
     layer_channels = ()
     slope = 0.3
+    conv_padding = "zeros"      # what the model was trained with ("zeros" | "circular"): a record save() / load() carry, set by the training script
 
     def __init__(self, cin=3, cout=2, seed=0, device="cuda"):
         self.cin, self.cout = cin, cout
@@ -67,10 +68,11 @@ class ConvNet:
         other = type(self)(self.cin, self.cout, 0, self.params.device)
         with torch.no_grad():
             other.params.copy_(self.params)
+        other.conv_padding = self.conv_padding
         return other
 
     def save(self, path):
-        torch.save({"name": self.name, "cin": self.cin, "cout": self.cout,
+        torch.save({"name": self.name, "cin": self.cin, "cout": self.cout, "conv_padding": self.conv_padding,
                     "weights": [torch.as_tensor(w) for w in self.get_weights()]}, path)
 
     @classmethod
@@ -89,6 +91,7 @@ class ConvNet:
         blob = torch.load(path, map_location="cpu")
         net = MODELS[blob["name"]](blob["cin"], blob["cout"], device=device)
         net.set_weights([w.numpy() for w in blob["weights"]])
+        net.conv_padding = blob.get("conv_padding", "zeros")
         return net
 
     def summary(self, print_fn=print):
@@ -110,6 +113,27 @@ def _conv_form(x, scaled, nslots):
     return lambda x_, w, b, r, act, s, i, o: ops.conv5x5_scaled(x_, w, b, r, act, s, None if i is None else am[i], None if o is None else am[o])
 
 
+def _circular_form(padding, periodic, scaled):
+    """padding="circular", periodic=(py, px): conv(...) of _conv_form composed from ops.conv5x5_circular (the linear layer, padded
+    circularly along the periodic axes) and torch operations for the skip and the LeakyReLU -- the autograd cross-check of
+    NetSchedule2D(padding="circular").  None for padding="zeros"."""
+    if padding not in ("zeros", "circular"):
+        raise ValueError("padding must be 'zeros' or 'circular' (got %r)" % (padding,))
+    if padding == "zeros":
+        return None
+    if periodic is None or not any(periodic):
+        raise ValueError("padding='circular' needs a periodic axis: periodic=(py, px) with one of them true (got %r)" % (periodic,))
+    if scaled:
+        raise ValueError("padding='circular' composes ops.conv5x5_circular; scaled=True (the absmax hand-over of ops.conv5x5_scaled) does not apply")
+
+    def conv(x, w, b, r, act, s, i, o):
+        z = ops.conv5x5_circular(x, w, b, periodic)
+        if r is not None:
+            z = z + r
+        return torch.nn.functional.leaky_relu(z, s) if act else z
+    return conv
+
+
 class MarsMoon(ConvNet):
     """model_mars_moon, karman_train.py:101-138: 12 convs, 260,354 parameters."""
     name = "mars_moon"
@@ -118,10 +142,10 @@ class MarsMoon(ConvNet):
     def channels(cin, cout):
         return [cin] + [32] * 11 + [cout]
 
-    def __call__(self, x, flat=None, scaled=False):
+    def __call__(self, x, flat=None, scaled=False, padding="zeros", periodic=None):
         p = self.tensors(flat)
         s = self.slope
-        conv = _conv_form(x, scaled, 11)
+        conv = _circular_form(padding, periodic, scaled) or _conv_form(x, scaled, 11)
         h = conv(x, p[0], p[1], None, True, s, None, 0)
         for k in range(5):
             a = conv(h, p[2 + 4 * k], p[3 + 4 * k], None, True, s, 2 * k, 2 * k + 1)
@@ -140,9 +164,9 @@ class Mercury(ConvNet):
     def channels(cin, cout):
         return [cin, 32, 64, cout]
 
-    def __call__(self, x, flat=None, scaled=False):
+    def __call__(self, x, flat=None, scaled=False, padding="zeros", periodic=None):
         p = self.tensors(flat)
-        conv = _conv_form(x, scaled, 3)
+        conv = _circular_form(padding, periodic, scaled) or _conv_form(x, scaled, 3)
         h = conv(x, p[0], p[1], None, True, 0.0, None, 0)
         b3a, b3b = ops.split_flat(p[3], (0, 32, 64))           # (1-D halves: not plain slices, see ConvNet.tensors)
         ha = conv(h, p[2][..., :32].contiguous(), b3a, None, True, 0.0, 0, 1)

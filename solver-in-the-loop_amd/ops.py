@@ -1195,6 +1195,78 @@ def conv5x5_scaled(x, w, b, residual=None, lrelu=False, slope=0.3, xmax=None, ym
     return Conv5x5ScaledFn.apply(x, w, b, residual, lrelu, slope, xmax, ymax)
 
 
+def conv_halo(buf, H, W, periodic, mode):
+    """sol_conv_halo in place on buf [B, H + 4 py, P, C] (include/sol_hip.h, "CIRCULAR PADDING"): mode "wrap" / "zero".  periodic: the
+    pair (py, px) or the bits 2 (y) | 4 (x).  -> buf"""
+    bits = periodic if isinstance(periodic, int) else periodic_bits(periodic)
+    B, _, P, c = buf.shape
+    check(_lib.load().sol_conv_halo(stream(), ptr(buf), B, int(H), int(W), P, c, int(bits), {"wrap": 0, "zero": 1}[mode]))
+    return buf
+
+
+class Conv5x5CircularFn(torch.autograd.Function):
+    """y = conv5x5(x, w) + b with CIRCULAR padding along the periodic axes: one linear layer, dense [B,H,W,c] in and out -- the
+    cross-check of schedule2d.NetSchedule2D(padding="circular"), kept apart from its buffer handling on purpose.  It builds its own
+    halo buffers (include/sol_hip.h, "CIRCULAR PADDING"): forward = wrap -> sol_conv5x5_cols -> crop; backward = zero -> weight gradient
+    -> wrap -> backward-data convolution -> crop.  The skip and the activation of a network are torch operations around it."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, bits):
+        _lib.require_gpu()
+        cin, cout = w.shape[2], w.shape[3]
+        assert cin in (1, 2, 3, 4, 32), "conv5x5 supports <=4 or 32 input channels"
+        x = _lib.f32(x); w = _lib.f32(w); b = _lib.f32(b)
+        B, H, W, _ = x.shape
+        r0, c0 = 2 * bool(bits & PERIODIC_Y), 2 * bool(bits & PERIODIC_X)
+        geo = (B, H, W, r0, c0, 64 * ((W + 2 * c0 + 63) // 64))
+        xb = Conv5x5CircularFn._halo_buffer(x, geo, 4 if cin <= 4 else 32)
+        conv_halo(xb, H, W, bits, "wrap")
+        yb = conv5x5_cols_raw(xb, _pack(w, cin, cout, CONV_FWD), b, None, None, cout, EPI_NONE, 0.0, W + 2 * c0)
+        ctx.save_for_backward(xb, w)
+        ctx.meta = (cin, cout, bits, geo)
+        return yb[:, r0:r0 + H, c0:c0 + W].contiguous()
+
+    @staticmethod
+    def _halo_buffer(t, geo, c):
+        """zeros [B, H + 2 r0, P, c] with t [B,H,W,<=c] in the valid pixels (a strided copy: a kernel)"""
+        B, H, W, r0, c0, P = geo
+        buf = torch.zeros(B, H + 2 * r0, P, c, dtype=torch.float32, device=t.device)
+        buf[:, r0:r0 + H, c0:c0 + W, :t.shape[-1]].copy_(t)
+        return buf
+
+    @staticmethod
+    def backward(ctx, gy):
+        lib = _lib.load()
+        xb, w = ctx.saved_tensors
+        cin, cout, bits, geo = ctx.meta
+        B, H, W, r0, c0, P = geo
+        assert cout in (2, 32), "conv5x5 backward-weight supports 2 or 32 output channels"
+        HB, cin_k = H + 2 * r0, xb.shape[-1]
+        gb = Conv5x5CircularFn._halo_buffer(gy, geo, 4 if cout <= 4 else 32)
+        # weight / bias gradient: x with its wrapped halo, dz zero in the halo -- the valid pixels only (the buffer is fresh, so the
+        # launch changes nothing here; it is the schedule's sequence, run as the schedule runs it)
+        conv_halo(gb, H, W, bits, "zero")
+        dz = gb if gb.shape[-1] == cout else gb[..., :cout].contiguous()
+        part = torch.zeros(lib.sol_conv5x5_bwd_weight_ws_floats(B, HB, P, cin_k, cout), dtype=torch.float32, device=xb.device)
+        check(lib.sol_conv5x5_bwd_weight(stream(), ptr(xb), ptr(dz), ptr(part), B, HB, P, cin_k, cout))
+        dw = torch.empty_like(w)
+        db = torch.empty(cout, dtype=torch.float32, device=xb.device)
+        check(lib.sol_conv5x5_bwd_weight_reduce(stream(), ptr(part), ptr(dw), ptr(db), B, HB, P, cin, cout, 0))
+        # data gradient: the circular correlation = the backward-data convolution of the wrapped dz
+        conv_halo(gb, H, W, bits, "wrap")
+        dxb = conv5x5_cols_raw(gb, _pack(w, cout, cin, CONV_BWD_DATA), None, None, None, cin, EPI_NONE, 0.0, W + 2 * c0)
+        return dxb[:, r0:r0 + H, c0:c0 + W].contiguous(), dw, db, None
+
+
+def conv5x5_circular(x, w, b, periodic):
+    """conv5x5(x, w) + b, NHWC, w in Keras HWIO layout, padded circularly along the axes of periodic = (py, px) and with zeros along the
+    others; any H, W >= 1.  Differentiable in x, w and b."""
+    bits = periodic_bits(periodic)
+    if not bits:
+        raise _lib.SolError("conv5x5_circular: periodic=%r names no periodic axis (ops.conv5x5 pads with zeros)" % (tuple(periodic),))
+    return Conv5x5CircularFn.apply(x, w, b, bits)
+
+
 # --------------------------------------------------------------------------------------
 # Burgers step
 # --------------------------------------------------------------------------------------

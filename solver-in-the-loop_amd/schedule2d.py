@@ -48,7 +48,7 @@ def row_pitch(H, W):
 
 
 class NetSchedule2D:
-    def __init__(self, net, B, H, W, train=True, any_width=False):
+    def __init__(self, net, B, H, W, train=True, any_width=False, padding="zeros", periodic=(False, False)):
         """train=False (a roll-out: forward only): no weight-gradient partial buffers, no backward-data packs, and the absmax slots of the
         forward are persistent buffers cleared by one library launch per call (no torch fill between the launches).
 
@@ -57,7 +57,21 @@ class NetSchedule2D:
         a zero-initialised [B,H,P,4] buffer, every convolution is sol_conv5x5_cols (the 64-pixel-tile kernels with a column-masked
         epilogue: the pad columns of every output are written as zeros, so the next layer reads them as its SAME padding), and the
         weight gradient is the unchanged sol_conv5x5_bwd_weight at the pitch (zero pad columns of x and dz add exact zeros to dw / db).
-        forward / backward take and return DENSE [B,H,W,c] tensors.  With any_width=False nothing changes."""
+        forward / backward take and return DENSE [B,H,W,c] tensors.  With any_width=False nothing changes.
+
+        padding="circular", periodic=(py, px): the convolutions pad CIRCULARLY along the periodic axes (include/sol_hip.h, "CIRCULAR
+        PADDING").  Whatever any_width says, the network runs in HALO buffers [B, H + 4 py, P, c], P = 64 * ceil((W + 4 px) / 64): the
+        valid pixels at rows [2 py, 2 py + H) and columns [2 px, 2 px + W), two halo rows / columns on either side of a periodic axis,
+        zero pad columns beyond.  Every convolution is sol_conv5x5_cols at the pitch with WV = W + 4 px; what it writes into the halo
+        (computed with zeros beyond the buffer edge) is wrong and is replaced by one sol_conv_halo launch: `wrap` on every activation
+        and on a dz before its backward-data convolution, `zero` on a dz before its weight gradient (x wrapped, dz zero in the halo:
+        dw and db sum over the valid pixels only).  padding="zeros" (the default): nothing changes."""
+        if padding not in ("zeros", "circular"):
+            raise _lib.SolError("NetSchedule2D: padding must be 'zeros' or 'circular' (got %r)" % (padding,))
+        py, px = (bool(periodic[0]), bool(periodic[1]))
+        self.circular = padding == "circular"
+        if self.circular and not (py or px):
+            raise _lib.SolError("NetSchedule2D: padding='circular' needs a periodic axis (periodic=%r)" % (tuple(periodic),))
         if net.name not in ("mars_moon", "mercury"):
             raise _lib.SolError("NetSchedule2D: no hand-written schedule for network %r" % net.name)
         _lib.require_gpu()
@@ -65,6 +79,11 @@ class NetSchedule2D:
         self.net, self.B, self.H, self.W = net, int(B), int(H), int(W)
         self.P = row_pitch(H, W) if any_width else self.W      # pixels per buffer row
         self.pitched = self.P != self.W
+        self.HB, self.WV, self.r0, self.c0, self.halo_bits = self.H, self.W, 0, 0, 0     # buffer rows, data pixels per row, where the image sits
+        if self.circular:
+            self.r0, self.c0, self.halo_bits = 2 * py, 2 * px, 2 * py + 4 * px
+            self.HB, self.WV = self.H + 2 * self.r0, self.W + 2 * self.c0
+            self.P, self.pitched = 64 * ((self.WV + 63) // 64), True
         self.scaled = self.P % 64 == 0               # 64-pixel rows: the split-precision kernels + absmax hand-over
         self.train = bool(train)
         if net.cin > 4:
@@ -80,7 +99,7 @@ class NetSchedule2D:
         for cin, cout in dims:
             u = _Unit()
             u.cin, u.cout, u.cin_k = cin, cout, (4 if cin <= 4 else 32)
-            u.ws = int(lib.sol_conv5x5_bwd_weight_ws_floats(self.B, self.H, self.P, u.cin_k, cout)) if self.train else 0
+            u.ws = int(lib.sol_conv5x5_bwd_weight_ws_floats(self.B, self.HB, self.P, u.cin_k, cout)) if self.train else 0
             total += (u.ws + 3) // 4 * 4
             u.pf = f(lib.sol_conv5x5_packed_floats(cin, cout, ops.CONV_FWD))
             u.pb = f(lib.sol_conv5x5_packed_floats(cout, cin, ops.CONV_BWD_DATA)) if self.train else None
@@ -93,8 +112,8 @@ class NetSchedule2D:
         self._zero_bias = torch.zeros(net.cout, dtype=torch.float32, device=dev)
         if self.pitched:
             # the dense input / output gradient land in the valid columns of these; nothing ever writes their pad columns or spare channels
-            self._xin = torch.zeros(self.B, self.H, self.P, 4, dtype=torch.float32, device=dev)
-            self._gin = torch.zeros(self.B, self.H, self.P, 4, dtype=torch.float32, device=dev) if self.train else None
+            self._xin = torch.zeros(self.B, self.HB, self.P, 4, dtype=torch.float32, device=dev)
+            self._gin = torch.zeros(self.B, self.HB, self.P, 4, dtype=torch.float32, device=dev) if self.train else None
         # kernels / biases: views of the flat parameter buffer (updated in place by Adam: the addresses are stable), or persistent copies of the
         # halves of model_mercury's 32 -> 64 / 64 -> 2 kernels (refreshed by begin_step)
         p = [t.detach() for t in net.tensors()]
@@ -121,7 +140,7 @@ class NetSchedule2D:
                            _int_array([u.cout for u in self.units] + [u.cin for u in self.units]), _int_array([ops.CONV_FWD] * n + [ops.CONV_BWD_DATA] * n),
                            _ptr_array([u.pf for u in self.units] + [u.pb for u in self.units]))
         self._reduce_args = (n, _ptr_array([u.part for u in self.units]), _ptr_array([u.dw for u in self.units]), _ptr_array([u.db for u in self.units]),
-                             self.B, self.H, self.P, _int_array([u.cin for u in self.units]), _int_array([u.cout for u in self.units]), 0)
+                             self.B, self.HB, self.P, _int_array([u.cin for u in self.units]), _int_array([u.cout for u in self.units]), 0)
 
     # ---- once per training step -------------------------------------------------------------------------------------------
     def begin_step(self):
@@ -141,7 +160,7 @@ class NetSchedule2D:
         sl = float(self.net.slope)
         if self.pitched:
             check(self.lib.sol_conv5x5_cols(stream(), ptr(x), ptr(packed), ptr(bias), ptr(residual), ptr(act_ref), ptr(y),
-                                            B, H, W, self.W, cin, cout, epi, sl, ptr(xmax), ptr(ymax)))
+                                            B, H, W, self.WV, cin, cout, epi, sl, ptr(xmax), ptr(ymax)))
         elif self.scaled:
             check(self.lib.sol_conv5x5_scaled(stream(), ptr(x), ptr(packed), ptr(bias), ptr(residual), ptr(act_ref), ptr(y),
                                               B, H, W, cin, cout, epi, sl, ptr(xmax), ptr(ymax)))
@@ -152,7 +171,7 @@ class NetSchedule2D:
 
     def _bww(self, u, xk, dz):
         """u.part += the weight-gradient partial sums of this step"""
-        check(self.lib.sol_conv5x5_bwd_weight(stream(), ptr(xk), ptr(dz), ptr(u.part), self.B, self.H, self.P, u.cin_k, u.cout))
+        check(self.lib.sol_conv5x5_bwd_weight(stream(), ptr(xk), ptr(dz), ptr(u.part), self.B, self.HB, self.P, u.cin_k, u.cout))
 
     def _slots(self, n, dev):
         if not self.train and self.scaled:          # forward only: the persistent slots, cleared by a library launch
@@ -162,37 +181,56 @@ class NetSchedule2D:
 
     # ---- pitched rows: dense <-> pitched copies (kernels: _lib.dcopy_ is a strided copy_ or sol_copy_words, never a memcpy node) ----
     def _pad_in(self, buf, x):
-        """buf[:, :, :W, :c] = x [B,H,W,c]; the pad columns and the spare channels of buf stay zero"""
-        _lib.dcopy_(buf[:, :, :self.W, :x.shape[-1]], x)
+        """the valid pixels of buf = x [B,H,W,c]; the pad columns and the spare channels of buf stay zero (the halo of a circular buffer
+        is the caller's: _wrap / _zero_halo)"""
+        _lib.dcopy_(buf[:, self.r0:self.r0 + self.H, self.c0:self.c0 + self.W, :x.shape[-1]], x)
         return buf
 
     def _crop(self, y):
-        """dense [B,H,W,c] copy of the valid columns of y [B,H,P,c]"""
-        return _lib.dcopy_(torch.empty(self.B, self.H, self.W, y.shape[-1], dtype=torch.float32, device=y.device), y[:, :, :self.W])
+        """dense [B,H,W,c] copy of the valid pixels of y [B,HB,P,c]"""
+        return _lib.dcopy_(torch.empty(self.B, self.H, self.W, y.shape[-1], dtype=torch.float32, device=y.device),
+                           y[:, self.r0:self.r0 + self.H, self.c0:self.c0 + self.W])
+
+    # ---- circular padding: the halo of a buffer, refreshed in place by one launch (nothing is launched with padding="zeros") ----
+    # The absmax slots a producer publishes include its wrong halo outputs.  They remain upper bounds of what the consumer reads: a
+    # refreshed halo holds copies of valid values (or zeros), all of which the slots cover, and an over-reported maximum costs fp16 range
+    # only (include/sol_hip.h, sol_conv5x5_bwd_weight_segments).
+    def _halo(self, buf, mode):
+        if self.circular:
+            check(self.lib.sol_conv_halo(stream(), ptr(buf), self.B, self.H, self.W, self.P, buf.shape[-1], self.halo_bits, mode))
+        return buf
+
+    def _wrap(self, buf):
+        """halo := the valid pixels at the wrapped index (an activation; a dz before its backward-data convolution)"""
+        return self._halo(buf, 0)
+
+    def _zero_halo(self, buf):
+        """halo := 0 (a dz before its weight gradient: only valid pixels contribute)"""
+        return self._halo(buf, 1)
 
     # ---- forward ------------------------------------------------------------------------------------------------------------
     def forward(self, x):
         """x [B,H,W,cin] -> (out [B,H,W,cout], state for backward)"""
         if self.pitched:
-            xk = self._pad_in(self._xin, _lib.f32(x.detach()))
+            xk = self._wrap(self._pad_in(self._xin, _lib.f32(x.detach())))
             if self.train:
                 xk = _lib.dclone(xk)                  # the reverse sweep reads this step's input after later steps have overwritten the buffer
         else:
             xk = ops._pad_channels(_lib.f32(x.detach()), 4)
-        U, L, N = self.units, ops.EPI_LRELU, ops.EPI_NONE
+        U, L, N, Wr = self.units, ops.EPI_LRELU, ops.EPI_NONE, self._wrap
         if self.net.name == "mars_moon":
             am = self._slots(11, xk.device)
-            acts = [self._conv(xk, U[0].pf, U[0].b, None, None, 32, L, None, am[0])]
+            acts = [Wr(self._conv(xk, U[0].pf, U[0].b, None, None, 32, L, None, am[0]))]
             for k in range(5):
-                a = self._conv(acts[-1], U[1 + 2 * k].pf, U[1 + 2 * k].b, None, None, 32, L, am[2 * k], am[2 * k + 1])
+                a = Wr(self._conv(acts[-1], U[1 + 2 * k].pf, U[1 + 2 * k].b, None, None, 32, L, am[2 * k], am[2 * k + 1]))
                 acts.append(a)
-                acts.append(self._conv(a, U[2 + 2 * k].pf, U[2 + 2 * k].b, acts[-2], None, 32, L, am[2 * k + 1], am[2 * k + 2]))
+                acts.append(Wr(self._conv(a, U[2 + 2 * k].pf, U[2 + 2 * k].b, acts[-2], None, 32, L, am[2 * k + 1], am[2 * k + 2])))
             out = self._conv(acts[-1], U[11].pf, U[11].b, None, None, self.net.cout, N, am[10], None)
         else:
             am = self._slots(3, xk.device)
-            h = self._conv(xk, U[0].pf, U[0].b, None, None, 32, L, None, am[0])
-            ha = self._conv(h, U[1].pf, U[1].b, None, None, 32, L, am[0], am[1])
-            hb = self._conv(h, U[2].pf, U[2].b, None, None, 32, L, am[0], am[2])
+            h = Wr(self._conv(xk, U[0].pf, U[0].b, None, None, 32, L, None, am[0]))
+            ha = Wr(self._conv(h, U[1].pf, U[1].b, None, None, 32, L, am[0], am[1]))
+            hb = Wr(self._conv(h, U[2].pf, U[2].b, None, None, 32, L, am[0], am[2]))
             oa = self._conv(ha, U[3].pf, U[3].b, None, None, self.net.cout, N, am[1], None)
             out = self._conv(hb, U[4].pf, U[4].b, oa, None, self.net.cout, N, am[2], None)
             acts = [h, ha, hb]
@@ -203,42 +241,44 @@ class NetSchedule2D:
     # ---- reverse sweep ------------------------------------------------------------------------------------------------------
     def backward(self, state, g_out):
         """d loss / d x [B,H,W,cin] for the output gradient g_out [B,H,W,cout]; the weight gradients of this call are added to the layers'
-        partial buffers (end_step reduces them)."""
+        partial buffers (end_step reduces them).  padding="circular", per layer: the dz a convolution hands over has wrong halo values ->
+        zero its halo -> the weight gradient -> wrap it -> the backward-data convolution (the adjoint of a circular convolution is the
+        circular correlation); Z / Wr launch nothing with padding="zeros"."""
         if not self.train:
             raise _lib.SolError("NetSchedule2D(train=False) runs the forward pass only")
         xk, am, acts = state
-        U, D, N = self.units, ops.EPI_DLRELU, ops.EPI_NONE
+        U, D, N, Z, Wr = self.units, ops.EPI_DLRELU, ops.EPI_NONE, self._zero_halo, self._wrap
         g = _lib.f32(g_out).contiguous()
         if self.pitched:
-            g4 = self._pad_in(self._gin, g)
+            g4 = Z(self._pad_in(self._gin, g))        # (the previous call left its wrapped halo in the buffer)
             g = g4[..., :g.shape[-1]].contiguous()    # [B,H,P,cout], zero pad columns: the last layer's dz
         else:
             g4 = ops._pad_channels(g, 4)
         if self.net.name == "mars_moon":
             zm = self._slots(11, xk.device)
             self._bww(U[11], acts[10], g)
-            dz = self._conv(g4, U[11].pb, None, None, acts[10], 32, D, None, zm[10])
+            dz = self._conv(Wr(g4), U[11].pb, None, None, acts[10], 32, D, None, zm[10])
             for k in range(4, -1, -1):
                 a, hprev = acts[1 + 2 * k], acts[2 * k]
-                self._bww(U[2 + 2 * k], a, dz)
-                dz1 = self._conv(dz, U[2 + 2 * k].pb, None, None, a, 32, D, zm[2 * k + 2], zm[2 * k + 1])
-                self._bww(U[1 + 2 * k], hprev, dz1)
-                dz = self._conv(dz1, U[1 + 2 * k].pb, None, dz, hprev, 32, D, zm[2 * k + 1], zm[2 * k])
-            self._bww(U[0], xk, dz)
-            dx = self._conv(dz, U[0].pb, None, None, None, U[0].cin, N, zm[0], None)
+                self._bww(U[2 + 2 * k], a, Z(dz))
+                dz1 = self._conv(Wr(dz), U[2 + 2 * k].pb, None, None, a, 32, D, zm[2 * k + 2], zm[2 * k + 1])
+                self._bww(U[1 + 2 * k], hprev, Z(dz1))
+                dz = self._conv(Wr(dz1), U[1 + 2 * k].pb, None, dz, hprev, 32, D, zm[2 * k + 1], zm[2 * k])
+            self._bww(U[0], xk, Z(dz))
+            dx = self._conv(Wr(dz), U[0].pb, None, None, None, U[0].cin, N, zm[0], None)
             return self._crop(dx) if self.pitched else dx
         h, ha, hb = acts
         zm = self._slots(3, xk.device)
         self._bww(U[3], ha, g)
         self._bww(U[4], hb, g)
-        dha = self._conv(g4, U[3].pb, None, None, ha, 32, D, None, zm[1])
+        dha = self._conv(Wr(g4), U[3].pb, None, None, ha, 32, D, None, zm[1])
         dhb = self._conv(g4, U[4].pb, None, None, hb, 32, D, None, zm[2])
-        self._bww(U[1], h, dha)
-        self._bww(U[2], h, dhb)
-        t = self._conv(dha, U[1].pb, None, None, None, 32, N, zm[1], None)
-        dh = self._conv(dhb, U[2].pb, None, t, h, 32, D, zm[2], zm[0])
-        self._bww(U[0], xk, dh)
-        dx = self._conv(dh, U[0].pb, None, None, None, U[0].cin, N, zm[0], None)
+        self._bww(U[1], h, Z(dha))
+        self._bww(U[2], h, Z(dhb))
+        t = self._conv(Wr(dha), U[1].pb, None, None, None, 32, N, zm[1], None)
+        dh = self._conv(Wr(dhb), U[2].pb, None, t, h, 32, D, zm[2], zm[0])
+        self._bww(U[0], xk, Z(dh))
+        dx = self._conv(Wr(dh), U[0].pb, None, None, None, U[0].cin, N, zm[0], None)
         return self._crop(dx) if self.pitched else dx
 
     # ---- once per training step ---------------------------------------------------------------------------------------------

@@ -29,6 +29,9 @@ def main(argv=None):
     p.add_argument("--stats", default="/tmp/phiflow/data/dataStats.pickle", help="path to datastats")
     p.add_argument("--model", default="/tmp/phiflow/tf/model.pt", help="path to a trained model")
     p.add_argument("--any-width", action="store_true", help="run the correction network on rows of any width (pitched rows with column-masked convolutions) instead of refusing a width the convolutions do not take")
+    p.add_argument("--conv-padding", default=None, choices=["zeros", "circular"],
+                   help="padding of the correction network's convolutions (default: what the model was trained with, recorded in the stats "
+                        "and with the model; an explicit value overrides the record)")
     add_scene_args(p, warm_start=True)
     add_buoyancy_arg(p)
     add_substeps_arg(p, auto=False)
@@ -88,6 +91,13 @@ def main(argv=None):
                            pressure_solver=params["pressure_solver"], multi_launch=multi_launch,
                            boundaries=sol_amd.karman.record_boundaries(rec or {}))
     log.info("pressure solver: %s" % masks.pressure_solver)
+    # the padding of the network's convolutions: the one the model was trained with (dataStats "conv_padding", else the model file's
+    # record; absent: zeros); an explicit flag overrides it
+    conv_padding = data_stats.get("conv_padding") or model.conv_padding
+    if params["conv_padding"] is not None and params["conv_padding"] != conv_padding:
+        log.info("--conv-padding %s overrides the record: the model was trained with %s padding" % (params["conv_padding"], conv_padding))
+        conv_padding = params["conv_padding"]
+    log.info("convolution padding: %s" % conv_padding)
     large = masks.large
     warm = bool(params["cg_warm_start"]) and large and masks.pressure_solver == "cg"
     if params["cg_warm_start"] and not warm:
@@ -96,7 +106,7 @@ def main(argv=None):
     # (a CG scene runs eagerly, every solve stops at convergence; a direct-solve scene replays one captured step)
     ro = sol_amd.make_rollout(model, masks, 1, Y, X, dom.dx[1], data_stats["std"][1], data_stats["ext.std"][0],
                               use_graph=ops.is_direct(masks.pressure_solver), cg_warm_start=warm, any_width=params["any_width"],
-                              buoyancy=buoyancy, diffusion_substeps=nsub, multi_launch=multi_launch, **advection)
+                              buoyancy=buoyancy, diffusion_substeps=nsub, multi_launch=multi_launch, conv_padding=conv_padding, **advection)
     f = lambda a: torch.as_tensor(np.ascontiguousarray(a), dtype=torch.float32, device="cuda").contiguous()
     vy0, vx0 = scene.split_staggered(np.asarray(vn, dtype=np.float32))
     d, vy, vx = f(np.asarray(d0)[..., 0]), f(vy0), f(vx0)

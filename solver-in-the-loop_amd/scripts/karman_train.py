@@ -51,6 +51,9 @@ def main(argv=None):
     p.add_argument("--host-feed", action="store_true", help="assemble every batch on the host and copy it (the reference's feed_dict path) "
                                                             "instead of gathering from the device-resident set")
     p.add_argument("--any-width", action="store_true", help="run the correction network on rows of any width (pitched rows with column-masked convolutions) instead of refusing a width the convolutions do not take")
+    p.add_argument("--conv-padding", default="zeros", choices=["zeros", "circular"],
+                   help="padding of the correction network's convolutions: zeros (the reference's padding='same') or circular (wraps along the "
+                        "periodic axes of the training set's scene; recommended for new periodic work; refused on an open scene)")
     add_scene_args(p)
     add_buoyancy_arg(p)
     add_substeps_arg(p, auto=False)
@@ -140,11 +143,17 @@ def main(argv=None):
                            pressure_solver=params["pressure_solver"], multi_launch=multi_launch,
                            boundaries=sol_amd.karman.record_boundaries(rec or {}))
     log.info("pressure solver: %s" % masks.pressure_solver)
+    conv_padding = params["conv_padding"]
+    if conv_padding == "circular" and not any(masks.periodic):
+        raise ValueError("--conv-padding circular needs a periodic axis, but the scene of the training set has --boundaries open; generate "
+                         "the set with --boundaries periodic / periodic-x / periodic-y, or train with --conv-padding zeros")
+    log.info("convolution padding: %s" % conv_padding)
     # eval('model_'+params['model']) (karman_train.py:394): mars_moon runs the C++ schedule (SolTrainer), mercury the
     # hand-written schedule captured into a hipGraph (GraphTrainer); a domain beyond the one-workgroup grids (-s 1 on a -r 128 set):
     # LargeGridTrainer, either model
     assert params["model"] in sol_amd.model.MODELS, "unknown model %r (have: %s)" % (params["model"], ", ".join(sol_amd.model.MODELS))
     model = sol_amd.model.MODELS[params["model"]](3, 2, seed, dev)
+    model.conv_padding = conv_padding            # travels with the saved model (ConvNet.save)
     model.summary(print_fn=log.info)
     if params["pretf"]:
         log.info("load a pre-trained model: {}".format(params["pretf"]))
@@ -160,6 +169,7 @@ def main(argv=None):
     dataset.dataStats.setdefault("advection", advection["advection"])
     dataset.dataStats.setdefault("correction_strength", advection["correction_strength"])
     dataset.dataStats.setdefault("multi_launch", multi_launch)
+    dataset.dataStats.setdefault("conv_padding", conv_padding)
     if params["resume"] < 1:
         if rank == 0:
             with open(params["tf"] + "/dataStats.pickle", "wb") as f:
@@ -173,7 +183,8 @@ def main(argv=None):
                                  in_std_v=dataset.dataStats["in.std"][1] if "in.std" in dataset.dataStats else None,
                                  out_std_v=dataset.dataStats["out.std"] if "out.std" in dataset.dataStats else None,
                                  pressure_solver=params["pressure_solver"], any_width=params["any_width"], buoyancy=buoyancy,
-                                 diffusion_substeps=nsub, multi_launch=multi_launch, **advection, **flow_kwargs(rec))
+                                 diffusion_substeps=nsub, multi_launch=multi_launch, conv_padding=conv_padding, **advection,
+                                 **flow_kwargs(rec))
     # persistent device buffers: the captured hipGraph keeps their addresses, new data is copied in
     f32 = lambda shape: torch.empty(shape, dtype=torch.float32, device=dev)
     d0, vy0, vx0, re = f32((Bl, Y, X)), f32((Bl, Y + 1, X)), f32((Bl, Y, X + 1)), f32((Bl,))

@@ -126,6 +126,26 @@ def _refuse_periodic(who, masks, use):
                          "serve)" % (who, ops.boundaries_name(masks.periodic), use))
 
 
+CONV_PADDINGS = ("zeros", "circular")
+
+
+def _conv_padding_arg(who, conv_padding, periodic=None, use=None):
+    """conv_padding: "zeros" (the reference's padding='same': the default) or "circular" (the network's convolutions wrap along the
+    periodic axes of the scene: NetSchedule2D(padding="circular")).  periodic: the (py, px) of the masks for a class that serves
+    "circular", None for one that does not (`use` names the class that does).  Refused at construction, by name.  -> the word"""
+    if conv_padding not in CONV_PADDINGS:
+        raise ValueError("%s: conv_padding must be 'zeros' or 'circular' (got %r)" % (who, conv_padding))
+    if conv_padding == "circular":
+        if periodic is None:
+            raise ValueError("%s: conv_padding='circular' pads the network's convolutions circularly along the periodic axes of a scene; this "
+                             "class runs the fused one-workgroup kernels, which are open on all sides.  Use %s on masks built with periodic "
+                             "boundaries" % (who, use))
+        if not any(periodic):
+            raise ValueError("%s: conv_padding='circular' needs a periodic axis, but the masks were built with open boundaries; build them "
+                             "with boundaries='periodic' or a pair (by, bx), or keep conv_padding='zeros'" % who)
+    return conv_padding
+
+
 def _train_cfg(kc, msteps, net, std_v, std_re, in_std_v, out_std_v):
     """TrainCfg with its normalisation fields.  --pretf (karman_train.py:351-355,416-421): separate input / output normalisation of a
     pre-trained supervised model; 0.0 pairs stand for "as std_v"."""
@@ -190,7 +210,7 @@ class SolTrainer(_AdamDP):
                  clip_grad=False, beta1=0.9, beta2=0.999, eps=1e-8, group=None, use_graph=True,
                  cg_rtol=1e-6, cg_atol=1e-9, cg_max_iter=2000, grad_pad="replicate", inflow_order="after",
                  conv_precision="split", comm=None, in_std_v=None, out_std_v=None, buoyancy=None, diffusion_substeps=1,
-                 advection="semi_lagrangian", correction_strength=1.0):
+                 advection="semi_lagrangian", correction_strength=1.0, conv_padding="zeros"):
         """conv_precision: arithmetic of the 32-channel convolutions (library option `conv_precision`):
         "split" (default) fp32-equivalent fp16x3 / bf16x6 operand splits on the 16-bit matrix pipe, "bf16x6",
         or "fp32" = strict fp32 MFMA.  The option is process wide in the library; every call of this trainer sets
@@ -202,6 +222,7 @@ class SolTrainer(_AdamDP):
         _refuse_substeps("SolTrainer", diffusion_substeps, Y, X)
         _refuse_advection("SolTrainer", advection, correction_strength)
         _refuse_periodic("SolTrainer", masks, "LargeGridTrainer")
+        _conv_padding_arg("SolTrainer", conv_padding, use="LargeGridTrainer")
         _lib.require_gpu()
         self.lib = _lib.load()
         self.conv_precision = _conv_precision_code(conv_precision)
@@ -309,10 +330,12 @@ class SolRollout:
     """No-grad roll-out of solver step + CNN correction (karman_apply.py:138-158)."""
 
     def __init__(self, net, masks, B, Y, X, dx, std_v, std_re, dt=1.0, res=None, in_std_v=None, out_std_v=None,
-                 conv_precision="split", diffusion_substeps=1, advection="semi_lagrangian", correction_strength=1.0, **solver):
+                 conv_precision="split", diffusion_substeps=1, advection="semi_lagrangian", correction_strength=1.0, conv_padding="zeros",
+                 **solver):
         _refuse_substeps("SolRollout", diffusion_substeps, Y, X)
         _refuse_advection("SolRollout", advection, correction_strength)
         _refuse_periodic("SolRollout", masks, "LargeGridRollout")
+        _conv_padding_arg("SolRollout", conv_padding, use="LargeGridRollout")
         _lib.require_gpu()
         self.lib = _lib.load()
         self.conv_precision = _conv_precision_code(conv_precision)
@@ -353,7 +376,7 @@ class LargeGridRollout:
 
     def __init__(self, net, masks, B, Y, X, dx, std_v, std_re, dt=1.0, res=None, in_std_v=None, out_std_v=None,
                  conv_precision="split", use_graph=True, cg_warm_start=False, any_width=False, buoyancy=None, diffusion_substeps=1,
-                 advection="semi_lagrangian", correction_strength=1.0, multi_launch=False, **solver):
+                 advection="semi_lagrangian", correction_strength=1.0, multi_launch=False, conv_padding="zeros", **solver):
         """multi_launch=True: a grid the one-workgroup roll-out would serve (Y, X >= 16), on masks built with multi_launch=True; a width
         the convolutions take as it is (schedule2d.row_pitch(Y, X) == X) runs dense, any other needs any_width=True.
         any_width=True: X need not be a multiple of 64 -- the network runs in pitched rows (NetSchedule2D(any_width=True): the features
@@ -362,7 +385,11 @@ class LargeGridRollout:
         (sol_karman_step_fwd_large_buoy: one launch more, captured with the rest; direct and CG scenes, warm start included).
         diffusion_substeps=n: n explicit diffusion substeps per solver step (ops.karman_step_large(diffusion_substeps=n): the
         pre-diffusion launches are part of the captured step).  advection="mac_cormack", correction_strength=s: the solver step advects
-        by the MacCormack scheme (sol_karman_step_fwd_large_adv; captured with the rest)."""
+        by the MacCormack scheme (sol_karman_step_fwd_large_adv; captured with the rest).
+        conv_padding="circular" (periodic masks only): the network's convolutions pad circularly along the periodic axes of the masks
+        (NetSchedule2D(padding="circular"): halo buffers, any width X, the halo launches captured with the rest); "zeros" (the default)
+        is the reference's padding='same' and gives the bits it always gave."""
+        self.conv_padding = _conv_padding_arg("LargeGridRollout", conv_padding, tuple(getattr(masks, "periodic", (False, False))))
         ph = self.physics = ops.StepPhysics.of(buoyancy=buoyancy, diffusion_substeps=diffusion_substeps, advection=advection,
                                                correction_strength=correction_strength, who="LargeGridRollout")
         self.buoyancy, self.diffusion_substeps, self.advection = ph.buoyancy, ph.nsub, ph.advection_kw
@@ -370,7 +397,7 @@ class LargeGridRollout:
         if not ops.beyond_one_workgroup(Y, X) and not self.multi_launch:
             raise ValueError("LargeGridRollout: a %dx%d domain is served by the one-workgroup roll-out -- use SolRollout (make_rollout picks); "
                              "multi_launch=True runs the multi-launch roll-out on it" % (Y, X))
-        if not _width_served(Y, X, any_width, self.multi_launch):
+        if not _width_served(Y, X, any_width or self.conv_padding == "circular", self.multi_launch):
             raise ValueError("LargeGridRollout: the convolutions of a large domain take rows of X %% 64 == 0 cells (got %dx%d); "
                              "no roll-out class serves this grid (KarmanFlow.step advances it without the network)" % (Y, X))
         # periodic masks (SceneMasks(boundaries=...)): the plain physics, a direct solve; the correction leaves the duplicate plane of a
@@ -399,7 +426,8 @@ class LargeGridRollout:
         self._fs3 = (C.c_float * 3)(*[1.0 / float(v) for v in (list(in_std_v if in_std_v is not None else std_v) + [std_re])])
         self._so = tuple(float(v) for v in (out_std_v if out_std_v is not None else std_v))
         self.any_width = bool(any_width)
-        self._sched = NetSchedule2D(net, B, Y, X, train=False, any_width=self.any_width)
+        self._sched = NetSchedule2D(net, B, Y, X, train=False, any_width=self.any_width, padding=self.conv_padding,
+                                    periodic=tuple(getattr(masks, "periodic", (False, False))))
         nd, ny, nx = B * Y * X, B * (Y + 1) * X, B * Y * (X + 1)
         z = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)
         views = lambda flat: (flat[:nd].view(B, Y, X), flat[nd:nd + ny].view(B, Y + 1, X), flat[nd + ny:].view(B, Y, X + 1))
@@ -500,9 +528,10 @@ class GraphTrainer(_AdamDP):
                  group=None, use_graph=True, comm=None, in_std_v=None, out_std_v=None, pressure_solver=None,
                  dx=None, dt=1.0, masks=None, cg_rtol=1e-6, cg_atol=1e-9, cg_max_iter=2000, grad_pad="replicate",
                  inflow_order="after", conv_precision="split", schedule="manual", obstacles=None, active=None,
-                 buoyancy=None, diffusion_substeps=1, advection="semi_lagrangian", correction_strength=1.0, boundaries=None):
+                 buoyancy=None, diffusion_substeps=1, advection="semi_lagrangian", correction_strength=1.0, boundaries=None,
+                 conv_padding="zeros"):
         """boundaries: "open" | "periodic" | (by, bx) (ops.boundaries_arg); None = those of `masks`, open without masks.  Periodic
-        boundaries are LargeGridTrainer's (this class refuses them).
+        boundaries are LargeGridTrainer's (this class refuses them), and so is conv_padding="circular".
         dx: cell size (default 100 / X, the reference's `--len 100`); the domain is box[0:Y*dx, 0:X*dx] as the scripts
         build it (karman_train.py:363: box[0:len*2, 0:len]).  obstacles / active: the scene of KarmanFlow (default: the reference's
         sphere).  masks: optional SceneMasks of the caller -- its boundary arrays are used; its scene must be the one KarmanFlow
@@ -520,6 +549,8 @@ class GraphTrainer(_AdamDP):
                              % (boundaries, ops.boundaries_name(getattr(masks, "periodic", (False, False)))))
         self._periodic_bits = ops.periodic_bits(periodic)
         self._check_boundaries(periodic, pressure_solver)
+        self._periodic = (bool(periodic[0]), bool(periodic[1]))
+        self.conv_padding = self._check_conv_padding(conv_padding, self._periodic)
         ph = self.physics = self._check_physics(Y, X, buoyancy=buoyancy, diffusion_substeps=diffusion_substeps, advection=advection,
                                                 correction_strength=correction_strength)
         self.buoyancy, self.diffusion_substeps, self.advection = ph.buoyancy, ph.nsub, ph.advection_kw
@@ -568,6 +599,10 @@ class GraphTrainer(_AdamDP):
 
     def _check_boundaries(self, periodic, pressure_solver):
         _refuse_periodic("GraphTrainer", types.SimpleNamespace(periodic_bits=ops.periodic_bits(periodic), periodic=periodic), "LargeGridTrainer")
+
+    @staticmethod
+    def _check_conv_padding(conv_padding, periodic):
+        return _conv_padding_arg("GraphTrainer", conv_padding, use="LargeGridTrainer")
 
     @staticmethod
     def _check_physics(Y, X, buoyancy, diffusion_substeps, advection, correction_strength):
@@ -640,7 +675,7 @@ class GraphTrainer(_AdamDP):
         """Once, on the first run of the schedule: the network's launches, the scene's device masks, the solver configuration"""
         from .schedule2d import NetSchedule2D
         B, Y, X = self.B, self.Y, self.X
-        self._sched = NetSchedule2D(self.net, B, Y, X, any_width=self._any_width)
+        self._sched = NetSchedule2D(self.net, B, Y, X, any_width=self._any_width, padding=self.conv_padding, periodic=self._periodic)
         self._mk = self.sim._masks(self.dom, self.bcv, self.bcm, self.device)
         self._kcfg = ops.karman_cfg(B, Y, X, self.dom.dx[1], dt=self.dt, res=self.res, masks=self._mk, **self.sim._solver)
         self._fs = [1.0 / float(v) for v in self._scale_in_host]
@@ -746,7 +781,13 @@ class LargeGridTrainer(GraphTrainer):
         here, so a captured step allocates nothing.  With a force _solver_fwd also keeps each step's input density and _solver_bwd =
         ops.karman_step_large_bwd_buoy (the buoyant velocity adjoint, then the density adjoint) carries g_d_in to the next (earlier)
         step as that step's g_d_out.  The loss looks at the velocity only, so the last step's g_d_out is zero; the carried gradient is
-        reset at the head of every run, so a replayed graph is self-contained."""
+        reset at the head of every run, so a replayed graph is self-contained.
+        conv_padding="circular" (keyword; periodic boundaries only): the network's convolutions pad circularly along the periodic axes
+        -- forward, backward-data and weight gradient (NetSchedule2D(padding="circular"): halo buffers refreshed by sol_conv_halo,
+        captured with the rest); any width X is served.  "zeros" (the default) is the reference's padding='same': the corrector then
+        sees a wall at the seam, and every existing run keeps its bits."""
+        # (before the base constructor: _check_grid reads it; the base constructor checks it against the boundaries)
+        self._circular = _conv_padding_arg("LargeGridTrainer", kw.get("conv_padding", "zeros"), (True, True)) == "circular"
         if any_width and kw.get("schedule", "manual") == "autograd":
             raise ValueError("LargeGridTrainer: any_width=True runs the hand-written schedule only; schedule='autograd' (the composition "
                              "over ops.conv5x5) takes no pitched rows")
@@ -762,7 +803,7 @@ class LargeGridTrainer(GraphTrainer):
         if not ops.beyond_one_workgroup(Y, X) and not self.multi_launch:
             raise ValueError("LargeGridTrainer: a %dx%d domain is served by the one-workgroup trainers -- use SolTrainer (mars_moon) or "
                              "GraphTrainer (make_trainer picks); multi_launch=True runs this trainer on it" % (Y, X))
-        if not _width_served(Y, X, self._any_width, self.multi_launch):
+        if not _width_served(Y, X, self._any_width or self._circular, self.multi_launch):
             raise ValueError("LargeGridTrainer: the convolutions of a large domain take rows of X %% 64 == 0 cells (got %dx%d)" % (Y, X))
 
     _adjoint_of_first_step = False
@@ -771,6 +812,10 @@ class LargeGridTrainer(GraphTrainer):
         """periodic boundaries: served (the seam sync / fold in the schedule); without a CG solve"""
         if any(periodic) and pressure_solver == "cg":
             raise ValueError("LargeGridTrainer: pressure_solver='cg' is not built for periodic boundaries; use 'auto', 'direct' or 'direct_scattered'")
+
+    @staticmethod
+    def _check_conv_padding(conv_padding, periodic):
+        return _conv_padding_arg("LargeGridTrainer", conv_padding, periodic)
 
     @staticmethod
     def _check_physics(Y, X, **keywords):
