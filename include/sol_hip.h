@@ -1265,6 +1265,31 @@ int sol_conv3d_bwd_weight_acc(void* stream, const float* x, const float* dz, con
                               int32_t B, int32_t D, int32_t H, int32_t W, int32_t cin, int32_t cout, int32_t cin_real, int32_t cout_real,
                               int32_t accumulate_partial, int32_t do_reduce);
 
+/* CIRCULAR PADDING, KARMAN-3D (csrc/conv3d_circular.hip): circular z padding of the Conv3D network on a z-periodic scene.  The network's
+ * tensors are [B,Y,X,Z,C] with z as the pixel axis of a row, and a row of Z + 4 pixels has no legal width; so the network runs on the
+ * TRANSPOSED volume [B,Y,HB,X,C] -- depth y, image rows z, pixels x -- with every layer's kernel axes 1 and 2 swapped by the caller:
+ *   rows [2, 2 + Z)            the Z planes (row 2 + z = plane z, transposed);
+ *   rows 0, 1, Z + 2, Z + 3    the circular halo (row r = plane (r - 2) mod Z);
+ *   rows [Z + 4, HB)           pad rows: HB >= Z + 4 is Z + 4 rounded up to what the convolutions ask of a row count (a multiple of
+ *                              64 / X when X < 64).
+ * sol_conv3d / _thin / _thin_out / the weight gradients run at (B, D = Y, H = HB, W = X) as they are, zero padding beyond the buffer.
+ * What a launch writes into halo and pad rows is wrong and is replaced by sol_conv3d_halo before the next consumer; its valid rows are
+ * the circular convolution, because their stencils read rows [0, Z + 4) only: wrapped copies, never pad rows.  The absmax slots a launch
+ * publishes also cover its halo and pad rows before the refresh: an upper bound of the true maximum.
+ *   sol_conv3d_circ_pack    src [B,Y,X,Z,C] -> dst [B,Y,HB,X,C], C == 4: every (X, Z) plane transposed into rows [2, Z + 2); halo rows
+ *                           wrapped (mode 0) or zero (mode 1); pad rows zero.
+ *   sol_conv3d_circ_unpack  src [B,Y,HB,X,C] -> dst [B,Y,X,Z,C], C in {3, 4}: the inverse on rows [2, Z + 2).
+ *   sol_conv3d_halo         buf [planes = B Y, HB, X, C] in place, C in {4, 32}: mode 0 -- halo rows = the wrapped valid rows, pad rows = 0
+ *                           (every activation; a dz before its backward-data convolution: the adjoint of a circular convolution is the
+ *                           circular correlation); mode 1 -- halo and pad rows = 0 (a dz before its weight gradient: only valid rows
+ *                           contribute to dw and db).  Valid rows are never written.
+ * Each is ONE launch through an LDS tile (pack, unpack: both global sides contiguous) or a plain copy (halo), vector stores, no atomics,
+ * no host synchronisation: capturable.  Every element of dst (pack, unpack) is written.  SOL_ERR_ARG with a message: NULL buffer, B, Y,
+ * planes, X < 1, Z < 2, HB < Z + 4, a C or mode it does not take, more than 2^31 pixels. */
+int sol_conv3d_circ_pack(void* stream, const float* src, float* dst, int32_t B, int32_t Y, int32_t X, int32_t Z, int32_t HB, int32_t C, int32_t mode);
+int sol_conv3d_circ_unpack(void* stream, const float* src, float* dst, int32_t B, int32_t Y, int32_t X, int32_t Z, int32_t HB, int32_t C);
+int sol_conv3d_halo(void* stream, float* buf, int32_t planes, int32_t Z, int32_t HB, int32_t X, int32_t C, int32_t mode);
+
 /* offsets (in floats) of layer l's kernel / bias inside the flat mars_moon parameter
  * vector; l in [0,12).  cin/cout may be NULL.                                            */
 int sol_mars_moon_layer(int32_t l, int64_t* kernel_off, int64_t* bias_off, int32_t* cin, int32_t* cout);

@@ -10,7 +10,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 DEFAULT_LIB = os.path.join(LIBDIR, "libsol_hip.so")
 LIB = os.environ.get("SOL_HIP_LIB") or DEFAULT_LIB      # SOL_HIP_LIB: an explicitly named PREBUILT variant (tools/ab_lib.py); never built, never stamped
-SOURCES = ["karman_step.hip", "karman_step_small.hip", "karman_large.hip", "karman_solve_small.hip", "karman_large_bwd.hip", "karman_periodic.hip", "karman_density_bwd.hip", "karman_buoyancy.hip", "karman_diffuse_sub.hip", "karman_maccormack.hip", "karman_re_bwd.hip", "karman3d.hip", "karman3d_density_bwd.hip", "karman3d_re_bwd.hip", "karman3d_buoyancy.hip", "karman3d_diffuse_sub.hip", "karman3d_maccormack.hip", "karman3d_periodic.hip", "pcg.hip", "conv3d_sb.hip", "burgers_step.hip", "conv5x5.hip", "conv5x5_sb.hip", "conv5x5_dx.hip", "conv5x5_thin.hip", "conv_halo.hip", "train.hip", "comm.hip", "cnn_chain.hip"]
+SOURCES = ["karman_step.hip", "karman_step_small.hip", "karman_large.hip", "karman_solve_small.hip", "karman_large_bwd.hip", "karman_periodic.hip", "karman_density_bwd.hip", "karman_buoyancy.hip", "karman_diffuse_sub.hip", "karman_maccormack.hip", "karman_re_bwd.hip", "karman3d.hip", "karman3d_density_bwd.hip", "karman3d_re_bwd.hip", "karman3d_buoyancy.hip", "karman3d_diffuse_sub.hip", "karman3d_maccormack.hip", "karman3d_periodic.hip", "pcg.hip", "conv3d_sb.hip", "burgers_step.hip", "conv5x5.hip", "conv5x5_sb.hip", "conv5x5_dx.hip", "conv5x5_thin.hip", "conv_halo.hip", "conv3d_circular.hip", "train.hip", "comm.hip", "cnn_chain.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics"]
 # the CG loop packs its vector updates by hand (float2); the SLP vectoriser only adds v_mov traffic there
 # conv3d_sb.hip: packed-f32 VALU (v_pk_mul/fma_f32, what SLP makes of the fp16 split of the row staging) costs ~22 cycles each

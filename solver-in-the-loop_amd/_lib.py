@@ -130,6 +130,9 @@ _SIGS = {
     "sol_conv5x5_scaled": (C.c_int, [_P] * 7 + [C.c_int32] * 6 + [C.c_float] + [_P] * 2),
     "sol_conv5x5_cols": (C.c_int, [_P] * 7 + [C.c_int32] * 7 + [C.c_float] + [_P] * 2),
     "sol_conv_halo": (C.c_int, [_P, _P] + [C.c_int32] * 7),
+    "sol_conv3d_circ_pack": (C.c_int, [_P, _P, _P] + [C.c_int32] * 7),
+    "sol_conv3d_circ_unpack": (C.c_int, [_P, _P, _P] + [C.c_int32] * 6),
+    "sol_conv3d_halo": (C.c_int, [_P, _P] + [C.c_int32] * 6),
     "sol_conv5x5_bwd_weight_ws_floats": (C.c_size_t, [C.c_int32] * 5),
     "sol_conv5x5_bwd_weight": (C.c_int, [_P] * 4 + [C.c_int32] * 5),
     "sol_conv5x5_bwd_weight_reduce": (C.c_int, [_P] * 4 + [C.c_int32] * 6),

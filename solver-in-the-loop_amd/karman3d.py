@@ -807,6 +807,43 @@ def net3d_shape_reason(Y, X, Z, train=True):
     return None
 
 
+def circular_rows3d(X, Z):
+    """HB, the row count of the circular network's buffers [B, Y, HB, X, C]: the Z planes and two halo rows on either side, rounded up to
+    a multiple of the 64 / X rows that share a tile when X < 64 (check_shape of csrc/conv5x5.hip: H % (64 / W) == 0)"""
+    q = 64 // int(X) if int(X) < 64 else 1
+    return -(-(int(Z) + 4) // q) * q
+
+
+def net3d_circular_shape_reason(Y, X, Z, train=True):
+    """net3d_shape_reason for the network with circular z padding (conv_padding="circular"): it runs on the transposed volume -- depth y,
+    image rows z (Z + 4 of them with the halo, padded up to circular_rows3d(X, Z)), pixels x --, so X takes the pixel rule and Z is free."""
+    Y, X, Z = int(Y), int(X), int(Z)
+    if Y < 3 or Z < 2:
+        return "Y = %d, Z = %d: the circular 5 x 5 x 5 convolutions need Y >= 3 planes and Z >= 2 periodic planes" % (Y, Z)
+    if X < 4 or not ((X <= 64 and 64 % X == 0) or X % 64 == 0):
+        return ("X = %d: with circular z padding x is the pixel axis of a row, which must be 4, 8, 16, 32 or 64 pixels long, or a multiple "
+                "of 64" % X)
+    if train and X > 64:
+        return ("X = %d: the weight gradients of the reverse sweep take rows up to 64 pixels, with circular z padding X <= 64; "
+                "a roll-out (Karman3DRollout, NetSchedule3D(train=False)) runs at this width" % X)
+    return None
+
+
+def conv_padding_arg3d(conv_padding, scene, who, train=True):
+    """the conv_padding keyword of Karman3DTrainer / Karman3DRollout, checked by name before any device call: "zeros" or "circular", the
+    latter on a z-periodic scene whose grid net3d_circular_shape_reason takes"""
+    if conv_padding not in ("zeros", "circular"):
+        raise _lib.SolError("%s: conv_padding must be 'zeros' or 'circular' (got %r)" % (who, conv_padding))
+    if conv_padding == "circular":
+        if not scene.periodic_bits:
+            raise _lib.SolError("%s: conv_padding='circular' needs a z-periodic scene (Scene3D(boundaries='periodic-z')); this scene's "
+                                "boundaries are open" % who)
+        why = net3d_circular_shape_reason(scene.Y, scene.X, scene.Z, train)
+        if why is not None:
+            raise _lib.SolError("%s: conv_padding='circular' at %d x %d x %d: %s" % (who, scene.Y, scene.X, scene.Z, why))
+    return conv_padding
+
+
 class MarsMoon3D:
     """12 Conv3D(5, padding='same') layers, 32 features, five residual blocks (karman_train.py:101-138 in 3-D): 4 -> 32,
     10 x 32 -> 32, 32 -> 3; 1 308 355 parameters in ONE flat fp32 buffer in Keras get_weights() order (kernels DHWIO).
@@ -847,23 +884,34 @@ class MarsMoon3D:
         itself; in-place torch ops on `params` bump `_version` and need nothing."""
         self._generation += 1
 
-    def schedule(self, B, Y, X, Z):
+    def schedule(self, B, Y, X, Z, padding="zeros"):
         """the training schedule (launch sequence, packed weights, weight-gradient partials) of this network at one shape, built once
-        (it refers back to the net weakly: no reference cycle, the buffers go with the net)"""
+        (it refers back to the net weakly: no reference cycle, the buffers go with the net).  padding="circular": the schedule with
+        circular z padding, kept beside the zero-padded one of the same shape"""
         from .schedule3d import NetSchedule3D
-        key = (int(B), int(Y), int(X), int(Z))
+        shape = (int(B), int(Y), int(X), int(Z))
+        key = shape if padding == "zeros" else shape + (padding,)
         if key not in self._schedules:
-            self._schedules[key] = NetSchedule3D(weakref.proxy(self), *key)
+            self._schedules[key] = NetSchedule3D(weakref.proxy(self), *shape, padding=padding)
         return self._schedules[key]
 
     fused_backward = True      # one autograd node with a hand-written reverse sweep (False: one node per layer, torch glue)
 
-    def __call__(self, x):
+    def __call__(self, x, padding="zeros"):
         """Differentiable forward (training): x [B,Y,X,Z,4] -> [B,Y,X,Z,cout]; gradients flow to self.params (set
-        `net.params.requires_grad_(True)`) and to x."""
+        `net.params.requires_grad_(True)`) and to x.  padding="circular": the convolutions wrap along z (a z-periodic scene)."""
         if self.fused_backward:
-            return _MarsMoon3DFn.apply(x, self.params, self)
+            return _MarsMoon3DFn.apply(x, self.params, self, padding)
         p = self.tensors()
+        if padding != "zeros":
+            if padding != "circular":
+                raise _lib.SolError("MarsMoon3D: padding must be 'zeros' or 'circular' (got %r)" % (padding,))
+            lr = lambda t: torch.nn.functional.leaky_relu(t, self.slope)
+            h = lr(conv3d_circular(x, p[0], p[1]))
+            for k in range(5):
+                a = lr(conv3d_circular(h, p[2 + 4 * k], p[3 + 4 * k]))
+                h = lr(conv3d_circular(a, p[4 + 4 * k], p[5 + 4 * k]) + h)
+            return conv3d_circular(h, p[22], p[23])
         pk = self.schedule(*x.shape[:4]).layer_packs()
         sl = self.slope
         h = conv3d_fn(x, p[0], p[1], None, True, sl, pk[0])
@@ -1112,8 +1160,8 @@ class _MarsMoon3DFn(torch.autograd.Function):
     launches and its hand-written reverse sweep, the weight gradients of this one call reduced at once."""
 
     @staticmethod
-    def forward(ctx, x, params, net):
-        ctx.net, ctx.sch = net, net.schedule(*x.shape[:4])
+    def forward(ctx, x, params, net, padding="zeros"):
+        ctx.net, ctx.sch = net, net.schedule(*x.shape[:4], padding=padding)
         out, (xk, amax, acts) = ctx.sch.forward(x)
         ctx.save_for_backward(xk, amax, *acts)
         return out
@@ -1122,12 +1170,59 @@ class _MarsMoon3DFn(torch.autograd.Function):
     def backward(ctx, g_out):
         xk, amax, *acts = ctx.saved_tensors
         dx, flat = ctx.sch.backward((xk, amax, acts), g_out)
-        return dx[..., :ctx.net.cin], flat, None
+        return dx[..., :ctx.net.cin], flat, None, None
 
 
 def conv3d_fn(x, w, b, residual=None, lrelu=False, slope=0.3, packs=None):
     """packs: optional (forward-packed, backward-data-packed) weight buffers of this layer (NetSchedule3D.layer_packs)."""
     return _Conv3DFn.apply(x, w, b, residual, lrelu, slope, packs)
+
+
+class _CircWrap3DFn(torch.autograd.Function):
+    """x [B,Y,X,Z,C] -> the halo buffer [B,Y,HB,X,C] of the circular network (include/sol_hip.h, "CIRCULAR PADDING, KARMAN-3D"): planes
+    transposed into rows [2, Z + 2), halo rows wrapped, pad rows zero.  C = 4: sol_conv3d_circ_pack; C = 32: a torch transpose and
+    sol_conv3d_halo.  backward: the adjoint, every halo row folded onto the plane it copied."""
+
+    @staticmethod
+    def forward(ctx, x):
+        _lib.require_gpu()
+        lib = _lib.load()
+        B, Y, X, Z, c = x.shape
+        assert c in (4, 32), "the halo buffers hold 4 or 32 channels"
+        HB = circular_rows3d(X, Z)
+        ctx.Z = Z
+        x = _lib.f32(x).contiguous()
+        buf = torch.empty(B, Y, HB, X, c, dtype=torch.float32, device=x.device)
+        if c == 4:
+            check(lib.sol_conv3d_circ_pack(stream(), ptr(x), ptr(buf), B, Y, X, Z, HB, 4, 0))
+        else:
+            buf[:, :, 2:Z + 2] = x.permute(0, 1, 3, 2, 4)
+            check(lib.sol_conv3d_halo(stream(), ptr(buf), B * Y, Z, HB, X, c, 0))
+        return buf
+
+    @staticmethod
+    def backward(ctx, g):
+        Z = ctx.Z
+        gx = g[:, :, 2:Z + 2].clone()
+        for r in (0, 1, Z + 2, Z + 3):
+            gx[:, :, (r - 2) % Z] += g[:, :, r]
+        return gx.permute(0, 1, 3, 2, 4).contiguous()
+
+
+def conv3d_circular(x, w, b):
+    """y [B,Y,X,Z,cout] = conv3d(x [B,Y,X,Z,cin], w [5,5,5,cin,cout] (Keras k_y, k_x, k_z, in, out)) + b with CIRCULAR padding along z and
+    zero padding along y and x: one differentiable linear layer, the cross-check of NetSchedule3D(padding="circular").  The layer wraps x
+    into the halo buffer, runs conv3d_fn there with kernel axes 1 and 2 swapped and crops the valid rows; autograd composes the adjoint
+    (zero cotangent in halo rows -> weight gradient over valid rows; the data gradient's halo rows folded back by the wrap's adjoint)."""
+    B, Y, X, Z, cin = x.shape
+    why = net3d_circular_shape_reason(Y, X, Z, train=X <= 64)
+    if why is not None:
+        raise _lib.SolError("conv3d_circular at %d x %d x %d: %s" % (Y, X, Z, why))
+    ck = 4 if cin <= 4 else 32
+    xb = _CircWrap3DFn.apply(x if cin == ck else torch.nn.functional.pad(x, (0, ck - cin)))
+    wk = w if cin == ck else torch.nn.functional.pad(w, (0, 0, 0, ck - cin))
+    yb = conv3d_fn(xb, wk.permute(0, 2, 1, 3, 4), b)
+    return yb[:, :, 2:Z + 2].permute(0, 1, 3, 2, 4).contiguous()
 
 
 def ops_l2_loss(pred, gt, std):
@@ -1146,7 +1241,7 @@ class Karman3DTrainer:
 
     def __init__(self, net, scene, B, msteps, std_v, std_re, dt=1.0, res=None, beta1=0.9, beta2=0.999, eps=1e-8, conv_precision="split",
                  use_graph=False, group=None, comm=None, schedule="manual", glue="fused", buoyancy=None, diffusion_substeps=1,
-                 advection="semi_lagrangian", correction_strength=1.0, **solver):
+                 advection="semi_lagrangian", correction_strength=1.0, conv_padding="zeros", **solver):
         """schedule: "manual" (default) = the hand-written forward unroll + reverse sweep over the C ABI (_unrolled_schedule), "autograd" = the
         torch-autograd composition of the differentiable HIP ops (rounds 3-4; kept as the cross-check).
         use_graph: capture the whole forward unroll + reverse sweep ONCE into a hipGraph over static input buffers (the
@@ -1157,17 +1252,21 @@ class Karman3DTrainer:
         cotangent is carried to the next (earlier) step (None at the last step: the loss does not look at the density).  Kernel launches
         only, the pre-diffusion's ping-pong buffers are the simulator's static ones: use_graph stays a graph of kernel nodes.
         advection="mac_cormack", correction_strength=s: the simulator's scheme (self.sim.adv); both schedules hand it to the solver pair.  The
-        MacCormack launches work in the simulator's workspace, sized at construction: kernel nodes only, as before."""
+        MacCormack launches work in the simulator's workspace, sized at construction: kernel nodes only, as before.
+        conv_padding="circular" (a z-periodic scene): the correction network pads circularly along z in the forward pass, the backward-data
+        pass and the weight gradient (NetSchedule3D(padding="circular")), under both schedules, eager and captured; X then takes the
+        pixel rule and Z is free (net3d_circular_shape_reason).  Kept as self.conv_padding."""
         from .trainer import _conv_precision_code
         from .dist import DPStep
         from .ops import advection_arg
         advection_arg(advection, correction_strength, "Karman3DTrainer: advection")       # (refused before the device is asked for)
+        self.conv_padding = conv_padding_arg3d(conv_padding, scene, "Karman3DTrainer")     # (likewise)
         _lib.require_gpu()
         self.lib = _lib.load()
         self.net, self.scene, self.B, self.ms = net, scene, B, msteps
         # the network's launches, packed weights and weight-gradient partials at this shape -- first: a grid the network does not take
         # (net3d_shape_reason) is refused here, before a simulator or a buffer exists
-        self.sch = net.schedule(B, scene.Y, scene.X, scene.Z)
+        self.sch = net.schedule(B, scene.Y, scene.X, scene.Z, padding=self.conv_padding)
         assert glue in ("fused", "torch")
         self.glue = glue          # reverse-sweep glue of the manual schedule: sol_karman3d_correct_bwd / _feature_bwd, or the torch elementwise composition
         self.sim = Karman3DFlow(scene, B, dt=dt, res=res, buoyancy=buoyancy, diffusion_substeps=diffusion_substeps, advection=advection,
@@ -1294,7 +1393,7 @@ class Karman3DTrainer:
         losses = []
         for i in range(self.ms):
             d, *v = self.sim.step(d, v[0], v[1], v[2], re)
-            out = self.net(to_feature3d(v[0], v[1], v[2], re) / self.std_in) * self.std_v
+            out = self.net(to_feature3d(v[0], v[1], v[2], re) / self.std_in, padding=self.conv_padding) * self.std_v
             v = tuple(a + c for a, c in zip(v, to_staggered3d(out)))
             if self.scene.periodic_bits:
                 v = (v[0], v[1], _SeamSync3DFn.apply(v[2], self.scene))
@@ -1363,18 +1462,21 @@ class Karman3DRollout:
     nsub = property(lambda self: self.sim.physics.nsub)
 
     def __init__(self, net, scene, B, std_v, std_re, dt=1.0, res=None, conv_precision="split", buoyancy=None, diffusion_substeps=1,
-                 advection="semi_lagrangian", correction_strength=1.0, **solver):
+                 advection="semi_lagrangian", correction_strength=1.0, conv_padding="zeros", **solver):
         """buoyancy=(fy, fx, fz), diffusion_substeps=n: the StepPhysics3D of the simulator (self.sim.physics); the features keep the true re.
-        advection="mac_cormack", correction_strength=s: the simulator's scheme (self.sim.adv)"""
+        advection="mac_cormack", correction_strength=s: the simulator's scheme (self.sim.adv)
+        conv_padding="circular" (a z-periodic scene): the network pads circularly along z; X takes the pixel rule (a multiple of 64 runs
+        here), Z is free.  Kept as self.conv_padding."""
         from .trainer import _conv_precision_code
         from .schedule3d import NetSchedule3D
         from .ops import advection_arg
         advection_arg(advection, correction_strength, "Karman3DRollout: advection")       # (refused before the device is asked for)
+        self.conv_padding = conv_padding_arg3d(conv_padding, scene, "Karman3DRollout", train=False)     # (likewise)
         _lib.require_gpu()
         self.lib = _lib.load()
         self.net, self.scene, self.B = net, scene, B
         # forward only, in its own persistent buffers -- first: a grid the network does not take (net3d_shape_reason) is refused here
-        self.sch = NetSchedule3D(net, B, scene.Y, scene.X, scene.Z, train=False)
+        self.sch = NetSchedule3D(net, B, scene.Y, scene.X, scene.Z, train=False, padding=self.conv_padding)
         self.sim = Karman3DFlow(scene, B, dt=dt, res=res, buoyancy=buoyancy, diffusion_substeps=diffusion_substeps, advection=advection,
                                 correction_strength=correction_strength, **solver)
         self.std_v = tuple(float(v) for v in std_v)

@@ -19,7 +19,9 @@ recorded in params.pickle and in the model file as "obstacle" and picked up from
 solves the cylinder's pressure without iteration (any mask that does not depend on z).
 --boundaries open|periodic-z: the spanwise axis periodic (Scene3D(boundaries=): the wake in a box periodic along the span), for generation,
 --model roll-out and --train-sol alike; recorded in params.pickle and in the model file as "boundaries" and picked up from there like the
-force.  With --obstacle cylinder it selects --pressure-solver direct_extruded unless another solver is named (auto names none)."""
+force.  With --obstacle cylinder it selects --pressure-solver direct_extruded unless another solver is named (auto names none).
+--conv-padding zeros|circular: the correction network's padding along z (--train-sol and the --model roll-out); circular needs
+--boundaries periodic-z; recorded in params.pickle and in the model file as "conv_padding" and picked up from there like the force."""
 import argparse
 import pickle
 
@@ -69,6 +71,9 @@ def parse_params(argv=None):
                         "(opt-in: the direct solve for a mask that does not depend on z, such as --obstacle cylinder)")
     p.add_argument("--boundaries", default=None, choices=BOUNDARIES, help="open, or periodic-z: the spanwise axis periodic; default: open, or what "
                    "the --model file recorded")
+    p.add_argument("--conv-padding", default=None, choices=("zeros", "circular"), help="padding of the correction network along z (--train-sol and "
+                   "the --model roll-out): zeros (Conv3D's 'same'), or circular on --boundaries periodic-z; default: zeros, or what the --model "
+                   "file recorded")
     add_buoyancy_arg(p, ncomp=3)
     add_substeps_arg(p, bound="1/6")
     add_advection_arg(p, where="")
@@ -98,6 +103,14 @@ def apply_model_record(params, record=None):
             raise SystemExit("--boundaries %s contradicts the boundaries recorded in %s (%s)" % (params["boundaries"], params["model"], record["boundaries"]))
         params["boundaries"] = record["boundaries"]
     params["boundaries"] = params.get("boundaries") or "open"
+    if record is not None and "conv_padding" in record:
+        if params.get("conv_padding") is not None and params["conv_padding"] != record["conv_padding"]:
+            raise SystemExit("--conv-padding %s contradicts the padding recorded in %s (%s)" % (params["conv_padding"], params["model"], record["conv_padding"]))
+        params["conv_padding"] = record["conv_padding"]
+    params["conv_padding"] = params.get("conv_padding") or "zeros"
+    if params["conv_padding"] == "circular" and params["boundaries"] != "periodic-z":
+        raise SystemExit("--conv-padding circular pads the correction network circularly along z and needs --boundaries periodic-z "
+                         "(the boundaries are %s)" % params["boundaries"])
     if params["boundaries"] == "periodic-z" and params["obstacle"] == "cylinder" and not params.get("obstacle_mask") and params.get("pressure_solver", "auto") == "auto":
         params["pressure_solver"] = "direct_extruded"       # (the dense periodic blob refuses an obstacle that spans the axis on all but small grids)
     if record is not None and "buoyancy" in record:
@@ -120,7 +133,8 @@ def main(argv=None):
     res = params["res"]
     Y, X, Z = 2 * res, res, res
     if blob is not None or params["train_sol"]:       # a grid the corrector does not take: say so before a device is asked for or a frame generated
-        why = k3.net3d_shape_reason(Y, X, Z, train=bool(params["train_sol"]))
+        reason = k3.net3d_circular_shape_reason if params["conv_padding"] == "circular" else k3.net3d_shape_reason
+        why = reason(Y, X, Z, train=bool(params["train_sol"]))
         if why is not None:
             raise SystemExit("karman3d.py: the correction network does not run at %d x %d x %d -- %s" % (Y, X, Z, why))
     select_gpu(params["gpu"])
@@ -155,6 +169,7 @@ def main(argv=None):
     log.info("pressure solver: %s%s" % (sc.pressure_solver, hint))
     log.info("obstacle: %s" % (params["obstacle_mask"] or params["obstacle"]))
     log.info("boundaries: %s" % params["boundaries"])
+    log.info("conv padding: %s" % params["conv_padding"])
     log.info("buoyancy: %s" % (buoyancy,))
     log.info("diffusion substeps: %d" % nsub)
     log.info("advection: %s (correction strength %g)" % (adv["advection"], adv["correction_strength"]))
@@ -162,7 +177,8 @@ def main(argv=None):
     if blob is not None:
         net = k3.MarsMoon3D(device=dev)
         net.set_weights([w.numpy() for w in blob["weights"]])
-        ro = k3.Karman3DRollout(net, sc, 1, blob["std_v"], blob["std_re"], buoyancy=buoyancy, diffusion_substeps=nsub, **adv)
+        ro = k3.Karman3DRollout(net, sc, 1, blob["std_v"], blob["std_re"], buoyancy=buoyancy, diffusion_substeps=nsub,
+                                conv_padding=params["conv_padding"], **adv)
     frames = []
     with torch.no_grad():
         for i in range(1, params["simsteps"]):
@@ -184,7 +200,8 @@ def main(argv=None):
         w = net.get_weights()
         w[22] = w[22] * 0.01
         net.set_weights(w)
-        tr = k3.Karman3DTrainer(net, sc, 1, ms, std_v, max(params["re"], 1.0), use_graph=True, buoyancy=buoyancy, diffusion_substeps=nsub, **adv)
+        tr = k3.Karman3DTrainer(net, sc, 1, ms, std_v, max(params["re"], 1.0), use_graph=True, buoyancy=buoyancy, diffusion_substeps=nsub,
+                                conv_padding=params["conv_padding"], **adv)
         rng = np.random.default_rng(params["seed"])
         for it in range(params["train_steps"]):
             k = int(rng.integers(0, len(frames) - ms))
@@ -193,7 +210,8 @@ def main(argv=None):
             log.info("train step {:04d}: loss={}".format(it + 1, loss))
         if path:
             torch.save({"name": net.name, "weights": [torch.as_tensor(a) for a in net.get_weights()], "std_v": std_v,
-                        "std_re": max(params["re"], 1.0), "buoyancy": buoyancy, "diffusion_substeps": nsub, "obstacle": params["obstacle"], "boundaries": params["boundaries"], **adv}, path + "/model3d.pt")
+                        "std_re": max(params["re"], 1.0), "buoyancy": buoyancy, "diffusion_substeps": nsub, "obstacle": params["obstacle"], "boundaries": params["boundaries"],
+                        "conv_padding": params["conv_padding"], **adv}, path + "/model3d.pt")
     return path if path else loss
 
 
